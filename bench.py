@@ -30,6 +30,13 @@ torch.distributed.run the other ranks only join the barriers around the timed re
 devices are usable.
 
 Rank 0 prints ONE JSON line (README / DESIGN.md §5 describe the fields).
+
+A plain run sets up, warms up, times the steps and prints the line.  --full adds the records
+beside the headline: the CPU baseline (the oracle on the host's cores), config 3's
+list on one GPU beside config 2, and at N>1 the check against one session with its timing,
+the weak and stream records beside the strong headline, and the one-rank-per-GPU form's
+check of every share against the whole list.  --dump-outputs DIR writes what the last timed
+step handed its caller (dump_outputs below).
 """
 import argparse
 import ctypes as C
@@ -243,6 +250,44 @@ def result_key(r):
     return (r.count, r.left_fuz, r.right_fuz, r.flags, r.draws, r.fill, tuple(r.substats), r.phaseC_count, tuple(r.lengths))
 
 
+DUMP_FIELDS = ("count", "left_fuz", "right_fuz", "flags", "fill_len", "draws", "vertices", "edges", "nontrivial_components",
+               "size_nontrivial_components", "vertices_final", "edges_final", "phaseC_count", "n_lengths", "backtrace_depth",
+               "backtrace_final_d")
+DUMP_BUDGET = 64 << 20  # bytes of .npy data in all
+
+
+def dump_outputs(results, outdir):
+    """--dump-outputs: the g2s_result records and fill text of one step as outdir/<name>.npy, gap by gap in list order:
+    every scalar field of the record (float64, one value per gap; fill_off is left out: it is where the text sits in the
+    caller's arena, not a result), `lengths` (float64, gaps x 2), `fill_text` (float32 ASCII codes of the gaps' fills
+    one after another, fill_len each; lower case marks unsafe bases) and `gap_index` (float64: which gaps of the list
+    the other arrays hold).  All gaps when they fit DUMP_BUDGET, else the gaps of a fixed seeded permutation of the list
+    taken in its order while they fit, written in list order."""
+    import numpy as np
+    n = len(results)
+    per_gap = lambda r: 8 * (len(DUMP_FIELDS) + 3) + 4 * len(r.fill)  # noqa: E731
+    if sum(per_gap(r) for r in results) <= DUMP_BUDGET:
+        keep = list(range(n))
+    else:
+        keep, used = [], 0
+        for i in np.random.default_rng(20240107).permutation(n).tolist():
+            used += per_gap(results[i])
+            if used > DUMP_BUDGET:
+                break
+            keep.append(i)
+        keep.sort()
+    sel = [results[i] for i in keep]
+    os.makedirs(outdir, exist_ok=True)
+    arrays = {"gap_index": np.array(keep, dtype=np.float64)}
+    for name in DUMP_FIELDS:
+        arrays[name] = np.array([getattr(r, name) for r in sel], dtype=np.float64)
+    arrays["lengths"] = np.array([(r.lengths + [0, 0])[:2] for r in sel], dtype=np.float64).reshape(len(sel), 2)
+    arrays["fill_text"] = np.frombuffer("".join(r.fill for r in sel).encode("ascii"), dtype=np.uint8).astype(np.float32)
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + ".npy"), a)
+    sys.stderr.write("bench.py: %d of %d gaps' results written to %s\n" % (len(keep), n, outdir))
+
+
 def run_rank_per_gpu(args, dist, rank, world, seen):
     """N ranks, one GPU each: rank r fills, traces and writes the r-th contiguous share of the list on the device it
     sees; the shares are placed in the one rand() stream by two all-gathers of host scalars (shard.fill_share).  The
@@ -287,15 +332,17 @@ def run_rank_per_gpu(args, dist, rank, world, seen):
         draws = shard.fill_share(P, sess, comm, arr, n, res, ap_, nbytes)
         return time.perf_counter() - t, draws
 
-    # ---- the shares must give the one-GPU result, bit for bit: every rank fills the WHOLE list once on its own GPU
-    # (g2s_fill_batch, untimed) and compares its share with that
-    whole = Runner(P, [sess], gaps, 0, True)
-    whole.step()
-    want = [result_key(r) for r in whole.results()][lo:hi]
-    whole.free()
+    # ---- --full: the shares must give the one-GPU result, bit for bit: every rank fills the WHOLE list once on its own
+    # GPU (g2s_fill_batch, untimed) and compares its share with that
+    want = None
+    if args.full:
+        whole = Runner(P, [sess], gaps, 0, True)
+        whole.step()
+        want = [result_key(r) for r in whole.results()][lo:hi]
+        whole.free()
     _, draws = step()
     got = None if draws is None else [result_key(P.FillResult(res[i], abuf.raw)) for i in range(n)]
-    same = comm.all_gather([1 if got == want else 0, 1 if draws is not None else 0])
+    same = comm.all_gather([1 if want is None or got == want else 0, 1 if draws is not None else 0])
     if not all(x[1] for x in same):
         if rank == 0:
             sys.stderr.write("bench.py: one rank per GPU: a share could not be taken on its device (shares of %s gaps)\n" % [b - a for a, b in shard.share_bounds(len(gaps), world)])
@@ -349,7 +396,7 @@ def run_rank_per_gpu(args, dist, rank, world, seen):
                              kernel_ms_per_launch=round(kern, 4), kernel_ms_per_launch_by_rank=[round(x, 4) for x in kms], launches_per_step=float(world)),
             "cpu_baseline": None,
             "filled": sum(p[6] for p in per_rank),
-            "equals_one_gpu_result": True,
+            "equals_one_gpu_result": True if args.full else None,
             "list_draws": draws,
             "setup_s": {"graph_build_and_upload_per_rank": round(t_graph, 3)},
         }
@@ -406,7 +453,14 @@ def main():
     ap.add_argument("--dry-run", action="store_true",
                     help="testing only (CPU): the launch protocol — rendezvous, barriers, timing reduction, one JSON "
                          "line from rank 0 — without touching a device or measuring anything")
+    ap.add_argument("--full", action="store_true",
+                    help="also the CPU baseline, config 3's list beside config 2, and at N>1 the checks against one "
+                         "session with the records beside the headline (a plain run measures the headline only)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the results of the last timed step as DIR/<name>.npy (dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 0:
+        ap.error("--steps must not be negative (0 = the configuration's default)")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -430,6 +484,11 @@ def main():
         seen = shard.DistComm(dist).all_gather([P0.G2S.device_count()])
         per_rank = args.rank_per_gpu or (seen[0][0] < ngpu and not args.share_device)
         if per_rank:
+            if args.dump_outputs:
+                if rank == 0:
+                    sys.stderr.write("bench.py: --dump-outputs needs one process for all GPUs (each rank holds only its share)\n")
+                dist.destroy_process_group()
+                return 2
             if world != ngpu or min(x[0] for x in seen) < 1:
                 if rank == 0:
                     sys.stderr.write("bench.py: --gpus %d with %d rank(s) seeing %s gfx950 device(s): neither one process for all "
@@ -574,10 +633,12 @@ def main():
     res = run.results()
     filled = sum(1 for r in res if r.count > 0)
     q7 = sum(1 for r in res if r.flags & P.G2S_GAP_Q7)
+    if args.dump_outputs:
+        dump_outputs(res, args.dump_outputs)
 
-    # ---- N>1: the list sharded over N GPUs must give the one-GPU result, bit for bit ----------
+    # ---- --full, N>1: the list sharded over N GPUs must give the one-GPU result, bit for bit ----------
     one_gpu = None
-    if len(sessions) > 1:
+    if args.full and len(sessions) > 1:
         solo = make_sessions(devices[:1], 1)
         r1 = Runner(P, solo, gaps, 0, not args.pageable_buffers)
         r1.step()
@@ -593,9 +654,9 @@ def main():
         for s in solo:
             s.destroy()
 
-    # ---- N=1 on C2: config 3's list on this one GPU, beside the headline ----------------------
+    # ---- --full, N=1 on C2: config 3's list on this one GPU, beside the headline ----------------------
     c3_beside = None
-    if ngpu == 1 and cfg_name == "C2" and not custom and not args.no_c3_beside:
+    if args.full and ngpu == 1 and cfg_name == "C2" and not custom and not args.no_c3_beside:
         g3 = parse_gaps(P.G2S.synth_gaps(reads, k, args.fuz, 10000, min_len, max_len, GAP_SEED), args.fuz)
         r3 = Runner(P, sessions[:1], g3, 0, not args.pageable_buffers)
         for _ in range(5):  # (the first three calls on a list of another size grow the session's buffers)
@@ -681,12 +742,12 @@ def main():
         for s_ in solo:
             s_.destroy()
 
-    # ---- N>1, the default line: the driver passes no flags, and the strong headline (config 3's ONE list over N GPUs)
-    # is bound by its 1 250-gap shares at N = 8 — beside it, in the same line: WEAK scaling (the config's gap count per
-    # GPU in one list, each GPU a share of 10 000) and a STREAM of such lists (the rand() stream running on from list
-    # to list), each checked against one session and timed against it
+    # ---- --full, N>1: the strong headline (config 3's ONE list over N GPUs) is bound by its 1 250-gap shares at N = 8 —
+    # beside it, in the same line: WEAK scaling (the config's gap count per GPU in one list, each GPU a share of 10 000)
+    # and a STREAM of such lists (the rand() stream running on from list to list), each checked against one session and
+    # timed against it
     weak_beside = None
-    if len(sessions) > 1 and not custom and not args.weak and args.stream_lists < 2 and group != 0:
+    if args.full and len(sessions) > 1 and not custom and not args.weak and args.stream_lists < 2 and group != 0:
         gw = parse_gaps(P.G2S.synth_gaps(reads, k, args.fuz, ngaps * ngpu, min_len, max_len, GAP_SEED), args.fuz)
         gweak = shard.group_size(len(gw), len(sessions) if args.share_device else len(set(devices)), per_session=args.groups_per_session)
         rw = Runner(P, sessions, gw, gweak, not args.pageable_buffers)
@@ -722,11 +783,11 @@ def main():
         for s_ in solo:
             s_.destroy()
 
-    # ---- CPU baseline: the oracle (port of the reference algorithm) on the GPU box's host cores,
+    # ---- --full, CPU baseline: the oracle (port of the reference algorithm) on the host's cores,
     # N=1 only, on a bounded sample of the same gaps
     cpu = None
     octr = None
-    if ngpu == 1 and not args.no_cpu_baseline:
+    if args.full and ngpu == 1 and not args.no_cpu_baseline:
         import oracle_lib as O
         og = O.OracleGraph(seqs, k, 1)
         sample = gaps

@@ -488,7 +488,7 @@ def test_multi_rank_bench_path(product, tmp_path):
     s.close()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3",
-           "--warmup", "1", "--genome", "300000", "--gaps", "600", "--share-device", "--group", "300"]
+           "--warmup", "1", "--genome", "300000", "--gaps", "600", "--share-device", "--group", "300", "--full"]
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-2000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
@@ -515,11 +515,11 @@ def test_bench_refuses_more_gpus_than_there_are(product):
 
 
 def test_bench_one_gpu_line(product):
-    """bench.py's default shape on a small graph: the timed region is the whole ABI call, the
+    """bench.py --full's default shape on a small graph: the timed region is the whole ABI call, the
     JSON line carries roofline and cpu_baseline, and the workload label names what ran."""
     import sys
     res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--genome",
-                          "300000", "--gaps", "200"], capture_output=True, text=True, timeout=600)
+                          "300000", "--gaps", "200", "--full"], capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-2000:]
     out = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][0])
     assert out["n_gpus"] == 1 and out["config"]["config"] == "C2-custom" and "custom" in out["config"]["workload"]
@@ -529,6 +529,38 @@ def test_bench_one_gpu_line(product):
     assert out["cpu_baseline"]["kind"] == "port" and out["cpu_baseline"]["cores"] == 1
     assert out["roofline"]["units_counted_by"].startswith("oracle (counted in this run") and 0 < out["roofline"]["frac"] < 1
     assert out["filled"] >= 190
+
+
+def test_bench_plain_line_and_dumped_outputs(product, tmp_path):
+    """A plain bench.py run times exactly --steps steps and carries nothing that --full adds; --dump-outputs writes the
+    last timed step's records and fill text, which are what one call on a fresh session seeded 1 returns."""
+    import sys
+    import numpy as np
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "1", "--genome",
+                          "300000", "--gaps", "200", "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-2000:]
+    out = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][0])
+    assert out["steps"] == 4 and out["warmup"] == 1 and out["ms_per_step"] > 0
+    assert out["cpu_baseline"] is None and "c3_on_one_gpu" not in out
+    assert len(out["breakdown_ms_per_step"]["wall_inside_the_abi_call_each"]) == 4
+    d = {f[:-4]: np.load(str(tmp_path / f)) for f in os.listdir(str(tmp_path))}
+    assert all(a.dtype in (np.float32, np.float64) for a in d.values())
+    reads = product.G2S.synth_genome(300000, 3, 20240101)
+    seqs = [ln for ln in reads.splitlines() if not ln.startswith(">")]
+    gaps = _parse_scaffolds(product.G2S.synth_gaps(reads, 31, 10, 200, 200, 1000, 20240103))
+    pg = product.Graph.from_seqs(seqs, 31, 1)
+    sess = product.Session(pg, 0, d_err=500, randseed=1)
+    try:
+        sess.srand(1)
+        want = sess.fill_batch(_gaps(product, gaps))
+    finally:
+        sess.destroy()
+        pg.free()
+    assert d["gap_index"].tolist() == list(range(200))
+    assert d["count"].tolist() == [r.count for r in want] and out["filled"] == sum(1 for r in want if r.count > 0)
+    assert d["draws"].tolist() == [r.draws for r in want] and d["fill_len"].tolist() == [len(r.fill) for r in want]
+    assert d["lengths"].shape == (200, 2)
+    assert d["fill_text"].astype(np.uint8).tobytes().decode("ascii") == "".join(r.fill for r in want)
 
 
 def _result_tuple(r):

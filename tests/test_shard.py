@@ -131,7 +131,10 @@ def test_dist_comm_all_gather_two_ranks_gloo(tmp_path):
         "got = c.all_gather(mine)\n"
         "empty = c.all_gather([] if c.rank else [9])\n"
         "fixed = c.all_gather([7, c.rank], 5)\n"
-        "print(json.dumps({'rank': c.rank, 'got': got, 'empty': empty, 'fixed': fixed}))\n"
+        # (one write per rank, newline included: both ranks share the pipe, and a line written in pieces can be split by
+        # the other rank's)
+        "sys.stdout.write(json.dumps({'rank': c.rank, 'got': got, 'empty': empty, 'fixed': fixed}) + '\\n')\n"
+        "sys.stdout.flush()\n"
         "dist.destroy_process_group()\n" % ROOT)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), str(script)]

@@ -6,7 +6,7 @@ V=${1:-r05m}
 O=gpurun_out/$V
 rm -rf $O; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
-timeout 400 python bench.py > $O/bench.json 2> $O/bench.err < /dev/null
+timeout 400 python bench.py --full > $O/bench.json 2> $O/bench.err < /dev/null
 python tools/bsum.py C2-full < $O/bench.json
 for C in C2 C3 C5; do
   c=$(echo $C | tr A-Z a-z)

@@ -7,7 +7,7 @@ V=${1:-r06m}; RH=${2:-150}
 O=gpurun_out/$V
 rm -rf $O; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
-timeout 600 python bench.py > $O/bench.json 2> $O/bench.err < /dev/null
+timeout 600 python bench.py --full > $O/bench.json 2> $O/bench.err < /dev/null
 python tools/bsum.py C2-full < $O/bench.json
 # the driver's own command line, three times (20 timed steps: a noisier line than the default 200)
 for r in 1 2 3; do timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 < /dev/null | tee -a $O/driver_style.jsonl | python tools/bsum.py driver-style; done
@@ -72,7 +72,7 @@ import sys, json
 d = json.loads([l for l in sys.stdin if l.startswith(chr(123))][0])
 print('one rank per GPU, N=$N ranks on the one device: strong', d['value'], 'gaps/s', d['ms_per_step'], 'ms/step | kernel ms by rank', d['roofline']['kernel_ms_per_launch_by_rank'], '|', d['config']['parallelism'][:160])"
   done
-  timeout 600 python bench.py --gpus 2 --share-device --steps 10 --warmup 3 2>/dev/null | tail -1 | python -c "
+  timeout 600 python bench.py --gpus 2 --share-device --steps 10 --warmup 3 --full 2>/dev/null | tail -1 | python -c "
 import sys, json
 d = json.loads(sys.stdin.read()); print('the default N=2 line (sessions on the one device): strong', d['value'], d['ms_per_step'], '| beside it:', json.dumps(d.get('weak_and_stream_beside'))[:900])"
 } | tee $O/shared.txt
