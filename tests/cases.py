@@ -98,6 +98,138 @@ def cut_gaps(seed, genome, k, fuz, ngaps, min_len, max_len, d_err, vary_fuz=True
     return out
 
 
+def clean_haplotypes(seqs, k):
+    """True when no k-mer is its own reverse complement, no k-mer meets its reverse strand anywhere in the
+    haplotypes and no haplotype holds a k-mer twice: what several haplotypes share is the same oriented k-mer."""
+    comp = str.maketrans("ACGT", "TGCA")
+    seen = {}
+    for h, s in enumerate(seqs):
+        for i in range(len(s) - k + 1):
+            x = s[i:i + k]
+            y = x.translate(comp)[::-1]
+            if x == y:
+                return False
+            at = seen.setdefault(min(x, y), (x, h, i))
+            if at[0] != x or (at[1] == h and at[2] != i):
+                return False
+    return True
+
+
+def bubble_ladder(seed, k, m, spacing, indel=False, lead=0, tail=0, out_tips=(), in_tips=(), fuz=3):
+    """A chain of m bubbles between two flanks, with tips added on demand.  Returns dict(seqs, gap, bubbles, paths):
+    seqs[0] is the random backbone, seqs[1] a second haplotype with m substitutions `spacing` (>= k + 1) bases apart,
+    the first `lead` bases after the left flank's last k-mer and the last `tail` bases in front of the right flank's
+    first k-mer; gap is the cut_gaps-style record of the one gap from the backbone's first k + fuz bases to its last.
+
+    Closure shape (k-mers, not bases): every substitution gives a bubble of two arms of k k-mers each; between two
+    bubbles the haplotypes share spacing - k k-mers, one unitig.  The left DP therefore logs one segment per arm and
+    one per shared stretch: about 3 segments per bubble, 2^m paths of one length (the count saturates at MAX_PATHS
+    from m = 30 on).  With indel=True every third bubble is a deletion on haplotype 2 instead (arms of k and k - 1
+    k-mers): later unitigs are entered at two depths, the paths have several lengths, and the closure has k-mers at
+    several depths (the fill kernels leave it to phase D2 on the device or to the host).
+
+    out_tips: backbone offsets (from the left flank's last k-mer) at which a dead end of k + 2 bases branches off
+    (a third read that leaves the backbone): in the left half of the gap each cuts one unitig in two and adds the
+    tip's own segment: +2 logged segments, no right-set entry.  in_tips: offsets at which a source of k + 2 bases
+    joins the backbone (a read that ends on it): the backbone's unitig is cut (+1 logged segment) and the tip is
+    one more predecessor for phase A to enter (+1 right-set entry when it lies in the right half).  Seeds whose
+    haplotypes repeat a k-mer anywhere (either strand) are rejected and the next seed of the stream is tried."""
+    assert spacing >= k + 1
+    rng = SplitMix(seed * 6151 + 101)
+    fl = k + fuz
+    n = fl + lead + (m - 1) * spacing + 1 + tail + fl if m else fl + lead + tail + fl
+    for _ in range(1000):
+        g = random_dna(rng, n)
+        h = list(g)
+        bubbles = []
+        for b in range(m):
+            p = fl + lead + b * spacing
+            if indel and b % 3 == 2:
+                h[p] = ""
+            else:
+                h[p] = "ACGT"[("ACGT".index(h[p]) + 1 + rng.randint(0, 2)) % 4]
+            bubbles.append(p)
+        seqs = [g, "".join(h)] if m else [g]
+        for t in out_tips:  # the backbone up to offset t, then a fresh k + 2 bases: a dead end behind fl + t
+            p = fl + t
+            seqs.append(g[p - k:p + 1] + rng.choice([c for c in "ACGT" if c != g[p + 1]]) + random_dna(rng, k + 1))
+        for t in in_tips:  # a fresh k + 2 bases, then the backbone from offset t on: a source in front of fl + t
+            p = fl + t
+            seqs.append(random_dna(rng, k + 1) + rng.choice([c for c in "ACGT" if c != g[p - 1]]) + g[p:p + k + 1])
+        if clean_haplotypes(seqs, k):
+            break
+    else:
+        raise RuntimeError("bubble_ladder: no clean seed")
+    true_len = n - 2 * fl
+    gap = dict(left=g[:fl], right=g[n - fl:], gap_len=true_len + k, lmf=fuz, rmf=fuz, true_len=true_len)
+    return dict(seqs=seqs, gap=gap, bubbles=bubbles, paths=(2 ** m if not indel else None))
+
+
+# Planted gaps at the per-gap capacities of the fill kernels (k = 31, bubbles 32 bases apart, a seed of its own
+# each, so that one graph can hold them all).  Each entry:
+# bubble_ladder's arguments and what the gap is meant to give: the segments the left DP logs (`nseg`: the segment
+# tier's log of G2S_SEG_CAP = 512, its 64-lane chunks, the 192 up to which the fill kernel analyses the closure
+# itself), the right set's entries (`nA`: 64 * G2S_SEG_ASETS = 256), the closure's segments (`ncl`: g2s_d2_small
+# takes 256) and phase C's path count (`count`, MAX_PATHS where absent).  tests/test_seg_model.py checks every value
+# against the segment tier's model and the oracle; tests/test_gpu_edges.py checks that the kernels count the same and
+# route the gap accordingly.  (3 segments a bubble + 2; an out-tip in the left half: +2 segments and +1 closure
+# segment; an out-tip in the right half: +1 segment, +1 entry; an in-tip in the right half: +1 segment, +2 entries.)
+_L = dict(k=31, spacing=32)
+MAX_PATHS = 2147483647 // 2 - 1  # (Gap2Seq.cpp:38: 2^30 - 2, so 2^30 paths is the first count that saturates)
+EDGE_LADDERS = {
+    "seg63": (dict(_L, seed=101, m=20, tail=100, out_tips=(700,)), dict(nseg=63, nA=31, ncl=62, count=1 << 20)),
+    "seg64": (dict(_L, seed=102, m=20, out_tips=(40,)), dict(nseg=64, nA=36, ncl=62, count=1 << 20)),
+    "seg65": (dict(_L, seed=103, m=21), dict(nseg=65, nA=36, ncl=64, count=1 << 21)),
+    "seg127": (dict(_L, seed=104, m=41, out_tips=(40,)), dict(nseg=127, nA=66, ncl=125)),
+    "seg128": (dict(_L, seed=105, m=42), dict(nseg=128, nA=69, ncl=127)),
+    "seg129": (dict(_L, seed=106, m=42, tail=100, out_tips=(1394,)), dict(nseg=129, nA=64, ncl=128)),
+    "seg191": (dict(_L, seed=107, m=63), dict(nseg=191, nA=99, ncl=190)),
+    "seg192": (dict(_L, seed=108, m=63, tail=100, out_tips=(2034,)), dict(nseg=192, nA=97, ncl=191)),
+    "seg193": (dict(_L, seed=109, m=63, out_tips=(40,)), dict(nseg=193, nA=99, ncl=191)),
+    "seg511": (dict(_L, seed=110, m=169, tail=5500, out_tips=(8000, 9000)), dict(nseg=511, nA=6, ncl=510)),
+    "seg512": (dict(_L, seed=111, m=170, tail=5500), dict(nseg=512, nA=4, ncl=511)),
+    "seg513": (dict(_L, seed=112, m=170, tail=5500, in_tips=(8440,)), dict(nseg=513, nA=6, ncl=512)),
+    "rs255": (dict(_L, seed=113, m=83, lead=3000, tail=100, in_tips=(5706,)), dict(nseg=252, nA=255, ncl=251)),
+    "rs256": (dict(_L, seed=114, m=84, lead=3000), dict(nseg=254, nA=256, ncl=253)),
+    "rs257": (dict(_L, seed=115, m=84, lead=3000, tail=100, out_tips=(5706,)), dict(nseg=255, nA=257, ncl=254)),
+    "cl255": (dict(_L, seed=116, m=84, out_tips=(40, 200)), dict(nseg=258, nA=132, ncl=255)),
+    "cl256": (dict(_L, seed=117, m=85), dict(nseg=257, nA=132, ncl=256)),
+    "cl257": (dict(_L, seed=118, m=85, out_tips=(40,)), dict(nseg=259, nA=132, ncl=257)),
+    "paths2^29": (dict(_L, seed=119, m=29), dict(nseg=89, nA=48, ncl=88, count=1 << 29)),
+    "paths2^30": (dict(_L, seed=120, m=30), dict(nseg=92, nA=51, ncl=91, count=MAX_PATHS)),
+    "paths2^31": (dict(_L, seed=121, m=31), dict(nseg=95, nA=51, ncl=94, count=MAX_PATHS)),
+    "indel20": (dict(_L, seed=122, m=20, indel=True), dict(nseg=239, nA=36, ncl=238, count=1 << 14)),
+}
+
+
+def edge_ladder(name):
+    kw, want = EDGE_LADDERS[name]
+    return bubble_ladder(**kw), want
+
+
+def edge_ladder_list(names, pad=0):
+    """The planted gaps of `names` as one list on one graph, among `pad` ordinary gaps of a plain genome (30 kbp,
+    20-300 bp gaps): (haplotypes, gaps, index of each planted gap in the list).  The segment tier packs the closures
+    of a list into one buffer of 64 segments a gap on average (g2s_api.hip, run_tier: a closure that finds it full
+    runs again in the large variant); enough ordinary gaps keep the planted ones clear of that limit, so that the
+    route of every gap is its own."""
+    seqs, gaps, idx = [], [], []
+    for name in names:
+        lad, _ = edge_ladder(name)
+        seqs += lad["seqs"]
+        gaps.append(lad["gap"])
+    if pad:
+        genome = random_dna(SplitMix(909), 30000)
+        seqs.append(genome)
+        planted, gaps = gaps, cut_gaps(31, genome, 31, fuz=3, ngaps=pad, min_len=20, max_len=300, d_err=10, vary_fuz=False)
+        for j, g in enumerate(planted):
+            idx.append(min(len(gaps), 3 + 4 * j))
+            gaps.insert(idx[-1], g)
+    else:
+        idx = list(range(len(gaps)))
+    return seqs, gaps, idx
+
+
 def scaffold_record(genome, k, fuz, pos_len_list, pad=5):
     """One multi-gap scaffold record: genome slice with N runs at the given
     (start, length, n_count) triples (sorted, non overlapping)."""

@@ -151,3 +151,70 @@ def test_model_small_k_without_strand_collisions(product, oracle, k, length):
         for skip, allp in ((False, True), (False, False), (True, True)):
             c, q = check_config(product, oracle, seqs, k, gaps, e, allp, skip)
             assert (c, q) == (len(gaps), 0)
+
+
+def _ladder_model(product, oracle, lad, e, allp=True, skip=False):
+    g = lad["gap"]
+    pg = product.Graph.from_seqs(lad["seqs"], 31, 1)
+    og = oracle.OracleGraph(lad["seqs"], 31, 1)
+    try:
+        tb = M.Tables(product, pg)
+        mg = _model_gap(pg, 31, g, e, allp, skip)
+        rs = M.right_set(tb, mg)
+        label = M.right_entries(tb, mg)
+        assert M.entries_to_set(tb, mg, label) == rs
+        m = M.fill_model(tb, mg, rs)
+        rng = oracle.OracleRng(5)
+        o = oracle.fill_gap(og, rng, g["left"], g["right"], g["gap_len"], e, g["lmf"], g["rmf"], skip, allp)
+        rng.free()
+    finally:
+        pg.free()
+        og.free()
+    return m, len(label), o
+
+
+@pytest.mark.parametrize("name", sorted(cases.EDGE_LADDERS))
+def test_edge_ladders_sit_where_the_gpu_tests_say(product, oracle, name):
+    """Every planted gap of cases.EDGE_LADDERS (tests/test_gpu_edges.py) at its capacity: the segments the left DP
+    logs, the right set's entries, the closure's segments and phase C's count are the model's, and the model's
+    count is the oracle's (2^29 exactly; 2^30 and 2^31 saturate at MAX_PATHS)."""
+    lad, want = cases.edge_ladder(name)
+    m, n_entries, o = _ladder_model(product, oracle, lad, 10)
+    assert not m.q7 and not o.info.q7
+    assert (m.n_seg, n_entries, len(m.compact)) == (want["nseg"], want["nA"], want["ncl"])
+    assert m.c_count == o.info.phaseC_count == want.get("count", cases.MAX_PATHS)
+    assert m.lengths == o.lengths and o.count > 0
+    if lad["paths"] is not None:
+        assert o.count == min(lad["paths"], cases.MAX_PATHS)
+
+
+def test_edge_ladders_step_by_one_across_each_capacity():
+    """The table holds cap - 1, cap and cap + 1 for every capacity the model sees."""
+    got = {}
+    for name, (_, want) in cases.EDGE_LADDERS.items():
+        for key in ("nseg", "nA", "ncl"):
+            got.setdefault(key, set()).add(want[key])
+    for cap in (64, 128, 192, 512):
+        assert {cap - 1, cap, cap + 1} <= got["nseg"], cap
+    assert {255, 256, 257} <= got["nA"]
+    assert {255, 256, 257} <= got["ncl"]
+    counts = {w.get("count", cases.MAX_PATHS) for _, w in cases.EDGE_LADDERS.values()}
+    assert 1 << 29 in counts and cases.MAX_PATHS == (1 << 30) - 2
+
+
+@pytest.mark.parametrize("name", ["paths2^29", "paths2^30", "paths2^31", "seg193", "indel20"])
+def test_edge_ladders_in_every_mode(product, oracle, name):
+    """The count ladders and two closures the host analyses, with -best-only and with the skip rule: the model
+    (the host half of phase D included) equals the oracle in every field."""
+    lad, want = cases.edge_ladder(name)
+    for skip, allp in ((False, True), (False, False), (True, True)):
+        c, q = check_config(product, oracle, lad["seqs"], 31, [lad["gap"]], 10, allp, skip)
+        assert (c, q) == (1, 0)
+
+
+def test_edge_ladders_share_one_graph():
+    """tests/test_gpu_edges.py runs the planted gaps as one list on one graph, among ordinary gaps: no ladder's
+    k-mer is another's or the plain genome's."""
+    seqs, gaps, idx = cases.edge_ladder_list(sorted(cases.EDGE_LADDERS), pad=300)
+    assert cases.clean_haplotypes(seqs, 31) and len(gaps) == 300 + len(cases.EDGE_LADDERS)
+    assert [gaps[i] for i in idx] == cases.edge_ladder_list(sorted(cases.EDGE_LADDERS))[1]
