@@ -67,7 +67,7 @@ int main(int argc, char** argv) {
     else if (a == "-fasta-width") fasta_width = atoi(val());
     else if (a == "-help" || a == "-h") {
       std::cout << "Gap2Seq-core (MI355X) -reads a.fq[,b.fq] -filled out.fa (-scaffolds in.fa | -left S -right S -length N)\n"
-                   "  [-k 31] [-solid 2] [-dist-error 500] [-fuz 10] [-max-mem 20] [-randseed 0]\n"
+                   "  [-k 31 (1..127)] [-solid 2] [-dist-error 500] [-fuz 10] [-max-mem 20] [-randseed 0]\n"
                    "  [-all-upper] [-best-only] [-unique] [-nb-cores N] [-device D | -devices D0,D1,...] [-streams 2]\n"
                    "  [-stream-gaps 8192] [-fasta-width 0]\n";
       return EXIT_SUCCESS;

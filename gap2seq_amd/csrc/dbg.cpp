@@ -22,9 +22,11 @@ namespace {
 template <class KT> std::vector<KT>& kmer_vec(Graph& g);
 template <> std::vector<uint64_t>& kmer_vec<uint64_t>(Graph& g) { return g.kmers64; }
 template <> std::vector<u128>& kmer_vec<u128>(Graph& g) { return g.kmers128; }
+template <> std::vector<u256>& kmer_vec<u256>(Graph& g) { return g.kmers256; }
 template <class KT> const std::vector<KT>& kmer_vec(const Graph& g);
 template <> const std::vector<uint64_t>& kmer_vec<uint64_t>(const Graph& g) { return g.kmers64; }
 template <> const std::vector<u128>& kmer_vec<u128>(const Graph& g) { return g.kmers128; }
+template <> const std::vector<u256>& kmer_vec<u256>(const Graph& g) { return g.kmers256; }
 
 template <class F>
 void parallel_for(uint64_t n, int nthreads, F f) {
@@ -326,14 +328,18 @@ uint32_t Graph::node_of(const char* s) const {
   if (n == 0) return kInvalidNode;
   int strand = 0;
   int64_t r;
-  if (!wide) {
+  if (kmer_bytes == 8) {
     uint64_t c;
     encode_kmer<uint64_t>(s, k, &c, &strand);
     r = rank_of<uint64_t>(*this, c);
-  } else {
+  } else if (kmer_bytes == 16) {
     u128 c;
     encode_kmer<u128>(s, k, &c, &strand);
     r = rank_of<u128>(*this, c);
+  } else {
+    u256 c;
+    encode_kmer<u256>(s, k, &c, &strand);
+    r = rank_of<u256>(*this, c);
   }
   if (r < 0) return kInvalidNode;
   return 2 * rank2id[(size_t)r] + ((uint32_t)strand ^ (uint32_t)flip[(size_t)r]);
@@ -342,18 +348,19 @@ uint32_t Graph::node_of(const char* s) const {
 std::string Graph::node_string(uint32_t v) const {
   const uint32_t r = id2rank[v >> 1];
   const int strand = (int)((v & 1u) ^ (uint32_t)flip[r]);
-  if (!wide) return decode_kmer<uint64_t>(kmers64[r], strand, k);
-  return decode_kmer<u128>(kmers128[r], strand, k);
+  if (kmer_bytes == 8) return decode_kmer<uint64_t>(kmers64[r], strand, k);
+  if (kmer_bytes == 16) return decode_kmer<u128>(kmers128[r], strand, k);
+  return decode_kmer<u256>(kmers256[r], strand, k);
 }
 
 Graph* graph_build(const std::vector<std::pair<const char*, uint64_t>>& seqs, int k, int solid, int nthreads,
                    std::string* err) {
-  if (k < 1 || k > 63) { if (err) *err = "k must be in [1,63]"; return nullptr; }
+  if (k < 1 || k > kMaxK) { if (err) *err = "k must be in [1," + std::to_string(kMaxK) + "]"; return nullptr; }
   if (nthreads <= 0) nthreads = (int)std::max(1u, std::thread::hardware_concurrency());
   Graph* g = new Graph();
   g->k = k;
   g->solid = solid;
-  g->wide = k >= 32;
+  g->kmer_bytes = kmer_width(k);
   const auto t0 = std::chrono::steady_clock::now();
   // the solid k-mer set: sort on the GPU when there is one (dbg_gpu.hip), host threads otherwise
   bool set_on_gpu = false;
@@ -362,10 +369,16 @@ Graph* graph_build(const std::vector<std::pair<const char*, uint64_t>>& seqs, in
     set_on_gpu = count_solid_gpu(*g, seqs, solid, getenv("G2S_DEVICE") ? atoi(getenv("G2S_DEVICE")) : 0, &why);
     if (!set_on_gpu && getenv("G2S_DEBUG")) fprintf(stderr, "[g2s]   k-mer set on the host (%s)\n", why.c_str());
   }
-  if (!set_on_gpu) { if (!g->wide) count_solid<uint64_t>(*g, seqs, solid, nthreads); else count_solid<u128>(*g, seqs, solid, nthreads); }
+  if (!set_on_gpu) {
+    if (g->kmer_bytes == 8) count_solid<uint64_t>(*g, seqs, solid, nthreads);
+    else if (g->kmer_bytes == 16) count_solid<u128>(*g, seqs, solid, nthreads);
+    else count_solid<u256>(*g, seqs, solid, nthreads);
+  }
   const auto t1 = std::chrono::steady_clock::now();
   if (g->n >= (1ull << 30)) { if (err) *err = "too many k-mers for 32-bit oriented node ids"; delete g; return nullptr; }
-  if (!g->wide) finish_graph<uint64_t>(*g, nthreads); else finish_graph<u128>(*g, nthreads);
+  if (g->kmer_bytes == 8) finish_graph<uint64_t>(*g, nthreads);
+  else if (g->kmer_bytes == 16) finish_graph<u128>(*g, nthreads);
+  else finish_graph<u256>(*g, nthreads);
   if (getenv("G2S_DEBUG"))
     fprintf(stderr, "[g2s] graph build: %llu k-mers; solid k-mer set %.3f s (%s), tables + unitig order %.3f s (%d threads)\n",
             (unsigned long long)g->n, std::chrono::duration<double>(t1 - t0).count(), set_on_gpu ? "GPU sort" : "host",
@@ -383,7 +396,10 @@ bool graph_save(const Graph& g, const std::string& path, std::string* err) {
   uint64_t hdr[4] = {(uint64_t)g.k, g.n, g.n_unitigs, (uint64_t)(g.pred.empty() ? 0 : 1) | ((uint64_t)std::max(0, g.solid) << 8)};
   bool ok = fwrite(kMagic, 1, 8, f) == 8 && fwrite(hdr, 8, 4, f) == 4;
   auto put = [&](const void* p, size_t bytes) { if (ok && bytes) ok = fwrite(p, 1, bytes, f) == bytes; };
-  if (!g.wide) put(g.kmers64.data(), g.kmers64.size() * 8); else put(g.kmers128.data(), g.kmers128.size() * 16);
+  // (the width follows from k: 8-, 16- or 32-byte k-mers, little-endian words, least significant first)
+  if (g.kmer_bytes == 8) put(g.kmers64.data(), g.kmers64.size() * 8);
+  else if (g.kmer_bytes == 16) put(g.kmers128.data(), g.kmers128.size() * 16);
+  else put(g.kmers256.data(), g.kmers256.size() * 32);
   put(g.rank2id.data(), g.rank2id.size() * 4);
   put(g.flip.data(), g.flip.size());
   put(g.succ.data(), g.succ.size() * 4);
@@ -407,13 +423,13 @@ Graph* graph_load(const std::string& path, std::string* err) {
   // the file is not trusted: every size and index is checked before it is used
   const uint64_t solid_of_cache = hdr[3] >> 8;
   hdr[3] &= 0xFFull;
-  if (hdr[0] < 1 || hdr[0] > 63 || hdr[1] >= (1ull << 30) || hdr[2] > hdr[1] || hdr[3] > 1 || solid_of_cache > (1ull << 30)) {
+  if (hdr[0] < 1 || hdr[0] > (uint64_t)kMaxK || hdr[1] >= (1ull << 30) || hdr[2] > hdr[1] || hdr[3] > 1 || solid_of_cache > (1ull << 30)) {
     fclose(f);
     if (err) *err = "corrupt graph cache header: " + path;
     return nullptr;
   }
   {
-    const uint64_t per = (hdr[0] >= 32 ? 16u : 8u) + 4u + 1u + 32u + (hdr[3] ? 32u : 0u) + 2u;
+    const uint64_t per = (uint64_t)kmer_width((int)hdr[0]) + 4u + 1u + 32u + (hdr[3] ? 32u : 0u) + 2u;
     const long here = ftell(f);
     fseek(f, 0, SEEK_END);
     const long end = ftell(f);
@@ -429,11 +445,12 @@ Graph* graph_load(const std::string& path, std::string* err) {
   g->solid = (int)solid_of_cache;
   g->n = hdr[1];
   g->n_unitigs = hdr[2];
-  g->wide = g->k >= 32;
+  g->kmer_bytes = kmer_width(g->k);
   bool ok = true;
   auto get = [&](void* p, size_t bytes) { if (ok && bytes) ok = fread(p, 1, bytes, f) == bytes; };
-  if (!g->wide) { g->kmers64.resize((size_t)g->n); get(g->kmers64.data(), (size_t)g->n * 8); }
-  else { g->kmers128.resize((size_t)g->n); get(g->kmers128.data(), (size_t)g->n * 16); }
+  if (g->kmer_bytes == 8) { g->kmers64.resize((size_t)g->n); get(g->kmers64.data(), (size_t)g->n * 8); }
+  else if (g->kmer_bytes == 16) { g->kmers128.resize((size_t)g->n); get(g->kmers128.data(), (size_t)g->n * 16); }
+  else { g->kmers256.resize((size_t)g->n); get(g->kmers256.data(), (size_t)g->n * 32); }
   g->rank2id.resize((size_t)g->n); get(g->rank2id.data(), (size_t)g->n * 4);
   g->flip.resize((size_t)g->n); get(g->flip.data(), (size_t)g->n);
   g->succ.resize((size_t)g->n * 8); get(g->succ.data(), (size_t)g->n * 32);
@@ -448,8 +465,9 @@ Graph* graph_load(const std::string& path, std::string* err) {
   };
   // sorted k-mer set, rank2id a permutation, neighbour ids in range, codes 0..3
   for (uint64_t r = 1; r < g->n; r++) {
-    const bool ascending = g->wide ? g->kmers128[(size_t)r - 1] < g->kmers128[(size_t)r]
-                                   : g->kmers64[(size_t)r - 1] < g->kmers64[(size_t)r];
+    const bool ascending = g->kmer_bytes == 8    ? g->kmers64[(size_t)r - 1] < g->kmers64[(size_t)r]
+                           : g->kmer_bytes == 16 ? g->kmers128[(size_t)r - 1] < g->kmers128[(size_t)r]
+                                                 : g->kmers256[(size_t)r - 1] < g->kmers256[(size_t)r];
     if (!ascending) return corrupt("k-mers not strictly ascending");
   }
   g->id2rank.assign((size_t)g->n, kInvalidNode);
@@ -462,7 +480,9 @@ Graph* graph_load(const std::string& path, std::string* err) {
   for (uint32_t w : g->pred) if (w != kInvalidNode && w >= 2 * g->n) return corrupt("predecessor out of range");
   for (uint8_t c : g->lastnt) if (c > 3) return corrupt("base code out of range");
   for (uint8_t c : g->flip) if (c > 1) return corrupt("strand flag out of range");
-  if (!g->wide) build_bucket_index<uint64_t>(*g); else build_bucket_index<u128>(*g);
+  if (g->kmer_bytes == 8) build_bucket_index<uint64_t>(*g);
+  else if (g->kmer_bytes == 16) build_bucket_index<u128>(*g);
+  else build_bucket_index<u256>(*g);
   build_ustart(*g);
   return g;
 }

@@ -33,12 +33,13 @@ struct DeviceGraph {
 struct Graph {
   int k = 0;
   int solid = 0;      // abundance threshold the set was built with (0: unknown, a cache written before it was recorded)
-  bool wide = false;  // 128-bit k-mers (k >= 32)
+  int kmer_bytes = 8; // k-mer width: 8 (k <= 31), 16 (k <= 63) or 32 bytes (k <= 127); kmer_width(k)
   uint64_t n = 0;     // canonical solid k-mers
   uint64_t n_unitigs = 0;
-  // sorted canonical k-mers; exactly one of the two is used
+  // sorted canonical k-mers; exactly one of the three is used (the one of kmer_bytes)
   std::vector<uint64_t> kmers64;
   std::vector<u128> kmers128;
+  std::vector<u256> kmers256;
   std::vector<uint32_t> bucket;   // prefix index over the sorted array
   int bucket_bits = 0;
   std::vector<uint32_t> rank2id;  // sorted rank -> node index (unitig order)
@@ -87,6 +88,10 @@ struct Graph {
   std::string node_string(uint32_t v) const;
   inline char last_char(uint32_t v) const { return kNtChar[lastnt[v]]; }
 };
+
+static const int kMaxK = 127;
+// bytes of the k-mer word for k in [1, kMaxK]
+static inline int kmer_width(int k) { return k <= 31 ? 8 : k <= 63 ? 16 : 32; }
 
 // seqs may contain any bytes; k-mers containing N/n are skipped (GATB model).
 Graph* graph_build(const std::vector<std::pair<const char*, uint64_t>>& seqs, int k, int solid, int nthreads,

@@ -3,7 +3,7 @@
 // The build (replaces gatb Graph::create, /root/reference/src/Gap2Seq.cpp:193-219) has four
 // steps after the sorted set of solid canonical k-mers exists (dbg.cpp: count_solid):
 //   1. successor table in sorted-rank space: 8 neighbour k-mers per k-mer, each a binary
-//      search inside its prefix bucket (k_succ; 64- and 128-bit k-mers);
+//      search inside its prefix bucket (k_succ; 64-, 128- and 256-bit k-mers);
 //   2. numbering along maximal non-branching paths.  On the host this is one dependent,
 //      cache-missing load per k-mer (0.35 s of a 0.49 s build at 3 Mbp, 11.7 s of 16.6 s at
 //      60 Mbp); here it is list ranking by pointer jumping:
@@ -116,6 +116,7 @@ __global__ void k_assign(const uint64_t* __restrict__ pd, const uint32_t* __rest
 
 // ---- successor table in sorted-rank space (dbg.cpp: build_tables_rank, odd k) -------------
 typedef unsigned __int128 u128;
+using g2s::u256;
 
 __device__ __forceinline__ uint64_t d_revcomp32(uint64_t x) {  // all 32 bases of a word (kmer.hpp)
   x = ((x >> 2) & 0x3333333333333333ULL) | ((x & 0x3333333333333333ULL) << 2);
@@ -127,6 +128,11 @@ __device__ __forceinline__ uint64_t d_revcomp(uint64_t x, int k) { return d_revc
 __device__ __forceinline__ u128 d_revcomp(u128 x, int k) {
   const u128 y = ((u128)d_revcomp32((uint64_t)x) << 64) | (u128)d_revcomp32((uint64_t)(x >> 64));
   return y >> (128 - 2 * k);
+}
+__device__ __forceinline__ u256 d_revcomp(const u256& x, int k) {
+  const u128 h = ((u128)d_revcomp32(x.word(0)) << 64) | (u128)d_revcomp32(x.word(1));
+  const u128 l = ((u128)d_revcomp32(x.word(2)) << 64) | (u128)d_revcomp32(x.word(3));
+  return u256(h, l) >> (256 - 2 * k);
 }
 
 template <class KT>
@@ -224,6 +230,22 @@ __global__ void k_join(const uint64_t* __restrict__ lo, const uint64_t* __restri
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   keys[i] = ((u128)hi[i] << 64) | (u128)lo[i];
+}
+// 256-bit keys are sorted as four stable 64-bit LSD passes over (word, index) pairs: before pass `w` the w-th word of
+// every key in the order of the passes so far (word 0 in text order, idx == nullptr), after the last pass the keys
+// gathered once (32-byte keys do not move four times)
+__global__ void k_word(const u256* __restrict__ keys, const uint32_t* __restrict__ idx, uint64_t n, int w,
+                       uint64_t* __restrict__ word, uint32_t* __restrict__ iota) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint64_t* src = (const uint64_t*)(keys + (idx ? idx[i] : (uint32_t)i));  // (u256: little-endian words)
+  word[i] = src[w];
+  if (!idx) iota[i] = (uint32_t)i;
+}
+__global__ void k_gather(const u256* __restrict__ keys, const uint32_t* __restrict__ idx, uint64_t n, u256* __restrict__ out) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  out[i] = keys[idx[i]];
 }
 // heads of runs of equal keys in the sorted array (the all-ones filler is no k-mer)
 template <class KT>
@@ -412,7 +434,8 @@ static bool finish_gpu_t(Graph& g, const std::vector<KT>& kmers, int device,
 }
 
 // The sorted set of solid canonical k-mers and its prefix index, from the reads.  One key per
-// text position, radix sort (rocPRIM; 128-bit keys as two stable 64-bit passes), run heads,
+// text position, radix sort (rocPRIM; 128-bit keys as two stable 64-bit passes, 256-bit keys as four over
+// (word, index) pairs), run heads,
 // runs of at least `solid` copies compacted.  Returns false (g untouched) when the device
 // cannot be used or the text does not fit comfortably.
 template <class KT>
@@ -432,7 +455,10 @@ static bool count_solid_gpu_t(Graph& g, std::vector<KT>& out, const std::vector<
   if (T == 0 || T >= (1ull << 32)) { if (why) *why = "text size"; return false; }
   size_t free_b = 0, total_b = 0;
   G2S_GPU_TRY(hipMemGetInfo(&free_b, &total_b));
-  if ((double)T * (double)(4 * sizeof(KT) + 24) > 0.5 * (double)free_b) { if (why) *why = "text too large for the device"; return false; }
+  // (bytes a text position at the sort's peak: keys, sorted copy or split words, the sort's scratch; 256-bit keys:
+  // the keys, the word and index double buffers, the sort's scratch, then the keys and their gathered copy)
+  const double per_pos = sizeof(KT) == 32 ? (double)(2 * sizeof(KT) + 40) : (double)(4 * sizeof(KT) + 24);
+  if ((double)T * per_pos > 0.5 * (double)free_b) { if (why) *why = "text too large for the device"; return false; }
   std::vector<uint8_t> text((size_t)T);
   {
     size_t pos = 0;
@@ -454,6 +480,28 @@ static bool count_solid_gpu_t(Graph& g, std::vector<KT>& out, const std::vector<
     G2S_GPU_TRY(d_tmp.alloc(tb));
     // (the filler is all-ones: sort on all 64 bits so that it ends up last)
     G2S_GPU_TRY(rocprim::radix_sort_keys(d_tmp.p, tb, (uint64_t*)d_keys.p, (uint64_t*)d_alt.p, (size_t)T, 0, 64));
+    sorted = (KT*)d_alt.p;
+  } else if constexpr (sizeof(KT) == 32) {
+    G2S_GPU_TRY(d_lo.alloc((size_t)T * 8));   // the pass's word, in and out
+    G2S_GPU_TRY(d_lo2.alloc((size_t)T * 8));
+    G2S_GPU_TRY(d_hi.alloc((size_t)T * 4));   // the key's index, in and out
+    G2S_GPU_TRY(d_hi2.alloc((size_t)T * 4));
+    uint64_t *w_in = (uint64_t*)d_lo.p, *w_out = (uint64_t*)d_lo2.p;
+    uint32_t *i_in = (uint32_t*)d_hi.p, *i_out = (uint32_t*)d_hi2.p;
+    size_t tb = 0;
+    G2S_GPU_TRY(rocprim::radix_sort_pairs(nullptr, tb, w_in, w_out, i_in, i_out, (size_t)T, 0, 64));
+    G2S_GPU_TRY(d_tmp.alloc(tb));
+    // least significant word first; every later pass is stable, so the order of the earlier words holds among equals
+    for (int w = 0; w < 4; w++) {
+      hipLaunchKernelGGL(k_word, grdT, blk, 0, 0, (const u256*)d_keys.p, w == 0 ? (const uint32_t*)nullptr : (const uint32_t*)i_in,
+                         T, w, w_in, i_in);
+      G2S_GPU_TRY(rocprim::radix_sort_pairs(d_tmp.p, tb, w_in, w_out, i_in, i_out, (size_t)T, 0, 64));
+      std::swap(i_in, i_out);
+    }
+    for (Dev* d : {&d_lo, &d_lo2, &d_tmp}) (void)hipFree(d->release());
+    G2S_GPU_TRY(d_alt.alloc((size_t)T * sizeof(KT)));
+    hipLaunchKernelGGL(k_gather, grdT, blk, 0, 0, (const u256*)d_keys.p, (const uint32_t*)i_in, T, (u256*)d_alt.p);
+    for (Dev* d : {&d_hi, &d_hi2, &d_keys}) (void)hipFree(d->release());
     sorted = (KT*)d_alt.p;
   } else {
     G2S_GPU_TRY(d_lo.alloc((size_t)T * 8));
@@ -543,15 +591,17 @@ static bool count_solid_gpu_t(Graph& g, std::vector<KT>& out, const std::vector<
 
 bool count_solid_gpu(Graph& g, const std::vector<std::pair<const char*, uint64_t>>& seqs, int solid, int device,
                      std::string* why) {
-  return g.wide ? count_solid_gpu_t<u128>(g, g.kmers128, seqs, solid, device, why)
-                : count_solid_gpu_t<uint64_t>(g, g.kmers64, seqs, solid, device, why);
+  if (g.kmer_bytes == 32) return count_solid_gpu_t<u256>(g, g.kmers256, seqs, solid, device, why);
+  return g.kmer_bytes == 16 ? count_solid_gpu_t<u128>(g, g.kmers128, seqs, solid, device, why)
+                            : count_solid_gpu_t<uint64_t>(g, g.kmers64, seqs, solid, device, why);
 }
 
 bool graph_finish_gpu(Graph& g, int device, const std::function<void(const std::vector<uint32_t>&, uint32_t)>& host_walk,
                       std::string* why) {
   if ((g.k % 2) == 0) { if (why) *why = "even k"; return false; }
-  return g.wide ? finish_gpu_t<u128>(g, g.kmers128, device, host_walk, why)
-                : finish_gpu_t<uint64_t>(g, g.kmers64, device, host_walk, why);
+  if (g.kmer_bytes == 32) return finish_gpu_t<u256>(g, g.kmers256, device, host_walk, why);
+  return g.kmer_bytes == 16 ? finish_gpu_t<u128>(g, g.kmers128, device, host_walk, why)
+                            : finish_gpu_t<uint64_t>(g, g.kmers64, device, host_walk, why);
 }
 
 }  // namespace g2s

@@ -424,7 +424,7 @@ __device__ __forceinline__ void seg_fill_one(uint32_t* lds, const SegArgs& A, co
       uint32_t* stage = (TWO && wave == 1) ? lds + (7u * G2S_SEG_CAP + 32u) : lds;
       const int k = A.lk.k;
       const int llen = k + lmf, rlen = k + rmf, tail = llen + rlen;
-      const uint32_t words = (uint32_t)(tail + rlen + 3) / 4u;  // (k <= 63, lmf, rmf <= 31: at most 71)
+      const uint32_t words = (uint32_t)(tail + rlen + 3) / 4u;  // (k <= 63 here — inline_ok —, lmf, rmf <= 31: at most 71)
       if (!inl_early) {
         const uint32_t* src = (const uint32_t*)(A.inl_text + gd.rs_mask);  // (4-byte aligned, padded: g2s_batch_prepare)
         if ((uint32_t)lane < words) tw0 = src[lane];

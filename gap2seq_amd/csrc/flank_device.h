@@ -25,6 +25,11 @@ __device__ __forceinline__ u128 d_revcomp(u128 x, int k) {
   const u128 y = ((u128)d_revcomp32((uint64_t)x) << 64) | (u128)d_revcomp32((uint64_t)(x >> 64));
   return y >> (128 - 2 * k);
 }
+__device__ __forceinline__ u256 d_revcomp(const u256& x, int k) {
+  const u128 h = ((u128)d_revcomp32(x.word(0)) << 64) | (u128)d_revcomp32(x.word(1));
+  const u128 l = ((u128)d_revcomp32(x.word(2)) << 64) | (u128)d_revcomp32(x.word(3));
+  return u256(h, l) >> (256 - 2 * k);
+}
 
 // The k characters from byte `off` of the text at `tw` (4-byte aligned words, in LDS; sizeof(KT) + 1 words from word
 // off / 4 on are read, whatever they hold) as a k-mer, GATB codec: A0 C1 T2 G3, any byte maps to a base ((c >> 1) & 3),

@@ -8,9 +8,11 @@ namespace g2s {
 // device copy of what Graph::node_of searches (dbg.hpp): the sorted canonical k-mers, their prefix
 // index, and the rank -> (node index, strand flip) tables
 struct FlankLookup {
-  const void* kmers = nullptr;      // uint64_t[n] (k <= 31) or unsigned __int128[n]
+  const void* kmers = nullptr;      // uint64_t[n] (k <= 31), unsigned __int128[n] (k <= 63) or u256[n] (k <= 127)
   const uint32_t* bucket = nullptr; // [(1 << bucket_bits) + 1]
   const uint32_t* rank2node = nullptr;  // by sorted rank: 2 * node id | strand flip of the canonical k-mer
+  // wide: the k-mer width code, 0: 64-bit, 1: 128-bit, 2: 256-bit (G2S_LK_*).  Only the look-up kernel takes 256-bit
+  // k-mers: the fill kernels' in-wave look-ups stay at k <= 63 (g2s_api.hip: inline_ok)
   int32_t k = 0, bucket_bits = 0, wide = 0, pad = 0;
 };
 
@@ -23,6 +25,9 @@ struct FlankDesc {
   uint16_t lmf, rmf;  // rmf: bit 15 = the right flank is exactly k + rmf characters and stands in the text once
 };
 #define G2S_FLANK_RIGHT_ONCE 0x8000u
+#define G2S_LK_64 0
+#define G2S_LK_128 1
+#define G2S_LK_256 2
 #define G2S_FLANK_TEXT_MAX 2048 /* bytes of flank text per gap the kernel stages in LDS */
 
 hipError_t launch_resolve_flanks(hipStream_t st, const FlankLookup& lk, uint32_t ngaps, const FlankDesc* desc /* device-readable */,

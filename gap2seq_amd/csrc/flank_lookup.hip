@@ -23,6 +23,7 @@
 namespace {
 
 using g2s::u128;
+using g2s::u256;
 
 // FLANK_WAVES waves a workgroup, a gap per wave at a time (a quarter of the dispatches of one-wave workgroups).  What
 // rocprofv3 shows as this kernel's 75-80 us on a 10 000-gap list is mostly the 1.5 MB copy of descriptors and flank text
@@ -34,7 +35,8 @@ __global__ __launch_bounds__(64 * FLANK_WAVES) void g2s_resolve_flanks(g2s::Flan
                                                                        uint32_t* __restrict__ nodes_host, uint32_t ngaps) {
   // the gap's flank text: [left: first k+lmf chars][right: first k+rmf chars][right: last k+rmf chars] — the last part
   // left out when it is the second (a flank of exactly k+rmf characters: what GapCutter writes)
-  __shared__ __attribute__((aligned(16))) uint32_t tws[FLANK_WAVES][G2S_FLANK_TEXT_MAX / 4 + 20];  // (+20: flank_encode reads sizeof(KT) + 1 words from an item's first)
+  // (+20 / +36: flank_encode reads sizeof(KT) + 1 words from an item's first, 33 of them at 256 bits)
+  __shared__ __attribute__((aligned(16))) uint32_t tws[FLANK_WAVES][G2S_FLANK_TEXT_MAX / 4 + (sizeof(KT) == 32 ? 36 : 20)];
   const int lane = (int)(threadIdx.x & 63u);
   const uint32_t wave = threadIdx.x >> 6;
   uint32_t* tw = tws[wave];
@@ -69,7 +71,9 @@ hipError_t launch_resolve_flanks(hipStream_t st, const FlankLookup& lk, uint32_t
                                  uint32_t* nodes_dev, uint32_t* nodes_host) {
   if (ngaps == 0) return hipSuccess;
   const uint32_t wgs = std::min<uint32_t>((ngaps + FLANK_WAVES - 1u) / FLANK_WAVES, 4096u);
-  if (lk.wide)
+  if (lk.wide == G2S_LK_256)
+    hipLaunchKernelGGL(g2s_resolve_flanks<u256>, dim3(wgs), dim3(64 * FLANK_WAVES), 0, st, lk, desc, text, nodes_dev, nodes_host, ngaps);
+  else if (lk.wide)
     hipLaunchKernelGGL(g2s_resolve_flanks<u128>, dim3(wgs), dim3(64 * FLANK_WAVES), 0, st, lk, desc, text, nodes_dev, nodes_host, ngaps);
   else
     hipLaunchKernelGGL(g2s_resolve_flanks<uint64_t>, dim3(wgs), dim3(64 * FLANK_WAVES), 0, st, lk, desc, text, nodes_dev, nodes_host, ngaps);

@@ -702,9 +702,11 @@ extern "C" int g2s_session_create(g2s_graph* g, int device, const g2s_params* p,
   }
   {  // what the flank look-up kernel searches: the sorted k-mer set, its prefix index, rank -> node
     const Graph& gr = *g->g;
-    const size_t kb = gr.wide ? gr.kmers128.size() * 16 : gr.kmers64.size() * 8;
+    const size_t kb = (size_t)gr.n * (size_t)gr.kmer_bytes;
+    const void* km = gr.kmer_bytes == 32 ? (const void*)gr.kmers256.data()
+                     : gr.kmer_bytes == 16 ? (const void*)gr.kmers128.data() : (const void*)gr.kmers64.data();
     hipError_t e = s->d_lk_kmers.ensure(std::max<size_t>(kb, 16));
-    if (e == hipSuccess && kb) e = hipMemcpy(s->d_lk_kmers.p, gr.wide ? (const void*)gr.kmers128.data() : (const void*)gr.kmers64.data(), kb, hipMemcpyHostToDevice);
+    if (e == hipSuccess && kb) e = hipMemcpy(s->d_lk_kmers.p, km, kb, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = s->d_lk_bucket.ensure(std::max<size_t>(gr.bucket.size() * 4, 16));
     if (e == hipSuccess && !gr.bucket.empty()) e = hipMemcpy(s->d_lk_bucket.p, gr.bucket.data(), gr.bucket.size() * 4, hipMemcpyHostToDevice);
     // (rank -> the oriented node of the canonical k-mer, one word: 2 * id | flip — one random access of the look-up
@@ -718,7 +720,7 @@ extern "C" int g2s_session_create(g2s_graph* g, int device, const g2s_params* p,
     if (e != hipSuccess) { delete s; return fail(G2S_ERR_HIP, std::string("session setup (look-up tables): ") + hipGetErrorString(e)); }
     s->lookup.kmers = s->d_lk_kmers.p; s->lookup.bucket = (const uint32_t*)s->d_lk_bucket.p;
     s->lookup.rank2node = (const uint32_t*)s->d_lk_rank2id.p;
-    s->lookup.k = gr.k; s->lookup.bucket_bits = gr.bucket_bits; s->lookup.wide = gr.wide ? 1 : 0;
+    s->lookup.k = gr.k; s->lookup.bucket_bits = gr.bucket_bits; s->lookup.wide = gr.kmer_bytes == 32 ? G2S_LK_256 : gr.kmer_bytes == 16 ? G2S_LK_128 : G2S_LK_64;
   }
   {  // phase D3 on the device (d3_device.hip): the last base of every oriented k-mer as text, the generator's jump tables
     const Graph& gr = *g->g;
@@ -1098,7 +1100,8 @@ extern "C" int g2s_batch_prepare(g2s_session* s, const g2s_gap* gaps, size_t n, 
   // whose longest gaps start in the large variant; G2S_FLANK_KERNEL=1: the look-up kernel as until round 5.  A list
   // without a bad flank gets its text at a FIXED STRIDE: when the launch takes the gaps in list order, a wave knows
   // where its text is before its descriptor has arrived — on a short list both come over the link.)
-  b->inline_ok = fast_gd != nullptr && b->dmax < 2500 && !GENV("G2S_FLANK_KERNEL");
+  // (k >= 64: the look-up kernel always — the fill kernels' in-wave look-ups take 64- and 128-bit k-mers only)
+  b->inline_ok = fast_gd != nullptr && b->dmax < 2500 && !GENV("G2S_FLANK_KERNEL") && s->lookup.wide != G2S_LK_256;
   uint32_t tstride = 0;
   if (b->inline_ok && n_desc == n && tb_max <= 508 && !GENV("G2S_NO_TEXT_STRIDE")) {
     tstride = (uint32_t)((tb_max + 3) & ~(size_t)3);

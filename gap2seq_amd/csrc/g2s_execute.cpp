@@ -292,7 +292,7 @@ extern "C" int g2s_execute_scaffolds_stream(g2s_session* s, const g2s_run_opts* 
         const int sres = r.count;
         const char* tail = arena + r.fill_off;
         if (r.flags & G2S_GAP_BACKTRACE_FAIL) {
-          char msg[192];
+          char msg[192];  // ("Unable to backtrace! " two ints and the k-mer: at most 173 bytes at k = 127)
           if (g2s_backtrace_text(&jobs[(size_t)ev.job], &r, k, msg, sizeof msg)) os << msg << "\n";
         }
         const int filledStart = (int)filledSeq.length() + kmer_start + k + lmf - r.left_fuz - prevGapEnd;
@@ -419,7 +419,7 @@ extern "C" int g2s_execute_single(g2s_session* s, const g2s_run_opts* o, const c
   int rc = g2s_fill_batch(s, &gj, 1, &r, arena.data(), arena.size());
   if (rc != G2S_OK) return rc;
   if (r.flags & G2S_GAP_BACKTRACE_FAIL) {
-    char msg[192];
+    char msg[192];  // (at most 173 bytes at k = 127)
     if (g2s_backtrace_text(&gj, &r, k, msg, sizeof msg)) os << msg << "\n";
   }
   const char* tail = arena.data() + r.fill_off;

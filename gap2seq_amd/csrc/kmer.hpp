@@ -7,14 +7,62 @@
 //   invalid(c) = (c>>3)&1 -> true for N/n, used only when counting k-mers
 //   first base most significant; complement = code ^ 2
 //   canonical = numeric min(forward, revcomp); strand 0 iff forward < revcomp
-//   64-bit words for k <= 31, 128-bit for 32 <= k <= 63.
+//   64-bit words for k <= 31, 128-bit for 32 <= k <= 63, 256-bit (u256) for 64 <= k <= 127.
 #pragma once
 #include <cstdint>
 #include <string>
 
+#if defined(__HIPCC__)
+#define G2S_HD __host__ __device__
+#else
+#define G2S_HD
+#endif
+
 namespace g2s {
 
 typedef unsigned __int128 u128;
+
+// 256-bit unsigned integer: what the k-mer templates ask of their word type (shifts, bitwise operations, subtraction,
+// numeric order, construction from small integers, truncating casts), on the host and on the device.  Two 128-bit
+// halves, the low one first in memory: a k-mer array is four little-endian 64-bit words, least significant first.
+// Order is numeric, most significant half first (GATB's A < C < T < G, first base most significant).
+struct u256 {
+  u128 lo, hi;
+  G2S_HD u256() : lo(0), hi(0) {}
+  G2S_HD u256(uint64_t x) : lo(x), hi(0) {}
+  G2S_HD u256(u128 h, u128 l) : lo(l), hi(h) {}
+  G2S_HD explicit operator uint64_t() const { return (uint64_t)lo; }
+  G2S_HD explicit operator uint32_t() const { return (uint32_t)lo; }
+  G2S_HD explicit operator uint8_t() const { return (uint8_t)lo; }
+  G2S_HD explicit operator int() const { return (int)(uint32_t)lo; }
+  G2S_HD uint64_t word(int i) const {  // 64-bit word i, 0 = least significant
+    return (uint64_t)((i & 2) ? (hi >> (64 * (i & 1))) : (lo >> (64 * (i & 1))));
+  }
+};
+static_assert(sizeof(u256) == 32, "u256 is four 64-bit words");
+
+G2S_HD inline u256 operator<<(const u256& a, int s) {
+  if (s <= 0) return a;
+  if (s >= 256) return u256();
+  if (s >= 128) return u256(a.lo << (s - 128), (u128)0);
+  return u256((a.hi << s) | (a.lo >> (128 - s)), a.lo << s);
+}
+G2S_HD inline u256 operator>>(const u256& a, int s) {
+  if (s <= 0) return a;
+  if (s >= 256) return u256();
+  if (s >= 128) return u256((u128)0, a.hi >> (s - 128));
+  return u256(a.hi >> s, (a.lo >> s) | (a.hi << (128 - s)));
+}
+G2S_HD inline u256 operator|(const u256& a, const u256& b) { return u256(a.hi | b.hi, a.lo | b.lo); }
+G2S_HD inline u256 operator&(const u256& a, const u256& b) { return u256(a.hi & b.hi, a.lo & b.lo); }
+G2S_HD inline u256 operator^(const u256& a, const u256& b) { return u256(a.hi ^ b.hi, a.lo ^ b.lo); }
+G2S_HD inline u256 operator~(const u256& a) { return u256(~a.hi, ~a.lo); }
+G2S_HD inline u256 operator-(const u256& a, const u256& b) { return u256(a.hi - b.hi - (a.lo < b.lo ? 1 : 0), a.lo - b.lo); }
+G2S_HD inline u256& operator<<=(u256& a, int s) { return a = a << s; }
+G2S_HD inline u256& operator>>=(u256& a, int s) { return a = a >> s; }
+G2S_HD inline bool operator==(const u256& a, const u256& b) { return a.hi == b.hi && a.lo == b.lo; }
+G2S_HD inline bool operator!=(const u256& a, const u256& b) { return !(a == b); }
+G2S_HD inline bool operator<(const u256& a, const u256& b) { return a.hi < b.hi || (a.hi == b.hi && a.lo < b.lo); }
 
 static inline int nt_code(char c) { return (c >> 1) & 3; }
 static inline bool nt_invalid(char c) { return ((c >> 3) & 1) != 0; }
@@ -50,6 +98,19 @@ struct KmerOps<u128> {
   }
   static uint64_t hash(u128 x) {
     return KmerOps<uint64_t>::hash((uint64_t)x) ^ KmerOps<uint64_t>::hash((uint64_t)(x >> 64) ^ 0x9e3779b97f4a7c15ULL);
+  }
+};
+
+template <>
+struct KmerOps<u256> {
+  static u256 mask(int k) { return k >= 128 ? ~u256() : (~u256()) >> (256 - 2 * k); }
+  static u256 revcomp(u256 x, int k) {
+    const u128 h = ((u128)revcomp32(x.word(0)) << 64) | (u128)revcomp32(x.word(1));
+    const u128 l = ((u128)revcomp32(x.word(2)) << 64) | (u128)revcomp32(x.word(3));
+    return u256(h, l) >> (256 - 2 * k);
+  }
+  static uint64_t hash(u256 x) {
+    return KmerOps<u128>::hash(x.lo) ^ KmerOps<u128>::hash(x.hi ^ (u128)0x85ebca6b27d4eb4fULL);
   }
 };
 

@@ -58,7 +58,7 @@ const char* g2s_last_error(void);
  *  Graph: replaces Graph::create(BankAlbum, "-kmer-size k -abundance-min solid
  *  ...") / Graph::load (Gap2Seq.cpp:193-219).  Exact solid canonical k-mer set
  *  (GATB codec A0 C1 T2 G3, canonical = min(fwd, revcomp), k-mers containing
- *  N/n skipped), numbered in unitig order, with a 4-slot successor table per
+ *  N/n skipped; k in [1, 127]: 64-, 128- or 256-bit k-mers), numbered in unitig order, with a 4-slot successor table per
  *  oriented node in GATB enumeration order (A,C,T,G).  Predecessors are read
  *  from the same table: pred(v)[i] = succ(v^1)[i]^1.
  *  The build itself (k-mer sort, successor table, unitig numbering) runs on
