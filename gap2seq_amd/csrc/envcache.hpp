@@ -4,8 +4,8 @@
 // step in front of the fill kernel's launch.  Here a switch has a slot (registered at its first look), the slots' values
 // are read once, and read again only when the environment has CHANGED — the tests switch settings between two calls of
 // one process (setenv / unsetenv replace or move the entries' pointers: the cheap fingerprint below sees it).
-//   GENV("G2S_X")      at a call site: the variable's value or nullptr, as getenv would give it
-//   g2s_env_sync()     once at every entry point of the ABI that may look at a switch
+//   GENV("G2S_SEG_WAVES")  at a call site: the variable's value or nullptr, as getenv would give it
+//   g2s_env_sync()         once at every entry point of the ABI that may look at a switch
 #pragma once
 #include <atomic>
 #include <cstdlib>

@@ -8,7 +8,7 @@
 
 #define G2S_SEG_CAP 512u  /* segments per gap kept in LDS */
 #define G2S_SEG_ASETS 4   /* right-set entries per gap: 64 per set, in registers */
-/* the large variant (g2s_fill_segx): gaps that outgrow the capacities above */
+/* the large variant (g2s_fill_segw, fill_segw.hip): gaps that outgrow the capacities above */
 #define G2S_SEGX_CAP 16384u  /* segments per gap, in the workgroup's global scratch */
 #define G2S_SEGX_EA 6144u    /* right-set entries */
 #define G2S_SEGX_AS 16384u   /* slots of the label table of phase A (LDS) */
@@ -93,21 +93,12 @@ hipError_t launch_fill_seg(hipStream_t st, uint32_t ngaps, const uint32_t* succ,
                            // the stream ~10 us a launch); null: not timed
                            hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
 
-// The large variant: `workgroups` persistent workgroups (one per compute unit) take the listed gaps
-// in order from the counter *next_gap (zero before the launch); scratch: fill_segx_scratch_bytes().
-size_t fill_segx_lds_bytes();
-size_t fill_segx_scratch_bytes(uint32_t workgroups);
-uint32_t fill_segx_dbg_words();
-hipError_t launch_fill_segx(hipStream_t st, uint32_t ngaps, uint32_t workgroups, const uint32_t* succ, const uint32_t* urec,
-                            const GapDev* gaps, const uint32_t* gap_ids, const uint32_t* flank_nodes, SubRec* sub_out,
-                            unsigned long long out_cap, unsigned long long* out_counter, GapOut* outs, GapOut* outs_host,
-                            uint32_t* done_list, int skip_confident, uint32_t* dbg, uint32_t* scratch,
-                            unsigned long long* next_gap);
-
-// The large variant on a workgroup of eight waves per gap (fill_segw.hip): same arguments; the workgroups take all of a
-// compute unit's LDS, scratch: fill_segw_scratch_bytes().  resident: closures and records stay in device memory.
+// The large variant on a workgroup of eight waves per gap (fill_segw.hip): `workgroups` persistent workgroups, one per
+// compute unit and each taking all of its LDS, take the listed gaps in order from the counter *next_gap (zero before
+// the launch); scratch: fill_segw_scratch_bytes().  resident: closures and records stay in device memory.
 size_t fill_segw_lds_bytes();
 size_t fill_segw_scratch_bytes(uint32_t workgroups);
+uint32_t fill_segx_dbg_words();  // words per gap of the large variant's optional diagnostics buffer
 hipError_t launch_fill_segw(hipStream_t st, uint32_t ngaps, uint32_t workgroups, const uint32_t* succ, const uint32_t* urec,
                             const GapDev* gaps, const uint32_t* gap_ids, const uint32_t* flank_nodes, SubRec* sub_out,
                             unsigned long long out_cap, unsigned long long* out_counter, GapOut* outs, GapOut* outs_host,

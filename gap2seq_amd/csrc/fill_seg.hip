@@ -3,13 +3,12 @@
 // search over UNITIG SEGMENTS instead of DP levels.  tests/seg_model.py is the executable restatement of this
 // algorithm that the CPU suite checks without a GPU; read the two side by side.
 //
-// Three kernels from one template (seg_fill_one):
+// Two kernels from one template (seg_fill_one):
 //   g2s_fill_seg    one wave per gap, everything in LDS and registers: lists that fill the chip
 //   g2s_fill_seg2   the same with two waves per gap (phase A beside the first half of phase B): short lists,
 //                   whose launch ends with its slowest gap
-//   g2s_fill_segx   the large variant for gaps that outgrow the LDS-resident capacities (-dist-error 2000):
-//                   segments in global scratch, pending events in an LDS hash table, the right set as sorted
-//                   index intervals searched per lane; persistent workgroups, one per compute unit
+// Gaps that outgrow the LDS-resident capacities (-dist-error 2000) go to the large variant, g2s_fill_segw
+// (fill_segw.hip).
 //
 // Why segments: one wave per SIMD is bound by instruction issue and by dependent LDS / memory round trips
 // (rocprofv3, profiles/r02_pmc_sq_*.json: a third of the wave cycles issue instructions, two thirds wait),
@@ -44,10 +43,9 @@
 //   output   the closure as 32-byte segment records (SegRec), children before parents, parents in GATB's
 //            predecessor order, written straight into pinned host memory; the host walks them (post.cpp).
 // A gap that outgrows a capacity (segments, pending events, right-set entries, host buffer) is flagged and
-// runs again in the next kernel of the chain (g2s_fill_segx, then the LDS tier).  Integer work only: no MFMA.
+// runs again in the next kernel of the chain (g2s_fill_segw, then the LDS tier).  Integer work only: no MFMA.
 #include "sync_debug.h"
 #include <hip/hip_runtime.h>
-#include <cstdlib>
 #include <mutex>
 #include <set>
 #include <utility>
@@ -238,12 +236,8 @@ __device__ __forceinline__ bool seg_q7_between(const uint32_t* s_node, const uin
   return found;
 }
 
-// One gap, one wave.  BIG = false: the tier proper (segments in LDS, pending events and the right set in
-// registers).  BIG = true: the same search for the gaps that outgrow those capacities (-dist-error 2000:
-// thousands of segments, hundreds of pending events, thousands of right-set entries): segments in the
-// workgroup's global scratch `scr`, pending events in an LDS hash table, the right set as a sorted array
-// of disjoint index intervals in LDS that every lane searches on its own.
-// TWO (with BIG = false): the workgroup has two waves — wave 1 runs phase A while wave 0 runs the part of
+// One gap, one wave: segments in LDS, pending events and the right set in registers.
+// TWO: the workgroup has two waves — wave 1 runs phase A while wave 0 runs the part of
 // phase B that does not look at the right set yet (:1050 first consults it at depth g/2 + e/2 + lmf), so
 // that phase A leaves the critical path of the slowest gaps; they meet at one barrier.
 #ifndef G2S_GUESS_LATE_CYCLES_LONG
@@ -253,10 +247,8 @@ __device__ __forceinline__ bool seg_q7_between(const uint32_t* s_node, const uin
 #define G2S_GUESS_LATE_CYCLES 100000u /* two waves per gap: a search that ends later than this leaves its traceback to the trace kernel */
 #endif
 
-template <bool BIG, bool TWO>
-__device__ __forceinline__ void seg_fill_one(uint32_t* lds, const SegArgs& A, const uint32_t x /* position in the launch */,
-                                             uint32_t* scr) {
-  static_assert(!(BIG && TWO), "the large variant is one wave per gap");
+template <bool TWO>
+__device__ __forceinline__ void seg_fill_one(uint32_t* lds, const SegArgs& A, const uint32_t x /* position in the launch */) {
   const uint32_t* __restrict__ succ = A.succ;
   const uint32_t* __restrict__ urec = A.urec;
   const uint32_t* __restrict__ gap_ids = A.gap_ids;
@@ -270,34 +262,31 @@ __device__ __forceinline__ void seg_fill_one(uint32_t* lds, const SegArgs& A, co
   const int skip_confident = A.skip_confident;
   uint32_t* dbg = A.dbg;
   const uint32_t dbg_words = A.dbg_words;
-  constexpr uint32_t CAP = BIG ? G2S_SEGX_CAP : G2S_SEG_CAP;
-  // segment arrays: LDS (7 arrays of G2S_SEG_CAP words + left seeds), or the scratch; s_aux / s_t always in LDS
-  uint32_t* s_node = BIG ? scr : lds;           // entry node of the segment
+  constexpr uint32_t CAP = G2S_SEG_CAP;
+  // segment arrays in LDS: 7 arrays of G2S_SEG_CAP words + left seeds
+  uint32_t* s_node = lds;                       // entry node of the segment
   uint32_t* s_dl = s_node + CAP;                // entry depth | length << 16
   uint32_t* s_cnt = s_dl + CAP;                 // path count of every state of the segment
   uint32_t* s_p01 = s_cnt + CAP;                // parents (segment ids, 16 bits each, 0xFFFF = none)
   uint32_t* s_p23 = s_p01 + CAP;
-  uint32_t* s_gen = s_p23 + CAP;                // (BIG) generation, copied into s_aux before phase D1
-  uint32_t* s_aux = BIG ? lds : s_p23 + CAP;    // generation | closure marks of the children << 16; later: emit offset
+  uint32_t* s_aux = s_p23 + CAP;                // generation | closure marks of the children << 16; later: emit offset
   uint32_t* s_t = s_aux + CAP;                  // last closure state: towards a sink | from a traceback start << 16 (0xFFFF none)
-  uint32_t* l_seed = BIG ? lds + (SEGX_LDS_WORDS - 32u) : s_t + CAP;  // left-flank seeds by depth [32]
+  uint32_t* l_seed = s_t + CAP;                 // left-flank seeds by depth [32]
 
   const int lane = (int)(threadIdx.x & 63u);
   const int wave = TWO ? (int)(threadIdx.x >> 6) : 0;
   const uint32_t gi = gap_ids ? uni(gap_ids[x]) : x;  // (no list: the launch takes the gaps in list order)
   // (look-ups in this kernel, the text at a fixed stride by gap: asked for beside the gap's descriptor — one round trip
   // instead of two; on a short list both come over the link)
-  bool inl = false, inl_early = false;
+  const bool inl = A.inl_text != nullptr;
+  bool inl_early = false;
   uint32_t tw0 = 0u, tw1 = 0u;  // (the text's words lane and lane + 64, in flight while the descriptor travels)
-  if constexpr (!BIG) {
-    inl = A.inl_text != nullptr;
-    if (inl && A.inl_stride) {
-      const uint32_t* src = (const uint32_t*)(A.inl_text + (size_t)gi * A.inl_stride);
-      const uint32_t words = A.inl_stride / 4u, w = threadIdx.x & 63u;
-      if (w < words) tw0 = src[w];
-      if (w + 64u < words) tw1 = src[w + 64u];
-      inl_early = true;
-    }
+  if (inl && A.inl_stride) {
+    const uint32_t* src = (const uint32_t*)(A.inl_text + (size_t)gi * A.inl_stride);
+    const uint32_t words = A.inl_stride / 4u, w = threadIdx.x & 63u;
+    if (w < words) tw0 = src[w];
+    if (w + 64u < words) tw1 = src[w + 64u];
+    inl_early = true;
   }
   const GapDev gd = A.gaps.load(gi);
   GapOut* go = &outs[gi];
@@ -335,18 +324,15 @@ __device__ __forceinline__ void seg_fill_one(uint32_t* lds, const SegArgs& A, co
   // Since round 3 this path only serves the host path of lists beyond 2 048 gaps (G2S_RESIDENT=0, or a list the
   // device gave back): resident mode announces nothing.  A batch whose closing wave gives up waiting (2^18 looks:
   // never seen) or that never fills is not lost — the host takes every gap not announced when the launch has ended.
-  // The large variant's workgroups publish what several waves stored: it keeps the fences.
   // (look-ups in this kernel: the host's copy of the gap's node ids is written only for the gaps the host will look
   // at — a closure it analyses, a gap that outgrew the tier — : 132 bytes a gap through the link for every gap were
   // 1.3 MB of a 10 000-gap list, 30 us of its launch)
   auto nodes_to_host = [&]() {
-    if constexpr (!BIG) {
-      if (A.inl_text != nullptr && A.inl_nodes_host != nullptr) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const uint32_t nit = (uint32_t)(gd.lmf + 1) + 2u * (uint32_t)(gd.rmf + 1);
-        for (uint32_t q = (uint32_t)(threadIdx.x & 63u); q < nit; q += 64u)
-          A.inl_nodes_host[gd.flank_off + q] = __hip_atomic_load(&A.inl_nodes_dev[gd.flank_off + q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
+    if (A.inl_text != nullptr && A.inl_nodes_host != nullptr) {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      const uint32_t nit = (uint32_t)(gd.lmf + 1) + 2u * (uint32_t)(gd.rmf + 1);
+      for (uint32_t q = (uint32_t)(threadIdx.x & 63u); q < nit; q += 64u)
+        A.inl_nodes_host[gd.flank_off + q] = __hip_atomic_load(&A.inl_nodes_dev[gd.flank_off + q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
   };
   auto publish = [&]() {
@@ -359,55 +345,46 @@ __device__ __forceinline__ void seg_fill_one(uint32_t* lds, const SegArgs& A, co
       if (A.d2_list && A.d2_tag && lane == 0) (void)atomicAdd(out_counter + 32 + (gi & 63u), 1ull);
       return;
     }
-    if constexpr (BIG) __threadfence();
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     if ((uint32_t)lane < sizeof(GapOut) / 4u)
       ((uint32_t*)&outs_host[gi])[lane] = __hip_atomic_load(&((const uint32_t*)go)[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if constexpr (BIG) {
-      __threadfence_system();
+    const uint32_t B = A.pub_batch;
+    if (B <= 1u) {
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");  // system scope: buffer_wbl2 sc0 sc1
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (the compiler leaves no wait between the write-back and a following store)
       if (lane == 0) {
         const unsigned long long at = atomicAdd(out_counter + 1, 1ull);
-        __hip_atomic_store(&done_list[at], gi, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+        __hip_atomic_store(&done_list[at], gi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
       }
-    } else {
-      const uint32_t B = A.pub_batch;
-      if (B <= 1u) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");  // system scope: buffer_wbl2 sc0 sc1
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (the compiler leaves no wait between the write-back and a following store)
-        if (lane == 0) {
-          const unsigned long long at = atomicAdd(out_counter + 1, 1ull);
-          __hip_atomic_store(&done_list[at], gi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-        return;
-      }
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the copy of the record too
-      const uint32_t xcd = (uint32_t)__builtin_amdgcn_s_getreg(20 | (3 << 11)) & 7u;  // HW_REG_XCC_ID, bits 0-3
-      uint32_t* list = A.xcd_list + (size_t)xcd * A.xcd_stride;
-      uint32_t t = 0;
-      if (lane == 0) {
-        t = (uint32_t)atomicAdd(A.xcd_tickets + xcd, 1ull);
-        __hip_atomic_store(&list[t], gi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-      t = uni((uint32_t)__shfl((int)t, 0));
-      if (((t + 1u) & (B - 1u)) != 0u) return;
-      const uint32_t first = t + 1u - B;
-      uint32_t e = G2S_DEV_INVALID;
-      bool all = true;
-      if ((uint32_t)lane < B) {
-        uint32_t spins = 0;
-        do {
-          e = __hip_atomic_load(&list[first + (uint32_t)lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        } while (e == G2S_DEV_INVALID && ++spins < (1u << 18));
-        all = e != G2S_DEV_INVALID;
-      }
-      if (__ballot(!all)) return;  // (never expected; the batch is then taken at the end of the launch)
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      unsigned long long base = 0;
-      if (lane == 0) base = atomicAdd(out_counter + 1, (unsigned long long)B);
-      base = (unsigned long long)(uint32_t)__shfl((int)(uint32_t)base, 0);
-      if ((uint32_t)lane < B) __hip_atomic_store(&done_list[base + (uint32_t)lane], e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      return;
     }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the copy of the record too
+    const uint32_t xcd = (uint32_t)__builtin_amdgcn_s_getreg(20 | (3 << 11)) & 7u;  // HW_REG_XCC_ID, bits 0-3
+    uint32_t* list = A.xcd_list + (size_t)xcd * A.xcd_stride;
+    uint32_t t = 0;
+    if (lane == 0) {
+      t = (uint32_t)atomicAdd(A.xcd_tickets + xcd, 1ull);
+      __hip_atomic_store(&list[t], gi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    t = uni((uint32_t)__shfl((int)t, 0));
+    if (((t + 1u) & (B - 1u)) != 0u) return;
+    const uint32_t first = t + 1u - B;
+    uint32_t e = G2S_DEV_INVALID;
+    bool all = true;
+    if ((uint32_t)lane < B) {
+      uint32_t spins = 0;
+      do {
+        e = __hip_atomic_load(&list[first + (uint32_t)lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      } while (e == G2S_DEV_INVALID && ++spins < (1u << 18));
+      all = e != G2S_DEV_INVALID;
+    }
+    if (__ballot(!all)) return;  // (never expected; the batch is then taken at the end of the launch)
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    unsigned long long base = 0;
+    if (lane == 0) base = atomicAdd(out_counter + 1, (unsigned long long)B);
+    base = (unsigned long long)(uint32_t)__shfl((int)(uint32_t)base, 0);
+    if ((uint32_t)lane < B) __hip_atomic_store(&done_list[base + (uint32_t)lane], e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   };
 
   // ---- the gap's flank nodes: lane d holds left seed d (f_l), lane j right seed j (f_r) and target j (tg).  From the
@@ -419,39 +396,37 @@ __device__ __forceinline__ void seg_fill_one(uint32_t* lds, const SegArgs& A, co
   // ids also go where the table would hold them (g2s_d2_*, the large variant's reruns and the host read them there).
   uint32_t f_l = G2S_DEV_INVALID, f_r = G2S_DEV_INVALID, tg = G2S_DEV_INVALID;
   if (inl) {
-    if constexpr (!BIG) {
-      // LDS of this wave (nothing of the search lives there yet): text [0, 128) words, node ids [128, 224)
-      uint32_t* stage = (TWO && wave == 1) ? lds + (7u * G2S_SEG_CAP + 32u) : lds;
-      const int k = A.lk.k;
-      const int llen = k + lmf, rlen = k + rmf, tail = llen + rlen;
-      const uint32_t words = (uint32_t)(tail + rlen + 3) / 4u;  // (k <= 63 here — inline_ok —, lmf, rmf <= 31: at most 71)
-      if (!inl_early) {
-        const uint32_t* src = (const uint32_t*)(A.inl_text + gd.rs_mask);  // (4-byte aligned, padded: g2s_batch_prepare)
-        if ((uint32_t)lane < words) tw0 = src[lane];
-        if ((uint32_t)lane + 64u < words) tw1 = src[lane + 64];
-      }
-      stage[lane] = tw0;
-      stage[lane + 64] = tw1;
-      asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_wave_barrier();
-      uint32_t* fn = stage + 128;
-      const int nl = lmf + 1, nr = rmf + 1;
-      for (int i = lane; i < nl + 2 * nr; i += 64) {
-        const bool right_seed = i >= nl && i < nl + nr;
-        if (TWO && right_seed != (wave == 1)) continue;
-        const int at = g2s::flank_item_offset(i, k, lmf, rmf, tail);
-        const uint32_t node = A.lk.wide ? g2s::flank_node_of<g2s::u128>(A.lk, stage, at) : g2s::flank_node_of<uint64_t>(A.lk, stage, at);
-        fn[i] = node;
-        A.inl_nodes_dev[gd.flank_off + (uint32_t)i] = node;  // (the pinned copy: only of the gaps the host will look at — publish)
-      }
-      lds_sync();
-      __builtin_amdgcn_wave_barrier();
-      if (lane <= lmf && lane < 32 && (!TWO || wave == 0)) f_l = fn[lane];
-      if (lane <= rmf && lane < 32 && (!TWO || wave == 1)) f_r = fn[nl + lane];
-      if (lane <= rmf && lane < 32 && (!TWO || wave == 0)) tg = fn[nl + nr + lane];
-      lds_sync();
-      __builtin_amdgcn_wave_barrier();
+    // LDS of this wave (nothing of the search lives there yet): text [0, 128) words, node ids [128, 224)
+    uint32_t* stage = (TWO && wave == 1) ? lds + (7u * G2S_SEG_CAP + 32u) : lds;
+    const int k = A.lk.k;
+    const int llen = k + lmf, rlen = k + rmf, tail = llen + rlen;
+    const uint32_t words = (uint32_t)(tail + rlen + 3) / 4u;  // (k <= 63 here — inline_ok —, lmf, rmf <= 31: at most 71)
+    if (!inl_early) {
+      const uint32_t* src = (const uint32_t*)(A.inl_text + gd.rs_mask);  // (4-byte aligned, padded: g2s_batch_prepare)
+      if ((uint32_t)lane < words) tw0 = src[lane];
+      if ((uint32_t)lane + 64u < words) tw1 = src[lane + 64];
     }
+    stage[lane] = tw0;
+    stage[lane + 64] = tw1;
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_wave_barrier();
+    uint32_t* fn = stage + 128;
+    const int nl = lmf + 1, nr = rmf + 1;
+    for (int i = lane; i < nl + 2 * nr; i += 64) {
+      const bool right_seed = i >= nl && i < nl + nr;
+      if (TWO && right_seed != (wave == 1)) continue;
+      const int at = g2s::flank_item_offset(i, k, lmf, rmf, tail);
+      const uint32_t node = A.lk.wide ? g2s::flank_node_of<g2s::u128>(A.lk, stage, at) : g2s::flank_node_of<uint64_t>(A.lk, stage, at);
+      fn[i] = node;
+      A.inl_nodes_dev[gd.flank_off + (uint32_t)i] = node;  // (the pinned copy: only of the gaps the host will look at — publish)
+    }
+    lds_sync();
+    __builtin_amdgcn_wave_barrier();
+    if (lane <= lmf && lane < 32 && (!TWO || wave == 0)) f_l = fn[lane];
+    if (lane <= rmf && lane < 32 && (!TWO || wave == 1)) f_r = fn[nl + lane];
+    if (lane <= rmf && lane < 32 && (!TWO || wave == 0)) tg = fn[nl + nr + lane];
+    lds_sync();
+    __builtin_amdgcn_wave_barrier();
   } else {
     if (lane <= lmf && lane < 32) f_l = lseeds[lane];
     if (lane <= rmf && lane < 32) { f_r = rseeds[lane]; tg = targets[lane]; }  // lane j: target k-mer j
@@ -459,14 +434,11 @@ __device__ __forceinline__ void seg_fill_one(uint32_t* lds, const SegArgs& A, co
   if (lane < 32 && wave == 0) l_seed[lane] = f_l;
 
   uint32_t nA = 0, roundsA = 0, nvis = 0, xa = 0;
-  uint32_t nM = 0;  // (regular tier) the right set's entries as merged k-mer index intervals: how many
-  // (!BIG) the right-set entries in registers: lane l of set s holds entry 64 s + l, as a k-mer index interval
+  uint32_t nM = 0;  // the right set's entries as merged k-mer index intervals: how many
+  // the right-set entries in registers: lane l of set s holds entry 64 s + l, as a k-mer index interval
   uint32_t an[G2S_SEG_ASETS], al[G2S_SEG_ASETS], ar[G2S_SEG_ASETS], alo[G2S_SEG_ASETS], ahi[G2S_SEG_ASETS];
 #pragma unroll
   for (int s = 0; s < G2S_SEG_ASETS; s++) { an[s] = G2S_DEV_INVALID; al[s] = 0; ar[s] = 0; alo[s] = 1u; ahi[s] = 0u; }
-  // (BIG) the right set as M disjoint, sorted index intervals in LDS: ivw[2 i] = last index, ivw[2 i + 1] = first
-  uint32_t* ivw = lds;
-  uint32_t M = 0, ivP = 0;  // ivP: largest power of two <= M
   // ---------------- phase A: the right set as (entry node, depth label) pairs ----------------
   // Label-correcting search over unitigs (:871-982 computes {v : fewest predecessor steps from a
   // right seed <= right_half}, seed j entering at depth j; only membership is consumed, :1050).
@@ -492,46 +464,43 @@ __device__ __forceinline__ void seg_fill_one(uint32_t* lds, const SegArgs& A, co
   // the table's entries, packed (the queues are idle by then), and from there into registers: lane l of set s
   // holds entry 64 s + l as a k-mer index interval; then Q7 in the right set
   auto load_right_set = [&]() {
-    if constexpr (!BIG) {
-      const uint32_t* cnode = aq0;
-      const uint32_t* clab = aq0 + ACAP;
-      const uint32_t* crem = (const uint32_t*)lab;
-      if (!overflow) {
-#pragma unroll
-        for (int s = 0; s < G2S_SEG_ASETS; s++) {
-          const uint32_t e = (uint32_t)s * 64u + (uint32_t)lane;
-          if (e < nA) { an[s] = cnode[e]; al[s] = clab[e]; ar[s] = crem[e]; }
-        }
-        lds_sync();
-      }
-      // the set's size (intervals of one unitig may overlap: an upper bound) and the expansions of the search
-#pragma unroll
-      for (int s = 0; s < G2S_SEG_ASETS; s++) {
-        const bool have = (uint32_t)s * 64u + (uint32_t)lane < nA;
-        const uint32_t steps = have ? min(ar[s], (uint32_t)gd.right_half - al[s]) : 0u;
-        if ((uint32_t)s * 64u < nA) {
-          nvis += wave_sum(have ? steps + 1u : 0u);
-          xa += wave_sum(have ? min(steps + 1u, (uint32_t)gd.right_half - al[s]) : 0u);
-        }
-      }
-      // the merged intervals [alo, ahi]: lane l of set s holds the (64 s + l)-th; lanes without one an empty interval
-      const uint64_t* ivl = (const uint64_t*)(aq0 + 2u * ACAP);
+    const uint32_t* cnode = aq0;
+    const uint32_t* clab = aq0 + ACAP;
+    const uint32_t* crem = (const uint32_t*)lab;
+    if (!overflow) {
 #pragma unroll
       for (int s = 0; s < G2S_SEG_ASETS; s++) {
         const uint32_t e = (uint32_t)s * 64u + (uint32_t)lane;
-        const uint64_t x = (!overflow && e < nM) ? ivl[e] : 1ull << 32;
-        alo[s] = (uint32_t)(x >> 32);
-        ahi[s] = (uint32_t)x;
+        if (e < nA) { an[s] = cnode[e]; al[s] = clab[e]; ar[s] = crem[e]; }
       }
       lds_sync();
     }
+    // the set's size (intervals of one unitig may overlap: an upper bound) and the expansions of the search
+#pragma unroll
+    for (int s = 0; s < G2S_SEG_ASETS; s++) {
+      const bool have = (uint32_t)s * 64u + (uint32_t)lane < nA;
+      const uint32_t steps = have ? min(ar[s], (uint32_t)gd.right_half - al[s]) : 0u;
+      if ((uint32_t)s * 64u < nA) {
+        nvis += wave_sum(have ? steps + 1u : 0u);
+        xa += wave_sum(have ? min(steps + 1u, (uint32_t)gd.right_half - al[s]) : 0u);
+      }
+    }
+    // the merged intervals [alo, ahi]: lane l of set s holds the (64 s + l)-th; lanes without one an empty interval
+    const uint64_t* ivl = (const uint64_t*)(aq0 + 2u * ACAP);
+#pragma unroll
+    for (int s = 0; s < G2S_SEG_ASETS; s++) {
+      const uint32_t e = (uint32_t)s * 64u + (uint32_t)lane;
+      const uint64_t x = (!overflow && e < nM) ? ivl[e] : 1ull << 32;
+      alo[s] = (uint32_t)(x >> 32);
+      ahi[s] = (uint32_t)x;
+    }
+    lds_sync();
   };
   unsigned long long cyc_a_end = cyc0;
 #ifdef G2S_SEG_PROFILE
   uint32_t prof_a[4] = {0, 0, 0, 0};  // phase A (one wave per gap): records wait | probes + atomics | results, slow path, queue | rest of the round
 #endif
-  if constexpr (!BIG) {
-   if (!TWO || wave == 1) {
+  if (!TWO || wave == 1) {
     for (uint32_t i = (uint32_t)lane; i < ALAB; i += 64u) lab[i] = G2S_DEV_EMPTY64;
     lds_sync();
     auto a_hash = [&](uint32_t p) -> uint32_t { uint32_t x = p; x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15; x *= 0x846ca68bU; x ^= x >> 16; return x & (ALAB - 1u); };
@@ -756,151 +725,9 @@ __device__ __forceinline__ void seg_fill_one(uint32_t* lds, const SegArgs& A, co
       __syncthreads();
       return;
     }
-   }
-   if constexpr (!TWO) load_right_set();
-  } else {
-    // ---- (BIG) the same label-correcting search with room for G2S_SEGX_EA entries.
-    // LDS: tab[AS] u64 (node << 32 | label); the two queues live in the workgroup's scratch.
-    constexpr uint32_t AS = G2S_SEGX_AS, EA = G2S_SEGX_EA, QCAP = G2S_SEGX_QCAP;
-    uint64_t* tab = (uint64_t*)lds;
-    uint32_t* gq = scr + 6u * G2S_SEGX_CAP;
-    bool stuck = false;  // (per lane) a probe ran past its bound
-    for (uint32_t i = (uint32_t)lane; i < AS; i += 64u) tab[i] = SEGX_EMPTY64;
-    lds_sync();
-    auto a_hash = [&](uint32_t p) -> uint32_t { uint32_t x = p; x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15; x *= 0x846ca68bU; x ^= x >> 16; return x & (AS - 1u); };
-    auto relabel = [&](bool active, uint32_t p, uint32_t dp) -> bool {
-      bool improved = false, fresh = false;
-      if (active) {
-        const uint64_t key = ((uint64_t)p << 32) | dp;
-        uint32_t h = a_hash(p);
-        uint32_t guard = 0;
-        while (true) {
-          if (++guard > 4u * AS) { stuck = true; break; }
-          const uint64_t c = tab[h];
-          if ((uint32_t)(c >> 32) == p) {
-            improved = atomicMin((unsigned long long*)&tab[h], (unsigned long long)key) > key;
-            break;
-          }
-          if (c == SEGX_EMPTY64) {
-            const unsigned long long prev =
-                atomicCAS((unsigned long long*)&tab[h], (unsigned long long)SEGX_EMPTY64, (unsigned long long)key);
-            if (prev == SEGX_EMPTY64) { improved = true; fresh = true; break; }
-            continue;
-          }
-          h = (h + 1u) & (AS - 1u);
-        }
-      }
-      nA += (uint32_t)__popcll(__ballot(fresh));
-      return improved;
-    };
-    if (!overflow) {
-      uint32_t cur = 0, ne = 0;
-      {
-        const uint32_t sd = (lane <= rmf && lane < 32) ? rseeds[lane] : G2S_DEV_INVALID;
-        const bool imp = relabel(sd != G2S_DEV_INVALID && lane <= gd.right_half, sd, (uint32_t)lane);
-        const uint64_t m = __ballot(imp);
-        if (imp) gq[(uint32_t)__popcll(m & below(lane))] = sd;
-        ne = (uint32_t)__popcll(m);
-      }
-      while (ne > 0 && !overflow) {
-        roundsA++;
-        if (roundsA > 65535u) { overflow = true; flags |= G2S_DEV_OVERFLOW_A | G2S_DEV_WATCHDOG; break; }
-        // (the queue was written by this wave; lines of it this compute unit read for an earlier gap go)
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        const uint32_t* qc = gq + cur * QCAP;
-        uint32_t* qn = gq + (cur ^ 1u) * QCAP;
-        uint32_t nn = 0;
-        for (uint32_t e0 = 0; e0 < ne && !overflow; e0 += 64u) {
-          const bool mine = e0 + (uint32_t)lane < ne;
-          const uint32_t v = mine ? qc[e0 + (uint32_t)lane] : 0u;
-          uint32_t d = 0;
-          if (mine) {
-            uint32_t slot = a_hash(v), guard = 0;
-            while ((uint32_t)(tab[slot] >> 32) != v) {
-              if (++guard > AS) { stuck = true; break; }
-              slot = (slot + 1u) & (AS - 1u);
-            }
-            d = (uint32_t)tab[slot];
-          }
-          if (__ballot(stuck)) { overflow = true; flags |= G2S_DEV_OVERFLOW_A | G2S_DEV_WATCHDOG; break; }
-          uint4 rec = make_uint4(G2S_DEV_INVALID, G2S_DEV_INVALID, G2S_DEV_INVALID, G2S_DEV_INVALID);
-          uint32_t r = 0;
-          if (mine) {
-            const uint4* u = (const uint4*)(urec + (size_t)(v ^ 1u) * 8);
-            rec = u[0];
-            r = u[1].x;
-          }
-          const uint32_t steps = min(r, (uint32_t)gd.right_half - d);
-          const bool live = mine && d + steps < (uint32_t)gd.right_half;
-          if (!live) rec = make_uint4(G2S_DEV_INVALID, G2S_DEV_INVALID, G2S_DEV_INVALID, G2S_DEV_INVALID);
-          const uint32_t dchild = d + steps + 1u;
-#pragma unroll
-          for (int q = 0; q < 4; q++) {
-            const uint32_t w = q == 0 ? rec.x : q == 1 ? rec.y : q == 2 ? rec.z : rec.w;
-            const bool imp = relabel(w != G2S_DEV_INVALID && !overflow, w ^ 1u, dchild);
-            const uint64_t m = __ballot(imp);
-            if (imp) {
-              const uint32_t at = nn + (uint32_t)__popcll(m & below(lane));
-              if (at < QCAP) qn[at] = w ^ 1u;
-            }
-            nn += (uint32_t)__popcll(m);
-            // (at most EA + 64 of the AS slots are ever taken, so every probe ends)
-            if (nn > QCAP || nA > EA) { overflow = true; flags |= G2S_DEV_OVERFLOW_A | G2S_DEV_WHY_RS; }
-            if (__ballot(stuck)) { overflow = true; flags |= G2S_DEV_OVERFLOW_A | G2S_DEV_WATCHDOG; }
-          }
-        }
-        lds_sync();
-        cur ^= 1u;
-        ne = nn;
-      }
-    }
-    if (!overflow) {
-      // the entries, packed to the front of the table (in place: the write cursor never passes the read cursor)
-      uint32_t got = 0;
-      for (uint32_t c = 0; c < AS; c += 64u) {
-        const uint64_t e = tab[c + (uint32_t)lane];
-        const bool have = e != SEGX_EMPTY64;
-        const uint64_t m = __ballot(have);
-        if (have) tab[got + (uint32_t)__popcll(m & below(lane))] = e;
-        got += (uint32_t)__popcll(m);
-      }
-      lds_sync();
-      // entry -> k-mer index interval (lo << 32 | orientation << 31 | hi): one record load each
-      uint32_t acc_vis = 0, acc_xa = 0;
-      uint32_t* o = dbg ? dbg + (size_t)x * dbg_words : nullptr;
-#pragma unroll 2
-      for (uint32_t e0 = 0; e0 < nA; e0 += 64u) {
-        const uint32_t e = e0 + (uint32_t)lane;
-        const bool have = e < nA;
-        const uint64_t ent = have ? tab[e] : 0ull;
-        const uint32_t v = (uint32_t)(ent >> 32), label = (uint32_t)ent;
-        const uint32_t r = have ? urec[(size_t)(v ^ 1u) * 8 + 4] : 0u;
-        const uint32_t steps = have ? min(r, (uint32_t)gd.right_half - label) : 0u;
-        const uint32_t w0 = v ^ 1u, idx = w0 >> 1;
-        const uint32_t lo = (w0 & 1u) ? idx - steps : idx, hi = (w0 & 1u) ? idx : idx + steps;
-        if (have) {
-          tab[e] = ((uint64_t)lo << 32) | ((uint64_t)(v & 1u) << 31) | hi;
-          acc_vis += steps + 1u;
-          acc_xa += min(steps + 1u, (uint32_t)gd.right_half - label);
-          if (o && 9u + 2u * e < dbg_words) { o[8u + 2u * e] = v; o[9u + 2u * e] = label; }
-        }
-      }
-      nvis = wave_sum(acc_vis);
-      xa = wave_sum(acc_xa);
-      uint32_t n2 = 2;
-      while (n2 < nA) n2 <<= 1;
-      for (uint32_t i = nA + (uint32_t)lane; i < n2; i += 64u) tab[i] = SEGX_EMPTY64;
-      lds_sync();
-      lds_sort64(tab, n2, lane);
-      // Q7 in the right set, conservatively as above: an entry of each orientation with overlapping intervals
-      bool cross = false;
-      M = lds_merge_intervals(tab, nA, lane, &cross);
-      if (cross) flags |= G2S_DEV_Q7_A;
-      ivP = M ? 1u << (31 - __builtin_clz(M)) : 0u;
-    }
   }
-  // k-mer index x in the right set?  (wave-uniform; BIG: iv_find below)
+  if constexpr (!TWO) load_right_set();
+  // k-mer index x in the right set?  (wave-uniform)
   auto contains = [&](uint32_t x) -> bool {
     uint64_t m = 0;
 #pragma unroll
@@ -1029,476 +856,148 @@ __device__ __forceinline__ void seg_fill_one(uint32_t* lds, const SegArgs& A, co
     est = me ? (src ? ((uint32_t)dw | ((uint32_t)dw << 16)) : pstop) : est;
     ev |= 1ull << l;
   };
-  if constexpr (!BIG) {
-    if (!overflow) {
-      // left seeds: left.substr(d, k) enters at depth d with the value 1 ASSIGNED (:995-1015, :1082-1105)
-      const uint32_t sd = f_l;
-      const uint32_t s0 = rl(sd, 0);
-      // The usual flank is a stretch of ONE unitig: seed d is the d-th node after seed 0 and the walk
-      // from seed 0 stays unitig-internal for lmf steps.  Levels 0 .. lmf-1 are then that chain with
-      // count 1 (every state has the next seed as its only successor, and a seed's value is 1 anyway):
-      // one segment, and the seed at depth lmf as the only pending event, instead of lmf rounds.
-      bool chain = lmf >= 1 && s0 != G2S_DEV_INVALID && __ballot(lane <= lmf && sd != seg_node(s0, (uint32_t)lane)) == 0ull;
-      if (chain) chain = uni(urec[(size_t)s0 * 8 + 4]) >= (uint32_t)lmf;
-      // (a target k-mer inside the chain could make one of its states a sink or a traceback start: every
-      // state there is a source of its own, which only single-state segments express: the general path then)
-      if (chain) chain = __ballot(seg_pos(s0, (uint32_t)lmf, tg) >= 0) == 0ull;
-      if (chain) {
-        if (lane == 0) {
-          s_node[0] = s0; s_dl[0] = (uint32_t)lmf << 16; s_cnt[0] = 1u; s_p01[0] = s_p23[0] = 0xFFFFFFFFu; s_aux[0] = 0u;
-          s_t[0] = 0x7FFFu;  // (holds no target k-mer: checked above)
-        }
-        nseg = 1; gen = 1;
-        sb += (uint32_t)lmf;
-        xb += (uint32_t)lmf;
-        ev = efx = 1ull << lmf;
-        if (lane == lmf) { en = sd; ed = lmf; ec = 1; ep01 = 0xFFFF0000u; ep23 = 0xFFFFFFFFu; es = 0u; est = (uint32_t)lmf | ((uint32_t)lmf << 16); }
-      } else {
-        ev = efx = __ballot(sd != G2S_DEV_INVALID && lane <= D);
-        if ((ev >> lane) & 1ull) { en = sd; ed = lane; ec = 1; ep01 = ep23 = 0xFFFFFFFFu; es = 0u; est = (uint32_t)lane | ((uint32_t)lane << 16); }
+  if (!overflow) {
+    // left seeds: left.substr(d, k) enters at depth d with the value 1 ASSIGNED (:995-1015, :1082-1105)
+    const uint32_t sd = f_l;
+    const uint32_t s0 = rl(sd, 0);
+    // The usual flank is a stretch of ONE unitig: seed d is the d-th node after seed 0 and the walk
+    // from seed 0 stays unitig-internal for lmf steps.  Levels 0 .. lmf-1 are then that chain with
+    // count 1 (every state has the next seed as its only successor, and a seed's value is 1 anyway):
+    // one segment, and the seed at depth lmf as the only pending event, instead of lmf rounds.
+    bool chain = lmf >= 1 && s0 != G2S_DEV_INVALID && __ballot(lane <= lmf && sd != seg_node(s0, (uint32_t)lane)) == 0ull;
+    if (chain) chain = uni(urec[(size_t)s0 * 8 + 4]) >= (uint32_t)lmf;
+    // (a target k-mer inside the chain could make one of its states a sink or a traceback start: every
+    // state there is a source of its own, which only single-state segments express: the general path then)
+    if (chain) chain = __ballot(seg_pos(s0, (uint32_t)lmf, tg) >= 0) == 0ull;
+    if (chain) {
+      if (lane == 0) {
+        s_node[0] = s0; s_dl[0] = (uint32_t)lmf << 16; s_cnt[0] = 1u; s_p01[0] = s_p23[0] = 0xFFFFFFFFu; s_aux[0] = 0u;
+        s_t[0] = 0x7FFFu;  // (holds no target k-mer: checked above)
       }
+      nseg = 1; gen = 1;
+      sb += (uint32_t)lmf;
+      xb += (uint32_t)lmf;
+      ev = efx = 1ull << lmf;
+      if (lane == lmf) { en = sd; ed = lmf; ec = 1; ep01 = 0xFFFF0000u; ep23 = 0xFFFFFFFFu; es = 0u; est = (uint32_t)lmf | ((uint32_t)lmf << 16); }
+    } else {
+      ev = efx = __ballot(sd != G2S_DEV_INVALID && lane <= D);
+      if ((ev >> lane) & 1ull) { en = sd; ed = lane; ec = 1; ep01 = ep23 = 0xFFFFFFFFu; es = 0u; est = (uint32_t)lane | ((uint32_t)lane << 16); }
     }
-    // (two waves: the rounds in two stretches — up to the round that first needs the right set, and from there on — so
-    // that the 21 registers it lives in change between two loops, not inside one: with take_right_set() in the loop the
-    // compiler copied them at the head and at the end of EVERY round, 40-odd moves of a round's ~800 instructions)
-    for (int stretch = 0; stretch < (TWO ? 2 : 1); stretch++) {
-    bool want_rs = false;
-    while (ev && !overflow) {
-      SEG_PROF_T(0);
-      if (((ev >> lane) & 1ull) && es == 0u) {  // one round trip for all events created last round
-        if (ed < lmf) { es = 1u; erec = *(const uint4*)(succ + (size_t)en * 4); }  // above the flank: one state, leaves at once
-        else { const uint4* u = (const uint4*)(urec + (size_t)en * 8); erec = u[0]; es = u[1].x + 1u; }
+  }
+  // (two waves: the rounds in two stretches — up to the round that first needs the right set, and from there on — so
+  // that the 21 registers it lives in change between two loops, not inside one: with take_right_set() in the loop the
+  // compiler copied them at the head and at the end of EVERY round, 40-odd moves of a round's ~800 instructions)
+  for (int stretch = 0; stretch < (TWO ? 2 : 1); stretch++) {
+  bool want_rs = false;
+  while (ev && !overflow) {
+    SEG_PROF_T(0);
+    if (((ev >> lane) & 1ull) && es == 0u) {  // one round trip for all events created last round
+      if (ed < lmf) { es = 1u; erec = *(const uint4*)(succ + (size_t)en * 4); }  // above the flank: one state, leaves at once
+      else { const uint4* u = (const uint4*)(urec + (size_t)en * 8); erec = u[0]; es = u[1].x + 1u; }
+    }
+    SEG_PROF_WAIT();
+    SEG_PROF_T(1);
+    // ---- which events are final: depth below the horizon
+    const bool valid = (ev >> lane) & 1ull;
+    const uint32_t H = wave_min(valid ? (uint32_t)ed + es : SEG_INF);
+    const uint64_t sel = ev & __ballot((uint32_t)ed < H);
+    const uint32_t nsel = (uint32_t)__popcll(sel);
+    if (nseg + nsel > G2S_SEG_CAP) { overflow = true; flags |= G2S_DEV_OVERFLOW_B | G2S_DEV_WHY_LOG; break; }
+    const bool mine = (sel >> lane) & 1ull;
+    const uint32_t cnt = ((efx >> lane) & 1ull) ? 1u : ec;
+    const uint32_t lcap = min(es, (uint32_t)(D - ed + 1));
+    uint32_t elen = lcap;
+    const uint32_t esid = nseg + (uint32_t)__popcll(sel & below(lane));
+    if constexpr (TWO) {  // a state or a child at or beyond the depth the pruning rule starts at: the right set now
+      // (nothing of this round has been written yet: it starts again behind the barrier)
+      if (!have_rs && (sel & __ballot(ed + (int)lcap >= gd.prune_from))) { want_rs = true; break; }
+    }
+    SEG_PROF_T(2);
+    // ---- their lengths under the pruning rule, their target hits (one segment at a time, wave-uniform)
+    for (uint64_t m = sel; m; m &= m - 1) {
+      const int l = __builtin_ctzll(m);
+      const uint32_t node = rl(en, l), lc = rl(lcap, l), c = rl(cnt, l), stl = rl(est, l);
+      const int depth = (int)rl((uint32_t)ed, l);
+      uint32_t L = lc;
+      if (lc > 1u && depth + (int)lc - 1 >= gd.prune_from) {  // interior states are entered under :1050
+        const uint32_t t1 = (uint32_t)max(1, gd.prune_from - depth);
+        const uint32_t idx0 = node >> 1;
+        if (!(node & 1u)) L = covered_up(idx0 + t1, idx0 + lc - 1u) - idx0 + 1u;
+        else L = idx0 - covered_down(idx0 - t1, idx0 - (lc - 1u)) + 1u;
+        if (lane == l) elen = L;
       }
-      SEG_PROF_WAIT();
-      SEG_PROF_T(1);
-      // ---- which events are final: depth below the horizon
-      const bool valid = (ev >> lane) & 1ull;
-      const uint32_t H = wave_min(valid ? (uint32_t)ed + es : SEG_INF);
-      const uint64_t sel = ev & __ballot((uint32_t)ed < H);
-      const uint32_t nsel = (uint32_t)__popcll(sel);
-      if (nseg + nsel > G2S_SEG_CAP) { overflow = true; flags |= G2S_DEV_OVERFLOW_B | G2S_DEV_WHY_LOG; break; }
-      const bool mine = (sel >> lane) & 1ull;
-      const uint32_t cnt = ((efx >> lane) & 1ull) ? 1u : ec;
-      const uint32_t lcap = min(es, (uint32_t)(D - ed + 1));
-      uint32_t elen = lcap;
-      const uint32_t esid = nseg + (uint32_t)__popcll(sel & below(lane));
-      if constexpr (TWO) {  // a state or a child at or beyond the depth the pruning rule starts at: the right set now
-        // (nothing of this round has been written yet: it starts again behind the barrier)
-        if (!have_rs && (sel & __ballot(ed + (int)lcap >= gd.prune_from))) { want_rs = true; break; }
-      }
-      SEG_PROF_T(2);
-      // ---- their lengths under the pruning rule, their target hits (one segment at a time, wave-uniform)
-      for (uint64_t m = sel; m; m &= m - 1) {
-        const int l = __builtin_ctzll(m);
-        const uint32_t node = rl(en, l), lc = rl(lcap, l), c = rl(cnt, l), stl = rl(est, l);
-        const int depth = (int)rl((uint32_t)ed, l);
-        uint32_t L = lc;
-        if (lc > 1u && depth + (int)lc - 1 >= gd.prune_from) {  // interior states are entered under :1050
-          const uint32_t t1 = (uint32_t)max(1, gd.prune_from - depth);
-          const uint32_t idx0 = node >> 1;
-          if (!(node & 1u)) L = covered_up(idx0 + t1, idx0 + lc - 1u) - idx0 + 1u;
-          else L = idx0 - covered_down(idx0 - t1, idx0 - (lc - 1u)) + 1u;
-          if (lane == l) elen = L;
-        }
-        sb += L;
-        xb += min(L, (uint32_t)(D - depth));
-        (void)c; (void)stl;  // (the target hits of the segments are looked for behind the search, all segments at once)
-      }
-      if (mine) {
-        s_node[esid] = en;
-        s_dl[esid] = (uint32_t)ed | (elen << 16);
-        s_cnt[esid] = cnt;
-        s_p01[esid] = ep01;
-        s_p23[esid] = ep23;
-        s_aux[esid] = gen;
-        s_t[esid] = est;  // (stop depths of the entry, until the hits have been looked for: phase D1 fills s_t later)
-      }
-      nseg += nsel;
-      SEG_PROF_T(3);
-      // ---- segments that reached the end of their stretch leave through the successor table
-      const uint64_t exits_m = sel & ballot_and(elen == es, ed + (int)elen - 1 < D);
-      const uint4 rec = erec;  // elen == lcap == es: the walk reached the node the record belongs to
-      const uint32_t xd = (uint32_t)ed + elen;  // depth of the children
-      const uint32_t est_sel = est;             // (add_event below may reuse a selected lane for a new event)
-      ev &= ~sel;
-      efx &= ~sel;
-      ed = mine ? SEG_NOEV : ed;  // (the selected events' lanes are free: they match no child)
-      // (successor slot by successor slot, only the lanes whose slot holds a node: the order in which the
-      // children arrive does not matter — counts add up, the host puts parents into GATB order)
+      sb += L;
+      xb += min(L, (uint32_t)(D - depth));
+      (void)c; (void)stl;  // (the target hits of the segments are looked for behind the search, all segments at once)
+    }
+    if (mine) {
+      s_node[esid] = en;
+      s_dl[esid] = (uint32_t)ed | (elen << 16);
+      s_cnt[esid] = cnt;
+      s_p01[esid] = ep01;
+      s_p23[esid] = ep23;
+      s_aux[esid] = gen;
+      s_t[esid] = est;  // (stop depths of the entry, until the hits have been looked for: phase D1 fills s_t later)
+    }
+    nseg += nsel;
+    SEG_PROF_T(3);
+    // ---- segments that reached the end of their stretch leave through the successor table
+    const uint64_t exits_m = sel & ballot_and(elen == es, ed + (int)elen - 1 < D);
+    const uint4 rec = erec;  // elen == lcap == es: the walk reached the node the record belongs to
+    const uint32_t xd = (uint32_t)ed + elen;  // depth of the children
+    const uint32_t est_sel = est;             // (add_event below may reuse a selected lane for a new event)
+    ev &= ~sel;
+    efx &= ~sel;
+    ed = mine ? SEG_NOEV : ed;  // (the selected events' lanes are free: they match no child)
+    // (successor slot by successor slot, only the lanes whose slot holds a node: the order in which the
+    // children arrive does not matter — counts add up, the host puts parents into GATB order)
 #pragma unroll
-      for (int q = 0; q < 4; q++) {
-        const uint32_t wv = q == 0 ? rec.x : q == 1 ? rec.y : q == 2 ? rec.z : rec.w;
-        for (uint64_t m = exits_m & __ballot(wv != G2S_DEV_INVALID); m && !overflow; m &= m - 1) {
-          const int l = __builtin_ctzll(m);
-          const uint32_t w = rl(wv, l);
-          const int dw = (int)rl(xd, l);
-          if (dw < gd.prune_from || contains(w >> 1)) add_event(w, dw, rl(cnt, l), rl(esid, l), rl(est_sel, l));  // :1050
-        }
-      }
-      SEG_PROF_T(4);
-      SEG_PROF_ACC();
-      gen++;
-    }
-    if (!want_rs) break;
-    take_right_set();
-    }
-    // ---- phase C's hits (:1107-1159): target k-mer j at position t of a segment is a hit at depth + t.  Behind the
-    // search, lane = segment and a loop over the <= 32 targets: inside the rounds the same look — one selected event
-    // at a time, wave-uniform — was a tenth of a round.  A hit (error, j) exists at most once above and once below its
-    // base depth (a DP state is in one segment), so the smallest key and its two counts are a reduction.
-    if (!overflow) {
-      lds_sync();
-      uint32_t mybest = SEG_INF, myc1 = 0, myc2 = 0, mys1 = 0x7FFFu, mys2 = 0x7FFFu;
-      for (uint32_t b0 = 0; b0 < nseg; b0 += 64u) {
-        const uint32_t b = b0 + (uint32_t)lane;
-        const bool hb = b < nseg;
-        const uint32_t node = hb ? s_node[b] : 0u, dl = hb ? s_dl[b] : 0u, c = hb ? s_cnt[b] : 0u, st = hb ? s_t[b] : 0x7FFFu;
-        const uint32_t L = dl >> 16;
-        const int depth = (int)(dl & 0xFFFFu);
-        for (int j = 0; j <= rmf && j < 32; j++) {
-          const int t = hb ? seg_pos(node, L, rl(tg, j)) : -1;
-          if (t < 0) continue;
-          const int td = depth + t, base = gd.g + lmf + j;
-          const int err = td >= base ? td - base : base - td;
-          if (err > gd.e) continue;
-          const uint32_t key = ((uint32_t)(err + gd.g + lmf + rmf) << 6) | (uint32_t)j;
-          if (key < mybest) { mybest = key; myc1 = 0; myc2 = 0; }
-          if (key == mybest) { if (td >= base) { myc1 = c; mys1 = st; } else { myc2 = c; mys2 = st; } }
-        }
-      }
-      best = wave_min(mybest);
-      if (best != SEG_INF) {
-        const uint64_t m1 = __ballot(mybest == best && myc1 != 0u), m2 = __ballot(mybest == best && myc2 != 0u);
-        if (m1) { c1 = rl(myc1, __builtin_ctzll(m1)); s1 = rl(mys1, __builtin_ctzll(m1)); }
-        if (m2) { c2 = rl(myc2, __builtin_ctzll(m2)); s2 = rl(mys2, __builtin_ctzll(m2)); }
+    for (int q = 0; q < 4; q++) {
+      const uint32_t wv = q == 0 ? rec.x : q == 1 ? rec.y : q == 2 ? rec.z : rec.w;
+      for (uint64_t m = exits_m & __ballot(wv != G2S_DEV_INVALID); m && !overflow; m &= m - 1) {
+        const int l = __builtin_ctzll(m);
+        const uint32_t w = rl(wv, l);
+        const int dw = (int)rl(xd, l);
+        if (dw < gd.prune_from || contains(w >> 1)) add_event(w, dw, rl(cnt, l), rl(esid, l), rl(est_sel, l));  // :1050
       }
     }
-  } else {
-    // ---- (BIG) the same search with the pending events in LDS.  Lane = event only while a chunk of them is
-    // looked at; an event lives in a SLOT (fields below), found by (node, depth) through an open-addressing
-    // table ht (node << 32 | depth << 16 | slot).  Children of a whole chunk of final events are inserted
-    // by all lanes at once: claim by compare-and-swap, counts merged with atomic adds (at most four
-    // parents of at most 2^30 - 1 each: no wrap; clamped when read), stop depths with atomic min / max.
-    // A selected event leaves a tombstone behind (no later proposal can carry its key: all have depths
-    // at or above the horizon); the table is rebuilt from the pending list when tombstones pile up.
-    // LDS (words): iv 2 EA | slots: node, depth|fixed<<15|parents<<16, count, p01, p23, stop lo, stop hi,
-    //   states to the unitig's end, table position [PE each], exit record [4 PE] | ht [2 HS] |
-    //   pending list x 2, free slots, new slots, final events of the round [PE each]
-    constexpr uint32_t PE = G2S_SEGX_PE, HS = G2S_SEGX_HS;
-    uint32_t* e_node = lds + 2u * G2S_SEGX_EA;
-    uint32_t* e_dp = e_node + PE;
-    uint32_t* e_cnt = e_dp + PE;
-    uint32_t* e_p01 = e_cnt + PE;
-    uint32_t* e_p23 = e_p01 + PE;
-    uint32_t* e_slo = e_p23 + PE;
-    uint32_t* e_shi = e_slo + PE;
-    uint32_t* e_es = e_shi + PE;
-    uint32_t* e_hpos = e_es + PE;
-    uint4* e_rec = (uint4*)(e_hpos + PE);
-    uint64_t* ht = (uint64_t*)(e_rec + PE);
-    uint32_t* plist = (uint32_t*)(ht + HS);
-    uint32_t* fstack = plist + 2u * PE;
-    uint32_t* newl = fstack + PE;
-    uint32_t* sell = newl + PE;
-    static_assert(2u * G2S_SEGX_EA + 9u * PE + 4u * PE + 2u * HS + 5u * PE + 64u <= SEGX_LDS_WORDS, "LDS layout of the large variant");
-    uint32_t np = 0, npn = 0, nnew = 0, nfree = PE, ntomb = 0, pcur = 0;
-    uint32_t acc_sb = 0, acc_xb = 0;
-    bool stuckb = false;  // (per lane) a probe ran past its bound
-    for (uint32_t i = (uint32_t)lane; i < HS; i += 64u) ht[i] = SEGX_EMPTY64;
-    for (uint32_t i = (uint32_t)lane; i < PE; i += 64u) fstack[i] = PE - 1u - i;  // slot 0 on top
+    SEG_PROF_T(4);
+    SEG_PROF_ACC();
+    gen++;
+  }
+  if (!want_rs) break;
+  take_right_set();
+  }
+  // ---- phase C's hits (:1107-1159): target k-mer j at position t of a segment is a hit at depth + t.  Behind the
+  // search, lane = segment and a loop over the <= 32 targets: inside the rounds the same look — one selected event
+  // at a time, wave-uniform — was a tenth of a round.  A hit (error, j) exists at most once above and once below its
+  // base depth (a DP state is in one segment), so the smallest key and its two counts are a reduction.
+  if (!overflow) {
     lds_sync();
-    auto e_hash = [&](uint32_t w, uint32_t dw) -> uint32_t {
-      uint32_t h = w * 0x9E3779B1u ^ dw * 0x85EBCA6Bu;
-      h ^= h >> 15; h *= 0x2C1B3C6Du; h ^= h >> 12;
-      return h & (HS - 1u);
-    };
-    // index of the last interval that begins at or before k-mer index q (-1: none), per lane
-    auto iv_find = [&](uint32_t q) -> int {
-      uint32_t pos = 0;
-      for (uint32_t st = ivP; st; st >>= 1) {
-        const uint32_t pp = pos + st;
-        if (pp <= M && ivw[2u * (pp - 1u) + 1u] <= q) pos = pp;
-      }
-      return (int)pos - 1;
-    };
-    // proposals of all lanes: event (w, dw) gains count c from segment par (0xFFFF: a seed, no parent)
-    auto ev_insert = [&](bool act, uint32_t w, uint32_t dw, uint32_t c, uint32_t par, uint32_t pslo, uint32_t pshi, bool fixed) {
-      const uint64_t am = __ballot(act);
-      const uint32_t na = (uint32_t)__popcll(am);
-      if (na == 0u) return;
-      if (nfree < na) { overflow = true; flags |= G2S_DEV_OVERFLOW_B | G2S_DEV_WHY_FRONTIER; return; }
-      uint32_t slot = 0;
-      if (act) slot = fstack[nfree - 1u - (uint32_t)__popcll(am & below(lane))];
-      nfree -= na;
-      bool src = false;
-      if (act && dw <= (uint32_t)lmf) { const uint32_t ls = l_seed[dw]; src = ls != G2S_DEV_INVALID && (w >> 1) == (ls >> 1); }  // :1270
-      const uint64_t kpart = ((uint64_t)w << 32) | ((uint64_t)dw << 16);
-      if (act) {  // the candidate slot is complete before it can be seen through the table
-        e_node[slot] = w;
-        e_dp[slot] = dw | (fixed ? 0x8000u : 0u) | (par != SEG_NOPAR ? 0x10000u : 0u);
-        e_cnt[slot] = c;
-        e_p01[slot] = 0xFFFF0000u | par;
-        e_p23[slot] = 0xFFFFFFFFu;
-        e_slo[slot] = src ? dw : pslo;
-        e_shi[slot] = src ? dw : pshi;
-        e_es[slot] = 0u;
-      }
-      bool fresh = false, merged = false;
-      uint32_t mslot = 0;
-      uint32_t pos = act ? e_hash(w, dw) : 0u;
-      int freepos = -1;
-      uint32_t guard = 0;
-      if (act) {  // among what was there before this call; the first free position of the probe sequence
-        while (true) {
-          if (++guard > 2u * HS) { stuckb = true; break; }
-          const uint64_t cc = ht[pos];
-          if (cc == SEGX_EMPTY64) break;
-          if (cc == SEGX_TOMB64) { if (freepos < 0) freepos = (int)pos; }
-          else if ((cc & ~0xFFFFull) == kpart) { merged = true; mslot = (uint32_t)cc & 0xFFFFu; break; }
-          pos = (pos + 1u) & (HS - 1u);
-        }
-        if (freepos >= 0) pos = (uint32_t)freepos;
-      }
-      __builtin_amdgcn_wave_barrier();
-      if (act && !merged && !stuckb) {  // claim it, or meet the lane that did with the same key
-        while (true) {
-          if (++guard > 8u * HS) { stuckb = true; break; }
-          const uint64_t cc = ht[pos];
-          if (cc == SEGX_EMPTY64 || cc == SEGX_TOMB64) {
-            const unsigned long long prev = atomicCAS((unsigned long long*)&ht[pos], (unsigned long long)cc, (unsigned long long)(kpart | slot));
-            if (prev == cc) { fresh = true; e_hpos[slot] = pos; break; }
-            continue;
-          }
-          if ((cc & ~0xFFFFull) == kpart) { merged = true; mslot = (uint32_t)cc & 0xFFFFu; break; }
-          pos = (pos + 1u) & (HS - 1u);
-        }
-      }
-      if (merged) {
-        atomicAdd(&e_cnt[mslot], c);
-        if (par != SEG_NOPAR) {
-          const uint32_t kk = (atomicAdd(&e_dp[mslot], 0x10000u) >> 16) & 0xFu;
-          if (kk == 0u) atomicAnd(&e_p01[mslot], 0xFFFF0000u | par);
-          else if (kk == 1u) atomicAnd(&e_p01[mslot], 0x0000FFFFu | (par << 16));
-          else if (kk == 2u) atomicAnd(&e_p23[mslot], 0xFFFF0000u | par);
-          else if (kk == 3u) atomicAnd(&e_p23[mslot], 0x0000FFFFu | (par << 16));
-        }
-        if (!src) { atomicMin(&e_slo[mslot], pslo); atomicMax(&e_shi[mslot], pshi); }
-      }
-      const uint64_t mm = __ballot(merged);
-      if (merged) fstack[nfree + (uint32_t)__popcll(mm & below(lane))] = slot;  // the candidate slot was not needed
-      nfree += (uint32_t)__popcll(mm);
-      const uint64_t fm = __ballot(fresh);
-      if (fresh) {
-        const uint32_t at = (uint32_t)__popcll(fm & below(lane));
-        plist[(pcur ^ 1u) * PE + npn + at] = slot;
-        newl[nnew + at] = slot;
-      }
-      npn += (uint32_t)__popcll(fm);
-      nnew += (uint32_t)__popcll(fm);
-      lds_sync();
-      // Q7: the other strand pending at this depth (looked up after the insertions of this call)
-      bool other = false;
-      if (fresh) {
-        const uint64_t okey = ((uint64_t)(w ^ 1u) << 32) | ((uint64_t)dw << 16);
-        uint32_t p2 = e_hash(w ^ 1u, dw), g2 = 0;
-        while (true) {
-          if (++g2 > 2u * HS) { stuckb = true; break; }
-          const uint64_t cc = ht[p2];
-          if (cc == SEGX_EMPTY64) break;
-          if (cc != SEGX_TOMB64 && (cc & ~0xFFFFull) == okey) { other = true; break; }
-          p2 = (p2 + 1u) & (HS - 1u);
-        }
-      }
-      if (__ballot(other)) flags |= G2S_DEV_Q7_B;
-      if (__ballot(stuckb)) { overflow = true; flags |= G2S_DEV_OVERFLOW_B | G2S_DEV_WATCHDOG; }
-    };
-    if (!overflow) {
-      // left seeds: left.substr(d, k) enters at depth d with the value 1 ASSIGNED (:995-1015, :1082-1105)
-      const uint32_t sd = lane <= lmf ? lseeds[lane] : G2S_DEV_INVALID;
-      const uint32_t s0 = rl(sd, 0);
-      bool chain = lmf >= 1 && s0 != G2S_DEV_INVALID && __ballot(lane <= lmf && sd != seg_node(s0, (uint32_t)lane)) == 0ull;
-      if (chain) chain = uni(urec[(size_t)s0 * 8 + 4]) >= (uint32_t)lmf;
-      if (chain) chain = __ballot(seg_pos(s0, (uint32_t)lmf, tg) >= 0) == 0ull;
-      if (chain) {  // (see above: the flank as one segment, the seed at depth lmf the only pending event)
-        if (lane == 0) {
-          s_node[0] = s0; s_dl[0] = (uint32_t)lmf << 16; s_cnt[0] = 1u; s_p01[0] = s_p23[0] = 0xFFFFFFFFu; s_gen[0] = 0u;
-        }
-        nseg = 1; gen = 1;
-        sb += (uint32_t)lmf;
-        xb += (uint32_t)lmf;
-        ev_insert(lane == lmf, sd, (uint32_t)lmf, 1u, 0u, (uint32_t)lmf, (uint32_t)lmf, true);
-      } else {
-        ev_insert(sd != G2S_DEV_INVALID && lane <= D, sd, (uint32_t)lane, 1u, SEG_NOPAR, (uint32_t)lane, (uint32_t)lane, true);
-      }
-      pcur ^= 1u; np = npn; npn = 0;
-    }
-    while (np > 0 && !overflow) {
-      SEG_PROF_T(0);
-      // ---- one round trip for all events created last round: states to the end of the unitig, exit record
-      for (uint32_t i0 = 0; i0 < nnew; i0 += 64u) {
-        if (i0 + (uint32_t)lane < nnew) {
-          const uint32_t slot = newl[i0 + (uint32_t)lane];
-          const uint32_t node = e_node[slot], dd = e_dp[slot] & 0x7FFFu;
-          if ((int)dd < lmf) { e_rec[slot] = *(const uint4*)(succ + (size_t)node * 4); e_es[slot] = 1u; }  // above the flank: one state
-          else { const uint4* u = (const uint4*)(urec + (size_t)node * 8); e_rec[slot] = u[0]; e_es[slot] = u[1].x + 1u; }
-        }
-      }
-      nnew = 0;
-      lds_sync();
-      SEG_PROF_WAIT();
-      SEG_PROF_T(1);
-      // ---- the horizon
-      const uint32_t* pl = plist + pcur * PE;
-      uint32_t hmin = SEG_INF;
-      for (uint32_t i0 = 0; i0 < np; i0 += 64u)
-        if (i0 + (uint32_t)lane < np) { const uint32_t slot = pl[i0 + (uint32_t)lane]; hmin = min(hmin, (e_dp[slot] & 0x7FFFu) + e_es[slot]); }
-      for (int o = 32; o > 0; o >>= 1) hmin = min(hmin, (uint32_t)__shfl_xor((int)hmin, o));
-      const uint32_t H = uni(hmin);
-      // ---- final events: gathered first (they are scattered over the pending list), then worked on in
-      // full chunks — every chunk below costs a few thousand cycles whatever the number of its events
-      uint32_t nsl = 0;
-      for (uint32_t i0 = 0; i0 < np; i0 += 64u) {
-        const bool have = i0 + (uint32_t)lane < np;
-        const uint32_t slot = have ? pl[i0 + (uint32_t)lane] : 0u;
-        const bool fin = have && (e_dp[slot] & 0x7FFFu) < H;
-        const uint64_t fm = __ballot(fin), km = __ballot(have && !fin);
-        if (fin) sell[nsl + (uint32_t)__popcll(fm & below(lane))] = slot;
-        if (have && !fin) plist[(pcur ^ 1u) * PE + npn + (uint32_t)__popcll(km & below(lane))] = slot;  // the others stay pending
-        nsl += (uint32_t)__popcll(fm);
-        npn += (uint32_t)__popcll(km);
-      }
-      lds_sync();
-      SEG_PROF_T(2);
-#ifdef G2S_SEG_PROFILE
-      unsigned long long prof_children = 0;
-#endif
-      for (uint32_t i0 = 0; i0 < nsl && !overflow; i0 += 64u) {
-        const bool mine = i0 + (uint32_t)lane < nsl;
-        const uint32_t slot = mine ? sell[i0 + (uint32_t)lane] : 0u;
-        const uint32_t dp = mine ? e_dp[slot] : 0u;
-        const int ed = (int)(dp & 0x7FFFu);
-        const uint64_t sel = __ballot(mine);
-        const uint32_t nsel = (uint32_t)__popcll(sel);
-        if (nseg + nsel > G2S_SEGX_CAP) { overflow = true; flags |= G2S_DEV_OVERFLOW_B | G2S_DEV_WHY_LOG; break; }
-        const uint32_t esid = nseg + (uint32_t)__popcll(sel & below(lane));
-        const uint32_t en = mine ? e_node[slot] : 0u, es = mine ? e_es[slot] : 1u;
-        const uint4 rec = mine ? e_rec[slot] : make_uint4(G2S_DEV_INVALID, G2S_DEV_INVALID, G2S_DEV_INVALID, G2S_DEV_INVALID);
-        const uint32_t cnt = (dp & 0x8000u) ? 1u : min(mine ? e_cnt[slot] : 0u, (uint32_t)G2S_DEV_MAX_PATHS);
-        const uint32_t slo = mine ? e_slo[slot] : 0x7FFFu, shi = mine ? e_shi[slot] : 0u;
-        const uint32_t p01 = mine ? e_p01[slot] : 0xFFFFFFFFu, p23 = mine ? e_p23[slot] : 0xFFFFFFFFu;
-        // the slots and table positions of the selected events are free again
-        if (mine) { ht[e_hpos[slot]] = SEGX_TOMB64; fstack[nfree + (uint32_t)__popcll(sel & below(lane))] = slot; }
-        nfree += nsel;
-        ntomb += nsel;
-        // ---- lengths under the pruning rule (:1050): every lane searches the intervals for its own event
-        const uint32_t lcap = min(es, (uint32_t)(D - ed + 1));
-        uint32_t L = lcap;
-        {
-          const bool pr = mine && lcap > 1u && ed + (int)lcap - 1 >= gd.prune_from;
-          const uint32_t t1 = (uint32_t)max(1, gd.prune_from - ed);
-          const uint32_t idx0 = en >> 1;
-          const uint32_t q0 = (en & 1u) ? idx0 - t1 : idx0 + t1;  // first state entered under the rule
-          const int f = iv_find(pr ? q0 : 0u);
-          if (pr) {
-            const bool in = f >= 0 && q0 <= ivw[2u * (uint32_t)f];
-            if (!(en & 1u)) {
-              const uint32_t y = in ? min(ivw[2u * (uint32_t)f], idx0 + lcap - 1u) : q0 - 1u;   // last covered index
-              L = y - idx0 + 1u;
-            } else {
-              const uint32_t y = in ? max(ivw[2u * (uint32_t)f + 1u], idx0 - (lcap - 1u)) : q0 + 1u;  // first covered index
-              L = idx0 - y + 1u;
-            }
-          }
-        }
-        if (mine) { acc_sb += L; acc_xb += min(L, (uint32_t)(D - ed)); }
-        // ---- phase C: target k-mer j at position t of a segment is a hit at depth + t
-        for (int j = 0; j <= rmf; j++) {
-          const uint32_t tj = rl(tg, j);
-          const int t = mine ? seg_pos(en, L, tj) : -1;
-          for (uint64_t hm = __ballot(t >= 0); hm; hm &= hm - 1) {
-            const int l = __builtin_ctzll(hm);
-            const int td = (int)rl((uint32_t)ed, l) + (int)rl((uint32_t)t, l), base = gd.g + lmf + j;
-            const int err = td >= base ? td - base : base - td;
-            if (err > gd.e) continue;
-            const uint32_t key = ((uint32_t)(err + gd.g + lmf + rmf) << 6) | (uint32_t)j;
-            const uint32_t c = rl(cnt, l), st = rl(slo, l) | (rl(shi, l) << 16);
-            if (key < best) { best = key; c1 = 0; c2 = 0; }
-            if (key == best) { if (td >= base) { c1 = c; s1 = st; } else { c2 = c; s2 = st; } }
-          }
-        }
-        if (mine) {
-          s_node[esid] = en;
-          s_dl[esid] = (uint32_t)ed | (L << 16);
-          s_cnt[esid] = cnt;
-          s_p01[esid] = p01;
-          s_p23[esid] = p23;
-          s_gen[esid] = gen;
-        }
-        nseg += nsel;
-        // ---- segments that reached the end of their stretch leave through the successor table
-        const bool exits = mine && L == es && ed + (int)L - 1 < D;
-        const uint32_t xd = (uint32_t)ed + L;  // depth of the children
-        // lane = (segment, successor slot): sixteen segments' children per pass, one search and one insertion each
-#ifdef G2S_SEG_PROFILE
-        const unsigned long long prof_c0 = __builtin_amdgcn_s_memtime();
-#endif
-        for (uint32_t g0 = 0; g0 < nsel && !overflow; g0 += 16u) {
-          const int from = (int)(g0 + ((uint32_t)lane >> 2));
-          const uint32_t q = (uint32_t)lane & 3u;
-          const uint32_t wx = (uint32_t)__shfl((int)rec.x, from), wy = (uint32_t)__shfl((int)rec.y, from);
-          const uint32_t wz = (uint32_t)__shfl((int)rec.z, from), ww = (uint32_t)__shfl((int)rec.w, from);
-          const uint32_t w = q == 0u ? wx : q == 1u ? wy : q == 2u ? wz : ww;
-          const bool ex = __shfl((int)exits, from) != 0;
-          const uint32_t xdl = (uint32_t)__shfl((int)xd, from), cl = (uint32_t)__shfl((int)cnt, from);
-          const uint32_t parl = (uint32_t)__shfl((int)esid, from);
-          const uint32_t slol = (uint32_t)__shfl((int)slo, from), shil = (uint32_t)__shfl((int)shi, from);
-          const int f = iv_find(w >> 1);
-          const bool inset = f >= 0 && (w >> 1) <= ivw[2u * (uint32_t)f];
-          const bool ok = ex && w != G2S_DEV_INVALID && ((int)xdl < gd.prune_from || inset);  // :1050
-          ev_insert(ok, w, xdl, cl, parl, slol, shil, false);
-        }
-#ifdef G2S_SEG_PROFILE
-        prof_children += __builtin_amdgcn_s_memtime() - prof_c0;
-#endif
-      }
-#ifdef G2S_SEG_PROFILE
-      // (sections: records wait | horizon + gather | lengths, hits, segment records | children)
-      prof_t[3] = __builtin_amdgcn_s_memtime() - prof_children;
-      prof_t[4] = prof_t[3] + prof_children;
-      SEG_PROF_ACC();
-#endif
-      pcur ^= 1u;
-      np = npn;
-      npn = 0;
-      gen++;
-      // ---- tombstones pile up: rebuild the table from the pending list
-      if (ntomb > HS / 4u && !overflow) {
-        for (uint32_t i = (uint32_t)lane; i < HS; i += 64u) ht[i] = SEGX_EMPTY64;
-        lds_sync();
-        const uint32_t* pn = plist + pcur * PE;
-        for (uint32_t i0 = 0; i0 < np; i0 += 64u) {
-          if (i0 + (uint32_t)lane < np) {
-            const uint32_t slot = pn[i0 + (uint32_t)lane];
-            const uint32_t w = e_node[slot], dw = e_dp[slot] & 0x7FFFu;
-            const uint64_t ent = ((uint64_t)w << 32) | ((uint64_t)dw << 16) | slot;
-            uint32_t pos = e_hash(w, dw), g3 = 0;
-            while (atomicCAS((unsigned long long*)&ht[pos], (unsigned long long)SEGX_EMPTY64, (unsigned long long)ent) != SEGX_EMPTY64) {
-              if (++g3 > 2u * HS) { stuckb = true; break; }
-              pos = (pos + 1u) & (HS - 1u);
-            }
-            e_hpos[slot] = pos;
-          }
-        }
-        ntomb = 0;
-        lds_sync();
-        if (__ballot(stuckb)) { overflow = true; flags |= G2S_DEV_OVERFLOW_B | G2S_DEV_WATCHDOG; }
+    uint32_t mybest = SEG_INF, myc1 = 0, myc2 = 0, mys1 = 0x7FFFu, mys2 = 0x7FFFu;
+    for (uint32_t b0 = 0; b0 < nseg; b0 += 64u) {
+      const uint32_t b = b0 + (uint32_t)lane;
+      const bool hb = b < nseg;
+      const uint32_t node = hb ? s_node[b] : 0u, dl = hb ? s_dl[b] : 0u, c = hb ? s_cnt[b] : 0u, st = hb ? s_t[b] : 0x7FFFu;
+      const uint32_t L = dl >> 16;
+      const int depth = (int)(dl & 0xFFFFu);
+      for (int j = 0; j <= rmf && j < 32; j++) {
+        const int t = hb ? seg_pos(node, L, rl(tg, j)) : -1;
+        if (t < 0) continue;
+        const int td = depth + t, base = gd.g + lmf + j;
+        const int err = td >= base ? td - base : base - td;
+        if (err > gd.e) continue;
+        const uint32_t key = ((uint32_t)(err + gd.g + lmf + rmf) << 6) | (uint32_t)j;
+        if (key < mybest) { mybest = key; myc1 = 0; myc2 = 0; }
+        if (key == mybest) { if (td >= base) { myc1 = c; mys1 = st; } else { myc2 = c; mys2 = st; } }
       }
     }
-    sb += wave_sum(acc_sb);
-    xb += wave_sum(acc_xb);
-    // (the segment arrays in the scratch are read back below; lines this compute unit read for an earlier gap go)
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    best = wave_min(mybest);
+    if (best != SEG_INF) {
+      const uint64_t m1 = __ballot(mybest == best && myc1 != 0u), m2 = __ballot(mybest == best && myc2 != 0u);
+      if (m1) { c1 = rl(myc1, __builtin_ctzll(m1)); s1 = rl(mys1, __builtin_ctzll(m1)); }
+      if (m2) { c2 = rl(myc2, __builtin_ctzll(m2)); s2 = rl(mys2, __builtin_ctzll(m2)); }
+    }
   }
   if (!have_rs) take_right_set();  // (the search ended before the pruning depth: wave 1 is met here)
   if (overflow && !(flags & G2S_DEV_OVERFLOW_A)) flags |= G2S_DEV_OVERFLOW_B;
@@ -1520,16 +1019,10 @@ __device__ __forceinline__ void seg_fill_one(uint32_t* lds, const SegArgs& A, co
   // of their tail — 130-265 k cycles at 230-310 segments, measured with the instrumented build
   // (profiles/r03_segprof_*.txt).  Almost no pair can meet: the two must share k-mers, i.e. overlap as index
   // intervals.  So the upward segments' index intervals are sorted and merged in LDS (the space of s_t, which
-  // phase D1 fills later; the large variant: the start of its LDS), a downward segment that touches none of them
-  // (the usual case) is done after one binary search, and only the few others are checked against every upward
-  // segment.  Lists of a few dozen segments keep the direct all-pairs pass.
-  if constexpr (BIG) {
-    if (!overflow && !(flags & G2S_DEV_Q7_B) && nseg > 1) {
-      bool f7 = false;
-      (void)seg_q7_sorted(s_node, s_dl, nseg, (uint64_t*)lds, G2S_SEGX_CAP, lane, &f7);
-      if (f7) flags |= G2S_DEV_Q7_B;
-    }
-  } else if constexpr (TWO) {
+  // phase D1 fills later), a downward segment that touches none of them (the usual case) is done after one binary
+  // search, and only the few others are checked against every upward segment.  Lists of a few dozen segments keep
+  // the direct all-pairs pass.
+  if constexpr (TWO) {
     // two waves: wave 1, idle since phase A, makes this check (in its own LDS region: the right set is in wave 0's
     // registers by now) while this wave goes on with phases C, D1 and D2; its verdict is collected where the gap's
     // flags are written for the last time (q7_collect)
@@ -1537,7 +1030,7 @@ __device__ __forceinline__ void seg_fill_one(uint32_t* lds, const SegArgs& A, co
     __syncthreads();
   }
   bool collected = false, segs_apart = false;  // no two segments share a k-mer
-  if constexpr (!BIG && !TWO) {
+  if constexpr (!TWO) {
     if (!overflow && !(flags & G2S_DEV_Q7_B) && nseg > 1) {
       bool f7 = false;
       // (one wave: the second verdict costs this wave what it saves on a few dozen segments; beyond, the sorted pass
@@ -1594,18 +1087,16 @@ __device__ __forceinline__ void seg_fill_one(uint32_t* lds, const SegArgs& A, co
     if (lane == 0) for (int pi = 0; pi < 4; pi++) o[dbg_words - 4u + pi] = prof_acc[pi];
     if (lane == 0 && !TWO) for (int pi = 0; pi < 4; pi++) o[dbg_words - 14u + pi] = prof_a[pi];
 #endif
-    if constexpr (!BIG) {  // (BIG: written while the entries were turned into intervals)
 #pragma unroll
-      for (int s = 0; s < G2S_SEG_ASETS; s++) {
-        const uint32_t e = (uint32_t)s * 64u + (uint32_t)lane;
-        if (e < nA && 8u + 2u * e + 1u < dbg_words) { o[8u + 2u * e] = an[s]; o[9u + 2u * e] = al[s]; }
-      }
+    for (int s = 0; s < G2S_SEG_ASETS; s++) {
+      const uint32_t e = (uint32_t)s * 64u + (uint32_t)lane;
+      if (e < nA && 8u + 2u * e + 1u < dbg_words) { o[8u + 2u * e] = an[s]; o[9u + 2u * e] = al[s]; }
     }
-    const uint32_t sb0 = 8u + 2u * (BIG ? G2S_SEGX_EA : 64u * G2S_SEG_ASETS);
+    const uint32_t sb0 = 8u + 2u * 64u * G2S_SEG_ASETS;
     for (uint32_t b = (uint32_t)lane; b < nseg; b += 64u)
       if (sb0 + 6u * b + 5u < dbg_words) {
         o[sb0 + 6u * b] = s_node[b]; o[sb0 + 6u * b + 1] = s_dl[b]; o[sb0 + 6u * b + 2] = s_cnt[b];
-        o[sb0 + 6u * b + 3] = s_p01[b]; o[sb0 + 6u * b + 4] = s_p23[b]; o[sb0 + 6u * b + 5] = BIG ? s_gen[b] : s_aux[b];
+        o[sb0 + 6u * b + 3] = s_p01[b]; o[sb0 + 6u * b + 4] = s_p23[b]; o[sb0 + 6u * b + 5] = s_aux[b];
       }
   }
   if (lane == 0) {
@@ -1633,10 +1124,6 @@ __device__ __forceinline__ void seg_fill_one(uint32_t* lds, const SegArgs& A, co
 
   // ---------------- phase D1: backward closure over the segments ---------------------------------
   SEG_PROF_TAIL(1);
-  if constexpr (BIG) {  // generations into LDS: s_aux collects the closure marks there
-    for (uint32_t b = (uint32_t)lane; b < nseg; b += 64u) s_aux[b] = s_gen[b];
-    lds_sync();
-  }
   const bool want_s = !skip_confident;
   const uint32_t sinknode = (want_s && gd.all_paths && rmf >= 1) ? rl(tg, rmf - 1) : G2S_DEV_INVALID;  // Q3/Q4
   const int lo_sink = max(0, lmf + gd.g - gd.e);  // :1196
@@ -1889,18 +1376,16 @@ __device__ __forceinline__ void seg_fill_one(uint32_t* lds, const SegArgs& A, co
   SegRec* edst = nullptr;
   uint32_t eslot = 0xFFFFFFFFu, eoff = 0xFFFFFFFFu;
   if (want_s && !analysed) nodes_to_host();  // (in front of the early item's release below, and of everything phase D3 hands over)
-  if constexpr (!BIG) {
-    if (A.early_items != nullptr && want_s && !analysed && nrec > 0u) {
-      unsigned long long slot = 0, so = 0;
-      if (lane == 0) {
-        slot = atomicAdd(&A.early_ctr[0], 1ull);
-        if (slot < (unsigned long long)A.early_cap_items) so = atomicAdd(&A.early_ctr[1], (unsigned long long)nrec);
-      }
-      slot = __shfl(slot, 0); so = __shfl(so, 0);
-      if (slot < (unsigned long long)A.early_cap_items) {
-        eslot = (uint32_t)slot;
-        if (so + nrec <= (unsigned long long)A.early_cap_segs) { eoff = (uint32_t)so; edst = A.early_segs + eoff; }  // (no room: the item says so)
-      }
+  if (A.early_items != nullptr && want_s && !analysed && nrec > 0u) {
+    unsigned long long slot = 0, so = 0;
+    if (lane == 0) {
+      slot = atomicAdd(&A.early_ctr[0], 1ull);
+      if (slot < (unsigned long long)A.early_cap_items) so = atomicAdd(&A.early_ctr[1], (unsigned long long)nrec);
+    }
+    slot = __shfl(slot, 0); so = __shfl(so, 0);
+    if (slot < (unsigned long long)A.early_cap_items) {
+      eslot = (uint32_t)slot;
+      if (so + nrec <= (unsigned long long)A.early_cap_segs) { eoff = (uint32_t)so; edst = A.early_segs + eoff; }  // (no room: the item says so)
     }
   }
   {
@@ -2012,20 +1497,18 @@ __device__ __forceinline__ void seg_fill_one(uint32_t* lds, const SegArgs& A, co
   }
 #endif
   q7_collect();
-  if constexpr (!BIG) {
-    if (eslot != 0xFFFFFFFFu && lane == 0) {  // the early item: the gap's finished record, then what says it is complete
-      if (edst) {
-        static_assert(sizeof(GapOut) % 16 == 0, "GapOut is copied in 16-byte words");
-        __threadfence();  // (the record's words above: read back below)
-        const uint4* gs = (const uint4*)go;
-        uint4* gd4 = (uint4*)&A.early_outs[eslot];
-        for (uint32_t q = 0; q < sizeof(GapOut) / 16u; q++) gd4[q] = gs[q];
-      }
-      uint32_t* it = A.early_items + 8u * (size_t)eslot;
-      it[0] = gi; it[1] = edst ? nrec : 0u; it[2] = eoff; it[3] = 0u;
-      __threadfence_system();
-      __hip_atomic_store(&it[4], 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+  if (eslot != 0xFFFFFFFFu && lane == 0) {  // the early item: the gap's finished record, then what says it is complete
+    if (edst) {
+      static_assert(sizeof(GapOut) % 16 == 0, "GapOut is copied in 16-byte words");
+      __threadfence();  // (the record's words above: read back below)
+      const uint4* gs = (const uint4*)go;
+      uint4* gd4 = (uint4*)&A.early_outs[eslot];
+      for (uint32_t q = 0; q < sizeof(GapOut) / 16u; q++) gd4[q] = gs[q];
     }
+    uint32_t* it = A.early_items + 8u * (size_t)eslot;
+    it[0] = gi; it[1] = edst ? nrec : 0u; it[2] = eoff; it[3] = 0u;
+    __threadfence_system();
+    __hip_atomic_store(&it[4], 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
   }
   // ---------------- the traceback of a gap whose path is its only one, here (round 6) -----------------------------
   // :1437-1522 draws rand() for the path length and at every traced base, but what a traceback WRITES depends on the
@@ -2038,237 +1521,235 @@ __device__ __forceinline__ void seg_fill_one(uint32_t* lds, const SegArgs& A, co
   // of the trace kernel finds G2S_DEVA_TRACED and leaves.  Everything here follows g2s_d3_trace step by step (the walk
   // along the parents, the safe bit of every base, lower case = not safe and k or more below the nearest safe base
   // above, :1466-1468); anything out of the ordinary leaves the gap to that kernel.
-  if constexpr (!BIG) {
-    const bool no_over = sb <= A.tr_max_states && nvis <= A.tr_max_states;  // (else the -max-mem verdict: phase D3's)
-    const uint32_t sa_w = c1 > 0 ? s1 : s2;
-    // (round 6, second step: a traceback that HAS choices is written here too — as a GUESS: the first path length, the
-    // first parent at every choice — with a copy of text and record in device memory.  The bench's genome has a second
-    // haplotype every ~500 bp: nine tracebacks in ten cross a bubble, but the two ways through one differ in a base or
-    // two.  Phase D3's trace kernel still traces such a gap for real, compares 64 bases at a time with what was guessed,
-    // and sends through the link only what differs: G2S_DEVA_SPEC.)
-    const bool sure = !choice && n_len == 1 && (sa_w & 0xFFFFu) == (sa_w >> 16);
-    bool may_guess = A.tr_spec_text != nullptr;
-    if constexpr (TWO) {
-      if (may_guess && A.tr_guess_until != 0u) may_guess = uni(guess_order) < A.tr_guess_until;  // (asked at the head of the tail)
-    } else {
-      // (a chip-filling list: its launch ends with its slowest gaps too — a few dozen of 10 000, whose searches took several
-      // times the mean: their guesses, 20-40 k cycles each, would be the launch's last; the trace kernel has them.
-      // Config 3: g2s_fill_seg 0.317 -> 0.313 ms)
-      if (may_guess && cyc2 - cyc0 > (unsigned long long)G2S_GUESS_LATE_CYCLES_LONG) may_guess = false;
+  const bool no_over = sb <= A.tr_max_states && nvis <= A.tr_max_states;  // (else the -max-mem verdict: phase D3's)
+  const uint32_t sa_w = c1 > 0 ? s1 : s2;
+  // (round 6, second step: a traceback that HAS choices is written here too — as a GUESS: the first path length, the
+  // first parent at every choice — with a copy of text and record in device memory.  The bench's genome has a second
+  // haplotype every ~500 bp: nine tracebacks in ten cross a bubble, but the two ways through one differ in a base or
+  // two.  Phase D3's trace kernel still traces such a gap for real, compares 64 bases at a time with what was guessed,
+  // and sends through the link only what differs: G2S_DEVA_SPEC.)
+  const bool sure = !choice && n_len == 1 && (sa_w & 0xFFFFu) == (sa_w >> 16);
+  bool may_guess = A.tr_spec_text != nullptr;
+  if constexpr (TWO) {
+    if (may_guess && A.tr_guess_until != 0u) may_guess = uni(guess_order) < A.tr_guess_until;  // (asked at the head of the tail)
+  } else {
+    // (a chip-filling list: its launch ends with its slowest gaps too — a few dozen of 10 000, whose searches took several
+    // times the mean: their guesses, 20-40 k cycles each, would be the launch's last; the trace kernel has them.
+    // Config 3: g2s_fill_seg 0.317 -> 0.313 ms)
+    if (may_guess && cyc2 - cyc0 > (unsigned long long)G2S_GUESS_LATE_CYCLES_LONG) may_guess = false;
+  }
+  if (A.tr_results != nullptr && (analysed || !want_s) && (sure || may_guess) && start_b0 != SEG_NOPAR && no_over &&
+      gd.rlog_cap == 0u /* no skip rule on this gap */ && len0 >= 1 && len0 <= 4096 && nrec <= 256u) {
+    const int len = len0, k = A.tr_k;
+    uint2* hop = (uint2*)s_cnt;           // by hop: the depth at which it is entered | the segment | entry state << 16
+    unsigned char* cb = (unsigned char*)s_p23;  // by fill-buffer index: safe bit, then the character (s_p23 and s_aux: 4 096 bytes)
+    lds_sync();
+    // (i) the chain of segments: from the start along the (first) parent to a source.  As in g2s_d3_trace: what the
+    // walk needs of a segment — the parent it goes on to, its emitted id (for the chain's hash), whether it is a source
+    // or has no way on — is packed into ONE word per segment by all lanes first, so that the walk itself, a chain of
+    // dependent steps on one wave, reads one LDS word a segment (with five reads and the tests a step it was 400
+    // cycles a segment, 10 k cycles of a guess); then all lanes check that the hops' depths follow each other.
+    uint32_t* pk2 = s_p23;  // parent | emitted id << 16 | source << 30 | no way on << 31   (s_p23: free until the characters go there)
+    for (uint32_t b0 = 0; b0 < nseg; b0 += 64u) {
+      const uint32_t b = b0 + (uint32_t)lane;
+      if (b >= nseg) continue;
+      const uint32_t dl = s_dl[b], v0 = s_node[b], par = s_p01[b] & 0xFFFFu;
+      const int d0 = (int)(dl & 0xFFFFu);
+      const uint32_t ls = d0 <= lmf ? l_seed[d0] : G2S_DEV_INVALID;
+      const bool source = ls != G2S_DEV_INVALID && (v0 >> 1) == (ls >> 1);  // :1455-1462
+      const bool stuck = !source && (d0 < 1 || par == SEG_NOPAR || par >= nseg);  // (:1493-1510: the trace kernel's, and the host's)
+      pk2[b] = (par & 0xFFFFu) | ((s_aux[b] & 0x3FFu) << 16) | (source ? 0x40000000u : 0u) | (stuck ? 0x80000000u : 0u);
     }
-    if (A.tr_results != nullptr && (analysed || !want_s) && (sure || may_guess) && start_b0 != SEG_NOPAR && no_over &&
-        gd.rlog_cap == 0u /* no skip rule on this gap */ && len0 >= 1 && len0 <= 4096 && nrec <= 256u) {
-      const int len = len0, k = A.tr_k;
-      uint2* hop = (uint2*)s_cnt;           // by hop: the depth at which it is entered | the segment | entry state << 16
-      unsigned char* cb = (unsigned char*)s_p23;  // by fill-buffer index: safe bit, then the character (s_p23 and s_aux: 4 096 bytes)
-      lds_sync();
-      // (i) the chain of segments: from the start along the (first) parent to a source.  As in g2s_d3_trace: what the
-      // walk needs of a segment — the parent it goes on to, its emitted id (for the chain's hash), whether it is a source
-      // or has no way on — is packed into ONE word per segment by all lanes first, so that the walk itself, a chain of
-      // dependent steps on one wave, reads one LDS word a segment (with five reads and the tests a step it was 400
-      // cycles a segment, 10 k cycles of a guess); then all lanes check that the hops' depths follow each other.
-      uint32_t* pk2 = s_p23;  // parent | emitted id << 16 | source << 30 | no way on << 31   (s_p23: free until the characters go there)
-      for (uint32_t b0 = 0; b0 < nseg; b0 += 64u) {
-        const uint32_t b = b0 + (uint32_t)lane;
-        if (b >= nseg) continue;
-        const uint32_t dl = s_dl[b], v0 = s_node[b], par = s_p01[b] & 0xFFFFu;
+    lds_sync();
+    bool bad = false;
+    int nh = 0, d_end = -1;
+    unsigned long long chain_hash = 14695981039346656037ull;  // (of the emitted ids of the segments entered, in order: the trace kernel's walk makes the same)
+    {
+      uint32_t si = start_b0, w = 0u;
+      for (;;) {
+        if (nh >= 256) { bad = true; break; }
+        w = uni(pk2[si]);
+        chain_hash = (chain_hash ^ (unsigned long long)((w >> 16) & 0x3FFu)) * 1099511628211ull;
+        if (lane == 0) hop[nh].y = si;
+        nh++;
+        if (w & 0xC0000000u) break;
+        si = w & 0xFFFFu;
+      }
+      if (!bad && !(w & 0x40000000u)) bad = true;
+    }
+    lds_sync();
+    // (ii) all lanes, a hop each: the walk enters the first segment at the start's state and every other at its last
+    // closure state, and steps from a segment's first state to the depth below: the depth at which hop h is entered is
+    // len less the states passed before it — a scan — and has to be the segment's own depth at that state
+    {
+      int carry = 0;
+      for (int h0 = 0; !bad && h0 < nh; h0 += 64) {
+        const int h = h0 + lane;
+        const bool in = h < nh;
+        const uint32_t sq = in ? hop[h].y : 0u;
+        const uint32_t dl = in ? s_dl[sq] : 0u, st = in ? s_t[sq] : 0x7FFF7FFFu;
         const int d0 = (int)(dl & 0xFFFFu);
-        const uint32_t ls = d0 <= lmf ? l_seed[d0] : G2S_DEV_INVALID;
-        const bool source = ls != G2S_DEV_INVALID && (v0 >> 1) == (ls >> 1);  // :1455-1462
-        const bool stuck = !source && (d0 < 1 || par == SEG_NOPAR || par >= nseg);  // (:1493-1510: the trace kernel's, and the host's)
-        pk2[b] = (par & 0xFFFFu) | ((s_aux[b] & 0x3FFu) << 16) | (source ? 0x40000000u : 0u) | (stuck ? 0x80000000u : 0u);
+        const int t = h == 0 ? (int)start_t0 : max(dec15(st), dec15(st >> 16));  // (a child in the closure puts the whole parent there)
+        const int inc = in ? t + 1 : 0;
+        const int incl = (int)wave_scan((uint32_t)inc, lane);
+        const int at = len - carry - (incl - inc);
+        if (__ballot(in && (t < 0 || d0 + t != at)) != 0ull) { bad = true; break; }
+        if (in) hop[h] = make_uint2((uint32_t)at, sq | ((uint32_t)t << 16));
+        if (__ballot(in && h + 1 == nh)) d_end = (int)rl((uint32_t)d0, (nh - 1) & 63);
+        carry += (int)rl((uint32_t)incl, 63);
       }
-      lds_sync();
-      bool bad = false;
-      int nh = 0, d_end = -1;
-      unsigned long long chain_hash = 14695981039346656037ull;  // (of the emitted ids of the segments entered, in order: the trace kernel's walk makes the same)
-      {
-        uint32_t si = start_b0, w = 0u;
-        for (;;) {
-          if (nh >= 256) { bad = true; break; }
-          w = uni(pk2[si]);
-          chain_hash = (chain_hash ^ (unsigned long long)((w >> 16) & 0x3FFu)) * 1099511628211ull;
-          if (lane == 0) hop[nh].y = si;
-          nh++;
-          if (w & 0xC0000000u) break;
-          si = w & 0xFFFFu;
-        }
-        if (!bad && !(w & 0x40000000u)) bad = true;
-      }
-      lds_sync();
-      // (ii) all lanes, a hop each: the walk enters the first segment at the start's state and every other at its last
-      // closure state, and steps from a segment's first state to the depth below: the depth at which hop h is entered is
-      // len less the states passed before it — a scan — and has to be the segment's own depth at that state
-      {
-        int carry = 0;
-        for (int h0 = 0; !bad && h0 < nh; h0 += 64) {
-          const int h = h0 + lane;
-          const bool in = h < nh;
-          const uint32_t sq = in ? hop[h].y : 0u;
-          const uint32_t dl = in ? s_dl[sq] : 0u, st = in ? s_t[sq] : 0x7FFF7FFFu;
+    }
+    lds_sync();
+    if (!bad && sure && d_end != (int)(sa_w & 0xFFFFu)) bad = true;  // (the stop depth the search itself found)
+    lds_sync();
+    if (!bad) {
+      const int stop0 = d_end, left_fuz = lmf - d_end, draws = 1 + len - d_end;
+      const int npos = len - stop0, per = (npos + 63) / 64;
+      const int hi_d = len - lane * per, cnt = max(0, min(per, hi_d - stop0));  // this lane: depths (hi_d - cnt, hi_d]
+      // the safe bit of the k-mer of state q of segment b (g2s_d3_trace: outside_safe, and the rule in front of it)
+      auto split_of = [&](uint32_t b, int ts) -> int {
+        int split = ts;
+        if (analysed && ts >= 0) {
+          const uint32_t dl = s_dl[b], v0 = s_node[b];
           const int d0 = (int)(dl & 0xFFFFu);
-          const int t = h == 0 ? (int)start_t0 : max(dec15(st), dec15(st >> 16));  // (a child in the closure puts the whole parent there)
-          const int inc = in ? t + 1 : 0;
-          const int incl = (int)wave_scan((uint32_t)inc, lane);
-          const int at = len - carry - (incl - inc);
-          if (__ballot(in && (t < 0 || d0 + t != at)) != 0ull) { bad = true; break; }
-          if (in) hop[h] = make_uint2((uint32_t)at, sq | ((uint32_t)t << 16));
-          if (__ballot(in && h + 1 == nh)) d_end = (int)rl((uint32_t)d0, (nh - 1) & 63);
-          carry += (int)rl((uint32_t)incl, 63);
+          const int ln = max(0, min((int)(dl >> 16), d_last - d0 + 1));
+          int sp = -1;
+          const int pk = seg_pos(v0, (uint32_t)ln, sinknode);
+          if (pk >= 0 && d0 + pk >= lo_sink) sp = pk;
+          if (t_is_s) { const int pt = seg_pos(v0, (uint32_t)ln, reached); if (pt >= 0 && (d0 + pt == len0 || (n_len > 1 && d0 + pt == len1))) sp = pt; }
+          if (sp >= 0 && sp < ts) split = sp;
+        }
+        return max(split, 0);
+      };
+      auto safe_of = [&](uint32_t b, int q) -> bool {
+        if (!want_s) return true;
+        const uint32_t st = s_t[b];
+        const int ts = dec15(st);
+        if (q > ts) {  // in the traceback closure only: the first segment in emission order that holds the k-mer on a path to a sink
+          const uint32_t v0 = s_node[b];
+          const uint32_t x = (v0 & 1u) ? (v0 >> 1) - (uint32_t)q : (v0 >> 1) + (uint32_t)q;
+          for (int o = (int)nseg - 1; o >= 0; o--) {
+            const uint32_t ost = s_t[o];
+            if (max(dec15(ost), dec15(ost >> 16)) < 0) continue;  // (not emitted)
+            const int ots = dec15(ost);
+            const uint32_t on = s_node[o], oidx = on >> 1;
+            const int tq = (on & 1u) ? (int)oidx - (int)x : (int)x - (int)oidx;
+            if (tq >= 0 && tq <= ots) return tq <= split_of((uint32_t)o, ots) ? (ost & 0x8000u) != 0u : (ost & 0x80000000u) != 0u;
+          }
+          return sink_safe;
+        }
+        return q > split_of(b, ts) ? (st & 0x80000000u) != 0u : (st & 0x8000u) != 0u;
+      };
+      auto hop_find = [&](int d) -> int {  // the last hop entered at or above depth d
+        int lo = 0, hi = nh;
+        while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if ((int)hop[mid].x >= d) lo = mid; else hi = mid; }
+        return lo;
+      };
+      // pass 1: the safe bits of this lane's stretch, from the top of the fill downwards.  What a segment says about
+      // its states — where its part on a path to a sink ends, where the bit changes inside it, the two bits — is
+      // worked out when the stretch enters the segment, not per base (with it per base this pass was most of the
+      // 19 k cycles a guess cost a gap's wave)
+      int lowest_safe = 0x7FFFFFFF;
+      if (cnt > 0) {
+        int h = hop_find(hi_d);
+        uint2 hr = hop[h];
+        int d0 = (int)hr.x - (int)(hr.y >> 16);
+        int h_ts = -1, h_split = 0;
+        bool h_a = true, h_b = true;
+        auto enter = [&]() {
+          if (!want_s) return;
+          const uint32_t b = hr.y & 0xFFFFu, st = s_t[b];
+          h_ts = dec15(st);
+          h_split = split_of(b, h_ts);
+          h_a = (st & 0x8000u) != 0u; h_b = (st & 0x80000000u) != 0u;
+        };
+        enter();
+        for (int c = 0; c < cnt; c++) {
+          const int p = hi_d - c;
+          if (p < d0) { h++; hr = hop[h]; d0 = (int)hr.x - (int)(hr.y >> 16); enter(); }
+          const int q = p - d0;
+          const bool sf = !want_s ? true : q > h_ts ? safe_of(hr.y & 0xFFFFu, q) : (q > h_split ? h_b : h_a);
+          if (sf) lowest_safe = p;
+          cb[p - 1] = sf ? 1u : 0u;
+        }
+      }
+      // the nearest safe depth above each lane's stretch (the walk begins with the top of the fill counting as safe)
+      int above = lowest_safe;
+      for (int o = 1; o < 64; o <<= 1) { const int y = __shfl_up(above, o); if (lane >= o) above = min(above, y); }
+      above = __shfl_up(above, 1);
+      if (lane == 0) above = 0x7FFFFFFF;
+      int last_solid = min(above, len);
+      // pass 2: case, and the characters (the last base of the k-mer, by orientation) — sixteen loads in flight: a lane's
+      // stretch of a 1 000-base fill in one round trip (with eight, the second round trip was a fifth of a guess's cost)
+      if (cnt > 0) {
+        int h = hop_find(hi_d);
+        uint2 hr = hop[h];
+        int d0 = (int)hr.x - (int)(hr.y >> 16);
+        uint32_t v0 = s_node[hr.y & 0xFFFFu];
+        for (int c0 = 0; c0 < cnt; c0 += 16) {
+          uint32_t xs[16];
+          bool lowc[16];
+#pragma unroll
+          for (int u = 0; u < 16; u++) {
+            const int c = c0 + u;
+            xs[u] = 0u; lowc[u] = false;
+            if (c < cnt) {
+              const int p = hi_d - c;
+              if (p < d0) { h++; hr = hop[h]; d0 = (int)hr.x - (int)(hr.y >> 16); v0 = s_node[hr.y & 0xFFFFu]; }
+              const int q = p - d0;
+              const bool up = (v0 & 1u) == 0u;
+              xs[u] = (up ? (v0 >> 1) + (uint32_t)q : (v0 >> 1) - (uint32_t)q) | (up ? 0u : 0x80000000u);
+              if (cb[p - 1]) last_solid = p;
+              else lowc[u] = p <= last_solid - k;
+            }
+          }
+          char ch[16];
+#pragma unroll
+          for (int u = 0; u < 16; u++) ch[u] = (c0 + u < cnt) ? ((xs[u] >> 31) ? A.tr_chd[xs[u] & 0x7FFFFFFFu] : A.tr_chu[xs[u]]) : (char)0;
+#pragma unroll
+          for (int u = 0; u < 16; u++)
+            if (c0 + u < cnt) cb[hi_d - (c0 + u) - 1] = (unsigned char)(lowc[u] ? (ch[u] | 0x20) : ch[u]);
         }
       }
       lds_sync();
-      if (!bad && sure && d_end != (int)(sa_w & 0xFFFFu)) bad = true;  // (the stop depth the search itself found)
-      lds_sync();
-      if (!bad) {
-        const int stop0 = d_end, left_fuz = lmf - d_end, draws = 1 + len - d_end;
-        const int npos = len - stop0, per = (npos + 63) / 64;
-        const int hi_d = len - lane * per, cnt = max(0, min(per, hi_d - stop0));  // this lane: depths (hi_d - cnt, hi_d]
-        // the safe bit of the k-mer of state q of segment b (g2s_d3_trace: outside_safe, and the rule in front of it)
-        auto split_of = [&](uint32_t b, int ts) -> int {
-          int split = ts;
-          if (analysed && ts >= 0) {
-            const uint32_t dl = s_dl[b], v0 = s_node[b];
-            const int d0 = (int)(dl & 0xFFFFu);
-            const int ln = max(0, min((int)(dl >> 16), d_last - d0 + 1));
-            int sp = -1;
-            const int pk = seg_pos(v0, (uint32_t)ln, sinknode);
-            if (pk >= 0 && d0 + pk >= lo_sink) sp = pk;
-            if (t_is_s) { const int pt = seg_pos(v0, (uint32_t)ln, reached); if (pt >= 0 && (d0 + pt == len0 || (n_len > 1 && d0 + pt == len1))) sp = pt; }
-            if (sp >= 0 && sp < ts) split = sp;
-          }
-          return max(split, 0);
-        };
-        auto safe_of = [&](uint32_t b, int q) -> bool {
-          if (!want_s) return true;
-          const uint32_t st = s_t[b];
-          const int ts = dec15(st);
-          if (q > ts) {  // in the traceback closure only: the first segment in emission order that holds the k-mer on a path to a sink
-            const uint32_t v0 = s_node[b];
-            const uint32_t x = (v0 & 1u) ? (v0 >> 1) - (uint32_t)q : (v0 >> 1) + (uint32_t)q;
-            for (int o = (int)nseg - 1; o >= 0; o--) {
-              const uint32_t ost = s_t[o];
-              if (max(dec15(ost), dec15(ost >> 16)) < 0) continue;  // (not emitted)
-              const int ots = dec15(ost);
-              const uint32_t on = s_node[o], oidx = on >> 1;
-              const int tq = (on & 1u) ? (int)oidx - (int)x : (int)x - (int)oidx;
-              if (tq >= 0 && tq <= ots) return tq <= split_of((uint32_t)o, ots) ? (ost & 0x8000u) != 0u : (ost & 0x80000000u) != 0u;
-            }
-            return sink_safe;
-          }
-          return q > split_of(b, ts) ? (st & 0x80000000u) != 0u : (st & 0x8000u) != 0u;
-        };
-        auto hop_find = [&](int d) -> int {  // the last hop entered at or above depth d
-          int lo = 0, hi = nh;
-          while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if ((int)hop[mid].x >= d) lo = mid; else hi = mid; }
-          return lo;
-        };
-        // pass 1: the safe bits of this lane's stretch, from the top of the fill downwards.  What a segment says about
-        // its states — where its part on a path to a sink ends, where the bit changes inside it, the two bits — is
-        // worked out when the stretch enters the segment, not per base (with it per base this pass was most of the
-        // 19 k cycles a guess cost a gap's wave)
-        int lowest_safe = 0x7FFFFFFF;
-        if (cnt > 0) {
-          int h = hop_find(hi_d);
-          uint2 hr = hop[h];
-          int d0 = (int)hr.x - (int)(hr.y >> 16);
-          int h_ts = -1, h_split = 0;
-          bool h_a = true, h_b = true;
-          auto enter = [&]() {
-            if (!want_s) return;
-            const uint32_t b = hr.y & 0xFFFFu, st = s_t[b];
-            h_ts = dec15(st);
-            h_split = split_of(b, h_ts);
-            h_a = (st & 0x8000u) != 0u; h_b = (st & 0x80000000u) != 0u;
-          };
-          enter();
-          for (int c = 0; c < cnt; c++) {
-            const int p = hi_d - c;
-            if (p < d0) { h++; hr = hop[h]; d0 = (int)hr.x - (int)(hr.y >> 16); enter(); }
-            const int q = p - d0;
-            const bool sf = !want_s ? true : q > h_ts ? safe_of(hr.y & 0xFFFFu, q) : (q > h_split ? h_b : h_a);
-            if (sf) lowest_safe = p;
-            cb[p - 1] = sf ? 1u : 0u;
-          }
-        }
-        // the nearest safe depth above each lane's stretch (the walk begins with the top of the fill counting as safe)
-        int above = lowest_safe;
-        for (int o = 1; o < 64; o <<= 1) { const int y = __shfl_up(above, o); if (lane >= o) above = min(above, y); }
-        above = __shfl_up(above, 1);
-        if (lane == 0) above = 0x7FFFFFFF;
-        int last_solid = min(above, len);
-        // pass 2: case, and the characters (the last base of the k-mer, by orientation) — sixteen loads in flight: a lane's
-        // stretch of a 1 000-base fill in one round trip (with eight, the second round trip was a fifth of a guess's cost)
-        if (cnt > 0) {
-          int h = hop_find(hi_d);
-          uint2 hr = hop[h];
-          int d0 = (int)hr.x - (int)(hr.y >> 16);
-          uint32_t v0 = s_node[hr.y & 0xFFFFu];
-          for (int c0 = 0; c0 < cnt; c0 += 16) {
-            uint32_t xs[16];
-            bool lowc[16];
-#pragma unroll
-            for (int u = 0; u < 16; u++) {
-              const int c = c0 + u;
-              xs[u] = 0u; lowc[u] = false;
-              if (c < cnt) {
-                const int p = hi_d - c;
-                if (p < d0) { h++; hr = hop[h]; d0 = (int)hr.x - (int)(hr.y >> 16); v0 = s_node[hr.y & 0xFFFFu]; }
-                const int q = p - d0;
-                const bool up = (v0 & 1u) == 0u;
-                xs[u] = (up ? (v0 >> 1) + (uint32_t)q : (v0 >> 1) - (uint32_t)q) | (up ? 0u : 0x80000000u);
-                if (cb[p - 1]) last_solid = p;
-                else lowc[u] = p <= last_solid - k;
-              }
-            }
-            char ch[16];
-#pragma unroll
-            for (int u = 0; u < 16; u++) ch[u] = (c0 + u < cnt) ? ((xs[u] >> 31) ? A.tr_chd[xs[u] & 0x7FFFFFFFu] : A.tr_chu[xs[u]]) : (char)0;
-#pragma unroll
-            for (int u = 0; u < 16; u++)
-              if (c0 + u < cnt) cb[hi_d - (c0 + u) - 1] = (unsigned char)(lowc[u] ? (ch[u] | 0x20) : ch[u]);
-          }
-        }
-        lds_sync();
-        // the text, 64 consecutive bytes an instruction, and the record, a word a lane (g2s_d3_trace: finish)
-        const uint64_t abs_off = A.tr_arena_base + gd.rlog_off;
-        char* buf = A.tr_arena + abs_off;
-        for (int p = stop0 + lane; p < len; p += 64) buf[p] = (char)cb[p];
-        if (lane == 0) buf[len] = '\0';
-        if (!sure) {  // (the guess, where the trace kernel can compare with it)
-          char* sbuf = A.tr_spec_text + abs_off;
-          for (int p = stop0 + lane; p < len; p += 64) sbuf[p] = (char)cb[p];
-        }
-        const uint64_t fo = abs_off + (uint64_t)stop0;
-        const uint32_t rflags = ((flags & (G2S_DEV_Q7_A | G2S_DEV_Q7_B | G2S_DEV_Q7_D)) ? G2S_GAP_Q7 : 0u) | G2S_GAP_PHASE_D;
-        const uint32_t cnt_out = (uint32_t)((want_s && gd.all_paths) ? count_s : c_count);
-        uint32_t w = 0u;
-        switch (lane) {
-          case 0: w = cnt_out; break;
-          case 1: w = (uint32_t)left_fuz; break;
-          case 2: w = (uint32_t)reached_j; break;
-          case 3: w = rflags; break;
-          case 4: w = (uint32_t)fo; break;
-          case 5: w = (uint32_t)(fo >> 32); break;
-          case 6: w = (uint32_t)(len - stop0); break;
-          case 7: w = (uint32_t)draws; break;
-          case 8: case 16: w = want_s ? sub_vertices : 0u; break;
-          case 10: case 18: w = want_s ? sub_edges : 0u; break;
-          case 20: w = (uint32_t)c_count; break;
-          case 21: w = (uint32_t)n_len; break;
-          case 22: w = (uint32_t)len0; break;
-          case 23: w = (uint32_t)len1; break;
-          default: break;
-        }
-        if (lane < 28) A.tr_results[(size_t)gi * 28u + (uint32_t)lane] = w;
-        if (!sure && lane < 28) A.tr_spec_res[(size_t)gi * 28u + (uint32_t)lane] = w;
-        if (lane == 0) {
-          go->top_level = (uint32_t)stop0 | ((uint32_t)len << 16);  // (where the text written here begins and ends)
-          go->dflags |= sure ? G2S_DEVA_TRACED : G2S_DEVA_SPEC;
-          // (a guess: which chain of segments it followed — the trace kernel's wave that finds its own chain to be the same
-          // one has nothing to compare or send; the two diagnostic words of the record carry it)
-          if (!sure) { go->stat[6] = (uint32_t)chain_hash; go->stat[7] = (uint32_t)(chain_hash >> 32); }
-        }
+      // the text, 64 consecutive bytes an instruction, and the record, a word a lane (g2s_d3_trace: finish)
+      const uint64_t abs_off = A.tr_arena_base + gd.rlog_off;
+      char* buf = A.tr_arena + abs_off;
+      for (int p = stop0 + lane; p < len; p += 64) buf[p] = (char)cb[p];
+      if (lane == 0) buf[len] = '\0';
+      if (!sure) {  // (the guess, where the trace kernel can compare with it)
+        char* sbuf = A.tr_spec_text + abs_off;
+        for (int p = stop0 + lane; p < len; p += 64) sbuf[p] = (char)cb[p];
+      }
+      const uint64_t fo = abs_off + (uint64_t)stop0;
+      const uint32_t rflags = ((flags & (G2S_DEV_Q7_A | G2S_DEV_Q7_B | G2S_DEV_Q7_D)) ? G2S_GAP_Q7 : 0u) | G2S_GAP_PHASE_D;
+      const uint32_t cnt_out = (uint32_t)((want_s && gd.all_paths) ? count_s : c_count);
+      uint32_t w = 0u;
+      switch (lane) {
+        case 0: w = cnt_out; break;
+        case 1: w = (uint32_t)left_fuz; break;
+        case 2: w = (uint32_t)reached_j; break;
+        case 3: w = rflags; break;
+        case 4: w = (uint32_t)fo; break;
+        case 5: w = (uint32_t)(fo >> 32); break;
+        case 6: w = (uint32_t)(len - stop0); break;
+        case 7: w = (uint32_t)draws; break;
+        case 8: case 16: w = want_s ? sub_vertices : 0u; break;
+        case 10: case 18: w = want_s ? sub_edges : 0u; break;
+        case 20: w = (uint32_t)c_count; break;
+        case 21: w = (uint32_t)n_len; break;
+        case 22: w = (uint32_t)len0; break;
+        case 23: w = (uint32_t)len1; break;
+        default: break;
+      }
+      if (lane < 28) A.tr_results[(size_t)gi * 28u + (uint32_t)lane] = w;
+      if (!sure && lane < 28) A.tr_spec_res[(size_t)gi * 28u + (uint32_t)lane] = w;
+      if (lane == 0) {
+        go->top_level = (uint32_t)stop0 | ((uint32_t)len << 16);  // (where the text written here begins and ends)
+        go->dflags |= sure ? G2S_DEVA_TRACED : G2S_DEVA_SPEC;
+        // (a guess: which chain of segments it followed — the trace kernel's wave that finds its own chain to be the same
+        // one has nothing to compare or send; the two diagnostic words of the record carry it)
+        if (!sure) { go->stat[6] = (uint32_t)chain_hash; go->stat[7] = (uint32_t)(chain_hash >> 32); }
       }
     }
   }
@@ -2278,7 +1759,7 @@ __device__ __forceinline__ void seg_fill_one(uint32_t* lds, const SegArgs& A, co
 // dynamic LDS: 7 arrays of G2S_SEG_CAP words + left seeds
 __global__ __launch_bounds__(64) void g2s_fill_seg(const SegArgs A) {
   extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
-  seg_fill_one<false, false>(lds, A, blockIdx.x, nullptr);
+  seg_fill_one<false>(lds, A, blockIdx.x);
 }
 
 // Two waves per gap (see seg_fill_one): for lists short enough to be latency-bound — the launch ends with its
@@ -2286,24 +1767,7 @@ __global__ __launch_bounds__(64) void g2s_fill_seg(const SegArgs A) {
 // dynamic LDS: the segment arrays and seeds, then phase A's table, queues and hand-over words
 __global__ __launch_bounds__(128) void g2s_fill_seg2(const SegArgs A) {
   extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
-  seg_fill_one<false, true>(lds, A, blockIdx.x, nullptr);
-}
-
-// The large variant: one workgroup per compute unit (it takes nearly all of the LDS), each working
-// through the list by an atomic counter so that the longest searches (the list is sorted) start first.
-__global__ __launch_bounds__(64) void g2s_fill_segx(const SegArgs A, uint32_t* scratch, uint32_t ngaps,
-                                                     unsigned long long* next_gap) {
-  extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
-  uint32_t* scr = scratch + (size_t)blockIdx.x * SEGX_SCR_WORDS;
-  while (true) {
-    unsigned long long x = 0;
-    if (threadIdx.x == 0) x = atomicAdd(next_gap, 1ull);
-    x = __shfl(x, 0);
-    if (x >= (unsigned long long)ngaps) break;
-    seg_fill_one<true, false>(lds, A, (uint32_t)x, scr);
-    lds_sync();
-    __threadfence_block();
-  }
+  seg_fill_one<true>(lds, A, blockIdx.x);
 }
 
 namespace g2s {
@@ -2316,8 +1780,6 @@ size_t fill_seg2_lds_bytes() {  // (... + the next round's records: 2 x 64 x set
   return 4u * (7u * G2S_SEG_CAP + 32u + 2u * 128u * G2S_SEG_ASETS + 128u * G2S_SEG_ASETS + 4u * 64u * G2S_SEG_ASETS + 16u + 2u * 64u * G2S_SEG_ASETS * 5u);
 }
 uint32_t fill_seg_dbg_words() { return 8u + 2u * 64u * G2S_SEG_ASETS + 6u * G2S_SEG_CAP + 14u; }  // (+14: profile words)
-size_t fill_segx_lds_bytes() { return 4u * SEGX_LDS_WORDS; }
-size_t fill_segx_scratch_bytes(uint32_t workgroups) { return (size_t)workgroups * SEGX_SCR_WORDS * 4u; }
 uint32_t fill_segx_dbg_words() { return 8u + 2u * G2S_SEGX_EA + 6u * G2S_SEGX_CAP + 14u; }
 
 hipError_t launch_fill_seg(hipStream_t st, uint32_t ngaps, const uint32_t* succ, const uint32_t* urec, const GapDev* gaps,
@@ -2328,10 +1790,7 @@ hipError_t launch_fill_seg(hipStream_t st, uint32_t ngaps, const uint32_t* succ,
                            uint32_t* d2_list, uint32_t d2_tag, const SegInline* inl, const SegEarly* early, const SegTrace* tr,
                            const GapLite* lite, int lite_e, int lite_all_paths, hipEvent_t ev_start, hipEvent_t ev_stop) {
   if (ngaps == 0) return hipSuccess;
-  size_t bytes = two_waves ? fill_seg2_lds_bytes() : fill_seg_lds_bytes();
-  // (G2S_SEG_LDS_PAD=BYTES, measurements only: a larger LDS request per gap = fewer gaps resident per compute unit)
-  static const size_t lds_pad = getenv("G2S_SEG_LDS_PAD") ? (size_t)atoi(getenv("G2S_SEG_LDS_PAD")) : 0;
-  bytes += lds_pad;
+  const size_t bytes = two_waves ? fill_seg2_lds_bytes() : fill_seg_lds_bytes();
   {  // (the attribute is per device and kernel: set when a device sees a kernel for the first time, not per launch)
     static std::mutex mu;
     static std::set<std::pair<int, int>> done;
@@ -2364,21 +1823,6 @@ hipError_t launch_fill_seg(hipStream_t st, uint32_t ngaps, const uint32_t* succ,
   }
   if (two_waves) hipLaunchKernelGGL(g2s_fill_seg2, dim3(ngaps), dim3(128), bytes, st, A);
   else hipLaunchKernelGGL(g2s_fill_seg, dim3(ngaps), dim3(64), bytes, st, A);
-  return hipGetLastError();
-}
-
-hipError_t launch_fill_segx(hipStream_t st, uint32_t ngaps, uint32_t workgroups, const uint32_t* succ, const uint32_t* urec,
-                            const GapDev* gaps, const uint32_t* gap_ids, const uint32_t* flank_nodes, SubRec* sub_out,
-                            unsigned long long out_cap, unsigned long long* out_counter, GapOut* outs, GapOut* outs_host,
-                            uint32_t* done_list, int skip_confident, uint32_t* dbg, uint32_t* scratch,
-                            unsigned long long* next_gap) {
-  if (ngaps == 0) return hipSuccess;
-  const size_t bytes = fill_segx_lds_bytes();
-  hipError_t e = hipFuncSetAttribute((const void*)g2s_fill_segx, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-  if (e != hipSuccess) return e;
-  const SegArgs A = {succ, urec, GapSrc{gaps, nullptr, 0, 0}, gap_ids, flank_nodes, sub_out, out_cap, out_counter, outs, outs_host, done_list,
-                     skip_confident, dbg, fill_segx_dbg_words(), nullptr, nullptr, 0u, 1u, 0u, 0u, nullptr};
-  hipLaunchKernelGGL(g2s_fill_segx, dim3(workgroups), dim3(64), bytes, st, A, scratch, ngaps, next_gap);
   return hipGetLastError();
 }
 

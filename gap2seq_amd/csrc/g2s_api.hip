@@ -1013,7 +1013,7 @@ extern "C" int g2s_batch_prepare(g2s_session* s, const g2s_gap* gaps, size_t n, 
   text_off.resize(n);
   didx.resize(n);
   const bool force_host_lookup = GENV("G2S_HOST_LOOKUP") != nullptr;
-  static const size_t max_tasks = getenv("G2S_PREP_TASKS") ? (size_t)std::max(1, atoi(getenv("G2S_PREP_TASKS"))) : 16;
+  constexpr size_t max_tasks = 16;
   const size_t per_task = std::max<size_t>(256, (n + max_tasks - 1) / max_tasks);  // (at most 16 tasks: every task wakes a thread)
   const size_t ntasks = (n + per_task - 1) / per_task;
   struct Part {
@@ -1097,13 +1097,13 @@ extern "C" int g2s_batch_prepare(g2s_session* s, const g2s_gap* gaps, size_t n, 
     }
   }
   // (the regular segment tier's waves resolve their own flanks when resident mode takes the list — not a deep list,
-  // whose longest gaps start in the large variant; G2S_FLANK_KERNEL=1: the look-up kernel as until round 5.  A list
-  // without a bad flank gets its text at a FIXED STRIDE: when the launch takes the gaps in list order, a wave knows
-  // where its text is before its descriptor has arrived — on a short list both come over the link.)
+  // whose longest gaps start in the large variant.  A list without a bad flank gets its text at a FIXED STRIDE: when
+  // the launch takes the gaps in list order, a wave knows where its text is before its descriptor has arrived — on a
+  // short list both come over the link.)
   // (k >= 64: the look-up kernel always — the fill kernels' in-wave look-ups take 64- and 128-bit k-mers only)
-  b->inline_ok = fast_gd != nullptr && b->dmax < 2500 && !GENV("G2S_FLANK_KERNEL") && s->lookup.wide != G2S_LK_256;
+  b->inline_ok = fast_gd != nullptr && b->dmax < 2500 && s->lookup.wide != G2S_LK_256;
   uint32_t tstride = 0;
-  if (b->inline_ok && n_desc == n && tb_max <= 508 && !GENV("G2S_NO_TEXT_STRIDE")) {
+  if (b->inline_ok && n_desc == n && tb_max <= 508) {
     tstride = (uint32_t)((tb_max + 3) & ~(size_t)3);
     if ((uint64_t)n * tstride < (1ull << 31)) text_bytes = (size_t)n * tstride; else tstride = 0;
   }
@@ -1235,7 +1235,7 @@ int g2s_batch::upload_flanks(bool allow_inline) {
       // (a long list: descriptors and flank text go to device memory in one copy in front of the kernel — 10 000
       // workgroups that each read their descriptor and then their text over the link are two round trips of the link
       // each: 0.10 ms for config 3's list, against a 1.5 MB copy and a kernel that reads device memory)
-      if (e == hipSuccess && n_desc > 2048 && !GENV("G2S_FLANKS_OVER_THE_LINK") && !staged) {
+      if (e == hipSuccess && n_desc > 2048 && !staged) {
         const size_t bytes = (size_t)((const char*)nodes - (const char*)desc);  // [descriptors][text], contiguous
         e = s->d_fstage.ensure(bytes);
         if (e == hipSuccess) e = hipMemcpyAsync(s->d_fstage.p, desc, bytes, hipMemcpyHostToDevice, s->stream);
@@ -1446,8 +1446,8 @@ int run_tier(g2s_batch* b, const std::vector<uint32_t>& ids, uint64_t scale, uin
     // gap; fill_seg.hip, `publish`): config 3's launch 0.8 -> 0.48 ms.  Short lists announce every gap by itself:
     // their launch ends with its slowest gap either way (config 2: 0.152 ms with batches of 4, 0.153 without), and
     // the gaps of unfinished batches would be analysed behind the launch's end instead of under it (config 2's
-    // step 0.39 ms against 0.37).  G2S_PUBLISH_BATCH=N forces (1 = every gap by itself).
-    uint32_t pub_batch = GENV("G2S_PUBLISH_BATCH") ? (uint32_t)atoi(GENV("G2S_PUBLISH_BATCH")) : (ids.size() <= 2048 ? 1u : 16u);
+    // step 0.39 ms against 0.37).
+    const uint32_t pub_batch = ids.size() <= 2048 ? 1u : 16u;
     size_t xcd_bytes = 0;
     if (seg == 1 && pub_batch > 1) {
       xcd_bytes = 64 + 8 * ids.size() * 4;
@@ -1467,17 +1467,8 @@ int run_tier(g2s_batch* b, const std::vector<uint32_t>& ids, uint64_t scale, uin
     if (seg == 2) {
       // one persistent workgroup per compute unit (the variant takes nearly all of a CU's LDS)
       const uint32_t wgs = (uint32_t)std::min<size_t>(ids.size(), (size_t)std::max(1, s->num_cus));
-      // (G2S_SEGX_ONE_WAVE=1: round 3's kernel, one wave per compute unit — measurements only)
-      static const bool one_wave = getenv("G2S_SEGX_ONE_WAVE") != nullptr;
-      HIP_TRY(s->d_segx.ensure(std::max(fill_segx_scratch_bytes(wgs), fill_segw_scratch_bytes(wgs))));
-      if (!one_wave)
-        HIP_TRY(launch_fill_segw(st, (uint32_t)ids.size(), wgs, dg.succ, dg.urec, gaps_dev, ids_dev, (const uint32_t*)s->d_flank.p,
-                                 (SubRec*)d_subs_host, (unsigned long long)out_states, (unsigned long long*)s->d_counter.p,
-                                 (GapOut*)s->d_outs.p, (GapOut*)d_outs_host, (uint32_t*)d_done_host,
-                                 s->params.skip_confident ? 1 : 0, seg_dbg, (uint32_t*)s->d_segx.p,
-                                 (unsigned long long*)s->d_counter.p + 2));
-      else
-      HIP_TRY(launch_fill_segx(st, (uint32_t)ids.size(), wgs, dg.succ, dg.urec, gaps_dev, ids_dev, (const uint32_t*)s->d_flank.p,
+      HIP_TRY(s->d_segx.ensure(fill_segw_scratch_bytes(wgs)));
+      HIP_TRY(launch_fill_segw(st, (uint32_t)ids.size(), wgs, dg.succ, dg.urec, gaps_dev, ids_dev, (const uint32_t*)s->d_flank.p,
                                (SubRec*)d_subs_host, (unsigned long long)out_states, (unsigned long long*)s->d_counter.p,
                                (GapOut*)s->d_outs.p, (GapOut*)d_outs_host, (uint32_t*)d_done_host,
                                s->params.skip_confident ? 1 : 0, seg_dbg, (uint32_t*)s->d_segx.p,
@@ -2023,14 +2014,14 @@ int batch_stage1(g2s_batch* b, bool analyze, g2s_result* results) {
       if (j.bad_flank || j.rmf > 31 || j.lmf > 31 || j.lmf + j.rmf + j.g + fp.d_err >= 32767) continue;
       seg_ids.push_back((uint32_t)i);
     }
-    // mode 1: the tier proper; mode 2: its large variant (g2s_fill_segx) for the gaps that outgrew a capacity of
+    // mode 1: the tier proper; mode 2: its large variant (g2s_fill_segw) for the gaps that outgrew a capacity of
     // mode 1 (-dist-error 2000: thousands of segments and right-set entries); what outgrows that too takes
     // the passes below
     // (tests: G2S_FORCE_SEGX=1 sends every gap to the large variant, G2S_NO_SEGX_TIER=1 none)
     for (int mode = GENV("G2S_FORCE_SEGX") ? 2 : 1; mode <= 2 && !seg_ids.empty(); mode++) {
       if (mode == 2 && GENV("G2S_NO_SEGX_TIER")) break;
       // longest searches first (see below): always for the large variant, whose workgroups take the list in order
-      if ((seg_ids.size() > 1024 || mode == 2) && !GENV("G2S_NO_LPT")) {
+      if (seg_ids.size() > 1024 || mode == 2) {
         // (a stable counting sort by gap length, longest first: a comparison sort of 10 000 ids cost 0.3 ms)
         int gmax = 0;
         for (uint32_t i : seg_ids) gmax = std::max(gmax, b->jobs[i].g);
@@ -2155,8 +2146,8 @@ int batch_stage1(g2s_batch* b, bool analyze, g2s_result* results) {
     if (cand[pass].empty()) continue;
     // Workgroups are dispatched in id order and a launch ends with its slowest gap: start the
     // gaps with the most DP levels first, so that the long ones are not the last to begin
-    // (lists longer than the chip holds at once; G2S_NO_LPT=1 keeps the input order).
-    if (cand[pass].size() > 1024 && !GENV("G2S_NO_LPT"))
+    // (lists longer than the chip holds at once).
+    if (cand[pass].size() > 1024)
       std::stable_sort(cand[pass].begin(), cand[pass].end(),
                        [&](uint32_t a, uint32_t c) { return b->jobs[a].g > b->jobs[c].g; });
     const std::vector<uint32_t>& ids = cand[pass];
@@ -2822,7 +2813,7 @@ static int resident_launch_fill(g2s_batch* b, ResidentLaunch* rl, g2s_result* re
   ids.clear();
   ids.reserve(n);
   bool ids_identity = false;  // the launch takes the gaps in list order, all of them
-  if (b->n_valid > 1024 && !GENV("G2S_NO_LPT") && (size_t)gmax <= 8 * b->n_valid + 65536) {
+  if (b->n_valid > 1024 && (size_t)gmax <= 8 * b->n_valid + 65536) {
     std::vector<uint32_t>& at = s->res_at;
     at.assign((size_t)gmax + 2, 0);
     for (size_t i = 0; i < n; i++) if (!b->jobs[i].bad_flank) at[(size_t)(gmax - b->jobs[i].g) + 1]++;
@@ -2957,13 +2948,12 @@ static int resident_launch_fill(g2s_batch* b, ResidentLaunch* rl, g2s_result* re
   // (measured, config 3: 0.93-0.96 ms per step against 0.89-0.92 with everything behind the fill kernel — the polling waves
   // cost the fill kernel 5 % — so: only with G2S_D2_POLL=1)
   const bool d2_poll = dev_d2 && !d2_deep && GENV("G2S_D2_POLL") && atoi(GENV("G2S_D2_POLL")) == 1;
-  const uint32_t d2_poll_wgs = d2_poll ? (uint32_t)std::min<size_t>(ids.size(), (size_t)std::max(1, atoi(GENV("G2S_D2_POLL_WGS") ? GENV("G2S_D2_POLL_WGS") : "16"))) : 0u;
+  const uint32_t d2_poll_wgs = d2_poll ? (uint32_t)std::min<size_t>(ids.size(), 16) : 0u;
   const uint32_t d2_tag = d2_poll ? (0x80000000u | ((++s->d2_lists & 0x7Fu) << 24)) : 0u;
   // (how many workgroups: the trace kernel's last wave waits until every one of them has left, and they are dispatched
   // beside that kernel's 10 000 waves — config 3's list, 70 closures: 0.89 ms per step with 128 workgroups, 1.2 with 512,
   // 1.6 with 1 024, profiles/r05_d2_workgroups_c3.txt; a deep list has hundreds of closures and waits for the kernel anyway)
-  const uint32_t d2_small_wgs = (uint32_t)std::min<size_t>(ids.size(), GENV("G2S_D2_SMALL_WGS") ? (size_t)std::max(1, atoi(GENV("G2S_D2_SMALL_WGS")))
-                                                                                   : (b->dmax >= 2500 ? (size_t)std::max(1, s->num_cus) * 4u : (size_t)128));
+  const uint32_t d2_small_wgs = (uint32_t)std::min<size_t>(ids.size(), b->dmax >= 2500 ? (size_t)std::max(1, s->num_cus) * 4u : (size_t)128);
   // (the large instantiation's workgroups need a whole compute unit's LDS each: on a list that is not deep only a few
   // are launched — what the small one passes on there is rare —, so that they find their units beside the trace kernel)
   const uint32_t d2_big_wgs = (uint32_t)std::min<size_t>(ids.size(), b->dmax >= 2500 ? (size_t)std::max(1, s->num_cus) : (size_t)8);
@@ -2998,8 +2988,7 @@ static int resident_launch_fill(g2s_batch* b, ResidentLaunch* rl, g2s_result* re
     // previous list's phase D2 — read the same buffers: stream order keeps the copies behind it)
     // (not for a stream of lists in flight: nine streams of three sessions share the hardware queues, and the copies
     // on one more of them cost twelve config-3 lists 17.5 instead of 21.2 M gaps/s)
-    static const bool beside_ok = !getenv("G2S_DESC_ON_STREAM");
-    const bool beside = beside_ok && !b->through_begin;
+    const bool beside = !b->through_begin;
     hipStream_t cs = beside ? s->stream3 : st;
     // (one copy: the short records and, right behind them, the launch order)
     HIP_TRY_S(hipMemcpyAsync(s->d_gaps.p, gd, n * sizeof(GapLite) + ids.size() * 4, hipMemcpyHostToDevice, cs));
@@ -3015,7 +3004,7 @@ static int resident_launch_fill(g2s_batch* b, ResidentLaunch* rl, g2s_result* re
   SegEarly early_dev;
   s->early_host = SegEarly();
   // (with phase D2 on the device — below — there is nothing to hand over early)
-  if (rerun && b->dmax >= 2500 && !s->in_team_list && !GENV("G2S_NO_EARLY_HANDOVER") && !dev_d2) {
+  if (rerun && b->dmax >= 2500 && !s->in_team_list && !dev_d2) {
     const size_t cap_items = n, cap_segs = (size_t)std::min<uint64_t>((uint64_t)n * 1024u, 2ull << 20) + 65536u;
     const size_t b_items = (cap_items * 32 + 63) & ~(size_t)63, b_outs = (cap_items * sizeof(GapOut) + 63) & ~(size_t)63;
     HIP_TRY_S(s->h_early.ensure(b_items + b_outs + cap_segs * sizeof(SegRec)));
@@ -3035,8 +3024,7 @@ static int resident_launch_fill(g2s_batch* b, ResidentLaunch* rl, g2s_result* re
   // (a list that is not deep, its closures left to the host — the short lists: the few closures the regular tier does not
   // analyse itself leave their gaps' waves the same way, and the thread that waits for the hand-over analyses them
   // meanwhile: resident_d3_wait.  The two counters live behind the fill kernel's cursors, zeroed with them.)
-  const bool early_reg = b->dmax < 2500 && !s->in_team_list && !dev_d2 && !s->params.skip_confident && !ids.empty() &&
-                         !GENV("G2S_NO_EARLY_HANDOVER");
+  const bool early_reg = b->dmax < 2500 && !s->in_team_list && !dev_d2 && !s->params.skip_confident && !ids.empty();
   if (early_reg) {
     const size_t cap_items = n, cap_segs = std::max<size_t>(n * 16, 65536);
     const size_t b_items = (cap_items * 32 + 63) & ~(size_t)63, b_outs = (cap_items * sizeof(GapOut) + 63) & ~(size_t)63;
@@ -3067,7 +3055,7 @@ static int resident_launch_fill(g2s_batch* b, ResidentLaunch* rl, g2s_result* re
     DA.d2out = (D2Out*)s->d_d2out.p; DA.runs = (uint32_t*)s->d_d2runs.p; DA.run_cursor = ctr + 8; DA.run_cap = d2_run_cap;
     DA.all_paths = s->params.all_paths ? 1 : 0; DA.list_cap = (uint32_t)n;
     DA.wgs_done = ctr + 9;
-    DA.behind = (d2_deep && !GENV("G2S_D2_RELEASE")) ? 1u : 0u;  // (a deep list's phase D3 waits for the launch: s->d2_wait)
+    DA.behind = d2_deep ? 1u : 0u;  // (a deep list's phase D3 waits for the launch: s->d2_wait)
     DA.tag = d2_tag;
     static const bool d2_prof = getenv("G2S_D2_PROF") != nullptr;
     if (d2_prof) {
@@ -3094,10 +3082,7 @@ static int resident_launch_fill(g2s_batch* b, ResidentLaunch* rl, g2s_result* re
   lap(2);
   rl->timed = kernel_events_on(s);
   // (a bracketed launch: the kernel's own start and stop times go into ev[1] / ev[2] with the dispatch — two
-  // hipEventRecord calls around it put packets of their own into the stream, ~10 us of such a step.  G2S_EVENT_RECORD=1:
-  // as until round 6.)
-  const bool ext_events = rl->timed && !GENV("G2S_EVENT_RECORD");
-  if (rl->timed && !ext_events) HIP_TRY_S(hipEventRecord(s->ev[1], st));
+  // hipEventRecord calls around it put packets of their own into the stream, ~10 us of such a step)
   // (the flank look-ups in this kernel's waves: every valid gap of such a list is in this launch — inline_ok excludes
   // the deep lists, whose longest gaps start in the large variant)
   SegInline inl;
@@ -3113,8 +3098,7 @@ static int resident_launch_fill(g2s_batch* b, ResidentLaunch* rl, g2s_result* re
   const uint32_t* ids_fill = (ids_identity && n_reg == n) ? nullptr : ids_dev;
   // (tracebacks that have no choice to make, by the gaps' own waves: fill_seg.hip.  G2S_TRACE_IN_FILL=0: all by phase D3.)
   SegTrace tr;
-  const bool use_tr = results != nullptr && !s->in_team_list && !GENV("G2S_D3_STAGE") &&
-                      !(GENV("G2S_TRACE_IN_FILL") && atoi(GENV("G2S_TRACE_IN_FILL")) == 0);
+  const bool use_tr = results != nullptr && !s->in_team_list && !(GENV("G2S_TRACE_IN_FILL") && atoi(GENV("G2S_TRACE_IN_FILL")) == 0);
   if (use_tr) {
     void *res_dev = nullptr, *arena_dev = nullptr;
     bool rd = false, ad = false;
@@ -3149,11 +3133,10 @@ static int resident_launch_fill(g2s_batch* b, ResidentLaunch* rl, g2s_result* re
                           nullptr, nullptr, 0u, 1u, true, rerun ? (uint32_t*)s->d_ovf.p : nullptr,
                           dev_d2 ? (uint32_t*)s->d_d2list.p : nullptr, d2_tag, use_inl ? &inl : nullptr,
                           early_reg ? &early_dev : nullptr, (use_tr && tr.chu) ? &tr : nullptr, gaps_dev, lite_e, lite_ap,
-                          ext_events ? s->ev[1] : nullptr, ext_events ? s->ev[2] : nullptr));
+                          rl->timed ? s->ev[1] : nullptr, rl->timed ? s->ev[2] : nullptr));
   if (use_inl) { b->inline_pending = false; b->nodes_dev_only = true; }  // (behind this kernel d_flank holds the ids; the pinned copy those of the host's gaps)
   s->lap_fill_queued = std::chrono::steady_clock::now();
   lap(3);
-  if (rl->timed && !ext_events) HIP_TRY_S(hipEventRecord(s->ev[2], st));
   // (queued BEHIND the regular tier's kernel, which takes the compute units first — a workgroup of the large variant
   // needs a whole unit's LDS and stays for the launch: started first, 256 of them leave the regular tier no unit until
   // the early list runs dry (4.4 instead of 3.65 ms, when the hardware happened to order them so); its workgroups
@@ -3254,7 +3237,7 @@ static int resident_rand(g2s_session* s, PinBuf* pin, size_t n, size_t list_cap,
 // (what the second half — waiting, the host-finished gaps, the summary — needs of the first: queueing the kernels)
 struct D3Pending {
   ResidentList L;
-  bool timed = false, res_direct = false, arena_direct = false, stage_dev = false, self_clean = false;
+  bool timed = false, res_direct = false, arena_direct = false, self_clean = false;
   bool discard = false;  // (its stream continued a list that did not end on the device: nothing of it counts)
   D3Side side_h;
   D3Work W;
@@ -3337,17 +3320,8 @@ static int resident_d3_launch(g2s_session* s, const ResidentList& L, bool timed,
   }
   // where the kernels write results and text: the caller's buffers when those are pinned, staging otherwise
   void *res_dev = nullptr, *arena_dev = nullptr;
-  // (G2S_D3_STAGE=device, measurements only: the kernels write device memory, two copies bring it to the caller)
-  const bool stage_dev = GENV("G2S_D3_STAGE") && !strcmp(GENV("G2S_D3_STAGE"), "device");
   bool res_direct = false, arena_direct = false;
-  if (!stage_dev) { const int rc = resident_targets(s, results, arena, n, L.arena_bytes, &res_dev, &arena_dev, &res_direct, &arena_direct); if (rc != G2S_OK) return rc; }
-  if (stage_dev) {
-    HIP_TRY_S(s->d_resout.ensure(n * sizeof(g2s_result)));
-    HIP_TRY_S(s->d_textout.ensure(L.arena_bytes + 16));
-    res_dev = s->d_resout.p;
-    arena_dev = s->d_textout.p;
-    res_direct = arena_direct = true;
-  }
+  { const int rc = resident_targets(s, results, arena, n, L.arena_bytes, &res_dev, &arena_dev, &res_direct, &arena_direct); if (rc != G2S_OK) return rc; }
   hipStream_t st = s->stream;
   void* d_dgaps = nullptr;
   HIP_TRY_S(hipHostGetDevicePointer(&d_dgaps, L.pin->p, 0));
@@ -3410,16 +3384,11 @@ static int resident_d3_launch(g2s_session* s, const ResidentList& L, bool timed,
                     s->d_d3.clean >= 1024 + 64 * 128, self_clean ? (uint32_t*)s->d_counter.p : nullptr,
                     no_spin ? s->ev_chain : nullptr /* (lists in flight: the next one's stream may wait for it) */,
                     (W.d2out && s->d2_wait) ? s->ev_d2 : nullptr,
-                    (timed && !GENV("G2S_EVENT_RECORD")) ? s->ev[3] : nullptr /* (the trace kernel's own stop time) */));
+                    timed ? s->ev[3] : nullptr /* (the trace kernel's own stop time) */));
   s->d_d3.clean = 0;
-  if (timed && !sharded && GENV("G2S_EVENT_RECORD")) HIP_TRY_S(hipEventRecord(s->ev[3], st));
-  if (stage_dev && !sharded) {
-    HIP_TRY_S(hipMemcpyAsync(results, s->d_resout.p, n * sizeof(g2s_result), hipMemcpyDeviceToHost, st));
-    HIP_TRY_S(hipMemcpyAsync(arena, s->d_textout.p, L.arena_bytes, hipMemcpyDeviceToHost, st));
-  }
   {
     D3Pending* dp = new D3Pending;
-    dp->L = L; dp->timed = timed; dp->res_direct = res_direct; dp->arena_direct = arena_direct; dp->stage_dev = stage_dev;
+    dp->L = L; dp->timed = timed; dp->res_direct = res_direct; dp->arena_direct = arena_direct;
     dp->self_clean = self_clean; dp->side_h = side_h; dp->W = W; dp->hsum = hsum; dp->d3_begin = d3_begin; dp->results = results;
     dp->arena = arena; dp->t_enter = t_enter; dp->t_launched = std::chrono::steady_clock::now();
     dp->sharded = sharded; dp->P = P; dp->side_dev = side; dp->res_dev = res_dev; dp->arena_dev = (char*)arena_dev;
@@ -3486,7 +3455,7 @@ static int resident_d3_wait(g2s_session* s, g2s_timing* tm_out, double* ms_d3_ou
   const size_t n = L.n;
   const Graph& g = *s->graph->g;
   const FillParams fp = fill_params_of(s);
-  const bool timed = dpp->timed, res_direct = dpp->res_direct, arena_direct = dpp->arena_direct, stage_dev = dpp->stage_dev;
+  const bool timed = dpp->timed, res_direct = dpp->res_direct, arena_direct = dpp->arena_direct;
   const bool self_clean = dpp->self_clean;
   const D3Side& side_h = dpp->side_h;
   const D3Work& W = dpp->W;
@@ -3526,7 +3495,7 @@ static int resident_d3_wait(g2s_session* s, g2s_timing* tm_out, double* ms_d3_ou
   // (a list that is not deep has a handful of such closures, a few hundred segments each: this thread takes them itself
   // while it waits — waking the pool costs more than they do)
   // (a long list whose closures are the host's — G2S_DEVICE_D2=0 — has dozens: the pool's, as on deep lists)
-  const bool early_inline = eh.cap_items && !stage_dev && L.groups.size() == 1 && L.dmax < 2500 && n < 3072;
+  const bool early_inline = eh.cap_items && L.groups.size() == 1 && L.dmax < 2500 && n < 3072;
   std::vector<std::pair<uint32_t, uint32_t>>& inline_done = s->early_inline_done;  // (gap, item) analysed here
   inline_done.clear();
   uint32_t inline_next = 0;
@@ -3545,7 +3514,7 @@ static int resident_d3_wait(g2s_session* s, g2s_timing* tm_out, double* ms_d3_ou
       if (seg_analyze(fp, L.groups[0]->jobs[gap], v, &pp, sc.data())) inline_done.emplace_back(gap, idx);
     }
   };
-  if (!early_inline && eh.cap_items && !stage_dev && L.groups.size() == 1 && s->pool->size() > 0 &&
+  if (!early_inline && eh.cap_items && L.groups.size() == 1 && s->pool->size() > 0 &&
       __atomic_load_n(side_h.count, __ATOMIC_ACQUIRE) == ~0ull) {
     s->early_of_gap.assign(n, -1);
     if (s->early_prep.size() < eh.cap_items) { s->early_prep.resize(eh.cap_items); s->early_scratch.resize(eh.cap_items); }
@@ -3594,9 +3563,9 @@ static int resident_d3_wait(g2s_session* s, g2s_timing* tm_out, double* ms_d3_ou
   const auto t_handed = std::chrono::steady_clock::now();
   std::atomic<int> host_bad(0);
   const size_t ni = (size_t)(handed & 0x7FFFFFFFFFFFFFFFull);
-  g2s_result* rs_host = res_direct && !stage_dev ? results : (g2s_result*)s->h_res.p;
+  g2s_result* rs_host = res_direct ? results : (g2s_result*)s->h_res.p;
   uint64_t host_fill_bytes = 0;
-  if (ni && !(handed >> 63) && !stage_dev) {
+  if (ni && !(handed >> 63)) {
     char* text = arena_direct ? arena : (char*)s->h_text.p;
     auto one = [&](size_t x) {
       // (the gap's wave of the trace kernel says when the item is complete)
@@ -3692,7 +3661,6 @@ static int resident_d3_wait(g2s_session* s, g2s_timing* tm_out, double* ms_d3_ou
     const int mine = waits++;
     test_fallback = strncmp(tf, "rel:", 4) != 0 || mine == atoi(tf + 4);
   }
-  if (stage_dev && hsum->host_items) hsum->anomalies++;  // (the measurement switch has no path for host-finished gaps)
   if (hsum->status != 0 || hsum->anomalies != 0 || test_fallback || host_bad.load() || hsum->host_items != ni) {
     if (GENV("G2S_DEBUG"))
       fprintf(stderr, "[g2s] resident mode: list of %zu gaps goes to the host path (status %#x, %u gaps not finished on the device, %u anomalies, %llu table entries, %d host-finished gaps disagree)\n",
@@ -3962,7 +3930,6 @@ struct TeamBarrier {
 static int team_resident_sharded(g2s_session* const* sessions, int nsessions, const g2s_gap* gaps, size_t n, size_t group_size,
                                  g2s_result* results, char* arena, g2s_timing* timing_out) {
   g2s_session* lead = sessions[0];
-  if (GENV("G2S_TEAM_GATHER")) return 1;  // (measurements: the gather form)
   const size_t ngroups = (n + group_size - 1) / group_size;
   if (nsessions < 2 || ngroups != (size_t)nsessions || nsessions > 16) return 1;
   for (int t = 0; t < nsessions; t++) if (!resident_applicable(sessions[t], n) || sessions[t]->d3_pending) return 1;

@@ -248,9 +248,4 @@ struct SegArgs {
   uint32_t tr_guess_until;
 };
 
-// LDS of the large variant (words): see the layout notes at each phase
-#define SEGX_LDS_WORDS 39936u
-// global scratch of one workgroup of the large variant (words): six segment arrays + two queues
-#define SEGX_SCR_WORDS (6u * G2S_SEGX_CAP + 2u * G2S_SEGX_QCAP)
 #define SEGX_EMPTY64 0xFFFFFFFFFFFFFFFFull
-#define SEGX_TOMB64 0xFFFFFFFFFFFFFFFEull

@@ -81,7 +81,7 @@ def test_c5_full_size_vs_oracle(product, oracle):
     """BASELINE config 5 at its stated size: the 3 Mbp V3 graph, -dist-error 2000, 1 000 gaps of
     2-5 kbp (D = 4-7 k levels), every gap against the oracle.  This list holds the gaps whose
     segments, pending events and right-set entries outgrow the segment tier's LDS-resident
-    capacities: they run in its large variant (g2s_fill_segx)."""
+    capacities: they run in its large variant (g2s_fill_segw)."""
     reads = product.G2S.synth_genome(3000000, 3, 20240101)
     seqs = _seqs(reads)
     gaps = _parse_scaffolds(product.G2S.synth_gaps(reads, 31, 10, 1000, 2000, 5000, 20240103))
