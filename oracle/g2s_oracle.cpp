@@ -69,6 +69,60 @@ static inline u128 kmer_revcomp(u128 x, int k) {
   u128 y = ((u128)rc64_full((uint64_t)x) << 64) | (u128)rc64_full((uint64_t)(x >> 64));
   return y >> (128 - 2 * k);
 }
+// 256-bit k-mer word for 64 <= k <= 127, written here on its own (the product's kmer.hpp is not included, so the two
+// cannot share a bug).  w[0] holds the least significant 64 bits, w[3] the most significant.
+struct W256 {
+  uint64_t w[4];
+  W256(uint64_t v = 0) : w{v, 0, 0, 0} {}
+  explicit operator int() const { return (int)w[0]; }
+  W256 operator~() const { W256 r; for (int i = 0; i < 4; i++) r.w[i] = ~w[i]; return r; }
+  W256 operator|(const W256& o) const { W256 r; for (int i = 0; i < 4; i++) r.w[i] = w[i] | o.w[i]; return r; }
+  W256 operator&(const W256& o) const { W256 r; for (int i = 0; i < 4; i++) r.w[i] = w[i] & o.w[i]; return r; }
+  W256 operator-(const W256& o) const {
+    W256 r;
+    uint64_t borrow = 0;
+    for (int i = 0; i < 4; i++) {
+      const uint64_t d = w[i] - o.w[i];
+      r.w[i] = d - borrow;
+      borrow = (w[i] < o.w[i]) || (d < borrow);
+    }
+    return r;
+  }
+  W256 operator<<(int s) const {
+    W256 r;
+    const int q = s / 64, b = s % 64;
+    for (int i = 3; i >= q; i--) {
+      uint64_t v = w[i - q] << b;
+      if (b && i - q - 1 >= 0) v |= w[i - q - 1] >> (64 - b);
+      r.w[i] = v;
+    }
+    return r;
+  }
+  W256 operator>>(int s) const {
+    W256 r;
+    const int q = s / 64, b = s % 64;
+    for (int i = 0; i + q < 4; i++) {
+      uint64_t v = w[i + q] >> b;
+      if (b && i + q + 1 < 4) v |= w[i + q + 1] << (64 - b);
+      r.w[i] = v;
+    }
+    return r;
+  }
+  W256& operator>>=(int s) { return *this = *this >> s; }
+  bool operator==(const W256& o) const { return w[0] == o.w[0] && w[1] == o.w[1] && w[2] == o.w[2] && w[3] == o.w[3]; }
+  bool operator!=(const W256& o) const { return !(*this == o); }
+  bool operator<(const W256& o) const {
+    for (int i = 3; i >= 0; i--)
+      if (w[i] != o.w[i]) return w[i] < o.w[i];
+    return false;
+  }
+};
+static inline W256 kmer_revcomp(const W256& x, int k) {
+  W256 y;
+  for (int i = 0; i < 4; i++) y.w[i] = rc64_full(x.w[3 - i]);
+  return y >> (256 - 2 * k);
+}
+
 static inline uint64_t mix64(uint64_t z) {
   z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ULL;
   z = (z ^ (z >> 27)) * 0x94d049bb133111ebULL;
@@ -77,6 +131,11 @@ static inline uint64_t mix64(uint64_t z) {
 struct KHash {
   size_t operator()(uint64_t x) const { return (size_t)mix64(x); }
   size_t operator()(u128 x) const { return (size_t)(mix64((uint64_t)x) ^ mix64((uint64_t)(x >> 64) + 0x9e3779b97f4a7c15ULL)); }
+  size_t operator()(const W256& x) const {
+    uint64_t h = 0;
+    for (int i = 0; i < 4; i++) h = mix64(h ^ (x.w[i] + 0x9e3779b97f4a7c15ULL * (uint64_t)(i + 1)));
+    return (size_t)h;
+  }
 };
 
 // Exact membership set (open addressing).  Replaces GATB's Bloom + cFP (D1).
@@ -264,9 +323,10 @@ static GraphBase* build_graph(const std::vector<std::string>& seqs, int k, int s
 }
 
 GraphBase* graph_from_seqs(const std::vector<std::string>& seqs, int k, int solid) {
-  if (k < 1 || k > 63) return NULL;
+  if (k < 1 || k > 127) return NULL;
   if (k <= 31) return build_graph<uint64_t>(seqs, k, solid);
-  return build_graph<u128>(seqs, k, solid);
+  if (k <= 63) return build_graph<u128>(seqs, k, solid);
+  return build_graph<W256>(seqs, k, solid);
 }
 
 GraphBase* graph_from_files(const std::vector<std::string>& files, int k, int solid) {
@@ -833,8 +893,12 @@ int fill_gap(const GraphBase* g, GlibcRand& rng, const std::string& kmer_left, c
     r = fill_gap_t<uint64_t>(*static_cast<const OGraph<uint64_t>*>(g), rng, kmer_left, kmer_right, gap_len, k, gap_err,
                              left_max_fuz, right_max_fuz, left_fuz, right_fuz, max_mem, fill, skip_confident,
                              all_paths, substats, info, &extra);
-  else
+  else if (g->k <= 63)
     r = fill_gap_t<u128>(*static_cast<const OGraph<u128>*>(g), rng, kmer_left, kmer_right, gap_len, k, gap_err,
+                         left_max_fuz, right_max_fuz, left_fuz, right_fuz, max_mem, fill, skip_confident, all_paths,
+                         substats, info, &extra);
+  else
+    r = fill_gap_t<W256>(*static_cast<const OGraph<W256>*>(g), rng, kmer_left, kmer_right, gap_len, k, gap_err,
                          left_max_fuz, right_max_fuz, left_fuz, right_fuz, max_mem, fill, skip_confident, all_paths,
                          substats, info, &extra);
   if (info) info->sub = *substats;
@@ -849,7 +913,10 @@ static int fill_gap_logged(const GraphBase* g, GlibcRand& rng, const std::string
   if (g->k <= 31)
     return fill_gap_t<uint64_t>(*static_cast<const OGraph<uint64_t>*>(g), rng, kl, kr, gap_len, k, gap_err, lmf, rmf, lf,
                                 rf, max_mem, fill, skip_confident, all_paths, ss, info, log);
-  return fill_gap_t<u128>(*static_cast<const OGraph<u128>*>(g), rng, kl, kr, gap_len, k, gap_err, lmf, rmf, lf, rf,
+  if (g->k <= 63)
+    return fill_gap_t<u128>(*static_cast<const OGraph<u128>*>(g), rng, kl, kr, gap_len, k, gap_err, lmf, rmf, lf, rf,
+                            max_mem, fill, skip_confident, all_paths, ss, info, log);
+  return fill_gap_t<W256>(*static_cast<const OGraph<W256>*>(g), rng, kl, kr, gap_len, k, gap_err, lmf, rmf, lf, rf,
                           max_mem, fill, skip_confident, all_paths, ss, info, log);
 }
 

@@ -244,3 +244,33 @@ def scaffold_record(genome, k, fuz, pos_len_list, pad=5):
         cur = p + ln
     out.append(genome[cur:hi])
     return "".join(out)
+
+
+def strand_flip_genome(seed, length, k, n=5, fuz=6):
+    """Both strands of a k-mer at one depth (Q7) at any k: a genome with n hairpins (S + revcomp(S),
+    |S| > k/2: a palindromic k-mer at even k) and a second haplotype with n inversions of k + 2r bases (the middle
+    k-mer of an inversion and its reverse complement lie at the same depth from a seed in front of it).  Returns
+    (haplotypes, gaps): the gaps of cut_gaps over the genome, then one gap across every hairpin and inversion."""
+    rng = SplitMix(seed * 6151 + 5)
+    comp = {"A": "T", "C": "G", "G": "C", "T": "A"}
+    rc = lambda s: "".join(comp[c] for c in reversed(s))
+    g = list(random_dna(rng, length))
+    spots = []
+    base = k + fuz + 40
+    step = (length - base) // n  # (>= 2 (3k + 60) bases: a hairpin, then an inversion, each with its gap's flanks)
+    for j in range(n):
+        pos = base + j * step
+        h = k // 2 + rng.randint(1, 8)
+        s = random_dna(rng, h)
+        g[pos:pos + 2 * h] = s + rc(s)
+        spots.append((pos, pos + step // 2, k + 2 * rng.randint(2, 20)))
+    g = "".join(g)
+    h = g
+    for pos, ipos, m in spots:
+        h = h[:ipos] + rc(g[ipos:ipos + m]) + h[ipos + m:]
+    gaps = cut_gaps(seed, g, k, fuz=fuz, ngaps=2 * n, min_len=5, max_len=80, d_err=k + 10)
+    for pos, ipos, m in spots:
+        for a, b in ((pos - 20, pos + k + 20), (ipos - 10, ipos + m + 10)):
+            gaps.append(dict(left=g[a - k - fuz:a], right=g[b:b + k + fuz], gap_len=b - a + k, lmf=fuz, rmf=fuz,
+                             true_len=b - a))
+    return [g, h], gaps

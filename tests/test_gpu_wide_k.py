@@ -231,9 +231,10 @@ def test_single_gap_command_line_at_k127(product, monkeypatch, tmp_path):
     assert filled == [True, False, True]
 
 
-def test_c2_shaped_list_at_k127(product, monkeypatch, capfd):
-    """at size, without an oracle: the GPU graph equals the host graph; the host path, resident mode and the segment
-    tier on one and on two waves give identical results, and nothing falls back to the host"""
+def test_c2_shaped_list_at_k127(product, oracle, monkeypatch, capfd):
+    """at size: the GPU graph equals the host graph; the host path, resident mode and the segment tier on one and on
+    two waves give identical results, nothing falls back to the host, and the host path's FASTA and per-gap lines are
+    the CPU oracle's"""
     k = 127
     reads = product.G2S.synth_genome(3_000_000, 3, 20240101)
     seqs = [ln for ln in reads.splitlines() if not ln.startswith(">")]
@@ -265,6 +266,14 @@ def test_c2_shaped_list_at_k127(product, monkeypatch, capfd):
             _check_path(path, tm)
             outs[path] = (fa, _gap_lines(log))
         assert all(o == outs["host"] for o in outs.values())
+        og = oracle.OracleGraph(seqs, k, 1)
+        try:
+            assert og.num_kmers == gg.num_kmers
+            ofa, olog, sm = oracle.execute_scaffolds(og, scaf, k, solid=1, d_err=500, max_fuz=10, randseed=1)
+        finally:
+            og.free()
+        assert sm.gaps == 500 and sm.q7_gaps == 0
+        assert outs["host"] == (ofa, _gap_lines(olog))
     finally:
         gg.free()
         if gh is not None:

@@ -36,7 +36,8 @@ def test_glibc_rand_matches_this_libc(oracle):
             assert libc.rand() == r.next()
 
 
-def _compare_with_pyref(oracle, seqs, k, gaps, e, skip, allp):
+def _compare_with_pyref(oracle, seqs, k, gaps, e, skip, allp, q7=None):
+    """every gap of the oracle against pyref; returns the number filled (q7: a list that gets each gap's Q7 flag)"""
     og = oracle.OracleGraph(seqs, k, 1)
     pg = pyref.Graph(seqs, k, 1)
     assert og.num_kmers == len(pg.kmers)
@@ -52,6 +53,8 @@ def _compare_with_pyref(oracle, seqs, k, gaps, e, skip, allp):
         assert o.lengths == pi.lengths
         assert o.info.draws == pi.draws
         assert o.info.q7 == pi.q7
+        if q7 is not None:
+            q7.append(pi.q7)
         assert (o.left_fuz, o.right_fuz) == (lf2, rf2)
         assert [int(x) for x in o.info.ctr] == [pi.ctr[x] for x in ("xA", "sA", "xB", "sB", "xD", "sD")]
         if o.phase_d:

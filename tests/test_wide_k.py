@@ -1,8 +1,10 @@
 """k-mer lengths 64 to 127 on the host: the 256-bit k-mer word (kmer.hpp: u256, KmerOps<u256>), the host graph build
-against the string restatement (oracle/pyref.py), the graph cache at 32-byte k-mers and the accepted range of k.
+against the string restatement (oracle/pyref.py), the graph cache at 32-byte k-mers and the accepted range of k; and
+the CPU oracle's own 256-bit word (oracle/g2s_oracle.cpp: W256) against pyref.
 No GPU: without a device the build runs on the host threads."""
 import os
 import random
+import re
 import shutil
 import subprocess
 
@@ -10,6 +12,7 @@ import pytest
 
 import cases
 import pyref
+from test_oracle import _compare_with_pyref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "gap2seq_amd", "csrc")
@@ -199,3 +202,69 @@ def test_u256_kmer_codec(u256_probe):
         assert f[3] == _hex(rc if strand == 0 else fwd)
         assert f[4] == s and f[5] == pyref.revcomp(s)
         assert f[6] == "1" and f[7] == _hex(c)
+
+
+# ---- the oracle's 256-bit word, against pyref -------------------------------------------------------------------------
+
+@pytest.mark.parametrize("k", [64, 65, 96, 127])
+def test_oracle_at_wide_k_equals_python_restatement(oracle, k):
+    """the oracle's fill_gap at k >= 64 against pyref in all three fill modes: counts, fuz, draws, Q7 flags, work
+    counters, fill text and subgraph statistics.  The fixture puts both strands of a k-mer at one depth (Q7); at even
+    k its hairpins hold palindromic k-mers."""
+    seqs, gaps = cases.strand_flip_genome(k, 4000, k)
+    if k % 2 == 0:
+        assert any(seqs[0][i:i + k] == pyref.revcomp(seqs[0][i:i + k]) for i in range(len(seqs[0]) - k + 1))
+    e = k + 10
+    for skip, allp in ((False, True), (False, False), (True, True)):
+        q7 = []
+        filled = _compare_with_pyref(oracle, seqs, k, gaps, e, skip, allp, q7)
+        assert len(q7) == len(gaps) == 20
+        assert filled >= 12 and sum(q7) >= 3, (filled, sum(q7))
+
+
+@pytest.mark.parametrize("k", [63, 64, 65, 96, 127])
+def test_oracle_kmer_counts_at_wide_k(oracle, k):
+    """the solid k-mer set: reads with N/n breaks, lower case, a read shorter than k and reads seen two and three times"""
+    seqs = _reads(k)
+    seqs += [seqs[0][100:900], seqs[0][300:1100], seqs[1][:k - 1], seqs[1][200:200 + k]]
+    for solid in (1, 2, 3):
+        og = oracle.OracleGraph(seqs, k, solid)
+        try:
+            assert og.num_kmers == len(pyref.Graph(seqs, k, solid).kmers), solid
+        finally:
+            og.free()
+
+
+def test_oracle_rejects_k_above_127(oracle):
+    L = oracle.lib()
+    arr = (oracle.C.c_char_p * 1)(b"ACGT" * 100)
+    assert not L.orc_graph_from_seqs(arr, 1, 128, 1)
+    assert not L.orc_graph_from_seqs(arr, 1, 0, 1)
+    h = L.orc_graph_from_seqs(arr, 1, 127, 1)
+    assert h and L.orc_graph_num_kmers(h) > 0
+    L.orc_graph_free(h)
+
+
+def _gap_lines(log):
+    return [ln for ln in log.splitlines() if ln.startswith(("Scaffold:", "SubgraphStats:")) or re.match(r"Filled \d+ gaps out of \d+$", ln)]
+
+
+def test_oracle_scaffold_mode_at_k127_equals_python_restatement(oracle):
+    """execute_scaffolds at k = 127: FASTA and per-gap log lines of the oracle equal pyref's, with a multi-gap record"""
+    k, fuz, e = 127, 10, 100
+    seqs = cases.toy_genome(k, 12000, k, repeats=10, tandem=2, snp_every=400)
+    gl = cases.cut_gaps(k, seqs[0], k, fuz, 16, 50, 400, e)
+    records = [("g%d" % i, g["left"] + "N" * g["gap_len"] + g["right"]) for i, g in enumerate(gl)]
+    records.append(("multi", cases.scaffold_record(seqs[0], k, fuz, [(1000 + 1500 * j, 60 + 7 * j, 60 + 7 * j + 3) for j in range(6)])))
+    text = "".join(">%s\n%s\n" % r for r in records)
+    og = oracle.OracleGraph(seqs, k, 1)
+    try:
+        for skip in (False, True):
+            fa, log, sm = oracle.execute_scaffolds(og, text, k, solid=1, d_err=e, max_fuz=fuz, randseed=1, skip_confident=skip)
+            pfa, plog, pfilled, pgaps = pyref.execute_scaffolds(pyref.Graph(seqs, k, 1), records, k, e, fuz, 1, skip_confident=skip)
+            assert (sm.gaps, sm.filled) == (pgaps, pfilled) == (22, pfilled)
+            assert 5 <= pfilled < 22
+            assert fa == pfa
+            assert _gap_lines(log) == _gap_lines(plog)
+    finally:
+        og.free()

@@ -50,7 +50,7 @@ def draw_big(rng):
 def draw(rng, big_share=0.08):
     if rng.random() < big_share:
         return draw_big(rng)
-    k = rng.choice([9, 11, 13, 15, 21, 25, 31, 31, 31, 33, 41, 55, 63, 16, 32])
+    k = rng.choice([9, 11, 13, 15, 21, 25, 31, 31, 31, 33, 41, 55, 63, 16, 32, 32, 63, 64, 65, 127])
     length = rng.choice([2000, 5000, 20000, 60000, 200000])
     dens = rng.choice([0, 1, 1, 3, 8])  # structures per 10 kbp
     units = max(1, length // 10000)
