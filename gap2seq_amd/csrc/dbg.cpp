@@ -16,6 +16,9 @@ bool count_solid_gpu(Graph& g, const std::vector<std::pair<const char*, uint64_t
                      std::string* why);
 bool graph_finish_gpu(Graph& g, int device, const std::function<void(const std::vector<uint32_t>&, uint32_t)>& host_walk,
                       std::string* why);
+bool graph_build_sets_gpu(Graph& g, const std::vector<std::pair<const char*, uint64_t>>& seqs, const std::vector<uint32_t>& seq_set,
+                          uint32_t nsets, int solid, int device,
+                          const std::function<void(const std::vector<uint32_t>&, uint32_t)>& host_walk, std::string* why);
 
 namespace {
 
@@ -55,10 +58,22 @@ int64_t rank_of(const Graph& g, KT x) {
   return (lo < g.bucket[b + 1] && v[lo] == x) ? (int64_t)lo : -1;
 }
 
+// sorted rank of a canonical k-mer within ranks [lo, hi), or -1 (a set of a set graph)
 template <class KT>
-void build_bucket_index(Graph& g) {
+int64_t rank_in(const Graph& g, uint64_t lo, uint64_t hi, KT x) {
   const std::vector<KT>& v = kmer_vec<KT>(g);
-  g.bucket_bits = std::min(2 * g.k, 22);
+  const uint64_t end = hi;
+  while (lo < hi) {
+    const uint64_t mid = (lo + hi) >> 1;
+    if (v[(size_t)mid] < x) lo = mid + 1; else hi = mid;
+  }
+  return (lo < end && v[(size_t)lo] == x) ? (int64_t)lo : -1;
+}
+
+template <class KT>
+void build_bucket_index(Graph& g, int max_bits = 22) {
+  const std::vector<KT>& v = kmer_vec<KT>(g);
+  g.bucket_bits = std::min(2 * g.k, max_bits);
   const int shift = 2 * g.k - g.bucket_bits;
   const size_t nb = (size_t)1 << g.bucket_bits;
   g.bucket.assign(nb + 1, 0);
@@ -262,6 +277,9 @@ void build_ustart(Graph& g) {
 }
 
 template <class KT>
+void finish_graph_host(Graph& g, int nthreads);
+
+template <class KT>
 void finish_graph(Graph& g, int nthreads) {
   const auto f0 = std::chrono::steady_clock::now();
   if (g.bucket.empty()) build_bucket_index<KT>(g);  // (the GPU k-mer set brings its index along)
@@ -280,6 +298,12 @@ void finish_graph(Graph& g, int nthreads) {
               ok ? "" : why.c_str(), ok ? "" : ")");
     if (ok) return;
   }
+  finish_graph_host<KT>(g, nthreads);
+}
+
+template <class KT>
+void finish_graph_host(Graph& g, int nthreads) {
+  const auto f0 = std::chrono::steady_clock::now();
   std::vector<uint32_t> succ_r, pred_r;
   build_tables_rank<KT>(g, nthreads, &succ_r, &pred_r);
   const auto f1 = std::chrono::steady_clock::now();
@@ -325,7 +349,7 @@ void finish_graph(Graph& g, int nthreads) {
 }  // namespace
 
 uint32_t Graph::node_of(const char* s) const {
-  if (n == 0) return kInvalidNode;
+  if (n == 0 || num_sets() > 1) return kInvalidNode;
   int strand = 0;
   int64_t r;
   if (kmer_bytes == 8) {
@@ -340,6 +364,30 @@ uint32_t Graph::node_of(const char* s) const {
     u256 c;
     encode_kmer<u256>(s, k, &c, &strand);
     r = rank_of<u256>(*this, c);
+  }
+  if (r < 0) return kInvalidNode;
+  return 2 * rank2id[(size_t)r] + ((uint32_t)strand ^ (uint32_t)flip[(size_t)r]);
+}
+
+uint32_t Graph::node_of_in(uint32_t set, const char* s) const {
+  if (set >= num_sets()) return kInvalidNode;
+  if (set_lo.empty()) return node_of(s);
+  const uint64_t lo = set_lo[set], hi = set_lo[(size_t)set + 1];
+  if (lo == hi) return kInvalidNode;
+  int strand = 0;
+  int64_t r;
+  if (kmer_bytes == 8) {
+    uint64_t c;
+    encode_kmer<uint64_t>(s, k, &c, &strand);
+    r = rank_in<uint64_t>(*this, lo, hi, c);
+  } else if (kmer_bytes == 16) {
+    u128 c;
+    encode_kmer<u128>(s, k, &c, &strand);
+    r = rank_in<u128>(*this, lo, hi, c);
+  } else {
+    u256 c;
+    encode_kmer<u256>(s, k, &c, &strand);
+    r = rank_in<u256>(*this, lo, hi, c);
   }
   if (r < 0) return kInvalidNode;
   return 2 * rank2id[(size_t)r] + ((uint32_t)strand ^ (uint32_t)flip[(size_t)r]);
@@ -383,6 +431,132 @@ Graph* graph_build(const std::vector<std::pair<const char*, uint64_t>>& seqs, in
     fprintf(stderr, "[g2s] graph build: %llu k-mers; solid k-mer set %.3f s (%s), tables + unitig order %.3f s (%d threads)\n",
             (unsigned long long)g->n, std::chrono::duration<double>(t1 - t0).count(), set_on_gpu ? "GPU sort" : "host",
             std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count(), nthreads);
+  return g;
+}
+
+namespace {
+
+// One set's graph on one host thread (a small prefix index: sets are small), appended to the union at ranks and node
+// indices [off, off + n_s).
+template <class KT>
+void build_set_part(const std::vector<std::pair<const char*, uint64_t>>& seqs, int k, int solid, Graph* part) {
+  part->k = k;
+  part->solid = solid;
+  part->kmer_bytes = kmer_width(k);
+  count_solid<KT>(*part, seqs, solid, 1);
+  int bits = 1;
+  while (bits < 22 && (1ull << bits) < part->n) bits++;
+  build_bucket_index<KT>(*part, bits);
+  finish_graph_host<KT>(*part, 1);
+}
+
+template <class KT>
+void append_set_part(Graph& u, const Graph& p, uint64_t off) {
+  std::vector<KT>& uk = kmer_vec<KT>(u);
+  const std::vector<KT>& pk = kmer_vec<KT>(p);
+  std::copy(pk.begin(), pk.end(), uk.begin() + (ptrdiff_t)off);
+  const uint32_t o = (uint32_t)off;
+  for (uint64_t r = 0; r < p.n; r++) {
+    u.rank2id[(size_t)(off + r)] = p.rank2id[(size_t)r] + o;
+    u.id2rank[(size_t)(off + r)] = p.id2rank[(size_t)r] + o;
+    u.flip[(size_t)(off + r)] = p.flip[(size_t)r];
+  }
+  for (size_t q = 0; q < p.succ.size(); q++) u.succ[(size_t)off * 8 + q] = p.succ[q] == kInvalidNode ? kInvalidNode : p.succ[q] + 2 * o;
+  for (size_t q = 0; q < p.pred.size(); q++) u.pred[(size_t)off * 8 + q] = p.pred[q] == kInvalidNode ? kInvalidNode : p.pred[q] + 2 * o;
+  std::copy(p.lastnt.begin(), p.lastnt.end(), u.lastnt.begin() + (ptrdiff_t)(2 * off));
+}
+
+}  // namespace
+
+Graph* graph_build_sets(const std::vector<std::pair<const char*, uint64_t>>& seqs, const std::vector<uint32_t>& seq_set,
+                        uint32_t nsets, int k, int solid, int nthreads, std::string* err) {
+  if (k < 1 || k > kMaxK) { if (err) *err = "k must be in [1," + std::to_string(kMaxK) + "]"; return nullptr; }
+  if (nsets == 0 || seq_set.size() != seqs.size()) { if (err) *err = "graph_build_sets: no sets, or a set id per sequence missing"; return nullptr; }
+  for (uint32_t s : seq_set)
+    if (s >= nsets) { if (err) *err = "graph_build_sets: set id " + std::to_string(s) + " out of range"; return nullptr; }
+  if (nthreads <= 0) nthreads = (int)std::max(1u, std::thread::hardware_concurrency());
+  const auto t0 = std::chrono::steady_clock::now();
+  // on the GPU when there is one (dbg_gpu.hip: keyed k-mer sort, successors searched inside their set); even k, no
+  // device, G2S_HOST_BUILD=1, an empty union: the host build below, set by set
+  if (!getenv("G2S_HOST_BUILD")) {
+    Graph* g = new Graph();
+    g->k = k;
+    g->solid = solid;
+    g->kmer_bytes = kmer_width(k);
+    std::string why;
+    const bool ok = graph_build_sets_gpu(*g, seqs, seq_set, nsets, solid, getenv("G2S_DEVICE") ? atoi(getenv("G2S_DEVICE")) : 0,
+                                         [&](const std::vector<uint32_t>& succ_r, uint32_t first_id) {
+                                           unitig_order(succ_r, g->n, false, &g->rank2id, &g->flip, &g->n_unitigs, true, first_id);
+                                         }, &why);
+    if (ok) {
+      if (getenv("G2S_DEBUG"))
+        fprintf(stderr, "[g2s] set graph build: %u sets, %llu k-mers, %.3f s on the GPU\n", nsets, (unsigned long long)g->n,
+                std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+      return g;
+    }
+    if (getenv("G2S_DEBUG")) fprintf(stderr, "[g2s]   set graph on the host (%s)\n", why.c_str());
+    delete g;
+  }
+  std::vector<std::vector<std::pair<const char*, uint64_t>>> by_set(nsets);
+  for (size_t j = 0; j < seqs.size(); j++) by_set[seq_set[j]].push_back(seqs[j]);
+  const int kb = kmer_width(k);
+  std::vector<Graph*> parts(nsets, nullptr);
+  {
+    std::atomic<uint32_t> next(0);
+    auto work = [&]() {
+      while (true) {
+        const uint32_t s = next.fetch_add(1);
+        if (s >= nsets) break;
+        Graph* p = new Graph();
+        if (kb == 8) build_set_part<uint64_t>(by_set[s], k, solid, p);
+        else if (kb == 16) build_set_part<u128>(by_set[s], k, solid, p);
+        else build_set_part<u256>(by_set[s], k, solid, p);
+        parts[s] = p;
+      }
+    };
+    std::vector<std::thread> th;
+    for (int t = 1; t < std::min<int>(nthreads, (int)nsets); t++) th.emplace_back(work);
+    work();
+    for (auto& x : th) x.join();
+  }
+  Graph* g = new Graph();
+  g->k = k;
+  g->solid = solid;
+  g->kmer_bytes = kb;
+  g->set_lo.assign((size_t)nsets + 1, 0);
+  for (uint32_t s = 0; s < nsets; s++) {
+    g->set_lo[(size_t)s + 1] = g->set_lo[s] + parts[s]->n;
+    g->n_unitigs += parts[s]->n_unitigs;
+  }
+  g->n = g->set_lo[nsets];
+  if (g->n >= (1ull << 30)) {
+    if (err) *err = "too many k-mers for 32-bit oriented node ids";
+    for (Graph* p : parts) delete p;
+    delete g;
+    return nullptr;
+  }
+  if (kb == 8) g->kmers64.resize((size_t)g->n);
+  else if (kb == 16) g->kmers128.resize((size_t)g->n);
+  else g->kmers256.resize((size_t)g->n);
+  g->rank2id.assign((size_t)g->n, 0);
+  g->id2rank.assign((size_t)g->n, 0);
+  g->flip.assign((size_t)g->n, 0);
+  g->succ.assign((size_t)g->n * 8, kInvalidNode);
+  if (k % 2 == 0) g->pred.assign((size_t)g->n * 8, kInvalidNode);
+  g->lastnt.assign((size_t)g->n * 2, 0);
+  parallel_for(nsets, std::min(nthreads, 16), [&](uint64_t b, uint64_t e, int) {
+    for (uint64_t s = b; s < e; s++) {
+      if (kb == 8) append_set_part<uint64_t>(*g, *parts[s], g->set_lo[s]);
+      else if (kb == 16) append_set_part<u128>(*g, *parts[s], g->set_lo[s]);
+      else append_set_part<u256>(*g, *parts[s], g->set_lo[s]);
+      delete parts[s];
+      parts[s] = nullptr;
+    }
+  });
+  build_ustart(*g);
+  if (getenv("G2S_DEBUG"))
+    fprintf(stderr, "[g2s] set graph build: %u sets, %llu k-mers, %.3f s on the host (%d threads)\n", nsets,
+            (unsigned long long)g->n, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(), nthreads);
   return g;
 }
 

@@ -75,9 +75,16 @@ struct Graph {
   // (v +/- 2) is exact: every node there has exactly one predecessor and one successor.
   std::vector<uint64_t> ustart;
   std::map<int, DeviceGraph> dev; // per device copies
+  // Set graphs (graph_build_sets): the disjoint union of one graph per read set, numbered set-major — set s holds
+  // the node indices AND the sorted ranks [set_lo[s], set_lo[s+1]), its k-mers sorted within that range, no edge
+  // leaves it.  Empty for a graph of one read set.
+  std::vector<uint64_t> set_lo;
+  uint32_t num_sets() const { return set_lo.empty() ? 1u : (uint32_t)(set_lo.size() - 1); }
 
-  // buildNode + contains
+  // buildNode + contains (kInvalidNode on a graph of several sets: a k-mer is a node of each set it is solid in)
   uint32_t node_of(const char* s) const;
+  // ...restricted to one set's range
+  uint32_t node_of_in(uint32_t set, const char* s) const;
   inline uint32_t succ_of(uint32_t v, int nt) const { return succ[(size_t)v * 4 + nt]; }
   // predecessor i in GATB order (prepend T,G,A,C)
   inline uint32_t pred_of(uint32_t v, int nt) const {
@@ -96,6 +103,11 @@ static inline int kmer_width(int k) { return k <= 31 ? 8 : k <= 63 ? 16 : 32; }
 // seqs may contain any bytes; k-mers containing N/n are skipped (GATB model).
 Graph* graph_build(const std::vector<std::pair<const char*, uint64_t>>& seqs, int k, int solid, int nthreads,
                    std::string* err);
+// One graph per read set, built on `nthreads` host threads (a set per thread at a time) and concatenated set-major
+// (Graph::set_lo); seq_set[j] < nsets names the set of seqs[j].  Every set's part is what graph_build gives for its
+// sequences alone, up to the numbering of nodes.
+Graph* graph_build_sets(const std::vector<std::pair<const char*, uint64_t>>& seqs, const std::vector<uint32_t>& seq_set,
+                        uint32_t nsets, int k, int solid, int nthreads, std::string* err);
 bool graph_save(const Graph& g, const std::string& path, std::string* err);
 Graph* graph_load(const std::string& path, std::string* err);
 

@@ -167,6 +167,33 @@ __global__ void k_succ(const KT* __restrict__ v, const uint32_t* __restrict__ bu
   *(uint4*)(succ + (size_t)t * 4) = make_uint4(out[0], out[1], out[2], out[3]);
 }
 
+// set graphs (dbg.cpp: graph_build_sets): the neighbour searched inside its own set's rank range only — sets are small,
+// a binary search over the range replaces the prefix index over the union
+template <class KT>
+__global__ void k_succ_set(const KT* __restrict__ v, const uint32_t* __restrict__ rank_set, const uint32_t* __restrict__ set_lo,
+                           uint32_t n2, int k, uint32_t* __restrict__ succ) {
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;  // oriented node in rank space: 2*rank + strand
+  if (t >= n2) return;
+  const KT mask = (2 * k >= (int)(8 * sizeof(KT))) ? ~(KT)0 : ((((KT)1) << (2 * k)) - 1);
+  const KT c = v[t >> 1], rc = d_revcomp(c, k);
+  const KT seq = (t & 1u) ? rc : c, rseq = (t & 1u) ? c : rc;
+  const uint32_t set = rank_set[t >> 1], lo0 = set_lo[set], hi0 = set_lo[set + 1];
+  uint32_t out[4];
+#pragma unroll
+  for (int nt = 0; nt < 4; nt++) {
+    const KT y = ((seq << 2) | (KT)nt) & mask;
+    const KT ry = (rseq >> 2) | ((KT)(nt ^ 2) << (2 * (k - 1)));
+    const KT x = y < ry ? y : ry;
+    uint32_t lo = lo0, hi = hi0;
+    while (lo < hi) {
+      const uint32_t mid = (lo + hi) >> 1;
+      if (v[mid] < x) lo = mid + 1; else hi = mid;
+    }
+    out[nt] = (lo < hi0 && v[lo] == x) ? 2u * lo + (y < ry ? 0u : 1u) : INV;
+  }
+  *(uint4*)(succ + (size_t)t * 4) = make_uint4(out[0], out[1], out[2], out[3]);
+}
+
 // ---- tables in id space (dbg.cpp: finish_graph) ----------------------------------------------
 template <class KT>
 __global__ void k_remap(const KT* __restrict__ v, const uint32_t* __restrict__ succ_r, const uint32_t* __restrict__ rank2id,
@@ -292,6 +319,85 @@ __global__ void k_bucket(const KT* __restrict__ v, uint32_t n, int shift, uint32
   bucket[b] = lo;
 }
 
+// ---- keyed solid k-mer sets (set graphs): sort key (set, canonical k-mer), set most significant
+// the set of every text position: seq_start[j] = where sequence j starts in the text (one separator after each)
+__global__ void k_pos_set(const uint64_t* __restrict__ seq_start, const uint32_t* __restrict__ seq_set, uint32_t nseqs, uint64_t T,
+                          uint32_t* __restrict__ sid) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= T) return;
+  uint32_t lo = 0, hi = nseqs;  // the last sequence starting at or before i
+  while (hi - lo > 1) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (seq_start[mid] <= i) lo = mid; else hi = mid;
+  }
+  sid[i] = seq_set[lo];
+}
+// word w (little-endian 64-bit words) of every key in the order of the passes so far (idx == nullptr: text order);
+// w == -1: the key's set id
+template <class KT>
+__global__ void k_key_word(const KT* __restrict__ keys, const uint32_t* __restrict__ sid, const uint32_t* __restrict__ idx, uint64_t n,
+                           int w, uint64_t* __restrict__ word, uint32_t* __restrict__ iota) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t j = idx ? idx[i] : (uint32_t)i;
+  word[i] = w < 0 ? (uint64_t)sid[j] : ((const uint64_t*)(keys + j))[w];
+  if (!idx) iota[i] = (uint32_t)i;
+}
+template <class KT>
+__global__ void k_gather_keyed(const KT* __restrict__ keys, const uint32_t* __restrict__ sid, const uint32_t* __restrict__ idx,
+                               uint64_t n, KT* __restrict__ out, uint32_t* __restrict__ out_sid) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  out[i] = keys[idx[i]];
+  out_sid[i] = sid[idx[i]];
+}
+// run heads and tails over (set, k-mer); the all-ones filler (a window with an N, or over a separator) is no k-mer
+template <class KT>
+__global__ void k_heads_keyed(const KT* __restrict__ keys, const uint32_t* __restrict__ sid, uint64_t n, uint32_t* __restrict__ flag) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const KT x = keys[i];
+  flag[i] = (x != ~(KT)0 && (i == 0 || keys[i - 1] != x || sid[i - 1] != sid[i])) ? 1u : 0u;
+}
+// run j = [hidx[j], tidx[j]]; (a position's run: the inclusive scan of the heads minus one)
+template <class KT>
+__global__ void k_runs_keyed(const KT* __restrict__ keys, const uint32_t* __restrict__ sid, const uint32_t* __restrict__ flag,
+                             const uint32_t* __restrict__ pos, uint64_t n, uint32_t* __restrict__ hidx, uint32_t* __restrict__ tidx) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const KT x = keys[i];
+  if (x == ~(KT)0) return;
+  const uint32_t run = pos[i] + flag[i] - 1u;
+  if (flag[i]) hidx[run] = (uint32_t)i;
+  if (i + 1 == n || keys[i + 1] != x || sid[i + 1] != sid[i]) tidx[run] = (uint32_t)i;
+}
+__global__ void k_solid_keyed(const uint32_t* __restrict__ hidx, const uint32_t* __restrict__ tidx, uint32_t nruns, uint32_t solid,
+                              uint32_t* __restrict__ keep) {
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= nruns) return;
+  keep[j] = (tidx[j] - hidx[j] + 1u >= solid) ? 1u : 0u;
+}
+template <class KT>
+__global__ void k_compact_keyed(const KT* __restrict__ keys, const uint32_t* __restrict__ sid, const uint32_t* __restrict__ hidx,
+                                const uint32_t* __restrict__ keep, const uint32_t* __restrict__ kpos, uint32_t nruns,
+                                KT* __restrict__ out, uint32_t* __restrict__ out_sid) {
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= nruns || !keep[j]) return;
+  out[kpos[j]] = keys[hidx[j]];
+  out_sid[kpos[j]] = sid[hidx[j]];
+}
+// every set's first rank in the set-major solid k-mer array (nsets + 1 entries, the last = n)
+__global__ void k_set_first(const uint32_t* __restrict__ rank_set, uint32_t n, uint32_t nsets, uint32_t* __restrict__ set_lo) {
+  const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s > nsets) return;
+  uint32_t lo = 0, hi = n;
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (rank_set[mid] < s) lo = mid + 1; else hi = mid;
+  }
+  set_lo[s] = lo;
+}
+
 struct Dev {
   void* p = nullptr;
   ~Dev() { if (p) (void)hipFree(p); }
@@ -311,7 +417,8 @@ namespace g2s {
 // used; nothing of g is touched then and the caller runs the host build.
 template <class KT>
 static bool finish_gpu_t(Graph& g, const std::vector<KT>& kmers, int device,
-                         const std::function<void(const std::vector<uint32_t>&, uint32_t)>& host_walk, std::string* why) {
+                         const std::function<void(const std::vector<uint32_t>&, uint32_t)>& host_walk, std::string* why,
+                         const std::vector<uint32_t>* rank_set = nullptr) {
 #define G2S_GPU_TRY(expr)                                                                 \
   do {                                                                                    \
     hipError_t e_ = (expr);                                                               \
@@ -328,12 +435,24 @@ static bool finish_gpu_t(Graph& g, const std::vector<KT>& kmers, int device,
   Dev d_km, d_bucket, d_succ, d_nxt, d_pd0, d_pd1, d_len, d_tail, d_cnt, d_base, d_id, d_flip, d_flag, d_tmp;
   // ---- successor table, rank space
   G2S_GPU_TRY(d_km.alloc(kmers.size() * sizeof(KT)));
-  G2S_GPU_TRY(d_bucket.alloc(g.bucket.size() * 4));
   G2S_GPU_TRY(d_succ.alloc((size_t)n2 * 16));
   G2S_GPU_TRY(hipMemcpy(d_km.p, kmers.data(), kmers.size() * sizeof(KT), hipMemcpyHostToDevice));
-  G2S_GPU_TRY(hipMemcpy(d_bucket.p, g.bucket.data(), g.bucket.size() * 4, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(k_succ<KT>, grd, blk, 0, 0, (const KT*)d_km.p, (const uint32_t*)d_bucket.p, 2 * k - g.bucket_bits, n2, k,
-                     (uint32_t*)d_succ.p);
+  if (rank_set) {  // set graph: every neighbour searched in its own set's range (g.set_lo)
+    Dev d_rs, d_sl;
+    std::vector<uint32_t> lo32(g.set_lo.begin(), g.set_lo.end());
+    G2S_GPU_TRY(d_rs.alloc((size_t)n * 4));
+    G2S_GPU_TRY(d_sl.alloc(lo32.size() * 4));
+    G2S_GPU_TRY(hipMemcpy(d_rs.p, rank_set->data(), (size_t)n * 4, hipMemcpyHostToDevice));
+    G2S_GPU_TRY(hipMemcpy(d_sl.p, lo32.data(), lo32.size() * 4, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_succ_set<KT>, grd, blk, 0, 0, (const KT*)d_km.p, (const uint32_t*)d_rs.p, (const uint32_t*)d_sl.p, n2, k,
+                       (uint32_t*)d_succ.p);
+    G2S_GPU_TRY(hipDeviceSynchronize());
+  } else {
+    G2S_GPU_TRY(d_bucket.alloc(g.bucket.size() * 4));
+    G2S_GPU_TRY(hipMemcpy(d_bucket.p, g.bucket.data(), g.bucket.size() * 4, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_succ<KT>, grd, blk, 0, 0, (const KT*)d_km.p, (const uint32_t*)d_bucket.p, 2 * k - g.bucket_bits, n2, k,
+                       (uint32_t*)d_succ.p);
+  }
   // ---- numbering along unitigs: list ranking
   G2S_GPU_TRY(d_nxt.alloc((size_t)n2 * 4));
   G2S_GPU_TRY(d_pd0.alloc((size_t)n2 * 8));
@@ -391,6 +510,16 @@ static bool finish_gpu_t(Graph& g, const std::vector<KT>& kmers, int device,
     G2S_GPU_TRY(hipMemcpy(g.rank2id.data(), d_id.p, (size_t)n * 4, hipMemcpyDeviceToHost));
     G2S_GPU_TRY(hipMemcpy(g.flip.data(), d_flip.p, (size_t)n, hipMemcpyDeviceToHost));
     host_walk(succ_r, next_id);
+    if (rank_set) {
+      // Set graphs: the walk numbered the circular unitigs after every set; each moves to the end of its own set's
+      // range (a stable reorder of the ids by set: list ranking's ids are set-major already — a chain's head and its
+      // nodes are in one set, heads take ids in rank order)
+      std::vector<uint32_t> id_set((size_t)n);
+      for (uint64_t r = 0; r < n; r++) id_set[g.rank2id[(size_t)r]] = (*rank_set)[(size_t)r];
+      std::vector<uint32_t> fill(g.set_lo.begin(), g.set_lo.end() - 1), new_id((size_t)n);
+      for (uint64_t id = 0; id < n; id++) new_id[(size_t)id] = fill[id_set[(size_t)id]]++;
+      for (uint64_t r = 0; r < n; r++) g.rank2id[(size_t)r] = new_id[g.rank2id[(size_t)r]];
+    }
     G2S_GPU_TRY(hipMemcpy(d_id.p, g.rank2id.data(), (size_t)n * 4, hipMemcpyHostToDevice));
     G2S_GPU_TRY(hipMemcpy(d_flip.p, g.flip.data(), (size_t)n, hipMemcpyHostToDevice));
   }
@@ -587,6 +716,164 @@ static bool count_solid_gpu_t(Graph& g, std::vector<KT>& out, const std::vector<
   g.bucket_bits = bits;
   return true;
 #undef G2S_GPU_TRY
+}
+
+// The solid k-mer sets of a set graph at once: one key per text position (all sets' sequences in one text, the set
+// from a per-sequence table), sorted by (set, canonical k-mer) — LSD passes over the k-mer's 64-bit words, then one
+// stable pass over the set id, as (word, index) pairs with one gather at the end — runs over (set, k-mer), solidity per
+// run, compaction, every set's first rank.  out / rank_set / g.set_lo set-major; false (g untouched) when the device
+// cannot be used.
+template <class KT>
+static bool count_solid_sets_gpu_t(Graph& g, std::vector<KT>& out, std::vector<uint32_t>* rank_set,
+                                   const std::vector<std::pair<const char*, uint64_t>>& seqs, const std::vector<uint32_t>& seq_set,
+                                   uint32_t nsets, int solid, int device, std::string* why) {
+#define G2S_GPU_TRY(expr)                                                                 \
+  do {                                                                                    \
+    hipError_t e_ = (expr);                                                               \
+    if (e_ != hipSuccess) { if (why) *why = std::string(#expr) + ": " + hipGetErrorString(e_); return false; } \
+  } while (0)
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) { if (why) *why = "no device"; return false; }
+  G2S_GPU_TRY(hipSetDevice(device));
+  const int k = g.k;
+  uint64_t T = 0;
+  for (auto& sq : seqs) T += sq.second + 1;  // one separator after every sequence
+  if (T == 0 || T >= (1ull << 32) || seqs.empty()) { if (why) *why = "text size"; return false; }
+  size_t free_b = 0, total_b = 0;
+  G2S_GPU_TRY(hipMemGetInfo(&free_b, &total_b));
+  // (bytes a text position at the peak: keys, set ids, word and index double buffers, the sort's scratch, the gathered copies)
+  const double per_pos = (double)(2 * sizeof(KT) + 56);
+  if ((double)T * per_pos > 0.5 * (double)free_b) { if (why) *why = "text too large for the device"; return false; }
+  std::vector<uint8_t> text((size_t)T);
+  std::vector<uint64_t> start(seqs.size());
+  {
+    size_t pos = 0;
+    for (size_t j = 0; j < seqs.size(); j++) {
+      start[j] = pos;
+      memcpy(text.data() + pos, seqs[j].first, (size_t)seqs[j].second);
+      pos += (size_t)seqs[j].second;
+      text[pos++] = 'N';
+    }
+  }
+  const uint32_t ns = (uint32_t)seqs.size();
+  Dev d_text, d_start, d_sset, d_keys, d_sid, d_w0, d_w1, d_i0, d_i1, d_tmp, d_sk, d_ss, d_flag, d_pos, d_hidx, d_tidx, d_keep,
+      d_kpos, d_out, d_osid, d_lo;
+  G2S_GPU_TRY(d_text.alloc((size_t)T));
+  G2S_GPU_TRY(d_start.alloc((size_t)ns * 8));
+  G2S_GPU_TRY(d_sset.alloc((size_t)ns * 4));
+  G2S_GPU_TRY(d_keys.alloc((size_t)T * sizeof(KT)));
+  G2S_GPU_TRY(d_sid.alloc((size_t)T * 4));
+  G2S_GPU_TRY(hipMemcpy(d_text.p, text.data(), (size_t)T, hipMemcpyHostToDevice));
+  G2S_GPU_TRY(hipMemcpy(d_start.p, start.data(), (size_t)ns * 8, hipMemcpyHostToDevice));
+  G2S_GPU_TRY(hipMemcpy(d_sset.p, seq_set.data(), (size_t)ns * 4, hipMemcpyHostToDevice));
+  const dim3 blk(256), grdT((unsigned)((T + 255) / 256));
+  hipLaunchKernelGGL(k_extract<KT>, grdT, blk, 0, 0, (const uint8_t*)d_text.p, T, k, (KT*)d_keys.p);
+  hipLaunchKernelGGL(k_pos_set, grdT, blk, 0, 0, (const uint64_t*)d_start.p, (const uint32_t*)d_sset.p, ns, T, (uint32_t*)d_sid.p);
+  for (Dev* d : {&d_text, &d_start, &d_sset}) (void)hipFree(d->release());
+  // ---- sort: (word, index) pairs, least significant word first, the set id last (every pass stable)
+  G2S_GPU_TRY(d_w0.alloc((size_t)T * 8));
+  G2S_GPU_TRY(d_w1.alloc((size_t)T * 8));
+  G2S_GPU_TRY(d_i0.alloc((size_t)T * 4));
+  G2S_GPU_TRY(d_i1.alloc((size_t)T * 4));
+  uint64_t *w_in = (uint64_t*)d_w0.p, *w_out = (uint64_t*)d_w1.p;
+  uint32_t *i_in = (uint32_t*)d_i0.p, *i_out = (uint32_t*)d_i1.p;
+  size_t tb = 0;
+  G2S_GPU_TRY(rocprim::radix_sort_pairs(nullptr, tb, w_in, w_out, i_in, i_out, (size_t)T, 0, 64));
+  G2S_GPU_TRY(d_tmp.alloc(tb));
+  constexpr int W = (int)(sizeof(KT) / 8);
+  for (int w = 0; w <= W; w++) {
+    const int word = w < W ? w : -1;
+    hipLaunchKernelGGL(k_key_word<KT>, grdT, blk, 0, 0, (const KT*)d_keys.p, (const uint32_t*)d_sid.p,
+                       w == 0 ? (const uint32_t*)nullptr : (const uint32_t*)i_in, T, word, w_in, i_in);
+    G2S_GPU_TRY(rocprim::radix_sort_pairs(d_tmp.p, tb, w_in, w_out, i_in, i_out, (size_t)T, 0, word < 0 ? 32 : 64));
+    std::swap(i_in, i_out);
+  }
+  for (Dev* d : {&d_w0, &d_w1, &d_tmp}) (void)hipFree(d->release());
+  G2S_GPU_TRY(d_sk.alloc((size_t)T * sizeof(KT)));
+  G2S_GPU_TRY(d_ss.alloc((size_t)T * 4));
+  hipLaunchKernelGGL(k_gather_keyed<KT>, grdT, blk, 0, 0, (const KT*)d_keys.p, (const uint32_t*)d_sid.p, (const uint32_t*)i_in, T,
+                     (KT*)d_sk.p, (uint32_t*)d_ss.p);
+  for (Dev* d : {&d_i0, &d_i1, &d_keys, &d_sid}) (void)hipFree(d->release());
+  const KT* sk = (const KT*)d_sk.p;
+  const uint32_t* ss = (const uint32_t*)d_ss.p;
+  // ---- runs over (set, k-mer) -> the k-mers seen at least `solid` times in their own set
+  G2S_GPU_TRY(d_flag.alloc((size_t)T * 4));
+  G2S_GPU_TRY(d_pos.alloc((size_t)T * 4));
+  hipLaunchKernelGGL(k_heads_keyed<KT>, grdT, blk, 0, 0, sk, ss, T, (uint32_t*)d_flag.p);
+  size_t tb2 = 0;
+  G2S_GPU_TRY(rocprim::exclusive_scan(nullptr, tb2, (const uint32_t*)d_flag.p, (uint32_t*)d_pos.p, 0u, (size_t)T,
+                                      rocprim::plus<uint32_t>()));
+  Dev d_tmp2;
+  G2S_GPU_TRY(d_tmp2.alloc(tb2));
+  G2S_GPU_TRY(rocprim::exclusive_scan(d_tmp2.p, tb2, (const uint32_t*)d_flag.p, (uint32_t*)d_pos.p, 0u, (size_t)T,
+                                      rocprim::plus<uint32_t>()));
+  uint32_t lastf = 0, lastp = 0;
+  G2S_GPU_TRY(hipMemcpy(&lastf, (const uint32_t*)d_flag.p + (T - 1), 4, hipMemcpyDeviceToHost));
+  G2S_GPU_TRY(hipMemcpy(&lastp, (const uint32_t*)d_pos.p + (T - 1), 4, hipMemcpyDeviceToHost));
+  const uint32_t nruns = lastp + lastf;
+  uint32_t n_solid = 0;
+  if (nruns) {
+    G2S_GPU_TRY(d_hidx.alloc((size_t)nruns * 4));
+    G2S_GPU_TRY(d_tidx.alloc((size_t)nruns * 4));
+    G2S_GPU_TRY(d_keep.alloc((size_t)nruns * 4));
+    G2S_GPU_TRY(d_kpos.alloc((size_t)nruns * 4));
+    hipLaunchKernelGGL(k_runs_keyed<KT>, grdT, blk, 0, 0, sk, ss, (const uint32_t*)d_flag.p, (const uint32_t*)d_pos.p, T,
+                       (uint32_t*)d_hidx.p, (uint32_t*)d_tidx.p);
+    const dim3 grdR((nruns + 255) / 256);
+    hipLaunchKernelGGL(k_solid_keyed, grdR, blk, 0, 0, (const uint32_t*)d_hidx.p, (const uint32_t*)d_tidx.p, nruns,
+                       (uint32_t)std::max(1, solid), (uint32_t*)d_keep.p);
+    size_t tb3 = 0;
+    G2S_GPU_TRY(rocprim::exclusive_scan(nullptr, tb3, (const uint32_t*)d_keep.p, (uint32_t*)d_kpos.p, 0u, (size_t)nruns,
+                                        rocprim::plus<uint32_t>()));
+    Dev d_tmp3;
+    G2S_GPU_TRY(d_tmp3.alloc(tb3));
+    G2S_GPU_TRY(rocprim::exclusive_scan(d_tmp3.p, tb3, (const uint32_t*)d_keep.p, (uint32_t*)d_kpos.p, 0u, (size_t)nruns,
+                                        rocprim::plus<uint32_t>()));
+    uint32_t lk = 0, lkp = 0;
+    G2S_GPU_TRY(hipMemcpy(&lk, (const uint32_t*)d_keep.p + (nruns - 1), 4, hipMemcpyDeviceToHost));
+    G2S_GPU_TRY(hipMemcpy(&lkp, (const uint32_t*)d_kpos.p + (nruns - 1), 4, hipMemcpyDeviceToHost));
+    n_solid = lk + lkp;
+    if (n_solid) {
+      G2S_GPU_TRY(d_out.alloc((size_t)n_solid * sizeof(KT)));
+      G2S_GPU_TRY(d_osid.alloc((size_t)n_solid * 4));
+      hipLaunchKernelGGL(k_compact_keyed<KT>, grdR, blk, 0, 0, sk, ss, (const uint32_t*)d_hidx.p, (const uint32_t*)d_keep.p,
+                         (const uint32_t*)d_kpos.p, nruns, (KT*)d_out.p, (uint32_t*)d_osid.p);
+    }
+  }
+  // ---- every set's first rank
+  std::vector<uint32_t> lo32((size_t)nsets + 1, 0);
+  std::vector<KT> host((size_t)n_solid);
+  std::vector<uint32_t> rs((size_t)n_solid);
+  if (n_solid) {
+    G2S_GPU_TRY(d_lo.alloc(((size_t)nsets + 1) * 4));
+    hipLaunchKernelGGL(k_set_first, dim3((nsets + 1 + 255) / 256), blk, 0, 0, (const uint32_t*)d_osid.p, n_solid, nsets, (uint32_t*)d_lo.p);
+    G2S_GPU_TRY(hipMemcpy(lo32.data(), d_lo.p, lo32.size() * 4, hipMemcpyDeviceToHost));
+    G2S_GPU_TRY(hipMemcpy(host.data(), d_out.p, (size_t)n_solid * sizeof(KT), hipMemcpyDeviceToHost));
+    G2S_GPU_TRY(hipMemcpy(rs.data(), d_osid.p, (size_t)n_solid * 4, hipMemcpyDeviceToHost));
+  }
+  G2S_GPU_TRY(hipGetLastError());
+  out.swap(host);
+  rank_set->swap(rs);
+  g.n = n_solid;
+  g.set_lo.assign(lo32.begin(), lo32.end());
+  return true;
+#undef G2S_GPU_TRY
+}
+
+bool graph_build_sets_gpu(Graph& g, const std::vector<std::pair<const char*, uint64_t>>& seqs, const std::vector<uint32_t>& seq_set,
+                          uint32_t nsets, int solid, int device,
+                          const std::function<void(const std::vector<uint32_t>&, uint32_t)>& host_walk, std::string* why) {
+  if ((g.k % 2) == 0) { if (why) *why = "even k"; return false; }
+  std::vector<uint32_t> rank_set;
+  bool ok;
+  if (g.kmer_bytes == 32) ok = count_solid_sets_gpu_t<u256>(g, g.kmers256, &rank_set, seqs, seq_set, nsets, solid, device, why);
+  else if (g.kmer_bytes == 16) ok = count_solid_sets_gpu_t<u128>(g, g.kmers128, &rank_set, seqs, seq_set, nsets, solid, device, why);
+  else ok = count_solid_sets_gpu_t<uint64_t>(g, g.kmers64, &rank_set, seqs, seq_set, nsets, solid, device, why);
+  if (!ok) return false;
+  if (g.kmer_bytes == 32) ok = finish_gpu_t<u256>(g, g.kmers256, device, host_walk, why, &rank_set);
+  else if (g.kmer_bytes == 16) ok = finish_gpu_t<u128>(g, g.kmers128, device, host_walk, why, &rank_set);
+  else ok = finish_gpu_t<uint64_t>(g, g.kmers64, device, host_walk, why, &rank_set);
+  return ok;
 }
 
 bool count_solid_gpu(Graph& g, const std::vector<std::pair<const char*, uint64_t>>& seqs, int solid, int device,

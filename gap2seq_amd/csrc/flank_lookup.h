@@ -30,7 +30,10 @@ struct FlankDesc {
 #define G2S_LK_256 2
 #define G2S_FLANK_TEXT_MAX 2048 /* bytes of flank text per gap the kernel stages in LDS */
 
+// ranges (set graphs, g2s_fill_sets): not null = descriptor i's k-mers are searched in sorted ranks
+// [ranges[i].x, ranges[i].y) only, its gap's read set, by binary search (the prefix index is not used)
 hipError_t launch_resolve_flanks(hipStream_t st, const FlankLookup& lk, uint32_t ngaps, const FlankDesc* desc /* device-readable */,
-                                 const char* text /* device-readable */, uint32_t* nodes_dev, uint32_t* nodes_host);
+                                 const char* text /* device-readable */, uint32_t* nodes_dev, uint32_t* nodes_host,
+                                 const uint2* ranges = nullptr /* device-readable */);
 
 }  // namespace g2s

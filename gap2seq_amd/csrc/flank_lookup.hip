@@ -25,6 +25,25 @@ namespace {
 using g2s::u128;
 using g2s::u256;
 
+// the k characters at byte `off` of the text at tw, searched among sorted ranks [lo, hi) only: one read set of a set
+// graph (its k-mers sorted within the set's range, no prefix index over the union)
+template <class KT>
+__device__ __forceinline__ uint32_t flank_node_in(const g2s::FlankLookup& lk, const uint32_t* tw, int off, uint32_t lo, uint32_t hi) {
+  const int k = lk.k;
+  const KT* v = (const KT*)lk.kmers;
+  const KT f = g2s::flank_encode<KT>(tw, off, k);
+  const KT r = g2s::d_revcomp(f, k);
+  const bool fwd = f < r;
+  const KT canon = fwd ? f : r;
+  const uint32_t end = hi;
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (v[mid] < canon) lo = mid + 1; else hi = mid;
+  }
+  if (lo >= end || !(v[lo] == canon)) return G2S_DEV_INVALID;
+  return lk.rank2node[lo] ^ (fwd ? 0u : 1u);
+}
+
 // FLANK_WAVES waves a workgroup, a gap per wave at a time (a quarter of the dispatches of one-wave workgroups).  What
 // rocprofv3 shows as this kernel's 75-80 us on a 10 000-gap list is mostly the 1.5 MB copy of descriptors and flank text
 // in front of it (53 us with the look-ups switched off; the look-ups themselves ~22 us)
@@ -32,7 +51,8 @@ using g2s::u256;
 template <class KT>
 __global__ __launch_bounds__(64 * FLANK_WAVES) void g2s_resolve_flanks(g2s::FlankLookup lk, const g2s::FlankDesc* __restrict__ desc,
                                                                        const char* __restrict__ text, uint32_t* __restrict__ nodes_dev,
-                                                                       uint32_t* __restrict__ nodes_host, uint32_t ngaps) {
+                                                                       uint32_t* __restrict__ nodes_host, uint32_t ngaps,
+                                                                       const uint2* __restrict__ ranges) {
   // the gap's flank text: [left: first k+lmf chars][right: first k+rmf chars][right: last k+rmf chars] — the last part
   // left out when it is the second (a flank of exactly k+rmf characters: what GapCutter writes)
   // (+20 / +36: flank_encode reads sizeof(KT) + 1 words from an item's first, 33 of them at 256 bits)
@@ -53,8 +73,10 @@ __global__ __launch_bounds__(64 * FLANK_WAVES) void g2s_resolve_flanks(g2s::Flan
     for (uint32_t w = (uint32_t)lane; w < words; w += 64u) tw[w] = ((const uint32_t*)(text + d.text_off))[w];  // (4-byte aligned, padded)
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");  // (the wave's own words: no other wave reads them)
     __builtin_amdgcn_wave_barrier();
+    const uint2 rg = ranges ? ranges[gap] : make_uint2(0u, 0u);
     for (int i = lane; i < nl + 2 * nr; i += 64) {
-      const uint32_t node = g2s::flank_node_of<KT>(lk, tw, g2s::flank_item_offset(i, k, (int)d.lmf, rmf, tail));
+      const int at = g2s::flank_item_offset(i, k, (int)d.lmf, rmf, tail);
+      const uint32_t node = ranges ? flank_node_in<KT>(lk, tw, at, rg.x, rg.y) : g2s::flank_node_of<KT>(lk, tw, at);
       nodes_dev[d.flank_off + (uint32_t)i] = node;
       nodes_host[d.flank_off + (uint32_t)i] = node;
     }
@@ -68,15 +90,15 @@ __global__ __launch_bounds__(64 * FLANK_WAVES) void g2s_resolve_flanks(g2s::Flan
 namespace g2s {
 
 hipError_t launch_resolve_flanks(hipStream_t st, const FlankLookup& lk, uint32_t ngaps, const FlankDesc* desc, const char* text,
-                                 uint32_t* nodes_dev, uint32_t* nodes_host) {
+                                 uint32_t* nodes_dev, uint32_t* nodes_host, const uint2* ranges) {
   if (ngaps == 0) return hipSuccess;
   const uint32_t wgs = std::min<uint32_t>((ngaps + FLANK_WAVES - 1u) / FLANK_WAVES, 4096u);
   if (lk.wide == G2S_LK_256)
-    hipLaunchKernelGGL(g2s_resolve_flanks<u256>, dim3(wgs), dim3(64 * FLANK_WAVES), 0, st, lk, desc, text, nodes_dev, nodes_host, ngaps);
+    hipLaunchKernelGGL(g2s_resolve_flanks<u256>, dim3(wgs), dim3(64 * FLANK_WAVES), 0, st, lk, desc, text, nodes_dev, nodes_host, ngaps, ranges);
   else if (lk.wide)
-    hipLaunchKernelGGL(g2s_resolve_flanks<u128>, dim3(wgs), dim3(64 * FLANK_WAVES), 0, st, lk, desc, text, nodes_dev, nodes_host, ngaps);
+    hipLaunchKernelGGL(g2s_resolve_flanks<u128>, dim3(wgs), dim3(64 * FLANK_WAVES), 0, st, lk, desc, text, nodes_dev, nodes_host, ngaps, ranges);
   else
-    hipLaunchKernelGGL(g2s_resolve_flanks<uint64_t>, dim3(wgs), dim3(64 * FLANK_WAVES), 0, st, lk, desc, text, nodes_dev, nodes_host, ngaps);
+    hipLaunchKernelGGL(g2s_resolve_flanks<uint64_t>, dim3(wgs), dim3(64 * FLANK_WAVES), 0, st, lk, desc, text, nodes_dev, nodes_host, ngaps, ranges);
   return hipGetLastError();
 }
 

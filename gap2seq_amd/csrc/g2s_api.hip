@@ -116,6 +116,35 @@ extern "C" int g2s_graph_build_seqs(const char* const* seqs, const uint64_t* len
   return G2S_OK;
 }
 
+extern "C" int g2s_graph_build_sets(const char* const* seqs, const uint64_t* lens, const uint32_t* seq_set, int nseqs,
+                                    uint32_t nsets, int k, int solid, int nthreads, g2s_graph** out) {
+  if ((!seqs && nseqs) || (!seq_set && nseqs) || !out || nseqs < 0 || nsets == 0) return fail(G2S_ERR_ARG, "g2s_graph_build_sets: bad argument");
+  for (int i = 0; i < nseqs; i++)
+    if (seq_set[i] >= nsets) return fail(G2S_ERR_ARG, "g2s_graph_build_sets: set id out of range");
+  if (nsets == 1) return g2s_graph_build_seqs(seqs, lens, nseqs, k, solid, nthreads, out);  // an ordinary graph
+  std::vector<std::pair<const char*, uint64_t>> v;
+  for (int i = 0; i < nseqs; i++) v.emplace_back(seqs[i], lens ? lens[i] : (uint64_t)strlen(seqs[i]));
+  std::string err;
+  Graph* g = graph_build_sets(v, std::vector<uint32_t>(seq_set, seq_set + nseqs), nsets, k, solid, nthreads, &err);
+  if (!g) return fail(G2S_ERR_ARG, err);
+  *out = new g2s_graph();
+  (*out)->g = g;
+  return G2S_OK;
+}
+extern "C" uint32_t g2s_graph_num_sets(const g2s_graph* g) { return g ? g->g->num_sets() : 0; }
+extern "C" int g2s_graph_set_nodes(const g2s_graph* g, uint32_t set, uint64_t* first_kmer, uint64_t* n_kmers) {
+  if (!g || set >= g->g->num_sets()) return fail(G2S_ERR_ARG, "g2s_graph_set_nodes: bad set");
+  const uint64_t lo = g->g->set_lo.empty() ? 0 : g->g->set_lo[set];
+  const uint64_t hi = g->g->set_lo.empty() ? g->g->n : g->g->set_lo[(size_t)set + 1];
+  if (first_kmer) *first_kmer = lo;
+  if (n_kmers) *n_kmers = hi - lo;
+  return G2S_OK;
+}
+extern "C" uint32_t g2s_graph_set_node(const g2s_graph* g, uint32_t set, const char* kmer) {
+  if (!g || !kmer || (int)strnlen(kmer, (size_t)g->g->k) < g->g->k) return G2S_INVALID_NODE;
+  return g->g->node_of_in(set, kmer);
+}
+
 extern "C" int g2s_graph_build_files(const char* reads_csv, int k, int solid, int nthreads, g2s_graph** out) {
   if (!reads_csv || !out) return fail(G2S_ERR_ARG, "g2s_graph_build_files: bad argument");
   std::vector<FastxRecord> recs;
@@ -144,6 +173,7 @@ extern "C" int g2s_graph_build_files(const char* reads_csv, int k, int solid, in
 extern "C" int g2s_graph_save(const g2s_graph* g, const char* path) {
   std::string err;
   if (!g || !path) return fail(G2S_ERR_ARG, "g2s_graph_save: bad argument");
+  if (g->g->num_sets() > 1) return fail(G2S_ERR_ARG, "g2s_graph_save: graphs of several read sets are not saved");
   return graph_save(*g->g, path, &err) ? G2S_OK : fail(G2S_ERR_IO, err);
 }
 extern "C" int g2s_graph_load(const char* path, g2s_graph** out) {
@@ -665,6 +695,11 @@ struct g2s_session {
   bool share_timed = false, share_two = false;
   uint32_t share_win[G2S_RAND_WINDOW];
   bool resident_off = false;
+  uint32_t seed0 = 0;  // what srand() was given at creation (randseed, or time(NULL) for 0)
+  // g2s_fill_sets: the read set of every gap of the list being prepared (set graphs: the look-ups search that set
+  // only), and the look-up kernel's per-descriptor rank ranges (pinned)
+  const uint32_t* set_gaps = nullptr;
+  PinBuf h_ranges;
 };
 
 static void d3_pending_drop(g2s_session* s);  // (D3Pending is defined with phase D3's launch code below)
@@ -744,7 +779,8 @@ extern "C" int g2s_session_create(g2s_graph* g, int device, const g2s_params* p,
   s->params = *p;
   memset(&s->last_timing, 0, sizeof s->last_timing);
   // srand((randseed > 0) ? randseed : time(NULL)) (Gap2Seq.cpp:178); params keep the user's value for the echo (:191)
-  s->rcache.seed(p->randseed > 0 ? p->randseed : (uint32_t)time(nullptr));
+  s->seed0 = p->randseed > 0 ? p->randseed : (uint32_t)time(nullptr);
+  s->rcache.seed(s->seed0);
   if (const char* env = GENV("G2S_NO_LDS_TIER")) s->no_lds_tier = atoi(env) != 0;
   hipError_t e = hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking);
   if (e == hipSuccess) e = hipStreamCreateWithFlags(&s->stream2, hipStreamNonBlocking);
@@ -889,6 +925,8 @@ struct g2s_batch {
   uint32_t* nodes = nullptr;   // oriented flank nodes of every gap (written by the look-up kernel)
   size_t n_desc = 0, n_nodes = 0;
   bool host_lookup = false;    // flanks too long for the kernel's staging buffer: resolved on the host
+  bool set_list = false;       // g2s_fill_sets: flanks resolved in the gap's read set, every gap's rand() stream restarted
+  uint2* ranges = nullptr;     // ...the look-up kernel's rank range per descriptor (the session's h_ranges)
   // what resident mode needs of the list, gathered by the preparation's own passes
   bool has_skip = false, seg_tier_all = true;  // a gap carries a skip rule; every gap with flanks fits the segment tier
   int gmax = 0, dmax = 0;                       // longest gap, deepest search
@@ -967,7 +1005,7 @@ static TierData* take_tier(g2s_session* s, size_t /*unused*/) {
 
 // Can a list of n gaps be finished on the device (run_resident)?  The checks that do not look at the gaps.
 static bool resident_applicable(const g2s_session* s, size_t n) {
-  if (s->resident_off || n == 0) return false;
+  if (s->resident_off || n == 0 || s->set_gaps) return false;  // (set lists: phase D on the host, streams restarted per gap)
   const int forced = GENV("G2S_RESIDENT") ? atoi(GENV("G2S_RESIDENT")) : -1;  // (1: lists of any length; 0: never)
   // (lists of a few dozen gaps: the host analyses gaps while the launch's stragglers run and is done before four
   // more launches would be; measured on config 2's 500 gaps: 0.32 ms on the device against 0.35-0.39 ms.  The
@@ -989,6 +1027,8 @@ extern "C" int g2s_batch_prepare(g2s_session* s, const g2s_gap* gaps, size_t n, 
   REFUSE_IN_FLIGHT(s, "g2s_batch_prepare");
   const Graph& g = *s->graph->g;
   const int k = g.k;
+  const uint32_t* gap_set = s->set_gaps;
+  if (g.num_sets() > 1 && !gap_set) return fail(G2S_ERR_ARG, "g2s_batch_prepare: a graph of several read sets is filled by g2s_fill_sets");
   const auto tp0 = std::chrono::steady_clock::now();
   g2s_batch* b = new g2s_batch();
   b->s = s;
@@ -1113,6 +1153,11 @@ extern "C" int g2s_batch_prepare(g2s_session* s, const g2s_gap* gaps, size_t n, 
   const size_t desc_bytes = (n_desc * sizeof(FlankDesc) + 15) & ~(size_t)15;
   const size_t text_pad = (text_bytes + 16 + 15) & ~(size_t)15;
   if (b->pin->ensure(desc_bytes + text_pad + n_nodes * 4 + 16) != hipSuccess) { delete b; return fail(G2S_ERR_NOMEM, "pinned flank buffer"); }
+  b->set_list = gap_set != nullptr;
+  if (b->set_list && !b->host_lookup) {
+    if (s->h_ranges.ensure(std::max<size_t>(n_desc, 1) * sizeof(uint2)) != hipSuccess) { delete b; return fail(G2S_ERR_NOMEM, "pinned set ranges"); }
+    b->ranges = (uint2*)s->h_ranges.p;
+  }
   b->desc = (FlankDesc*)b->pin->p;
   b->text = (char*)b->pin->p + desc_bytes;
   b->nodes = (uint32_t*)((char*)b->pin->p + desc_bytes + text_pad);
@@ -1159,11 +1204,20 @@ extern "C" int g2s_batch_prepare(g2s_session* s, const g2s_gap* gaps, size_t n, 
         d.flank_off = b->flank_off[i];
         d.lmf = (uint16_t)j.lmf;
         d.rmf = (uint16_t)j.rmf;
-        if (b->host_lookup) {  // node ids on the host (Graph::node_of), uploaded by upload_flanks
+        if (b->host_lookup && b->set_list) {  // ...in the gap's read set (Graph::node_of_in)
+          const uint32_t set = gap_set[i];
+          uint32_t* fn = b->nodes + b->flank_off[i];
+          for (int x = 0; x <= j.lmf; x++) *fn++ = g.node_of_in(set, t + x);
+          for (int x = 0; x <= j.rmf; x++) *fn++ = g.node_of_in(set, t + ll + rl2 + (rl2 - k - x));
+          for (int x = 0; x <= j.rmf; x++) *fn++ = g.node_of_in(set, t + ll + x);
+        } else if (b->host_lookup) {  // node ids on the host (Graph::node_of), uploaded by upload_flanks
           uint32_t* fn = b->nodes + b->flank_off[i];
           for (int x = 0; x <= j.lmf; x++) *fn++ = g.node_of(t + x);                          // :995,1083
           for (int x = 0; x <= j.rmf; x++) *fn++ = g.node_of(t + ll + rl2 + (rl2 - k - x));   // :878,954
           for (int x = 0; x <= j.rmf; x++) *fn++ = g.node_of(t + ll + x);                     // :1113
+        } else if (b->ranges) {
+          const uint32_t set = gap_set[i];
+          b->ranges[didx[i]] = g.set_lo.empty() ? make_uint2(0u, (uint32_t)g.n) : make_uint2((uint32_t)g.set_lo[set], (uint32_t)g.set_lo[(size_t)set + 1]);
         }
       }
     };
@@ -1242,9 +1296,11 @@ int g2s_batch::upload_flanks(bool allow_inline) {
         d_desc = s->d_fstage.p;
         d_text = (char*)s->d_fstage.p + ((const char*)text - (const char*)desc);
       }
+      void* d_ranges = nullptr;
+      if (e == hipSuccess && ranges) e = hipHostGetDevicePointer(&d_ranges, ranges, 0);
       if (e == hipSuccess)
         e = launch_resolve_flanks(s->stream, s->lookup, (uint32_t)n_desc, (const FlankDesc*)d_desc, (const char*)d_text,
-                                  (uint32_t*)s->d_flank.p, (uint32_t*)d_nodes);
+                                  (uint32_t*)s->d_flank.p, (uint32_t*)d_nodes, (const uint2*)d_ranges);
     }
   }
   if (e != hipSuccess) return fail(G2S_ERR_HIP, std::string("batch flank look-up: ") + hipGetErrorString(e));
@@ -2328,6 +2384,9 @@ int batch_stage1(g2s_batch* b, bool analyze, g2s_result* results) {
 int batches_stage2(const std::vector<g2s_batch*>& bs, g2s_session* lead, g2s_result* results, char* arena,
                    g2s_timing* timing, bool analyze) {
   const Graph& g = *lead->graph->g;
+  // set lists (g2s_fill_sets): every gap draws from the start of the stream (a fresh srand(randseed) per gap), and the
+  // stream is not consumed
+  const bool restart = !bs.empty() && bs[0]->set_list;
   const FillParams fp = fill_params_of(lead);
   auto t_begin = std::chrono::steady_clock::now();
   size_t n = 0;
@@ -2357,7 +2416,7 @@ int batches_stage2(const std::vector<g2s_batch*>& bs, g2s_session* lead, g2s_res
   bool serial = false;
   size_t draws_used = 0;
 
-  size_t draws_total = 0;
+  size_t draws_total = 0, restart_max = 0;
   bool prev_filled = false;
   int prev_right_fuz = 0;
   bool jobs_in_flight = false;  // tracebacks of an earlier segment are reading the rand() buffer
@@ -2406,6 +2465,7 @@ int batches_stage2(const std::vector<g2s_batch*>& bs, g2s_session* lead, g2s_res
       if (in.kind != 0) { prev_filled = false; continue; }
       int right_fuz = 0;
       if (in.n_len > 0) {
+        if (restart) draws_total = 0;
         rand_off[gi] = draws_total;
         if (in.n_len > 1) grow_rands(draws_total + 1);
         const int pick = in.n_len > 1 ? (int)(lead->rcache.at_const(draws_total) % in.n_len) : 0;
@@ -2444,12 +2504,14 @@ int batches_stage2(const std::vector<g2s_batch*>& bs, g2s_session* lead, g2s_res
         }
         expect_draws[gi] = draws;
         draws_total += (size_t)draws;
+        if (restart) restart_max = std::max(restart_max, draws_total);
       }
       prev_filled = (in.filled & 1) != 0;
       prev_right_fuz = right_fuz;
     }
+    if (restart) draws_total = restart_max;
     grow_rands(draws_total + 1);
-    draws_used = draws_total;
+    draws_used = restart ? 0 : draws_total;
     ms_order += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     ms_order_loop = ms_order;
   };
@@ -2474,7 +2536,7 @@ int batches_stage2(const std::vector<g2s_batch*>& bs, g2s_session* lead, g2s_res
   // (tests: G2S_STAGE2_BLOCK=<gaps per block> makes short lists take this path too, two blocks and up)
   static const size_t fb_env = getenv("G2S_STAGE2_BLOCK") ? (size_t)std::max(1, atoi(getenv("G2S_STAGE2_BLOCK"))) : 0;
   const size_t FB = fb_env ? fb_env : 1024;
-  const bool blocks = n >= 2 * FB;
+  const bool blocks = !restart && n >= 2 * FB;
   const size_t nblk = blocks ? (n + FB - 1) / FB : 0;
   std::vector<size_t> blk_fix(nblk, 0), blk_fixbase(nblk + 1, 0), blk_rest(nblk, 0);
   std::vector<uint32_t> blk_varbase(nblk + 1, 0), vrank(blocks ? n : 0), vars_flat;
@@ -3845,8 +3907,10 @@ extern "C" int g2s_batch_run(g2s_batch* b, g2s_result* results, char* arena, siz
   // rand() values are input independent: materialise what this batch will need while the
   // GPU runs (one draw per traced base plus one per gap, Gap2Seq.cpp:1440,1513)
   size_t rand_need = 0;
-  for (size_t i = 0; i < n; i++)
-    rand_need += (size_t)(b->jobs[i].g + s->graph->g->k + b->jobs[i].lmf + b->jobs[i].rmf + 2);
+  for (size_t i = 0; i < n; i++) {
+    const size_t need = (size_t)(b->jobs[i].g + s->graph->g->k + b->jobs[i].lmf + b->jobs[i].rmf + 2);
+    rand_need = b->set_list ? std::max(rand_need, need) : rand_need + need;  // (set lists: every gap from the start)
+  }
   s->bg.submit([s, rand_need]() { s->rcache.ensure(rand_need); });
   s->tier_cursor = 0;
   b->arena = arena;
@@ -4489,6 +4553,60 @@ extern "C" int g2s_fill_batch(g2s_session* s, const g2s_gap* gaps, size_t n, g2s
   return rc;
 }
 
+// Independent gaps over a set graph: the wrapper's per-gap Gap2Seq-core runs (Gap2Seq.py:133-218) in one list.  The
+// fill kernels see the disjoint union of the sets' graphs as one graph; the look-ups search each gap's own set
+// (upload_flanks: the look-up kernel's rank ranges; host look-ups: Graph::node_of_in), and phase D gives every gap the
+// stream of a fresh srand(randseed) (batches_stage2: restart) from a generator of its own, so the session's is left as
+// it was.  Cut into groups of the size g2s_fill_batch cuts lists with (the HBM of one launch's state logs); groups
+// change nothing, every gap being on its own.
+extern "C" int g2s_fill_sets(g2s_session* s, const g2s_gap* gaps, const uint32_t* gap_set, size_t n, g2s_result* results,
+                             char* fill_arena, size_t arena_cap) {
+  g2s_env_sync();
+  if (!s || (n && (!gaps || !gap_set || !results))) return fail(G2S_ERR_ARG, "g2s_fill_sets: bad argument");
+  REFUSE_IN_FLIGHT(s, "g2s_fill_sets");
+  if (!s->helpers.empty() || s->in_team_list) return fail(G2S_ERR_STATE, "g2s_fill_sets: the session is in a team");
+  const uint32_t nsets = s->graph->g->num_sets();
+  for (size_t i = 0; i < n; i++) {
+    if (gap_set[i] >= nsets) return fail(G2S_ERR_ARG, "g2s_fill_sets: set id out of range");
+    if (gaps[i].skip_if_prev_right_fuz_gt != -1) return fail(G2S_ERR_ARG, "g2s_fill_sets: independent gaps carry no skip rule");
+  }
+  const auto t_begin = std::chrono::steady_clock::now();
+  RandCache fresh;
+  fresh.seed(s->params.randseed > 0 ? s->params.randseed : s->seed0);
+  s->rcache.swap(fresh);
+  const size_t group = team_group_for(s, n);
+  g2s_timing total;
+  memset(&total, 0, sizeof total);
+  int rc = G2S_OK;
+  size_t aoff = 0;
+  for (size_t off = 0; off < n && rc == G2S_OK; off += group) {
+    const size_t cnt = std::min(group, n - off);
+    s->set_gaps = gap_set + off;
+    g2s_batch* b = nullptr;
+    rc = g2s_batch_prepare(s, gaps + off, cnt, &b);
+    if (rc != G2S_OK) break;
+    // (set_gaps stays up through the run: resident_applicable keeps the list on the host path)
+    rc = g2s_batch_run(b, results + off, fill_arena ? fill_arena + std::min(aoff, arena_cap) : nullptr, aoff <= arena_cap ? arena_cap - aoff : 0);
+    if (rc == G2S_OK) {
+      for (size_t q = 0; q < cnt; q++) results[off + q].fill_off += (uint64_t)aoff;  // (offsets within the group's share)
+      const g2s_timing& t = b->timing;
+      total.ms_right_bfs += t.ms_right_bfs; total.ms_left_dp += t.ms_left_dp; total.ms_extract += t.ms_extract;
+      total.ms_host_post += t.ms_host_post; total.ms_fill_lds += t.ms_fill_lds; total.ms_fill_seg += t.ms_fill_seg;
+      total.ms_fill_segx += t.ms_fill_segx; total.flank_bytes += t.flank_bytes; total.fill_bytes += t.fill_bytes;
+      total.lds_tier_gaps += t.lds_tier_gaps; total.seg_tier_gaps += t.seg_tier_gaps; total.segx_tier_gaps += t.segx_tier_gaps;
+      total.seg_launches += t.seg_launches; total.segx_launches += t.segx_launches; total.lds_launches += t.lds_launches;
+    }
+    aoff += b->arena_bytes;
+    g2s_batch_free(b);
+  }
+  s->set_gaps = nullptr;
+  s->bg.wait();  // (nobody materialises values into the list's generator any more)
+  s->rcache.swap(fresh);
+  total.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+  s->last_timing = total;
+  return rc;
+}
+
 // ---- lists in flight (Gap2Seq-core -stream-gaps, bench.py --stream-lists): the product's steady state is a
 // SEQUENCE of lists, and a list's step is a chain — preparation, look-ups, fill kernel, phase D3, of which the last
 // writes the results through the link.  g2s_fill_begin queues all of it and returns; g2s_fill_end finishes the oldest
@@ -5026,6 +5144,18 @@ extern "C" int64_t g2s_graph_validate(const g2s_graph* gr, char* msg, size_t msg
     if (!only(b ^ 1u, a ^ 1u)) note("internal edge is not the only successor (odd orientation)", i);
   }
   if (starts != g.n_unitigs) note("bitmap population differs from the unitig count", starts);
+  if (!g.set_lo.empty()) {  // set graphs: the sets' ranges tile the nodes, no edge leaves its set
+    if (g.set_lo.front() != 0 || g.set_lo.back() != g.n) note("set ranges do not cover the k-mers", g.n);
+    for (size_t s = 0; s + 1 < g.set_lo.size(); s++) {
+      if (g.set_lo[s] > g.set_lo[s + 1]) { note("set ranges not ascending", g.set_lo[s]); continue; }
+      for (uint64_t i = g.set_lo[s]; i < g.set_lo[s + 1]; i++)
+        for (uint32_t v = (uint32_t)(2 * i); v <= (uint32_t)(2 * i + 1); v++)
+          for (int nt = 0; nt < 4; nt++) {
+            const uint32_t w = g.succ_of(v, nt);
+            if (w != kInvalidNode && ((w >> 1) < g.set_lo[s] || (w >> 1) >= g.set_lo[s + 1])) note("successor outside its set", i);
+          }
+    }
+  }
   for (uint64_t v = 0; v < 2 * g.n; v++)
     for (int nt = 0; nt < 4; nt++) {
       const uint32_t w = g.succ_of((uint32_t)v, nt);

@@ -1,0 +1,291 @@
+// gap2seq_amd/csrc/libraries_main.cpp — `Gap2Seq-libraries`: the wrapper's libraries flow (Gap2Seq.py -l,
+// /root/reference/src/Gap2Seq.py:133-218) in one process.  For every gap the wrapper extracts the reads of every library
+// that can belong to it (ReadFilter), adds every library's unmapped reads when too few bases came out, and runs a fresh
+// Gap2Seq-core over those reads alone.  Here the reads are extracted the same way (g2s_filter_reads), every gap's reads
+// become one read set of a set graph (g2s_graph_build_sets) and the gaps are filled as one list (g2s_fill_sets): every
+// gap's fill is what its own Gap2Seq-core -reads S(i) -left L -right R -length G run writes.
+//
+//   Gap2Seq-libraries -libraries libs.txt -gaps gaps.fa -bed gaps.bed -filled out.fa
+//                     [-k 31] [-fuz 10] [-solid 2] [-dist-error 500] [-max-mem 20] [-randseed 0]
+//                     [-all-upper] [-unique] [-best-only] [-device D]
+//
+// libs.txt: tab separated `bam mean std_dev threshold`, one library a line.  out.fa: per gap, in input order,
+// `comment\nfill\n` (the file GapMerger -gaps takes); stdout ends with `Filled X out of Y gaps`.
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <iostream>
+#include <sstream>
+#include <string>
+#include <vector>
+
+#include "../../include/g2s.h"
+#include "fastx.hpp"
+
+namespace {
+
+struct Library {
+  std::string bam;
+  int mean = 0, sd = 0;
+  double threshold = 0;
+  std::string unmapped;  // FASTA text of the library's unmapped reads ("" when none: no file, Gap2Seq.py:164-167)
+};
+
+struct GapRec {
+  std::string comment, left, right, scaffold;
+  int gap_length = 0, flank_length = 0, breakpoint = 0;
+};
+
+// `grep '^[^>;]' file | wc -c` (Gap2Seq.py:156-159): bytes of the lines that do not start with '>' or ';', newlines included
+size_t sequence_bytes(const std::string& fasta) {
+  size_t n = 0, p = 0;
+  while (p < fasta.size()) {
+    size_t e = fasta.find('\n', p);
+    const bool nl = e != std::string::npos;
+    if (!nl) e = fasta.size();
+    if (e > p && fasta[p] != '>' && fasta[p] != ';') n += (e - p) + (nl ? 1 : 0);
+    p = e + 1;
+  }
+  return n;
+}
+
+// parse_gap (Gap2Seq.py:246-262): left up to the first N/n, right after the last one
+GapRec parse_gap(const std::string& record, const std::string& bed_line) {
+  GapRec g;
+  const size_t nl = record.find('\n');
+  g.comment = record.substr(0, nl);
+  std::string seq;
+  if (nl != std::string::npos)
+    for (size_t i = nl + 1; i < record.size(); i++)
+      if (record[i] != '\n') seq += record[i];
+  const size_t first = seq.find_first_of("Nn"), last = seq.find_last_of("Nn");
+  g.left = first == std::string::npos ? seq.substr(0, seq.size() ? seq.size() - 1 : 0) : seq.substr(0, first);  // (find -1)
+  g.right = last == std::string::npos ? seq : seq.substr(last + 1);
+  g.flank_length = (int)std::min(g.left.size(), g.right.size());
+  g.gap_length = (int)seq.size() - (int)g.left.size() - (int)g.right.size();
+  std::vector<std::string> cols;
+  std::stringstream ss(bed_line);
+  std::string c;
+  while (std::getline(ss, c, '\t')) cols.push_back(c);
+  g.scaffold = cols.size() > 0 ? cols[0] : "";
+  g.breakpoint = (cols.size() > 1 ? atoi(cols[1].c_str()) : 0) + (int)g.left.size();
+  return g;
+}
+
+// the gap records of the gaps file as the wrapper cuts them (Gap2Seq.py:284-294): a new record at every '>' line
+std::vector<std::string> gap_records(const std::string& text) {
+  std::vector<std::string> out;
+  std::string cur;
+  size_t p = 0;
+  while (p < text.size()) {
+    size_t e = text.find('\n', p);
+    e = e == std::string::npos ? text.size() : e + 1;
+    const std::string line = text.substr(p, e - p);
+    if (!line.empty() && line[0] == '>' && !cur.empty()) { out.push_back(cur); cur.clear(); }
+    cur += line;
+    p = e;
+  }
+  if (!cur.empty()) out.push_back(cur);
+  return out;
+}
+
+std::string filter(const Library& lib, const g2s_filter_opts& base, const std::string& scaffold, int breakpoint, int gap_length,
+                   int flank_length, bool unmapped_only, bool* ok) {
+  g2s_filter_opts o = base;
+  o.mean_insert = lib.mean;
+  o.std_dev = lib.sd;
+  o.scaffold = scaffold.c_str();
+  o.breakpoint = breakpoint;
+  o.gap_length = gap_length;
+  o.flank_length = flank_length;
+  o.unmapped_only = unmapped_only ? 1 : 0;
+  char *fasta = nullptr, *log = nullptr, *warn = nullptr;
+  int64_t extracted = 0, total = 0;
+  *ok = g2s_filter_reads(lib.bam.c_str(), &o, &fasta, &log, &warn, &extracted, &total) == G2S_OK;
+  std::string out = (*ok && extracted > 0 && fasta) ? std::string(fasta) : std::string();
+  g2s_free(fasta);
+  g2s_free(log);
+  g2s_free(warn);
+  return out;
+}
+
+}  // namespace
+
+int main(int argc, char** argv) {
+  std::string libs_path, gaps_path, bed_path, filled_path;
+  int k = 31, fuz = 10, solid = 2, derr = 500, device = 0;
+  double max_mem = 20;
+  uint32_t randseed = 0;
+  bool upper = false, unique = false, best = false;
+  for (int i = 1; i < argc; i++) {
+    const std::string a = argv[i];
+    auto val = [&]() -> const char* { return (i + 1 < argc) ? argv[++i] : ""; };
+    if (a == "-libraries") libs_path = val();
+    else if (a == "-gaps") gaps_path = val();
+    else if (a == "-bed") bed_path = val();
+    else if (a == "-filled") filled_path = val();
+    else if (a == "-k") k = atoi(val());
+    else if (a == "-fuz") fuz = atoi(val());
+    else if (a == "-solid") solid = atoi(val());
+    else if (a == "-dist-error") derr = atoi(val());
+    else if (a == "-max-mem") max_mem = atof(val());
+    else if (a == "-randseed") randseed = (uint32_t)strtoul(val(), nullptr, 10);
+    else if (a == "-device") device = atoi(val());
+    else if (a == "-all-upper") upper = true;
+    else if (a == "-unique") unique = true;
+    else if (a == "-best-only") best = true;
+    else { std::cerr << "Gap2Seq-libraries: unknown parameter '" << a << "'" << std::endl; return EXIT_FAILURE; }
+  }
+  if (libs_path.empty() || gaps_path.empty() || bed_path.empty() || filled_path.empty()) {
+    std::cerr << "Gap2Seq-libraries: -libraries, -gaps, -bed and -filled are required" << std::endl;
+    return EXIT_FAILURE;
+  }
+  std::string libs_text, gaps_text, bed_text;
+  if (!g2s::read_text_file(libs_path, &libs_text) || !g2s::read_text_file(gaps_path, &gaps_text) ||
+      !g2s::read_text_file(bed_path, &bed_text)) {
+    std::cerr << "Gap2Seq-libraries: cannot read the input files" << std::endl;
+    return EXIT_FAILURE;
+  }
+  std::vector<Library> libs;
+  {
+    std::stringstream ls(libs_text);
+    std::string line;
+    while (std::getline(ls, line)) {
+      if (line.empty()) continue;
+      std::vector<std::string> cols;
+      std::stringstream cs(line);
+      std::string c;
+      while (std::getline(cs, c, '\t')) cols.push_back(c);
+      if (cols.size() < 4) { std::cerr << "Gap2Seq-libraries: a library line needs bam, mean, std_dev, threshold" << std::endl; return EXIT_FAILURE; }
+      Library L;
+      L.bam = cols[0];
+      L.mean = atoi(cols[1].c_str());
+      L.sd = atoi(cols[2].c_str());
+      L.threshold = atof(cols[3].c_str());
+      libs.push_back(L);
+    }
+  }
+  g2s_filter_opts base;
+  memset(&base, 0, sizeof base);
+  double threshold = 0;
+  for (Library& L : libs) {  // every library's unmapped reads, once (Gap2Seq.py:64-72, :437-439)
+    bool ok = false;
+    L.unmapped = filter(L, base, "0", 0, 0, -1, true, &ok);
+    threshold += L.threshold;
+  }
+  const std::vector<std::string> records = gap_records(gaps_text);
+  std::vector<std::string> bed_lines;
+  {
+    std::stringstream bs(bed_text);
+    std::string line;
+    while (std::getline(bs, line)) bed_lines.push_back(line);
+  }
+  const size_t ngaps = records.size();
+  std::vector<GapRec> gaps(ngaps);
+  std::vector<std::string> reads(ngaps);  // FASTA text of every gap's read set
+  for (size_t i = 0; i < ngaps; i++) {
+    gaps[i] = parse_gap(records[i], i < bed_lines.size() ? bed_lines[i] : std::string());
+    const GapRec& g = gaps[i];
+    size_t filtered_length = 0;
+    for (const Library& L : libs) {  // (Gap2Seq.py:143-159)
+      bool ok = false;
+      const std::string f = filter(L, base, g.scaffold, g.breakpoint, g.gap_length, g.flank_length, false, &ok);
+      filtered_length += sequence_bytes(f);
+      reads[i] += f;
+    }
+    const double ratio = g.gap_length > 0 ? (double)filtered_length / (double)g.gap_length : INFINITY;
+    if (ratio < threshold)  // (Gap2Seq.py:161-167)
+      for (const Library& L : libs) reads[i] += L.unmapped;
+  }
+  // ---- fill: chunks of gaps whose read text fits a budget, one set graph and one list each
+  g2s_params p;
+  memset(&p, 0, sizeof p);
+  p.d_err = derr;
+  p.skip_confident = upper ? 1 : 0;
+  p.all_paths = best ? 0 : 1;
+  p.unique_paths = unique ? 1 : 0;
+  p.max_mem = (int64_t)(max_mem * 1024.0 * 1024.0 * 1024.0);  // (the wrapper's per-gap core runs with -nb-cores 1)
+  p.randseed = randseed;
+  std::vector<std::string> fills(ngaps);
+  const size_t budget = (size_t)256 << 20;
+  size_t lo = 0;
+  while (lo < ngaps) {
+    size_t hi = lo, bytes = 0;
+    while (hi < ngaps && (hi == lo || bytes + reads[hi].size() <= budget)) bytes += reads[hi++].size();
+    std::vector<g2s::FastxRecord> recs;
+    std::vector<uint32_t> rec_set;
+    for (size_t i = lo; i < hi; i++) {
+      const size_t before = recs.size();
+      g2s::parse_fastx(reads[i], &recs);
+      rec_set.resize(recs.size(), (uint32_t)(i - lo));
+      (void)before;
+    }
+    std::vector<const char*> sp(recs.size());
+    std::vector<uint64_t> sl(recs.size());
+    for (size_t j = 0; j < recs.size(); j++) { sp[j] = recs[j].seq.data(); sl[j] = recs[j].seq.size(); }
+    g2s_graph* graph = nullptr;
+    int rc = g2s_graph_build_sets(sp.data(), sl.data(), rec_set.data(), (int)recs.size(), (uint32_t)(hi - lo), k, solid, 0, &graph);
+    g2s_session* s = nullptr;
+    if (rc == G2S_OK) rc = g2s_session_create(graph, device, &p, &s);
+    if (rc != G2S_OK) {
+      std::cerr << "Gap2Seq-libraries: " << g2s_last_error() << std::endl;
+      if (graph) g2s_graph_free(graph);
+      return EXIT_FAILURE;
+    }
+    std::vector<g2s_gap> gv;
+    std::vector<uint32_t> gs, idx;
+    for (size_t i = lo; i < hi; i++) {
+      const GapRec& g = gaps[i];
+      if ((int)g.left.size() < k || (int)g.right.size() < k) continue;  // Gap2Seq-core writes nothing (Gap2Seq.cpp:233-236)
+      g2s_gap x;
+      memset(&x, 0, sizeof x);
+      x.left = g.left.c_str();
+      x.right = g.right.c_str();
+      x.left_len = (int)g.left.size();
+      x.right_len = (int)g.right.size();
+      x.gap_len = g.gap_length;
+      x.lmf = std::min((int)g.left.size() - k, fuz);
+      x.rmf = std::min((int)g.right.size() - k, fuz);
+      x.skip_if_prev_right_fuz_gt = -1;
+      gv.push_back(x);
+      gs.push_back((uint32_t)(i - lo));
+      idx.push_back((uint32_t)i);
+    }
+    size_t arena_bytes = 0;
+    for (const g2s_gap& x : gv) arena_bytes += (size_t)(std::max(0, x.gap_len) + k + derr + x.lmf + x.rmf + 3);
+    std::vector<char> arena(std::max<size_t>(arena_bytes, 1));
+    std::vector<g2s_result> res(std::max<size_t>(gv.size(), 1));
+    rc = g2s_fill_sets(s, gv.data(), gs.data(), gv.size(), res.data(), arena.data(), arena.size());
+    if (rc != G2S_OK) {
+      std::cerr << "Gap2Seq-libraries: " << g2s_last_error() << std::endl;
+      g2s_session_destroy(s);
+      g2s_graph_free(graph);
+      return EXIT_FAILURE;
+    }
+    for (size_t q = 0; q < gv.size(); q++) {  // the sequence of g2s_execute_single's FASTA (Gap2Seq.cpp:266-273)
+      const GapRec& g = gaps[idx[q]];
+      const g2s_result& r = res[q];
+      if (r.count > 0 && (!unique || r.count == 1))
+        fills[idx[q]] = g.left.substr(0, g.left.size() - (size_t)r.left_fuz) + std::string(arena.data() + r.fill_off);
+    }
+    g2s_session_destroy(s);
+    g2s_graph_free(graph);
+    lo = hi;
+  }
+  // ---- output in input order; a gap without a fill: left + N * gap + right (Gap2Seq.py:210)
+  std::string out;
+  size_t successful = 0;
+  for (size_t i = 0; i < ngaps; i++) {
+    const GapRec& g = gaps[i];
+    if (fills[i].empty()) fills[i] = g.left + std::string((size_t)std::max(0, g.gap_length), 'N') + g.right;
+    if (fills[i].find_first_of("Nn") == std::string::npos) successful++;  // (Gap2Seq.py:216)
+    out += g.comment + "\n" + fills[i] + "\n";
+  }
+  FILE* f = fopen(filled_path.c_str(), "wb");
+  if (!f) { std::cerr << "Gap2Seq-libraries: cannot write " << filled_path << std::endl; return EXIT_FAILURE; }
+  fwrite(out.data(), 1, out.size(), f);
+  fclose(f);
+  std::cout << "Filled " << successful << " out of " << ngaps << " gaps" << std::endl;  // (Gap2Seq.py:513)
+  return EXIT_SUCCESS;
+}

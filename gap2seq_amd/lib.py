@@ -103,6 +103,11 @@ _SIGS = {
     "g2s_graph_build_files": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.POINTER(_VP)]),
     "g2s_graph_build_seqs": (C.c_int, [C.POINTER(C.c_char_p), C.POINTER(C.c_uint64), C.c_int, C.c_int, C.c_int,
                                        C.c_int, C.POINTER(_VP)]),
+    "g2s_graph_build_sets": (C.c_int, [C.POINTER(C.c_char_p), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.c_int,
+                                       C.c_uint32, C.c_int, C.c_int, C.c_int, C.POINTER(_VP)]),
+    "g2s_graph_num_sets": (C.c_uint32, [_VP]),
+    "g2s_graph_set_nodes": (C.c_int, [_VP, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "g2s_graph_set_node": (C.c_uint32, [_VP, C.c_uint32, C.c_char_p]),
     "g2s_graph_save": (C.c_int, [_VP, C.c_char_p]),
     "g2s_graph_load": (C.c_int, [C.c_char_p, C.POINTER(_VP)]),
     "g2s_graph_free": (None, [_VP]),
@@ -133,6 +138,8 @@ _SIGS = {
     "g2s_team_fill": (C.c_int, [C.POINTER(_VP), C.c_int, C.POINTER(g2s_gap), C.c_size_t, C.c_size_t,
                                 C.POINTER(g2s_result), C.c_char_p, C.c_size_t, C.POINTER(g2s_timing)]),
     "g2s_team_arena_bytes": (C.c_size_t, [_VP, C.POINTER(g2s_gap), C.c_size_t]),
+    "g2s_fill_sets": (C.c_int, [_VP, C.POINTER(g2s_gap), C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(g2s_result),
+                                C.c_char_p, C.c_size_t]),
     "g2s_session_set_team": (C.c_int, [_VP, C.POINTER(_VP), C.c_int, C.c_size_t]),
     "g2s_execute_scaffolds_stream": (C.c_int, [_VP, C.POINTER(g2s_run_opts), C.c_char_p, C.c_char_p, C.c_char_p, C.c_size_t,
                                              TEXT_FN, TEXT_FN, _VP, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
@@ -297,6 +304,36 @@ class Graph:
         h = _VP()
         _check(lib.g2s_graph_build_seqs(arr, lens, len(enc), k, solid, nthreads, C.byref(h)))
         return cls(h)
+
+    @classmethod
+    def from_sets(cls, sets, k, solid, nthreads=0):
+        """g2s_graph_build_sets: one graph per read set (`sets`: a list of lists of sequences), numbered set-major."""
+        lib = load_library()
+        enc, owner = [], []
+        for si, seqs in enumerate(sets):
+            for s in seqs:
+                enc.append(s.encode("ascii") if isinstance(s, str) else s)
+                owner.append(si)
+        n = len(enc)
+        arr = (C.c_char_p * max(1, n))(*enc)
+        lens = (C.c_uint64 * max(1, n))(*[len(e) for e in enc])
+        sets_of = (C.c_uint32 * max(1, n))(*owner)
+        h = _VP()
+        _check(lib.g2s_graph_build_sets(arr, lens, sets_of, n, len(sets), k, solid, nthreads, C.byref(h)))
+        return cls(h)
+
+    @property
+    def num_sets(self):
+        return load_library().g2s_graph_num_sets(self.h)
+
+    def set_nodes(self, s):
+        """(first node index, number of k-mers) of read set s."""
+        first, cnt = C.c_uint64(), C.c_uint64()
+        _check(load_library().g2s_graph_set_nodes(self.h, s, C.byref(first), C.byref(cnt)))
+        return first.value, cnt.value
+
+    def set_node(self, s, kmer):
+        return load_library().g2s_graph_set_node(self.h, s, kmer.encode("ascii"))
 
     @classmethod
     def from_files(cls, reads_csv, k, solid, nthreads=0):
@@ -533,6 +570,26 @@ class Session:
         finally:
             for hb in bufs:
                 hb.free()
+        if want_timing:
+            t = g2s_timing()
+            _check(lib.g2s_session_last_timing(self.h, C.byref(t)))
+            return out, t
+        return out
+
+    def fill_sets(self, gaps, gap_set, want_timing=False):
+        """g2s_fill_sets: gap i filled in read set gap_set[i] of a set graph, every gap from a fresh srand(randseed);
+        returns what fill_batch returns."""
+        lib = load_library()
+        if len(gap_set) != len(gaps):
+            raise ValueError("fill_sets: one set id per gap")
+        arr, keep = _gap_array(gaps)
+        ids = (C.c_uint32 * max(1, len(gaps)))(*gap_set)
+        nbytes = lib.g2s_team_arena_bytes(self.h, arr, len(gaps))
+        arena = C.create_string_buffer(max(1, nbytes))
+        res = (g2s_result * max(1, len(gaps)))()
+        _check(lib.g2s_fill_sets(self.h, arr, ids, len(gaps), res, arena, nbytes))
+        raw = arena.raw
+        out = [FillResult(res[i], raw) for i in range(len(gaps))]
         if want_timing:
             t = g2s_timing()
             _check(lib.g2s_session_last_timing(self.h, C.byref(t)))

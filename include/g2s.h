@@ -70,6 +70,19 @@ const char* g2s_last_error(void);
 int g2s_graph_build_files(const char* reads_csv, int k, int solid, int nthreads, g2s_graph** out);
 int g2s_graph_build_seqs(const char* const* seqs, const uint64_t* lens, int nseqs, int k, int solid,
                          int nthreads, g2s_graph** out);
+/* Set graphs: one graph per read set in one handle, for the wrapper's per-gap libraries flow (Gap2Seq.py:133-218:
+ * a fresh Gap2Seq-core over each gap's own reads).  seqs[j] belongs to set seq_set[j] < nsets; every set's graph is
+ * built from its own sequences alone (solidity counted per set) with the same k and solid.  Node indices are
+ * numbered set-major: set s holds one contiguous range [first_kmer, first_kmer + n_kmers) of node indices (oriented
+ * ids 2*index + strand), the sets' ranges follow in set order, and no edge leaves a set.  A set may be empty.
+ * nsets == 1 gives an ordinary graph (what g2s_graph_build_seqs gives); otherwise g2s_graph_node returns
+ * G2S_INVALID_NODE (a k-mer is a different node in every set it is solid in): use g2s_graph_set_node.  Graphs of
+ * several sets are built on host threads and cannot be saved (g2s_graph_save: G2S_ERR_ARG). */
+int g2s_graph_build_sets(const char* const* seqs, const uint64_t* lens, const uint32_t* seq_set, int nseqs, uint32_t nsets,
+                         int k, int solid, int nthreads, g2s_graph** out);
+uint32_t g2s_graph_num_sets(const g2s_graph* g); /* 1 for every graph built the other ways */
+int g2s_graph_set_nodes(const g2s_graph* g, uint32_t set, uint64_t* first_kmer, uint64_t* n_kmers);
+uint32_t g2s_graph_set_node(const g2s_graph* g, uint32_t set, const char* kmer); /* G2S_INVALID_NODE if absent */
 /* Own binary cache (the reference reuses "<reads>.h5", Gap2Seq.cpp:171,195-197). */
 int g2s_graph_save(const g2s_graph* g, const char* path);
 int g2s_graph_load(const char* path, g2s_graph** out);
@@ -272,6 +285,15 @@ int g2s_session_last_timing(const g2s_session* s, g2s_timing* out);
 /* prepare + run + free. */
 int g2s_fill_batch(g2s_session* s, const g2s_gap* gaps, size_t n, g2s_result* results, char* fill_arena,
                    size_t arena_cap);
+/* Independent gaps over a set graph (g2s_graph_build_sets): gap i is filled in set gap_set[i] alone, with a rand()
+ * stream that starts from srand(randseed) for every gap, as a fresh Gap2Seq-core -reads S(i) -left L -right R
+ * -length G -randseed randseed would (g2s_execute_single on a one-set graph of S(i), Gap2Seq.cpp:227-283).  A gap's
+ * result depends neither on its position in the list nor on the other gaps, and the session's own stream is not
+ * advanced.  Several gaps may name one set.  randseed 0 takes the seed the session was created with.
+ * Arena as for g2s_fill_batch.  G2S_ERR_ARG: a set id out of range, a gap with skip_if_prev_right_fuz_gt != -1;
+ * G2S_ERR_STATE: lists in flight, or the session is in a team.  Always the host path (no resident mode). */
+int g2s_fill_sets(g2s_session* s, const g2s_gap* gaps, const uint32_t* gap_set, size_t n, g2s_result* results,
+                  char* fill_arena, size_t arena_cap);
 
 /* ---------------------------------------------------------------------------
  *  Several sessions on one gap list = the reference's dispatcher
