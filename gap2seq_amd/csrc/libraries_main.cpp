@@ -1,14 +1,16 @@
 // gap2seq_amd/csrc/libraries_main.cpp — `Gap2Seq-libraries`: the wrapper's libraries flow (Gap2Seq.py -l,
 // /root/reference/src/Gap2Seq.py:133-218) in one process.  For every gap the wrapper extracts the reads of every library
 // that can belong to it (ReadFilter), adds every library's unmapped reads when too few bases came out, and runs a fresh
-// Gap2Seq-core over those reads alone.  Here the reads are extracted the same way (g2s_filter_reads), every gap's reads
-// become one read set of a set graph (g2s_graph_build_sets) and the gaps are filled as one list (g2s_fill_sets): every
-// gap's fill is what its own Gap2Seq-core -reads S(i) -left L -right R -length G run writes.
+// Gap2Seq-core over those reads alone.  Here every library's reads are extracted for all gaps at once, with its unmapped
+// reads, in two passes over its BAM (g2s_filter_reads_gaps: gap i's reads are g2s_filter_reads' for gap i), every gap's
+// reads become one read set of a set graph (g2s_graph_build_sets) and the gaps are filled as one list (g2s_fill_sets):
+// every gap's fill is what its own Gap2Seq-core -reads S(i) -left L -right R -length G run writes.
 //
 //   Gap2Seq-libraries -libraries libs.txt -gaps gaps.fa -bed gaps.bed -filled out.fa
 //                     [-k 31] [-fuz 10] [-solid 2] [-dist-error 500] [-max-mem 20] [-randseed 0]
-//                     [-all-upper] [-unique] [-best-only] [-device D]
+//                     [-all-upper] [-unique] [-best-only] [-device D] [-filter-device D|-1]
 //
+// -filter-device: the GPU the read filter's joins run on (default: -device), -1 = host threads.
 // libs.txt: tab separated `bam mean std_dev threshold`, one library a line.  out.fa: per gap, in input order,
 // `comment\nfill\n` (the file GapMerger -gaps takes); stdout ends with `Filled X out of Y gaps`.
 #include <cmath>
@@ -90,23 +92,41 @@ std::vector<std::string> gap_records(const std::string& text) {
   return out;
 }
 
-std::string filter(const Library& lib, const g2s_filter_opts& base, const std::string& scaffold, int breakpoint, int gap_length,
-                   int flank_length, bool unmapped_only, bool* ok) {
-  g2s_filter_opts o = base;
+// the reads of every gap from one library, and the library's unmapped reads, in one call (two passes over the BAM).
+// A library whose BAM cannot be read gives no reads (as the wrapper's ReadFilter run that fails, Gap2Seq.py:151-153).
+std::vector<std::string> filter_library(Library& lib, const std::vector<GapRec>& gaps, int device) {
+  g2s_filter_opts o;
+  memset(&o, 0, sizeof o);
   o.mean_insert = lib.mean;
   o.std_dev = lib.sd;
-  o.scaffold = scaffold.c_str();
-  o.breakpoint = breakpoint;
-  o.gap_length = gap_length;
-  o.flank_length = flank_length;
-  o.unmapped_only = unmapped_only ? 1 : 0;
-  char *fasta = nullptr, *log = nullptr, *warn = nullptr;
-  int64_t extracted = 0, total = 0;
-  *ok = g2s_filter_reads(lib.bam.c_str(), &o, &fasta, &log, &warn, &extracted, &total) == G2S_OK;
-  std::string out = (*ok && extracted > 0 && fasta) ? std::string(fasta) : std::string();
-  g2s_free(fasta);
-  g2s_free(log);
-  g2s_free(warn);
+  std::vector<g2s_filter_gap> gv(gaps.size());
+  for (size_t i = 0; i < gaps.size(); i++) {
+    gv[i].scaffold = gaps[i].scaffold.c_str();
+    gv[i].breakpoint = gaps[i].breakpoint;
+    gv[i].gap_length = gaps[i].gap_length;
+    gv[i].flank_length = gaps[i].flank_length;
+  }
+  std::vector<char*> fasta(std::max<size_t>(1, gaps.size()), nullptr);
+  char* unmapped = nullptr;
+  int64_t total = 0;
+  int rc = g2s_filter_reads_gaps(lib.bam.c_str(), &o, gv.data(), gv.size(), device, fasta.data(), nullptr, nullptr, nullptr,
+                                 &total, &unmapped, nullptr, nullptr);
+  if (rc != G2S_OK && rc != G2S_ERR_IO && device >= 0) {  // (the device could not take it: the same joins on the host)
+    std::cerr << "Gap2Seq-libraries: " << lib.bam << ": " << g2s_filter_last_error() << "; filtering on the host" << std::endl;
+    rc = g2s_filter_reads_gaps(lib.bam.c_str(), &o, gv.data(), gv.size(), -1, fasta.data(), nullptr, nullptr, nullptr,
+                               &total, &unmapped, nullptr, nullptr);
+  }
+  std::vector<std::string> out(gaps.size());
+  if (rc != G2S_OK) {
+    std::cerr << "Gap2Seq-libraries: " << lib.bam << ": " << g2s_filter_last_error() << std::endl;
+    return out;
+  }
+  for (size_t i = 0; i < gaps.size(); i++) {
+    out[i] = fasta[i];
+    g2s_free(fasta[i]);
+  }
+  lib.unmapped = unmapped;
+  g2s_free(unmapped);
   return out;
 }
 
@@ -114,7 +134,8 @@ std::string filter(const Library& lib, const g2s_filter_opts& base, const std::s
 
 int main(int argc, char** argv) {
   std::string libs_path, gaps_path, bed_path, filled_path;
-  int k = 31, fuz = 10, solid = 2, derr = 500, device = 0;
+  int k = 31, fuz = 10, solid = 2, derr = 500, device = 0, filter_device = 0;
+  bool filter_device_set = false;
   double max_mem = 20;
   uint32_t randseed = 0;
   bool upper = false, unique = false, best = false;
@@ -132,6 +153,7 @@ int main(int argc, char** argv) {
     else if (a == "-max-mem") max_mem = atof(val());
     else if (a == "-randseed") randseed = (uint32_t)strtoul(val(), nullptr, 10);
     else if (a == "-device") device = atoi(val());
+    else if (a == "-filter-device") { filter_device = atoi(val()); filter_device_set = true; }
     else if (a == "-all-upper") upper = true;
     else if (a == "-unique") unique = true;
     else if (a == "-best-only") best = true;
@@ -166,14 +188,6 @@ int main(int argc, char** argv) {
       libs.push_back(L);
     }
   }
-  g2s_filter_opts base;
-  memset(&base, 0, sizeof base);
-  double threshold = 0;
-  for (Library& L : libs) {  // every library's unmapped reads, once (Gap2Seq.py:64-72, :437-439)
-    bool ok = false;
-    L.unmapped = filter(L, base, "0", 0, 0, -1, true, &ok);
-    threshold += L.threshold;
-  }
   const std::vector<std::string> records = gap_records(gaps_text);
   std::vector<std::string> bed_lines;
   {
@@ -183,18 +197,21 @@ int main(int argc, char** argv) {
   }
   const size_t ngaps = records.size();
   std::vector<GapRec> gaps(ngaps);
+  for (size_t i = 0; i < ngaps; i++) gaps[i] = parse_gap(records[i], i < bed_lines.size() ? bed_lines[i] : std::string());
   std::vector<std::string> reads(ngaps);  // FASTA text of every gap's read set
-  for (size_t i = 0; i < ngaps; i++) {
-    gaps[i] = parse_gap(records[i], i < bed_lines.size() ? bed_lines[i] : std::string());
-    const GapRec& g = gaps[i];
-    size_t filtered_length = 0;
-    for (const Library& L : libs) {  // (Gap2Seq.py:143-159)
-      bool ok = false;
-      const std::string f = filter(L, base, g.scaffold, g.breakpoint, g.gap_length, g.flank_length, false, &ok);
-      filtered_length += sequence_bytes(f);
-      reads[i] += f;
+  std::vector<size_t> filtered_length(ngaps, 0);
+  double threshold = 0;
+  for (Library& L : libs) {  // (Gap2Seq.py:143-159; every library's unmapped reads, Gap2Seq.py:64-72, :437-439)
+    const std::vector<std::string> f = filter_library(L, gaps, filter_device_set ? filter_device : device);
+    for (size_t i = 0; i < ngaps; i++) {
+      filtered_length[i] += sequence_bytes(f[i]);
+      reads[i] += f[i];
     }
-    const double ratio = g.gap_length > 0 ? (double)filtered_length / (double)g.gap_length : INFINITY;
+    threshold += L.threshold;
+  }
+  for (size_t i = 0; i < ngaps; i++) {
+    const GapRec& g = gaps[i];
+    const double ratio = g.gap_length > 0 ? (double)filtered_length[i] / (double)g.gap_length : INFINITY;
     if (ratio < threshold)  // (Gap2Seq.py:161-167)
       for (const Library& L : libs) reads[i] += L.unmapped;
   }

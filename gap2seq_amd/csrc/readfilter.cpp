@@ -16,8 +16,16 @@
 
 #include "../../include/g2s.h"
 #include "bam.hpp"
+#include "readfilter_gaps.hpp"
 
 namespace {
+
+using g2s::Region;
+using g2s::append_fasta;
+using g2s::make_region;
+using g2s::mate_name;
+using g2s::overlaps;
+using g2s::own_name;
 
 thread_local std::string rf_error;
 
@@ -44,55 +52,6 @@ class NameFilter {
   uint64_t bits_;
   std::vector<uint64_t> words_;
 };
-
-// ReadFilter.cpp:165-173: the read's name with its end, and its mate's
-inline std::string own_name(const g2s::BamRec& r) {
-  return std::string(r.name, strnlen(r.name, r.l_name)) + ((r.flag & g2s::BAM_READ1) ? "/1" : "/2");
-}
-inline std::string mate_name(const g2s::BamRec& r) {
-  return std::string(r.name, strnlen(r.name, r.l_name)) + ((r.flag & g2s::BAM_READ1) ? "/2" : "/1");
-}
-
-// ReadFilter.cpp:105-161: the read as sequenced (reverse strand alignments are complemented back); every code
-// other than A, C, G, T becomes N
-void append_fasta(const g2s::BamRec& r, std::string* out) {
-  static const char fwd[16] = {'N', 'A', 'C', 'N', 'G', 'N', 'N', 'N', 'T', 'N', 'N', 'N', 'N', 'N', 'N', 'N'};
-  static const char rev[16] = {'N', 'T', 'G', 'N', 'C', 'N', 'N', 'N', 'A', 'N', 'N', 'N', 'N', 'N', 'N', 'N'};
-  out->push_back('>');
-  out->append(own_name(r));
-  out->push_back('\n');
-  const size_t at = out->size();
-  out->resize(at + (size_t)r.l_seq);
-  char* d = &(*out)[at];
-  if (!(r.flag & g2s::BAM_REVERSE))
-    for (int32_t i = 0; i < r.l_seq; i++) d[i] = fwd[r.base4(i)];
-  else
-    for (int32_t i = 0; i < r.l_seq; i++) d[i] = rev[r.base4(r.l_seq - 1 - i)];
-  out->push_back('\n');
-}
-
-// htslib's region iterator as the reference calls it (sam_itr_queryi, ReadFilter.cpp:184-191): a negative
-// start is 0; an end in front of the start gives NO iterator (the reference then prints a warning and reads
-// nothing, :188-190,213-217) — which is what happens to its right-hand window, whose bounds are written
-// the wrong way round (:388-389), whenever the standard deviation is not 0.
-struct Region {
-  int tid;
-  int64_t beg, end;
-  bool valid;
-};
-Region make_region(int tid, int64_t beg, int64_t end, std::string* warn) {
-  Region q{tid, beg < 0 ? 0 : beg, end, true};
-  if (tid < 0 || q.end < q.beg) {
-    q.valid = false;
-    warn->append("WARNING: SAM iterator is NULL!\n");
-  }
-  return q;
-}
-// (an empty region [x, x) yields nothing and no warning: htslib's reg2bins returns no bin for beg >= end, so the
-// iterator exists and ends at once — it is not a point query)
-inline bool overlaps(const g2s::BamRec& r, const Region& q) {
-  return q.valid && q.beg < q.end && r.ref_id == q.tid && (int64_t)r.pos < q.end && r.end_pos() > q.beg;
-}
 
 char* dup_text(const std::string& s) {
   char* p = (char*)malloc(s.size() + 1);
@@ -138,10 +97,11 @@ int run_filter(g2s::BamFile& bam, const g2s_filter_opts* o, char** fasta_out, ch
     const Region left = make_region(tid, bp - (mu + 3 * sd + 2 * rl), bp - (mu - 3 * sd + rl), &warn);
     const Region right = make_region(tid, bp + (mu + 3 * sd + rl) + gl, bp + (mu - 3 * sd + rl) + gl, &warn);
     // pass 2 (:300-310): names of reads in the windows whose mate is unmapped
-    auto in_window = [](int64_t pos, int64_t end, const Region& q) { return q.valid && pos < q.end && end > q.beg; };
+    // (in_region: an empty window [x, x) — the right-hand one when the standard deviation is 0 — holds nothing here
+    // either, as in `overlaps`)
     if ((left.valid || right.valid) && cands_complete) {
       for (const Cand& c : cands)
-        if (in_window(c.pos, c.end, left) || in_window(c.pos, c.end, right)) names.insert(c.name);
+        if (g2s::in_region(c.pos, c.end, left) || g2s::in_region(c.pos, c.end, right)) names.insert(c.name);
     } else if (left.valid || right.valid) {
       if (!bam.for_each([&](const g2s::BamRec& r) {
             if (!(r.flag & g2s::BAM_MATE_UNMAPPED)) return true;
@@ -195,6 +155,8 @@ int run_filter(g2s::BamFile& bam, const g2s_filter_opts* o, char** fasta_out, ch
 }
 
 }  // namespace
+
+void g2s::set_filter_error(const std::string& e) { rf_error = e; }
 
 extern "C" {
 

@@ -1,0 +1,341 @@
+// gap2seq_amd/csrc/readfilter_gaps.cpp — g2s_filter_reads_gaps: the reads of N gaps from one library in two
+// inflating passes over the BAM, whatever N is.  Gap i's outputs are g2s_filter_reads' for gap i, byte for byte.
+//
+//   pass A (host, inflating threads)  one compact row per record (readfilter_gaps.hpp: FilterRows): reference, position,
+//                                     end position, flag, std::hash of the read's name and of its mate's.  The record
+//                                     count and the longest read fall out of it, so every gap's windows are known at
+//                                     its end.
+//   joins (device or host threads)    per gap the filter's bits (B_g), list 1 (records whose mate's bit is in B_g) and
+//                                     list 2 (records overlapping the flanks whose own bit is not), as (gap, row) pairs
+//                                     in (gap, row) order: readfilter_gpu.hip, or filter_join_host below.
+//   pass B (host, inflating threads)  the FASTA text of every row some gap (or the unmapped list) selected; every gap's
+//                                     text is its list 1 rows' text followed by its list 2 rows'.
+//
+// Pass B inflates the file a second time rather than keeping every record's bases from pass A (which would save that
+// inflate and cost half a byte of every base of the file on the host): the host holds 36 bytes a record (the rows),
+// then 13 bytes a record (pass B's selection and text offsets) and the text of the SELECTED records, once each however
+// many gaps select them.  The per-gap outputs themselves are the text of each gap's reads.
+#include <algorithm>
+#include <atomic>
+#include <chrono>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <functional>
+#include <string>
+#include <thread>
+#include <vector>
+
+#include "../../include/g2s.h"
+#include "bam.hpp"
+#include "readfilter_gaps.hpp"
+
+namespace g2s {
+
+namespace {
+
+// fn(t, lo, hi) on `threads` threads over [0, n) cut into contiguous ranges, in range order by t
+void parallel_ranges(size_t n, int threads, const std::function<void(int, size_t, size_t)>& fn) {
+  const int T = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::max(1, threads), n / 4096 + 1));
+  if (T == 1) { fn(0, 0, n); return; }
+  std::vector<std::thread> th;
+  for (int t = 1; t < T; t++) th.emplace_back(fn, t, n * (size_t)t / (size_t)T, n * (size_t)(t + 1) / (size_t)T);
+  fn(0, 0, n / (size_t)T);
+  for (auto& x : th) x.join();
+}
+
+// fn(i) for i in [0, n) on `threads` threads, dynamically (gaps differ a lot in work)
+void parallel_items(size_t n, int threads, const std::function<void(size_t)>& fn) {
+  const int T = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::max(1, threads), n));
+  std::atomic<size_t> next{0};
+  auto work = [&] { for (size_t i; (i = next.fetch_add(1)) < n;) fn(i); };
+  if (T == 1) { work(); return; }
+  std::vector<std::thread> th;
+  for (int t = 1; t < T; t++) th.emplace_back(work);
+  work();
+  for (auto& x : th) x.join();
+}
+
+double ms_since(std::chrono::steady_clock::time_point t0) {
+  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+}  // namespace
+
+// The joins on host threads: the same steps as the device path (readfilter_gpu.hip), with sorted vectors and binary
+// searches in place of its kernels.
+int filter_join_host(FilterJoin& j, int threads, std::string* err) {
+  const FilterRows& R = *j.rows;
+  const size_t nr = R.size(), n = j.gaps();
+  j.list1.clear();
+  j.list2.clear();
+  if (!nr || !j.bits || !n) return G2S_OK;  // (no records: the filter is empty and no window holds anything)
+  // 1. the bits of every row's name and mate's name
+  std::vector<uint64_t> b_own(nr), b_mate(nr);
+  parallel_ranges(nr, threads, [&](int, size_t lo, size_t hi) {
+    for (size_t r = lo; r < hi; r++) { b_own[r] = R.h_own[r] % j.bits; b_mate[r] = R.h_mate[r] % j.bits; }
+  });
+  // 2. the rows indexed by (ref_id, pos) — a coordinate-sorted file is its own index
+  std::vector<uint64_t> ikey(nr);
+  std::vector<uint32_t> irow(nr);
+  for (size_t r = 0; r < nr; r++) { ikey[r] = filter_index_key(R.ref_id[r], R.pos[r]); irow[r] = (uint32_t)r; }
+  if (!std::is_sorted(ikey.begin(), ikey.end())) {
+    std::vector<std::pair<uint64_t, uint32_t>> kv(nr);
+    for (size_t r = 0; r < nr; r++) kv[r] = {ikey[r], (uint32_t)r};
+    std::sort(kv.begin(), kv.end());
+    for (size_t r = 0; r < nr; r++) { ikey[r] = kv[r].first; irow[r] = kv[r].second; }
+  }
+  // the rows of a window: keys in [(tid, beg - max_span + 1), (tid, end)), then the overlap test on the end position
+  auto window_rows = [&](const FilterWindow& w, const std::function<void(uint32_t)>& fn) {
+    if (w.tid < 0 || w.beg >= w.end) return;
+    const size_t lo = (size_t)(std::lower_bound(ikey.begin(), ikey.end(), filter_index_key(w.tid, w.beg - R.max_span + 1)) - ikey.begin());
+    const size_t hi = (size_t)(std::lower_bound(ikey.begin(), ikey.end(), filter_index_key(w.tid, w.end)) - ikey.begin());
+    for (size_t i = lo; i < hi; i++)
+      if (R.end[irow[i]] > w.beg) fn(irow[i]);
+  };
+  // 3. every gap's filter: (bit << 29 | gap) of the mate-unmapped rows in its left and right windows, sorted, unique
+  std::vector<std::vector<uint64_t>> per_gap(n);
+  parallel_items(n, threads, [&](size_t g) {
+    for (int w = 0; w < 2; w++)
+      window_rows(j.win[3 * g + w], [&](uint32_t r) {
+        if (R.flag[r] & BAM_MATE_UNMAPPED) per_gap[g].push_back(b_own[r] << kFilterGapBits | g);
+      });
+  });
+  uint64_t pairs = 0;
+  for (auto& v : per_gap) pairs += v.size();
+  if (pairs > j.max_pairs) { *err = "more filter pairs than the cap (G2S_FILTER_MAX_PAIRS)"; return G2S_ERR_NOMEM; }
+  std::vector<uint64_t> U;
+  U.reserve((size_t)pairs);
+  for (auto& v : per_gap) { U.insert(U.end(), v.begin(), v.end()); std::vector<uint64_t>().swap(v); }
+  std::sort(U.begin(), U.end());
+  U.erase(std::unique(U.begin(), U.end()), U.end());
+  // 4. list 1: every row whose mate's bit is some gap's — one pair per such gap; rows in order within a gap (a
+  // stable counting sort of the row ranges' pairs by gap)
+  const int T = std::max(1, threads);
+  std::vector<std::vector<uint64_t>> part((size_t)T);
+  parallel_ranges(nr, threads, [&](int t, size_t lo, size_t hi) {
+    for (size_t r = lo; r < hi; r++) {
+      const uint64_t m = b_mate[r];
+      auto a = std::lower_bound(U.begin(), U.end(), m << kFilterGapBits);
+      for (; a != U.end() && (*a >> kFilterGapBits) == m; ++a) part[(size_t)t].push_back((*a & kFilterGapMask) << 32 | r);
+    }
+  });
+  uint64_t n1 = 0;
+  for (auto& v : part) n1 += v.size();
+  if (pairs + n1 > j.max_pairs) { *err = "more filter pairs than the cap (G2S_FILTER_MAX_PAIRS)"; return G2S_ERR_NOMEM; }
+  {
+    std::vector<uint64_t> at(n + 1, 0);
+    for (auto& v : part)
+      for (uint64_t x : v) at[(size_t)(x >> 32) + 1]++;
+    for (size_t g = 0; g < n; g++) at[g + 1] += at[g];
+    j.list1.resize((size_t)n1);
+    for (auto& v : part) {
+      for (uint64_t x : v) j.list1[(size_t)at[(size_t)(x >> 32)]++] = x;
+      std::vector<uint64_t>().swap(v);
+    }
+  }
+  // 5. list 2: per gap, the rows overlapping `around` whose own bit is not in the gap's filter, in row order
+  std::vector<std::vector<uint32_t>> l2(n);
+  parallel_items(n, threads, [&](size_t g) {
+    window_rows(j.win[3 * g + 2], [&](uint32_t r) {
+      if (!std::binary_search(U.begin(), U.end(), b_own[r] << kFilterGapBits | g)) l2[g].push_back(r);
+    });
+    std::sort(l2[g].begin(), l2[g].end());
+  });
+  uint64_t n2 = 0;
+  for (auto& v : l2) n2 += v.size();
+  if (pairs + n1 + n2 > j.max_pairs) { *err = "more filter pairs than the cap (G2S_FILTER_MAX_PAIRS)"; return G2S_ERR_NOMEM; }
+  j.list2.reserve((size_t)n2);
+  for (size_t g = 0; g < n; g++) {
+    for (uint32_t r : l2[g]) j.list2.push_back((uint64_t)g << 32 | r);
+    std::vector<uint32_t>().swap(l2[g]);
+  }
+  return G2S_OK;
+}
+
+namespace {
+
+char* dup_text(const char* p, size_t n) {
+  char* q = (char*)malloc(n + 1);
+  if (!q) return nullptr;
+  if (n) memcpy(q, p, n);
+  q[n] = 0;
+  return q;
+}
+
+int run_filter_gaps(BamFile& bam, const g2s_filter_opts* lib, const g2s_filter_gap* gaps, size_t n, int device,
+                    char** fasta_out, char** log_out, char** warn_out, int64_t* extracted_out, int64_t* total_out,
+                    char** unmapped_out, int64_t* unmapped_extracted, g2s_filter_stats* stats) {
+  std::string err;
+  g2s_filter_stats st;
+  memset(&st, 0, sizeof st);
+  const int threads = lib->threads > 0 ? lib->threads : (int)std::min(8u, std::max(1u, std::thread::hardware_concurrency()));
+  bam.set_threads(threads);
+  // ---- pass A
+  auto t0 = std::chrono::steady_clock::now();
+  FilterRows R;
+  int32_t read_length = 0;
+  bool too_many = false;
+  std::string nm;
+  st.file_passes++;
+  if (!bam.for_each([&](const BamRec& r) {
+        if (R.size() >= (size_t)UINT32_MAX - 1) { too_many = true; return false; }
+        const int64_t e = r.end_pos();
+        R.ref_id.push_back(r.ref_id);
+        R.pos.push_back(r.pos);
+        R.end.push_back(e);
+        R.flag.push_back(r.flag);
+        nm.assign(r.name, strnlen(r.name, r.l_name));
+        const bool r1 = (r.flag & BAM_READ1) != 0;
+        nm += r1 ? "/1" : "/2";
+        R.h_own.push_back((uint64_t)std::hash<std::string>{}(nm));
+        nm.back() = r1 ? '2' : '1';
+        R.h_mate.push_back((uint64_t)std::hash<std::string>{}(nm));
+        read_length = std::max(read_length, r.l_seq);
+        if (r.ref_id >= 0) R.max_span = std::max(R.max_span, e - (int64_t)r.pos);
+        return true;
+      }, &err)) {
+    set_filter_error(err);
+    return G2S_ERR_IO;
+  }
+  if (too_many) { set_filter_error("more than 2^32 - 2 records"); return G2S_ERR_ARG; }
+  st.ms_inflate = ms_since(t0);
+  const uint64_t total = R.size();
+  // ---- every gap's windows and warnings (readfilter.cpp: run_filter)
+  t0 = std::chrono::steady_clock::now();
+  FilterJoin J;
+  J.rows = &R;
+  J.bits = 5 * total;
+  const char* cap = getenv("G2S_FILTER_MAX_PAIRS");
+  J.max_pairs = cap ? (uint64_t)strtoull(cap, nullptr, 10) : (uint64_t)1 << 31;
+  J.win.resize(3 * n);
+  std::vector<std::string> warn(n);
+  for (size_t i = 0; i < n; i++) {
+    const g2s_filter_gap& g = gaps[i];
+    const int tid = bam.ref_id(g.scaffold ? g.scaffold : "");
+    const int64_t bp = g.breakpoint, mu = lib->mean_insert, sd = lib->std_dev, gl = g.gap_length, rl = read_length;
+    J.win[3 * i] = filter_window(make_region(tid, bp - (mu + 3 * sd + 2 * rl), bp - (mu - 3 * sd + rl), &warn[i]));
+    J.win[3 * i + 1] = filter_window(make_region(tid, bp + (mu + 3 * sd + rl) + gl, bp + (mu - 3 * sd + rl) + gl, &warn[i]));
+    if (g.flank_length != -1)
+      J.win[3 * i + 2] = filter_window(make_region(tid, bp - (int64_t)g.flank_length, bp + (int64_t)g.flank_length + gl, &warn[i]));
+    else
+      J.win[3 * i + 2] = FilterWindow{-1, 0, 0, 0};
+  }
+  // ---- the joins
+  const char* host_env = getenv("G2S_HOST_FILTER");
+  const bool on_device = device >= 0 && !(host_env && strcmp(host_env, "1") == 0) && filter_device_usable(device);
+  const int rc = on_device ? filter_join_device(J, device, &err) : filter_join_host(J, threads, &err);
+  if (rc != G2S_OK) { set_filter_error(err); return rc; }
+  st.on_device = on_device ? 1 : 0;
+  st.ms_join = ms_since(t0);
+  // ---- pass B: the text of the selected rows
+  t0 = std::chrono::steady_clock::now();
+  std::vector<uint8_t> sel(total, 0);
+  for (uint64_t x : J.list1) sel[(uint32_t)x] = 1;
+  for (uint64_t x : J.list2) sel[(uint32_t)x] = 1;
+  std::vector<uint64_t> toff(total, 0);
+  std::vector<uint32_t> tlen(total, 0);
+  std::string text, unmapped;
+  int64_t n_unmapped = 0;
+  const bool want_unmapped = unmapped_out != nullptr;
+  size_t row = 0;
+  st.file_passes++;
+  if (!bam.for_each([&](const BamRec& r) {
+        if (row >= total) return false;  // (the file changed under us: guarded below)
+        if (sel[row]) {
+          toff[row] = text.size();
+          append_fasta(r, &text);
+          tlen[row] = (uint32_t)(text.size() - toff[row]);
+        }
+        if (want_unmapped && (r.flag & BAM_UNMAPPED)) { append_fasta(r, &unmapped); n_unmapped++; }
+        row++;
+        return true;
+      }, &err)) {
+    set_filter_error(err);
+    return G2S_ERR_IO;
+  }
+  if (row != total) { set_filter_error("the BAM file changed between passes"); return G2S_ERR_IO; }
+  // ---- every gap's text: list 1's rows, then list 2's
+  std::vector<size_t> at1(n + 1, 0), at2(n + 1, 0);
+  for (uint64_t x : J.list1) at1[(size_t)(x >> 32) + 1]++;
+  for (uint64_t x : J.list2) at2[(size_t)(x >> 32) + 1]++;
+  for (size_t g = 0; g < n; g++) { at1[g + 1] += at1[g]; at2[g + 1] += at2[g]; }
+  std::vector<char*> fa(n, nullptr), lg(n, nullptr), wn(n, nullptr);
+  std::atomic<bool> oom{false};
+  parallel_items(n, threads, [&](size_t g) {
+    size_t bytes = 0;
+    for (size_t q = at1[g]; q < at1[g + 1]; q++) bytes += tlen[(uint32_t)J.list1[q]];
+    for (size_t q = at2[g]; q < at2[g + 1]; q++) bytes += tlen[(uint32_t)J.list2[q]];
+    if (fasta_out) {
+      char* p = (char*)malloc(bytes + 1);
+      if (!p) { oom = true; return; }
+      size_t o = 0;
+      for (size_t q = at1[g]; q < at1[g + 1]; q++) { const uint32_t r = (uint32_t)J.list1[q]; memcpy(p + o, text.data() + toff[r], tlen[r]); o += tlen[r]; }
+      for (size_t q = at2[g]; q < at2[g + 1]; q++) { const uint32_t r = (uint32_t)J.list2[q]; memcpy(p + o, text.data() + toff[r], tlen[r]); o += tlen[r]; }
+      p[o] = 0;
+      fa[g] = p;
+    }
+    const int64_t ex = (int64_t)(at1[g + 1] - at1[g] + at2[g + 1] - at2[g]);
+    if (extracted_out) extracted_out[g] = ex;
+    if (log_out) {
+      const std::string log = "Extracted " + std::to_string(ex) + " out of " + std::to_string(total) + " reads\n";  // :406
+      if (!(lg[g] = dup_text(log.data(), log.size()))) oom = true;
+    }
+    if (warn_out && !(wn[g] = dup_text(warn[g].data(), warn[g].size()))) oom = true;
+  });
+  char* un = nullptr;
+  if (want_unmapped && !(un = dup_text(unmapped.data(), unmapped.size()))) oom = true;
+  if (oom) {
+    for (size_t g = 0; g < n; g++) { free(fa[g]); free(lg[g]); free(wn[g]); }
+    free(un);
+    set_filter_error("out of memory");
+    return G2S_ERR_NOMEM;
+  }
+  for (size_t g = 0; g < n; g++) {
+    if (fasta_out) fasta_out[g] = fa[g];
+    if (log_out) log_out[g] = lg[g];
+    if (warn_out) warn_out[g] = wn[g];
+  }
+  if (want_unmapped) *unmapped_out = un;
+  if (unmapped_extracted) *unmapped_extracted = n_unmapped;
+  if (total_out) *total_out = (int64_t)total;
+  st.ms_text = ms_since(t0);
+  if (stats) *stats = st;
+  return G2S_OK;
+}
+
+bool gap_args_ok(const g2s_filter_opts* lib, const g2s_filter_gap* gaps, size_t n) {
+  if (!lib || (n && !gaps)) { set_filter_error("null argument"); return false; }
+  if (n > kFilterGapMask) { set_filter_error("more than 2^29 - 1 gaps in one call"); return false; }
+  return true;
+}
+
+}  // namespace
+
+}  // namespace g2s
+
+extern "C" {
+
+int g2s_filter_reads_gaps(const char* bam_path, const g2s_filter_opts* lib, const g2s_filter_gap* gaps, size_t n, int device,
+                          char** fasta_out, char** log_out, char** warn_out, int64_t* extracted, int64_t* total,
+                          char** unmapped_out, int64_t* unmapped_extracted, g2s_filter_stats* stats) {
+  if (!bam_path || !g2s::gap_args_ok(lib, gaps, n)) return G2S_ERR_ARG;
+  g2s::BamFile bam;
+  std::string err;
+  if (!bam.open_path(bam_path, &err)) { g2s::set_filter_error(err); return G2S_ERR_IO; }
+  return g2s::run_filter_gaps(bam, lib, gaps, n, device, fasta_out, log_out, warn_out, extracted, total, unmapped_out,
+                              unmapped_extracted, stats);
+}
+
+int g2s_filter_reads_gaps_mem(const void* bam_bytes, size_t nbytes, const g2s_filter_opts* lib, const g2s_filter_gap* gaps,
+                              size_t n, int device, char** fasta_out, char** log_out, char** warn_out, int64_t* extracted,
+                              int64_t* total, char** unmapped_out, int64_t* unmapped_extracted, g2s_filter_stats* stats) {
+  if (!bam_bytes || !g2s::gap_args_ok(lib, gaps, n)) return G2S_ERR_ARG;
+  g2s::BamFile bam;
+  std::string err;
+  if (!bam.open_mem(bam_bytes, nbytes, &err)) { g2s::set_filter_error(err); return G2S_ERR_IO; }
+  return g2s::run_filter_gaps(bam, lib, gaps, n, device, fasta_out, log_out, warn_out, extracted, total, unmapped_out,
+                              unmapped_extracted, stats);
+}
+
+}  // extern "C"

@@ -85,6 +85,16 @@ class g2s_filter_opts(C.Structure):
                 ("scaffold", C.c_char_p)]
 
 
+class g2s_filter_gap(C.Structure):
+    _fields_ = [("scaffold", C.c_char_p), ("breakpoint", C.c_int32), ("gap_length", C.c_int32),
+                ("flank_length", C.c_int32)]
+
+
+class g2s_filter_stats(C.Structure):
+    _fields_ = [("file_passes", C.c_uint32), ("on_device", C.c_uint32), ("ms_inflate", C.c_double),
+                ("ms_join", C.c_double), ("ms_text", C.c_double)]
+
+
 # every symbol include/g2s.h declares: name -> (restype, argtypes)
 _VP = C.c_void_p
 TEXT_FN = C.CFUNCTYPE(None, C.POINTER(C.c_char), C.c_size_t, C.c_void_p)  # g2s_text_fn
@@ -159,6 +169,14 @@ _SIGS = {
                                    C.POINTER(_VP), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "g2s_filter_reads_mem": (C.c_int, [C.c_char_p, C.c_size_t, C.POINTER(g2s_filter_opts), C.POINTER(_VP),
                                        C.POINTER(_VP), C.POINTER(_VP), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "g2s_filter_reads_gaps": (C.c_int, [C.c_char_p, C.POINTER(g2s_filter_opts), C.POINTER(g2s_filter_gap), C.c_size_t,
+                                        C.c_int, C.POINTER(_VP), C.POINTER(_VP), C.POINTER(_VP), C.POINTER(C.c_int64),
+                                        C.POINTER(C.c_int64), C.POINTER(_VP), C.POINTER(C.c_int64),
+                                        C.POINTER(g2s_filter_stats)]),
+    "g2s_filter_reads_gaps_mem": (C.c_int, [C.c_char_p, C.c_size_t, C.POINTER(g2s_filter_opts), C.POINTER(g2s_filter_gap),
+                                            C.c_size_t, C.c_int, C.POINTER(_VP), C.POINTER(_VP), C.POINTER(_VP),
+                                            C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(_VP),
+                                            C.POINTER(C.c_int64), C.POINTER(g2s_filter_stats)]),
     "g2s_filter_last_error": (C.c_char_p, []),
     "g2s_device_count": (C.c_int, []),
     "g2s_synth_genome": (C.c_int, [C.c_uint64, C.c_uint32, C.c_uint64, C.POINTER(_VP)]),
@@ -287,6 +305,49 @@ def filter_reads(bam, mean, std_dev, scaffold, breakpoint, gap_length=-1, flank_
         texts.append(C.string_at(x).decode("latin-1") if x else "")
         lib.g2s_free(x)
     return tuple(texts) + (ext.value, tot.value)
+
+
+def filter_reads_gaps(bam, mean, std_dev, gaps, device=0, threads=0, unmapped=False):
+    """g2s_filter_reads_gaps / g2s_filter_reads_gaps_mem: the reads of every gap of `gaps` from one library in two
+    passes over the file.  `gaps`: (scaffold, breakpoint[, gap_length[, flank_length]]) tuples or dicts with those
+    keys (gap_length and flank_length default to -1, as in filter_reads).  device -1 = the joins on host threads.
+    Returns (per-gap list of (fasta, stdout_text, stderr_text, extracted, total) as filter_reads returns them, stats
+    dict); with unmapped=True a third item, filter_reads(..., unmapped_only=True)'s tuple, from the same passes."""
+    lib = load_library()
+    arr = (g2s_filter_gap * max(1, len(gaps)))()
+    for i, g in enumerate(gaps):
+        if isinstance(g, dict):
+            g = (g["scaffold"], g["breakpoint"], g.get("gap_length", -1), g.get("flank_length", -1))
+        g = tuple(g) + (-1,) * (4 - len(g))
+        arr[i] = g2s_filter_gap(g[0].encode(), g[1], g[2], g[3])
+    n = len(gaps)
+    o = g2s_filter_opts(mean, std_dev, 0, -1, -1, 0, threads, b"")
+    fa, lg, wn = (_VP * max(1, n))(), (_VP * max(1, n))(), (_VP * max(1, n))()
+    ext = (C.c_int64 * max(1, n))()
+    tot, un_ext = C.c_int64(0), C.c_int64(0)
+    un = _VP()
+    st = g2s_filter_stats()
+    tail = [C.byref(o), arr, n, device, fa, lg, wn, ext, C.byref(tot), C.byref(un) if unmapped else None,
+            C.byref(un_ext), C.byref(st)]
+    if isinstance(bam, (bytes, bytearray)):
+        rc = lib.g2s_filter_reads_gaps_mem(bytes(bam), len(bam), *tail)
+    else:
+        rc = lib.g2s_filter_reads_gaps(str(bam).encode(), *tail)
+    if rc != G2S_OK:
+        raise G2SError(rc, (lib.g2s_filter_last_error() or b"").decode("utf-8", "replace"))
+
+    def take(p):  # (read names are bytes of the BAM file: not necessarily ASCII)
+        s = C.string_at(p).decode("latin-1") if p else ""
+        lib.g2s_free(p)
+        return s
+    out = [(take(fa[i]), take(lg[i]), take(wn[i]), ext[i], tot.value) for i in range(n)]
+    stats = dict(file_passes=st.file_passes, on_device=st.on_device, ms_inflate=st.ms_inflate, ms_join=st.ms_join,
+                 ms_text=st.ms_text)
+    if not unmapped:
+        return out, stats
+    un_fa = take(un)
+    un_log = "Extracted %d out of %d reads\n" % (un_ext.value, tot.value)
+    return out, stats, (un_fa, un_log, "", un_ext.value, tot.value)
 
 
 class Graph:

@@ -416,6 +416,41 @@ int g2s_filter_reads_mem(const void* bam_bytes, size_t n, const g2s_filter_opts*
 const char* g2s_filter_last_error(void);
 
 /* ---------------------------------------------------------------------------
+ *  The same filter for N gaps of one library in ONE call (ABI 6, additive): two inflating passes over the BAM
+ *  whatever N is, where N calls of g2s_filter_reads make 2N.  For every i, fasta_out[i], log_out[i], warn_out[i],
+ *  extracted[i] and *total are what g2s_filter_reads(bam, opts_i) returns, byte for byte, opts_i being `lib` with
+ *  gap i's scaffold, breakpoint, gap_length and flank_length and unmapped_only = 0 (lib's own gap fields and
+ *  unmapped_only are not read; its mean_insert, std_dev and threads are).
+ *
+ *  Pass A keeps a compact row of every record (position, end, flag, the std::hash of its name and its mate's); the
+ *  joins between rows and gaps run on the GPU `device` (readfilter_gpu.hip), or on host threads when device is -1,
+ *  when that device is not a gfx950, or with G2S_HOST_FILTER=1; pass B inflates the file again to write the text of
+ *  the selected reads.  Limits: fewer than 2^32 - 1 records (G2S_ERR_ARG), fewer than 2^29 gaps a call (G2S_ERR_ARG),
+ *  at most 2^31 join pairs a call (G2S_ERR_NOMEM; G2S_FILTER_MAX_PAIRS lowers the cap).
+ *
+ *  fasta_out, log_out, warn_out: arrays of n pointers (each may be NULL), filled with malloc'ed strings released with
+ *  g2s_free.  extracted: n entries, or NULL.  unmapped_out (may be NULL): the FASTA text of g2s_filter_reads with
+ *  unmapped_only, every unmapped read of the file, collected in the same two passes; unmapped_extracted its count.
+ *  stats may be NULL.  n = 0 is allowed (the total and the unmapped reads only).  g2s_filter_last_error() describes a
+ *  failure; nothing is allocated then.
+ * ------------------------------------------------------------------------ */
+typedef struct g2s_filter_gap {
+  const char* scaffold;              /* -scaffold */
+  int32_t breakpoint, gap_length, flank_length;   /* as in g2s_filter_opts; flank_length -1 = no flank reads */
+} g2s_filter_gap;
+typedef struct g2s_filter_stats {
+  uint32_t file_passes;              /* inflating passes over the BAM made by this call (2) */
+  uint32_t on_device;                /* 1 when the joins ran on the GPU */
+  double ms_inflate, ms_join, ms_text;   /* laps: pass A; windows and joins; pass B and the per-gap texts */
+} g2s_filter_stats;
+int g2s_filter_reads_gaps(const char* bam_path, const g2s_filter_opts* lib, const g2s_filter_gap* gaps, size_t n, int device,
+                          char** fasta_out, char** log_out, char** warn_out, int64_t* extracted, int64_t* total,
+                          char** unmapped_out, int64_t* unmapped_extracted, g2s_filter_stats* stats);
+int g2s_filter_reads_gaps_mem(const void* bam_bytes, size_t nbytes, const g2s_filter_opts* lib, const g2s_filter_gap* gaps,
+                              size_t n, int device, char** fasta_out, char** log_out, char** warn_out, int64_t* extracted,
+                              int64_t* total, char** unmapped_out, int64_t* unmapped_extracted, g2s_filter_stats* stats);
+
+/* ---------------------------------------------------------------------------
  *  Page-locked host memory the GPUs can write: a `results` array or fill arena
  *  allocated here is written by the kernels directly (no staging copy) when a
  *  list is finished on the device.  Any other memory works too.  The reference's

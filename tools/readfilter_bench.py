@@ -1,0 +1,83 @@
+"""tools/readfilter_bench.py — the read extraction of libraries mode, three ways, on one simulated library:
+
+  per_gap   g2s_filter_reads once a gap (what Gap2Seq-libraries did before g2s_filter_reads_gaps), timed on the first
+            --loop-gaps gaps and extrapolated linearly to all of them (every call inflates the file twice)
+  host      g2s_filter_reads_gaps with the joins on host threads (device -1)
+  device    g2s_filter_reads_gaps with the joins on the GPU, with its laps: the first call of the process (HIP's
+            start-up falls into its join lap) and a second one
+
+Prints one JSON line.  The library is tests/bamwriter.simulate_library's, about --pairs read pairs on 10 scaffolds,
+with --gaps gaps at random breakpoints; the same gaps for all three, on the coordinate-sorted file and on the same
+records shuffled (where the host joins sort their index, which a sorted file spares them).
+
+  python tools/readfilter_bench.py [--pairs 1000000] [--gaps 1000] [--loop-gaps 20] [--device 0] [--threads 0]
+"""
+import argparse
+import json
+import os
+import random
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+
+import bamwriter as BW  # noqa: E402
+from gap2seq_amd import lib as P  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--pairs", type=int, default=1000000)
+    ap.add_argument("--gaps", type=int, default=1000)
+    ap.add_argument("--loop-gaps", type=int, default=20)
+    ap.add_argument("--scaffolds", type=int, default=10)
+    ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--threads", type=int, default=0)
+    ap.add_argument("--seed", type=int, default=5)
+    a = ap.parse_args()
+    t0 = time.time()
+    scaffold_len = max(10000, a.pairs // a.scaffolds * 2)
+    refs, recs, _ = BW.simulate_library(a.seed, n_scaffolds=a.scaffolds, scaffold_len=scaffold_len,
+                                        gap=(scaffold_len // 2, 300), pairs=a.pairs // a.scaffolds, mean=300, sd=20,
+                                        unmapped_pairs=a.pairs // 100, ambiguous=0.0)
+    bam = BW.bam_bytes(refs, recs)
+    recs = list(recs)
+    random.Random(a.seed + 1).shuffle(recs)
+    shuffled = BW.bam_bytes(refs, recs)
+    del recs
+    t_sim = time.time() - t0
+    rng = random.Random(a.seed)
+    gaps = [(rng.choice(refs)[0], rng.randrange(1000, scaffold_len - 1000), rng.randrange(50, 500), rng.randrange(30, 100))
+            for _ in range(a.gaps)]
+    mean, sd = 300, 20
+    # the per-gap loop on the first gaps
+    t0 = time.perf_counter()
+    loop = []
+    for s, bp, gl, fl in gaps[:a.loop_gaps]:
+        loop.append(P.filter_reads(bam, mean=mean, std_dev=sd, scaffold=s, breakpoint=bp, gap_length=gl, flank_length=fl,
+                                   threads=a.threads))
+    t_loop = time.perf_counter() - t0
+    out = dict(workload="readfilter_gaps", pairs=a.pairs, records=loop[0][4] if loop else None, gaps=a.gaps,
+               bam_mb=round(len(bam) / 1e6, 1), simulate_s=round(t_sim, 1),
+               per_gap_s_measured=round(t_loop, 3), per_gap_gaps_measured=a.loop_gaps,
+               per_gap_s_extrapolated=round(t_loop / max(1, a.loop_gaps) * a.gaps, 2))
+    runs = (("host", bam, -1), ("device_first", bam, a.device), ("device", bam, a.device),
+            ("shuffled_host", shuffled, -1), ("shuffled_device", shuffled, a.device))
+    # (the shuffled file's reads come out in its own order: checked against the per-gap filter on that file)
+    check = {id(bam): loop, id(shuffled): [P.filter_reads(shuffled, mean=mean, std_dev=sd, scaffold=s, breakpoint=bp,
+                                                          gap_length=gl, flank_length=fl) for s, bp, gl, fl in gaps[:3]]}
+    for label, data, dev in runs:
+        t0 = time.perf_counter()
+        got, st = P.filter_reads_gaps(data, mean, sd, gaps, device=dev, threads=a.threads)
+        dt = time.perf_counter() - t0
+        want = check[id(data)]
+        assert got[:len(want)] == want, label + ": differs from the per-gap filter"
+        out[label] = dict(s=round(dt, 3), inflate_ms=round(st["ms_inflate"], 1), join_ms=round(st["ms_join"], 1),
+                          text_ms=round(st["ms_text"], 1), on_device=st["on_device"], file_passes=st["file_passes"],
+                          extracted=sum(x[3] for x in got))
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
