@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "../../include/g2s.h"
+#include "../../include/g2s_test.h"
 #include "bam.hpp"
 #include "readfilter_gaps.hpp"
 
@@ -336,6 +337,48 @@ int g2s_filter_reads_gaps_mem(const void* bam_bytes, size_t nbytes, const g2s_fi
   if (!bam.open_mem(bam_bytes, nbytes, &err)) { g2s::set_filter_error(err); return G2S_ERR_IO; }
   return g2s::run_filter_gaps(bam, lib, gaps, n, device, fasta_out, log_out, warn_out, extracted, total, unmapped_out,
                               unmapped_extracted, stats);
+}
+
+// TEST HOOK (include/g2s_test.h): one of the joins on the caller's rows and windows.  The path is the caller's
+// choice alone: no G2S_HOST_FILTER, and a device that cannot run the kernels is an error, not the host path.
+int g2s_test_filter_join(int device, int32_t threads, uint64_t nr, const int32_t* ref_id, const int32_t* pos,
+                         const int64_t* end, const uint32_t* flag, const uint64_t* h_own, const uint64_t* h_mate,
+                         int64_t max_span, uint64_t bits, uint64_t n, const int64_t* windows, uint64_t max_pairs,
+                         uint64_t* list1, uint64_t cap1, uint64_t* n1, uint64_t* list2, uint64_t cap2, uint64_t* n2) {
+  if ((nr && (!ref_id || !pos || !end || !flag || !h_own || !h_mate)) || (n && !windows) || !n1 || !n2 ||
+      (cap1 && !list1) || (cap2 && !list2) || nr >= (uint64_t)UINT32_MAX - 1 || n > g2s::kFilterGapMask || threads < 1) {
+    g2s::set_filter_error("g2s_test_filter_join: bad argument");
+    return G2S_ERR_ARG;
+  }
+  *n1 = *n2 = 0;
+  if (device >= 0 && !g2s::filter_device_usable(device)) {
+    g2s::set_filter_error("g2s_test_filter_join: no usable gfx950 device " + std::to_string(device));
+    return G2S_ERR_NO_DEVICE;
+  }
+  g2s::FilterRows R;
+  R.ref_id.assign(ref_id, ref_id + nr);
+  R.pos.assign(pos, pos + nr);
+  R.end.assign(end, end + nr);
+  R.flag.assign(flag, flag + nr);
+  R.h_own.assign(h_own, h_own + nr);
+  R.h_mate.assign(h_mate, h_mate + nr);
+  R.max_span = max_span;
+  g2s::FilterJoin J;
+  J.rows = &R;
+  J.bits = bits;
+  J.max_pairs = max_pairs;
+  J.win.resize(3 * (size_t)n);
+  for (size_t i = 0; i < 3 * (size_t)n; i++)
+    J.win[i] = g2s::FilterWindow{(int32_t)windows[3 * i], 0, windows[3 * i + 1], windows[3 * i + 2]};
+  std::string err;
+  const int rc = device >= 0 ? g2s::filter_join_device(J, device, &err) : g2s::filter_join_host(J, threads, &err);
+  g2s::set_filter_error(err);
+  if (rc != G2S_OK) return rc;
+  *n1 = J.list1.size();
+  *n2 = J.list2.size();
+  if (cap1 && *n1) memcpy(list1, J.list1.data(), 8 * (size_t)std::min<uint64_t>(cap1, *n1));
+  if (cap2 && *n2) memcpy(list2, J.list2.data(), 8 * (size_t)std::min<uint64_t>(cap2, *n2));
+  return G2S_OK;
 }
 
 }  // extern "C"

@@ -200,6 +200,11 @@ _SIGS = {
     "g2s_test_worker_pool": (C.c_int, [C.c_int32, C.c_int32, C.c_int32]),
     "g2s_test_group_queue": (C.c_int, [C.c_int32, C.c_uint64, C.c_uint64, C.POINTER(C.c_int32)]),
     "g2s_test_group_queue_slow": (C.c_int, [C.c_int32, C.c_uint64, C.c_uint64, C.c_int32, C.c_uint32, C.POINTER(C.c_int32)]),
+    "g2s_test_filter_join": (C.c_int, [C.c_int, C.c_int32, C.c_uint64, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                       C.POINTER(C.c_int64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64),
+                                       C.POINTER(C.c_uint64), C.c_int64, C.c_uint64, C.c_uint64, C.POINTER(C.c_int64),
+                                       C.c_uint64, C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(C.c_uint64),
+                                       C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(C.c_uint64)]),
     "g2s_graph_validate": (C.c_int64, [C.c_void_p, C.c_char_p, C.c_size_t]),
     "g2s_test_post_gap": (C.c_int, [_VP, C.POINTER(g2s_params), C.POINTER(g2s_gap), C.c_int32,
                                     C.POINTER(C.c_uint32), C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.c_int32,
@@ -891,3 +896,28 @@ def test_rand_stream(seed, skip, n):
     out = (C.c_int32 * max(1, n))()
     _check(load_library().g2s_test_rand_stream(seed, skip, n, out))
     return [out[i] for i in range(n)]
+
+
+def test_filter_join(ref_id, pos, end, flag, h_own, h_mate, max_span, bits, windows, max_pairs, device=-1, threads=1):
+    """TEST HOOK binding: the joins of the batched read filter on the caller's rows; `windows` holds three
+    (tid, beg, end) a gap.  device < 0: the host joins on `threads` threads; otherwise the device joins (no host path
+    in their place).  Returns (the join's code, list 1, list 2, g2s_filter_last_error's text) with the lists as
+    (gap, row) tuples; nothing is raised, the code is the caller's to check."""
+    lib = load_library()
+    nr, n = len(pos), len(windows) // 3
+    assert len(windows) == 3 * n and all(len(x) == nr for x in (ref_id, end, flag, h_own, h_mate))
+    flat = [v for w in windows for v in w]
+    args = [(C.c_int32 * max(1, nr))(*ref_id), (C.c_int32 * max(1, nr))(*pos), (C.c_int64 * max(1, nr))(*end),
+            (C.c_uint32 * max(1, nr))(*flag), (C.c_uint64 * max(1, nr))(*h_own), (C.c_uint64 * max(1, nr))(*h_mate)]
+    win = (C.c_int64 * max(1, len(flat)))(*flat)
+    cap1 = cap2 = 1 << 16
+    while True:
+        l1, l2 = (C.c_uint64 * cap1)(), (C.c_uint64 * cap2)()
+        n1, n2 = C.c_uint64(0), C.c_uint64(0)
+        rc = lib.g2s_test_filter_join(device, threads, nr, *args, max_span, bits, n, win, max_pairs, l1, cap1,
+                                      C.byref(n1), l2, cap2, C.byref(n2))
+        if rc != G2S_OK or (n1.value <= cap1 and n2.value <= cap2):
+            break
+        cap1, cap2 = max(cap1, n1.value), max(cap2, n2.value)
+    msg = (lib.g2s_filter_last_error() or b"").decode("utf-8", "replace")
+    return rc, [(x >> 32, x & 0xFFFFFFFF) for x in l1[:n1.value]], [(x >> 32, x & 0xFFFFFFFF) for x in l2[:n2.value]], msg

@@ -3,7 +3,8 @@
  * Nothing here is a fill path (none of these can compute the DP) and nothing of the reference binds to them: they let
  * the unit tests (tests/test_host.py, tests/test_seg_model.py, tests/test_shard.py, tests/test_gpu_*.py) drive single
  * pieces of the host side — the host half of phase D on caller-supplied tables, the graph tables, the rand() stream
- * of the host and of the device, the worker pool, the shared group counter — without a kernel run. */
+ * of the host and of the device, the worker pool, the shared group counter — without a kernel run; and one drives the
+ * joins of the batched read filter (host or device) on rows and windows instead of a BAM file. */
 #ifndef G2S_TEST_H_
 #define G2S_TEST_H_
 #include "g2s.h"
@@ -80,6 +81,19 @@ int g2s_test_group_queue(int32_t nworkers, uint64_t n, uint64_t group_size, int3
  * or slower device): what it does not get to is taken by the others — the queue hands a group to whoever asks. */
 int g2s_test_group_queue_slow(int32_t nworkers, uint64_t n, uint64_t group_size, int32_t slow_worker, uint32_t slow_us,
                               int32_t* owner);
+
+/* TEST HOOK: the joins of the batched read filter (readfilter_gaps.hpp: FilterRows, FilterJoin) on rows and windows
+ * supplied by the caller, without a BAM file: nr rows (reference, position, end position, flag, hash of the own name
+ * and of the mate's), the longest span, the filter's size in bits, n gaps with three windows each (`windows`: 9 values
+ * a gap, (tid, beg, end) of the left, the right and the flank window) and the pair cap.  device < 0: filter_join_host
+ * on `threads` threads; device >= 0: filter_join_device on that device — G2S_ERR_NO_DEVICE when it is no usable
+ * gfx950 (never the host path in its place; G2S_HOST_FILTER is not read).  Returns the join's own code, its message in
+ * g2s_filter_last_error().  *n1 / *n2 receive the true sizes of list 1 / list 2 ((gap << 32 | row), ascending); the
+ * first min(cap, size) pairs of each are written, so a caller whose capacity was too small calls again. */
+int g2s_test_filter_join(int device, int32_t threads, uint64_t nr, const int32_t* ref_id, const int32_t* pos,
+                         const int64_t* end, const uint32_t* flag, const uint64_t* h_own, const uint64_t* h_mate,
+                         int64_t max_span, uint64_t bits, uint64_t n, const int64_t* windows, uint64_t max_pairs,
+                         uint64_t* list1, uint64_t cap1, uint64_t* n1, uint64_t* list2, uint64_t cap2, uint64_t* n2);
 
 #ifdef __cplusplus
 }

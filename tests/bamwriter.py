@@ -61,7 +61,7 @@ def record(name, flag, tid, pos, cigar, seq, mtid=-1, mpos=-1, tlen=0, mapq=30, 
     ops = parse_cigar(cigar) if isinstance(cigar, str) else cigar
     nm = name.encode() + b"\0"
     rlen = sum(n for n, op in ops if op in (0, 2, 3, 7, 8)) if not (flag & 4) else 0
-    b = _reg2bin(max(pos, 0), max(pos, 0) + (rlen or 1))
+    b = min(_reg2bin(max(pos, 0), max(pos, 0) + (rlen or 1)), 0xFFFF)  # (beyond 2^29 the bin has no 16-bit value; no reader here uses it)
     codes = [SEQ_CODES.index(c) if c in SEQ_CODES else 15 for c in seq.upper()]
     if len(codes) % 2:
         codes.append(0)

@@ -30,6 +30,19 @@ def test_every_gap_equals_the_per_gap_filter(case):
         assert x == w, g
 
 
+NEW_LIBRARIES = ("sd-negative", "long-span", "mixed-lengths", "repeated-names", "placed-at-minus-one", "many-scaffolds",
+                 "high-coordinates")
+
+
+@pytest.mark.parametrize("case", [c for c in FC.all_cases() if c[0].startswith(NEW_LIBRARIES)], ids=lambda c: c[0])
+def test_the_per_gap_filters_pass_over_the_file_agrees_too(case, monkeypatch):
+    """the per-gap filter without its candidate list (G2S_FILTER_MAX_CANDS=0: the windows applied in a pass over the
+    file) on the libraries whose windows and spans are unusual: the restatement's answer again"""
+    _, bam, mean, sd, gaps = case
+    monkeypatch.setenv("G2S_FILTER_MAX_CANDS", "0")
+    FC.expected(P, bam, mean, sd, gaps)
+
+
 def test_golden_batch_covers_the_committed_answers():
     """All the committed calls (tests/golden/readfilter_cases.json) through the batched call, against the answers
     committed with them — the unmapped reads from the same two passes included."""
