@@ -19,6 +19,9 @@ bool graph_finish_gpu(Graph& g, int device, const std::function<void(const std::
 bool graph_build_sets_gpu(Graph& g, const std::vector<std::pair<const char*, uint64_t>>& seqs, const std::vector<uint32_t>& seq_set,
                           uint32_t nsets, int solid, int device,
                           const std::function<void(const std::vector<uint32_t>&, uint32_t)>& host_walk, std::string* why);
+bool graph_build_pool_gpu(Graph& g, const PoolSets& ps, int solid, int device,
+                          const std::function<void(const std::vector<uint32_t>&, uint32_t)>& host_walk, PoolBuildInfo* info,
+                          std::string* why);
 
 namespace {
 
@@ -466,6 +469,10 @@ void append_set_part(Graph& u, const Graph& p, uint64_t off) {
   std::copy(p.lastnt.begin(), p.lastnt.end(), u.lastnt.begin() + (ptrdiff_t)(2 * off));
 }
 
+using SetSeqsFn = std::function<const std::vector<std::pair<const char*, uint64_t>>*(uint32_t, std::vector<std::pair<const char*, uint64_t>>*)>;
+Graph* build_sets_host(const SetSeqsFn& set_seqs, uint32_t nsets, int k, int solid, int nthreads,
+                       std::chrono::steady_clock::time_point t0, std::string* err);
+
 }  // namespace
 
 Graph* graph_build_sets(const std::vector<std::pair<const char*, uint64_t>>& seqs, const std::vector<uint32_t>& seq_set,
@@ -499,18 +506,30 @@ Graph* graph_build_sets(const std::vector<std::pair<const char*, uint64_t>>& seq
   }
   std::vector<std::vector<std::pair<const char*, uint64_t>>> by_set(nsets);
   for (size_t j = 0; j < seqs.size(); j++) by_set[seq_set[j]].push_back(seqs[j]);
+  return build_sets_host([&](uint32_t s, std::vector<std::pair<const char*, uint64_t>>* tmp) { (void)tmp; return &by_set[s]; }, nsets, k,
+                         solid, nthreads, t0, err);
+}
+
+namespace {
+
+// The set graph on host threads, set by set: set_seqs(s, tmp) gives set s's (pointer, length) list (its own, or one
+// written into tmp, a list of the calling thread).
+Graph* build_sets_host(const SetSeqsFn& set_seqs, uint32_t nsets, int k, int solid, int nthreads,
+                       std::chrono::steady_clock::time_point t0, std::string* err) {
   const int kb = kmer_width(k);
   std::vector<Graph*> parts(nsets, nullptr);
   {
     std::atomic<uint32_t> next(0);
     auto work = [&]() {
+      std::vector<std::pair<const char*, uint64_t>> tmp;
       while (true) {
         const uint32_t s = next.fetch_add(1);
         if (s >= nsets) break;
         Graph* p = new Graph();
-        if (kb == 8) build_set_part<uint64_t>(by_set[s], k, solid, p);
-        else if (kb == 16) build_set_part<u128>(by_set[s], k, solid, p);
-        else build_set_part<u256>(by_set[s], k, solid, p);
+        const std::vector<std::pair<const char*, uint64_t>>& mine = *set_seqs(s, &tmp);
+        if (kb == 8) build_set_part<uint64_t>(mine, k, solid, p);
+        else if (kb == 16) build_set_part<u128>(mine, k, solid, p);
+        else build_set_part<u256>(mine, k, solid, p);
         parts[s] = p;
       }
     };
@@ -557,6 +576,83 @@ Graph* graph_build_sets(const std::vector<std::pair<const char*, uint64_t>>& seq
   if (getenv("G2S_DEBUG"))
     fprintf(stderr, "[g2s] set graph build: %u sets, %llu k-mers, %.3f s on the host (%d threads)\n", nsets,
             (unsigned long long)g->n, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(), nthreads);
+  return g;
+}
+
+std::mutex g_pool_info_mu;
+PoolBuildInfo g_pool_info;
+
+}  // namespace
+
+PoolBuildInfo last_pool_build() {
+  std::lock_guard<std::mutex> lk(g_pool_info_mu);
+  return g_pool_info;
+}
+
+Graph* graph_build_pool(const PoolSets& ps, int k, int solid, int nthreads, std::string* err) {
+  if (k < 1 || k > kMaxK) { if (err) *err = "k must be in [1," + std::to_string(kMaxK) + "]"; return nullptr; }
+  const std::vector<std::pair<const char*, uint64_t>>& seqs = *ps.seqs;
+  if (ps.nsets == 0 || seqs.size() >= (1ull << 32)) { if (err) *err = "graph_build_pool: no sets, or 2^32 sequences or more"; return nullptr; }
+  for (uint32_t s = 0; s < ps.nsets; s++)
+    if (ps.set_begin[s + 1] < ps.set_begin[s]) { if (err) *err = "graph_build_pool: set_begin decreases at set " + std::to_string(s); return nullptr; }
+  for (uint64_t q = ps.set_begin[0]; q < ps.set_begin[ps.nsets]; q++)
+    if (ps.set_seq[q] >= seqs.size()) { if (err) *err = "graph_build_pool: sequence index " + std::to_string(ps.set_seq[q]) + " out of range"; return nullptr; }
+  for (uint64_t x = 0; x < ps.nshared; x++)
+    if (ps.shared_seq[x] >= seqs.size()) { if (err) *err = "graph_build_pool: shared sequence index " + std::to_string(ps.shared_seq[x]) + " out of range"; return nullptr; }
+  // a set's expanded list: pointers only, no text moves
+  auto expand = [&](uint32_t s, std::vector<std::pair<const char*, uint64_t>>* out) {
+    out->clear();
+    for (uint64_t q = ps.set_begin[s]; q < ps.set_begin[s + 1]; q++) out->push_back(seqs[ps.set_seq[q]]);
+    if (ps.flagged(s))
+      for (uint64_t x = 0; x < ps.nshared; x++) out->push_back(seqs[ps.shared_seq[x]]);
+    return out;
+  };
+  if (ps.nsets == 1) {  // an ordinary graph, as graph_build_sets' callers get for one set
+    std::vector<std::pair<const char*, uint64_t>> all;
+    return graph_build(*expand(0, &all), k, solid, nthreads, err);
+  }
+  if (nthreads <= 0) nthreads = (int)std::max(1u, std::thread::hardware_concurrency());
+  const auto t0 = std::chrono::steady_clock::now();
+  PoolBuildInfo info;
+  // on the GPU when there is one (dbg_gpu.hip: the pool's k-mers extracted once, the own lists' (set, k-mer) pairs and
+  // the shared list's k-mers gathered from them, the shared list sorted once and merged into every flagged set); even
+  // k, no device, G2S_HOST_BUILD=1, an empty union: the host build, set by set over each set's pointers
+  if (!getenv("G2S_HOST_BUILD")) {
+    Graph* g = new Graph();
+    g->k = k;
+    g->solid = solid;
+    g->kmer_bytes = kmer_width(k);
+    std::string why;
+    const bool ok = graph_build_pool_gpu(*g, ps, solid, getenv("G2S_DEVICE") ? atoi(getenv("G2S_DEVICE")) : 0,
+                                         [&](const std::vector<uint32_t>& succ_r, uint32_t first_id) {
+                                           unitig_order(succ_r, g->n, false, &g->rank2id, &g->flip, &g->n_unitigs, true, first_id);
+                                         }, &info, &why);
+    if (ok) {
+      if (getenv("G2S_DEBUG"))
+        fprintf(stderr, "[g2s] pooled set graph build: %u sets, %llu k-mers, %llu own + %llu shared positions, %llu keys sorted, %.3f s on the GPU\n",
+                ps.nsets, (unsigned long long)g->n, (unsigned long long)info.own_positions, (unsigned long long)info.shared_positions,
+                (unsigned long long)info.keys_sorted, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+      info.on_device = 1;
+      std::lock_guard<std::mutex> lk(g_pool_info_mu);
+      g_pool_info = info;
+      return g;
+    }
+    if (getenv("G2S_DEBUG")) fprintf(stderr, "[g2s]   pooled set graph on the host (%s)\n", why.c_str());
+    delete g;
+  }
+  info = PoolBuildInfo();
+  uint64_t flagged = 0;
+  for (uint32_t s = 0; s < ps.nsets; s++) flagged += ps.flagged(s) ? 1 : 0;
+  for (uint64_t q = ps.set_begin[0]; q < ps.set_begin[ps.nsets]; q++) info.own_positions += seqs[ps.set_seq[q]].second + 1;
+  if (flagged)
+    for (uint64_t x = 0; x < ps.nshared; x++) info.shared_positions += seqs[ps.shared_seq[x]].second + 1;
+  info.keys_sorted = info.own_positions + flagged * info.shared_positions;
+  Graph* g = build_sets_host([&](uint32_t s, std::vector<std::pair<const char*, uint64_t>>* tmp) { return expand(s, tmp); }, ps.nsets, k,
+                             solid, nthreads, t0, err);
+  if (g) {
+    std::lock_guard<std::mutex> lk(g_pool_info_mu);
+    g_pool_info = info;
+  }
   return g;
 }
 

@@ -108,6 +108,30 @@ Graph* graph_build(const std::vector<std::pair<const char*, uint64_t>>& seqs, in
 // sequences alone, up to the numbering of nodes.
 Graph* graph_build_sets(const std::vector<std::pair<const char*, uint64_t>>& seqs, const std::vector<uint32_t>& seq_set,
                         uint32_t nsets, int k, int solid, int nthreads, std::string* err);
+// The same set graph from a POOL of sequences the sets share, without the expanded list: set s is the multiset
+// seqs[set_seq[q]], q in [set_begin[s], set_begin[s+1]) (its own list), followed by seqs[shared_seq[*]] when
+// set_shared[s] is set.  A sequence may be in any number of sets, and more than once in one; every occurrence counts
+// towards solidity.  The graph is graph_build_sets' for the expanded list, up to the numbering of nodes inside a set.
+// On the device (odd k; dbg_gpu.hip) the shared list is encoded and sorted once, whatever the number of flagged sets.
+struct PoolSets {
+  const std::vector<std::pair<const char*, uint64_t>>* seqs = nullptr;
+  const uint64_t* set_begin = nullptr;   // [nsets + 1]
+  const uint32_t* set_seq = nullptr;     // [set_begin[nsets]]
+  const uint32_t* shared_seq = nullptr;  // [nshared]
+  uint64_t nshared = 0;
+  const uint8_t* set_shared = nullptr;   // [nsets], or nullptr: no set holds the shared list
+  uint32_t nsets = 0;
+  bool flagged(uint32_t s) const { return set_shared && set_shared[s] != 0; }
+};
+Graph* graph_build_pool(const PoolSets& ps, int k, int solid, int nthreads, std::string* err);
+// What the process's last graph_build_pool of several sets did (g2s_test_last_pool_build): the positions (bases + 1 a
+// sequence) of the own lists and of the shared list, and the keys that went through a sort — on the device
+// own + shared whatever the number of flagged sets; the host build works on every flagged set's expanded list.
+struct PoolBuildInfo {
+  uint64_t own_positions = 0, shared_positions = 0, keys_sorted = 0;
+  int on_device = 0;
+};
+PoolBuildInfo last_pool_build();
 bool graph_save(const Graph& g, const std::string& path, std::string* err);
 Graph* graph_load(const std::string& path, std::string* err);
 

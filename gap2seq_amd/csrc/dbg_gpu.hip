@@ -398,6 +398,146 @@ __global__ void k_set_first(const uint32_t* __restrict__ rank_set, uint32_t n, u
   set_lo[s] = lo;
 }
 
+// ---- pooled set graphs (dbg.hpp: PoolSets): the pool's k-mers are extracted once, one key per pool position; the sets'
+// lists name pool sequences, an INSTANCE being one occurrence of a sequence in a list (own lists in set order, or
+// the shared list)
+__global__ void k_inst_len(const uint32_t* __restrict__ inst_seq, const uint32_t* __restrict__ seq_len1, uint32_t ninst,
+                           uint32_t* __restrict__ len1) {
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j < ninst) len1[j] = seq_len1[inst_seq[j]];
+}
+// one (key, set) pair per instance position: the instance by binary search in the instances' start table (the scan of
+// their lengths + 1), the key by gather from the pool position.  A window that crosses the sequence's end or holds an
+// N is the all-ones filler there already.  sid / inst_set == nullptr: keys only (the shared list).
+template <class KT>
+__global__ void k_pool_pairs(const KT* __restrict__ pool_keys, const uint32_t* __restrict__ inst_start,
+                             const uint32_t* __restrict__ inst_seq, const uint32_t* __restrict__ inst_set,
+                             const uint32_t* __restrict__ seq_start, uint32_t ninst, uint64_t I, KT* __restrict__ keys,
+                             uint32_t* __restrict__ sid) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= I) return;
+  uint32_t lo = 0, hi = ninst;  // the last instance starting at or before i (every instance has a position: its separator)
+  while (hi - lo > 1) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if ((uint64_t)inst_start[mid] <= i) lo = mid; else hi = mid;
+  }
+  keys[i] = pool_keys[(size_t)seq_start[inst_seq[lo]] + (size_t)(i - inst_start[lo])];
+  if (sid) sid[i] = inst_set[lo];
+}
+template <class KT>
+__global__ void k_gather_keys(const KT* __restrict__ keys, const uint32_t* __restrict__ idx, uint64_t n, KT* __restrict__ out) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  out[i] = keys[idx[i]];
+}
+// the own lists' runs as a table: (k-mer, set, count), ascending by (set, k-mer)
+template <class KT>
+__global__ void k_run_table(const KT* __restrict__ sk, const uint32_t* __restrict__ ss, const uint32_t* __restrict__ hidx,
+                            const uint32_t* __restrict__ tidx, uint32_t nruns, KT* __restrict__ rkey, uint32_t* __restrict__ rset,
+                            uint32_t* __restrict__ rcnt) {
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= nruns) return;
+  rkey[j] = sk[hidx[j]];
+  rset[j] = ss[hidx[j]];
+  rcnt[j] = tidx[j] - hidx[j] + 1u;
+}
+// the shared list's runs as a table: (k-mer, count), ascending
+template <class KT>
+__global__ void k_shared_table(const KT* __restrict__ sorted, const uint32_t* __restrict__ hidx, uint32_t nheads, uint32_t n_valid,
+                               KT* __restrict__ hkey, uint32_t* __restrict__ hcnt) {
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= nheads) return;
+  hkey[j] = sorted[hidx[j]];
+  hcnt[j] = (j + 1 < nheads ? hidx[j + 1] : n_valid) - hidx[j];
+}
+template <class KT>
+__device__ __forceinline__ uint32_t d_lower_bound(const KT* __restrict__ v, uint32_t lo, uint32_t hi, const KT& x) {
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (v[mid] < x) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+// The merge of the own runs and the shared table, per set.  A set without the flag keeps its runs of at least `solid`
+// copies.  A flagged set (set_fidx[s] = its number among the F flagged sets, else INV) keeps every shared k-mer whose
+// shared count plus own count reaches `solid` (item f * U + u below) and every run of at least `solid` copies whose
+// k-mer the shared table does not hold.  Both flag arrays carry one more entry, zero, so that their exclusive scans
+// end in the totals.
+template <class KT>
+__global__ void k_pool_keep_own(const KT* __restrict__ rkey, const uint32_t* __restrict__ rset, const uint32_t* __restrict__ rcnt,
+                                uint32_t nruns, const uint32_t* __restrict__ set_fidx, const KT* __restrict__ hkey, uint32_t U,
+                                uint32_t solid, uint32_t* __restrict__ keep) {
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j > nruns) return;
+  bool kp = j < nruns && rcnt[j] >= solid;
+  if (kp && set_fidx[rset[j]] != INV) {
+    const KT x = rkey[j];
+    const uint32_t u = d_lower_bound<KT>(hkey, 0u, U, x);
+    kp = !(u < U && hkey[u] == x);  // (in the shared table: the shared item decides, on the sum)
+  }
+  keep[j] = kp ? 1u : 0u;
+}
+template <class KT>
+__global__ void k_pool_keep_shared(const KT* __restrict__ hkey, const uint32_t* __restrict__ hcnt, uint32_t U,
+                                   const uint32_t* __restrict__ fset, uint32_t FU, const uint32_t* __restrict__ run_lo,
+                                   const KT* __restrict__ rkey, const uint32_t* __restrict__ rcnt, uint32_t solid,
+                                   uint32_t* __restrict__ keep) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i > FU) return;
+  if (i == FU) { keep[i] = 0u; return; }
+  const uint32_t f = i / U, u = i - f * U, s = fset[f], hi = run_lo[s + 1];
+  const KT x = hkey[u];
+  const uint32_t r = d_lower_bound<KT>(rkey, run_lo[s], hi, x);
+  const uint64_t own = (r < hi && rkey[r] == x) ? rcnt[r] : 0u;
+  keep[i] = ((uint64_t)hcnt[u] + own >= (uint64_t)solid) ? 1u : 0u;
+}
+// every set's k-mers kept (pown / psh: the exclusive scans of the two flag arrays); cnt[nsets] = 0
+__global__ void k_pool_set_count(const uint32_t* __restrict__ run_lo, const uint32_t* __restrict__ pown,
+                                 const uint32_t* __restrict__ set_fidx, const uint32_t* __restrict__ psh, uint32_t U, uint32_t nsets,
+                                 uint32_t* __restrict__ cnt) {
+  const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s > nsets) return;
+  uint32_t c = 0;
+  if (s < nsets) {
+    c = pown[run_lo[s + 1]] - pown[run_lo[s]];
+    const uint32_t f = set_fidx[s];
+    if (f != INV) c += psh[(f + 1u) * U] - psh[f * U];
+  }
+  cnt[s] = c;
+}
+// The output is written in (set, k-mer) order without a second sort: in set s, from base[s] on, a kept k-mer lands
+// behind the kept shared k-mers and the kept own-only runs that are smaller than it.
+template <class KT>
+__global__ void k_pool_write_own(const KT* __restrict__ rkey, const uint32_t* __restrict__ rset, uint32_t nruns,
+                                 const uint32_t* __restrict__ keep, const uint32_t* __restrict__ pown,
+                                 const uint32_t* __restrict__ run_lo, const uint32_t* __restrict__ set_fidx,
+                                 const KT* __restrict__ hkey, uint32_t U, const uint32_t* __restrict__ psh,
+                                 const uint32_t* __restrict__ base, KT* __restrict__ out, uint32_t* __restrict__ out_sid) {
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= nruns || !keep[j]) return;
+  const uint32_t s = rset[j], f = set_fidx[s];
+  const KT x = rkey[j];
+  uint32_t pos = base[s] + (pown[j] - pown[run_lo[s]]);
+  if (f != INV) pos += psh[f * U + d_lower_bound<KT>(hkey, 0u, U, x)] - psh[f * U];
+  out[pos] = x;
+  out_sid[pos] = s;
+}
+template <class KT>
+__global__ void k_pool_write_shared(const KT* __restrict__ hkey, uint32_t U, const uint32_t* __restrict__ fset, uint32_t FU,
+                                    const uint32_t* __restrict__ keep, const uint32_t* __restrict__ psh,
+                                    const uint32_t* __restrict__ run_lo, const KT* __restrict__ rkey,
+                                    const uint32_t* __restrict__ pown, const uint32_t* __restrict__ base, KT* __restrict__ out,
+                                    uint32_t* __restrict__ out_sid) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= FU || !keep[i]) return;
+  const uint32_t f = i / U, u = i - f * U, s = fset[f], lo = run_lo[s];
+  const KT x = hkey[u];
+  const uint32_t r = d_lower_bound<KT>(rkey, lo, run_lo[s + 1], x);  // (a run of x itself is not kept as own: either bound will do)
+  const uint32_t pos = base[s] + (psh[i] - psh[f * U]) + (pown[r] - pown[lo]);
+  out[pos] = x;
+  out_sid[pos] = s;
+}
+
 struct Dev {
   void* p = nullptr;
   ~Dev() { if (p) (void)hipFree(p); }
@@ -718,6 +858,81 @@ static bool count_solid_gpu_t(Graph& g, std::vector<KT>& out, const std::vector<
 #undef G2S_GPU_TRY
 }
 
+#define G2S_GPU_TRY(expr)                                                                 \
+  do {                                                                                    \
+    hipError_t e_ = (expr);                                                               \
+    if (e_ != hipSuccess) { if (why) *why = std::string(#expr) + ": " + hipGetErrorString(e_); return false; } \
+  } while (0)
+
+// T keys sorted by (set, k-mer), or by k-mer alone without set ids (d_sid / d_ss == nullptr): LSD passes over the
+// k-mer's 64-bit words, then one stable pass over the set id, as (word, index) pairs with one gather at the end.
+// d_keys and d_sid are consumed; the sorted copies land in d_sk / d_ss.
+template <class KT>
+static bool sort_keyed_gpu(Dev& d_keys, Dev* d_sid, uint64_t T, Dev& d_sk, Dev* d_ss, std::string* why) {
+  Dev d_w0, d_w1, d_i0, d_i1, d_tmp;
+  const dim3 blk(256), grdT((unsigned)((T + 255) / 256));
+  G2S_GPU_TRY(d_w0.alloc((size_t)T * 8));
+  G2S_GPU_TRY(d_w1.alloc((size_t)T * 8));
+  G2S_GPU_TRY(d_i0.alloc((size_t)T * 4));
+  G2S_GPU_TRY(d_i1.alloc((size_t)T * 4));
+  uint64_t *w_in = (uint64_t*)d_w0.p, *w_out = (uint64_t*)d_w1.p;
+  uint32_t *i_in = (uint32_t*)d_i0.p, *i_out = (uint32_t*)d_i1.p;
+  size_t tb = 0;
+  G2S_GPU_TRY(rocprim::radix_sort_pairs(nullptr, tb, w_in, w_out, i_in, i_out, (size_t)T, 0, 64));
+  G2S_GPU_TRY(d_tmp.alloc(tb));
+  constexpr int W = (int)(sizeof(KT) / 8);
+  const uint32_t* sid = d_sid ? (const uint32_t*)d_sid->p : nullptr;
+  for (int w = 0; w < (sid ? W + 1 : W); w++) {
+    const int word = w < W ? w : -1;
+    hipLaunchKernelGGL(k_key_word<KT>, grdT, blk, 0, 0, (const KT*)d_keys.p, sid,
+                       w == 0 ? (const uint32_t*)nullptr : (const uint32_t*)i_in, T, word, w_in, i_in);
+    G2S_GPU_TRY(rocprim::radix_sort_pairs(d_tmp.p, tb, w_in, w_out, i_in, i_out, (size_t)T, 0, word < 0 ? 32 : 64));
+    std::swap(i_in, i_out);
+  }
+  for (Dev* d : {&d_w0, &d_w1, &d_tmp}) (void)hipFree(d->release());
+  G2S_GPU_TRY(d_sk.alloc((size_t)T * sizeof(KT)));
+  if (sid) {
+    G2S_GPU_TRY(d_ss->alloc((size_t)T * 4));
+    hipLaunchKernelGGL(k_gather_keyed<KT>, grdT, blk, 0, 0, (const KT*)d_keys.p, sid, (const uint32_t*)i_in, T, (KT*)d_sk.p,
+                       (uint32_t*)d_ss->p);
+    (void)hipFree(d_sid->release());
+  } else {
+    hipLaunchKernelGGL(k_gather_keys<KT>, grdT, blk, 0, 0, (const KT*)d_keys.p, (const uint32_t*)i_in, T, (KT*)d_sk.p);
+  }
+  G2S_GPU_TRY(hipGetLastError());
+  (void)hipFree(d_keys.release());
+  return true;
+}
+
+// the runs of equal (set, k-mer) in T sorted keys: run j = [hidx[j], tidx[j]]
+template <class KT>
+static bool runs_keyed_gpu(const KT* sk, const uint32_t* ss, uint64_t T, Dev& d_hidx, Dev& d_tidx, uint32_t* nruns_out, std::string* why) {
+  Dev d_flag, d_pos, d_tmp2;
+  const dim3 blk(256), grdT((unsigned)((T + 255) / 256));
+  G2S_GPU_TRY(d_flag.alloc((size_t)T * 4));
+  G2S_GPU_TRY(d_pos.alloc((size_t)T * 4));
+  hipLaunchKernelGGL(k_heads_keyed<KT>, grdT, blk, 0, 0, sk, ss, T, (uint32_t*)d_flag.p);
+  size_t tb2 = 0;
+  G2S_GPU_TRY(rocprim::exclusive_scan(nullptr, tb2, (const uint32_t*)d_flag.p, (uint32_t*)d_pos.p, 0u, (size_t)T,
+                                      rocprim::plus<uint32_t>()));
+  G2S_GPU_TRY(d_tmp2.alloc(tb2));
+  G2S_GPU_TRY(rocprim::exclusive_scan(d_tmp2.p, tb2, (const uint32_t*)d_flag.p, (uint32_t*)d_pos.p, 0u, (size_t)T,
+                                      rocprim::plus<uint32_t>()));
+  uint32_t lastf = 0, lastp = 0;
+  G2S_GPU_TRY(hipMemcpy(&lastf, (const uint32_t*)d_flag.p + (T - 1), 4, hipMemcpyDeviceToHost));
+  G2S_GPU_TRY(hipMemcpy(&lastp, (const uint32_t*)d_pos.p + (T - 1), 4, hipMemcpyDeviceToHost));
+  const uint32_t nruns = lastp + lastf;
+  if (nruns) {
+    G2S_GPU_TRY(d_hidx.alloc((size_t)nruns * 4));
+    G2S_GPU_TRY(d_tidx.alloc((size_t)nruns * 4));
+    hipLaunchKernelGGL(k_runs_keyed<KT>, grdT, blk, 0, 0, sk, ss, (const uint32_t*)d_flag.p, (const uint32_t*)d_pos.p, T,
+                       (uint32_t*)d_hidx.p, (uint32_t*)d_tidx.p);
+  }
+  *nruns_out = nruns;
+  return true;
+}
+#undef G2S_GPU_TRY
+
 // The solid k-mer sets of a set graph at once: one key per text position (all sets' sequences in one text, the set
 // from a per-sequence table), sorted by (set, canonical k-mer) — LSD passes over the k-mer's 64-bit words, then one
 // stable pass over the set id, as (word, index) pairs with one gather at the end — runs over (set, k-mer), solidity per
@@ -756,8 +971,7 @@ static bool count_solid_sets_gpu_t(Graph& g, std::vector<KT>& out, std::vector<u
     }
   }
   const uint32_t ns = (uint32_t)seqs.size();
-  Dev d_text, d_start, d_sset, d_keys, d_sid, d_w0, d_w1, d_i0, d_i1, d_tmp, d_sk, d_ss, d_flag, d_pos, d_hidx, d_tidx, d_keep,
-      d_kpos, d_out, d_osid, d_lo;
+  Dev d_text, d_start, d_sset, d_keys, d_sid, d_sk, d_ss, d_hidx, d_tidx, d_keep, d_kpos, d_out, d_osid, d_lo;
   G2S_GPU_TRY(d_text.alloc((size_t)T));
   G2S_GPU_TRY(d_start.alloc((size_t)ns * 8));
   G2S_GPU_TRY(d_sset.alloc((size_t)ns * 4));
@@ -770,55 +984,16 @@ static bool count_solid_sets_gpu_t(Graph& g, std::vector<KT>& out, std::vector<u
   hipLaunchKernelGGL(k_extract<KT>, grdT, blk, 0, 0, (const uint8_t*)d_text.p, T, k, (KT*)d_keys.p);
   hipLaunchKernelGGL(k_pos_set, grdT, blk, 0, 0, (const uint64_t*)d_start.p, (const uint32_t*)d_sset.p, ns, T, (uint32_t*)d_sid.p);
   for (Dev* d : {&d_text, &d_start, &d_sset}) (void)hipFree(d->release());
-  // ---- sort: (word, index) pairs, least significant word first, the set id last (every pass stable)
-  G2S_GPU_TRY(d_w0.alloc((size_t)T * 8));
-  G2S_GPU_TRY(d_w1.alloc((size_t)T * 8));
-  G2S_GPU_TRY(d_i0.alloc((size_t)T * 4));
-  G2S_GPU_TRY(d_i1.alloc((size_t)T * 4));
-  uint64_t *w_in = (uint64_t*)d_w0.p, *w_out = (uint64_t*)d_w1.p;
-  uint32_t *i_in = (uint32_t*)d_i0.p, *i_out = (uint32_t*)d_i1.p;
-  size_t tb = 0;
-  G2S_GPU_TRY(rocprim::radix_sort_pairs(nullptr, tb, w_in, w_out, i_in, i_out, (size_t)T, 0, 64));
-  G2S_GPU_TRY(d_tmp.alloc(tb));
-  constexpr int W = (int)(sizeof(KT) / 8);
-  for (int w = 0; w <= W; w++) {
-    const int word = w < W ? w : -1;
-    hipLaunchKernelGGL(k_key_word<KT>, grdT, blk, 0, 0, (const KT*)d_keys.p, (const uint32_t*)d_sid.p,
-                       w == 0 ? (const uint32_t*)nullptr : (const uint32_t*)i_in, T, word, w_in, i_in);
-    G2S_GPU_TRY(rocprim::radix_sort_pairs(d_tmp.p, tb, w_in, w_out, i_in, i_out, (size_t)T, 0, word < 0 ? 32 : 64));
-    std::swap(i_in, i_out);
-  }
-  for (Dev* d : {&d_w0, &d_w1, &d_tmp}) (void)hipFree(d->release());
-  G2S_GPU_TRY(d_sk.alloc((size_t)T * sizeof(KT)));
-  G2S_GPU_TRY(d_ss.alloc((size_t)T * 4));
-  hipLaunchKernelGGL(k_gather_keyed<KT>, grdT, blk, 0, 0, (const KT*)d_keys.p, (const uint32_t*)d_sid.p, (const uint32_t*)i_in, T,
-                     (KT*)d_sk.p, (uint32_t*)d_ss.p);
-  for (Dev* d : {&d_i0, &d_i1, &d_keys, &d_sid}) (void)hipFree(d->release());
+  // ---- sort by (set, k-mer), then the runs -> the k-mers seen at least `solid` times in their own set
+  if (!sort_keyed_gpu<KT>(d_keys, &d_sid, T, d_sk, &d_ss, why)) return false;
   const KT* sk = (const KT*)d_sk.p;
   const uint32_t* ss = (const uint32_t*)d_ss.p;
-  // ---- runs over (set, k-mer) -> the k-mers seen at least `solid` times in their own set
-  G2S_GPU_TRY(d_flag.alloc((size_t)T * 4));
-  G2S_GPU_TRY(d_pos.alloc((size_t)T * 4));
-  hipLaunchKernelGGL(k_heads_keyed<KT>, grdT, blk, 0, 0, sk, ss, T, (uint32_t*)d_flag.p);
-  size_t tb2 = 0;
-  G2S_GPU_TRY(rocprim::exclusive_scan(nullptr, tb2, (const uint32_t*)d_flag.p, (uint32_t*)d_pos.p, 0u, (size_t)T,
-                                      rocprim::plus<uint32_t>()));
-  Dev d_tmp2;
-  G2S_GPU_TRY(d_tmp2.alloc(tb2));
-  G2S_GPU_TRY(rocprim::exclusive_scan(d_tmp2.p, tb2, (const uint32_t*)d_flag.p, (uint32_t*)d_pos.p, 0u, (size_t)T,
-                                      rocprim::plus<uint32_t>()));
-  uint32_t lastf = 0, lastp = 0;
-  G2S_GPU_TRY(hipMemcpy(&lastf, (const uint32_t*)d_flag.p + (T - 1), 4, hipMemcpyDeviceToHost));
-  G2S_GPU_TRY(hipMemcpy(&lastp, (const uint32_t*)d_pos.p + (T - 1), 4, hipMemcpyDeviceToHost));
-  const uint32_t nruns = lastp + lastf;
+  uint32_t nruns = 0;
+  if (!runs_keyed_gpu<KT>(sk, ss, T, d_hidx, d_tidx, &nruns, why)) return false;
   uint32_t n_solid = 0;
   if (nruns) {
-    G2S_GPU_TRY(d_hidx.alloc((size_t)nruns * 4));
-    G2S_GPU_TRY(d_tidx.alloc((size_t)nruns * 4));
     G2S_GPU_TRY(d_keep.alloc((size_t)nruns * 4));
     G2S_GPU_TRY(d_kpos.alloc((size_t)nruns * 4));
-    hipLaunchKernelGGL(k_runs_keyed<KT>, grdT, blk, 0, 0, sk, ss, (const uint32_t*)d_flag.p, (const uint32_t*)d_pos.p, T,
-                       (uint32_t*)d_hidx.p, (uint32_t*)d_tidx.p);
     const dim3 grdR((nruns + 255) / 256);
     hipLaunchKernelGGL(k_solid_keyed, grdR, blk, 0, 0, (const uint32_t*)d_hidx.p, (const uint32_t*)d_tidx.p, nruns,
                        (uint32_t)std::max(1, solid), (uint32_t*)d_keep.p);
@@ -869,6 +1044,262 @@ bool graph_build_sets_gpu(Graph& g, const std::vector<std::pair<const char*, uin
   if (g.kmer_bytes == 32) ok = count_solid_sets_gpu_t<u256>(g, g.kmers256, &rank_set, seqs, seq_set, nsets, solid, device, why);
   else if (g.kmer_bytes == 16) ok = count_solid_sets_gpu_t<u128>(g, g.kmers128, &rank_set, seqs, seq_set, nsets, solid, device, why);
   else ok = count_solid_sets_gpu_t<uint64_t>(g, g.kmers64, &rank_set, seqs, seq_set, nsets, solid, device, why);
+  if (!ok) return false;
+  if (g.kmer_bytes == 32) ok = finish_gpu_t<u256>(g, g.kmers256, device, host_walk, why, &rank_set);
+  else if (g.kmer_bytes == 16) ok = finish_gpu_t<u128>(g, g.kmers128, device, host_walk, why, &rank_set);
+  else ok = finish_gpu_t<uint64_t>(g, g.kmers64, device, host_walk, why, &rank_set);
+  return ok;
+}
+
+// The solid k-mer sets of a pooled set graph (dbg.hpp: PoolSets).  The expanded lists are never formed: the text of the
+// pool's sequences that some list names goes up once and gives one key per pool position; the own lists' (key, set)
+// pairs and the shared list's keys are gathered from those; the own pairs take the keyed sort and run detection of
+// count_solid_sets_gpu_t; the shared keys are sorted ONCE and run-length counted, however many sets hold them; the two
+// tables are merged per set into the (set, k-mer) order the rest of the build wants.  info: positions and keys sorted.
+template <class KT>
+static bool count_solid_pool_gpu_t(Graph& g, std::vector<KT>& out, std::vector<uint32_t>* rank_set, const PoolSets& ps, int solid,
+                                   int device, PoolBuildInfo* info, std::string* why) {
+#define G2S_GPU_TRY(expr)                                                                 \
+  do {                                                                                    \
+    hipError_t e_ = (expr);                                                               \
+    if (e_ != hipSuccess) { if (why) *why = std::string(#expr) + ": " + hipGetErrorString(e_); return false; } \
+  } while (0)
+#define G2S_SCAN(in, outp, count)                                                                                          \
+  do {                                                                                                                     \
+    size_t tb_ = 0;                                                                                                        \
+    G2S_GPU_TRY(rocprim::exclusive_scan(nullptr, tb_, (const uint32_t*)(in), (uint32_t*)(outp), 0u, (size_t)(count),       \
+                                        rocprim::plus<uint32_t>()));                                                      \
+    Dev d_tmp_;                                                                                                            \
+    G2S_GPU_TRY(d_tmp_.alloc(tb_));                                                                                        \
+    G2S_GPU_TRY(rocprim::exclusive_scan(d_tmp_.p, tb_, (const uint32_t*)(in), (uint32_t*)(outp), 0u, (size_t)(count),      \
+                                        rocprim::plus<uint32_t>()));                                                      \
+  } while (0)
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) { if (why) *why = "no device"; return false; }
+  G2S_GPU_TRY(hipSetDevice(device));
+  const int k = g.k;
+  const std::vector<std::pair<const char*, uint64_t>>& seqs = *ps.seqs;
+  const uint32_t nsets = ps.nsets;
+  // ---- the instances, and the pool sequences they name (numbered in order of first use)
+  std::vector<uint32_t> local(seqs.size(), INV), used;
+  auto use = [&](uint32_t j) -> uint32_t {
+    if (local[j] == INV) { local[j] = (uint32_t)used.size(); used.push_back(j); }
+    return local[j];
+  };
+  const uint64_t q0 = ps.set_begin[0], ninst64 = ps.set_begin[nsets] - q0;
+  if (ninst64 >= (1ull << 32) || ps.nshared >= (1ull << 32)) { if (why) *why = "text size"; return false; }
+  std::vector<uint32_t> inst_seq((size_t)ninst64), inst_set((size_t)ninst64), set_fidx(nsets, INV), fset, sh_seq;
+  uint64_t I = 0, S = 0, P = 0;  // positions (bases + 1) of the own instances, of the shared list, of the pool in use
+  for (uint32_t s = 0; s < nsets; s++) {
+    for (uint64_t q = ps.set_begin[s]; q < ps.set_begin[s + 1]; q++) {
+      inst_seq[(size_t)(q - q0)] = use(ps.set_seq[q]);
+      inst_set[(size_t)(q - q0)] = s;
+      I += seqs[ps.set_seq[q]].second + 1;
+    }
+    if (ps.flagged(s)) { set_fidx[s] = (uint32_t)fset.size(); fset.push_back(s); }
+  }
+  const uint32_t F = (uint32_t)fset.size();
+  if (F)
+    for (uint64_t x = 0; x < ps.nshared; x++) {
+      sh_seq.push_back(use(ps.shared_seq[x]));
+      S += seqs[ps.shared_seq[x]].second + 1;
+    }
+  const uint32_t nu = (uint32_t)used.size(), ninst = (uint32_t)ninst64, nsh = (uint32_t)sh_seq.size();
+  std::vector<uint32_t> seq_start(nu), seq_len1(nu);
+  for (uint32_t u = 0; u < nu && P < (1ull << 32); u++) {
+    const uint64_t len = std::min<uint64_t>(seqs[used[u]].second, 1ull << 32);  // (a longer one fails the guard below)
+    seq_start[u] = (uint32_t)P;
+    seq_len1[u] = (uint32_t)(len + 1);
+    P += len + 1;
+  }
+  // (instance positions + shared positions below 2^32, as the set build wants of its text; the pool in use is no larger)
+  if (I + S == 0 || I + S >= (1ull << 32) || P >= (1ull << 32)) { if (why) *why = "text size"; return false; }
+  size_t free_b = 0, total_b = 0;
+  G2S_GPU_TRY(hipMemGetInfo(&free_b, &total_b));
+  // (the pool's text and keys while the pairs are gathered; a gathered position at its sort's peak as in
+  // count_solid_sets_gpu_t; the merge is checked once the shared table's size is known)
+  if ((double)P * (double)(sizeof(KT) + 1) + (double)(I + S) * (double)(2 * sizeof(KT) + 56) > 0.5 * (double)free_b) {
+    if (why) *why = "text too large for the device";
+    return false;
+  }
+  std::vector<uint8_t> text((size_t)P);
+  for (uint32_t u = 0; u < nu; u++) {
+    memcpy(text.data() + seq_start[u], seqs[used[u]].first, (size_t)seqs[used[u]].second);
+    text[(size_t)seq_start[u] + seq_len1[u] - 1] = 'N';  // one separator after every sequence
+  }
+  const dim3 blk(256);
+  auto grid = [](uint64_t n) { return dim3((unsigned)((n + 255) / 256)); };
+  Dev d_keys, d_sid, d_hkeys;
+  {
+    Dev d_text, d_pkeys, d_sstart, d_slen1, d_iseq, d_iset, d_ilen, d_istart;
+    G2S_GPU_TRY(d_text.alloc((size_t)P));
+    G2S_GPU_TRY(d_pkeys.alloc((size_t)P * sizeof(KT)));
+    G2S_GPU_TRY(d_sstart.alloc((size_t)nu * 4));
+    G2S_GPU_TRY(d_slen1.alloc((size_t)nu * 4));
+    G2S_GPU_TRY(hipMemcpy(d_text.p, text.data(), (size_t)P, hipMemcpyHostToDevice));
+    G2S_GPU_TRY(hipMemcpy(d_sstart.p, seq_start.data(), (size_t)nu * 4, hipMemcpyHostToDevice));
+    G2S_GPU_TRY(hipMemcpy(d_slen1.p, seq_len1.data(), (size_t)nu * 4, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_extract<KT>, grid(P), blk, 0, 0, (const uint8_t*)d_text.p, P, k, (KT*)d_pkeys.p);
+    // the own lists' pairs, then the shared list's keys: instance -> pool position through the instances' start table
+    for (int pass = 0; pass < 2; pass++) {
+      const uint32_t ni = pass == 0 ? ninst : nsh;
+      const uint64_t np = pass == 0 ? I : S;
+      if (!np) continue;
+      G2S_GPU_TRY(d_iseq.alloc((size_t)ni * 4));
+      G2S_GPU_TRY(d_ilen.alloc((size_t)ni * 4));
+      G2S_GPU_TRY(d_istart.alloc((size_t)ni * 4));
+      G2S_GPU_TRY(hipMemcpy(d_iseq.p, pass == 0 ? inst_seq.data() : sh_seq.data(), (size_t)ni * 4, hipMemcpyHostToDevice));
+      if (pass == 0) {
+        G2S_GPU_TRY(d_iset.alloc((size_t)ni * 4));
+        G2S_GPU_TRY(hipMemcpy(d_iset.p, inst_set.data(), (size_t)ni * 4, hipMemcpyHostToDevice));
+        G2S_GPU_TRY(d_sid.alloc((size_t)np * 4));
+      }
+      Dev& d_dst = pass == 0 ? d_keys : d_hkeys;
+      G2S_GPU_TRY(d_dst.alloc((size_t)np * sizeof(KT)));
+      hipLaunchKernelGGL(k_inst_len, grid(ni), blk, 0, 0, (const uint32_t*)d_iseq.p, (const uint32_t*)d_slen1.p, ni, (uint32_t*)d_ilen.p);
+      G2S_SCAN(d_ilen.p, d_istart.p, ni);
+      hipLaunchKernelGGL(k_pool_pairs<KT>, grid(np), blk, 0, 0, (const KT*)d_pkeys.p, (const uint32_t*)d_istart.p,
+                         (const uint32_t*)d_iseq.p, pass == 0 ? (const uint32_t*)d_iset.p : (const uint32_t*)nullptr,
+                         (const uint32_t*)d_sstart.p, ni, np, (KT*)d_dst.p, pass == 0 ? (uint32_t*)d_sid.p : (uint32_t*)nullptr);
+      G2S_GPU_TRY(hipGetLastError());
+      for (Dev* d : {&d_iseq, &d_iset, &d_ilen, &d_istart}) { if (d->p) (void)hipFree(d->release()); }
+    }
+  }
+  info->own_positions = I;
+  info->shared_positions = S;
+  info->keys_sorted = 0;
+  // ---- the own lists: (set, k-mer) sort, runs, the run table and every set's first run
+  Dev d_rkey, d_rset, d_rcnt, d_rlo;
+  uint32_t nruns = 0;
+  if (I) {
+    Dev d_sk, d_ss, d_hidx, d_tidx;
+    if (!sort_keyed_gpu<KT>(d_keys, &d_sid, I, d_sk, &d_ss, why)) return false;
+    info->keys_sorted += I;
+    if (!runs_keyed_gpu<KT>((const KT*)d_sk.p, (const uint32_t*)d_ss.p, I, d_hidx, d_tidx, &nruns, why)) return false;
+    G2S_GPU_TRY(d_rkey.alloc((size_t)nruns * sizeof(KT)));
+    G2S_GPU_TRY(d_rset.alloc((size_t)nruns * 4));
+    G2S_GPU_TRY(d_rcnt.alloc((size_t)nruns * 4));
+    if (nruns) {
+      hipLaunchKernelGGL(k_run_table<KT>, grid(nruns), blk, 0, 0, (const KT*)d_sk.p, (const uint32_t*)d_ss.p, (const uint32_t*)d_hidx.p,
+                         (const uint32_t*)d_tidx.p, nruns, (KT*)d_rkey.p, (uint32_t*)d_rset.p, (uint32_t*)d_rcnt.p);
+    }
+    G2S_GPU_TRY(hipDeviceSynchronize());
+  } else {
+    G2S_GPU_TRY(d_rkey.alloc(0));
+    G2S_GPU_TRY(d_rset.alloc(0));
+    G2S_GPU_TRY(d_rcnt.alloc(0));
+  }
+  G2S_GPU_TRY(d_rlo.alloc(((size_t)nsets + 1) * 4));
+  hipLaunchKernelGGL(k_set_first, grid((uint64_t)nsets + 1), blk, 0, 0, (const uint32_t*)d_rset.p, nruns, nsets, (uint32_t*)d_rlo.p);
+  // ---- the shared list: sorted once as plain k-mers, run-length counted
+  Dev d_hkey, d_hcnt;
+  uint32_t U = 0;
+  if (S) {
+    Dev d_hs, d_flag, d_pos, d_hidx, d_misc;
+    if (!sort_keyed_gpu<KT>(d_hkeys, nullptr, S, d_hs, nullptr, why)) return false;
+    info->keys_sorted += S;
+    G2S_GPU_TRY(d_flag.alloc((size_t)S * 4));
+    G2S_GPU_TRY(d_pos.alloc((size_t)S * 4));
+    G2S_GPU_TRY(d_misc.alloc(16));
+    hipLaunchKernelGGL(k_heads<KT>, grid(S), blk, 0, 0, (const KT*)d_hs.p, S, (uint32_t*)d_flag.p);
+    G2S_SCAN(d_flag.p, d_pos.p, S);
+    uint32_t lastf = 0, lastp = 0;
+    G2S_GPU_TRY(hipMemcpy(&lastf, (const uint32_t*)d_flag.p + (S - 1), 4, hipMemcpyDeviceToHost));
+    G2S_GPU_TRY(hipMemcpy(&lastp, (const uint32_t*)d_pos.p + (S - 1), 4, hipMemcpyDeviceToHost));
+    U = lastp + lastf;
+    if (U) {
+      G2S_GPU_TRY(d_hidx.alloc((size_t)U * 4));
+      G2S_GPU_TRY(d_hkey.alloc((size_t)U * sizeof(KT)));
+      G2S_GPU_TRY(d_hcnt.alloc((size_t)U * 4));
+      G2S_GPU_TRY(hipMemset(d_misc.p, 0, 16));
+      hipLaunchKernelGGL(k_head_index<KT>, grid(S), blk, 0, 0, (const KT*)d_hs.p, (const uint32_t*)d_flag.p, (const uint32_t*)d_pos.p, S,
+                         (uint32_t*)d_hidx.p, (uint32_t*)d_misc.p);
+      uint32_t n_valid = 0;
+      G2S_GPU_TRY(hipMemcpy(&n_valid, d_misc.p, 4, hipMemcpyDeviceToHost));
+      hipLaunchKernelGGL(k_shared_table<KT>, grid(U), blk, 0, 0, (const KT*)d_hs.p, (const uint32_t*)d_hidx.p, U, n_valid,
+                         (KT*)d_hkey.p, (uint32_t*)d_hcnt.p);
+      G2S_GPU_TRY(hipDeviceSynchronize());
+    }
+  }
+  if (!U) {
+    G2S_GPU_TRY(d_hkey.alloc(0));
+    G2S_GPU_TRY(d_hcnt.alloc(0));
+  }
+  // ---- the merge: flags, scans, every set's count and first rank, then the writes — every buffer sized by its count
+  const uint64_t FU64 = (uint64_t)F * U;
+  if (FU64 + nruns >= (1ull << 31)) { if (why) *why = "size"; return false; }
+  const uint32_t FU = (uint32_t)FU64, so = (uint32_t)std::max(1, solid);
+  G2S_GPU_TRY(hipMemGetInfo(&free_b, &total_b));
+  // (two words an item for the flags and their scans, then at most one k-mer and its set id an item in the output)
+  if ((double)(FU64 + nruns) * (double)(sizeof(KT) + 12) > 0.5 * (double)free_b) {
+    if (why) *why = "merge too large for the device";
+    return false;
+  }
+  Dev d_sf, d_fset, d_kown, d_ksh, d_pown, d_psh, d_cnt, d_base, d_out, d_osid;
+  G2S_GPU_TRY(d_sf.alloc((size_t)nsets * 4));
+  G2S_GPU_TRY(d_fset.alloc((size_t)F * 4));
+  G2S_GPU_TRY(hipMemcpy(d_sf.p, set_fidx.data(), (size_t)nsets * 4, hipMemcpyHostToDevice));
+  if (F) G2S_GPU_TRY(hipMemcpy(d_fset.p, fset.data(), (size_t)F * 4, hipMemcpyHostToDevice));
+  G2S_GPU_TRY(d_kown.alloc(((size_t)nruns + 1) * 4));
+  G2S_GPU_TRY(d_pown.alloc(((size_t)nruns + 1) * 4));
+  G2S_GPU_TRY(d_ksh.alloc(((size_t)FU + 1) * 4));
+  G2S_GPU_TRY(d_psh.alloc(((size_t)FU + 1) * 4));
+  hipLaunchKernelGGL(k_pool_keep_own<KT>, grid((uint64_t)nruns + 1), blk, 0, 0, (const KT*)d_rkey.p, (const uint32_t*)d_rset.p,
+                     (const uint32_t*)d_rcnt.p, nruns, (const uint32_t*)d_sf.p, (const KT*)d_hkey.p, U, so, (uint32_t*)d_kown.p);
+  if (FU) {
+    hipLaunchKernelGGL(k_pool_keep_shared<KT>, grid((uint64_t)FU + 1), blk, 0, 0, (const KT*)d_hkey.p, (const uint32_t*)d_hcnt.p, U,
+                       (const uint32_t*)d_fset.p, FU, (const uint32_t*)d_rlo.p, (const KT*)d_rkey.p, (const uint32_t*)d_rcnt.p, so,
+                       (uint32_t*)d_ksh.p);
+  } else {
+    G2S_GPU_TRY(hipMemset(d_ksh.p, 0, 4));
+  }
+  G2S_SCAN(d_kown.p, d_pown.p, (size_t)nruns + 1);
+  G2S_SCAN(d_ksh.p, d_psh.p, (size_t)FU + 1);
+  G2S_GPU_TRY(d_cnt.alloc(((size_t)nsets + 1) * 4));
+  G2S_GPU_TRY(d_base.alloc(((size_t)nsets + 1) * 4));
+  hipLaunchKernelGGL(k_pool_set_count, grid((uint64_t)nsets + 1), blk, 0, 0, (const uint32_t*)d_rlo.p, (const uint32_t*)d_pown.p,
+                     (const uint32_t*)d_sf.p, (const uint32_t*)d_psh.p, U, nsets, (uint32_t*)d_cnt.p);
+  G2S_SCAN(d_cnt.p, d_base.p, (size_t)nsets + 1);
+  std::vector<uint32_t> lo32((size_t)nsets + 1, 0);
+  G2S_GPU_TRY(hipMemcpy(lo32.data(), d_base.p, lo32.size() * 4, hipMemcpyDeviceToHost));
+  const uint32_t n_solid = lo32[nsets];
+  std::vector<KT> host((size_t)n_solid);
+  std::vector<uint32_t> rs((size_t)n_solid);
+  if (n_solid) {
+    G2S_GPU_TRY(d_out.alloc((size_t)n_solid * sizeof(KT)));
+    G2S_GPU_TRY(d_osid.alloc((size_t)n_solid * 4));
+    if (nruns) {
+      hipLaunchKernelGGL(k_pool_write_own<KT>, grid(nruns), blk, 0, 0, (const KT*)d_rkey.p, (const uint32_t*)d_rset.p, nruns,
+                         (const uint32_t*)d_kown.p, (const uint32_t*)d_pown.p, (const uint32_t*)d_rlo.p, (const uint32_t*)d_sf.p,
+                         (const KT*)d_hkey.p, U, (const uint32_t*)d_psh.p, (const uint32_t*)d_base.p, (KT*)d_out.p, (uint32_t*)d_osid.p);
+    }
+    if (FU) {
+      hipLaunchKernelGGL(k_pool_write_shared<KT>, grid(FU), blk, 0, 0, (const KT*)d_hkey.p, U, (const uint32_t*)d_fset.p, FU,
+                         (const uint32_t*)d_ksh.p, (const uint32_t*)d_psh.p, (const uint32_t*)d_rlo.p, (const KT*)d_rkey.p,
+                         (const uint32_t*)d_pown.p, (const uint32_t*)d_base.p, (KT*)d_out.p, (uint32_t*)d_osid.p);
+    }
+    G2S_GPU_TRY(hipMemcpy(host.data(), d_out.p, (size_t)n_solid * sizeof(KT), hipMemcpyDeviceToHost));
+    G2S_GPU_TRY(hipMemcpy(rs.data(), d_osid.p, (size_t)n_solid * 4, hipMemcpyDeviceToHost));
+  }
+  G2S_GPU_TRY(hipGetLastError());
+  out.swap(host);
+  rank_set->swap(rs);
+  g.n = n_solid;
+  g.set_lo.assign(lo32.begin(), lo32.end());
+  return true;
+#undef G2S_SCAN
+#undef G2S_GPU_TRY
+}
+
+bool graph_build_pool_gpu(Graph& g, const PoolSets& ps, int solid, int device,
+                          const std::function<void(const std::vector<uint32_t>&, uint32_t)>& host_walk, PoolBuildInfo* info,
+                          std::string* why) {
+  if ((g.k % 2) == 0) { if (why) *why = "even k"; return false; }
+  std::vector<uint32_t> rank_set;
+  bool ok;
+  if (g.kmer_bytes == 32) ok = count_solid_pool_gpu_t<u256>(g, g.kmers256, &rank_set, ps, solid, device, info, why);
+  else if (g.kmer_bytes == 16) ok = count_solid_pool_gpu_t<u128>(g, g.kmers128, &rank_set, ps, solid, device, info, why);
+  else ok = count_solid_pool_gpu_t<uint64_t>(g, g.kmers64, &rank_set, ps, solid, device, info, why);
   if (!ok) return false;
   if (g.kmer_bytes == 32) ok = finish_gpu_t<u256>(g, g.kmers256, device, host_walk, why, &rank_set);
   else if (g.kmer_bytes == 16) ok = finish_gpu_t<u128>(g, g.kmers128, device, host_walk, why, &rank_set);

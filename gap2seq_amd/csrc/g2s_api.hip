@@ -131,6 +131,41 @@ extern "C" int g2s_graph_build_sets(const char* const* seqs, const uint64_t* len
   (*out)->g = g;
   return G2S_OK;
 }
+extern "C" int g2s_graph_build_pool(const char* const* seqs, const uint64_t* lens, uint64_t nseqs, const uint64_t* set_begin,
+                                    const uint32_t* set_seq, const uint32_t* shared_seq, uint64_t nshared, const uint8_t* set_shared,
+                                    uint32_t nsets, int k, int solid, int nthreads, g2s_graph** out) {
+  if ((!seqs && nseqs) || !set_begin || !out || nsets == 0 || nseqs >= (1ull << 32) || (!shared_seq && nshared))
+    return fail(G2S_ERR_ARG, "g2s_graph_build_pool: bad argument");
+  for (uint32_t s = 0; s < nsets; s++)
+    if (set_begin[s + 1] < set_begin[s]) return fail(G2S_ERR_ARG, "g2s_graph_build_pool: set_begin decreases");
+  if (!set_seq && set_begin[nsets] > set_begin[0]) return fail(G2S_ERR_ARG, "g2s_graph_build_pool: bad argument");
+  std::vector<std::pair<const char*, uint64_t>> v;
+  v.reserve((size_t)nseqs);
+  for (uint64_t i = 0; i < nseqs; i++) v.emplace_back(seqs[i], lens ? lens[i] : (uint64_t)strlen(seqs[i]));
+  PoolSets ps;
+  ps.seqs = &v;
+  ps.set_begin = set_begin;
+  ps.set_seq = set_seq;
+  ps.shared_seq = shared_seq;
+  ps.nshared = nshared;
+  ps.set_shared = set_shared;
+  ps.nsets = nsets;
+  std::string err;
+  Graph* g = graph_build_pool(ps, k, solid, nthreads, &err);
+  if (!g) return fail(G2S_ERR_ARG, err);
+  *out = new g2s_graph();
+  (*out)->g = g;
+  return G2S_OK;
+}
+// TEST HOOK (include/g2s_test.h)
+extern "C" int g2s_test_last_pool_build(uint64_t* own_positions, uint64_t* shared_positions, uint64_t* keys_sorted, int* on_device) {
+  const PoolBuildInfo info = last_pool_build();
+  if (own_positions) *own_positions = info.own_positions;
+  if (shared_positions) *shared_positions = info.shared_positions;
+  if (keys_sorted) *keys_sorted = info.keys_sorted;
+  if (on_device) *on_device = info.on_device;
+  return G2S_OK;
+}
 extern "C" uint32_t g2s_graph_num_sets(const g2s_graph* g) { return g ? g->g->num_sets() : 0; }
 extern "C" int g2s_graph_set_nodes(const g2s_graph* g, uint32_t set, uint64_t* first_kmer, uint64_t* n_kmers) {
   if (!g || set >= g->g->num_sets()) return fail(G2S_ERR_ARG, "g2s_graph_set_nodes: bad set");

@@ -2,9 +2,11 @@
 // /root/reference/src/Gap2Seq.py:133-218) in one process.  For every gap the wrapper extracts the reads of every library
 // that can belong to it (ReadFilter), adds every library's unmapped reads when too few bases came out, and runs a fresh
 // Gap2Seq-core over those reads alone.  Here every library's reads are extracted for all gaps at once, with its unmapped
-// reads, in two passes over its BAM (g2s_filter_reads_gaps: gap i's reads are g2s_filter_reads' for gap i), every gap's
-// reads become one read set of a set graph (g2s_graph_build_sets) and the gaps are filled as one list (g2s_fill_sets):
-// every gap's fill is what its own Gap2Seq-core -reads S(i) -left L -right R -length G run writes.
+// reads, in two passes over its BAM, as a pool that holds every read once (g2s_filter_reads_gaps_pool: gap i's reads are
+// g2s_filter_reads' for gap i); every gap's reads become one read set of a set graph built from the pools
+// (g2s_graph_build_pool: a gap's own reads as indices, the unmapped reads as the list every gap under the threshold
+// shares, encoded and sorted once a chunk) and the gaps are filled as one list (g2s_fill_sets): every gap's fill is
+// what its own Gap2Seq-core -reads S(i) -left L -right R -length G run writes.  No FASTA text is formed.
 //
 //   Gap2Seq-libraries -libraries libs.txt -gaps gaps.fa -bed gaps.bed -filled out.fa
 //                     [-k 31] [-fuz 10] [-solid 2] [-dist-error 500] [-max-mem 20] [-randseed 0]
@@ -31,26 +33,12 @@ struct Library {
   std::string bam;
   int mean = 0, sd = 0;
   double threshold = 0;
-  std::string unmapped;  // FASTA text of the library's unmapped reads ("" when none: no file, Gap2Seq.py:164-167)
 };
 
 struct GapRec {
   std::string comment, left, right, scaffold;
   int gap_length = 0, flank_length = 0, breakpoint = 0;
 };
-
-// `grep '^[^>;]' file | wc -c` (Gap2Seq.py:156-159): bytes of the lines that do not start with '>' or ';', newlines included
-size_t sequence_bytes(const std::string& fasta) {
-  size_t n = 0, p = 0;
-  while (p < fasta.size()) {
-    size_t e = fasta.find('\n', p);
-    const bool nl = e != std::string::npos;
-    if (!nl) e = fasta.size();
-    if (e > p && fasta[p] != '>' && fasta[p] != ';') n += (e - p) + (nl ? 1 : 0);
-    p = e + 1;
-  }
-  return n;
-}
 
 // parse_gap (Gap2Seq.py:246-262): left up to the first N/n, right after the last one
 GapRec parse_gap(const std::string& record, const std::string& bed_line) {
@@ -92,9 +80,10 @@ std::vector<std::string> gap_records(const std::string& text) {
   return out;
 }
 
-// the reads of every gap from one library, and the library's unmapped reads, in one call (two passes over the BAM).
-// A library whose BAM cannot be read gives no reads (as the wrapper's ReadFilter run that fails, Gap2Seq.py:151-153).
-std::vector<std::string> filter_library(Library& lib, const std::vector<GapRec>& gaps, int device) {
+// the reads of every gap from one library, and the library's unmapped reads, in one call (two passes over the BAM), as
+// a pool: every read held once however many gaps select it, every gap a list of indices.  A library whose BAM cannot
+// be read gives no reads (as the wrapper's ReadFilter run that fails, Gap2Seq.py:151-153).
+g2s_read_pool* filter_library(const Library& lib, const std::vector<GapRec>& gaps, int device) {
   g2s_filter_opts o;
   memset(&o, 0, sizeof o);
   o.mean_insert = lib.mean;
@@ -106,28 +95,19 @@ std::vector<std::string> filter_library(Library& lib, const std::vector<GapRec>&
     gv[i].gap_length = gaps[i].gap_length;
     gv[i].flank_length = gaps[i].flank_length;
   }
-  std::vector<char*> fasta(std::max<size_t>(1, gaps.size()), nullptr);
-  char* unmapped = nullptr;
+  g2s_read_pool* pool = nullptr;
   int64_t total = 0;
-  int rc = g2s_filter_reads_gaps(lib.bam.c_str(), &o, gv.data(), gv.size(), device, fasta.data(), nullptr, nullptr, nullptr,
-                                 &total, &unmapped, nullptr, nullptr);
+  // (with names: the chunk rule below counts the bytes of the FASTA text the reads would make)
+  int rc = g2s_filter_reads_gaps_pool(lib.bam.c_str(), &o, gv.data(), gv.size(), device, 1, 1, &pool, &total, nullptr);
   if (rc != G2S_OK && rc != G2S_ERR_IO && device >= 0) {  // (the device could not take it: the same joins on the host)
     std::cerr << "Gap2Seq-libraries: " << lib.bam << ": " << g2s_filter_last_error() << "; filtering on the host" << std::endl;
-    rc = g2s_filter_reads_gaps(lib.bam.c_str(), &o, gv.data(), gv.size(), -1, fasta.data(), nullptr, nullptr, nullptr,
-                               &total, &unmapped, nullptr, nullptr);
+    rc = g2s_filter_reads_gaps_pool(lib.bam.c_str(), &o, gv.data(), gv.size(), -1, 1, 1, &pool, &total, nullptr);
   }
-  std::vector<std::string> out(gaps.size());
   if (rc != G2S_OK) {
     std::cerr << "Gap2Seq-libraries: " << lib.bam << ": " << g2s_filter_last_error() << std::endl;
-    return out;
+    return nullptr;
   }
-  for (size_t i = 0; i < gaps.size(); i++) {
-    out[i] = fasta[i];
-    g2s_free(fasta[i]);
-  }
-  lib.unmapped = unmapped;
-  g2s_free(unmapped);
-  return out;
+  return pool;
 }
 
 }  // namespace
@@ -198,22 +178,66 @@ int main(int argc, char** argv) {
   const size_t ngaps = records.size();
   std::vector<GapRec> gaps(ngaps);
   for (size_t i = 0; i < ngaps; i++) gaps[i] = parse_gap(records[i], i < bed_lines.size() ? bed_lines[i] : std::string());
-  std::vector<std::string> reads(ngaps);  // FASTA text of every gap's read set
-  std::vector<size_t> filtered_length(ngaps, 0);
+  // ---- every library's pool; the reads of all libraries as one array of (pointer, length), every gap's own list
+  // (its reads of library 0, 1, ... in order) as indices into it, and the shared list: every library's unmapped reads
+  // in library order.  What is held is the pools and the index lists: nothing grows with gaps x unmapped reads.
+  std::vector<g2s_read_pool*> pools;
+  std::vector<const char*> seq_ptr;
+  std::vector<uint64_t> seq_len, seq_fasta;  // (bytes of the read's FASTA record: '>' name '\n' bases '\n')
+  std::vector<uint32_t> lib_first;
   double threshold = 0;
-  for (Library& L : libs) {  // (Gap2Seq.py:143-159; every library's unmapped reads, Gap2Seq.py:64-72, :437-439)
-    const std::vector<std::string> f = filter_library(L, gaps, filter_device_set ? filter_device : device);
-    for (size_t i = 0; i < ngaps; i++) {
-      filtered_length[i] += sequence_bytes(f[i]);
-      reads[i] += f[i];
+  for (const Library& L : libs) {  // (Gap2Seq.py:143-159; every library's unmapped reads, Gap2Seq.py:64-72, :437-439)
+    g2s_read_pool* P = filter_library(L, gaps, filter_device_set ? filter_device : device);
+    pools.push_back(P);
+    lib_first.push_back((uint32_t)seq_ptr.size());
+    if (P) {
+      if (seq_ptr.size() + P->n_reads >= ((uint64_t)1 << 32)) { std::cerr << "Gap2Seq-libraries: 2^32 reads or more selected" << std::endl; return EXIT_FAILURE; }
+      for (uint64_t r = 0; r < P->n_reads; r++) {
+        seq_ptr.push_back(P->bases + P->base_off[r]);
+        seq_len.push_back(P->base_off[r + 1] - P->base_off[r]);
+        seq_fasta.push_back(seq_len.back() + (P->name_off[r + 1] - P->name_off[r]) + 3);
+      }
     }
     threshold += L.threshold;
   }
+  std::vector<uint64_t> own_begin(ngaps + 1, 0);
+  for (size_t i = 0; i < ngaps; i++) {
+    own_begin[i + 1] = own_begin[i];
+    for (const g2s_read_pool* P : pools)
+      if (P) own_begin[i + 1] += P->gap_begin[i + 1] - P->gap_begin[i];
+  }
+  std::vector<uint32_t> own_seq((size_t)own_begin[ngaps]), shared_seq;
+  std::vector<size_t> filtered_length(ngaps, 0), text_bytes(ngaps, 0);  // (text_bytes: of the gap's reads as FASTA text)
+  size_t shared_bytes = 0;
+  for (size_t l = 0; l < pools.size(); l++) {
+    if (!pools[l]) continue;
+    for (uint64_t q = 0; q < pools[l]->n_unmapped; q++) {
+      shared_seq.push_back(lib_first[l] + pools[l]->unmapped_read[q]);
+      shared_bytes += (size_t)seq_fasta[shared_seq.back()];
+    }
+  }
+  for (size_t i = 0; i < ngaps; i++) {
+    size_t o = (size_t)own_begin[i];
+    for (size_t l = 0; l < pools.size(); l++) {
+      if (!pools[l]) continue;
+      for (uint64_t q = pools[l]->gap_begin[i]; q < pools[l]->gap_begin[i + 1]; q++) {
+        const uint32_t j = lib_first[l] + pools[l]->gap_read[q];
+        own_seq[o++] = j;
+        // `grep '^[^>;]' file | wc -c` (Gap2Seq.py:156-159) on the FASTA text of these reads: every sequence line with its
+        // newline; a read without bases leaves an empty line, which the pattern does not match
+        if (seq_len[j]) filtered_length[i] += (size_t)seq_len[j] + 1;
+        text_bytes[i] += (size_t)seq_fasta[j];
+      }
+    }
+  }
+  std::vector<uint8_t> takes_unmapped(ngaps, 0);
   for (size_t i = 0; i < ngaps; i++) {
     const GapRec& g = gaps[i];
     const double ratio = g.gap_length > 0 ? (double)filtered_length[i] / (double)g.gap_length : INFINITY;
-    if (ratio < threshold)  // (Gap2Seq.py:161-167)
-      for (const Library& L : libs) reads[i] += L.unmapped;
+    if (ratio < threshold) {  // (Gap2Seq.py:161-167)
+      takes_unmapped[i] = 1;
+      text_bytes[i] += shared_bytes;
+    }
   }
   // ---- fill: chunks of gaps whose read text fits a budget, one set graph and one list each
   g2s_params p;
@@ -226,23 +250,32 @@ int main(int argc, char** argv) {
   p.randseed = randseed;
   std::vector<std::string> fills(ngaps);
   const size_t budget = (size_t)256 << 20;
+  std::vector<uint32_t> chunk_of(seq_ptr.size(), UINT32_MAX), touched;  // a read's index in the chunk being built
   size_t lo = 0;
   while (lo < ngaps) {
     size_t hi = lo, bytes = 0;
-    while (hi < ngaps && (hi == lo || bytes + reads[hi].size() <= budget)) bytes += reads[hi++].size();
-    std::vector<g2s::FastxRecord> recs;
-    std::vector<uint32_t> rec_set;
+    while (hi < ngaps && (hi == lo || bytes + text_bytes[hi] <= budget)) bytes += text_bytes[hi++];
+    // the chunk's sets over the reads the chunk names: indices rebased to the chunk, no text moves
+    std::vector<const char*> sp;
+    std::vector<uint64_t> sl, set_begin(1, 0);
+    std::vector<uint32_t> set_seq, chunk_shared;
+    auto local = [&](uint32_t j) -> uint32_t {
+      if (chunk_of[j] == UINT32_MAX) { chunk_of[j] = (uint32_t)sp.size(); sp.push_back(seq_ptr[j]); sl.push_back(seq_len[j]); touched.push_back(j); }
+      return chunk_of[j];
+    };
+    bool any_shared = false;
     for (size_t i = lo; i < hi; i++) {
-      const size_t before = recs.size();
-      g2s::parse_fastx(reads[i], &recs);
-      rec_set.resize(recs.size(), (uint32_t)(i - lo));
-      (void)before;
+      for (uint64_t q = own_begin[i]; q < own_begin[i + 1]; q++) set_seq.push_back(local(own_seq[(size_t)q]));
+      set_begin.push_back(set_seq.size());
+      any_shared = any_shared || takes_unmapped[i];
     }
-    std::vector<const char*> sp(recs.size());
-    std::vector<uint64_t> sl(recs.size());
-    for (size_t j = 0; j < recs.size(); j++) { sp[j] = recs[j].seq.data(); sl[j] = recs[j].seq.size(); }
+    if (any_shared)
+      for (uint32_t j : shared_seq) chunk_shared.push_back(local(j));
     g2s_graph* graph = nullptr;
-    int rc = g2s_graph_build_sets(sp.data(), sl.data(), rec_set.data(), (int)recs.size(), (uint32_t)(hi - lo), k, solid, 0, &graph);
+    int rc = g2s_graph_build_pool(sp.data(), sl.data(), sp.size(), set_begin.data(), set_seq.data(), chunk_shared.data(),
+                                  chunk_shared.size(), takes_unmapped.data() + lo, (uint32_t)(hi - lo), k, solid, 0, &graph);
+    for (uint32_t j : touched) chunk_of[j] = UINT32_MAX;
+    touched.clear();
     g2s_session* s = nullptr;
     if (rc == G2S_OK) rc = g2s_session_create(graph, device, &p, &s);
     if (rc != G2S_OK) {
@@ -303,6 +336,7 @@ int main(int argc, char** argv) {
   if (!f) { std::cerr << "Gap2Seq-libraries: cannot write " << filled_path << std::endl; return EXIT_FAILURE; }
   fwrite(out.data(), 1, out.size(), f);
   fclose(f);
+  for (g2s_read_pool* P : pools) g2s_read_pool_free(P);
   std::cout << "Filled " << successful << " out of " << ngaps << " gaps" << std::endl;  // (Gap2Seq.py:513)
   return EXIT_SUCCESS;
 }

@@ -164,9 +164,24 @@ char* dup_text(const char* p, size_t n) {
   return q;
 }
 
+// a malloc'ed copy of a vector's elements (one element at least, so that an empty array is not NULL)
+template <class T>
+T* dup_array(const T* p, size_t n) {
+  T* q = (T*)malloc(std::max<size_t>(n, 1) * sizeof(T));
+  if (q && n) memcpy(q, p, n * sizeof(T));
+  return q;
+}
+
+// what g2s_filter_reads_gaps_pool asks of run_filter_gaps in place of the per-gap texts
+struct PoolRequest {
+  bool names, unmapped;
+  g2s_read_pool** out;
+};
+
 int run_filter_gaps(BamFile& bam, const g2s_filter_opts* lib, const g2s_filter_gap* gaps, size_t n, int device,
                     char** fasta_out, char** log_out, char** warn_out, int64_t* extracted_out, int64_t* total_out,
-                    char** unmapped_out, int64_t* unmapped_extracted, g2s_filter_stats* stats) {
+                    char** unmapped_out, int64_t* unmapped_extracted, g2s_filter_stats* stats,
+                    const PoolRequest* pool = nullptr) {
   std::string err;
   g2s_filter_stats st;
   memset(&st, 0, sizeof st);
@@ -234,15 +249,31 @@ int run_filter_gaps(BamFile& bam, const g2s_filter_opts* lib, const g2s_filter_g
   std::vector<uint8_t> sel(total, 0);
   for (uint64_t x : J.list1) sel[(uint32_t)x] = 1;
   for (uint64_t x : J.list2) sel[(uint32_t)x] = 1;
-  std::vector<uint64_t> toff(total, 0);
-  std::vector<uint32_t> tlen(total, 0);
+  std::vector<uint64_t> toff(pool ? 0 : total, 0);
+  std::vector<uint32_t> tlen(pool ? 0 : total, 0);
   std::string text, unmapped;
   int64_t n_unmapped = 0;
-  const bool want_unmapped = unmapped_out != nullptr;
+  const bool want_unmapped = pool ? pool->unmapped : unmapped_out != nullptr;
+  // (the pool: every held record once — its bases, its name when asked for, and its index by row)
+  std::string pbases, pnames;
+  std::vector<uint64_t> pboff(1, 0), pnoff(1, 0);
+  std::vector<uint32_t> pidx(pool ? total : 0, 0), punmapped;
   size_t row = 0;
   st.file_passes++;
   if (!bam.for_each([&](const BamRec& r) {
         if (row >= total) return false;  // (the file changed under us: guarded below)
+        if (pool) {
+          const bool un = want_unmapped && (r.flag & BAM_UNMAPPED);
+          if (sel[row] || un) {
+            pidx[row] = (uint32_t)(pboff.size() - 1);
+            if (un) punmapped.push_back(pidx[row]);
+            append_bases(r, &pbases);
+            pboff.push_back(pbases.size());
+            if (pool->names) { pnames += own_name(r); pnoff.push_back(pnames.size()); }
+          }
+          row++;
+          return true;
+        }
         if (sel[row]) {
           toff[row] = text.size();
           append_fasta(r, &text);
@@ -261,6 +292,41 @@ int run_filter_gaps(BamFile& bam, const g2s_filter_opts* lib, const g2s_filter_g
   for (uint64_t x : J.list1) at1[(size_t)(x >> 32) + 1]++;
   for (uint64_t x : J.list2) at2[(size_t)(x >> 32) + 1]++;
   for (size_t g = 0; g < n; g++) { at1[g + 1] += at1[g]; at2[g + 1] += at2[g]; }
+  if (pool) {  // ... as indices into the pool, in the same order
+    std::vector<uint64_t> gbeg(n + 1, 0);
+    std::vector<uint32_t> gread(J.list1.size() + J.list2.size());
+    for (size_t g = 0; g < n; g++) {
+      size_t o = (size_t)gbeg[g];
+      for (size_t q = at1[g]; q < at1[g + 1]; q++) gread[o++] = pidx[(uint32_t)J.list1[q]];
+      for (size_t q = at2[g]; q < at2[g + 1]; q++) gread[o++] = pidx[(uint32_t)J.list2[q]];
+      gbeg[g + 1] = o;
+    }
+    g2s_read_pool* P = (g2s_read_pool*)calloc(1, sizeof(g2s_read_pool));
+    if (P) {
+      P->n_reads = pboff.size() - 1;
+      P->bases = dup_array(pbases.data(), pbases.size());
+      P->base_off = dup_array(pboff.data(), pboff.size());
+      if (pool->names) {
+        P->names = dup_array(pnames.data(), pnames.size());
+        P->name_off = dup_array(pnoff.data(), pnoff.size());
+      }
+      P->gap_begin = dup_array(gbeg.data(), gbeg.size());
+      P->gap_read = dup_array(gread.data(), gread.size());
+      P->n_unmapped = punmapped.size();
+      P->unmapped_read = dup_array(punmapped.data(), punmapped.size());
+    }
+    if (!P || !P->bases || !P->base_off || (pool->names && (!P->names || !P->name_off)) || !P->gap_begin || !P->gap_read ||
+        !P->unmapped_read) {
+      g2s_read_pool_free(P);
+      set_filter_error("out of memory");
+      return G2S_ERR_NOMEM;
+    }
+    *pool->out = P;
+    if (total_out) *total_out = (int64_t)total;
+    st.ms_text = ms_since(t0);
+    if (stats) *stats = st;
+    return G2S_OK;
+  }
   std::vector<char*> fa(n, nullptr), lg(n, nullptr), wn(n, nullptr);
   std::atomic<bool> oom{false};
   parallel_items(n, threads, [&](size_t g) {
@@ -337,6 +403,39 @@ int g2s_filter_reads_gaps_mem(const void* bam_bytes, size_t nbytes, const g2s_fi
   if (!bam.open_mem(bam_bytes, nbytes, &err)) { g2s::set_filter_error(err); return G2S_ERR_IO; }
   return g2s::run_filter_gaps(bam, lib, gaps, n, device, fasta_out, log_out, warn_out, extracted, total, unmapped_out,
                               unmapped_extracted, stats);
+}
+
+int g2s_filter_reads_gaps_pool(const char* bam_path, const g2s_filter_opts* lib, const g2s_filter_gap* gaps, size_t n, int device,
+                               int want_names, int want_unmapped, g2s_read_pool** out, int64_t* total, g2s_filter_stats* stats) {
+  if (!bam_path || !out || !g2s::gap_args_ok(lib, gaps, n)) return G2S_ERR_ARG;
+  g2s::BamFile bam;
+  std::string err;
+  if (!bam.open_path(bam_path, &err)) { g2s::set_filter_error(err); return G2S_ERR_IO; }
+  const g2s::PoolRequest req{want_names != 0, want_unmapped != 0, out};
+  return g2s::run_filter_gaps(bam, lib, gaps, n, device, nullptr, nullptr, nullptr, nullptr, total, nullptr, nullptr, stats, &req);
+}
+
+int g2s_filter_reads_gaps_pool_mem(const void* bam_bytes, size_t nbytes, const g2s_filter_opts* lib, const g2s_filter_gap* gaps,
+                                   size_t n, int device, int want_names, int want_unmapped, g2s_read_pool** out, int64_t* total,
+                                   g2s_filter_stats* stats) {
+  if (!bam_bytes || !out || !g2s::gap_args_ok(lib, gaps, n)) return G2S_ERR_ARG;
+  g2s::BamFile bam;
+  std::string err;
+  if (!bam.open_mem(bam_bytes, nbytes, &err)) { g2s::set_filter_error(err); return G2S_ERR_IO; }
+  const g2s::PoolRequest req{want_names != 0, want_unmapped != 0, out};
+  return g2s::run_filter_gaps(bam, lib, gaps, n, device, nullptr, nullptr, nullptr, nullptr, total, nullptr, nullptr, stats, &req);
+}
+
+void g2s_read_pool_free(g2s_read_pool* p) {
+  if (!p) return;
+  free(p->bases);
+  free(p->base_off);
+  free(p->names);
+  free(p->name_off);
+  free(p->gap_begin);
+  free(p->gap_read);
+  free(p->unmapped_read);
+  free(p);
 }
 
 // TEST HOOK (include/g2s_test.h): one of the joins on the caller's rows and windows.  The path is the caller's

@@ -31,12 +31,9 @@ inline std::string mate_name(const BamRec& r) {
 
 // ReadFilter.cpp:105-161: the read as sequenced (reverse strand alignments are complemented back); every code
 // other than A, C, G, T becomes N
-inline void append_fasta(const BamRec& r, std::string* out) {
+inline void append_bases(const BamRec& r, std::string* out) {
   static const char fwd[16] = {'N', 'A', 'C', 'N', 'G', 'N', 'N', 'N', 'T', 'N', 'N', 'N', 'N', 'N', 'N', 'N'};
   static const char rev[16] = {'N', 'T', 'G', 'N', 'C', 'N', 'N', 'N', 'A', 'N', 'N', 'N', 'N', 'N', 'N', 'N'};
-  out->push_back('>');
-  out->append(own_name(r));
-  out->push_back('\n');
   const size_t at = out->size();
   out->resize(at + (size_t)r.l_seq);
   char* d = &(*out)[at];
@@ -44,6 +41,12 @@ inline void append_fasta(const BamRec& r, std::string* out) {
     for (int32_t i = 0; i < r.l_seq; i++) d[i] = fwd[r.base4(i)];
   else
     for (int32_t i = 0; i < r.l_seq; i++) d[i] = rev[r.base4(r.l_seq - 1 - i)];
+}
+inline void append_fasta(const BamRec& r, std::string* out) {
+  out->push_back('>');
+  out->append(own_name(r));
+  out->push_back('\n');
+  append_bases(r, out);
   out->push_back('\n');
 }
 

@@ -95,6 +95,12 @@ class g2s_filter_stats(C.Structure):
                 ("ms_join", C.c_double), ("ms_text", C.c_double)]
 
 
+class g2s_read_pool(C.Structure):
+    _fields_ = [("n_reads", C.c_uint64), ("bases", C.POINTER(C.c_char)), ("base_off", C.POINTER(C.c_uint64)),
+                ("names", C.POINTER(C.c_char)), ("name_off", C.POINTER(C.c_uint64)), ("gap_begin", C.POINTER(C.c_uint64)),
+                ("gap_read", C.POINTER(C.c_uint32)), ("n_unmapped", C.c_uint64), ("unmapped_read", C.POINTER(C.c_uint32))]
+
+
 # every symbol include/g2s.h declares: name -> (restype, argtypes)
 _VP = C.c_void_p
 TEXT_FN = C.CFUNCTYPE(None, C.POINTER(C.c_char), C.c_size_t, C.c_void_p)  # g2s_text_fn
@@ -115,6 +121,11 @@ _SIGS = {
                                        C.c_int, C.POINTER(_VP)]),
     "g2s_graph_build_sets": (C.c_int, [C.POINTER(C.c_char_p), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.c_int,
                                        C.c_uint32, C.c_int, C.c_int, C.c_int, C.POINTER(_VP)]),
+    "g2s_graph_build_pool": (C.c_int, [C.POINTER(C.c_char_p), C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(C.c_uint64),
+                                       C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_uint64, C.POINTER(C.c_uint8),
+                                       C.c_uint32, C.c_int, C.c_int, C.c_int, C.POINTER(_VP)]),
+    "g2s_test_last_pool_build": (C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                           C.POINTER(C.c_int)]),
     "g2s_graph_num_sets": (C.c_uint32, [_VP]),
     "g2s_graph_set_nodes": (C.c_int, [_VP, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "g2s_graph_set_node": (C.c_uint32, [_VP, C.c_uint32, C.c_char_p]),
@@ -177,6 +188,13 @@ _SIGS = {
                                             C.c_size_t, C.c_int, C.POINTER(_VP), C.POINTER(_VP), C.POINTER(_VP),
                                             C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(_VP),
                                             C.POINTER(C.c_int64), C.POINTER(g2s_filter_stats)]),
+    "g2s_filter_reads_gaps_pool": (C.c_int, [C.c_char_p, C.POINTER(g2s_filter_opts), C.POINTER(g2s_filter_gap), C.c_size_t,
+                                             C.c_int, C.c_int, C.c_int, C.POINTER(C.POINTER(g2s_read_pool)),
+                                             C.POINTER(C.c_int64), C.POINTER(g2s_filter_stats)]),
+    "g2s_filter_reads_gaps_pool_mem": (C.c_int, [C.c_char_p, C.c_size_t, C.POINTER(g2s_filter_opts), C.POINTER(g2s_filter_gap),
+                                                 C.c_size_t, C.c_int, C.c_int, C.c_int, C.POINTER(C.POINTER(g2s_read_pool)),
+                                                 C.POINTER(C.c_int64), C.POINTER(g2s_filter_stats)]),
+    "g2s_read_pool_free": (None, [C.POINTER(g2s_read_pool)]),
     "g2s_filter_last_error": (C.c_char_p, []),
     "g2s_device_count": (C.c_int, []),
     "g2s_synth_genome": (C.c_int, [C.c_uint64, C.c_uint32, C.c_uint64, C.POINTER(_VP)]),
@@ -319,12 +337,7 @@ def filter_reads_gaps(bam, mean, std_dev, gaps, device=0, threads=0, unmapped=Fa
     Returns (per-gap list of (fasta, stdout_text, stderr_text, extracted, total) as filter_reads returns them, stats
     dict); with unmapped=True a third item, filter_reads(..., unmapped_only=True)'s tuple, from the same passes."""
     lib = load_library()
-    arr = (g2s_filter_gap * max(1, len(gaps)))()
-    for i, g in enumerate(gaps):
-        if isinstance(g, dict):
-            g = (g["scaffold"], g["breakpoint"], g.get("gap_length", -1), g.get("flank_length", -1))
-        g = tuple(g) + (-1,) * (4 - len(g))
-        arr[i] = g2s_filter_gap(g[0].encode(), g[1], g[2], g[3])
+    arr = _filter_gap_array(gaps)
     n = len(gaps)
     o = g2s_filter_opts(mean, std_dev, 0, -1, -1, 0, threads, b"")
     fa, lg, wn = (_VP * max(1, n))(), (_VP * max(1, n))(), (_VP * max(1, n))()
@@ -353,6 +366,109 @@ def filter_reads_gaps(bam, mean, std_dev, gaps, device=0, threads=0, unmapped=Fa
     un_fa = take(un)
     un_log = "Extracted %d out of %d reads\n" % (un_ext.value, tot.value)
     return out, stats, (un_fa, un_log, "", un_ext.value, tot.value)
+
+
+def _filter_gap_array(gaps):
+    arr = (g2s_filter_gap * max(1, len(gaps)))()
+    for i, g in enumerate(gaps):
+        if isinstance(g, dict):
+            g = (g["scaffold"], g["breakpoint"], g.get("gap_length", -1), g.get("flank_length", -1))
+        g = tuple(g) + (-1,) * (4 - len(g))
+        arr[i] = g2s_filter_gap(g[0].encode(), g[1], g[2], g[3])
+    return arr
+
+
+class ReadPool:
+    """g2s_read_pool: every read some gap selected (or that is unmapped) held once, and every gap a list of indices
+    into the pool.  seqs / names: the reads' bases / "name/1" or "name/2" as bytes (names None unless asked for);
+    gap_reads(i): gap i's read indices in the order of filter_reads_gaps' FASTA; unmapped: the unmapped reads' indices;
+    total: records in the file; stats: as filter_reads_gaps returns them."""
+
+    def __init__(self, ptr, n_gaps, total, stats):
+        self.p, self.n_gaps, self.total, self.stats = ptr, n_gaps, total, stats
+        self._seqs = self._names = None
+
+    def _take(self, text, off):
+        p = self.p.contents
+        n = p.n_reads
+        raw = C.string_at(text, off[n]) if off[n] else b""
+        return [raw[off[i]:off[i + 1]] for i in range(n)]
+
+    @property
+    def n_reads(self):
+        return self.p.contents.n_reads
+
+    @property
+    def seqs(self):
+        if self._seqs is None:
+            self._seqs = self._take(self.p.contents.bases, self.p.contents.base_off)
+        return self._seqs
+
+    @property
+    def names(self):
+        if self._names is None and self.p.contents.names:
+            self._names = self._take(self.p.contents.names, self.p.contents.name_off)
+        return self._names
+
+    def gap_reads(self, i):
+        if not 0 <= i < self.n_gaps:
+            raise IndexError(i)
+        p = self.p.contents
+        return p.gap_read[p.gap_begin[i]:p.gap_begin[i + 1]]
+
+    @property
+    def unmapped(self):
+        p = self.p.contents
+        return p.unmapped_read[0:p.n_unmapped]
+
+    def _fasta(self, reads):  # (read names are bytes of the BAM file: not necessarily ASCII)
+        if self.names is None:
+            raise ValueError("the pool was made without names")
+        return b"".join(b">" + self.names[r] + b"\n" + self.seqs[r] + b"\n" for r in reads).decode("latin-1")
+
+    def fasta(self, i):
+        """gap i's FASTA text: filter_reads_gaps' for that gap, byte for byte"""
+        return self._fasta(self.gap_reads(i))
+
+    def unmapped_fasta(self):
+        return self._fasta(self.unmapped)
+
+    @property
+    def nbytes(self):
+        """bytes of the arrays the pool holds"""
+        p = self.p.contents
+        n = p.n_reads
+        b = p.base_off[n] + 8 * (n + 1) + 8 * (self.n_gaps + 1) + 4 * p.gap_begin[self.n_gaps] + 4 * p.n_unmapped
+        if p.names:
+            b += p.name_off[n] + 8 * (n + 1)
+        return b
+
+    def free(self):
+        if self.p:
+            load_library().g2s_read_pool_free(self.p)
+            self.p = None
+
+
+def filter_reads_gaps_pool(bam, mean, std_dev, gaps, device=0, threads=0, names=True, unmapped=True):
+    """g2s_filter_reads_gaps_pool / _mem: filter_reads_gaps with the reads handed over as a ReadPool (every read held
+    once however many gaps select it) instead of per-gap FASTA text.  `bam`, `gaps`, `device` as there."""
+    lib = load_library()
+    arr = _filter_gap_array(gaps)
+    n = len(gaps)
+    o = g2s_filter_opts(mean, std_dev, 0, -1, -1, 0, threads, b"")
+    out = C.POINTER(g2s_read_pool)()
+    tot = C.c_int64(0)
+    st = g2s_filter_stats()
+    tail = [C.byref(o), arr, n, device, int(bool(names)), int(bool(unmapped)), C.byref(out), C.byref(tot), C.byref(st)]
+    if isinstance(bam, (bytes, bytearray)):
+        rc = lib.g2s_filter_reads_gaps_pool_mem(bytes(bam), len(bam), *tail)
+    else:
+        rc = lib.g2s_filter_reads_gaps_pool(str(bam).encode(), *tail)
+    if rc != G2S_OK:
+        raise G2SError(rc, (lib.g2s_filter_last_error() or b"").decode("utf-8", "replace"))
+    stats = dict(file_passes=st.file_passes, on_device=st.on_device, ms_inflate=st.ms_inflate, ms_join=st.ms_join,
+                 ms_text=st.ms_text)
+    return ReadPool(out, n, tot.value, stats)
 
 
 class Graph:
@@ -386,6 +502,34 @@ class Graph:
         sets_of = (C.c_uint32 * max(1, n))(*owner)
         h = _VP()
         _check(lib.g2s_graph_build_sets(arr, lens, sets_of, n, len(sets), k, solid, nthreads, C.byref(h)))
+        return cls(h)
+
+    @classmethod
+    def from_pool(cls, seqs, set_lists, k, solid, shared=None, set_shared=None, nthreads=0):
+        """g2s_graph_build_pool: the set graph of from_sets for sets given as lists of indices into one pool of
+        sequences (`set_lists`: per set, indices into `seqs`; a sequence may be in many sets, and twice in one).
+        `shared`: indices of a list that every set with a true `set_shared` entry holds behind its own."""
+        lib = load_library()
+        enc = [s.encode("ascii") if isinstance(s, str) else s for s in seqs]
+        n = len(enc)
+        arr = (C.c_char_p * max(1, n))(*enc)
+        lens = (C.c_uint64 * max(1, n))(*[len(e) for e in enc])
+        begin, flat = [0], []
+        for lst in set_lists:
+            flat.extend(lst)
+            begin.append(len(flat))
+        set_begin = (C.c_uint64 * len(begin))(*begin)
+        set_seq = (C.c_uint32 * max(1, len(flat)))(*flat)
+        shared = list(shared) if shared is not None else []
+        sh = (C.c_uint32 * len(shared))(*shared) if shared else None
+        flags = None
+        if set_shared is not None:
+            if len(set_shared) != len(set_lists):
+                raise ValueError("set_shared needs one entry a set")
+            flags = (C.c_uint8 * max(1, len(set_lists)))(*[1 if f else 0 for f in set_shared])
+        h = _VP()
+        _check(lib.g2s_graph_build_pool(arr, lens, n, set_begin, set_seq, sh, len(shared), flags, len(set_lists), k, solid,
+                                        nthreads, C.byref(h)))
         return cls(h)
 
     @property
@@ -896,6 +1040,13 @@ def test_rand_stream(seed, skip, n):
     out = (C.c_int32 * max(1, n))()
     _check(load_library().g2s_test_rand_stream(seed, skip, n, out))
     return [out[i] for i in range(n)]
+
+
+def test_last_pool_build():
+    """g2s_test_last_pool_build: dict(own_positions, shared_positions, keys_sorted, on_device) of the last pooled build"""
+    a, b, c, d = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_int()
+    _check(load_library().g2s_test_last_pool_build(C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
+    return dict(own_positions=a.value, shared_positions=b.value, keys_sorted=c.value, on_device=d.value)
 
 
 def test_filter_join(ref_id, pos, end, flag, h_own, h_mate, max_span, bits, windows, max_pairs, device=-1, threads=1):

@@ -80,6 +80,30 @@ int g2s_graph_build_seqs(const char* const* seqs, const uint64_t* lens, int nseq
  * several sets are built on host threads and cannot be saved (g2s_graph_save: G2S_ERR_ARG). */
 int g2s_graph_build_sets(const char* const* seqs, const uint64_t* lens, const uint32_t* seq_set, int nseqs, uint32_t nsets,
                          int k, int solid, int nthreads, g2s_graph** out);
+/* The same set graph from a POOL of sequences that the sets share (ABI 6, additive), for read sets that overlap — the
+ * libraries flow's gaps select the same reads again and again, and every gap under the threshold takes every unmapped
+ * read.  Set s is the MULTISET of the sequences seqs[set_seq[q]], q in [set_begin[s], set_begin[s+1]) (its own list),
+ * followed by seqs[shared_seq[0 .. nshared)] when set_shared[s] is nonzero.  The graph is the one
+ * g2s_graph_build_sets gives for that expanded list: the same sets, the same solid k-mers per set, the same edges,
+ * set-major numbering, g2s_graph_set_nodes equal (the numbering of nodes inside a set may differ where the host and
+ * the device build differ).  A sequence may be in any number of sets and more than once in one set; every occurrence
+ * counts towards solidity, as the concatenated FASTA files count it in the reference flow.  No text is copied on the
+ * host.  On the device (odd k) the pool's text goes up once, the own lists' k-mers are sorted by (set, k-mer), and the
+ * shared list's k-mers are sorted ONCE and merged into every flagged set, so the keys sorted are the own lists'
+ * positions plus the shared list's, whatever the number of flagged sets; when the device cannot take it (the own and
+ * shared positions reach 2^32, the estimate exceeds half the free device memory — the merge's flagged sets x distinct
+ * shared k-mers included — or 2^30 k-mers result) the host builds it set by set from each set's pointers, as for even
+ * k, without a device and with G2S_HOST_BUILD=1 (G2S_DEBUG=1 says which, and why).
+ * shared_seq may be NULL when nshared == 0; set_shared NULL = no set holds the shared list; nsets == 1 gives an
+ * ordinary graph.  G2S_ERR_ARG: an index >= nseqs, nseqs >= 2^32, a decreasing set_begin, nsets == 0, k out of range;
+ * *out is not written then. */
+int g2s_graph_build_pool(const char* const* seqs, const uint64_t* lens, uint64_t nseqs,
+                         const uint64_t* set_begin,   /* [nsets + 1] */
+                         const uint32_t* set_seq,     /* [set_begin[nsets]] indices into seqs */
+                         const uint32_t* shared_seq,  /* [nshared] indices into seqs */
+                         uint64_t nshared,
+                         const uint8_t* set_shared,   /* [nsets] */
+                         uint32_t nsets, int k, int solid, int nthreads, g2s_graph** out);
 uint32_t g2s_graph_num_sets(const g2s_graph* g); /* 1 for every graph built the other ways */
 int g2s_graph_set_nodes(const g2s_graph* g, uint32_t set, uint64_t* first_kmer, uint64_t* n_kmers);
 uint32_t g2s_graph_set_node(const g2s_graph* g, uint32_t set, const char* kmer); /* G2S_INVALID_NODE if absent */
@@ -449,6 +473,34 @@ int g2s_filter_reads_gaps(const char* bam_path, const g2s_filter_opts* lib, cons
 int g2s_filter_reads_gaps_mem(const void* bam_bytes, size_t nbytes, const g2s_filter_opts* lib, const g2s_filter_gap* gaps,
                               size_t n, int device, char** fasta_out, char** log_out, char** warn_out, int64_t* extracted,
                               int64_t* total, char** unmapped_out, int64_t* unmapped_extracted, g2s_filter_stats* stats);
+
+/* ---------------------------------------------------------------------------
+ *  The same call handing over a POOL of reads instead of per-gap text (ABI 6, additive): every record that some gap
+ *  selected, or (with want_unmapped) that is unmapped, is held ONCE, and every gap is a list of indices into the pool —
+ *  what g2s_graph_build_pool takes.  The memory returned does not grow with the gaps that select a read.  Pass A, the
+ *  joins and pass B are g2s_filter_reads_gaps'; so are the limits, the device rule and the errors.
+ *  Contract: with names, writing ">" name "\n" bases "\n" for gap_read[gap_begin[i] .. gap_begin[i+1]) in order gives
+ *  fasta_out[i] of g2s_filter_reads_gaps byte for byte (a read may be named twice by one gap, as there), and doing so
+ *  for unmapped_read gives unmapped_out.  *out is written on G2S_OK only; release it with g2s_read_pool_free.
+ * ------------------------------------------------------------------------ */
+typedef struct g2s_read_pool {
+  uint64_t n_reads;        /* distinct records held: selected by some gap, or unmapped; file order */
+  char* bases;             /* the reads as sequenced, back to back, no separators */
+  uint64_t* base_off;      /* [n_reads + 1] */
+  char* names;             /* "name/1" or "name/2" back to back; NULL unless asked for */
+  uint64_t* name_off;      /* [n_reads + 1], NULL with names */
+  uint64_t* gap_begin;     /* [n + 1] */
+  uint32_t* gap_read;      /* [gap_begin[n]] gap i's reads, in the order of g2s_filter_reads_gaps' fasta_out[i] */
+  uint64_t n_unmapped;     /* 0 unless asked for */
+  uint32_t* unmapped_read; /* [n_unmapped] ascending; an unmapped read some gap selected is the same pool entry */
+} g2s_read_pool;
+int g2s_filter_reads_gaps_pool(const char* bam_path, const g2s_filter_opts* lib, const g2s_filter_gap* gaps, size_t n,
+                               int device, int want_names, int want_unmapped, g2s_read_pool** out, int64_t* total,
+                               g2s_filter_stats* stats);
+int g2s_filter_reads_gaps_pool_mem(const void* bam_bytes, size_t nbytes, const g2s_filter_opts* lib, const g2s_filter_gap* gaps,
+                                   size_t n, int device, int want_names, int want_unmapped, g2s_read_pool** out, int64_t* total,
+                                   g2s_filter_stats* stats);
+void g2s_read_pool_free(g2s_read_pool* p);
 
 /* ---------------------------------------------------------------------------
  *  Page-locked host memory the GPUs can write: a `results` array or fill arena

@@ -95,6 +95,14 @@ int g2s_test_filter_join(int device, int32_t threads, uint64_t nr, const int32_t
                          int64_t max_span, uint64_t bits, uint64_t n, const int64_t* windows, uint64_t max_pairs,
                          uint64_t* list1, uint64_t cap1, uint64_t* n1, uint64_t* list2, uint64_t cap2, uint64_t* n2);
 
+/* TEST HOOK: what the process's last g2s_graph_build_pool of several sets did.  own_positions: bases + 1 of every
+ * occurrence of a sequence in the sets' own lists; shared_positions: the same of the shared list, once (0 when no set
+ * is flagged); keys_sorted: the keys that went through a sort.  On the device (*on_device = 1) keys_sorted ==
+ * own_positions + shared_positions whatever the number of flagged sets: the shared list is sorted once.  The host
+ * build (*on_device = 0) works on every set's expanded list: own_positions + flagged sets * shared_positions.  Any
+ * pointer may be NULL. */
+int g2s_test_last_pool_build(uint64_t* own_positions, uint64_t* shared_positions, uint64_t* keys_sorted, int* on_device);
+
 #ifdef __cplusplus
 }
 #endif
