@@ -159,7 +159,10 @@ struct D3Params {
   // their gap's verdict word, and the wave that cleans up behind the list waits until d2_wgs workgroups of it have
   // left (*d2_done counts them; null: nothing of the kind is running)
   const unsigned long long* d2_done;
-  uint32_t d2_wgs, pad1;
+  uint32_t d2_wgs;
+  // a set list (g2s_fill_sets): every gap draws from value 0 of the stream — all offsets 0, no gap depends on
+  // another, no generator state is left for a following list; D3Summary.draws_total is the most draws of one gap
+  uint32_t restart;
 };
 
 // the stream: values [0, capacity) into rnd_all[31 ..] (sum_dev = nullptr; independent of the list's kernels, so
@@ -178,6 +181,8 @@ hipError_t launch_rand_fill(hipStream_t st, uint32_t* rnd_all, const RandTables&
 //   g2s_d3_handoff every gap's first draw and draw count; what the host needs to finish the gaps whose closure it
 //                  analyses, into pinned memory (*side.count says when: the host polls it)
 //   g2s_d3_trace   one wave per gap: the traceback, fill text and result record; the last wave copies the summary
+// With P.restart (a set list) the kernels between the fill kernel and the trace kernel are one: g2s_d3_restart — the
+// classes, every gap's draw count from value 0 and the hand-off; ev_chain is not recorded and W.link not written.
 // The same in three steps, for a list whose groups stay on the GPUs that filled them (one session per GPU, every one
 // tracing its own gaps and writing its own results through its own link).  Between the steps the host exchanges a
 // few words per group:

@@ -643,7 +643,9 @@ __device__ int d3_walk_count(int n_len, int len0, int len1, uint32_t start_seg, 
 // value per segment entered, no counters carried along.  (The depths are the records': a closure whose segments do
 // not follow each other as their depths say is the trace kernel's to find — it checks every hop of the walk that is
 // taken — and the host's to decide.)
-__device__ int d3_walk_count_lite(int n_len, int len0, int len1, uint32_t start_seg, int nsegs, const SegLite* __restrict__ segs,
+// (SegT: SegLite — the links in LDS — or SegW: the records where they lie, for the one walk a gap of a set list needs)
+template <typename SegT>
+__device__ int d3_walk_count_lite(int n_len, int len0, int len1, uint32_t start_seg, int nsegs, const SegT* __restrict__ segs,
                                   const uint32_t* lwin, uint32_t nwin, uint64_t avail, bool* bad) {
   if (avail < 1 || nwin < 1) { *bad = true; return 1; }
   const int pick = n_len > 1 ? (int)((lwin[0] >> 1) & 1u) : 0;  // :1440 (n_len <= 2)
@@ -652,7 +654,7 @@ __device__ int d3_walk_count_lite(int n_len, int len0, int len1, uint32_t start_
   int i = sg == 0xFFFFu ? -1 : (int)sg;
   if (i < 0 || i >= nsegs || len < 0) { *bad = true; return 1; }
   for (int hop = 0; hop <= nsegs; hop++) {  // (a traceback descends: it enters a segment once)
-    const SegLite s = segs[i];
+    const SegLite s = seg_lite(segs, i);
     const int d0 = (int)(s.depth_len & 0xFFFFu);
     if (d0 > len) break;
     if (s.flags & G2S_SUB_SOURCE) return 1 + len - d0;  // :1455-1462
@@ -843,6 +845,9 @@ __global__ __launch_bounds__(1024) void g2s_d3_front(const D3Params P, const D3W
 // (the body: one wave, the 64 gaps from i0 on; true when it handed something over.  ldvar/ltab/ltoff: the
 // deviations, tables and table offsets in LDS when the caller holds them there, else null; lcur: the three cursors
 // of the side buffers in LDS when one workgroup hands the whole list over, else null — the summary's are used)
+// RESTART (a set list, D3Params.restart): every gap draws from value 0 of the stream — no offsets, no deviations, no
+// tables; a draw-dependent gap's one draw count is walked here, by its lane.
+template <bool RESTART>
 __device__ __forceinline__ bool d3_handoff_body(const D3Params& P, const D3Work& W, const GapOut* __restrict__ outs,
                                                 const SubRec* __restrict__ sub, const uint32_t* __restrict__ rnd, uint64_t capacity,
                                                 const g2s::D3Side& side, uint32_t i0, const uint32_t* ldvar, const uint16_t* ltab,
@@ -854,7 +859,7 @@ __device__ __forceinline__ bool d3_handoff_body(const D3Params& P, const D3Work&
   uint32_t gi = 0, my_off = 0, my_want = 0, my_ns = 0;
   if (have) {
     gi = W.ginfo[mine];
-    const uint32_t vr = W.vrank[mine], base = W.base[mine], dmin = W.dmin[mine];
+    const uint32_t dmin = W.dmin[mine];
     const GapOut& go = outs[mine];
     my_ns = go.n_xl;
     // (g2s_d2_* runs beside these kernels: a gap it was to analyse and has given up on — beyond its capacities — is the
@@ -863,10 +868,30 @@ __device__ __forceinline__ bool d3_handoff_body(const D3Params& P, const D3Work&
       const uint32_t dfl = go.dflags;
       if ((dfl & G2S_DEVA_D2_PENDING) && (dfl & G2S_DEVA_D2_FAILED)) gi |= GI_HOST;
     }
-    const uint32_t dv = ldvar ? ldvar[vr] : W.dvar[vr];
-    my_off = base + dv;
     my_want = dmin;
-    if (GI_CLASS(gi) == 2u) my_want += ltab ? (uint32_t)ltab[ltoff[vr] + dv] : (uint32_t)W.tab[(uint64_t)W.var_toff[vr] + dv];
+    if constexpr (RESTART) {
+      if (GI_CLASS(gi) == 2u) {
+        // (what g2s_d3_tables computes per deviation, for the one start this gap has: the same walks over the same
+        // window — dmin + dspread + 1 values from the stream's first — and the same verdict on what they return)
+        const uint32_t dspread = W.dspread[mine];
+        const uint4 h0 = ((const uint4*)&W.tdesc[mine])[0];  // (sub_at: the classes wrote it)
+        const SegW* gs = (const SegW*)(sub + ((uint64_t)h0.z | ((uint64_t)h0.w << 32)));
+        const uint32_t nwin = min(P.map_cap + D3_TILE, dmin + dspread + 1u);
+        bool bad = false;
+        const int draws = my_ns > D3_TAB_SEGS
+                              ? d3_walk_count(go.n_len, go.len[0], go.len[1], go.start_seg, go.start_t, (int)my_ns, gs, rnd, nwin, capacity, &bad)
+                              : d3_walk_count_lite(go.n_len, go.len[0], go.len[1], go.start_seg, (int)my_ns, gs, rnd, nwin, capacity, &bad);
+        const int dev = draws - (int)dmin;
+        if (dev < 0 || dev > (int)dspread) bad = true;
+        if (bad) atomicAdd(&S->anomalies, 1u);
+        else my_want += (uint32_t)dev;
+      }
+    } else {
+      const uint32_t vr = W.vrank[mine], base = W.base[mine];
+      const uint32_t dv = ldvar ? ldvar[vr] : W.dvar[vr];
+      my_off = base + dv;
+      if (GI_CLASS(gi) == 2u) my_want += ltab ? (uint32_t)ltab[ltoff[vr] + dv] : (uint32_t)W.tab[(uint64_t)W.var_toff[vr] + dv];
+    }
     // the half of the trace kernel's record that depends on the offsets (the classes wrote the other)
     ((uint4*)&W.tdesc[mine])[1] = make_uint4(gi, my_off, my_want, (gi >> 16) | (min(my_ns, 0xFFFFu) << 16));
   }
@@ -905,6 +930,15 @@ __device__ __forceinline__ bool d3_handoff_body(const D3Params& P, const D3Work&
   }
   if (hm != 0ull) __threadfence_system();  // (the items are in host memory before the count that announces them)
   (void)sub; (void)rnd; (void)outs;
+  if constexpr (RESTART) {  // (the summary's words the scan and the chain write on other lists: draw-dependent gaps; most draws of a gap)
+    const uint32_t nv = (uint32_t)__popcll(__ballot(have && GI_CLASS(gi) == 2u));
+    uint32_t mx = have ? my_want : 0u;
+    for (int o = 32; o > 0; o >>= 1) mx = max(mx, (uint32_t)__shfl_xor((int)mx, o));
+    if (lane == 0) {
+      if (nv) atomicAdd(&S->n_var, nv);
+      atomicMax((unsigned long long*)&S->draws_total, (unsigned long long)mx);
+    }
+  }
   return hm != 0ull;
 }
 // (*side.count is ~0 until the hand-over is complete: the host polls it.  Bit 63: something did not fit, or the
@@ -914,7 +948,7 @@ __global__ __launch_bounds__(64) void g2s_d3_handoff(const D3Params P, const D3W
                                                      const g2s::D3Side side) {
   D3Summary* S = W.sum;
   const bool dead = S->status != 0u;
-  if (!dead) (void)d3_handoff_body(P, W, outs, sub, rnd, capacity, side, blockIdx.x * 64u, nullptr, nullptr, nullptr, nullptr);
+  if (!dead) (void)d3_handoff_body<false>(P, W, outs, sub, rnd, capacity, side, blockIdx.x * 64u, nullptr, nullptr, nullptr, nullptr);
   if ((threadIdx.x & 63u) == 0u) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (this wave's additions to the cursors have been acknowledged)
     const unsigned int done = atomicAdd(&S->handoff_waves, 1u) + 1u;
@@ -922,6 +956,33 @@ __global__ __launch_bounds__(64) void g2s_d3_handoff(const D3Params P, const D3W
       const unsigned long long items = atomicAdd(&S->host_items, 0ull);
       const uint32_t anomalies = atomicAdd(&S->anomalies, 0u);
       __hip_atomic_store(side.count, (items & 0x7FFFFFFFFFFFFFFFull) | ((unsigned long long)((anomalies || dead) ? 1u : 0u) << 63),
+                         __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+  }
+}
+// A set list (D3Params.restart: g2s_fill_sets): every gap's stream is that of a fresh srand(), so gap i reads the values
+// from 0 on whatever stands in front of it — nothing of phase D3 is serial, and nothing is handed to a next list.  The
+// classes, every gap's draw count and the hand-off in ONE launch for a list of any length: a workgroup of four waves
+// takes 256 consecutive gaps, thread t of the launch gap t (the grid is exactly (n + 255) / 256 workgroups), so a
+// thread reads back only what it wrote itself.  The wave that is through last knows the list's counters: it writes
+// the status the trace kernel reads and the count the host polls.
+__global__ __launch_bounds__(256) void g2s_d3_restart(const D3Params P, const D3Work W, const GapOut* __restrict__ outs,
+                                                      const D3Gap* __restrict__ dgaps, const SubRec* __restrict__ sub,
+                                                      const uint32_t* __restrict__ rnd, uint64_t capacity, const g2s::D3Side side) {
+  __shared__ unsigned long long red[4 * 8];
+  D3Summary* S = W.sum;
+  (void)d3_classify_body(P, W, outs, dgaps, blockIdx.x * 256u + threadIdx.x, gridDim.x * 256u, nullptr, nullptr, nullptr, nullptr, red, false);
+  // (a list with a gap the segment tier did not finish goes to the host path whole: known only when every workgroup
+  // has classified — what the waves hand over until then is dropped with the list)
+  (void)d3_handoff_body<true>(P, W, outs, sub, rnd, capacity, side, blockIdx.x * 256u + (threadIdx.x & ~63u), nullptr, nullptr, nullptr, nullptr);
+  if ((threadIdx.x & 63u) == 0u) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (this wave's additions to the counters and cursors have been acknowledged)
+    const unsigned int done = atomicAdd(&S->handoff_waves, 1u) + 1u;
+    if (done == gridDim.x * 4u) {
+      const unsigned long long items = atomicAdd(&S->host_items, 0ull);
+      const uint32_t anomalies = atomicAdd(&S->anomalies, 0u), unhandled = atomicAdd(&S->unhandled, 0u);
+      S->status = unhandled ? G2S_D3_UNHANDLED : 0u;
+      __hip_atomic_store(side.count, (items & 0x7FFFFFFFFFFFFFFFull) | ((unsigned long long)((anomalies || unhandled) ? 1u : 0u) << 63),
                          __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     }
   }
@@ -977,7 +1038,7 @@ __global__ __launch_bounds__(1024) void g2s_d3_back(const D3Params P, const D3Wo
   }
   if (threadIdx.x == 0) stamp(W, 10);
   for (uint32_t i0 = (threadIdx.x >> 6) * 64u; i0 < P.n; i0 += 1024u)
-    (void)d3_handoff_body(P, W, outs, sub, Wd + 31, capacity, side, i0, in_lds ? ldvar : nullptr, in_lds ? ltab : nullptr,
+    (void)d3_handoff_body<false>(P, W, outs, sub, Wd + 31, capacity, side, i0, in_lds ? ldvar : nullptr, in_lds ? ltab : nullptr,
                           in_lds ? ltoff : nullptr, lcur);
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -1711,7 +1772,10 @@ hipError_t launch_d3(hipStream_t st, const D3Params& P, const D3Work& W, const G
   hipError_t e = summary_is_clean ? hipSuccess : hipMemsetAsync(W.sum, 0, 1024 + 64 * 128, st);
   if (e != hipSuccess) return e;
   const bool short_list = P.n <= D3_FRONT_GAPS;
-  if (short_list) hipLaunchKernelGGL(g2s_d3_front, dim3(1), dim3(1024), 0, st, P, W, outs, dgaps);
+  if (P.restart) {  // (a set list: classes, draw counts and hand-off in one launch; the trace kernel as for any list)
+    if (ev_d2) { e = hipStreamWaitEvent(st, ev_d2, 0); if (e != hipSuccess) return e; }
+    hipLaunchKernelGGL(g2s_d3_restart, dim3((P.n + 255u) / 256u), dim3(256), 0, st, P, W, outs, dgaps, sub, rnd_all + 31, rnd_capacity, side);
+  } else if (short_list) hipLaunchKernelGGL(g2s_d3_front, dim3(1), dim3(1024), 0, st, P, W, outs, dgaps);
   else {
     hipLaunchKernelGGL(g2s_d3_classify, dim3((P.n + 255u) / 256u), dim3(256), 0, st, P, W, outs, dgaps);
     launch_scan(st, P, W, outs);
@@ -1719,12 +1783,15 @@ hipError_t launch_d3(hipStream_t st, const D3Params& P, const D3Work& W, const G
   // (a tile of 256 deviations per workgroup, grid-stride: a short list has a few dozen tiles)
   const uint32_t tgrid = std::min(8192u, std::max(128u, P.n / 2u));
   const size_t win = ((size_t)P.map_cap + 256) * 4;
-  e = hipFuncSetAttribute((const void*)g2s_d3_tables, hipFuncAttributeMaxDynamicSharedMemorySize, (int)win);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(g2s_d3_tables, dim3(tgrid), dim3(256), win, st, P, W, sub, rnd_all + 31, rnd_capacity);
+  if (!P.restart) {
+    e = hipFuncSetAttribute((const void*)g2s_d3_tables, hipFuncAttributeMaxDynamicSharedMemorySize, (int)win);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(g2s_d3_tables, dim3(tgrid), dim3(256), win, st, P, W, sub, rnd_all + 31, rnd_capacity);
+  }
   // (g2s_d2_* runs on a stream of its own beside the kernels above; the hand-off reads what it decided)
-  if (ev_d2 && short_list) { e = hipStreamWaitEvent(st, ev_d2, 0); if (e != hipSuccess) return e; }
-  if (short_list) {
+  if (ev_d2 && short_list && !P.restart) { e = hipStreamWaitEvent(st, ev_d2, 0); if (e != hipSuccess) return e; }
+  if (P.restart) (void)ev_chain;  // (no chain: the list's draws are nobody's to continue)
+  else if (short_list) {
     hipLaunchKernelGGL(g2s_d3_back, dim3(1), dim3(1024), 0, st, P, W, outs, sub, rnd_all, rnd_capacity, side);
     if (ev_chain) { e = hipEventRecord(ev_chain, st); if (e != hipSuccess) return e; }
   } else {

@@ -966,6 +966,7 @@ struct g2s_batch {
   bool has_skip = false, seg_tier_all = true;  // a gap carries a skip rule; every gap with flanks fits the segment tier
   int gmax = 0, dmax = 0;                       // longest gap, deepest search
   size_t rnd_cap = 0, n_valid = 0;              // rand() values the list can draw at most; gaps with complete flanks
+  size_t rnd_sum = 0;                           // the same summed over the gaps (a set list: rnd_cap is the most of one gap)
   bool fast_desc = false;                       // GapDev / D3Gap of every gap are in the session's pinned buffers (desc_owner)
   // g2s_fill_begin: the fill kernel of this list has been queued already (resident_launch_fill); g2s_batch_run goes on
   // with phase D3
@@ -1040,7 +1041,7 @@ static TierData* take_tier(g2s_session* s, size_t /*unused*/) {
 
 // Can a list of n gaps be finished on the device (run_resident)?  The checks that do not look at the gaps.
 static bool resident_applicable(const g2s_session* s, size_t n) {
-  if (s->resident_off || n == 0 || s->set_gaps) return false;  // (set lists: phase D on the host, streams restarted per gap)
+  if (s->resident_off || n == 0) return false;
   const int forced = GENV("G2S_RESIDENT") ? atoi(GENV("G2S_RESIDENT")) : -1;  // (1: lists of any length; 0: never)
   // (lists of a few dozen gaps: the host analyses gaps while the launch's stragglers run and is done before four
   // more launches would be; measured on config 2's 500 gaps: 0.32 ms on the device against 0.35-0.39 ms.  The
@@ -1092,7 +1093,7 @@ extern "C" int g2s_batch_prepare(g2s_session* s, const g2s_gap* gaps, size_t n, 
   const size_t per_task = std::max<size_t>(256, (n + max_tasks - 1) / max_tasks);  // (at most 16 tasks: every task wakes a thread)
   const size_t ntasks = (n + per_task - 1) / per_task;
   struct Part {
-    size_t n_nodes = 0, text_bytes = 0, n_desc = 0, arena_bytes = 0, rnd_cap = 0;
+    size_t n_nodes = 0, text_bytes = 0, n_desc = 0, arena_bytes = 0, rnd_cap = 0, rnd_max = 0;
     uint64_t flank_bytes = 0;
     int gmax = 0, dmax = 0;
     size_t tb_max = 0;
@@ -1128,6 +1129,7 @@ extern "C" int g2s_batch_prepare(g2s_session* s, const g2s_gap* gaps, size_t n, 
         P.gmax = std::max(P.gmax, j.g);
         P.dmax = std::max(P.dmax, dd);
         P.rnd_cap += (size_t)(dd + 2);
+        P.rnd_max = std::max(P.rnd_max, (size_t)(dd + 2));
       } else {
         j.lmf = std::max(0, j.lmf);
         j.rmf = std::max(0, j.rmf);
@@ -1147,7 +1149,9 @@ extern "C" int g2s_batch_prepare(g2s_session* s, const g2s_gap* gaps, size_t n, 
     const Part& P = parts[t];
     base_nodes[t] = n_nodes; base_text[t] = text_bytes; base_desc[t] = n_desc; base_arena[t] = b->arena_bytes;
     n_nodes += P.n_nodes; text_bytes += P.text_bytes; n_desc += P.n_desc; b->arena_bytes += P.arena_bytes;
-    b->rnd_cap += P.rnd_cap;
+    // (a set list: every gap draws from the stream's first value — the stream is as long as the longest gap needs)
+    b->rnd_cap = gap_set ? std::max(b->rnd_cap, P.rnd_max) : b->rnd_cap + P.rnd_cap;
+    b->rnd_sum += P.rnd_cap;
     b->timing.flank_bytes += P.flank_bytes;
     b->gmax = std::max(b->gmax, P.gmax);
     b->dmax = std::max(b->dmax, P.dmax);
@@ -1176,7 +1180,8 @@ extern "C" int g2s_batch_prepare(g2s_session* s, const g2s_gap* gaps, size_t n, 
   // the launch takes the gaps in list order, a wave knows where its text is before its descriptor has arrived — on a
   // short list both come over the link.)
   // (k >= 64: the look-up kernel always — the fill kernels' in-wave look-ups take 64- and 128-bit k-mers only)
-  b->inline_ok = fast_gd != nullptr && b->dmax < 2500 && s->lookup.wide != G2S_LK_256;
+  // (a set list: the look-up kernel too — it searches each gap's own set, by rank range)
+  b->inline_ok = fast_gd != nullptr && b->dmax < 2500 && s->lookup.wide != G2S_LK_256 && !gap_set;
   uint32_t tstride = 0;
   if (b->inline_ok && n_desc == n && tb_max <= 508) {
     tstride = (uint32_t)((tb_max + 3) & ~(size_t)3);
@@ -3301,6 +3306,8 @@ struct ResidentList {
   uint64_t sub_region = 0;
   PinBuf* pin = nullptr;               // [D3Gap x n | summary | fill-byte counters | stream window], D3Gap filled by the caller
   size_t rnd_cap = 0;
+  size_t rnd_sum = 0;                  // a set list: the draws summed over the gaps (what the host-finished gaps' values can take)
+  bool restart = false;                // a set list: every gap draws from value 0 of the stream (D3Params.restart)
   int dmax = 0;
   bool has_skip = false;
   const GapDev* gaps_dev = nullptr;
@@ -3379,7 +3386,8 @@ static int resident_d3_launch(g2s_session* s, const ResidentList& L, bool timed,
     // (deep searches — -dist-error in the thousands — leave closures of thousands of segments to the host's analysis)
     const bool deep = L.dmax >= 2500;
     side_h.cap_segs = deep ? std::min<uint64_t>((uint64_t)n * 4096u, 4ull << 20) + 65536u : std::max<uint64_t>((uint64_t)n * 16u, 65536u);
-    side_h.cap_rnd = deep ? rnd_cap + 65536u : rnd_cap / 8 + 65536u;
+    const size_t side_rnd = std::max(rnd_cap, rand_capacity(L.rnd_sum));  // (a set list: the stream is one gap's, the side buffer all gaps')
+    side_h.cap_rnd = deep ? side_rnd + 65536u : side_rnd / 8 + 65536u;
     const size_t b_items = (n * sizeof(D3HostItem) + 63) & ~(size_t)63, b_outs = (n * sizeof(GapOut) + 63) & ~(size_t)63;
     const size_t b_segs = side_h.cap_segs * sizeof(SegRec);
     const void* side_was = s->h_side.p;
@@ -3408,7 +3416,7 @@ static int resident_d3_launch(g2s_session* s, const ResidentList& L, bool timed,
   }
   D3Work W;
   d3_work_carve(s->d_d3.p, (uint32_t)n, &W);
-  W.link = sharded ? nullptr : (uint32_t*)s->d_link.p;
+  W.link = (sharded || L.restart) ? nullptr : (uint32_t*)s->d_link.p;
   if (s->spec_on && !sharded && L.groups.size() == 1 && L.outs_dev == (const GapOut*)s->d_outs.p) {  // (this session's own fill launch left guesses)
     W.spec_text = (const char*)s->d_textout.p; W.spec_res = (const uint32_t*)s->d_resout.p;
   }
@@ -3471,6 +3479,7 @@ static int resident_d3_launch(g2s_session* s, const ResidentList& L, bool timed,
   if (W.d2out) { P.d2_done = (const unsigned long long*)s->d_counter.p + 9; P.d2_wgs = s->d2_wgs; }
   P.seg_cap = fp.skip_confident ? G2S_SEG_CAP : 192u;
   P.map_cap = ((uint32_t)L.dmax + 2u + 3u) & ~3u;
+  P.restart = L.restart ? 1u : 0u;
   if (sharded) {
     HIP_TRY_S(launch_d3_sharded_classes(st, P, W, L.outs_dev, (const D3Gap*)d_dgaps, s->d_d3.clean >= 1024 + 64 * 128));
     HIP_TRY_S(hipMemcpyAsync(hsum, W.sum, sizeof(D3Summary), hipMemcpyDeviceToHost, st));  // (the group's totals)
@@ -3480,7 +3489,9 @@ static int resident_d3_launch(g2s_session* s, const ResidentList& L, bool timed,
                     (uint64_t)rnd_cap, res_dev, (char*)arena_dev, side, (char*)d_dgaps + ((char*)hsum - (char*)L.pin->p),
                     s->d_d3.clean >= 1024 + 64 * 128, self_clean ? (uint32_t*)s->d_counter.p : nullptr,
                     no_spin ? s->ev_chain : nullptr /* (lists in flight: the next one's stream may wait for it) */,
-                    (W.d2out && s->d2_wait) ? s->ev_d2 : nullptr,
+                    // (a set list's hand-off is the first kernel behind the fill kernel: it would look at the closures g2s_d2_*
+                    // analyses before that kernel has said which of them it gives up — those are the host's — so it waits)
+                    (W.d2out && (s->d2_wait || L.restart)) ? s->ev_d2 : nullptr,
                     timed ? s->ev[3] : nullptr /* (the trace kernel's own stop time) */));
   s->d_d3.clean = 0;
   {
@@ -3788,7 +3799,8 @@ static int resident_d3_wait(g2s_session* s, g2s_timing* tm_out, double* ms_d3_ou
     if (ntasks > 2) s->pool->run(ntasks, copy_range);
     else for (size_t t = 0; t < ntasks; t++) copy_range(t);
   }
-  if (!dpp->sharded) s->rcache.jump((size_t)hsum->draws_total, hsum->rand_state);  // (a sharded list: the team's lead, once)
+  // (a sharded list: the team's lead, once; a set list consumes nothing — its next group starts at value 0 again)
+  if (!dpp->sharded && !L.restart) s->rcache.jump((size_t)hsum->draws_total, hsum->rand_state);
   g2s_timing& tm = *tm_out;
   tm.xA += hsum->xA; tm.sA += hsum->sA; tm.xB += hsum->xB; tm.sB += hsum->sB; tm.xD += hsum->xD; tm.sD += hsum->sD;
   tm.seg_segments += hsum->segs;
@@ -3865,6 +3877,7 @@ static int run_resident_queue(g2s_batch* b, g2s_result* results, char* arena, bo
   L.sub_region = 0;
   L.pin = &s->h_d3;
   L.rnd_cap = b->rnd_cap; L.dmax = b->dmax; L.has_skip = b->has_skip;
+  L.rnd_sum = b->rnd_sum; L.restart = b->set_list;
   L.gaps_dev = (const GapDev*)s->d_gaps.p;
   if (b->arena_base) {  // (the D3Gap offsets are within the batch's share: make them offsets into the arena)
     D3Gap* dq = (D3Gap*)s->h_d3.p;
@@ -4591,8 +4604,9 @@ extern "C" int g2s_fill_batch(g2s_session* s, const g2s_gap* gaps, size_t n, g2s
 // Independent gaps over a set graph: the wrapper's per-gap Gap2Seq-core runs (Gap2Seq.py:133-218) in one list.  The
 // fill kernels see the disjoint union of the sets' graphs as one graph; the look-ups search each gap's own set
 // (upload_flanks: the look-up kernel's rank ranges; host look-ups: Graph::node_of_in), and phase D gives every gap the
-// stream of a fresh srand(randseed) (batches_stage2: restart) from a generator of its own, so the session's is left as
-// it was.  Cut into groups of the size g2s_fill_batch cuts lists with (the HBM of one launch's state logs); groups
+// stream of a fresh srand(randseed) from a generator of its own, so the session's is left as it was: on the device for
+// the lists resident mode takes (D3Params.restart: every gap reads the stream from value 0, nothing is consumed), on
+// the host otherwise and for a list the device gives back (batches_stage2: restart).  Cut into groups of the size g2s_fill_batch cuts lists with (the HBM of one launch's state logs); groups
 // change nothing, every gap being on its own.
 extern "C" int g2s_fill_sets(g2s_session* s, const g2s_gap* gaps, const uint32_t* gap_set, size_t n, g2s_result* results,
                              char* fill_arena, size_t arena_cap) {
@@ -4620,7 +4634,7 @@ extern "C" int g2s_fill_sets(g2s_session* s, const g2s_gap* gaps, const uint32_t
     g2s_batch* b = nullptr;
     rc = g2s_batch_prepare(s, gaps + off, cnt, &b);
     if (rc != G2S_OK) break;
-    // (set_gaps stays up through the run: resident_applicable keeps the list on the host path)
+    // (set_gaps stays up through the run)
     rc = g2s_batch_run(b, results + off, fill_arena ? fill_arena + std::min(aoff, arena_cap) : nullptr, aoff <= arena_cap ? arena_cap - aoff : 0);
     if (rc == G2S_OK) {
       for (size_t q = 0; q < cnt; q++) results[off + q].fill_off += (uint64_t)aoff;  // (offsets within the group's share)
@@ -4630,6 +4644,12 @@ extern "C" int g2s_fill_sets(g2s_session* s, const g2s_gap* gaps, const uint32_t
       total.ms_fill_segx += t.ms_fill_segx; total.flank_bytes += t.flank_bytes; total.fill_bytes += t.fill_bytes;
       total.lds_tier_gaps += t.lds_tier_gaps; total.seg_tier_gaps += t.seg_tier_gaps; total.segx_tier_gaps += t.segx_tier_gaps;
       total.seg_launches += t.seg_launches; total.segx_launches += t.segx_launches; total.lds_launches += t.lds_launches;
+      total.resident_launches += t.resident_launches; total.resident_fallbacks += t.resident_fallbacks; total.ms_d3 += t.ms_d3;
+      total.draw_dependent_gaps += t.draw_dependent_gaps; total.host_finished_gaps += t.host_finished_gaps;
+      total.traced_in_fill_gaps += t.traced_in_fill_gaps; total.guessed_in_fill_gaps += t.guessed_in_fill_gaps;
+      total.guessed_groups += t.guessed_groups; total.guessed_groups_resent += t.guessed_groups_resent;
+      total.d3_table_entries += t.d3_table_entries; total.seg_timed_launches += t.seg_timed_launches;
+      total.xA += t.xA; total.sA += t.sA; total.xB += t.xB; total.sB += t.sB; total.xD += t.xD; total.sD += t.sD;
     }
     aoff += b->arena_bytes;
     g2s_batch_free(b);

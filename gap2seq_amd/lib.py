@@ -788,7 +788,9 @@ class Session:
 
     def fill_sets(self, gaps, gap_set, want_timing=False):
         """g2s_fill_sets: gap i filled in read set gap_set[i] of a set graph, every gap from a fresh srand(randseed);
-        returns what fill_batch returns."""
+        returns what fill_batch returns.  Lists of 256 gaps or more are finished on the device (resident mode,
+        G2S_RESIDENT=0|1 as for fill_batch); the timing sums the list's groups, resident_launches /
+        resident_fallbacks / host_finished_gaps included."""
         lib = load_library()
         if len(gap_set) != len(gaps):
             raise ValueError("fill_sets: one set id per gap")

@@ -315,7 +315,10 @@ int g2s_fill_batch(g2s_session* s, const g2s_gap* gaps, size_t n, g2s_result* re
  * result depends neither on its position in the list nor on the other gaps, and the session's own stream is not
  * advanced.  Several gaps may name one set.  randseed 0 takes the seed the session was created with.
  * Arena as for g2s_fill_batch.  G2S_ERR_ARG: a set id out of range, a gap with skip_if_prev_right_fuz_gt != -1;
- * G2S_ERR_STATE: lists in flight, or the session is in a team.  Always the host path (no resident mode). */
+ * G2S_ERR_STATE: lists in flight, or the session is in a team.  Groups of 256 gaps or more are finished on the device
+ * like any list (resident mode, G2S_RESIDENT=0|1 as for g2s_fill_batch): phase D3 in its restart form — every gap reads
+ * the stream from value 0, nothing is consumed; a group the device gives back takes the host path.  The timing of the
+ * call (g2s_session_last_timing) sums the groups', the resident counters included. */
 int g2s_fill_sets(g2s_session* s, const g2s_gap* gaps, const uint32_t* gap_set, size_t n, g2s_result* results,
                   char* fill_arena, size_t arena_cap);
 

@@ -50,13 +50,14 @@ def run_sets(sets, gaps, k):
     t1 = time.perf_counter()
     s = P.Session(g, 0, d_err=500, randseed=1)
     t2 = time.perf_counter()
-    res = s.fill_sets(gaps, list(range(len(gaps))))
+    res, tm = s.fill_sets(gaps, list(range(len(gaps))), want_timing=True)
     t3 = time.perf_counter()
     filled = sum(r.count > 0 for r in res)
     s.destroy()
     g.free()
     return dict(build_ms=(t1 - t0) * 1e3, session_ms=(t2 - t1) * 1e3, fill_ms=(t3 - t2) * 1e3,
-                gaps_per_s=len(gaps) / (t3 - t0), filled=filled)
+                resident_launches=tm.resident_launches, resident_fallbacks=tm.resident_fallbacks,
+                host_finished_gaps=tm.host_finished_gaps, gaps_per_s=len(gaps) / (t3 - t0), filled=filled)
 
 
 def run_loop(sets, gaps, k):
@@ -115,9 +116,10 @@ def run_shared(way, seqs, set_lists, shared, set_shared, gaps, k, reps):
         out["pool_build"] = P.test_last_pool_build()
     s = P.Session(g, 0, d_err=500, randseed=1)
     t0 = time.perf_counter()
-    res = s.fill_sets(gaps, list(range(len(gaps))))
+    res, tm = s.fill_sets(gaps, list(range(len(gaps))), want_timing=True)
     out.update(build_ms=min(times), build_ms_all=[round(t, 1) for t in times], fill_ms=(time.perf_counter() - t0) * 1e3,
-               filled=sum(r.count > 0 for r in res), kmers=g.num_kmers, peak_mb_end=peak_mb())
+               resident_launches=tm.resident_launches, resident_fallbacks=tm.resident_fallbacks,
+               host_finished_gaps=tm.host_finished_gaps, filled=sum(r.count > 0 for r in res), kmers=g.num_kmers, peak_mb_end=peak_mb())
     s.destroy()
     g.free()
     return out
