@@ -8,6 +8,7 @@
 #include <cstring>
 #include <functional>
 #include <thread>
+#include <unordered_set>
 
 namespace g2s {
 
@@ -21,7 +22,8 @@ bool graph_build_sets_gpu(Graph& g, const std::vector<std::pair<const char*, uin
                           const std::function<void(const std::vector<uint32_t>&, uint32_t)>& host_walk, std::string* why);
 bool graph_build_pool_gpu(Graph& g, const PoolSets& ps, int solid, int device,
                           const std::function<void(const std::vector<uint32_t>&, uint32_t)>& host_walk, PoolBuildInfo* info,
-                          std::string* why);
+                          std::string* why, const PoolReach* reach = nullptr, PoolReachInfo* rinfo = nullptr,
+                          bool* device_usable = nullptr);
 
 namespace {
 
@@ -470,8 +472,10 @@ void append_set_part(Graph& u, const Graph& p, uint64_t off) {
 }
 
 using SetSeqsFn = std::function<const std::vector<std::pair<const char*, uint64_t>>*(uint32_t, std::vector<std::pair<const char*, uint64_t>>*)>;
+// (own_part(s, mine, part): true when it built set s's part itself — a set with a reach record)
+using SetPartFn = std::function<bool(uint32_t, const std::vector<std::pair<const char*, uint64_t>>&, Graph*)>;
 Graph* build_sets_host(const SetSeqsFn& set_seqs, uint32_t nsets, int k, int solid, int nthreads,
-                       std::chrono::steady_clock::time_point t0, std::string* err);
+                       std::chrono::steady_clock::time_point t0, std::string* err, const SetPartFn* own_part = nullptr);
 
 }  // namespace
 
@@ -515,7 +519,7 @@ namespace {
 // The set graph on host threads, set by set: set_seqs(s, tmp) gives set s's (pointer, length) list (its own, or one
 // written into tmp, a list of the calling thread).
 Graph* build_sets_host(const SetSeqsFn& set_seqs, uint32_t nsets, int k, int solid, int nthreads,
-                       std::chrono::steady_clock::time_point t0, std::string* err) {
+                       std::chrono::steady_clock::time_point t0, std::string* err, const SetPartFn* own_part) {
   const int kb = kmer_width(k);
   std::vector<Graph*> parts(nsets, nullptr);
   {
@@ -527,7 +531,8 @@ Graph* build_sets_host(const SetSeqsFn& set_seqs, uint32_t nsets, int k, int sol
         if (s >= nsets) break;
         Graph* p = new Graph();
         const std::vector<std::pair<const char*, uint64_t>>& mine = *set_seqs(s, &tmp);
-        if (kb == 8) build_set_part<uint64_t>(mine, k, solid, p);
+        if (own_part && (*own_part)(s, mine, p)) {}
+        else if (kb == 8) build_set_part<uint64_t>(mine, k, solid, p);
         else if (kb == 16) build_set_part<u128>(mine, k, solid, p);
         else build_set_part<u256>(mine, k, solid, p);
         parts[s] = p;
@@ -589,16 +594,22 @@ PoolBuildInfo last_pool_build() {
   return g_pool_info;
 }
 
-Graph* graph_build_pool(const PoolSets& ps, int k, int solid, int nthreads, std::string* err) {
-  if (k < 1 || k > kMaxK) { if (err) *err = "k must be in [1," + std::to_string(kMaxK) + "]"; return nullptr; }
+static bool check_pool_sets(const PoolSets& ps, int k, std::string* err) {
+  if (k < 1 || k > kMaxK) { if (err) *err = "k must be in [1," + std::to_string(kMaxK) + "]"; return false; }
   const std::vector<std::pair<const char*, uint64_t>>& seqs = *ps.seqs;
-  if (ps.nsets == 0 || seqs.size() >= (1ull << 32)) { if (err) *err = "graph_build_pool: no sets, or 2^32 sequences or more"; return nullptr; }
+  if (ps.nsets == 0 || seqs.size() >= (1ull << 32)) { if (err) *err = "graph_build_pool: no sets, or 2^32 sequences or more"; return false; }
   for (uint32_t s = 0; s < ps.nsets; s++)
-    if (ps.set_begin[s + 1] < ps.set_begin[s]) { if (err) *err = "graph_build_pool: set_begin decreases at set " + std::to_string(s); return nullptr; }
+    if (ps.set_begin[s + 1] < ps.set_begin[s]) { if (err) *err = "graph_build_pool: set_begin decreases at set " + std::to_string(s); return false; }
   for (uint64_t q = ps.set_begin[0]; q < ps.set_begin[ps.nsets]; q++)
-    if (ps.set_seq[q] >= seqs.size()) { if (err) *err = "graph_build_pool: sequence index " + std::to_string(ps.set_seq[q]) + " out of range"; return nullptr; }
+    if (ps.set_seq[q] >= seqs.size()) { if (err) *err = "graph_build_pool: sequence index " + std::to_string(ps.set_seq[q]) + " out of range"; return false; }
   for (uint64_t x = 0; x < ps.nshared; x++)
-    if (ps.shared_seq[x] >= seqs.size()) { if (err) *err = "graph_build_pool: shared sequence index " + std::to_string(ps.shared_seq[x]) + " out of range"; return nullptr; }
+    if (ps.shared_seq[x] >= seqs.size()) { if (err) *err = "graph_build_pool: shared sequence index " + std::to_string(ps.shared_seq[x]) + " out of range"; return false; }
+  return true;
+}
+
+Graph* graph_build_pool(const PoolSets& ps, int k, int solid, int nthreads, std::string* err) {
+  if (!check_pool_sets(ps, k, err)) return nullptr;
+  const std::vector<std::pair<const char*, uint64_t>>& seqs = *ps.seqs;
   // a set's expanded list: pointers only, no text moves
   auto expand = [&](uint32_t s, std::vector<std::pair<const char*, uint64_t>>* out) {
     out->clear();
@@ -653,6 +664,253 @@ Graph* graph_build_pool(const PoolSets& ps, int k, int solid, int nthreads, std:
     std::lock_guard<std::mutex> lk(g_pool_info_mu);
     g_pool_info = info;
   }
+  return g;
+}
+
+// ---- pooled set graphs bounded by reach records (dbg.hpp: PoolReach) ---------------------------------
+namespace {
+
+std::mutex g_reach_info_mu;
+PoolReachInfo g_reach_info;
+
+template <class KT>
+struct KmerHasher {
+  size_t operator()(const KT& x) const { return (size_t)KmerOps<KT>::hash(x); }
+};
+
+// the canonical k-mers of a list of sequences as a sorted (k-mer, copies) table
+template <class KT>
+struct CountTable {
+  std::vector<KT> key;
+  std::vector<uint32_t> cnt;
+  void build(const std::vector<std::pair<const char*, uint64_t>>& seqs, int k) {
+    std::vector<KT> all;
+    for (auto& s : seqs) {
+      KmerRoller<KT> r(k);
+      for (uint64_t i = 0; i < s.second; i++)
+        if (r.push(s.first[i])) all.push_back(r.canonical());
+    }
+    std::sort(all.begin(), all.end());
+    for (size_t i = 0; i < all.size();) {
+      size_t j = i + 1;
+      while (j < all.size() && all[j] == all[i]) j++;
+      key.push_back(all[i]);
+      cnt.push_back((uint32_t)std::min<size_t>(j - i, 0xFFFFFFFFu));
+      i = j;
+    }
+  }
+  uint64_t count(const KT& x) const {
+    auto it = std::lower_bound(key.begin(), key.end(), x);
+    return (it != key.end() && *it == x) ? cnt[(size_t)(it - key.begin())] : 0;
+  }
+};
+
+// One set with a reach record on one host thread: a breadth-first search from the seeds over the implicit full graph
+// (a k-mer is in it when its copies in the own table and, for a flagged set, in the shared table reach `solid`); the
+// full graph is never formed.  full != nullptr: its k-mers are counted (a pass over the two tables).
+template <class KT>
+void build_reach_part(const std::vector<std::pair<const char*, uint64_t>>& own_seqs, const CountTable<KT>* shared,
+                      const char* const* seeds, uint64_t nseeds, int32_t radius, int k, int solid, Graph* part, uint64_t* full,
+                      uint32_t* levels) {
+  part->k = k;
+  part->solid = solid;
+  part->kmer_bytes = kmer_width(k);
+  const uint64_t so = (uint64_t)std::max(1, solid);
+  CountTable<KT> own;
+  own.build(own_seqs, k);
+  auto member = [&](const KT& x) { return own.count(x) + (shared ? shared->count(x) : 0) >= so; };
+  std::unordered_set<KT, KmerHasher<KT>> seen;
+  std::vector<KT> frontier, next;
+  for (uint64_t i = 0; i < nseeds; i++) {
+    KT c;
+    int strand;
+    encode_kmer<KT>(seeds[i], k, &c, &strand);
+    if (member(c) && seen.insert(c).second) frontier.push_back(c);
+  }
+  const KT mask = KmerOps<KT>::mask(k);
+  uint32_t level = 0;
+  while (!frontier.empty() && (int64_t)level < (int64_t)radius) {
+    next.clear();
+    for (const KT& c : frontier) {
+      const KT rc = KmerOps<KT>::revcomp(c, k);
+      for (int strand = 0; strand < 2; strand++) {
+        const KT seq = strand == 0 ? c : rc, rseq = strand == 0 ? rc : c;
+        for (int nt = 0; nt < 4; nt++) {
+          const KT y = ((seq << 2) | (KT)nt) & mask;
+          const KT ry = (rseq >> 2) | ((KT)(nt ^ 2) << (2 * (k - 1)));
+          const KT x = y < ry ? y : ry;
+          if (seen.count(x) || !member(x)) continue;
+          seen.insert(x);
+          next.push_back(x);
+        }
+      }
+    }
+    if (next.empty()) break;
+    level++;
+    frontier.swap(next);
+  }
+  *levels = level;
+  std::vector<KT>& keep = kmer_vec<KT>(*part);
+  keep.assign(seen.begin(), seen.end());
+  std::sort(keep.begin(), keep.end());
+  part->n = keep.size();
+  if (full) {
+    uint64_t f = 0;
+    for (size_t i = 0; i < own.key.size(); i++) f += member(own.key[i]) ? 1 : 0;
+    if (shared)
+      for (size_t u = 0; u < shared->key.size(); u++)
+        if (shared->cnt[u] >= so && own.count(shared->key[u]) == 0) f++;
+    *full = f;
+  }
+  int bits = 1;
+  while (bits < 22 && (1ull << bits) < part->n) bits++;
+  build_bucket_index<KT>(*part, bits);
+  finish_graph_host<KT>(*part, 1);
+}
+
+template <class KT>
+Graph* build_pool_reach_host(const PoolSets& ps, const PoolReach& reach, int k, int solid, int nthreads, bool count_full,
+                             std::chrono::steady_clock::time_point t0, PoolReachInfo* rinfo, std::string* err) {
+  const std::vector<std::pair<const char*, uint64_t>>& seqs = *ps.seqs;
+  CountTable<KT> shared;  // built once, for the flagged sets with a record
+  bool want_shared = false;
+  for (uint32_t s = 0; s < ps.nsets; s++) want_shared = want_shared || (reach.has(s) && ps.flagged(s));
+  if (want_shared) {
+    std::vector<std::pair<const char*, uint64_t>> sh;
+    for (uint64_t x = 0; x < ps.nshared; x++) sh.push_back(seqs[ps.shared_seq[x]]);
+    shared.build(sh, k);
+  }
+  std::vector<uint64_t> full(ps.nsets, 0), kept(ps.nsets, 0);
+  std::vector<uint32_t> levels(ps.nsets, 0);
+  const SetPartFn own_part = [&](uint32_t s, const std::vector<std::pair<const char*, uint64_t>>&, Graph* part) -> bool {
+    if (!reach.has(s)) return false;
+    std::vector<std::pair<const char*, uint64_t>> own;
+    for (uint64_t q = ps.set_begin[s]; q < ps.set_begin[s + 1]; q++) own.push_back(seqs[ps.set_seq[q]]);
+    build_reach_part<KT>(own, ps.flagged(s) ? &shared : nullptr, reach.seed.data() + reach.seed_begin[s],
+                         reach.seed_begin[s + 1] - reach.seed_begin[s], reach.radius[s], k, solid, part,
+                         count_full ? &full[s] : nullptr, &levels[s]);
+    kept[s] = part->n;
+    return true;
+  };
+  auto expand = [&](uint32_t s, std::vector<std::pair<const char*, uint64_t>>* out) {
+    out->clear();
+    if (reach.has(s)) return out;  // (own_part reads the lists itself)
+    for (uint64_t q = ps.set_begin[s]; q < ps.set_begin[s + 1]; q++) out->push_back(seqs[ps.set_seq[q]]);
+    if (ps.flagged(s))
+      for (uint64_t x = 0; x < ps.nshared; x++) out->push_back(seqs[ps.shared_seq[x]]);
+    return out;
+  };
+  Graph* g = build_sets_host([&](uint32_t s, std::vector<std::pair<const char*, uint64_t>>* tmp) { return expand(s, tmp); }, ps.nsets, k,
+                             solid, nthreads, t0, err, &own_part);
+  for (uint32_t s = 0; s < ps.nsets; s++) {
+    if (!reach.has(s)) continue;
+    rinfo->reach_sets++;
+    rinfo->full_kmers += full[s];
+    rinfo->kept_kmers += kept[s];
+    rinfo->levels = std::max(rinfo->levels, levels[s]);
+  }
+  rinfo->full_known = count_full ? 1 : 0;
+  rinfo->on_device = 0;
+  return g;
+}
+
+// a graph of one set as the ordinary graph the pooled builds give for nsets == 1
+template <class KT>
+void collapse_to_one_set(Graph& g) {
+  g.set_lo.clear();
+  build_bucket_index<KT>(g);
+}
+
+}  // namespace
+
+PoolReachInfo last_pool_reach() {
+  std::lock_guard<std::mutex> lk(g_reach_info_mu);
+  return g_reach_info;
+}
+
+Graph* graph_build_pool_reach(const PoolSets& ps_in, const PoolReach& reach_in, int k, int solid, int nthreads, std::string* err) {
+  if (!reach_in.any()) return graph_build_pool(ps_in, k, solid, nthreads, err);
+  if (!check_pool_sets(ps_in, k, err)) return nullptr;
+  if (reach_in.radius.size() != ps_in.nsets || reach_in.seed_begin.size() != (size_t)ps_in.nsets + 1) {
+    if (err) *err = "graph_build_pool_reach: a reach record per set missing";
+    return nullptr;
+  }
+  // one set: built as two (the second empty, without a record) and handed back as an ordinary graph
+  PoolSets ps = ps_in;
+  PoolReach reach1;
+  std::vector<uint64_t> begin2;
+  std::vector<uint8_t> shared2;
+  const bool one = ps_in.nsets == 1;
+  if (one) {
+    begin2 = {ps_in.set_begin[0], ps_in.set_begin[1], ps_in.set_begin[1]};
+    shared2 = {(uint8_t)(ps_in.flagged(0) ? 1 : 0), 0};
+    ps.set_begin = begin2.data();
+    ps.set_shared = shared2.data();
+    ps.nsets = 2;
+    reach1 = reach_in;
+    reach1.radius.push_back(-1);
+    reach1.seed_begin.push_back(reach1.seed_begin.back());
+  }
+  const PoolReach& reach = one ? reach1 : reach_in;
+  if (nthreads <= 0) nthreads = (int)std::max(1u, std::thread::hardware_concurrency());
+  const auto t0 = std::chrono::steady_clock::now();
+  const std::vector<std::pair<const char*, uint64_t>>& seqs = *ps.seqs;
+  const int kb = kmer_width(k);
+  PoolBuildInfo info;
+  PoolReachInfo rinfo;
+  Graph* g = nullptr;
+  bool device_gave_up = false;
+  if (!getenv("G2S_HOST_BUILD")) {
+    g = new Graph();
+    g->k = k;
+    g->solid = solid;
+    g->kmer_bytes = kb;
+    std::string why;
+    const bool ok = graph_build_pool_gpu(*g, ps, solid, getenv("G2S_DEVICE") ? atoi(getenv("G2S_DEVICE")) : 0,
+                                         [&](const std::vector<uint32_t>& succ_r, uint32_t first_id) {
+                                           unitig_order(succ_r, g->n, false, &g->rank2id, &g->flip, &g->n_unitigs, true, first_id);
+                                         }, &info, &why, &reach, &rinfo, &device_gave_up);
+    if (ok) {
+      if (getenv("G2S_DEBUG"))
+        fprintf(stderr, "[g2s] pooled set graph build: %u sets, %llu k-mers, %llu own + %llu shared positions, %llu keys sorted, %.3f s on the GPU; "
+                        "reach: %llu sets, %llu k-mers kept, %u levels\n",
+                ps_in.nsets, (unsigned long long)g->n, (unsigned long long)info.own_positions, (unsigned long long)info.shared_positions,
+                (unsigned long long)info.keys_sorted, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(),
+                (unsigned long long)rinfo.reach_sets, (unsigned long long)rinfo.kept_kmers, rinfo.levels);
+      info.on_device = 1;
+    } else {
+      if (getenv("G2S_DEBUG")) fprintf(stderr, "[g2s]   pooled set graph on the host (%s)\n", why.c_str());
+      // (device_gave_up: the build got as far as selecting the device — not even k, not a machine without one)
+      delete g;
+      g = nullptr;
+    }
+  }
+  if (!g) {
+    info = PoolBuildInfo();
+    rinfo = PoolReachInfo();
+    uint64_t whole = 0, bounded = 0;  // flagged sets without / with a record
+    for (uint32_t s = 0; s < ps.nsets; s++)
+      if (ps.flagged(s)) (reach.has(s) ? bounded : whole)++;
+    for (uint64_t q = ps.set_begin[0]; q < ps.set_begin[ps.nsets]; q++) info.own_positions += seqs[ps.set_seq[q]].second + 1;
+    if (whole + bounded)
+      for (uint64_t x = 0; x < ps.nshared; x++) info.shared_positions += seqs[ps.shared_seq[x]].second + 1;
+    info.keys_sorted = info.own_positions + (whole + (bounded ? 1 : 0)) * info.shared_positions;  // (the shared table: once)
+    if (kb == 8) g = build_pool_reach_host<uint64_t>(ps, reach, k, solid, nthreads, !device_gave_up, t0, &rinfo, err);
+    else if (kb == 16) g = build_pool_reach_host<u128>(ps, reach, k, solid, nthreads, !device_gave_up, t0, &rinfo, err);
+    else g = build_pool_reach_host<u256>(ps, reach, k, solid, nthreads, !device_gave_up, t0, &rinfo, err);
+    if (!g) return nullptr;
+  }
+  if (one) {
+    if (kb == 8) collapse_to_one_set<uint64_t>(*g);
+    else if (kb == 16) collapse_to_one_set<u128>(*g);
+    else collapse_to_one_set<u256>(*g);
+  }
+  {
+    std::lock_guard<std::mutex> lk(g_pool_info_mu);
+    g_pool_info = info;
+  }
+  std::lock_guard<std::mutex> lk(g_reach_info_mu);
+  g_reach_info = rinfo;
   return g;
 }
 

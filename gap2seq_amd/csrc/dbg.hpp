@@ -132,6 +132,30 @@ struct PoolBuildInfo {
   int on_device = 0;
 };
 PoolBuildInfo last_pool_build();
+// Reach records of a pooled build (g2s_graph_build_pool_reach): set s with radius[s] >= 0 keeps, of its full graph, only
+// the k-mers within radius[s] undirected steps (canonical k-mers, the eight neighbours of each) of one of its seeds —
+// seed[seed_begin[s] .. seed_begin[s+1]), each k characters encoded as the fill's flank look-ups encode them
+// (Graph::node_of_in).  A seed outside the full graph is ignored; a set whose seeds are all outside it is empty.
+// radius[s] < 0: the whole set.
+struct PoolReach {
+  std::vector<int32_t> radius;        // [nsets]
+  std::vector<uint64_t> seed_begin;   // [nsets + 1]
+  std::vector<const char*> seed;      // [seed_begin[nsets]]
+  bool has(uint32_t s) const { return s < radius.size() && radius[s] >= 0; }
+  bool any() const { for (int32_t r : radius) if (r >= 0) return true; return false; }
+};
+Graph* graph_build_pool_reach(const PoolSets& ps, const PoolReach& reach, int k, int solid, int nthreads, std::string* err);
+// What the process's last graph_build_pool_reach with a reach record did (g2s_test_last_pool_reach): the sets with a
+// record, the k-mers of their full graphs (full_known == 0: not counted — the device build never forms them, and the
+// host build does not count them behind a device build that gave up), the k-mers kept, the deepest level a set's
+// search ran, and whether the search ran on the device.
+struct PoolReachInfo {
+  uint64_t reach_sets = 0, full_kmers = 0, kept_kmers = 0;
+  int full_known = 0;
+  uint32_t levels = 0;
+  int on_device = 0;
+};
+PoolReachInfo last_pool_reach();
 bool graph_save(const Graph& g, const std::string& path, std::string* err);
 Graph* graph_load(const std::string& path, std::string* err);
 

@@ -538,6 +538,195 @@ __global__ void k_pool_write_shared(const KT* __restrict__ hkey, uint32_t U, con
   out_sid[pos] = s;
 }
 
+// ---- reach sets of a pooled build (dbg.hpp: PoolReach): the k-mers of a set within `radius` undirected steps of its
+// seeds, by a breadth-first search over the IMPLICIT full graph — a k-mer is in set s when its copies in the set's own
+// runs plus, for a flagged set, in the shared table reach `solid`: two binary searches, as in k_pool_keep_shared /
+// k_pool_keep_own.  Persistent workgroups draw sets from a ticket (one atomic add a claim); a set is searched by one
+// workgroup from its seeds to its last level, so levels are separated by workgroup barriers only and no workgroup
+// waits for another.  lane = (frontier k-mer, neighbour): 32 k-mers a step.  A k-mer is claimed by atomicOr on its
+// bit — one bit per own run, one per (flagged set with a record, shared entry); the shared bit names a k-mer that is in
+// both tables.  Claimed k-mers are staged in LDS and leave for the queue in device memory in chunks (one atomic add on
+// the queue's fill a chunk); a level's chunks are the next level's frontier, read back from the queue, and the queue
+// at the end holds every kept (k-mer, set) once.  Nothing is written past a buffer: a chunk that would not fit the
+// queue, or the chunk list of a level, raises the overflow word instead and the search stops at the next ticket.
+constexpr uint32_t kReachThreads = 256;
+constexpr uint32_t kReachStage = 1024;   // k-mers staged in LDS before they leave as one chunk
+constexpr uint32_t kReachChunks = 512;   // chunks of one level of one set
+struct ReachArgs {
+  const uint32_t* rsets;    // [R] the sets with a record
+  const int32_t* radius;    // [R]
+  const uint32_t* seed_lo;  // [R + 1] into the seeds
+  const uint32_t* set_fr;   // [nsets] the set's row in the shared bitmap (flagged, with a record), else INV
+  const uint32_t* run_lo;   // [nsets + 1]
+  const uint32_t* rcnt;     // [nruns]
+  const uint32_t* hcnt;     // [U]
+  uint32_t* own_bits;       // [(nruns + 31) / 32]
+  uint32_t* sh_bits;        // [rows * W]
+  uint32_t* out_set;        // [Q]
+  uint32_t* ctl;            // ticket, queue fill, overflow, deepest level
+  uint32_t U, W, R, Q, solid;
+  int k;
+};
+enum { kReachTicket = 0, kReachFill = 1, kReachOverflow = 2, kReachLevels = 3 };
+enum : uint32_t { kReachQueueFull = 1u, kReachChunkListFull = 2u };  // bits of the overflow word
+
+template <class KT>
+__device__ __forceinline__ bool d_reach_claim(const ReachArgs& a, const KT* __restrict__ rkey, const KT* __restrict__ hkey, uint32_t s,
+                                              uint32_t fr, const KT& x) {
+  uint64_t cnt = 0;
+  uint32_t u = 0;
+  bool in_sh = false;
+  if (fr != INV) {
+    u = d_lower_bound<KT>(hkey, 0u, a.U, x);
+    in_sh = u < a.U && hkey[u] == x;
+    if (in_sh) cnt = a.hcnt[u];
+  }
+  const uint32_t hi = a.run_lo[s + 1], r = d_lower_bound<KT>(rkey, a.run_lo[s], hi, x);
+  const bool in_own = r < hi && rkey[r] == x;
+  if (in_own) cnt += a.rcnt[r];
+  if ((!in_sh && !in_own) || cnt < (uint64_t)a.solid) return false;
+  uint32_t* word = in_sh ? a.sh_bits + (size_t)fr * a.W + (u >> 5) : a.own_bits + (r >> 5);
+  const uint32_t bit = 1u << ((in_sh ? u : r) & 31u);
+  return (atomicOr(word, bit) & bit) == 0u;
+}
+
+template <class KT>
+__global__ __launch_bounds__(256) void k_reach_bfs(ReachArgs a, const KT* __restrict__ rkey, const KT* __restrict__ hkey,
+                                                   const KT* __restrict__ seeds, KT* __restrict__ out_key) {
+  __shared__ __attribute__((aligned(16))) uint64_t stage_words[kReachStage * (sizeof(KT) / 8)];  // (u256 has constructors)
+  KT* stage = (KT*)stage_words;
+  __shared__ uint2 chunks[2][kReachChunks];
+  __shared__ uint32_t n_stage, n_chunk[2], sh_r, sh_stop, sh_base;
+  const uint32_t tid = threadIdx.x;
+  const int k = a.k;
+  const KT mask = (2 * k >= (int)(8 * sizeof(KT))) ? ~(KT)0 : ((((KT)1) << (2 * k)) - 1);
+  for (;;) {
+    __syncthreads();  // (the last set's reads of the words below are over)
+    if (tid == 0) {
+      sh_stop = atomicAdd(&a.ctl[kReachOverflow], 0u);
+      sh_r = atomicAdd(&a.ctl[kReachTicket], 1u);
+      n_stage = 0u;
+      n_chunk[0] = 0u;
+      n_chunk[1] = 0u;
+    }
+    __syncthreads();
+    const uint32_t r = sh_r;
+    if (r >= a.R || sh_stop) return;
+    const uint32_t s = a.rsets[r], fr = a.set_fr[s];
+    const uint32_t radius = (uint32_t)a.radius[r];
+    // the staged k-mers leave as one chunk of level list `list`; false: no room (the overflow word is up)
+    auto flush = [&](uint32_t list) -> bool {
+      __syncthreads();
+      const uint32_t n = n_stage;
+      __syncthreads();
+      if (n == 0u) return true;
+      if (tid == 0) {
+        const uint32_t base = atomicAdd(&a.ctl[kReachFill], n);
+        // (after an overflow other workgroups may add to the fill once more each before they see the word at their next
+        // ticket; should the 32-bit fill ever wrap, a later chunk lands inside the queue again — in bounds, and the
+        // overflow word stays up, so the host discards all of it)
+        const bool fits = (uint64_t)base + n <= (uint64_t)a.Q, listed = n_chunk[list] < kReachChunks;
+        const bool ok = fits && listed;
+        if (ok) chunks[list][n_chunk[list]++] = make_uint2(base, n);
+        else atomicOr(&a.ctl[kReachOverflow], fits ? kReachChunkListFull : kReachQueueFull);
+        sh_base = ok ? base : INV;
+        n_stage = 0u;
+      }
+      __syncthreads();
+      const uint32_t base = sh_base;
+      if (base == INV) return false;
+      for (uint32_t i = tid; i < n; i += kReachThreads) {
+        out_key[(size_t)base + i] = stage[i];
+        a.out_set[(size_t)base + i] = s;
+      }
+      __threadfence_block();
+      __syncthreads();
+      return true;
+    };
+    // room for one step's claims (at most one a lane) before the step
+    auto room = [&](uint32_t list) -> bool {
+      __syncthreads();
+      const uint32_t n = n_stage;
+      __syncthreads();
+      return n + kReachThreads <= kReachStage ? true : flush(list);
+    };
+    bool ok = true;
+    // level 0: the seeds that are k-mers of the set
+    const uint32_t s_lo = a.seed_lo[r], s_hi = a.seed_lo[r + 1];
+    for (uint32_t i0 = s_lo; ok && i0 < s_hi; i0 += kReachThreads) {
+      ok = room(0u);
+      if (!ok) break;
+      if (i0 + tid < s_hi) {
+        const KT x = seeds[i0 + tid];
+        if (d_reach_claim<KT>(a, rkey, hkey, s, fr, x)) stage[atomicAdd(&n_stage, 1u)] = x;
+      }
+    }
+    ok = ok && flush(0u);
+    uint32_t cur = 0u, level = 0u;
+    while (ok && n_chunk[cur] > 0u && level < radius) {
+      const uint32_t nxt = cur ^ 1u, nc = n_chunk[cur];
+      __syncthreads();
+      if (tid == 0) n_chunk[nxt] = 0u;
+      for (uint32_t c = 0; ok && c < nc; c++) {
+        const uint2 ch = chunks[cur][c];
+        for (uint32_t i0 = 0; i0 < ch.y; i0 += kReachThreads / 8u) {
+          ok = room(nxt);
+          if (!ok) break;
+          const uint32_t item = i0 + (tid >> 3);
+          if (item < ch.y) {
+            const KT km = out_key[(size_t)ch.x + item], rc = d_revcomp(km, k);
+            const uint32_t strand = (tid >> 2) & 1u, nt = tid & 3u;
+            const KT seq = strand ? rc : km, rseq = strand ? km : rc;
+            const KT y = ((seq << 2) | (KT)nt) & mask;
+            const KT ry = (rseq >> 2) | ((KT)(nt ^ 2u) << (2 * (k - 1)));
+            const KT x = y < ry ? y : ry;
+            if (d_reach_claim<KT>(a, rkey, hkey, s, fr, x)) stage[atomicAdd(&n_stage, 1u)] = x;
+          }
+        }
+      }
+      ok = ok && flush(nxt);
+      if (!ok || n_chunk[nxt] == 0u) break;
+      level++;
+      cur = nxt;
+    }
+    if (ok && tid == 0) atomicMax(&a.ctl[kReachLevels], level);
+  }
+}
+// the run table with the sets with a record replaced by what their searches kept: every set's new run count ...
+__global__ void k_reach_set_count(const uint32_t* __restrict__ run_lo, const uint32_t* __restrict__ set_ridx,
+                                  const uint32_t* __restrict__ vis_lo, uint32_t nsets, uint32_t* __restrict__ cnt) {
+  const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s > nsets) return;
+  cnt[s] = s == nsets ? 0u : set_ridx[s] != INV ? vis_lo[s + 1] - vis_lo[s] : run_lo[s + 1] - run_lo[s];
+}
+// ... the runs of the sets without a record, copied ...
+template <class KT>
+__global__ void k_reach_copy_runs(const KT* __restrict__ rkey, const uint32_t* __restrict__ rset, const uint32_t* __restrict__ rcnt,
+                                  uint32_t nruns, const uint32_t* __restrict__ set_ridx, const uint32_t* __restrict__ run_lo,
+                                  const uint32_t* __restrict__ new_lo, KT* __restrict__ nkey, uint32_t* __restrict__ nset,
+                                  uint32_t* __restrict__ ncnt) {
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= nruns) return;
+  const uint32_t s = rset[j];
+  if (set_ridx[s] != INV) return;
+  const uint32_t d = new_lo[s] + (j - run_lo[s]);
+  nkey[d] = rkey[j];
+  nset[d] = s;
+  ncnt[d] = rcnt[j];
+}
+// ... and the kept k-mers (sorted by (set, k-mer)) as runs of `solid` copies: the merge keeps them as they are
+template <class KT>
+__global__ void k_reach_copy_kept(const KT* __restrict__ sk, const uint32_t* __restrict__ ss, uint32_t n,
+                                  const uint32_t* __restrict__ vis_lo, const uint32_t* __restrict__ new_lo, uint32_t solid,
+                                  KT* __restrict__ nkey, uint32_t* __restrict__ nset, uint32_t* __restrict__ ncnt) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t s = ss[i], d = new_lo[s] + (i - vis_lo[s]);
+  nkey[d] = sk[i];
+  nset[d] = s;
+  ncnt[d] = solid;
+}
+
 struct Dev {
   void* p = nullptr;
   ~Dev() { if (p) (void)hipFree(p); }
@@ -1058,7 +1247,8 @@ bool graph_build_sets_gpu(Graph& g, const std::vector<std::pair<const char*, uin
 // tables are merged per set into the (set, k-mer) order the rest of the build wants.  info: positions and keys sorted.
 template <class KT>
 static bool count_solid_pool_gpu_t(Graph& g, std::vector<KT>& out, std::vector<uint32_t>* rank_set, const PoolSets& ps, int solid,
-                                   int device, PoolBuildInfo* info, std::string* why) {
+                                   int device, PoolBuildInfo* info, std::string* why, const PoolReach* reach, PoolReachInfo* rinfo,
+                                   bool* device_usable) {
 #define G2S_GPU_TRY(expr)                                                                 \
   do {                                                                                    \
     hipError_t e_ = (expr);                                                               \
@@ -1077,6 +1267,7 @@ static bool count_solid_pool_gpu_t(Graph& g, std::vector<KT>& out, std::vector<u
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) { if (why) *why = "no device"; return false; }
   G2S_GPU_TRY(hipSetDevice(device));
+  if (device_usable) *device_usable = true;  // (a failure from here on is the device build giving up, not its absence)
   const int k = g.k;
   const std::vector<std::pair<const char*, uint64_t>>& seqs = *ps.seqs;
   const uint32_t nsets = ps.nsets;
@@ -1098,7 +1289,7 @@ static bool count_solid_pool_gpu_t(Graph& g, std::vector<KT>& out, std::vector<u
     }
     if (ps.flagged(s)) { set_fidx[s] = (uint32_t)fset.size(); fset.push_back(s); }
   }
-  const uint32_t F = (uint32_t)fset.size();
+  uint32_t F = (uint32_t)fset.size();
   if (F)
     for (uint64_t x = 0; x < ps.nshared; x++) {
       sh_seq.push_back(use(ps.shared_seq[x]));
@@ -1225,6 +1416,152 @@ static bool count_solid_pool_gpu_t(Graph& g, std::vector<KT>& out, std::vector<u
     G2S_GPU_TRY(d_hkey.alloc(0));
     G2S_GPU_TRY(d_hcnt.alloc(0));
   }
+  // ---- the sets with a reach record (dbg.hpp: PoolReach): a bounded search per set over the two tables; what it kept
+  // replaces those sets' runs (as runs of `solid` copies) and the sets lose their flag, so that the merge below keeps
+  // exactly the kept k-mers for them and its flagged sets x shared k-mers items are those of the sets without a record
+  if (reach && reach->any()) {
+    const uint32_t so = (uint32_t)std::max(1, solid);
+    std::vector<uint32_t> rsets, set_ridx(nsets, INV), set_fr(nsets, INV), seed_lo(1, 0), run_lo((size_t)nsets + 1);
+    std::vector<int32_t> radius;
+    std::vector<KT> seeds;
+    uint32_t rows = 0;
+    G2S_GPU_TRY(hipMemcpy(run_lo.data(), d_rlo.p, run_lo.size() * 4, hipMemcpyDeviceToHost));
+    uint64_t upper = 0, own_rec = 0;  // the k-mers the searches can visit at most; the own runs among them
+    for (uint32_t s = 0; s < nsets; s++) {
+      if (!reach->has(s)) continue;
+      set_ridx[s] = (uint32_t)rsets.size();
+      rsets.push_back(s);
+      radius.push_back(reach->radius[s]);
+      if (set_fidx[s] != INV && U) set_fr[s] = rows++;
+      own_rec += (uint64_t)(run_lo[s + 1] - run_lo[s]);
+      upper += (uint64_t)(run_lo[s + 1] - run_lo[s]) + (set_fr[s] != INV ? U : 0u);
+      for (uint64_t q = reach->seed_begin[s]; q < reach->seed_begin[s + 1]; q++) {
+        KT c;
+        int strand;
+        encode_kmer<KT>(reach->seed[(size_t)q], k, &c, &strand);
+        seeds.push_back(c);
+      }
+      if (seeds.size() >= (1ull << 32)) { if (why) *why = "reach: 2^32 seeds or more"; return false; }
+      seed_lo.push_back((uint32_t)seeds.size());
+    }
+    const uint32_t R = (uint32_t)rsets.size(), W = (U + 31u) / 32u;
+    const size_t own_words = ((size_t)nruns + 31) / 32, sh_words = (size_t)rows * W;
+    G2S_GPU_TRY(hipMemGetInfo(&free_b, &total_b));
+    // (a queued k-mer: the queue, then the sort of count_solid_sets_gpu_t over what was queued; the bitmaps beside it)
+    const double per_item = (double)(2 * sizeof(KT) + 56), bitmap_bytes = (double)(own_words + sh_words) * 4.0;
+    if (bitmap_bytes > 0.25 * (double)free_b) { if (why) *why = "reach: visited bitmaps too large for the device"; return false; }
+    // The queue is sized by what the searches can plausibly keep, not by sets x shared k-mers: the own runs of the sets
+    // with a record plus kReachShare k-mers a set; when it overflows it is made four times as large and the searches
+    // run again (bitmaps cleared), up to `cap`: what the sets could hold at most, what fits half the free memory, 2^31 - 1.
+    // (G2S_REACH_QUEUE_CAP: the tests make the queue small, and final, to take the overflow path)
+    constexpr uint64_t kReachShare = 4096;
+    uint64_t cap = std::min<uint64_t>(std::max<uint64_t>(upper, 1), (1ull << 31) - 1);
+    cap = std::min<uint64_t>(cap, (uint64_t)std::max(1.0, (0.5 * (double)free_b - bitmap_bytes) / per_item));
+    if (getenv("G2S_REACH_QUEUE_CAP")) cap = std::min<uint64_t>(cap, (uint64_t)std::max(1ll, atoll(getenv("G2S_REACH_QUEUE_CAP"))));
+    uint64_t Q = std::min<uint64_t>(cap, own_rec + kReachShare * (uint64_t)rsets.size());
+    const size_t own_bytes = std::max<size_t>(own_words * 4, 16), sh_bytes = std::max<size_t>(sh_words * 4, 16);
+    Dev d_rsets, d_radius, d_seedlo, d_setfr, d_ridx, d_seeds, d_ownb, d_shb, d_qkey, d_qset, d_ctl;
+    G2S_GPU_TRY(d_rsets.alloc((size_t)R * 4));
+    G2S_GPU_TRY(d_radius.alloc((size_t)R * 4));
+    G2S_GPU_TRY(d_seedlo.alloc(((size_t)R + 1) * 4));
+    G2S_GPU_TRY(d_setfr.alloc((size_t)nsets * 4));
+    G2S_GPU_TRY(d_ridx.alloc((size_t)nsets * 4));
+    G2S_GPU_TRY(d_seeds.alloc(seeds.size() * sizeof(KT)));
+    G2S_GPU_TRY(d_ownb.alloc(own_bytes));
+    G2S_GPU_TRY(d_shb.alloc(sh_bytes));
+    G2S_GPU_TRY(d_ctl.alloc(16));
+    G2S_GPU_TRY(hipMemcpy(d_rsets.p, rsets.data(), (size_t)R * 4, hipMemcpyHostToDevice));
+    G2S_GPU_TRY(hipMemcpy(d_radius.p, radius.data(), (size_t)R * 4, hipMemcpyHostToDevice));
+    G2S_GPU_TRY(hipMemcpy(d_seedlo.p, seed_lo.data(), ((size_t)R + 1) * 4, hipMemcpyHostToDevice));
+    G2S_GPU_TRY(hipMemcpy(d_setfr.p, set_fr.data(), (size_t)nsets * 4, hipMemcpyHostToDevice));
+    G2S_GPU_TRY(hipMemcpy(d_ridx.p, set_ridx.data(), (size_t)nsets * 4, hipMemcpyHostToDevice));
+    if (!seeds.empty()) G2S_GPU_TRY(hipMemcpy(d_seeds.p, seeds.data(), seeds.size() * sizeof(KT), hipMemcpyHostToDevice));
+    ReachArgs ra;
+    ra.rsets = (const uint32_t*)d_rsets.p;
+    ra.radius = (const int32_t*)d_radius.p;
+    ra.seed_lo = (const uint32_t*)d_seedlo.p;
+    ra.set_fr = (const uint32_t*)d_setfr.p;
+    ra.run_lo = (const uint32_t*)d_rlo.p;
+    ra.rcnt = (const uint32_t*)d_rcnt.p;
+    ra.hcnt = (const uint32_t*)d_hcnt.p;
+    ra.own_bits = (uint32_t*)d_ownb.p;
+    ra.sh_bits = (uint32_t*)d_shb.p;
+    ra.ctl = (uint32_t*)d_ctl.p;
+    ra.U = U; ra.W = W; ra.R = R; ra.solid = so; ra.k = k;
+    uint32_t ctl[4] = {0, 0, 0, 0};
+    for (;;) {
+      G2S_GPU_TRY(d_qkey.alloc((size_t)Q * sizeof(KT)));
+      G2S_GPU_TRY(d_qset.alloc((size_t)Q * 4));
+      G2S_GPU_TRY(hipMemset(d_ownb.p, 0, own_bytes));
+      G2S_GPU_TRY(hipMemset(d_shb.p, 0, sh_bytes));
+      G2S_GPU_TRY(hipMemset(d_ctl.p, 0, 16));
+      ra.out_set = (uint32_t*)d_qset.p;
+      ra.Q = (uint32_t)Q;
+      hipLaunchKernelGGL(k_reach_bfs<KT>, dim3(std::min<uint32_t>(R, 1024u)), dim3(kReachThreads), 0, 0, ra, (const KT*)d_rkey.p,
+                         (const KT*)d_hkey.p, (const KT*)d_seeds.p, (KT*)d_qkey.p);
+      G2S_GPU_TRY(hipGetLastError());
+      G2S_GPU_TRY(hipMemcpy(ctl, d_ctl.p, 16, hipMemcpyDeviceToHost));
+      if (!ctl[kReachOverflow]) break;
+      if ((ctl[kReachOverflow] & kReachChunkListFull) || Q >= cap) {
+        if (why) *why = "reach: the search's queue of " + std::to_string(Q) + " k-mers (or a level's chunk list) overflowed";
+        return false;
+      }
+      if (getenv("G2S_DEBUG"))
+        fprintf(stderr, "[g2s]   reach: the queue of %llu k-mers overflowed, searching again with %llu\n", (unsigned long long)Q,
+                (unsigned long long)std::min<uint64_t>(cap, Q * 4));
+      Q = std::min<uint64_t>(cap, Q * 4);
+      (void)hipFree(d_qkey.release());
+      (void)hipFree(d_qset.release());
+    }
+    const uint32_t nvis = ctl[kReachFill];
+    for (Dev* d : {&d_ownb, &d_shb, &d_seeds}) (void)hipFree(d->release());
+    // the kept k-mers by (set, k-mer), every set's first; then the new run table
+    Dev d_sk, d_ss, d_vlo, d_ncnt, d_nlo, d_nkey, d_nset, d_nrc;
+    G2S_GPU_TRY(d_vlo.alloc(((size_t)nsets + 1) * 4));
+    if (nvis) {
+      if (!sort_keyed_gpu<KT>(d_qkey, &d_qset, nvis, d_sk, &d_ss, why)) return false;
+      hipLaunchKernelGGL(k_set_first, grid((uint64_t)nsets + 1), blk, 0, 0, (const uint32_t*)d_ss.p, nvis, nsets, (uint32_t*)d_vlo.p);
+    } else {
+      G2S_GPU_TRY(hipMemset(d_vlo.p, 0, ((size_t)nsets + 1) * 4));
+      G2S_GPU_TRY(d_sk.alloc(0));
+      G2S_GPU_TRY(d_ss.alloc(0));
+    }
+    G2S_GPU_TRY(d_ncnt.alloc(((size_t)nsets + 1) * 4));
+    G2S_GPU_TRY(d_nlo.alloc(((size_t)nsets + 1) * 4));
+    hipLaunchKernelGGL(k_reach_set_count, grid((uint64_t)nsets + 1), blk, 0, 0, (const uint32_t*)d_rlo.p, (const uint32_t*)d_ridx.p,
+                       (const uint32_t*)d_vlo.p, nsets, (uint32_t*)d_ncnt.p);
+    G2S_SCAN(d_ncnt.p, d_nlo.p, (size_t)nsets + 1);
+    uint32_t nruns2 = 0;
+    G2S_GPU_TRY(hipMemcpy(&nruns2, (const uint32_t*)d_nlo.p + nsets, 4, hipMemcpyDeviceToHost));
+    G2S_GPU_TRY(d_nkey.alloc((size_t)nruns2 * sizeof(KT)));
+    G2S_GPU_TRY(d_nset.alloc((size_t)nruns2 * 4));
+    G2S_GPU_TRY(d_nrc.alloc((size_t)nruns2 * 4));
+    if (nruns)
+      hipLaunchKernelGGL(k_reach_copy_runs<KT>, grid(nruns), blk, 0, 0, (const KT*)d_rkey.p, (const uint32_t*)d_rset.p,
+                         (const uint32_t*)d_rcnt.p, nruns, (const uint32_t*)d_ridx.p, (const uint32_t*)d_rlo.p, (const uint32_t*)d_nlo.p,
+                         (KT*)d_nkey.p, (uint32_t*)d_nset.p, (uint32_t*)d_nrc.p);
+    if (nvis)
+      hipLaunchKernelGGL(k_reach_copy_kept<KT>, grid(nvis), blk, 0, 0, (const KT*)d_sk.p, (const uint32_t*)d_ss.p, nvis,
+                         (const uint32_t*)d_vlo.p, (const uint32_t*)d_nlo.p, so, (KT*)d_nkey.p, (uint32_t*)d_nset.p, (uint32_t*)d_nrc.p);
+    G2S_GPU_TRY(hipDeviceSynchronize());
+    std::swap(d_rkey.p, d_nkey.p);
+    std::swap(d_rset.p, d_nset.p);
+    std::swap(d_rcnt.p, d_nrc.p);
+    std::swap(d_rlo.p, d_nlo.p);
+    nruns = nruns2;
+    fset.clear();
+    for (uint32_t s = 0; s < nsets; s++) {
+      if (reach->has(s)) set_fidx[s] = INV;
+      else if (set_fidx[s] != INV) { set_fidx[s] = (uint32_t)fset.size(); fset.push_back(s); }
+    }
+    F = (uint32_t)fset.size();
+    rinfo->reach_sets = R;
+    rinfo->kept_kmers = nvis;
+    rinfo->full_kmers = 0;
+    rinfo->full_known = 0;
+    rinfo->levels = ctl[kReachLevels];
+    rinfo->on_device = 1;
+  }
   // ---- the merge: flags, scans, every set's count and first rank, then the writes — every buffer sized by its count
   const uint64_t FU64 = (uint64_t)F * U;
   if (FU64 + nruns >= (1ull << 31)) { if (why) *why = "size"; return false; }
@@ -1293,13 +1630,14 @@ static bool count_solid_pool_gpu_t(Graph& g, std::vector<KT>& out, std::vector<u
 
 bool graph_build_pool_gpu(Graph& g, const PoolSets& ps, int solid, int device,
                           const std::function<void(const std::vector<uint32_t>&, uint32_t)>& host_walk, PoolBuildInfo* info,
-                          std::string* why) {
+                          std::string* why, const PoolReach* reach, PoolReachInfo* rinfo, bool* device_usable) {
+  if (device_usable) *device_usable = false;
   if ((g.k % 2) == 0) { if (why) *why = "even k"; return false; }
   std::vector<uint32_t> rank_set;
   bool ok;
-  if (g.kmer_bytes == 32) ok = count_solid_pool_gpu_t<u256>(g, g.kmers256, &rank_set, ps, solid, device, info, why);
-  else if (g.kmer_bytes == 16) ok = count_solid_pool_gpu_t<u128>(g, g.kmers128, &rank_set, ps, solid, device, info, why);
-  else ok = count_solid_pool_gpu_t<uint64_t>(g, g.kmers64, &rank_set, ps, solid, device, info, why);
+  if (g.kmer_bytes == 32) ok = count_solid_pool_gpu_t<u256>(g, g.kmers256, &rank_set, ps, solid, device, info, why, reach, rinfo, device_usable);
+  else if (g.kmer_bytes == 16) ok = count_solid_pool_gpu_t<u128>(g, g.kmers128, &rank_set, ps, solid, device, info, why, reach, rinfo, device_usable);
+  else ok = count_solid_pool_gpu_t<uint64_t>(g, g.kmers64, &rank_set, ps, solid, device, info, why, reach, rinfo, device_usable);
   if (!ok) return false;
   if (g.kmer_bytes == 32) ok = finish_gpu_t<u256>(g, g.kmers256, device, host_walk, why, &rank_set);
   else if (g.kmer_bytes == 16) ok = finish_gpu_t<u128>(g, g.kmers128, device, host_walk, why, &rank_set);

@@ -131,30 +131,83 @@ extern "C" int g2s_graph_build_sets(const char* const* seqs, const uint64_t* len
   (*out)->g = g;
   return G2S_OK;
 }
+// the pooled builds' arguments, checked and as a PoolSets over `v`
+static int pool_sets_of(const char* name, const char* const* seqs, const uint64_t* lens, uint64_t nseqs, const uint64_t* set_begin,
+                        const uint32_t* set_seq, const uint32_t* shared_seq, uint64_t nshared, const uint8_t* set_shared,
+                        uint32_t nsets, g2s_graph** out, std::vector<std::pair<const char*, uint64_t>>* v, PoolSets* ps) {
+  if ((!seqs && nseqs) || !set_begin || !out || nsets == 0 || nseqs >= (1ull << 32) || (!shared_seq && nshared))
+    return fail(G2S_ERR_ARG, std::string(name) + ": bad argument");
+  for (uint32_t s = 0; s < nsets; s++)
+    if (set_begin[s + 1] < set_begin[s]) return fail(G2S_ERR_ARG, std::string(name) + ": set_begin decreases");
+  if (!set_seq && set_begin[nsets] > set_begin[0]) return fail(G2S_ERR_ARG, std::string(name) + ": bad argument");
+  v->reserve((size_t)nseqs);
+  for (uint64_t i = 0; i < nseqs; i++) v->emplace_back(seqs[i], lens ? lens[i] : (uint64_t)strlen(seqs[i]));
+  ps->seqs = v;
+  ps->set_begin = set_begin;
+  ps->set_seq = set_seq;
+  ps->shared_seq = shared_seq;
+  ps->nshared = nshared;
+  ps->set_shared = set_shared;
+  ps->nsets = nsets;
+  return G2S_OK;
+}
 extern "C" int g2s_graph_build_pool(const char* const* seqs, const uint64_t* lens, uint64_t nseqs, const uint64_t* set_begin,
                                     const uint32_t* set_seq, const uint32_t* shared_seq, uint64_t nshared, const uint8_t* set_shared,
                                     uint32_t nsets, int k, int solid, int nthreads, g2s_graph** out) {
-  if ((!seqs && nseqs) || !set_begin || !out || nsets == 0 || nseqs >= (1ull << 32) || (!shared_seq && nshared))
-    return fail(G2S_ERR_ARG, "g2s_graph_build_pool: bad argument");
-  for (uint32_t s = 0; s < nsets; s++)
-    if (set_begin[s + 1] < set_begin[s]) return fail(G2S_ERR_ARG, "g2s_graph_build_pool: set_begin decreases");
-  if (!set_seq && set_begin[nsets] > set_begin[0]) return fail(G2S_ERR_ARG, "g2s_graph_build_pool: bad argument");
   std::vector<std::pair<const char*, uint64_t>> v;
-  v.reserve((size_t)nseqs);
-  for (uint64_t i = 0; i < nseqs; i++) v.emplace_back(seqs[i], lens ? lens[i] : (uint64_t)strlen(seqs[i]));
   PoolSets ps;
-  ps.seqs = &v;
-  ps.set_begin = set_begin;
-  ps.set_seq = set_seq;
-  ps.shared_seq = shared_seq;
-  ps.nshared = nshared;
-  ps.set_shared = set_shared;
-  ps.nsets = nsets;
+  const int rc = pool_sets_of("g2s_graph_build_pool", seqs, lens, nseqs, set_begin, set_seq, shared_seq, nshared, set_shared, nsets, out, &v, &ps);
+  if (rc != G2S_OK) return rc;
   std::string err;
   Graph* g = graph_build_pool(ps, k, solid, nthreads, &err);
   if (!g) return fail(G2S_ERR_ARG, err);
   *out = new g2s_graph();
   (*out)->g = g;
+  return G2S_OK;
+}
+extern "C" int g2s_graph_build_pool_reach(const char* const* seqs, const uint64_t* lens, uint64_t nseqs, const uint64_t* set_begin,
+                                          const uint32_t* set_seq, const uint32_t* shared_seq, uint64_t nshared,
+                                          const uint8_t* set_shared, uint32_t nsets, int k, int solid, int nthreads,
+                                          const g2s_gap* reach_gap, const int32_t* reach_radius, g2s_graph** out) {
+  if ((reach_gap == nullptr) != (reach_radius == nullptr)) return fail(G2S_ERR_ARG, "g2s_graph_build_pool_reach: reach_gap and reach_radius go together");
+  if (!reach_radius) return g2s_graph_build_pool(seqs, lens, nseqs, set_begin, set_seq, shared_seq, nshared, set_shared, nsets, k, solid, nthreads, out);
+  std::vector<std::pair<const char*, uint64_t>> v;
+  PoolSets ps;
+  const int rc = pool_sets_of("g2s_graph_build_pool_reach", seqs, lens, nseqs, set_begin, set_seq, shared_seq, nshared, set_shared, nsets, out, &v, &ps);
+  if (rc != G2S_OK) return rc;
+  if (k < 1 || k > kMaxK) return fail(G2S_ERR_ARG, "k must be in [1," + std::to_string(kMaxK) + "]");  // (the seeds below read k characters)
+  // the seeds: the flank k-mers the fill looks up (g2s_batch_prepare), none for a gap it rejects
+  PoolReach reach;
+  reach.radius.assign(reach_radius, reach_radius + nsets);
+  reach.seed_begin.assign(1, 0);
+  for (uint32_t s = 0; s < nsets; s++) {
+    const g2s_gap& in = reach_gap[s];
+    const bool bad = reach_radius[s] < 0 || !in.left || !in.right || in.lmf < 0 || in.rmf < 0 || in.gap_len < 0 ||
+                     in.left_len < k + in.lmf || in.right_len < k + in.rmf;
+    if (!bad) {
+      for (int x = 0; x <= in.lmf; x++) reach.seed.push_back(in.left + x);
+      for (int x = 0; x <= in.rmf; x++) reach.seed.push_back(in.right + (in.right_len - k - x));
+      for (int x = 0; x <= in.rmf; x++) reach.seed.push_back(in.right + x);
+    }
+    reach.seed_begin.push_back(reach.seed.size());
+  }
+  std::string err;
+  Graph* g = graph_build_pool_reach(ps, reach, k, solid, nthreads, &err);
+  if (!g) return fail(G2S_ERR_ARG, err);
+  *out = new g2s_graph();
+  (*out)->g = g;
+  return G2S_OK;
+}
+// TEST HOOK (include/g2s_test.h)
+extern "C" int g2s_test_last_pool_reach(uint64_t* reach_sets, uint64_t* full_kmers, int* full_known, uint64_t* kept_kmers,
+                                        uint32_t* levels, int* on_device) {
+  const PoolReachInfo info = last_pool_reach();
+  if (reach_sets) *reach_sets = info.reach_sets;
+  if (full_kmers) *full_kmers = info.full_kmers;
+  if (full_known) *full_known = info.full_known;
+  if (kept_kmers) *kept_kmers = info.kept_kmers;
+  if (levels) *levels = info.levels;
+  if (on_device) *on_device = info.on_device;
   return G2S_OK;
 }
 // TEST HOOK (include/g2s_test.h)

@@ -271,9 +271,29 @@ int main(int argc, char** argv) {
     }
     if (any_shared)
       for (uint32_t j : shared_seq) chunk_shared.push_back(local(j));
+    // every gap's set bounded to what its fill can reach (g2s_graph_build_pool_reach: the sound radius); a gap that is
+    // not filled (a flank shorter than k) gets an empty set.  G2S_NO_REACH=1: the whole sets.
+    std::vector<g2s_gap> reach_gap(hi - lo);
+    std::vector<int32_t> reach_radius(hi - lo, -1);
+    const bool use_reach = !(getenv("G2S_NO_REACH") && atoi(getenv("G2S_NO_REACH")) != 0);
+    for (size_t i = lo; use_reach && i < hi; i++) {
+      const GapRec& g = gaps[i];
+      g2s_gap& x = reach_gap[i - lo];
+      memset(&x, 0, sizeof x);
+      x.left = g.left.c_str();
+      x.right = g.right.c_str();
+      x.left_len = (int)g.left.size();
+      x.right_len = (int)g.right.size();
+      x.gap_len = g.gap_length;
+      x.lmf = std::min((int)g.left.size() - k, fuz);   // (negative for a flank shorter than k: no seeds, an empty set)
+      x.rmf = std::min((int)g.right.size() - k, fuz);
+      x.skip_if_prev_right_fuz_gt = -1;
+      reach_radius[i - lo] = std::max(0, g.gap_length + derr) + std::max(0, x.lmf) + std::max(0, x.rmf);
+    }
     g2s_graph* graph = nullptr;
-    int rc = g2s_graph_build_pool(sp.data(), sl.data(), sp.size(), set_begin.data(), set_seq.data(), chunk_shared.data(),
-                                  chunk_shared.size(), takes_unmapped.data() + lo, (uint32_t)(hi - lo), k, solid, 0, &graph);
+    int rc = g2s_graph_build_pool_reach(sp.data(), sl.data(), sp.size(), set_begin.data(), set_seq.data(), chunk_shared.data(),
+                                        chunk_shared.size(), takes_unmapped.data() + lo, (uint32_t)(hi - lo), k, solid, 0,
+                                        use_reach ? reach_gap.data() : nullptr, use_reach ? reach_radius.data() : nullptr, &graph);
     for (uint32_t j : touched) chunk_of[j] = UINT32_MAX;
     touched.clear();
     g2s_session* s = nullptr;

@@ -124,6 +124,12 @@ _SIGS = {
     "g2s_graph_build_pool": (C.c_int, [C.POINTER(C.c_char_p), C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(C.c_uint64),
                                        C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_uint64, C.POINTER(C.c_uint8),
                                        C.c_uint32, C.c_int, C.c_int, C.c_int, C.POINTER(_VP)]),
+    "g2s_graph_build_pool_reach": (C.c_int, [C.POINTER(C.c_char_p), C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(C.c_uint64),
+                                             C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_uint64, C.POINTER(C.c_uint8),
+                                             C.c_uint32, C.c_int, C.c_int, C.c_int, C.POINTER(g2s_gap), C.POINTER(C.c_int32),
+                                             C.POINTER(_VP)]),
+    "g2s_test_last_pool_reach": (C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.POINTER(C.c_uint64),
+                                           C.POINTER(C.c_uint32), C.POINTER(C.c_int)]),
     "g2s_test_last_pool_build": (C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
                                            C.POINTER(C.c_int)]),
     "g2s_graph_num_sets": (C.c_uint32, [_VP]),
@@ -505,10 +511,13 @@ class Graph:
         return cls(h)
 
     @classmethod
-    def from_pool(cls, seqs, set_lists, k, solid, shared=None, set_shared=None, nthreads=0):
+    def from_pool(cls, seqs, set_lists, k, solid, shared=None, set_shared=None, nthreads=0, reach=None):
         """g2s_graph_build_pool: the set graph of from_sets for sets given as lists of indices into one pool of
         sequences (`set_lists`: per set, indices into `seqs`; a sequence may be in many sets, and twice in one).
-        `shared`: indices of a list that every set with a true `set_shared` entry holds behind its own."""
+        `shared`: indices of a list that every set with a true `set_shared` entry holds behind its own.
+        `reach` (g2s_graph_build_pool_reach): per set, None or (gap, radius) — the set keeps only the k-mers within
+        `radius` steps of the flank k-mers the fill looks up for `gap` (a Gap); a negative radius keeps the whole set.
+        reach_radius(gap, d_err) is the radius that loses nothing of a fill with that d_err."""
         lib = load_library()
         enc = [s.encode("ascii") if isinstance(s, str) else s for s in seqs]
         n = len(enc)
@@ -528,6 +537,16 @@ class Graph:
                 raise ValueError("set_shared needs one entry a set")
             flags = (C.c_uint8 * max(1, len(set_lists)))(*[1 if f else 0 for f in set_shared])
         h = _VP()
+        if reach is not None:
+            if len(reach) != len(set_lists):
+                raise ValueError("reach needs one entry a set")
+            blank = Gap("", "", 0, 0, 0)
+            gaps, keep = _gap_array([r[0] if r is not None else blank for r in reach])
+            radius = (C.c_int32 * max(1, len(reach)))(*[int(r[1]) if r is not None else -1 for r in reach])
+            _check(lib.g2s_graph_build_pool_reach(arr, lens, n, set_begin, set_seq, sh, len(shared), flags, len(set_lists), k,
+                                                  solid, nthreads, gaps, radius, C.byref(h)))
+            del keep
+            return cls(h)
         _check(lib.g2s_graph_build_pool(arr, lens, n, set_begin, set_seq, sh, len(shared), flags, len(set_lists), k, solid,
                                         nthreads, C.byref(h)))
         return cls(h)
@@ -1042,6 +1061,23 @@ def test_rand_stream(seed, skip, n):
     out = (C.c_int32 * max(1, n))()
     _check(load_library().g2s_test_rand_stream(seed, skip, n, out))
     return [out[i] for i in range(n)]
+
+
+def reach_radius(gap, d_err):
+    """The sound radius of g2s_graph_build_pool_reach for a fill of `gap` with -dist-error `d_err`:
+    max(0, gap_len + d_err) + lmf + rmf, the depth bound of the reference's search."""
+    return max(0, gap.gap_len + d_err) + gap.lmf + gap.rmf
+
+
+def test_last_pool_reach():
+    """g2s_test_last_pool_reach: dict(reach_sets, full_kmers (None when not counted), kept_kmers, levels, on_device) of
+    the last pooled build with a reach record"""
+    a, b, d = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    known, on = C.c_int(), C.c_int()
+    lv = C.c_uint32()
+    _check(load_library().g2s_test_last_pool_reach(C.byref(a), C.byref(b), C.byref(known), C.byref(d), C.byref(lv), C.byref(on)))
+    return dict(reach_sets=a.value, full_kmers=b.value if known.value else None, kept_kmers=d.value, levels=lv.value,
+                on_device=on.value)
 
 
 def test_last_pool_build():

@@ -104,6 +104,43 @@ int g2s_graph_build_pool(const char* const* seqs, const uint64_t* lens, uint64_t
                          uint64_t nshared,
                          const uint8_t* set_shared,   /* [nsets] */
                          uint32_t nsets, int k, int solid, int nthreads, g2s_graph** out);
+struct g2s_gap;
+/* g2s_graph_build_pool with every set bounded to the k-mers its gap's fill can reach (ABI 6, additive).  The first
+ * thirteen arguments are g2s_graph_build_pool's.  Set s with reach_radius[s] >= 0 has a REACH RECORD, the gap
+ * reach_gap[s], and is built as follows:
+ *   full graph  what g2s_graph_build_pool builds for s: the solid canonical k-mers of its own list (+ the shared list
+ *               when flagged);
+ *   seeds       the flank k-mers the fill looks up for reach_gap[s] (the (lmf+1) k-mers of left[0 .. k+lmf), the
+ *               (rmf+1) k-mers of the last k+rmf characters of right and the (rmf+1) of its first k+rmf), encoded as
+ *               the fill encodes them; none for a gap the fill rejects (NULL flank, negative lmf / rmf / gap_len,
+ *               left_len < k+lmf or right_len < k+rmf).  A seed that is no k-mer of the full graph is ignored;
+ *   kept set    every k-mer of the full graph at an undirected distance <= reach_radius[s] of some seed, the distance
+ *               counted over canonical k-mers, each with its eight possible neighbours (four extensions either way);
+ *   the set     the subgraph of the full graph induced on the kept set; EMPTY when no seed is in the full graph.
+ * reach_radius[s] < 0: the whole set, as g2s_graph_build_pool builds it (reach_gap[s] is not read).  Numbering is
+ * set-major and g2s_graph_set_nodes works as for any set graph.  With both arrays NULL, or every radius negative, the
+ * graph is g2s_graph_build_pool's.
+ *   SOUND RADIUS: for a fill with g2s_params.d_err = d_err the radius max(0, gap_len + d_err) + lmf + rmf loses
+ * nothing — the search of fill_gap is depth-bounded (right search: right_half; left search: left_half + right_half
+ * = gap_len + d_err + lmf + rmf, Gap2Seq.cpp:862-863, 908, 1029), so g2s_fill_sets gives the same results on the
+ * bounded graph as on the whole one.  The bound is safe, not tight: the kept set is the union of the balls round ALL
+ * seeds, the right flank's included, so a closing path of L steps is kept whole from radius (L - 1) / 2 on and a fill
+ * first changes one below that (tests/test_gpu_pool_reach.py pins both sides).
+ *   On the device (odd k) the bounded sets are found by a breadth-first search per set over the own lists' and the
+ * shared list's sorted count tables — membership of a k-mer is two binary searches, the sets' full graphs are never
+ * formed, and the work and the memory follow the k-mers visited plus one bit a (set with a record, distinct shared
+ * k-mer) instead of flagged sets x distinct shared k-mers.  When the device cannot take it (the conditions of
+ * g2s_graph_build_pool — its flagged sets x shared k-mers term counting the flagged sets WITHOUT a record only — the
+ * kept k-mers exceeding the search's queue at its largest — it starts at the own k-mers plus 4 096 a set and grows on
+ * overflow, never sized by sets x shared k-mers up front — or a level of one set exceeding its chunk list) the host builds the
+ * same graph by a search per set, also without forming a full graph (G2S_DEBUG=1 says which, and why).
+ * G2S_ERR_ARG: g2s_graph_build_pool's, and exactly one of the two arrays NULL; *out is not written then. */
+int g2s_graph_build_pool_reach(const char* const* seqs, const uint64_t* lens, uint64_t nseqs,
+                               const uint64_t* set_begin, const uint32_t* set_seq, const uint32_t* shared_seq,
+                               uint64_t nshared, const uint8_t* set_shared, uint32_t nsets, int k, int solid, int nthreads,
+                               const struct g2s_gap* reach_gap,  /* [nsets], or NULL */
+                               const int32_t* reach_radius,      /* [nsets], or NULL */
+                               g2s_graph** out);
 uint32_t g2s_graph_num_sets(const g2s_graph* g); /* 1 for every graph built the other ways */
 int g2s_graph_set_nodes(const g2s_graph* g, uint32_t set, uint64_t* first_kmer, uint64_t* n_kmers);
 uint32_t g2s_graph_set_node(const g2s_graph* g, uint32_t set, const char* kmer); /* G2S_INVALID_NODE if absent */

@@ -13,6 +13,12 @@ Per way: build_ms (the best and all of --reps), fill_ms, what g2s_test_last_pool
 peak resident size (resource.getrusage, MB) before the lists were made, before the build and after the fill.
 
     python tools/libmode_bench.py --gaps 1000 --shared-bases 2000000 --flagged 0.1 [--build pool] [--reps 3]
+
+With --reach (pool builds) every set gets a reach record — its gap, with the sound radius reach_radius(gap, 500) —
+through Graph.from_pool(..., reach=...), and the line also holds what g2s_test_last_pool_reach counted: the k-mers
+kept, and the k-mers of the full sets where the build counted them (the host build; null on the device).  --model
+prints instead, without a device, the k-mers the brute-force model of tests/reach_cases.py keeps for the same workload
+(and the full sets' k-mers): the number the graph's k-mer count with --reach must equal.
 """
 import argparse
 import json
@@ -97,11 +103,41 @@ def shared_workload(n, k, shared_bases, flagged, seed=3):
     return seqs, set_lists, shared, [1 if s in marks else 0 for s in range(n)], gaps
 
 
-def run_shared(way, seqs, set_lists, shared, set_shared, gaps, k, reps):
+def model_kmers(seqs, set_lists, shared, set_shared, gaps, k):
+    """(kept, full) summed over the sets, by the model of tests/reach_cases.py on two count tables (the shared list
+    counted once)"""
+    import reach_cases as RC
+    sh = RC.kmer_counts([seqs[i] for i in shared], k)
+    kept_all = full_all = 0
+    for s, own_list in enumerate(set_lists):
+        own = RC.kmer_counts([seqs[i] for i in own_list], k)
+        flagged = bool(set_shared[s])
+        member = (lambda x: x in own or x in sh) if flagged else (lambda x: x in own)  # (solid = 1)
+        full_all += len(own) + (sum(1 for x in sh if x not in own) if flagged else 0)
+        g = gaps[s]
+        gd = dict(left=g.left, right=g.right, gap_len=g.gap_len, lmf=g.lmf, rmf=g.rmf)
+        kept = {x for x in RC.seeds_of(gd, k) if member(x)}
+        frontier, level, radius = list(kept), 0, P.reach_radius(g, 500)
+        while frontier and level < radius:
+            nxt = []
+            for x in frontier:
+                for y in RC.neighbours(x):
+                    if y not in kept and member(y):
+                        kept.add(y)
+                        nxt.append(y)
+            frontier, level = nxt, level + 1
+        kept_all += len(kept)
+    return kept_all, full_all
+
+
+def run_shared(way, seqs, set_lists, shared, set_shared, gaps, k, reps, reach=False):
     out = {"peak_mb_start": peak_mb()}
     if way == "sets":
         sets = [[seqs[i] for i in own] + ([seqs[i] for i in shared] if set_shared[s] else []) for s, own in enumerate(set_lists)]
         build = lambda: P.Graph.from_sets(sets, k, 1)  # noqa: E731
+    elif reach:
+        records = [(g, P.reach_radius(g, 500)) for g in gaps]
+        build = lambda: P.Graph.from_pool(seqs, set_lists, k, 1, shared=shared, set_shared=set_shared, reach=records)  # noqa: E731
     else:
         build = lambda: P.Graph.from_pool(seqs, set_lists, k, 1, shared=shared, set_shared=set_shared)  # noqa: E731
     out["peak_mb_lists"] = peak_mb()
@@ -114,7 +150,11 @@ def run_shared(way, seqs, set_lists, shared, set_shared, gaps, k, reps):
             g.free()
     if way == "pool":
         out["pool_build"] = P.test_last_pool_build()
+    if way == "pool" and reach:
+        out["pool_reach"] = P.test_last_pool_reach()
+    t0 = time.perf_counter()
     s = P.Session(g, 0, d_err=500, randseed=1)
+    out["session_ms"] = (time.perf_counter() - t0) * 1e3
     t0 = time.perf_counter()
     res, tm = s.fill_sets(gaps, list(range(len(gaps))), want_timing=True)
     out.update(build_ms=min(times), build_ms_all=[round(t, 1) for t in times], fill_ms=(time.perf_counter() - t0) * 1e3,
@@ -134,7 +174,16 @@ def main():
     ap.add_argument("--flagged", type=float, default=0.1, help="share of the sets that hold the shared list")
     ap.add_argument("--build", choices=["sets", "pool", "both"], default="both")
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--reach", action="store_true", help="pool builds with a reach record a set (the sound radius)")
+    ap.add_argument("--model", action="store_true", help="no device: the k-mers the model keeps for the --reach workload")
     a = ap.parse_args()
+    if a.model:
+        out = {"k": a.k, "shared_bases": a.shared_bases, "flagged": a.flagged}
+        for n in [int(x) for x in a.gaps.split(",")]:
+            kept, full = model_kmers(*shared_workload(n, a.k, a.shared_bases or 0, a.flagged), a.k)
+            out["model_%d" % n] = dict(kept_kmers=kept, full_kmers=full)
+        print(json.dumps(out))
+        return
     if P.G2S.device_count() < 1:
         raise SystemExit("libmode_bench: no gfx950 device")
     out = {"k": a.k}
@@ -145,7 +194,7 @@ def main():
         for n in [int(x) for x in a.gaps.split(",")]:
             w = shared_workload(n, a.k, a.shared_bases, a.flagged)
             for way in (["pool", "sets"] if a.build == "both" else [a.build]):
-                out["%s_%d" % (way, n)] = run_shared(way, *w, a.k, a.reps)
+                out["%s_%d" % (way, n)] = run_shared(way, *w, a.k, a.reps, reach=a.reach and way == "pool")
         print(json.dumps(out))
         return
     for n in [int(x) for x in a.gaps.split(",")]:
