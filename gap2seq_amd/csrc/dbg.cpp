@@ -288,14 +288,15 @@ template <class KT>
 void finish_graph(Graph& g, int nthreads) {
   const auto f0 = std::chrono::steady_clock::now();
   if (g.bucket.empty()) build_bucket_index<KT>(g);  // (the GPU k-mer set brings its index along)
-  // With a GPU (odd k): successor table by binary search, numbering along unitigs by list
-  // ranking, tables in id space and the unitig-start bitmap all on the device (dbg_gpu.hip);
-  // the host only numbers circular unitigs.  Otherwise, and for even k, the host build below.
+  // With a GPU: successor table (at even k the predecessor table too) by binary search, numbering
+  // along unitigs by list ranking, tables in id space and the unitig-start bitmap all on the device
+  // (dbg_gpu.hip); the host only numbers circular unitigs.  Otherwise the host build below, which
+  // is the authority on palindromic k-mers (even k) the device build is tested against.
   if (!getenv("G2S_HOST_BUILD")) {
     std::string why;
     const int dev = getenv("G2S_DEVICE") ? atoi(getenv("G2S_DEVICE")) : 0;
     const bool ok = graph_finish_gpu(g, dev, [&](const std::vector<uint32_t>& succ_r, uint32_t first_id) {
-      unitig_order(succ_r, g.n, false, &g.rank2id, &g.flip, &g.n_unitigs, true, first_id);
+      unitig_order(succ_r, g.n, (g.k % 2) == 0, &g.rank2id, &g.flip, &g.n_unitigs, true, first_id);
     }, &why);
     if (getenv("G2S_DEBUG"))
       fprintf(stderr, "[g2s]   tables, unitig order, id space: %.3f s on the %s%s%s\n",
@@ -487,8 +488,8 @@ Graph* graph_build_sets(const std::vector<std::pair<const char*, uint64_t>>& seq
     if (s >= nsets) { if (err) *err = "graph_build_sets: set id " + std::to_string(s) + " out of range"; return nullptr; }
   if (nthreads <= 0) nthreads = (int)std::max(1u, std::thread::hardware_concurrency());
   const auto t0 = std::chrono::steady_clock::now();
-  // on the GPU when there is one (dbg_gpu.hip: keyed k-mer sort, successors searched inside their set); even k, no
-  // device, G2S_HOST_BUILD=1, an empty union: the host build below, set by set
+  // on the GPU when there is one (dbg_gpu.hip: keyed k-mer sort, successors searched inside their set); no device,
+  // G2S_HOST_BUILD=1, an empty union: the host build below, set by set
   if (!getenv("G2S_HOST_BUILD")) {
     Graph* g = new Graph();
     g->k = k;
@@ -497,7 +498,7 @@ Graph* graph_build_sets(const std::vector<std::pair<const char*, uint64_t>>& seq
     std::string why;
     const bool ok = graph_build_sets_gpu(*g, seqs, seq_set, nsets, solid, getenv("G2S_DEVICE") ? atoi(getenv("G2S_DEVICE")) : 0,
                                          [&](const std::vector<uint32_t>& succ_r, uint32_t first_id) {
-                                           unitig_order(succ_r, g->n, false, &g->rank2id, &g->flip, &g->n_unitigs, true, first_id);
+                                           unitig_order(succ_r, g->n, (g->k % 2) == 0, &g->rank2id, &g->flip, &g->n_unitigs, true, first_id);
                                          }, &why);
     if (ok) {
       if (getenv("G2S_DEBUG"))
@@ -626,8 +627,8 @@ Graph* graph_build_pool(const PoolSets& ps, int k, int solid, int nthreads, std:
   const auto t0 = std::chrono::steady_clock::now();
   PoolBuildInfo info;
   // on the GPU when there is one (dbg_gpu.hip: the pool's k-mers extracted once, the own lists' (set, k-mer) pairs and
-  // the shared list's k-mers gathered from them, the shared list sorted once and merged into every flagged set); even
-  // k, no device, G2S_HOST_BUILD=1, an empty union: the host build, set by set over each set's pointers
+  // the shared list's k-mers gathered from them, the shared list sorted once and merged into every flagged set); no
+  // device, G2S_HOST_BUILD=1, an empty union: the host build, set by set over each set's pointers
   if (!getenv("G2S_HOST_BUILD")) {
     Graph* g = new Graph();
     g->k = k;
@@ -636,7 +637,7 @@ Graph* graph_build_pool(const PoolSets& ps, int k, int solid, int nthreads, std:
     std::string why;
     const bool ok = graph_build_pool_gpu(*g, ps, solid, getenv("G2S_DEVICE") ? atoi(getenv("G2S_DEVICE")) : 0,
                                          [&](const std::vector<uint32_t>& succ_r, uint32_t first_id) {
-                                           unitig_order(succ_r, g->n, false, &g->rank2id, &g->flip, &g->n_unitigs, true, first_id);
+                                           unitig_order(succ_r, g->n, (g->k % 2) == 0, &g->rank2id, &g->flip, &g->n_unitigs, true, first_id);
                                          }, &info, &why);
     if (ok) {
       if (getenv("G2S_DEBUG"))
@@ -868,7 +869,7 @@ Graph* graph_build_pool_reach(const PoolSets& ps_in, const PoolReach& reach_in, 
     std::string why;
     const bool ok = graph_build_pool_gpu(*g, ps, solid, getenv("G2S_DEVICE") ? atoi(getenv("G2S_DEVICE")) : 0,
                                          [&](const std::vector<uint32_t>& succ_r, uint32_t first_id) {
-                                           unitig_order(succ_r, g->n, false, &g->rank2id, &g->flip, &g->n_unitigs, true, first_id);
+                                           unitig_order(succ_r, g->n, (g->k % 2) == 0, &g->rank2id, &g->flip, &g->n_unitigs, true, first_id);
                                          }, &info, &why, &reach, &rinfo, &device_gave_up);
     if (ok) {
       if (getenv("G2S_DEBUG"))
@@ -880,7 +881,7 @@ Graph* graph_build_pool_reach(const PoolSets& ps_in, const PoolReach& reach_in, 
       info.on_device = 1;
     } else {
       if (getenv("G2S_DEBUG")) fprintf(stderr, "[g2s]   pooled set graph on the host (%s)\n", why.c_str());
-      // (device_gave_up: the build got as far as selecting the device — not even k, not a machine without one)
+      // (device_gave_up: the build got as far as selecting the device — not a machine without one)
       delete g;
       g = nullptr;
     }

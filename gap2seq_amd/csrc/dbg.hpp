@@ -23,7 +23,7 @@ static const uint32_t kUstartPad = 64;  // 64-bit words of all-ones padding on e
 
 struct DeviceGraph {
   uint32_t* succ = nullptr;  // [2n*4]
-  uint32_t* pred = nullptr;  // [2n*4], only when k is even (palindromic k-mers exist)
+  uint32_t* pred = nullptr;  // [2n*4], only when k is even (palindromic k-mers exist); the device build leaves its own here
   uint64_t* ustart = nullptr;  // unitig-start bitmap, offset by kUstartPad words of all-ones padding
   uint32_t* rem = nullptr;     // [2n] unitig-internal steps left from an oriented node (seg_tables.hip), odd k only
   uint32_t* urec = nullptr;    // [2n][8] successor record of the end of the node's unitig walk + rem (seg_tables.hip)
@@ -112,7 +112,7 @@ Graph* graph_build_sets(const std::vector<std::pair<const char*, uint64_t>>& seq
 // seqs[set_seq[q]], q in [set_begin[s], set_begin[s+1]) (its own list), followed by seqs[shared_seq[*]] when
 // set_shared[s] is set.  A sequence may be in any number of sets, and more than once in one; every occurrence counts
 // towards solidity.  The graph is graph_build_sets' for the expanded list, up to the numbering of nodes inside a set.
-// On the device (odd k; dbg_gpu.hip) the shared list is encoded and sorted once, whatever the number of flagged sets.
+// On the device (dbg_gpu.hip) the shared list is encoded and sorted once, whatever the number of flagged sets.
 struct PoolSets {
   const std::vector<std::pair<const char*, uint64_t>>* seqs = nullptr;
   const uint64_t* set_begin = nullptr;   // [nsets + 1]

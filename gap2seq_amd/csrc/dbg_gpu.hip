@@ -3,7 +3,10 @@
 // The build (replaces gatb Graph::create, /root/reference/src/Gap2Seq.cpp:193-219) has four
 // steps after the sorted set of solid canonical k-mers exists (dbg.cpp: count_solid):
 //   1. successor table in sorted-rank space: 8 neighbour k-mers per k-mer, each a binary
-//      search inside its prefix bucket (k_succ; 64-, 128- and 256-bit k-mers);
+//      search inside its prefix bucket (k_succ; 64-, 128- and 256-bit k-mers).  At even k a k-mer
+//      can be its own reverse complement: such a palindrome exists on strand 1 only, and the
+//      same searches also fill an explicit predecessor table (pred(v) = succ(v^1)^1 does not
+//      hold next to a palindrome); odd k allocates and writes no such table;
 //   2. numbering along maximal non-branching paths.  On the host this is one dependent,
 //      cache-missing load per k-mer (0.35 s of a 0.49 s build at 3 Mbp, 11.7 s of 16.6 s at
 //      60 Mbp); here it is list ranking by pointer jumping:
@@ -18,7 +21,11 @@
 //                 chain lengths), node id = base[head] + distance, orientation bit = the
 //                 node's strand on that chain.
 //      Circular unitigs have no head; the host walk numbers them after the rest.
-//   3. the tables permuted into id space + the last base of every oriented node (k_remap);
+//      A palindrome is always a unitig of its own (its strand-0 row is empty, so no edge at it
+//      passes the predicate's test that the edge back leads to v^1); k_keep gives such a k-mer the
+//      strand the host walk would start on.
+//   3. the tables (at even k both) permuted into id space + the last base of every oriented node
+//      (k_remap);
 //   4. the unitig-start bitmap (k_ustart).
 // The id-space table and the bitmap stay on the device: they are the graph's copy for the
 // fill path.  All of it is HBM-bound random access: 0.05 s at 3 Mbp.
@@ -91,13 +98,25 @@ __global__ void k_tail(const uint32_t* __restrict__ nxt, const uint64_t* __restr
   tailof[h] = v;
 }
 
-// cnt[v] = length of the chain headed by v when that chain is the one kept of its mirrored pair
+// cnt[v] = length of the chain headed by v when that chain is the one kept of its mirrored pair.
+// EVEN (even k): a k-mer that is a unitig of its own is numbered on the strand the host's walk starts on (dbg.cpp:
+// unitig_order) — strand 1 when its strand-0 row is empty and strand 1 has an out-edge.  A palindromic k-mer is always
+// such a unitig (no edge at it is internal), and its two rows are no mirror images: this fixes its flip.
+template <bool EVEN>
 __global__ void k_keep(const uint32_t* __restrict__ len, const uint32_t* __restrict__ tailof, uint32_t n2,
-                       uint32_t* __restrict__ cnt, uint32_t* n_kept) {
+                       uint32_t* __restrict__ cnt, uint32_t* n_kept, const uint32_t* __restrict__ succ) {
   const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
   if (v >= n2) return;
   const uint32_t l = len[v];
-  const bool keep = l != 0u && v < (tailof[v] ^ 1u);
+  bool keep = l != 0u && v < (tailof[v] ^ 1u);
+  if constexpr (EVEN) {
+    if (l == 1u) {
+      uint32_t deg0, deg1;
+      (void)only_succ(succ, v & ~1u, &deg0);
+      (void)only_succ(succ, v | 1u, &deg1);
+      keep = (v & 1u) == ((deg0 == 0u && deg1 > 0u) ? 1u : 0u);
+    }
+  }
   cnt[v] = keep ? l : 0u;
   if (keep) atomicAdd(n_kept, 1u);
 }
@@ -114,7 +133,7 @@ __global__ void k_assign(const uint64_t* __restrict__ pd, const uint32_t* __rest
   flip[v >> 1] = (uint8_t)(v & 1u);
 }
 
-// ---- successor table in sorted-rank space (dbg.cpp: build_tables_rank, odd k) -------------
+// ---- successor (and, at even k, predecessor) table in sorted-rank space (dbg.cpp: build_tables_rank) -------------
 typedef unsigned __int128 u128;
 using g2s::u256;
 
@@ -148,57 +167,79 @@ __device__ __forceinline__ uint32_t d_rank_of(const KT* __restrict__ v, const ui
   return (lo < end && v[lo] == x) ? lo : INV;
 }
 
-template <class KT>
+// EVEN (even k; dbg.cpp: build_tables_rank): a palindromic k-mer (c == revcomp(c)) exists on strand 1 only — its strand-0
+// rows stay INVALID in both tables, and a neighbour that is a palindrome is named with orientation 1 (the tie rule).  The
+// predecessor table comes from the same searches: the successor y of the oriented node t by nt is, read on the other
+// strand, the predecessor by nt of the node whose sequence is t's reverse complement — t ^ 1, or t itself when t is a
+// palindrome — with the orientation of the other strand, ties to 1 again.
+template <bool EVEN>
+__device__ __forceinline__ void d_store_rows(uint32_t t, bool pal, const uint32_t (&out)[4], const uint32_t (&pout)[4],
+                                             uint32_t* __restrict__ succ, uint32_t* __restrict__ pred) {
+  *(uint4*)(succ + (size_t)t * 4) = make_uint4(out[0], out[1], out[2], out[3]);
+  if constexpr (EVEN) *(uint4*)(pred + (size_t)(pal ? t : (t ^ 1u)) * 4) = make_uint4(pout[0], pout[1], pout[2], pout[3]);
+}
+
+template <class KT, bool EVEN>
 __global__ void k_succ(const KT* __restrict__ v, const uint32_t* __restrict__ bucket, int shift, uint32_t n2, int k,
-                       uint32_t* __restrict__ succ) {
+                       uint32_t* __restrict__ succ, uint32_t* __restrict__ pred) {
   const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;  // oriented node in rank space: 2*rank + strand
   if (t >= n2) return;
   const KT mask = (2 * k >= (int)(8 * sizeof(KT))) ? ~(KT)0 : ((((KT)1) << (2 * k)) - 1);
   const KT c = v[t >> 1], rc = d_revcomp(c, k);
   const KT seq = (t & 1u) ? rc : c, rseq = (t & 1u) ? c : rc;
-  uint32_t out[4];
+  const bool pal = EVEN && c == rc;
+  uint32_t out[4] = {INV, INV, INV, INV}, pout[4] = {INV, INV, INV, INV};
+  if (!(pal && (t & 1u) == 0u)) {
 #pragma unroll
-  for (int nt = 0; nt < 4; nt++) {
-    const KT y = ((seq << 2) | (KT)nt) & mask;
-    const KT ry = (rseq >> 2) | ((KT)(nt ^ 2) << (2 * (k - 1)));
-    const uint32_t r = d_rank_of<KT>(v, bucket, shift, y < ry ? y : ry);
-    out[nt] = r == INV ? INV : 2u * r + (y < ry ? 0u : 1u);
+    for (int nt = 0; nt < 4; nt++) {
+      const KT y = ((seq << 2) | (KT)nt) & mask;
+      const KT ry = (rseq >> 2) | ((KT)(nt ^ 2) << (2 * (k - 1)));
+      const uint32_t r = d_rank_of<KT>(v, bucket, shift, y < ry ? y : ry);
+      out[nt] = r == INV ? INV : 2u * r + (y < ry ? 0u : 1u);
+      if constexpr (EVEN) pout[nt] = r == INV ? INV : 2u * r + (ry < y ? 0u : 1u);
+    }
   }
-  *(uint4*)(succ + (size_t)t * 4) = make_uint4(out[0], out[1], out[2], out[3]);
+  d_store_rows<EVEN>(t, pal, out, pout, succ, pred);
 }
 
 // set graphs (dbg.cpp: graph_build_sets): the neighbour searched inside its own set's rank range only — sets are small,
 // a binary search over the range replaces the prefix index over the union
-template <class KT>
+template <class KT, bool EVEN>
 __global__ void k_succ_set(const KT* __restrict__ v, const uint32_t* __restrict__ rank_set, const uint32_t* __restrict__ set_lo,
-                           uint32_t n2, int k, uint32_t* __restrict__ succ) {
+                           uint32_t n2, int k, uint32_t* __restrict__ succ, uint32_t* __restrict__ pred) {
   const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;  // oriented node in rank space: 2*rank + strand
   if (t >= n2) return;
   const KT mask = (2 * k >= (int)(8 * sizeof(KT))) ? ~(KT)0 : ((((KT)1) << (2 * k)) - 1);
   const KT c = v[t >> 1], rc = d_revcomp(c, k);
   const KT seq = (t & 1u) ? rc : c, rseq = (t & 1u) ? c : rc;
+  const bool pal = EVEN && c == rc;
   const uint32_t set = rank_set[t >> 1], lo0 = set_lo[set], hi0 = set_lo[set + 1];
-  uint32_t out[4];
+  uint32_t out[4] = {INV, INV, INV, INV}, pout[4] = {INV, INV, INV, INV};
+  if (!(pal && (t & 1u) == 0u)) {
 #pragma unroll
-  for (int nt = 0; nt < 4; nt++) {
-    const KT y = ((seq << 2) | (KT)nt) & mask;
-    const KT ry = (rseq >> 2) | ((KT)(nt ^ 2) << (2 * (k - 1)));
-    const KT x = y < ry ? y : ry;
-    uint32_t lo = lo0, hi = hi0;
-    while (lo < hi) {
-      const uint32_t mid = (lo + hi) >> 1;
-      if (v[mid] < x) lo = mid + 1; else hi = mid;
+    for (int nt = 0; nt < 4; nt++) {
+      const KT y = ((seq << 2) | (KT)nt) & mask;
+      const KT ry = (rseq >> 2) | ((KT)(nt ^ 2) << (2 * (k - 1)));
+      const KT x = y < ry ? y : ry;
+      uint32_t lo = lo0, hi = hi0;
+      while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (v[mid] < x) lo = mid + 1; else hi = mid;
+      }
+      const bool hit = lo < hi0 && v[lo] == x;
+      out[nt] = hit ? 2u * lo + (y < ry ? 0u : 1u) : INV;
+      if constexpr (EVEN) pout[nt] = hit ? 2u * lo + (ry < y ? 0u : 1u) : INV;
     }
-    out[nt] = (lo < hi0 && v[lo] == x) ? 2u * lo + (y < ry ? 0u : 1u) : INV;
   }
-  *(uint4*)(succ + (size_t)t * 4) = make_uint4(out[0], out[1], out[2], out[3]);
+  d_store_rows<EVEN>(t, pal, out, pout, succ, pred);
 }
 
 // ---- tables in id space (dbg.cpp: finish_graph) ----------------------------------------------
-template <class KT>
-__global__ void k_remap(const KT* __restrict__ v, const uint32_t* __restrict__ succ_r, const uint32_t* __restrict__ rank2id,
-                        const uint8_t* __restrict__ flip, uint32_t n2, int k, uint32_t* __restrict__ succ_id,
-                        uint8_t* __restrict__ lastnt, uint32_t* __restrict__ id2rank) {
+template <class KT, bool EVEN>
+__global__ void k_remap(const KT* __restrict__ v, const uint32_t* __restrict__ succ_r, const uint32_t* __restrict__ pred_r,
+                        const uint32_t* __restrict__ rank2id, const uint8_t* __restrict__ flip, uint32_t n2, int k,
+                        uint32_t* __restrict__ succ_id, uint32_t* __restrict__ pred_id, uint8_t* __restrict__ lastnt,
+                        uint32_t* __restrict__ id2rank) {
   const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= n2) return;
   const uint32_t r = t >> 1, s = t & 1u;
@@ -206,6 +247,10 @@ __global__ void k_remap(const KT* __restrict__ v, const uint32_t* __restrict__ s
   const uint4 in = *(const uint4*)(succ_r + (size_t)t * 4);
   auto remap = [&](uint32_t w) -> uint32_t { return w == INV ? INV : 2u * rank2id[w >> 1] + ((w & 1u) ^ (uint32_t)flip[w >> 1]); };
   *(uint4*)(succ_id + (size_t)row * 4) = make_uint4(remap(in.x), remap(in.y), remap(in.z), remap(in.w));
+  if constexpr (EVEN) {  // the explicit predecessor table (even k only)
+    const uint4 pin = *(const uint4*)(pred_r + (size_t)t * 4);
+    *(uint4*)(pred_id + (size_t)row * 4) = make_uint4(remap(pin.x), remap(pin.y), remap(pin.z), remap(pin.w));
+  }
   const KT c = v[r];
   lastnt[row] = s == 0 ? (uint8_t)(c & 3) : (uint8_t)(((c >> (2 * (k - 1))) & 3) ^ 2);
   if (s == 0) id2rank[rank2id[r]] = r;
@@ -744,10 +789,10 @@ namespace g2s {
 // fill path (g2s_graph_upload finds them).  `host_walk` numbers what list ranking leaves
 // unnumbered (circular unitigs).  Returns false (with a reason) when the device cannot be
 // used; nothing of g is touched then and the caller runs the host build.
-template <class KT>
-static bool finish_gpu_t(Graph& g, const std::vector<KT>& kmers, int device,
+template <class KT, bool EVEN>
+static bool finish_gpu_e(Graph& g, const std::vector<KT>& kmers, int device,
                          const std::function<void(const std::vector<uint32_t>&, uint32_t)>& host_walk, std::string* why,
-                         const std::vector<uint32_t>* rank_set = nullptr) {
+                         const std::vector<uint32_t>* rank_set) {
 #define G2S_GPU_TRY(expr)                                                                 \
   do {                                                                                    \
     hipError_t e_ = (expr);                                                               \
@@ -761,10 +806,11 @@ static bool finish_gpu_t(Graph& g, const std::vector<KT>& kmers, int device,
   const uint32_t n2 = (uint32_t)(2 * n);
   const int k = g.k;
   const dim3 blk(256), grd((n2 + 255) / 256);
-  Dev d_km, d_bucket, d_succ, d_nxt, d_pd0, d_pd1, d_len, d_tail, d_cnt, d_base, d_id, d_flip, d_flag, d_tmp;
-  // ---- successor table, rank space
+  Dev d_km, d_bucket, d_succ, d_pred, d_nxt, d_pd0, d_pd1, d_len, d_tail, d_cnt, d_base, d_id, d_flip, d_flag, d_tmp;
+  // ---- successor table, rank space (even k: the predecessor table beside it; odd k allocates and writes none)
   G2S_GPU_TRY(d_km.alloc(kmers.size() * sizeof(KT)));
   G2S_GPU_TRY(d_succ.alloc((size_t)n2 * 16));
+  if constexpr (EVEN) G2S_GPU_TRY(d_pred.alloc((size_t)n2 * 16));
   G2S_GPU_TRY(hipMemcpy(d_km.p, kmers.data(), kmers.size() * sizeof(KT), hipMemcpyHostToDevice));
   if (rank_set) {  // set graph: every neighbour searched in its own set's range (g.set_lo)
     Dev d_rs, d_sl;
@@ -773,14 +819,14 @@ static bool finish_gpu_t(Graph& g, const std::vector<KT>& kmers, int device,
     G2S_GPU_TRY(d_sl.alloc(lo32.size() * 4));
     G2S_GPU_TRY(hipMemcpy(d_rs.p, rank_set->data(), (size_t)n * 4, hipMemcpyHostToDevice));
     G2S_GPU_TRY(hipMemcpy(d_sl.p, lo32.data(), lo32.size() * 4, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_succ_set<KT>, grd, blk, 0, 0, (const KT*)d_km.p, (const uint32_t*)d_rs.p, (const uint32_t*)d_sl.p, n2, k,
-                       (uint32_t*)d_succ.p);
+    hipLaunchKernelGGL((k_succ_set<KT, EVEN>), grd, blk, 0, 0, (const KT*)d_km.p, (const uint32_t*)d_rs.p, (const uint32_t*)d_sl.p, n2,
+                       k, (uint32_t*)d_succ.p, (uint32_t*)d_pred.p);
     G2S_GPU_TRY(hipDeviceSynchronize());
   } else {
     G2S_GPU_TRY(d_bucket.alloc(g.bucket.size() * 4));
     G2S_GPU_TRY(hipMemcpy(d_bucket.p, g.bucket.data(), g.bucket.size() * 4, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_succ<KT>, grd, blk, 0, 0, (const KT*)d_km.p, (const uint32_t*)d_bucket.p, 2 * k - g.bucket_bits, n2, k,
-                       (uint32_t*)d_succ.p);
+    hipLaunchKernelGGL((k_succ<KT, EVEN>), grd, blk, 0, 0, (const KT*)d_km.p, (const uint32_t*)d_bucket.p, 2 * k - g.bucket_bits, n2,
+                       k, (uint32_t*)d_succ.p, (uint32_t*)d_pred.p);
   }
   // ---- numbering along unitigs: list ranking
   G2S_GPU_TRY(d_nxt.alloc((size_t)n2 * 4));
@@ -811,8 +857,8 @@ static bool finish_gpu_t(Graph& g, const std::vector<KT>& kmers, int device,
   hipLaunchKernelGGL(k_tail, grd, blk, 0, 0, (const uint32_t*)d_nxt.p, (const uint64_t*)cur, n2, (uint32_t*)d_len.p,
                      (uint32_t*)d_tail.p);
   G2S_GPU_TRY(hipMemset(d_flag.p, 0, 4));
-  hipLaunchKernelGGL(k_keep, grd, blk, 0, 0, (const uint32_t*)d_len.p, (const uint32_t*)d_tail.p, n2, (uint32_t*)d_cnt.p,
-                     (uint32_t*)d_flag.p);
+  hipLaunchKernelGGL(k_keep<EVEN>, grd, blk, 0, 0, (const uint32_t*)d_len.p, (const uint32_t*)d_tail.p, n2, (uint32_t*)d_cnt.p,
+                     (uint32_t*)d_flag.p, (const uint32_t*)d_succ.p);
   size_t tmp_bytes = 0;
   G2S_GPU_TRY(rocprim::exclusive_scan(nullptr, tmp_bytes, (const uint32_t*)d_cnt.p, (uint32_t*)d_base.p, 0u, (size_t)n2,
                                       rocprim::plus<uint32_t>()));
@@ -853,8 +899,9 @@ static bool finish_gpu_t(Graph& g, const std::vector<KT>& kmers, int device,
     G2S_GPU_TRY(hipMemcpy(d_flip.p, g.flip.data(), (size_t)n, hipMemcpyHostToDevice));
   }
   // ---- tables in id space
-  Dev d_sid, d_last, d_i2r, d_us;
+  Dev d_sid, d_pid, d_last, d_i2r, d_us;
   const size_t sbytes = (size_t)n2 * 16;
+  if constexpr (EVEN) G2S_GPU_TRY(d_pid.alloc(sbytes));
   const size_t words = (size_t)((n + 63) / 64 + 1);
   G2S_GPU_TRY(d_sid.alloc(sbytes + 1024));  // the LDS tier may read past the end: INVALID padding
   G2S_GPU_TRY(hipMemset(d_sid.p, 0xFF, sbytes + 1024));
@@ -862,18 +909,21 @@ static bool finish_gpu_t(Graph& g, const std::vector<KT>& kmers, int device,
   G2S_GPU_TRY(d_i2r.alloc((size_t)n * 4));
   G2S_GPU_TRY(d_us.alloc((words + 2 * kUstartPad) * 8));
   G2S_GPU_TRY(hipMemset(d_us.p, 0xFF, (words + 2 * kUstartPad) * 8));
-  hipLaunchKernelGGL(k_remap<KT>, grd, blk, 0, 0, (const KT*)d_km.p, (const uint32_t*)d_succ.p, (const uint32_t*)d_id.p,
-                     (const uint8_t*)d_flip.p, n2, k, (uint32_t*)d_sid.p, (uint8_t*)d_last.p, (uint32_t*)d_i2r.p);
+  hipLaunchKernelGGL((k_remap<KT, EVEN>), grd, blk, 0, 0, (const KT*)d_km.p, (const uint32_t*)d_succ.p, (const uint32_t*)d_pred.p,
+                     (const uint32_t*)d_id.p, (const uint8_t*)d_flip.p, n2, k, (uint32_t*)d_sid.p, (uint32_t*)d_pid.p,
+                     (uint8_t*)d_last.p, (uint32_t*)d_i2r.p);
   const uint32_t nbits = (uint32_t)(words * 64);
   hipLaunchKernelGGL(k_ustart, dim3((nbits + 255) / 256), blk, 0, 0, (const uint32_t*)d_sid.p, (uint32_t)n, nbits,
                      (uint64_t*)d_us.p + kUstartPad);
   G2S_GPU_TRY(hipGetLastError());
   g.succ.resize((size_t)n2 * 4);
   g.pred.clear();
+  if constexpr (EVEN) g.pred.resize((size_t)n2 * 4);
   g.lastnt.resize((size_t)n2);
   g.id2rank.resize((size_t)n);
   g.ustart.resize(words);
   G2S_GPU_TRY(hipMemcpy(g.succ.data(), d_sid.p, sbytes, hipMemcpyDeviceToHost));
+  if constexpr (EVEN) G2S_GPU_TRY(hipMemcpy(g.pred.data(), d_pid.p, sbytes, hipMemcpyDeviceToHost));
   G2S_GPU_TRY(hipMemcpy(g.lastnt.data(), d_last.p, (size_t)n2, hipMemcpyDeviceToHost));
   G2S_GPU_TRY(hipMemcpy(g.id2rank.data(), d_i2r.p, (size_t)n * 4, hipMemcpyDeviceToHost));
   G2S_GPU_TRY(hipMemcpy(g.ustart.data(), (uint64_t*)d_us.p + kUstartPad, words * 8, hipMemcpyDeviceToHost));
@@ -886,9 +936,21 @@ static bool finish_gpu_t(Graph& g, const std::vector<KT>& kmers, int device,
   dg.succ = (uint32_t*)d_sid.release();
   dg.ustart = (uint64_t*)d_us.release() + kUstartPad;
   dg.bytes = sbytes + (words + 2 * kUstartPad) * 8;
+  if constexpr (EVEN) {
+    dg.pred = (uint32_t*)d_pid.release();
+    dg.bytes += sbytes;
+  }
   g.dev[device] = dg;
   return true;
 #undef G2S_GPU_TRY
+}
+
+template <class KT>
+static bool finish_gpu_t(Graph& g, const std::vector<KT>& kmers, int device,
+                         const std::function<void(const std::vector<uint32_t>&, uint32_t)>& host_walk, std::string* why,
+                         const std::vector<uint32_t>* rank_set = nullptr) {
+  return (g.k % 2) == 0 ? finish_gpu_e<KT, true>(g, kmers, device, host_walk, why, rank_set)
+                        : finish_gpu_e<KT, false>(g, kmers, device, host_walk, why, rank_set);
 }
 
 // The sorted set of solid canonical k-mers and its prefix index, from the reads.  One key per
@@ -1227,7 +1289,6 @@ static bool count_solid_sets_gpu_t(Graph& g, std::vector<KT>& out, std::vector<u
 bool graph_build_sets_gpu(Graph& g, const std::vector<std::pair<const char*, uint64_t>>& seqs, const std::vector<uint32_t>& seq_set,
                           uint32_t nsets, int solid, int device,
                           const std::function<void(const std::vector<uint32_t>&, uint32_t)>& host_walk, std::string* why) {
-  if ((g.k % 2) == 0) { if (why) *why = "even k"; return false; }
   std::vector<uint32_t> rank_set;
   bool ok;
   if (g.kmer_bytes == 32) ok = count_solid_sets_gpu_t<u256>(g, g.kmers256, &rank_set, seqs, seq_set, nsets, solid, device, why);
@@ -1632,7 +1693,6 @@ bool graph_build_pool_gpu(Graph& g, const PoolSets& ps, int solid, int device,
                           const std::function<void(const std::vector<uint32_t>&, uint32_t)>& host_walk, PoolBuildInfo* info,
                           std::string* why, const PoolReach* reach, PoolReachInfo* rinfo, bool* device_usable) {
   if (device_usable) *device_usable = false;
-  if ((g.k % 2) == 0) { if (why) *why = "even k"; return false; }
   std::vector<uint32_t> rank_set;
   bool ok;
   if (g.kmer_bytes == 32) ok = count_solid_pool_gpu_t<u256>(g, g.kmers256, &rank_set, ps, solid, device, info, why, reach, rinfo, device_usable);
@@ -1654,7 +1714,6 @@ bool count_solid_gpu(Graph& g, const std::vector<std::pair<const char*, uint64_t
 
 bool graph_finish_gpu(Graph& g, int device, const std::function<void(const std::vector<uint32_t>&, uint32_t)>& host_walk,
                       std::string* why) {
-  if ((g.k % 2) == 0) { if (why) *why = "even k"; return false; }
   if (g.kmer_bytes == 32) return finish_gpu_t<u256>(g, g.kmers256, device, host_walk, why);
   return g.kmer_bytes == 16 ? finish_gpu_t<u128>(g, g.kmers128, device, host_walk, why)
                             : finish_gpu_t<uint64_t>(g, g.kmers64, device, host_walk, why);

@@ -59,12 +59,15 @@ const char* g2s_last_error(void);
  *  ...") / Graph::load (Gap2Seq.cpp:193-219).  Exact solid canonical k-mer set
  *  (GATB codec A0 C1 T2 G3, canonical = min(fwd, revcomp), k-mers containing
  *  N/n skipped; k in [1, 127]: 64-, 128- or 256-bit k-mers), numbered in unitig order, with a 4-slot successor table per
- *  oriented node in GATB enumeration order (A,C,T,G).  Predecessors are read
- *  from the same table: pred(v)[i] = succ(v^1)[i]^1.
+ *  oriented node in GATB enumeration order (A,C,T,G).  At odd k predecessors are
+ *  read from the same table: pred(v)[i] = succ(v^1)[i]^1.  At even k a k-mer
+ *  can be its own reverse complement; only one strand of such a k-mer exists,
+ *  the identity fails next to it, and the graph carries an explicit
+ *  predecessor table (g2s_graph_predecessors reads whichever applies).
  *  The build itself (k-mer sort, successor table, unitig numbering) runs on
  *  the GPU named by the environment variable G2S_DEVICE (default 0) when there
  *  is one, and the graph then already resides on that device; without a
- *  device, for even k, or with G2S_HOST_BUILD=1 it runs on `nthreads` host
+ *  device or with G2S_HOST_BUILD=1 it runs on `nthreads` host
  *  threads.  Either way the same graph results, up to the numbering of nodes.
  * ------------------------------------------------------------------------ */
 int g2s_graph_build_files(const char* reads_csv, int k, int solid, int nthreads, g2s_graph** out);
@@ -88,7 +91,7 @@ int g2s_graph_build_sets(const char* const* seqs, const uint64_t* lens, const ui
  * set-major numbering, g2s_graph_set_nodes equal (the numbering of nodes inside a set may differ where the host and
  * the device build differ).  A sequence may be in any number of sets and more than once in one set; every occurrence
  * counts towards solidity, as the concatenated FASTA files count it in the reference flow.  No text is copied on the
- * host.  On the device (odd k) the pool's text goes up once, the own lists' k-mers are sorted by (set, k-mer), and the
+ * host.  On the device (any k) the pool's text goes up once, the own lists' k-mers are sorted by (set, k-mer), and the
  * shared list's k-mers are sorted ONCE and merged into every flagged set, so the keys sorted are the own lists'
  * positions plus the shared list's, whatever the number of flagged sets; when the device cannot take it (the own and
  * shared positions reach 2^32, the estimate exceeds half the free device memory — the merge's flagged sets x distinct
@@ -126,7 +129,7 @@ struct g2s_gap;
  * bounded graph as on the whole one.  The bound is safe, not tight: the kept set is the union of the balls round ALL
  * seeds, the right flank's included, so a closing path of L steps is kept whole from radius (L - 1) / 2 on and a fill
  * first changes one below that (tests/test_gpu_pool_reach.py pins both sides).
- *   On the device (odd k) the bounded sets are found by a breadth-first search per set over the own lists' and the
+ *   On the device (any k) the bounded sets are found by a breadth-first search per set over the own lists' and the
  * shared list's sorted count tables — membership of a k-mer is two binary searches, the sets' full graphs are never
  * formed, and the work and the memory follow the k-mers visited plus one bit a (set with a record, distinct shared
  * k-mer) instead of flagged sets x distinct shared k-mers.  When the device cannot take it (the conditions of

@@ -105,7 +105,7 @@ int g2s_test_last_pool_build(uint64_t* own_positions, uint64_t* shared_positions
 
 /* TEST HOOK: what the process's last g2s_graph_build_pool_reach with at least one reach record did.  reach_sets: the
  * sets with a record; full_kmers: the k-mers of those sets' full graphs, valid when *full_known != 0 (the host build
- * counts them when it was the first choice — even k, no device, G2S_HOST_BUILD=1; the device build never forms the
+ * counts them when it was the first choice — no device, G2S_HOST_BUILD=1; the device build never forms the
  * full graphs and does not count them, nor does the host build behind a device build that gave up); kept_kmers: the
  * k-mers those sets hold in the graph; levels: the deepest level any set's search ran (0: seeds only; never more than
  * the largest radius); on_device: the search ran in the device kernel.  Any pointer may be NULL. */
