@@ -25,8 +25,11 @@ struct DeviceGraph {
   uint32_t* succ = nullptr;  // [2n*4]
   uint32_t* pred = nullptr;  // [2n*4], only when k is even (palindromic k-mers exist); the device build leaves its own here
   uint64_t* ustart = nullptr;  // unitig-start bitmap, offset by kUstartPad words of all-ones padding
-  uint32_t* rem = nullptr;     // [2n] unitig-internal steps left from an oriented node (seg_tables.hip), odd k only
+  uint32_t* rem = nullptr;     // [2n] unitig-internal steps left from an oriented node (seg_tables.hip)
   uint32_t* urec = nullptr;    // [2n][8] successor record of the end of the node's unitig walk + rem (seg_tables.hip)
+  uint32_t* brec = nullptr;    // [2n][8] the same for walks backwards, only beside pred (seg_tables.h); odd k: urec serves
+  // what the segment tier's kernels walk backwards with, and where they read a node's predecessors in slot order
+  const uint32_t* back_table() const { return brec ? brec : urec; }
   uint64_t bytes = 0;
 };
 

@@ -20,6 +20,18 @@
 
 namespace g2s {
 
+// The graph's tables as the segment tier reads them (seg_tables.h).  back: the records of backward walks — urec itself
+// on a graph without a predecessor table (odd k: walking back from v is walking on from v ^ 1), brec beside one.  ptab,
+// pflip: a node v's predecessors in slot order are the row of v ^ pflip in ptab, each word ^ pflip: (succ, 1) without a
+// predecessor table, (pred, 0) with one.
+struct SegGraph {
+  const uint32_t* succ = nullptr;
+  const uint32_t* urec = nullptr;
+  const uint32_t* back = nullptr;
+  const uint32_t* ptab = nullptr;
+  uint32_t pflip = 1u;
+};
+
 // resident mode, deep lists: where g2s_fill_segw puts the closures the host will analyse the moment their gaps end
 // (SegArgs.early_*: device-visible pinned memory, the counters in device memory)
 struct SegEarly {
@@ -59,7 +71,7 @@ size_t fill_seg_lds_bytes();
 uint32_t fill_seg_dbg_words();  // words per gap of the optional diagnostics buffer
 // phases A-D1 of every listed gap in one launch; results land in pinned host memory exactly as
 // the LDS tier leaves them (GapOut per gap, closures packed by an atomic cursor, completion list)
-hipError_t launch_fill_seg(hipStream_t st, uint32_t ngaps, const uint32_t* succ, const uint32_t* urec /* seg_tables.hip */,
+hipError_t launch_fill_seg(hipStream_t st, uint32_t ngaps, const SegGraph& graph /* seg_tables.hip */,
                            const GapDev* gaps,
                            const uint32_t* gap_ids, const uint32_t* flank_nodes, SubRec* sub_out /* pinned host */,
                            unsigned long long out_cap /* records */, unsigned long long* out_counter, GapOut* outs,
@@ -99,7 +111,7 @@ hipError_t launch_fill_seg(hipStream_t st, uint32_t ngaps, const uint32_t* succ,
 size_t fill_segw_lds_bytes();
 size_t fill_segw_scratch_bytes(uint32_t workgroups);
 uint32_t fill_segx_dbg_words();  // words per gap of the large variant's optional diagnostics buffer
-hipError_t launch_fill_segw(hipStream_t st, uint32_t ngaps, uint32_t workgroups, const uint32_t* succ, const uint32_t* urec,
+hipError_t launch_fill_segw(hipStream_t st, uint32_t ngaps, uint32_t workgroups, const SegGraph& graph,
                             const GapDev* gaps, const uint32_t* gap_ids, const uint32_t* flank_nodes, SubRec* sub_out,
                             unsigned long long out_cap, unsigned long long* out_counter, GapOut* outs, GapOut* outs_host,
                             uint32_t* done_list, int skip_confident, uint32_t* dbg, uint32_t* scratch,

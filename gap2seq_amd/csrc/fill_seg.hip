@@ -251,6 +251,7 @@ template <bool TWO>
 __device__ __forceinline__ void seg_fill_one(uint32_t* lds, const SegArgs& A, const uint32_t x /* position in the launch */) {
   const uint32_t* __restrict__ succ = A.succ;
   const uint32_t* __restrict__ urec = A.urec;
+  const uint32_t* __restrict__ back = A.back;  // urec itself without a predecessor table (fill_seg.h: SegGraph)
   const uint32_t* __restrict__ gap_ids = A.gap_ids;
   const uint32_t* __restrict__ flank_nodes = A.flank_nodes;
   SubRec* sub_out = A.sub_out;
@@ -541,7 +542,7 @@ __device__ __forceinline__ void seg_fill_one(uint32_t* lds, const SegArgs& A, co
         if (imp) { aq0[(uint32_t)__popcll(m & below(lane))] = sd; aqs[(uint32_t)__popcll(m & below(lane))] = at; }
         if constexpr (TWO) {
           if (imp) {
-            const uint4* u = (const uint4*)(urec + (size_t)(sd ^ 1u) * 8);
+            const uint4* u = (const uint4*)(back + (size_t)(sd ^ 1u) * 8);
             qrec[(uint32_t)__popcll(m & below(lane))] = u[0];
             qrem[(uint32_t)__popcll(m & below(lane))] = u[1].x;
           }
@@ -576,14 +577,16 @@ __device__ __forceinline__ void seg_fill_one(uint32_t* lds, const SegArgs& A, co
           const uint32_t slot = mine ? qcs[eidx] : 0u;
           // walking back from v = walking on from v^1: steps left in the unitig and the successor record
           // of the walk's last node (graph.predecessors(last)[i] = succ(last^1)[i] ^ 1) in one record,
-          // asked for before the entry's label is read (the label comes from LDS while the record travels)
+          // asked for before the entry's label is read (the label comes from LDS while the record travels).
+          // (That identity is the graph's without a predecessor table; beside one the record is brec's, which
+          // holds the predecessors themselves, flipped: seg_tables.h)
           uint32_t w = G2S_DEV_INVALID, r = 0;
           if (mine) {
             if constexpr (TWO) {
               w = ((const uint32_t*)(qcr + eidx))[q];
               r = qcm[eidx];
             } else {
-              const uint32_t* u = urec + (size_t)(v ^ 1u) * 8;
+              const uint32_t* u = back + (size_t)(v ^ 1u) * 8;
               w = u[q];
               r = u[4];
             }
@@ -606,7 +609,7 @@ __device__ __forceinline__ void seg_fill_one(uint32_t* lds, const SegArgs& A, co
           uint32_t prem = 0u;
           if constexpr (TWO) {
             if (act) {
-              const uint4* u = (const uint4*)(urec + (size_t)w * 8);  // (pnode ^ 1 = w)
+              const uint4* u = (const uint4*)(back + (size_t)w * 8);  // (pnode ^ 1 = w)
               prec = u[0];
               prem = u[1].x;
             }
@@ -1423,13 +1426,15 @@ __device__ __forceinline__ void seg_fill_one(uint32_t* lds, const SegArgs& A, co
         const uint32_t ps[4] = {p01 & 0xFFFFu, p01 >> 16, p23 & 0xFFFFu, p23 >> 16};
         const uint32_t k = (ps[0] != SEG_NOPAR) + (ps[1] != SEG_NOPAR) + (ps[2] != SEG_NOPAR) + (ps[3] != SEG_NOPAR);
         // Several parents: the traceback picks predecessors(v)[rand() % n] (:1476-1513), i.e. in GATB's
-        // neighbour order.  predecessors(v)[i] = succ(v^1)[i] ^ 1, so the slot of a parent is where its last
-        // node shows up in v's record of the table; sorted here, the host's sequential in-order pass and
+        // neighbour order.  predecessors(v)[i] = succ(v^1)[i] ^ 1 without a predecessor table, the table's row of
+        // v beside one (seg_tables.h), so the slot of a parent is where its last node shows up in that row (ptab,
+        // pflip: fill_seg.h); sorted here, the host's sequential in-order pass and
         // the tracebacks do not have to look the order up per segment (G2S_SEG_ORDERED).
         uint32_t key[4] = {0u, 1u, 2u, 3u}, id[4];
         bool ordered = true;
         uint4 sr = make_uint4(G2S_DEV_INVALID, G2S_DEV_INVALID, G2S_DEV_INVALID, G2S_DEV_INVALID);
-        if (k > 1u) sr = *(const uint4*)(succ + (size_t)(v0 ^ 1u) * 4);
+        // (v's predecessors in slot order: succ(v^1)[i] ^ 1, or the row of the predecessor table where the graph has one)
+        if (k > 1u) sr = *(const uint4*)(A.ptab + (size_t)(v0 ^ A.pflip) * 4);
 #pragma unroll
         for (int q = 0; q < 4; q++) {
           id[q] = SEG_NOPAR;
@@ -1437,7 +1442,7 @@ __device__ __forceinline__ void seg_fill_one(uint32_t* lds, const SegArgs& A, co
           id[q] = s_aux[ps[q]];
           if (k > 1u) {
             const uint32_t pn = s_node[ps[q]];
-            const uint32_t pl = seg_node(pn, (s_dl[ps[q]] >> 16) - 1u) ^ 1u;  // the parent's last node, flipped
+            const uint32_t pl = seg_node(pn, (s_dl[ps[q]] >> 16) - 1u) ^ A.pflip;  // the parent's last node as the row names it
             key[q] = sr.x == pl ? 0u : sr.y == pl ? 1u : sr.z == pl ? 2u : sr.w == pl ? 3u : 4u;
             if (key[q] == 4u) ordered = false;  // (cannot happen on a consistent table: the host sorts then)
           }
@@ -1782,7 +1787,7 @@ size_t fill_seg2_lds_bytes() {  // (... + the next round's records: 2 x 64 x set
 uint32_t fill_seg_dbg_words() { return 8u + 2u * 64u * G2S_SEG_ASETS + 6u * G2S_SEG_CAP + 14u; }  // (+14: profile words)
 uint32_t fill_segx_dbg_words() { return 8u + 2u * G2S_SEGX_EA + 6u * G2S_SEGX_CAP + 14u; }
 
-hipError_t launch_fill_seg(hipStream_t st, uint32_t ngaps, const uint32_t* succ, const uint32_t* urec, const GapDev* gaps,
+hipError_t launch_fill_seg(hipStream_t st, uint32_t ngaps, const SegGraph& graph, const GapDev* gaps,
                            const uint32_t* gap_ids, const uint32_t* flank_nodes, SubRec* sub_out,
                            unsigned long long out_cap, unsigned long long* out_counter, GapOut* outs, GapOut* outs_host,
                            uint32_t* done_list, int skip_confident, uint32_t* dbg, bool two_waves, unsigned long long* xcd_tickets,
@@ -1804,7 +1809,7 @@ hipError_t launch_fill_seg(hipStream_t st, uint32_t ngaps, const uint32_t* succ,
     }
   }
   if (!xcd_tickets || !xcd_list || pub_batch < 2u || pub_batch > 64u || (pub_batch & (pub_batch - 1u))) pub_batch = 1u;
-  const SegArgs A = {succ, urec, GapSrc{gaps, resident ? lite : nullptr, lite_e, lite_all_paths}, gap_ids, flank_nodes, sub_out, out_cap, out_counter, outs, outs_host, done_list,
+  const SegArgs A = {graph.succ, graph.urec, graph.back, graph.ptab, graph.pflip, GapSrc{gaps, resident ? lite : nullptr, lite_e, lite_all_paths}, gap_ids, flank_nodes, sub_out, out_cap, out_counter, outs, outs_host, done_list,
                      skip_confident, dbg, fill_seg_dbg_words(), xcd_tickets, xcd_list, xcd_stride, pub_batch, resident ? 1u : 0u,
                      (resident && d2_list) ? g2s::d2_ticks_offset : 0u, resident ? ovf_list : nullptr,
                      (resident && early) ? early->segs : nullptr, (resident && early) ? early->items : nullptr,

@@ -107,6 +107,7 @@ __device__ __forceinline__ void segw_fill_one(uint32_t* lds, const SegArgs& A, c
   constexpr uint32_t PE = G2S_SEGX_PE, HS = G2S_SEGX_HS;
   const uint32_t* __restrict__ succ = A.succ;
   const uint32_t* __restrict__ urec = A.urec;
+  const uint32_t* __restrict__ back = A.back;  // urec itself without a predecessor table (fill_seg.h: SegGraph)
   SubRec* sub_out = A.sub_out;
   const unsigned long long out_cap = A.out_cap;
   unsigned long long* out_counter = A.out_counter;
@@ -233,10 +234,12 @@ __device__ __forceinline__ void segw_fill_one(uint32_t* lds, const SegArgs& A, c
         const bool mine = e < ne;
         const uint32_t v = mine ? qc[e] : 0u;
         // walking back from v = walking on from v^1: steps left in the unitig and the successor record of the
-        // walk's last node (graph.predecessors(last)[i] = succ(last^1)[i] ^ 1) in one record
+        // walk's last node (graph.predecessors(last)[i] = succ(last^1)[i] ^ 1) in one record.  (That identity is the
+        // graph's without a predecessor table; beside one the record is brec's, which holds the predecessors themselves,
+        // flipped: seg_tables.h)
         uint32_t w = G2S_DEV_INVALID, r = 0;
         if (mine) {
-          const uint32_t* u = urec + (size_t)(v ^ 1u) * 8;
+          const uint32_t* u = back + (size_t)(v ^ 1u) * 8;
           w = u[q];
           r = u[4];
         }
@@ -303,7 +306,7 @@ __device__ __forceinline__ void segw_fill_one(uint32_t* lds, const SegArgs& A, c
       if (e < nA) {
         const uint64_t ent = pk[e];
         const uint32_t v = (uint32_t)(ent >> 32), label = (uint32_t)ent;
-        const uint32_t r = urec[(size_t)(v ^ 1u) * 8 + 4];
+        const uint32_t r = back[(size_t)(v ^ 1u) * 8 + 4];
         const uint32_t steps = min(r, (uint32_t)gd.right_half - label);
         const uint32_t w0 = v ^ 1u, idx = w0 >> 1;
         const uint32_t lo = (w0 & 1u) ? idx - steps : idx, hi = (w0 & 1u) ? idx : idx + steps;
@@ -1240,7 +1243,8 @@ __device__ __forceinline__ void segw_fill_one(uint32_t* lds, const SegArgs& A, c
         uint32_t key[4] = {0u, 1u, 2u, 3u}, id[4];
         bool ordered = true;
         uint4 sr = make_uint4(G2S_DEV_INVALID, G2S_DEV_INVALID, G2S_DEV_INVALID, G2S_DEV_INVALID);
-        if (k > 1u) sr = *(const uint4*)(succ + (size_t)(v0 ^ 1u) * 4);
+        // (v's predecessors in slot order: succ(v^1)[i] ^ 1, or the row of the predecessor table where the graph has one)
+        if (k > 1u) sr = *(const uint4*)(A.ptab + (size_t)(v0 ^ A.pflip) * 4);
 #pragma unroll
         for (int q = 0; q < 4; q++) {
           id[q] = SEG_NOPAR;
@@ -1248,7 +1252,7 @@ __device__ __forceinline__ void segw_fill_one(uint32_t* lds, const SegArgs& A, c
           id[q] = s_aux[ps[q]];
           if (k > 1u) {
             const uint32_t pn = s_node[ps[q]];
-            const uint32_t pl = seg_node(pn, (s_dl[ps[q]] >> 16) - 1u) ^ 1u;  // the parent's last node, flipped
+            const uint32_t pl = seg_node(pn, (s_dl[ps[q]] >> 16) - 1u) ^ A.pflip;  // the parent's last node as the row names it
             key[q] = sr.x == pl ? 0u : sr.y == pl ? 1u : sr.z == pl ? 2u : sr.w == pl ? 3u : 4u;
             if (key[q] == 4u) ordered = false;  // (cannot happen on a consistent table: the host sorts then)
           }
@@ -1354,7 +1358,7 @@ namespace g2s {
 size_t fill_segw_lds_bytes() { return 4u * SEGW_LDS_WORDS; }
 size_t fill_segw_scratch_bytes(uint32_t workgroups) { return (size_t)workgroups * SEGW_SCR_WORDS * 4u; }
 
-hipError_t launch_fill_segw(hipStream_t st, uint32_t ngaps, uint32_t workgroups, const uint32_t* succ, const uint32_t* urec,
+hipError_t launch_fill_segw(hipStream_t st, uint32_t ngaps, uint32_t workgroups, const SegGraph& graph,
                             const GapDev* gaps, const uint32_t* gap_ids, const uint32_t* flank_nodes, SubRec* sub_out,
                             unsigned long long out_cap, unsigned long long* out_counter, GapOut* outs, GapOut* outs_host,
                             uint32_t* done_list, int skip_confident, uint32_t* dbg, uint32_t* scratch,
@@ -1364,7 +1368,7 @@ hipError_t launch_fill_segw(hipStream_t st, uint32_t ngaps, uint32_t workgroups,
   const size_t bytes = fill_segw_lds_bytes();
   hipError_t e = hipFuncSetAttribute((const void*)g2s_fill_segw, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
   if (e != hipSuccess) return e;
-  SegArgs A = {succ, urec, GapSrc{gaps, resident ? lite : nullptr, lite_e, lite_all_paths}, gap_ids, flank_nodes, sub_out, out_cap, out_counter, outs, outs_host, done_list,
+  SegArgs A = {graph.succ, graph.urec, graph.back, graph.ptab, graph.pflip, GapSrc{gaps, resident ? lite : nullptr, lite_e, lite_all_paths}, gap_ids, flank_nodes, sub_out, out_cap, out_counter, outs, outs_host, done_list,
                skip_confident, dbg, fill_segx_dbg_words(), nullptr, nullptr, 0u, 1u, resident ? 1u : 0u,
                (resident && d2_list) ? d2_ticks_offset : 0u, nullptr, early ? early->segs : nullptr, early ? early->items : nullptr, early ? early->outs : nullptr,
                early ? early->ctr : nullptr, early ? early->cap_items : 0u, early ? early->cap_segs : 0u, resident ? d2_list : nullptr, resident ? d2_tag : 0u};

@@ -283,6 +283,7 @@ extern "C" void g2s_graph_free(g2s_graph* g) {
         if (kv.second.ustart) (void)hipFree(kv.second.ustart - kUstartPad);
         if (kv.second.rem) (void)hipFree(kv.second.rem);
         if (kv.second.urec) (void)hipFree(kv.second.urec);
+        if (kv.second.brec) (void)hipFree(kv.second.brec);
       }
     }
     delete g->g;
@@ -804,20 +805,60 @@ struct InternalCall {
   do { if (lists_in_flight(s)) return fail(G2S_ERR_STATE, who ": lists are in flight on this session (g2s_fill_end them first)"); } while (0)
 }  // namespace
 
+// the segment tier's tables of an uploaded graph, derived on the device from the bitmap that is already there (the
+// device is current)
+static int ensure_seg_tables(g2s_graph* g, int device) {
+  DeviceGraph& dg = g->g->dev.at(device);
+  if (dg.rem || g->g->n == 0) return G2S_OK;
+  // all of them or none: dg.rem is what the gates and this function's early return read, so it is set last, and a table
+  // that fails takes the ones before it along (a later session on the graph builds them again)
+  uint32_t *rem = nullptr, *urec = nullptr, *brec = nullptr;
+  hipError_t e = build_rem_table(dg.ustart, g->g->n, &rem);
+  if (e == hipSuccess) e = build_urec_table(dg.succ, rem, g->g->n, &urec);
+  // even k: backward walks have a table of their own (next to a palindrome pred(v) is not succ(v ^ 1) ^ 1)
+  if (e == hipSuccess && dg.pred) e = build_brec_table(dg.succ, dg.pred, rem, g->g->n, &brec);
+  if (e != hipSuccess) {
+    if (brec) (void)hipFree(brec);
+    if (urec) (void)hipFree(urec);
+    if (rem) (void)hipFree(rem);
+    return fail(G2S_ERR_HIP, std::string("the segment tier's tables: ") + hipGetErrorString(e));
+  }
+  dg.urec = urec;
+  dg.brec = brec;
+  dg.rem = rem;
+  dg.bytes += g->g->n * (8 + 64 + (brec ? 64 : 0));
+  return G2S_OK;
+}
+static g2s::SegGraph seg_graph(const DeviceGraph& dg) {
+  g2s::SegGraph t;
+  t.succ = dg.succ;
+  t.urec = dg.urec;
+  t.back = dg.back_table();
+  t.ptab = dg.pred ? dg.pred : dg.succ;
+  t.pflip = dg.pred ? 0u : 1u;
+  return t;
+}
+// TEST HOOK (include/g2s_test.h)
+extern "C" int g2s_test_seg_back_record(g2s_graph* g, int device, uint32_t node, uint32_t out[5]) {
+  g2s_env_sync();
+  if (!g || !out || (uint64_t)node >= 2 * g->g->n) return fail(G2S_ERR_ARG, "g2s_test_seg_back_record: bad argument");
+  int rc = g2s_graph_upload(g, device);
+  if (rc != G2S_OK) return rc;
+  HIP_TRY(hipSetDevice(device));
+  rc = ensure_seg_tables(g, device);
+  if (rc != G2S_OK) return rc;
+  HIP_TRY(hipMemcpy(out, g->g->dev.at(device).back_table() + (size_t)(node ^ 1u) * 8, 5 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  return G2S_OK;
+}
+
 extern "C" int g2s_session_create(g2s_graph* g, int device, const g2s_params* p, g2s_session** out) {
   g2s_env_sync();
   if (!g || !p || !out) return fail(G2S_ERR_ARG, "g2s_session_create: bad argument");
   int rc = g2s_graph_upload(g, device);
   if (rc != G2S_OK) return rc;
   HIP_TRY(hipSetDevice(device));
-  {  // the segment tier's table, derived on the device from the bitmap that is already there
-    DeviceGraph& dg = g->g->dev.at(device);
-    if (!dg.rem && !dg.pred && g->g->n > 0) {
-      HIP_TRY(build_rem_table(dg.ustart, g->g->n, &dg.rem));
-      HIP_TRY(build_urec_table(dg.succ, dg.rem, g->g->n, &dg.urec));
-      dg.bytes += g->g->n * (8 + 64);
-    }
-  }
+  rc = ensure_seg_tables(g, device);
+  if (rc != G2S_OK) return rc;
   g2s_session* s = new g2s_session();
   {
     int cus = 0;
@@ -1107,7 +1148,7 @@ static bool resident_applicable(const g2s_session* s, size_t n) {
   auto it = g.dev.find(s->device);
   if (it == g.dev.end()) return false;
   const DeviceGraph& dg = it->second;
-  return dg.pred == nullptr && dg.rem != nullptr && !s->no_lds_tier && g.n < (1ull << 28) - 1;
+  return dg.rem != nullptr && !s->no_lds_tier && g.n < (1ull << 28) - 1;
 }
 
 extern "C" int g2s_batch_prepare(g2s_session* s, const g2s_gap* gaps, size_t n, g2s_batch** out) {
@@ -1617,13 +1658,13 @@ int run_tier(g2s_batch* b, const std::vector<uint32_t>& ids, uint64_t scale, uin
       // one persistent workgroup per compute unit (the variant takes nearly all of a CU's LDS)
       const uint32_t wgs = (uint32_t)std::min<size_t>(ids.size(), (size_t)std::max(1, s->num_cus));
       HIP_TRY(s->d_segx.ensure(fill_segw_scratch_bytes(wgs)));
-      HIP_TRY(launch_fill_segw(st, (uint32_t)ids.size(), wgs, dg.succ, dg.urec, gaps_dev, ids_dev, (const uint32_t*)s->d_flank.p,
+      HIP_TRY(launch_fill_segw(st, (uint32_t)ids.size(), wgs, seg_graph(dg), gaps_dev, ids_dev, (const uint32_t*)s->d_flank.p,
                                (SubRec*)d_subs_host, (unsigned long long)out_states, (unsigned long long*)s->d_counter.p,
                                (GapOut*)s->d_outs.p, (GapOut*)d_outs_host, (uint32_t*)d_done_host,
                                s->params.skip_confident ? 1 : 0, seg_dbg, (uint32_t*)s->d_segx.p,
                                (unsigned long long*)s->d_counter.p + 2));
     } else if (seg)
-      HIP_TRY(launch_fill_seg(st, (uint32_t)ids.size(), dg.succ, dg.urec, gaps_dev, ids_dev, (const uint32_t*)s->d_flank.p,
+      HIP_TRY(launch_fill_seg(st, (uint32_t)ids.size(), seg_graph(dg), gaps_dev, ids_dev, (const uint32_t*)s->d_flank.p,
                               (SubRec*)d_subs_host, (unsigned long long)out_states, (unsigned long long*)s->d_counter.p,
                               (GapOut*)s->d_outs.p, (GapOut*)d_outs_host, (uint32_t*)d_done_host,
                               s->params.skip_confident ? 1 : 0, seg_dbg,
@@ -2150,12 +2191,14 @@ int batch_stage1(g2s_batch* b, bool analyze, g2s_result* results) {
   // ---- GPU: phases A-D1, retrying gaps whose tables overflowed with 8x larger ones
   std::vector<uint32_t> todo, lds_ids, late1, late2;  // late1/late2: gaps that start in pass 1 / pass 2
   // (the LDS right set keeps 28-bit k-mer indices)
-  const bool lds_ok = s->graph->g->dev.at(s->device).pred == nullptr && !s->no_lds_tier &&
-                      s->graph->g->n < (1ull << 28) - 1;
-  // ---- segment tier first (fill_seg.hip): every gap it can hold (odd k, -fuz <= 31, D < 2^15);
+  const bool idx_ok = !s->no_lds_tier && s->graph->g->n < (1ull << 28) - 1;
+  // (the LDS tier derives predecessors from the successor table: closed to graphs with a predecessor table, even k,
+  // whose gaps go from the segment tier and its large variant straight to the HBM tier)
+  const bool lds_ok = idx_ok && s->graph->g->dev.at(s->device).pred == nullptr;
+  // ---- segment tier first (fill_seg.hip): every gap it can hold (-fuz <= 31, D < 2^15);
   // a gap that outgrows one of its capacities comes back flagged and takes the passes below
   std::vector<char> seg_done(n, 0);
-  const bool seg_ok = lds_ok && s->graph->g->dev.at(s->device).rem != nullptr && !GENV("G2S_NO_SEG_TIER");
+  const bool seg_ok = idx_ok && s->graph->g->dev.at(s->device).rem != nullptr && !GENV("G2S_NO_SEG_TIER");
   if (seg_ok) {
     std::vector<uint32_t> seg_ids;
     for (size_t i = 0; i < n; i++) {
@@ -3282,7 +3325,7 @@ static int resident_launch_fill(g2s_batch* b, ResidentLaunch* rl, g2s_result* re
     }
   }
   s->spec_on = use_tr && tr.spec_text != nullptr;
-  HIP_TRY_S(launch_fill_seg(st, (uint32_t)n_reg, dg.succ, dg.urec, nullptr, ids_fill, (const uint32_t*)s->d_flank.p,
+  HIP_TRY_S(launch_fill_seg(st, (uint32_t)n_reg, seg_graph(dg), nullptr, ids_fill, (const uint32_t*)s->d_flank.p,
                           (SubRec*)s->d_sub.p, (unsigned long long)out_states, (unsigned long long*)s->d_counter.p,
                           (GapOut*)s->d_outs.p, nullptr, nullptr, s->params.skip_confident ? 1 : 0, nullptr, two_waves,
                           nullptr, nullptr, 0u, 1u, true, rerun ? (uint32_t*)s->d_ovf.p : nullptr,
@@ -3300,7 +3343,7 @@ static int resident_launch_fill(g2s_batch* b, ResidentLaunch* rl, g2s_result* re
     const uint32_t wgs1 = (uint32_t)std::min<size_t>(n_early, (size_t)std::max(1, s->num_cus));
     HIP_TRY_S(s->d_segx1.ensure(fill_segw_scratch_bytes(wgs1)));
     HIP_TRY_S(hipStreamWaitEvent(s->stream3, s->ev_pre, 0));
-    HIP_TRY_S(launch_fill_segw(s->stream3, (uint32_t)n_early, wgs1, dg.succ, dg.urec, nullptr, ids_dev + n_reg,
+    HIP_TRY_S(launch_fill_segw(s->stream3, (uint32_t)n_early, wgs1, seg_graph(dg), nullptr, ids_dev + n_reg,
                                (const uint32_t*)s->d_flank.p, (SubRec*)s->d_sub.p, (unsigned long long)out_states,
                                (unsigned long long*)s->d_counter.p, (GapOut*)s->d_outs.p, nullptr, nullptr,
                                s->params.skip_confident ? 1 : 0, nullptr, (uint32_t*)s->d_segx1.p,
@@ -3311,7 +3354,7 @@ static int resident_launch_fill(g2s_batch* b, ResidentLaunch* rl, g2s_result* re
   // (the large variant for what the launch above listed: its workgroups read the list's length from device memory and
   // leave at once when it is empty — the usual case)
   if (rerun)
-    HIP_TRY_S(launch_fill_segw(st, (uint32_t)std::max<size_t>(n_reg, 1), segw_wgs, dg.succ, dg.urec, nullptr, (const uint32_t*)s->d_ovf.p,
+    HIP_TRY_S(launch_fill_segw(st, (uint32_t)std::max<size_t>(n_reg, 1), segw_wgs, seg_graph(dg), nullptr, (const uint32_t*)s->d_ovf.p,
                              (const uint32_t*)s->d_flank.p, (SubRec*)s->d_sub.p, (unsigned long long)out_states,
                              (unsigned long long*)s->d_counter.p, (GapOut*)s->d_outs.p, nullptr, nullptr,
                              s->params.skip_confident ? 1 : 0, nullptr, (uint32_t*)s->d_segx.p,

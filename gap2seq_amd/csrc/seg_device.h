@@ -172,6 +172,10 @@ __device__ __forceinline__ uint32_t lds_merge_intervals(uint64_t* a, uint32_t n,
 struct SegArgs {
   const uint32_t* succ;
   const uint32_t* urec;
+  // backward walks and predecessor slots (fill_seg.h: SegGraph): urec / succ / 1 on a graph without a predecessor table
+  const uint32_t* back;
+  const uint32_t* ptab;
+  uint32_t pflip;
   GapSrc gaps;
   const uint32_t* gap_ids;
   const uint32_t* flank_nodes;

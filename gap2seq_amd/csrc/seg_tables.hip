@@ -83,9 +83,46 @@ __global__ __launch_bounds__(256) void k_urec(const uint32_t* __restrict__ succ,
   urec[2 * v + 1] = make_uint4(r, 0u, 0u, 0u);
 }
 
+// brec[x] (seg_tables.h): the backward counterpart of urec[x] on a graph with a predecessor table.  A strand whose rows are
+// empty in BOTH tables is the missing strand of a palindrome (or a k-mer without any edge, whose other strand has no
+// predecessor either): the walk's far end is then the walk's last node itself.  The inference rests on both builds
+// leaving a palindrome's strand-0 rows INVALID in both tables (dbg.cpp, dbg_gpu.hip), and a loaded .g2s file holds
+// the tables as a build wrote them, so it holds there as well.
+__global__ __launch_bounds__(256) void k_brec(const uint32_t* __restrict__ succ, const uint32_t* __restrict__ pred,
+                                              const uint32_t* __restrict__ rem, uint64_t n2, uint4* __restrict__ brec) {
+  const uint64_t x = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  if (x >= n2) return;
+  const uint32_t r = rem[x];
+  const uint32_t e = (x & 1u) ? (uint32_t)x - 2u * r : (uint32_t)x + 2u * r;
+  const uint32_t b = e ^ 1u;
+  uint4 p = *(const uint4*)(pred + (size_t)b * 4);
+  if ((p.x & p.y & p.z & p.w) == g2s::kInvalidNode) {
+    const uint4 s = *(const uint4*)(succ + (size_t)b * 4);
+    if ((s.x & s.y & s.z & s.w) == g2s::kInvalidNode) p = *(const uint4*)(pred + (size_t)e * 4);
+  }
+  auto flip = [](uint32_t w) -> uint32_t { return w == g2s::kInvalidNode ? w : (w ^ 1u); };
+  brec[2 * x] = make_uint4(flip(p.x), flip(p.y), flip(p.z), flip(p.w));
+  brec[2 * x + 1] = make_uint4(r, 0u, 0u, 0u);
+}
+
 }  // namespace
 
 namespace g2s {
+
+hipError_t build_brec_table(const uint32_t* succ_dev, const uint32_t* pred_dev, const uint32_t* rem_dev, uint64_t n,
+                            uint32_t** brec_out) {
+  *brec_out = nullptr;
+  if (n == 0) return hipSuccess;
+  uint32_t* brec = nullptr;
+  hipError_t e = hipMalloc((void**)&brec, (size_t)n * 64 + 64);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_brec, dim3((unsigned)((2 * n + 255) / 256)), dim3(256), 0, 0, succ_dev, pred_dev, rem_dev, 2 * n, (uint4*)brec);
+  e = hipGetLastError();
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e != hipSuccess) { (void)hipFree(brec); return e; }
+  *brec_out = brec;
+  return hipSuccess;
+}
 
 hipError_t build_urec_table(const uint32_t* succ_dev, const uint32_t* rem_dev, uint64_t n, uint32_t** urec_out) {
   *urec_out = nullptr;

@@ -132,6 +132,7 @@ _SIGS = {
                                            C.POINTER(C.c_uint32), C.POINTER(C.c_int)]),
     "g2s_test_last_pool_build": (C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
                                            C.POINTER(C.c_int)]),
+    "g2s_test_seg_back_record": (C.c_int, [_VP, C.c_int, C.c_uint32, C.POINTER(C.c_uint32)]),
     "g2s_graph_num_sets": (C.c_uint32, [_VP]),
     "g2s_graph_set_nodes": (C.c_int, [_VP, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "g2s_graph_set_node": (C.c_uint32, [_VP, C.c_uint32, C.c_char_p]),
@@ -1078,6 +1079,14 @@ def test_last_pool_reach():
     _check(load_library().g2s_test_last_pool_reach(C.byref(a), C.byref(b), C.byref(known), C.byref(d), C.byref(lv), C.byref(on)))
     return dict(reach_sets=a.value, full_kmers=b.value if known.value else None, kept_kmers=d.value, levels=lv.value,
                 on_device=on.value)
+
+
+def test_seg_back_record(graph, device, node):
+    """TEST HOOK binding (g2s_test_seg_back_record): ([four words], steps) — what the segment tier reads to walk backwards
+    from the oriented node `node`: the far end's predecessors in slot order, orientation bits flipped, and the walk's length"""
+    out = (C.c_uint32 * 5)()
+    _check(load_library().g2s_test_seg_back_record(graph.h, device, node, out))
+    return list(out[:4]), out[4]
 
 
 def test_last_pool_build():

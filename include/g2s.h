@@ -63,7 +63,9 @@ const char* g2s_last_error(void);
  *  read from the same table: pred(v)[i] = succ(v^1)[i]^1.  At even k a k-mer
  *  can be its own reverse complement; only one strand of such a k-mer exists,
  *  the identity fails next to it, and the graph carries an explicit
- *  predecessor table (g2s_graph_predecessors reads whichever applies).
+ *  predecessor table (g2s_graph_predecessors reads whichever applies).  Such a
+ *  graph fills on the same kernels as any other (segment tier, resident mode):
+ *  a session derives the table of their backward walks from the predecessor table.
  *  The build itself (k-mer sort, successor table, unitig numbering) runs on
  *  the GPU named by the environment variable G2S_DEVICE (default 0) when there
  *  is one, and the graph then already resides on that device; without a

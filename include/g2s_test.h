@@ -112,6 +112,14 @@ int g2s_test_last_pool_build(uint64_t* own_positions, uint64_t* shared_positions
 int g2s_test_last_pool_reach(uint64_t* reach_sets, uint64_t* full_kmers, int* full_known, uint64_t* kept_kmers,
                              uint32_t* levels, int* on_device);
 
+/* The record the segment tier's kernels read when they walk BACKWARDS from the oriented node `node` of a graph on
+ * `device` (the graph is uploaded and its tables are built if they are not there yet): out[0..3] = the predecessors, in
+ * slot order and each with its orientation bit flipped (G2S_INVALID_NODE stays), of the node b at which the
+ * unitig-internal walk back from `node` ends; out[4] = the steps of that walk.  At odd k this is the forward record of
+ * node ^ 1; at even k it comes from the explicit predecessor table, and for either id of a palindromic k-mer b is the
+ * palindrome's one node. */
+int g2s_test_seg_back_record(g2s_graph* g, int device, uint32_t node, uint32_t out[5]);
+
 #ifdef __cplusplus
 }
 #endif
