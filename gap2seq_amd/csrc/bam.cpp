@@ -9,23 +9,28 @@
 
 #include <algorithm>
 #include <atomic>
+#include <chrono>
+#include <cstdio>
 #include <cstdlib>
 #include <thread>
+
+#include "bgzf_inflate.h"
+#include "inflate_core.h"
 
 namespace g2s {
 
 namespace {
 inline uint16_t rd16(const uint8_t* p) { return (uint16_t)(p[0] | (p[1] << 8)); }
 inline uint32_t rd32(const uint8_t* p) { uint32_t v; memcpy(&v, p, 4); return v; }  // (little-endian host)
-// inflated bytes per refill (G2S_BAM_CHUNK: the tests make it small so that records span refills)
+// inflated bytes per refill (G2S_BAM_CHUNK: the tests make it small so that records span refills), read when a
+// pass over the file begins
 size_t chunk_bytes() {
-  static const size_t v = [] {
-    const char* e = getenv("G2S_BAM_CHUNK");
-    const long long n = e ? atoll(e) : 0;
-    return n > 0 ? (size_t)n : (size_t)32 << 20;
-  }();
-  return v;
+  const char* e = getenv("G2S_BAM_CHUNK");
+  const long long n = e ? atoll(e) : 0;
+  return n > 0 ? (size_t)n : (size_t)32 << 20;
 }
+// device path: room in front of a page-locked window for the bytes carried over from the window before
+constexpr size_t kDeviceFront = (size_t)256 << 10;
 }  // namespace
 
 BamFile::~BamFile() {
@@ -86,10 +91,20 @@ bool BamFile::index_blocks(std::string* err) {
 struct BamFile::Stream {
   const BamFile& f;
   size_t next_blk = 0;
-  std::vector<uint8_t> buf;
+  std::vector<uint8_t> buf;        // the host path's window
+  const uint8_t* base = nullptr;   // where [lo, hi) is: buf, or a page-locked window of the device path read in place
   size_t lo = 0, hi = 0;
   std::string err;
+  int64_t bad_blk = -1;
+  const size_t chunk = chunk_bytes();
+  // device path: the slot whose window is being read, and the window in flight
+  BgzfDevice* dev = nullptr;
+  int cur = -1, fly = -1;
+  size_t fly_end = 0, fly_beg = 0, fly_bytes = 0, fly_in = 0;
   explicit Stream(const BamFile& file) : f(file) {}
+  ~Stream() {
+    if (dev && fly >= 0) (void)dev->wait(fly, nullptr);  // (a walk that ended early leaves its look-ahead behind)
+  }
 
   static bool inflate_block(z_stream* zs, const BamFile& f, size_t b, uint8_t* out) {
     const uint8_t* blk = f.data_ + f.blk_off_[b];
@@ -100,22 +115,67 @@ struct BamFile::Stream {
     zs->avail_in = f.blk_csize_[b] - f.blk_dataoff_[b] - 8;
     zs->next_out = out;
     zs->avail_out = isize;
-    if (inflate(zs, Z_FINISH) != Z_STREAM_END || zs->avail_out != 0) return false;
+    if (::inflate(zs, Z_FINISH) != Z_STREAM_END || zs->avail_out != 0) return false;
     return (uint32_t)crc32(crc32(0L, Z_NULL, 0), out, isize) == rd32(blk + f.blk_csize_[b] - 8);
+  }
+  // the same with inflate_core.h, CRC by slices as the kernel computes it (set_inflate_core: tests)
+  static bool inflate_block_core(const BamFile& f, size_t b, uint8_t* out) {
+    const uint8_t* blk = f.data_ + f.blk_off_[b];
+    const uint32_t isize = f.blk_isize_[b];
+    if (isize == 0) return true;
+    inflate::Tables T;
+    inflate::HostSink sink{out};
+    if (inflate::inflate_member(blk + f.blk_dataoff_[b], f.blk_csize_[b] - f.blk_dataoff_[b] - 8, isize, &T, sink) != inflate::kOk)
+      return false;
+    return inflate::crc_by_slices(out, isize) == rd32(blk + f.blk_csize_[b] - 8);
+  }
+
+  // the members [b0, e) of the window that starts at b0, and their inflated bytes
+  size_t window_end(size_t b0, size_t* bytes) const {
+    const size_t nb = f.blk_off_.size();
+    size_t e = b0;
+    *bytes = 0;
+    while (e < nb && (e == b0 || *bytes + f.blk_isize_[e] <= chunk)) *bytes += f.blk_isize_[e++];
+    return e;
   }
 
   bool refill() {
+    const auto t0 = std::chrono::steady_clock::now();
+    const bool ok = refill_window();
+    f.stats_.ms_refill += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return ok;
+  }
+
+  bool refill_window() {
     const size_t nb = f.blk_off_.size();
     if (next_blk >= nb || !err.empty()) return false;
-    if (lo) { memmove(buf.data(), buf.data() + lo, hi - lo); hi -= lo; lo = 0; }
-    size_t e = next_blk, bytes = 0;
-    while (e < nb && (e == next_blk || bytes + f.blk_isize_[e] <= chunk_bytes())) bytes += f.blk_isize_[e++];
+    if (f.inflate_device_ >= 0 && !f.dev_refused_) {
+      const int r = refill_device();
+      if (r >= 0) return r == 1;
+    }
+    const size_t left = hi - lo;
+    if (base == buf.data()) {
+      if (lo) memmove(buf.data(), buf.data() + lo, left);
+    } else {  // (bytes left in a device window: the host path goes on from them)
+      if (buf.size() < left) buf.resize(left);
+      if (left) memcpy(buf.data(), base + lo, left);
+    }
+    lo = 0;
+    hi = left;
+    size_t bytes = 0;
+    const size_t e = window_end(next_blk, &bytes);
     if (buf.size() < hi + bytes) buf.resize(hi + bytes);
+    base = buf.data();
     std::vector<size_t> at(e - next_blk);
     for (size_t b = next_blk, o = hi; b < e; b++) { at[b - next_blk] = o; o += f.blk_isize_[b]; }
     const int T = (int)std::min<size_t>((size_t)f.threads_, std::max<size_t>(1, (e - next_blk) / 16));
     std::atomic<size_t> bad{(size_t)-1};
     auto work = [&](int t) {
+      if (f.use_core_) {
+        for (size_t b = next_blk + (size_t)t; b < e; b += (size_t)T)
+          if (!inflate_block_core(f, b, buf.data() + at[b - next_blk])) { bad = b; break; }
+        return;
+      }
       z_stream zs;
       memset(&zs, 0, sizeof zs);
       if (inflateInit2(&zs, -15) != Z_OK) { bad = next_blk; return; }
@@ -130,16 +190,107 @@ struct BamFile::Stream {
       work(0);
       for (auto& x : th) x.join();
     }
-    if (bad.load() != (size_t)-1) { err = "corrupt BGZF block " + std::to_string(bad.load()); return false; }
+    if (bad.load() != (size_t)-1) {
+      bad_blk = (int64_t)bad.load();
+      err = "corrupt BGZF block " + std::to_string(bad.load());
+      return false;
+    }
+    for (size_t b = next_blk; b < e; b++) f.stats_.bytes_in += f.blk_csize_[b];
+    f.stats_.members += e - next_blk;
+    f.stats_.bytes_out += bytes;
+    f.stats_.host_windows++;
     hi += bytes;
     next_blk = e;
     return true;
   }
+
+  // ---- the device path.  Window n is read in place from its slot's page-locked buffer while window n + 1 is on its
+  // way through the other slot: staged, copied up, inflated, copied down, an event at the end.
+  void refuse(const std::string& why) {
+    f.dev_refused_ = true;
+    if (getenv("G2S_DEBUG")) fprintf(stderr, "[g2s] BGZF inflate: the device refused (%s): zlib on the host from block %zu\n",
+                                     why.c_str(), next_blk);
+  }
+  bool issue(int slot, size_t b0, std::string* why) {
+    size_t bytes = 0, in = 0, file_bytes = 0;
+    const size_t e = window_end(b0, &bytes);
+    for (size_t b = b0; b < e; b++) {
+      if (f.blk_isize_[b]) in += ((size_t)(f.blk_csize_[b] - f.blk_dataoff_[b] - 8) + 15) & ~(size_t)15;
+      file_bytes += f.blk_csize_[b];
+    }
+    if (!dev->fits(e - b0, in, bytes)) { *why = "a window larger than the buffers"; return false; }
+    BgzfMember* M = dev->members(slot);
+    uint8_t* hin = dev->in(slot);
+    size_t out = 0;
+    in = 0;
+    for (size_t b = b0; b < e; b++) {
+      const uint8_t* blk = f.data_ + f.blk_off_[b];
+      const uint32_t dl = f.blk_csize_[b] - f.blk_dataoff_[b] - 8, isize = f.blk_isize_[b];
+      M[b - b0] = BgzfMember{in, out, dl, isize, rd32(blk + f.blk_csize_[b] - 8), 0};
+      if (isize) {
+        memcpy(hin + in, blk + f.blk_dataoff_[b], dl);
+        in += ((size_t)dl + 15) & ~(size_t)15;
+      }
+      out += isize;
+    }
+    if (!dev->launch(slot, e - b0, in, bytes, why)) return false;
+    fly = slot;
+    fly_beg = b0;
+    fly_end = e;
+    fly_bytes = bytes;
+    fly_in = file_bytes;
+    return true;
+  }
+  // 1: a window was handed out; 0: a corrupt member (err); -1: the device refused, the host path inflates this window
+  int refill_device() {
+    std::string why;
+    if (!dev && !(dev = f.device_buffers())) return -1;  // (device_buffers has said why)
+    if (fly < 0 && !issue(cur < 0 ? 0 : 1 - cur, next_blk, &why)) { refuse(why); return -1; }
+    if (!dev->wait(fly, &why)) { fly = -1; refuse(why); return -1; }
+    const int slot = fly;
+    fly = -1;
+    const uint32_t* st = dev->status(slot);
+    for (size_t i = 0; i < fly_end - fly_beg; i++)
+      if (st[i] != inflate::kOk) {
+        bad_blk = (int64_t)(fly_beg + i);
+        err = "corrupt BGZF block " + std::to_string(fly_beg + i);
+        return 0;
+      }
+    // the bytes of a record cut by the last window's end go in front of this one
+    const size_t left = hi - lo;
+    uint8_t* win = dev->window(slot);
+    if (left <= dev->front()) {
+      if (left) memcpy(win - left, base + lo, left);
+      base = win - left;
+    } else {  // (a record longer than the room in front: this window is read from the host buffer)
+      if (base == buf.data()) {
+        if (lo) memmove(buf.data(), buf.data() + lo, left);
+        buf.resize(left + fly_bytes);
+      } else {
+        std::vector<uint8_t> nb(left + fly_bytes);
+        memcpy(nb.data(), base + lo, left);
+        buf.swap(nb);
+      }
+      if (fly_bytes) memcpy(buf.data() + left, win, fly_bytes);
+      base = buf.data();
+    }
+    lo = 0;
+    hi = left + fly_bytes;
+    cur = slot;
+    next_blk = fly_end;
+    f.stats_.members += fly_end - fly_beg;
+    f.stats_.bytes_in += fly_in;
+    f.stats_.bytes_out += fly_bytes;
+    f.stats_.device_windows++;
+    if (next_blk < f.blk_off_.size() && !issue(1 - slot, next_blk, &why)) refuse(why);  // (this window is good)
+    return 1;
+  }
+
   // n contiguous bytes at the read position, or null at the end of the stream / on an error
   const uint8_t* need(size_t n) {
     while (hi - lo < n)
       if (!refill()) return nullptr;
-    return buf.data() + lo;
+    return base + lo;
   }
   void consume(size_t n) { lo += n; }
   bool skip(uint64_t n) {
@@ -153,6 +304,53 @@ struct BamFile::Stream {
   }
   size_t left() const { return hi - lo; }
 };
+
+void BamFile::set_inflate_device(int device) {
+  if (device != inflate_device_) { dev_.reset(); dev_refused_ = false; }
+  inflate_device_ = device < 0 ? -1 : device;
+}
+
+// the buffers of the device path, sized by the file's largest window
+BgzfDevice* BamFile::device_buffers() const {
+  if (dev_) return dev_.get();
+  Stream s(*this);
+  size_t max_in = 0, max_out = 0, max_members = 0;
+  for (size_t b = 0; b < blk_off_.size();) {
+    size_t bytes = 0, in = 0;
+    const size_t e = s.window_end(b, &bytes);
+    for (size_t i = b; i < e; i++)
+      if (blk_isize_[i]) in += ((size_t)(blk_csize_[i] - blk_dataoff_[i] - 8) + 15) & ~(size_t)15;
+    max_in = std::max(max_in, in);
+    max_out = std::max(max_out, bytes);
+    max_members = std::max(max_members, e - b);
+    b = e;
+  }
+  std::string why;
+  dev_.reset(BgzfDevice::create(inflate_device_, max_in, max_out, max_members, kDeviceFront, &why));
+  if (!dev_) {
+    dev_refused_ = true;
+    if (getenv("G2S_DEBUG")) fprintf(stderr, "[g2s] BGZF inflate: the device refused (%s): zlib on the host\n", why.c_str());
+  }
+  return dev_.get();
+}
+
+bool BamFile::open_bgzf(const void* bytes, size_t n, std::string* err) {
+  data_ = (const uint8_t*)bytes;
+  size_ = n;
+  return index_blocks(err);
+}
+
+bool BamFile::read_all(std::vector<uint8_t>* out, std::string* err, int64_t* bad_block) const {
+  Stream s(*this);
+  out->clear();
+  while (s.refill()) {
+    out->insert(out->end(), s.base + s.lo, s.base + s.hi);
+    s.lo = s.hi;
+  }
+  if (bad_block) *bad_block = s.bad_blk;
+  if (!s.err.empty()) { *err = s.err; return false; }
+  return true;
+}
 
 // BAM header (SAM specification 4.2): magic, SAM text, reference names and lengths
 bool BamFile::read_header(std::string* err) {

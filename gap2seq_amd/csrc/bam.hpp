@@ -1,5 +1,6 @@
 // gap2seq_amd/csrc/bam.hpp — a BAM reader for the read filter (readfilter.cpp): BGZF blocks
-// inflated with zlib, several blocks at a time on a few threads, records handed to a callback
+// inflated with zlib, several blocks at a time on a few threads — or on the GPU (set_inflate_device,
+// bgzf_inflate.hip), a window ahead of the records being walked — records handed to a callback
 // in file order.  It replaces the part of htslib the reference's ReadFilter uses
 // (/root/reference/src/ReadFilter.cpp:66-101 io_t, :176-222 sam_iterator): open, header,
 // "every record" and "records overlapping [beg, end) of one reference".  No index is read:
@@ -12,10 +13,13 @@
 #include <cstdint>
 #include <cstring>
 #include <functional>
+#include <memory>
 #include <string>
 #include <vector>
 
 namespace g2s {
+
+class BgzfDevice;
 
 enum : uint32_t {
   BAM_PAIRED = 1, BAM_UNMAPPED = 4, BAM_MATE_UNMAPPED = 8, BAM_REVERSE = 16, BAM_READ1 = 64, BAM_READ2 = 128
@@ -60,6 +64,24 @@ class BamFile {
   bool for_each(const std::function<bool(const BamRec&)>& fn, std::string* err) const;
   void set_threads(int t) { threads_ = t < 1 ? 1 : t; }
   size_t blocks() const { return blk_off_.size(); }
+  // Where for_each / read_all inflate.  device >= 0: the members of a window are inflated by g2s_bgzf_inflate on that
+  // device while the window before is being walked; a device that refuses (no usable gfx950, an allocation or a HIP
+  // call that fails) hands the file to the host path for good, silently (G2S_DEBUG=1 prints why).  -1: zlib on host
+  // threads.  A corrupt member is the same error on either.
+  void set_inflate_device(int device);
+  // test paths (g2s_test_bgzf_inflate): the host path with inflate_core.h in zlib's place; any BGZF file, no BAM header
+  void set_inflate_core(bool on) { use_core_ = on; }
+  bool open_bgzf(const void* bytes, size_t n, std::string* err);
+  // the whole inflated stream; false: *err, and *bad_block = the corrupt member when that is the error (else -1)
+  bool read_all(std::vector<uint8_t>* out, std::string* err, int64_t* bad_block) const;
+  // what the refills since reset_inflate_stats() did: members and bytes in and out, the time inside refill (with the
+  // device: what the walk waited), and whether every window came from the device
+  struct InflateStats {
+    uint64_t members = 0, bytes_in = 0, bytes_out = 0, device_windows = 0, host_windows = 0;
+    double ms_refill = 0;
+  };
+  const InflateStats& inflate_stats() const { return stats_; }
+  void reset_inflate_stats() const { stats_ = InflateStats(); }
 
  private:
   bool index_blocks(std::string* err);
@@ -76,6 +98,12 @@ class BamFile {
   std::vector<std::string> ref_names_;
   uint64_t first_rec_ = 0;            // inflated offset of the first alignment record
   int threads_ = 4;
+  bool use_core_ = false;
+  int inflate_device_ = -1;
+  BgzfDevice* device_buffers() const;           // made at the first device refill, kept for the passes that follow
+  mutable std::shared_ptr<BgzfDevice> dev_;
+  mutable bool dev_refused_ = false;
+  mutable InflateStats stats_;
 };
 
 }  // namespace g2s

@@ -1,16 +1,18 @@
 // gap2seq_amd/csrc/readfilter_gaps.cpp — g2s_filter_reads_gaps: the reads of N gaps from one library in two
 // inflating passes over the BAM, whatever N is.  Gap i's outputs are g2s_filter_reads' for gap i, byte for byte.
 //
-//   pass A (host, inflating threads)  one compact row per record (readfilter_gaps.hpp: FilterRows): reference, position,
+//   pass A (host walk)                one compact row per record (readfilter_gaps.hpp: FilterRows): reference, position,
 //                                     end position, flag, std::hash of the read's name and of its mate's.  The record
 //                                     count and the longest read fall out of it, so every gap's windows are known at
 //                                     its end.
 //   joins (device or host threads)    per gap the filter's bits (B_g), list 1 (records whose mate's bit is in B_g) and
 //                                     list 2 (records overlapping the flanks whose own bit is not), as (gap, row) pairs
 //                                     in (gap, row) order: readfilter_gpu.hip, or filter_join_host below.
-//   pass B (host, inflating threads)  the FASTA text of every row some gap (or the unmapped list) selected; every gap's
+//   pass B (host walk)                the FASTA text of every row some gap (or the unmapped list) selected; every gap's
 //                                     text is its list 1 rows' text followed by its list 2 rows'.
 //
+// Both passes read the file through BamFile (bam.cpp), which inflates it on the device the joins run on
+// (bgzf_inflate.hip, a window ahead of the walk) or with zlib on host threads (no device, G2S_HOST_INFLATE=1).
 // Pass B inflates the file a second time rather than keeping every record's bases from pass A (which would save that
 // inflate and cost half a byte of every base of the file on the host): the host holds 36 bytes a record (the rows),
 // then 13 bytes a record (pass B's selection and text offsets) and the text of the SELECTED records, once each however
@@ -22,6 +24,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <mutex>
 #include <string>
 #include <thread>
 #include <vector>
@@ -172,6 +175,24 @@ T* dup_array(const T* p, size_t n) {
   return q;
 }
 
+// Whether the reader inflates on the device when nothing says otherwise (G2S_HOST_INFLATE=1 / G2S_DEVICE_INFLATE=1).
+// DESIGN 3.6b has the measurement this follows.
+constexpr bool kDeviceInflateDefault = true;
+
+bool env_is_1(const char* name) {
+  const char* e = getenv(name);
+  return e && strcmp(e, "1") == 0;
+}
+
+// g2s_test_last_filter_inflate: what the reader did in the process's last batched call
+struct LastInflate {
+  int on_device = 0;
+  uint64_t members = 0, bytes_in = 0, bytes_out = 0;
+  double ms_a = 0, ms_b = 0;
+};
+std::mutex g_last_mu;
+LastInflate g_last;
+
 // what g2s_filter_reads_gaps_pool asks of run_filter_gaps in place of the per-gap texts
 struct PoolRequest {
   bool names, unmapped;
@@ -187,6 +208,26 @@ int run_filter_gaps(BamFile& bam, const g2s_filter_opts* lib, const g2s_filter_g
   memset(&st, 0, sizeof st);
   const int threads = lib->threads > 0 ? lib->threads : (int)std::min(8u, std::max(1u, std::thread::hardware_concurrency()));
   bam.set_threads(threads);
+  // the reader inflates where the joins run, by the same rule, unless a switch says otherwise
+  const bool device_wanted = device >= 0 && !env_is_1("G2S_HOST_FILTER");
+  const bool device_inflate = device_wanted && !env_is_1("G2S_HOST_INFLATE") &&
+                              (kDeviceInflateDefault || env_is_1("G2S_DEVICE_INFLATE")) && filter_device_usable(device);
+  bam.set_inflate_device(device_inflate ? device : -1);
+  bam.reset_inflate_stats();
+  LastInflate li;
+  bool all_device = device_inflate;
+  auto note_pass = [&](double* ms) {
+    const BamFile::InflateStats& is = bam.inflate_stats();
+    *ms = is.ms_refill;
+    li.members += is.members;
+    li.bytes_in += is.bytes_in;
+    li.bytes_out += is.bytes_out;
+    if (is.host_windows || !is.device_windows) all_device = false;
+    li.on_device = all_device ? 1 : 0;
+    bam.reset_inflate_stats();
+    std::lock_guard<std::mutex> lk(g_last_mu);
+    g_last = li;
+  };
   // ---- pass A
   auto t0 = std::chrono::steady_clock::now();
   FilterRows R;
@@ -211,9 +252,11 @@ int run_filter_gaps(BamFile& bam, const g2s_filter_opts* lib, const g2s_filter_g
         if (r.ref_id >= 0) R.max_span = std::max(R.max_span, e - (int64_t)r.pos);
         return true;
       }, &err)) {
+    note_pass(&li.ms_a);
     set_filter_error(err);
     return G2S_ERR_IO;
   }
+  note_pass(&li.ms_a);
   if (too_many) { set_filter_error("more than 2^32 - 2 records"); return G2S_ERR_ARG; }
   st.ms_inflate = ms_since(t0);
   const uint64_t total = R.size();
@@ -238,8 +281,7 @@ int run_filter_gaps(BamFile& bam, const g2s_filter_opts* lib, const g2s_filter_g
       J.win[3 * i + 2] = FilterWindow{-1, 0, 0, 0};
   }
   // ---- the joins
-  const char* host_env = getenv("G2S_HOST_FILTER");
-  const bool on_device = device >= 0 && !(host_env && strcmp(host_env, "1") == 0) && filter_device_usable(device);
+  const bool on_device = device_wanted && filter_device_usable(device);
   const int rc = on_device ? filter_join_device(J, device, &err) : filter_join_host(J, threads, &err);
   if (rc != G2S_OK) { set_filter_error(err); return rc; }
   st.on_device = on_device ? 1 : 0;
@@ -283,9 +325,11 @@ int run_filter_gaps(BamFile& bam, const g2s_filter_opts* lib, const g2s_filter_g
         row++;
         return true;
       }, &err)) {
+    note_pass(&li.ms_b);
     set_filter_error(err);
     return G2S_ERR_IO;
   }
+  note_pass(&li.ms_b);
   if (row != total) { set_filter_error("the BAM file changed between passes"); return G2S_ERR_IO; }
   // ---- every gap's text: list 1's rows, then list 2's
   std::vector<size_t> at1(n + 1, 0), at2(n + 1, 0);
@@ -436,6 +480,56 @@ void g2s_read_pool_free(g2s_read_pool* p) {
   free(p->gap_read);
   free(p->unmapped_read);
   free(p);
+}
+
+// TEST HOOK (include/g2s_test.h): a whole BGZF file through one of the three inflaters.
+int g2s_test_bgzf_inflate(const void* bytes, size_t n, int device, uint8_t* out, size_t cap, size_t* out_n, int64_t* bad_member) {
+  if (!bytes || !out_n || (cap && !out) || device < -2) {
+    g2s::set_filter_error("g2s_test_bgzf_inflate: bad argument");
+    return G2S_ERR_ARG;
+  }
+  *out_n = 0;
+  if (bad_member) *bad_member = -1;
+  if (device >= 0 && !g2s::filter_device_usable(device)) {
+    g2s::set_filter_error("g2s_test_bgzf_inflate: no usable gfx950 device " + std::to_string(device));
+    return G2S_ERR_NO_DEVICE;
+  }
+  g2s::BamFile bam;
+  std::string err;
+  if (!bam.open_bgzf(bytes, n, &err)) { g2s::set_filter_error(err); return G2S_ERR_IO; }
+  bam.set_threads(1);
+  bam.set_inflate_core(device == -2);
+  bam.set_inflate_device(device >= 0 ? device : -1);
+  bam.reset_inflate_stats();
+  std::vector<uint8_t> all;
+  int64_t bad = -1;
+  const bool ok = bam.read_all(&all, &err, &bad);
+  if (device >= 0 && bam.inflate_stats().host_windows) {  // (never the host in the kernel's place)
+    g2s::set_filter_error("g2s_test_bgzf_inflate: the device refused");
+    return G2S_ERR_HIP;
+  }
+  if (!ok) {
+    if (bad_member) *bad_member = bad;
+    g2s::set_filter_error(err);
+    return G2S_ERR_IO;
+  }
+  g2s::set_filter_error("");
+  *out_n = all.size();
+  if (cap && !all.empty()) memcpy(out, all.data(), std::min(cap, all.size()));
+  return G2S_OK;
+}
+
+// TEST HOOK (include/g2s_test.h)
+int g2s_test_last_filter_inflate(int* on_device, uint64_t* members, uint64_t* bytes_in, uint64_t* bytes_out,
+                                 double* ms_pass_a_inflate, double* ms_pass_b_inflate) {
+  std::lock_guard<std::mutex> lk(g2s::g_last_mu);
+  if (on_device) *on_device = g2s::g_last.on_device;
+  if (members) *members = g2s::g_last.members;
+  if (bytes_in) *bytes_in = g2s::g_last.bytes_in;
+  if (bytes_out) *bytes_out = g2s::g_last.bytes_out;
+  if (ms_pass_a_inflate) *ms_pass_a_inflate = g2s::g_last.ms_a;
+  if (ms_pass_b_inflate) *ms_pass_b_inflate = g2s::g_last.ms_b;
+  return G2S_OK;
 }
 
 // TEST HOOK (include/g2s_test.h): one of the joins on the caller's rows and windows.  The path is the caller's

@@ -230,6 +230,10 @@ _SIGS = {
                                        C.POINTER(C.c_uint64), C.c_int64, C.c_uint64, C.c_uint64, C.POINTER(C.c_int64),
                                        C.c_uint64, C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(C.c_uint64),
                                        C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(C.c_uint64)]),
+    "g2s_test_bgzf_inflate": (C.c_int, [C.c_char_p, C.c_size_t, C.c_int, C.POINTER(C.c_uint8), C.c_size_t,
+                                        C.POINTER(C.c_size_t), C.POINTER(C.c_int64)]),
+    "g2s_test_last_filter_inflate": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                               C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "g2s_graph_validate": (C.c_int64, [C.c_void_p, C.c_char_p, C.c_size_t]),
     "g2s_test_post_gap": (C.c_int, [_VP, C.POINTER(g2s_params), C.POINTER(g2s_gap), C.c_int32,
                                     C.POINTER(C.c_uint32), C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.c_int32,
@@ -1119,3 +1123,30 @@ def test_filter_join(ref_id, pos, end, flag, h_own, h_mate, max_span, bits, wind
         cap1, cap2 = max(cap1, n1.value), max(cap2, n2.value)
     msg = (lib.g2s_filter_last_error() or b"").decode("utf-8", "replace")
     return rc, [(x >> 32, x & 0xFFFFFFFF) for x in l1[:n1.value]], [(x >> 32, x & 0xFFFFFFFF) for x in l2[:n2.value]], msg
+
+
+def bgzf_inflate(data, device=-1):
+    """TEST HOOK binding (g2s_test_bgzf_inflate): a whole BGZF file inflated on `device` (>= 0: the kernel; -1: zlib;
+    -2: the kernel's decoder compiled for the host).  Returns (code, bytes, bad_member, g2s_filter_last_error's text);
+    nothing is raised, the code is the caller's to check."""
+    lib = load_library()
+    data = bytes(data)
+    cap = max(1 << 16, 4 * len(data))
+    while True:
+        out = (C.c_uint8 * cap)()
+        n, bad = C.c_size_t(0), C.c_int64(-1)
+        rc = lib.g2s_test_bgzf_inflate(data, len(data), device, out, cap, C.byref(n), C.byref(bad))
+        if rc != G2S_OK or n.value <= cap:
+            break
+        cap = n.value
+    msg = (lib.g2s_filter_last_error() or b"").decode("utf-8", "replace")
+    return rc, (bytes(out[:n.value]) if rc == G2S_OK else b""), bad.value, msg
+
+
+def last_filter_inflate():
+    """TEST HOOK binding (g2s_test_last_filter_inflate): dict(on_device, members, bytes_in, bytes_out, ms_pass_a_inflate,
+    ms_pass_b_inflate) of the process's last batched filter call"""
+    d, m, bi, bo, a, b = C.c_int(), C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_double(), C.c_double()
+    _check(load_library().g2s_test_last_filter_inflate(C.byref(d), C.byref(m), C.byref(bi), C.byref(bo), C.byref(a), C.byref(b)))
+    return dict(on_device=d.value, members=m.value, bytes_in=bi.value, bytes_out=bo.value, ms_pass_a_inflate=a.value,
+                ms_pass_b_inflate=b.value)

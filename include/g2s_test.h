@@ -120,6 +120,23 @@ int g2s_test_last_pool_reach(uint64_t* reach_sets, uint64_t* full_kmers, int* fu
  * palindrome's one node. */
 int g2s_test_seg_back_record(g2s_graph* g, int device, uint32_t node, uint32_t out[5]);
 
+/* TEST HOOK: a whole BGZF file (any members, no BAM header needed) inflated by one of the reader's three inflaters
+ * (bam.cpp), through the reader's windows (G2S_BAM_CHUNK).  device >= 0: the kernel g2s_bgzf_inflate on that device —
+ * G2S_ERR_NO_DEVICE when it is no usable gfx950, G2S_ERR_HIP when it refuses later; never the host in its place.
+ * device == -1: zlib, the product's host path.  device == -2: csrc/inflate_core.h, the kernel's decoder and its CRC by
+ * slices, compiled for the host, one member after another.  G2S_OK, or G2S_ERR_IO with g2s_filter_last_error()'s text
+ * and, when a member is corrupt, its index in *bad_member (else -1).  *out_n receives the inflated size; the first
+ * min(cap, size) bytes are written, so a caller whose capacity was too small calls again. */
+int g2s_test_bgzf_inflate(const void* bytes, size_t n, int device, uint8_t* out, size_t cap, size_t* out_n,
+                          int64_t* bad_member);
+
+/* TEST HOOK: what the reader did in the process's last g2s_filter_reads_gaps[_mem] / _pool[_mem] call: whether every
+ * window of both passes was inflated on the device, the members and bytes in and out of both passes together, and per
+ * pass the time spent inside the reader's refills (with the device's look-ahead: what the record walk waited).  Any
+ * pointer may be NULL. */
+int g2s_test_last_filter_inflate(int* on_device, uint64_t* members, uint64_t* bytes_in, uint64_t* bytes_out,
+                                 double* ms_pass_a_inflate, double* ms_pass_b_inflate);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,13 +4,18 @@
             --loop-gaps gaps and extrapolated linearly to all of them (every call inflates the file twice)
   host      g2s_filter_reads_gaps with the joins on host threads (device -1)
   device    g2s_filter_reads_gaps with the joins on the GPU, with its laps: the first call of the process (HIP's
-            start-up falls into its join lap) and a second one
+            start-up falls into its first device lap) and a second one; the file is inflated on the GPU too
+  device_host_inflate   (--host-inflate) the same with G2S_HOST_INFLATE=1: zlib on host threads, the joins on the GPU
+
+Every run also carries the reader's own laps (g2s_test_last_filter_inflate): whether the file was inflated on the
+device and the time inside the reader's refills in pass A and pass B.
 
 Prints one JSON line.  The library is tests/bamwriter.simulate_library's, about --pairs read pairs on 10 scaffolds,
 with --gaps gaps at random breakpoints; the same gaps for all three, on the coordinate-sorted file and on the same
 records shuffled (where the host joins sort their index, which a sorted file spares them).
 
   python tools/readfilter_bench.py [--pairs 1000000] [--gaps 1000] [--loop-gaps 20] [--device 0] [--threads 0]
+                                   [--host-inflate]
 """
 import argparse
 import json
@@ -35,6 +40,7 @@ def main():
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--threads", type=int, default=0)
     ap.add_argument("--seed", type=int, default=5)
+    ap.add_argument("--host-inflate", action="store_true", help="add a leg with G2S_HOST_INFLATE=1")
     a = ap.parse_args()
     t0 = time.time()
     scaffold_len = max(10000, a.pairs // a.scaffolds * 2)
@@ -62,20 +68,27 @@ def main():
                bam_mb=round(len(bam) / 1e6, 1), simulate_s=round(t_sim, 1),
                per_gap_s_measured=round(t_loop, 3), per_gap_gaps_measured=a.loop_gaps,
                per_gap_s_extrapolated=round(t_loop / max(1, a.loop_gaps) * a.gaps, 2))
-    runs = (("host", bam, -1), ("device_first", bam, a.device), ("device", bam, a.device),
-            ("shuffled_host", shuffled, -1), ("shuffled_device", shuffled, a.device))
+    runs = [("host", bam, -1), ("device_first", bam, a.device), ("device", bam, a.device)]
+    if a.host_inflate:
+        runs.append(("device_host_inflate", bam, a.device))
+    runs += [("shuffled_host", shuffled, -1), ("shuffled_device", shuffled, a.device)]
     # (the shuffled file's reads come out in its own order: checked against the per-gap filter on that file)
     check = {id(bam): loop, id(shuffled): [P.filter_reads(shuffled, mean=mean, std_dev=sd, scaffold=s, breakpoint=bp,
                                                           gap_length=gl, flank_length=fl) for s, bp, gl, fl in gaps[:3]]}
     for label, data, dev in runs:
+        if label == "device_host_inflate":
+            os.environ["G2S_HOST_INFLATE"] = "1"
         t0 = time.perf_counter()
         got, st = P.filter_reads_gaps(data, mean, sd, gaps, device=dev, threads=a.threads)
         dt = time.perf_counter() - t0
+        os.environ.pop("G2S_HOST_INFLATE", None)
+        inf = P.last_filter_inflate()
         want = check[id(data)]
         assert got[:len(want)] == want, label + ": differs from the per-gap filter"
         out[label] = dict(s=round(dt, 3), inflate_ms=round(st["ms_inflate"], 1), join_ms=round(st["ms_join"], 1),
                           text_ms=round(st["ms_text"], 1), on_device=st["on_device"], file_passes=st["file_passes"],
-                          extracted=sum(x[3] for x in got))
+                          extracted=sum(x[3] for x in got), inflate_on_device=inf["on_device"],
+                          refill_a_ms=round(inf["ms_pass_a_inflate"], 1), refill_b_ms=round(inf["ms_pass_b_inflate"], 1))
     print(json.dumps(out))
 
 
