@@ -14,6 +14,7 @@
 #include <cstdlib>
 #include <thread>
 
+#include "bam_rows.h"
 #include "bgzf_inflate.h"
 #include "inflate_core.h"
 
@@ -211,7 +212,8 @@ struct BamFile::Stream {
     if (getenv("G2S_DEBUG")) fprintf(stderr, "[g2s] BGZF inflate: the device refused (%s): zlib on the host from block %zu\n",
                                      why.c_str(), next_blk);
   }
-  bool issue(int slot, size_t b0, std::string* why) {
+  // (`down` false: the window stays in device memory, for rows_on_device)
+  bool issue(int slot, size_t b0, std::string* why, bool down = true) {
     size_t bytes = 0, in = 0, file_bytes = 0;
     const size_t e = window_end(b0, &bytes);
     for (size_t b = b0; b < e; b++) {
@@ -233,7 +235,7 @@ struct BamFile::Stream {
       }
       out += isize;
     }
-    if (!dev->launch(slot, e - b0, in, bytes, why)) return false;
+    if (!dev->launch(slot, e - b0, in, bytes, why, down)) return false;
     fly = slot;
     fly_beg = b0;
     fly_end = e;
@@ -425,6 +427,95 @@ bool BamFile::for_each(const std::function<bool(const BamRec&)>& fn, std::string
     if (!fn(r)) return true;
     s.consume(4 + (size_t)bs);
   }
+}
+
+// Pass A without the walk: every window is inflated into its slot's device buffer and left there, and the row kernels
+// (bam_rows.hip) follow the inflate kernel on the same stream; the host stages window n + 1 while window n is on the
+// device, and looks at a window's member status two windows later, when its slot is needed again.
+BamRowsDevice* BamFile::rows_on_device(size_t walk_window, int* anomaly, std::string* why) const {
+  const auto t0 = std::chrono::steady_clock::now();
+  *anomaly = kRowsHip;
+  if (inflate_device_ < 0 || dev_refused_) { *why = "the reader does not inflate on a device"; return nullptr; }
+  Stream s(*this);
+  if (!(s.dev = device_buffers())) { *why = "no device buffers"; return nullptr; }
+  BgzfDevice* dev = s.dev;
+  const size_t nb = blk_off_.size();
+  uint64_t total = 0;
+  size_t max_out = 0, first_bytes = 0;
+  for (size_t b = 0; b < nb;) {
+    size_t bytes = 0;
+    const size_t e = s.window_end(b, &bytes);
+    if (b == 0) first_bytes = bytes;
+    total += bytes;
+    max_out = std::max(max_out, bytes);
+    b = e;
+  }
+  const uint64_t cap_rows = total / 36 + 1;
+  if (first_rec_ > first_bytes || max_out + dev->front() + 64 >= (size_t)INT32_MAX || cap_rows >= (uint64_t)UINT32_MAX - 1) {
+    *anomaly = kRowsLimits;
+    *why = "a header beyond the first window, or a file outside the row kernels' index widths";
+    return nullptr;
+  }
+  std::unique_ptr<BamRowsDevice> R(BamRowsDevice::create(inflate_device_, dev->stream(), max_out, walk_window, dev->front(),
+                                                         cap_rows, (int32_t)ref_names_.size(), first_rec_, why));
+  if (!R) return nullptr;
+  size_t used_beg[2] = {0, 0}, used_end[2] = {0, 0};
+  // the members of the window that went through `slot` last: 0, or the anomaly
+  auto settle = [&](int slot) -> int {
+    if (used_end[slot] == used_beg[slot]) return kRowsOk;
+    if (!dev->wait(slot, why)) return kRowsHip;
+    const uint32_t* st = dev->status(slot);
+    for (size_t i = 0; i < used_end[slot] - used_beg[slot]; i++)
+      if (st[i] != inflate::kOk) {
+        *why = "corrupt BGZF block " + std::to_string(used_beg[slot] + i);
+        return kRowsCorrupt;
+      }
+    used_end[slot] = used_beg[slot];
+    return kRowsOk;
+  };
+  InflateStats is;
+  size_t last_bytes = 0;
+  int a = kRowsOk;
+  bool ok = true;
+  for (size_t b = 0, w = 0; b < nb && ok; w++) {
+    const int slot = (int)(w & 1);
+    if ((a = settle(slot)) != kRowsOk) { ok = false; break; }
+    a = kRowsHip;
+    if (!s.issue(slot, b, why, false)) { ok = false; break; }
+    used_beg[slot] = s.fly_beg;
+    used_end[slot] = s.fly_end;
+    ok = R->window(dev->device_window(slot), w == 0 ? (size_t)first_rec_ : 0, s.fly_bytes, why);
+    b = s.fly_end;
+    if (ok && b < nb) ok = R->carry(dev->device_window(slot), s.fly_bytes, dev->device_window(1 - slot), why);
+    last_bytes = s.fly_bytes;
+    is.members += s.fly_end - s.fly_beg;
+    is.bytes_in += s.fly_in;
+    is.bytes_out += s.fly_bytes;
+    is.device_windows++;
+    a = kRowsOk;
+  }
+  for (int slot = 0; slot < 2 && ok; slot++)
+    if ((a = settle(slot)) != kRowsOk) ok = false;
+  if (ok) {
+    a = kRowsHip;
+    ok = R->finish(last_bytes, &a, why) && a == kRowsOk;
+    if (a != kRowsOk && why->empty()) *why = "the row kernels met anomaly " + std::to_string(a);
+  }
+  if (!ok) {  // (nothing of this pass is left in flight when the host walk takes the buffers over)
+    (void)dev->wait(0, nullptr);
+    (void)dev->wait(1, nullptr);
+    *anomaly = a == kRowsOk ? (int)kRowsHip : a;
+    rows_windows_ = R->windows();
+    return nullptr;
+  }
+  *anomaly = kRowsOk;
+  rows_windows_ = R->windows();
+  stats_.members += is.members;
+  stats_.bytes_in += is.bytes_in;
+  stats_.bytes_out += is.bytes_out;
+  stats_.device_windows += is.device_windows;
+  stats_.ms_refill += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return R.release();
 }
 
 }  // namespace g2s

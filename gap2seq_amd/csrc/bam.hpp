@@ -20,6 +20,7 @@
 namespace g2s {
 
 class BgzfDevice;
+class BamRowsDevice;
 
 enum : uint32_t {
   BAM_PAIRED = 1, BAM_UNMAPPED = 4, BAM_MATE_UNMAPPED = 8, BAM_REVERSE = 16, BAM_READ1 = 64, BAM_READ2 = 128
@@ -69,6 +70,12 @@ class BamFile {
   // call that fails) hands the file to the host path for good, silently (G2S_DEBUG=1 prints why).  -1: zlib on host
   // threads.  A corrupt member is the same error on either.
   void set_inflate_device(int device);
+  // Pass A of the batched filter without a walk (bam_rows.h): the rows of every record made by kernels on the inflate
+  // device from the windows while they lie in device memory, `walk_window` bytes at a time (0: a whole window of
+  // inflated members).  The caller owns the result.  Null: *anomaly (bam_rows.h: RowsAnomaly) and *why say what
+  // stood in the way; nothing is left in flight, no inflate statistics were counted, and for_each is the way to go on.
+  BamRowsDevice* rows_on_device(size_t walk_window, int* anomaly, std::string* why) const;
+  uint64_t rows_windows() const { return rows_windows_; }  // walk windows of the last rows_on_device
   // test paths (g2s_test_bgzf_inflate): the host path with inflate_core.h in zlib's place; any BGZF file, no BAM header
   void set_inflate_core(bool on) { use_core_ = on; }
   bool open_bgzf(const void* bytes, size_t n, std::string* err);
@@ -104,6 +111,7 @@ class BamFile {
   mutable std::shared_ptr<BgzfDevice> dev_;
   mutable bool dev_refused_ = false;
   mutable InflateStats stats_;
+  mutable uint64_t rows_windows_ = 0;
 };
 
 }  // namespace g2s

@@ -1,0 +1,73 @@
+// gap2seq_amd/csrc/bam_rows.h — pass A of the batched read filter on the device (bam_rows.hip): the rows of
+// readfilter_gaps.hpp's FilterRows made by kernels from the inflated windows while they lie in device memory.
+// bam.cpp (BamFile::rows_on_device) hands the windows over; readfilter_gpu.hip's joins read the rows where they are.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+#include <string>
+
+namespace g2s {
+
+// why a pass gave up its device rows (g2s_test_last_filter_rows); the host walk then runs and is the authority
+enum RowsAnomaly : int {
+  kRowsOk = 0,
+  kRowsDeadLink = 1,   // a record of the chain points at an offset that can be no record (or the head itself cannot)
+  kRowsOverflow = 2,   // more candidates in a window than its capacity
+  kRowsCarry = 3,      // a cut record's head longer than the room in front of a window
+  kRowsWrongEnd = 4,   // the chain does not end at the stream's end
+  kRowsHip = 5,        // an allocation or a HIP call failed
+  kRowsHash = 6,       // name_hash.h is not this build's std::hash<std::string>
+  kRowsCorrupt = 7,    // a member did not inflate
+  kRowsLimits = 8,     // a file outside the kernels' index widths, or a header that does not end in the first window
+};
+
+// rows in device memory, in file order; the arrays belong to the BamRowsDevice that made them
+struct DeviceRows {
+  int32_t *ref_id = nullptr, *pos = nullptr;
+  int64_t* end = nullptr;
+  uint32_t* flag = nullptr;
+  uint64_t *h_own = nullptr, *h_mate = nullptr;  // (the joins replace them by their bits, in place)
+  uint64_t n = 0;
+  int64_t max_span = 1;
+  int32_t read_length = 0;
+};
+
+class BamRowsDevice {
+ public:
+  // Kernels on `stream` (a hipStream_t: the reader's own, behind its inflate kernel) for windows of at most max_window
+  // bytes, walked `walk_window` bytes at a time, each with `front` bytes of room in front; at most cap_rows rows;
+  // references [0, n_ref); the first record at offset first_head of the first window.  Null: *why.
+  static BamRowsDevice* create(int device, void* stream, size_t max_window, size_t walk_window, size_t front,
+                               uint64_t cap_rows, int32_t n_ref, uint64_t first_head, std::string* why);
+  ~BamRowsDevice();
+  BamRowsDevice(const BamRowsDevice&) = delete;
+  BamRowsDevice& operator=(const BamRowsDevice&) = delete;
+  // the walk windows of one inflated window of `bytes` bytes at d_win (a device pointer), from offset `start`: enqueued
+  bool window(const uint8_t* d_win, size_t start, size_t bytes, std::string* why);
+  // the cut record's head moved in front of the next window's buffer: enqueued
+  bool carry(const uint8_t* d_win, size_t bytes, uint8_t* d_next_win, std::string* why);
+  // the end of the stream behind a last window of last_bytes bytes: waits, and reads the counts down.  False: a HIP
+  // call failed (*why).  *anomaly: kRowsOk, or what the kernels met.
+  bool finish(size_t last_bytes, int* anomaly, std::string* why);
+  // the first m rows copied to the host (tests)
+  bool download(uint64_t m, int32_t* ref_id, int32_t* pos, int64_t* end, uint32_t* flag, uint64_t* h_own, uint64_t* h_mate,
+                std::string* why) const;
+  const DeviceRows& rows() const { return rows_; }
+  uint64_t windows() const { return windows_; }
+  uint64_t candidates() const { return candidates_; }
+
+ private:
+  BamRowsDevice() {}
+  int device_ = -1;
+  void* stream_ = nullptr;
+  size_t walk_ = 0, front_ = 0;
+  uint32_t cap_cand_ = 0, max_tiles_ = 0;
+  uint64_t cap_rows_ = 0;
+  int32_t n_ref_ = 0;
+  DeviceRows rows_;
+  void *state_ = nullptr, *cand_ = nullptr, *link_ = nullptr, *j0_ = nullptr, *j1_ = nullptr, *mark_ = nullptr, *emit_ = nullptr,
+       *blk_ = nullptr;
+  uint64_t windows_ = 0, candidates_ = 0;
+};
+
+}  // namespace g2s

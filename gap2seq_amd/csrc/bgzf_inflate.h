@@ -33,11 +33,16 @@ class BgzfDevice {
   uint8_t* window(int slot) const { return s_[slot].h_out + front_; }
   const uint32_t* status(int slot) const { return s_[slot].h_st; }
   size_t front() const { return front_; }
+  // the same window in device memory, with the same room in front of it (bam_rows.hip reads it there), and the stream
+  // (a hipStream_t) everything of this object runs on
+  uint8_t* device_window(int slot) const { return s_[slot].d_out + front_; }
+  void* stream() const { return stream_; }
   bool fits(size_t n_members, size_t in_bytes, size_t out_bytes) const {
     return n_members <= cap_members_ && in_bytes <= cap_in_ && out_bytes <= cap_out_;
   }
-  // copies up, the kernel, copies down: all asynchronous, on the object's own stream
-  bool launch(int slot, size_t n_members, size_t in_bytes, size_t out_bytes, std::string* why);
+  // copies up, the kernel, copies down (the status words alone when `down` is false: the window stays on the device):
+  // all asynchronous, on the object's own stream
+  bool launch(int slot, size_t n_members, size_t in_bytes, size_t out_bytes, std::string* why, bool down = true);
   bool wait(int slot, std::string* why);
 
  private:

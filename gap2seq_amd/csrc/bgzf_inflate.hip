@@ -169,7 +169,7 @@ BgzfDevice* BgzfDevice::create(int device, size_t max_in, size_t max_out, size_t
       G2S_BZ_TRY(hipHostMalloc((void**)&s.h_mem, (max_members + 1) * sizeof(BgzfMember), hipHostMallocDefault));
       G2S_BZ_TRY(hipHostMalloc((void**)&s.h_st, (max_members + 1) * 4, hipHostMallocDefault));
       G2S_BZ_TRY(hipMalloc((void**)&s.d_in, max_in + 16));
-      G2S_BZ_TRY(hipMalloc((void**)&s.d_out, max_out + 16));
+      G2S_BZ_TRY(hipMalloc((void**)&s.d_out, front + max_out + 64));
       G2S_BZ_TRY(hipMalloc((void**)&s.d_mem, (max_members + 1) * sizeof(BgzfMember)));
       G2S_BZ_TRY(hipMalloc((void**)&s.d_st, (max_members + 1) * 4));
       hipEvent_t ev;
@@ -202,7 +202,7 @@ BgzfDevice::~BgzfDevice() {
   if (stream_) (void)hipStreamDestroy((hipStream_t)stream_);
 }
 
-bool BgzfDevice::launch(int slot, size_t n_members, size_t in_bytes, size_t out_bytes, std::string* why) {
+bool BgzfDevice::launch(int slot, size_t n_members, size_t in_bytes, size_t out_bytes, std::string* why, bool down) {
   Slot& s = s_[slot];
   hipStream_t st = (hipStream_t)stream_;
   if (!fits(n_members, in_bytes, out_bytes)) {
@@ -214,9 +214,9 @@ bool BgzfDevice::launch(int slot, size_t n_members, size_t in_bytes, size_t out_
     if (in_bytes) G2S_BZ_TRY(hipMemcpyAsync(s.d_in, s.h_in, in_bytes, hipMemcpyHostToDevice, st));
     G2S_BZ_TRY(hipMemcpyAsync(s.d_mem, s.h_mem, n_members * sizeof(BgzfMember), hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(g2s_bgzf_inflate, dim3((unsigned)n_members), dim3(kWave), 0, st, (const uint8_t*)s.d_in,
-                       (const BgzfMember*)s.d_mem, (uint32_t)n_members, s.d_out, s.d_st);
+                       (const BgzfMember*)s.d_mem, (uint32_t)n_members, s.d_out + front_, s.d_st);
     G2S_BZ_TRY(hipGetLastError());
-    G2S_BZ_TRY(hipMemcpyAsync(s.h_out + front_, s.d_out, out_bytes, hipMemcpyDeviceToHost, st));
+    if (down) G2S_BZ_TRY(hipMemcpyAsync(s.h_out + front_, s.d_out + front_, out_bytes, hipMemcpyDeviceToHost, st));
     G2S_BZ_TRY(hipMemcpyAsync(s.h_st, s.d_st, n_members * 4, hipMemcpyDeviceToHost, st));
   } else {
     memset(s.h_st, 0, n_members * 4);  // (members without bytes succeed: inflate_core.h kOk)

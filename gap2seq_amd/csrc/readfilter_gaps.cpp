@@ -1,7 +1,7 @@
 // gap2seq_amd/csrc/readfilter_gaps.cpp — g2s_filter_reads_gaps: the reads of N gaps from one library in two
 // inflating passes over the BAM, whatever N is.  Gap i's outputs are g2s_filter_reads' for gap i, byte for byte.
 //
-//   pass A (host walk)                one compact row per record (readfilter_gaps.hpp: FilterRows): reference, position,
+//   pass A (device kernels or host walk)  one compact row per record (readfilter_gaps.hpp: FilterRows): reference, position,
 //                                     end position, flag, std::hash of the read's name and of its mate's.  The record
 //                                     count and the longest read fall out of it, so every gap's windows are known at
 //                                     its end.
@@ -11,6 +11,9 @@
 //   pass B (host walk)                the FASTA text of every row some gap (or the unmapped list) selected; every gap's
 //                                     text is its list 1 rows' text followed by its list 2 rows'.
 //
+// With device inflate pass A's rows can be made by kernels from the inflated windows where they lie (bam_rows.hip:
+// G2S_DEVICE_ROWS=1 / G2S_HOST_ROWS=1, kDeviceRowsDefault), and the joins read them there; whatever those kernels cannot
+// account for hands pass A to the host walk, which is the authority on a file's errors.
 // Both passes read the file through BamFile (bam.cpp), which inflates it on the device the joins run on
 // (bgzf_inflate.hip, a window ahead of the walk) or with zlib on host threads (no device, G2S_HOST_INFLATE=1).
 // Pass B inflates the file a second time rather than keeping every record's bases from pass A (which would save that
@@ -24,6 +27,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -32,6 +36,8 @@
 #include "../../include/g2s.h"
 #include "../../include/g2s_test.h"
 #include "bam.hpp"
+#include "bam_rows.h"
+#include "name_hash.h"
 #include "readfilter_gaps.hpp"
 
 namespace g2s {
@@ -193,6 +199,100 @@ struct LastInflate {
 std::mutex g_last_mu;
 LastInflate g_last;
 
+// Whether pass A's rows are made on the device when the reader inflates there and nothing says otherwise
+// (G2S_HOST_ROWS=1 / G2S_DEVICE_ROWS=1).  By DESIGN 3.6b's table the whole call with device rows is 32-35 ms faster than
+// the parent's on average, more than the parent's own spread over six calls, with 8 and with 2 host threads.
+constexpr bool kDeviceRowsDefault = true;
+
+// g2s_test_last_filter_rows: what pass A of the process's last batched call (or g2s_test_bam_rows) did
+struct LastRows {
+  int on_device = 0, anomaly = 0;
+  uint64_t windows = 0, records = 0, candidates = 0;
+};
+LastRows g_last_rows;
+
+// pass A on the host: the walk, one row per record
+bool pass_a_host(const BamFile& bam, FilterRows& R, int32_t* read_length, bool* too_many, std::string* err) {
+  std::string nm;
+  return bam.for_each([&](const BamRec& r) {
+    if (R.size() >= (size_t)UINT32_MAX - 1) { *too_many = true; return false; }
+    const int64_t e = r.end_pos();
+    R.ref_id.push_back(r.ref_id);
+    R.pos.push_back(r.pos);
+    R.end.push_back(e);
+    R.flag.push_back(r.flag);
+    nm.assign(r.name, strnlen(r.name, r.l_name));
+    const bool r1 = (r.flag & BAM_READ1) != 0;
+    nm += r1 ? "/1" : "/2";
+    R.h_own.push_back((uint64_t)std::hash<std::string>{}(nm));
+    nm.back() = r1 ? '2' : '1';
+    R.h_mate.push_back((uint64_t)std::hash<std::string>{}(nm));
+    *read_length = std::max(*read_length, r.l_seq);
+    if (r.ref_id >= 0) R.max_span = std::max(R.max_span, e - (int64_t)r.pos);
+    return true;
+  }, err);
+}
+
+// The probe of name_hash.h against this build's std::hash<std::string>: names of every length 0 to 40 and of 254,
+// bytes >= 0x80 in each of a name's last seven positions, names with a NUL inside (the part in front counts) and 500
+// names of random bytes, each with /1 and /2.  tests/bam_walk_cases.py's hash_names() builds the same names from the
+// same generator (xorshift64 from 0x9E3779B97F4A7C15, one draw a byte), so the tests pin what a process checks.
+bool name_hash_probe() {
+  std::vector<std::string> names;
+  uint64_t x = 0x9E3779B97F4A7C15ull;
+  auto next = [&] { x ^= x << 13; x ^= x >> 7; x ^= x << 17; return x; };
+  auto printable = [&](size_t len) {
+    std::string s;
+    for (size_t i = 0; i < len; i++) s.push_back((char)('!' + next() % 94));
+    return s;
+  };
+  for (size_t len = 0; len <= 40; len++) names.push_back(printable(len));
+  names.push_back(printable(254));
+  for (size_t len : {7u, 8u, 9u, 15u, 16u, 23u})
+    for (size_t back = 1; back <= 7; back++) {
+      std::string s(len, 'a');
+      s[len - back] = (char)(0x80 + next() % 128);
+      names.push_back(s);
+    }
+  for (const std::string& s : {std::string("ab\0cd", 5), std::string("\0zzz", 4), std::string("abcdefg\0hij\0", 12),
+                               std::string("abcdefgh\0", 9)})
+    names.push_back(s.substr(0, strnlen(s.data(), s.size())));
+  for (int i = 0; i < 500; i++) {
+    std::string s;
+    const size_t len = next() % 64;
+    for (size_t k = 0; k < len; k++) s.push_back((char)(1 + next() % 255));
+    names.push_back(s);
+  }
+  for (const std::string& s : names)
+    for (uint32_t which = 1; which <= 2; which++) {
+      const std::string full = s + (which == 1 ? "/1" : "/2");
+      if ((uint64_t)std::hash<std::string>{}(full) != name_hash((const uint8_t*)s.data(), (uint32_t)s.size(), which)) return false;
+    }
+  return true;
+}
+bool name_hash_usable() {
+  static const bool ok = name_hash_probe();  // once a process
+  return ok;
+}
+
+// Pass A on the device.  Null: *anomaly says why (kRowsOk: nothing asked for it), the reader's statistics are as they
+// were, and the host walk runs.
+std::unique_ptr<BamRowsDevice> pass_a_device(const BamFile& bam, size_t walk_window, int* anomaly) {
+  std::string why;
+  *anomaly = kRowsOk;
+  std::unique_ptr<BamRowsDevice> D;
+  if (!name_hash_usable()) {
+    *anomaly = kRowsHash;
+    why = "name_hash.h is not this build's std::hash<std::string>";
+  } else {
+    D.reset(bam.rows_on_device(walk_window, anomaly, &why));
+  }
+  if (!D && getenv("G2S_DEBUG"))
+    fprintf(stderr, "[g2s] pass A: no device rows (anomaly %d: %s): the host walk\n", *anomaly, why.c_str());
+  if (D && getenv("G2S_DEBUG")) fprintf(stderr, "[g2s] pass A: rows on the device (%zu windows)\n", (size_t)bam.rows_windows());
+  return D;
+}
+
 // what g2s_filter_reads_gaps_pool asks of run_filter_gaps in place of the per-gap texts
 struct PoolRequest {
   bool names, unmapped;
@@ -233,25 +333,27 @@ int run_filter_gaps(BamFile& bam, const g2s_filter_opts* lib, const g2s_filter_g
   FilterRows R;
   int32_t read_length = 0;
   bool too_many = false;
-  std::string nm;
   st.file_passes++;
-  if (!bam.for_each([&](const BamRec& r) {
-        if (R.size() >= (size_t)UINT32_MAX - 1) { too_many = true; return false; }
-        const int64_t e = r.end_pos();
-        R.ref_id.push_back(r.ref_id);
-        R.pos.push_back(r.pos);
-        R.end.push_back(e);
-        R.flag.push_back(r.flag);
-        nm.assign(r.name, strnlen(r.name, r.l_name));
-        const bool r1 = (r.flag & BAM_READ1) != 0;
-        nm += r1 ? "/1" : "/2";
-        R.h_own.push_back((uint64_t)std::hash<std::string>{}(nm));
-        nm.back() = r1 ? '2' : '1';
-        R.h_mate.push_back((uint64_t)std::hash<std::string>{}(nm));
-        read_length = std::max(read_length, r.l_seq);
-        if (r.ref_id >= 0) R.max_span = std::max(R.max_span, e - (int64_t)r.pos);
-        return true;
-      }, &err)) {
+  // the rows on the device, under the rule that inflates there, unless a switch says otherwise
+  std::unique_ptr<BamRowsDevice> drows;
+  LastRows lr;
+  if (device_inflate && !env_is_1("G2S_HOST_ROWS") && (kDeviceRowsDefault || env_is_1("G2S_DEVICE_ROWS"))) {
+    drows = pass_a_device(bam, 0, &lr.anomaly);
+    lr.windows = bam.rows_windows();
+    if (!drows) bam.reset_inflate_stats();
+  }
+  if (drows) {
+    lr.on_device = 1;
+    lr.records = drows->rows().n;
+    lr.candidates = drows->candidates();
+    read_length = drows->rows().read_length;
+    R.max_span = drows->rows().max_span;
+  }
+  {
+    std::lock_guard<std::mutex> lk(g_last_mu);
+    g_last_rows = lr;
+  }
+  if (!drows && !pass_a_host(bam, R, &read_length, &too_many, &err)) {
     note_pass(&li.ms_a);
     set_filter_error(err);
     return G2S_ERR_IO;
@@ -259,11 +361,16 @@ int run_filter_gaps(BamFile& bam, const g2s_filter_opts* lib, const g2s_filter_g
   note_pass(&li.ms_a);
   if (too_many) { set_filter_error("more than 2^32 - 2 records"); return G2S_ERR_ARG; }
   st.ms_inflate = ms_since(t0);
-  const uint64_t total = R.size();
+  const uint64_t total = drows ? drows->rows().n : R.size();
+  if (!drows) {
+    std::lock_guard<std::mutex> lk(g_last_mu);
+    g_last_rows.records = total;
+  }
   // ---- every gap's windows and warnings (readfilter.cpp: run_filter)
   t0 = std::chrono::steady_clock::now();
   FilterJoin J;
   J.rows = &R;
+  if (drows) J.device_rows = &drows->rows();
   J.bits = 5 * total;
   const char* cap = getenv("G2S_FILTER_MAX_PAIRS");
   J.max_pairs = cap ? (uint64_t)strtoull(cap, nullptr, 10) : (uint64_t)1 << 31;
@@ -286,6 +393,7 @@ int run_filter_gaps(BamFile& bam, const g2s_filter_opts* lib, const g2s_filter_g
   if (rc != G2S_OK) { set_filter_error(err); return rc; }
   st.on_device = on_device ? 1 : 0;
   st.ms_join = ms_since(t0);
+  drows.reset();
   // ---- pass B: the text of the selected rows
   t0 = std::chrono::steady_clock::now();
   std::vector<uint8_t> sel(total, 0);
@@ -529,6 +637,99 @@ int g2s_test_last_filter_inflate(int* on_device, uint64_t* members, uint64_t* by
   if (bytes_out) *bytes_out = g2s::g_last.bytes_out;
   if (ms_pass_a_inflate) *ms_pass_a_inflate = g2s::g_last.ms_a;
   if (ms_pass_b_inflate) *ms_pass_b_inflate = g2s::g_last.ms_b;
+  return G2S_OK;
+}
+
+// TEST HOOK (include/g2s_test.h): pass A alone
+int g2s_test_bam_rows(const void* bytes, size_t n, int device, size_t window, uint64_t cap, int32_t* ref_id, int32_t* pos,
+                      int64_t* end, uint32_t* flag, uint64_t* h_own, uint64_t* h_mate, uint64_t* total, int32_t* read_length,
+                      int64_t* max_span) {
+  if (!bytes || !total || !read_length || !max_span || (cap && (!ref_id || !pos || !end || !flag || !h_own || !h_mate))) {
+    g2s::set_filter_error("g2s_test_bam_rows: bad argument");
+    return G2S_ERR_ARG;
+  }
+  *total = 0;
+  *read_length = 0;
+  *max_span = 1;
+  if (device >= 0 && !g2s::filter_device_usable(device)) {
+    g2s::set_filter_error("g2s_test_bam_rows: no usable gfx950 device " + std::to_string(device));
+    return G2S_ERR_NO_DEVICE;
+  }
+  g2s::BamFile bam;
+  std::string err;
+  if (!bam.open_mem(bytes, n, &err)) { g2s::set_filter_error(err); return G2S_ERR_IO; }
+  bam.set_threads(1);
+  bam.set_inflate_device(device >= 0 ? device : -1);
+  g2s::LastRows lr;
+  auto note = [&] {
+    std::lock_guard<std::mutex> lk(g2s::g_last_mu);
+    g2s::g_last_rows = lr;
+  };
+  if (device >= 0) {
+    std::unique_ptr<g2s::BamRowsDevice> D = g2s::pass_a_device(bam, window, &lr.anomaly);
+    lr.windows = bam.rows_windows();
+    if (!D) {  // (never the host in the kernels' place)
+      note();
+      g2s::set_filter_error("g2s_test_bam_rows: the device gave up its rows (anomaly " + std::to_string(lr.anomaly) + ")");
+      return G2S_ERR_HIP;
+    }
+    const g2s::DeviceRows& R = D->rows();
+    lr.on_device = 1;
+    lr.records = R.n;
+    lr.candidates = D->candidates();
+    note();
+    *total = R.n;
+    *read_length = R.read_length;
+    *max_span = R.max_span;
+    if (!D->download(std::min<uint64_t>(cap, R.n), ref_id, pos, end, flag, h_own, h_mate, &err)) {
+      g2s::set_filter_error(err);
+      return G2S_ERR_HIP;
+    }
+    g2s::set_filter_error("");
+    return G2S_OK;
+  }
+  g2s::FilterRows R;
+  bool too_many = false;
+  if (!g2s::pass_a_host(bam, R, read_length, &too_many, &err)) { g2s::set_filter_error(err); return G2S_ERR_IO; }
+  if (too_many) { g2s::set_filter_error("more than 2^32 - 2 records"); return G2S_ERR_ARG; }
+  lr.records = R.size();
+  note();
+  *total = R.size();
+  *max_span = R.max_span;
+  const size_t m = (size_t)std::min<uint64_t>(cap, R.size());
+  if (m) {
+    memcpy(ref_id, R.ref_id.data(), m * 4);
+    memcpy(pos, R.pos.data(), m * 4);
+    memcpy(end, R.end.data(), m * 8);
+    memcpy(flag, R.flag.data(), m * 4);
+    memcpy(h_own, R.h_own.data(), m * 8);
+    memcpy(h_mate, R.h_mate.data(), m * 8);
+  }
+  g2s::set_filter_error("");
+  return G2S_OK;
+}
+
+// TEST HOOK (include/g2s_test.h)
+int g2s_test_name_hash(const void* bytes, size_t len, int which, uint64_t* std_hash, uint64_t* own_hash) {
+  if ((len && !bytes) || (which != 1 && which != 2) || !std_hash || !own_hash || len > 255) {
+    g2s::set_filter_error("g2s_test_name_hash: bad argument");
+    return G2S_ERR_ARG;
+  }
+  const size_t nlen = len ? strnlen((const char*)bytes, len) : 0;
+  const std::string full = std::string((const char*)bytes, nlen) + (which == 1 ? "/1" : "/2");
+  *std_hash = (uint64_t)std::hash<std::string>{}(full);
+  *own_hash = g2s::name_hash((const uint8_t*)bytes, (uint32_t)nlen, (uint32_t)which);
+  return G2S_OK;
+}
+
+// TEST HOOK (include/g2s_test.h)
+int g2s_test_last_filter_rows(int* on_device, uint64_t* windows, uint64_t* records, uint64_t* candidates, int* anomaly) {
+  std::lock_guard<std::mutex> lk(g2s::g_last_mu);
+  if (on_device) *on_device = g2s::g_last_rows.on_device;
+  if (windows) *windows = g2s::g_last_rows.windows;
+  if (records) *records = g2s::g_last_rows.records;
+  if (candidates) *candidates = g2s::g_last_rows.candidates;
+  if (anomaly) *anomaly = g2s::g_last_rows.anomaly;
   return G2S_OK;
 }
 

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "bam.hpp"
+#include "bam_rows.h"
 
 namespace g2s {
 
@@ -114,6 +115,7 @@ inline uint64_t filter_index_key(int32_t tid, int64_t p) {
 struct FilterJoin {
   // in
   const FilterRows* rows = nullptr;
+  const DeviceRows* device_rows = nullptr;  // filter_join_device: the rows lie on its device already (`rows` is unused)
   uint64_t bits = 0;                   // 5 * records
   std::vector<FilterWindow> win;       // 3 a gap: left, right, around
   uint64_t max_pairs = 0;

@@ -1,7 +1,8 @@
 // gap2seq_amd/csrc/readfilter_gpu.hip — the joins of the batched read filter (readfilter_gaps.cpp) on the GPU.
 //
 // In: one row per BAM record (reference, position, end position, flag, std::hash of the read's name and of its
-// mate's — the strings never reach the device) and three windows a gap (readfilter_gaps.hpp).  Out: lists 1 and 2 as
+// mate's), copied up from the host walk's FilterRows or left in device memory by pass A's kernels (bam_rows.hip), and
+// three windows a gap (readfilter_gaps.hpp).  Out: lists 1 and 2 as
 // (gap << 32 | row) pairs in ascending order.  Steps, each sized before it is written (count, exclusive scan, write):
 //   1. k_bits         bit = hash % (5 * records) of every name and mate name, in place (64-bit modulo)
 //   2. index          (ref_id, pos) keys radix-sorted with their rows (rocPRIM, as the set build in dbg_gpu.hip); a
@@ -147,7 +148,9 @@ int filter_join_device(FilterJoin& j, int device, std::string* err) {
     if ((count) > j.max_pairs) { *err = "more filter pairs than the cap (G2S_FILTER_MAX_PAIRS)"; return G2S_ERR_NOMEM; } \
   } while (0)
   const FilterRows& R = *j.rows;
-  const uint64_t nr = R.size();
+  const DeviceRows* DR = j.device_rows;
+  const uint64_t nr = DR ? DR->n : R.size();
+  const int64_t max_span = DR ? DR->max_span : R.max_span;
   const uint32_t n = (uint32_t)j.gaps();
   j.list1.clear();
   j.list2.clear();
@@ -156,26 +159,35 @@ int filter_join_device(FilterJoin& j, int device, std::string* err) {
   const dim3 blk(256), grdR((unsigned)((nr + 255) / 256));
   // ---- rows up, bits, index
   Dev d_ref, d_pos, d_end, d_flag, d_own, d_mate, d_ikey, d_irow, d_ikey2, d_irow2, d_win, d_tmp;
-  G2S_RF_TRY(d_ref.alloc(nr * 4));
-  G2S_RF_TRY(d_pos.alloc(nr * 4));
-  G2S_RF_TRY(d_end.alloc(nr * 8));
-  G2S_RF_TRY(d_flag.alloc(nr * 4));
-  G2S_RF_TRY(d_own.alloc(nr * 8));
-  G2S_RF_TRY(d_mate.alloc(nr * 8));
   G2S_RF_TRY(d_win.alloc(j.win.size() * sizeof(FilterWindow)));
-  G2S_RF_TRY(hipMemcpy(d_ref.p, R.ref_id.data(), nr * 4, hipMemcpyHostToDevice));
-  G2S_RF_TRY(hipMemcpy(d_pos.p, R.pos.data(), nr * 4, hipMemcpyHostToDevice));
-  G2S_RF_TRY(hipMemcpy(d_end.p, R.end.data(), nr * 8, hipMemcpyHostToDevice));
-  G2S_RF_TRY(hipMemcpy(d_flag.p, R.flag.data(), nr * 4, hipMemcpyHostToDevice));
-  G2S_RF_TRY(hipMemcpy(d_own.p, R.h_own.data(), nr * 8, hipMemcpyHostToDevice));
-  G2S_RF_TRY(hipMemcpy(d_mate.p, R.h_mate.data(), nr * 8, hipMemcpyHostToDevice));
   G2S_RF_TRY(hipMemcpy(d_win.p, j.win.data(), j.win.size() * sizeof(FilterWindow), hipMemcpyHostToDevice));
+  if (!DR) {
+    G2S_RF_TRY(d_ref.alloc(nr * 4));
+    G2S_RF_TRY(d_pos.alloc(nr * 4));
+    G2S_RF_TRY(d_end.alloc(nr * 8));
+    G2S_RF_TRY(d_flag.alloc(nr * 4));
+    G2S_RF_TRY(d_own.alloc(nr * 8));
+    G2S_RF_TRY(d_mate.alloc(nr * 8));
+    G2S_RF_TRY(hipMemcpy(d_ref.p, R.ref_id.data(), nr * 4, hipMemcpyHostToDevice));
+    G2S_RF_TRY(hipMemcpy(d_pos.p, R.pos.data(), nr * 4, hipMemcpyHostToDevice));
+    G2S_RF_TRY(hipMemcpy(d_end.p, R.end.data(), nr * 8, hipMemcpyHostToDevice));
+    G2S_RF_TRY(hipMemcpy(d_flag.p, R.flag.data(), nr * 4, hipMemcpyHostToDevice));
+    G2S_RF_TRY(hipMemcpy(d_own.p, R.h_own.data(), nr * 8, hipMemcpyHostToDevice));
+    G2S_RF_TRY(hipMemcpy(d_mate.p, R.h_mate.data(), nr * 8, hipMemcpyHostToDevice));
+  }
+  // (rows that pass A left on the device are read where they lie, and stay their owner's)
+  const int32_t* p_ref = DR ? DR->ref_id : d_ref.as<int32_t>();
+  const int32_t* p_pos = DR ? DR->pos : d_pos.as<int32_t>();
+  const int64_t* p_end = DR ? DR->end : d_end.as<int64_t>();
+  const uint32_t* p_flag = DR ? DR->flag : d_flag.as<uint32_t>();
+  uint64_t* p_own = DR ? DR->h_own : d_own.as<uint64_t>();
+  uint64_t* p_mate = DR ? DR->h_mate : d_mate.as<uint64_t>();
   G2S_RF_TRY(d_ikey.alloc(nr * 8));
   G2S_RF_TRY(d_irow.alloc(nr * 4));
   G2S_RF_TRY(d_ikey2.alloc(nr * 8));
   G2S_RF_TRY(d_irow2.alloc(nr * 4));
-  hipLaunchKernelGGL(k_bits, grdR, blk, 0, 0, d_own.as<uint64_t>(), d_mate.as<uint64_t>(), (uint32_t)nr, j.bits,
-                     d_ref.as<int32_t>(), d_pos.as<int32_t>(), d_ikey.as<uint64_t>(), d_irow.as<uint32_t>());
+  hipLaunchKernelGGL(k_bits, grdR, blk, 0, 0, p_own, p_mate, (uint32_t)nr, j.bits, p_ref, p_pos, d_ikey.as<uint64_t>(),
+                     d_irow.as<uint32_t>());
   G2S_RF_TRY(hipGetLastError());
   size_t tb = 0;
   G2S_RF_TRY(rocprim::radix_sort_pairs(nullptr, tb, d_ikey.as<uint64_t>(), d_ikey2.as<uint64_t>(), d_irow.as<uint32_t>(),
@@ -207,8 +219,8 @@ int filter_join_device(FilterJoin& j, int device, std::string* err) {
   G2S_RF_TRY(d_gcnt.alloc((size_t)n * 8));
   G2S_RF_TRY(d_goff.alloc((size_t)n * 8));
   hipLaunchKernelGGL((k_gap<0, false>), dim3(n), dim3(kWave), 0, 0, d_win.as<FilterWindow>(), n, ikey, irow, nr,
-                     d_end.as<int64_t>(), d_flag.as<uint32_t>(), d_own.as<uint64_t>(), (const uint64_t*)nullptr, (uint64_t)0,
-                     R.max_span, d_gcnt.as<uint64_t>(), (const uint64_t*)nullptr, (uint64_t*)nullptr);
+                     p_end, p_flag, p_own, (const uint64_t*)nullptr, (uint64_t)0,
+                     max_span, d_gcnt.as<uint64_t>(), (const uint64_t*)nullptr, (uint64_t*)nullptr);
   G2S_RF_TRY(hipGetLastError());
   uint64_t nb = 0;
   G2S_RF_TRY(scan(d_gcnt.as<uint64_t>(), d_goff.as<uint64_t>(), n, &nb));
@@ -219,8 +231,8 @@ int filter_join_device(FilterJoin& j, int device, std::string* err) {
     G2S_RF_TRY(d_bk.alloc(nb * 8));
     G2S_RF_TRY(d_bk2.alloc(nb * 8));
     hipLaunchKernelGGL((k_gap<0, true>), dim3(n), dim3(kWave), 0, 0, d_win.as<FilterWindow>(), n, ikey, irow, nr,
-                       d_end.as<int64_t>(), d_flag.as<uint32_t>(), d_own.as<uint64_t>(), (const uint64_t*)nullptr,
-                       (uint64_t)0, R.max_span, (uint64_t*)nullptr, d_goff.as<const uint64_t>(), d_bk.as<uint64_t>());
+                       p_end, p_flag, p_own, (const uint64_t*)nullptr,
+                       (uint64_t)0, max_span, (uint64_t*)nullptr, d_goff.as<const uint64_t>(), d_bk.as<uint64_t>());
     G2S_RF_TRY(hipGetLastError());
     size_t sb = 0;
     G2S_RF_TRY(rocprim::radix_sort_keys(nullptr, sb, d_bk.as<uint64_t>(), d_bk2.as<uint64_t>(), (size_t)nb, 0, 64));
@@ -242,7 +254,7 @@ int filter_join_device(FilterJoin& j, int device, std::string* err) {
     Dev d_rcnt, d_roff;
     G2S_RF_TRY(d_rcnt.alloc(nr * 8));
     G2S_RF_TRY(d_roff.alloc(nr * 8));
-    hipLaunchKernelGGL((k_mates<false>), grdR, blk, 0, 0, d_mate.as<uint64_t>(), (uint32_t)nr, U, nu, d_rcnt.as<uint64_t>(),
+    hipLaunchKernelGGL((k_mates<false>), grdR, blk, 0, 0, p_mate, (uint32_t)nr, U, nu, d_rcnt.as<uint64_t>(),
                        (const uint64_t*)nullptr, (uint64_t*)nullptr);
     G2S_RF_TRY(hipGetLastError());
     G2S_RF_TRY(scan(d_rcnt.as<uint64_t>(), d_roff.as<uint64_t>(), nr, &n1));
@@ -250,7 +262,7 @@ int filter_join_device(FilterJoin& j, int device, std::string* err) {
     if (n1) {
       G2S_RF_TRY(d_l1.alloc(n1 * 8));
       G2S_RF_TRY(d_l1s.alloc(n1 * 8));
-      hipLaunchKernelGGL((k_mates<true>), grdR, blk, 0, 0, d_mate.as<uint64_t>(), (uint32_t)nr, U, nu, (uint64_t*)nullptr,
+      hipLaunchKernelGGL((k_mates<true>), grdR, blk, 0, 0, p_mate, (uint32_t)nr, U, nu, (uint64_t*)nullptr,
                          d_roff.as<const uint64_t>(), d_l1.as<uint64_t>());
       G2S_RF_TRY(hipGetLastError());
     }
@@ -259,7 +271,7 @@ int filter_join_device(FilterJoin& j, int device, std::string* err) {
   uint64_t n2 = 0;
   Dev d_l2, d_l2s;
   hipLaunchKernelGGL((k_gap<1, false>), dim3(n), dim3(kWave), 0, 0, d_win.as<FilterWindow>(), n, ikey, irow, nr,
-                     d_end.as<int64_t>(), d_flag.as<uint32_t>(), d_own.as<uint64_t>(), U, nu, R.max_span,
+                     p_end, p_flag, p_own, U, nu, max_span,
                      d_gcnt.as<uint64_t>(), (const uint64_t*)nullptr, (uint64_t*)nullptr);
   G2S_RF_TRY(hipGetLastError());
   G2S_RF_TRY(scan(d_gcnt.as<uint64_t>(), d_goff.as<uint64_t>(), n, &n2));
@@ -268,7 +280,7 @@ int filter_join_device(FilterJoin& j, int device, std::string* err) {
     G2S_RF_TRY(d_l2.alloc(n2 * 8));
     G2S_RF_TRY(d_l2s.alloc(n2 * 8));
     hipLaunchKernelGGL((k_gap<1, true>), dim3(n), dim3(kWave), 0, 0, d_win.as<FilterWindow>(), n, ikey, irow, nr,
-                       d_end.as<int64_t>(), d_flag.as<uint32_t>(), d_own.as<uint64_t>(), U, nu, R.max_span, (uint64_t*)nullptr,
+                       p_end, p_flag, p_own, U, nu, max_span, (uint64_t*)nullptr,
                        d_goff.as<const uint64_t>(), d_l2.as<uint64_t>());
     G2S_RF_TRY(hipGetLastError());
   }

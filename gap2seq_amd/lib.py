@@ -234,6 +234,12 @@ _SIGS = {
                                         C.POINTER(C.c_size_t), C.POINTER(C.c_int64)]),
     "g2s_test_last_filter_inflate": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
                                                C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "g2s_test_bam_rows": (C.c_int, [C.c_char_p, C.c_size_t, C.c_int, C.c_size_t, C.c_uint64, C.POINTER(C.c_int32),
+                                    C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64),
+                                    C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+    "g2s_test_name_hash": (C.c_int, [C.c_char_p, C.c_size_t, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "g2s_test_last_filter_rows": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                            C.POINTER(C.c_uint64), C.POINTER(C.c_int)]),
     "g2s_graph_validate": (C.c_int64, [C.c_void_p, C.c_char_p, C.c_size_t]),
     "g2s_test_post_gap": (C.c_int, [_VP, C.POINTER(g2s_params), C.POINTER(g2s_gap), C.c_int32,
                                     C.POINTER(C.c_uint32), C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.c_int32,
@@ -1150,3 +1156,46 @@ def last_filter_inflate():
     _check(load_library().g2s_test_last_filter_inflate(C.byref(d), C.byref(m), C.byref(bi), C.byref(bo), C.byref(a), C.byref(b)))
     return dict(on_device=d.value, members=m.value, bytes_in=bi.value, bytes_out=bo.value, ms_pass_a_inflate=a.value,
                 ms_pass_b_inflate=b.value)
+
+
+def bam_rows(data, device=-1, window=0):
+    """TEST HOOK binding (g2s_test_bam_rows): pass A alone on a BAM file in memory, by the host walk (device -1) or by the
+    kernels on `device`, `window` bytes at a time (0: the reader's window).  Returns (code, rows, g2s_filter_last_error's
+    text) with rows = dict(ref_id, pos, end, flag, h_own, h_mate: lists in file order; total, read_length, max_span), or
+    None when the code is not G2S_OK; nothing is raised, the code is the caller's to check."""
+    lib = load_library()
+    data = bytes(data)
+    cap = 1 << 12
+    while True:
+        arr = [(C.c_int32 * cap)(), (C.c_int32 * cap)(), (C.c_int64 * cap)(), (C.c_uint32 * cap)(), (C.c_uint64 * cap)(),
+               (C.c_uint64 * cap)()]
+        total, rl, span = C.c_uint64(0), C.c_int32(0), C.c_int64(0)
+        rc = lib.g2s_test_bam_rows(data, len(data), device, window, cap, *arr, C.byref(total), C.byref(rl), C.byref(span))
+        if rc != G2S_OK or total.value <= cap:
+            break
+        cap = total.value
+    msg = (lib.g2s_filter_last_error() or b"").decode("utf-8", "replace")
+    if rc != G2S_OK:
+        return rc, None, msg
+    n = total.value
+    names = ("ref_id", "pos", "end", "flag", "h_own", "h_mate")
+    rows = {k: list(a[:n]) for k, a in zip(names, arr)}
+    rows.update(total=n, read_length=rl.value, max_span=span.value)
+    return rc, rows, msg
+
+
+def name_hash(name, which):
+    """TEST HOOK binding (g2s_test_name_hash): (std::hash<std::string> of name + "/1" or "/2", the same from
+    csrc/name_hash.h); `name` is the l_name bytes of a record, of which the part in front of the first NUL counts."""
+    a, b = C.c_uint64(), C.c_uint64()
+    name = bytes(name)
+    _check(load_library().g2s_test_name_hash(name, len(name), which, C.byref(a), C.byref(b)))
+    return a.value, b.value
+
+
+def last_filter_rows():
+    """TEST HOOK binding (g2s_test_last_filter_rows): dict(on_device, windows, records, candidates, anomaly) of pass A in
+    the process's last batched filter call or bam_rows call"""
+    d, w, r, c, a = C.c_int(), C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_int()
+    _check(load_library().g2s_test_last_filter_rows(C.byref(d), C.byref(w), C.byref(r), C.byref(c), C.byref(a)))
+    return dict(on_device=d.value, windows=w.value, records=r.value, candidates=c.value, anomaly=a.value)

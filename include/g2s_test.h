@@ -137,6 +137,33 @@ int g2s_test_bgzf_inflate(const void* bytes, size_t n, int device, uint8_t* out,
 int g2s_test_last_filter_inflate(int* on_device, uint64_t* members, uint64_t* bytes_in, uint64_t* bytes_out,
                                  double* ms_pass_a_inflate, double* ms_pass_b_inflate);
 
+/* TEST HOOK: pass A of the batched read filter alone, on a BAM file in memory: one row per record in file order
+ * (reference, position, end position, flag, hash of the own name and of the mate's), the record count, the longest
+ * l_seq and the longest span of a record with a reference (1 when there is none).  device == -1: the host walk
+ * (BamFile::for_each).  device >= 0: the kernels of csrc/bam_rows.hip behind the device inflate — G2S_ERR_NO_DEVICE when
+ * it is no usable gfx950, G2S_ERR_HIP when the kernels refuse or meet an anomaly (g2s_test_last_filter_rows says
+ * which); never the host walk in their place, and no switch is read.  `window`: the bytes the kernels walk at a time;
+ * 0 = a whole window of inflated members (G2S_BAM_CHUNK), and smaller values cut that window further.  The first
+ * min(cap, *total) rows are written, so a caller whose capacity was too small calls again.  A file the host walk
+ * rejects is G2S_ERR_IO with its message in g2s_filter_last_error(). */
+int g2s_test_bam_rows(const void* bytes, size_t n, int device, size_t window, uint64_t cap, int32_t* ref_id, int32_t* pos,
+                      int64_t* end, uint32_t* flag, uint64_t* h_own, uint64_t* h_mate, uint64_t* total, int32_t* read_length,
+                      int64_t* max_span);
+
+/* TEST HOOK: the hash of the name bytes[0 .. strnlen(bytes, len)) followed by "/1" or "/2" (`which`: 1 or 2; len at
+ * most 255): *std_hash from std::hash<std::string>, as the host walk takes it, and *own_hash from the host compilation
+ * of csrc/name_hash.h, the function the kernels run. */
+int g2s_test_name_hash(const void* bytes, size_t len, int which, uint64_t* std_hash, uint64_t* own_hash);
+
+/* TEST HOOK: what pass A did in the process's last g2s_filter_reads_gaps[_mem] / _pool[_mem] call, or in the last
+ * g2s_test_bam_rows: whether its rows were made on the device, the windows the kernels walked, the records, the
+ * candidate record starts the kernels flagged (0 for a host walk), and the anomaly (csrc/bam_rows.h: RowsAnomaly; 0 =
+ * none) that handed the pass to the host walk: 1 a dead link of the chain, 2 more candidates than a window's capacity,
+ * 3 a carried record head longer than the room in front of a window, 4 a chain that does not end at the stream's end,
+ * 5 an allocation or a HIP call failed, 6 name_hash.h is not this build's std::hash, 7 a member did not inflate, 8 a
+ * file outside the kernels' limits.  Any pointer may be NULL. */
+int g2s_test_last_filter_rows(int* on_device, uint64_t* windows, uint64_t* records, uint64_t* candidates, int* anomaly);
+
 #ifdef __cplusplus
 }
 #endif
