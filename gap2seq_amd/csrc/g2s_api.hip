@@ -66,6 +66,39 @@ static int fail(int code, const std::string& msg) { tl_error = msg; return code;
     }                                                                                         \
   } while (0)
 
+// wall time in milliseconds: between two time points, and from one until now
+using TimePoint = std::chrono::steady_clock::time_point;
+static inline double ms_between(TimePoint a, TimePoint b) { return std::chrono::duration<double, std::milli>(b - a).count(); }
+static inline double ms_since(TimePoint t0) { return ms_between(t0, std::chrono::steady_clock::now()); }
+
+// The sum of two g2s_timing: every figure that counts gaps, launches, lists, bytes or the milliseconds of kernels and
+// host phases.  Not ms_total (a wall time: the caller measures its own), team_sessions and team_d3_sharded (what a
+// call was, not how much), the per-session team_ms_* (a team's own: the slices of g2s_team_fill add them), host_us
+// (one list on one session) and reserved1.
+static void timing_add(g2s_timing& into, const g2s_timing& part) {
+  into.ms_right_bfs += part.ms_right_bfs; into.ms_left_dp += part.ms_left_dp; into.ms_extract += part.ms_extract;
+  into.ms_d2h += part.ms_d2h; into.ms_host_post += part.ms_host_post;
+  into.xA += part.xA; into.sA += part.sA; into.xB += part.xB; into.sB += part.sB; into.xD += part.xD; into.sD += part.sD;
+  into.flank_bytes += part.flank_bytes; into.fill_bytes += part.fill_bytes;
+  into.launches_left_dp += part.launches_left_dp; into.retried_gaps += part.retried_gaps;
+  into.ms_fill_lds += part.ms_fill_lds; into.ms_extract_lds += part.ms_extract_lds;
+  into.x_fill_lds += part.x_fill_lds; into.s_fill_lds += part.s_fill_lds;
+  into.lds_tier_gaps += part.lds_tier_gaps; into.lds_launches += part.lds_launches;
+  into.log_pool_gaps += part.log_pool_gaps; into.rs_pool_gaps += part.rs_pool_gaps;
+  into.ms_prepare += part.ms_prepare;
+  into.ms_fill_seg += part.ms_fill_seg; into.seg_tier_gaps += part.seg_tier_gaps; into.seg_launches += part.seg_launches;
+  into.seg_segments += part.seg_segments; into.seg_timed_launches += part.seg_timed_launches; into.seg2_launches += part.seg2_launches;
+  into.ms_fill_segx += part.ms_fill_segx; into.segx_tier_gaps += part.segx_tier_gaps; into.segx_launches += part.segx_launches;
+  into.watchdog_gaps += part.watchdog_gaps;
+  into.ms_d3 += part.ms_d3; into.resident_launches += part.resident_launches; into.resident_fallbacks += part.resident_fallbacks;
+  into.draw_dependent_gaps += part.draw_dependent_gaps; into.d3_table_entries += part.d3_table_entries;
+  into.host_finished_gaps += part.host_finished_gaps; into.traced_in_fill_gaps += part.traced_in_fill_gaps;
+  into.guessed_in_fill_gaps += part.guessed_in_fill_gaps; into.guessed_groups += part.guessed_groups;
+  into.guessed_groups_resent += part.guessed_groups_resent;
+  into.team_groups += part.team_groups;
+  for (int q = 0; q < 16; q++) into.team_groups_by_session[q] += part.team_groups_by_session[q];
+}
+
 extern "C" int g2s_abi_version(void) { return G2S_ABI_VERSION; }
 extern "C" size_t g2s_backtrace_text(const g2s_gap* gap, const g2s_result* r, int k, char* out, size_t cap) {
   if (!gap || !r || !out || cap == 0 || !(r->flags & G2S_GAP_BACKTRACE_FAIL)) return 0;
@@ -1043,6 +1076,14 @@ extern "C" int g2s_session_skip_draws(g2s_session* s, uint64_t n) {
 // batch
 // ---------------------------------------------------------------------------
 
+// what resident_launch_fill says of one batch's fill launch (*units: 16-byte units of closure records it may write)
+struct ResidentLaunch {
+  uint64_t units = 0;
+  bool two_waves = false;
+  bool timed = false;  // HIP events around the fill kernel
+  bool segw = false;   // the large variant was launched behind it
+  size_t launched = 0;
+};
 struct g2s_batch {
   g2s_session* s = nullptr;
   std::vector<GapJob> jobs;
@@ -1064,12 +1105,12 @@ struct g2s_batch {
   bool fast_desc = false;                       // GapDev / D3Gap of every gap are in the session's pinned buffers (desc_owner)
   // g2s_fill_begin: the fill kernel of this list has been queued already (resident_launch_fill); g2s_batch_run goes on
   // with phase D3
-  bool pre_launched = false, pre_two = false, pre_timed = false, pre_segw = false;
+  bool pre_launched = false;
+  ResidentLaunch pre;      // ...that launch (and, with d3_queued, the one run_resident_queue went on from)
   bool d3_queued = false;  // ...and its phase D3 too (resident_queue_d3): g2s_batch_run only waits
   bool chain_broken = false;  // ...from the device state of a list in front of it which then did not end on the device
   bool others_in_flight = false;  // begun while another list was in flight: the device is shared (resident_launch_fill)
   bool through_begin = false;     // handed over by g2s_fill_begin: other lists' kernels will run beside this one's
-  uint64_t pre_units = 0;
   // Flank look-ups: by the look-up kernel in front of the fill kernels (upload_flanks queues it), or — allow_inline, a
   // list resident mode is about to launch in the regular segment tier — by the fill kernel's own waves (fill_seg.hip):
   // then only the text is staged and inline_pending says that d_flank does not hold the ids yet.  Whoever needs the ids
@@ -1370,8 +1411,7 @@ extern "C" int g2s_batch_prepare(g2s_session* s, const g2s_gap* gaps, size_t n, 
   if (rc != G2S_OK) { delete b; return rc; }
   if (n >= 1024 && GENV("G2S_DEBUG"))
     fprintf(stderr, "[g2s] prepare: sizes %.3f ms, text + descriptors %.3f ms, look-up launch %.3f ms\n",
-            std::chrono::duration<double, std::milli>(tp1 - tp0).count(), std::chrono::duration<double, std::milli>(tp2 - tp1).count(),
-            std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tp2).count());
+            ms_between(tp0, tp1), ms_between(tp1, tp2), ms_since(tp2));
   *out = b;
   return G2S_OK;
 }
@@ -1770,8 +1810,8 @@ int run_tier(g2s_batch* b, const std::vector<uint32_t>& ids, uint64_t scale, uin
         const auto now = std::chrono::steady_clock::now();
         if (seen != before) last_arrival = now;
         const bool finished = hipEventQuery(s->ev[2]) != hipErrorNotReady;
-        if (dbg_first < 0 && seen > 0) dbg_first = std::chrono::duration<double, std::milli>(now - t_launched).count();
-        if (dbg_fin < 0 && finished) dbg_fin = std::chrono::duration<double, std::milli>(now - t_launched).count();
+        if (dbg_first < 0 && seen > 0) dbg_first = ms_between(t_launched, now);
+        if (dbg_fin < 0 && finished) dbg_fin = ms_between(t_launched, now);
         const bool lull = seen > given && std::chrono::duration<double, std::micro>(now - last_arrival).count() > 60.0;
         if (seen - given >= chunk || lull || (finished && seen > given) || seen == total) {
           (*on_done)((const uint32_t*)td->done.p + given, seen - given);
@@ -1834,9 +1874,7 @@ int run_tier(g2s_batch* b, const std::vector<uint32_t>& ids, uint64_t scale, uin
     }
     if (GENV("G2S_DEBUG"))
       fprintf(stderr, "[g2s] run_tier: plan+upload+launch %.3f ms, polling/analysis %.3f ms, final sync %.3f ms\n",
-              std::chrono::duration<double, std::milli>(t_launched - t_enter).count(),
-              std::chrono::duration<double, std::milli>(t_polled - t_launched).count(),
-              std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_polled).count());
+              ms_between(t_enter, t_launched), ms_between(t_launched, t_polled), ms_since(t_polled));
   } else {
     // device -> host: per-gap results, then the packed closures
     HIP_TRY(td->outs.ensure(n * sizeof(GapOut)));
@@ -1849,7 +1887,7 @@ int run_tier(g2s_batch* b, const std::vector<uint32_t>& ids, uint64_t scale, uin
     if (total_sub)
       HIP_TRY(hipMemcpyAsync(td->subs.p, s->d_subout.p, total_sub * sizeof(SubState), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    b->timing.ms_d2h += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    b->timing.ms_d2h += ms_since(t0);
   }
   progress_note("finished: %zu gaps, lds %d seg %d", ids.size(), (int)lds, seg);
   float ms = 0;
@@ -2027,7 +2065,7 @@ int batch_stage1(g2s_batch* b, bool analyze, g2s_result* results) {
   auto lap = [&](const char* what) {  // (diagnostics) where stage 1 spends its time outside the launches
     if (!dbg_laps) return;
     const auto now = std::chrono::steady_clock::now();
-    fprintf(stderr, "[g2s] stage 1 lap %s: %.3f ms\n", what, std::chrono::duration<double, std::milli>(now - t_lap).count());
+    fprintf(stderr, "[g2s] stage 1 lap %s: %.3f ms\n", what, ms_between(t_lap, now));
     t_lap = now;
   };
   { const int rc = b->upload_flanks(); if (rc != G2S_OK) return rc; }
@@ -2157,7 +2195,7 @@ int batch_stage1(g2s_batch* b, bool analyze, g2s_result* results) {
         for (size_t h = 0; h < nh; h++) heavy_wait.push_back(heavy_here[h]);
       });
       if (!heavy_wait.empty() && s->pool->idle()) post_heavy();
-      ms_stream += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+      ms_stream += ms_since(t0);
       return;
     }
     fresh.clear();
@@ -2185,7 +2223,7 @@ int batch_stage1(g2s_batch* b, bool analyze, g2s_result* results) {
       });
     }
     if (!heavy_wait.empty() && s->pool->idle()) post_heavy();
-    ms_stream += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    ms_stream += ms_since(t0);
   };
 
   // ---- GPU: phases A-D1, retrying gaps whose tables overflowed with 8x larger ones
@@ -2482,7 +2520,7 @@ int batch_stage1(g2s_batch* b, bool analyze, g2s_result* results) {
     scale *= 8;
   }
 
-  b->timing.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+  b->timing.ms_total = ms_since(t_begin);
   if (analyze) {
     // ---- host: D2 + stop-depth analysis per gap, thread pool (teams: per group, so that it
     // overlaps the other sessions' kernels)
@@ -2495,7 +2533,7 @@ int batch_stage1(g2s_batch* b, bool analyze, g2s_result* results) {
     s->pool->run(nt, [&](size_t t) {
       for (size_t x = t * per; x < std::min(fresh.size(), (t + 1) * per); x++) analyze_gap(b, fresh[x], fp, &results[fresh[x]]);
     });
-    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_post).count();
+    const double ms = ms_since(t_post);
     b->timing.ms_host_post = ms + ms_stream;  // ms_stream overlapped the kernels
     b->timing.ms_total += ms;
     if (GENV("G2S_DEBUG")) {
@@ -2634,7 +2672,7 @@ int batches_stage2(const std::vector<g2s_batch*>& bs, g2s_session* lead, g2s_res
           }
           draws = b->prep[i].seg_mode ? seg_count_draws(g, v, b->prep[i], lead->rcache.ptr(draws_total))
                                       : sub_count_draws(g, v, b->prep[i], lead->rcache.ptr(draws_total));
-          ms_walks += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tw0).count();
+          ms_walks += ms_since(tw0);
           todo_tb[gi] = 1;
           right_fuz = in.reached_j;
         }
@@ -2648,7 +2686,7 @@ int batches_stage2(const std::vector<g2s_batch*>& bs, g2s_session* lead, g2s_res
     if (restart) draws_total = restart_max;
     grow_rands(draws_total + 1);
     draws_used = restart ? 0 : draws_total;
-    ms_order += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    ms_order += ms_since(t0);
     ms_order_loop = ms_order;
   };
 
@@ -2658,7 +2696,7 @@ int batches_stage2(const std::vector<g2s_batch*>& bs, g2s_session* lead, g2s_res
     lead->pool->run(nchunks, [&](size_t c) {
       for (size_t gi = c * per; gi < std::min(n, (c + 1) * per); gi++) analyze_gap(owner[gi], local[gi], fp, &results[gi]);
     });
-  ms_ana = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+  ms_ana = ms_since(t_begin);
   // The in-order pass and the tracebacks are pipelined over segments of the gap list: while
   // the pool traces segment s, this thread assigns the offsets of segment s+1.  When the
   // analysis has already written most fills, the few that are left are traced by the
@@ -2736,7 +2774,7 @@ int batches_stage2(const std::vector<g2s_batch*>& bs, g2s_session* lead, g2s_res
       n_rest += blk_rest[t];
     }
     var_cum.assign(vars_flat.size() + 1, 0);
-    ms_blocks = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tb0).count();
+    ms_blocks = ms_since(tb0);
   } else {
     for (size_t gi = 0; gi < n; gi++) {
       const g2s_batch::GapInfo& in = owner[gi]->info[local[gi]];
@@ -2782,7 +2820,7 @@ int batches_stage2(const std::vector<g2s_batch*>& bs, g2s_session* lead, g2s_res
         }
         draws = b->prep[i].seg_mode ? seg_count_draws(g, v, b->prep[i], lead->rcache.ptr(off))
                                     : sub_count_draws(g, v, b->prep[i], lead->rcache.ptr(off));
-        ms_walks += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tw0).count();
+        ms_walks += ms_since(tw0);
         todo_tb[gi] = 1;
       }
       expect_draws[gi] = draws;
@@ -2794,7 +2832,7 @@ int batches_stage2(const std::vector<g2s_batch*>& bs, g2s_session* lead, g2s_res
       grow_rands(draws_total + 1);
       draws_used = draws_total;
     }
-    ms_order += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    ms_order += ms_since(t0);
   };
   const size_t nseg = serial ? 1 : (n >= 256 ? std::min<size_t>(8, n / 128) : 1);
   std::vector<std::function<void(size_t)>> jobs(nseg);
@@ -2854,12 +2892,12 @@ int batches_stage2(const std::vector<g2s_batch*>& bs, g2s_session* lead, g2s_res
   auto t_end = std::chrono::steady_clock::now();
   if (GENV("G2S_DEBUG"))
     fprintf(stderr, "[g2s] host stage 2 (%s analysis): %.3f ms = setup+analysis %.3f + block pass %.3f + in-order pass %.3f (draw-count walks %.3f; %zu gaps traced inline, %zu with two lengths, %zu not traced by the analysis) + tracebacks\n",
-            analyze ? "with" : "after", std::chrono::duration<double, std::milli>(t_end - t_begin).count(), ms_ana, ms_blocks, ms_order,
+            analyze ? "with" : "after", ms_between(t_begin, t_end), ms_ana, ms_blocks, ms_order,
             ms_walks, n_inline, n_two, n_rest);
   if (timing) {
     timing->fill_bytes += fill_bytes.load();
-    timing->ms_host_post += std::chrono::duration<double, std::milli>(t_end - t_begin).count();
-    timing->ms_total += std::chrono::duration<double, std::milli>(t_end - t_begin).count();
+    timing->ms_host_post += ms_between(t_begin, t_end);
+    timing->ms_total += ms_between(t_begin, t_end);
   }
   return G2S_OK;
 }
@@ -2942,8 +2980,7 @@ static bool finish_gap_on_host(const Graph& g, const FillParams& fp, const GapJo
   }
   if (dbg_analysis_stats && n_segs >= 2000)
     fprintf(stderr, "[g2s] host-finished gap of %u segments: analysis %.3f ms (%s, %zu runs), traceback %.3f ms\n", n_segs,
-            std::chrono::duration<double, std::milli>(t_an - t_fin0).count(), pp.run_mode ? "runs" : pp.seg_mode ? "segments" : "states", pp.runs.size(),
-            std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_an).count());
+            ms_between(t_fin0, t_an), pp.run_mode ? "runs" : pp.seg_mode ? "segments" : "states", pp.runs.size(), ms_since(t_an));
   if ((uint32_t)r->draws != expect_draws || (r->flags & G2S_GAP_BACKTRACE_FAIL)) return false;
   r->fill_off = arena_off + (uint64_t)(j.lmf - r->left_fuz);
   r->fill_len = (int32_t)strlen(arena + r->fill_off);
@@ -2952,14 +2989,7 @@ static bool finish_gap_on_host(const Graph& g, const FillParams& fp, const GapJo
 
 // ---- resident mode, first half: one batch's fill kernel on its session's stream, records and closures into the
 // session's own device buffers (d_outs, d_sub).  *units: 16-byte units of closure records the launch may write.
-// Returns G2S_OK, 1 (the batch is not one for this mode) or an error.
-struct ResidentLaunch {
-  uint64_t units = 0;
-  bool two_waves = false;
-  bool timed = false;  // HIP events around the fill kernel
-  bool segw = false;   // the large variant was launched behind it
-  size_t launched = 0;
-};
+// Returns G2S_OK, 1 (the batch is not one for this mode) or an error.  (ResidentLaunch: in front of g2s_batch)
 // Resident mode brackets its kernels with HIP events on one launch in eight (the session's first included): an
 // event between two kernels costs the stream 4-5 us, three of them 4 % of a 500-gap list's step, and the product
 // has no use for the durations — bench.py and the tests read them.  G2S_KERNEL_TIMING=all|off|sample:N overrides.
@@ -3784,7 +3814,7 @@ static int resident_d3_wait(g2s_session* s, g2s_timing* tm_out, double* ms_d3_ou
       const auto t_one = std::chrono::steady_clock::now();
       struct Lap { const std::chrono::steady_clock::time_point t0, th; const D3HostItem& h; size_t x; bool on;
                    ~Lap() { if (on && h.n_segs >= 2000) fprintf(stderr, "[g2s] host-finished item %zu (gap %u): %u segments, %u draws: picked up %.3f ms after the hand-over, %.3f ms\n", x, h.gap, h.n_segs, h.draws,
-                                                              std::chrono::duration<double, std::milli>(t0 - th).count(), std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count()); } }
+                                                              ms_between(th, t0), ms_since(t0)); } }
           lap{t_one, t_handed, h, x, dbg_analysis_stats};
       int32_t ei = early_posted ? s->early_of_gap[h.gap] : -1;  // (analysed when it arrived: the traceback is left)
       if (early_inline) for (const auto& pr : inline_done) if (pr.first == h.gap) { ei = (int32_t)pr.second; break; }
@@ -3916,9 +3946,8 @@ static int resident_d3_wait(g2s_session* s, g2s_timing* tm_out, double* ms_d3_ou
   s->laps_valid = true;
   if (GENV("G2S_DEBUG"))
     fprintf(stderr, "[g2s] resident mode, phase D3 of %zu gaps: set-up + launches %.3f ms, wait for the hand-over %.3f ms, %zu gaps finished by the host in %.3f ms, wait for the trace kernel %.3f ms, results %.3f ms (kernels %.3f ms); %u draw-dependent gaps, %llu table entries, %llu draws; results %s, text %s\n",
-            n, std::chrono::duration<double, std::milli>(t_launched - t_enter).count(), std::chrono::duration<double, std::milli>(t_handed - t_launched).count(),
-            ni, std::chrono::duration<double, std::milli>(t_finished - t_handed).count(), std::chrono::duration<double, std::milli>(t_synced - t_finished).count(),
-            std::chrono::duration<double, std::milli>(t_end - t_synced).count(), ms_d3, hsum->n_var,
+            n, ms_between(t_enter, t_launched), ms_between(t_launched, t_handed), ni, ms_between(t_handed, t_finished),
+            ms_between(t_finished, t_synced), ms_between(t_synced, t_end), ms_d3, hsum->n_var,
             (unsigned long long)hsum->table_entries, (unsigned long long)hsum->draws_total, res_direct ? "direct" : "staged",
             arena_direct ? "direct" : "staged");
   return G2S_OK;
@@ -3930,6 +3959,88 @@ static int resident_d3(g2s_session* s, const ResidentList& L, bool timed, bool r
   const int rc = resident_d3_launch(s, L, timed, rand_launched, results, arena, false);
   if (rc != G2S_OK) return rc;
   return resident_d3_wait(s, tm_out, ms_d3_out, fell_back);
+}
+
+// The list that is ONE batch on its own session — a list of run_resident, a group of a sharded list, a rank's share:
+// records and closures where the batch's fill kernel left them.  arena_base: where the batch's share of the arena
+// begins, arena_total: the whole arena.
+static ResidentList resident_list_of(g2s_batch* b, size_t arena_base, size_t arena_total) {
+  g2s_session* s = b->s;
+  const size_t n = b->jobs.size();
+  ResidentList L;
+  L.groups.push_back(b);
+  L.n = n; L.group_size = std::max<size_t>(n, 1);
+  L.group_arena.push_back(arena_base);
+  L.arena_bytes = arena_total;
+  L.outs_dev = (const GapOut*)s->d_outs.p;
+  L.sub_dev = (const SubRec*)s->d_sub.p;
+  L.sub_region = 0;
+  L.pin = &s->h_d3;
+  L.rnd_cap = b->rnd_cap; L.dmax = b->dmax; L.has_skip = b->has_skip;
+  L.gaps_dev = (const GapDev*)s->d_gaps.p;
+  return L;
+}
+// (the D3Gap offsets of the session's n gaps are within their batch's share: make them offsets into the arena)
+static void shift_arena_offsets(g2s_session* s, size_t n, size_t base) {
+  D3Gap* dq = (D3Gap*)s->h_d3.p;
+  for (size_t i = 0; i < n; i++) dq[i].arena_off += (uint64_t)base;
+}
+// A session whose queued phase D3 will not be finished (its list goes another way): what it queued is waited for
+// and dropped, the buffers of its fill launch (n gaps; 0: it made none) are reset.
+static void resident_abandon(g2s_session* s, size_t n) {
+  (void)hipSetDevice(s->device);
+  (void)hipStreamSynchronize(s->stream);
+  (void)hipStreamSynchronize(s->stream2);
+  delete (D3Pending*)s->d3_pending;
+  s->d3_pending = nullptr;
+  s->d_d3.clean = 0;
+  if (n) (void)resident_reset_fill(s, n);
+}
+
+// ---- One batch of a list whose phase D3 is SHARDED (the comment in front of team_resident_sharded): the three steps
+// on the batch's session.  What lies between them — the batches' places in the list's one rand() stream — is the
+// caller's: the threads of a team meet at barriers, the ranks of g2s_share_* exchange through their communicator.
+// Each step returns G2S_OK, an error, or why this is not a list for the form:
+enum { SHARD_NOT_RESIDENT = 1,   // the batch is not one for resident mode (resident_launch_fill)
+       SHARD_NOT_D3 = 2,         // ...not one for phase D3 on the device (resident_d3_launch)
+       SHARD_BEYOND_DEVICE = 3   // a gap beyond every tier of the device, or tables beyond the budget (D3Summary.status)
+};
+// step 1: fill kernel, classes, the batch's totals (fewest draws, spread).  The batch is prepared (prepare_group);
+// results: of its first gap; arena: the whole list's, arena_total bytes; what: the text of a failing wait.
+static int shard_fill(g2s_batch* b, g2s_result* results, char* arena, size_t arena_total, ResidentLaunch* rl, uint64_t totals[2],
+                      const char* what) {
+  g2s_session* s = b->s;
+  int rc = resident_launch_fill(b, rl);
+  if (rc != G2S_OK) return rc == 1 ? (int)SHARD_NOT_RESIDENT : rc;
+  const ResidentList L = resident_list_of(b, b->arena_base, arena_total);
+  if (b->arena_base) shift_arena_offsets(s, L.n, b->arena_base);
+  rc = resident_d3_launch(s, L, rl->timed, false, results, arena, true, true);
+  if (rc == 1) return SHARD_NOT_D3;
+  if (rc == G2S_OK && hipStreamSynchronize(s->stream) != hipSuccess) rc = fail(G2S_ERR_HIP, what);
+  if (rc != G2S_OK) return rc;
+  const D3Summary* hs = ((D3Pending*)s->d3_pending)->hsum;
+  if (hs->status != 0) return SHARD_BEYOND_DEVICE;
+  totals[0] = hs->draws_min; totals[1] = hs->draws_spread;
+  return G2S_OK;
+}
+// step 2: the stream as far as the batch reaches, the tables, the group function (pinned memory of the session)
+static int shard_tables(g2s_session* s, uint32_t base0, uint32_t R0, const uint32_t* win, const uint32_t** group_fn, const char* what) {
+  int rc = resident_d3_sharded_tables(s, base0, R0, win);
+  if (rc == G2S_OK && hipStreamSynchronize(s->stream) != hipSuccess) rc = fail(G2S_ERR_HIP, what);
+  if (rc != G2S_OK) return rc;
+  const D3Pending* dp = (const D3Pending*)s->d3_pending;
+  if (dp->hsum->status != 0) return SHARD_BEYOND_DEVICE;
+  *group_fn = dp->group_fn;
+  return G2S_OK;
+}
+// step 3: chain from the deviation the batch starts with, hand-off, trace kernel; the gaps the host finishes; the summary
+static int shard_trace(g2s_batch* b, uint32_t d_in, double* ms_d3, bool* fell_back) {
+  g2s_session* s = b->s;
+  *fell_back = false;
+  int rc = resident_d3_sharded_trace(s, d_in);
+  if (rc == G2S_OK) rc = resident_d3_wait(s, &b->timing, ms_d3, fell_back);
+  if (rc == G2S_OK) rc = resident_reset_fill(s, b->jobs.size());
+  return rc;
 }
 
 // One batch on one session.  Returns G2S_OK (done), 1 (not applicable / fall back to the host path), or an error.
@@ -3954,7 +4065,7 @@ static int run_resident_queue(g2s_batch* b, g2s_result* results, char* arena, bo
     rand_launched = true;
   }
   if (b->pre_launched) {  // (g2s_fill_begin queued the fill kernel when the list was handed over)
-    rl.units = b->pre_units; rl.two_waves = b->pre_two; rl.timed = b->pre_timed; rl.segw = b->pre_segw; rl.launched = b->n_valid;
+    rl = b->pre;
     b->pre_launched = false;
   } else {
     const int rc = resident_launch_fill(b, &rl, results, arena);
@@ -3963,23 +4074,9 @@ static int run_resident_queue(g2s_batch* b, g2s_result* results, char* arena, bo
       return rc;
     }
   }
-  ResidentList L;
-  L.groups.push_back(b);
-  L.n = n; L.group_size = std::max<size_t>(n, 1);
-  L.group_arena.push_back(b->arena_base);
-  L.arena_bytes = b->arena_base + b->arena_bytes;
-  L.outs_dev = (const GapOut*)s->d_outs.p;
-  L.sub_dev = (const SubRec*)s->d_sub.p;
-  L.sub_region = 0;
-  L.pin = &s->h_d3;
-  L.rnd_cap = b->rnd_cap; L.dmax = b->dmax; L.has_skip = b->has_skip;
+  ResidentList L = resident_list_of(b, b->arena_base, b->arena_base + b->arena_bytes);
   L.rnd_sum = b->rnd_sum; L.restart = b->set_list;
-  L.gaps_dev = (const GapDev*)s->d_gaps.p;
-  if (b->arena_base) {  // (the D3Gap offsets are within the batch's share: make them offsets into the arena)
-    D3Gap* dq = (D3Gap*)s->h_d3.p;
-    for (size_t i = 0; i < n; i++) dq[i].arena_off += (uint64_t)b->arena_base;
-    s->desc_owner = nullptr;
-  }
+  if (b->arena_base) { shift_arena_offsets(s, n, b->arena_base); s->desc_owner = nullptr; }
   return resident_d3_launch(s, L, rl.timed, rand_launched, results, arena, no_spin, false, chain_from);
 }
 static int run_resident_finish(g2s_batch* b, const ResidentLaunch& rl, std::chrono::steady_clock::time_point t_enter) {
@@ -4002,7 +4099,7 @@ static int run_resident_finish(g2s_batch* b, const ResidentLaunch& rl, std::chro
   tm.seg_launches++;
   if (rl.timed) tm.seg_timed_launches++;
   if (rl.two_waves) tm.seg2_launches++;
-  tm.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_enter).count();
+  tm.ms_total = ms_since(t_enter);
   if (GENV("G2S_DEBUG")) fprintf(stderr, "[g2s] resident mode: %zu gaps in %.3f ms (fill kernel %.3f ms)\n", n, tm.ms_total, ms_fill);
   return G2S_OK;
 }
@@ -4011,7 +4108,7 @@ int run_resident(g2s_batch* b, g2s_result* results, char* arena) {
   ResidentLaunch rl;
   if (b->d3_queued) {  // (g2s_fill_begin queued everything already)
     b->d3_queued = false;
-    rl.units = b->pre_units; rl.two_waves = b->pre_two; rl.timed = b->pre_timed; rl.segw = b->pre_segw; rl.launched = b->n_valid;
+    rl = b->pre;
     if (!b->chain_broken) return run_resident_finish(b, rl, t_enter);
     // Its rand() stream was to continue, on the device, that of a list which then did not end there: the kernels
     // are waited for, what they wrote is dropped, and the list runs again from the host's generator.
@@ -4066,9 +4163,8 @@ extern "C" int g2s_batch_run(g2s_batch* b, g2s_result* results, char* arena, siz
   const auto t_run2 = std::chrono::steady_clock::now();
   if (rc == G2S_OK) rc = batches_stage2(std::vector<g2s_batch*>{b}, s, results, arena, &b->timing, false);
   if (GENV("G2S_DEBUG")) {
-    auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point c) { return std::chrono::duration<double, std::milli>(c - a).count(); };
     fprintf(stderr, "[g2s] batch_run: init %.3f ms, stage 1 %.3f ms, wait for rand() values %.3f ms, stage 2 %.3f ms\n",
-            ms(t_run0, t_run1), ms(t_run1, t_join), ms(t_join, t_run2), ms(t_run2, std::chrono::steady_clock::now()));
+            ms_between(t_run0, t_run1), ms_between(t_run1, t_join), ms_between(t_join, t_run2), ms_since(t_run2));
   }
   s->last_timing = b->timing;
   return rc;
@@ -4134,7 +4230,65 @@ struct TeamBarrier {
     cv.wait(lk, [&] { return gen != g; });
   }
 };
+// While a team fills a list: the size threshold of resident mode is the list's, not the groups' (in_team_list), and
+// sessions that share a device know it; sharded: every session finishes its own group.
+struct InTeam {
+  g2s_session* const* ss; int ns; bool sharded;
+  InTeam(g2s_session* const* a, int b_, bool sharded_) : ss(a), ns(b_), sharded(sharded_) {
+    for (int t = 0; t < ns; t++) {
+      ss[t]->in_team_list = true;
+      if (sharded) { ss[t]->team_sharded = true; ss[t]->team_sessions = ns; }
+      for (int u = 0; u < ns; u++) if (u != t && ss[u]->device == ss[t]->device) ss[t]->team_shares_device = true;
+    }
+  }
+  ~InTeam() {
+    for (int t = 0; t < ns; t++) {
+      ss[t]->in_team_list = false; ss[t]->team_shares_device = false;
+      if (sharded) { ss[t]->team_sharded = false; ss[t]->team_sessions = 1; }
+    }
+  }
+};
 }  // namespace
+// where each group's share of the list's fill arena begins (and, last, where the arena ends)
+static std::vector<size_t> group_arena_offsets(const g2s_session* lead, const g2s_gap* gaps, size_t n, size_t group_size) {
+  const size_t ngroups = (n + group_size - 1) / group_size;
+  std::vector<size_t> at(ngroups + 1, 0);
+  for (size_t gi = 0; gi < ngroups; gi++) {
+    const size_t off = gi * group_size, cnt = std::min(group_size, n - off);
+    at[gi + 1] = at[gi] + g2s_team_arena_bytes(lead, gaps + off, cnt);
+  }
+  return at;
+}
+// g2s_batch_prepare for a group of a list: how long it took, and the group's share of the list's arena
+static int prepare_group(g2s_session* s, const g2s_gap* gaps, size_t cnt, char* arena, size_t arena_base, g2s_batch** out) {
+  g2s_batch* b = nullptr;
+  const auto t0 = std::chrono::steady_clock::now();
+  const int rc = g2s_batch_prepare(s, gaps, cnt, &b);
+  if (rc != G2S_OK) return rc;
+  b->timing.ms_prepare = ms_since(t0);
+  b->arena = arena + arena_base;
+  b->arena_base = arena_base;
+  *out = b;
+  return G2S_OK;
+}
+// worker(t) for every session t of a team, each on a host thread of its own from the lead's team pool (persistent:
+// creating and joining a thread per session and list cost a 10 000-gap list on eight sessions 0.2 ms)
+template <class Worker>
+static void team_run(g2s_session* lead, int nsessions, Worker&& worker) {
+  if (nsessions <= 1) { worker(0); return; }
+  if (!lead->team_pool || lead->team_pool->size() < nsessions - 1) {
+    delete lead->team_pool;
+    lead->team_pool = new WorkerPool(nsessions - 1);
+  }
+  const std::function<void(size_t)> job = [&](size_t t) { worker((int)t); };
+  lead->team_pool->run((size_t)nsessions, job);
+}
+// what a team's call returns when sessions failed: the code and the text of the last one that did
+static int team_last_error(const std::vector<int>& rcs, const std::vector<std::string>& errs) {
+  int rc = G2S_OK;
+  for (size_t t = 0; t < rcs.size(); t++) if (rcs[t] != G2S_OK) { rc = rcs[t]; tl_error = errs[t]; }
+  return rc;
+}
 static int team_resident_sharded(g2s_session* const* sessions, int nsessions, const g2s_gap* gaps, size_t n, size_t group_size,
                                  g2s_result* results, char* arena, g2s_timing* timing_out) {
   g2s_session* lead = sessions[0];
@@ -4146,22 +4300,9 @@ static int team_resident_sharded(g2s_session* const* sessions, int nsessions, co
     void* d = nullptr;
     if (!device_pointer_of(results, &d) || !device_pointer_of(arena, &d)) return 1;
   }
-  struct InTeam {
-    g2s_session* const* ss; int ns;
-    InTeam(g2s_session* const* a, int b_) : ss(a), ns(b_) {
-      for (int t = 0; t < ns; t++) {
-        ss[t]->in_team_list = true; ss[t]->team_sharded = true; ss[t]->team_sessions = ns;
-        for (int u = 0; u < ns; u++) if (u != t && ss[u]->device == ss[t]->device) ss[t]->team_shares_device = true;
-      }
-    }
-    ~InTeam() { for (int t = 0; t < ns; t++) { ss[t]->in_team_list = false; ss[t]->team_sharded = false; ss[t]->team_shares_device = false; ss[t]->team_sessions = 1; } }
-  } in_team(sessions, nsessions);
+  InTeam in_team(sessions, nsessions, true);
   const auto t_begin = std::chrono::steady_clock::now();
-  std::vector<size_t> group_arena(ngroups + 1, 0);
-  for (size_t gi = 0; gi < ngroups; gi++) {
-    const size_t off = gi * group_size, cnt = std::min(group_size, n - off);
-    group_arena[gi + 1] = group_arena[gi] + g2s_team_arena_bytes(lead, gaps + off, cnt);
-  }
+  const std::vector<size_t> group_arena = group_arena_offsets(lead, gaps, n, group_size);
   std::vector<g2s_batch*> subs(ngroups, nullptr);
   std::vector<ResidentLaunch> rls(ngroups);
   std::vector<int> rcs((size_t)nsessions, G2S_OK);
@@ -4182,42 +4323,15 @@ static int team_resident_sharded(g2s_session* const* sessions, int nsessions, co
     // ---- step 1: fill kernel, classes, totals
     bool mine_ok = false;
     {
-      g2s_batch* b = nullptr;
-      const auto t0 = std::chrono::steady_clock::now();
-      int rc = g2s_batch_prepare(s, gaps + off, cnt, &b);
+      int rc = prepare_group(s, gaps + off, cnt, arena, group_arena[(size_t)t], &subs[(size_t)t]);
       if (rc == G2S_OK) {
-        subs[(size_t)t] = b;
-        b->timing.ms_prepare = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        b->arena = arena + group_arena[(size_t)t];
-        b->arena_base = group_arena[(size_t)t];
-        rc = resident_launch_fill(b, &rls[(size_t)t]);
-        if (rc == 1) give_up.store(1);
-        else if (rc == G2S_OK) {
-          ResidentList L;
-          L.groups.push_back(b);
-          L.n = cnt; L.group_size = std::max<size_t>(cnt, 1);
-          L.group_arena.push_back(group_arena[(size_t)t]);
-          L.arena_bytes = group_arena[ngroups];
-          L.outs_dev = (const GapOut*)s->d_outs.p;
-          L.sub_dev = (const SubRec*)s->d_sub.p;
-          L.sub_region = 0;
-          L.pin = &s->h_d3;
-          L.rnd_cap = b->rnd_cap; L.dmax = b->dmax; L.has_skip = b->has_skip;
-          L.gaps_dev = (const GapDev*)s->d_gaps.p;
-          {  // (the D3Gap offsets are within the group's share: make them offsets into the arena)
-            D3Gap* dq = (D3Gap*)s->h_d3.p;
-            for (size_t i = 0; i < cnt; i++) dq[i].arena_off += (uint64_t)group_arena[(size_t)t];
-            s->desc_owner = nullptr;
-          }
-          rc = resident_d3_launch(s, L, rls[(size_t)t].timed, false, results + off, arena, true, true);
-          if (rc == G2S_OK && hipStreamSynchronize(s->stream) != hipSuccess) rc = fail(G2S_ERR_HIP, "sharded list, step 1");
-          if (rc == G2S_OK) {
-            const D3Summary* hs = ((D3Pending*)s->d3_pending)->hsum;
-            if (hs->status != 0) give_up.store(1);  // (a gap beyond every tier, tables beyond the budget: the host path's business)
-            tot_min[(size_t)t] = hs->draws_min; tot_spread[(size_t)t] = hs->draws_spread;
-            mine_ok = true;
-          }
-        }
+        uint64_t tot[2] = {0, 0};
+        rc = shard_fill(subs[(size_t)t], results + off, arena, group_arena[ngroups], &rls[(size_t)t], tot, "sharded list, step 1");
+        if (rc >= 0 && rc != SHARD_NOT_RESIDENT) s->desc_owner = nullptr;  // (its D3Gap offsets are the arena's now)
+        if (rc == G2S_OK) { tot_min[(size_t)t] = tot[0]; tot_spread[(size_t)t] = tot[1]; mine_ok = true; }
+        // (beyond the device: the host path's business.  SHARD_NOT_D3 is not reported here, unlike in g2s_share_begin:
+        // the group's session sits the steps out — resident_launch_fill in front of it has the same bounds)
+        else if (rc == SHARD_NOT_RESIDENT || rc == SHARD_BEYOND_DEVICE) give_up.store(1);
       }
       if (rc < 0) failed(rc);
     }
@@ -4230,10 +4344,8 @@ static int team_resident_sharded(g2s_session* const* sessions, int nsessions, co
     // ---- step 2: the stream, the tables, the group function
     if (go2) {
       base0[(size_t)t] = (uint32_t)b0; R0[(size_t)t] = (uint32_t)r0;
-      int rc = resident_d3_sharded_tables(s, (uint32_t)b0, (uint32_t)r0, win);
-      if (rc == G2S_OK && hipStreamSynchronize(s->stream) != hipSuccess) rc = fail(G2S_ERR_HIP, "sharded list, step 2");
-      if (rc == G2S_OK && ((D3Pending*)s->d3_pending)->hsum->status != 0) give_up.store(1);
-      if (rc == G2S_OK) gfn[(size_t)t] = ((D3Pending*)s->d3_pending)->group_fn;
+      const int rc = shard_tables(s, (uint32_t)b0, (uint32_t)r0, win, &gfn[(size_t)t], "sharded list, step 2");
+      if (rc == SHARD_BEYOND_DEVICE) give_up.store(1);
       if (rc < 0) failed(rc);
     }
     bar.wait();
@@ -4244,33 +4356,15 @@ static int team_resident_sharded(g2s_session* const* sessions, int nsessions, co
       for (int q = 0; q < t; q++) d = gfn[(size_t)q][std::min(d, R0[(size_t)q])];
       d_in[(size_t)t] = d;
       // ---- step 3: chain, hand-off, trace; the gaps the host finishes; the summary
-      int rc = resident_d3_sharded_trace(s, d);
       bool fb = false;
-      if (rc == G2S_OK) rc = resident_d3_wait(s, &subs[(size_t)t]->timing, &ms_d3[(size_t)t], &fb);
-      if (rc == G2S_OK) rc = resident_reset_fill(s, cnt);
+      const int rc = shard_trace(subs[(size_t)t], d, &ms_d3[(size_t)t], &fb);
       fell[(size_t)t] = fb ? 1 : 0;
-      ms_wall[(size_t)t] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+      ms_wall[(size_t)t] = ms_since(t_begin);
       if (rc < 0) failed(rc);
-    } else if (s->d3_pending) {  // (the list goes another way: what this session queued is waited for and dropped)
-      (void)hipSetDevice(s->device);
-      (void)hipStreamSynchronize(s->stream);
-      (void)hipStreamSynchronize(s->stream2);
-      delete (D3Pending*)s->d3_pending;
-      s->d3_pending = nullptr;
-      s->d_d3.clean = 0;
-      (void)resident_reset_fill(s, cnt);
-    }
+    } else if (s->d3_pending) resident_abandon(s, cnt);  // (the list goes another way)
   };
-  {
-    if (!lead->team_pool || lead->team_pool->size() < nsessions - 1) {
-      delete lead->team_pool;
-      lead->team_pool = new WorkerPool(nsessions - 1);
-    }
-    const std::function<void(size_t)> job = [&](size_t t) { worker((int)t); };
-    lead->team_pool->run((size_t)nsessions, job);
-  }
-  int rc = G2S_OK;
-  for (int t = 0; t < nsessions; t++) if (rcs[(size_t)t] != G2S_OK) { rc = rcs[(size_t)t]; tl_error = errs[(size_t)t]; }
+  team_run(lead, nsessions, worker);
+  int rc = team_last_error(rcs, errs);
   bool fell_back = give_up.load() == 1;
   for (size_t q = 0; q < ngroups; q++) fell_back = fell_back || fell[q] != 0 || !subs[q];
   g2s_timing total;
@@ -4285,12 +4379,10 @@ static int team_resident_sharded(g2s_session* const* sessions, int nsessions, co
     for (size_t gi = 0; gi < ngroups; gi++) {
       const g2s_timing& t = subs[gi]->timing;
       g2s_session* s = sessions[gi];
-      total.flank_bytes += t.flank_bytes; total.ms_prepare += t.ms_prepare;
-      total.xA += t.xA; total.sA += t.sA; total.xB += t.xB; total.sB += t.sB; total.xD += t.xD; total.sD += t.sD;
-      total.seg_segments += t.seg_segments; total.seg_tier_gaps += t.seg_tier_gaps; total.segx_tier_gaps += t.segx_tier_gaps;
-      total.fill_bytes += t.fill_bytes; total.ms_d3 += t.ms_d3;
-      total.draw_dependent_gaps += t.draw_dependent_gaps; total.host_finished_gaps += t.host_finished_gaps;
-      total.d3_table_entries += t.d3_table_entries;
+      // (a group's timing holds what its preparation and resident_d3_wait wrote and zeros otherwise: the fill launch
+      // is counted below, where its events are read; no fill kernel of a team's list traces or guesses —
+      // resident_launch_fill, use_tr.  The groups' resident_launches are replaced behind the loop: one list)
+      timing_add(total, t);
       float ms_fill = 0;
       if (rls[gi].timed && hipSetDevice(s->device) == hipSuccess && hipEventElapsedTime(&ms_fill, s->ev[1], s->ev[2]) == hipSuccess) {
         total.ms_fill_seg += ms_fill; total.seg_timed_launches++;
@@ -4308,7 +4400,7 @@ static int team_resident_sharded(g2s_session* const* sessions, int nsessions, co
   for (g2s_batch* b : subs) if (b) g2s_batch_free(b);
   if (rc != G2S_OK) return rc;
   if (fell_back) return 1;
-  total.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+  total.ms_total = ms_since(t_begin);
   if (timing_out) *timing_out = total;
   lead->last_timing = total;
   return G2S_OK;
@@ -4323,16 +4415,7 @@ static int team_resident(g2s_session* const* sessions, int nsessions, const g2s_
   g2s_session* lead = sessions[0];
   if (!resident_applicable(lead, n)) return 1;
   for (int t = 1; t < nsessions; t++) if (!resident_applicable(sessions[t], n)) return 1;
-  struct InTeam {  // (the size threshold of resident mode is the list's, not the groups')
-    g2s_session* const* ss; int ns;
-    InTeam(g2s_session* const* a, int b_) : ss(a), ns(b_) {
-      for (int t = 0; t < ns; t++) {
-        ss[t]->in_team_list = true;
-        for (int u = 0; u < ns; u++) if (u != t && ss[u]->device == ss[t]->device) ss[t]->team_shares_device = true;
-      }
-    }
-    ~InTeam() { for (int t = 0; t < ns; t++) { ss[t]->in_team_list = false; ss[t]->team_shares_device = false; } }
-  } in_team(sessions, nsessions);
+  InTeam in_team(sessions, nsessions, false);
   const auto t_begin = std::chrono::steady_clock::now();
   GroupQueue queue(n, group_size);
   const size_t ngroups = queue.ngroups;
@@ -4340,11 +4423,7 @@ static int team_resident(g2s_session* const* sessions, int nsessions, const g2s_
   std::vector<int> owner(ngroups, -1);
   std::vector<float> fill_ms(ngroups, 0.f);
   std::vector<char> two(ngroups, 0), timed_g(ngroups, 0);
-  std::vector<size_t> group_arena(ngroups + 1, 0);
-  for (size_t gi = 0; gi < ngroups; gi++) {
-    const size_t off = gi * group_size, cnt = std::min(group_size, n - off);
-    group_arena[gi + 1] = group_arena[gi] + g2s_team_arena_bytes(lead, gaps + off, cnt);
-  }
+  const std::vector<size_t> group_arena = group_arena_offsets(lead, gaps, n, group_size);
   // the lead's device gathers every group's records and closure records (a region per group)
   const uint64_t region = (uint64_t)group_size * 128u + 2u * G2S_SEG_CAP;  // 16-byte units, what one launch may write
   if (hipSetDevice(lead->device) != hipSuccess) return fail(G2S_ERR_NO_DEVICE, "cannot select device");
@@ -4375,16 +4454,10 @@ static int team_resident(g2s_session* const* sessions, int nsessions, const g2s_
     size_t gi = 0, off = 0, cnt = 0;
     while (queue.pull(&gi, &off, &cnt)) {
       owner[gi] = t;
-      g2s_batch* b = nullptr;
-      auto t0 = std::chrono::steady_clock::now();
-      int rc = g2s_batch_prepare(s, gaps + off, cnt, &b);
+      int rc = prepare_group(s, gaps + off, cnt, arena, group_arena[gi], &subs[gi]);
       if (rc == G2S_OK) {
-        subs[gi] = b;
-        b->timing.ms_prepare = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        b->arena = arena + group_arena[gi];
-        b->arena_base = group_arena[gi];
         ResidentLaunch rl;
-        rc = resident_launch_fill(b, &rl);
+        rc = resident_launch_fill(subs[gi], &rl);
         if (rc == 1) { not_for_us.fetch_add(1); queue.abort(); break; }
         if (rc == G2S_OK) {
           two[gi] = rl.two_waves ? 1 : 0;
@@ -4414,19 +4487,8 @@ static int team_resident(g2s_session* const* sessions, int nsessions, const g2s_
       if (rc != G2S_OK) { rcs[(size_t)t] = rc; errs[(size_t)t] = tl_error; queue.abort(); break; }
     }
   };
-  {
-    // one host thread per session, from the lead's team pool (persistent: creating and joining a thread per
-    // session and list cost a 10 000-gap list on eight sessions 0.2 ms)
-    if (nsessions > 1 && (!lead->team_pool || lead->team_pool->size() < nsessions - 1)) {
-      delete lead->team_pool;
-      lead->team_pool = new WorkerPool(nsessions - 1);
-    }
-    const std::function<void(size_t)> job = [&](size_t t) { worker((int)t); };
-    if (nsessions > 1) lead->team_pool->run((size_t)nsessions, job);
-    else worker(0);
-  }
-  int rc = G2S_OK;
-  for (int t = 0; t < nsessions; t++) if (rcs[(size_t)t] != G2S_OK) { rc = rcs[(size_t)t]; tl_error = errs[(size_t)t]; }
+  team_run(lead, nsessions, worker);
+  int rc = team_last_error(rcs, errs);
   bool fell_back = not_for_us.load() != 0;
   for (g2s_batch* b : subs) if (!b) fell_back = fell_back || rc == G2S_OK;  // (aborted before every group ran)
   g2s_timing total;
@@ -4463,7 +4525,7 @@ static int team_resident(g2s_session* const* sessions, int nsessions, const g2s_
   for (g2s_batch* b : subs) g2s_batch_free(b);
   if (rc != G2S_OK) return rc;
   if (fell_back) return 1;
-  total.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+  total.ms_total = ms_since(t_begin);
   if (timing_out) *timing_out = total;
   lead->last_timing = total;
   return G2S_OK;
@@ -4515,29 +4577,14 @@ extern "C" int g2s_team_fill(g2s_session* const* sessions, int nsessions, const 
       const int rc = g2s_team_fill(sessions, nsessions, gaps + lo, cnt, std::min(group_size, per), results + lo, arena + abase, abytes, &tm);
       if (rc != G2S_OK) return rc;
       for (size_t i = lo; i < hi; i++) results[i].fill_off += (uint64_t)abase;  // (offsets into the whole arena)
-      total.ms_right_bfs += tm.ms_right_bfs; total.ms_left_dp += tm.ms_left_dp; total.ms_extract += tm.ms_extract;
-      total.ms_fill_lds += tm.ms_fill_lds; total.ms_extract_lds += tm.ms_extract_lds; total.ms_d2h += tm.ms_d2h;
-      total.ms_host_post += tm.ms_host_post; total.ms_prepare += tm.ms_prepare; total.ms_d3 += tm.ms_d3;
-      total.xA += tm.xA; total.sA += tm.sA; total.xB += tm.xB; total.sB += tm.sB; total.xD += tm.xD; total.sD += tm.sD;
-      total.flank_bytes += tm.flank_bytes; total.fill_bytes += tm.fill_bytes; total.launches_left_dp += tm.launches_left_dp;
-      total.retried_gaps += tm.retried_gaps; total.x_fill_lds += tm.x_fill_lds; total.s_fill_lds += tm.s_fill_lds;
-      total.lds_tier_gaps += tm.lds_tier_gaps; total.lds_launches += tm.lds_launches; total.log_pool_gaps += tm.log_pool_gaps;
-      total.rs_pool_gaps += tm.rs_pool_gaps; total.ms_fill_seg += tm.ms_fill_seg; total.seg_tier_gaps += tm.seg_tier_gaps;
-      total.seg_launches += tm.seg_launches; total.seg_timed_launches += tm.seg_timed_launches; total.seg_segments += tm.seg_segments; total.ms_fill_segx += tm.ms_fill_segx;
-      total.segx_tier_gaps += tm.segx_tier_gaps; total.segx_launches += tm.segx_launches; total.watchdog_gaps += tm.watchdog_gaps;
-      total.seg2_launches += tm.seg2_launches; total.resident_launches += tm.resident_launches;
-      total.resident_fallbacks += tm.resident_fallbacks; total.draw_dependent_gaps += tm.draw_dependent_gaps;
-      total.d3_table_entries += tm.d3_table_entries; total.host_finished_gaps += tm.host_finished_gaps;
-      total.team_groups += tm.team_groups; total.team_sessions = tm.team_sessions;
-      for (int q = 0; q < 16; q++) {
-        total.team_groups_by_session[q] += tm.team_groups_by_session[q];
-        total.team_ms_fill[q] += tm.team_ms_fill[q]; total.team_ms_d3[q] += tm.team_ms_d3[q]; total.team_ms_wall[q] += tm.team_ms_wall[q];
-      }
+      timing_add(total, tm);  // (traced_in_fill_gaps and guessed_* with the rest: zero in a team's timing)
+      total.team_sessions = tm.team_sessions;
+      for (int q = 0; q < 16; q++) { total.team_ms_fill[q] += tm.team_ms_fill[q]; total.team_ms_d3[q] += tm.team_ms_d3[q]; total.team_ms_wall[q] += tm.team_ms_wall[q]; }
       total.team_d3_sharded = (lo == 0 ? 1u : total.team_d3_sharded) & tm.team_d3_sharded;  // (every slice)
       lo = hi;
       abase += abytes;
     }
-    total.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+    total.ms_total = ms_since(t_begin);
     if (timing_out) *timing_out = total;
     sessions[0]->last_timing = total;
     return G2S_OK;
@@ -4565,11 +4612,7 @@ extern "C" int g2s_team_fill(g2s_session* const* sessions, int nsessions, const 
     }
   }
   lead->bg.submit([lead, gaps, n]() { lead->rcache.ensure(rand_need_of(gaps, n, lead->graph->g->k)); });
-  std::vector<size_t> group_arena(ngroups + 1, 0);  // where each group's fill buffers start
-  for (size_t gi = 0; gi < ngroups; gi++) {
-    const size_t off = gi * group_size, cnt = std::min(group_size, n - off);
-    group_arena[gi + 1] = group_arena[gi] + g2s_team_arena_bytes(lead, gaps + off, cnt);
-  }
+  const std::vector<size_t> group_arena = group_arena_offsets(lead, gaps, n, group_size);
   std::vector<int> group_owner(ngroups, -1);
   auto worker = [&](int t) {
     g2s_session* s = sessions[t];
@@ -4577,66 +4620,32 @@ extern "C" int g2s_team_fill(g2s_session* const* sessions, int nsessions, const 
     size_t gi = 0, off = 0, cnt = 0;
     while (queue.pull(&gi, &off, &cnt)) {
       group_owner[gi] = t;
-      g2s_batch* b = nullptr;
-      auto t0 = std::chrono::steady_clock::now();
-      int rc = g2s_batch_prepare(s, gaps + off, cnt, &b);
-      auto t1 = std::chrono::steady_clock::now();
-      if (rc == G2S_OK) {
-        subs[gi] = b;
-        b->timing.ms_prepare = std::chrono::duration<double, std::milli>(t1 - t0).count();
-        b->arena = arena + group_arena[gi];
-        b->arena_base = group_arena[gi];
-        rc = batch_stage1(b, true, results + off);
-      }
+      const auto t0 = std::chrono::steady_clock::now();
+      int rc = prepare_group(s, gaps + off, cnt, arena, group_arena[gi], &subs[gi]);
+      const auto t1 = std::chrono::steady_clock::now();
+      if (rc == G2S_OK) rc = batch_stage1(subs[gi], true, results + off);
       if (GENV("G2S_DEBUG"))
         fprintf(stderr, "[g2s] team session %d group %zu (%zu gaps): prepare %.3f ms, stage 1 %.3f ms\n", t, gi, cnt,
-                std::chrono::duration<double, std::milli>(t1 - t0).count(),
-                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count());
+                ms_between(t0, t1), ms_since(t1));
       if (rc != G2S_OK) { rcs[(size_t)t] = rc; errs[(size_t)t] = tl_error; queue.abort(); break; }
     }
   };
-  {
-    // one host thread per session, from the lead's team pool (persistent: creating and joining a thread per
-    // session and list cost a 10 000-gap list on eight sessions 0.2 ms)
-    if (nsessions > 1 && (!lead->team_pool || lead->team_pool->size() < nsessions - 1)) {
-      delete lead->team_pool;
-      lead->team_pool = new WorkerPool(nsessions - 1);
-    }
-    const std::function<void(size_t)> job = [&](size_t t) { worker((int)t); };
-    if (nsessions > 1) lead->team_pool->run((size_t)nsessions, job);
-    else worker(0);
-  }
+  team_run(lead, nsessions, worker);
   lead->bg.wait();
-  int rc = G2S_OK;
-  for (int t = 0; t < nsessions; t++) if (rcs[(size_t)t] != G2S_OK) { rc = rcs[(size_t)t]; tl_error = errs[(size_t)t]; }
+  int rc = team_last_error(rcs, errs);
   g2s_timing total;
   memset(&total, 0, sizeof total);
   if (rc == G2S_OK) {
-    {
-      for (g2s_batch* b : subs) {
-        const g2s_timing& t = b->timing;
-        total.ms_right_bfs += t.ms_right_bfs; total.ms_left_dp += t.ms_left_dp; total.ms_extract += t.ms_extract;
-        total.ms_fill_lds += t.ms_fill_lds; total.ms_extract_lds += t.ms_extract_lds; total.ms_d2h += t.ms_d2h;
-        total.ms_host_post += t.ms_host_post;
-        total.xA += t.xA; total.sA += t.sA; total.xB += t.xB; total.sB += t.sB; total.xD += t.xD; total.sD += t.sD;
-        total.flank_bytes += t.flank_bytes; total.launches_left_dp += t.launches_left_dp;
-        total.retried_gaps += t.retried_gaps; total.x_fill_lds += t.x_fill_lds; total.s_fill_lds += t.s_fill_lds;
-        total.lds_tier_gaps += t.lds_tier_gaps; total.lds_launches += t.lds_launches;
-        total.log_pool_gaps += t.log_pool_gaps; total.rs_pool_gaps += t.rs_pool_gaps;
-        total.ms_prepare += t.ms_prepare;
-        total.ms_fill_seg += t.ms_fill_seg; total.seg_tier_gaps += t.seg_tier_gaps; total.seg_launches += t.seg_launches; total.seg_timed_launches += t.seg_timed_launches;
-        total.seg_segments += t.seg_segments;
-        total.ms_fill_segx += t.ms_fill_segx; total.segx_tier_gaps += t.segx_tier_gaps; total.segx_launches += t.segx_launches;
-        total.watchdog_gaps += t.watchdog_gaps; total.seg2_launches += t.seg2_launches;
-      }
-      rc = batches_stage2(subs, lead, results, arena, &total, false);
-      total.team_groups = (uint32_t)ngroups;
-      total.team_sessions = (uint32_t)nsessions;
-      for (size_t q = 0; q < ngroups; q++) if (group_owner[q] >= 0 && group_owner[q] < 16) total.team_groups_by_session[group_owner[q]]++;
-    }
+    // (stage 1's figures; everything else is zero in a batch that has been through batch_stage1 and nothing more —
+    // fill_bytes and the rest of phase D are stage 2's, which adds them to `total` itself below)
+    for (g2s_batch* b : subs) timing_add(total, b->timing);
+    rc = batches_stage2(subs, lead, results, arena, &total, false);
+    total.team_groups = (uint32_t)ngroups;
+    total.team_sessions = (uint32_t)nsessions;
+    for (size_t q = 0; q < ngroups; q++) if (group_owner[q] >= 0 && group_owner[q] < 16) total.team_groups_by_session[group_owner[q]]++;
   }
   for (g2s_batch* b : subs) g2s_batch_free(b);
-  total.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+  total.ms_total = ms_since(t_begin);
   if (timing_out) *timing_out = total;
   return rc;
 }
@@ -4678,7 +4687,7 @@ extern "C" int g2s_fill_batch(g2s_session* s, const g2s_gap* gaps, size_t n, g2s
   g2s_batch* b = nullptr;
   int rc = g2s_batch_prepare(s, gaps, n, &b);
   if (rc != G2S_OK) return rc;
-  const double ms_prep = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+  const double ms_prep = ms_since(t_begin);
   s->laps_valid = false;
   rc = g2s_batch_run(b, results, fill_arena, arena_cap);
   const auto t_free = std::chrono::steady_clock::now();
@@ -4691,9 +4700,9 @@ extern "C" int g2s_fill_batch(g2s_session* s, const g2s_gap* gaps, size_t n, g2s
   }
   if (GENV("G2S_DEBUG"))
     fprintf(stderr, "[g2s] fill_batch: prepare %.3f ms, free %.3f ms\n", ms_prep,
-            std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_free).count());
+            ms_since(t_free));
   s->last_timing.ms_prepare = ms_prep;
-  s->last_timing.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+  s->last_timing.ms_total = ms_since(t_begin);
   return rc;
 }
 
@@ -4734,18 +4743,7 @@ extern "C" int g2s_fill_sets(g2s_session* s, const g2s_gap* gaps, const uint32_t
     rc = g2s_batch_run(b, results + off, fill_arena ? fill_arena + std::min(aoff, arena_cap) : nullptr, aoff <= arena_cap ? arena_cap - aoff : 0);
     if (rc == G2S_OK) {
       for (size_t q = 0; q < cnt; q++) results[off + q].fill_off += (uint64_t)aoff;  // (offsets within the group's share)
-      const g2s_timing& t = b->timing;
-      total.ms_right_bfs += t.ms_right_bfs; total.ms_left_dp += t.ms_left_dp; total.ms_extract += t.ms_extract;
-      total.ms_host_post += t.ms_host_post; total.ms_fill_lds += t.ms_fill_lds; total.ms_fill_seg += t.ms_fill_seg;
-      total.ms_fill_segx += t.ms_fill_segx; total.flank_bytes += t.flank_bytes; total.fill_bytes += t.fill_bytes;
-      total.lds_tier_gaps += t.lds_tier_gaps; total.seg_tier_gaps += t.seg_tier_gaps; total.segx_tier_gaps += t.segx_tier_gaps;
-      total.seg_launches += t.seg_launches; total.segx_launches += t.segx_launches; total.lds_launches += t.lds_launches;
-      total.resident_launches += t.resident_launches; total.resident_fallbacks += t.resident_fallbacks; total.ms_d3 += t.ms_d3;
-      total.draw_dependent_gaps += t.draw_dependent_gaps; total.host_finished_gaps += t.host_finished_gaps;
-      total.traced_in_fill_gaps += t.traced_in_fill_gaps; total.guessed_in_fill_gaps += t.guessed_in_fill_gaps;
-      total.guessed_groups += t.guessed_groups; total.guessed_groups_resent += t.guessed_groups_resent;
-      total.d3_table_entries += t.d3_table_entries; total.seg_timed_launches += t.seg_timed_launches;
-      total.xA += t.xA; total.sA += t.sA; total.xB += t.xB; total.sB += t.sB; total.xD += t.xD; total.sD += t.sD;
+      timing_add(total, b->timing);  // (everything g2s_batch_run counted; ms_prepare is zero: nobody measured it)
     }
     aoff += b->arena_bytes;
     g2s_batch_free(b);
@@ -4753,7 +4751,7 @@ extern "C" int g2s_fill_sets(g2s_session* s, const g2s_gap* gaps, const uint32_t
   s->set_gaps = nullptr;
   s->bg.wait();  // (nobody materialises values into the list's generator any more)
   s->rcache.swap(fresh);
-  total.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+  total.ms_total = ms_since(t_begin);
   s->last_timing = total;
   return rc;
 }
@@ -4792,7 +4790,7 @@ int inflight_settle(g2s_session* s) {
     if (on != s) on->rcache.swap(s->rcache);
     if (rc < 0) return rc;
     if (rc != G2S_OK) break;  // (its fill kernel ran for nothing: the host path when it is ended)
-    f.b->d3_queued = true; f.b->pre_units = rl.units; f.b->pre_two = rl.two_waves; f.b->pre_timed = rl.timed; f.b->pre_segw = rl.segw;
+    f.b->d3_queued = true; f.b->pre = rl;
     f.chained = chain_from != nullptr;
   }
   return G2S_OK;
@@ -4826,7 +4824,7 @@ extern "C" int g2s_fill_begin(g2s_session* s, const g2s_gap* gaps, size_t n, g2s
     const auto t0 = std::chrono::steady_clock::now();
     int rc = g2s_batch_prepare(on, gaps, n, &f.b);
     if (rc != G2S_OK) return rc;
-    f.ms_prepare = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    f.ms_prepare = ms_since(t0);
     if (arena_cap < f.b->arena_bytes) { g2s_batch_free(f.b); return fail(G2S_ERR_ARG, "g2s_fill_begin: fill arena too small"); }
     f.on = on;
     f.b->arena = fill_arena;
@@ -4836,9 +4834,7 @@ extern "C" int g2s_fill_begin(g2s_session* s, const g2s_gap* gaps, size_t n, g2s
     ResidentLaunch rl;
     rc = resident_launch_fill(f.b, &rl, results, fill_arena);  // (1: not a list for resident mode — g2s_fill_end runs it on the host path)
     if (rc < 0) { g2s_batch_free(f.b); return rc; }
-    if (rc == G2S_OK) {
-      f.b->pre_launched = true; f.b->pre_units = rl.units; f.b->pre_two = rl.two_waves; f.b->pre_timed = rl.timed; f.b->pre_segw = rl.segw;
-    }
+    if (rc == G2S_OK) { f.b->pre_launched = true; f.b->pre = rl; }
   }  // (a list for the team pipeline, or an empty one: g2s_fill_end calls g2s_fill_batch)
   s->inflight[s->n_inflight++] = f;
   s->begun++;
@@ -4887,19 +4883,15 @@ extern "C" int g2s_fill_end(g2s_session* s) {
 }
 extern "C" int g2s_fill_in_flight(const g2s_session* s) { return s ? s->n_inflight : 0; }
 
-// ---- one list over several processes, a GPU and a share each (include/g2s.h): the three steps of team_resident_sharded
-// with the exchanges between them left to the caller (gap2seq_amd/shard.py: gloo all-gathers of host scalars)
+// ---- one list over several processes, a GPU and a share each (include/g2s.h): the three steps of a sharded list
+// (shard_fill, shard_tables, shard_trace: the ones team_resident_sharded's threads take) with the exchanges between
+// them left to the caller (gap2seq_amd/shard.py: gloo all-gathers of host scalars)
 namespace {
 void share_drop(g2s_session* s) {
-  if (s->d3_pending) {
-    (void)hipSetDevice(s->device);
-    (void)hipStreamSynchronize(s->stream);
-    (void)hipStreamSynchronize(s->stream2);
-    delete (D3Pending*)s->d3_pending;
-    s->d3_pending = nullptr;
-    s->d_d3.clean = 0;
-  }
-  if (s->share_batch) { (void)resident_reset_fill(s, s->share_batch->jobs.size()); g2s_batch_free(s->share_batch); s->share_batch = nullptr; }
+  const size_t n = s->share_batch ? s->share_batch->jobs.size() : 0;
+  if (s->d3_pending) resident_abandon(s, n);
+  else if (n) (void)resident_reset_fill(s, n);  // (its fill launch, if it got that far, and nothing behind it)
+  if (s->share_batch) { g2s_batch_free(s->share_batch); s->share_batch = nullptr; }
   s->share_step = 0;
   s->in_team_list = false; s->team_sharded = false; s->team_sessions = 1;
 }
@@ -4919,38 +4911,19 @@ extern "C" int g2s_share_begin(g2s_session* s, const g2s_gap* gaps, size_t n, g2
   s->in_team_list = true; s->team_sharded = true; s->team_sessions = 1;
   if (!resident_applicable(s, n) || s->d3_pending) { share_drop(s); return fail(G2S_ERR_STATE, "g2s_share_begin: not a list for resident mode on this session"); }
   memcpy(s->share_win, s->rcache.window(G2S_RAND_WINDOW), sizeof s->share_win);  // the generator where the LIST starts (every rank's is there)
-  g2s_batch* b = nullptr;
-  const auto t0 = std::chrono::steady_clock::now();
-  int rc = g2s_batch_prepare(s, gaps, n, &b);
+  // (the share is a list of its own to the kernels: its arena is the caller's buffer, from offset 0)
+  int rc = prepare_group(s, gaps, n, fill_arena, 0, &s->share_batch);
   if (rc != G2S_OK) { share_drop(s); return rc; }
-  s->share_batch = b;
-  b->timing.ms_prepare = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  g2s_batch* b = s->share_batch;
   if (arena_cap < b->arena_bytes) { share_drop(s); return fail(G2S_ERR_ARG, "g2s_share_begin: fill arena too small"); }
-  b->arena = fill_arena;
-  b->arena_base = 0;
   ResidentLaunch rl;
-  rc = resident_launch_fill(b, &rl);
-  if (rc == 1) { share_drop(s); return fail(G2S_ERR_STATE, "g2s_share_begin: not a list for resident mode"); }
-  if (rc != G2S_OK) { share_drop(s); return rc; }
+  rc = shard_fill(b, results, fill_arena, b->arena_bytes, &rl, totals, "g2s_share_begin: the share's first kernels");
+  if (rc != G2S_OK) share_drop(s);
+  if (rc == SHARD_NOT_RESIDENT) return fail(G2S_ERR_STATE, "g2s_share_begin: not a list for resident mode");
+  if (rc == SHARD_NOT_D3) return fail(G2S_ERR_STATE, "g2s_share_begin: not a list for phase D3 on the device");
+  if (rc == SHARD_BEYOND_DEVICE) return fail(G2S_ERR_STATE, "g2s_share_begin: a gap beyond every tier of the device, or tables beyond the budget");
+  if (rc != G2S_OK) return rc;
   s->share_timed = rl.timed; s->share_two = rl.two_waves;
-  ResidentList L;
-  L.groups.push_back(b);
-  L.n = n; L.group_size = std::max<size_t>(n, 1);
-  L.group_arena.push_back(0);
-  L.arena_bytes = b->arena_bytes;
-  L.outs_dev = (const GapOut*)s->d_outs.p;
-  L.sub_dev = (const SubRec*)s->d_sub.p;
-  L.sub_region = 0;
-  L.pin = &s->h_d3;
-  L.rnd_cap = b->rnd_cap; L.dmax = b->dmax; L.has_skip = b->has_skip;
-  L.gaps_dev = (const GapDev*)s->d_gaps.p;
-  rc = resident_d3_launch(s, L, rl.timed, false, results, fill_arena, true, true);
-  if (rc == 1) { share_drop(s); return fail(G2S_ERR_STATE, "g2s_share_begin: not a list for phase D3 on the device"); }
-  if (rc == G2S_OK && hipStreamSynchronize(s->stream) != hipSuccess) rc = fail(G2S_ERR_HIP, "g2s_share_begin: the share's first kernels");
-  if (rc != G2S_OK) { share_drop(s); return rc; }
-  const D3Summary* hs = ((D3Pending*)s->d3_pending)->hsum;
-  if (hs->status != 0) { share_drop(s); return fail(G2S_ERR_STATE, "g2s_share_begin: a gap beyond every tier of the device, or tables beyond the budget"); }
-  totals[0] = hs->draws_min; totals[1] = hs->draws_spread;
   s->share_step = 1;
   return G2S_OK;
 }
@@ -4959,11 +4932,10 @@ extern "C" int g2s_share_tables(g2s_session* s, uint64_t base0, uint64_t R0, con
   if (!s || !fn) return fail(G2S_ERR_ARG, "g2s_share_tables: bad argument");
   if (s->share_step != 1) return fail(G2S_ERR_STATE, "g2s_share_tables: no share begun on this session");
   if (base0 + R0 >= 0xF0000000ull) { share_drop(s); return fail(G2S_ERR_STATE, "g2s_share_tables: the list draws more than phase D3 on the device counts"); }
-  int rc = resident_d3_sharded_tables(s, (uint32_t)base0, (uint32_t)R0, s->share_win);
-  if (rc == G2S_OK && hipStreamSynchronize(s->stream) != hipSuccess) rc = fail(G2S_ERR_HIP, "g2s_share_tables: the share's tables");
-  if (rc != G2S_OK) { share_drop(s); return rc; }
-  if (((D3Pending*)s->d3_pending)->hsum->status != 0) { share_drop(s); return fail(G2S_ERR_STATE, "g2s_share_tables: tables beyond the budget"); }
-  *fn = ((D3Pending*)s->d3_pending)->group_fn;
+  const int rc = shard_tables(s, (uint32_t)base0, (uint32_t)R0, s->share_win, fn, "g2s_share_tables: the share's tables");
+  if (rc != G2S_OK) share_drop(s);
+  if (rc == SHARD_BEYOND_DEVICE) return fail(G2S_ERR_STATE, "g2s_share_tables: tables beyond the budget");
+  if (rc != G2S_OK) return rc;
   s->share_step = 2;
   return G2S_OK;
 }
@@ -4972,12 +4944,9 @@ extern "C" int g2s_share_trace(g2s_session* s, uint32_t d_in) {
   if (!s) return fail(G2S_ERR_ARG, "g2s_share_trace: bad argument");
   if (s->share_step != 2) return fail(G2S_ERR_STATE, "g2s_share_trace: no tables on this session (g2s_share_tables first)");
   g2s_batch* b = s->share_batch;
-  const size_t n = b->jobs.size();
-  int rc = resident_d3_sharded_trace(s, d_in);
   bool fb = false;
   double ms_d3 = 0;
-  if (rc == G2S_OK) rc = resident_d3_wait(s, &b->timing, &ms_d3, &fb);
-  if (rc == G2S_OK) rc = resident_reset_fill(s, n);
+  const int rc = shard_trace(b, d_in, &ms_d3, &fb);
   if (rc != G2S_OK) { share_drop(s); return rc; }
   if (fb) { share_drop(s); return fail(G2S_ERR_STATE, "g2s_share_trace: the share was not finished on the device"); }
   float ms_fill = 0;

@@ -616,6 +616,10 @@ def test_long_lists_go_slice_by_slice(product, monkeypatch):
         for s in team:
             s.destroy()
         assert [_key(r) for r in got2] == want and tm2.resident_launches == 2 and tm2.team_groups == 4
+        # the slices' sum of the team's sums: the per-gap figures of the one session's two slices (test_gpu_list_timing.py)
+        from test_gpu_list_timing import checked_fields
+        print("team, sliced: %r\none session, sliced: %r" % (checked_fields(tm2), checked_fields(tm)))
+        assert checked_fields(tm2) == checked_fields(tm)
         assert sum(1 for r in want if r[3] & product.G2S_GAP_SKIPPED) >= 1  # (a right fuz beyond 0 is rare on this genome)
     finally:
         pg.free()
