@@ -213,7 +213,8 @@ struct BamFile::Stream {
                                      why.c_str(), next_blk);
   }
   // (`down` false: the window stays in device memory, for rows_on_device)
-  bool issue(int slot, size_t b0, std::string* why, bool down = true) {
+  // (`d_dst`: its place in the resident stream of one-pass mode)
+  bool issue(int slot, size_t b0, std::string* why, bool down = true, uint8_t* d_dst = nullptr) {
     size_t bytes = 0, in = 0, file_bytes = 0;
     const size_t e = window_end(b0, &bytes);
     for (size_t b = b0; b < e; b++) {
@@ -235,7 +236,7 @@ struct BamFile::Stream {
       }
       out += isize;
     }
-    if (!dev->launch(slot, e - b0, in, bytes, why, down)) return false;
+    if (!dev->launch(slot, e - b0, in, bytes, why, down, d_dst)) return false;
     fly = slot;
     fly_beg = b0;
     fly_end = e;
@@ -432,7 +433,12 @@ bool BamFile::for_each(const std::function<bool(const BamRec&)>& fn, std::string
 // Pass A without the walk: every window is inflated into its slot's device buffer and left there, and the row kernels
 // (bam_rows.hip) follow the inflate kernel on the same stream; the host stages window n + 1 while window n is on the
 // device, and looks at a window's member status two windows later, when its slot is needed again.
-BamRowsDevice* BamFile::rows_on_device(size_t walk_window, int* anomaly, std::string* why) const {
+// One-pass mode (`resident`): the windows are inflated into one allocation, each at its inflated offset, and stay there
+// for pass B (bam_text.hip).  A window's base is then no word boundary in general, so the row kernels are given the
+// word boundary in front of it and start that many bytes in; a record cut by a window's end is whole in memory, and in
+// place of the carry the chain's head moves by the distance between the two bases (BamRowsDevice::advance).
+BamRowsDevice* BamFile::rows_on_device(size_t walk_window, int* anomaly, std::string* why, bool resident, uint64_t resident_cap,
+                                       int* resident_refused) const {
   const auto t0 = std::chrono::steady_clock::now();
   *anomaly = kRowsHip;
   if (inflate_device_ < 0 || dev_refused_) { *why = "the reader does not inflate on a device"; return nullptr; }
@@ -456,9 +462,16 @@ BamRowsDevice* BamFile::rows_on_device(size_t walk_window, int* anomaly, std::st
     *why = "a header beyond the first window, or a file outside the row kernels' index widths";
     return nullptr;
   }
+  ResidentAsk ask;
+  ask.bytes = resident ? total : 0;
+  ask.cap = resident_cap;
+  int refused = kResidentKept;
   std::unique_ptr<BamRowsDevice> R(BamRowsDevice::create(inflate_device_, dev->stream(), max_out, walk_window, dev->front(),
-                                                         cap_rows, (int32_t)ref_names_.size(), first_rec_, why));
+                                                         cap_rows, (int32_t)ref_names_.size(), first_rec_, why, &ask, &refused));
+  if (resident_refused) *resident_refused = refused;
   if (!R) return nullptr;
+  uint8_t* const keep = R->stream_buffer();  // (null: today's two slots)
+  uint64_t off = 0;                          // inflated offset of the window at hand
   size_t used_beg[2] = {0, 0}, used_end[2] = {0, 0};
   // the members of the window that went through `slot` last: 0, or the anomaly
   auto settle = [&](int slot) -> int {
@@ -481,13 +494,22 @@ BamRowsDevice* BamFile::rows_on_device(size_t walk_window, int* anomaly, std::st
     const int slot = (int)(w & 1);
     if ((a = settle(slot)) != kRowsOk) { ok = false; break; }
     a = kRowsHip;
-    if (!s.issue(slot, b, why, false)) { ok = false; break; }
+    if (!s.issue(slot, b, why, false, keep ? keep + off : nullptr)) { ok = false; break; }
     used_beg[slot] = s.fly_beg;
     used_end[slot] = s.fly_end;
-    ok = R->window(dev->device_window(slot), w == 0 ? (size_t)first_rec_ : 0, s.fly_bytes, why);
     b = s.fly_end;
-    if (ok && b < nb) ok = R->carry(dev->device_window(slot), s.fly_bytes, dev->device_window(1 - slot), why);
-    last_bytes = s.fly_bytes;
+    if (keep) {
+      const uint64_t base = off & ~(uint64_t)3, next = (off + s.fly_bytes) & ~(uint64_t)3;
+      const size_t lead = (size_t)(off - base);
+      ok = R->window(keep + base, w == 0 ? (size_t)first_rec_ : lead, lead + s.fly_bytes, why, base);
+      if (ok && b < nb) ok = R->advance(lead + s.fly_bytes, (size_t)(next - base), why);
+      last_bytes = lead + s.fly_bytes;
+      off += s.fly_bytes;
+    } else {
+      ok = R->window(dev->device_window(slot), w == 0 ? (size_t)first_rec_ : 0, s.fly_bytes, why);
+      if (ok && b < nb) ok = R->carry(dev->device_window(slot), s.fly_bytes, dev->device_window(1 - slot), why);
+      last_bytes = s.fly_bytes;
+    }
     is.members += s.fly_end - s.fly_beg;
     is.bytes_in += s.fly_in;
     is.bytes_out += s.fly_bytes;

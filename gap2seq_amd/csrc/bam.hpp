@@ -74,7 +74,12 @@ class BamFile {
   // device from the windows while they lie in device memory, `walk_window` bytes at a time (0: a whole window of
   // inflated members).  The caller owns the result.  Null: *anomaly (bam_rows.h: RowsAnomaly) and *why say what
   // stood in the way; nothing is left in flight, no inflate statistics were counted, and for_each is the way to go on.
-  BamRowsDevice* rows_on_device(size_t walk_window, int* anomaly, std::string* why) const;
+  // `resident` (one-pass mode): the inflated stream stays in one device allocation of the result, with every record's
+  // offset in it (BamRowsDevice::stream_buffer, DeviceRows::rec_off), when it fits the cap (bam_rows.h: ResidentAsk;
+  // resident_cap 0: half the free device memory alone); *resident_refused (bam_rows.h: ResidentRefused) says when it did
+  // not, and the rows are then made the two-slot way.
+  BamRowsDevice* rows_on_device(size_t walk_window, int* anomaly, std::string* why, bool resident = false,
+                                uint64_t resident_cap = 0, int* resident_refused = nullptr) const;
   uint64_t rows_windows() const { return rows_windows_; }  // walk windows of the last rows_on_device
   // test paths (g2s_test_bgzf_inflate): the host path with inflate_core.h in zlib's place; any BGZF file, no BAM header
   void set_inflate_core(bool on) { use_core_ = on; }

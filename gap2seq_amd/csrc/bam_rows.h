@@ -27,25 +27,46 @@ struct DeviceRows {
   int64_t* end = nullptr;
   uint32_t* flag = nullptr;
   uint64_t *h_own = nullptr, *h_mate = nullptr;  // (the joins replace them by their bits, in place)
+  uint64_t* rec_off = nullptr;  // one-pass mode: every record's offset in the resident inflated stream (else null)
   uint64_t n = 0;
   int64_t max_span = 1;
   int32_t read_length = 0;
 };
+
+// One-pass mode (bam_text.h): what pass A is asked to keep, and why it did not
+struct ResidentAsk {
+  uint64_t bytes = 0;  // the inflated stream, whole; 0: nothing is kept
+  uint64_t cap = 0;    // G2S_FILTER_RESIDENT_CAP; 0: half the free device memory alone
+};
+enum ResidentRefused : int { kResidentKept = 0, kResidentOverCap = 1, kResidentNoMemory = 2 };
 
 class BamRowsDevice {
  public:
   // Kernels on `stream` (a hipStream_t: the reader's own, behind its inflate kernel) for windows of at most max_window
   // bytes, walked `walk_window` bytes at a time, each with `front` bytes of room in front; at most cap_rows rows;
   // references [0, n_ref); the first record at offset first_head of the first window.  Null: *why.
+  // `ask` (may be null): one device allocation for the whole inflated stream and an offset per row beside the rows, taken
+  // only when stream and rows fit within half the free device memory (and ask->cap).  When they do not, or the
+  // allocation fails, the object is made without them and *resident_refused says which.
   static BamRowsDevice* create(int device, void* stream, size_t max_window, size_t walk_window, size_t front,
-                               uint64_t cap_rows, int32_t n_ref, uint64_t first_head, std::string* why);
+                               uint64_t cap_rows, int32_t n_ref, uint64_t first_head, std::string* why,
+                               const ResidentAsk* ask = nullptr, int* resident_refused = nullptr);
   ~BamRowsDevice();
   BamRowsDevice(const BamRowsDevice&) = delete;
   BamRowsDevice& operator=(const BamRowsDevice&) = delete;
   // the walk windows of one inflated window of `bytes` bytes at d_win (a device pointer), from offset `start`: enqueued
-  bool window(const uint8_t* d_win, size_t start, size_t bytes, std::string* why);
+  // (win_off: d_win's offset in the resident stream, for DeviceRows::rec_off)
+  bool window(const uint8_t* d_win, size_t start, size_t bytes, std::string* why, uint64_t win_off = 0);
   // the cut record's head moved in front of the next window's buffer: enqueued
   bool carry(const uint8_t* d_win, size_t bytes, uint8_t* d_next_win, std::string* why);
+  // the same step between two windows of the resident stream, whose (word aligned) bases lie `step` bytes apart, the
+  // first ending win_end bytes behind its base: nothing to copy, the head moves: enqueued
+  bool advance(size_t win_end, size_t step, std::string* why);
+  // the resident stream (null without one-pass mode) and its size
+  uint8_t* stream_buffer() const { return stream_buf_; }
+  uint64_t stream_bytes() const { return stream_bytes_; }
+  int device() const { return device_; }
+  void* stream() const { return stream_; }
   // the end of the stream behind a last window of last_bytes bytes: waits, and reads the counts down.  False: a HIP
   // call failed (*why).  *anomaly: kRowsOk, or what the kernels met.
   bool finish(size_t last_bytes, int* anomaly, std::string* why);
@@ -68,6 +89,8 @@ class BamRowsDevice {
   void *state_ = nullptr, *cand_ = nullptr, *link_ = nullptr, *j0_ = nullptr, *j1_ = nullptr, *mark_ = nullptr, *emit_ = nullptr,
        *blk_ = nullptr;
   uint64_t windows_ = 0, candidates_ = 0;
+  uint8_t* stream_buf_ = nullptr;
+  uint64_t stream_bytes_ = 0;
 };
 
 }  // namespace g2s

@@ -252,7 +252,8 @@ __global__ void __launch_bounds__(kBlock) k_round(const State* __restrict__ st, 
 
 __device__ __forceinline__ void make_row(const uint8_t* __restrict__ rec, uint64_t row, State* st, int32_t* __restrict__ ref_id,
                                          int32_t* __restrict__ pos_out, int64_t* __restrict__ end_out, uint32_t* __restrict__ flag_out,
-                                         uint64_t* __restrict__ h_own, uint64_t* __restrict__ h_mate) {
+                                         uint64_t* __restrict__ h_own, uint64_t* __restrict__ h_mate,
+                                         uint64_t* __restrict__ rec_off, uint64_t off) {
   const uint8_t* p = rec + 4;
   const int32_t ref = (int32_t)g_ld32(p), pos = (int32_t)g_ld32(p + 4), l_seq = (int32_t)g_ld32(p + 16);
   const uint32_t l_name = p[8], w = g_ld32(p + 12), n_cigar = w & 0xFFFFu, flag = w >> 16;
@@ -275,6 +276,7 @@ __device__ __forceinline__ void make_row(const uint8_t* __restrict__ rec, uint64
   flag_out[row] = flag;
   h_own[row] = g2s::name_hash(name, n, own);
   h_mate[row] = g2s::name_hash(name, n, 3u - own);
+  if (rec_off) rec_off[row] = off;  // (one-pass mode: where pass B finds the record in the resident stream)
   if (l_seq > st->read_length) atomicMax(&st->read_length, l_seq);
   if (ref >= 0) {
     const uint64_t span = (uint64_t)(end - (int64_t)pos);
@@ -289,7 +291,8 @@ template <bool WRITE>
 __global__ void __launch_bounds__(kBlock) k_rec(const uint8_t* __restrict__ win, State* st, const int32_t* __restrict__ cand,
                                                 const uint32_t* __restrict__ link, const uint8_t* __restrict__ mark,
                                                 const uint8_t* __restrict__ emit, uint32_t* __restrict__ blk, int32_t* ref_id,
-                                                int32_t* pos, int64_t* end, uint32_t* flag, uint64_t* h_own, uint64_t* h_mate) {
+                                                int32_t* pos, int64_t* end, uint32_t* flag, uint64_t* h_own, uint64_t* h_mate,
+                                                uint64_t* rec_off, uint64_t win_off) {
   __shared__ uint32_t wave_cnt[kWaves];
   if (st->anomaly) return;
   const uint32_t n = st->n_cand, tid = threadIdx.x, i = blockIdx.x * kBlock + tid, wave = tid / kWave, lane = tid % kWave;
@@ -310,7 +313,8 @@ __global__ void __launch_bounds__(kBlock) k_rec(const uint8_t* __restrict__ win,
   if (!take) return;
   uint32_t rank = blk[blockIdx.x] + (uint32_t)__popcll(mask & (((uint64_t)1 << lane) - 1));
   for (uint32_t w = 0; w < wave; w++) rank += wave_cnt[w];
-  make_row(win + cand[i], st->row_base + rank, st, ref_id, pos, end, flag, h_own, h_mate);
+  make_row(win + cand[i], st->row_base + rank, st, ref_id, pos, end, flag, h_own, h_mate, rec_off,
+           (uint64_t)((int64_t)win_off + (int64_t)cand[i]));
 }
 
 // the bytes from the chain's exit to the window's end, in front of the next window's buffer
@@ -326,6 +330,18 @@ __global__ void __launch_bounds__(kBlock) k_carry(const uint8_t* __restrict__ wi
   const uint8_t* src = win + st->head;
   uint8_t* dst = next_win - carry;
   for (int64_t i = gid; i < carry; i += (int64_t)gridDim.x * kBlock) dst[i] = src[i];
+}
+// the same step in a resident stream, where the window that follows lies behind this one and the cut record is whole
+// in memory already: the room in front is checked as k_carry checks it (so that a file is handed over to the host walk
+// in either mode or in neither), nothing is copied, and the head moves by the distance between the windows' bases
+__global__ void k_advance(State* st, int64_t win_end, int64_t step, int64_t front) {
+  if (st->anomaly) return;
+  const int64_t carry = win_end - (int64_t)st->head;
+  if (carry < 0 || carry > front) {
+    st->anomaly = g2s::kRowsCarry;
+    return;
+  }
+  st->head = (int32_t)((int64_t)st->head - step);
 }
 __global__ void k_rebase(State* st, int64_t bytes) {
   if (!st->anomaly) st->head = (int32_t)((int64_t)st->head - bytes);
@@ -352,7 +368,8 @@ namespace g2s {
   } while (0)
 
 BamRowsDevice* BamRowsDevice::create(int device, void* stream, size_t max_window, size_t walk_window, size_t front,
-                                     uint64_t cap_rows, int32_t n_ref, uint64_t first_head, std::string* why) {
+                                     uint64_t cap_rows, int32_t n_ref, uint64_t first_head, std::string* why,
+                                     const ResidentAsk* ask, int* resident_refused) {
   const size_t walk = walk_window && walk_window < max_window ? walk_window : (max_window ? max_window : 1);
   if (max_window + front + 64 >= (size_t)INT32_MAX || first_head > max_window || cap_rows >= (uint64_t)UINT32_MAX - 1) {
     if (why) *why = "a file outside the row kernels' index widths";
@@ -371,6 +388,25 @@ BamRowsDevice* BamRowsDevice::create(int device, void* stream, size_t max_window
   auto make = [&]() -> bool {
     const size_t rows = (size_t)cap_rows + 1, cc = D->cap_cand_;
     G2S_BR_TRY(hipSetDevice(device));
+    // one-pass mode: the whole inflated stream and the records' offsets, when they fit under the cap with the rows
+    if (ask && ask->bytes) {
+      size_t free_b = 0, total_b = 0;
+      G2S_BR_TRY(hipMemGetInfo(&free_b, &total_b));
+      const uint64_t need = ask->bytes + 64 + rows * 52, cap = std::min<uint64_t>(free_b / 2, ask->cap ? ask->cap : UINT64_MAX);
+      if (need > cap) {
+        *resident_refused = kResidentOverCap;
+      } else if (hipMalloc((void**)&D->stream_buf_, (size_t)ask->bytes + 64) != hipSuccess ||
+                 hipMalloc((void**)&D->rows_.rec_off, rows * 8) != hipSuccess) {
+        (void)hipGetLastError();
+        if (D->stream_buf_) (void)hipFree(D->stream_buf_);
+        if (D->rows_.rec_off) (void)hipFree(D->rows_.rec_off);
+        D->stream_buf_ = nullptr;
+        D->rows_.rec_off = nullptr;
+        *resident_refused = kResidentNoMemory;
+      } else {
+        D->stream_bytes_ = ask->bytes;
+      }
+    }
     G2S_BR_TRY(hipMalloc(&D->state_, sizeof(State)));
     G2S_BR_TRY(hipMalloc(&D->cand_, cc * 4));
     G2S_BR_TRY(hipMalloc(&D->link_, cc * 4));
@@ -403,11 +439,11 @@ BamRowsDevice::~BamRowsDevice() {
   if (device_ >= 0) (void)hipSetDevice(device_);
   if (stream_) (void)hipStreamSynchronize((hipStream_t)stream_);
   for (void* p : {state_, cand_, link_, j0_, j1_, mark_, emit_, blk_, (void*)rows_.ref_id, (void*)rows_.pos, (void*)rows_.end,
-                  (void*)rows_.flag, (void*)rows_.h_own, (void*)rows_.h_mate})
+                  (void*)rows_.flag, (void*)rows_.h_own, (void*)rows_.h_mate, (void*)rows_.rec_off, (void*)stream_buf_})
     if (p) (void)hipFree(p);
 }
 
-bool BamRowsDevice::window(const uint8_t* d_win, size_t start, size_t bytes, std::string* why) {
+bool BamRowsDevice::window(const uint8_t* d_win, size_t start, size_t bytes, std::string* why, uint64_t win_off) {
   hipStream_t s = (hipStream_t)stream_;
   State* st = (State*)state_;
   int32_t* cand = (int32_t*)cand_;
@@ -434,11 +470,11 @@ bool BamRowsDevice::window(const uint8_t* d_win, size_t start, size_t bytes, std
     }
     hipLaunchKernelGGL((k_rec<false>), dim3(groups), dim3(kBlock), 0, s, d_win, st, (const int32_t*)cand, (const uint32_t*)link,
                        (const uint8_t*)mark, (const uint8_t*)emit, blk, rows_.ref_id, rows_.pos, rows_.end, rows_.flag, rows_.h_own,
-                       rows_.h_mate);
+                       rows_.h_mate, rows_.rec_off, win_off);
     hipLaunchKernelGGL((k_scan<1>), dim3(1), dim3(kScan), 0, s, blk, groups, st, cap, cap_rows_, cand);
     hipLaunchKernelGGL((k_rec<true>), dim3(groups), dim3(kBlock), 0, s, d_win, st, (const int32_t*)cand, (const uint32_t*)link,
                        (const uint8_t*)mark, (const uint8_t*)emit, blk, rows_.ref_id, rows_.pos, rows_.end, rows_.flag, rows_.h_own,
-                       rows_.h_mate);
+                       rows_.h_mate, rows_.rec_off, win_off);
     G2S_BR_TRY(hipGetLastError());
     windows_++;
   }
@@ -450,6 +486,14 @@ bool BamRowsDevice::carry(const uint8_t* d_win, size_t bytes, uint8_t* d_next_wi
   G2S_BR_TRY(hipSetDevice(device_));
   hipLaunchKernelGGL(k_carry, dim3(64), dim3(kBlock), 0, s, d_win, (int64_t)bytes, d_next_win, (int64_t)front_, (State*)state_);
   hipLaunchKernelGGL(k_rebase, dim3(1), dim3(1), 0, s, (State*)state_, (int64_t)bytes);
+  G2S_BR_TRY(hipGetLastError());
+  return true;
+}
+
+bool BamRowsDevice::advance(size_t win_end, size_t step, std::string* why) {
+  hipStream_t s = (hipStream_t)stream_;
+  G2S_BR_TRY(hipSetDevice(device_));
+  hipLaunchKernelGGL(k_advance, dim3(1), dim3(1), 0, s, (State*)state_, (int64_t)win_end, (int64_t)step, (int64_t)front_);
   G2S_BR_TRY(hipGetLastError());
   return true;
 }

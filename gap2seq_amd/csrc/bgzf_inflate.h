@@ -41,8 +41,10 @@ class BgzfDevice {
     return n_members <= cap_members_ && in_bytes <= cap_in_ && out_bytes <= cap_out_;
   }
   // copies up, the kernel, copies down (the status words alone when `down` is false: the window stays on the device):
-  // all asynchronous, on the object's own stream
-  bool launch(int slot, size_t n_members, size_t in_bytes, size_t out_bytes, std::string* why, bool down = true);
+  // all asynchronous, on the object's own stream.  `d_dst` (with `down` false): the kernel writes the window there, any
+  // device address with out_bytes bytes of room, in place of the slot's own buffer.
+  bool launch(int slot, size_t n_members, size_t in_bytes, size_t out_bytes, std::string* why, bool down = true,
+              uint8_t* d_dst = nullptr);
   bool wait(int slot, std::string* why);
 
  private:

@@ -202,11 +202,16 @@ BgzfDevice::~BgzfDevice() {
   if (stream_) (void)hipStreamDestroy((hipStream_t)stream_);
 }
 
-bool BgzfDevice::launch(int slot, size_t n_members, size_t in_bytes, size_t out_bytes, std::string* why, bool down) {
+bool BgzfDevice::launch(int slot, size_t n_members, size_t in_bytes, size_t out_bytes, std::string* why, bool down,
+                        uint8_t* d_dst) {
   Slot& s = s_[slot];
   hipStream_t st = (hipStream_t)stream_;
   if (!fits(n_members, in_bytes, out_bytes)) {
     if (why) *why = "a window larger than the buffers";
+    return false;
+  }
+  if (d_dst && down) {
+    if (why) *why = "a window with a destination of its own is not copied down";
     return false;
   }
   G2S_BZ_TRY(hipSetDevice(device_));
@@ -214,7 +219,7 @@ bool BgzfDevice::launch(int slot, size_t n_members, size_t in_bytes, size_t out_
     if (in_bytes) G2S_BZ_TRY(hipMemcpyAsync(s.d_in, s.h_in, in_bytes, hipMemcpyHostToDevice, st));
     G2S_BZ_TRY(hipMemcpyAsync(s.d_mem, s.h_mem, n_members * sizeof(BgzfMember), hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(g2s_bgzf_inflate, dim3((unsigned)n_members), dim3(kWave), 0, st, (const uint8_t*)s.d_in,
-                       (const BgzfMember*)s.d_mem, (uint32_t)n_members, s.d_out + front_, s.d_st);
+                       (const BgzfMember*)s.d_mem, (uint32_t)n_members, d_dst ? d_dst : s.d_out + front_, s.d_st);
     G2S_BZ_TRY(hipGetLastError());
     if (down) G2S_BZ_TRY(hipMemcpyAsync(s.h_out + front_, s.d_out + front_, out_bytes, hipMemcpyDeviceToHost, st));
     G2S_BZ_TRY(hipMemcpyAsync(s.h_st, s.d_st, n_members * 4, hipMemcpyDeviceToHost, st));

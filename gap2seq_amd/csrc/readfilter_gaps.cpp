@@ -8,18 +8,26 @@
 //   joins (device or host threads)    per gap the filter's bits (B_g), list 1 (records whose mate's bit is in B_g) and
 //                                     list 2 (records overlapping the flanks whose own bit is not), as (gap, row) pairs
 //                                     in (gap, row) order: readfilter_gpu.hip, or filter_join_host below.
-//   pass B (host walk)                the FASTA text of every row some gap (or the unmapped list) selected; every gap's
-//                                     text is its list 1 rows' text followed by its list 2 rows'.
+//   pass B (host walk, or device      the FASTA text of every row some gap (or the unmapped list) selected; every gap's
+//           kernels in one-pass mode) text is its list 1 rows' text followed by its list 2 rows'.
 //
 // With device inflate pass A's rows can be made by kernels from the inflated windows where they lie (bam_rows.hip:
 // G2S_DEVICE_ROWS=1 / G2S_HOST_ROWS=1, kDeviceRowsDefault), and the joins read them there; whatever those kernels cannot
 // account for hands pass A to the host walk, which is the authority on a file's errors.
 // Both passes read the file through BamFile (bam.cpp), which inflates it on the device the joins run on
 // (bgzf_inflate.hip, a window ahead of the walk) or with zlib on host threads (no device, G2S_HOST_INFLATE=1).
-// Pass B inflates the file a second time rather than keeping every record's bases from pass A (which would save that
-// inflate and cost half a byte of every base of the file on the host): the host holds 36 bytes a record (the rows),
-// then 13 bytes a record (pass B's selection and text offsets) and the text of the SELECTED records, once each however
-// many gaps select them.  The per-gap outputs themselves are the text of each gap's reads.
+// By default pass B is a second walk of the host over the file, inflated a second time rather than keeping every
+// record's bases from pass A on the host (which would save that inflate and cost half a byte of every base of the file
+// there): the host holds 36 bytes a record (the rows), then 13 bytes a record (pass B's selection and text offsets) and
+// the text of the SELECTED records, once each however many gaps select them.  The per-gap outputs themselves are the
+// text of each gap's reads.
+// One-pass mode (g2s_filter_set_one_pass, G2S_FILTER_ONE_PASS=1; off unless asked for): when the joins, the inflate and
+// pass A's rows all run on the device and the inflated file fits half the free device memory with the rows
+// (G2S_FILTER_RESIDENT_CAP lowers that), pass A inflates every window to its place in one device allocation and
+// records every row's offset in it, and pass B is kernels (bam_text.hip) that gather and decode the selected records
+// from there: the file is inflated once and the host walks nothing.  Whatever stands in the way — not asked for, no
+// device rows, over the cap, a failed allocation or HIP call — sends the call down the two-pass route from the point it
+// is at, with the resident buffer released first and nothing tried twice on the device; the outputs are the same bytes.
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -37,6 +45,7 @@
 #include "../../include/g2s_test.h"
 #include "bam.hpp"
 #include "bam_rows.h"
+#include "bam_text.h"
 #include "name_hash.h"
 #include "readfilter_gaps.hpp"
 
@@ -211,6 +220,37 @@ struct LastRows {
 };
 LastRows g_last_rows;
 
+// g2s_filter_set_one_pass: -1 follows G2S_FILTER_ONE_PASS (read per call), 0 forbids, 1 asks
+std::atomic<int> g_one_pass{-1};
+bool one_pass_asked() {
+  const int m = g_one_pass.load();
+  return m < 0 ? env_is_1("G2S_FILTER_ONE_PASS") : m > 0;
+}
+
+// g2s_test_last_filter_text: what pass B of the process's last batched call did
+struct LastText {
+  int one_pass = 0, reason = kTextNotAsked;
+  uint64_t reads = 0, bytes = 0, resident_bytes = 0;
+};
+LastText g_last_text;
+
+// G2S_DEBUG=1: where a batched call's time outside its three laps goes — opening the file (the BGZF index and the header,
+// whose first window zlib inflates), releasing run_filter_gaps' buffers, releasing the reader (its page-locked and device
+// buffers).  Declared in front of the BamFile, so that it is destroyed behind it.
+thread_local std::chrono::steady_clock::time_point g_laps_end;
+struct OutsideLaps {
+  using clock = std::chrono::steady_clock;
+  clock::time_point enter = clock::now(), opened = enter, returned = enter;
+  void open_done() { opened = clock::now(); }
+  int run_done(int rc) { returned = clock::now(); return rc; }
+  ~OutsideLaps() {
+    if (returned == enter || !getenv("G2S_DEBUG")) return;
+    auto ms = [](clock::time_point a, clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+    fprintf(stderr, "[g2s] outside the laps: open %.1f ms, the call's buffers released in %.1f ms, the reader in %.1f ms\n",
+            ms(enter, opened), ms(g_laps_end, returned), ms(returned, clock::now()));
+  }
+};
+
 // pass A on the host: the walk, one row per record
 bool pass_a_host(const BamFile& bam, FilterRows& R, int32_t* read_length, bool* too_many, std::string* err) {
   std::string nm;
@@ -277,7 +317,8 @@ bool name_hash_usable() {
 
 // Pass A on the device.  Null: *anomaly says why (kRowsOk: nothing asked for it), the reader's statistics are as they
 // were, and the host walk runs.
-std::unique_ptr<BamRowsDevice> pass_a_device(const BamFile& bam, size_t walk_window, int* anomaly) {
+std::unique_ptr<BamRowsDevice> pass_a_device(const BamFile& bam, size_t walk_window, int* anomaly, bool resident = false,
+                                             int* resident_refused = nullptr) {
   std::string why;
   *anomaly = kRowsOk;
   std::unique_ptr<BamRowsDevice> D;
@@ -285,12 +326,48 @@ std::unique_ptr<BamRowsDevice> pass_a_device(const BamFile& bam, size_t walk_win
     *anomaly = kRowsHash;
     why = "name_hash.h is not this build's std::hash<std::string>";
   } else {
-    D.reset(bam.rows_on_device(walk_window, anomaly, &why));
+    const char* cap = getenv("G2S_FILTER_RESIDENT_CAP");
+    D.reset(bam.rows_on_device(walk_window, anomaly, &why, resident, cap ? (uint64_t)strtoull(cap, nullptr, 10) : 0,
+                               resident_refused));
   }
   if (!D && getenv("G2S_DEBUG"))
     fprintf(stderr, "[g2s] pass A: no device rows (anomaly %d: %s): the host walk\n", *anomaly, why.c_str());
   if (D && getenv("G2S_DEBUG")) fprintf(stderr, "[g2s] pass A: rows on the device (%zu windows)\n", (size_t)bam.rows_windows());
   return D;
+}
+
+// pass B on the host: a second walk over the file, for the rows of `sel` (and the unmapped reads when asked for)
+bool pass_b_host(const BamFile& bam, uint64_t total, const std::vector<uint8_t>& sel, const BamTextAsk& ask, BamText* T,
+                 uint64_t* rows_seen, std::string* err) {
+  *T = BamText();
+  if (ask.pool) T->pidx.assign((size_t)total, 0);
+  else { T->toff.assign((size_t)total, 0); T->tlen.assign((size_t)total, 0); }
+  size_t row = 0;
+  const bool ok = bam.for_each([&](const BamRec& r) {
+    if (row >= total) return false;  // (the file changed under us: the caller's guard)
+    if (ask.pool) {
+      const bool un = ask.unmapped && (r.flag & BAM_UNMAPPED);
+      if (sel[row] || un) {
+        T->pidx[row] = (uint32_t)(T->pboff.size() - 1);
+        if (un) T->punmapped.push_back(T->pidx[row]);
+        append_bases(r, &T->pbases);
+        T->pboff.push_back(T->pbases.size());
+        if (ask.names) { T->pnames += own_name(r); T->pnoff.push_back(T->pnames.size()); }
+      }
+      row++;
+      return true;
+    }
+    if (sel[row]) {
+      T->toff[row] = T->text.size();
+      append_fasta(r, &T->text);
+      T->tlen[row] = (uint32_t)(T->text.size() - T->toff[row]);
+    }
+    if (ask.unmapped && (r.flag & BAM_UNMAPPED)) { append_fasta(r, &T->unmapped); T->n_unmapped++; }
+    row++;
+    return true;
+  }, err);
+  *rows_seen = row;
+  return ok;
 }
 
 // what g2s_filter_reads_gaps_pool asks of run_filter_gaps in place of the per-gap texts
@@ -337,11 +414,30 @@ int run_filter_gaps(BamFile& bam, const g2s_filter_opts* lib, const g2s_filter_g
   // the rows on the device, under the rule that inflates there, unless a switch says otherwise
   std::unique_ptr<BamRowsDevice> drows;
   LastRows lr;
+  // one-pass mode: asked for, and then whatever stands in its way is the reason it did not run
+  LastText lt;
+  const bool asked = one_pass_asked();
+  lt.reason = asked ? kTextNoDeviceRows : kTextNotAsked;
   if (device_inflate && !env_is_1("G2S_HOST_ROWS") && (kDeviceRowsDefault || env_is_1("G2S_DEVICE_ROWS"))) {
-    drows = pass_a_device(bam, 0, &lr.anomaly);
+    int refused = kResidentKept;
+    drows = pass_a_device(bam, 0, &lr.anomaly, asked, &refused);
     lr.windows = bam.rows_windows();
     if (!drows) bam.reset_inflate_stats();
+    if (asked && refused != kResidentKept) lt.reason = refused == kResidentOverCap ? kTextOverCap : kTextFailed;
+    else if (asked && drows && drows->stream_buffer()) lt.resident_bytes = drows->stream_bytes();
   }
+  const bool resident = drows && drows->stream_buffer();
+  if (asked && getenv("G2S_DEBUG")) {
+    static const char* const kWhy[] = {"", "", "pass A's rows were not made on the device", "over the cap", "an allocation failed"};
+    if (resident) fprintf(stderr, "[g2s] one-pass route: the inflated file stays on the device (%llu bytes)\n",
+                          (unsigned long long)lt.resident_bytes);
+    else fprintf(stderr, "[g2s] two-pass route (%s)\n", kWhy[lt.reason]);
+  }
+  auto note_text = [&] {
+    std::lock_guard<std::mutex> lk(g_last_mu);
+    g_last_text = lt;
+  };
+  note_text();
   if (drows) {
     lr.on_device = 1;
     lr.records = drows->rows().n;
@@ -393,52 +489,51 @@ int run_filter_gaps(BamFile& bam, const g2s_filter_opts* lib, const g2s_filter_g
   if (rc != G2S_OK) { set_filter_error(err); return rc; }
   st.on_device = on_device ? 1 : 0;
   st.ms_join = ms_since(t0);
-  drows.reset();
+  if (!resident) drows.reset();
   // ---- pass B: the text of the selected rows
   t0 = std::chrono::steady_clock::now();
   std::vector<uint8_t> sel(total, 0);
   for (uint64_t x : J.list1) sel[(uint32_t)x] = 1;
   for (uint64_t x : J.list2) sel[(uint32_t)x] = 1;
-  std::vector<uint64_t> toff(pool ? 0 : total, 0);
-  std::vector<uint32_t> tlen(pool ? 0 : total, 0);
-  std::string text, unmapped;
-  int64_t n_unmapped = 0;
-  const bool want_unmapped = pool ? pool->unmapped : unmapped_out != nullptr;
-  // (the pool: every held record once — its bases, its name when asked for, and its index by row)
-  std::string pbases, pnames;
-  std::vector<uint64_t> pboff(1, 0), pnoff(1, 0);
-  std::vector<uint32_t> pidx(pool ? total : 0, 0), punmapped;
-  size_t row = 0;
-  st.file_passes++;
-  if (!bam.for_each([&](const BamRec& r) {
-        if (row >= total) return false;  // (the file changed under us: guarded below)
-        if (pool) {
-          const bool un = want_unmapped && (r.flag & BAM_UNMAPPED);
-          if (sel[row] || un) {
-            pidx[row] = (uint32_t)(pboff.size() - 1);
-            if (un) punmapped.push_back(pidx[row]);
-            append_bases(r, &pbases);
-            pboff.push_back(pbases.size());
-            if (pool->names) { pnames += own_name(r); pnoff.push_back(pnames.size()); }
-          }
-          row++;
-          return true;
-        }
-        if (sel[row]) {
-          toff[row] = text.size();
-          append_fasta(r, &text);
-          tlen[row] = (uint32_t)(text.size() - toff[row]);
-        }
-        if (want_unmapped && (r.flag & BAM_UNMAPPED)) { append_fasta(r, &unmapped); n_unmapped++; }
-        row++;
-        return true;
-      }, &err)) {
-    note_pass(&li.ms_b);
-    set_filter_error(err);
-    return G2S_ERR_IO;
+  BamTextAsk ask;
+  ask.pool = pool != nullptr;
+  ask.names = pool && pool->names;
+  ask.unmapped = pool ? pool->unmapped : unmapped_out != nullptr;
+  BamText T;
+  bool text_done = false;
+  if (resident) {  // (one-pass mode: from the stream pass A left on the device)
+    std::string why;
+    const double ms_sel = ms_since(t0);
+    text_done = bam_text_device(*drows, sel.data(), ask, &T, &why);
+    const double ms_dev = ms_since(t0);
+    drows.reset();  // (the resident buffer goes before anything else runs)
+    if (getenv("G2S_DEBUG"))
+      fprintf(stderr, "[g2s] pass B on the device: selection %.1f ms, kernels and copies %.1f ms, release %.1f ms\n", ms_sel,
+              ms_dev - ms_sel, ms_since(t0) - ms_dev);
+    if (text_done) {
+      lt.one_pass = 1;
+      lt.reason = kTextOnDevice;
+      lt.reads = pool ? T.pboff.size() - 1 : (uint64_t)std::count(sel.begin(), sel.end(), (uint8_t)1) + (uint64_t)T.n_unmapped;
+      lt.bytes = pool ? T.pbases.size() + T.pnames.size() : T.text.size() + T.unmapped.size();
+    } else {
+      lt.reason = kTextFailed;
+      if (getenv("G2S_DEBUG")) fprintf(stderr, "[g2s] one-pass route given up in pass B (%s): the second pass on the host\n", why.c_str());
+    }
+    note_text();
   }
-  note_pass(&li.ms_b);
-  if (row != total) { set_filter_error("the BAM file changed between passes"); return G2S_ERR_IO; }
+  if (!text_done) {
+    uint64_t row = 0;
+    st.file_passes++;
+    const bool ok = pass_b_host(bam, total, sel, ask, &T, &row, &err);
+    note_pass(&li.ms_b);
+    if (!ok) { set_filter_error(err); return G2S_ERR_IO; }
+    if (row != total) { set_filter_error("the BAM file changed between passes"); return G2S_ERR_IO; }
+  }
+  const std::vector<uint64_t>&toff = T.toff, &pboff = T.pboff, &pnoff = T.pnoff;
+  const std::vector<uint32_t>&tlen = T.tlen, &pidx = T.pidx, &punmapped = T.punmapped;
+  const std::string &text = T.text, &unmapped = T.unmapped, &pbases = T.pbases, &pnames = T.pnames;
+  const int64_t n_unmapped = T.n_unmapped;
+  const bool want_unmapped = ask.unmapped;
   // ---- every gap's text: list 1's rows, then list 2's
   std::vector<size_t> at1(n + 1, 0), at2(n + 1, 0);
   for (uint64_t x : J.list1) at1[(size_t)(x >> 32) + 1]++;
@@ -477,6 +572,7 @@ int run_filter_gaps(BamFile& bam, const g2s_filter_opts* lib, const g2s_filter_g
     if (total_out) *total_out = (int64_t)total;
     st.ms_text = ms_since(t0);
     if (stats) *stats = st;
+    g_laps_end = std::chrono::steady_clock::now();
     return G2S_OK;
   }
   std::vector<char*> fa(n, nullptr), lg(n, nullptr), wn(n, nullptr);
@@ -520,6 +616,7 @@ int run_filter_gaps(BamFile& bam, const g2s_filter_opts* lib, const g2s_filter_g
   if (total_out) *total_out = (int64_t)total;
   st.ms_text = ms_since(t0);
   if (stats) *stats = st;
+  g_laps_end = std::chrono::steady_clock::now();
   return G2S_OK;
 }
 
@@ -539,43 +636,53 @@ int g2s_filter_reads_gaps(const char* bam_path, const g2s_filter_opts* lib, cons
                           char** fasta_out, char** log_out, char** warn_out, int64_t* extracted, int64_t* total,
                           char** unmapped_out, int64_t* unmapped_extracted, g2s_filter_stats* stats) {
   if (!bam_path || !g2s::gap_args_ok(lib, gaps, n)) return G2S_ERR_ARG;
+  g2s::OutsideLaps laps;
   g2s::BamFile bam;
   std::string err;
   if (!bam.open_path(bam_path, &err)) { g2s::set_filter_error(err); return G2S_ERR_IO; }
-  return g2s::run_filter_gaps(bam, lib, gaps, n, device, fasta_out, log_out, warn_out, extracted, total, unmapped_out,
-                              unmapped_extracted, stats);
+  laps.open_done();
+  return laps.run_done(g2s::run_filter_gaps(bam, lib, gaps, n, device, fasta_out, log_out, warn_out, extracted, total,
+                                            unmapped_out, unmapped_extracted, stats));
 }
 
 int g2s_filter_reads_gaps_mem(const void* bam_bytes, size_t nbytes, const g2s_filter_opts* lib, const g2s_filter_gap* gaps,
                               size_t n, int device, char** fasta_out, char** log_out, char** warn_out, int64_t* extracted,
                               int64_t* total, char** unmapped_out, int64_t* unmapped_extracted, g2s_filter_stats* stats) {
   if (!bam_bytes || !g2s::gap_args_ok(lib, gaps, n)) return G2S_ERR_ARG;
+  g2s::OutsideLaps laps;
   g2s::BamFile bam;
   std::string err;
   if (!bam.open_mem(bam_bytes, nbytes, &err)) { g2s::set_filter_error(err); return G2S_ERR_IO; }
-  return g2s::run_filter_gaps(bam, lib, gaps, n, device, fasta_out, log_out, warn_out, extracted, total, unmapped_out,
-                              unmapped_extracted, stats);
+  laps.open_done();
+  return laps.run_done(g2s::run_filter_gaps(bam, lib, gaps, n, device, fasta_out, log_out, warn_out, extracted, total,
+                                            unmapped_out, unmapped_extracted, stats));
 }
 
 int g2s_filter_reads_gaps_pool(const char* bam_path, const g2s_filter_opts* lib, const g2s_filter_gap* gaps, size_t n, int device,
                                int want_names, int want_unmapped, g2s_read_pool** out, int64_t* total, g2s_filter_stats* stats) {
   if (!bam_path || !out || !g2s::gap_args_ok(lib, gaps, n)) return G2S_ERR_ARG;
+  g2s::OutsideLaps laps;
   g2s::BamFile bam;
   std::string err;
   if (!bam.open_path(bam_path, &err)) { g2s::set_filter_error(err); return G2S_ERR_IO; }
+  laps.open_done();
   const g2s::PoolRequest req{want_names != 0, want_unmapped != 0, out};
-  return g2s::run_filter_gaps(bam, lib, gaps, n, device, nullptr, nullptr, nullptr, nullptr, total, nullptr, nullptr, stats, &req);
+  return laps.run_done(g2s::run_filter_gaps(bam, lib, gaps, n, device, nullptr, nullptr, nullptr, nullptr, total, nullptr, nullptr,
+                                            stats, &req));
 }
 
 int g2s_filter_reads_gaps_pool_mem(const void* bam_bytes, size_t nbytes, const g2s_filter_opts* lib, const g2s_filter_gap* gaps,
                                    size_t n, int device, int want_names, int want_unmapped, g2s_read_pool** out, int64_t* total,
                                    g2s_filter_stats* stats) {
   if (!bam_bytes || !out || !g2s::gap_args_ok(lib, gaps, n)) return G2S_ERR_ARG;
+  g2s::OutsideLaps laps;
   g2s::BamFile bam;
   std::string err;
   if (!bam.open_mem(bam_bytes, nbytes, &err)) { g2s::set_filter_error(err); return G2S_ERR_IO; }
+  laps.open_done();
   const g2s::PoolRequest req{want_names != 0, want_unmapped != 0, out};
-  return g2s::run_filter_gaps(bam, lib, gaps, n, device, nullptr, nullptr, nullptr, nullptr, total, nullptr, nullptr, stats, &req);
+  return laps.run_done(g2s::run_filter_gaps(bam, lib, gaps, n, device, nullptr, nullptr, nullptr, nullptr, total, nullptr, nullptr,
+                                            stats, &req));
 }
 
 void g2s_read_pool_free(g2s_read_pool* p) {
@@ -640,10 +747,98 @@ int g2s_test_last_filter_inflate(int* on_device, uint64_t* members, uint64_t* by
   return G2S_OK;
 }
 
-// TEST HOOK (include/g2s_test.h): pass A alone
-int g2s_test_bam_rows(const void* bytes, size_t n, int device, size_t window, uint64_t cap, int32_t* ref_id, int32_t* pos,
-                      int64_t* end, uint32_t* flag, uint64_t* h_own, uint64_t* h_mate, uint64_t* total, int32_t* read_length,
-                      int64_t* max_span) {
+// TEST HOOK (include/g2s_test.h)
+int g2s_test_last_filter_text(int* one_pass, int* reason, uint64_t* reads, uint64_t* bytes, uint64_t* resident_bytes) {
+  std::lock_guard<std::mutex> lk(g2s::g_last_mu);
+  if (one_pass) *one_pass = g2s::g_last_text.one_pass;
+  if (reason) *reason = g2s::g_last_text.reason;
+  if (reads) *reads = g2s::g_last_text.reads;
+  if (bytes) *bytes = g2s::g_last_text.bytes;
+  if (resident_bytes) *resident_bytes = g2s::g_last_text.resident_bytes;
+  return G2S_OK;
+}
+
+int g2s_filter_set_one_pass(int mode) { return g2s::g_one_pass.exchange(mode < 0 ? -1 : mode > 0 ? 1 : 0); }
+
+// TEST HOOK (include/g2s_test.h): pass B alone
+int g2s_test_bam_text(const void* bytes, size_t n, int device, const uint32_t* rows, uint64_t n_rows, int want_names, int fasta,
+                      uint8_t* bases, uint64_t bases_cap, uint64_t* bases_n, uint8_t* names, uint64_t names_cap,
+                      uint64_t* names_n, uint64_t* base_off, uint64_t* name_off, uint64_t off_cap, uint64_t* n_reads) {
+  if (!bytes || (n_rows && !rows) || !bases_n || !names_n || !n_reads || (bases_cap && !bases) || (names_cap && !names) ||
+      (off_cap && (!base_off || !name_off))) {
+    g2s::set_filter_error("g2s_test_bam_text: bad argument");
+    return G2S_ERR_ARG;
+  }
+  *bases_n = *names_n = *n_reads = 0;
+  if (device >= 0 && !g2s::filter_device_usable(device)) {
+    g2s::set_filter_error("g2s_test_bam_text: no usable gfx950 device " + std::to_string(device));
+    return G2S_ERR_NO_DEVICE;
+  }
+  g2s::BamFile bam;
+  std::string err;
+  if (!bam.open_mem(bytes, n, &err)) { g2s::set_filter_error(err); return G2S_ERR_IO; }
+  bam.set_threads(1);
+  bam.set_inflate_device(device >= 0 ? device : -1);
+  // pass A, for the record count (and, on the device, the resident stream)
+  std::unique_ptr<g2s::BamRowsDevice> D;
+  uint64_t total = 0;
+  if (device >= 0) {
+    int anomaly = 0, refused = 0;
+    D = g2s::pass_a_device(bam, 0, &anomaly, true, &refused);
+    if (!D || !D->stream_buffer()) {  // (never the host in the kernels' place)
+      g2s::set_filter_error("g2s_test_bam_text: no resident stream (anomaly " + std::to_string(anomaly) + ", refused " +
+                            std::to_string(refused) + ")");
+      return G2S_ERR_HIP;
+    }
+    total = D->rows().n;
+  } else {
+    g2s::FilterRows R;
+    int32_t rl = 0;
+    bool too_many = false;
+    if (!g2s::pass_a_host(bam, R, &rl, &too_many, &err)) { g2s::set_filter_error(err); return G2S_ERR_IO; }
+    if (too_many) { g2s::set_filter_error("more than 2^32 - 2 records"); return G2S_ERR_ARG; }
+    total = R.size();
+  }
+  std::vector<uint8_t> sel((size_t)total, 0);
+  for (uint64_t i = 0; i < n_rows; i++) {
+    if (rows[i] >= total) { g2s::set_filter_error("g2s_test_bam_text: a row beyond the file's records"); return G2S_ERR_ARG; }
+    sel[rows[i]] = 1;
+  }
+  g2s::BamTextAsk ask;
+  ask.pool = !fasta;
+  ask.names = !fasta && want_names;
+  g2s::BamText T;
+  if (device >= 0) {
+    if (!g2s::bam_text_device(*D, sel.data(), ask, &T, &err)) { g2s::set_filter_error("g2s_test_bam_text: " + err); return G2S_ERR_HIP; }
+  } else {
+    uint64_t seen = 0;
+    if (!g2s::pass_b_host(bam, total, sel, ask, &T, &seen, &err)) { g2s::set_filter_error(err); return G2S_ERR_IO; }
+  }
+  // the selected rows' pieces in file order: the pool's arrays, or the FASTA records with their offsets
+  std::vector<uint64_t> foff(1, 0);
+  std::string ftext;
+  if (fasta)
+    for (size_t r = 0; r < (size_t)total; r++)
+      if (sel[r]) { ftext.append(T.text, (size_t)T.toff[r], T.tlen[r]); foff.push_back(ftext.size()); }
+  const std::string& B = fasta ? ftext : T.pbases;
+  const std::vector<uint64_t>& BO = fasta ? foff : T.pboff;
+  *n_reads = BO.size() - 1;
+  *bases_n = B.size();
+  *names_n = T.pnames.size();
+  if (bases_cap && !B.empty()) memcpy(bases, B.data(), (size_t)std::min<uint64_t>(bases_cap, B.size()));
+  if (names_cap && !T.pnames.empty()) memcpy(names, T.pnames.data(), (size_t)std::min<uint64_t>(names_cap, T.pnames.size()));
+  for (uint64_t i = 0; i < std::min<uint64_t>(off_cap, BO.size()); i++) {
+    base_off[i] = BO[i];
+    name_off[i] = ask.names ? T.pnoff[i] : 0;
+  }
+  g2s::set_filter_error("");
+  return G2S_OK;
+}
+
+// pass A alone (g2s_test_bam_rows; `keep`: g2s_test_bam_rows_kept)
+static int bam_rows_hook(bool keep, const void* bytes, size_t n, int device, size_t window, uint64_t cap, int32_t* ref_id,
+                         int32_t* pos, int64_t* end, uint32_t* flag, uint64_t* h_own, uint64_t* h_mate, uint64_t* total,
+                         int32_t* read_length, int64_t* max_span) {
   if (!bytes || !total || !read_length || !max_span || (cap && (!ref_id || !pos || !end || !flag || !h_own || !h_mate))) {
     g2s::set_filter_error("g2s_test_bam_rows: bad argument");
     return G2S_ERR_ARG;
@@ -666,8 +861,14 @@ int g2s_test_bam_rows(const void* bytes, size_t n, int device, size_t window, ui
     g2s::g_last_rows = lr;
   };
   if (device >= 0) {
-    std::unique_ptr<g2s::BamRowsDevice> D = g2s::pass_a_device(bam, window, &lr.anomaly);
+    int refused = 0;
+    std::unique_ptr<g2s::BamRowsDevice> D = g2s::pass_a_device(bam, window, &lr.anomaly, keep, &refused);
     lr.windows = bam.rows_windows();
+    if (D && keep && !D->stream_buffer()) {  // (never the two-slot route in the resident one's place)
+      note();
+      g2s::set_filter_error("g2s_test_bam_rows_kept: the stream was not kept (refused " + std::to_string(refused) + ")");
+      return G2S_ERR_HIP;
+    }
     if (!D) {  // (never the host in the kernels' place)
       note();
       g2s::set_filter_error("g2s_test_bam_rows: the device gave up its rows (anomaly " + std::to_string(lr.anomaly) + ")");
@@ -707,6 +908,19 @@ int g2s_test_bam_rows(const void* bytes, size_t n, int device, size_t window, ui
   }
   g2s::set_filter_error("");
   return G2S_OK;
+}
+
+// TEST HOOKS (include/g2s_test.h)
+int g2s_test_bam_rows(const void* bytes, size_t n, int device, size_t window, uint64_t cap, int32_t* ref_id, int32_t* pos,
+                      int64_t* end, uint32_t* flag, uint64_t* h_own, uint64_t* h_mate, uint64_t* total, int32_t* read_length,
+                      int64_t* max_span) {
+  return bam_rows_hook(false, bytes, n, device, window, cap, ref_id, pos, end, flag, h_own, h_mate, total, read_length, max_span);
+}
+int g2s_test_bam_rows_kept(const void* bytes, size_t n, int device, size_t window, uint64_t cap, int32_t* ref_id, int32_t* pos,
+                           int64_t* end, uint32_t* flag, uint64_t* h_own, uint64_t* h_mate, uint64_t* total,
+                           int32_t* read_length, int64_t* max_span) {
+  return bam_rows_hook(device >= 0, bytes, n, device, window, cap, ref_id, pos, end, flag, h_own, h_mate, total, read_length,
+                       max_span);
 }
 
 // TEST HOOK (include/g2s_test.h)

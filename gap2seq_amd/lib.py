@@ -237,9 +237,19 @@ _SIGS = {
     "g2s_test_bam_rows": (C.c_int, [C.c_char_p, C.c_size_t, C.c_int, C.c_size_t, C.c_uint64, C.POINTER(C.c_int32),
                                     C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64),
                                     C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+    "g2s_test_bam_rows_kept": (C.c_int, [C.c_char_p, C.c_size_t, C.c_int, C.c_size_t, C.c_uint64, C.POINTER(C.c_int32),
+                                         C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64),
+                                         C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     "g2s_test_name_hash": (C.c_int, [C.c_char_p, C.c_size_t, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "g2s_test_last_filter_rows": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
                                             C.POINTER(C.c_uint64), C.POINTER(C.c_int)]),
+    "g2s_filter_set_one_pass": (C.c_int, [C.c_int]),
+    "g2s_test_last_filter_text": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                            C.POINTER(C.c_uint64)]),
+    "g2s_test_bam_text": (C.c_int, [C.c_char_p, C.c_size_t, C.c_int, C.POINTER(C.c_uint32), C.c_uint64, C.c_int, C.c_int,
+                                    C.POINTER(C.c_uint8), C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint8), C.c_uint64,
+                                    C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_uint64,
+                                    C.POINTER(C.c_uint64)]),
     "g2s_graph_validate": (C.c_int64, [C.c_void_p, C.c_char_p, C.c_size_t]),
     "g2s_test_post_gap": (C.c_int, [_VP, C.POINTER(g2s_params), C.POINTER(g2s_gap), C.c_int32,
                                     C.POINTER(C.c_uint32), C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.c_int32,
@@ -1158,19 +1168,21 @@ def last_filter_inflate():
                 ms_pass_b_inflate=b.value)
 
 
-def bam_rows(data, device=-1, window=0):
+def bam_rows(data, device=-1, window=0, kept=False):
     """TEST HOOK binding (g2s_test_bam_rows): pass A alone on a BAM file in memory, by the host walk (device -1) or by the
     kernels on `device`, `window` bytes at a time (0: the reader's window).  Returns (code, rows, g2s_filter_last_error's
     text) with rows = dict(ref_id, pos, end, flag, h_own, h_mate: lists in file order; total, read_length, max_span), or
-    None when the code is not G2S_OK; nothing is raised, the code is the caller's to check."""
+    None when the code is not G2S_OK; nothing is raised, the code is the caller's to check.  kept=True
+    (g2s_test_bam_rows_kept): pass A as one-pass mode runs it, the inflated file kept in one device allocation."""
     lib = load_library()
+    hook = lib.g2s_test_bam_rows_kept if kept else lib.g2s_test_bam_rows
     data = bytes(data)
     cap = 1 << 12
     while True:
         arr = [(C.c_int32 * cap)(), (C.c_int32 * cap)(), (C.c_int64 * cap)(), (C.c_uint32 * cap)(), (C.c_uint64 * cap)(),
                (C.c_uint64 * cap)()]
         total, rl, span = C.c_uint64(0), C.c_int32(0), C.c_int64(0)
-        rc = lib.g2s_test_bam_rows(data, len(data), device, window, cap, *arr, C.byref(total), C.byref(rl), C.byref(span))
+        rc = hook(data, len(data), device, window, cap, *arr, C.byref(total), C.byref(rl), C.byref(span))
         if rc != G2S_OK or total.value <= cap:
             break
         cap = total.value
@@ -1199,3 +1211,47 @@ def last_filter_rows():
     d, w, r, c, a = C.c_int(), C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_int()
     _check(load_library().g2s_test_last_filter_rows(C.byref(d), C.byref(w), C.byref(r), C.byref(c), C.byref(a)))
     return dict(on_device=d.value, windows=w.value, records=r.value, candidates=c.value, anomaly=a.value)
+
+
+def filter_set_one_pass(mode):
+    """g2s_filter_set_one_pass: 1 asks for one-pass mode in every later batched filter call of the process, 0 forbids it,
+    -1 follows G2S_FILTER_ONE_PASS.  Returns the previous mode."""
+    return load_library().g2s_filter_set_one_pass(int(mode))
+
+
+TEXT_REASONS = ("on the device", "not asked", "no device rows", "over the cap", "allocation or HIP failure")
+
+
+def last_filter_text():
+    """TEST HOOK binding (g2s_test_last_filter_text): dict(one_pass, reason (index into TEXT_REASONS), reads, bytes,
+    resident_bytes) of pass B in the process's last batched filter call"""
+    o, r, n, b, rb = C.c_int(), C.c_int(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+    _check(load_library().g2s_test_last_filter_text(C.byref(o), C.byref(r), C.byref(n), C.byref(b), C.byref(rb)))
+    return dict(one_pass=o.value, reason=r.value, reads=n.value, bytes=b.value, resident_bytes=rb.value)
+
+
+def bam_text(data, rows, device=-1, names=True, fasta=False):
+    """TEST HOOK binding (g2s_test_bam_text): pass B alone on a BAM file in memory for the records `rows` (indices in file
+    order), by the host walk (device -1) or by the kernels on `device`.  Returns (code, dict(bases, base_off, names,
+    name_off) or None, g2s_filter_last_error's text): the pool's arrays of the selected records in file order, or with
+    fasta=True their FASTA records in `bases`; nothing is raised, the code is the caller's to check."""
+    lib = load_library()
+    data = bytes(data)
+    rows = list(rows)
+    arr = (C.c_uint32 * max(1, len(rows)))(*rows)
+    bcap, ncap, ocap = 1 << 16, 1 << 12, len(set(rows)) + 1
+    while True:
+        B, N = (C.c_uint8 * bcap)(), (C.c_uint8 * ncap)()
+        bo, no = (C.c_uint64 * ocap)(), (C.c_uint64 * ocap)()
+        bn, nn, nr = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        rc = lib.g2s_test_bam_text(data, len(data), device, arr, len(rows), int(names), int(fasta), B, bcap, C.byref(bn), N, ncap,
+                                   C.byref(nn), bo, no, ocap, C.byref(nr))
+        if rc != G2S_OK or (bn.value <= bcap and nn.value <= ncap and nr.value + 1 <= ocap):
+            break
+        bcap, ncap, ocap = max(bcap, bn.value), max(ncap, nn.value), max(ocap, nr.value + 1)
+    msg = (lib.g2s_filter_last_error() or b"").decode("utf-8", "replace")
+    if rc != G2S_OK:
+        return rc, None, msg
+    m = nr.value + 1
+    return rc, dict(bases=bytes(B[:bn.value]), base_off=list(bo[:m]), names=bytes(N[:nn.value]),
+                    name_off=list(no[:m]) if names and not fasta else None), msg

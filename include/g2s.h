@@ -508,7 +508,7 @@ typedef struct g2s_filter_gap {
   int32_t breakpoint, gap_length, flank_length;   /* as in g2s_filter_opts; flank_length -1 = no flank reads */
 } g2s_filter_gap;
 typedef struct g2s_filter_stats {
-  uint32_t file_passes;              /* inflating passes over the BAM made by this call (2) */
+  uint32_t file_passes;              /* inflating passes over the BAM made by this call (2, or 1 in one-pass mode) */
   uint32_t on_device;                /* 1 when the joins ran on the GPU */
   double ms_inflate, ms_join, ms_text;   /* laps: pass A; windows and joins; pass B and the per-gap texts */
 } g2s_filter_stats;
@@ -546,6 +546,15 @@ int g2s_filter_reads_gaps_pool_mem(const void* bam_bytes, size_t nbytes, const g
                                    size_t n, int device, int want_names, int want_unmapped, g2s_read_pool** out, int64_t* total,
                                    g2s_filter_stats* stats);
 void g2s_read_pool_free(g2s_read_pool* p);
+
+/* One-pass mode of the four batched calls above (ABI 6, additive), process-wide and atomic: 1 asks for it in every
+ * later call, 0 forbids it, -1 (the initial state) follows the environment (G2S_FILTER_ONE_PASS=1|0, read per call;
+ * off when it is not set).  Returns the previous mode.  In one-pass mode pass A leaves the inflated file in device memory
+ * and pass B is kernels that gather the selected reads from it: the file is inflated once.  It is taken only when the
+ * joins, the inflate and pass A's rows all run on the device and the inflated file with its rows fits half the free
+ * device memory (G2S_FILTER_RESIDENT_CAP=BYTES lowers that); otherwise the call takes the two-pass route.  Outputs,
+ * messages and codes are the same bytes on either route; g2s_filter_stats::file_passes says which one ran. */
+int g2s_filter_set_one_pass(int mode);
 
 /* ---------------------------------------------------------------------------
  *  Page-locked host memory the GPUs can write: a `results` array or fill arena

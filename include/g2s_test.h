@@ -150,6 +150,14 @@ int g2s_test_bam_rows(const void* bytes, size_t n, int device, size_t window, ui
                       int64_t* end, uint32_t* flag, uint64_t* h_own, uint64_t* h_mate, uint64_t* total, int32_t* read_length,
                       int64_t* max_span);
 
+/* TEST HOOK: g2s_test_bam_rows with pass A as one-pass mode runs it on a device (csrc/bam_text.h): every window inflated
+ * to its place in one device allocation, the row kernels on the word boundary in front of it, the chain's head moved from
+ * window to window in place of the carry.  The rows must be g2s_test_bam_rows'.  G2S_ERR_HIP also when the stream was not
+ * kept (over the cap, a failed allocation); device == -1 is the host walk, as there. */
+int g2s_test_bam_rows_kept(const void* bytes, size_t n, int device, size_t window, uint64_t cap, int32_t* ref_id, int32_t* pos,
+                           int64_t* end, uint32_t* flag, uint64_t* h_own, uint64_t* h_mate, uint64_t* total,
+                           int32_t* read_length, int64_t* max_span);
+
 /* TEST HOOK: the hash of the name bytes[0 .. strnlen(bytes, len)) followed by "/1" or "/2" (`which`: 1 or 2; len at
  * most 255): *std_hash from std::hash<std::string>, as the host walk takes it, and *own_hash from the host compilation
  * of csrc/name_hash.h, the function the kernels run. */
@@ -163,6 +171,30 @@ int g2s_test_name_hash(const void* bytes, size_t len, int which, uint64_t* std_h
  * 5 an allocation or a HIP call failed, 6 name_hash.h is not this build's std::hash, 7 a member did not inflate, 8 a
  * file outside the kernels' limits.  Any pointer may be NULL. */
 int g2s_test_last_filter_rows(int* on_device, uint64_t* windows, uint64_t* records, uint64_t* candidates, int* anomaly);
+
+/* TEST HOOK: what pass B did in the process's last g2s_filter_reads_gaps[_mem] / _pool[_mem] call.  *one_pass: 1 when it
+ * ran on the device from the stream pass A kept there (one-pass mode, g2s_filter_set_one_pass); *reason why it did not
+ * (csrc/bam_text.h: TextReason): 0 it did, 1 not asked for, 2 pass A's rows were not made on the device (no device, a
+ * switch, an anomaly), 3 the inflated file and its rows are over the cap (half the free device memory,
+ * G2S_FILTER_RESIDENT_CAP), 4 an allocation or a HIP call failed.  *reads / *bytes: the records pass B's kernels
+ * produced and the bytes of their bases, names or text (0 when it did not run there); *resident_bytes: the inflated
+ * stream pass A kept on the device (0: none).  Any pointer may be NULL. */
+int g2s_test_last_filter_text(int* one_pass, int* reason, uint64_t* reads, uint64_t* bytes, uint64_t* resident_bytes);
+
+/* TEST HOOK: pass B of the batched read filter alone, on a BAM file in memory, for the records whose indices (in file
+ * order, from 0) are rows[0 .. n_rows) — in any order, repeats allowed; a row beyond the file's records is G2S_ERR_ARG.
+ * device == -1: the host walk (BamFile::for_each with append_bases / own_name).  device >= 0: pass A's kernels with the
+ * inflated file kept on the device, then the kernels of csrc/bam_text.hip — G2S_ERR_NO_DEVICE when it is no usable
+ * gfx950, G2S_ERR_HIP when anything on the device refuses; never the host walk in their place.
+ * fasta == 0: the pool's arrays for the selected records in file order: their bases back to back with base_off, and with
+ * want_names their names (name, "/1" or "/2") back to back with name_off.  fasta != 0: `bases` receives the records'
+ * FASTA texts (">" name "/1|/2" "\n" bases "\n") back to back and base_off where each begins; no names.
+ * *n_reads: the distinct selected records; base_off / name_off have *n_reads + 1 entries, of which the first
+ * min(off_cap, *n_reads + 1) are written; *bases_n / *names_n are the true sizes and the first min(cap, size) bytes are
+ * written, so a caller whose capacity was too small calls again. */
+int g2s_test_bam_text(const void* bytes, size_t n, int device, const uint32_t* rows, uint64_t n_rows, int want_names, int fasta,
+                      uint8_t* bases, uint64_t bases_cap, uint64_t* bases_n, uint8_t* names, uint64_t names_cap,
+                      uint64_t* names_n, uint64_t* base_off, uint64_t* name_off, uint64_t off_cap, uint64_t* n_reads);
 
 #ifdef __cplusplus
 }

@@ -6,6 +6,8 @@
   device    g2s_filter_reads_gaps with the joins on the GPU, with its laps: the first call of the process (HIP's
             start-up falls into its first device lap) and a second one; the file is inflated on the GPU too
   device_host_inflate   (--host-inflate) the same with G2S_HOST_INFLATE=1: zlib on host threads, the joins on the GPU
+  --one-pass            asks for one-pass mode in every batched call (g2s_filter_set_one_pass(1)): the device legs then
+                        report file_passes 1, and every leg says whether pass B ran on the device (text_on_device)
 
 Every run also carries the reader's own laps (g2s_test_last_filter_inflate): whether the file was inflated on the
 device and the time inside the reader's refills in pass A and pass B.
@@ -15,7 +17,7 @@ with --gaps gaps at random breakpoints; the same gaps for all three, on the coor
 records shuffled (where the host joins sort their index, which a sorted file spares them).
 
   python tools/readfilter_bench.py [--pairs 1000000] [--gaps 1000] [--loop-gaps 20] [--device 0] [--threads 0]
-                                   [--host-inflate]
+                                   [--host-inflate] [--one-pass]
 """
 import argparse
 import json
@@ -41,7 +43,10 @@ def main():
     ap.add_argument("--threads", type=int, default=0)
     ap.add_argument("--seed", type=int, default=5)
     ap.add_argument("--host-inflate", action="store_true", help="add a leg with G2S_HOST_INFLATE=1")
+    ap.add_argument("--one-pass", action="store_true", help="ask for one-pass mode (g2s_filter_set_one_pass(1))")
     a = ap.parse_args()
+    if a.one_pass:
+        P.filter_set_one_pass(1)
     t0 = time.time()
     scaffold_len = max(10000, a.pairs // a.scaffolds * 2)
     refs, recs, _ = BW.simulate_library(a.seed, n_scaffolds=a.scaffolds, scaffold_len=scaffold_len,
@@ -82,11 +87,13 @@ def main():
         got, st = P.filter_reads_gaps(data, mean, sd, gaps, device=dev, threads=a.threads)
         dt = time.perf_counter() - t0
         os.environ.pop("G2S_HOST_INFLATE", None)
-        inf = P.last_filter_inflate()
+        inf, txt = P.last_filter_inflate(), P.last_filter_text()
         want = check[id(data)]
         assert got[:len(want)] == want, label + ": differs from the per-gap filter"
         out[label] = dict(s=round(dt, 3), inflate_ms=round(st["ms_inflate"], 1), join_ms=round(st["ms_join"], 1),
                           text_ms=round(st["ms_text"], 1), on_device=st["on_device"], file_passes=st["file_passes"],
+                          text_on_device=txt["one_pass"], text_reason=P.TEXT_REASONS[txt["reason"]],
+                          resident_mb=round(txt["resident_bytes"] / 1e6, 1),
                           extracted=sum(x[3] for x in got), inflate_on_device=inf["on_device"],
                           refill_a_ms=round(inf["ms_pass_a_inflate"], 1), refill_b_ms=round(inf["ms_pass_b_inflate"], 1))
     print(json.dumps(out))
