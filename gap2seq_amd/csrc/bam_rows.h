@@ -86,8 +86,8 @@ class BamRowsDevice {
   uint64_t cap_rows_ = 0;
   int32_t n_ref_ = 0;
   DeviceRows rows_;
-  void *state_ = nullptr, *cand_ = nullptr, *link_ = nullptr, *j0_ = nullptr, *j1_ = nullptr, *mark_ = nullptr, *emit_ = nullptr,
-       *blk_ = nullptr;
+  struct Buffers;  // (bam_rows.hip) the device allocations, rows_' arrays and stream_buf_ among them
+  Buffers* buf_ = nullptr;
   uint64_t windows_ = 0, candidates_ = 0;
   uint8_t* stream_buf_ = nullptr;
   uint64_t stream_bytes_ = 0;

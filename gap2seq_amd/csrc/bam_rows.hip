@@ -33,6 +33,7 @@
 #include <string>
 
 #include "bam_rows.h"
+#include "hip_host.h"
 #include "name_hash.h"
 #include "readfilter_gaps.hpp"
 
@@ -350,22 +351,16 @@ __global__ void k_end(State* st, int64_t bytes) {
   if (!st->anomaly && (int64_t)st->head != bytes) st->anomaly = g2s::kRowsWrongEnd;
 }
 
-bool fail(std::string* why, const char* what, hipError_t e) {
-  if (why) *why = std::string(what) + ": " + hipGetErrorString(e);
-  return false;
-}
-
 uint32_t window_capacity(size_t bytes) { return (uint32_t)(bytes / kHead) + kSlack + 1u; }
 
 }  // namespace
 
 namespace g2s {
 
-#define G2S_BR_TRY(expr)                                  \
-  do {                                                    \
-    const hipError_t e_ = (expr);                         \
-    if (e_ != hipSuccess) return fail(why, #expr, e_);    \
-  } while (0)
+// the object's device allocations: freed by their destructors, the last declared first
+struct BamRowsDevice::Buffers {
+  DevMem stream_buf, rec_off, h_mate, h_own, flag, end, pos, ref_id, blk, emit, mark, j1, j0, link, cand, state;
+};
 
 BamRowsDevice* BamRowsDevice::create(int device, void* stream, size_t max_window, size_t walk_window, size_t front,
                                      uint64_t cap_rows, int32_t n_ref, uint64_t first_head, std::string* why,
@@ -376,6 +371,7 @@ BamRowsDevice* BamRowsDevice::create(int device, void* stream, size_t max_window
     return nullptr;
   }
   BamRowsDevice* D = new BamRowsDevice();
+  Buffers& B = *(D->buf_ = new Buffers());
   D->device_ = device;
   D->stream_ = stream;
   D->walk_ = walk;
@@ -387,45 +383,48 @@ BamRowsDevice* BamRowsDevice::create(int device, void* stream, size_t max_window
   const size_t nblk = std::max<size_t>(D->max_tiles_, (D->cap_cand_ + kBlock - 1) / kBlock) + 1;
   auto make = [&]() -> bool {
     const size_t rows = (size_t)cap_rows + 1, cc = D->cap_cand_;
-    G2S_BR_TRY(hipSetDevice(device));
+    G2S_HIP_TRY(hipSetDevice(device));
     // one-pass mode: the whole inflated stream and the records' offsets, when they fit under the cap with the rows
     if (ask && ask->bytes) {
       size_t free_b = 0, total_b = 0;
-      G2S_BR_TRY(hipMemGetInfo(&free_b, &total_b));
+      G2S_HIP_TRY(hipMemGetInfo(&free_b, &total_b));
       const uint64_t need = ask->bytes + 64 + rows * 52, cap = std::min<uint64_t>(free_b / 2, ask->cap ? ask->cap : UINT64_MAX);
       if (need > cap) {
         *resident_refused = kResidentOverCap;
-      } else if (hipMalloc((void**)&D->stream_buf_, (size_t)ask->bytes + 64) != hipSuccess ||
-                 hipMalloc((void**)&D->rows_.rec_off, rows * 8) != hipSuccess) {
-        (void)hipGetLastError();
-        if (D->stream_buf_) (void)hipFree(D->stream_buf_);
-        if (D->rows_.rec_off) (void)hipFree(D->rows_.rec_off);
-        D->stream_buf_ = nullptr;
-        D->rows_.rec_off = nullptr;
-        *resident_refused = kResidentNoMemory;
       } else {
-        D->stream_bytes_ = ask->bytes;
+        DevMem off, buf;  // (taken buf first; when either fails, freed buf first, before anything else is taken)
+        if (buf.alloc((size_t)ask->bytes + 64) != hipSuccess || off.alloc(rows * 8) != hipSuccess) {
+          (void)hipGetLastError();
+          *resident_refused = kResidentNoMemory;
+        } else {
+          D->stream_buf_ = (B.stream_buf = std::move(buf)).as<uint8_t>();
+          D->rows_.rec_off = (B.rec_off = std::move(off)).as<uint64_t>();
+          D->stream_bytes_ = ask->bytes;
+        }
       }
     }
-    G2S_BR_TRY(hipMalloc(&D->state_, sizeof(State)));
-    G2S_BR_TRY(hipMalloc(&D->cand_, cc * 4));
-    G2S_BR_TRY(hipMalloc(&D->link_, cc * 4));
-    G2S_BR_TRY(hipMalloc(&D->j0_, cc * 4));
-    G2S_BR_TRY(hipMalloc(&D->j1_, cc * 4));
-    G2S_BR_TRY(hipMalloc(&D->mark_, cc));
-    G2S_BR_TRY(hipMalloc(&D->emit_, cc));
-    G2S_BR_TRY(hipMalloc(&D->blk_, nblk * 4));
-    G2S_BR_TRY(hipMalloc((void**)&D->rows_.ref_id, rows * 4));
-    G2S_BR_TRY(hipMalloc((void**)&D->rows_.pos, rows * 4));
-    G2S_BR_TRY(hipMalloc((void**)&D->rows_.end, rows * 8));
-    G2S_BR_TRY(hipMalloc((void**)&D->rows_.flag, rows * 4));
-    G2S_BR_TRY(hipMalloc((void**)&D->rows_.h_own, rows * 8));
-    G2S_BR_TRY(hipMalloc((void**)&D->rows_.h_mate, rows * 8));
+    G2S_HIP_TRY(B.state.alloc(sizeof(State)));
+    G2S_HIP_TRY(B.cand.alloc(cc * 4));
+    G2S_HIP_TRY(B.link.alloc(cc * 4));
+    G2S_HIP_TRY(B.j0.alloc(cc * 4));
+    G2S_HIP_TRY(B.j1.alloc(cc * 4));
+    G2S_HIP_TRY(B.mark.alloc(cc));
+    G2S_HIP_TRY(B.emit.alloc(cc));
+    G2S_HIP_TRY(B.blk.alloc(nblk * 4));
+    G2S_HIP_TRY(B.ref_id.alloc(rows * 4));
+    G2S_HIP_TRY(B.pos.alloc(rows * 4));
+    G2S_HIP_TRY(B.end.alloc(rows * 8));
+    G2S_HIP_TRY(B.flag.alloc(rows * 4));
+    G2S_HIP_TRY(B.h_own.alloc(rows * 8));
+    G2S_HIP_TRY(B.h_mate.alloc(rows * 8));
+    DeviceRows& R = D->rows_;  // (the plain pointers the joins read)
+    R.ref_id = B.ref_id.as<int32_t>(), R.pos = B.pos.as<int32_t>(), R.end = B.end.as<int64_t>(), R.flag = B.flag.as<uint32_t>();
+    R.h_own = B.h_own.as<uint64_t>(), R.h_mate = B.h_mate.as<uint64_t>();
     State s{};
     s.head = (int32_t)first_head;
     s.max_span = 1;
-    G2S_BR_TRY(hipMemcpyAsync(D->state_, &s, sizeof s, hipMemcpyHostToDevice, (hipStream_t)stream));
-    G2S_BR_TRY(hipStreamSynchronize((hipStream_t)stream));  // (`s` leaves scope)
+    G2S_HIP_TRY(hipMemcpyAsync(B.state.p, &s, sizeof s, hipMemcpyHostToDevice, (hipStream_t)stream));
+    G2S_HIP_TRY(hipStreamSynchronize((hipStream_t)stream));  // (`s` leaves scope)
     return true;
   };
   if (!make()) {
@@ -438,18 +437,16 @@ BamRowsDevice* BamRowsDevice::create(int device, void* stream, size_t max_window
 BamRowsDevice::~BamRowsDevice() {
   if (device_ >= 0) (void)hipSetDevice(device_);
   if (stream_) (void)hipStreamSynchronize((hipStream_t)stream_);
-  for (void* p : {state_, cand_, link_, j0_, j1_, mark_, emit_, blk_, (void*)rows_.ref_id, (void*)rows_.pos, (void*)rows_.end,
-                  (void*)rows_.flag, (void*)rows_.h_own, (void*)rows_.h_mate, (void*)rows_.rec_off, (void*)stream_buf_})
-    if (p) (void)hipFree(p);
+  delete buf_;  // (the allocations free themselves)
 }
 
 bool BamRowsDevice::window(const uint8_t* d_win, size_t start, size_t bytes, std::string* why, uint64_t win_off) {
   hipStream_t s = (hipStream_t)stream_;
-  State* st = (State*)state_;
-  int32_t* cand = (int32_t*)cand_;
-  uint32_t *link = (uint32_t*)link_, *blk = (uint32_t*)blk_;
-  uint8_t *mark = (uint8_t*)mark_, *emit = (uint8_t*)emit_;
-  G2S_BR_TRY(hipSetDevice(device_));
+  State* st = buf_->state.as<State>();
+  int32_t* cand = buf_->cand.as<int32_t>();
+  uint32_t *link = buf_->link.as<uint32_t>(), *blk = buf_->blk.as<uint32_t>();
+  uint8_t *mark = buf_->mark.as<uint8_t>(), *emit = buf_->emit.as<uint8_t>();
+  G2S_HIP_TRY(hipSetDevice(device_));
   for (size_t ws = start; ws < bytes; ws += walk_) {
     const size_t we = std::min(ws + walk_, bytes);
     const uint32_t cap = window_capacity(we - ws);  // (at most cap_cand_)
@@ -462,8 +459,8 @@ bool BamRowsDevice::window(const uint8_t* d_win, size_t start, size_t bytes, std
     hipLaunchKernelGGL((k_flag<true>), dim3(tiles), dim3(kBlock), 0, s, d_win, (const State*)st, (int32_t)ws, (int32_t)we, n_ref_,
                        cap, blk, cand);
     hipLaunchKernelGGL(k_links, dim3(groups), dim3(kBlock), 0, s, d_win, (const State*)st, (int32_t)we, n_ref_,
-                       (const int32_t*)cand, link, (uint32_t*)j0_, mark, emit);
-    uint32_t *jin = (uint32_t*)j0_, *jout = (uint32_t*)j1_;
+                       (const int32_t*)cand, link, buf_->j0.as<uint32_t>(), mark, emit);
+    uint32_t *jin = buf_->j0.as<uint32_t>(), *jout = buf_->j1.as<uint32_t>();
     for (uint32_t r = 0; r < rounds; r++) {
       hipLaunchKernelGGL(k_round, dim3(groups), dim3(kBlock), 0, s, (const State*)st, (const uint32_t*)jin, jout, mark);
       std::swap(jin, jout);
@@ -475,7 +472,7 @@ bool BamRowsDevice::window(const uint8_t* d_win, size_t start, size_t bytes, std
     hipLaunchKernelGGL((k_rec<true>), dim3(groups), dim3(kBlock), 0, s, d_win, st, (const int32_t*)cand, (const uint32_t*)link,
                        (const uint8_t*)mark, (const uint8_t*)emit, blk, rows_.ref_id, rows_.pos, rows_.end, rows_.flag, rows_.h_own,
                        rows_.h_mate, rows_.rec_off, win_off);
-    G2S_BR_TRY(hipGetLastError());
+    G2S_HIP_TRY(hipGetLastError());
     windows_++;
   }
   return true;
@@ -483,29 +480,29 @@ bool BamRowsDevice::window(const uint8_t* d_win, size_t start, size_t bytes, std
 
 bool BamRowsDevice::carry(const uint8_t* d_win, size_t bytes, uint8_t* d_next_win, std::string* why) {
   hipStream_t s = (hipStream_t)stream_;
-  G2S_BR_TRY(hipSetDevice(device_));
-  hipLaunchKernelGGL(k_carry, dim3(64), dim3(kBlock), 0, s, d_win, (int64_t)bytes, d_next_win, (int64_t)front_, (State*)state_);
-  hipLaunchKernelGGL(k_rebase, dim3(1), dim3(1), 0, s, (State*)state_, (int64_t)bytes);
-  G2S_BR_TRY(hipGetLastError());
+  G2S_HIP_TRY(hipSetDevice(device_));
+  hipLaunchKernelGGL(k_carry, dim3(64), dim3(kBlock), 0, s, d_win, (int64_t)bytes, d_next_win, (int64_t)front_, buf_->state.as<State>());
+  hipLaunchKernelGGL(k_rebase, dim3(1), dim3(1), 0, s, buf_->state.as<State>(), (int64_t)bytes);
+  G2S_HIP_TRY(hipGetLastError());
   return true;
 }
 
 bool BamRowsDevice::advance(size_t win_end, size_t step, std::string* why) {
   hipStream_t s = (hipStream_t)stream_;
-  G2S_BR_TRY(hipSetDevice(device_));
-  hipLaunchKernelGGL(k_advance, dim3(1), dim3(1), 0, s, (State*)state_, (int64_t)win_end, (int64_t)step, (int64_t)front_);
-  G2S_BR_TRY(hipGetLastError());
+  G2S_HIP_TRY(hipSetDevice(device_));
+  hipLaunchKernelGGL(k_advance, dim3(1), dim3(1), 0, s, buf_->state.as<State>(), (int64_t)win_end, (int64_t)step, (int64_t)front_);
+  G2S_HIP_TRY(hipGetLastError());
   return true;
 }
 
 bool BamRowsDevice::finish(size_t last_bytes, int* anomaly, std::string* why) {
   hipStream_t s = (hipStream_t)stream_;
-  G2S_BR_TRY(hipSetDevice(device_));
-  hipLaunchKernelGGL(k_end, dim3(1), dim3(1), 0, s, (State*)state_, (int64_t)last_bytes);
-  G2S_BR_TRY(hipGetLastError());
+  G2S_HIP_TRY(hipSetDevice(device_));
+  hipLaunchKernelGGL(k_end, dim3(1), dim3(1), 0, s, buf_->state.as<State>(), (int64_t)last_bytes);
+  G2S_HIP_TRY(hipGetLastError());
   State h{};
-  G2S_BR_TRY(hipMemcpyAsync(&h, state_, sizeof h, hipMemcpyDeviceToHost, s));
-  G2S_BR_TRY(hipStreamSynchronize(s));
+  G2S_HIP_TRY(hipMemcpyAsync(&h, buf_->state.p, sizeof h, hipMemcpyDeviceToHost, s));
+  G2S_HIP_TRY(hipStreamSynchronize(s));
   *anomaly = (int)h.anomaly;
   rows_.n = h.base;
   rows_.max_span = (int64_t)h.max_span;
@@ -517,16 +514,14 @@ bool BamRowsDevice::finish(size_t last_bytes, int* anomaly, std::string* why) {
 bool BamRowsDevice::download(uint64_t m, int32_t* ref_id, int32_t* pos, int64_t* end, uint32_t* flag, uint64_t* h_own,
                              uint64_t* h_mate, std::string* why) const {
   if (!m) return true;
-  G2S_BR_TRY(hipSetDevice(device_));
-  G2S_BR_TRY(hipMemcpy(ref_id, rows_.ref_id, m * 4, hipMemcpyDeviceToHost));
-  G2S_BR_TRY(hipMemcpy(pos, rows_.pos, m * 4, hipMemcpyDeviceToHost));
-  G2S_BR_TRY(hipMemcpy(end, rows_.end, m * 8, hipMemcpyDeviceToHost));
-  G2S_BR_TRY(hipMemcpy(flag, rows_.flag, m * 4, hipMemcpyDeviceToHost));
-  G2S_BR_TRY(hipMemcpy(h_own, rows_.h_own, m * 8, hipMemcpyDeviceToHost));
-  G2S_BR_TRY(hipMemcpy(h_mate, rows_.h_mate, m * 8, hipMemcpyDeviceToHost));
+  G2S_HIP_TRY(hipSetDevice(device_));
+  G2S_HIP_TRY(hipMemcpy(ref_id, rows_.ref_id, m * 4, hipMemcpyDeviceToHost));
+  G2S_HIP_TRY(hipMemcpy(pos, rows_.pos, m * 4, hipMemcpyDeviceToHost));
+  G2S_HIP_TRY(hipMemcpy(end, rows_.end, m * 8, hipMemcpyDeviceToHost));
+  G2S_HIP_TRY(hipMemcpy(flag, rows_.flag, m * 4, hipMemcpyDeviceToHost));
+  G2S_HIP_TRY(hipMemcpy(h_own, rows_.h_own, m * 8, hipMemcpyDeviceToHost));
+  G2S_HIP_TRY(hipMemcpy(h_mate, rows_.h_mate, m * 8, hipMemcpyDeviceToHost));
   return true;
 }
-
-#undef G2S_BR_TRY
 
 }  // namespace g2s

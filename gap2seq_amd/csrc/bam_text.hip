@@ -25,10 +25,9 @@
 #include <utility>
 #include <vector>
 
-#include <rocprim/rocprim.hpp>
-
 #include "bam.hpp"
 #include "bam_text.h"
+#include "hip_host.h"
 
 namespace {
 
@@ -186,11 +185,6 @@ __global__ void __launch_bounds__(kBlock) k_decode(const uint8_t* __restrict__ s
   }
 }
 
-bool fail(std::string* why, const char* what, hipError_t e) {
-  if (why) *why = std::string(what) + ": " + hipGetErrorString(e);
-  return false;
-}
-
 // a piece of an Arena
 struct Buf {
   void* p = nullptr;
@@ -199,18 +193,17 @@ struct Buf {
 // one device allocation cut into pieces of 256-byte alignment (an allocation and its release cost more than the kernels
 // here): add() every piece, get(), then the pieces point into it
 struct Arena {
-  void* base = nullptr;
+  g2s::DevMem base;
   size_t bytes = 0;
   std::vector<std::pair<Buf*, size_t>> pieces;
-  ~Arena() { if (base) (void)hipFree(base); }
   void add(Buf* b, size_t n) {
     pieces.push_back({b, bytes});
     bytes += (n + 255) & ~(size_t)255;
   }
   hipError_t get() {
-    const hipError_t e = hipMalloc(&base, bytes ? bytes : 256);
+    const hipError_t e = base.alloc(bytes ? bytes : 256);
     if (e == hipSuccess)
-      for (auto& pc : pieces) pc.first->p = (uint8_t*)base + pc.second;
+      for (auto& pc : pieces) pc.first->p = base.as<uint8_t>() + pc.second;
     return e;
   }
 };
@@ -218,12 +211,6 @@ struct Arena {
 }  // namespace
 
 namespace g2s {
-
-#define G2S_BT_TRY(expr)                                  \
-  do {                                                    \
-    const hipError_t e_ = (expr);                         \
-    if (e_ != hipSuccess) return fail(why, #expr, e_);    \
-  } while (0)
 
 bool bam_text_device(const BamRowsDevice& rows, const uint8_t* sel, const BamTextAsk& ask, BamText* out, std::string* why) {
   const DeviceRows& R = rows.rows();
@@ -237,14 +224,13 @@ bool bam_text_device(const BamRowsDevice& rows, const uint8_t* sel, const BamTex
   else { out->toff.assign((size_t)n, 0); out->tlen.assign((size_t)n, 0); }
   if (!n) return true;
   hipStream_t s = (hipStream_t)rows.stream();
-  G2S_BT_TRY(hipSetDevice(rows.device()));
+  G2S_HIP_TRY(hipSetDevice(rows.device()));
   const size_t m = (size_t)n + 1;
   const unsigned groups = (unsigned)((m + kBlock - 1) / kBlock);
   Buf d_sel, d_len_a, d_len_b, d_held, d_un, d_off_a, d_off_b, d_idx, d_uidx, d_tot, d_tmp;
-  size_t tb64 = 0, tb32 = 0;  // (a size query reads no array)
-  G2S_BT_TRY(rocprim::exclusive_scan(nullptr, tb64, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint64_t)0, m,
-                                     rocprim::plus<uint64_t>(), s));
-  G2S_BT_TRY(rocprim::exclusive_scan(nullptr, tb32, (uint32_t*)nullptr, (uint32_t*)nullptr, 0u, m, rocprim::plus<uint32_t>(), s));
+  size_t tb64 = 0, tb32 = 0;
+  G2S_HIP_TRY(exclusive_scan_bytes<uint64_t>(m, &tb64, s));
+  G2S_HIP_TRY(exclusive_scan_bytes<uint32_t>(m, &tb32, s));
   const size_t tb = tb64 > tb32 ? tb64 : tb32;
   Arena work;
   work.add(&d_sel, (size_t)n);
@@ -258,27 +244,27 @@ bool bam_text_device(const BamRowsDevice& rows, const uint8_t* sel, const BamTex
   work.add(&d_uidx, m * 4);
   work.add(&d_tot, sizeof(Totals));
   work.add(&d_tmp, tb);
-  G2S_BT_TRY(work.get());
-  G2S_BT_TRY(hipMemcpyAsync(d_sel.p, sel, (size_t)n, hipMemcpyHostToDevice, s));
-  G2S_BT_TRY(hipMemsetAsync(d_tot.p, 0, sizeof(Totals), s));
+  G2S_HIP_TRY(work.get());
+  G2S_HIP_TRY(hipMemcpyAsync(d_sel.p, sel, (size_t)n, hipMemcpyHostToDevice, s));
+  G2S_HIP_TRY(hipMemsetAsync(d_tot.p, 0, sizeof(Totals), s));
   hipLaunchKernelGGL(k_lengths, dim3(groups), dim3(kBlock), 0, s, (const uint8_t*)rows.stream_buffer(), rows.stream_bytes(),
                      (const uint64_t*)R.rec_off, n, d_sel.as<const uint8_t>(), (int)ask.pool, (int)ask.names, (int)ask.unmapped,
                      d_len_a.as<uint64_t>(), d_len_b.as<uint64_t>(), d_held.as<uint32_t>(), d_un.as<uint32_t>(), d_tot.as<Totals>());
-  G2S_BT_TRY(hipGetLastError());
+  G2S_HIP_TRY(hipGetLastError());
   // ---- the offsets
-  size_t tb_a = tb, tb_b = tb, tb_h = tb, tb_u = tb;  // (the calls take the size by reference)
-  G2S_BT_TRY(rocprim::exclusive_scan(d_tmp.p, tb_a, d_len_a.as<uint64_t>(), d_off_a.as<uint64_t>(), (uint64_t)0, m,
-                                     rocprim::plus<uint64_t>(), s));
-  G2S_BT_TRY(rocprim::exclusive_scan(d_tmp.p, tb_b, d_len_b.as<uint64_t>(), d_off_b.as<uint64_t>(), (uint64_t)0, m,
-                                     rocprim::plus<uint64_t>(), s));
-  G2S_BT_TRY(rocprim::exclusive_scan(d_tmp.p, tb_h, d_held.as<uint32_t>(), d_idx.as<uint32_t>(), 0u, m, rocprim::plus<uint32_t>(), s));
-  G2S_BT_TRY(rocprim::exclusive_scan(d_tmp.p, tb_u, d_un.as<uint32_t>(), d_uidx.as<uint32_t>(), 0u, m, rocprim::plus<uint32_t>(), s));
+  Scratch tmp;  // (the arena's piece serves all four)
+  tmp.p = d_tmp.p;
+  tmp.bytes = tb;
+  G2S_HIP_TRY(exclusive_scan(tmp, d_len_a.as<uint64_t>(), d_off_a.as<uint64_t>(), m, s));
+  G2S_HIP_TRY(exclusive_scan(tmp, d_len_b.as<uint64_t>(), d_off_b.as<uint64_t>(), m, s));
+  G2S_HIP_TRY(exclusive_scan(tmp, d_held.as<uint32_t>(), d_idx.as<uint32_t>(), m, s));
+  G2S_HIP_TRY(exclusive_scan(tmp, d_un.as<uint32_t>(), d_uidx.as<uint32_t>(), m, s));
   hipLaunchKernelGGL(k_totals, dim3(1), dim3(1), 0, s, n, d_off_a.as<const uint64_t>(), d_off_b.as<const uint64_t>(),
                      d_idx.as<const uint32_t>(), d_uidx.as<const uint32_t>(), d_tot.as<Totals>());
-  G2S_BT_TRY(hipGetLastError());
+  G2S_HIP_TRY(hipGetLastError());
   Totals tot{};
-  G2S_BT_TRY(hipMemcpyAsync(&tot, d_tot.p, sizeof tot, hipMemcpyDeviceToHost, s));
-  G2S_BT_TRY(hipStreamSynchronize(s));
+  G2S_HIP_TRY(hipMemcpyAsync(&tot, d_tot.p, sizeof tot, hipMemcpyDeviceToHost, s));
+  G2S_HIP_TRY(hipStreamSynchronize(s));
   const uint64_t bytes_a = tot.bytes_a, bytes_b = tot.bytes_b;
   const uint32_t n_held = tot.n_held, n_un = tot.n_un;
   if (tot.bad) {
@@ -296,7 +282,7 @@ bool bam_text_device(const BamRowsDevice& rows, const uint8_t* sel, const BamTex
     outs.add(&d_unl, (size_t)n_un * 4);
     outs.add(&d_pidx, (size_t)n * 4);
   }
-  G2S_BT_TRY(outs.get());
+  G2S_HIP_TRY(outs.get());
   const unsigned waves_wanted = (unsigned)((n + kWave - 1) / kWave);
   const unsigned dgroups = std::max(1u, std::min((waves_wanted + kBlock / kWave - 1) / (kBlock / kWave), 256u * 16u));
   if (ask.pool) {
@@ -312,31 +298,31 @@ bool bam_text_device(const BamRowsDevice& rows, const uint8_t* sel, const BamTex
                        (const uint64_t*)R.rec_off, n, d_off_a.as<const uint64_t>(), d_off_b.as<const uint64_t>(),
                        d_out_a.as<uint8_t>(), bytes_a, d_out_b.as<uint8_t>(), bytes_b);
   }
-  G2S_BT_TRY(hipGetLastError());
+  G2S_HIP_TRY(hipGetLastError());
   // ---- down, once
   if (ask.pool) {
     out->pbases.resize((size_t)bytes_a);
     out->pboff.assign((size_t)n_held + 1, 0);
     out->punmapped.assign((size_t)n_un, 0);
-    if (bytes_a) G2S_BT_TRY(hipMemcpyAsync(&out->pbases[0], d_out_a.p, (size_t)bytes_a, hipMemcpyDeviceToHost, s));
-    G2S_BT_TRY(hipMemcpyAsync(out->pboff.data(), d_boff.p, ((size_t)n_held + 1) * 8, hipMemcpyDeviceToHost, s));
-    if (n_un) G2S_BT_TRY(hipMemcpyAsync(out->punmapped.data(), d_unl.p, (size_t)n_un * 4, hipMemcpyDeviceToHost, s));
-    G2S_BT_TRY(hipMemcpyAsync(out->pidx.data(), d_pidx.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+    if (bytes_a) G2S_HIP_TRY(hipMemcpyAsync(&out->pbases[0], d_out_a.p, (size_t)bytes_a, hipMemcpyDeviceToHost, s));
+    G2S_HIP_TRY(hipMemcpyAsync(out->pboff.data(), d_boff.p, ((size_t)n_held + 1) * 8, hipMemcpyDeviceToHost, s));
+    if (n_un) G2S_HIP_TRY(hipMemcpyAsync(out->punmapped.data(), d_unl.p, (size_t)n_un * 4, hipMemcpyDeviceToHost, s));
+    G2S_HIP_TRY(hipMemcpyAsync(out->pidx.data(), d_pidx.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
     if (ask.names) {
       out->pnames.resize((size_t)bytes_b);
       out->pnoff.assign((size_t)n_held + 1, 0);
-      if (bytes_b) G2S_BT_TRY(hipMemcpyAsync(&out->pnames[0], d_out_b.p, (size_t)bytes_b, hipMemcpyDeviceToHost, s));
-      G2S_BT_TRY(hipMemcpyAsync(out->pnoff.data(), d_noff.p, ((size_t)n_held + 1) * 8, hipMemcpyDeviceToHost, s));
+      if (bytes_b) G2S_HIP_TRY(hipMemcpyAsync(&out->pnames[0], d_out_b.p, (size_t)bytes_b, hipMemcpyDeviceToHost, s));
+      G2S_HIP_TRY(hipMemcpyAsync(out->pnoff.data(), d_noff.p, ((size_t)n_held + 1) * 8, hipMemcpyDeviceToHost, s));
     }
-    G2S_BT_TRY(hipStreamSynchronize(s));
+    G2S_HIP_TRY(hipStreamSynchronize(s));
   } else {
     std::vector<uint64_t> off(m);
     out->text.resize((size_t)bytes_a);
     out->unmapped.resize((size_t)bytes_b);
-    if (bytes_a) G2S_BT_TRY(hipMemcpyAsync(&out->text[0], d_out_a.p, (size_t)bytes_a, hipMemcpyDeviceToHost, s));
-    if (bytes_b) G2S_BT_TRY(hipMemcpyAsync(&out->unmapped[0], d_out_b.p, (size_t)bytes_b, hipMemcpyDeviceToHost, s));
-    G2S_BT_TRY(hipMemcpyAsync(off.data(), d_off_a.p, m * 8, hipMemcpyDeviceToHost, s));
-    G2S_BT_TRY(hipStreamSynchronize(s));
+    if (bytes_a) G2S_HIP_TRY(hipMemcpyAsync(&out->text[0], d_out_a.p, (size_t)bytes_a, hipMemcpyDeviceToHost, s));
+    if (bytes_b) G2S_HIP_TRY(hipMemcpyAsync(&out->unmapped[0], d_out_b.p, (size_t)bytes_b, hipMemcpyDeviceToHost, s));
+    G2S_HIP_TRY(hipMemcpyAsync(off.data(), d_off_a.p, m * 8, hipMemcpyDeviceToHost, s));
+    G2S_HIP_TRY(hipStreamSynchronize(s));
     for (size_t r = 0; r < (size_t)n; r++)
       if (sel[r]) {  // (a row nothing selected keeps offset and length 0, as on the host walk)
         out->toff[r] = off[r];
@@ -346,7 +332,5 @@ bool bam_text_device(const BamRowsDevice& rows, const uint8_t* sel, const BamTex
   }
   return true;
 }
-
-#undef G2S_BT_TRY
 
 }  // namespace g2s

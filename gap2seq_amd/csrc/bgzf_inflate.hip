@@ -24,6 +24,7 @@
 #include <string>
 
 #include "bgzf_inflate.h"
+#include "hip_host.h"
 #include "inflate_core.h"
 #include "readfilter_gaps.hpp"
 
@@ -134,19 +135,6 @@ __global__ void __launch_bounds__(64) g2s_bgzf_inflate(const uint8_t* __restrict
 
 namespace g2s {
 
-namespace {
-bool fail(std::string* why, const char* what, hipError_t e) {
-  if (why) *why = std::string(what) + ": " + hipGetErrorString(e);
-  return false;
-}
-}  // namespace
-
-#define G2S_BZ_TRY(expr)                                       \
-  do {                                                         \
-    const hipError_t e_ = (expr);                              \
-    if (e_ != hipSuccess) return fail(why, #expr, e_);         \
-  } while (0)
-
 BgzfDevice* BgzfDevice::create(int device, size_t max_in, size_t max_out, size_t max_members, size_t front, std::string* why) {
   if (!filter_device_usable(device)) {
     if (why) *why = "no usable gfx950 device " + std::to_string(device);
@@ -159,21 +147,21 @@ BgzfDevice* BgzfDevice::create(int device, size_t max_in, size_t max_out, size_t
   D->cap_out_ = max_out;
   D->cap_members_ = max_members;
   auto make = [&]() -> bool {
-    G2S_BZ_TRY(hipSetDevice(device));
+    G2S_HIP_TRY(hipSetDevice(device));
     hipStream_t st;
-    G2S_BZ_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+    G2S_HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
     D->stream_ = st;
     for (Slot& s : D->s_) {
-      G2S_BZ_TRY(hipHostMalloc((void**)&s.h_in, max_in + 16, hipHostMallocDefault));
-      G2S_BZ_TRY(hipHostMalloc((void**)&s.h_out, front + max_out + 16, hipHostMallocDefault));
-      G2S_BZ_TRY(hipHostMalloc((void**)&s.h_mem, (max_members + 1) * sizeof(BgzfMember), hipHostMallocDefault));
-      G2S_BZ_TRY(hipHostMalloc((void**)&s.h_st, (max_members + 1) * 4, hipHostMallocDefault));
-      G2S_BZ_TRY(hipMalloc((void**)&s.d_in, max_in + 16));
-      G2S_BZ_TRY(hipMalloc((void**)&s.d_out, front + max_out + 64));
-      G2S_BZ_TRY(hipMalloc((void**)&s.d_mem, (max_members + 1) * sizeof(BgzfMember)));
-      G2S_BZ_TRY(hipMalloc((void**)&s.d_st, (max_members + 1) * 4));
+      G2S_HIP_TRY(hipHostMalloc((void**)&s.h_in, max_in + 16, hipHostMallocDefault));
+      G2S_HIP_TRY(hipHostMalloc((void**)&s.h_out, front + max_out + 16, hipHostMallocDefault));
+      G2S_HIP_TRY(hipHostMalloc((void**)&s.h_mem, (max_members + 1) * sizeof(BgzfMember), hipHostMallocDefault));
+      G2S_HIP_TRY(hipHostMalloc((void**)&s.h_st, (max_members + 1) * 4, hipHostMallocDefault));
+      G2S_HIP_TRY(hipMalloc((void**)&s.d_in, max_in + 16));
+      G2S_HIP_TRY(hipMalloc((void**)&s.d_out, front + max_out + 64));
+      G2S_HIP_TRY(hipMalloc((void**)&s.d_mem, (max_members + 1) * sizeof(BgzfMember)));
+      G2S_HIP_TRY(hipMalloc((void**)&s.d_st, (max_members + 1) * 4));
       hipEvent_t ev;
-      G2S_BZ_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+      G2S_HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
       s.done = ev;
     }
     return true;
@@ -214,19 +202,19 @@ bool BgzfDevice::launch(int slot, size_t n_members, size_t in_bytes, size_t out_
     if (why) *why = "a window with a destination of its own is not copied down";
     return false;
   }
-  G2S_BZ_TRY(hipSetDevice(device_));
+  G2S_HIP_TRY(hipSetDevice(device_));
   if (n_members && out_bytes) {
-    if (in_bytes) G2S_BZ_TRY(hipMemcpyAsync(s.d_in, s.h_in, in_bytes, hipMemcpyHostToDevice, st));
-    G2S_BZ_TRY(hipMemcpyAsync(s.d_mem, s.h_mem, n_members * sizeof(BgzfMember), hipMemcpyHostToDevice, st));
+    if (in_bytes) G2S_HIP_TRY(hipMemcpyAsync(s.d_in, s.h_in, in_bytes, hipMemcpyHostToDevice, st));
+    G2S_HIP_TRY(hipMemcpyAsync(s.d_mem, s.h_mem, n_members * sizeof(BgzfMember), hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(g2s_bgzf_inflate, dim3((unsigned)n_members), dim3(kWave), 0, st, (const uint8_t*)s.d_in,
                        (const BgzfMember*)s.d_mem, (uint32_t)n_members, d_dst ? d_dst : s.d_out + front_, s.d_st);
-    G2S_BZ_TRY(hipGetLastError());
-    if (down) G2S_BZ_TRY(hipMemcpyAsync(s.h_out + front_, s.d_out + front_, out_bytes, hipMemcpyDeviceToHost, st));
-    G2S_BZ_TRY(hipMemcpyAsync(s.h_st, s.d_st, n_members * 4, hipMemcpyDeviceToHost, st));
+    G2S_HIP_TRY(hipGetLastError());
+    if (down) G2S_HIP_TRY(hipMemcpyAsync(s.h_out + front_, s.d_out + front_, out_bytes, hipMemcpyDeviceToHost, st));
+    G2S_HIP_TRY(hipMemcpyAsync(s.h_st, s.d_st, n_members * 4, hipMemcpyDeviceToHost, st));
   } else {
     memset(s.h_st, 0, n_members * 4);  // (members without bytes succeed: inflate_core.h kOk)
   }
-  G2S_BZ_TRY(hipEventRecord((hipEvent_t)s.done, st));
+  G2S_HIP_TRY(hipEventRecord((hipEvent_t)s.done, st));
   s.busy = true;
   return true;
 }
@@ -235,11 +223,9 @@ bool BgzfDevice::wait(int slot, std::string* why) {
   Slot& s = s_[slot];
   if (!s.busy) return true;
   s.busy = false;
-  G2S_BZ_TRY(hipSetDevice(device_));
-  G2S_BZ_TRY(hipEventSynchronize((hipEvent_t)s.done));
+  G2S_HIP_TRY(hipSetDevice(device_));
+  G2S_HIP_TRY(hipEventSynchronize((hipEvent_t)s.done));
   return true;
 }
-
-#undef G2S_BZ_TRY
 
 }  // namespace g2s

@@ -37,9 +37,8 @@
 #include <string>
 #include <vector>
 
-#include <rocprim/rocprim.hpp>
-
 #include "dbg.hpp"
+#include "hip_host.h"
 
 namespace {
 
@@ -772,13 +771,6 @@ __global__ void k_reach_copy_kept(const KT* __restrict__ sk, const uint32_t* __r
   ncnt[d] = solid;
 }
 
-struct Dev {
-  void* p = nullptr;
-  ~Dev() { if (p) (void)hipFree(p); }
-  hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
-  void* release() { void* q = p; p = nullptr; return q; }
-};
-
 }  // namespace
 
 namespace g2s {
@@ -793,97 +785,85 @@ template <class KT, bool EVEN>
 static bool finish_gpu_e(Graph& g, const std::vector<KT>& kmers, int device,
                          const std::function<void(const std::vector<uint32_t>&, uint32_t)>& host_walk, std::string* why,
                          const std::vector<uint32_t>* rank_set) {
-#define G2S_GPU_TRY(expr)                                                                 \
-  do {                                                                                    \
-    hipError_t e_ = (expr);                                                               \
-    if (e_ != hipSuccess) { if (why) *why = std::string(#expr) + ": " + hipGetErrorString(e_); return false; } \
-  } while (0)
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) { if (why) *why = "no device"; return false; }
+  if (!device_exists(device)) { if (why) *why = "no device"; return false; }
   const uint64_t n = g.n;
   if (n == 0 || 2 * n >= (1ull << 31)) { if (why) *why = "size"; return false; }
-  G2S_GPU_TRY(hipSetDevice(device));
+  G2S_HIP_TRY(hipSetDevice(device));
   const uint32_t n2 = (uint32_t)(2 * n);
   const int k = g.k;
   const dim3 blk(256), grd((n2 + 255) / 256);
-  Dev d_km, d_bucket, d_succ, d_pred, d_nxt, d_pd0, d_pd1, d_len, d_tail, d_cnt, d_base, d_id, d_flip, d_flag, d_tmp;
+  DevMem d_km, d_bucket, d_succ, d_pred, d_nxt, d_pd0, d_pd1, d_len, d_tail, d_cnt, d_base, d_id, d_flip, d_flag;
+  Scratch d_tmp;
   // ---- successor table, rank space (even k: the predecessor table beside it; odd k allocates and writes none)
-  G2S_GPU_TRY(d_km.alloc(kmers.size() * sizeof(KT)));
-  G2S_GPU_TRY(d_succ.alloc((size_t)n2 * 16));
-  if constexpr (EVEN) G2S_GPU_TRY(d_pred.alloc((size_t)n2 * 16));
-  G2S_GPU_TRY(hipMemcpy(d_km.p, kmers.data(), kmers.size() * sizeof(KT), hipMemcpyHostToDevice));
+  G2S_HIP_TRY(d_km.alloc(kmers.size() * sizeof(KT)));
+  G2S_HIP_TRY(d_succ.alloc((size_t)n2 * 16));
+  if constexpr (EVEN) G2S_HIP_TRY(d_pred.alloc((size_t)n2 * 16));
+  G2S_HIP_TRY(hipMemcpy(d_km.p, kmers.data(), kmers.size() * sizeof(KT), hipMemcpyHostToDevice));
   if (rank_set) {  // set graph: every neighbour searched in its own set's range (g.set_lo)
-    Dev d_rs, d_sl;
+    DevMem d_rs, d_sl;
     std::vector<uint32_t> lo32(g.set_lo.begin(), g.set_lo.end());
-    G2S_GPU_TRY(d_rs.alloc((size_t)n * 4));
-    G2S_GPU_TRY(d_sl.alloc(lo32.size() * 4));
-    G2S_GPU_TRY(hipMemcpy(d_rs.p, rank_set->data(), (size_t)n * 4, hipMemcpyHostToDevice));
-    G2S_GPU_TRY(hipMemcpy(d_sl.p, lo32.data(), lo32.size() * 4, hipMemcpyHostToDevice));
+    G2S_HIP_TRY(d_rs.alloc((size_t)n * 4));
+    G2S_HIP_TRY(d_sl.alloc(lo32.size() * 4));
+    G2S_HIP_TRY(hipMemcpy(d_rs.p, rank_set->data(), (size_t)n * 4, hipMemcpyHostToDevice));
+    G2S_HIP_TRY(hipMemcpy(d_sl.p, lo32.data(), lo32.size() * 4, hipMemcpyHostToDevice));
     hipLaunchKernelGGL((k_succ_set<KT, EVEN>), grd, blk, 0, 0, (const KT*)d_km.p, (const uint32_t*)d_rs.p, (const uint32_t*)d_sl.p, n2,
                        k, (uint32_t*)d_succ.p, (uint32_t*)d_pred.p);
-    G2S_GPU_TRY(hipDeviceSynchronize());
+    G2S_HIP_TRY(hipDeviceSynchronize());
   } else {
-    G2S_GPU_TRY(d_bucket.alloc(g.bucket.size() * 4));
-    G2S_GPU_TRY(hipMemcpy(d_bucket.p, g.bucket.data(), g.bucket.size() * 4, hipMemcpyHostToDevice));
+    G2S_HIP_TRY(d_bucket.alloc(g.bucket.size() * 4));
+    G2S_HIP_TRY(hipMemcpy(d_bucket.p, g.bucket.data(), g.bucket.size() * 4, hipMemcpyHostToDevice));
     hipLaunchKernelGGL((k_succ<KT, EVEN>), grd, blk, 0, 0, (const KT*)d_km.p, (const uint32_t*)d_bucket.p, 2 * k - g.bucket_bits, n2,
                        k, (uint32_t*)d_succ.p, (uint32_t*)d_pred.p);
   }
   // ---- numbering along unitigs: list ranking
-  G2S_GPU_TRY(d_nxt.alloc((size_t)n2 * 4));
-  G2S_GPU_TRY(d_pd0.alloc((size_t)n2 * 8));
-  G2S_GPU_TRY(d_pd1.alloc((size_t)n2 * 8));
-  G2S_GPU_TRY(d_len.alloc((size_t)n2 * 4));
-  G2S_GPU_TRY(d_tail.alloc((size_t)n2 * 4));
-  G2S_GPU_TRY(d_cnt.alloc((size_t)n2 * 4));
-  G2S_GPU_TRY(d_base.alloc((size_t)n2 * 4));
-  G2S_GPU_TRY(d_id.alloc((size_t)n * 4));
-  G2S_GPU_TRY(d_flip.alloc((size_t)n));
-  G2S_GPU_TRY(d_flag.alloc(16));
-  G2S_GPU_TRY(hipMemset(d_len.p, 0, (size_t)n2 * 4));
-  G2S_GPU_TRY(hipMemset(d_tail.p, 0, (size_t)n2 * 4));
-  G2S_GPU_TRY(hipMemset(d_id.p, 0xFF, (size_t)n * 4));
-  G2S_GPU_TRY(hipMemset(d_flip.p, 0, (size_t)n));
+  G2S_HIP_TRY(d_nxt.alloc((size_t)n2 * 4));
+  G2S_HIP_TRY(d_pd0.alloc((size_t)n2 * 8));
+  G2S_HIP_TRY(d_pd1.alloc((size_t)n2 * 8));
+  G2S_HIP_TRY(d_len.alloc((size_t)n2 * 4));
+  G2S_HIP_TRY(d_tail.alloc((size_t)n2 * 4));
+  G2S_HIP_TRY(d_cnt.alloc((size_t)n2 * 4));
+  G2S_HIP_TRY(d_base.alloc((size_t)n2 * 4));
+  G2S_HIP_TRY(d_id.alloc((size_t)n * 4));
+  G2S_HIP_TRY(d_flip.alloc((size_t)n));
+  G2S_HIP_TRY(d_flag.alloc(16));
+  G2S_HIP_TRY(hipMemset(d_len.p, 0, (size_t)n2 * 4));
+  G2S_HIP_TRY(hipMemset(d_tail.p, 0, (size_t)n2 * 4));
+  G2S_HIP_TRY(hipMemset(d_id.p, 0xFF, (size_t)n * 4));
+  G2S_HIP_TRY(hipMemset(d_flip.p, 0, (size_t)n));
   hipLaunchKernelGGL(k_next, grd, blk, 0, 0, (const uint32_t*)d_succ.p, n2, (uint32_t*)d_nxt.p);
   hipLaunchKernelGGL(k_init, grd, blk, 0, 0, (const uint32_t*)d_nxt.p, n2, (uint64_t*)d_pd0.p);
   uint64_t *cur = (uint64_t*)d_pd0.p, *oth = (uint64_t*)d_pd1.p;
   for (int round = 0; round < 34; round++) {  // 2^32 > any chain; cycles never settle and stop here
-    G2S_GPU_TRY(hipMemset(d_flag.p, 0, 4));
+    G2S_HIP_TRY(hipMemset(d_flag.p, 0, 4));
     hipLaunchKernelGGL(k_jump, grd, blk, 0, 0, (const uint64_t*)cur, oth, n2, (uint32_t*)d_flag.p);
     uint32_t changed = 0;
-    G2S_GPU_TRY(hipMemcpy(&changed, d_flag.p, 4, hipMemcpyDeviceToHost));
+    G2S_HIP_TRY(hipMemcpy(&changed, d_flag.p, 4, hipMemcpyDeviceToHost));
     std::swap(cur, oth);
     if (!changed) break;
   }
   hipLaunchKernelGGL(k_tail, grd, blk, 0, 0, (const uint32_t*)d_nxt.p, (const uint64_t*)cur, n2, (uint32_t*)d_len.p,
                      (uint32_t*)d_tail.p);
-  G2S_GPU_TRY(hipMemset(d_flag.p, 0, 4));
+  G2S_HIP_TRY(hipMemset(d_flag.p, 0, 4));
   hipLaunchKernelGGL(k_keep<EVEN>, grd, blk, 0, 0, (const uint32_t*)d_len.p, (const uint32_t*)d_tail.p, n2, (uint32_t*)d_cnt.p,
                      (uint32_t*)d_flag.p, (const uint32_t*)d_succ.p);
-  size_t tmp_bytes = 0;
-  G2S_GPU_TRY(rocprim::exclusive_scan(nullptr, tmp_bytes, (const uint32_t*)d_cnt.p, (uint32_t*)d_base.p, 0u, (size_t)n2,
-                                      rocprim::plus<uint32_t>()));
-  G2S_GPU_TRY(d_tmp.alloc(tmp_bytes));
-  G2S_GPU_TRY(rocprim::exclusive_scan(d_tmp.p, tmp_bytes, (const uint32_t*)d_cnt.p, (uint32_t*)d_base.p, 0u, (size_t)n2,
-                                      rocprim::plus<uint32_t>()));
+  G2S_HIP_TRY(exclusive_scan(d_tmp, (const uint32_t*)d_cnt.p, (uint32_t*)d_base.p, (size_t)n2));
   hipLaunchKernelGGL(k_assign, grd, blk, 0, 0, (const uint64_t*)cur, (const uint32_t*)d_cnt.p, (const uint32_t*)d_base.p, n2,
                      (uint32_t*)d_id.p, (uint8_t*)d_flip.p);
-  G2S_GPU_TRY(hipGetLastError());
-  uint32_t kept = 0, last_base = 0, last_cnt = 0;
-  G2S_GPU_TRY(hipMemcpy(&kept, d_flag.p, 4, hipMemcpyDeviceToHost));
-  G2S_GPU_TRY(hipMemcpy(&last_base, (const uint32_t*)d_base.p + (n2 - 1), 4, hipMemcpyDeviceToHost));
-  G2S_GPU_TRY(hipMemcpy(&last_cnt, (const uint32_t*)d_cnt.p + (n2 - 1), 4, hipMemcpyDeviceToHost));
-  const uint32_t next_id = last_base + last_cnt;  // ids handed out so far
+  G2S_HIP_TRY(hipGetLastError());
+  uint32_t kept = 0, next_id = 0;  // next_id: the ids handed out so far
+  G2S_HIP_TRY(hipMemcpy(&kept, d_flag.p, 4, hipMemcpyDeviceToHost));
+  G2S_HIP_TRY(read_total((const uint32_t*)d_cnt.p, (const uint32_t*)d_base.p, (size_t)n2, &next_id));
   // free the ranking scratch before the id-space tables are allocated
-  for (Dev* d : {&d_nxt, &d_pd0, &d_pd1, &d_len, &d_tail, &d_cnt, &d_base, &d_tmp}) { if (d->p) (void)hipFree(d->release()); }
+  d_nxt.free(); d_pd0.free(); d_pd1.free(); d_len.free(); d_tail.free(); d_cnt.free(); d_base.free(); d_tmp.free();
   // ---- everything that can still fail is done: from here on g is written
   g.rank2id.assign((size_t)n, kInvalidNode);
   g.flip.assign((size_t)n, 0);
   g.n_unitigs = kept;
   if (next_id < n) {  // circular unitigs: the host walk numbers them after the rest
     std::vector<uint32_t> succ_r((size_t)n2 * 4);
-    G2S_GPU_TRY(hipMemcpy(succ_r.data(), d_succ.p, (size_t)n2 * 16, hipMemcpyDeviceToHost));
-    G2S_GPU_TRY(hipMemcpy(g.rank2id.data(), d_id.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-    G2S_GPU_TRY(hipMemcpy(g.flip.data(), d_flip.p, (size_t)n, hipMemcpyDeviceToHost));
+    G2S_HIP_TRY(hipMemcpy(succ_r.data(), d_succ.p, (size_t)n2 * 16, hipMemcpyDeviceToHost));
+    G2S_HIP_TRY(hipMemcpy(g.rank2id.data(), d_id.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+    G2S_HIP_TRY(hipMemcpy(g.flip.data(), d_flip.p, (size_t)n, hipMemcpyDeviceToHost));
     host_walk(succ_r, next_id);
     if (rank_set) {
       // Set graphs: the walk numbered the circular unitigs after every set; each moves to the end of its own set's
@@ -895,41 +875,41 @@ static bool finish_gpu_e(Graph& g, const std::vector<KT>& kmers, int device,
       for (uint64_t id = 0; id < n; id++) new_id[(size_t)id] = fill[id_set[(size_t)id]]++;
       for (uint64_t r = 0; r < n; r++) g.rank2id[(size_t)r] = new_id[g.rank2id[(size_t)r]];
     }
-    G2S_GPU_TRY(hipMemcpy(d_id.p, g.rank2id.data(), (size_t)n * 4, hipMemcpyHostToDevice));
-    G2S_GPU_TRY(hipMemcpy(d_flip.p, g.flip.data(), (size_t)n, hipMemcpyHostToDevice));
+    G2S_HIP_TRY(hipMemcpy(d_id.p, g.rank2id.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+    G2S_HIP_TRY(hipMemcpy(d_flip.p, g.flip.data(), (size_t)n, hipMemcpyHostToDevice));
   }
   // ---- tables in id space
-  Dev d_sid, d_pid, d_last, d_i2r, d_us;
+  DevMem d_sid, d_pid, d_last, d_i2r, d_us;
   const size_t sbytes = (size_t)n2 * 16;
-  if constexpr (EVEN) G2S_GPU_TRY(d_pid.alloc(sbytes));
+  if constexpr (EVEN) G2S_HIP_TRY(d_pid.alloc(sbytes));
   const size_t words = (size_t)((n + 63) / 64 + 1);
-  G2S_GPU_TRY(d_sid.alloc(sbytes + 1024));  // the LDS tier may read past the end: INVALID padding
-  G2S_GPU_TRY(hipMemset(d_sid.p, 0xFF, sbytes + 1024));
-  G2S_GPU_TRY(d_last.alloc((size_t)n2));
-  G2S_GPU_TRY(d_i2r.alloc((size_t)n * 4));
-  G2S_GPU_TRY(d_us.alloc((words + 2 * kUstartPad) * 8));
-  G2S_GPU_TRY(hipMemset(d_us.p, 0xFF, (words + 2 * kUstartPad) * 8));
+  G2S_HIP_TRY(d_sid.alloc(sbytes + 1024));  // the LDS tier may read past the end: INVALID padding
+  G2S_HIP_TRY(hipMemset(d_sid.p, 0xFF, sbytes + 1024));
+  G2S_HIP_TRY(d_last.alloc((size_t)n2));
+  G2S_HIP_TRY(d_i2r.alloc((size_t)n * 4));
+  G2S_HIP_TRY(d_us.alloc((words + 2 * kUstartPad) * 8));
+  G2S_HIP_TRY(hipMemset(d_us.p, 0xFF, (words + 2 * kUstartPad) * 8));
   hipLaunchKernelGGL((k_remap<KT, EVEN>), grd, blk, 0, 0, (const KT*)d_km.p, (const uint32_t*)d_succ.p, (const uint32_t*)d_pred.p,
                      (const uint32_t*)d_id.p, (const uint8_t*)d_flip.p, n2, k, (uint32_t*)d_sid.p, (uint32_t*)d_pid.p,
                      (uint8_t*)d_last.p, (uint32_t*)d_i2r.p);
   const uint32_t nbits = (uint32_t)(words * 64);
   hipLaunchKernelGGL(k_ustart, dim3((nbits + 255) / 256), blk, 0, 0, (const uint32_t*)d_sid.p, (uint32_t)n, nbits,
                      (uint64_t*)d_us.p + kUstartPad);
-  G2S_GPU_TRY(hipGetLastError());
+  G2S_HIP_TRY(hipGetLastError());
   g.succ.resize((size_t)n2 * 4);
   g.pred.clear();
   if constexpr (EVEN) g.pred.resize((size_t)n2 * 4);
   g.lastnt.resize((size_t)n2);
   g.id2rank.resize((size_t)n);
   g.ustart.resize(words);
-  G2S_GPU_TRY(hipMemcpy(g.succ.data(), d_sid.p, sbytes, hipMemcpyDeviceToHost));
-  if constexpr (EVEN) G2S_GPU_TRY(hipMemcpy(g.pred.data(), d_pid.p, sbytes, hipMemcpyDeviceToHost));
-  G2S_GPU_TRY(hipMemcpy(g.lastnt.data(), d_last.p, (size_t)n2, hipMemcpyDeviceToHost));
-  G2S_GPU_TRY(hipMemcpy(g.id2rank.data(), d_i2r.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-  G2S_GPU_TRY(hipMemcpy(g.ustart.data(), (uint64_t*)d_us.p + kUstartPad, words * 8, hipMemcpyDeviceToHost));
+  G2S_HIP_TRY(hipMemcpy(g.succ.data(), d_sid.p, sbytes, hipMemcpyDeviceToHost));
+  if constexpr (EVEN) G2S_HIP_TRY(hipMemcpy(g.pred.data(), d_pid.p, sbytes, hipMemcpyDeviceToHost));
+  G2S_HIP_TRY(hipMemcpy(g.lastnt.data(), d_last.p, (size_t)n2, hipMemcpyDeviceToHost));
+  G2S_HIP_TRY(hipMemcpy(g.id2rank.data(), d_i2r.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+  G2S_HIP_TRY(hipMemcpy(g.ustart.data(), (uint64_t*)d_us.p + kUstartPad, words * 8, hipMemcpyDeviceToHost));
   if (next_id >= n) {
-    G2S_GPU_TRY(hipMemcpy(g.rank2id.data(), d_id.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-    G2S_GPU_TRY(hipMemcpy(g.flip.data(), d_flip.p, (size_t)n, hipMemcpyDeviceToHost));
+    G2S_HIP_TRY(hipMemcpy(g.rank2id.data(), d_id.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+    G2S_HIP_TRY(hipMemcpy(g.flip.data(), d_flip.p, (size_t)n, hipMemcpyDeviceToHost));
   }
   // the device copy of the graph for the fill path
   DeviceGraph dg;
@@ -942,7 +922,6 @@ static bool finish_gpu_e(Graph& g, const std::vector<KT>& kmers, int device,
   }
   g.dev[device] = dg;
   return true;
-#undef G2S_GPU_TRY
 }
 
 template <class KT>
@@ -961,20 +940,14 @@ static bool finish_gpu_t(Graph& g, const std::vector<KT>& kmers, int device,
 template <class KT>
 static bool count_solid_gpu_t(Graph& g, std::vector<KT>& out, const std::vector<std::pair<const char*, uint64_t>>& seqs,
                               int solid, int device, std::string* why) {
-#define G2S_GPU_TRY(expr)                                                                 \
-  do {                                                                                    \
-    hipError_t e_ = (expr);                                                               \
-    if (e_ != hipSuccess) { if (why) *why = std::string(#expr) + ": " + hipGetErrorString(e_); return false; } \
-  } while (0)
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) { if (why) *why = "no device"; return false; }
-  G2S_GPU_TRY(hipSetDevice(device));
+  if (!device_exists(device)) { if (why) *why = "no device"; return false; }
+  G2S_HIP_TRY(hipSetDevice(device));
   const int k = g.k;
   uint64_t T = 0;
   for (auto& sq : seqs) T += sq.second + 1;  // one separator after every sequence
   if (T == 0 || T >= (1ull << 32)) { if (why) *why = "text size"; return false; }
   size_t free_b = 0, total_b = 0;
-  G2S_GPU_TRY(hipMemGetInfo(&free_b, &total_b));
+  G2S_HIP_TRY(hipMemGetInfo(&free_b, &total_b));
   // (bytes a text position at the sort's peak: keys, sorted copy or split words, the sort's scratch; 256-bit keys:
   // the keys, the word and index double buffers, the sort's scratch, then the keys and their gathered copy)
   const double per_pos = sizeof(KT) == 32 ? (double)(2 * sizeof(KT) + 40) : (double)(4 * sizeof(KT) + 24);
@@ -984,205 +957,162 @@ static bool count_solid_gpu_t(Graph& g, std::vector<KT>& out, const std::vector<
     size_t pos = 0;
     for (auto& sq : seqs) { memcpy(text.data() + pos, sq.first, (size_t)sq.second); pos += (size_t)sq.second; text[pos++] = 'N'; }
   }
-  Dev d_text, d_keys, d_alt, d_lo, d_hi, d_lo2, d_hi2, d_flag, d_pos, d_hidx, d_keep, d_kpos, d_out, d_tmp, d_misc;
-  G2S_GPU_TRY(d_text.alloc((size_t)T));
-  G2S_GPU_TRY(d_keys.alloc((size_t)T * sizeof(KT)));
-  G2S_GPU_TRY(d_misc.alloc(16));
-  G2S_GPU_TRY(hipMemcpy(d_text.p, text.data(), (size_t)T, hipMemcpyHostToDevice));
+  DevMem d_text, d_keys, d_alt, d_lo, d_hi, d_lo2, d_hi2, d_flag, d_pos, d_hidx, d_keep, d_kpos, d_out;
+  Scratch d_tmp;
+  DevMem d_misc;
+  G2S_HIP_TRY(d_text.alloc((size_t)T));
+  G2S_HIP_TRY(d_keys.alloc((size_t)T * sizeof(KT)));
+  G2S_HIP_TRY(d_misc.alloc(16));
+  G2S_HIP_TRY(hipMemcpy(d_text.p, text.data(), (size_t)T, hipMemcpyHostToDevice));
   const dim3 blk(256), grdT((unsigned)((T + 255) / 256));
   hipLaunchKernelGGL(k_extract<KT>, grdT, blk, 0, 0, (const uint8_t*)d_text.p, T, k, (KT*)d_keys.p);
-  (void)hipFree(d_text.release());
+  d_text.free();
   KT* sorted = nullptr;
   if constexpr (sizeof(KT) == 8) {
-    G2S_GPU_TRY(d_alt.alloc((size_t)T * 8));
-    size_t tb = 0;
-    G2S_GPU_TRY(rocprim::radix_sort_keys(nullptr, tb, (uint64_t*)d_keys.p, (uint64_t*)d_alt.p, (size_t)T, 0, 64));
-    G2S_GPU_TRY(d_tmp.alloc(tb));
+    G2S_HIP_TRY(d_alt.alloc((size_t)T * 8));
     // (the filler is all-ones: sort on all 64 bits so that it ends up last)
-    G2S_GPU_TRY(rocprim::radix_sort_keys(d_tmp.p, tb, (uint64_t*)d_keys.p, (uint64_t*)d_alt.p, (size_t)T, 0, 64));
+    G2S_HIP_TRY(radix_sort_keys(d_tmp, (uint64_t*)d_keys.p, (uint64_t*)d_alt.p, (size_t)T));
     sorted = (KT*)d_alt.p;
   } else if constexpr (sizeof(KT) == 32) {
-    G2S_GPU_TRY(d_lo.alloc((size_t)T * 8));   // the pass's word, in and out
-    G2S_GPU_TRY(d_lo2.alloc((size_t)T * 8));
-    G2S_GPU_TRY(d_hi.alloc((size_t)T * 4));   // the key's index, in and out
-    G2S_GPU_TRY(d_hi2.alloc((size_t)T * 4));
+    G2S_HIP_TRY(d_lo.alloc((size_t)T * 8));   // the pass's word, in and out
+    G2S_HIP_TRY(d_lo2.alloc((size_t)T * 8));
+    G2S_HIP_TRY(d_hi.alloc((size_t)T * 4));   // the key's index, in and out
+    G2S_HIP_TRY(d_hi2.alloc((size_t)T * 4));
     uint64_t *w_in = (uint64_t*)d_lo.p, *w_out = (uint64_t*)d_lo2.p;
     uint32_t *i_in = (uint32_t*)d_hi.p, *i_out = (uint32_t*)d_hi2.p;
-    size_t tb = 0;
-    G2S_GPU_TRY(rocprim::radix_sort_pairs(nullptr, tb, w_in, w_out, i_in, i_out, (size_t)T, 0, 64));
-    G2S_GPU_TRY(d_tmp.alloc(tb));
+    G2S_HIP_TRY((radix_sort_pairs_reserve<uint64_t, uint32_t>(d_tmp, (size_t)T)));  // one scratch for the four passes
     // least significant word first; every later pass is stable, so the order of the earlier words holds among equals
     for (int w = 0; w < 4; w++) {
       hipLaunchKernelGGL(k_word, grdT, blk, 0, 0, (const u256*)d_keys.p, w == 0 ? (const uint32_t*)nullptr : (const uint32_t*)i_in,
                          T, w, w_in, i_in);
-      G2S_GPU_TRY(rocprim::radix_sort_pairs(d_tmp.p, tb, w_in, w_out, i_in, i_out, (size_t)T, 0, 64));
+      G2S_HIP_TRY(radix_sort_pairs(d_tmp, w_in, w_out, i_in, i_out, (size_t)T));
       std::swap(i_in, i_out);
     }
-    for (Dev* d : {&d_lo, &d_lo2, &d_tmp}) (void)hipFree(d->release());
-    G2S_GPU_TRY(d_alt.alloc((size_t)T * sizeof(KT)));
+    d_lo.free(); d_lo2.free(); d_tmp.free();
+    G2S_HIP_TRY(d_alt.alloc((size_t)T * sizeof(KT)));
     hipLaunchKernelGGL(k_gather, grdT, blk, 0, 0, (const u256*)d_keys.p, (const uint32_t*)i_in, T, (u256*)d_alt.p);
-    for (Dev* d : {&d_hi, &d_hi2, &d_keys}) (void)hipFree(d->release());
+    d_hi.free(); d_hi2.free(); d_keys.free();
     sorted = (KT*)d_alt.p;
   } else {
-    G2S_GPU_TRY(d_lo.alloc((size_t)T * 8));
-    G2S_GPU_TRY(d_hi.alloc((size_t)T * 8));
-    G2S_GPU_TRY(d_lo2.alloc((size_t)T * 8));
-    G2S_GPU_TRY(d_hi2.alloc((size_t)T * 8));
+    G2S_HIP_TRY(d_lo.alloc((size_t)T * 8));
+    G2S_HIP_TRY(d_hi.alloc((size_t)T * 8));
+    G2S_HIP_TRY(d_lo2.alloc((size_t)T * 8));
+    G2S_HIP_TRY(d_hi2.alloc((size_t)T * 8));
     hipLaunchKernelGGL(k_split<KT>, grdT, blk, 0, 0, (const KT*)d_keys.p, T, (uint64_t*)d_lo.p, (uint64_t*)d_hi.p);
-    size_t tb = 0;
-    G2S_GPU_TRY(rocprim::radix_sort_pairs(nullptr, tb, (uint64_t*)d_lo.p, (uint64_t*)d_lo2.p, (uint64_t*)d_hi.p,
-                                          (uint64_t*)d_hi2.p, (size_t)T, 0, 64));
-    G2S_GPU_TRY(d_tmp.alloc(tb));
-    // least significant word first, then a stable pass on the most significant word
-    G2S_GPU_TRY(rocprim::radix_sort_pairs(d_tmp.p, tb, (uint64_t*)d_lo.p, (uint64_t*)d_lo2.p, (uint64_t*)d_hi.p,
-                                          (uint64_t*)d_hi2.p, (size_t)T, 0, 64));
-    G2S_GPU_TRY(rocprim::radix_sort_pairs(d_tmp.p, tb, (uint64_t*)d_hi2.p, (uint64_t*)d_hi.p, (uint64_t*)d_lo2.p,
-                                          (uint64_t*)d_lo.p, (size_t)T, 0, 64));
+    // least significant word first, then a stable pass on the most significant word (the first call's scratch serves both)
+    G2S_HIP_TRY(radix_sort_pairs(d_tmp, (uint64_t*)d_lo.p, (uint64_t*)d_lo2.p, (uint64_t*)d_hi.p, (uint64_t*)d_hi2.p, (size_t)T));
+    G2S_HIP_TRY(radix_sort_pairs(d_tmp, (uint64_t*)d_hi2.p, (uint64_t*)d_hi.p, (uint64_t*)d_lo2.p, (uint64_t*)d_lo.p, (size_t)T));
     hipLaunchKernelGGL(k_join, grdT, blk, 0, 0, (const uint64_t*)d_lo.p, (const uint64_t*)d_hi.p, T, (u128*)d_keys.p);
     sorted = (KT*)d_keys.p;
-    for (Dev* d : {&d_lo2, &d_hi2}) (void)hipFree(d->release());
+    d_lo2.free(); d_hi2.free();
   }
   // ---- runs of equal keys -> the k-mers seen at least `solid` times
-  G2S_GPU_TRY(d_flag.alloc((size_t)T * 4));
-  G2S_GPU_TRY(d_pos.alloc((size_t)T * 4));
+  G2S_HIP_TRY(d_flag.alloc((size_t)T * 4));
+  G2S_HIP_TRY(d_pos.alloc((size_t)T * 4));
   hipLaunchKernelGGL(k_heads<KT>, grdT, blk, 0, 0, (const KT*)sorted, T, (uint32_t*)d_flag.p);
-  size_t tb2 = 0;
-  G2S_GPU_TRY(rocprim::exclusive_scan(nullptr, tb2, (const uint32_t*)d_flag.p, (uint32_t*)d_pos.p, 0u, (size_t)T,
-                                      rocprim::plus<uint32_t>()));
-  Dev d_tmp2;
-  G2S_GPU_TRY(d_tmp2.alloc(tb2));
-  G2S_GPU_TRY(rocprim::exclusive_scan(d_tmp2.p, tb2, (const uint32_t*)d_flag.p, (uint32_t*)d_pos.p, 0u, (size_t)T,
-                                      rocprim::plus<uint32_t>()));
-  uint32_t lastf = 0, lastp = 0;
-  G2S_GPU_TRY(hipMemcpy(&lastf, (const uint32_t*)d_flag.p + (T - 1), 4, hipMemcpyDeviceToHost));
-  G2S_GPU_TRY(hipMemcpy(&lastp, (const uint32_t*)d_pos.p + (T - 1), 4, hipMemcpyDeviceToHost));
-  const uint32_t nheads = lastp + lastf;
-  uint32_t n_solid = 0;
+  Scratch d_tmp2;
+  uint32_t nheads = 0, n_solid = 0;
+  G2S_HIP_TRY(scan_total(d_tmp2, (const uint32_t*)d_flag.p, (uint32_t*)d_pos.p, (size_t)T, &nheads));
   if (nheads) {
-    G2S_GPU_TRY(d_hidx.alloc((size_t)nheads * 4));
-    G2S_GPU_TRY(d_keep.alloc((size_t)nheads * 4));
-    G2S_GPU_TRY(d_kpos.alloc((size_t)nheads * 4));
-    G2S_GPU_TRY(hipMemset(d_misc.p, 0, 16));
+    G2S_HIP_TRY(d_hidx.alloc((size_t)nheads * 4));
+    G2S_HIP_TRY(d_keep.alloc((size_t)nheads * 4));
+    G2S_HIP_TRY(d_kpos.alloc((size_t)nheads * 4));
+    G2S_HIP_TRY(hipMemset(d_misc.p, 0, 16));
     hipLaunchKernelGGL(k_head_index<KT>, grdT, blk, 0, 0, (const KT*)sorted, (const uint32_t*)d_flag.p,
                        (const uint32_t*)d_pos.p, T, (uint32_t*)d_hidx.p, (uint32_t*)d_misc.p);
     uint32_t n_valid = 0;
-    G2S_GPU_TRY(hipMemcpy(&n_valid, d_misc.p, 4, hipMemcpyDeviceToHost));
+    G2S_HIP_TRY(hipMemcpy(&n_valid, d_misc.p, 4, hipMemcpyDeviceToHost));
     const dim3 grdH((nheads + 255) / 256);
     hipLaunchKernelGGL(k_solid_flag, grdH, blk, 0, 0, (const uint32_t*)d_hidx.p, nheads, n_valid, (uint32_t)std::max(1, solid),
                        (uint32_t*)d_keep.p);
-    size_t tb3 = 0;
-    G2S_GPU_TRY(rocprim::exclusive_scan(nullptr, tb3, (const uint32_t*)d_keep.p, (uint32_t*)d_kpos.p, 0u, (size_t)nheads,
-                                        rocprim::plus<uint32_t>()));
-    Dev d_tmp3;
-    G2S_GPU_TRY(d_tmp3.alloc(tb3));
-    G2S_GPU_TRY(rocprim::exclusive_scan(d_tmp3.p, tb3, (const uint32_t*)d_keep.p, (uint32_t*)d_kpos.p, 0u, (size_t)nheads,
-                                        rocprim::plus<uint32_t>()));
-    uint32_t lk = 0, lkp = 0;
-    G2S_GPU_TRY(hipMemcpy(&lk, (const uint32_t*)d_keep.p + (nheads - 1), 4, hipMemcpyDeviceToHost));
-    G2S_GPU_TRY(hipMemcpy(&lkp, (const uint32_t*)d_kpos.p + (nheads - 1), 4, hipMemcpyDeviceToHost));
-    n_solid = lk + lkp;
+    Scratch d_tmp3;
+    G2S_HIP_TRY(scan_total(d_tmp3, (const uint32_t*)d_keep.p, (uint32_t*)d_kpos.p, (size_t)nheads, &n_solid));
     if (n_solid) {
-      G2S_GPU_TRY(d_out.alloc((size_t)n_solid * sizeof(KT)));
+      G2S_HIP_TRY(d_out.alloc((size_t)n_solid * sizeof(KT)));
       hipLaunchKernelGGL(k_compact<KT>, grdH, blk, 0, 0, (const KT*)sorted, (const uint32_t*)d_hidx.p,
                          (const uint32_t*)d_keep.p, (const uint32_t*)d_kpos.p, nheads, (KT*)d_out.p);
     }
   }
-  G2S_GPU_TRY(hipGetLastError());
+  G2S_HIP_TRY(hipGetLastError());
   // ---- prefix index and the copies the host keeps (node look-ups, node strings)
   const int bits = std::min(2 * k, 22);
   const uint32_t nb = 1u << bits;
   std::vector<uint32_t> bucket((size_t)nb + 1, 0);
   std::vector<KT> host((size_t)n_solid);
   if (n_solid) {
-    Dev d_bucket;
-    G2S_GPU_TRY(d_bucket.alloc(((size_t)nb + 1) * 4));
+    DevMem d_bucket;
+    G2S_HIP_TRY(d_bucket.alloc(((size_t)nb + 1) * 4));
     hipLaunchKernelGGL(k_bucket<KT>, dim3((nb + 1 + 255) / 256), blk, 0, 0, (const KT*)d_out.p, n_solid, 2 * k - bits, nb,
                        (uint32_t*)d_bucket.p);
-    G2S_GPU_TRY(hipMemcpy(bucket.data(), d_bucket.p, ((size_t)nb + 1) * 4, hipMemcpyDeviceToHost));
-    G2S_GPU_TRY(hipMemcpy(host.data(), d_out.p, (size_t)n_solid * sizeof(KT), hipMemcpyDeviceToHost));
+    G2S_HIP_TRY(hipMemcpy(bucket.data(), d_bucket.p, ((size_t)nb + 1) * 4, hipMemcpyDeviceToHost));
+    G2S_HIP_TRY(hipMemcpy(host.data(), d_out.p, (size_t)n_solid * sizeof(KT), hipMemcpyDeviceToHost));
   }
   out.swap(host);
   g.n = n_solid;
   g.bucket.swap(bucket);
   g.bucket_bits = bits;
   return true;
-#undef G2S_GPU_TRY
 }
-
-#define G2S_GPU_TRY(expr)                                                                 \
-  do {                                                                                    \
-    hipError_t e_ = (expr);                                                               \
-    if (e_ != hipSuccess) { if (why) *why = std::string(#expr) + ": " + hipGetErrorString(e_); return false; } \
-  } while (0)
 
 // T keys sorted by (set, k-mer), or by k-mer alone without set ids (d_sid / d_ss == nullptr): LSD passes over the
 // k-mer's 64-bit words, then one stable pass over the set id, as (word, index) pairs with one gather at the end.
 // d_keys and d_sid are consumed; the sorted copies land in d_sk / d_ss.
 template <class KT>
-static bool sort_keyed_gpu(Dev& d_keys, Dev* d_sid, uint64_t T, Dev& d_sk, Dev* d_ss, std::string* why) {
-  Dev d_w0, d_w1, d_i0, d_i1, d_tmp;
+static bool sort_keyed_gpu(DevMem& d_keys, DevMem* d_sid, uint64_t T, DevMem& d_sk, DevMem* d_ss, std::string* why) {
+  DevMem d_w0, d_w1, d_i0, d_i1;
+  Scratch d_tmp;
   const dim3 blk(256), grdT((unsigned)((T + 255) / 256));
-  G2S_GPU_TRY(d_w0.alloc((size_t)T * 8));
-  G2S_GPU_TRY(d_w1.alloc((size_t)T * 8));
-  G2S_GPU_TRY(d_i0.alloc((size_t)T * 4));
-  G2S_GPU_TRY(d_i1.alloc((size_t)T * 4));
+  G2S_HIP_TRY(d_w0.alloc((size_t)T * 8));
+  G2S_HIP_TRY(d_w1.alloc((size_t)T * 8));
+  G2S_HIP_TRY(d_i0.alloc((size_t)T * 4));
+  G2S_HIP_TRY(d_i1.alloc((size_t)T * 4));
   uint64_t *w_in = (uint64_t*)d_w0.p, *w_out = (uint64_t*)d_w1.p;
   uint32_t *i_in = (uint32_t*)d_i0.p, *i_out = (uint32_t*)d_i1.p;
-  size_t tb = 0;
-  G2S_GPU_TRY(rocprim::radix_sort_pairs(nullptr, tb, w_in, w_out, i_in, i_out, (size_t)T, 0, 64));
-  G2S_GPU_TRY(d_tmp.alloc(tb));
+  G2S_HIP_TRY((radix_sort_pairs_reserve<uint64_t, uint32_t>(d_tmp, (size_t)T)));  // one scratch for every pass
   constexpr int W = (int)(sizeof(KT) / 8);
   const uint32_t* sid = d_sid ? (const uint32_t*)d_sid->p : nullptr;
   for (int w = 0; w < (sid ? W + 1 : W); w++) {
     const int word = w < W ? w : -1;
     hipLaunchKernelGGL(k_key_word<KT>, grdT, blk, 0, 0, (const KT*)d_keys.p, sid,
                        w == 0 ? (const uint32_t*)nullptr : (const uint32_t*)i_in, T, word, w_in, i_in);
-    G2S_GPU_TRY(rocprim::radix_sort_pairs(d_tmp.p, tb, w_in, w_out, i_in, i_out, (size_t)T, 0, word < 0 ? 32 : 64));
+    G2S_HIP_TRY(radix_sort_pairs(d_tmp, w_in, w_out, i_in, i_out, (size_t)T, word < 0 ? 32 : 64));
     std::swap(i_in, i_out);
   }
-  for (Dev* d : {&d_w0, &d_w1, &d_tmp}) (void)hipFree(d->release());
-  G2S_GPU_TRY(d_sk.alloc((size_t)T * sizeof(KT)));
+  d_w0.free(); d_w1.free(); d_tmp.free();
+  G2S_HIP_TRY(d_sk.alloc((size_t)T * sizeof(KT)));
   if (sid) {
-    G2S_GPU_TRY(d_ss->alloc((size_t)T * 4));
+    G2S_HIP_TRY(d_ss->alloc((size_t)T * 4));
     hipLaunchKernelGGL(k_gather_keyed<KT>, grdT, blk, 0, 0, (const KT*)d_keys.p, sid, (const uint32_t*)i_in, T, (KT*)d_sk.p,
                        (uint32_t*)d_ss->p);
-    (void)hipFree(d_sid->release());
+    d_sid->free();
   } else {
     hipLaunchKernelGGL(k_gather_keys<KT>, grdT, blk, 0, 0, (const KT*)d_keys.p, (const uint32_t*)i_in, T, (KT*)d_sk.p);
   }
-  G2S_GPU_TRY(hipGetLastError());
-  (void)hipFree(d_keys.release());
+  G2S_HIP_TRY(hipGetLastError());
+  d_keys.free();
   return true;
 }
 
 // the runs of equal (set, k-mer) in T sorted keys: run j = [hidx[j], tidx[j]]
 template <class KT>
-static bool runs_keyed_gpu(const KT* sk, const uint32_t* ss, uint64_t T, Dev& d_hidx, Dev& d_tidx, uint32_t* nruns_out, std::string* why) {
-  Dev d_flag, d_pos, d_tmp2;
+static bool runs_keyed_gpu(const KT* sk, const uint32_t* ss, uint64_t T, DevMem& d_hidx, DevMem& d_tidx, uint32_t* nruns_out, std::string* why) {
+  DevMem d_flag, d_pos;
+  Scratch d_tmp2;
   const dim3 blk(256), grdT((unsigned)((T + 255) / 256));
-  G2S_GPU_TRY(d_flag.alloc((size_t)T * 4));
-  G2S_GPU_TRY(d_pos.alloc((size_t)T * 4));
+  G2S_HIP_TRY(d_flag.alloc((size_t)T * 4));
+  G2S_HIP_TRY(d_pos.alloc((size_t)T * 4));
   hipLaunchKernelGGL(k_heads_keyed<KT>, grdT, blk, 0, 0, sk, ss, T, (uint32_t*)d_flag.p);
-  size_t tb2 = 0;
-  G2S_GPU_TRY(rocprim::exclusive_scan(nullptr, tb2, (const uint32_t*)d_flag.p, (uint32_t*)d_pos.p, 0u, (size_t)T,
-                                      rocprim::plus<uint32_t>()));
-  G2S_GPU_TRY(d_tmp2.alloc(tb2));
-  G2S_GPU_TRY(rocprim::exclusive_scan(d_tmp2.p, tb2, (const uint32_t*)d_flag.p, (uint32_t*)d_pos.p, 0u, (size_t)T,
-                                      rocprim::plus<uint32_t>()));
-  uint32_t lastf = 0, lastp = 0;
-  G2S_GPU_TRY(hipMemcpy(&lastf, (const uint32_t*)d_flag.p + (T - 1), 4, hipMemcpyDeviceToHost));
-  G2S_GPU_TRY(hipMemcpy(&lastp, (const uint32_t*)d_pos.p + (T - 1), 4, hipMemcpyDeviceToHost));
-  const uint32_t nruns = lastp + lastf;
+  uint32_t nruns = 0;
+  G2S_HIP_TRY(scan_total(d_tmp2, (const uint32_t*)d_flag.p, (uint32_t*)d_pos.p, (size_t)T, &nruns));
   if (nruns) {
-    G2S_GPU_TRY(d_hidx.alloc((size_t)nruns * 4));
-    G2S_GPU_TRY(d_tidx.alloc((size_t)nruns * 4));
+    G2S_HIP_TRY(d_hidx.alloc((size_t)nruns * 4));
+    G2S_HIP_TRY(d_tidx.alloc((size_t)nruns * 4));
     hipLaunchKernelGGL(k_runs_keyed<KT>, grdT, blk, 0, 0, sk, ss, (const uint32_t*)d_flag.p, (const uint32_t*)d_pos.p, T,
                        (uint32_t*)d_hidx.p, (uint32_t*)d_tidx.p);
   }
   *nruns_out = nruns;
   return true;
 }
-#undef G2S_GPU_TRY
 
 // The solid k-mer sets of a set graph at once: one key per text position (all sets' sequences in one text, the set
 // from a per-sequence table), sorted by (set, canonical k-mer) — LSD passes over the k-mer's 64-bit words, then one
@@ -1193,20 +1123,14 @@ template <class KT>
 static bool count_solid_sets_gpu_t(Graph& g, std::vector<KT>& out, std::vector<uint32_t>* rank_set,
                                    const std::vector<std::pair<const char*, uint64_t>>& seqs, const std::vector<uint32_t>& seq_set,
                                    uint32_t nsets, int solid, int device, std::string* why) {
-#define G2S_GPU_TRY(expr)                                                                 \
-  do {                                                                                    \
-    hipError_t e_ = (expr);                                                               \
-    if (e_ != hipSuccess) { if (why) *why = std::string(#expr) + ": " + hipGetErrorString(e_); return false; } \
-  } while (0)
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) { if (why) *why = "no device"; return false; }
-  G2S_GPU_TRY(hipSetDevice(device));
+  if (!device_exists(device)) { if (why) *why = "no device"; return false; }
+  G2S_HIP_TRY(hipSetDevice(device));
   const int k = g.k;
   uint64_t T = 0;
   for (auto& sq : seqs) T += sq.second + 1;  // one separator after every sequence
   if (T == 0 || T >= (1ull << 32) || seqs.empty()) { if (why) *why = "text size"; return false; }
   size_t free_b = 0, total_b = 0;
-  G2S_GPU_TRY(hipMemGetInfo(&free_b, &total_b));
+  G2S_HIP_TRY(hipMemGetInfo(&free_b, &total_b));
   // (bytes a text position at the peak: keys, set ids, word and index double buffers, the sort's scratch, the gathered copies)
   const double per_pos = (double)(2 * sizeof(KT) + 56);
   if ((double)T * per_pos > 0.5 * (double)free_b) { if (why) *why = "text too large for the device"; return false; }
@@ -1222,19 +1146,19 @@ static bool count_solid_sets_gpu_t(Graph& g, std::vector<KT>& out, std::vector<u
     }
   }
   const uint32_t ns = (uint32_t)seqs.size();
-  Dev d_text, d_start, d_sset, d_keys, d_sid, d_sk, d_ss, d_hidx, d_tidx, d_keep, d_kpos, d_out, d_osid, d_lo;
-  G2S_GPU_TRY(d_text.alloc((size_t)T));
-  G2S_GPU_TRY(d_start.alloc((size_t)ns * 8));
-  G2S_GPU_TRY(d_sset.alloc((size_t)ns * 4));
-  G2S_GPU_TRY(d_keys.alloc((size_t)T * sizeof(KT)));
-  G2S_GPU_TRY(d_sid.alloc((size_t)T * 4));
-  G2S_GPU_TRY(hipMemcpy(d_text.p, text.data(), (size_t)T, hipMemcpyHostToDevice));
-  G2S_GPU_TRY(hipMemcpy(d_start.p, start.data(), (size_t)ns * 8, hipMemcpyHostToDevice));
-  G2S_GPU_TRY(hipMemcpy(d_sset.p, seq_set.data(), (size_t)ns * 4, hipMemcpyHostToDevice));
+  DevMem d_text, d_start, d_sset, d_keys, d_sid, d_sk, d_ss, d_hidx, d_tidx, d_keep, d_kpos, d_out, d_osid, d_lo;
+  G2S_HIP_TRY(d_text.alloc((size_t)T));
+  G2S_HIP_TRY(d_start.alloc((size_t)ns * 8));
+  G2S_HIP_TRY(d_sset.alloc((size_t)ns * 4));
+  G2S_HIP_TRY(d_keys.alloc((size_t)T * sizeof(KT)));
+  G2S_HIP_TRY(d_sid.alloc((size_t)T * 4));
+  G2S_HIP_TRY(hipMemcpy(d_text.p, text.data(), (size_t)T, hipMemcpyHostToDevice));
+  G2S_HIP_TRY(hipMemcpy(d_start.p, start.data(), (size_t)ns * 8, hipMemcpyHostToDevice));
+  G2S_HIP_TRY(hipMemcpy(d_sset.p, seq_set.data(), (size_t)ns * 4, hipMemcpyHostToDevice));
   const dim3 blk(256), grdT((unsigned)((T + 255) / 256));
   hipLaunchKernelGGL(k_extract<KT>, grdT, blk, 0, 0, (const uint8_t*)d_text.p, T, k, (KT*)d_keys.p);
   hipLaunchKernelGGL(k_pos_set, grdT, blk, 0, 0, (const uint64_t*)d_start.p, (const uint32_t*)d_sset.p, ns, T, (uint32_t*)d_sid.p);
-  for (Dev* d : {&d_text, &d_start, &d_sset}) (void)hipFree(d->release());
+  d_text.free(); d_start.free(); d_sset.free();
   // ---- sort by (set, k-mer), then the runs -> the k-mers seen at least `solid` times in their own set
   if (!sort_keyed_gpu<KT>(d_keys, &d_sid, T, d_sk, &d_ss, why)) return false;
   const KT* sk = (const KT*)d_sk.p;
@@ -1243,25 +1167,16 @@ static bool count_solid_sets_gpu_t(Graph& g, std::vector<KT>& out, std::vector<u
   if (!runs_keyed_gpu<KT>(sk, ss, T, d_hidx, d_tidx, &nruns, why)) return false;
   uint32_t n_solid = 0;
   if (nruns) {
-    G2S_GPU_TRY(d_keep.alloc((size_t)nruns * 4));
-    G2S_GPU_TRY(d_kpos.alloc((size_t)nruns * 4));
+    G2S_HIP_TRY(d_keep.alloc((size_t)nruns * 4));
+    G2S_HIP_TRY(d_kpos.alloc((size_t)nruns * 4));
     const dim3 grdR((nruns + 255) / 256);
     hipLaunchKernelGGL(k_solid_keyed, grdR, blk, 0, 0, (const uint32_t*)d_hidx.p, (const uint32_t*)d_tidx.p, nruns,
                        (uint32_t)std::max(1, solid), (uint32_t*)d_keep.p);
-    size_t tb3 = 0;
-    G2S_GPU_TRY(rocprim::exclusive_scan(nullptr, tb3, (const uint32_t*)d_keep.p, (uint32_t*)d_kpos.p, 0u, (size_t)nruns,
-                                        rocprim::plus<uint32_t>()));
-    Dev d_tmp3;
-    G2S_GPU_TRY(d_tmp3.alloc(tb3));
-    G2S_GPU_TRY(rocprim::exclusive_scan(d_tmp3.p, tb3, (const uint32_t*)d_keep.p, (uint32_t*)d_kpos.p, 0u, (size_t)nruns,
-                                        rocprim::plus<uint32_t>()));
-    uint32_t lk = 0, lkp = 0;
-    G2S_GPU_TRY(hipMemcpy(&lk, (const uint32_t*)d_keep.p + (nruns - 1), 4, hipMemcpyDeviceToHost));
-    G2S_GPU_TRY(hipMemcpy(&lkp, (const uint32_t*)d_kpos.p + (nruns - 1), 4, hipMemcpyDeviceToHost));
-    n_solid = lk + lkp;
+    Scratch d_tmp3;
+    G2S_HIP_TRY(scan_total(d_tmp3, (const uint32_t*)d_keep.p, (uint32_t*)d_kpos.p, (size_t)nruns, &n_solid));
     if (n_solid) {
-      G2S_GPU_TRY(d_out.alloc((size_t)n_solid * sizeof(KT)));
-      G2S_GPU_TRY(d_osid.alloc((size_t)n_solid * 4));
+      G2S_HIP_TRY(d_out.alloc((size_t)n_solid * sizeof(KT)));
+      G2S_HIP_TRY(d_osid.alloc((size_t)n_solid * 4));
       hipLaunchKernelGGL(k_compact_keyed<KT>, grdR, blk, 0, 0, sk, ss, (const uint32_t*)d_hidx.p, (const uint32_t*)d_keep.p,
                          (const uint32_t*)d_kpos.p, nruns, (KT*)d_out.p, (uint32_t*)d_osid.p);
     }
@@ -1271,19 +1186,18 @@ static bool count_solid_sets_gpu_t(Graph& g, std::vector<KT>& out, std::vector<u
   std::vector<KT> host((size_t)n_solid);
   std::vector<uint32_t> rs((size_t)n_solid);
   if (n_solid) {
-    G2S_GPU_TRY(d_lo.alloc(((size_t)nsets + 1) * 4));
+    G2S_HIP_TRY(d_lo.alloc(((size_t)nsets + 1) * 4));
     hipLaunchKernelGGL(k_set_first, dim3((nsets + 1 + 255) / 256), blk, 0, 0, (const uint32_t*)d_osid.p, n_solid, nsets, (uint32_t*)d_lo.p);
-    G2S_GPU_TRY(hipMemcpy(lo32.data(), d_lo.p, lo32.size() * 4, hipMemcpyDeviceToHost));
-    G2S_GPU_TRY(hipMemcpy(host.data(), d_out.p, (size_t)n_solid * sizeof(KT), hipMemcpyDeviceToHost));
-    G2S_GPU_TRY(hipMemcpy(rs.data(), d_osid.p, (size_t)n_solid * 4, hipMemcpyDeviceToHost));
+    G2S_HIP_TRY(hipMemcpy(lo32.data(), d_lo.p, lo32.size() * 4, hipMemcpyDeviceToHost));
+    G2S_HIP_TRY(hipMemcpy(host.data(), d_out.p, (size_t)n_solid * sizeof(KT), hipMemcpyDeviceToHost));
+    G2S_HIP_TRY(hipMemcpy(rs.data(), d_osid.p, (size_t)n_solid * 4, hipMemcpyDeviceToHost));
   }
-  G2S_GPU_TRY(hipGetLastError());
+  G2S_HIP_TRY(hipGetLastError());
   out.swap(host);
   rank_set->swap(rs);
   g.n = n_solid;
   g.set_lo.assign(lo32.begin(), lo32.end());
   return true;
-#undef G2S_GPU_TRY
 }
 
 bool graph_build_sets_gpu(Graph& g, const std::vector<std::pair<const char*, uint64_t>>& seqs, const std::vector<uint32_t>& seq_set,
@@ -1310,24 +1224,8 @@ template <class KT>
 static bool count_solid_pool_gpu_t(Graph& g, std::vector<KT>& out, std::vector<uint32_t>* rank_set, const PoolSets& ps, int solid,
                                    int device, PoolBuildInfo* info, std::string* why, const PoolReach* reach, PoolReachInfo* rinfo,
                                    bool* device_usable) {
-#define G2S_GPU_TRY(expr)                                                                 \
-  do {                                                                                    \
-    hipError_t e_ = (expr);                                                               \
-    if (e_ != hipSuccess) { if (why) *why = std::string(#expr) + ": " + hipGetErrorString(e_); return false; } \
-  } while (0)
-#define G2S_SCAN(in, outp, count)                                                                                          \
-  do {                                                                                                                     \
-    size_t tb_ = 0;                                                                                                        \
-    G2S_GPU_TRY(rocprim::exclusive_scan(nullptr, tb_, (const uint32_t*)(in), (uint32_t*)(outp), 0u, (size_t)(count),       \
-                                        rocprim::plus<uint32_t>()));                                                      \
-    Dev d_tmp_;                                                                                                            \
-    G2S_GPU_TRY(d_tmp_.alloc(tb_));                                                                                        \
-    G2S_GPU_TRY(rocprim::exclusive_scan(d_tmp_.p, tb_, (const uint32_t*)(in), (uint32_t*)(outp), 0u, (size_t)(count),      \
-                                        rocprim::plus<uint32_t>()));                                                      \
-  } while (0)
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) { if (why) *why = "no device"; return false; }
-  G2S_GPU_TRY(hipSetDevice(device));
+  if (!device_exists(device)) { if (why) *why = "no device"; return false; }
+  G2S_HIP_TRY(hipSetDevice(device));
   if (device_usable) *device_usable = true;  // (a failure from here on is the device build giving up, not its absence)
   const int k = g.k;
   const std::vector<std::pair<const char*, uint64_t>>& seqs = *ps.seqs;
@@ -1367,7 +1265,7 @@ static bool count_solid_pool_gpu_t(Graph& g, std::vector<KT>& out, std::vector<u
   // (instance positions + shared positions below 2^32, as the set build wants of its text; the pool in use is no larger)
   if (I + S == 0 || I + S >= (1ull << 32) || P >= (1ull << 32)) { if (why) *why = "text size"; return false; }
   size_t free_b = 0, total_b = 0;
-  G2S_GPU_TRY(hipMemGetInfo(&free_b, &total_b));
+  G2S_HIP_TRY(hipMemGetInfo(&free_b, &total_b));
   // (the pool's text and keys while the pairs are gathered; a gathered position at its sort's peak as in
   // count_solid_sets_gpu_t; the merge is checked once the shared table's size is known)
   if ((double)P * (double)(sizeof(KT) + 1) + (double)(I + S) * (double)(2 * sizeof(KT) + 56) > 0.5 * (double)free_b) {
@@ -1381,101 +1279,99 @@ static bool count_solid_pool_gpu_t(Graph& g, std::vector<KT>& out, std::vector<u
   }
   const dim3 blk(256);
   auto grid = [](uint64_t n) { return dim3((unsigned)((n + 255) / 256)); };
-  Dev d_keys, d_sid, d_hkeys;
+  DevMem d_keys, d_sid, d_hkeys;
   {
-    Dev d_text, d_pkeys, d_sstart, d_slen1, d_iseq, d_iset, d_ilen, d_istart;
-    G2S_GPU_TRY(d_text.alloc((size_t)P));
-    G2S_GPU_TRY(d_pkeys.alloc((size_t)P * sizeof(KT)));
-    G2S_GPU_TRY(d_sstart.alloc((size_t)nu * 4));
-    G2S_GPU_TRY(d_slen1.alloc((size_t)nu * 4));
-    G2S_GPU_TRY(hipMemcpy(d_text.p, text.data(), (size_t)P, hipMemcpyHostToDevice));
-    G2S_GPU_TRY(hipMemcpy(d_sstart.p, seq_start.data(), (size_t)nu * 4, hipMemcpyHostToDevice));
-    G2S_GPU_TRY(hipMemcpy(d_slen1.p, seq_len1.data(), (size_t)nu * 4, hipMemcpyHostToDevice));
+    DevMem d_text, d_pkeys, d_sstart, d_slen1, d_iseq, d_iset, d_ilen, d_istart;
+    G2S_HIP_TRY(d_text.alloc((size_t)P));
+    G2S_HIP_TRY(d_pkeys.alloc((size_t)P * sizeof(KT)));
+    G2S_HIP_TRY(d_sstart.alloc((size_t)nu * 4));
+    G2S_HIP_TRY(d_slen1.alloc((size_t)nu * 4));
+    G2S_HIP_TRY(hipMemcpy(d_text.p, text.data(), (size_t)P, hipMemcpyHostToDevice));
+    G2S_HIP_TRY(hipMemcpy(d_sstart.p, seq_start.data(), (size_t)nu * 4, hipMemcpyHostToDevice));
+    G2S_HIP_TRY(hipMemcpy(d_slen1.p, seq_len1.data(), (size_t)nu * 4, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(k_extract<KT>, grid(P), blk, 0, 0, (const uint8_t*)d_text.p, P, k, (KT*)d_pkeys.p);
     // the own lists' pairs, then the shared list's keys: instance -> pool position through the instances' start table
     for (int pass = 0; pass < 2; pass++) {
       const uint32_t ni = pass == 0 ? ninst : nsh;
       const uint64_t np = pass == 0 ? I : S;
       if (!np) continue;
-      G2S_GPU_TRY(d_iseq.alloc((size_t)ni * 4));
-      G2S_GPU_TRY(d_ilen.alloc((size_t)ni * 4));
-      G2S_GPU_TRY(d_istart.alloc((size_t)ni * 4));
-      G2S_GPU_TRY(hipMemcpy(d_iseq.p, pass == 0 ? inst_seq.data() : sh_seq.data(), (size_t)ni * 4, hipMemcpyHostToDevice));
+      G2S_HIP_TRY(d_iseq.alloc((size_t)ni * 4));
+      G2S_HIP_TRY(d_ilen.alloc((size_t)ni * 4));
+      G2S_HIP_TRY(d_istart.alloc((size_t)ni * 4));
+      G2S_HIP_TRY(hipMemcpy(d_iseq.p, pass == 0 ? inst_seq.data() : sh_seq.data(), (size_t)ni * 4, hipMemcpyHostToDevice));
       if (pass == 0) {
-        G2S_GPU_TRY(d_iset.alloc((size_t)ni * 4));
-        G2S_GPU_TRY(hipMemcpy(d_iset.p, inst_set.data(), (size_t)ni * 4, hipMemcpyHostToDevice));
-        G2S_GPU_TRY(d_sid.alloc((size_t)np * 4));
+        G2S_HIP_TRY(d_iset.alloc((size_t)ni * 4));
+        G2S_HIP_TRY(hipMemcpy(d_iset.p, inst_set.data(), (size_t)ni * 4, hipMemcpyHostToDevice));
+        G2S_HIP_TRY(d_sid.alloc((size_t)np * 4));
       }
-      Dev& d_dst = pass == 0 ? d_keys : d_hkeys;
-      G2S_GPU_TRY(d_dst.alloc((size_t)np * sizeof(KT)));
+      DevMem& d_dst = pass == 0 ? d_keys : d_hkeys;
+      G2S_HIP_TRY(d_dst.alloc((size_t)np * sizeof(KT)));
       hipLaunchKernelGGL(k_inst_len, grid(ni), blk, 0, 0, (const uint32_t*)d_iseq.p, (const uint32_t*)d_slen1.p, ni, (uint32_t*)d_ilen.p);
-      G2S_SCAN(d_ilen.p, d_istart.p, ni);
+      G2S_HIP_TRY(exclusive_scan((const uint32_t*)d_ilen.p, (uint32_t*)d_istart.p, (size_t)ni));
       hipLaunchKernelGGL(k_pool_pairs<KT>, grid(np), blk, 0, 0, (const KT*)d_pkeys.p, (const uint32_t*)d_istart.p,
                          (const uint32_t*)d_iseq.p, pass == 0 ? (const uint32_t*)d_iset.p : (const uint32_t*)nullptr,
                          (const uint32_t*)d_sstart.p, ni, np, (KT*)d_dst.p, pass == 0 ? (uint32_t*)d_sid.p : (uint32_t*)nullptr);
-      G2S_GPU_TRY(hipGetLastError());
-      for (Dev* d : {&d_iseq, &d_iset, &d_ilen, &d_istart}) { if (d->p) (void)hipFree(d->release()); }
+      G2S_HIP_TRY(hipGetLastError());
+      d_iseq.free(); d_iset.free(); d_ilen.free(); d_istart.free();
     }
   }
   info->own_positions = I;
   info->shared_positions = S;
   info->keys_sorted = 0;
   // ---- the own lists: (set, k-mer) sort, runs, the run table and every set's first run
-  Dev d_rkey, d_rset, d_rcnt, d_rlo;
+  DevMem d_rkey, d_rset, d_rcnt, d_rlo;
   uint32_t nruns = 0;
   if (I) {
-    Dev d_sk, d_ss, d_hidx, d_tidx;
+    DevMem d_sk, d_ss, d_hidx, d_tidx;
     if (!sort_keyed_gpu<KT>(d_keys, &d_sid, I, d_sk, &d_ss, why)) return false;
     info->keys_sorted += I;
     if (!runs_keyed_gpu<KT>((const KT*)d_sk.p, (const uint32_t*)d_ss.p, I, d_hidx, d_tidx, &nruns, why)) return false;
-    G2S_GPU_TRY(d_rkey.alloc((size_t)nruns * sizeof(KT)));
-    G2S_GPU_TRY(d_rset.alloc((size_t)nruns * 4));
-    G2S_GPU_TRY(d_rcnt.alloc((size_t)nruns * 4));
+    G2S_HIP_TRY(d_rkey.alloc((size_t)nruns * sizeof(KT)));
+    G2S_HIP_TRY(d_rset.alloc((size_t)nruns * 4));
+    G2S_HIP_TRY(d_rcnt.alloc((size_t)nruns * 4));
     if (nruns) {
       hipLaunchKernelGGL(k_run_table<KT>, grid(nruns), blk, 0, 0, (const KT*)d_sk.p, (const uint32_t*)d_ss.p, (const uint32_t*)d_hidx.p,
                          (const uint32_t*)d_tidx.p, nruns, (KT*)d_rkey.p, (uint32_t*)d_rset.p, (uint32_t*)d_rcnt.p);
     }
-    G2S_GPU_TRY(hipDeviceSynchronize());
+    G2S_HIP_TRY(hipDeviceSynchronize());
   } else {
-    G2S_GPU_TRY(d_rkey.alloc(0));
-    G2S_GPU_TRY(d_rset.alloc(0));
-    G2S_GPU_TRY(d_rcnt.alloc(0));
+    G2S_HIP_TRY(d_rkey.alloc(0));
+    G2S_HIP_TRY(d_rset.alloc(0));
+    G2S_HIP_TRY(d_rcnt.alloc(0));
   }
-  G2S_GPU_TRY(d_rlo.alloc(((size_t)nsets + 1) * 4));
+  G2S_HIP_TRY(d_rlo.alloc(((size_t)nsets + 1) * 4));
   hipLaunchKernelGGL(k_set_first, grid((uint64_t)nsets + 1), blk, 0, 0, (const uint32_t*)d_rset.p, nruns, nsets, (uint32_t*)d_rlo.p);
   // ---- the shared list: sorted once as plain k-mers, run-length counted
-  Dev d_hkey, d_hcnt;
+  DevMem d_hkey, d_hcnt;
   uint32_t U = 0;
   if (S) {
-    Dev d_hs, d_flag, d_pos, d_hidx, d_misc;
+    DevMem d_hs, d_flag, d_pos, d_hidx, d_misc;
     if (!sort_keyed_gpu<KT>(d_hkeys, nullptr, S, d_hs, nullptr, why)) return false;
     info->keys_sorted += S;
-    G2S_GPU_TRY(d_flag.alloc((size_t)S * 4));
-    G2S_GPU_TRY(d_pos.alloc((size_t)S * 4));
-    G2S_GPU_TRY(d_misc.alloc(16));
+    G2S_HIP_TRY(d_flag.alloc((size_t)S * 4));
+    G2S_HIP_TRY(d_pos.alloc((size_t)S * 4));
+    G2S_HIP_TRY(d_misc.alloc(16));
     hipLaunchKernelGGL(k_heads<KT>, grid(S), blk, 0, 0, (const KT*)d_hs.p, S, (uint32_t*)d_flag.p);
-    G2S_SCAN(d_flag.p, d_pos.p, S);
-    uint32_t lastf = 0, lastp = 0;
-    G2S_GPU_TRY(hipMemcpy(&lastf, (const uint32_t*)d_flag.p + (S - 1), 4, hipMemcpyDeviceToHost));
-    G2S_GPU_TRY(hipMemcpy(&lastp, (const uint32_t*)d_pos.p + (S - 1), 4, hipMemcpyDeviceToHost));
-    U = lastp + lastf;
+    // (not scan_total: the scan's scratch is freed before the two copies, as the pool build always did)
+    G2S_HIP_TRY(exclusive_scan((const uint32_t*)d_flag.p, (uint32_t*)d_pos.p, (size_t)S));
+    G2S_HIP_TRY(read_total((const uint32_t*)d_flag.p, (const uint32_t*)d_pos.p, (size_t)S, &U));
     if (U) {
-      G2S_GPU_TRY(d_hidx.alloc((size_t)U * 4));
-      G2S_GPU_TRY(d_hkey.alloc((size_t)U * sizeof(KT)));
-      G2S_GPU_TRY(d_hcnt.alloc((size_t)U * 4));
-      G2S_GPU_TRY(hipMemset(d_misc.p, 0, 16));
+      G2S_HIP_TRY(d_hidx.alloc((size_t)U * 4));
+      G2S_HIP_TRY(d_hkey.alloc((size_t)U * sizeof(KT)));
+      G2S_HIP_TRY(d_hcnt.alloc((size_t)U * 4));
+      G2S_HIP_TRY(hipMemset(d_misc.p, 0, 16));
       hipLaunchKernelGGL(k_head_index<KT>, grid(S), blk, 0, 0, (const KT*)d_hs.p, (const uint32_t*)d_flag.p, (const uint32_t*)d_pos.p, S,
                          (uint32_t*)d_hidx.p, (uint32_t*)d_misc.p);
       uint32_t n_valid = 0;
-      G2S_GPU_TRY(hipMemcpy(&n_valid, d_misc.p, 4, hipMemcpyDeviceToHost));
+      G2S_HIP_TRY(hipMemcpy(&n_valid, d_misc.p, 4, hipMemcpyDeviceToHost));
       hipLaunchKernelGGL(k_shared_table<KT>, grid(U), blk, 0, 0, (const KT*)d_hs.p, (const uint32_t*)d_hidx.p, U, n_valid,
                          (KT*)d_hkey.p, (uint32_t*)d_hcnt.p);
-      G2S_GPU_TRY(hipDeviceSynchronize());
+      G2S_HIP_TRY(hipDeviceSynchronize());
     }
   }
   if (!U) {
-    G2S_GPU_TRY(d_hkey.alloc(0));
-    G2S_GPU_TRY(d_hcnt.alloc(0));
+    G2S_HIP_TRY(d_hkey.alloc(0));
+    G2S_HIP_TRY(d_hcnt.alloc(0));
   }
   // ---- the sets with a reach record (dbg.hpp: PoolReach): a bounded search per set over the two tables; what it kept
   // replaces those sets' runs (as runs of `solid` copies) and the sets lose their flag, so that the merge below keeps
@@ -1486,7 +1382,7 @@ static bool count_solid_pool_gpu_t(Graph& g, std::vector<KT>& out, std::vector<u
     std::vector<int32_t> radius;
     std::vector<KT> seeds;
     uint32_t rows = 0;
-    G2S_GPU_TRY(hipMemcpy(run_lo.data(), d_rlo.p, run_lo.size() * 4, hipMemcpyDeviceToHost));
+    G2S_HIP_TRY(hipMemcpy(run_lo.data(), d_rlo.p, run_lo.size() * 4, hipMemcpyDeviceToHost));
     uint64_t upper = 0, own_rec = 0;  // the k-mers the searches can visit at most; the own runs among them
     for (uint32_t s = 0; s < nsets; s++) {
       if (!reach->has(s)) continue;
@@ -1507,7 +1403,7 @@ static bool count_solid_pool_gpu_t(Graph& g, std::vector<KT>& out, std::vector<u
     }
     const uint32_t R = (uint32_t)rsets.size(), W = (U + 31u) / 32u;
     const size_t own_words = ((size_t)nruns + 31) / 32, sh_words = (size_t)rows * W;
-    G2S_GPU_TRY(hipMemGetInfo(&free_b, &total_b));
+    G2S_HIP_TRY(hipMemGetInfo(&free_b, &total_b));
     // (a queued k-mer: the queue, then the sort of count_solid_sets_gpu_t over what was queued; the bitmaps beside it)
     const double per_item = (double)(2 * sizeof(KT) + 56), bitmap_bytes = (double)(own_words + sh_words) * 4.0;
     if (bitmap_bytes > 0.25 * (double)free_b) { if (why) *why = "reach: visited bitmaps too large for the device"; return false; }
@@ -1521,22 +1417,22 @@ static bool count_solid_pool_gpu_t(Graph& g, std::vector<KT>& out, std::vector<u
     if (getenv("G2S_REACH_QUEUE_CAP")) cap = std::min<uint64_t>(cap, (uint64_t)std::max(1ll, atoll(getenv("G2S_REACH_QUEUE_CAP"))));
     uint64_t Q = std::min<uint64_t>(cap, own_rec + kReachShare * (uint64_t)rsets.size());
     const size_t own_bytes = std::max<size_t>(own_words * 4, 16), sh_bytes = std::max<size_t>(sh_words * 4, 16);
-    Dev d_rsets, d_radius, d_seedlo, d_setfr, d_ridx, d_seeds, d_ownb, d_shb, d_qkey, d_qset, d_ctl;
-    G2S_GPU_TRY(d_rsets.alloc((size_t)R * 4));
-    G2S_GPU_TRY(d_radius.alloc((size_t)R * 4));
-    G2S_GPU_TRY(d_seedlo.alloc(((size_t)R + 1) * 4));
-    G2S_GPU_TRY(d_setfr.alloc((size_t)nsets * 4));
-    G2S_GPU_TRY(d_ridx.alloc((size_t)nsets * 4));
-    G2S_GPU_TRY(d_seeds.alloc(seeds.size() * sizeof(KT)));
-    G2S_GPU_TRY(d_ownb.alloc(own_bytes));
-    G2S_GPU_TRY(d_shb.alloc(sh_bytes));
-    G2S_GPU_TRY(d_ctl.alloc(16));
-    G2S_GPU_TRY(hipMemcpy(d_rsets.p, rsets.data(), (size_t)R * 4, hipMemcpyHostToDevice));
-    G2S_GPU_TRY(hipMemcpy(d_radius.p, radius.data(), (size_t)R * 4, hipMemcpyHostToDevice));
-    G2S_GPU_TRY(hipMemcpy(d_seedlo.p, seed_lo.data(), ((size_t)R + 1) * 4, hipMemcpyHostToDevice));
-    G2S_GPU_TRY(hipMemcpy(d_setfr.p, set_fr.data(), (size_t)nsets * 4, hipMemcpyHostToDevice));
-    G2S_GPU_TRY(hipMemcpy(d_ridx.p, set_ridx.data(), (size_t)nsets * 4, hipMemcpyHostToDevice));
-    if (!seeds.empty()) G2S_GPU_TRY(hipMemcpy(d_seeds.p, seeds.data(), seeds.size() * sizeof(KT), hipMemcpyHostToDevice));
+    DevMem d_rsets, d_radius, d_seedlo, d_setfr, d_ridx, d_seeds, d_ownb, d_shb, d_qkey, d_qset, d_ctl;
+    G2S_HIP_TRY(d_rsets.alloc((size_t)R * 4));
+    G2S_HIP_TRY(d_radius.alloc((size_t)R * 4));
+    G2S_HIP_TRY(d_seedlo.alloc(((size_t)R + 1) * 4));
+    G2S_HIP_TRY(d_setfr.alloc((size_t)nsets * 4));
+    G2S_HIP_TRY(d_ridx.alloc((size_t)nsets * 4));
+    G2S_HIP_TRY(d_seeds.alloc(seeds.size() * sizeof(KT)));
+    G2S_HIP_TRY(d_ownb.alloc(own_bytes));
+    G2S_HIP_TRY(d_shb.alloc(sh_bytes));
+    G2S_HIP_TRY(d_ctl.alloc(16));
+    G2S_HIP_TRY(hipMemcpy(d_rsets.p, rsets.data(), (size_t)R * 4, hipMemcpyHostToDevice));
+    G2S_HIP_TRY(hipMemcpy(d_radius.p, radius.data(), (size_t)R * 4, hipMemcpyHostToDevice));
+    G2S_HIP_TRY(hipMemcpy(d_seedlo.p, seed_lo.data(), ((size_t)R + 1) * 4, hipMemcpyHostToDevice));
+    G2S_HIP_TRY(hipMemcpy(d_setfr.p, set_fr.data(), (size_t)nsets * 4, hipMemcpyHostToDevice));
+    G2S_HIP_TRY(hipMemcpy(d_ridx.p, set_ridx.data(), (size_t)nsets * 4, hipMemcpyHostToDevice));
+    if (!seeds.empty()) G2S_HIP_TRY(hipMemcpy(d_seeds.p, seeds.data(), seeds.size() * sizeof(KT), hipMemcpyHostToDevice));
     ReachArgs ra;
     ra.rsets = (const uint32_t*)d_rsets.p;
     ra.radius = (const int32_t*)d_radius.p;
@@ -1551,17 +1447,17 @@ static bool count_solid_pool_gpu_t(Graph& g, std::vector<KT>& out, std::vector<u
     ra.U = U; ra.W = W; ra.R = R; ra.solid = so; ra.k = k;
     uint32_t ctl[4] = {0, 0, 0, 0};
     for (;;) {
-      G2S_GPU_TRY(d_qkey.alloc((size_t)Q * sizeof(KT)));
-      G2S_GPU_TRY(d_qset.alloc((size_t)Q * 4));
-      G2S_GPU_TRY(hipMemset(d_ownb.p, 0, own_bytes));
-      G2S_GPU_TRY(hipMemset(d_shb.p, 0, sh_bytes));
-      G2S_GPU_TRY(hipMemset(d_ctl.p, 0, 16));
+      G2S_HIP_TRY(d_qkey.alloc((size_t)Q * sizeof(KT)));
+      G2S_HIP_TRY(d_qset.alloc((size_t)Q * 4));
+      G2S_HIP_TRY(hipMemset(d_ownb.p, 0, own_bytes));
+      G2S_HIP_TRY(hipMemset(d_shb.p, 0, sh_bytes));
+      G2S_HIP_TRY(hipMemset(d_ctl.p, 0, 16));
       ra.out_set = (uint32_t*)d_qset.p;
       ra.Q = (uint32_t)Q;
       hipLaunchKernelGGL(k_reach_bfs<KT>, dim3(std::min<uint32_t>(R, 1024u)), dim3(kReachThreads), 0, 0, ra, (const KT*)d_rkey.p,
                          (const KT*)d_hkey.p, (const KT*)d_seeds.p, (KT*)d_qkey.p);
-      G2S_GPU_TRY(hipGetLastError());
-      G2S_GPU_TRY(hipMemcpy(ctl, d_ctl.p, 16, hipMemcpyDeviceToHost));
+      G2S_HIP_TRY(hipGetLastError());
+      G2S_HIP_TRY(hipMemcpy(ctl, d_ctl.p, 16, hipMemcpyDeviceToHost));
       if (!ctl[kReachOverflow]) break;
       if ((ctl[kReachOverflow] & kReachChunkListFull) || Q >= cap) {
         if (why) *why = "reach: the search's queue of " + std::to_string(Q) + " k-mers (or a level's chunk list) overflowed";
@@ -1571,32 +1467,32 @@ static bool count_solid_pool_gpu_t(Graph& g, std::vector<KT>& out, std::vector<u
         fprintf(stderr, "[g2s]   reach: the queue of %llu k-mers overflowed, searching again with %llu\n", (unsigned long long)Q,
                 (unsigned long long)std::min<uint64_t>(cap, Q * 4));
       Q = std::min<uint64_t>(cap, Q * 4);
-      (void)hipFree(d_qkey.release());
-      (void)hipFree(d_qset.release());
+      d_qkey.free();
+      d_qset.free();
     }
     const uint32_t nvis = ctl[kReachFill];
-    for (Dev* d : {&d_ownb, &d_shb, &d_seeds}) (void)hipFree(d->release());
+    d_ownb.free(); d_shb.free(); d_seeds.free();
     // the kept k-mers by (set, k-mer), every set's first; then the new run table
-    Dev d_sk, d_ss, d_vlo, d_ncnt, d_nlo, d_nkey, d_nset, d_nrc;
-    G2S_GPU_TRY(d_vlo.alloc(((size_t)nsets + 1) * 4));
+    DevMem d_sk, d_ss, d_vlo, d_ncnt, d_nlo, d_nkey, d_nset, d_nrc;
+    G2S_HIP_TRY(d_vlo.alloc(((size_t)nsets + 1) * 4));
     if (nvis) {
       if (!sort_keyed_gpu<KT>(d_qkey, &d_qset, nvis, d_sk, &d_ss, why)) return false;
       hipLaunchKernelGGL(k_set_first, grid((uint64_t)nsets + 1), blk, 0, 0, (const uint32_t*)d_ss.p, nvis, nsets, (uint32_t*)d_vlo.p);
     } else {
-      G2S_GPU_TRY(hipMemset(d_vlo.p, 0, ((size_t)nsets + 1) * 4));
-      G2S_GPU_TRY(d_sk.alloc(0));
-      G2S_GPU_TRY(d_ss.alloc(0));
+      G2S_HIP_TRY(hipMemset(d_vlo.p, 0, ((size_t)nsets + 1) * 4));
+      G2S_HIP_TRY(d_sk.alloc(0));
+      G2S_HIP_TRY(d_ss.alloc(0));
     }
-    G2S_GPU_TRY(d_ncnt.alloc(((size_t)nsets + 1) * 4));
-    G2S_GPU_TRY(d_nlo.alloc(((size_t)nsets + 1) * 4));
+    G2S_HIP_TRY(d_ncnt.alloc(((size_t)nsets + 1) * 4));
+    G2S_HIP_TRY(d_nlo.alloc(((size_t)nsets + 1) * 4));
     hipLaunchKernelGGL(k_reach_set_count, grid((uint64_t)nsets + 1), blk, 0, 0, (const uint32_t*)d_rlo.p, (const uint32_t*)d_ridx.p,
                        (const uint32_t*)d_vlo.p, nsets, (uint32_t*)d_ncnt.p);
-    G2S_SCAN(d_ncnt.p, d_nlo.p, (size_t)nsets + 1);
+    G2S_HIP_TRY(exclusive_scan((const uint32_t*)d_ncnt.p, (uint32_t*)d_nlo.p, (size_t)nsets + 1));
     uint32_t nruns2 = 0;
-    G2S_GPU_TRY(hipMemcpy(&nruns2, (const uint32_t*)d_nlo.p + nsets, 4, hipMemcpyDeviceToHost));
-    G2S_GPU_TRY(d_nkey.alloc((size_t)nruns2 * sizeof(KT)));
-    G2S_GPU_TRY(d_nset.alloc((size_t)nruns2 * 4));
-    G2S_GPU_TRY(d_nrc.alloc((size_t)nruns2 * 4));
+    G2S_HIP_TRY(hipMemcpy(&nruns2, (const uint32_t*)d_nlo.p + nsets, 4, hipMemcpyDeviceToHost));
+    G2S_HIP_TRY(d_nkey.alloc((size_t)nruns2 * sizeof(KT)));
+    G2S_HIP_TRY(d_nset.alloc((size_t)nruns2 * 4));
+    G2S_HIP_TRY(d_nrc.alloc((size_t)nruns2 * 4));
     if (nruns)
       hipLaunchKernelGGL(k_reach_copy_runs<KT>, grid(nruns), blk, 0, 0, (const KT*)d_rkey.p, (const uint32_t*)d_rset.p,
                          (const uint32_t*)d_rcnt.p, nruns, (const uint32_t*)d_ridx.p, (const uint32_t*)d_rlo.p, (const uint32_t*)d_nlo.p,
@@ -1604,7 +1500,7 @@ static bool count_solid_pool_gpu_t(Graph& g, std::vector<KT>& out, std::vector<u
     if (nvis)
       hipLaunchKernelGGL(k_reach_copy_kept<KT>, grid(nvis), blk, 0, 0, (const KT*)d_sk.p, (const uint32_t*)d_ss.p, nvis,
                          (const uint32_t*)d_vlo.p, (const uint32_t*)d_nlo.p, so, (KT*)d_nkey.p, (uint32_t*)d_nset.p, (uint32_t*)d_nrc.p);
-    G2S_GPU_TRY(hipDeviceSynchronize());
+    G2S_HIP_TRY(hipDeviceSynchronize());
     std::swap(d_rkey.p, d_nkey.p);
     std::swap(d_rset.p, d_nset.p);
     std::swap(d_rcnt.p, d_nrc.p);
@@ -1627,21 +1523,21 @@ static bool count_solid_pool_gpu_t(Graph& g, std::vector<KT>& out, std::vector<u
   const uint64_t FU64 = (uint64_t)F * U;
   if (FU64 + nruns >= (1ull << 31)) { if (why) *why = "size"; return false; }
   const uint32_t FU = (uint32_t)FU64, so = (uint32_t)std::max(1, solid);
-  G2S_GPU_TRY(hipMemGetInfo(&free_b, &total_b));
+  G2S_HIP_TRY(hipMemGetInfo(&free_b, &total_b));
   // (two words an item for the flags and their scans, then at most one k-mer and its set id an item in the output)
   if ((double)(FU64 + nruns) * (double)(sizeof(KT) + 12) > 0.5 * (double)free_b) {
     if (why) *why = "merge too large for the device";
     return false;
   }
-  Dev d_sf, d_fset, d_kown, d_ksh, d_pown, d_psh, d_cnt, d_base, d_out, d_osid;
-  G2S_GPU_TRY(d_sf.alloc((size_t)nsets * 4));
-  G2S_GPU_TRY(d_fset.alloc((size_t)F * 4));
-  G2S_GPU_TRY(hipMemcpy(d_sf.p, set_fidx.data(), (size_t)nsets * 4, hipMemcpyHostToDevice));
-  if (F) G2S_GPU_TRY(hipMemcpy(d_fset.p, fset.data(), (size_t)F * 4, hipMemcpyHostToDevice));
-  G2S_GPU_TRY(d_kown.alloc(((size_t)nruns + 1) * 4));
-  G2S_GPU_TRY(d_pown.alloc(((size_t)nruns + 1) * 4));
-  G2S_GPU_TRY(d_ksh.alloc(((size_t)FU + 1) * 4));
-  G2S_GPU_TRY(d_psh.alloc(((size_t)FU + 1) * 4));
+  DevMem d_sf, d_fset, d_kown, d_ksh, d_pown, d_psh, d_cnt, d_base, d_out, d_osid;
+  G2S_HIP_TRY(d_sf.alloc((size_t)nsets * 4));
+  G2S_HIP_TRY(d_fset.alloc((size_t)F * 4));
+  G2S_HIP_TRY(hipMemcpy(d_sf.p, set_fidx.data(), (size_t)nsets * 4, hipMemcpyHostToDevice));
+  if (F) G2S_HIP_TRY(hipMemcpy(d_fset.p, fset.data(), (size_t)F * 4, hipMemcpyHostToDevice));
+  G2S_HIP_TRY(d_kown.alloc(((size_t)nruns + 1) * 4));
+  G2S_HIP_TRY(d_pown.alloc(((size_t)nruns + 1) * 4));
+  G2S_HIP_TRY(d_ksh.alloc(((size_t)FU + 1) * 4));
+  G2S_HIP_TRY(d_psh.alloc(((size_t)FU + 1) * 4));
   hipLaunchKernelGGL(k_pool_keep_own<KT>, grid((uint64_t)nruns + 1), blk, 0, 0, (const KT*)d_rkey.p, (const uint32_t*)d_rset.p,
                      (const uint32_t*)d_rcnt.p, nruns, (const uint32_t*)d_sf.p, (const KT*)d_hkey.p, U, so, (uint32_t*)d_kown.p);
   if (FU) {
@@ -1649,23 +1545,23 @@ static bool count_solid_pool_gpu_t(Graph& g, std::vector<KT>& out, std::vector<u
                        (const uint32_t*)d_fset.p, FU, (const uint32_t*)d_rlo.p, (const KT*)d_rkey.p, (const uint32_t*)d_rcnt.p, so,
                        (uint32_t*)d_ksh.p);
   } else {
-    G2S_GPU_TRY(hipMemset(d_ksh.p, 0, 4));
+    G2S_HIP_TRY(hipMemset(d_ksh.p, 0, 4));
   }
-  G2S_SCAN(d_kown.p, d_pown.p, (size_t)nruns + 1);
-  G2S_SCAN(d_ksh.p, d_psh.p, (size_t)FU + 1);
-  G2S_GPU_TRY(d_cnt.alloc(((size_t)nsets + 1) * 4));
-  G2S_GPU_TRY(d_base.alloc(((size_t)nsets + 1) * 4));
+  G2S_HIP_TRY(exclusive_scan((const uint32_t*)d_kown.p, (uint32_t*)d_pown.p, (size_t)nruns + 1));
+  G2S_HIP_TRY(exclusive_scan((const uint32_t*)d_ksh.p, (uint32_t*)d_psh.p, (size_t)FU + 1));
+  G2S_HIP_TRY(d_cnt.alloc(((size_t)nsets + 1) * 4));
+  G2S_HIP_TRY(d_base.alloc(((size_t)nsets + 1) * 4));
   hipLaunchKernelGGL(k_pool_set_count, grid((uint64_t)nsets + 1), blk, 0, 0, (const uint32_t*)d_rlo.p, (const uint32_t*)d_pown.p,
                      (const uint32_t*)d_sf.p, (const uint32_t*)d_psh.p, U, nsets, (uint32_t*)d_cnt.p);
-  G2S_SCAN(d_cnt.p, d_base.p, (size_t)nsets + 1);
+  G2S_HIP_TRY(exclusive_scan((const uint32_t*)d_cnt.p, (uint32_t*)d_base.p, (size_t)nsets + 1));
   std::vector<uint32_t> lo32((size_t)nsets + 1, 0);
-  G2S_GPU_TRY(hipMemcpy(lo32.data(), d_base.p, lo32.size() * 4, hipMemcpyDeviceToHost));
+  G2S_HIP_TRY(hipMemcpy(lo32.data(), d_base.p, lo32.size() * 4, hipMemcpyDeviceToHost));
   const uint32_t n_solid = lo32[nsets];
   std::vector<KT> host((size_t)n_solid);
   std::vector<uint32_t> rs((size_t)n_solid);
   if (n_solid) {
-    G2S_GPU_TRY(d_out.alloc((size_t)n_solid * sizeof(KT)));
-    G2S_GPU_TRY(d_osid.alloc((size_t)n_solid * 4));
+    G2S_HIP_TRY(d_out.alloc((size_t)n_solid * sizeof(KT)));
+    G2S_HIP_TRY(d_osid.alloc((size_t)n_solid * 4));
     if (nruns) {
       hipLaunchKernelGGL(k_pool_write_own<KT>, grid(nruns), blk, 0, 0, (const KT*)d_rkey.p, (const uint32_t*)d_rset.p, nruns,
                          (const uint32_t*)d_kown.p, (const uint32_t*)d_pown.p, (const uint32_t*)d_rlo.p, (const uint32_t*)d_sf.p,
@@ -1676,17 +1572,15 @@ static bool count_solid_pool_gpu_t(Graph& g, std::vector<KT>& out, std::vector<u
                          (const uint32_t*)d_ksh.p, (const uint32_t*)d_psh.p, (const uint32_t*)d_rlo.p, (const KT*)d_rkey.p,
                          (const uint32_t*)d_pown.p, (const uint32_t*)d_base.p, (KT*)d_out.p, (uint32_t*)d_osid.p);
     }
-    G2S_GPU_TRY(hipMemcpy(host.data(), d_out.p, (size_t)n_solid * sizeof(KT), hipMemcpyDeviceToHost));
-    G2S_GPU_TRY(hipMemcpy(rs.data(), d_osid.p, (size_t)n_solid * 4, hipMemcpyDeviceToHost));
+    G2S_HIP_TRY(hipMemcpy(host.data(), d_out.p, (size_t)n_solid * sizeof(KT), hipMemcpyDeviceToHost));
+    G2S_HIP_TRY(hipMemcpy(rs.data(), d_osid.p, (size_t)n_solid * 4, hipMemcpyDeviceToHost));
   }
-  G2S_GPU_TRY(hipGetLastError());
+  G2S_HIP_TRY(hipGetLastError());
   out.swap(host);
   rank_set->swap(rs);
   g.n = n_solid;
   g.set_lo.assign(lo32.begin(), lo32.end());
   return true;
-#undef G2S_SCAN
-#undef G2S_GPU_TRY
 }
 
 bool graph_build_pool_gpu(Graph& g, const PoolSets& ps, int solid, int device,

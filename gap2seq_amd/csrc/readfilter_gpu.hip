@@ -21,21 +21,15 @@
 #include <string>
 #include <vector>
 
-#include <rocprim/rocprim.hpp>
-
 #include "../../include/g2s.h"
+#include "hip_host.h"
 #include "readfilter_gaps.hpp"
 
 namespace {
 
 constexpr int kWave = 64;
 
-struct Dev {
-  void* p = nullptr;
-  ~Dev() { if (p) (void)hipFree(p); }
-  hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
-  template <class T> T* as() const { return (T*)p; }
-};
+int hip_code(hipError_t e) { return e == hipErrorOutOfMemory ? G2S_ERR_NOMEM : G2S_ERR_HIP; }  // (G2S_HIP_TRY_CODE)
 
 __device__ __forceinline__ uint64_t lower_bound_u64(const uint64_t* __restrict__ a, uint64_t n, uint64_t key) {
   uint64_t lo = 0, hi = n;
@@ -135,18 +129,10 @@ bool filter_device_usable(int device) {
 }
 
 int filter_join_device(FilterJoin& j, int device, std::string* err) {
-#define G2S_RF_TRY(expr)                                                                                  \
-  do {                                                                                                    \
-    hipError_t e_ = (expr);                                                                               \
-    if (e_ != hipSuccess) {                                                                               \
-      *err = std::string(#expr) + ": " + hipGetErrorString(e_);                                           \
-      return e_ == hipErrorOutOfMemory ? G2S_ERR_NOMEM : G2S_ERR_HIP;                                     \
-    }                                                                                                     \
-  } while (0)
-#define G2S_RF_CAP(count)                                                                                 \
-  do {                                                                                                    \
-    if ((count) > j.max_pairs) { *err = "more filter pairs than the cap (G2S_FILTER_MAX_PAIRS)"; return G2S_ERR_NOMEM; } \
-  } while (0)
+  auto over_cap = [&](uint64_t count) {
+    if (count > j.max_pairs) *err = "more filter pairs than the cap (G2S_FILTER_MAX_PAIRS)";
+    return count > j.max_pairs;
+  };
   const FilterRows& R = *j.rows;
   const DeviceRows* DR = j.device_rows;
   const uint64_t nr = DR ? DR->n : R.size();
@@ -154,26 +140,27 @@ int filter_join_device(FilterJoin& j, int device, std::string* err) {
   const uint32_t n = (uint32_t)j.gaps();
   j.list1.clear();
   j.list2.clear();
-  G2S_RF_TRY(hipSetDevice(device));
+  G2S_HIP_TRY_CODE(hipSetDevice(device));
   if (!nr || !j.bits || !n) return G2S_OK;  // (no records: the filter is empty and no window holds anything)
   const dim3 blk(256), grdR((unsigned)((nr + 255) / 256));
-  // ---- rows up, bits, index
-  Dev d_ref, d_pos, d_end, d_flag, d_own, d_mate, d_ikey, d_irow, d_ikey2, d_irow2, d_win, d_tmp;
-  G2S_RF_TRY(d_win.alloc(j.win.size() * sizeof(FilterWindow)));
-  G2S_RF_TRY(hipMemcpy(d_win.p, j.win.data(), j.win.size() * sizeof(FilterWindow), hipMemcpyHostToDevice));
+  // ---- rows up
+  DevMem d_ref, d_pos, d_end, d_flag, d_own, d_mate, d_ikey, d_irow, d_ikey2, d_irow2, d_win;
+  Scratch d_tmp;
+  G2S_HIP_TRY_CODE(d_win.alloc(j.win.size() * sizeof(FilterWindow)));
+  G2S_HIP_TRY_CODE(hipMemcpy(d_win.p, j.win.data(), j.win.size() * sizeof(FilterWindow), hipMemcpyHostToDevice));
   if (!DR) {
-    G2S_RF_TRY(d_ref.alloc(nr * 4));
-    G2S_RF_TRY(d_pos.alloc(nr * 4));
-    G2S_RF_TRY(d_end.alloc(nr * 8));
-    G2S_RF_TRY(d_flag.alloc(nr * 4));
-    G2S_RF_TRY(d_own.alloc(nr * 8));
-    G2S_RF_TRY(d_mate.alloc(nr * 8));
-    G2S_RF_TRY(hipMemcpy(d_ref.p, R.ref_id.data(), nr * 4, hipMemcpyHostToDevice));
-    G2S_RF_TRY(hipMemcpy(d_pos.p, R.pos.data(), nr * 4, hipMemcpyHostToDevice));
-    G2S_RF_TRY(hipMemcpy(d_end.p, R.end.data(), nr * 8, hipMemcpyHostToDevice));
-    G2S_RF_TRY(hipMemcpy(d_flag.p, R.flag.data(), nr * 4, hipMemcpyHostToDevice));
-    G2S_RF_TRY(hipMemcpy(d_own.p, R.h_own.data(), nr * 8, hipMemcpyHostToDevice));
-    G2S_RF_TRY(hipMemcpy(d_mate.p, R.h_mate.data(), nr * 8, hipMemcpyHostToDevice));
+    G2S_HIP_TRY_CODE(d_ref.alloc(nr * 4));
+    G2S_HIP_TRY_CODE(d_pos.alloc(nr * 4));
+    G2S_HIP_TRY_CODE(d_end.alloc(nr * 8));
+    G2S_HIP_TRY_CODE(d_flag.alloc(nr * 4));
+    G2S_HIP_TRY_CODE(d_own.alloc(nr * 8));
+    G2S_HIP_TRY_CODE(d_mate.alloc(nr * 8));
+    G2S_HIP_TRY_CODE(hipMemcpy(d_ref.p, R.ref_id.data(), nr * 4, hipMemcpyHostToDevice));
+    G2S_HIP_TRY_CODE(hipMemcpy(d_pos.p, R.pos.data(), nr * 4, hipMemcpyHostToDevice));
+    G2S_HIP_TRY_CODE(hipMemcpy(d_end.p, R.end.data(), nr * 8, hipMemcpyHostToDevice));
+    G2S_HIP_TRY_CODE(hipMemcpy(d_flag.p, R.flag.data(), nr * 4, hipMemcpyHostToDevice));
+    G2S_HIP_TRY_CODE(hipMemcpy(d_own.p, R.h_own.data(), nr * 8, hipMemcpyHostToDevice));
+    G2S_HIP_TRY_CODE(hipMemcpy(d_mate.p, R.h_mate.data(), nr * 8, hipMemcpyHostToDevice));
   }
   // (rows that pass A left on the device are read where they lie, and stay their owner's)
   const int32_t* p_ref = DR ? DR->ref_id : d_ref.as<int32_t>();
@@ -182,109 +169,85 @@ int filter_join_device(FilterJoin& j, int device, std::string* err) {
   const uint32_t* p_flag = DR ? DR->flag : d_flag.as<uint32_t>();
   uint64_t* p_own = DR ? DR->h_own : d_own.as<uint64_t>();
   uint64_t* p_mate = DR ? DR->h_mate : d_mate.as<uint64_t>();
-  G2S_RF_TRY(d_ikey.alloc(nr * 8));
-  G2S_RF_TRY(d_irow.alloc(nr * 4));
-  G2S_RF_TRY(d_ikey2.alloc(nr * 8));
-  G2S_RF_TRY(d_irow2.alloc(nr * 4));
+  // ---- 1, 2: bits, and the index sorted
+  G2S_HIP_TRY_CODE(d_ikey.alloc(nr * 8));
+  G2S_HIP_TRY_CODE(d_irow.alloc(nr * 4));
+  G2S_HIP_TRY_CODE(d_ikey2.alloc(nr * 8));
+  G2S_HIP_TRY_CODE(d_irow2.alloc(nr * 4));
   hipLaunchKernelGGL(k_bits, grdR, blk, 0, 0, p_own, p_mate, (uint32_t)nr, j.bits, p_ref, p_pos, d_ikey.as<uint64_t>(),
                      d_irow.as<uint32_t>());
-  G2S_RF_TRY(hipGetLastError());
-  size_t tb = 0;
-  G2S_RF_TRY(rocprim::radix_sort_pairs(nullptr, tb, d_ikey.as<uint64_t>(), d_ikey2.as<uint64_t>(), d_irow.as<uint32_t>(),
-                                       d_irow2.as<uint32_t>(), (size_t)nr, 0, 64));
-  G2S_RF_TRY(d_tmp.alloc(tb));
-  G2S_RF_TRY(rocprim::radix_sort_pairs(d_tmp.p, tb, d_ikey.as<uint64_t>(), d_ikey2.as<uint64_t>(), d_irow.as<uint32_t>(),
-                                       d_irow2.as<uint32_t>(), (size_t)nr, 0, 64));
+  G2S_HIP_TRY_CODE(hipGetLastError());
+  G2S_HIP_TRY_CODE(radix_sort_pairs(d_tmp, d_ikey.as<uint64_t>(), d_ikey2.as<uint64_t>(), d_irow.as<uint32_t>(),
+                                    d_irow2.as<uint32_t>(), (size_t)nr));
   const uint64_t* ikey = d_ikey2.as<uint64_t>();
   const uint32_t* irow = d_irow2.as<uint32_t>();
-  // the scan of a count array into offsets; returns the total
-  Dev d_misc;
-  G2S_RF_TRY(d_misc.alloc(16));
-  G2S_RF_TRY(hipMemset(d_misc.p, 0, 16));
-  auto scan = [&](const uint64_t* cnt, uint64_t* off, uint64_t m, uint64_t* total) -> hipError_t {
-    size_t sb = 0;
-    hipError_t e = rocprim::exclusive_scan(nullptr, sb, cnt, off, (uint64_t)0, (size_t)m, rocprim::plus<uint64_t>());
-    if (e != hipSuccess) return e;
-    Dev s;
-    if ((e = s.alloc(sb)) != hipSuccess) return e;
-    if ((e = rocprim::exclusive_scan(s.p, sb, cnt, off, (uint64_t)0, (size_t)m, rocprim::plus<uint64_t>())) != hipSuccess) return e;
-    uint64_t last[2] = {0, 0};
-    if ((e = hipMemcpy(&last[0], cnt + (m - 1), 8, hipMemcpyDeviceToHost)) != hipSuccess) return e;
-    if ((e = hipMemcpy(&last[1], off + (m - 1), 8, hipMemcpyDeviceToHost)) != hipSuccess) return e;
-    *total = last[0] + last[1];
-    return hipSuccess;
-  };
-  // ---- every gap's filter keys: count, scan, write, sort, unique
-  Dev d_gcnt, d_goff, d_bk, d_bk2, d_U;
-  G2S_RF_TRY(d_gcnt.alloc((size_t)n * 8));
-  G2S_RF_TRY(d_goff.alloc((size_t)n * 8));
+  DevMem d_misc;
+  G2S_HIP_TRY_CODE(d_misc.alloc(16));
+  G2S_HIP_TRY_CODE(hipMemset(d_misc.p, 0, 16));
+  // ---- 3: every gap's filter keys: count, scan, write, sort, unique
+  DevMem d_gcnt, d_goff, d_bk, d_bk2, d_U;
+  G2S_HIP_TRY_CODE(d_gcnt.alloc((size_t)n * 8));
+  G2S_HIP_TRY_CODE(d_goff.alloc((size_t)n * 8));
   hipLaunchKernelGGL((k_gap<0, false>), dim3(n), dim3(kWave), 0, 0, d_win.as<FilterWindow>(), n, ikey, irow, nr,
                      p_end, p_flag, p_own, (const uint64_t*)nullptr, (uint64_t)0,
                      max_span, d_gcnt.as<uint64_t>(), (const uint64_t*)nullptr, (uint64_t*)nullptr);
-  G2S_RF_TRY(hipGetLastError());
+  G2S_HIP_TRY_CODE(hipGetLastError());
   uint64_t nb = 0;
-  G2S_RF_TRY(scan(d_gcnt.as<uint64_t>(), d_goff.as<uint64_t>(), n, &nb));
-  G2S_RF_CAP(nb);
+  G2S_HIP_TRY_CODE(scan_total(d_gcnt.as<const uint64_t>(), d_goff.as<uint64_t>(), n, &nb));
+  if (over_cap(nb)) return G2S_ERR_NOMEM;
   uint64_t nu = 0;
-  G2S_RF_TRY(d_U.alloc(nb * 8));
+  G2S_HIP_TRY_CODE(d_U.alloc(nb * 8));
   if (nb) {
-    G2S_RF_TRY(d_bk.alloc(nb * 8));
-    G2S_RF_TRY(d_bk2.alloc(nb * 8));
+    G2S_HIP_TRY_CODE(d_bk.alloc(nb * 8));
+    G2S_HIP_TRY_CODE(d_bk2.alloc(nb * 8));
     hipLaunchKernelGGL((k_gap<0, true>), dim3(n), dim3(kWave), 0, 0, d_win.as<FilterWindow>(), n, ikey, irow, nr,
                        p_end, p_flag, p_own, (const uint64_t*)nullptr,
                        (uint64_t)0, max_span, (uint64_t*)nullptr, d_goff.as<const uint64_t>(), d_bk.as<uint64_t>());
-    G2S_RF_TRY(hipGetLastError());
-    size_t sb = 0;
-    G2S_RF_TRY(rocprim::radix_sort_keys(nullptr, sb, d_bk.as<uint64_t>(), d_bk2.as<uint64_t>(), (size_t)nb, 0, 64));
-    Dev s;
-    G2S_RF_TRY(s.alloc(sb));
-    G2S_RF_TRY(rocprim::radix_sort_keys(s.p, sb, d_bk.as<uint64_t>(), d_bk2.as<uint64_t>(), (size_t)nb, 0, 64));
-    size_t ub = 0;
-    G2S_RF_TRY(rocprim::unique(nullptr, ub, d_bk2.as<uint64_t>(), d_U.as<uint64_t>(), d_misc.as<uint64_t>(), (size_t)nb));
-    Dev s2;
-    G2S_RF_TRY(s2.alloc(ub));
-    G2S_RF_TRY(rocprim::unique(s2.p, ub, d_bk2.as<uint64_t>(), d_U.as<uint64_t>(), d_misc.as<uint64_t>(), (size_t)nb));
-    G2S_RF_TRY(hipMemcpy(&nu, d_misc.p, 8, hipMemcpyDeviceToHost));
+    G2S_HIP_TRY_CODE(hipGetLastError());
+    Scratch s, s2;
+    G2S_HIP_TRY_CODE(radix_sort_keys(s, d_bk.as<uint64_t>(), d_bk2.as<uint64_t>(), (size_t)nb));
+    G2S_HIP_TRY_CODE(unique(s2, d_bk2.as<uint64_t>(), d_U.as<uint64_t>(), d_misc.as<uint64_t>(), (size_t)nb));
+    G2S_HIP_TRY_CODE(hipMemcpy(&nu, d_misc.p, 8, hipMemcpyDeviceToHost));
   }
   const uint64_t* U = d_U.as<uint64_t>();
-  // ---- list 1: count per row, scan, write, sort
+  // ---- 4: list 1: count per row, scan, write
   uint64_t n1 = 0;
-  Dev d_l1, d_l1s;
+  DevMem d_l1, d_l1s;
   if (nu) {
-    Dev d_rcnt, d_roff;
-    G2S_RF_TRY(d_rcnt.alloc(nr * 8));
-    G2S_RF_TRY(d_roff.alloc(nr * 8));
+    DevMem d_rcnt, d_roff;
+    G2S_HIP_TRY_CODE(d_rcnt.alloc(nr * 8));
+    G2S_HIP_TRY_CODE(d_roff.alloc(nr * 8));
     hipLaunchKernelGGL((k_mates<false>), grdR, blk, 0, 0, p_mate, (uint32_t)nr, U, nu, d_rcnt.as<uint64_t>(),
                        (const uint64_t*)nullptr, (uint64_t*)nullptr);
-    G2S_RF_TRY(hipGetLastError());
-    G2S_RF_TRY(scan(d_rcnt.as<uint64_t>(), d_roff.as<uint64_t>(), nr, &n1));
-    G2S_RF_CAP(nb + n1);
+    G2S_HIP_TRY_CODE(hipGetLastError());
+    G2S_HIP_TRY_CODE(scan_total(d_rcnt.as<const uint64_t>(), d_roff.as<uint64_t>(), nr, &n1));
+    if (over_cap(nb + n1)) return G2S_ERR_NOMEM;
     if (n1) {
-      G2S_RF_TRY(d_l1.alloc(n1 * 8));
-      G2S_RF_TRY(d_l1s.alloc(n1 * 8));
+      G2S_HIP_TRY_CODE(d_l1.alloc(n1 * 8));
+      G2S_HIP_TRY_CODE(d_l1s.alloc(n1 * 8));
       hipLaunchKernelGGL((k_mates<true>), grdR, blk, 0, 0, p_mate, (uint32_t)nr, U, nu, (uint64_t*)nullptr,
                          d_roff.as<const uint64_t>(), d_l1.as<uint64_t>());
-      G2S_RF_TRY(hipGetLastError());
+      G2S_HIP_TRY_CODE(hipGetLastError());
     }
   }
-  // ---- list 2: count per gap, scan, write
+  // ---- 5: list 2: count per gap, scan, write
   uint64_t n2 = 0;
-  Dev d_l2, d_l2s;
+  DevMem d_l2, d_l2s;
   hipLaunchKernelGGL((k_gap<1, false>), dim3(n), dim3(kWave), 0, 0, d_win.as<FilterWindow>(), n, ikey, irow, nr,
                      p_end, p_flag, p_own, U, nu, max_span,
                      d_gcnt.as<uint64_t>(), (const uint64_t*)nullptr, (uint64_t*)nullptr);
-  G2S_RF_TRY(hipGetLastError());
-  G2S_RF_TRY(scan(d_gcnt.as<uint64_t>(), d_goff.as<uint64_t>(), n, &n2));
-  G2S_RF_CAP(nb + n1 + n2);
+  G2S_HIP_TRY_CODE(hipGetLastError());
+  G2S_HIP_TRY_CODE(scan_total(d_gcnt.as<const uint64_t>(), d_goff.as<uint64_t>(), n, &n2));
+  if (over_cap(nb + n1 + n2)) return G2S_ERR_NOMEM;
   if (n2) {
-    G2S_RF_TRY(d_l2.alloc(n2 * 8));
-    G2S_RF_TRY(d_l2s.alloc(n2 * 8));
+    G2S_HIP_TRY_CODE(d_l2.alloc(n2 * 8));
+    G2S_HIP_TRY_CODE(d_l2s.alloc(n2 * 8));
     hipLaunchKernelGGL((k_gap<1, true>), dim3(n), dim3(kWave), 0, 0, d_win.as<FilterWindow>(), n, ikey, irow, nr,
                        p_end, p_flag, p_own, U, nu, max_span, (uint64_t*)nullptr,
                        d_goff.as<const uint64_t>(), d_l2.as<uint64_t>());
-    G2S_RF_TRY(hipGetLastError());
+    G2S_HIP_TRY_CODE(hipGetLastError());
   }
-  // ---- both lists in (gap, row) order, down
+  // ---- 6: both lists in (gap, row) order, down
   int end_bit = 33;
   while (end_bit < 64 && ((uint64_t)1 << (end_bit - 32)) < (uint64_t)n) end_bit++;
   for (int l = 0; l < 2; l++) {
@@ -292,19 +255,14 @@ int filter_join_device(FilterJoin& j, int device, std::string* err) {
     if (!m) continue;
     uint64_t* in = (l == 0 ? d_l1 : d_l2).as<uint64_t>();
     uint64_t* outp = (l == 0 ? d_l1s : d_l2s).as<uint64_t>();
-    size_t sb = 0;
-    G2S_RF_TRY(rocprim::radix_sort_keys(nullptr, sb, in, outp, (size_t)m, 0, end_bit));
-    Dev s;
-    G2S_RF_TRY(s.alloc(sb));
-    G2S_RF_TRY(rocprim::radix_sort_keys(s.p, sb, in, outp, (size_t)m, 0, end_bit));
+    Scratch s;
+    G2S_HIP_TRY_CODE(radix_sort_keys(s, in, outp, (size_t)m, end_bit));
     std::vector<uint64_t>& dst = l == 0 ? j.list1 : j.list2;
     dst.resize((size_t)m);
-    G2S_RF_TRY(hipMemcpy(dst.data(), outp, m * 8, hipMemcpyDeviceToHost));
+    G2S_HIP_TRY_CODE(hipMemcpy(dst.data(), outp, m * 8, hipMemcpyDeviceToHost));
   }
-  G2S_RF_TRY(hipDeviceSynchronize());
+  G2S_HIP_TRY_CODE(hipDeviceSynchronize());
   return G2S_OK;
-#undef G2S_RF_TRY
-#undef G2S_RF_CAP
 }
 
 }  // namespace g2s

@@ -16,6 +16,7 @@
 
 #include "dbg.hpp"
 #include "seg_tables.h"
+#include "hip_host.h"
 
 namespace {
 
@@ -109,48 +110,44 @@ __global__ __launch_bounds__(256) void k_brec(const uint32_t* __restrict__ succ,
 
 namespace g2s {
 
+// what a table's build ends with: the launch's error, the wait, and the table handed to the caller (else freed)
+static hipError_t keep_table(DevMem& table, uint32_t** out) {
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e == hipSuccess) *out = (uint32_t*)table.release();
+  return e;
+}
+
 hipError_t build_brec_table(const uint32_t* succ_dev, const uint32_t* pred_dev, const uint32_t* rem_dev, uint64_t n,
                             uint32_t** brec_out) {
   *brec_out = nullptr;
   if (n == 0) return hipSuccess;
-  uint32_t* brec = nullptr;
-  hipError_t e = hipMalloc((void**)&brec, (size_t)n * 64 + 64);
+  DevMem brec;
+  const hipError_t e = brec.alloc((size_t)n * 64 + 64);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_brec, dim3((unsigned)((2 * n + 255) / 256)), dim3(256), 0, 0, succ_dev, pred_dev, rem_dev, 2 * n, (uint4*)brec);
-  e = hipGetLastError();
-  if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (e != hipSuccess) { (void)hipFree(brec); return e; }
-  *brec_out = brec;
-  return hipSuccess;
+  hipLaunchKernelGGL(k_brec, dim3((unsigned)((2 * n + 255) / 256)), dim3(256), 0, 0, succ_dev, pred_dev, rem_dev, 2 * n, brec.as<uint4>());
+  return keep_table(brec, brec_out);
 }
 
 hipError_t build_urec_table(const uint32_t* succ_dev, const uint32_t* rem_dev, uint64_t n, uint32_t** urec_out) {
   *urec_out = nullptr;
   if (n == 0) return hipSuccess;
-  uint32_t* urec = nullptr;
-  hipError_t e = hipMalloc((void**)&urec, (size_t)n * 64 + 64);
+  DevMem urec;
+  const hipError_t e = urec.alloc((size_t)n * 64 + 64);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_urec, dim3((unsigned)((2 * n + 255) / 256)), dim3(256), 0, 0, succ_dev, rem_dev, 2 * n, (uint4*)urec);
-  e = hipGetLastError();
-  if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (e != hipSuccess) { (void)hipFree(urec); return e; }
-  *urec_out = urec;
-  return hipSuccess;
+  hipLaunchKernelGGL(k_urec, dim3((unsigned)((2 * n + 255) / 256)), dim3(256), 0, 0, succ_dev, rem_dev, 2 * n, urec.as<uint4>());
+  return keep_table(urec, urec_out);
 }
 
 hipError_t build_rem_table(const uint64_t* ustart_dev, uint64_t n, uint32_t** rem_out) {
   *rem_out = nullptr;
   if (n == 0) return hipSuccess;
-  uint32_t* rem = nullptr;
-  hipError_t e = hipMalloc((void**)&rem, (size_t)n * 8 + 64);
+  DevMem rem;
+  const hipError_t e = rem.alloc((size_t)n * 8 + 64);
   if (e != hipSuccess) return e;
   const uint64_t nwords = (n + 63) / 64;
-  hipLaunchKernelGGL(k_rem, dim3((unsigned)((nwords + 3) / 4)), dim3(256), 0, 0, ustart_dev, nwords, n, rem);
-  e = hipGetLastError();
-  if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (e != hipSuccess) { (void)hipFree(rem); return e; }
-  *rem_out = rem;
-  return hipSuccess;
+  hipLaunchKernelGGL(k_rem, dim3((unsigned)((nwords + 3) / 4)), dim3(256), 0, 0, ustart_dev, nwords, n, rem.as<uint32_t>());
+  return keep_table(rem, rem_out);
 }
 
 }  // namespace g2s

@@ -274,3 +274,15 @@ def strand_flip_genome(seed, length, k, n=5, fuz=6):
             gaps.append(dict(left=g[a - k - fuz:a], right=g[b:b + k + fuz], gap_len=b - a + k, lmf=fuz, rmf=fuz,
                              true_len=b - a))
     return [g, h], gaps
+
+
+BARELY_K, BARELY_SOLID = 5, 3
+
+
+def barely_solid_reads(n_solid):
+    """Reads for k = 5 at solid = 3 of which no k-mer (n_solid 0) or exactly one (n_solid 1) is solid: a text that holds
+    every 5-mer over {A, C} once (none is another's reverse complement) as two reads, so a build finds 32 runs of two
+    copies and has nothing to keep; and a third copy of one k-mer as a read of its own."""
+    text = "AAAAACAAACCAACACAACCCACACCACCCCCAAAA"
+    assert len({text[i:i + 5] for i in range(32)}) == 32 and set(text) == set("AC") and n_solid in (0, 1)
+    return [text, text] + ["AACAC"] * n_solid

@@ -354,7 +354,14 @@ def degenerate():
     c5 = make("no-bits", rows, windows_at_rows(rng, rows, 5), 0)
     for c in (c3, c4, c5):
         assert c["model"]["rc"] == M.OK and c["model"]["list1"] == [] and c["model"]["list2"] == []
-    return [c0, c1, c2, c3, c4, c5]
+    # one row and one gap: every scan is over one element.  In the filter, the row is its own mate's bit (one list 1
+    # pair) and its flank window gives nothing (a total of zero behind a scan that ran); out of it, only list 2 has it
+    one = [(0, 90, 120), NONE, (0, 50, 200)]
+    c6 = make("one-row-one-gap", [(0, 100, 150, PAIRED | MATE_UNMAPPED | READ1, 7, 12)], one, 5)
+    assert (c6["model"]["nb"], c6["model"]["n1"], c6["model"]["n2"]) == (1, 1, 0)
+    c7 = make("one-row-one-gap-flank", [(0, 100, 150, PAIRED | READ1, 7, 12)], one, 5)
+    assert (c7["model"]["nb"], c7["model"]["n1"], c7["model"]["n2"]) == (0, 0, 1)
+    return [c0, c1, c2, c3, c4, c5, c6, c7]
 
 
 def pair_cap():

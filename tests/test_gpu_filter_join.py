@@ -7,7 +7,7 @@ span far beyond the read length, (bit, gap) keys beyond 2^63, the clamps of the 
 never runs the host joins in the device's place, so nothing here can pass without the kernels.
 
 Cost on one MI355X: this file alone, 79 tests in 7 s (pytest's own figure, the model's runs during collection
-included).  The whole `-m gpu` suite with it and with the ten libraries added to tests/filter_gap_cases.py: 455 tests
+included); the two one-row cases of degenerate() came later and make it 81.  The whole `-m gpu` suite with it and with the ten libraries added to tests/filter_gap_cases.py: 455 tests
 in 388 s; none of the added tests is among that run's 60 slowest (the 60th took 0.86 s), so the suite without them
 took between 372 and 381 s on the same machine."""
 import os

@@ -275,3 +275,28 @@ def test_graph_build_whole_graph(product, oracle, monkeypatch, capfd, k):
             gg.free()
             gh.free()
             og.free()
+
+
+@pytest.mark.parametrize("n_solid", [0, 1])
+def test_graph_build_with_no_or_one_solid_kmer(product, monkeypatch, capfd, n_solid):
+    """the edges of the device build's scans (cases.barely_solid_reads): run heads and a total of zero behind the scan
+    of their solid flags, so nothing to compact; and one k-mer kept, whose tables are scans over two elements.  Every
+    node against the host build."""
+    reads, k, solid = cases.barely_solid_reads(n_solid), cases.BARELY_K, cases.BARELY_SOLID
+    _set(monkeypatch, G2S_HOST_BUILD="1")
+    gh = product.Graph.from_seqs(reads, k, solid)
+    _set(monkeypatch, G2S_DEBUG="1")
+    capfd.readouterr()
+    gg = product.Graph.from_seqs(reads, k, solid)
+    err = capfd.readouterr().err
+    _set(monkeypatch)
+    try:
+        assert "GPU sort" in err, err[-2000:]
+        if n_solid:  # (an empty graph has no tables to make)
+            assert any("tables, unitig order, id space:" in ln and ln.endswith("on the GPU") for ln in err.splitlines()), err[-2000:]
+        assert gg.num_kmers == gh.num_kmers == n_solid and gg.num_unitigs == gh.num_unitigs == n_solid
+        assert gg.validate() == (0, "") and gh.validate() == (0, "")
+        assert _graph_map(gg) == _graph_map(gh) and len(_graph_map(gg)) == 2 * n_solid
+    finally:
+        gg.free()
+        gh.free()

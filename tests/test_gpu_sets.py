@@ -310,3 +310,33 @@ def test_device_set_build_equals_host_set_build(product, monkeypatch, capfd, k):
     finally:
         dev.free()
         host.free()
+
+
+@pytest.mark.parametrize("n_solid", [0, 1])
+def test_device_set_build_with_no_or_one_solid_kmer(product, monkeypatch, capfd, n_solid):
+    """the edges of the keyed build's scans (cases.barely_solid_reads): runs of (set, k-mer) and a total of zero behind
+    the scan of their solid flags, and exactly one k-mer kept in one set; set by set against the host build"""
+    k, solid = cases.BARELY_K, cases.BARELY_SOLID
+    sets = [cases.barely_solid_reads(n_solid), cases.barely_solid_reads(0)[:1], []]
+    monkeypatch.delenv("G2S_HOST_BUILD", raising=False)
+    monkeypatch.setenv("G2S_DEBUG", "1")
+    capfd.readouterr()
+    dev = product.Graph.from_sets(sets, k, solid)
+    err = capfd.readouterr().err
+    monkeypatch.delenv("G2S_DEBUG")
+    monkeypatch.setenv("G2S_HOST_BUILD", "1")
+    host = product.Graph.from_sets(sets, k, solid)
+    try:
+        if n_solid:
+            assert "set graph build" in err and "on the GPU" in err, err[-2000:]
+        else:  # (the device counted, found the union empty and handed it to the host build: it did run)
+            assert "set graph on the host (size)" in err, err[-2000:]
+        assert dev.num_sets == host.num_sets == len(sets)
+        assert dev.num_kmers == host.num_kmers == n_solid and dev.num_unitigs == host.num_unitigs == n_solid
+        for s in range(len(sets)):
+            assert dev.set_nodes(s) == host.set_nodes(s) and dev.set_nodes(s)[1] == (n_solid if s == 0 else 0), "set %d" % s
+            assert _set_view(product, dev, s) == _set_view(product, host, s), "set %d" % s
+        assert dev.validate() == (0, "")
+    finally:
+        dev.free()
+        host.free()
