@@ -14,7 +14,7 @@ namespace g2s {
 
 // dbg_gpu.hip
 bool count_solid_gpu(Graph& g, const std::vector<std::pair<const char*, uint64_t>>& seqs, int solid, int device,
-                     std::string* why);
+                     std::string* why, SolidCountInfo* info);
 bool graph_finish_gpu(Graph& g, int device, const std::function<void(const std::vector<uint32_t>&, uint32_t)>& host_walk,
                       std::string* why);
 bool graph_build_sets_gpu(Graph& g, const std::vector<std::pair<const char*, uint64_t>>& seqs, const std::vector<uint32_t>& seq_set,
@@ -407,6 +407,16 @@ std::string Graph::node_string(uint32_t v) const {
   return decode_kmer<u256>(kmers256[r], strand, k);
 }
 
+namespace {
+std::mutex g_solid_info_mu;
+SolidCountInfo g_solid_info;
+}  // namespace
+
+SolidCountInfo last_solid_count() {
+  std::lock_guard<std::mutex> lk(g_solid_info_mu);
+  return g_solid_info;
+}
+
 Graph* graph_build(const std::vector<std::pair<const char*, uint64_t>>& seqs, int k, int solid, int nthreads,
                    std::string* err) {
   if (k < 1 || k > kMaxK) { if (err) *err = "k must be in [1," + std::to_string(kMaxK) + "]"; return nullptr; }
@@ -418,9 +428,11 @@ Graph* graph_build(const std::vector<std::pair<const char*, uint64_t>>& seqs, in
   const auto t0 = std::chrono::steady_clock::now();
   // the solid k-mer set: sort on the GPU when there is one (dbg_gpu.hip), host threads otherwise
   bool set_on_gpu = false;
+  SolidCountInfo info;
+  for (auto& sq : seqs) info.positions += sq.second + 1;
   if (!getenv("G2S_HOST_BUILD")) {
     std::string why;
-    set_on_gpu = count_solid_gpu(*g, seqs, solid, getenv("G2S_DEVICE") ? atoi(getenv("G2S_DEVICE")) : 0, &why);
+    set_on_gpu = count_solid_gpu(*g, seqs, solid, getenv("G2S_DEVICE") ? atoi(getenv("G2S_DEVICE")) : 0, &why, &info);
     if (!set_on_gpu && getenv("G2S_DEBUG")) fprintf(stderr, "[g2s]   k-mer set on the host (%s)\n", why.c_str());
   }
   if (!set_on_gpu) {
@@ -429,13 +441,21 @@ Graph* graph_build(const std::vector<std::pair<const char*, uint64_t>>& seqs, in
     else count_solid<u256>(*g, seqs, solid, nthreads);
   }
   const auto t1 = std::chrono::steady_clock::now();
+  if (!set_on_gpu) info.passes = info.refined_bins = 0, info.max_pass_keys = 0;
+  info.on_device = set_on_gpu ? 1 : 0;
+  info.solid = g->n;
+  {
+    std::lock_guard<std::mutex> lk(g_solid_info_mu);
+    g_solid_info = info;
+  }
+  const std::string how = !set_on_gpu ? "host" : info.passes ? "GPU, " + std::to_string(info.passes) + " key-range passes" : "GPU sort";
   if (g->n >= (1ull << 30)) { if (err) *err = "too many k-mers for 32-bit oriented node ids"; delete g; return nullptr; }
   if (g->kmer_bytes == 8) finish_graph<uint64_t>(*g, nthreads);
   else if (g->kmer_bytes == 16) finish_graph<u128>(*g, nthreads);
   else finish_graph<u256>(*g, nthreads);
   if (getenv("G2S_DEBUG"))
     fprintf(stderr, "[g2s] graph build: %llu k-mers; solid k-mer set %.3f s (%s), tables + unitig order %.3f s (%d threads)\n",
-            (unsigned long long)g->n, std::chrono::duration<double>(t1 - t0).count(), set_on_gpu ? "GPU sort" : "host",
+            (unsigned long long)g->n, std::chrono::duration<double>(t1 - t0).count(), how.c_str(),
             std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count(), nthreads);
   return g;
 }

@@ -106,6 +106,16 @@ static inline int kmer_width(int k) { return k <= 31 ? 8 : k <= 63 ? 16 : 32; }
 // seqs may contain any bytes; k-mers containing N/n are skipped (GATB model).
 Graph* graph_build(const std::vector<std::pair<const char*, uint64_t>>& seqs, int k, int solid, int nthreads,
                    std::string* err);
+// What the process's last graph_build did for its solid k-mer set (g2s_test_last_solid_count): the text positions (bases
+// + 1 a sequence), the key-range passes that ran (dbg_gpu.hip's pass form; 0: the one-sort device count, or the host), the
+// histogram bins that had to be histogrammed again, the keys of the largest pass, the solid k-mers found, and whether the
+// set was made on the device.
+struct SolidCountInfo {
+  uint64_t positions = 0, max_pass_keys = 0, solid = 0;
+  uint32_t passes = 0, refined_bins = 0;
+  int on_device = 0;
+};
+SolidCountInfo last_solid_count();
 // One graph per read set, built on `nthreads` host threads (a set per thread at a time) and concatenated set-major
 // (Graph::set_lo); seq_set[j] < nsets names the set of seqs[j].  Every set's part is what graph_build gives for its
 // sequences alone, up to the numbering of nodes.

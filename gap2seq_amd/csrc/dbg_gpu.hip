@@ -932,26 +932,34 @@ static bool finish_gpu_t(Graph& g, const std::vector<KT>& kmers, int device,
                         : finish_gpu_e<KT, false>(g, kmers, device, host_walk, why, rank_set);
 }
 
+// solid_passes.h
+template <class KT>
+static bool count_solid_passes_gpu_t(Graph& g, std::vector<KT>& out, const std::vector<std::pair<const char*, uint64_t>>& seqs,
+                                     int solid, uint64_t T, double per_key, std::string* why, SolidCountInfo* info);
+static bool solid_passes_forced();
+
 // The sorted set of solid canonical k-mers and its prefix index, from the reads.  One key per
 // text position, radix sort (rocPRIM; 128-bit keys as two stable 64-bit passes, 256-bit keys as four over
 // (word, index) pairs), run heads,
-// runs of at least `solid` copies compacted.  Returns false (g untouched) when the device
-// cannot be used or the text does not fit comfortably.
+// runs of at least `solid` copies compacted.  A text beyond one sort (2^32 positions, or half the free memory at the
+// sort's bytes a position) goes through the key-range passes of solid_passes.h, as does every text under
+// G2S_BUILD_PASS_KEYS.  Returns false (g untouched) when the device cannot be used or not even the passes fit.
 template <class KT>
 static bool count_solid_gpu_t(Graph& g, std::vector<KT>& out, const std::vector<std::pair<const char*, uint64_t>>& seqs,
-                              int solid, int device, std::string* why) {
+                              int solid, int device, std::string* why, SolidCountInfo* info) {
   if (!device_exists(device)) { if (why) *why = "no device"; return false; }
   G2S_HIP_TRY(hipSetDevice(device));
   const int k = g.k;
   uint64_t T = 0;
   for (auto& sq : seqs) T += sq.second + 1;  // one separator after every sequence
-  if (T == 0 || T >= (1ull << 32)) { if (why) *why = "text size"; return false; }
+  if (T == 0) { if (why) *why = "text size"; return false; }
   size_t free_b = 0, total_b = 0;
   G2S_HIP_TRY(hipMemGetInfo(&free_b, &total_b));
   // (bytes a text position at the sort's peak: keys, sorted copy or split words, the sort's scratch; 256-bit keys:
   // the keys, the word and index double buffers, the sort's scratch, then the keys and their gathered copy)
   const double per_pos = sizeof(KT) == 32 ? (double)(2 * sizeof(KT) + 40) : (double)(4 * sizeof(KT) + 24);
-  if ((double)T * per_pos > 0.5 * (double)free_b) { if (why) *why = "text too large for the device"; return false; }
+  if (T >= (1ull << 32) || (double)T * per_pos > 0.5 * (double)free_b || solid_passes_forced())
+    return count_solid_passes_gpu_t<KT>(g, out, seqs, solid, T, per_pos, why, info);
   std::vector<uint8_t> text((size_t)T);
   {
     size_t pos = 0;
@@ -1599,11 +1607,17 @@ bool graph_build_pool_gpu(Graph& g, const PoolSets& ps, int solid, int device,
   return ok;
 }
 
+}  // namespace g2s
+
+#include "solid_passes.h"
+
+namespace g2s {
+
 bool count_solid_gpu(Graph& g, const std::vector<std::pair<const char*, uint64_t>>& seqs, int solid, int device,
-                     std::string* why) {
-  if (g.kmer_bytes == 32) return count_solid_gpu_t<u256>(g, g.kmers256, seqs, solid, device, why);
-  return g.kmer_bytes == 16 ? count_solid_gpu_t<u128>(g, g.kmers128, seqs, solid, device, why)
-                            : count_solid_gpu_t<uint64_t>(g, g.kmers64, seqs, solid, device, why);
+                     std::string* why, SolidCountInfo* info) {
+  if (g.kmer_bytes == 32) return count_solid_gpu_t<u256>(g, g.kmers256, seqs, solid, device, why, info);
+  return g.kmer_bytes == 16 ? count_solid_gpu_t<u128>(g, g.kmers128, seqs, solid, device, why, info)
+                            : count_solid_gpu_t<uint64_t>(g, g.kmers64, seqs, solid, device, why, info);
 }
 
 bool graph_finish_gpu(Graph& g, int device, const std::function<void(const std::vector<uint32_t>&, uint32_t)>& host_walk,

@@ -37,6 +37,7 @@
 #include "fill_seg.h"
 #include "flank_lookup.h"
 #include "glibc_rand.hpp"
+#include "pass_plan.hpp"
 #include "post.hpp"
 #include "seg_tables.h"
 
@@ -250,6 +251,28 @@ extern "C" int g2s_test_last_pool_build(uint64_t* own_positions, uint64_t* share
   if (shared_positions) *shared_positions = info.shared_positions;
   if (keys_sorted) *keys_sorted = info.keys_sorted;
   if (on_device) *on_device = info.on_device;
+  return G2S_OK;
+}
+// TEST HOOK (include/g2s_test.h)
+extern "C" int g2s_test_last_solid_count(uint64_t* positions, uint32_t* passes, uint32_t* refined_bins, uint64_t* max_pass_keys,
+                                         uint64_t* solid, int* on_device) {
+  const SolidCountInfo info = last_solid_count();
+  if (positions) *positions = info.positions;
+  if (passes) *passes = info.passes;
+  if (refined_bins) *refined_bins = info.refined_bins;
+  if (max_pass_keys) *max_pass_keys = info.max_pass_keys;
+  if (solid) *solid = info.solid;
+  if (on_device) *on_device = info.on_device;
+  return G2S_OK;
+}
+// TEST HOOK (include/g2s_test.h)
+extern "C" int g2s_test_plan_passes(const uint64_t* hist, uint32_t nbins, uint64_t cap, uint32_t* first_bin_of_pass,
+                                    uint32_t max_passes, uint32_t* npasses, uint32_t* first_oversized_bin) {
+  if ((!hist && nbins) || (!first_bin_of_pass && max_passes) || !npasses)
+    return fail(G2S_ERR_ARG, "g2s_test_plan_passes: bad argument");
+  std::vector<uint32_t> first_bin;
+  *npasses = plan_passes(hist, nbins, cap, &first_bin, first_oversized_bin);
+  for (uint32_t p = 0; p < std::min(*npasses, max_passes); p++) first_bin_of_pass[p] = first_bin[p];
   return G2S_OK;
 }
 extern "C" uint32_t g2s_graph_num_sets(const g2s_graph* g) { return g ? g->g->num_sets() : 0; }

@@ -1,6 +1,6 @@
 // gap2seq_amd/csrc/hip_host.h — the host side's plumbing around HIP and rocPRIM, once, for the .hip files of the graph
 // build and the read filter (dbg_gpu, readfilter_gpu, bam_rows, bam_text, bgzf_inflate, seg_tables): an owned device
-// allocation, "run this HIP call or leave with its text", rocPRIM's two-call protocol, scan-and-total, "is there such a
+// allocation, page-locked buffer and event, "run this HIP call or leave with its text", rocPRIM's two-call protocol, scan-and-total, "is there such a
 // device".  Host only; no kernel, no other project header.  (g2s_api.hip's DevBuf / PinBuf are grow-only session buffers,
 // another thing.)
 #pragma once
@@ -32,6 +32,24 @@ struct DevMem {
   void free() { if (p) (void)hipFree(release()); }
   void* release() { void* q = p; p = nullptr; return q; }  // the caller owns it from here (DeviceGraph's kept tables)
   template <class T> T* as() const { return (T*)p; }
+};
+
+// ---- an owned page-locked host allocation (a staging buffer of an asynchronous copy) and an owned event
+struct PinMem {
+  void* p = nullptr;
+  PinMem() = default;
+  PinMem(const PinMem&) = delete;
+  PinMem& operator=(const PinMem&) = delete;
+  ~PinMem() { if (p) (void)hipHostFree(p); }
+  hipError_t alloc(size_t bytes) { return hipHostMalloc(&p, bytes ? bytes : 16, hipHostMallocDefault); }
+};
+struct DevEvent {
+  hipEvent_t e = nullptr;
+  DevEvent() = default;
+  DevEvent(const DevEvent&) = delete;
+  DevEvent& operator=(const DevEvent&) = delete;
+  ~DevEvent() { if (e) (void)hipEventDestroy(e); }
+  hipError_t create() { return hipEventCreateWithFlags(&e, hipEventDisableTiming); }
 };
 
 // ---- "<expression>: <error string>", and the ways to leave with it

@@ -132,6 +132,10 @@ _SIGS = {
                                            C.POINTER(C.c_uint32), C.POINTER(C.c_int)]),
     "g2s_test_last_pool_build": (C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
                                            C.POINTER(C.c_int)]),
+    "g2s_test_last_solid_count": (C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                            C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int)]),
+    "g2s_test_plan_passes": (C.c_int, [C.POINTER(C.c_uint64), C.c_uint32, C.c_uint64, C.POINTER(C.c_uint32), C.c_uint32,
+                                       C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "g2s_test_seg_back_record": (C.c_int, [_VP, C.c_int, C.c_uint32, C.POINTER(C.c_uint32)]),
     "g2s_graph_num_sets": (C.c_uint32, [_VP]),
     "g2s_graph_set_nodes": (C.c_int, [_VP, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
@@ -1114,6 +1118,28 @@ def test_last_pool_build():
     a, b, c, d = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_int()
     _check(load_library().g2s_test_last_pool_build(C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
     return dict(own_positions=a.value, shared_positions=b.value, keys_sorted=c.value, on_device=d.value)
+
+
+def test_last_solid_count():
+    """g2s_test_last_solid_count: dict(positions, passes, refined_bins, max_pass_keys, solid, on_device) of the last
+    single-graph build's solid k-mer count (passes == 0: the one-sort device count, or the host count)"""
+    pos, mx, so = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    ps, rf, on = C.c_uint32(), C.c_uint32(), C.c_int()
+    _check(load_library().g2s_test_last_solid_count(C.byref(pos), C.byref(ps), C.byref(rf), C.byref(mx), C.byref(so), C.byref(on)))
+    return dict(positions=pos.value, passes=ps.value, refined_bins=rf.value, max_pass_keys=mx.value, solid=so.value,
+                on_device=on.value)
+
+
+def test_plan_passes(hist, cap):
+    """TEST HOOK binding (g2s_test_plan_passes): (the first bin of every pass, the first bin with more than `cap` keys or
+    None) for the histogram `hist` cut greedily into key-range passes of at most `cap` keys"""
+    nb = len(hist)
+    h = (C.c_uint64 * max(1, nb))(*hist)
+    first = (C.c_uint32 * max(1, nb))()
+    n, over = C.c_uint32(), C.c_uint32()
+    _check(load_library().g2s_test_plan_passes(h, nb, cap, first, nb, C.byref(n), C.byref(over)))
+    assert n.value <= nb
+    return list(first[:n.value]), (over.value if over.value < nb else None)
 
 
 def test_filter_join(ref_id, pos, end, flag, h_own, h_mate, max_span, bits, windows, max_pairs, device=-1, threads=1):

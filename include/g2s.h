@@ -71,6 +71,12 @@ const char* g2s_last_error(void);
  *  is one, and the graph then already resides on that device; without a
  *  device or with G2S_HOST_BUILD=1 it runs on `nthreads` host
  *  threads.  Either way the same graph results, up to the numbering of nodes.
+ *  Read sets beyond one device sort (2^32 positions — bases + 1 a read — or half
+ *  the free device memory at 56-104 bytes a position) stay on the device: the
+ *  reads are kept there as text and the solid k-mers are counted in key-range
+ *  passes.  The host counts them only when the text does not fit beside one
+ *  pass or one k-mer alone occurs more often than a pass holds keys
+ *  (G2S_DEBUG=1 says which).  The graph itself holds fewer than 2^30 k-mers.
  * ------------------------------------------------------------------------ */
 int g2s_graph_build_files(const char* reads_csv, int k, int solid, int nthreads, g2s_graph** out);
 int g2s_graph_build_seqs(const char* const* seqs, const uint64_t* lens, int nseqs, int k, int solid,

@@ -103,6 +103,24 @@ int g2s_test_filter_join(int device, int32_t threads, uint64_t nr, const int32_t
  * pointer may be NULL. */
 int g2s_test_last_pool_build(uint64_t* own_positions, uint64_t* shared_positions, uint64_t* keys_sorted, int* on_device);
 
+/* TEST HOOK: what the process's last single-graph build (g2s_graph_build_files / g2s_graph_build_seqs) did for its solid
+ * k-mer set.  positions: bases + 1 of every sequence; passes: the key-range passes that ran on the device (0: the
+ * one-sort device count, or the host count); refined_bins: the histogram bins that held more than a pass's keys and were
+ * histogrammed again on their next bits; max_pass_keys: the keys of the largest pass (never more than
+ * G2S_BUILD_PASS_KEYS); solid: the solid k-mers found; on_device: the set was made on the device (0 also when the
+ * device count gave up and the host count took over).  Any pointer may be NULL. */
+int g2s_test_last_solid_count(uint64_t* positions, uint32_t* passes, uint32_t* refined_bins, uint64_t* max_pass_keys,
+                              uint64_t* solid, int* on_device);
+
+/* TEST HOOK: the planner of the key-range passes (pass_plan.hpp) on a histogram of the caller's: nbins consecutive bins
+ * of the key space, cut greedily and in order into passes of at most cap keys — a pass is closed in front of the first
+ * bin that would take it beyond cap, empty bins join the open pass.  *npasses receives the number of passes and
+ * first_bin_of_pass[p] the first bin of pass p for p < min(*npasses, max_passes) (pass p ends where pass p + 1 begins,
+ * the last one at nbins).  A bin with more than cap keys stands alone in its pass; *first_oversized_bin (may be NULL)
+ * receives the first such bin, or nbins when there is none. */
+int g2s_test_plan_passes(const uint64_t* hist, uint32_t nbins, uint64_t cap, uint32_t* first_bin_of_pass,
+                         uint32_t max_passes, uint32_t* npasses, uint32_t* first_oversized_bin);
+
 /* TEST HOOK: what the process's last g2s_graph_build_pool_reach with at least one reach record did.  reach_sets: the
  * sets with a record; full_kmers: the k-mers of those sets' full graphs, valid when *full_known != 0 (the host build
  * counts them when it was the first choice — no device, G2S_HOST_BUILD=1; the device build never forms the
