@@ -22,7 +22,9 @@ class BgzfDevice {
   // Buffers for windows of at most max_in staged bytes, max_out inflated bytes and max_members members; `front` bytes
   // of room in front of every inflated window (for the bytes a reader carries over from the window before).  Null
   // when the device is no usable gfx950 or something could not be allocated: *why says which.
-  static BgzfDevice* create(int device, size_t max_in, size_t max_out, size_t max_members, size_t front, std::string* why);
+  // host_window false: no page-locked window (a caller whose windows all stay on the device: launch with `down` false)
+  static BgzfDevice* create(int device, size_t max_in, size_t max_out, size_t max_members, size_t front, std::string* why,
+                            bool host_window = true);
   ~BgzfDevice();
   BgzfDevice(const BgzfDevice&) = delete;
   BgzfDevice& operator=(const BgzfDevice&) = delete;

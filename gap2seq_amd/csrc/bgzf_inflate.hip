@@ -135,7 +135,8 @@ __global__ void __launch_bounds__(64) g2s_bgzf_inflate(const uint8_t* __restrict
 
 namespace g2s {
 
-BgzfDevice* BgzfDevice::create(int device, size_t max_in, size_t max_out, size_t max_members, size_t front, std::string* why) {
+BgzfDevice* BgzfDevice::create(int device, size_t max_in, size_t max_out, size_t max_members, size_t front, std::string* why,
+                               bool host_window) {
   if (!filter_device_usable(device)) {
     if (why) *why = "no usable gfx950 device " + std::to_string(device);
     return nullptr;
@@ -153,11 +154,11 @@ BgzfDevice* BgzfDevice::create(int device, size_t max_in, size_t max_out, size_t
     D->stream_ = st;
     for (Slot& s : D->s_) {
       G2S_HIP_TRY(hipHostMalloc((void**)&s.h_in, max_in + 16, hipHostMallocDefault));
-      G2S_HIP_TRY(hipHostMalloc((void**)&s.h_out, front + max_out + 16, hipHostMallocDefault));
+      if (host_window) G2S_HIP_TRY(hipHostMalloc((void**)&s.h_out, front + max_out + 16, hipHostMallocDefault));
       G2S_HIP_TRY(hipHostMalloc((void**)&s.h_mem, (max_members + 1) * sizeof(BgzfMember), hipHostMallocDefault));
       G2S_HIP_TRY(hipHostMalloc((void**)&s.h_st, (max_members + 1) * 4, hipHostMallocDefault));
       G2S_HIP_TRY(hipMalloc((void**)&s.d_in, max_in + 16));
-      G2S_HIP_TRY(hipMalloc((void**)&s.d_out, front + max_out + 64));
+      if (host_window) G2S_HIP_TRY(hipMalloc((void**)&s.d_out, front + max_out + 64));  // (else: the caller's destination)
       G2S_HIP_TRY(hipMalloc((void**)&s.d_mem, (max_members + 1) * sizeof(BgzfMember)));
       G2S_HIP_TRY(hipMalloc((void**)&s.d_st, (max_members + 1) * 4));
       hipEvent_t ev;
@@ -196,6 +197,10 @@ bool BgzfDevice::launch(int slot, size_t n_members, size_t in_bytes, size_t out_
   hipStream_t st = (hipStream_t)stream_;
   if (!fits(n_members, in_bytes, out_bytes)) {
     if (why) *why = "a window larger than the buffers";
+    return false;
+  }
+  if (!d_dst && !s.d_out) {
+    if (why) *why = "a window without a destination";
     return false;
   }
   if (d_dst && down) {

@@ -1,5 +1,6 @@
 // gap2seq_amd/csrc/dbg.cpp — see dbg.hpp.
 #include "dbg.hpp"
+#include "reads_text.h"
 
 #include <algorithm>
 #include <chrono>
@@ -13,8 +14,7 @@
 namespace g2s {
 
 // dbg_gpu.hip
-bool count_solid_gpu(Graph& g, const std::vector<std::pair<const char*, uint64_t>>& seqs, int solid, int device,
-                     std::string* why, SolidCountInfo* info);
+bool count_solid_gpu(Graph& g, const BuildInput& in, int solid, int device, std::string* why, SolidCountInfo* info);
 bool graph_finish_gpu(Graph& g, int device, const std::function<void(const std::vector<uint32_t>&, uint32_t)>& host_walk,
                       std::string* why);
 bool graph_build_sets_gpu(Graph& g, const std::vector<std::pair<const char*, uint64_t>>& seqs, const std::vector<uint32_t>& seq_set,
@@ -417,8 +417,24 @@ SolidCountInfo last_solid_count() {
   return g_solid_info;
 }
 
+namespace {
+Graph* graph_build_from(const BuildInput& in, int k, int solid, int nthreads, std::string* err, bool* gave_up);
+}
 Graph* graph_build(const std::vector<std::pair<const char*, uint64_t>>& seqs, int k, int solid, int nthreads,
                    std::string* err) {
+  BuildInput in;
+  in.seqs = &seqs;
+  return graph_build_from(in, k, solid, nthreads, err, nullptr);
+}
+Graph* graph_build_text(DeviceText* text, int k, int solid, int nthreads, std::string* err, bool* gave_up) {
+  BuildInput in;
+  in.text = text;
+  *gave_up = false;
+  return graph_build_from(in, k, solid, nthreads, err, gave_up);
+}
+
+namespace {
+Graph* graph_build_from(const BuildInput& in, int k, int solid, int nthreads, std::string* err, bool* gave_up) {
   if (k < 1 || k > kMaxK) { if (err) *err = "k must be in [1," + std::to_string(kMaxK) + "]"; return nullptr; }
   if (nthreads <= 0) nthreads = (int)std::max(1u, std::thread::hardware_concurrency());
   Graph* g = new Graph();
@@ -429,13 +445,21 @@ Graph* graph_build(const std::vector<std::pair<const char*, uint64_t>>& seqs, in
   // the solid k-mer set: sort on the GPU when there is one (dbg_gpu.hip), host threads otherwise
   bool set_on_gpu = false;
   SolidCountInfo info;
-  for (auto& sq : seqs) info.positions += sq.second + 1;
+  if (in.text) info.positions = in.text->T;
+  else for (auto& sq : *in.seqs) info.positions += sq.second + 1;
+  std::string why = "G2S_HOST_BUILD";
   if (!getenv("G2S_HOST_BUILD")) {
-    std::string why;
-    set_on_gpu = count_solid_gpu(*g, seqs, solid, getenv("G2S_DEVICE") ? atoi(getenv("G2S_DEVICE")) : 0, &why, &info);
+    set_on_gpu = count_solid_gpu(*g, in, solid, getenv("G2S_DEVICE") ? atoi(getenv("G2S_DEVICE")) : 0, &why, &info);
     if (!set_on_gpu && getenv("G2S_DEBUG")) fprintf(stderr, "[g2s]   k-mer set on the host (%s)\n", why.c_str());
   }
+  if (!set_on_gpu && in.text) {  // (the host count reads sequences: the caller loads them on the host and comes back)
+    if (err) *err = why;
+    *gave_up = true;
+    delete g;
+    return nullptr;
+  }
   if (!set_on_gpu) {
+    const auto& seqs = *in.seqs;
     if (g->kmer_bytes == 8) count_solid<uint64_t>(*g, seqs, solid, nthreads);
     else if (g->kmer_bytes == 16) count_solid<u128>(*g, seqs, solid, nthreads);
     else count_solid<u256>(*g, seqs, solid, nthreads);
@@ -459,6 +483,7 @@ Graph* graph_build(const std::vector<std::pair<const char*, uint64_t>>& seqs, in
             std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count(), nthreads);
   return g;
 }
+}  // namespace
 
 namespace {
 

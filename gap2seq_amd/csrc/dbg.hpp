@@ -106,6 +106,17 @@ static inline int kmer_width(int k) { return k <= 31 ? 8 : k <= 63 ? 16 : 32; }
 // seqs may contain any bytes; k-mers containing N/n are skipped (GATB model).
 Graph* graph_build(const std::vector<std::pair<const char*, uint64_t>>& seqs, int k, int solid, int nthreads,
                    std::string* err);
+// What the solid k-mer count reads: the caller's sequences, or a text that is already on a device (reads_text.h: every
+// sequence followed by one 'N').  The device count frees a text as soon as it has read it for the last time.
+struct DeviceText;
+struct BuildInput {
+  const std::vector<std::pair<const char*, uint64_t>>* seqs = nullptr;
+  DeviceText* text = nullptr;
+};
+// graph_build from a text on a device.  Only the device count can read it: when that gives up (G2S_HOST_BUILD, no room,
+// a HIP error) the result is nullptr with *gave_up set and the reason in *err, and the caller builds from the sequences.
+// The text is the caller's to free either way (free_device_text: what the count has freed already is not freed twice).
+Graph* graph_build_text(DeviceText* text, int k, int solid, int nthreads, std::string* err, bool* gave_up);
 // What the process's last graph_build did for its solid k-mer set (g2s_test_last_solid_count): the text positions (bases
 // + 1 a sequence), the key-range passes that ran (dbg_gpu.hip's pass form; 0: the one-sort device count, or the host), the
 // histogram bins that had to be histogrammed again, the keys of the largest pass, the solid k-mers found, and whether the

@@ -39,6 +39,7 @@
 
 #include "dbg.hpp"
 #include "hip_host.h"
+#include "reads_text.h"
 
 namespace {
 
@@ -934,8 +935,8 @@ static bool finish_gpu_t(Graph& g, const std::vector<KT>& kmers, int device,
 
 // solid_passes.h
 template <class KT>
-static bool count_solid_passes_gpu_t(Graph& g, std::vector<KT>& out, const std::vector<std::pair<const char*, uint64_t>>& seqs,
-                                     int solid, uint64_t T, double per_key, std::string* why, SolidCountInfo* info);
+static bool count_solid_passes_gpu_t(Graph& g, std::vector<KT>& out, const BuildInput& in, int solid, uint64_t T, double per_key,
+                                     std::string* why, SolidCountInfo* info);
 static bool solid_passes_forced();
 
 // The sorted set of solid canonical k-mers and its prefix index, from the reads.  One key per
@@ -945,13 +946,15 @@ static bool solid_passes_forced();
 // sort's bytes a position) goes through the key-range passes of solid_passes.h, as does every text under
 // G2S_BUILD_PASS_KEYS.  Returns false (g untouched) when the device cannot be used or not even the passes fit.
 template <class KT>
-static bool count_solid_gpu_t(Graph& g, std::vector<KT>& out, const std::vector<std::pair<const char*, uint64_t>>& seqs,
-                              int solid, int device, std::string* why, SolidCountInfo* info) {
+static bool count_solid_gpu_t(Graph& g, std::vector<KT>& out, const BuildInput& in, int solid, int device, std::string* why,
+                              SolidCountInfo* info) {
+  if (in.text) device = in.text->device;  // (where the text is)
   if (!device_exists(device)) { if (why) *why = "no device"; return false; }
   G2S_HIP_TRY(hipSetDevice(device));
   const int k = g.k;
   uint64_t T = 0;
-  for (auto& sq : seqs) T += sq.second + 1;  // one separator after every sequence
+  if (in.text) T = in.text->T;
+  else for (auto& sq : *in.seqs) T += sq.second + 1;  // one separator after every sequence
   if (T == 0) { if (why) *why = "text size"; return false; }
   size_t free_b = 0, total_b = 0;
   G2S_HIP_TRY(hipMemGetInfo(&free_b, &total_b));
@@ -959,21 +962,23 @@ static bool count_solid_gpu_t(Graph& g, std::vector<KT>& out, const std::vector<
   // the keys, the word and index double buffers, the sort's scratch, then the keys and their gathered copy)
   const double per_pos = sizeof(KT) == 32 ? (double)(2 * sizeof(KT) + 40) : (double)(4 * sizeof(KT) + 24);
   if (T >= (1ull << 32) || (double)T * per_pos > 0.5 * (double)free_b || solid_passes_forced())
-    return count_solid_passes_gpu_t<KT>(g, out, seqs, solid, T, per_pos, why, info);
-  std::vector<uint8_t> text((size_t)T);
-  {
-    size_t pos = 0;
-    for (auto& sq : seqs) { memcpy(text.data() + pos, sq.first, (size_t)sq.second); pos += (size_t)sq.second; text[pos++] = 'N'; }
-  }
+    return count_solid_passes_gpu_t<KT>(g, out, in, solid, T, per_pos, why, info);
   DevMem d_text, d_keys, d_alt, d_lo, d_hi, d_lo2, d_hi2, d_flag, d_pos, d_hidx, d_keep, d_kpos, d_out;
   Scratch d_tmp;
   DevMem d_misc;
-  G2S_HIP_TRY(d_text.alloc((size_t)T));
+  if (!in.text) {
+    std::vector<uint8_t> text((size_t)T);
+    size_t pos = 0;
+    for (auto& sq : *in.seqs) { memcpy(text.data() + pos, sq.first, (size_t)sq.second); pos += (size_t)sq.second; text[pos++] = 'N'; }
+    G2S_HIP_TRY(d_text.alloc((size_t)T));
+    G2S_HIP_TRY(hipMemcpy(d_text.p, text.data(), (size_t)T, hipMemcpyHostToDevice));
+  }
   G2S_HIP_TRY(d_keys.alloc((size_t)T * sizeof(KT)));
   G2S_HIP_TRY(d_misc.alloc(16));
-  G2S_HIP_TRY(hipMemcpy(d_text.p, text.data(), (size_t)T, hipMemcpyHostToDevice));
   const dim3 blk(256), grdT((unsigned)((T + 255) / 256));
-  hipLaunchKernelGGL(k_extract<KT>, grdT, blk, 0, 0, (const uint8_t*)d_text.p, T, k, (KT*)d_keys.p);
+  hipLaunchKernelGGL(k_extract<KT>, grdT, blk, 0, 0, in.text ? (const uint8_t*)in.text->d_text : (const uint8_t*)d_text.p, T, k,
+                     (KT*)d_keys.p);
+  if (in.text) free_device_text(in.text);  // (as d_text.free(): the text is not needed beside the sort)
   d_text.free();
   KT* sorted = nullptr;
   if constexpr (sizeof(KT) == 8) {
@@ -1613,11 +1618,10 @@ bool graph_build_pool_gpu(Graph& g, const PoolSets& ps, int solid, int device,
 
 namespace g2s {
 
-bool count_solid_gpu(Graph& g, const std::vector<std::pair<const char*, uint64_t>>& seqs, int solid, int device,
-                     std::string* why, SolidCountInfo* info) {
-  if (g.kmer_bytes == 32) return count_solid_gpu_t<u256>(g, g.kmers256, seqs, solid, device, why, info);
-  return g.kmer_bytes == 16 ? count_solid_gpu_t<u128>(g, g.kmers128, seqs, solid, device, why, info)
-                            : count_solid_gpu_t<uint64_t>(g, g.kmers64, seqs, solid, device, why, info);
+bool count_solid_gpu(Graph& g, const BuildInput& in, int solid, int device, std::string* why, SolidCountInfo* info) {
+  if (g.kmer_bytes == 32) return count_solid_gpu_t<u256>(g, g.kmers256, in, solid, device, why, info);
+  return g.kmer_bytes == 16 ? count_solid_gpu_t<u128>(g, g.kmers128, in, solid, device, why, info)
+                            : count_solid_gpu_t<uint64_t>(g, g.kmers64, in, solid, device, why, info);
 }
 
 bool graph_finish_gpu(Graph& g, int device, const std::function<void(const std::vector<uint32_t>&, uint32_t)>& host_walk,

@@ -1,7 +1,10 @@
 // gap2seq_amd/csrc/fastx.cpp — see fastx.hpp.
 #include "fastx.hpp"
 
+#include <zlib.h>
+
 #include <cstdio>
+#include <cstring>
 
 namespace g2s {
 
@@ -14,6 +17,68 @@ bool read_text_file(const std::string& path, std::string* out) {
   while ((got = fread(buf, 1, sizeof buf, f)) > 0) out->append(buf, got);
   fclose(f);
   return true;
+}
+
+GzipReader::GzipReader(const uint8_t* bytes, size_t n) {
+  z_stream* zs = new z_stream;
+  memset(zs, 0, sizeof *zs);
+  zs->next_in = const_cast<Bytef*>(bytes);
+  zs->avail_in = 0;
+  zs_ = zs;
+  left_ = n;
+  if (inflateInit2(zs, 16 + 15) != Z_OK) { delete zs; zs_ = nullptr; }
+  done_ = n == 0;
+}
+GzipReader::~GzipReader() {
+  if (zs_) { inflateEnd((z_stream*)zs_); delete (z_stream*)zs_; }
+}
+bool GzipReader::read(uint8_t* dst, size_t cap, size_t* got, std::string* err) {
+  *got = 0;
+  z_stream* zs = (z_stream*)zs_;
+  if (!zs) { *err = "zlib could not be started"; return false; }
+  while (*got < cap && !done_) {
+    if (zs->avail_in == 0 && left_) {  // (avail_in is 32 bits wide: the input goes in by slices)
+      const size_t step = std::min<size_t>(left_, (size_t)1 << 30);
+      zs->avail_in = (uInt)step;
+      left_ -= step;
+    }
+    if (!in_member_) {
+      if (zs->avail_in == 0) { done_ = true; break; }
+      if (inflateReset(zs) != Z_OK) { *err = "zlib could not be started"; return false; }
+      in_member_ = true;
+    }
+    const size_t room = std::min<size_t>(cap - *got, (size_t)1 << 30);
+    zs->next_out = dst + *got;
+    zs->avail_out = (uInt)room;
+    const int rc = ::inflate(zs, Z_NO_FLUSH);
+    *got += room - zs->avail_out;
+    if (rc == Z_STREAM_END) { in_member_ = false; continue; }
+    if (rc == Z_BUF_ERROR && zs->avail_in == 0 && left_ == 0) { *err = "truncated gzip stream"; return false; }
+    if (rc != Z_OK && rc != Z_BUF_ERROR) { *err = std::string("corrupt gzip stream (") + (zs->msg ? zs->msg : "zlib") + ")"; return false; }
+    if (rc == Z_OK && zs->avail_in == 0 && left_ == 0 && zs->avail_out != 0) { *err = "truncated gzip stream"; return false; }
+  }
+  return true;
+}
+
+bool reads_text_of_bytes(const uint8_t* bytes, size_t n, const std::string& name, std::string* out, bool* gz, std::string* err) {
+  if (gz) *gz = is_gzip(bytes, n);
+  if (!is_gzip(bytes, n)) { out->assign((const char*)bytes, n); return true; }
+  out->clear();
+  GzipReader zr(bytes, n);
+  std::vector<uint8_t> buf((size_t)1 << 20);
+  while (!zr.at_end()) {
+    size_t got = 0;
+    std::string why;
+    if (!zr.read(buf.data(), buf.size(), &got, &why)) { *err = name + ": " + why; return false; }
+    out->append((const char*)buf.data(), got);
+  }
+  return true;
+}
+bool read_reads_file(const std::string& path, std::string* out, bool* gz, std::string* err) {
+  std::string raw;
+  if (!read_text_file(path, &raw)) { *err = "cannot read " + path; return false; }
+  if (!is_gzip((const uint8_t*)raw.data(), raw.size())) { if (gz) *gz = false; out->swap(raw); return true; }
+  return reads_text_of_bytes((const uint8_t*)raw.data(), raw.size(), path, out, gz, err);
 }
 
 namespace {

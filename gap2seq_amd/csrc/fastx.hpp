@@ -6,6 +6,8 @@
 // sequence.
 #pragma once
 #include <algorithm>
+#include <cstddef>
+#include <cstdint>
 #include <string>
 #include <vector>
 
@@ -18,6 +20,32 @@ struct FastxRecord {
 
 bool read_text_file(const std::string& path, std::string* out);
 void parse_fastx(const std::string& text, std::vector<FastxRecord>* out);
+
+// ---- gzip input (read files: GATB's bank reads .gz transparently).  Recognised by the magic bytes 1f 8b, never by name.
+inline bool is_gzip(const uint8_t* p, size_t n) { return n >= 2 && p[0] == 0x1f && p[1] == 0x8b; }
+// A gzip stream of any number of members inflated by zlib, a buffer at a time.  The compressed bytes stay where they
+// are (a mapped file, the caller's memory).  Strict: whatever follows a member must be another member, so trailing bytes
+// that are none — the zero padding some tape and block writers leave, which gzip(1) ignores — are a corrupt stream.
+class GzipReader {
+ public:
+  GzipReader(const uint8_t* bytes, size_t n);
+  ~GzipReader();
+  GzipReader(const GzipReader&) = delete;
+  GzipReader& operator=(const GzipReader&) = delete;
+  // up to cap inflated bytes into dst; fewer than cap only at the end of the stream.  false with *err set when the
+  // stream is truncated or corrupt (a member's CRC and size are checked at its end).
+  bool read(uint8_t* dst, size_t cap, size_t* got, std::string* err);
+  bool at_end() const { return done_; }
+
+ private:
+  void* zs_ = nullptr;  // z_stream
+  size_t left_ = 0;    // input bytes not yet handed to zlib
+  bool done_ = false, in_member_ = false;
+};
+// a whole read file as text: its bytes, inflated when they are gzip.  *gz (may be null): whether they were.  false with
+// *err naming the file when it cannot be read or its gzip stream is truncated or corrupt.
+bool read_reads_file(const std::string& path, std::string* out, bool* gz, std::string* err);
+bool reads_text_of_bytes(const uint8_t* bytes, size_t n, const std::string& name, std::string* out, bool* gz, std::string* err);
 inline void append_fasta(std::string* out, const std::string& comment, const std::string& seq) {
   out->push_back('>');
   out->append(comment);

@@ -39,6 +39,8 @@
 #include "glibc_rand.hpp"
 #include "pass_plan.hpp"
 #include "post.hpp"
+#include "reads_text.h"
+#include "readfilter_gaps.hpp"
 #include "seg_tables.h"
 
 using namespace g2s;
@@ -289,28 +291,164 @@ extern "C" uint32_t g2s_graph_set_node(const g2s_graph* g, uint32_t set, const c
   return g->g->node_of_in(set, kmer);
 }
 
-extern "C" int g2s_graph_build_files(const char* reads_csv, int k, int solid, int nthreads, g2s_graph** out) {
-  if (!reads_csv || !out) return fail(G2S_ERR_ARG, "g2s_graph_build_files: bad argument");
-  std::vector<FastxRecord> recs;
+// ---- graphs from read files.  The device loader (reads_text.h) makes the build's text on the device from the files' raw
+// bytes and hands it to the device count; the host loader (zlib, parse_fastx, graph_build) is the fallback for everything
+// but a file that cannot be read, and what G2S_HOST_BUILD=1, G2S_HOST_READS=1 or a machine without a device get.
+namespace {
+std::mutex g_reads_info_mu;
+ReadsLoadInfo g_reads_info;
+void set_reads_info(const ReadsLoadInfo& info) {
+  std::lock_guard<std::mutex> lk(g_reads_info_mu);
+  g_reads_info = info;
+}
+uint64_t env_bytes(const char* name) {
+  const char* s = getenv(name);
+  return s && *s ? strtoull(s, nullptr, 10) : 0;
+}
+bool env_on(const char* name) {
+  const char* s = getenv(name);
+  return s && *s && strcmp(s, "0") != 0;
+}
+std::vector<std::string> split_csv(const char* reads_csv) {  // comma separated list (Gap2Seq.cpp:199-210)
+  std::vector<std::string> files;
   std::string csv(reads_csv);
   size_t pos = 0;
-  while (pos <= csv.size()) {  // comma separated list (Gap2Seq.cpp:199-210)
+  while (pos <= csv.size()) {
     size_t e = csv.find(',', pos);
     if (e == std::string::npos) e = csv.size();
-    std::string file = csv.substr(pos, e - pos);
+    if (e > pos) files.push_back(csv.substr(pos, e - pos));
     pos = e + 1;
-    if (file.empty()) continue;
-    std::string text;
-    if (!read_text_file(file, &text)) return fail(G2S_ERR_IO, "cannot read " + file);
+  }
+  return files;
+}
+}  // namespace
+
+extern "C" int g2s_graph_build_files(const char* reads_csv, int k, int solid, int nthreads, g2s_graph** out) {
+  if (!reads_csv || !out) return fail(G2S_ERR_ARG, "g2s_graph_build_files: bad argument");
+  const std::vector<std::string> files = split_csv(reads_csv);
+  const bool debug = getenv("G2S_DEBUG") != nullptr;
+  // (G2S_HOST_BUILD: set to anything, as graph_build reads it)
+  if (!getenv("G2S_HOST_BUILD") && !env_on("G2S_HOST_READS")) {
+    const auto t0 = std::chrono::steady_clock::now();
+    std::vector<ReadsInput> inputs(files.size());
+    for (size_t i = 0; i < files.size(); i++) inputs[i].path = files[i];
+    const uint64_t piece = env_bytes("G2S_BUILD_PIECE_BYTES");
+    DeviceText text;
+    ReadsLoadInfo info;
+    std::string why;
+    const ReadsLoadResult r = load_reads_device(inputs, getenv("G2S_DEVICE") ? atoi(getenv("G2S_DEVICE")) : 0,
+                                                (size_t)piece, env_bytes("G2S_BUILD_TEXT_FIRST_BYTES"),
+                                                env_on("G2S_HOST_INFLATE"), &text, &info, &why);
+    if (r == kReadsIoError) return fail(G2S_ERR_IO, why);
+    if (r == kReadsOk && text.T == 0) {  // (no sequence at all: the empty graph, as the host loader builds it)
+      free_device_text(&text);
+      why = "no text";
+    } else if (r == kReadsOk) {
+      if (debug)
+        fprintf(stderr, "[g2s] reads: %llu files, %llu raw bytes, %llu text positions, %llu records in %llu pieces on the device, %.3f s\n",
+                (unsigned long long)info.files, (unsigned long long)info.raw_bytes, (unsigned long long)info.positions,
+                (unsigned long long)info.records, (unsigned long long)info.pieces, ms_since(t0) / 1e3);
+      bool gave_up = false;
+      std::string err;
+      Graph* g = graph_build_text(&text, k, solid, nthreads, &err, &gave_up);
+      free_device_text(&text);
+      if (g) {
+        set_reads_info(info);
+        *out = new g2s_graph();
+        (*out)->g = g;
+        return G2S_OK;
+      }
+      if (!gave_up) return fail(G2S_ERR_ARG, err);
+      why = "the device count gave up: " + err;
+    }
+    if (debug) fprintf(stderr, "[g2s] reads: the host loader takes over (%s)\n", why.c_str());
+  }
+  ReadsLoadInfo info;
+  std::vector<FastxRecord> recs;
+  for (const std::string& file : files) {
+    std::string text, err;
+    bool gz = false;
+    if (!read_reads_file(file, &text, &gz, &err)) return fail(G2S_ERR_IO, err);
+    info.files++;
+    info.raw_bytes += text.size();
+    info.inflate.push_back(gz ? kInflateZlib : kInflateNone);
     parse_fastx(text, &recs);
   }
   std::vector<std::pair<const char*, uint64_t>> v;
-  for (auto& r : recs) v.emplace_back(r.seq.data(), (uint64_t)r.seq.size());
+  for (auto& r : recs) {
+    v.emplace_back(r.seq.data(), (uint64_t)r.seq.size());
+    info.positions += r.seq.size() + 1;
+  }
+  info.records = recs.size();
   std::string err;
   Graph* g = graph_build(v, k, solid, nthreads, &err);
   if (!g) return fail(G2S_ERR_ARG, err);
+  set_reads_info(info);
   *out = new g2s_graph();
   (*out)->g = g;
+  return G2S_OK;
+}
+// TEST HOOK (include/g2s_test.h)
+extern "C" int g2s_test_last_reads_load(uint64_t* files, uint64_t* raw_bytes, uint64_t* positions, uint64_t* records,
+                                        uint64_t* pieces, int* on_device, int* inflate, uint64_t inflate_cap, uint64_t* grows) {
+  ReadsLoadInfo info;
+  {
+    std::lock_guard<std::mutex> lk(g_reads_info_mu);
+    info = g_reads_info;
+  }
+  if (files) *files = info.files;
+  if (raw_bytes) *raw_bytes = info.raw_bytes;
+  if (positions) *positions = info.positions;
+  if (records) *records = info.records;
+  if (pieces) *pieces = info.pieces;
+  if (on_device) *on_device = info.on_device;
+  if (grows) *grows = info.grows;
+  if (inflate)
+    for (uint64_t i = 0; i < std::min<uint64_t>(inflate_cap, info.inflate.size()); i++) inflate[i] = info.inflate[i];
+  return G2S_OK;
+}
+// TEST HOOK (include/g2s_test.h)
+extern "C" int g2s_test_reads_text(const void* bytes, size_t n, int device, size_t piece_bytes, uint8_t* out, size_t cap,
+                                   size_t* out_n) {
+  if ((!bytes && n) || (!out && cap) || !out_n || device < -2) return fail(G2S_ERR_ARG, "g2s_test_reads_text: bad argument");
+  const uint8_t* p = (const uint8_t*)bytes;
+  if (device < 0) {
+    std::string raw, err, text;
+    if (!reads_text_of_bytes(p, n, "(memory)", &raw, nullptr, &err)) return fail(G2S_ERR_IO, err);
+    ReadsLoadInfo info;
+    info.files = 1;
+    info.raw_bytes = raw.size();
+    if (device == -1) {
+      std::vector<FastxRecord> recs;
+      parse_fastx(raw, &recs);
+      for (auto& r : recs) { text += r.seq; text.push_back('N'); }
+      info.records = recs.size();
+    } else {
+      machine_text_host((const uint8_t*)raw.data(), raw.size(), &text, &info.records);
+    }
+    info.positions = text.size();
+    set_reads_info(info);
+    *out_n = text.size();
+    if (!text.empty()) memcpy(out, text.data(), std::min(cap, text.size()));
+    return G2S_OK;
+  }
+  if (!filter_device_usable(device)) return fail(G2S_ERR_NO_DEVICE, "g2s_test_reads_text: no usable gfx950 device " + std::to_string(device));
+  std::vector<ReadsInput> inputs(1);
+  inputs[0].mem = p;
+  inputs[0].mem_n = n;
+  DeviceText text;
+  ReadsLoadInfo info;
+  std::string why;
+  const ReadsLoadResult r = load_reads_device(inputs, device, piece_bytes,
+                                              env_bytes("G2S_BUILD_TEXT_FIRST_BYTES"), env_on("G2S_HOST_INFLATE"), &text, &info, &why);
+  if (r == kReadsIoError) return fail(G2S_ERR_IO, why);
+  if (r != kReadsOk) return fail(G2S_ERR_HIP, "g2s_test_reads_text: the device refused (" + why + ")");
+  set_reads_info(info);
+  *out_n = (size_t)text.T;
+  const size_t take = std::min<size_t>(cap, (size_t)text.T);
+  const hipError_t e = take ? hipMemcpy(out, text.d_text, take, hipMemcpyDeviceToHost) : hipSuccess;
+  free_device_text(&text);
+  if (e != hipSuccess) return fail(G2S_ERR_HIP, std::string("g2s_test_reads_text: ") + hipGetErrorString(e));
   return G2S_OK;
 }
 

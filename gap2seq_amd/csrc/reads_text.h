@@ -1,0 +1,62 @@
+// gap2seq_amd/csrc/reads_text.h — the graph build's text made from read files (reads_text.hip).
+//
+// For the sequences s0 ... s(n-1) of a list of FASTA/FASTQ files the build's text is s0 N s1 N ... s(n-1) N.  The device
+// loader makes it in device memory from the files' raw bytes, a piece at a time, with the kernels k_fastx_* (the state
+// machine of fastx_machine.h); gzip input is inflated on the way: BGZF members on the device (bgzf_inflate.h), any
+// other gzip stream by zlib into the staging buffers.  The host loader (fastx.hpp) is the fallback and the authority.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "fastx_machine.h"
+
+namespace g2s {
+
+// how a file's bytes were inflated
+enum ReadsInflate : int { kInflateNone = 0, kInflateZlib = 1, kInflateDevice = 2, kInflateMixed = 3 };
+
+// What the process's last g2s_graph_build_files did to load its reads (g2s_test_last_reads_load).
+struct ReadsLoadInfo {
+  uint64_t files = 0, raw_bytes = 0, positions = 0, records = 0, pieces = 0, grows = 0;
+  int on_device = 0;
+  std::vector<int> inflate;  // per file: ReadsInflate
+};
+
+// one input of the loader: a file by name, or bytes in memory (the test hook)
+struct ReadsInput {
+  std::string path;
+  const uint8_t* mem = nullptr;
+  size_t mem_n = 0;
+};
+
+// A text resident on a device.  d_text has `capacity` bytes, at least device_text_bytes(T): what the key-range passes
+// read, T rounded up to their tile plus their halo (solid_passes.h); the bytes from T to there are 'N'.  The owner frees
+// d_text (free_device_text).
+struct DeviceText {
+  uint8_t* d_text = nullptr;
+  uint64_t T = 0, capacity = 0;
+  int device = -1;
+};
+// the bytes a text of T positions needs (solid_passes.h: tile padding and halo)
+uint64_t device_text_bytes(uint64_t T);
+
+enum ReadsLoadResult : int {
+  kReadsOk = 0,
+  kReadsGaveUp = 1,   // the device cannot be used or refused: *err says why; the host loader takes over
+  kReadsIoError = 2,  // a file cannot be read, or is truncated or corrupt: *err names it
+};
+
+// The text of `inputs` (in order, the parser's state fresh for each) made on `device` in pieces of `piece` raw bytes
+// (0: chosen by the files' sizes, 32 MiB at most);
+// first_cap: the text buffer's first capacity in bytes when no bound is known (compressed input), 0 = the default.
+// host_inflate: BGZF members go to zlib too.  On kReadsOk *out owns the text (also when T == 0).
+ReadsLoadResult load_reads_device(const std::vector<ReadsInput>& inputs, int device, size_t piece, uint64_t first_cap,
+                                  bool host_inflate, DeviceText* out, ReadsLoadInfo* info, std::string* err);
+void free_device_text(DeviceText* t);
+
+// the machine of fastx_machine.h walked line by line on the host over one file's bytes: the text is appended to *out
+void machine_text_host(const uint8_t* bytes, size_t n, std::string* out, uint64_t* records);
+
+}  // namespace g2s

@@ -341,10 +341,15 @@ static bool solid_passes_forced() { return env_u64("G2S_BUILD_PASS_KEYS") != 0; 
 // reason (g untouched) when the text does not fit beside a pass or one k-mer alone is more than a pass.  g.bucket stays
 // empty: finish_graph builds the prefix index as for a host-made set.
 template <class KT>
-static bool count_solid_passes_gpu_t(Graph& g, std::vector<KT>& out, const std::vector<std::pair<const char*, uint64_t>>& seqs,
-                                     int solid, uint64_t T, double per_key, std::string* why, SolidCountInfo* info) {
+static bool count_solid_passes_gpu_t(Graph& g, std::vector<KT>& out, const BuildInput& in, int solid, uint64_t T, double per_key,
+                                     std::string* why, SolidCountInfo* info) {
   const uint64_t ntiles = (T + PB_TILE - 1) / PB_TILE;
-  const uint64_t text_bytes = ntiles * (uint64_t)PB_TILE + PB_HALO;
+  // (a text that is on the device already has this padding and takes no further room: reads_text.h)
+  const uint64_t text_bytes = in.text ? 0 : ntiles * (uint64_t)PB_TILE + PB_HALO;
+  if (in.text && (device_text_bytes(T) != ntiles * (uint64_t)PB_TILE + PB_HALO || in.text->capacity < device_text_bytes(T))) {
+    if (why) *why = "the resident text lacks the passes' padding";
+    return false;
+  }
   size_t free_b = 0, total_b = 0;
   G2S_HIP_TRY(hipMemGetInfo(&free_b, &total_b));
   const uint64_t cap_max = 1ull << 31;  // (a pass's keys are indexed in 32 bits)
@@ -354,10 +359,12 @@ static bool count_solid_passes_gpu_t(Graph& g, std::vector<KT>& out, const std::
   const double need = (double)text_bytes + (forced ? (double)cap : (double)(1u << 24)) * per_key;
   if (need > 0.5 * (double)free_b) { if (why) *why = "text does not fit on the device beside a pass"; return false; }
   DevMem d_text;
-  G2S_HIP_TRY(d_text.alloc((size_t)text_bytes));
-  G2S_HIP_TRY(hipMemset(d_text.as<uint8_t>() + T, 'N', (size_t)(text_bytes - T)));
-  const uint64_t piece = env_u64("G2S_BUILD_PIECE_BYTES");
-  if (!upload_text_staged(d_text.as<uint8_t>(), seqs, T, (size_t)(piece ? std::max<uint64_t>(piece, 16) : std::min<uint64_t>(32u << 20, T)), why)) return false;
+  if (!in.text) {
+    G2S_HIP_TRY(d_text.alloc((size_t)text_bytes));
+    G2S_HIP_TRY(hipMemset(d_text.as<uint8_t>() + T, 'N', (size_t)(text_bytes - T)));
+    const uint64_t piece = env_u64("G2S_BUILD_PIECE_BYTES");
+    if (!upload_text_staged(d_text.as<uint8_t>(), *in.seqs, T, (size_t)(piece ? std::max<uint64_t>(piece, 16) : std::min<uint64_t>(32u << 20, T)), why)) return false;
+  }
   if (!forced) {
     G2S_HIP_TRY(hipMemGetInfo(&free_b, &total_b));
     cap = (uint64_t)(0.5 * (double)free_b / per_key);
@@ -365,7 +372,7 @@ static bool count_solid_passes_gpu_t(Graph& g, std::vector<KT>& out, const std::
   cap = std::min(cap, cap_max);
   std::vector<KT> kept;
   SolidPasses<KT> sp;
-  sp.d_text = d_text.as<uint8_t>();
+  sp.d_text = in.text ? in.text->d_text : d_text.as<uint8_t>();
   sp.ntiles = ntiles;
   sp.cap = cap;
   sp.k = g.k;
@@ -375,6 +382,7 @@ static bool count_solid_passes_gpu_t(Graph& g, std::vector<KT>& out, const std::
   G2S_HIP_TRY(sp.d_hist.alloc((size_t)PB_MAX_BINS * 8));
   G2S_HIP_TRY(sp.d_cursor.alloc(8));
   if (!sp.run_level(0, KT((uint64_t)0))) return false;
+  if (in.text) free_device_text(in.text);  // (the passes were its last readers; d_text goes at the function's end)
   if (getenv("G2S_DEBUG"))
     fprintf(stderr, "[g2s]   k-mer set in %u key-range passes of at most %llu keys (largest %llu, %u bins refined, %llu of %llu positions valid)\n",
             sp.passes, (unsigned long long)cap, (unsigned long long)sp.max_pass_keys, sp.refined,

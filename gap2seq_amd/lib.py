@@ -234,6 +234,11 @@ _SIGS = {
                                        C.POINTER(C.c_uint64), C.c_int64, C.c_uint64, C.c_uint64, C.POINTER(C.c_int64),
                                        C.c_uint64, C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(C.c_uint64),
                                        C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(C.c_uint64)]),
+    "g2s_test_reads_text": (C.c_int, [C.c_char_p, C.c_size_t, C.c_int, C.c_size_t, C.POINTER(C.c_uint8), C.c_size_t,
+                                      C.POINTER(C.c_size_t)]),
+    "g2s_test_last_reads_load": (C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                           C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int),
+                                           C.POINTER(C.c_int), C.c_uint64, C.POINTER(C.c_uint64)]),
     "g2s_test_bgzf_inflate": (C.c_int, [C.c_char_p, C.c_size_t, C.c_int, C.POINTER(C.c_uint8), C.c_size_t,
                                         C.POINTER(C.c_size_t), C.POINTER(C.c_int64)]),
     "g2s_test_last_filter_inflate": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
@@ -1165,6 +1170,36 @@ def test_filter_join(ref_id, pos, end, flag, h_own, h_mate, max_span, bits, wind
         cap1, cap2 = max(cap1, n1.value), max(cap2, n2.value)
     msg = (lib.g2s_filter_last_error() or b"").decode("utf-8", "replace")
     return rc, [(x >> 32, x & 0xFFFFFFFF) for x in l1[:n1.value]], [(x >> 32, x & 0xFFFFFFFF) for x in l2[:n2.value]], msg
+
+
+def reads_text(data, device=-1, piece_bytes=0):
+    """TEST HOOK binding (g2s_test_reads_text): the build's text (every sequence followed by N) of one read file in
+    memory, plain, gzip or BGZF.  device -1: the host loader (zlib, parse_fastx); -2: the kernels' state machine walked
+    on the host; >= 0: the kernels on that device in pieces of `piece_bytes` raw bytes.  Raises G2SError."""
+    lib = load_library()
+    data = bytes(data)
+    cap = max(1 << 12, 2 * len(data))
+    while True:
+        out = (C.c_uint8 * cap)()
+        n = C.c_size_t(0)
+        _check(lib.g2s_test_reads_text(data, len(data), device, piece_bytes, out, cap, C.byref(n)))
+        if n.value <= cap:
+            return bytes(out[:n.value])
+        cap = n.value
+
+
+def last_reads_load():
+    """TEST HOOK binding (g2s_test_last_reads_load): dict(files, raw_bytes, positions, records, pieces, on_device,
+    inflate, grows) of the process's last Graph.from_files or reads_text; inflate is a list with one of "none", "zlib",
+    "device", "mixed" a file"""
+    f, rb, ps, rc, pc, gr = (C.c_uint64() for _ in range(6))
+    on = C.c_int()
+    _check(load_library().g2s_test_last_reads_load(C.byref(f), None, None, None, None, None, None, 0, None))
+    how = (C.c_int * max(1, f.value))()
+    _check(load_library().g2s_test_last_reads_load(C.byref(f), C.byref(rb), C.byref(ps), C.byref(rc), C.byref(pc), C.byref(on),
+                                                   how, f.value, C.byref(gr)))
+    return dict(files=f.value, raw_bytes=rb.value, positions=ps.value, records=rc.value, pieces=pc.value,
+                on_device=on.value, inflate=[("none", "zlib", "device", "mixed")[x] for x in how[:f.value]], grows=gr.value)
 
 
 def bgzf_inflate(data, device=-1):

@@ -77,6 +77,13 @@ const char* g2s_last_error(void);
  *  passes.  The host counts them only when the text does not fit beside one
  *  pass or one k-mer alone occurs more often than a pass holds keys
  *  (G2S_DEBUG=1 says which).  The graph itself holds fewer than 2^30 k-mers.
+ *  g2s_graph_build_files: reads_csv is a comma-separated list of FASTA/FASTQ
+ *  files; gzip-compressed ones (plain gzip or BGZF, recognised by their magic
+ *  bytes, not their names) are read transparently.  With a usable device the
+ *  files' bytes are parsed there and never form sequences on the host
+ *  (G2S_HOST_READS=1: the host loader).  G2S_ERR_IO with the file's name in
+ *  g2s_last_error() for a file that cannot be read or whose gzip stream is
+ *  truncated or corrupt.
  * ------------------------------------------------------------------------ */
 int g2s_graph_build_files(const char* reads_csv, int k, int solid, int nthreads, g2s_graph** out);
 int g2s_graph_build_seqs(const char* const* seqs, const uint64_t* lens, int nseqs, int k, int solid,

@@ -112,6 +112,26 @@ int g2s_test_last_pool_build(uint64_t* own_positions, uint64_t* shared_positions
 int g2s_test_last_solid_count(uint64_t* positions, uint32_t* passes, uint32_t* refined_bins, uint64_t* max_pass_keys,
                               uint64_t* solid, int* on_device);
 
+/* TEST HOOK: the graph build's text of ONE read file in memory (FASTA or FASTQ, plain, gzip or BGZF, recognised by its
+ * magic bytes): every sequence followed by one 'N'.  device == -1: the host loader — zlib when the bytes are gzip, then
+ * parse_fastx.  device == -2: the line state machine of csrc/fastx_machine.h, the one the kernels run, walked line by line
+ * on the host.  device >= 0: the kernels k_fastx_* of csrc/reads_text.hip on that device, in pieces of piece_bytes raw
+ * bytes (0: the product's choice, 32 MiB at most), BGZF members inflated on the device unless G2S_HOST_INFLATE=1 —
+ * G2S_ERR_NO_DEVICE when it is no usable gfx950, G2S_ERR_HIP when anything on the device refuses; never the host in
+ * their place.  G2S_ERR_IO with g2s_last_error()'s text for a truncated or corrupt gzip stream.  *out_n receives the
+ * text's size; the first min(cap, size) bytes are written, so a caller whose capacity was too small calls again.
+ * g2s_test_last_reads_load then speaks of this call. */
+int g2s_test_reads_text(const void* bytes, size_t n, int device, size_t piece_bytes, uint8_t* out, size_t cap, size_t* out_n);
+
+/* TEST HOOK: how the process's last g2s_graph_build_files (or g2s_test_reads_text) loaded its reads.  files; raw_bytes:
+ * the files' bytes after inflation; positions: the text's (bases + 1 a record); records; pieces: the pieces the kernels
+ * walked (0 on the host); on_device: the text was made by the kernels (0 also when the device loader or the device
+ * count gave up and the host loader took over); inflate[i] for the first min(inflate_cap, files) files: 0 not compressed,
+ * 1 zlib on the host, 2 BGZF members inflated on the device, 3 both (BGZF members first, then another gzip stream);
+ * grows: how often the text buffer was enlarged.  Any pointer may be NULL. */
+int g2s_test_last_reads_load(uint64_t* files, uint64_t* raw_bytes, uint64_t* positions, uint64_t* records, uint64_t* pieces,
+                             int* on_device, int* inflate, uint64_t inflate_cap, uint64_t* grows);
+
 /* TEST HOOK: the planner of the key-range passes (pass_plan.hpp) on a histogram of the caller's: nbins consecutive bins
  * of the key space, cut greedily and in order into passes of at most cap keys — a pass is closed in front of the first
  * bin that would take it beyond cap, empty bins join the open pass.  *npasses receives the number of passes and

@@ -1,0 +1,149 @@
+#!/usr/bin/env python3
+"""Time g2s_graph_build_files (Graph.from_files, Gap2Seq-core -reads) on bench.py's read sets written as FASTA, FASTQ,
+gzip FASTQ and BGZF FASTQ: the device loader (gap2seq_amd/csrc/reads_text.hip, the default), the host loader
+(G2S_HOST_READS=1), BGZF through zlib (G2S_HOST_INFLATE=1), and — on the two uncompressed files, all it can read —
+another build of the library (--parent path/to/libg2s_hip.so, the commit before).  Every build runs in a process of its
+own, so that its peak resident set is its own: the wall time is that of the one call, up to its return, behind a small
+warm-up build that loads the runtime and the kernels; the resident set is the peak over the process less what the warm-up
+left.  The ways alternate, --reps builds each; the median and the spread of each are printed as one JSON line.
+
+  python tools/build_files_bench.py --config C4 --reps 5 --threads 16 [--parent PATH/TO/libg2s_hip.so]
+  python tools/build_files_bench.py --config C4 --once fastq     # one device-loader build in this process (kernel trace)
+
+Needs a GPU."""
+import argparse
+import ctypes as C
+import gzip
+import json
+import os
+import resource
+import statistics
+import subprocess
+import sys
+import tempfile
+import time
+import zlib
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+SWITCHES = ("G2S_HOST_BUILD", "G2S_HOST_READS", "G2S_HOST_INFLATE", "G2S_BUILD_PASS_KEYS", "G2S_BUILD_PIECE_BYTES",
+            "G2S_BUILD_TEXT_FIRST_BYTES")
+
+
+def bgzf(raw, out):
+    for o in range(0, len(raw), 65280):
+        payload = raw[o:o + 65280]
+        c = zlib.compressobj(6, zlib.DEFLATED, -15)
+        cdata = c.compress(payload) + c.flush()
+        out.write(b"\x1f\x8b\x08\x04\x00\x00\x00\x00\x00\xff\x06\x00BC\x02\x00" + (len(cdata) + 25).to_bytes(2, "little") + cdata +
+                  (zlib.crc32(payload) & 0xFFFFFFFF).to_bytes(4, "little") + len(payload).to_bytes(4, "little"))
+    out.write(bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000"))
+
+
+def write_files(config, d):
+    import bench
+    from gap2seq_amd import lib as P
+    genome_bp, k = bench.CONFIGS[config][:2]
+    fa = P.G2S.synth_genome(genome_bp, 3, bench.GENOME_SEED).encode("ascii")
+    lines = fa.split(b"\n")
+    fq = b"".join(b"@" + lines[i][1:] + b"\n" + lines[i + 1] + b"\n+\n" + b"I" * len(lines[i + 1]) + b"\n"
+                  for i in range(0, len(lines) - 1, 2))
+    paths = {f: os.path.join(d, "reads." + f) for f in ("fasta", "fastq", "fastq.gz", "bgzf.fastq.gz")}
+    open(paths["fasta"], "wb").write(fa)
+    open(paths["fastq"], "wb").write(fq)
+    with gzip.GzipFile(paths["fastq.gz"], "wb", compresslevel=6, mtime=0) as f:
+        f.write(fq)
+    with open(paths["bgzf.fastq.gz"], "wb") as f:
+        bgzf(fq, f)
+    return k, paths
+
+
+def child(library, path, k, threads):
+    """one build in this process: a JSON line with its wall time, k-mers and resident set"""
+    lib = C.CDLL(library)
+    lib.g2s_graph_build_files.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+    lib.g2s_graph_num_kmers.restype = C.c_uint64
+    lib.g2s_graph_num_kmers.argtypes = [C.c_void_p]
+    lib.g2s_graph_free.argtypes = [C.c_void_p]
+    lib.g2s_last_error.restype = C.c_char_p
+    with tempfile.NamedTemporaryFile(suffix=".fa") as warm:
+        warm.write(b">w\n" + b"ACGTTGCAAGGCTTAACCGGTATCGATCGGATTACAGGCATT" * 50 + b"\n")
+        warm.flush()
+        h = C.c_void_p()
+        if lib.g2s_graph_build_files(warm.name.encode(), k, 1, threads, C.byref(h)) != 0:
+            raise SystemExit("warm-up: " + (lib.g2s_last_error() or b"").decode())
+        lib.g2s_graph_free(h)
+    rss0 = resource.getrusage(resource.RUSAGE_SELF).ru_maxrss
+    h = C.c_void_p()
+    t0 = time.perf_counter()
+    rc = lib.g2s_graph_build_files(path.encode(), k, 1, threads, C.byref(h))
+    wall = time.perf_counter() - t0
+    if rc != 0:
+        raise SystemExit("build: " + (lib.g2s_last_error() or b"").decode())
+    out = dict(wall_s=wall, kmers=lib.g2s_graph_num_kmers(h), rss_mb=(resource.getrusage(resource.RUSAGE_SELF).ru_maxrss - rss0) / 1024.0)
+    try:
+        lib.g2s_test_last_reads_load.argtypes = [C.POINTER(C.c_uint64)] * 5 + [C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_uint64,
+                                                                               C.POINTER(C.c_uint64)]
+        raw, pos, on = C.c_uint64(), C.c_uint64(), C.c_int()
+        lib.g2s_test_last_reads_load(None, C.byref(raw), C.byref(pos), None, None, C.byref(on), None, 0, None)
+        out.update(raw_bytes=raw.value, positions=pos.value, text_on_device=on.value)
+    except AttributeError:  # (the parent's library)
+        pass
+    lib.g2s_graph_free(h)
+    print(json.dumps(out), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--config", default="C4")
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--threads", type=int, default=16)
+    ap.add_argument("--parent", default="", help="the library of the commit before, for the uncompressed files")
+    ap.add_argument("--once", default="", help="one device-loader build of this form in this process, nothing else")
+    ap.add_argument("--child", nargs=4, metavar=("LIBRARY", "PATH", "K", "THREADS"), help=argparse.SUPPRESS)
+    args = ap.parse_args()
+    if args.child:
+        child(args.child[0], args.child[1], int(args.child[2]), int(args.child[3]))
+        return 0
+    here = os.path.join(ROOT, "gap2seq_amd", "libg2s_hip.so")
+    with tempfile.TemporaryDirectory() as d:
+        k, paths = write_files(args.config, d)
+        sizes = {f: os.path.getsize(p) for f, p in paths.items()}
+        if args.once:
+            for name in SWITCHES:
+                os.environ.pop(name, None)
+            child(here, paths[args.once], k, args.threads)
+            return 0
+        ways = []  # (name, form, library, switches)
+        for f in paths:
+            ways.append(("device " + f, f, here, {}))
+            ways.append(("host-reads " + f, f, here, {"G2S_HOST_READS": "1"}))
+            if args.parent and not f.endswith(".gz"):
+                ways.append(("parent " + f, f, args.parent, {}))
+        ways.append(("device+zlib bgzf.fastq.gz", "bgzf.fastq.gz", here, {"G2S_HOST_INFLATE": "1"}))
+        runs = {w[0]: [] for w in ways}
+        for rep in range(args.reps):
+            for name, form, library, switches in ways:
+                env = {key: v for key, v in os.environ.items() if key not in SWITCHES}
+                env.update(switches)
+                res = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", library, paths[form], str(k), str(args.threads)],
+                                     env=env, capture_output=True, text=True, timeout=900)
+                if res.returncode != 0:
+                    raise SystemExit("%s failed:\n%s%s" % (name, res.stdout, res.stderr))
+                r = json.loads(res.stdout.strip().splitlines()[-1])
+                runs[name].append(r)
+                print("rep %d %-28s %.3f s, %7.0f MiB resident, %d k-mers %s" % (
+                    rep, name, r["wall_s"], r["rss_mb"], r["kmers"], "(text on the device)" if r.get("text_on_device") else ""), flush=True)
+    out = {"config": args.config, "k": k, "file_bytes": sizes, "ways": {}}
+    for name, rs in runs.items():
+        ts = sorted(r["wall_s"] for r in rs)
+        out["ways"][name] = dict(median_s=statistics.median(ts), min_s=ts[0], max_s=ts[-1], reps=len(ts), kmers=rs[0]["kmers"],
+                                 rss_mb=statistics.median(r["rss_mb"] for r in rs), text_on_device=rs[0].get("text_on_device"),
+                                 raw_bytes=rs[0].get("raw_bytes"), positions=rs[0].get("positions"))
+    out["same_kmers"] = len({v["kmers"] for v in out["ways"].values()}) == 1
+    print(json.dumps(out))
+    return 0 if out["same_kmers"] else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())
