@@ -135,6 +135,9 @@ struct D3Work {
   // link what differs.  Null: every traced gap is written in full.
   const char* spec_text = nullptr;
   const uint32_t* spec_res = nullptr;
+  // (not carved: the test hook's) beside every entry of tab that g2s_d3_tables writes, whether its walk was bad — an
+  // entry of 0 does not say.  Null in the product.
+  uint8_t* tab_bad = nullptr;
 };
 size_t d3_work_bytes(uint32_t n);
 void d3_work_carve(void* p, uint32_t n, D3Work* w);
@@ -216,5 +219,14 @@ hipError_t launch_d3(hipStream_t st, const D3Params& P, const D3Work& W, const G
                      hipEvent_t ev_chain = nullptr /* recorded behind the kernel that knows the list's draws (W.link is written) */,
                      hipEvent_t ev_d2 = nullptr /* behind g2s_d2_* on its own stream: the hand-off waits for it (null: nothing to wait for) */,
                      hipEvent_t ev_stop = nullptr /* the trace kernel's own stop time (hipExtLaunchKernelGGL): a timed list's last kernel */);
+
+// TEST HOOK (g2s_test_d3_tables): a short list's tables kernel, g2s_d3_tables_waves, through the product's launch, for ONE draw-dependent gap whose closure,
+// stream and place in it the caller designs: nsegs segments of four words (depth | length << 16, parents 0-1, parents
+// 2-3, flags), the start segments of both path lengths (as GapOut.start_seg), rnd_cap raw words of the stream from its
+// first value, the gap's first draw at deviation 0 (base), its deviations 0 .. R, dmin and dspread.  entries / bad:
+// R + 1 each, what the kernel wrote to the table and whether that walk was bad; *anomalies: the summary's counter.
+hipError_t test_d3_tables(const uint32_t* segs, uint32_t nsegs, int32_t n_len, int32_t len0, int32_t len1, uint32_t start_seg,
+                          const uint32_t* rnd, uint64_t rnd_cap, uint32_t base, uint32_t R, uint32_t dmin, uint32_t dspread,
+                          uint16_t* entries, uint8_t* bad, uint32_t* anomalies);
 
 }  // namespace g2s

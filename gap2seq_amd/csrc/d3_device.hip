@@ -18,8 +18,9 @@
 //                  (x^(2^20 a) x^(4096 b) x^(64 l) modulo x^31 - x^28 - 1 over Z/2^32, seed independent
 //                  tables), then every lane runs the recurrence for its 64 values.  On a stream of its own.
 //   g2s_d3_tables  A draw-dependent gap v can only start at base_v + d, d in [0, R_v], R_v = the summed spreads of
-//                  the draw-dependent gaps before it: its draw count for EVERY such start, one lane per (v, d), the
-//                  closure's links and the tile's window of the stream in LDS — the serial chain "offset of v+1 =
+//                  the draw-dependent gaps before it: its draw count for EVERY such start — a wave per (v, d), the walk
+//                  by pointer jumping over the closure's segments, where the tables are small; else a lane per (v, d),
+//                  the closure's links and the tile's window of the stream in LDS — the serial chain "offset of v+1 =
 //                  offset of v + draws of v" becomes table look-ups.
 //   g2s_d3_blocks  the chain through 16 consecutive tables for every deviation a block can start with;
 //   g2s_d3_chain   the chain over blocks (one lane), then back into the blocks: the deviation in front of
@@ -29,7 +30,7 @@
 //                  tables and the chain in LDS.)
 //   g2s_d3_trace   one wave per gap: the traceback over the closure segments (post.cpp: seg_traceback is
 //                  the host version and the reference for every branch here) as a per-segment choice of parent
-//                  (all lanes: the draw made at a depth does not depend on the path), a chase through those, and a
+//                  (all lanes: the draw made at a depth does not depend on the path), the chain through those by jump tables, and a
 //                  lane-parallel pass for base sources, safe bits and case; fill text and result record
 //                  written where the caller wants them (pinned host memory, or a staging buffer); host-finished
 //                  gaps handed over by their own waves; the last wave copies the summary to the host and, for a
@@ -43,9 +44,12 @@
 #include <hip/hip_ext.h>
 
 #include <algorithm>
+#include <cstddef>
 #include <cstdlib>
+#include <cstring>
 #include <mutex>
 #include <set>
+#include <vector>
 
 #include "../../include/g2s.h"
 #include "d3_device.h"
@@ -670,13 +674,146 @@ __device__ int d3_walk_count_lite(int n_len, int len0, int len1, uint32_t start_
   return 1;
 }
 
-// draws of draw-dependent gap v when its draws start at base + d, for every d it can meet: a workgroup takes 256
-// consecutive deviations of one gap: the closure's links in LDS, one walk per thread.  What it needs to know comes
-// in three round trips: the tile's gap (tile_var), that gap's record (D3Var), then the closure's links and the
-// rand() values the tile's walks can read — both into LDS: a walk asks for a value at every choice between
-// parents, and a round trip to memory per choice was the kernel's time (20 us for a 30-segment path).
-// (the window: map_cap + 256 words of dynamic LDS — the longest path of the list, 256 starts)
+// Wave-local order in LDS: what this wave wrote is there for every lane of it to read.
+__device__ __forceinline__ void wave_lds_sync() {
+#ifdef G2S_SYNC_DEBUG
+  g2s_sync_jitter(0xD37u);
+  g2s_wait_all();
+#endif
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_wave_barrier();
+}
+
+// The count of d3_walk_count_lite by pointer jumping, one WAVE per walk.  The parent a walk takes from a segment does
+// not depend on how it got there (see above), so the walk is a functional graph over the closure's segments: lane s
+// works out next[s] — or that s ends the walk, at a source (with 1 + len - d0 draws) or badly — with one gathered rand()
+// value, next is squared ceil(log2 ns) times, and the start's pointer then stands at the segment that ends its walk.  A
+// start whose pointer does not stand at a source by then has a walk that ends badly, or none that ends: depths that lie,
+// or a cycle — the serial walk gives those up at its hop cap.
+// Up to 64 segments the pointers stay in registers and a squaring is one ds_bpermute.  Up to D3_TAB_SEGS a lane owns
+// segments lane, lane + 64, ...: the pointers in jmp[D3_TAB_SEGS] (bit 15: the segment is a source, where a walk
+// ends well) and the depths in dep[D3_TAB_SEGS], this wave's own; the links come four segments a lane at a time — all
+// eight in flight cost the kernel waves the tiles' pass can have on a compute unit.
+// Every argument is wave-uniform.  Returns the draws; *bad as the serial walk sets it.
 #define D3_TAB_SEGS 512u
+#define D3_JMP_SOURCE 0x8000u
+#define D3_JMP_SEG (D3_TAB_SEGS - 1u)
+// NQ segments of this lane, s0, s0 + 64, ...: nx[] = next (a segment that ends the walk: itself), val[] = the draws of a
+// walk that ends there, 0 when that is no source.  rnd: the gap's first draw; lim: the values a walk may read;
+// first_word: the first of them, which picks the path length.
+template <int NQ>
+__device__ __forceinline__ void d3_wave_links(const SegW* __restrict__ gs, uint32_t ns /* >= 1 */, uint32_t s0, bool two, int len0, int len1,
+                                              const uint32_t* __restrict__ rnd, uint32_t lim /* >= 1 */, uint32_t first_word, uint32_t* nx, uint32_t* val) {
+  // (written without branches — a lane beyond the closure reads its last segment, a segment without a choice the first
+  // value: every nested condition would park a copy of the execution mask in scalar registers, which this kernel is short of)
+  uint32_t dl[NQ], p01[NQ], p23[NQ], fl[NQ], rv0[NQ], rv1[NQ];
+  // (the links, and the value each segment would draw for either path length: all loads asked for before the first is used)
+#pragma unroll
+  for (int q = 0; q < NQ; q++) {
+    const uint32_t s = min(s0 + 64u * (uint32_t)q, ns - 1u);
+    dl[q] = gs[s].depth_len; p01[q] = gs[s].par01; p23[q] = gs[s].par23; fl[q] = gs[s].flags;
+  }
+  // (the draw made at a segment's first state, at depth d0, is value at = 1 + len - d0 of the gap's; one that does not
+  // exist, or lies outside [1, lim), is not one a walk can ask for: that segment ends it)
+  auto value_at = [&](int q, int len) -> uint32_t {
+    const uint32_t at = (uint32_t)(1 + len - (int)(dl[q] & 0xFFFFu));
+    return rnd[at < lim ? at : 0u] >> 1;
+  };
+#pragma unroll
+  for (int q = 0; q < NQ; q++) {
+    rv0[q] = value_at(q, len0);
+    rv1[q] = two ? value_at(q, len1) : 0u;
+  }
+  const int pick = two ? (int)((first_word >> 1) & 1u) : 0;  // :1440 (n_len <= 2)
+  const int len = pick ? len1 : len0;
+#pragma unroll
+  for (int q = 0; q < NQ; q++) {
+    const uint32_t s = s0 + 64u * (uint32_t)q;
+    const int d0 = (int)(dl[q] & 0xFFFFu);
+    const bool live = s < ns && d0 <= len, source = (fl[q] & G2S_SUB_SOURCE) != 0u;  // :1455-1462
+    const int nb = seg_nparents(p01[q], p23[q]);
+    const uint32_t at = (uint32_t)(1 + len - d0);
+    const uint32_t to = seg_parent(p01[q], p23[q], nb > 1 ? pick_parent(pick ? rv1[q] : rv0[q], nb) : 0);  // :1513, GATB predecessor order
+    // (on to a parent: not from depth 0 — no depth below, :1493-1510 —, not without a parent, not where their order is
+    // the host's to find, not beyond the stream, not to a segment that is none)
+    const bool on = live && !source && d0 != 0 && nb != 0 && (nb == 1 || (fl[q] & G2S_SEG_ORDERED)) && at < lim && to < ns;
+    nx[q] = on ? to : s;
+    val[q] = live && source ? (uint32_t)(1 + len - d0) : 0u;
+  }
+}
+__device__ __forceinline__ int d3_count_wave(int n_len, int len0, int len1, uint32_t start_seg, uint32_t ns, const SegW* __restrict__ gs,
+                                             const uint32_t* __restrict__ rnd /* the first draw */, uint32_t nwin, uint64_t avail,
+                                             uint16_t* jmp, uint16_t* dep, bool* bad) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t lim = (uint32_t)min((uint64_t)nwin, avail);  // values of the stream a walk may read
+  if (lim < 1u || ns < 1u) { *bad = true; return 1; }
+  const bool two = n_len > 1;
+  const uint32_t first = rnd[0];  // (used behind the links' loads)
+  const int pick = two ? (int)((uni(first) >> 1) & 1u) : 0;
+  const int len = pick ? len1 : len0;
+  const uint32_t sg = (start_seg >> (16 * pick)) & 0xFFFFu;
+  uint32_t draws = 0u;  // of the start's walk, if it ends at a source
+  if (ns <= 64u) {
+    uint32_t p, val;
+    d3_wave_links<1>(gs, ns, lane, two, len0, len1, rnd, lim, first, &p, &val);
+    if (sg == 0xFFFFu || sg >= ns || len < 0) { *bad = true; return 1; }
+    for (uint32_t span = 1u; span < ns; span <<= 1) p = (uint32_t)__shfl((int)p, (int)p);
+    const uint32_t end = uni((uint32_t)__shfl((int)p, (int)sg));
+    draws = uni((uint32_t)__shfl((int)val, (int)end));
+  } else {
+    uint16_t* a = jmp;
+#pragma unroll 1
+    for (uint32_t s0 = lane; s0 < ns; s0 += 256u) {  // (lanes beyond ns write nothing)
+      uint32_t nx[4], val[4];
+      d3_wave_links<4>(gs, ns, s0, two, len0, len1, rnd, lim, first, nx, val);
+#pragma unroll
+      for (int q = 0; q < 4; q++) {
+        const uint32_t s = s0 + 64u * (uint32_t)q;
+        if (s >= ns) continue;
+        a[s] = (uint16_t)(nx[q] | (val[q] ? D3_JMP_SOURCE : 0u));
+        dep[s] = (uint16_t)(1 + len - (int)val[q]);  // (a source's depth)
+      }
+    }
+    if (sg == 0xFFFFu || sg >= ns || len < 0) { *bad = true; return 1; }
+    wave_lds_sync();
+    for (uint32_t span = 1u; span < ns; span <<= 1) {  // (a squaring: every lane reads its segments' new pointers, then writes them)
+      uint32_t t[D3_TAB_SEGS / 64u];
+#pragma unroll
+      for (uint32_t q = 0; q < D3_TAB_SEGS / 64u; q++) t[q] = lane + 64u * q < ns ? a[a[lane + 64u * q] & D3_JMP_SEG] : 0u;
+      wave_lds_sync();
+#pragma unroll
+      for (uint32_t q = 0; q < D3_TAB_SEGS / 64u; q++)
+        if (lane + 64u * q < ns) a[lane + 64u * q] = (uint16_t)t[q];
+      wave_lds_sync();
+    }
+    const uint32_t end = uni((uint32_t)a[sg]);
+    if (end & D3_JMP_SOURCE) draws = (uint32_t)(1 + len - (int)uni((uint32_t)dep[end & D3_JMP_SEG]));
+    wave_lds_sync();  // (read before the wave's next walk writes here)
+  }
+  if (draws == 0u) { *bad = true; return 1; }
+  return (int)draws;
+}
+
+// draws of draw-dependent gap v when its draws start at base + d, for every d it can meet.  Two kernels, one launch: the
+// host knows a short list (one g2s_d3_front: up to D3_FRONT_GAPS gaps) from a long one, not the tables' size.
+//   g2s_d3_tables        long lists (config 3: thousands of tiles) — by tile: a workgroup takes 256 consecutive
+//              deviations of one gap, the closure's links in LDS, one serial walk per thread.  What it needs to know
+//              comes in three round trips: the tile's gap (tile_var), that gap's record (D3Var), then the closure's
+//              links and the rand() values the tile's walks can read — both into LDS: a walk asks for a value at every
+//              choice between parents, and a round trip to memory per choice was the kernel's time (20 us for a
+//              30-segment path).  (the window: map_cap + 256 words of dynamic LDS — the longest path, 256 starts)
+//   g2s_d3_tables_waves  short lists.  It reads the table layout from the summary.  Up to D3_WAVE_TILES tiles — by wave:
+//              a WAVE per (v, d), d3_count_wave: the chip takes them all at once or nearly, and no walk is a chain of
+//              30-70 dependent hops.  Unit u of the launch is deviation u % 256 of tile u / 256, the units taken from
+//              the launch's last workgroup down; a closure of more than D3_TAB_SEGS segments is left to a tiles' pass
+//              behind, which the first workgroups begin at once.  More tiles: that tiles' pass for all of them.
+// D3_WAVE_TILES: a unit is four round trips to memory and the jumping, ~3 us; a tile's walks take ~8 us (the first
+// workgroup's laps on configs 2 and 3) however many tiles the chip holds at once, so the waves have to be through in three
+// rounds or so to be ahead: four units per wave of the launch, of which the deviations beyond a gap's R take a moment.
+// Measured at config 2 (25 tiles), config 5 (~50, closures beyond D3_TAB_SEGS among them) and config 4 (~110).
+#define D3_WAVE_GRID 2048u  /* workgroups of g2s_d3_tables_waves' launch: 8 192 waves */
+#define D3_WAVE_ROUNDS 4u
+#define D3_WAVE_TILES (D3_WAVE_GRID * 4u * D3_WAVE_ROUNDS / D3_TILE)
 __global__ __launch_bounds__(256) void g2s_d3_tables(const D3Params P, const D3Work W, const SubRec* __restrict__ sub,
                                                      const uint32_t* __restrict__ rnd /* first upcoming value */, uint64_t capacity) {
   __shared__ SegLite lseg[D3_TAB_SEGS];
@@ -733,6 +870,129 @@ __global__ __launch_bounds__(256) void g2s_d3_tables(const D3Params P, const D3W
     unsigned long long* laps = (unsigned long long*)((char*)W.sum + 512);
     if (blockIdx.x < tiles) atomicMax(&laps[32], wall_clock64());
     atomicMax(&laps[33], wall_clock64());
+  }
+}
+
+
+// (96 scalar registers: eight waves a SIMD for the tiles' pass in this kernel too — with five or seven a list's tiles, which
+// come in rounds, took 5-10 % longer; what does not fit is kept in vector registers' lanes, in the prologue and the waves'
+// pass, none of it in a walk's loop.  Both this and the empty asm below lean on the compiler: to check after a compiler
+// change, `hipcc -O3 --offload-arch=gfx950 -c d3_device.hip -Rpass-analysis=kernel-resource-usage` must say for this kernel
+// Occupancy 8, ScratchSize 0, and the first four global loads of its code must stand in front of its first s_waitcnt vmcnt.)
+__global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(96))) void g2s_d3_tables_waves(const D3Params P, const D3Work W, const SubRec* __restrict__ sub,
+                                                     const uint32_t* __restrict__ rnd /* first upcoming value */, uint64_t capacity) {
+  // (by tile: the closure's links; by wave: every wave's pointers and depths — never both in one launch for one closure)
+  __shared__ __attribute__((aligned(16))) uint32_t lraw[D3_TAB_SEGS * 4u];
+  static_assert(sizeof(SegLite) * D3_TAB_SEGS == sizeof(uint32_t) * D3_TAB_SEGS * 4u && 4u * 2u * D3_TAB_SEGS * sizeof(uint16_t) <= sizeof(uint32_t) * D3_TAB_SEGS * 4u, "one LDS area for both");
+  SegLite* lseg = (SegLite*)lraw;
+  extern __shared__ __attribute__((aligned(16))) uint32_t lwin[];
+  const uint32_t win_cap = P.map_cap + D3_TILE;
+  const D3Summary* S = W.sum;
+  const bool st0 = blockIdx.x == 0 && threadIdx.x == 0;
+  if (st0) stamp(W, 3);
+  const uint32_t tid = threadIdx.x;
+  // The first round trip to memory brings, besides the list's status and its tiles, the gap of this workgroup's first
+  // tile and of this wave's first unit (tile_var has more than 8 192 entries; what lies beyond `tiles` is not used) —
+  // asked for behind the status check, as the compiler would have it, they were a round trip of their own, ~1 us of
+  // every launch.  The second: whether that first tile's closure is one for the tiles' pass of a list that goes by wave.
+  const uint32_t u_first = (gridDim.x - 1u - blockIdx.x) * 4u + (tid >> 6);
+  uint32_t status = S->status, tiles = S->tiles, v_first = W.tile_var[blockIdx.x], v_unit = W.tile_var[u_first / D3_TILE];
+  asm volatile("" : "+v"(status), "+v"(tiles), "+v"(v_first), "+v"(v_unit));  // (all four in flight together)
+  status = uni(status); tiles = uni(tiles); v_first = uni(v_first); v_unit = uni(v_unit);
+  const uint32_t ns_first = W.vdesc[min(v_first, P.n)].ns;
+  if (status) return;
+  if (st0) stamp(W, 4);
+  const bool by_wave = tiles <= D3_WAVE_TILES;  // (the launch is D3_WAVE_GRID workgroups)
+  bool bad_any = false, worked = false;
+  if (by_wave) {
+    const uint32_t wave = uni(tid >> 6), units = tiles * D3_TILE;
+    uint16_t *jmp = (uint16_t*)lraw + wave * 2u * D3_TAB_SEGS, *dep = jmp + D3_TAB_SEGS;
+    // (from the launch's last workgroup down: the first ones have the tiles' pass behind this one, where a closure is large)
+    const bool stw = blockIdx.x == gridDim.x - 1u && tid == 0;  // (unit 0: its laps in the first workgroup's place)
+    for (uint32_t u = uni(u_first); u < units; u += gridDim.x * 4u) {
+      const uint32_t tile = u / D3_TILE;
+      const uint32_t v = uni(u == uni(u_first) ? v_unit : W.tile_var[tile]);
+      const uint4* vp = (const uint4*)&W.vdesc[v];
+      const uint4 h0 = vp[0], h1 = vp[1], h2 = vp[2], h3 = vp[3];  // (the record's words by position)
+      static_assert(offsetof(g2s::D3Var, R) == 4 && offsetof(g2s::D3Var, toff) == 8 && offsetof(g2s::D3Var, tile0) == 12 && offsetof(g2s::D3Var, base) == 16 &&
+                    offsetof(g2s::D3Var, dmin) == 20 && offsetof(g2s::D3Var, dspread) == 24 && offsetof(g2s::D3Var, ns) == 28 && offsetof(g2s::D3Var, sub_at) == 32 &&
+                    offsetof(g2s::D3Var, start_seg) == 40 && offsetof(g2s::D3Var, len0) == 48 && offsetof(g2s::D3Var, len1) == 52 && offsetof(g2s::D3Var, n_len) == 56, "D3Var by words");
+      // (what steers the wave goes to the scalar unit; the rest stays where it was loaded: the kernel is short of scalar registers)
+      const uint32_t R = uni(h0.y), toff = h0.z, tile0 = uni(h0.w), base = uni(h1.x), dmin = h1.y, dspread = h1.z, ns = uni(h1.w);
+      const uint32_t d = (tile - tile0) * D3_TILE + u % D3_TILE;
+      if (stw) stamp(W, 5);
+      if (d > R || ns > D3_TAB_SEGS) continue;
+      worked = true;
+      const uint64_t sub_at = (uint64_t)uni(h2.x) | ((uint64_t)uni(h2.y) << 32);
+      const uint64_t at = (uint64_t)base + d;
+      bool bad = false;
+      // (the values a walk from this deviation may read: dmin + dspread + 1 from its first.  The tiles' pass gives thread tid
+      // the tile's window less tid values, which is that many or more: a walk that asks for a value beyond them has drawn
+      // more than dmin + dspread times and is bad by the check below either way.  start_t is not read, as in
+      // d3_walk_count_lite: the walk begins at depth len, state len - d0 of its start segment.)
+      const int draws = d3_count_wave((int)uni(h3.z), (int)h3.x, (int)h3.y, h2.z, ns, (const SegW*)(sub + sub_at), rnd + at,
+                                      min(win_cap, dmin + dspread + 1u), capacity > at ? capacity - at : 0ull, jmp, dep, &bad);
+      if (stw) stamp(W, 6);
+      const int dev = draws - (int)dmin;
+      if (dev < 0 || dev > (int)dspread) bad = true;
+      if ((tid & 63u) == 0u) {
+        W.tab[(uint64_t)toff + d] = bad ? (uint16_t)0 : (uint16_t)dev;
+        if (W.tab_bad) W.tab_bad[(uint64_t)toff + d] = bad ? 1 : 0;
+        bad_any |= bad;
+      }
+    }
+  }
+  for (uint32_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+    if (by_wave && tile == blockIdx.x && ns_first <= D3_TAB_SEGS) continue;  // (the waves' — known without another round trip)
+    const uint32_t v = tile == blockIdx.x ? v_first : W.tile_var[tile];
+    const g2s::D3Var vd = W.vdesc[v];
+    const uint32_t ns = vd.ns;
+    if (by_wave && ns <= D3_TAB_SEGS) continue;
+    worked = true;
+    const uint32_t d0 = (tile - vd.tile0) * D3_TILE, d = d0 + tid;
+    const uint64_t at0 = (uint64_t)vd.base + d0;  // the tile's first value; thread tid starts tid values further on
+    const bool mine = d <= vd.R;
+    // a walk from deviation d reads values [d, d + dmin + dspread) of the tile's window
+    const uint32_t want = min(win_cap, min(vd.R - d0, D3_TILE - 1u) + vd.dmin + vd.dspread + 1u);
+    if (st0 && !by_wave) stamp(W, 5);  // (by wave: unit 0's laps)
+    __syncthreads();  // (the previous tile's walks are over)
+    {
+      const SegW* gs = (const SegW*)(sub + vd.sub_at);
+      const uint32_t in_lds = ns <= D3_TAB_SEGS ? ns : 0u;  // (a larger closure is walked where it lies)
+#pragma unroll
+      for (uint32_t it = 0; it < D3_TAB_SEGS / 256u; it++) {
+        const uint32_t q = tid + 256u * it;
+        if (q >= in_lds) continue;
+        SegLite l;
+        l.depth_len = gs[q].depth_len; l.par01 = gs[q].par01; l.par23 = gs[q].par23; l.flags = gs[q].flags;
+        lseg[q] = l;
+      }
+      for (uint32_t x = tid; x < want; x += 256u) lwin[x] = at0 + x < capacity ? rnd[at0 + x] : 0u;
+    }
+    __syncthreads();
+    if (st0 && !by_wave) stamp(W, 6);
+    if (mine) {
+      // (the closures of deep searches — thousands of segments, the large variant's — are walked where they lie)
+      bool bad = false;
+      const uint64_t at = at0 + tid;
+      const uint32_t nw = want > tid ? want - tid : 0u;
+      const uint64_t av = capacity > at ? capacity - at : 0ull;
+      const int draws = ns > D3_TAB_SEGS
+                            ? d3_walk_count(vd.n_len, vd.len0, vd.len1, vd.start_seg, vd.start_t, (int)ns, (const SegW*)(sub + vd.sub_at), lwin + tid, nw, av, &bad)
+                            : d3_walk_count_lite(vd.n_len, vd.len0, vd.len1, vd.start_seg, (int)ns, lseg, lwin + tid, nw, av, &bad);
+      const int dev = draws - (int)vd.dmin;
+      if (dev < 0 || dev > (int)vd.dspread) bad = true;
+      W.tab[(uint64_t)vd.toff + d] = bad ? (uint16_t)0 : (uint16_t)dev;
+      if (W.tab_bad) W.tab_bad[(uint64_t)vd.toff + d] = bad ? 1 : 0;
+      bad_any |= bad;
+    }
+  }
+  if (bad_any) atomicAdd(&W.sum->anomalies, 1u);
+  if (st0) stamp(W, 7);
+  if (P.laps && (tid & 63u) == 0u) {  // (G2S_DEBUG: the first workgroup's entry; the end of the last wave with a walk, and of the last workgroup of all)
+    unsigned long long* laps = (unsigned long long*)((char*)W.sum + 512);
+    if (worked) atomicMax(&laps[32], wall_clock64());
+    if (tid == 0) atomicMax(&laps[33], wall_clock64());
   }
 }
 
@@ -1059,7 +1319,7 @@ __global__ __launch_bounds__(1024) void g2s_d3_back(const D3Params P, const D3Wo
 // the closure and the first rand() value follow from the D3Trace record: two round trips in front of the walk)
 // NW waves per gap: one on a list that fills the chip; four on a short list, whose trace kernel is its slowest gap —
 // the passes over the closure, over the stretches of the fill and over its bases are shared by the workgroup's threads,
-// the chain of segments is walked by every wave for itself (LDS reads; the same words written by all)
+// the chain's jump tables too; every wave then lists the chain's segments for itself (LDS reads; the same words written by all)
 template <int NW>
 __global__ __launch_bounds__(64 * NW) void g2s_d3_trace(const D3Params P, const D3Work W, GapOut* __restrict__ outs,
                                                    const SubRec* __restrict__ sub, const char* __restrict__ chu,
@@ -1392,7 +1652,8 @@ __global__ __launch_bounds__(64 * NW) void g2s_d3_trace(const D3Params P, const 
   int nh = 0;
   {
     // (i) The chain of segments: from the start along the parents chosen above until a source or a segment without a
-    // way on — ONE LDS word and a dozen scalar instructions per segment entered (the walk that also carried depths and
+    // way on.  By jump tables (below) where they fit; else, and until this was written for every closure, hop by hop —
+    // ONE LDS word and a dozen scalar instructions per segment entered (the walk that also carried depths and
     // checked them was 80 instructions and 500 cycles a segment: 8 of the 27 us of config 2's longest wave).
     // A traceback descends: it enters a segment once, so a chain of more than nsegs segments is not one.
     const uint32_t sg = (go.start_seg >> (16 * pick)) & 0xFFFFu;
@@ -1402,7 +1663,47 @@ __global__ __launch_bounds__(64 * NW) void g2s_d3_trace(const D3Params P, const 
     uint32_t last = 0x80000000u;
     const int hop_cap = (int)(big ? nsegs : min(nsegs, P.seg_cap));
     unsigned long long chain_hash = 14695981039346656037ull;
-    if (!bad && !big) {
+    // (the chain by pointer jumping where its tables fit the base map's room, which nobody uses yet: next^(2^j) for j < L =
+    // ceil(log2 nsegs), 16 bits a segment — a segment that ends the walk points at itself —, built by the whole workgroup
+    // in L - 1 squarings; lane h then finds the segment hop h enters from the binary digits of h, L dependent reads for
+    // all hops at once instead of one per hop.  The segments that do not end the walk are a prefix of the hops: their
+    // number is the last hop's.  A start that has not come to an end within nsegs hops is on a cycle.)
+    const uint32_t L = nsegs > 1u ? 32u - (uint32_t)__builtin_clz(nsegs - 1u) : 0u;
+    const bool jump = !big && L * nsegs <= 2u * P.map_cap;
+    uint16_t* J = (uint16_t*)cmap;
+    if (jump) {  // (every wave of the workgroup, whatever it thinks of the start: the barriers are the workgroup's)
+      for (uint32_t q = (uint32_t)tid; q < nsegs && L > 0u; q += (uint32_t)NT) { const uint32_t y = pk[q].y; J[q] = (uint16_t)((y & 0xC0000000u) ? q : (y & 0xFFFFu)); }
+      wg_sync();
+      for (uint32_t j = 1; j < L; j++) {
+        for (uint32_t q = (uint32_t)tid; q < nsegs; q += (uint32_t)NT) J[j * nsegs + q] = J[(j - 1u) * nsegs + J[(j - 1u) * nsegs + q]];
+        wg_sync();
+      }
+    }
+    if (!bad && jump) {
+      bool ended_chain = false;
+      for (uint32_t h0 = 0; h0 < (uint32_t)hop_cap; h0 += 64u) {
+        const uint32_t h = h0 + (uint32_t)lane;
+        const bool in = h < (uint32_t)hop_cap;
+        uint32_t sq = (uint32_t)si;
+        for (uint32_t j = 0; j < L; j++) { const uint32_t to = J[j * nsegs + sq]; sq = ((h >> j) & 1u) ? to : sq; }
+        const uint32_t y = pk[sq].y;
+        const uint32_t on = (uint32_t)__popcll(__ballot(in && !(y & 0xC0000000u)));  // (hops of this stretch that go on: its first `on`)
+        if (in && (uint32_t)lane <= on) hop[h].y = sq;
+        if (on < min(64u, (uint32_t)hop_cap - h0)) {  // (the walk ends in this stretch)
+          nh = (int)(h0 + on) + 1;
+          last = uni((uint32_t)__shfl((int)y, (int)on));
+          ended_chain = true;
+          break;
+        }
+      }
+      if (!ended_chain) { nh = hop_cap; bad = true; }
+      if (!bad && spec) {  // (a guessed gap: the chain's hash over the hops in the order of the walk)
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_wave_barrier();
+        for (int h = 0; h < nh; h++) chain_hash = (chain_hash ^ (unsigned long long)uni(hop[h].y)) * 1099511628211ull;
+      }
+    }
+    if (!bad && !big && !jump) {
       if (spec) {  // (a guessed gap: the chain's hash in the order of the walk)
         for (;;) {
           if (nh >= hop_cap) { bad = true; break; }
@@ -1429,6 +1730,8 @@ __global__ __launch_bounds__(64 * NW) void g2s_d3_trace(const D3Params P, const 
         }
         if (!bad && (nh & 63) != 0 && lane < (nh & 63)) hop[(nh & ~63) + lane].y = hv;
       }
+    }
+    if (!bad && !big) {
       if (P.laps) hops = (unsigned long long)nh;
       // (the fill kernel's wave guessed THIS chain, from this length: text, case, fuz values and draws are the guess's —
       // they are in the caller's buffers already)
@@ -1716,6 +2019,70 @@ static void launch_scan(hipStream_t st, const D3Params& P, const D3Work& W, cons
   hipLaunchKernelGGL(g2s_d3_scan, dim3(1), dim3(1024), lds, st, P, W, outs);
 }
 
+// The tables' kernel of a list: g2s_d3_tables_waves for a short list — D3_WAVE_GRID workgroups, wide enough for its tables
+// to go a wave per entry; a workgroup without work leaves after two loads — and g2s_d3_tables, a tile per workgroup and
+// grid-stride, for a long one.
+static hipError_t launch_tables(hipStream_t st, const D3Params& P, const D3Work& W, const SubRec* sub, uint32_t* rnd_all, uint64_t rnd_capacity) {
+  const size_t win = ((size_t)P.map_cap + D3_TILE) * 4;
+  const bool waves = P.n <= D3_FRONT_GAPS;
+  const hipError_t e = hipFuncSetAttribute(waves ? (const void*)g2s_d3_tables_waves : (const void*)g2s_d3_tables, hipFuncAttributeMaxDynamicSharedMemorySize, (int)win);
+  if (e != hipSuccess) return e;
+  if (waves) hipLaunchKernelGGL(g2s_d3_tables_waves, dim3(D3_WAVE_GRID), dim3(256), win, st, P, W, sub, rnd_all + 31, rnd_capacity);  // (it reads tile_var[blockIdx.x])
+  else hipLaunchKernelGGL(g2s_d3_tables, dim3(std::min(8192u, std::max(128u, P.n / 2u))), dim3(256), win, st, P, W, sub, rnd_all + 31, rnd_capacity);
+  return hipGetLastError();
+}
+
+hipError_t test_d3_tables(const uint32_t* segs, uint32_t nsegs, int32_t n_len, int32_t len0, int32_t len1, uint32_t start_seg,
+                          const uint32_t* rnd, uint64_t rnd_cap, uint32_t base, uint32_t R, uint32_t dmin, uint32_t dspread,
+                          uint16_t* entries, uint8_t* bad, uint32_t* anomalies) {
+  // one list of one draw-dependent gap, laid out as g2s_d3_front leaves it: the summary, the gap's record, its tiles
+  const uint32_t tiles = (R + D3_TILE) / D3_TILE;
+  const size_t n_tile_var = 8192u + tiles, n_rnd = 31u + (size_t)rnd_cap + 64u;
+  std::vector<SegW> hs(std::max(nsegs, 1u));
+  for (uint32_t q = 0; q < nsegs; q++) {
+    SegW w = {};
+    w.depth_len = segs[4u * q]; w.par01 = segs[4u * q + 1u]; w.par23 = segs[4u * q + 2u]; w.flags = segs[4u * q + 3u];
+    hs[q] = w;
+  }
+  std::vector<uint32_t> hr(n_rnd, 0u);
+  for (uint64_t x = 0; x < rnd_cap; x++) hr[31u + x] = rnd[x];
+  D3Var vd = {};
+  vd.gap = 0; vd.R = R; vd.toff = 0; vd.tile0 = 0; vd.base = base; vd.dmin = dmin; vd.dspread = dspread; vd.ns = nsegs;
+  // (the state at which a path length enters its start segment, as the fill kernel leaves it: the one at depth len)
+  auto start_t = [&](int pick) -> uint32_t {
+    const uint32_t sg = (start_seg >> (16 * pick)) & 0xFFFFu;
+    const int t = sg < nsegs ? (pick ? len1 : len0) - (int)(segs[4u * sg] & 0xFFFFu) : 0;
+    return t >= 0 && t <= 0xFFFF ? (uint32_t)t : 0u;
+  };
+  vd.sub_at = 0; vd.start_seg = start_seg; vd.start_t = start_t(0) | (start_t(1) << 16); vd.len0 = len0; vd.len1 = len1; vd.n_len = n_len;
+  D3Summary sum = {};
+  sum.n_var = 1; sum.tiles = tiles; sum.table_entries = (uint64_t)R + 1u;
+  void *d_sum = nullptr, *d_vd = nullptr, *d_tv = nullptr, *d_seg = nullptr, *d_rnd = nullptr, *d_tab = nullptr, *d_bad = nullptr;
+  auto release = [&]() { for (void* p : {d_sum, d_vd, d_tv, d_seg, d_rnd, d_tab, d_bad}) if (p) (void)hipFree(p); };
+  hipError_t e = hipSuccess;
+  auto ok = [&](hipError_t x) { if (e == hipSuccess) e = x; return e == hipSuccess; };
+  if (ok(hipMalloc(&d_sum, 1024)) && ok(hipMalloc(&d_vd, 4 * sizeof(D3Var))) && ok(hipMalloc(&d_tv, n_tile_var * 4)) &&
+      ok(hipMalloc(&d_seg, hs.size() * sizeof(SegW))) && ok(hipMalloc(&d_rnd, n_rnd * 4)) && ok(hipMalloc(&d_tab, ((size_t)R + 1u) * 2)) &&
+      ok(hipMalloc(&d_bad, (size_t)R + 1u)) && ok(hipMemset(d_sum, 0, 1024)) && ok(hipMemset(d_vd, 0, 4 * sizeof(D3Var))) &&
+      ok(hipMemset(d_tv, 0, n_tile_var * 4)) && ok(hipMemset(d_tab, 0xFF, ((size_t)R + 1u) * 2)) && ok(hipMemset(d_bad, 0xFF, (size_t)R + 1u)) &&
+      ok(hipMemcpy(d_sum, &sum, sizeof sum, hipMemcpyHostToDevice)) && ok(hipMemcpy(d_vd, &vd, sizeof vd, hipMemcpyHostToDevice)) &&
+      ok(hipMemcpy(d_seg, hs.data(), hs.size() * sizeof(SegW), hipMemcpyHostToDevice)) &&
+      ok(hipMemcpy(d_rnd, hr.data(), n_rnd * 4, hipMemcpyHostToDevice))) {
+    D3Params P;
+    memset(&P, 0, sizeof P);
+    P.n = 1; P.group_size = 1;
+    P.map_cap = ((uint32_t)std::max(std::max(len0, len1), 0) + 2u + 3u) & ~3u;  // (as the session sets it: the longest path + 2)
+    D3Work W;
+    W.sum = (D3Summary*)d_sum; W.vdesc = (D3Var*)d_vd; W.tile_var = (uint32_t*)d_tv; W.tab = (uint16_t*)d_tab; W.tab_bad = (uint8_t*)d_bad;
+    if (ok(launch_tables(nullptr, P, W, (const SubRec*)d_seg, (uint32_t*)d_rnd, rnd_cap)) && ok(hipDeviceSynchronize()) &&
+        ok(hipMemcpy(entries, d_tab, ((size_t)R + 1u) * 2, hipMemcpyDeviceToHost)) && ok(hipMemcpy(bad, d_bad, (size_t)R + 1u, hipMemcpyDeviceToHost)) &&
+        ok(hipMemcpy(&sum, d_sum, sizeof sum, hipMemcpyDeviceToHost)))
+      *anomalies = sum.anomalies;
+  }
+  release();
+  return e;
+}
+
 hipError_t launch_rand_window(hipStream_t st, uint32_t* rnd_all, const uint32_t* link) {
   hipLaunchKernelGGL(g2s_rand_window, dim3(1), dim3(64), 0, st, rnd_all, link);
   return hipGetLastError();
@@ -1734,11 +2101,8 @@ hipError_t launch_d3_sharded_tables(hipStream_t st, const D3Params& P, const D3W
                                     uint32_t* rnd_all, uint64_t rnd_capacity, uint32_t* group_fn) {
   if (P.n == 0) return hipSuccess;
   launch_scan(st, P, W, outs);  // (the layout again, behind the groups in front)
-  const uint32_t tgrid = std::min(8192u, std::max(128u, P.n / 2u));
-  const size_t win = ((size_t)P.map_cap + 256) * 4;
-  hipError_t e = hipFuncSetAttribute((const void*)g2s_d3_tables, hipFuncAttributeMaxDynamicSharedMemorySize, (int)win);
+  const hipError_t e = launch_tables(st, P, W, sub, rnd_all, rnd_capacity);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(g2s_d3_tables, dim3(tgrid), dim3(256), win, st, P, W, sub, rnd_all + 31, rnd_capacity);
   hipLaunchKernelGGL(g2s_d3_blocks, dim3(256), dim3(256), 0, st, W);
   hipLaunchKernelGGL(g2s_d3_groupfn, dim3(std::min(256u, (P.R0 + 256u) / 256u)), dim3(256), 0, st, W, P.R0, group_fn);
   return hipGetLastError();
@@ -1780,14 +2144,7 @@ hipError_t launch_d3(hipStream_t st, const D3Params& P, const D3Work& W, const G
     hipLaunchKernelGGL(g2s_d3_classify, dim3((P.n + 255u) / 256u), dim3(256), 0, st, P, W, outs, dgaps);
     launch_scan(st, P, W, outs);
   }
-  // (a tile of 256 deviations per workgroup, grid-stride: a short list has a few dozen tiles)
-  const uint32_t tgrid = std::min(8192u, std::max(128u, P.n / 2u));
-  const size_t win = ((size_t)P.map_cap + 256) * 4;
-  if (!P.restart) {
-    e = hipFuncSetAttribute((const void*)g2s_d3_tables, hipFuncAttributeMaxDynamicSharedMemorySize, (int)win);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(g2s_d3_tables, dim3(tgrid), dim3(256), win, st, P, W, sub, rnd_all + 31, rnd_capacity);
-  }
+  if (!P.restart) { e = launch_tables(st, P, W, sub, rnd_all, rnd_capacity); if (e != hipSuccess) return e; }
   // (g2s_d2_* runs on a stream of its own beside the kernels above; the hand-off reads what it decided)
   if (ev_d2 && short_list && !P.restart) { e = hipStreamWaitEvent(st, ev_d2, 0); if (e != hipSuccess) return e; }
   if (P.restart) (void)ev_chain;  // (no chain: the list's draws are nobody's to continue)

@@ -5532,6 +5532,20 @@ extern "C" int g2s_test_device_rand(int device, uint32_t seed, uint64_t skip, ui
   return G2S_OK;
 }
 
+// TEST HOOK: g2s_d3_tables_waves for one gap of the caller's design (d3_device.h: test_d3_tables)
+extern "C" int g2s_test_d3_tables(int device, const uint32_t* segs, uint32_t n_segs, int32_t n_len, int32_t len0, int32_t len1,
+                                  uint32_t start_seg, const uint32_t* rnd, uint64_t rnd_cap, uint32_t base, uint32_t R, uint32_t dmin,
+                                  uint32_t dspread, uint16_t* entries, uint8_t* bad, uint32_t* anomalies) {
+  if ((!segs && n_segs) || (!rnd && rnd_cap) || !entries || !bad || !anomalies || n_segs > 0xFFFFu || n_len < 1 || n_len > 2 ||
+      (uint64_t)R + 1u > (uint64_t)G2S_D3_TABLE_BUDGET)
+    return fail(G2S_ERR_ARG, "g2s_test_d3_tables: bad argument");
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return fail(G2S_ERR_NO_DEVICE, "no such device");
+  HIP_TRY(hipSetDevice(device));
+  HIP_TRY(test_d3_tables(segs, n_segs, n_len, len0, len1, start_seg, rnd, rnd_cap, base, R, dmin, dspread, entries, bad, anomalies));
+  return G2S_OK;
+}
+
 // TEST HOOK: the n values behind `skip` values that were drawn elsewhere — GlibcRandStream::skip, the jump by the
 // recurrence's polynomial g2s_share_end moves a rank's generator with — for comparison with g2s_test_rand_stream
 extern "C" int g2s_test_rand_skip(uint32_t seed, uint64_t skip, uint32_t n, int32_t* out) {

@@ -214,6 +214,9 @@ _SIGS = {
     "g2s_test_rand_skip": (C.c_int, [C.c_uint32, C.c_uint64, C.c_uint32, C.POINTER(C.c_int32)]),
     "g2s_test_rand_stream": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_int32)]),
     "g2s_test_device_rand": (C.c_int, [C.c_int, C.c_uint32, C.c_uint64, C.c_uint32, C.POINTER(C.c_int32)]),
+    "g2s_test_d3_tables": (C.c_int, [C.c_int, C.POINTER(C.c_uint32), C.c_uint32, C.c_int32, C.c_int32, C.c_int32, C.c_uint32,
+                                     C.POINTER(C.c_uint32), C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                     C.POINTER(C.c_uint16), C.POINTER(C.c_uint8), C.POINTER(C.c_uint32)]),
     "g2s_test_post_closure": (C.c_int, [_VP, C.POINTER(g2s_params), C.POINTER(g2s_gap), C.c_uint32,
                                         C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint64), C.c_int32, C.c_int32,
                                         C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_uint32, C.c_uint64,
@@ -1070,6 +1073,19 @@ def test_device_rand(device, seed, skip, n):
     out = (C.c_int32 * max(1, n))()
     _check(load_library().g2s_test_device_rand(device, seed, skip, n, out))
     return [out[i] for i in range(n)]
+
+
+def test_d3_tables(device, segs, n_len, len0, len1, start_seg, rnd, base, R, dmin, dspread):
+    """TEST HOOK binding (g2s_test_d3_tables): the product's kernel g2s_d3_tables_waves for one designed gap.  segs: a list of
+    (depth | len << 16, parents 0-1, parents 2-3, flags); rnd: the stream's raw words (nothing exists behind them).
+    Returns (entries, bad, anomalies): the table entry and the bad verdict of every deviation 0 .. R, the list's counter."""
+    flat = [w for s in segs for w in s]
+    sa = (C.c_uint32 * max(1, len(flat)))(*flat)
+    ra = (C.c_uint32 * max(1, len(rnd)))(*rnd)
+    ent, bad, anom = (C.c_uint16 * (R + 1))(), (C.c_uint8 * (R + 1))(), C.c_uint32()
+    _check(load_library().g2s_test_d3_tables(device, sa, len(segs), n_len, len0, len1, start_seg, ra, len(rnd), base, R, dmin,
+                                             dspread, ent, bad, C.byref(anom)))
+    return list(ent), list(bad), anom.value
 
 
 def test_group_queue_slow(nworkers, n, group_size, slow_worker, slow_us):

@@ -68,6 +68,18 @@ int g2s_test_rand_skip(uint32_t seed, uint64_t skip, uint32_t n, int32_t* out);
  * values handed over by the host, every block of 4096 values reached with three jump polynomials). */
 int g2s_test_device_rand(int device, uint32_t seed, uint64_t skip, uint32_t n, int32_t* out);
 
+/* TEST HOOK: the product's kernel g2s_d3_tables_waves (d3_device.hip, a short list's tables: the draws of a draw-dependent gap's traceback for every
+ * place of the list's rand() stream it can start at) for ONE gap of the caller's design, on `device`.  segs: n_segs closure
+ * segments of four words {depth | len << 16, parents 0-1, parents 2-3, flags} (a parent slot without a parent: 0xFFFF);
+ * n_len (1 or 2) path lengths len0 / len1 and their start segments start_seg = start 0 | start 1 << 16; rnd: rnd_cap raw
+ * words of the stream from its first value (rand() = word >> 1; nothing exists behind them); base: the gap's first draw
+ * at deviation 0; R: its deviations are 0 .. R; dmin / dspread: its fewest draws and most - fewest.  entries[d] receives
+ * what the kernel wrote to the table (draws - dmin, or 0 for a bad walk), bad[d] whether the walk was bad, for d in
+ * [0, R]; *anomalies the list's anomaly counter (nonzero = the list would go to the host path). */
+int g2s_test_d3_tables(int device, const uint32_t* segs, uint32_t n_segs, int32_t n_len, int32_t len0, int32_t len1,
+                       uint32_t start_seg, const uint32_t* rnd, uint64_t rnd_cap, uint32_t base, uint32_t R, uint32_t dmin,
+                       uint32_t dspread, uint16_t* entries, uint8_t* bad, uint32_t* anomalies);
+
 /* TEST HOOK: the host worker pool that runs the per-gap analysis and tracebacks: `rounds`
  * parallel-for rounds of `n` tasks on `threads` threads (task i adds i+1 to a per-round
  * sum); returns G2S_OK when every task of every round ran exactly once. */
