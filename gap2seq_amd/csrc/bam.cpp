@@ -97,7 +97,7 @@ struct BamFile::Stream {
   size_t lo = 0, hi = 0;
   std::string err;
   int64_t bad_blk = -1;
-  const size_t chunk = chunk_bytes();
+  const size_t chunk = f.window_bytes_ ? f.window_bytes_ : chunk_bytes();
   // device path: the slot whose window is being read, and the window in flight
   BgzfDevice* dev = nullptr;
   int cur = -1, fly = -1;

@@ -23,7 +23,8 @@ class BgzfDevice;
 class BamRowsDevice;
 
 enum : uint32_t {
-  BAM_PAIRED = 1, BAM_UNMAPPED = 4, BAM_MATE_UNMAPPED = 8, BAM_REVERSE = 16, BAM_READ1 = 64, BAM_READ2 = 128
+  BAM_PAIRED = 1, BAM_UNMAPPED = 4, BAM_MATE_UNMAPPED = 8, BAM_REVERSE = 16, BAM_READ1 = 64, BAM_READ2 = 128,
+  BAM_SECONDARY = 0x100, BAM_SUPPLEMENTARY = 0x800
 };
 
 // one alignment record, pointing into the reader's buffer (valid during the callback only)
@@ -64,6 +65,8 @@ class BamFile {
   // every record in file order; stops early (returning true) when fn returns false.  False = broken file.
   bool for_each(const std::function<bool(const BamRec&)>& fn, std::string* err) const;
   void set_threads(int t) { threads_ = t < 1 ? 1 : t; }
+  // inflated bytes a window (whole members, one at the least) of the passes that follow; 0: G2S_BAM_CHUNK, else 32 MiB
+  void set_window_bytes(size_t n) { window_bytes_ = n; }
   size_t blocks() const { return blk_off_.size(); }
   // Where for_each / read_all inflate.  device >= 0: the members of a window are inflated by g2s_bgzf_inflate on that
   // device while the window before is being walked; a device that refuses (no usable gfx950, an allocation or a HIP
@@ -110,6 +113,7 @@ class BamFile {
   std::vector<std::string> ref_names_;
   uint64_t first_rec_ = 0;            // inflated offset of the first alignment record
   int threads_ = 4;
+  size_t window_bytes_ = 0;
   bool use_core_ = false;
   int inflate_device_ = -1;
   BgzfDevice* device_buffers() const;           // made at the first device refill, kept for the passes that follow

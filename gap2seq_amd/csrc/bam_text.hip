@@ -26,17 +26,15 @@
 #include <vector>
 
 #include "bam.hpp"
+#include "bam_decode.h"
 #include "bam_text.h"
 #include "hip_host.h"
 
 namespace {
 
-constexpr uint32_t kBlock = 256, kWave = 64;
-constexpr uint32_t kRecHead = 36;  // block_size and the 32 fixed bytes
+using namespace g2s::bam_decode;  // (kWave, kRecHead, ld32, Piece, emit: one record's bytes by a wave)
 
-__device__ __forceinline__ uint32_t ld32(const uint8_t* p) {
-  return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24;
-}
+constexpr uint32_t kBlock = 256;
 
 // what comes down between the scans and the outputs, in one copy
 struct Totals {
@@ -124,42 +122,6 @@ __global__ void k_totals(uint64_t n, const uint64_t* __restrict__ off_a, const u
   tot->bytes_b = off_b[n];
   tot->n_held = idx[n];
   tot->n_un = uidx[n];
-}
-
-enum Piece : int { kBases = 0, kName = 1, kFasta = 2 };
-
-// `len` bytes of one record's output at dst, by the lanes of a wave: byte i by lane i mod 64
-template <int PIECE>
-__device__ __forceinline__ void emit(const uint8_t* __restrict__ rec, uint64_t len, uint8_t* __restrict__ dst, uint32_t lane) {
-  const uint32_t l_name = rec[12], w = ld32(rec + 16), n_cigar = w & 0xFFFFu, flag = w >> 16;
-  const uint64_t l_seq = ld32(rec + 20);
-  const uint8_t* name = rec + kRecHead;
-  const uint8_t* seq = name + l_name + 4u * (size_t)n_cigar;
-  const bool reverse = (flag & g2s::BAM_REVERSE) != 0;
-  const char end = (flag & g2s::BAM_READ1) ? '1' : '2';
-  // the name's length follows from the piece's: nothing is searched twice
-  const uint64_t nl = PIECE == kName ? len - 2 : PIECE == kFasta ? len - 5 - l_seq : 0;
-  auto base = [&](uint64_t j) {
-    const uint64_t at = reverse ? l_seq - 1 - j : j;
-    return g2s::base_char((uint32_t)(seq[at >> 1] >> ((~at & 1u) << 2)) & 15u, reverse);
-  };
-  for (uint64_t i = lane; i < len; i += kWave) {
-    char c;
-    if (PIECE == kBases) {
-      c = i < l_seq ? base(i) : 'N';
-    } else if (PIECE == kName) {
-      c = i < nl ? (char)name[i] : i == nl ? '/' : end;
-    } else {  // > name /1 \n bases \n
-      if (i == 0) c = '>';
-      else if (i <= nl) c = (char)name[i - 1];
-      else if (i == nl + 1) c = '/';
-      else if (i == nl + 2) c = end;
-      else if (i == nl + 3) c = '\n';
-      else if (i - (nl + 4) < l_seq) c = base(i - (nl + 4));
-      else c = '\n';
-    }
-    dst[i] = (uint8_t)c;
-  }
 }
 
 template <int PIECE_A, int PIECE_B>

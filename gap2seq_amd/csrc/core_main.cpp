@@ -69,7 +69,9 @@ int main(int argc, char** argv) {
       std::cout << "Gap2Seq-core (MI355X) -reads a.fq[,b.fq] -filled out.fa (-scaffolds in.fa | -left S -right S -length N)\n"
                    "  [-k 31 (1..127)] [-solid 2] [-dist-error 500] [-fuz 10] [-max-mem 20] [-randseed 0]\n"
                    "  [-all-upper] [-best-only] [-unique] [-nb-cores N] [-device D | -devices D0,D1,...] [-streams 2]\n"
-                   "  [-stream-gaps 8192] [-fasta-width 0]\n";
+                   "  [-stream-gaps 8192] [-fasta-width 0]\n"
+                   "  -reads: FASTA or FASTQ files (plain, gzip or BGZF) and BAM files, told by their bytes; a BAM file gives\n"
+                   "  every record that is neither secondary nor supplementary, as the read was sequenced\n";
       return EXIT_SUCCESS;
     }
     else {  // GATB's OptionsParser rejects what it does not know; main.cpp:29-31 prints the message

@@ -60,6 +60,38 @@ bool GzipReader::read(uint8_t* dst, size_t cap, size_t* got, std::string* err) {
   return true;
 }
 
+bool is_bam(const uint8_t* p, size_t n) {
+  uint8_t head[4];
+  size_t have = 0, o = 0;
+  while (have < 4) {
+    if (o + 18 > n || p[o] != 0x1f || p[o + 1] != 0x8b || p[o + 2] != 8 || !(p[o + 3] & 4)) return false;
+    const size_t xlen = (size_t)p[o + 10] | (size_t)p[o + 11] << 8;
+    if (o + 12 + xlen > n) return false;
+    size_t bsize = 0;
+    for (size_t x = o + 12; x + 4 <= o + 12 + xlen;) {
+      const size_t slen = (size_t)p[x + 2] | (size_t)p[x + 3] << 8;
+      if (p[x] == 'B' && p[x + 1] == 'C' && slen == 2 && x + 6 <= o + 12 + xlen) bsize = ((size_t)p[x + 4] | (size_t)p[x + 5] << 8) + 1;
+      x += 4 + slen;
+    }
+    if (bsize < 12 + xlen + 8 || (p[o + 3] & ~4)) return false;
+    const size_t data = o + 12 + xlen, data_end = std::min(o + bsize - 8, n);
+    z_stream zs;
+    memset(&zs, 0, sizeof zs);
+    if (inflateInit2(&zs, -15) != Z_OK) return false;
+    zs.next_in = const_cast<Bytef*>(p + data);
+    zs.avail_in = (uInt)(data_end - data);
+    zs.next_out = head + have;
+    zs.avail_out = (uInt)(4 - have);
+    const int rc = ::inflate(&zs, Z_SYNC_FLUSH);
+    have = 4 - zs.avail_out;
+    inflateEnd(&zs);
+    if (rc != Z_OK && rc != Z_STREAM_END && rc != Z_BUF_ERROR) return false;
+    if (have < 4 && rc != Z_STREAM_END) return false;  // (a member that ends without its end: no BAM file)
+    o += bsize;
+  }
+  return memcmp(head, "BAM\1", 4) == 0;
+}
+
 bool reads_text_of_bytes(const uint8_t* bytes, size_t n, const std::string& name, std::string* out, bool* gz, std::string* err) {
   if (gz) *gz = is_gzip(bytes, n);
   if (!is_gzip(bytes, n)) { out->assign((const char*)bytes, n); return true; }

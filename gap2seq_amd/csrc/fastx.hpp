@@ -42,6 +42,10 @@ class GzipReader {
   size_t left_ = 0;    // input bytes not yet handed to zlib
   bool done_ = false, in_member_ = false;
 };
+// A BAM file among the read files, told by its content alone: the bytes are gzip, their first member is a BGZF member (an
+// extra subfield 'B','C'), and the inflated stream begins with "BAM\1".  Members are inflated until four bytes are known
+// (n may be the head of a longer file: a member cut by n gives the bytes it has).  Any other gzip file is FASTA/FASTQ.
+bool is_bam(const uint8_t* bytes, size_t n);
 // a whole read file as text: its bytes, inflated when they are gzip.  *gz (may be null): whether they were.  false with
 // *err naming the file when it cannot be read or its gzip stream is truncated or corrupt.
 bool read_reads_file(const std::string& path, std::string* out, bool* gz, std::string* err);

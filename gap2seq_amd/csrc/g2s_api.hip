@@ -39,6 +39,7 @@
 #include "glibc_rand.hpp"
 #include "pass_plan.hpp"
 #include "post.hpp"
+#include "bam_reads.h"
 #include "reads_text.h"
 #include "readfilter_gaps.hpp"
 #include "seg_tables.h"
@@ -327,6 +328,7 @@ extern "C" int g2s_graph_build_files(const char* reads_csv, int k, int solid, in
   if (!reads_csv || !out) return fail(G2S_ERR_ARG, "g2s_graph_build_files: bad argument");
   const std::vector<std::string> files = split_csv(reads_csv);
   const bool debug = getenv("G2S_DEBUG") != nullptr;
+  int bam_reason = kBamReadsNotAsked, bam_anomaly = 0;  // what the device loader met in a BAM file, when it gave up
   // (G2S_HOST_BUILD: set to anything, as graph_build reads it)
   if (!getenv("G2S_HOST_BUILD") && !env_on("G2S_HOST_READS")) {
     const auto t0 = std::chrono::steady_clock::now();
@@ -338,8 +340,9 @@ extern "C" int g2s_graph_build_files(const char* reads_csv, int k, int solid, in
     std::string why;
     const ReadsLoadResult r = load_reads_device(inputs, getenv("G2S_DEVICE") ? atoi(getenv("G2S_DEVICE")) : 0,
                                                 (size_t)piece, env_bytes("G2S_BUILD_TEXT_FIRST_BYTES"),
-                                                env_on("G2S_HOST_INFLATE"), &text, &info, &why);
+                                                env_on("G2S_HOST_INFLATE"), &text, &info, &why, env_bytes("G2S_BUILD_RESIDENT_CAP"));
     if (r == kReadsIoError) return fail(G2S_ERR_IO, why);
+    if (r != kReadsOk) { bam_reason = info.bam_reason; bam_anomaly = info.bam_anomaly; }
     if (r == kReadsOk && text.T == 0) {  // (no sequence at all: the empty graph, as the host loader builds it)
       free_device_text(&text);
       why = "no text";
@@ -364,14 +367,34 @@ extern "C" int g2s_graph_build_files(const char* reads_csv, int k, int solid, in
     if (debug) fprintf(stderr, "[g2s] reads: the host loader takes over (%s)\n", why.c_str());
   }
   ReadsLoadInfo info;
+  info.bam_reason = bam_reason;
+  info.bam_anomaly = bam_anomaly;
   std::vector<FastxRecord> recs;
   for (const std::string& file : files) {
-    std::string text, err;
-    bool gz = false;
-    if (!read_reads_file(file, &text, &gz, &err)) return fail(G2S_ERR_IO, err);
+    std::string raw, text, err;
+    if (!read_text_file(file, &raw)) return fail(G2S_ERR_IO, "cannot read " + file);
+    const uint8_t* bytes = (const uint8_t*)raw.data();
+    const bool gz = is_gzip(bytes, raw.size());
     info.files++;
-    info.raw_bytes += text.size();
     info.inflate.push_back(gz ? kInflateZlib : kInflateNone);
+    if (gz && is_bam(bytes, raw.size())) {  // (bam_reads.h: the kept records' sequences, by the reader's walk)
+      ReadsInput in;
+      in.path = file;
+      in.mem = bytes;
+      in.mem_n = raw.size();
+      std::vector<std::string> seqs;
+      if (!bam_reads_host(in, &seqs, &info.bam_skipped, &info.raw_bytes, &err)) return fail(G2S_ERR_IO, err);
+      info.bam_files++;
+      info.bam_kept += seqs.size();
+      for (std::string& q : seqs) {
+        recs.emplace_back();
+        recs.back().seq.swap(q);
+      }
+      continue;
+    }
+    if (!gz) text.swap(raw);
+    else if (!reads_text_of_bytes(bytes, raw.size(), file, &text, nullptr, &err)) return fail(G2S_ERR_IO, err);
+    info.raw_bytes += text.size();
     parse_fastx(text, &recs);
   }
   std::vector<std::pair<const char*, uint64_t>> v;
@@ -408,23 +431,51 @@ extern "C" int g2s_test_last_reads_load(uint64_t* files, uint64_t* raw_bytes, ui
   return G2S_OK;
 }
 // TEST HOOK (include/g2s_test.h)
+extern "C" int g2s_test_last_reads_bam(uint64_t* bam_files, uint64_t* kept, uint64_t* skipped, int* by_kernels, int* reason,
+                                       int* anomaly) {
+  ReadsLoadInfo info;
+  {
+    std::lock_guard<std::mutex> lk(g_reads_info_mu);
+    info = g_reads_info;
+  }
+  if (bam_files) *bam_files = info.bam_files;
+  if (kept) *kept = info.bam_kept;
+  if (skipped) *skipped = info.bam_skipped;
+  if (by_kernels) *by_kernels = info.bam_kernels;
+  if (reason) *reason = info.bam_reason;
+  if (anomaly) *anomaly = info.bam_anomaly;
+  return G2S_OK;
+}
+// TEST HOOK (include/g2s_test.h)
 extern "C" int g2s_test_reads_text(const void* bytes, size_t n, int device, size_t piece_bytes, uint8_t* out, size_t cap,
                                    size_t* out_n) {
   if ((!bytes && n) || (!out && cap) || !out_n || device < -2) return fail(G2S_ERR_ARG, "g2s_test_reads_text: bad argument");
   const uint8_t* p = (const uint8_t*)bytes;
   if (device < 0) {
     std::string raw, err, text;
-    if (!reads_text_of_bytes(p, n, "(memory)", &raw, nullptr, &err)) return fail(G2S_ERR_IO, err);
     ReadsLoadInfo info;
     info.files = 1;
-    info.raw_bytes = raw.size();
-    if (device == -1) {
-      std::vector<FastxRecord> recs;
-      parse_fastx(raw, &recs);
-      for (auto& r : recs) { text += r.seq; text.push_back('N'); }
-      info.records = recs.size();
+    if (is_bam(p, n)) {  // (either host form: there is no line machine for BAM)
+      ReadsInput in;
+      in.mem = p;
+      in.mem_n = n;
+      std::vector<std::string> seqs;
+      if (!bam_reads_host(in, &seqs, &info.bam_skipped, &info.raw_bytes, &err)) return fail(G2S_ERR_IO, err);
+      for (const std::string& q : seqs) { text += q; text.push_back('N'); }
+      info.records = info.bam_kept = seqs.size();
+      info.bam_files = 1;
+      info.inflate.push_back(kInflateZlib);
     } else {
-      machine_text_host((const uint8_t*)raw.data(), raw.size(), &text, &info.records);
+      if (!reads_text_of_bytes(p, n, "(memory)", &raw, nullptr, &err)) return fail(G2S_ERR_IO, err);
+      info.raw_bytes = raw.size();
+      if (device == -1) {
+        std::vector<FastxRecord> recs;
+        parse_fastx(raw, &recs);
+        for (auto& r : recs) { text += r.seq; text.push_back('N'); }
+        info.records = recs.size();
+      } else {
+        machine_text_host((const uint8_t*)raw.data(), raw.size(), &text, &info.records);
+      }
     }
     info.positions = text.size();
     set_reads_info(info);
@@ -440,9 +491,13 @@ extern "C" int g2s_test_reads_text(const void* bytes, size_t n, int device, size
   ReadsLoadInfo info;
   std::string why;
   const ReadsLoadResult r = load_reads_device(inputs, device, piece_bytes,
-                                              env_bytes("G2S_BUILD_TEXT_FIRST_BYTES"), env_on("G2S_HOST_INFLATE"), &text, &info, &why);
+                                              env_bytes("G2S_BUILD_TEXT_FIRST_BYTES"), env_on("G2S_HOST_INFLATE"), &text, &info, &why,
+                                              env_bytes("G2S_BUILD_RESIDENT_CAP"));
   if (r == kReadsIoError) return fail(G2S_ERR_IO, why);
-  if (r != kReadsOk) return fail(G2S_ERR_HIP, "g2s_test_reads_text: the device refused (" + why + ")");
+  if (r != kReadsOk) {
+    set_reads_info(info);  // (g2s_test_last_reads_bam: what a BAM file met)
+    return fail(G2S_ERR_HIP, "g2s_test_reads_text: the device refused (" + why + ")");
+  }
   set_reads_info(info);
   *out_n = (size_t)text.T;
   const size_t take = std::min<size_t>(cap, (size_t)text.T);

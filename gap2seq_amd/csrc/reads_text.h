@@ -1,6 +1,6 @@
 // gap2seq_amd/csrc/reads_text.h — the graph build's text made from read files (reads_text.hip).
 //
-// For the sequences s0 ... s(n-1) of a list of FASTA/FASTQ files the build's text is s0 N s1 N ... s(n-1) N.  The device
+// For the sequences s0 ... s(n-1) of a list of FASTA/FASTQ (and BAM: bam_reads.h) files the build's text is s0 N s1 N ... s(n-1) N.  The device
 // loader makes it in device memory from the files' raw bytes, a piece at a time, with the kernels k_fastx_* (the state
 // machine of fastx_machine.h); gzip input is inflated on the way: BGZF members on the device (bgzf_inflate.h), any
 // other gzip stream by zlib into the staging buffers.  The host loader (fastx.hpp) is the fallback and the authority.
@@ -17,11 +17,23 @@ namespace g2s {
 // how a file's bytes were inflated
 enum ReadsInflate : int { kInflateNone = 0, kInflateZlib = 1, kInflateDevice = 2, kInflateMixed = 3 };
 
-// What the process's last g2s_graph_build_files did to load its reads (g2s_test_last_reads_load).
+// who wrote the text of the BAM files among the read files (g2s_test_last_reads_bam), and when not the kernels, why
+enum BamReadsReason : int {
+  kBamReadsKernels = 0,   // k_bamreads_* (bam_reads.hip)
+  kBamReadsNotAsked = 1,  // G2S_HOST_BUILD, G2S_HOST_READS=1, G2S_HOST_INFLATE=1, or no usable device
+  kBamReadsAnomaly = 2,   // the row kernels gave the file back (bam_rows.h: RowsAnomaly says which)
+  kBamReadsOverCap = 3,   // stream, rows and text beyond half the free device memory, or G2S_BUILD_RESIDENT_CAP
+  kBamReadsHip = 4,       // an allocation or a HIP call failed
+};
+
+// What the process's last g2s_graph_build_files did to load its reads (g2s_test_last_reads_load, g2s_test_last_reads_bam).
 struct ReadsLoadInfo {
   uint64_t files = 0, raw_bytes = 0, positions = 0, records = 0, pieces = 0, grows = 0;
   int on_device = 0;
   std::vector<int> inflate;  // per file: ReadsInflate
+  // the BAM files among them: their number, the records kept and skipped, whether the kernels wrote their text
+  uint64_t bam_files = 0, bam_kept = 0, bam_skipped = 0;
+  int bam_kernels = 0, bam_reason = kBamReadsNotAsked, bam_anomaly = 0;
 };
 
 // one input of the loader: a file by name, or bytes in memory (the test hook)
@@ -52,8 +64,13 @@ enum ReadsLoadResult : int {
 // (0: chosen by the files' sizes, 32 MiB at most);
 // first_cap: the text buffer's first capacity in bytes when no bound is known (compressed input), 0 = the default.
 // host_inflate: BGZF members go to zlib too.  On kReadsOk *out owns the text (also when T == 0).
+// A BAM file of the list (bam_reads.h) gives its text through the kernels k_bamreads_* behind what the list has given so
+// far, the text buffer sized from its count; `piece` is then its window, resident_cap (G2S_BUILD_RESIDENT_CAP, 0: none)
+// lowers the bound of half the free device memory on its stream, rows and text.  With host_inflate its text is made by
+// the host walk and copied up.  On kReadsGaveUp info->bam_reason / bam_anomaly say what a BAM file met.
 ReadsLoadResult load_reads_device(const std::vector<ReadsInput>& inputs, int device, size_t piece, uint64_t first_cap,
-                                  bool host_inflate, DeviceText* out, ReadsLoadInfo* info, std::string* err);
+                                  bool host_inflate, DeviceText* out, ReadsLoadInfo* info, std::string* err,
+                                  uint64_t resident_cap = 0);
 void free_device_text(DeviceText* t);
 
 // the machine of fastx_machine.h walked line by line on the host over one file's bytes: the text is appended to *out

@@ -17,6 +17,9 @@
 // A record's separator is written when the NEXT record's header is met; so that no position depends on "is this the
 // file's first record" the kernels count the stream  N s0 N s1 ...  and write its byte j to text[base + j - 1]: byte 0
 // falls away and the file's end writes the last N.
+//
+// A BAM file of the list (told by fastx.hpp: is_bam) takes no piece: Loader::run_bam_file has bam_reads.hip make its text
+// behind what the list gave so far and moves the carry's text base past it.
 #include <hip/hip_runtime.h>
 #include <fcntl.h>
 #include <sys/mman.h>
@@ -33,6 +36,7 @@
 #include <string>
 #include <vector>
 
+#include "bam_reads.h"
 #include "bgzf_inflate.h"
 #include "fastx.hpp"
 #include "hip_host.h"
@@ -414,6 +418,10 @@ struct Loader {
   size_t piece = 0, raw_cap = 0;
   uint64_t first_cap = 0;
   bool host_inflate = false;
+  size_t bam_window = 0;       // a BAM file's window: the piece as asked for (0: the reader's own)
+  uint64_t resident_cap = 0;   // G2S_BUILD_RESIDENT_CAP
+  uint64_t mem_limit = 0;      // half the free device memory when the loader began, and the cap
+  uint64_t bam_by_host = 0;    // BAM files whose text the host walk made (host_inflate)
   ReadsLoadInfo* info = nullptr;
   std::string* why = nullptr;  // (G2S_HIP_TRY)
   std::string io_error;
@@ -506,6 +514,74 @@ struct Loader {
     return true;
   }
 
+  // room for a BAM file's `more` text bytes behind the `have` there are: sized from the count, once, padding included
+  bool room(uint64_t have, uint64_t more) {
+    const uint64_t need = device_text_bytes(have + more);
+    if (need <= cap) return true;
+    DevMem bigger;
+    G2S_HIP_TRY(bigger.alloc((size_t)need));
+    if (have) G2S_HIP_TRY(hipMemcpy(bigger.p, d_text.p, (size_t)std::min(have, cap), hipMemcpyDeviceToDevice));
+    d_text = std::move(bigger);
+    cap = need;
+    return true;
+  }
+
+  // One BAM file (bam_reads.h): its text behind what the list has given so far, and the carry's text base moved past
+  // it, so that a FASTA/FASTQ file behind it lands in the right place.  The resident stream and the rows are gone when
+  // this returns.  kReadsOk, kReadsGaveUp (*why, info->bam_reason) or kReadsIoError (io_error).
+  ReadsLoadResult run_bam_file(const ReadsInput& in, int* how) {
+    FxCarry c;
+    if (!read_carry(&c)) return kReadsGaveUp;  // (waits for the files in front; between files file_emit is 0)
+    const uint64_t have = c.base;
+    uint64_t kept = 0, skipped = 0, bytes = 0;
+    info->bam_files++;
+    auto gave_up = [&](int reason, int anomaly, const std::string& w) {
+      info->bam_reason = reason;
+      info->bam_anomaly = anomaly;
+      if (why) *why = w;
+      return kReadsGaveUp;
+    };
+    if (host_inflate) {  // (zlib and the host walk; the text is copied up and the list goes on)
+      std::vector<std::string> seqs;
+      uint64_t raw = 0;
+      if (!bam_reads_host(in, &seqs, &skipped, &raw, &io_error)) return kReadsIoError;
+      std::string text;
+      for (const std::string& q : seqs) { text += q; text.push_back('N'); }
+      bytes = text.size();
+      kept = seqs.size();
+      if (!room(have, bytes)) return gave_up(kBamReadsHip, 0, why ? *why : std::string());
+      if (bytes) G2S_HIP_TRY_AS(hipMemcpy(d_text.as<uint8_t>() + have, text.data(), text.size(), hipMemcpyHostToDevice),
+                                (hip_fail(why, what_, e_), info->bam_reason = kBamReadsHip, kReadsGaveUp));
+      info->raw_bytes += raw;
+      bam_by_host++;
+      *how = kInflateZlib;
+    } else {
+      BamReadsDevice B;
+      int reason = kBamReadsHip, anomaly = 0;
+      std::string w;
+      const BamReadsDevice::Result r = B.prepare(in, device, bam_window, resident_cap, &reason, &anomaly, &w);
+      if (r == BamReadsDevice::kIoError) { io_error = w; return kReadsIoError; }
+      if (r != BamReadsDevice::kOk) return gave_up(reason, anomaly, w);
+      bytes = B.text_bytes();
+      if (B.resident_bytes() + device_text_bytes(have + bytes) > mem_limit)
+        return gave_up(kBamReadsOverCap, 0, "a BAM file's stream, rows and text are over the cap");
+      if (!room(have, bytes)) return gave_up(kBamReadsHip, 0, why ? *why : std::string());
+      if (!B.write(d_text.as<uint8_t>(), have, cap, &w)) return gave_up(kBamReadsHip, 0, w);
+      kept = B.kept();
+      skipped = B.skipped();
+      info->pieces += B.windows();
+      info->raw_bytes += B.stream_bytes();
+      *how = kInflateDevice;
+    }
+    c.base = have + bytes;
+    c.records += kept;
+    G2S_HIP_TRY_AS(hipMemcpy(d_carry.p, &c, sizeof c, hipMemcpyHostToDevice), (hip_fail(why, what_, e_), info->bam_reason = kBamReadsHip, kReadsGaveUp));
+    bound = c.base;
+    info->bam_kept += kept;
+    info->bam_skipped += skipped;
+    return kReadsOk;
+  }
+
   // the kernels of one piece: m bytes at d_raw[b], the halo behind them unless `last`
   bool run_piece(int b, uint32_t m, bool last) {
     const uint8_t* raw = d_raw[b].as<uint8_t>();
@@ -556,6 +632,13 @@ struct Loader {
   ReadsLoadResult run_file(const ReadsInput& in, int* how) {
     OpenInput f;
     if (!f.open(in, &io_error)) return kReadsIoError;
+    if (f.gz && is_bam(f.mem, f.n)) {  // (read where it is mapped, under the file's name)
+      ReadsInput mapped;
+      mapped.path = f.name;
+      mapped.mem = f.mem;
+      mapped.mem_n = f.n;
+      return run_bam_file(mapped, how);
+    }
     enum { PLAIN, ZLIB, BGZF } mode = !f.gz ? PLAIN : ZLIB;
     size_t bsize = 0, doff = 0;
     if (f.gz && !host_inflate && bgzf_member(f.mem, f.n, &bsize, &doff)) mode = BGZF;
@@ -661,14 +744,17 @@ struct Loader {
 }  // namespace
 
 ReadsLoadResult load_reads_device(const std::vector<ReadsInput>& inputs, int device, size_t piece, uint64_t first_cap,
-                                  bool host_inflate, DeviceText* out, ReadsLoadInfo* info, std::string* err) {
+                                  bool host_inflate, DeviceText* out, ReadsLoadInfo* info, std::string* err,
+                                  uint64_t resident_cap) {
   *info = ReadsLoadInfo();
   if (!filter_device_usable(device)) { *err = "no usable gfx950 device " + std::to_string(device); return kReadsGaveUp; }
   // the text's bound: an uncompressed file gives no more text than it has bytes; compressed input has no bound
   uint64_t plain = 0;
   bool bounded = true;
   for (const ReadsInput& in : inputs) {
+    // (a BAM file's text is sized from its count when its turn comes: it adds nothing to the first capacity)
     if (in.mem || in.path.empty()) {
+      if (is_bam(in.mem, in.mem_n)) continue;
       plain += in.mem_n;
       bounded = bounded && !is_gzip(in.mem, in.mem_n);
       continue;
@@ -682,7 +768,14 @@ ReadsLoadResult load_reads_device(const std::vector<ReadsInput>& inputs, int dev
     const int fd = ::open(in.path.c_str(), O_RDONLY);
     if (fd < 0) { *err = "cannot read " + in.path; return kReadsIoError; }
     const ssize_t got = pread(fd, magic, 2, 0);
+    bool bam = false;
+    if (got == 2 && is_gzip(magic, 2)) {  // (the head of the file: a BAM file says so in its first members)
+      std::vector<uint8_t> head((size_t)std::min<uint64_t>((uint64_t)st.st_size, (uint64_t)1 << 18));
+      const ssize_t h = pread(fd, head.data(), head.size(), 0);
+      bam = h > 0 && is_bam(head.data(), (size_t)h);
+    }
     ::close(fd);
+    if (bam) continue;
     plain += (uint64_t)st.st_size;
     bounded = bounded && !(got == 2 && is_gzip(magic, 2));
   }
@@ -694,6 +787,8 @@ ReadsLoadResult load_reads_device(const std::vector<ReadsInput>& inputs, int dev
   L.piece = piece ? std::max<size_t>(piece, 16)
                   : (size_t)std::min<uint64_t>((uint64_t)32 << 20, std::max<uint64_t>((uint64_t)1 << 20, (expect / 4 + 65535) & ~(uint64_t)65535));
   L.host_inflate = host_inflate;
+  L.bam_window = piece;
+  L.resident_cap = resident_cap;
   L.info = info;
   L.why = err;
   // (compressed reads: four times their bytes to begin with, and from there by doubling)
@@ -701,6 +796,7 @@ ReadsLoadResult load_reads_device(const std::vector<ReadsInput>& inputs, int dev
   size_t free_b = 0, total_b = 0;
   if (hipSetDevice(device) != hipSuccess || hipMemGetInfo(&free_b, &total_b) != hipSuccess) { *err = "the device cannot be used"; return kReadsGaveUp; }
   if ((double)cap0 > 0.5 * (double)free_b) { *err = "the text does not fit on the device"; return kReadsGaveUp; }
+  L.mem_limit = std::min<uint64_t>(free_b / 2, resident_cap ? resident_cap : UINT64_MAX);
   const bool debug = getenv("G2S_DEBUG") != nullptr;
   const auto t0 = std::chrono::steady_clock::now();
   if (!L.init(cap0)) return kReadsGaveUp;
@@ -727,6 +823,8 @@ ReadsLoadResult load_reads_device(const std::vector<ReadsInput>& inputs, int dev
   info->positions = T;
   info->records = c.records;
   info->on_device = 1;
+  info->bam_kernels = info->bam_files && !L.bam_by_host ? 1 : 0;
+  info->bam_reason = info->bam_kernels ? kBamReadsKernels : kBamReadsNotAsked;
   out->d_text = (uint8_t*)L.d_text.release();
   out->T = T;
   out->capacity = L.cap;

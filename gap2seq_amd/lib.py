@@ -242,6 +242,8 @@ _SIGS = {
     "g2s_test_last_reads_load": (C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
                                            C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int),
                                            C.POINTER(C.c_int), C.c_uint64, C.POINTER(C.c_uint64)]),
+    "g2s_test_last_reads_bam": (C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                          C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "g2s_test_bgzf_inflate": (C.c_int, [C.c_char_p, C.c_size_t, C.c_int, C.POINTER(C.c_uint8), C.c_size_t,
                                         C.POINTER(C.c_size_t), C.POINTER(C.c_int64)]),
     "g2s_test_last_filter_inflate": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
@@ -599,6 +601,9 @@ class Graph:
 
     @classmethod
     def from_files(cls, reads_csv, k, solid, nthreads=0):
+        """The graph of a comma-separated list of read files: FASTA or FASTQ (plain, gzip or BGZF) and BAM, in any
+        mixture, each told by its bytes, never by its name.  A BAM file gives every record that is neither secondary
+        nor supplementary, mapped or not, as the read was sequenced (include/g2s.h: g2s_graph_build_files)."""
         h = _VP()
         _check(load_library().g2s_graph_build_files(reads_csv.encode(), k, solid, nthreads, C.byref(h)))
         return cls(h)
@@ -1190,8 +1195,9 @@ def test_filter_join(ref_id, pos, end, flag, h_own, h_mate, max_span, bits, wind
 
 def reads_text(data, device=-1, piece_bytes=0):
     """TEST HOOK binding (g2s_test_reads_text): the build's text (every sequence followed by N) of one read file in
-    memory, plain, gzip or BGZF.  device -1: the host loader (zlib, parse_fastx); -2: the kernels' state machine walked
-    on the host; >= 0: the kernels on that device in pieces of `piece_bytes` raw bytes.  Raises G2SError."""
+    memory, plain, gzip or BGZF, or of one BAM file.  device -1: the host loader (zlib, parse_fastx; the reader's walk
+    for BAM); -2: the kernels' state machine walked on the host (BAM: as -1); >= 0: the kernels on that device in pieces
+    (BAM: windows) of `piece_bytes` raw bytes.  Raises G2SError."""
     lib = load_library()
     data = bytes(data)
     cap = max(1 << 12, 2 * len(data))
@@ -1216,6 +1222,21 @@ def last_reads_load():
                                                    how, f.value, C.byref(gr)))
     return dict(files=f.value, raw_bytes=rb.value, positions=ps.value, records=rc.value, pieces=pc.value,
                 on_device=on.value, inflate=[("none", "zlib", "device", "mixed")[x] for x in how[:f.value]], grows=gr.value)
+
+
+BAM_READS_REASONS = ("kernels", "not asked", "rows anomaly", "over the cap", "hip")
+
+
+def last_reads_bam():
+    """TEST HOOK binding (g2s_test_last_reads_bam): dict(files, kept, skipped, kernels, reason, anomaly) of the BAM
+    files in the process's last Graph.from_files or reads_text; reason is one of BAM_READS_REASONS, anomaly the
+    RowsAnomaly (csrc/bam_rows.h) behind "rows anomaly" """
+    f, kept, skipped = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    kernels, reason, anomaly = C.c_int(), C.c_int(), C.c_int()
+    _check(load_library().g2s_test_last_reads_bam(C.byref(f), C.byref(kept), C.byref(skipped), C.byref(kernels),
+                                                  C.byref(reason), C.byref(anomaly)))
+    return dict(files=f.value, kept=kept.value, skipped=skipped.value, kernels=kernels.value,
+                reason=BAM_READS_REASONS[reason.value], anomaly=anomaly.value)
 
 
 def bgzf_inflate(data, device=-1):

@@ -79,11 +79,20 @@ const char* g2s_last_error(void);
  *  (G2S_DEBUG=1 says which).  The graph itself holds fewer than 2^30 k-mers.
  *  g2s_graph_build_files: reads_csv is a comma-separated list of FASTA/FASTQ
  *  files; gzip-compressed ones (plain gzip or BGZF, recognised by their magic
- *  bytes, not their names) are read transparently.  With a usable device the
+ *  bytes, not their names) are read transparently.  BAM files may stand in
+ *  the list too, in any order: a file is BAM when it is gzip, its first
+ *  member is a BGZF member and its inflated stream begins with "BAM\1".
+ *  Every alignment record that is neither secondary (0x100) nor
+ *  supplementary (0x800) gives one sequence, mapped or not, in file order —
+ *  the reads `samtools fastq` would emit: the 4-bit codes 1, 2, 4, 8 are
+ *  A, C, G, T, every other code is N, and a reverse-strand record (0x10) is
+ *  reverse-complemented back to the read as sequenced; a record without
+ *  bases is an empty sequence.  With a usable device the
  *  files' bytes are parsed there and never form sequences on the host
  *  (G2S_HOST_READS=1: the host loader).  G2S_ERR_IO with the file's name in
  *  g2s_last_error() for a file that cannot be read or whose gzip stream is
- *  truncated or corrupt.
+ *  truncated or corrupt, and for a BAM file with a member that does not
+ *  inflate, a cut record or a header that does not parse.
  * ------------------------------------------------------------------------ */
 int g2s_graph_build_files(const char* reads_csv, int k, int solid, int nthreads, g2s_graph** out);
 int g2s_graph_build_seqs(const char* const* seqs, const uint64_t* lens, int nseqs, int k, int solid,

@@ -130,7 +130,10 @@ int g2s_test_last_solid_count(uint64_t* positions, uint32_t* passes, uint32_t* r
  * on the host.  device >= 0: the kernels k_fastx_* of csrc/reads_text.hip on that device, in pieces of piece_bytes raw
  * bytes (0: the product's choice, 32 MiB at most), BGZF members inflated on the device unless G2S_HOST_INFLATE=1 —
  * G2S_ERR_NO_DEVICE when it is no usable gfx950, G2S_ERR_HIP when anything on the device refuses; never the host in
- * their place.  G2S_ERR_IO with g2s_last_error()'s text for a truncated or corrupt gzip stream.  *out_n receives the
+ * their place.  The bytes of a BAM file give the BAM text (include/g2s.h): device == -1 and -2 by the reader's walk (there
+ * is no line machine for BAM), device >= 0 by the kernels k_bamreads_* of csrc/bam_reads.hip, piece_bytes being the
+ * window; with G2S_HOST_INFLATE=1 by the reader's walk, copied up.
+ * G2S_ERR_IO with g2s_last_error()'s text for a truncated or corrupt gzip stream.  *out_n receives the
  * text's size; the first min(cap, size) bytes are written, so a caller whose capacity was too small calls again.
  * g2s_test_last_reads_load then speaks of this call. */
 int g2s_test_reads_text(const void* bytes, size_t n, int device, size_t piece_bytes, uint8_t* out, size_t cap, size_t* out_n);
@@ -143,6 +146,15 @@ int g2s_test_reads_text(const void* bytes, size_t n, int device, size_t piece_by
  * grows: how often the text buffer was enlarged.  Any pointer may be NULL. */
 int g2s_test_last_reads_load(uint64_t* files, uint64_t* raw_bytes, uint64_t* positions, uint64_t* records, uint64_t* pieces,
                              int* on_device, int* inflate, uint64_t inflate_cap, uint64_t* grows);
+
+/* TEST HOOK: the BAM files (csrc/bam_reads.h) among the read files of the process's last g2s_graph_build_files (or
+ * g2s_test_reads_text).  bam_files; kept / skipped: their records that gave a sequence / that were secondary or
+ * supplementary; by_kernels: 1 when k_bamreads_* wrote the text of every one of them; reason, when they did not:
+ * 0 the kernels wrote it, 1 not asked (G2S_HOST_BUILD, G2S_HOST_READS=1, G2S_HOST_INFLATE=1, no usable device, or the
+ * host loader took over for another reason), 2 the row kernels gave a file back — *anomaly is then the RowsAnomaly of
+ * csrc/bam_rows.h —, 3 stream, rows and text over half the free device memory or G2S_BUILD_RESIDENT_CAP, 4 an
+ * allocation or a HIP call failed.  Any pointer may be NULL. */
+int g2s_test_last_reads_bam(uint64_t* bam_files, uint64_t* kept, uint64_t* skipped, int* by_kernels, int* reason, int* anomaly);
 
 /* TEST HOOK: the planner of the key-range passes (pass_plan.hpp) on a histogram of the caller's: nbins consecutive bins
  * of the key space, cut greedily and in order into passes of at most cap keys — a pass is closed in front of the first

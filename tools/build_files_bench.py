@@ -6,9 +6,14 @@ another build of the library (--parent path/to/libg2s_hip.so, the commit before)
 own, so that its peak resident set is its own: the wall time is that of the one call, up to its return, behind a small
 warm-up build that loads the runtime and the kernels; the resident set is the peak over the process less what the warm-up
 left.  The ways alternate, --reps builds each; the median and the spread of each are printed as one JSON line.
+--bam: the same reads as unaligned BAM records (a writer of this tool's own; --read-length L cuts bench.py's genome-long sequences into short reads of the same k-mers,
+in every form) through the device route
+(gap2seq_amd/csrc/bam_reads.hip) and through the host loader, beside --parent's library on the BGZF FASTQ file — what a
+BAM file had to be converted to before BAM was read.
 
   python tools/build_files_bench.py --config C4 --reps 5 --threads 16 [--parent PATH/TO/libg2s_hip.so]
   python tools/build_files_bench.py --config C4 --once fastq     # one device-loader build in this process (kernel trace)
+  python tools/build_files_bench.py --config C4 --bam --reps 5 [--parent PATH/TO/libg2s_hip.so]   (and --once bam)
 
 Needs a GPU."""
 import argparse
@@ -18,6 +23,7 @@ import json
 import os
 import resource
 import statistics
+import struct
 import subprocess
 import sys
 import tempfile
@@ -27,7 +33,7 @@ import zlib
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 SWITCHES = ("G2S_HOST_BUILD", "G2S_HOST_READS", "G2S_HOST_INFLATE", "G2S_BUILD_PASS_KEYS", "G2S_BUILD_PIECE_BYTES",
-            "G2S_BUILD_TEXT_FIRST_BYTES")
+            "G2S_BUILD_TEXT_FIRST_BYTES", "G2S_BUILD_RESIDENT_CAP")
 
 
 def bgzf(raw, out):
@@ -40,12 +46,43 @@ def bgzf(raw, out):
     out.write(bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000"))
 
 
-def write_files(config, d):
+_HEX = bytes.maketrans(b"ACGTacgt", b"12481248")
+
+
+def bam(lines, out):
+    """the FASTA records of `lines` (header, sequence, header, ...) as unaligned BAM records: no reference, flag 4"""
+    raw = [b"BAM\x01" + struct.pack("<i", 0) + struct.pack("<i", 0)]
+    for i in range(0, len(lines) - 1, 2):
+        name, seq = lines[i][1:].split()[0] + b"\0", lines[i + 1]
+        # (two codes a byte, the first in the high nibble: the codes written as hexadecimal digits; anything else is N)
+        digits = bytes(c if c in b"1248" else 102 for c in seq.translate(_HEX)) if seq.strip(b"ACGTacgt") else seq.translate(_HEX)
+        packed = bytes.fromhex((digits + b"0" * (len(seq) & 1)).decode("ascii"))
+        body = struct.pack("<iiBBHHHiiii", -1, -1, len(name), 0, 4680, 0, 4, len(seq), -1, -1, 0) + name + packed + b"\xff" * len(seq)
+        raw.append(struct.pack("<i", len(body)) + body)
+    bgzf(b"".join(raw), out)
+
+
+def cut_reads(lines, length, k):
+    """every sequence of `lines` (header, sequence, ...) as reads of `length` bases that overlap by k - 1: every k-mer of
+    the sequence lies in one of them, so at solid 1 the graph is the uncut sequences'"""
+    out = []
+    for i in range(0, len(lines) - 1, 2):
+        name, seq = lines[i].split()[0], lines[i + 1]
+        for n, at in enumerate(range(0, max(len(seq) - k + 1, 1), length - k + 1)):
+            out.append(name + b".%d" % n)
+            out.append(seq[at:at + length])
+    return out + [b""]
+
+
+def write_files(config, d, with_bam=False, read_length=0):
     import bench
     from gap2seq_amd import lib as P
     genome_bp, k = bench.CONFIGS[config][:2]
     fa = P.G2S.synth_genome(genome_bp, 3, bench.GENOME_SEED).encode("ascii")
     lines = fa.split(b"\n")
+    if read_length:  # (bench.py's read sets are a few sequences of the genome's length: short reads of the same k-mers)
+        lines = cut_reads(lines, max(read_length, k), k)
+        fa = b"\n".join(lines)
     fq = b"".join(b"@" + lines[i][1:] + b"\n" + lines[i + 1] + b"\n+\n" + b"I" * len(lines[i + 1]) + b"\n"
                   for i in range(0, len(lines) - 1, 2))
     paths = {f: os.path.join(d, "reads." + f) for f in ("fasta", "fastq", "fastq.gz", "bgzf.fastq.gz")}
@@ -55,6 +92,10 @@ def write_files(config, d):
         f.write(fq)
     with open(paths["bgzf.fastq.gz"], "wb") as f:
         bgzf(fq, f)
+    if with_bam:
+        paths["bam"] = os.path.join(d, "reads.bam")
+        with open(paths["bam"], "wb") as f:
+            bam(lines, f)
     return k, paths
 
 
@@ -87,6 +128,11 @@ def child(library, path, k, threads):
         raw, pos, on = C.c_uint64(), C.c_uint64(), C.c_int()
         lib.g2s_test_last_reads_load(None, C.byref(raw), C.byref(pos), None, None, C.byref(on), None, 0, None)
         out.update(raw_bytes=raw.value, positions=pos.value, text_on_device=on.value)
+        lib.g2s_test_last_reads_bam.argtypes = [C.POINTER(C.c_uint64)] * 3 + [C.POINTER(C.c_int)] * 3
+        files, kernels, reason, anomaly = C.c_uint64(), C.c_int(), C.c_int(), C.c_int()
+        lib.g2s_test_last_reads_bam(C.byref(files), None, None, C.byref(kernels), C.byref(reason), C.byref(anomaly))
+        if files.value:  # (a BAM file: whether the kernels wrote its text, and when not, why — include/g2s_test.h)
+            out.update(bam_by_kernels=kernels.value, bam_reason=reason.value, bam_anomaly=anomaly.value)
     except AttributeError:  # (the parent's library)
         pass
     lib.g2s_graph_free(h)
@@ -99,6 +145,8 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--parent", default="", help="the library of the commit before, for the uncompressed files")
+    ap.add_argument("--bam", action="store_true", help="the BAM form: device route, host loader, and --parent on BGZF FASTQ")
+    ap.add_argument("--read-length", type=int, default=0, help="cut the sequences into reads of this length that overlap by k - 1")
     ap.add_argument("--once", default="", help="one device-loader build of this form in this process, nothing else")
     ap.add_argument("--child", nargs=4, metavar=("LIBRARY", "PATH", "K", "THREADS"), help=argparse.SUPPRESS)
     args = ap.parse_args()
@@ -107,7 +155,7 @@ def main():
         return 0
     here = os.path.join(ROOT, "gap2seq_amd", "libg2s_hip.so")
     with tempfile.TemporaryDirectory() as d:
-        k, paths = write_files(args.config, d)
+        k, paths = write_files(args.config, d, args.bam or args.once == "bam", args.read_length)
         sizes = {f: os.path.getsize(p) for f, p in paths.items()}
         if args.once:
             for name in SWITCHES:
@@ -115,12 +163,17 @@ def main():
             child(here, paths[args.once], k, args.threads)
             return 0
         ways = []  # (name, form, library, switches)
-        for f in paths:
+        if args.bam:
+            ways = [("device bam", "bam", here, {}), ("host-reads bam", "bam", here, {"G2S_HOST_READS": "1"})]
+            if args.parent:
+                ways.append(("parent bgzf.fastq.gz", "bgzf.fastq.gz", args.parent, {}))
+        for f in ([] if args.bam else paths):
             ways.append(("device " + f, f, here, {}))
             ways.append(("host-reads " + f, f, here, {"G2S_HOST_READS": "1"}))
             if args.parent and not f.endswith(".gz"):
                 ways.append(("parent " + f, f, args.parent, {}))
-        ways.append(("device+zlib bgzf.fastq.gz", "bgzf.fastq.gz", here, {"G2S_HOST_INFLATE": "1"}))
+        if not args.bam:
+            ways.append(("device+zlib bgzf.fastq.gz", "bgzf.fastq.gz", here, {"G2S_HOST_INFLATE": "1"}))
         runs = {w[0]: [] for w in ways}
         for rep in range(args.reps):
             for name, form, library, switches in ways:
@@ -134,12 +187,13 @@ def main():
                 runs[name].append(r)
                 print("rep %d %-28s %.3f s, %7.0f MiB resident, %d k-mers %s" % (
                     rep, name, r["wall_s"], r["rss_mb"], r["kmers"], "(text on the device)" if r.get("text_on_device") else ""), flush=True)
-    out = {"config": args.config, "k": k, "file_bytes": sizes, "ways": {}}
+    out = {"config": args.config, "k": k, "read_length": args.read_length, "file_bytes": sizes, "ways": {}}
     for name, rs in runs.items():
         ts = sorted(r["wall_s"] for r in rs)
         out["ways"][name] = dict(median_s=statistics.median(ts), min_s=ts[0], max_s=ts[-1], reps=len(ts), kmers=rs[0]["kmers"],
                                  rss_mb=statistics.median(r["rss_mb"] for r in rs), text_on_device=rs[0].get("text_on_device"),
-                                 raw_bytes=rs[0].get("raw_bytes"), positions=rs[0].get("positions"))
+                                 raw_bytes=rs[0].get("raw_bytes"), positions=rs[0].get("positions"),
+                                 bam_by_kernels=rs[0].get("bam_by_kernels"), bam_reason=rs[0].get("bam_reason"))
     out["same_kmers"] = len({v["kmers"] for v in out["ways"].values()}) == 1
     print(json.dumps(out))
     return 0 if out["same_kmers"] else 1
