@@ -884,7 +884,7 @@ static bool finish_gpu_e(Graph& g, const std::vector<KT>& kmers, int device,
   const size_t sbytes = (size_t)n2 * 16;
   if constexpr (EVEN) G2S_HIP_TRY(d_pid.alloc(sbytes));
   const size_t words = (size_t)((n + 63) / 64 + 1);
-  G2S_HIP_TRY(d_sid.alloc(sbytes + 1024));  // the LDS tier may read past the end: INVALID padding
+  G2S_HIP_TRY(d_sid.alloc(sbytes + 1024));  // INVALID padding behind the table, as the host build's upload has it
   G2S_HIP_TRY(hipMemset(d_sid.p, 0xFF, sbytes + 1024));
   G2S_HIP_TRY(d_last.alloc((size_t)n2));
   G2S_HIP_TRY(d_i2r.alloc((size_t)n * 4));

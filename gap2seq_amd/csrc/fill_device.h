@@ -15,26 +15,18 @@
 #define G2S_DEV_Q7_B 0x2u        /* both strands of a k-mer at one DP level        */
 #define G2S_DEV_OVERFLOW_A 0x4u  /* right-set tables too small for this gap        */
 #define G2S_DEV_OVERFLOW_B 0x8u  /* state tables too small for this gap            */
-#define G2S_DEV_Q7_D 0x10u       /* both strands of a k-mer at one level of the backward sweep (HBM tier; the LDS
-                                    tier's closure is a subset of the DP states, covered by Q7_B) */
-/* why a gap left the LDS tier (diagnostics, set together with OVERFLOW_B) */
-#define G2S_DEV_WHY_FRONTIER 0x100u /* a DP level wider than the LDS frontier buffers */
-#define G2S_DEV_WHY_HITS 0x200u     /* more target hits than the LDS list holds       */
-#define G2S_DEV_WHY_LOG 0x400u      /* state log full                                 */
-#define G2S_DEV_WHY_RS 0x800u       /* (with OVERFLOW_A) the right-set table was full */
-/* diagnostics of the LDS tier's pools (no effect on results) */
-#define G2S_DEV_LOG_POOL 0x1000u    /* the state log moved to a chunk of the log pool        */
-#define G2S_DEV_RS_POOL 0x2000u     /* the right set moved from LDS to a chunk of the spill pool */
+#define G2S_DEV_Q7_D 0x10u       /* both strands of a k-mer at one level of the backward sweep (HBM tier) */
+/* why a gap left a segment tier (diagnostics, set together with an OVERFLOW bit) */
+#define G2S_DEV_WHY_FRONTIER 0x100u /* more pending events than the tier's table holds */
+#define G2S_DEV_WHY_LOG 0x400u      /* more segments than the tier holds               */
+#define G2S_DEV_WHY_RS 0x800u       /* (with OVERFLOW_A) the right-set table was full  */
 /* the closure of this gap was emitted as segments (SegRec, segment tier), not as per-state records */
 #define G2S_DEV_COMPACT 0x4000u
 /* (with an OVERFLOW bit) a probe loop of the segment tier's large variant ran past its bound: a defect, never
-   expected; the gap runs again in the LDS tier instead of holding the GPU */
+   expected; the gap runs again in the HBM tier instead of holding the GPU */
 #define G2S_DEV_WATCHDOG 0x8000u
 /* the gap ran in the large variant of the segment tier (fill_segw.hip) */
 #define G2S_DEV_BIG 0x10000u
-/* LDS tier, lvl[]: bit 31 of the END offset of level L = L was produced by a bulk step
- * (same width as level L-1, state r has the single parent r of level L-1) */
-#define G2S_LVL_UNIFORM 0x80000000u
 
 struct GapDev {
   int32_t g;           // gap_len
@@ -49,12 +41,12 @@ struct GapDev {
   uint32_t rlog_cap;   // right BFS visit log capacity
   uint32_t st_mask;    // state hash: capacity-1
   uint32_t slog_cap;   // state log capacity (<= (st_mask+1)/2)
-  uint32_t pad0;       // LDS tier: capacity of the gap's extra-parent list
+  uint32_t pad0;
   uint64_t rs_off;     // element offsets into the session arrays
   uint64_t rlog_off;
-  uint64_t st_off;     // LDS tier: offset of the gap's extra-parent list
-  uint64_t slog_off;   // also: offset of the gap's state log / closure scratch in the LDS tier
-  uint64_t lvl_off;    // LDS tier: D+2 level offsets into the state log
+  uint64_t st_off;
+  uint64_t slog_off;   // also: offset of the gap's closure scratch
+  uint64_t pad1;       // (96 bytes)
 };
 
 /* Resident mode, segment tier: the 32 bytes of a gap that are not the same for the whole list and cannot be derived —
@@ -85,7 +77,7 @@ struct GapSrc {
     d.prune_from = d.g / 2 + e / 2 + d.lmf;        // :1050
     d.all_paths = all_paths;
     d.flank_off = l.flank_off; d.rs_mask = l.text_off; d.rlog_cap = l.has_skip; d.st_mask = 0u; d.slog_cap = 0u; d.pad0 = 0u;
-    d.rs_off = 0ull; d.rlog_off = l.arena_off; d.st_off = 0ull; d.slog_off = 0ull; d.lvl_off = 0ull;
+    d.rs_off = 0ull; d.rlog_off = l.arena_off; d.st_off = 0ull; d.slog_off = 0ull; d.pad1 = 0ull;
     return d;
   }
 };
@@ -112,7 +104,7 @@ struct SubState {
   int32_t pred[4];
 };
 
-/* The closure as the host works on it and as the LDS tier emits it: 16 bytes per state.
+/* The closure as the host works on it: 16 bytes per state.
  * Almost every state has one parent; the others set G2S_SUB_MORE in `pred` and list their
  * further parents in the gap's side list xp[] = (state << 32 | parent), sorted by state.
  * Parents are a set here; where their GATB order matters (the traceback, :1476-1513) it
@@ -158,11 +150,12 @@ struct GapOut {
   uint32_t n_sub;      // states in the backward closure (phase D input)
   uint64_t sub_off;    // offset of this gap's closure in the packed output (SubRec / SubState units)
   uint32_t x_sub;      // expansions done by the backward sweep
-  uint32_t n_xl;       // LDS tier: entries in the gap's extra-parent list; segment tier: SegRec records emitted
-  uint32_t top_level;  // LDS tier: last DP level that holds a state
-  uint32_t n_xp;       // LDS tier: entries of the closure's side list (parents beyond the first)
-  // LDS tier statistics: per-level iterations / bulk iterations of phases A, B, D1 and
-  // shader cycles (in units of 256) spent in A, B+C, D1
+  uint32_t n_xl;       // segment tier: SegRec records emitted
+  uint32_t top_level;  // segment tier, a gap its wave traced or guessed (G2S_DEVA_TRACED, G2S_DEVA_SPEC below)
+  uint32_t n_xp;       // segment tier: entries of the expanded closure's side list (parents beyond the first)
+  // segment tier statistics: [0] rounds and [1] entries of phase A, [2] rounds of phase B, [3] segments, and shader
+  // cycles (in units of 256) spent in [4] A, [5] B+C, [7] D1 + emit; [6] rounds of D1, or with [7] the hash of the
+  // chain a guessed traceback took
   uint32_t stat[8];
   // segment tier: phase D2 and the stop-depth analysis done on the device (valid with G2S_DEVA_ANALYSED)
   int32_t fixed_draws[2];  // rand() draws a traceback from start j consumes, or -1 when that depends on the draws

@@ -69,8 +69,8 @@ extern uint32_t d2_ticks_offset;
 
 size_t fill_seg_lds_bytes();
 uint32_t fill_seg_dbg_words();  // words per gap of the optional diagnostics buffer
-// phases A-D1 of every listed gap in one launch; results land in pinned host memory exactly as
-// the LDS tier leaves them (GapOut per gap, closures packed by an atomic cursor, completion list)
+// phases A-D1 of every listed gap in one launch; results land in pinned host memory
+// (GapOut per gap, closures packed by an atomic cursor, completion list)
 hipError_t launch_fill_seg(hipStream_t st, uint32_t ngaps, const SegGraph& graph /* seg_tables.hip */,
                            const GapDev* gaps,
                            const uint32_t* gap_ids, const uint32_t* flank_nodes, SubRec* sub_out /* pinned host */,

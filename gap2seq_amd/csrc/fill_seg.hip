@@ -12,7 +12,7 @@
 //
 // Why segments: one wave per SIMD is bound by instruction issue and by dependent LDS / memory round trips
 // (rocprofv3, profiles/r02_pmc_sq_*.json: a third of the wave cycles issue instructions, two thirds wait),
-// so what a gap costs is the number of dependent steps it takes.  The LDS tier (fill_lds.hip) takes one
+// so what a gap costs is the number of dependent steps it takes.  A level-by-level search (round 1's tier in LDS, retired since) takes one
 // step per DP level that is not unitig-internal for EVERY border state (~190 + ~190 steps for the slowest
 // gaps of BASELINE config 2).  Here the unit of work is the segment: node ids are numbered along unitigs
 // (dbg.hpp: inside a unitig the only successor of an even id v is v+2, of an odd id v-2, and v is that node's
@@ -43,7 +43,7 @@
 //   output   the closure as 32-byte segment records (SegRec), children before parents, parents in GATB's
 //            predecessor order, written straight into pinned host memory; the host walks them (post.cpp).
 // A gap that outgrows a capacity (segments, pending events, right-set entries, host buffer) is flagged and
-// runs again in the next kernel of the chain (g2s_fill_segw, then the LDS tier).  Integer work only: no MFMA.
+// runs again in the next kernel of the chain (g2s_fill_segw, then the HBM tier).  Integer work only: no MFMA.
 #include "sync_debug.h"
 #include <hip/hip_runtime.h>
 #include <mutex>
@@ -300,7 +300,7 @@ __device__ __forceinline__ void seg_fill_one(uint32_t* lds, const SegArgs& A, co
   uint32_t flags = 0;
   bool overflow = D >= 32767 || rmf + 1 > 32 || lmf + 1 > 32;  // (16-bit depths and lengths, 32 seeds / targets)
 
-  // Results go to pinned host memory as each gap finishes (as in the LDS tier).  One wave publishes what it stored
+  // Results go to pinned host memory as each gap finishes.  One wave publishes what it stored
   // itself: the record it wrote to device memory went through the L1 into this XCD's L2, where the copy below reads
   // it back (agent-scope loads bypass the L1) once "s_waitcnt vmcnt(0)" says the stores were acknowledged — no
   // fence is needed for that.  A system-scope release (a write-back of this XCD's L2) then puts closure segments
@@ -681,8 +681,8 @@ __device__ __forceinline__ void seg_fill_one(uint32_t* lds, const SegArgs& A, co
     }
     // The entries as k-mer index intervals, sorted and merged in LDS (holes between any two): phase B's pruning test
     // and the lengths of its runs then take ONE look at the list instead of following chains of overlapping entries,
-    // and the list is shorter (fewer 64-entry sets to ballot over per child).  Q7 in the right set, conservatively as
-    // in the LDS tier — both strands of some k-mer are in it = an entry of each orientation with overlapping
+    // and the list is shorter (fewer 64-entry sets to ballot over per child).  Q7 in the right set, conservatively
+    // — both strands of some k-mer are in it = an entry of each orientation with overlapping
     // intervals — falls out of the merge.
     if (!overflow && nA > 0u) {
       const uint32_t* cnode = aq0;
@@ -1366,7 +1366,7 @@ __device__ __forceinline__ void seg_fill_one(uint32_t* lds, const SegArgs& A, co
   unsigned long long hbase = 0;
   if (lane == 0) hbase = atomicAdd(out_counter, (unsigned long long)nres);
   hbase = __shfl(hbase, 0);
-  if (hbase + nres > out_cap) {  // the host buffer is full: the gap runs again in the LDS tier
+  if (hbase + nres > out_cap) {  // the host buffer is full: the gap runs again in the next tier
     if (lane == 0) go->flags = flags | G2S_DEV_OVERFLOW_B | G2S_DEV_WHY_LOG;
     q7_collect();
     publish();

@@ -698,7 +698,7 @@ __device__ __forceinline__ void segw_fill_one(uint32_t* lds, const SegArgs& A, c
         const uint32_t esid = rl(rsv, 0) + ((uint32_t)lane >> 2);
         const uint32_t back = rl(rsv, 1) + ((uint32_t)lane >> 2);
         const uint32_t at = rl(rsv, 2) + (uint32_t)__popcll(cmk & below(lane));
-        if (ballot_and(mine, esid >= CAP)) {  // (the gap then runs in the LDS tier)
+        if (ballot_and(mine, esid >= CAP)) {  // (the gap then runs in the HBM tier)
           if (mine && esid >= CAP) { cact = false; lflags |= G2S_DEV_OVERFLOW_B | G2S_DEV_WHY_LOG; sh[SH_OVF] = 1u; }
         }
         if (lead) {
@@ -813,7 +813,7 @@ __device__ __forceinline__ void segw_fill_one(uint32_t* lds, const SegArgs& A, c
       }
       __syncthreads();
       const uint32_t nc = sh[SH_NC];
-      if (nc > SEGW_CL_CAP) {  // (never seen: the gap runs in the LDS tier)
+      if (nc > SEGW_CL_CAP) {  // (never seen: the gap runs in the HBM tier)
         flags |= G2S_DEV_OVERFLOW_B | G2S_DEV_WHY_LOG;
         overflow = true;
       }
@@ -1204,7 +1204,7 @@ __device__ __forceinline__ void segw_fill_one(uint32_t* lds, const SegArgs& A, c
   const uint32_t eslot = sh[SH_ESLOT], eoff = sh[SH_EOFF];
   SegRec* edst = (eslot != 0xFFFFFFFFu && eoff != 0xFFFFFFFFu) ? A.early_segs + eoff : nullptr;
   const unsigned long long hbase = (unsigned long long)sh[SH_HBASE_LO] | ((unsigned long long)sh[SH_HBASE_HI] << 32);
-  if (hbase + nres > out_cap) {  // the output buffer is full: the gap runs again in the LDS tier
+  if (hbase + nres > out_cap) {  // the output buffer is full: the gap runs again in the HBM tier
     if (tid == 0) go->flags = flags | G2S_DEV_OVERFLOW_B | G2S_DEV_WHY_LOG;
     publish();
     return;

@@ -78,17 +78,13 @@ static inline double ms_since(TimePoint t0) { return ms_between(t0, std::chrono:
 // The sum of two g2s_timing: every figure that counts gaps, launches, lists, bytes or the milliseconds of kernels and
 // host phases.  Not ms_total (a wall time: the caller measures its own), team_sessions and team_d3_sharded (what a
 // call was, not how much), the per-session team_ms_* (a team's own: the slices of g2s_team_fill add them), host_us
-// (one list on one session) and reserved1.
+// (one list on one session), reserved1 and the retired LDS tier's fields (always zero).
 static void timing_add(g2s_timing& into, const g2s_timing& part) {
   into.ms_right_bfs += part.ms_right_bfs; into.ms_left_dp += part.ms_left_dp; into.ms_extract += part.ms_extract;
   into.ms_d2h += part.ms_d2h; into.ms_host_post += part.ms_host_post;
   into.xA += part.xA; into.sA += part.sA; into.xB += part.xB; into.sB += part.sB; into.xD += part.xD; into.sD += part.sD;
   into.flank_bytes += part.flank_bytes; into.fill_bytes += part.fill_bytes;
   into.launches_left_dp += part.launches_left_dp; into.retried_gaps += part.retried_gaps;
-  into.ms_fill_lds += part.ms_fill_lds; into.ms_extract_lds += part.ms_extract_lds;
-  into.x_fill_lds += part.x_fill_lds; into.s_fill_lds += part.s_fill_lds;
-  into.lds_tier_gaps += part.lds_tier_gaps; into.lds_launches += part.lds_launches;
-  into.log_pool_gaps += part.log_pool_gaps; into.rs_pool_gaps += part.rs_pool_gaps;
   into.ms_prepare += part.ms_prepare;
   into.ms_fill_seg += part.ms_fill_seg; into.seg_tier_gaps += part.seg_tier_gaps; into.seg_launches += part.seg_launches;
   into.seg_segments += part.seg_segments; into.seg_timed_launches += part.seg_timed_launches; into.seg2_launches += part.seg2_launches;
@@ -583,7 +579,7 @@ extern "C" int g2s_graph_upload(g2s_graph* gh, int device) {
   HIP_TRY(hipSetDevice(device));
   DeviceGraph dg;
   const size_t bytes = g.succ.size() * sizeof(uint32_t);
-  // the LDS tier reads whole 512 B blocks: pad the table with INVALID entries
+  // 1 KB of INVALID entries behind the table: a read a little past its last row finds no successor
   HIP_TRY(hipMalloc((void**)&dg.succ, bytes + 1024));
   HIP_TRY(hipMemset(dg.succ, 0xFF, bytes + 1024));
   HIP_TRY(hipMemcpy(dg.succ, g.succ.data(), bytes, hipMemcpyHostToDevice));
@@ -641,7 +637,7 @@ struct PinBuf {  // grow-only pinned host allocation
     if (bytes <= cap) return hipSuccess;
     if (p) { (void)hipHostFree(p); p = nullptr; cap = 0; }
     size_t want = bytes + bytes / 4 + 256;
-    // mapped + coherent: the LDS tier's kernels write their results here directly
+    // mapped + coherent: the segment tiers' kernels write their results here directly
     hipError_t e = hipHostMalloc(&p, want, hipHostMallocMapped | hipHostMallocCoherent);
     if (e == hipSuccess) cap = want;
     return e;
@@ -675,7 +671,7 @@ static void progress_note(const char* fmt, ...) {
 namespace {
 struct TierData {  // what came back from one launch group (pinned buffers live in the session)
   PinBuf outs, subs;
-  PinBuf done;  // LDS tier: gap indices in completion order, written by the kernel as gaps finish
+  PinBuf done;  // segment tiers: gap indices in completion order, written by the kernel as gaps finish
   std::vector<SubRec> conv;        // HBM tier: closures converted to the host's 16-byte records
   std::vector<uint64_t> conv_xp;
   std::vector<uint32_t> gap_ids;
@@ -923,7 +919,6 @@ struct g2s_session {
   BgWorker bg;
   WorkerPool* pool = nullptr;
   WorkerPool* team_pool = nullptr;  // (a lead session's) one thread per other session of a team
-  bool no_lds_tier = false;  // G2S_NO_LDS_TIER=1: force the general HBM tier (tests, A/B timing)
   size_t mem_budget = 0;  // bytes of HBM this session may use for work areas
   DevBuf d_gaps, d_ids, d_flank, d_outs, d_rs, d_rlog, d_keys, d_cnt, d_mark, d_slog, d_subscr, d_subout, d_counter;
   DevBuf d_xcd;  // segment tier, batched announcements: 8 ticket counters (64 bytes), then 8 lists of finished gaps
@@ -934,7 +929,6 @@ struct g2s_session {
   std::vector<uint32_t> spare_u32[3];
   std::vector<size_t> spare_sz;
   std::vector<SubPrep> spare_prep;
-  DevBuf d_log, d_lvl, d_plk, d_xl, d_xo;  // LDS tier: state log, level offsets, parent links, closure side lists
   DevBuf d_segx;  // large variant of the segment tier: segment arrays and queues of its persistent workgroups
   DevBuf d_ovf;   // resident mode: the gaps of a launch that outgrew the regular tier (the large variant's list)
   // resident mode, phase D2 on the device for the closures the fill kernels leave (d2_device.hip): the gaps they list
@@ -953,8 +947,6 @@ struct g2s_session {
   size_t d2_ticks_n = 0;     // (G2S_D2_LOG) gaps of the last list whose listing times are in d_d2list
   bool d2_prof_on = false;   // (G2S_D2_PROF) the section counters behind the cursors have been zeroed
   int num_cus = 256;
-  DevBuf d_rspool;
-  DevBuf d_logpool;  // chunks for state logs that outgrow their slice of d_log (LDS tier)                          // LDS tier: spill pool for right sets
   std::vector<void*> tier_pool;  // recycled TierData (pinned host buffers)
   size_t tier_cursor = 0;        // next free slot of tier_pool in the current run
   const void* flank_owner = nullptr;  // batch whose flank nodes d_flank holds
@@ -1159,7 +1151,6 @@ extern "C" int g2s_session_create(g2s_graph* g, int device, const g2s_params* p,
   // srand((randseed > 0) ? randseed : time(NULL)) (Gap2Seq.cpp:178); params keep the user's value for the echo (:191)
   s->seed0 = p->randseed > 0 ? p->randseed : (uint32_t)time(nullptr);
   s->rcache.seed(s->seed0);
-  if (const char* env = GENV("G2S_NO_LDS_TIER")) s->no_lds_tier = atoi(env) != 0;
   hipError_t e = hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking);
   if (e == hipSuccess) e = hipStreamCreateWithFlags(&s->stream2, hipStreamNonBlocking);
   if (e == hipSuccess) e = hipEventCreateWithFlags(&s->ev_rand, hipEventDisableTiming);
@@ -1239,7 +1230,7 @@ extern "C" void g2s_session_destroy(g2s_session* s) {
   for (hipStream_t st : {s->stream, s->stream2, s->stream3}) if (st) (void)hipStreamSynchronize(st);
   DevBuf* bufs[] = {&s->d_gaps, &s->d_ids, &s->d_flank, &s->d_outs, &s->d_rs, &s->d_rlog, &s->d_keys,
                     &s->d_cnt, &s->d_mark, &s->d_slog, &s->d_subscr, &s->d_subout, &s->d_counter, &s->d_xcd,
-                    &s->d_log, &s->d_lvl, &s->d_plk, &s->d_xl, &s->d_xo, &s->d_rspool, &s->d_logpool, &s->d_segx, &s->d_ovf};
+                    &s->d_segx, &s->d_ovf};
   for (DevBuf* b : bufs) b->release();
   delete s->pool;
   delete s->team_pool;
@@ -1399,13 +1390,13 @@ static bool resident_applicable(const g2s_session* s, size_t n) {
   // groups of a team's list may be short: the list is what counts)
   if (forced == 0 || (forced != 1 && !s->in_team_list && n < 256)) return false;
   if (GENV("G2S_NO_SEG_TIER") || GENV("G2S_FORCE_SEGX") || GENV("G2S_HOST_D2") || GENV("G2S_SEG_DUMP") ||
-      GENV("G2S_DUMP_STATS") || GENV("G2S_NO_LDS_TIER") || GENV("G2S_STATE_D2"))
+      GENV("G2S_DUMP_STATS") || GENV("G2S_STATE_D2"))
     return false;
   const Graph& g = *s->graph->g;
   auto it = g.dev.find(s->device);
   if (it == g.dev.end()) return false;
   const DeviceGraph& dg = it->second;
-  return dg.rem != nullptr && !s->no_lds_tier && g.n < (1ull << 28) - 1;
+  return dg.rem != nullptr && g.n < (1ull << 28) - 1;
 }
 
 extern "C" int g2s_batch_prepare(g2s_session* s, const g2s_gap* gaps, size_t n, g2s_batch** out) {
@@ -1713,25 +1704,6 @@ struct Plan {  // per-gap capacities at one scale
   uint64_t bytes;
 };
 
-// LDS tier: capacity of the in-LDS right set for one gap, 0 when the gap is not eligible
-// `room` = entries the launch can afford per gap (LDS per CU / gaps per CU).
-uint32_t lds_rs_cap(const GapJob& j, int d_err, uint32_t room) {
-  const int right_half = j.rmf + (j.g + d_err + 1) / 2;
-  if (j.rmf > (int)fill_lds_max_fuz()) return 0;
-  const uint64_t need = (uint64_t)pow2ceil(std::max<uint64_t>(512, 2ull * (uint64_t)(right_half + j.rmf + 2)));
-  if (need > room) return 0;
-  // small batches leave most of the 160 KB/CU unused: take it, branching right sets then stay in LDS
-  return (uint32_t)std::max<uint64_t>(need, room);
-}
-// entries of right set each gap may have in LDS when `ngaps` gaps share the chip
-uint32_t lds_room(size_t ngaps) {
-  const size_t per_cu = std::max<size_t>(1, (ngaps + 255) / 256);
-  const size_t bytes = (160u * 1024u) / std::min<size_t>(per_cu, 6) - fill_lds_bytes(0, 64) - 512;
-  uint32_t cap = 512;
-  while ((size_t)cap * 2 * 4 <= bytes && cap < 16384) cap <<= 1;
-  return cap;
-}
-
 Plan plan_gap(const GapJob& j, int d_err, uint64_t scale, uint64_t max_states) {
   const int right_half = j.rmf + (j.g + d_err + 1) / 2;
   const int D = j.lmf + j.rmf + j.g + d_err;
@@ -1748,34 +1720,38 @@ Plan plan_gap(const GapJob& j, int d_err, uint64_t scale, uint64_t max_states) {
   return p;
 }
 
-// Launch phases A-D1 for the listed gaps and bring the results back.  lds = true: the
-// LDS-resident kernels (fill_lds.hip); false: the general tier with per-gap tables in
-// HBM (fill_kernels.hip) at the given table scale.
-// on_done (LDS tier): called on the calling thread while the kernel runs, with the indices of
+// on_done (segment tiers): called on the calling thread while the kernel runs, with the indices of
 // gaps whose results have arrived in td->outs / td->subs since the last call.
 using DoneFn = std::function<void(const uint32_t* gaps_done, size_t count)>;
-int run_tier(g2s_batch* b, const std::vector<uint32_t>& ids, uint64_t scale, uint64_t max_states, TierData* td,
-             bool lds, uint32_t lds_room_override = 0, bool rs_in_hbm = false, uint32_t fcap = 64,
-             const DoneFn* on_done = nullptr,
-             int seg = 0 /* segment tier (fill_seg.hip): 1 the tier proper, 2 its large variant; needs lds = true */) {
+
+// d_outs and the cursors are reset right after a segment-tier launch has finished, while the host
+// works on its results: the next launch then starts behind one copy instead of behind three
+// memsets (~25 us on the stream).  Any launch takes them from here: wiped now unless still clean.
+int take_outs_and_cursors(g2s_session* s, size_t n, hipStream_t st) {
+  if (s->d_outs.clean < n * sizeof(GapOut)) HIP_TRY(hipMemsetAsync(s->d_outs.p, 0, n * sizeof(GapOut), st));
+  if (s->d_counter.clean < 32) HIP_TRY(hipMemsetAsync(s->d_counter.p, 0, 32, st));  // [0] output cursor, [1] completion-list cursor, [2] the large variant's next gap
+  s->d_outs.clean = 0;
+  s->d_counter.clean = 0;
+  return G2S_OK;
+}
+
+// Phases A-D1 of the listed gaps in one launch of the segment tier (fill_seg.hip; mode 1) or of its large variant
+// (fill_segw.hip; mode 2).  The kernel writes its results to pinned host memory itself: GapOut per gap, closures
+// packed by an atomic cursor, and the list of finished gaps that on_done is fed from.
+int run_seg_tier(g2s_batch* b, const std::vector<uint32_t>& ids, int mode, TierData* td, const DoneFn* on_done) {
   const auto t_enter = std::chrono::steady_clock::now();
   g2s_session* s = b->s;
-  uint32_t* seg_dbg = nullptr;
   const DeviceGraph& dg = s->graph->g->dev.at(s->device);
   const size_t n = b->jobs.size();
   const int d_err = s->params.d_err;
   HIP_TRY(s->h_gaps.ensure(n * sizeof(GapDev) + ids.size() * 4 + 16));
   GapDev* gd = (GapDev*)s->h_gaps.p;
-  uint32_t* ids_pinned = (uint32_t*)(gd + n);  // the LDS tier reads descriptors and ids from here (no upload)
+  uint32_t* ids_pinned = (uint32_t*)(gd + n);  // short lists: the kernel reads descriptors and ids from here (no upload)
   if (!ids.empty()) memcpy(ids_pinned, ids.data(), ids.size() * 4);
   memset(gd, 0, n * sizeof(GapDev));
-  uint64_t rs_total = 0, rlog_total = 0, st_total = 0, slog_total = 0, lvl_total = 0, xl_total = 0, out_states = 0, out_max = 0;
-  uint32_t lds_cap_max = 0;
   td->gap_ids = ids;
-  for (size_t x = 0; x < ids.size(); x++) {
-    const uint32_t i = ids[x];
+  for (const uint32_t i : ids) {  // (no work-area fields: the search state is in LDS, registers and the variant's d_segx)
     const GapJob& j = b->jobs[i];
-    const Plan p = plan_gap(j, d_err, scale, max_states);
     GapDev& d = gd[i];
     d.g = j.g; d.e = d_err; d.lmf = j.lmf; d.rmf = j.rmf;
     d.D = j.lmf + j.rmf + j.g + d_err;
@@ -1783,197 +1759,92 @@ int run_tier(g2s_batch* b, const std::vector<uint32_t>& ids, uint64_t scale, uin
     d.prune_from = j.g / 2 + d_err / 2 + j.lmf;
     d.all_paths = s->params.all_paths ? 1 : 0;
     d.flank_off = b->flank_off[i];
-    d.rlog_cap = p.rlog_cap; d.rs_mask = 2 * p.rlog_cap - 1;
-    d.slog_cap = p.slog_cap; d.st_mask = 2 * p.slog_cap - 1;
-    d.rs_off = rs_total; rs_total += 2ull * p.rlog_cap;
-    d.rlog_off = rlog_total; rlog_total += p.rlog_cap;
-    d.st_off = st_total; st_total += 2ull * p.slog_cap;
-    d.slog_off = slog_total; slog_total += p.slog_cap;
-    d.lvl_off = lvl_total; lvl_total += (uint64_t)(d.D + 2);
-    // pinned output pool of the LDS tier: 4 states per DP level and gap, plus room for one
-    // gap's worst case (what does not fit is run again by the next pass)
-    out_states += std::min<uint64_t>(p.slog_cap, 4ull * (uint64_t)(d.D + 2));
-    out_max = std::max<uint64_t>(out_max, p.slog_cap);
-    if (lds && !seg) {  // extra-parent list of merged states: a quarter of the log's capacity
-      d.pad0 = std::max(64u, p.slog_cap / 4);
-      d.st_off = xl_total;
-      xl_total += d.pad0;
-    }
-    if (lds && !rs_in_hbm && !seg) {
-      const uint32_t c = lds_rs_cap(j, d_err, lds_room_override ? lds_room_override : lds_room(ids.size()));
-      d.rs_mask = c - 1;
-      lds_cap_max = std::max(lds_cap_max, c);
-    }
   }
   HIP_TRY(s->d_gaps.ensure(n * sizeof(GapDev)));
   HIP_TRY(s->d_ids.ensure(std::max<size_t>(ids.size() * 4, 16)));
   HIP_TRY(s->d_outs.ensure(n * sizeof(GapOut)));
-  if (!seg) HIP_TRY(s->d_subscr.ensure(slog_total * (lds ? sizeof(SubRec) : sizeof(SubState))));
-  if (!lds) HIP_TRY(s->d_subout.ensure(slog_total * sizeof(SubState)));
   HIP_TRY(s->d_counter.ensure(32));
   hipStream_t st = s->stream;
-  if (!lds) {
+  { const int rc = take_outs_and_cursors(s, n, st); if (rc != G2S_OK) return rc; }
+  HIP_TRY(hipEventRecord(s->ev[1], st));
+  // results go straight to pinned host memory (closures packed by an atomic cursor)
+  HIP_TRY(td->outs.ensure(n * sizeof(GapOut)));
+  // (segment tier: two 16-byte units per closure segment; ~15 segments per gap, at most G2S_SEG_CAP.  Large variant:
+  // closures of a few thousand segments, <= 128 MB pinned; what does not fit runs in the HBM tier)
+  const uint64_t out_units = mode == 2 ? std::min<uint64_t>((uint64_t)ids.size() * 4096u, 8ull << 20) + 2u * G2S_SEGX_CAP
+                                       : (uint64_t)ids.size() * 128u + 2u * G2S_SEG_CAP;
+  HIP_TRY(td->subs.ensure(std::max<uint64_t>(out_units * sizeof(SubRec), 16)));
+  HIP_TRY(td->done.ensure(std::max<size_t>(ids.size() * 4, 16)));
+  memset(td->done.p, 0xFF, ids.size() * 4);
+  void *d_outs_host = nullptr, *d_subs_host = nullptr, *d_done_host = nullptr;
+  HIP_TRY(hipHostGetDevicePointer(&d_outs_host, td->outs.p, 0));
+  HIP_TRY(hipHostGetDevicePointer(&d_subs_host, td->subs.p, 0));
+  HIP_TRY(hipHostGetDevicePointer(&d_done_host, td->done.p, 0));
+  // short lists: gap descriptors and the id list are read once per gap, straight from pinned
+  // host memory — with no upload in front of it the kernel starts ~13 us earlier (2-3 % of a
+  // 500-gap step); at 10 000 gaps the reads over the link cost more (kernel +4 %) than the
+  // upload, so long lists keep it
+  void* d_gaps_host = nullptr;
+  HIP_TRY(hipHostGetDevicePointer(&d_gaps_host, s->h_gaps.p, 0));
+  const GapDev* gaps_dev = (const GapDev*)d_gaps_host;
+  const uint32_t* ids_dev = (const uint32_t*)(gaps_dev + n);
+  if (ids.size() > 2048) {
     HIP_TRY(hipMemcpyAsync(s->d_gaps.p, gd, n * sizeof(GapDev), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(s->d_ids.p, ids.data(), ids.size() * 4, hipMemcpyHostToDevice, st));
+    gaps_dev = (const GapDev*)s->d_gaps.p;
+    ids_dev = (const uint32_t*)s->d_ids.p;
   }
-  // d_outs, the cursors and the spill pool are reset right after an LDS-tier launch has
-  // finished, while the host works on its results: the next launch then starts behind one
-  // copy instead of behind three fill kernels (~25 us on the stream)
-  size_t pool_bytes_used = 0, xcd_bytes_used = 0;
-  if (s->d_outs.clean < n * sizeof(GapOut)) HIP_TRY(hipMemsetAsync(s->d_outs.p, 0, n * sizeof(GapOut), st));
-  if (s->d_counter.clean < 32) HIP_TRY(hipMemsetAsync(s->d_counter.p, 0, 32, st));  // [0] output cursor, [1] completion-list cursor, [2] spill-pool cursor, [3] log-pool cursor
-  s->d_outs.clean = 0;
-  s->d_counter.clean = 0;
-  if (lds) {
-    if (!seg) {
-      HIP_TRY(s->d_log.ensure(slog_total * 8));
-      HIP_TRY(s->d_lvl.ensure(lvl_total * 4));
-      HIP_TRY(s->d_plk.ensure(slog_total * 4));
-      HIP_TRY(s->d_xl.ensure(std::max<uint64_t>(xl_total * 8, 16)));
-      HIP_TRY(s->d_xo.ensure(std::max<uint64_t>(xl_total * 8, 16)));
+  const char* seg_dump = GENV("G2S_SEG_DUMP");  // diagnostics: phase A entries + segments of every gap
+  const uint32_t seg_dbg_w = mode == 2 ? fill_segx_dbg_words() : fill_seg_dbg_words();
+  uint32_t* seg_dbg = nullptr;
+  const bool seg_two_waves = GENV("G2S_SEG_WAVES") ? atoi(GENV("G2S_SEG_WAVES")) == 2 : ids.size() <= 2048;
+  if (mode == 1 && seg_two_waves) b->timing.seg2_launches++;
+  // long lists: finished gaps are announced in batches of 16 per XCD (one L2 write-back per batch instead of per
+  // gap; fill_seg.hip, `publish`): config 3's launch 0.8 -> 0.48 ms.  Short lists announce every gap by itself:
+  // their launch ends with its slowest gap either way (config 2: 0.152 ms with batches of 4, 0.153 without), and
+  // the gaps of unfinished batches would be analysed behind the launch's end instead of under it (config 2's
+  // step 0.39 ms against 0.37).
+  const uint32_t pub_batch = ids.size() <= 2048 ? 1u : 16u;
+  size_t xcd_bytes = 0;
+  if (mode == 1 && pub_batch > 1) {
+    xcd_bytes = 64 + 8 * ids.size() * 4;
+    HIP_TRY(s->d_xcd.ensure(xcd_bytes));
+    if (s->d_xcd.clean < xcd_bytes) {
+      HIP_TRY(hipMemsetAsync(s->d_xcd.p, 0, 64, st));
+      HIP_TRY(hipMemsetAsync((char*)s->d_xcd.p + 64, 0xFF, xcd_bytes - 64, st));
     }
-    if (rs_in_hbm) {
-      HIP_TRY(s->d_rs.ensure(rs_total * 4));
-      HIP_TRY(hipMemsetAsync(s->d_rs.p, 0xFF, rs_total * 4, st));
-    }
-    HIP_TRY(hipEventRecord(s->ev[0], st));
-    HIP_TRY(hipEventRecord(s->ev[1], st));  // phases A-C are one kernel in this tier
-    const uint32_t num_oriented = (uint32_t)(2 * s->graph->g->n);
-    // results go straight to pinned host memory (closures packed by an atomic cursor)
-    HIP_TRY(td->outs.ensure(n * sizeof(GapOut)));
-    out_states += out_max;
-    // (segment tier: two 16-byte units per closure segment; ~15 segments per gap, at most G2S_SEG_CAP)
-    if (seg == 1) out_states = (uint64_t)ids.size() * 128u + 2u * G2S_SEG_CAP;
-    // (large variant: closures of a few thousand segments; what does not fit runs in the LDS tier)
-    if (seg == 2) out_states = std::min<uint64_t>((uint64_t)ids.size() * 4096u, 8ull << 20) + 2u * G2S_SEGX_CAP;  // (<= 128 MB pinned)
-    HIP_TRY(td->subs.ensure(std::max<uint64_t>(out_states * sizeof(SubRec), 16)));
-    HIP_TRY(td->done.ensure(std::max<size_t>(ids.size() * 4, 16)));
-    memset(td->done.p, 0xFF, ids.size() * 4);
-    void *d_outs_host = nullptr, *d_subs_host = nullptr, *d_done_host = nullptr;
-    HIP_TRY(hipHostGetDevicePointer(&d_outs_host, td->outs.p, 0));
-    HIP_TRY(hipHostGetDevicePointer(&d_subs_host, td->subs.p, 0));
-    HIP_TRY(hipHostGetDevicePointer(&d_done_host, td->done.p, 0));
-    // spill pool for right sets that outgrow their LDS share (launches with the right set in LDS):
-    // chunks of 32 K entries for an eighth of the gaps
-    const uint32_t chunk_entries = 32768u;
-    uint32_t pool_chunks = 0;
-    if (!rs_in_hbm && lds_cap_max < chunk_entries && !seg) {
-      pool_chunks = (uint32_t)std::min<size_t>(ids.size() / 8 + 16, (s->mem_budget / 8) / ((size_t)chunk_entries * 4));
-      HIP_TRY(s->d_rspool.ensure((size_t)pool_chunks * chunk_entries * 4));
-      if (s->d_rspool.clean < (size_t)pool_chunks * chunk_entries * 4)
-        HIP_TRY(hipMemsetAsync(s->d_rspool.p, 0xFF, (size_t)pool_chunks * chunk_entries * 4, st));
-      s->d_rspool.clean = 0;
-      pool_bytes_used = (size_t)pool_chunks * chunk_entries * 4;
-    }
-    // log pool: a gap whose state log outgrows its slice takes a chunk and goes on (a handful
-    // of repeat-rich gaps per ten thousand; without it they would run again after the launch)
-    const uint32_t log_chunk_states = 131072u;
-    const uint32_t log_chunks = (uint32_t)std::min<size_t>(ids.size() / 64 + 4, 256);
-    if (!seg) HIP_TRY(s->d_logpool.ensure((size_t)log_chunks * fill_lds_log_chunk_bytes(log_chunk_states)));
-    // short lists: gap descriptors and the id list are read once per gap, straight from pinned
-    // host memory — with no upload in front of it the kernel starts ~13 us earlier (2-3 % of a
-    // 500-gap step); at 10 000 gaps the reads over the link cost more (kernel +4 %) than the
-    // upload, so long lists keep it
-    void* d_gaps_host = nullptr;
-    HIP_TRY(hipHostGetDevicePointer(&d_gaps_host, s->h_gaps.p, 0));
-    const GapDev* gaps_dev = (const GapDev*)d_gaps_host;
-    const uint32_t* ids_dev = (const uint32_t*)(gaps_dev + n);
-    if (ids.size() > 2048) {
-      HIP_TRY(hipMemcpyAsync(s->d_gaps.p, gd, n * sizeof(GapDev), hipMemcpyHostToDevice, st));
-      HIP_TRY(hipMemcpyAsync(s->d_ids.p, ids.data(), ids.size() * 4, hipMemcpyHostToDevice, st));
-      gaps_dev = (const GapDev*)s->d_gaps.p;
-      ids_dev = (const uint32_t*)s->d_ids.p;
-    }
-    const char* seg_dump = seg ? GENV("G2S_SEG_DUMP") : nullptr;  // diagnostics: phase A entries + segments of every gap
-    const uint32_t seg_dbg_w = seg == 2 ? fill_segx_dbg_words() : fill_seg_dbg_words();
-    const bool seg_two_waves = GENV("G2S_SEG_WAVES") ? atoi(GENV("G2S_SEG_WAVES")) == 2 : ids.size() <= 2048;
-    if (seg == 1 && seg_two_waves) b->timing.seg2_launches++;
-    // long lists: finished gaps are announced in batches of 16 per XCD (one L2 write-back per batch instead of per
-    // gap; fill_seg.hip, `publish`): config 3's launch 0.8 -> 0.48 ms.  Short lists announce every gap by itself:
-    // their launch ends with its slowest gap either way (config 2: 0.152 ms with batches of 4, 0.153 without), and
-    // the gaps of unfinished batches would be analysed behind the launch's end instead of under it (config 2's
-    // step 0.39 ms against 0.37).
-    const uint32_t pub_batch = ids.size() <= 2048 ? 1u : 16u;
-    size_t xcd_bytes = 0;
-    if (seg == 1 && pub_batch > 1) {
-      xcd_bytes = 64 + 8 * ids.size() * 4;
-      HIP_TRY(s->d_xcd.ensure(xcd_bytes));
-      if (s->d_xcd.clean < xcd_bytes) {
-        HIP_TRY(hipMemsetAsync(s->d_xcd.p, 0, 64, st));
-        HIP_TRY(hipMemsetAsync((char*)s->d_xcd.p + 64, 0xFF, xcd_bytes - 64, st));
-      }
-      s->d_xcd.clean = 0;
-      xcd_bytes_used = xcd_bytes;
-    }
-    if (seg_dump) {
-      HIP_TRY(s->d_slog.ensure((size_t)ids.size() * seg_dbg_w * 4));
-      HIP_TRY(hipMemsetAsync(s->d_slog.p, 0, (size_t)ids.size() * seg_dbg_w * 4, st));
-      seg_dbg = (uint32_t*)s->d_slog.p;
-    }
-    if (seg == 2) {
-      // one persistent workgroup per compute unit (the variant takes nearly all of a CU's LDS)
-      const uint32_t wgs = (uint32_t)std::min<size_t>(ids.size(), (size_t)std::max(1, s->num_cus));
-      HIP_TRY(s->d_segx.ensure(fill_segw_scratch_bytes(wgs)));
-      HIP_TRY(launch_fill_segw(st, (uint32_t)ids.size(), wgs, seg_graph(dg), gaps_dev, ids_dev, (const uint32_t*)s->d_flank.p,
-                               (SubRec*)d_subs_host, (unsigned long long)out_states, (unsigned long long*)s->d_counter.p,
-                               (GapOut*)s->d_outs.p, (GapOut*)d_outs_host, (uint32_t*)d_done_host,
-                               s->params.skip_confident ? 1 : 0, seg_dbg, (uint32_t*)s->d_segx.p,
-                               (unsigned long long*)s->d_counter.p + 2));
-    } else if (seg)
-      HIP_TRY(launch_fill_seg(st, (uint32_t)ids.size(), seg_graph(dg), gaps_dev, ids_dev, (const uint32_t*)s->d_flank.p,
-                              (SubRec*)d_subs_host, (unsigned long long)out_states, (unsigned long long*)s->d_counter.p,
-                              (GapOut*)s->d_outs.p, (GapOut*)d_outs_host, (uint32_t*)d_done_host,
-                              s->params.skip_confident ? 1 : 0, seg_dbg,
-                              // short lists are latency-bound (the launch ends with its slowest gap): two waves per
-                              // gap; long lists fill the chip and are throughput-bound: one (G2S_SEG_WAVES=1|2 forces)
-                              seg_two_waves, (unsigned long long*)s->d_xcd.p, (uint32_t*)((char*)s->d_xcd.p + 64),
-                              (uint32_t)ids.size(), pub_batch));
-    else
-    HIP_TRY(launch_fill_lds(st, (uint32_t)ids.size(), lds_cap_max, num_oriented, dg.succ, dg.ustart,
-                            gaps_dev, ids_dev, (const uint32_t*)s->d_flank.p,
-                            (uint64_t*)s->d_log.p, (uint32_t*)s->d_lvl.p, (uint32_t*)s->d_plk.p, (uint64_t*)s->d_xl.p,
-                            (uint64_t*)s->d_xo.p, (SubRec*)s->d_subscr.p, (SubRec*)d_subs_host,
-                            (unsigned long long)out_states,
-                            (unsigned long long*)s->d_counter.p, (GapOut*)s->d_outs.p, (GapOut*)d_outs_host,
-                            (uint32_t*)d_done_host, s->params.skip_confident ? 1 : 0,
-                            rs_in_hbm ? (uint32_t*)s->d_rs.p : nullptr, fcap, (uint32_t*)s->d_rspool.p, pool_chunks,
-                            chunk_entries, s->d_logpool.p, log_chunks, log_chunk_states));
-    HIP_TRY(hipEventRecord(s->ev[2], st));
-    HIP_TRY(hipEventRecord(s->ev[3], st));
+    s->d_xcd.clean = 0;
+  }
+  if (seg_dump) {
+    HIP_TRY(s->d_slog.ensure((size_t)ids.size() * seg_dbg_w * 4));
+    HIP_TRY(hipMemsetAsync(s->d_slog.p, 0, (size_t)ids.size() * seg_dbg_w * 4, st));
+    seg_dbg = (uint32_t*)s->d_slog.p;
+  }
+  if (mode == 2) {
+    // one persistent workgroup per compute unit (the variant takes nearly all of a CU's LDS)
+    const uint32_t wgs = (uint32_t)std::min<size_t>(ids.size(), (size_t)std::max(1, s->num_cus));
+    HIP_TRY(s->d_segx.ensure(fill_segw_scratch_bytes(wgs)));
+    HIP_TRY(launch_fill_segw(st, (uint32_t)ids.size(), wgs, seg_graph(dg), gaps_dev, ids_dev, (const uint32_t*)s->d_flank.p,
+                             (SubRec*)d_subs_host, (unsigned long long)out_units, (unsigned long long*)s->d_counter.p,
+                             (GapOut*)s->d_outs.p, (GapOut*)d_outs_host, (uint32_t*)d_done_host,
+                             s->params.skip_confident ? 1 : 0, seg_dbg, (uint32_t*)s->d_segx.p,
+                             (unsigned long long*)s->d_counter.p + 2));
   } else {
-    HIP_TRY(s->d_rs.ensure(rs_total * 4));
-    HIP_TRY(s->d_rlog.ensure(rlog_total * 4));
-    HIP_TRY(s->d_keys.ensure(st_total * 8));
-    HIP_TRY(s->d_cnt.ensure(st_total * 4));
-    HIP_TRY(s->d_mark.ensure(st_total * 4));
-    HIP_TRY(s->d_slog.ensure(slog_total * 4));
-    HIP_TRY(hipMemsetAsync(s->d_rs.p, 0xFF, rs_total * 4, st));
-    HIP_TRY(hipMemsetAsync(s->d_keys.p, 0xFF, st_total * 8, st));
-    HIP_TRY(hipMemsetAsync(s->d_cnt.p, 0, st_total * 4, st));
-    HIP_TRY(hipMemsetAsync(s->d_mark.p, 0, st_total * 4, st));
-    HIP_TRY(hipEventRecord(s->ev[0], st));
-    HIP_TRY(launch_right_bfs(st, (uint32_t)ids.size(), dg.succ, dg.pred, (const GapDev*)s->d_gaps.p,
-                             (const uint32_t*)s->d_ids.p, (const uint32_t*)s->d_flank.p, (uint32_t*)s->d_rs.p,
-                             (uint32_t*)s->d_rlog.p, (GapOut*)s->d_outs.p));
-    HIP_TRY(hipEventRecord(s->ev[1], st));
-    HIP_TRY(launch_left_dp(st, (uint32_t)ids.size(), dg.succ, (const GapDev*)s->d_gaps.p,
-                           (const uint32_t*)s->d_ids.p, (const uint32_t*)s->d_flank.p, (const uint32_t*)s->d_rs.p,
-                           (uint64_t*)s->d_keys.p, (uint32_t*)s->d_cnt.p, (uint32_t*)s->d_slog.p,
-                           (GapOut*)s->d_outs.p));
-    HIP_TRY(hipEventRecord(s->ev[2], st));
-    HIP_TRY(launch_extract(st, (uint32_t)ids.size(), dg.succ, dg.pred, (const GapDev*)s->d_gaps.p,
-                           (const uint32_t*)s->d_ids.p, (const uint32_t*)s->d_flank.p, (const uint64_t*)s->d_keys.p,
-                           (const uint32_t*)s->d_cnt.p, (uint32_t*)s->d_mark.p, (SubState*)s->d_subscr.p,
-                           (SubState*)s->d_subout.p, (unsigned long long*)s->d_counter.p, (GapOut*)s->d_outs.p,
-                           s->params.skip_confident ? 1 : 0));
-    HIP_TRY(hipEventRecord(s->ev[3], st));
+    HIP_TRY(launch_fill_seg(st, (uint32_t)ids.size(), seg_graph(dg), gaps_dev, ids_dev, (const uint32_t*)s->d_flank.p,
+                            (SubRec*)d_subs_host, (unsigned long long)out_units, (unsigned long long*)s->d_counter.p,
+                            (GapOut*)s->d_outs.p, (GapOut*)d_outs_host, (uint32_t*)d_done_host,
+                            s->params.skip_confident ? 1 : 0, seg_dbg,
+                            // short lists are latency-bound (the launch ends with its slowest gap): two waves per
+                            // gap; long lists fill the chip and are throughput-bound: one (G2S_SEG_WAVES=1|2 forces)
+                            seg_two_waves, (unsigned long long*)s->d_xcd.p, (uint32_t*)((char*)s->d_xcd.p + 64),
+                            (uint32_t)ids.size(), pub_batch));
   }
+  HIP_TRY(hipEventRecord(s->ev[2], st));
 
   const auto t_launched = std::chrono::steady_clock::now();
-  progress_note("launched: %zu gaps, lds %d seg %d scale %llu", ids.size(), (int)lds, seg, (unsigned long long)scale);
-  if (lds) {
-   if (seg && on_done) {
-    // Segment tier: the analysis of a gap costs a fraction of a microsecond (it runs on the closure
+  progress_note("launched: %zu gaps, segment tier mode %d", ids.size(), mode);
+  if (on_done) {
+    // The analysis of a gap costs a fraction of a microsecond (it runs on the closure
     // segments, or only copies what the device found).  Short lists: whatever has arrived is analysed
     // at once on this thread.  Long lists: a hand-over to the pool for every eighth of the list, so that
     // an eighth at most is left when the kernel ends.  Only this thread polls, napping between looks.
@@ -2003,134 +1874,151 @@ int run_tier(g2s_batch* b, const std::vector<uint32_t>& ids, uint64_t scale, uin
       }
     }
     prctl(PR_SET_TIMERSLACK, old_slack > 0 ? (unsigned long)old_slack : 50000UL, 0, 0, 0);
-   } else if (on_done) {
-      // gaps finish at very different times (the longest take 10x the median): hand the
-      // finished ones to the caller while the kernel is still running.  Only this thread
-      // polls, and it naps between looks: a busy host must not starve the HIP runtime.
-      const volatile uint32_t* done = (const volatile uint32_t*)td->done.p;
-      size_t seen = 0, given = 0;
-      const size_t total = ids.size();
-      // a few large hand-overs (every one of them wakes the worker pool) while gaps arrive in
-      // numbers; once arrivals dry up — the stragglers — whatever is there goes out at once,
-      // so that next to nothing is left when the last gap finishes
-      const size_t chunk = std::max<size_t>(32, total / 8);
-      // the naps below are a few microseconds; the default timer slack (50 us) would stretch them
-      const int old_slack = prctl(PR_GET_TIMERSLACK, 0, 0, 0, 0);
-      prctl(PR_SET_TIMERSLACK, 1000UL, 0, 0, 0);
-      auto last_arrival = std::chrono::steady_clock::now();
-      double dbg_first = -1, dbg_fin = -1;
-      while (given < total) {
-        const size_t before = seen;
-        while (seen < total && done[seen] != 0xFFFFFFFFu) seen++;
-        std::atomic_thread_fence(std::memory_order_acquire);
-        const auto now = std::chrono::steady_clock::now();
-        if (seen != before) last_arrival = now;
-        const bool finished = hipEventQuery(s->ev[2]) != hipErrorNotReady;
-        if (dbg_first < 0 && seen > 0) dbg_first = ms_between(t_launched, now);
-        if (dbg_fin < 0 && finished) dbg_fin = ms_between(t_launched, now);
-        const bool lull = seen > given && std::chrono::duration<double, std::micro>(now - last_arrival).count() > 60.0;
-        if (seen - given >= chunk || lull || (finished && seen > given) || seen == total) {
-          (*on_done)((const uint32_t*)td->done.p + given, seen - given);
-          given = seen;
-        } else if (finished) {
-          while (seen < total && done[seen] != 0xFFFFFFFFu) seen++;
-          if (seen == given) break;  // kernel over and nothing new: an error, reported by the sync below
-        } else {
-          // (short naps once only the stragglers are left: their arrival ends the launch)
-          struct timespec ts = {0, seen * 10 > total * 9 ? 4000 : 20000};
-          nanosleep(&ts, nullptr);
-        }
-      }
-      prctl(PR_SET_TIMERSLACK, old_slack > 0 ? (unsigned long)old_slack : 50000UL, 0, 0, 0);
-      if (GENV("G2S_DEBUG"))
-        fprintf(stderr, "[g2s] run_tier: first gap seen %.3f ms after the launch call, kernel seen finished at %.3f ms\n", dbg_first, dbg_fin);
-    }
-    const auto t_polled = std::chrono::steady_clock::now();
-    // (measured: leaving this wait to the end of the run makes the step slower, not faster — the runtime's
-    // completion handling then competes with the tracebacks for the host's CPUs)
-    HIP_TRY(hipStreamSynchronize(st));  // the kernels wrote td->outs / td->subs themselves
-    if (seg_dbg) {
-      const uint32_t W = seg == 2 ? fill_segx_dbg_words() : fill_seg_dbg_words();
-      const uint32_t ecap = seg == 2 ? G2S_SEGX_EA : 64u * G2S_SEG_ASETS, scap = seg == 2 ? G2S_SEGX_CAP : G2S_SEG_CAP;
-      std::vector<uint32_t> h((size_t)ids.size() * W);
-      HIP_TRY(hipMemcpy(h.data(), seg_dbg, h.size() * 4, hipMemcpyDeviceToHost));
-      if (FILE* f = fopen(GENV("G2S_SEG_DUMP"), "a")) {
-        const uint32_t sb0 = 8u + 2u * ecap;
-        for (size_t x = 0; x < ids.size(); x++) {
-          const uint32_t* o = h.data() + x * W;
-          fprintf(f, "gap %u nA %u nseg %u flags %#x roundsA %u roundsB %u c_count %u best %u\n", o[0], o[1], o[2], o[3], o[4], o[5], o[6], o[7]);
-          if (o[W - 4] | o[W - 3] | o[W - 2] | o[W - 1])  // (-DG2S_SEG_PROFILE builds) cycles of phase B's sections
-            fprintf(f, "P %u %u %u %u %u %u %u %u %u %u\n", o[W - 4], o[W - 3], o[W - 2], o[W - 1], o[W - 8], o[W - 7], o[W - 6], o[W - 5],
-                    o[W - 10], o[W - 9]);
-          if (o[W - 14] | o[W - 13] | o[W - 12] | o[W - 11])  // (the same builds, one wave per gap) cycles of phase A's sections
-            fprintf(f, "PA %u %u %u %u\n", o[W - 14], o[W - 13], o[W - 12], o[W - 11]);
-          if (GENV("G2S_SEG_DUMP_BRIEF")) continue;  // (profiles: no entries, no segments)
-          for (uint32_t e = 0; e < o[1] && e < ecap; e++) fprintf(f, "A %u %u\n", o[8 + 2 * e], o[9 + 2 * e]);
-          for (uint32_t q = 0; q < o[2] && q < scap; q++)
-            fprintf(f, "S %u %u %u %u %#x %#x %u\n", o[sb0 + 6 * q], o[sb0 + 6 * q + 1] & 0xFFFF, o[sb0 + 6 * q + 1] >> 16,
-                    o[sb0 + 6 * q + 2], o[sb0 + 6 * q + 3], o[sb0 + 6 * q + 4], o[sb0 + 6 * q + 5]);
-        }
-        fclose(f);
-      }
-    }
-    {  // resets for the next launch, off its critical path (nobody waits for them here)
-      HIP_TRY(hipMemsetAsync(s->d_outs.p, 0, n * sizeof(GapOut), st));
-      s->d_outs.clean = n * sizeof(GapOut);
-      HIP_TRY(hipMemsetAsync(s->d_counter.p, 0, 32, st));
-      s->d_counter.clean = 32;
-      if (xcd_bytes_used) {
-        HIP_TRY(hipMemsetAsync(s->d_xcd.p, 0, 64, st));
-        HIP_TRY(hipMemsetAsync((char*)s->d_xcd.p + 64, 0xFF, xcd_bytes_used - 64, st));
-        s->d_xcd.clean = xcd_bytes_used;
-      }
-      if (pool_bytes_used) {
-        HIP_TRY(hipMemsetAsync(s->d_rspool.p, 0xFF, pool_bytes_used, st));
-        s->d_rspool.clean = pool_bytes_used;
-      }
-    }
-    if (GENV("G2S_DEBUG"))
-      fprintf(stderr, "[g2s] run_tier: plan+upload+launch %.3f ms, polling/analysis %.3f ms, final sync %.3f ms\n",
-              ms_between(t_enter, t_launched), ms_between(t_launched, t_polled), ms_since(t_polled));
-  } else {
-    // device -> host: per-gap results, then the packed closures
-    HIP_TRY(td->outs.ensure(n * sizeof(GapOut)));
-    unsigned long long total_sub = 0;
-    HIP_TRY(hipMemcpyAsync(td->outs.p, s->d_outs.p, n * sizeof(GapOut), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(&total_sub, s->d_counter.p, 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    auto t0 = std::chrono::steady_clock::now();
-    HIP_TRY(td->subs.ensure(std::max<uint64_t>(total_sub * sizeof(SubState), 16)));
-    if (total_sub)
-      HIP_TRY(hipMemcpyAsync(td->subs.p, s->d_subout.p, total_sub * sizeof(SubState), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    b->timing.ms_d2h += ms_since(t0);
   }
-  progress_note("finished: %zu gaps, lds %d seg %d", ids.size(), (int)lds, seg);
+  const auto t_polled = std::chrono::steady_clock::now();
+  // (measured: leaving this wait to the end of the run makes the step slower, not faster — the runtime's
+  // completion handling then competes with the tracebacks for the host's CPUs)
+  HIP_TRY(hipStreamSynchronize(st));  // the kernel wrote td->outs / td->subs itself
+  if (seg_dbg) {
+    const uint32_t W = seg_dbg_w;
+    const uint32_t ecap = mode == 2 ? G2S_SEGX_EA : 64u * G2S_SEG_ASETS, scap = mode == 2 ? G2S_SEGX_CAP : G2S_SEG_CAP;
+    std::vector<uint32_t> h((size_t)ids.size() * W);
+    HIP_TRY(hipMemcpy(h.data(), seg_dbg, h.size() * 4, hipMemcpyDeviceToHost));
+    if (FILE* f = fopen(seg_dump, "a")) {
+      const uint32_t sb0 = 8u + 2u * ecap;
+      for (size_t x = 0; x < ids.size(); x++) {
+        const uint32_t* o = h.data() + x * W;
+        fprintf(f, "gap %u nA %u nseg %u flags %#x roundsA %u roundsB %u c_count %u best %u\n", o[0], o[1], o[2], o[3], o[4], o[5], o[6], o[7]);
+        if (o[W - 4] | o[W - 3] | o[W - 2] | o[W - 1])  // (-DG2S_SEG_PROFILE builds) cycles of phase B's sections
+          fprintf(f, "P %u %u %u %u %u %u %u %u %u %u\n", o[W - 4], o[W - 3], o[W - 2], o[W - 1], o[W - 8], o[W - 7], o[W - 6], o[W - 5],
+                  o[W - 10], o[W - 9]);
+        if (o[W - 14] | o[W - 13] | o[W - 12] | o[W - 11])  // (the same builds, one wave per gap) cycles of phase A's sections
+          fprintf(f, "PA %u %u %u %u\n", o[W - 14], o[W - 13], o[W - 12], o[W - 11]);
+        if (GENV("G2S_SEG_DUMP_BRIEF")) continue;  // (profiles: no entries, no segments)
+        for (uint32_t e = 0; e < o[1] && e < ecap; e++) fprintf(f, "A %u %u\n", o[8 + 2 * e], o[9 + 2 * e]);
+        for (uint32_t q = 0; q < o[2] && q < scap; q++)
+          fprintf(f, "S %u %u %u %u %#x %#x %u\n", o[sb0 + 6 * q], o[sb0 + 6 * q + 1] & 0xFFFF, o[sb0 + 6 * q + 1] >> 16,
+                  o[sb0 + 6 * q + 2], o[sb0 + 6 * q + 3], o[sb0 + 6 * q + 4], o[sb0 + 6 * q + 5]);
+      }
+      fclose(f);
+    }
+  }
+  {  // resets for the next launch, off its critical path (nobody waits for them here)
+    HIP_TRY(hipMemsetAsync(s->d_outs.p, 0, n * sizeof(GapOut), st));
+    s->d_outs.clean = n * sizeof(GapOut);
+    HIP_TRY(hipMemsetAsync(s->d_counter.p, 0, 32, st));
+    s->d_counter.clean = 32;
+    if (xcd_bytes) {
+      HIP_TRY(hipMemsetAsync(s->d_xcd.p, 0, 64, st));
+      HIP_TRY(hipMemsetAsync((char*)s->d_xcd.p + 64, 0xFF, xcd_bytes - 64, st));
+      s->d_xcd.clean = xcd_bytes;
+    }
+  }
+  if (GENV("G2S_DEBUG"))
+    fprintf(stderr, "[g2s] run_seg_tier: plan+upload+launch %.3f ms, polling/analysis %.3f ms, final sync %.3f ms\n",
+            ms_between(t_enter, t_launched), ms_between(t_launched, t_polled), ms_since(t_polled));
+  progress_note("finished: %zu gaps, segment tier mode %d", ids.size(), mode);
   float ms = 0;
-  if (seg == 2) {
-    HIP_TRY(hipEventElapsedTime(&ms, s->ev[1], s->ev[2]));
+  HIP_TRY(hipEventElapsedTime(&ms, s->ev[1], s->ev[2]));
+  if (mode == 2) {
     b->timing.ms_fill_segx += ms;
     b->timing.segx_launches++;
-  } else if (seg) {
-    HIP_TRY(hipEventElapsedTime(&ms, s->ev[1], s->ev[2]));
+  } else {
     b->timing.ms_fill_seg += ms;
     b->timing.seg_launches++;
     b->timing.seg_timed_launches++;
-  } else if (lds) {
-    HIP_TRY(hipEventElapsedTime(&ms, s->ev[1], s->ev[2]));
-    b->timing.ms_fill_lds += ms;
-    b->timing.lds_launches++;
-    HIP_TRY(hipEventElapsedTime(&ms, s->ev[2], s->ev[3]));
-    b->timing.ms_extract_lds += ms;
-  } else {
-    HIP_TRY(hipEventElapsedTime(&ms, s->ev[0], s->ev[1]));
-    b->timing.ms_right_bfs += ms;
-    HIP_TRY(hipEventElapsedTime(&ms, s->ev[1], s->ev[2]));
-    b->timing.ms_left_dp += ms;
-    HIP_TRY(hipEventElapsedTime(&ms, s->ev[2], s->ev[3]));
-    b->timing.ms_extract += ms;
-    b->timing.launches_left_dp++;
   }
+  return G2S_OK;
+}
+
+// Phases A-D1 of the listed gaps in the general tier (fill_kernels.hip): three kernels over per-gap tables in HBM at
+// the given table scale, then the results copied back.  The fallback behind the segment tiers.
+int run_hbm_tier(g2s_batch* b, const std::vector<uint32_t>& ids, uint64_t scale, uint64_t max_states, TierData* td) {
+  g2s_session* s = b->s;
+  const DeviceGraph& dg = s->graph->g->dev.at(s->device);
+  const size_t n = b->jobs.size();
+  const int d_err = s->params.d_err;
+  HIP_TRY(s->h_gaps.ensure(n * sizeof(GapDev)));
+  GapDev* gd = (GapDev*)s->h_gaps.p;  // (staging: the kernels read the copy in d_gaps)
+  memset(gd, 0, n * sizeof(GapDev));
+  uint64_t rs_total = 0, rlog_total = 0, st_total = 0, slog_total = 0;
+  td->gap_ids = ids;
+  for (const uint32_t i : ids) {
+    const GapJob& j = b->jobs[i];
+    const Plan p = plan_gap(j, d_err, scale, max_states);
+    GapDev& d = gd[i];
+    d.g = j.g; d.e = d_err; d.lmf = j.lmf; d.rmf = j.rmf;
+    d.D = j.lmf + j.rmf + j.g + d_err;
+    d.right_half = j.rmf + (j.g + d_err + 1) / 2;
+    d.prune_from = j.g / 2 + d_err / 2 + j.lmf;
+    d.all_paths = s->params.all_paths ? 1 : 0;
+    d.flank_off = b->flank_off[i];
+    d.rlog_cap = p.rlog_cap; d.rs_mask = 2 * p.rlog_cap - 1;
+    d.slog_cap = p.slog_cap; d.st_mask = 2 * p.slog_cap - 1;
+    d.rs_off = rs_total; rs_total += 2ull * p.rlog_cap;
+    d.rlog_off = rlog_total; rlog_total += p.rlog_cap;
+    d.st_off = st_total; st_total += 2ull * p.slog_cap;
+    d.slog_off = slog_total; slog_total += p.slog_cap;
+  }
+  HIP_TRY(s->d_gaps.ensure(n * sizeof(GapDev)));
+  HIP_TRY(s->d_ids.ensure(std::max<size_t>(ids.size() * 4, 16)));
+  HIP_TRY(s->d_outs.ensure(n * sizeof(GapOut)));
+  HIP_TRY(s->d_subscr.ensure(slog_total * sizeof(SubState)));
+  HIP_TRY(s->d_subout.ensure(slog_total * sizeof(SubState)));
+  HIP_TRY(s->d_counter.ensure(32));
+  hipStream_t st = s->stream;
+  HIP_TRY(hipMemcpyAsync(s->d_gaps.p, gd, n * sizeof(GapDev), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(s->d_ids.p, ids.data(), ids.size() * 4, hipMemcpyHostToDevice, st));
+  { const int rc = take_outs_and_cursors(s, n, st); if (rc != G2S_OK) return rc; }
+  HIP_TRY(s->d_rs.ensure(rs_total * 4));
+  HIP_TRY(s->d_rlog.ensure(rlog_total * 4));
+  HIP_TRY(s->d_keys.ensure(st_total * 8));
+  HIP_TRY(s->d_cnt.ensure(st_total * 4));
+  HIP_TRY(s->d_mark.ensure(st_total * 4));
+  HIP_TRY(s->d_slog.ensure(slog_total * 4));
+  HIP_TRY(hipMemsetAsync(s->d_rs.p, 0xFF, rs_total * 4, st));
+  HIP_TRY(hipMemsetAsync(s->d_keys.p, 0xFF, st_total * 8, st));
+  HIP_TRY(hipMemsetAsync(s->d_cnt.p, 0, st_total * 4, st));
+  HIP_TRY(hipMemsetAsync(s->d_mark.p, 0, st_total * 4, st));
+  HIP_TRY(hipEventRecord(s->ev[0], st));
+  HIP_TRY(launch_right_bfs(st, (uint32_t)ids.size(), dg.succ, dg.pred, (const GapDev*)s->d_gaps.p,
+                           (const uint32_t*)s->d_ids.p, (const uint32_t*)s->d_flank.p, (uint32_t*)s->d_rs.p,
+                           (uint32_t*)s->d_rlog.p, (GapOut*)s->d_outs.p));
+  HIP_TRY(hipEventRecord(s->ev[1], st));
+  HIP_TRY(launch_left_dp(st, (uint32_t)ids.size(), dg.succ, (const GapDev*)s->d_gaps.p,
+                         (const uint32_t*)s->d_ids.p, (const uint32_t*)s->d_flank.p, (const uint32_t*)s->d_rs.p,
+                         (uint64_t*)s->d_keys.p, (uint32_t*)s->d_cnt.p, (uint32_t*)s->d_slog.p,
+                         (GapOut*)s->d_outs.p));
+  HIP_TRY(hipEventRecord(s->ev[2], st));
+  HIP_TRY(launch_extract(st, (uint32_t)ids.size(), dg.succ, dg.pred, (const GapDev*)s->d_gaps.p,
+                         (const uint32_t*)s->d_ids.p, (const uint32_t*)s->d_flank.p, (const uint64_t*)s->d_keys.p,
+                         (const uint32_t*)s->d_cnt.p, (uint32_t*)s->d_mark.p, (SubState*)s->d_subscr.p,
+                         (SubState*)s->d_subout.p, (unsigned long long*)s->d_counter.p, (GapOut*)s->d_outs.p,
+                         s->params.skip_confident ? 1 : 0));
+  HIP_TRY(hipEventRecord(s->ev[3], st));
+  progress_note("launched: %zu gaps, HBM tier scale %llu", ids.size(), (unsigned long long)scale);
+
+  // device -> host: per-gap results, then the packed closures
+  HIP_TRY(td->outs.ensure(n * sizeof(GapOut)));
+  unsigned long long total_sub = 0;
+  HIP_TRY(hipMemcpyAsync(td->outs.p, s->d_outs.p, n * sizeof(GapOut), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(&total_sub, s->d_counter.p, 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  auto t0 = std::chrono::steady_clock::now();
+  HIP_TRY(td->subs.ensure(std::max<uint64_t>(total_sub * sizeof(SubState), 16)));
+  if (total_sub)
+    HIP_TRY(hipMemcpyAsync(td->subs.p, s->d_subout.p, total_sub * sizeof(SubState), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  b->timing.ms_d2h += ms_since(t0);
+  progress_note("finished: %zu gaps, HBM tier", ids.size());
+  float ms = 0;
+  HIP_TRY(hipEventElapsedTime(&ms, s->ev[0], s->ev[1]));
+  b->timing.ms_right_bfs += ms;
+  HIP_TRY(hipEventElapsedTime(&ms, s->ev[1], s->ev[2]));
+  b->timing.ms_left_dp += ms;
+  HIP_TRY(hipEventElapsedTime(&ms, s->ev[2], s->ev[3]));
+  b->timing.ms_extract += ms;
+  b->timing.launches_left_dp++;
   return G2S_OK;
 }
 
@@ -2232,7 +2120,7 @@ void analyze_gap(g2s_batch* b, size_t i, const FillParams& fp, g2s_result* r) {
   }
   if (!analysed) {
     const auto ta0 = std::chrono::steady_clock::now();
-    if (v.n_xp > 1) std::sort(const_cast<uint64_t*>(v.xp), const_cast<uint64_t*>(v.xp) + v.n_xp);  // by state (the kernel appends per level)
+    if (v.n_xp > 1) std::sort(const_cast<uint64_t*>(v.xp), const_cast<uint64_t*>(v.xp) + v.n_xp);  // by state, then by parent
     sub_analyze(fp, j, v, &pp);
     if (dbg_analysis_stats) {
       dbg_ns_state.fetch_add((uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - ta0).count());
@@ -2336,12 +2224,12 @@ int batch_stage1(g2s_batch* b, bool analyze, g2s_result* results) {
   };
   struct DoneSums { uint64_t xA = 0, sA = 0, xB = 0, sB = 0, xD = 0, sD = 0, segs = 0; uint32_t seg_gaps = 0, segx_gaps = 0; };
   // a finished gap's view of the launch's buffers and its share of the launch's sums; 0: nothing to analyse (seen
-  // before, or it runs again in a later pass), 1: analyse now, 2: a large closure for the host, analysed without waiting
+  // before, or it runs again in the next tier), 1: analyse now, 2: a large closure for the host, analysed without waiting
   auto admit = [&](uint32_t i, DoneSums& acc) -> int {
     if (i >= n || analyzed[i]) return 0;
     const GapOut* outs = (const GapOut*)td_live->outs.p;
     const GapOut& go = outs[i];
-    if (go.flags & (G2S_DEV_OVERFLOW_A | G2S_DEV_OVERFLOW_B)) return 0;  // runs again in a later pass
+    if (go.flags & (G2S_DEV_OVERFLOW_A | G2S_DEV_OVERFLOW_B)) return 0;  // runs again in the next tier
     if ((go.flags & G2S_DEV_COMPACT) && ((uint64_t)go.n_states > max_states || (uint64_t)go.n_right > max_states))
       mem_exceeded[i] = 1;  // segment tier: the -max-mem analogue is applied to the state count
     SubView& v = views[i];
@@ -2442,17 +2330,12 @@ int batch_stage1(g2s_batch* b, bool analyze, g2s_result* results) {
     ms_stream += ms_since(t0);
   };
 
-  // ---- GPU: phases A-D1, retrying gaps whose tables overflowed with 8x larger ones
-  std::vector<uint32_t> todo, lds_ids, late1, late2;  // late1/late2: gaps that start in pass 1 / pass 2
-  // (the LDS right set keeps 28-bit k-mer indices)
-  const bool idx_ok = !s->no_lds_tier && s->graph->g->n < (1ull << 28) - 1;
-  // (the LDS tier derives predecessors from the successor table: closed to graphs with a predecessor table, even k,
-  // whose gaps go from the segment tier and its large variant straight to the HBM tier)
-  const bool lds_ok = idx_ok && s->graph->g->dev.at(s->device).pred == nullptr;
-  // ---- segment tier first (fill_seg.hip): every gap it can hold (-fuz <= 31, D < 2^15);
-  // a gap that outgrows one of its capacities comes back flagged and takes the passes below
+  // ---- GPU: phases A-D1
+  // ---- segment tier first (fill_seg.hip): every gap it can hold (-fuz <= 31, D < 2^15) on a graph it is open to
+  // (node ids below 2^28 - 1); a gap that outgrows one of its capacities comes back flagged and takes the fallback below
   std::vector<char> seg_done(n, 0);
-  const bool seg_ok = idx_ok && s->graph->g->dev.at(s->device).rem != nullptr && !GENV("G2S_NO_SEG_TIER");
+  const bool seg_idx_ok = s->graph->g->n < (1ull << 28) - 1;
+  const bool seg_ok = seg_idx_ok && s->graph->g->dev.at(s->device).rem != nullptr && !GENV("G2S_NO_SEG_TIER");
   if (seg_ok) {
     std::vector<uint32_t> seg_ids;
     for (size_t i = 0; i < n; i++) {
@@ -2462,7 +2345,7 @@ int batch_stage1(g2s_batch* b, bool analyze, g2s_result* results) {
     }
     // mode 1: the tier proper; mode 2: its large variant (g2s_fill_segw) for the gaps that outgrew a capacity of
     // mode 1 (-dist-error 2000: thousands of segments and right-set entries); what outgrows that too takes
-    // the passes below
+    // the fallback below
     // (tests: G2S_FORCE_SEGX=1 sends every gap to the large variant, G2S_NO_SEGX_TIER=1 none)
     for (int mode = GENV("G2S_FORCE_SEGX") ? 2 : 1; mode <= 2 && !seg_ids.empty(); mode++) {
       if (mode == 2 && GENV("G2S_NO_SEGX_TIER")) break;
@@ -2494,11 +2377,11 @@ int batch_stage1(g2s_batch* b, bool analyze, g2s_result* results) {
       }
       lap("segment pass set-up");
       seg_mode_live = mode;
-      int rc = run_tier(b, seg_ids, 1, max_states, td, true, 0, false, 64u, analyze ? &on_done : nullptr, mode);
+      int rc = run_seg_tier(b, seg_ids, mode, td, analyze ? &on_done : nullptr);
       seg_mode_live = 0;
       flush_heavy();
       if (rc != G2S_OK) return rc;
-      lap("segment pass run_tier");
+      lap("segment pass run_seg_tier");
       const GapOut* outs = (const GapOut*)td->outs.p;
       std::vector<uint32_t> left;
       for (uint32_t i : seg_ids) {
@@ -2513,9 +2396,9 @@ int batch_stage1(g2s_batch* b, bool analyze, g2s_result* results) {
           if (GENV("G2S_DEBUG"))
             fprintf(stderr, "[g2s] gap %u left the segment tier (mode %d): flags 0x%x entries %u segments %u g %d\n", i, mode,
                     go.flags, go.stat[1], go.stat[3], b->jobs[i].g);
-          if (go.flags & G2S_DEV_WATCHDOG) {  // a defect, never expected: say so, the gap is filled by the LDS tier
+          if (go.flags & G2S_DEV_WATCHDOG) {  // a defect, never expected: say so, the gap is filled by the HBM tier
             b->timing.watchdog_gaps++;
-            fprintf(stderr, "[g2s] segment tier (mode %d): a probe loop ran past its bound on gap %u (flags 0x%x); the gap runs in the LDS tier\n",
+            fprintf(stderr, "[g2s] segment tier (mode %d): a probe loop ran past its bound on gap %u (flags 0x%x); the gap runs in the HBM tier\n",
                     mode, i, go.flags);
           }
           left.push_back(i);
@@ -2564,111 +2447,13 @@ int batch_stage1(g2s_batch* b, bool analyze, g2s_result* results) {
       seg_ids.swap(left);
     }
   }
-  {
-    size_t nvalid = 0;
-    for (size_t i = 0; i < n; i++) nvalid += !b->jobs[i].bad_flank && !seg_done[i];
-    const uint32_t room = lds_room(std::max<size_t>(1, nvalid));
-    for (size_t i = 0; i < n; i++) {
-      if (b->jobs[i].bad_flank || seg_done[i]) continue;
-      if (lds_ok && lds_rs_cap(b->jobs[i], fp.d_err, room) != 0) lds_ids.push_back((uint32_t)i);
-      else if (lds_ok && lds_rs_cap(b->jobs[i], fp.d_err, 16384u) != 0) late1.push_back((uint32_t)i);   // pass 1's table
-      else if (lds_ok && b->jobs[i].rmf <= (int)fill_lds_max_fuz()) late2.push_back((uint32_t)i);        // right set in HBM
-      else todo.push_back((uint32_t)i);
-    }
-  }
-  // ---- tier 0: LDS-resident kernels.  Pass 1 shares the CU's LDS among as many gaps as
-  // the batch needs resident; gaps whose right set outgrows that share are run again with
-  // the largest LDS tables (pass 2, few gaps per CU); what still does not fit (frontier
-  // > 64, > 128 target hits, state log) falls through to the HBM tier.
-  //   pass 0: LDS shared among all gaps of the batch, state log 8 (D+2)
-  //   pass 1: largest LDS right set (16 K entries), state log 64 (D+2)
-  //   pass 2: right set in HBM (any size up to -max-mem), the rest still in LDS
-  std::vector<uint32_t> cand[3];
-  cand[0] = lds_ids;
-  cand[1] = late1;
-  cand[2] = late2;
-  const bool room0_is_max = lds_room(n) >= 16384u;
-  for (int pass = 0; pass < 3; pass++) {
-    if (cand[pass].empty()) continue;
-    // Workgroups are dispatched in id order and a launch ends with its slowest gap: start the
-    // gaps with the most DP levels first, so that the long ones are not the last to begin
-    // (lists longer than the chip holds at once).
-    if (cand[pass].size() > 1024)
-      std::stable_sort(cand[pass].begin(), cand[pass].end(),
-                       [&](uint32_t a, uint32_t c) { return b->jobs[a].g > b->jobs[c].g; });
-    const std::vector<uint32_t>& ids = cand[pass];
-    const uint32_t room = pass == 0 ? 0u : 16384u;
-    TierData* td = take_tier(s, b->tiers.size());
-    b->tiers.push_back(td);
-    // pass 0 keeps the LDS footprint small (frontier 64); later passes run few gaps per CU and
-    // take wide frontiers (1024 entries) so that repeat-rich gaps stay out of the HBM tier
-    td_live = td;
-    int rc = run_tier(b, ids, pass == 0 ? 1 : 8, max_states, td, true, room, pass == 2, pass == 0 ? 64u : 1024u,
-                      analyze ? &on_done : nullptr);
-    if (rc != G2S_OK) return rc;
-    const GapOut* outs = (const GapOut*)td->outs.p;
-    for (uint32_t i : ids) {
-      const GapOut& go = outs[i];
-      if (go.flags & (G2S_DEV_OVERFLOW_A | G2S_DEV_OVERFLOW_B)) {
-        if (GENV("G2S_DEBUG"))
-          fprintf(stderr, "[g2s] gap %u left LDS pass %d: flags 0x%x n_right %u x_right %u n_states %u x_left %u final_d %d g %d\n",
-                  i, pass, go.flags, go.n_right, go.x_right, go.n_states, go.x_left, go.final_d, b->jobs[i].g);
-        // a right-set overflow is cured by a larger right set (pass 1 unless pass 0 already
-        // had the largest LDS table, else pass 2); state-log and frontier overflows by pass 1's
-        // larger log and 1024-entry frontier; what still overflows goes to the HBM tier
-        const bool only_a = (go.flags & G2S_DEV_OVERFLOW_A) && !(go.flags & G2S_DEV_OVERFLOW_B);
-        int target = 3;
-        // deep searches (-dist-error in the thousands) overflow the largest LDS right set too
-        const bool deep = b->jobs[i].rmf + (b->jobs[i].g + fp.d_err + 1) / 2 > 2048;
-        if (pass == 0) target = (only_a && (room0_is_max || deep)) ? 2 : 1;
-        else if (pass == 1 && only_a) target = 2;
-        if (target < 3) cand[target].push_back(i);
-        else { todo.push_back(i); b->timing.retried_gaps++; }
-        continue;
-      }
-      SubView& v = views[i];
-      v.out = &go;
-      v.st = (const SubRec*)td->subs.p + go.sub_off;
-      v.n = go.n_sub;
-      v.xp = (const uint64_t*)(v.st + go.n_sub);
-      v.n_xp = go.n_xp;
-      b->timing.xA += go.x_right; b->timing.sA += go.n_right;
-      b->timing.xB += go.x_left; b->timing.sB += go.n_states;
-      b->timing.xD += go.x_sub; b->timing.sD += go.n_sub;
-      b->timing.x_fill_lds += (uint64_t)go.x_right + go.x_left;
-      b->timing.s_fill_lds += (uint64_t)go.n_right + go.n_states;
-      b->timing.lds_tier_gaps++;
-      b->timing.log_pool_gaps += (go.flags & G2S_DEV_LOG_POOL) != 0;
-      b->timing.rs_pool_gaps += (go.flags & G2S_DEV_RS_POOL) != 0;
-    }
-    if (const char* dump = GENV("G2S_DUMP_STATS")) {  // diagnostics: one line per gap of this pass (appended)
-      if (FILE* f = fopen(dump, "a")) {
-        fprintf(f, "# pass %d: gap g flags A_steps A_rounds B_slow B_bulk cycA cycB D_slow D_bulk cycD n_right x_right n_states x_left n_sub top_level\n", pass);
-        for (uint32_t i : ids) {
-          const GapOut& o = outs[i];
-          fprintf(f, "%u %d %#x %u %u %u %u %llu %llu %u %u %llu %u %u %u %u %u %u\n", i, b->jobs[i].g, o.flags, o.stat[0], o.stat[1],
-                  o.stat[2], o.stat[3], (unsigned long long)o.stat[4] << 8, (unsigned long long)o.stat[5] << 8, o.stat[6] & 0xFFFF,
-                  o.stat[6] >> 16, (unsigned long long)o.stat[7] << 8, o.n_right, o.x_right, o.n_states, o.x_left, o.n_sub, o.top_level);
-        }
-        fclose(f);
-      }
-    }
-    if (GENV("G2S_DEBUG")) {  // the slowest gaps of the LDS tier and why
-      std::vector<uint32_t> ord(ids);
-      std::sort(ord.begin(), ord.end(), [&](uint32_t a, uint32_t c) {
-        return outs[a].stat[4] + outs[a].stat[5] + outs[a].stat[7] > outs[c].stat[4] + outs[c].stat[5] + outs[c].stat[7]; });
-      for (size_t q = 0; q < ord.size() && q < 4; q++) {
-        const GapOut& o = outs[ord[q]];
-        fprintf(stderr, "[g2s] pass %d slow gap %u: g %d | A per-level %u bulk %u kcyc %u | B per-level %u bulk %u kcyc %u | D1 per-level %u bulk %u kcyc %u | xA %u xB %u xD %u | right set %u states %u final_d %d top level %u flags %#x count %d\n",
-                pass, ord[q], b->jobs[ord[q]].g, o.stat[0], o.stat[1], o.stat[4] >> 2, o.stat[2], o.stat[3], o.stat[5] >> 2,
-                o.stat[6] & 0xFFFF, o.stat[6] >> 16, o.stat[7] >> 2, o.x_right, o.x_left, o.x_sub, o.n_right, o.n_states,
-                o.final_d, o.top_level, o.flags, o.c_count);
-      }
-    }
-  }
-  std::sort(todo.begin(), todo.end());
-  // gaps that outgrew the LDS tier are known to branch: start them with 8x tables
-  uint64_t scale = (lds_ids.empty() && late1.empty() && late2.empty()) ? 1 : 8;
+  // ---- the fallback (fill_kernels.hip): what the segment tiers did not finish, and every gap where they are closed
+  // (a graph of 2^28 - 1 k-mers or more, -fuz > 31, D >= 32767, G2S_NO_SEG_TIER=1), in gap order, with per-gap
+  // tables in HBM that grow 8x for the gaps that overflow them
+  std::vector<uint32_t> todo;
+  for (size_t i = 0; i < n; i++)
+    if (!b->jobs[i].bad_flank && !seg_done[i]) todo.push_back((uint32_t)i);
+  uint64_t scale = 1;
   while (!todo.empty()) {
     std::vector<uint32_t> next_todo;
     size_t pos = 0;
@@ -2683,7 +2468,7 @@ int batch_stage1(g2s_batch* b, bool analyze, g2s_result* results) {
       }
       TierData* td = take_tier(s, b->tiers.size());
       b->tiers.push_back(td);
-      int rc = run_tier(b, group, scale, max_states, td, false);
+      int rc = run_hbm_tier(b, group, scale, max_states, td);
       if (rc != G2S_OK) return rc;
       const GapOut* outs = (const GapOut*)td->outs.p;
       // this tier's kernel emits 32-byte records with the parents by GATB slot: convert them

@@ -1,8 +1,8 @@
 // gap2seq_amd/csrc/seg_tables.hip — the table the segment tier (fill_seg.hip) walks unitigs
 // with: rem[v] = how many further unitig-internal steps the oriented node v can take in its
 // walking direction (even orientation: ids grow by 2 per step, odd: shrink; dbg.hpp).  One
-// 4-byte load then tells a wave how long a whole run of DP states is, where the LDS tier
-// reads words of the unitig-start bitmap level by level.
+// 4-byte load then tells a wave how long a whole run of DP states is, where a level-by-level
+// search reads words of the unitig-start bitmap at every level.
 //
 // Built on the device from the unitig-start bitmap that is already there (bit i set = the
 // edge 2(i-1) -> 2i is not unitig-internal), one wave per 64-bit word: lane b answers for

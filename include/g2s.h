@@ -293,15 +293,15 @@ typedef struct g2s_timing {
   uint64_t fill_bytes;    /* sum over gaps of fill_len                              */
   uint32_t launches_left_dp; /* >1 when overflowing gaps were retried with larger tables */
   uint32_t retried_gaps;
-  /* LDS tier (kernels g2s_fill_lds = phases A-C fused, g2s_extract_lds = D1) */
+  /* retired tier (round 1's level-by-level kernels in LDS), kept for the layout: always zero */
   double ms_fill_lds;
   double ms_extract_lds;
-  uint64_t x_fill_lds;       /* expansions (A+B) of the gaps that completed in the LDS tier */
-  uint64_t s_fill_lds;       /* states set (A+B) by those gaps */
-  uint32_t lds_tier_gaps;    /* gaps that completed in the LDS tier */
-  uint32_t lds_launches;     /* launches of g2s_fill_lds (2 when a second pass with larger LDS tables ran) */
-  uint32_t log_pool_gaps;    /* gaps whose state log moved to a chunk of the launch's log pool */
-  uint32_t rs_pool_gaps;     /* gaps whose right set moved from LDS to a chunk of the launch's spill pool */
+  uint64_t x_fill_lds;
+  uint64_t s_fill_lds;
+  uint32_t lds_tier_gaps;
+  uint32_t lds_launches;
+  uint32_t log_pool_gaps;
+  uint32_t rs_pool_gaps;
   double ms_prepare;         /* g2s_fill_batch / g2s_team_fill: flank k-mer -> node resolution + descriptor upload
                                 (g2s_batch_prepare), inside ms_total; summed over sessions for a team */
   /* segment tier (kernel g2s_fill_seg = phases A-D1 over unitig segments, fill_seg.hip) */

@@ -86,7 +86,7 @@ class Gap:
 
 def right_set(tb, gap):
     """Phase A (:871-982): k-mer indices within right_half predecessor steps of a right-flank
-    seed (seed j enters at depth j).  The tier keeps phase A of the LDS tier; only the set matters."""
+    seed (seed j enters at depth j).  Only the set matters."""
     INF = 1 << 60
     depth = {}
     frontier = []

@@ -87,11 +87,11 @@ def test_edge_ladders_route_by_the_kernels_own_counts(product, monkeypatch, tmp_
         assert res[i].phaseC_count == _want(name).get("count", cases.MAX_PATHS), name
 
 
-@pytest.fixture(params=["seg", "seg1", "res", "segx", "lds", "hbm"])
+@pytest.fixture(params=["seg", "seg1", "res", "segx", "hbm"])
 def edge_tier(request, monkeypatch):
     """The kernel tiers of test_gpu_parity's `tier`, and the segment tier on one wave per gap ("seg1": the
     kernel with the pairwise cross-check of 65 to 192 segments)."""
-    for v in ("G2S_NO_LDS_TIER", "G2S_NO_SEG_TIER", "G2S_FORCE_SEGX", "G2S_SEG_WAVES"):
+    for v in ("G2S_NO_SEG_TIER", "G2S_FORCE_SEGX", "G2S_SEG_WAVES"):
         monkeypatch.delenv(v, raising=False)
     p = request.param
     monkeypatch.setenv("G2S_RESIDENT", "1" if p == "res" else "0")
@@ -100,8 +100,6 @@ def edge_tier(request, monkeypatch):
     elif p == "segx":
         monkeypatch.setenv("G2S_FORCE_SEGX", "1")
     elif p == "hbm":
-        monkeypatch.setenv("G2S_NO_LDS_TIER", "1")
-    elif p == "lds":
         monkeypatch.setenv("G2S_NO_SEG_TIER", "1")
     return p
 
@@ -111,10 +109,9 @@ def _tier_counts(tier, tm, n):
         assert tm.seg_tier_gaps + tm.segx_tier_gaps == n and tm.segx_tier_gaps == 2, (tm.seg_tier_gaps, tm.segx_tier_gaps)
     elif tier == "segx":
         assert tm.segx_tier_gaps == n
-    elif tier == "lds":
-        assert tm.seg_tier_gaps == 0 and tm.segx_tier_gaps == 0 and tm.lds_tier_gaps + tm.retried_gaps >= n
     else:
         assert tm.seg_tier_gaps == 0 and tm.segx_tier_gaps == 0 and tm.lds_tier_gaps == 0
+        assert tm.launches_left_dp >= 1
     if tier == "res":
         assert tm.resident_launches == 1 and tm.resident_fallbacks == 0
 
@@ -126,6 +123,22 @@ def test_edge_ladders_equal_the_oracle_on_every_tier(product, oracle, edge_tier)
     c, f, tm, _, _ = _check_batch(product, oracle, seqs, K, gaps, E)
     assert c == len(gaps)
     _tier_counts(edge_tier, tm, len(gaps))
+
+
+def test_segment_tier_overflows_are_finished_by_the_hbm_tier(product, oracle, monkeypatch):
+    """Without the large variant the two planted overflows (seg513, rs257) leave the segment tier with their flags
+    and go straight to the HBM tier, at odd k as at even k: every gap of the list equals the oracle."""
+    for v in ("G2S_NO_SEG_TIER", "G2S_FORCE_SEGX", "G2S_SEG_WAVES"):
+        monkeypatch.delenv(v, raising=False)
+    monkeypatch.setenv("G2S_RESIDENT", "0")
+    monkeypatch.setenv("G2S_NO_SEGX_TIER", "1")
+    seqs, gaps, idx = cases.edge_ladder_list(NAMES, pad=100)
+    c, f, tm, _, _ = _check_batch(product, oracle, seqs, K, gaps, E)
+    assert tm.seg_tier_gaps == len(gaps) - 2
+    assert tm.segx_tier_gaps == 0 and tm.lds_tier_gaps == 0
+    assert tm.launches_left_dp >= 1
+    assert tm.watchdog_gaps == 0
+    assert c == len(gaps)
 
 
 COUNT_LADDERS = ["paths2^29", "paths2^30", "paths2^31", "seg64", "seg65"]
@@ -237,17 +250,15 @@ def _deep_ladder():
     return lad
 
 
-@pytest.mark.parametrize("tier", ["default", "segx", "lds", "hbm"])
+@pytest.mark.parametrize("tier", ["default", "segx", "hbm"])
 def test_depth_limit_of_the_segment_tiers(product, oracle, monkeypatch, tier):
     """D = 32766 is the deepest gap the segment tiers take (16-bit depths, 0x7FFF / 0x8000 reserved); 32767 and
-    32768 go to the level-by-level LDS tier, or the HBM tier without it.  Equal to the oracle on every path."""
+    32768 go to the HBM tier.  Equal to the oracle on every path."""
     monkeypatch.setenv("G2S_RESIDENT", "0")
     if tier == "segx":
         monkeypatch.setenv("G2S_FORCE_SEGX", "1")
-    elif tier == "lds":
-        monkeypatch.setenv("G2S_NO_SEG_TIER", "1")
     elif tier == "hbm":
-        monkeypatch.setenv("G2S_NO_LDS_TIER", "1")
+        monkeypatch.setenv("G2S_NO_SEG_TIER", "1")
     lad = _deep_ladder()
     gaps = []
     for D in (32766, 32767, 32768):
@@ -259,24 +270,23 @@ def test_depth_limit_of_the_segment_tiers(product, oracle, monkeypatch, tier):
         c, f, tm, _, _ = _check_batch(product, oracle, lad["seqs"], K, gaps, E, skip, allp)
         assert c == f == 3 and tm.watchdog_gaps == 0
         if tier == "default":
-            assert (tm.seg_tier_gaps, tm.segx_tier_gaps, tm.lds_tier_gaps) == (1, 0, 2)
+            assert (tm.seg_tier_gaps, tm.segx_tier_gaps, tm.lds_tier_gaps) == (1, 0, 0)
         elif tier == "segx":
-            assert (tm.seg_tier_gaps, tm.segx_tier_gaps, tm.lds_tier_gaps) == (0, 1, 2)
-        elif tier == "lds":
-            assert (tm.seg_tier_gaps, tm.segx_tier_gaps, tm.lds_tier_gaps) == (0, 0, 3)
+            assert (tm.seg_tier_gaps, tm.segx_tier_gaps, tm.lds_tier_gaps) == (0, 1, 0)
         else:
             assert (tm.seg_tier_gaps, tm.segx_tier_gaps, tm.lds_tier_gaps) == (0, 0, 0)
+        assert tm.launches_left_dp >= 1
 
 
 @pytest.mark.parametrize("tier", ["default", "segx", "hbm"])
 def test_fuz_31_and_32(product, oracle, monkeypatch, tier):
-    """lmf, rmf = 31 is the last fuz the segment tiers hold (32 seeds, 32 targets in lanes); lmf = 32 goes to the
-    LDS tier, rmf = 32 past its 32 targets (LDS_TG) to the HBM tier."""
+    """lmf, rmf = 31 is the last fuz the segment tiers hold (32 seeds, 32 targets in lanes); lmf = 32 or rmf = 32 goes
+    to the HBM tier."""
     monkeypatch.setenv("G2S_RESIDENT", "0")
     if tier == "segx":
         monkeypatch.setenv("G2S_FORCE_SEGX", "1")
     elif tier == "hbm":
-        monkeypatch.setenv("G2S_NO_LDS_TIER", "1")
+        monkeypatch.setenv("G2S_NO_SEG_TIER", "1")
     lad = cases.bubble_ladder(202, K, 5, 32, lead=100, tail=100, fuz=32)
     g0 = lad["gap"]
     gaps = []
@@ -286,8 +296,9 @@ def test_fuz_31_and_32(product, oracle, monkeypatch, tier):
         c, f, tm, _, _ = _check_batch(product, oracle, lad["seqs"], K, gaps, E, skip, allp)
         assert c == f == 4 and tm.watchdog_gaps == 0
         if tier == "default":
-            assert (tm.seg_tier_gaps, tm.segx_tier_gaps, tm.lds_tier_gaps, tm.retried_gaps) == (1, 0, 1, 0)
+            assert (tm.seg_tier_gaps, tm.segx_tier_gaps, tm.lds_tier_gaps, tm.retried_gaps) == (1, 0, 0, 0)
         elif tier == "segx":
-            assert (tm.seg_tier_gaps, tm.segx_tier_gaps, tm.lds_tier_gaps) == (0, 1, 1)
+            assert (tm.seg_tier_gaps, tm.segx_tier_gaps, tm.lds_tier_gaps) == (0, 1, 0)
         else:
             assert (tm.seg_tier_gaps, tm.segx_tier_gaps, tm.lds_tier_gaps) == (0, 0, 0)
+        assert tm.launches_left_dp >= 1

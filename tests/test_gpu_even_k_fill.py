@@ -12,7 +12,7 @@ from test_gpu_parity import _check_batch, _gaps, _result_tuple
 pytestmark = pytest.mark.gpu
 
 INVALID = 0xFFFFFFFF
-PATH_VARS = ("G2S_RESIDENT", "G2S_SEG_WAVES", "G2S_FORCE_SEGX", "G2S_DEVICE_D2", "G2S_NO_SEG_TIER", "G2S_NO_LDS_TIER",
+PATH_VARS = ("G2S_RESIDENT", "G2S_SEG_WAVES", "G2S_FORCE_SEGX", "G2S_DEVICE_D2", "G2S_NO_SEG_TIER",
              "G2S_HOST_BUILD", "G2S_NO_SEGX_TIER", "G2S_HOST_D2")
 PATHS = ("host", "resident", "waves1", "waves2", "segx", "resident_d2")
 
@@ -31,7 +31,6 @@ def _set_path(monkeypatch, path):
         monkeypatch.setenv("G2S_DEVICE_D2", "1")
     elif path == "hbm":  # what every even-k list ran on before
         monkeypatch.setenv("G2S_NO_SEG_TIER", "1")
-        monkeypatch.setenv("G2S_NO_LDS_TIER", "1")
 
 
 def _check_path(path, tm, n):

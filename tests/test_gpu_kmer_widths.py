@@ -12,7 +12,7 @@ from test_gpu_parity import _check_batch, _compare_with_oracle_in_parallel, _gap
 
 pytestmark = pytest.mark.gpu
 
-LOOKUP_VARS = ("G2S_RESIDENT", "G2S_HOST_LOOKUP", "G2S_FORCE_SEGX", "G2S_NO_LDS_TIER", "G2S_NO_SEG_TIER", "G2S_HOST_BUILD",
+LOOKUP_VARS = ("G2S_RESIDENT", "G2S_HOST_LOOKUP", "G2S_FORCE_SEGX", "G2S_NO_SEG_TIER", "G2S_HOST_BUILD",
                "G2S_DEBUG")
 
 

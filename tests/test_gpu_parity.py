@@ -141,24 +141,39 @@ def _check_batch(product, oracle, seqs, k, gaps, e, skip=False, allp=True, seed=
     return compared, filled, tm, xb, sb
 
 
-@pytest.fixture(params=["seg", "res", "segx", "lds", "hbm"])
+def _set_tier(param, monkeypatch):
+    for v in ("G2S_NO_SEG_TIER", "G2S_NO_SEGX_TIER", "G2S_FORCE_SEGX"):
+        monkeypatch.delenv(v, raising=False)
+    monkeypatch.setenv("G2S_RESIDENT", "1" if param == "res" else "0")
+    if param == "segx":
+        monkeypatch.setenv("G2S_FORCE_SEGX", "1")
+    elif param == "hbm":
+        monkeypatch.setenv("G2S_NO_SEG_TIER", "1")
+    elif param == "lds":
+        monkeypatch.setenv("G2S_NO_SEGX_TIER", "1")
+    return param
+
+
+@pytest.fixture(params=["seg", "res", "segx", "hbm"])
 def tier(request, monkeypatch):
     """All kernel tiers: the segment tier (default: the search over unitig segments) with phase D on the host
     ("seg") and with the whole list finished on the device ("res": resident mode, d3_device.hip), its large
-    variant (what a gap takes when it outgrows the LDS-resident capacities), the LDS tier (level by
-    level, round 1's kernel: the fallback behind both) and the general tier with per-gap tables in
-    HBM (the last resort)."""
-    monkeypatch.delenv("G2S_NO_LDS_TIER", raising=False)
-    monkeypatch.delenv("G2S_NO_SEG_TIER", raising=False)
-    monkeypatch.delenv("G2S_FORCE_SEGX", raising=False)
-    monkeypatch.setenv("G2S_RESIDENT", "1" if request.param == "res" else "0")
-    if request.param == "segx":
-        monkeypatch.setenv("G2S_FORCE_SEGX", "1")
-    elif request.param == "hbm":
-        monkeypatch.setenv("G2S_NO_LDS_TIER", "1")
-    elif request.param == "lds":
-        monkeypatch.setenv("G2S_NO_SEG_TIER", "1")
-    return request.param
+    variant (what a gap takes when it outgrows the LDS-resident capacities) and the general tier with
+    per-gap tables in HBM (the fallback behind both)."""
+    return _set_tier(request.param, monkeypatch)
+
+
+@pytest.fixture(params=["seg", "res", "segx", "lds", "hbm"])
+def tier_and_fallback_route(request, monkeypatch):
+    """The tiers of `tier`, and as "lds" (the leg's name from when the level-by-level LDS tier stood there) the route
+    that tier's gaps take now: the segment tier without its large variant (G2S_NO_SEGX_TIER=1), so that a gap which
+    outgrows it goes straight to the HBM tier."""
+    return _set_tier(request.param, monkeypatch)
+
+
+def _route_counts(tier, tm):
+    if tier == "lds":
+        assert tm.segx_tier_gaps == 0 and tm.lds_tier_gaps == 0 and tm.watchdog_gaps == 0
 
 
 @pytest.mark.parametrize("seed", range(12))
@@ -179,7 +194,7 @@ def test_toy_graphs_all_modes(product, oracle, seed, tier):
 
 
 @pytest.mark.parametrize("k,length", [(5, 60), (5, 100), (7, 200)])
-def test_small_k_without_strand_collisions(product, oracle, k, length, tier):
+def test_small_k_without_strand_collisions(product, oracle, k, length, tier_and_fallback_route):
     """k = 5 and 7 on genomes over {A, C} (cases.one_strand_genome): no k-mer meets its reverse strand, so the
     oracle sees no Q7 case and EVERY gap is compared bit for bit — dense graphs, closures made of cycles,
     counts that saturate (on the toy graphs above nearly every gap at these k is a Q7 case and only its flag
@@ -235,7 +250,7 @@ def test_golden_vectors_on_gpu(product):
 
 
 @pytest.mark.parametrize("variant", [0, 1, 2, 3])
-def test_k31_default_parameters(product, oracle, variant, tier):
+def test_k31_default_parameters(product, oracle, variant, tier_and_fallback_route):
     """k=31, -fuz 10, -dist-error 500 on a 200 kbp genome: V0 plain, V1 repeats,
     V2 bubbles, V3 both; device work counters equal the oracle's."""
     reads = product.G2S.synth_genome(200000, variant, 20240101)
@@ -244,6 +259,7 @@ def test_k31_default_parameters(product, oracle, variant, tier):
     c, f, tm, xb, sb = _check_batch(product, oracle, seqs, 31, gaps, 500)
     assert c == 80 and f >= 70
     assert (tm.xB, tm.sB) == (xb, sb)
+    _route_counts(tier_and_fallback_route, tm)
 
 
 def test_wide_kmers_k63_and_even_k(product, oracle):
@@ -257,19 +273,20 @@ def test_wide_kmers_k63_and_even_k(product, oracle):
         assert c >= 25 and f >= 15
 
 
-def test_deep_dp_dist_error_2000(product, oracle, tier):
+def test_deep_dp_dist_error_2000(product, oracle, tier_and_fallback_route):
     """BASELINE config 5 shape (wide rows): -dist-error 2000, gaps of 2-5 kbp, few gaps."""
     reads = product.G2S.synth_genome(300000, 3, 20240101)
     seqs = [ln for ln in reads.splitlines() if not ln.startswith(">")]
     gaps = _parse_scaffolds(product.G2S.synth_gaps(reads, 31, 10, 16, 2000, 5000, 5))
-    c, f, _, _, _ = _check_batch(product, oracle, seqs, 31, gaps, 2000)
+    c, f, tm, _, _ = _check_batch(product, oracle, seqs, 31, gaps, 2000)
     assert c == 16 and f >= 12
+    _route_counts(tier_and_fallback_route, tm)
 
 
 @pytest.mark.parametrize("lmf,rmf", [(31, 31), (40, 40), (3, 25), (25, 0)])
 def test_fuz_extremes(product, oracle, lmf, rmf):
-    """Flank fuzz at and beyond what the LDS tier holds (32 target k-mers): -fuz 31 stays in the
-    LDS tier, -fuz 40 takes the HBM tier; asymmetric values as `execute` produces them near
+    """Flank fuzz at and beyond what the segment tiers hold (32 target k-mers): -fuz 31 stays in the
+    segment tier, -fuz 40 takes the HBM tier; asymmetric values as `execute` produces them near
     record ends (:349,360)."""
     reads = product.G2S.synth_genome(120000, 3, 20240101)
     seqs = [ln for ln in reads.splitlines() if not ln.startswith(">")]
@@ -316,11 +333,11 @@ def test_table_overflow_retry_and_memory_verdict(product, oracle):
     gaps = _parse_scaffolds(product.G2S.synth_gaps(reads, 31, 10, 120, 200, 1000, 3))
     c, f, tm, _, _ = _check_batch(product, oracle, seqs, 31, gaps, 500)
     assert c == 120
-    os.environ["G2S_NO_LDS_TIER"] = "1"
+    os.environ["G2S_NO_SEG_TIER"] = "1"
     try:
         c, f, tm, _, _ = _check_batch(product, oracle, seqs, 31, gaps, 500)
     finally:
-        del os.environ["G2S_NO_LDS_TIER"]
+        del os.environ["G2S_NO_SEG_TIER"]
     assert c == 120
     pg = product.Graph.from_seqs(seqs, 31, 1)
     sess = product.Session(pg, 0, d_err=500, max_mem=1 << 16)  # 1024 states per gap
@@ -346,7 +363,7 @@ def test_scaffold_mode_fasta_and_log_identical(product, oracle):
     pg.free()
 
 
-def test_scaffold_mode_many_records_vs_oracle(product, oracle, tier):
+def test_scaffold_mode_many_records_vs_oracle(product, oracle, tier_and_fallback_route):
     """Multi-gap scaffolds with close gaps (right_fuz coupling), k < fuz (left_max_fuz
     coupling -> batch barrier), lower-case n runs."""
     for k, fuz, e in ((11, 4, 30), (5, 8, 20), (21, 10, 60)):
@@ -443,16 +460,11 @@ def test_log_keeps_the_references_max_mem_line_whatever_budget_applies(product, 
         pg.free()
 
 
-@pytest.mark.parametrize("which", ["res", "seg", "lds"])
+@pytest.mark.parametrize("which", ["res", "seg"])
 def test_c3_gap_list_on_the_branching_genome_vs_oracle(product, oracle, which, monkeypatch):
     """BASELINE config 3's list length (10 000 gaps, 3 Mbp, k=31, -fuz 10, -dist-error 500) on
     the V3 genome (repeats + bubbles), gap by gap against the oracle.  Segment tier: every gap
-    of this list fits its capacities (one launch, nothing left for the other tiers).  LDS tier
-    alone (G2S_NO_SEG_TIER): at this list length the LDS share per gap is at its smallest,
-    right sets spill to the launch's pool in HBM and the few repeat-rich gaps whose state log
-    outgrows its slice move to the log pool; both must have happened, in a single launch."""
-    if which == "lds":
-        monkeypatch.setenv("G2S_NO_SEG_TIER", "1")
+    of this list fits its capacities (one launch, nothing left for the other tiers)."""
     monkeypatch.setenv("G2S_RESIDENT", "1" if which == "res" else "0")
     reads = product.G2S.synth_genome(3000000, 3, 20240101)
     scaff = product.G2S.synth_gaps(reads, 31, 10, 10000, 200, 1000, 20240103)
@@ -467,12 +479,8 @@ def test_c3_gap_list_on_the_branching_genome_vs_oracle(product, oracle, which, m
         # left to the host's threads)
         assert tm.host_finished_gaps <= 5
         assert tm.draw_dependent_gaps > 100
-    if which in ("seg", "res"):
-        assert tm.seg_tier_gaps == 10000 and tm.seg_launches == 1 and tm.lds_launches == 0
-        assert 100000 < tm.seg_segments < 300000  # ~17 segments per gap for ~1000 DP states
-    else:
-        assert tm.lds_tier_gaps == 10000 and tm.lds_launches == 1
-        assert tm.rs_pool_gaps > 0 and tm.log_pool_gaps > 0
+    assert tm.seg_tier_gaps == 10000 and tm.seg_launches == 1 and tm.lds_launches == 0
+    assert 100000 < tm.seg_segments < 300000  # ~17 segments per gap for ~1000 DP states
 
 
 def test_multi_rank_bench_path(product, tmp_path):
@@ -978,7 +986,7 @@ def test_fuzz_regressions(product, oracle, idx, monkeypatch):
     gaps = cases.cut_gaps(cfg["cseed"], seqs[0], k, fuz=cfg["fuz"], ngaps=cfg["ngaps"], min_len=cfg["min_len"],
                           max_len=cfg["max_len"], d_err=cfg["d_err"])
     if cfg["hbm_tier"]:
-        monkeypatch.setenv("G2S_NO_LDS_TIER", "1")
+        monkeypatch.setenv("G2S_NO_SEG_TIER", "1")
     if cfg.get("force_segx"):  # (every gap through the large variant of the segment tier, on the host path)
         monkeypatch.setenv("G2S_FORCE_SEGX", "1")
         monkeypatch.setenv("G2S_RESIDENT", "0")

@@ -30,8 +30,8 @@ IN_FLIGHT = False  # (--in-flight)
 
 
 def draw_big(rng):
-    """Long gap lists and deep gaps: small LDS shares, the right-set spill pool, passes 1 and 2,
-    gaps that start in a later pass, the HBM tier as the last resort."""
+    """Long gap lists and deep gaps: lists that fill the chip, the large variant of the segment tier, the HBM tier
+    behind it."""
     length = rng.choice([300000, 1000000])
     units = length // 10000
     deep = rng.random() < 0.4
@@ -89,9 +89,9 @@ def run(cfg):
     gaps = cases.cut_gaps(cfg["cseed"], seqs[0], k, fuz=cfg["fuz"], ngaps=cfg["ngaps"], min_len=cfg["min_len"],
                           max_len=cfg["max_len"], d_err=cfg["d_err"])
     if cfg["hbm_tier"]:
-        os.environ["G2S_NO_LDS_TIER"] = "1"
+        os.environ["G2S_NO_SEG_TIER"] = "1"
     else:
-        os.environ.pop("G2S_NO_LDS_TIER", None)
+        os.environ.pop("G2S_NO_SEG_TIER", None)
     return tp._check_batch(product, oracle_lib, seqs, k, gaps, cfg["d_err"], cfg["skip"], cfg["allp"],
                            seed=cfg["randseed"], run_product=in_flight_runner(cfg) if IN_FLIGHT else None)
 
@@ -190,7 +190,7 @@ def explain(cfg):
     gaps = cases.cut_gaps(cfg["cseed"], seqs[0], k, fuz=cfg["fuz"], ngaps=cfg["ngaps"], min_len=cfg["min_len"],
                           max_len=cfg["max_len"], d_err=cfg["d_err"])
     if cfg["hbm_tier"]:
-        os.environ["G2S_NO_LDS_TIER"] = "1"
+        os.environ["G2S_NO_SEG_TIER"] = "1"
     if os.environ.get("G2S_FUZZ_ONLY"):  # indices of the gaps to keep (the rand() stream then differs, counts do not)
         gaps = [gaps[int(x)] for x in os.environ["G2S_FUZZ_ONLY"].split(",")]
     og = oracle_lib.OracleGraph(seqs, k, 1)

@@ -25,7 +25,7 @@ os.environ["G2S_SEG_DUMP"] = dump
 pg = P.Graph.from_seqs(seqs, k, 1)
 sess = P.Session(pg, 0, d_err=e, randseed=1)
 res, tm = sess.fill_batch([P.Gap(g["left"], g["right"], g["gap_len"], g["lmf"], g["rmf"]) for g in gaps], True)
-print("seg tier gaps", tm.seg_tier_gaps, "of", len(gaps), "lds tier", tm.lds_tier_gaps, "segments", tm.seg_segments)
+print("seg tier gaps", tm.seg_tier_gaps, "of", len(gaps), "large variant", tm.segx_tier_gaps, "HBM launches", tm.launches_left_dp, "segments", tm.seg_segments)
 tb = M.Tables(P, pg)
 cur = None
 dev = {}
