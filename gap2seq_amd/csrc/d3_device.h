@@ -84,6 +84,8 @@ struct D3Summary {
   uint32_t traced_gaps;     // gaps whose fill kernel's wave wrote text and record itself (G2S_DEVA_TRACED)
   uint32_t spec_gaps;       // gaps whose fill kernel's wave wrote a guess (G2S_DEVA_SPEC); how much of them the trace kernel sent
                             // again: word 1 of each of the 64 fill-byte counters' lines (groups of 64 bases compared | sent << 32)
+  uint32_t handoff_gaps;    // gaps that may be the host's to finish (GI_HOST, or listed for g2s_d2_*): on the short route their
+                            // workgroups of the trace kernel are the ones that count themselves in handoff_waves
 };
 static_assert(sizeof(D3Summary) <= 512, "the lap stamps live at byte 512 of the summary's slot");
 
@@ -184,6 +186,8 @@ hipError_t launch_rand_fill(hipStream_t st, uint32_t* rnd_all, const RandTables&
 //   g2s_d3_handoff every gap's first draw and draw count; what the host needs to finish the gaps whose closure it
 //                  analyses, into pinned memory (*side.count says when: the host polls it)
 //   g2s_d3_trace   one wave per gap: the traceback, fill text and result record; the last wave copies the summary
+// A list of up to 768 gaps on one session (no ev_chain to record, one group) has no chain or hand-off kernel: the trace
+// kernel's workgroups walk the chain themselves and hand their own gaps over (g2s_d3_trace<4, true>; G2S_D3_BACK=1: not).
 // With P.restart (a set list) the kernels between the fill kernel and the trace kernel are one: g2s_d3_restart — the
 // classes, every gap's draw count from value 0 and the hand-off; ev_chain is not recorded and W.link not written.
 // The same in three steps, for a list whose groups stay on the GPUs that filled them (one session per GPU, every one
@@ -228,5 +232,9 @@ hipError_t launch_d3(hipStream_t st, const D3Params& P, const D3Work& W, const G
 hipError_t test_d3_tables(const uint32_t* segs, uint32_t nsegs, int32_t n_len, int32_t len0, int32_t len1, uint32_t start_seg,
                           const uint32_t* rnd, uint64_t rnd_cap, uint32_t base, uint32_t R, uint32_t dmin, uint32_t dspread,
                           uint16_t* entries, uint8_t* bad, uint32_t* anomalies);
+
+// TEST HOOK (g2s_test_d3_chain_launches): how many lists this process has queued on the short route — launch_d3 without
+// g2s_d3_back, the chain walked by the trace kernel's workgroups
+uint64_t d3_chain_launches();
 
 }  // namespace g2s

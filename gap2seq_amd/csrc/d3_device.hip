@@ -27,7 +27,8 @@
 //                  every draw-dependent gap;
 //   g2s_d3_handoff every gap's first draw and draw count (second half of D3Trace), a slot in pinned memory for the
 //                  gaps whose closure the host analyses.  (Short lists: one launch g2s_d3_back for the three, the
-//                  tables and the chain in LDS.)
+//                  tables and the chain in LDS; lists of up to 768 gaps on one session: no launch at all — every
+//                  workgroup of g2s_d3_trace<4, true> walks the chain up to its own gap, launch_d3.)
 //   g2s_d3_trace   one wave per gap: the traceback over the closure segments (post.cpp: seg_traceback is
 //                  the host version and the reference for every branch here) as a per-segment choice of parent
 //                  (all lanes: the draw made at a depth does not depend on the path), the chain through those by jump tables, and a
@@ -44,6 +45,7 @@
 #include <hip/hip_ext.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cstddef>
 #include <cstdlib>
 #include <cstring>
@@ -131,7 +133,7 @@ __device__ __forceinline__ uint32_t d3_classify_body(const D3Params& P, const D3
                                                      unsigned long long* red, bool one_wg) {
   const uint32_t n = P.n;
   unsigned long long xA = 0, sA = 0, xB = 0, sB = 0, xD = 0, sD = 0, segs = 0;
-  uint32_t unhandled = 0, seg_gaps = 0, big = 0, traced = 0, spec = 0;
+  uint32_t unhandled = 0, seg_gaps = 0, big = 0, traced = 0, spec = 0, handoff = 0;
   for (uint32_t i = first; i < n; i += stride) {
     // (the descriptor comes over the link on a short list, the record from device memory: asked for together)
     const D3Gap dg = dgaps[i];
@@ -164,6 +166,8 @@ __device__ __forceinline__ uint32_t d3_classify_body(const D3Params& P, const D3
         if (phase_d) {
           gi |= GI_PHASE_D;
           if (by_host) gi |= GI_HOST;
+          // (what g2s_d3_trace<4, true> counts its hand-off by: the same two conditions on the same words)
+          if (by_host || (!P.skip_confident && (dflags & G2S_DEVA_D2_PENDING))) handoff++;
           int lo_d = 0x7FFFFFFF, hi_d = 0;
 #pragma unroll
           for (int q = 0; q < 2; q++) {
@@ -209,6 +213,8 @@ __device__ __forceinline__ uint32_t d3_classify_body(const D3Params& P, const D3
   if ((threadIdx.x & 63u) == 0u && traced) atomicAdd(&W.sum->traced_gaps, traced);
   spec = dpp_sum(spec);
   if ((threadIdx.x & 63u) == 0u && spec) atomicAdd(&W.sum->spec_gaps, spec);
+  handoff = dpp_sum(handoff);
+  if ((threadIdx.x & 63u) == 0u && handoff) atomicAdd(&W.sum->handoff_gaps, handoff);
   const uint32_t wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
   if ((threadIdx.x & 63u) == 0u) {
     unsigned long long* r = red + wave * 8u;
@@ -1251,6 +1257,10 @@ __global__ __launch_bounds__(256) void g2s_d3_restart(const D3Params P, const D3
 // list: a thousand entries) they come into LDS in one pass and one lane walks the chain there — a chain of loads
 // from LDS instead of two passes of 16 dependent loads from memory.
 #define D3_BACK_TAB 24576u
+// (the route without g2s_d3_back, g2s_d3_trace<4, true>: gaps of a list that takes it; 16-bit entries of the tables its
+// workgroups ask for ahead of knowing how many there are)
+#define D3_CHAIN_GAPS 768u
+#define D3_CHAIN_ROOM 4096u
 __global__ __launch_bounds__(1024) void g2s_d3_back(const D3Params P, const D3Work W, const GapOut* __restrict__ outs,
                                                     const SubRec* __restrict__ sub, const uint32_t* __restrict__ Wd, uint64_t capacity,
                                                     const g2s::D3Side side) {
@@ -1320,13 +1330,21 @@ __global__ __launch_bounds__(1024) void g2s_d3_back(const D3Params P, const D3Wo
 // NW waves per gap: one on a list that fills the chip; four on a short list, whose trace kernel is its slowest gap —
 // the passes over the closure, over the stretches of the fill and over its bases are shared by the workgroup's threads,
 // the chain's jump tables too; every wave then lists the chain's segments for itself (LDS reads; the same words written by all)
-template <int NW>
+// CHAIN (a short list on one session, launch_d3: the route without g2s_d3_back): the workgroup walks the offsets' chain up to
+// its own gap itself — every workgroup the same walk, redundantly, none reading what another of this launch wrote —, hands
+// its gap to the host where that finishes it, and — only a gap that may be the host's, D3Summary.handoff_gaps of them — takes
+// a ticket (D3Summary.handoff_waves, as g2s_d3_handoff's waves do): the workgroup that completes the count publishes
+// *side.count.  The tables come into the dynamic LDS, which nothing uses yet, 16 bits an entry: chain_room such entries
+// (launch_d3 says why that many); tables beyond them are walked where they lie.
+template <int NW, bool CHAIN = false>
 __global__ __launch_bounds__(64 * NW) void g2s_d3_trace(const D3Params P, const D3Work W, GapOut* __restrict__ outs,
                                                    const SubRec* __restrict__ sub, const char* __restrict__ chu,
                                                    const char* __restrict__ chd, const uint32_t* __restrict__ rnd,
                                                    uint64_t capacity, g2s_result* __restrict__ results,
                                                    char* __restrict__ arena, uint32_t* __restrict__ summary_host,
-                                                   const g2s::D3Side side, uint32_t* __restrict__ clean_words /* or null */) {
+                                                   const g2s::D3Side side, uint32_t* __restrict__ clean_words /* or null */,
+                                                   uint32_t chain_room /* CHAIN only */) {
+  static_assert(!CHAIN || NW == 4, "the chain's loads are laid out for 256 threads");
   extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
   D3Summary* S = W.sum;
   const uint32_t i = blockIdx.x;
@@ -1346,14 +1364,6 @@ __global__ __launch_bounds__(64 * NW) void g2s_d3_trace(const D3Params P, const 
   if (P.laps && i == 0 && tid == 0) laps[13] = tk0;
   const uint32_t status = uni(S->status);
   // (every lane loads the same words: handed to the scalar unit, so that the walk below is scalar code)
-  g2s::D3Trace td;
-  {
-    const uint4 h0 = ((const uint4*)&W.tdesc[i])[0], h1 = ((const uint4*)&W.tdesc[i])[1];
-    td.arena_off = (uint64_t)uni(h0.x) | ((uint64_t)uni(h0.y) << 32);
-    td.sub_at = (uint64_t)uni(h0.z) | ((uint64_t)uni(h0.w) << 32);
-    td.gi = uni(h1.x); td.off = uni(h1.y); td.want = uni(h1.z);
-    td.lmf = (uint16_t)(uni(h1.w) & 0xFFFFu); td.nsegs = (uint16_t)(uni(h1.w) >> 16);
-  }
   struct {
     uint32_t flags, dflags, start_seg, start_t, sub_vertices, sub_edges, top_level;
     int32_t c_count, n_len, len[2], reached_j, count_s;
@@ -1366,6 +1376,100 @@ __global__ __launch_bounds__(64 * NW) void g2s_d3_trace(const D3Params P, const 
     go.c_count = (int32_t)uni((uint32_t)g.c_count); go.n_len = (int32_t)uni((uint32_t)g.n_len);
     go.len[0] = (int32_t)uni((uint32_t)g.len[0]); go.len[1] = (int32_t)uni((uint32_t)g.len[1]);
     go.reached_j = (int32_t)uni((uint32_t)g.reached_j); go.count_s = (int32_t)uni((uint32_t)g.count_s);
+  }
+  g2s::D3Trace td;
+  // (CHAIN: the gap's words of the scan, the list's of the summary; the deviation in front of the gap and its table's entry there)
+  uint32_t c_dmin = 0, c_vr = 0, c_base = 0, c_V = 0, c_dev = 0, c_step = 0, c_ns = 0, c_handoff = 0;
+  uint64_t c_T = 0, c_draws_min = 0;
+  if constexpr (!CHAIN) {
+    const uint4 h0 = ((const uint4*)&W.tdesc[i])[0], h1 = ((const uint4*)&W.tdesc[i])[1];
+    td.arena_off = (uint64_t)uni(h0.x) | ((uint64_t)uni(h0.y) << 32);
+    td.sub_at = (uint64_t)uni(h0.z) | ((uint64_t)uni(h0.w) << 32);
+    td.gi = uni(h1.x); td.off = uni(h1.y); td.want = uni(h1.z);
+    td.lmf = (uint16_t)(uni(h1.w) & 0xFFFFu); td.nsegs = (uint16_t)(uni(h1.w) >> 16);
+  } else {
+    // One round trip: the record's first half (the classes wrote it), the gap's words, the summary's, and — before V and T
+    // are known — as much of var_toff[0 .. n] and of the tables as the room takes.  (var_toff has n + 64 words, the tables
+    // G2S_D3_TABLE_BUDGET entries: what is read beyond V and T is memory of the list's own, and never looked at.)
+    const uint32_t n = P.n;
+    const uint32_t toff_len = (n + 2u) & ~1u;  // (16-bit entries in front of the tables': an even number)
+    const uint32_t tab_room = chain_room > toff_len ? min(chain_room - toff_len, D3_CHAIN_ROOM) & ~1u : 0u;
+    uint16_t* ltoff = (uint16_t*)lds;
+    uint16_t* ltab = ltoff + toff_len;
+    const uint4 h0 = ((const uint4*)&W.tdesc[i])[0];
+    uint32_t gi_w = W.ginfo[i], dm_w = W.dmin[i], vr_w = W.vrank[i], bs_w = W.base[i], ns_w = outs[i].n_xl, V_w = S->n_var;
+    c_T = S->table_entries;
+    c_draws_min = S->draws_min;
+    uint32_t hg_w = S->handoff_gaps;
+    static_assert(D3_CHAIN_ROOM <= 8u * 2u * 256u && D3_CHAIN_GAPS <= 4u * 256u, "the unrolled loads below cover the room");
+    uint32_t tw[8], ow[4];
+    const uint32_t* tab32 = (const uint32_t*)W.tab;  // (the tables start at a multiple of four bytes: d3_work_carve)
+    // (no branch around a load — an index beyond the room asks for the room's last word again —: all twelve stand in one
+    // block, in front of the first wait)
+    const uint32_t tab_last = max(tab_room / 2u, 1u) - 1u;
+#pragma unroll
+    for (uint32_t q = 0; q < 8u; q++) tw[q] = tab32[min((uint32_t)tid + 256u * q, tab_last)];
+#pragma unroll
+    for (uint32_t q = 0; q < 4u; q++) ow[q] = W.var_toff[min((uint32_t)tid + 256u * q, n)];
+#pragma unroll
+    for (uint32_t q = 0; q < 8u; q++) { const uint32_t x = (uint32_t)tid + 256u * q; if (x < tab_room / 2u) ((uint32_t*)ltab)[x] = tw[q]; }
+#pragma unroll
+    for (uint32_t q = 0; q < 4u; q++) { const uint32_t x = (uint32_t)tid + 256u * q; if (x <= n) ltoff[x] = (uint16_t)ow[q]; }
+    td.arena_off = (uint64_t)uni(h0.x) | ((uint64_t)uni(h0.y) << 32);
+    td.sub_at = (uint64_t)uni(h0.z) | ((uint64_t)uni(h0.w) << 32);
+    td.gi = uni(gi_w); td.off = 0u; td.want = 0u;
+    td.lmf = (uint16_t)(td.gi >> 16);
+    c_ns = uni(ns_w);
+    td.nsegs = (uint16_t)min(c_ns, 0xFFFFu);
+    c_dmin = uni(dm_w); c_vr = uni(vr_w); c_base = uni(bs_w); c_V = uni(V_w); c_handoff = uni(hg_w);
+    c_T = (uint64_t)uni((uint32_t)c_T) | ((uint64_t)uni((uint32_t)(c_T >> 32)) << 32);
+    c_draws_min = (uint64_t)uni((uint32_t)c_draws_min) | ((uint64_t)uni((uint32_t)(c_draws_min >> 32)) << 32);
+    __syncthreads();
+    if (!status) {
+      // (every lane of every wave walks: the same words, no hand between the waves.  A table's start does not depend on the
+      // deviation: asked for a step ahead, a step is one dependent read.  An entry is at most its gap's spread, so the
+      // deviation in front of gap v stays within R_v and every index within T; the clamps hold whatever the tables say.)
+      const bool in_lds = c_T <= (uint64_t)tab_room && c_T <= 0xFFFFull && c_V <= n;
+      const uint32_t v0 = min(c_vr, c_V), var = GI_CLASS(td.gi) == 2u && v0 < c_V ? 1u : 0u;
+      const uint32_t v_end = i + 1u == n ? c_V : v0 + var;  // (the list's last gap: to the end, for the list's total)
+      uint32_t d = 0, dv = 0, d1 = 0;
+      if (in_lds) {
+        uint32_t t = ltoff[0];
+        for (uint32_t v = 0; v < v_end; v++) {
+          const uint32_t tn = ltoff[v + 1u];
+          if (v == v0) dv = d;
+          d += ltab[min(t + d, tab_room - 1u)];
+          if (v == v0) d1 = d;
+          t = tn;
+        }
+      } else {
+        for (uint32_t v = 0; v < v_end; v++) {
+          if (v == v0) dv = d;
+          d += W.tab[min((uint64_t)W.var_toff[v] + d, (uint64_t)G2S_D3_TABLE_BUDGET - 1u)];
+          if (v == v0) d1 = d;
+        }
+      }
+      if (v_end <= v0) dv = d;
+      c_dev = uni(dv);
+      c_step = var ? uni(d1) - c_dev : 0u;
+      td.off = c_base + c_dev;
+      td.want = c_dmin + c_step;
+      if (i + 1u == n && w0) {  // (what the chain's kernel writes once a list: the total, the generator's state behind it)
+        const uint32_t d_all = uni(d);
+        const uint64_t total = c_draws_min + d_all;
+        if (lane == 0) {
+          W.dvar[c_V] = d_all;
+          __hip_atomic_store((unsigned long long*)&S->draws_total, (unsigned long long)total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        if (lane < 31) {
+          const uint32_t w = (rnd - 31)[total + (uint32_t)lane];
+          __hip_atomic_store(&S->rand_state[lane], w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          if (W.link) W.link[lane] = w;
+        }
+        __threadfence();  // (in memory before this workgroup's ticket and its counter of leave(): the last wave copies the summary)
+      }
+    }
+    __syncthreads();  // (the tables' room is the closure's and the maps' from here)
   }
   // (the gap's closure is g2s_d2_*'s to analyse, on its own stream: until its verdict word says it has — or has given
   // up —, this wave waits; then the words that kernel wrote are read again)
@@ -1383,6 +1487,54 @@ __global__ __launch_bounds__(64 * NW) void g2s_d3_trace(const D3Params P, const 
     go.sub_vertices = uni(__hip_atomic_load(&outs[i].sub_vertices, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
     go.sub_edges = uni(__hip_atomic_load(&outs[i].sub_edges, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
     if (!(v & (G2S_DEVA_RUNS | G2S_DEVA_D2_FAILED))) d2_lost = true;  // (never expected: the list goes to the host path)
+  }
+  // (CHAIN: this workgroup hands its gap over itself, behind the verdict — a closure g2s_d2_* gave up on is the host's, however late)
+  uint32_t h_it = 0xFFFFFFFFu, h_ns = 0, h_want = 0;  // the gap's item of D3Side (~0: none, or it did not fit)
+  uint64_t h_so = 0, h_ro = 0;
+  bool lost_counted = false;
+  if constexpr (CHAIN) {
+    // (the gaps that count themselves: the classes counted the same ones into the summary — ginfo's bit, or the flag of
+    // g2s_d2_*'s list, which the fill kernel set and nobody takes back.  A ticket every workgroup takes was 500 additions
+    // to one word at the kernel's start, and every later wait of the wave that took one waited for its turn too: +5 us.)
+    const bool counts = (td.gi & GI_HOST) || ((td.gi & GI_PHASE_D) && !P.skip_confident && (go.dflags & G2S_DEVA_D2_PENDING));
+    if (!status && !d2_lost) {
+      if ((td.gi & GI_PHASE_D) && !P.skip_confident && (go.dflags & G2S_DEVA_D2_PENDING) && (go.dflags & G2S_DEVA_D2_FAILED)) td.gi |= GI_HOST;
+      if (td.gi & GI_HOST) {  // (d3_handoff_body's part for one gap, on the summary's cursors)
+        __shared__ unsigned long long l_hand[3];
+        if (tid == 0) {
+          const uint32_t ns = c_ns, want = td.want;
+          unsigned long long it = atomicAdd(&S->host_items, 1ull);
+          const unsigned long long so = atomicAdd(&S->host_segs, (unsigned long long)ns);
+          const unsigned long long ro = atomicAdd(&S->host_rnd, ((unsigned long long)want + 8ull) / 8ull);  // (its draws go to the host four bits each)
+          if (it >= side.cap_items || so + ns > side.cap_segs || ro + (want + 8ull) / 8ull > side.cap_rnd || (uint64_t)td.off + want + 1ull > capacity) {
+            atomicAdd(&S->anomalies, 1u);
+            it = 0xFFFFFFFFull;
+          } else {
+            uint32_t* hi = (uint32_t*)&side.items[it];  // (without the ready word: the host takes the items largest closure first)
+            hi[0] = i; hi[1] = ns; hi[2] = (uint32_t)so; hi[3] = (uint32_t)(so >> 32); hi[4] = (uint32_t)ro; hi[5] = (uint32_t)(ro >> 32); hi[6] = want;
+            __threadfence_system();  // (the item is in host memory before the count that announces it)
+          }
+          l_hand[0] = it; l_hand[1] = so; l_hand[2] = ro;
+        }
+        __syncthreads();
+        h_it = uni((uint32_t)l_hand[0]);
+        h_so = (uint64_t)uni((uint32_t)l_hand[1]) | ((uint64_t)uni((uint32_t)(l_hand[1] >> 32)) << 32);
+        h_ro = (uint64_t)uni((uint32_t)l_hand[2]) | ((uint64_t)uni((uint32_t)(l_hand[2] >> 32)) << 32);
+        h_ns = c_ns; h_want = td.want;
+      }
+    }
+    // (the count the host polls: published by the gap that completes the ticket, or — a list without such gaps — by gap 0)
+    if (tid == 0 && (counts || (c_handoff == 0u && i == 0u))) {
+      if (d2_lost && !status) { atomicAdd(&S->anomalies, 1u); lost_counted = true; }  // (in front of the ticket: the count's bit 63 says so)
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (this workgroup's additions to the cursors have been acknowledged)
+      const unsigned int done = counts ? atomicAdd(&S->handoff_waves, 1u) + 1u : 0u;
+      if (done == c_handoff) {
+        const unsigned long long items = atomicAdd(&S->host_items, 0ull);
+        const uint32_t anomalies = atomicAdd(&S->anomalies, 0u);
+        __hip_atomic_store(side.count, (items & 0x7FFFFFFFFFFFFFFFull) | ((unsigned long long)((anomalies || status) ? 1u : 0u) << 63),
+                           __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+      }
+    }
   }
   // (given up after the hand-off looked: too late for a slot in the host's side buffers — counted, the host path's)
   if ((go.dflags & G2S_DEVA_D2_PENDING) && (go.dflags & G2S_DEVA_D2_FAILED) && !(td.gi & GI_HOST) && (td.gi & GI_PHASE_D)) d2_lost = true;
@@ -1442,7 +1594,7 @@ __global__ __launch_bounds__(64 * NW) void g2s_d3_trace(const D3Params P, const 
   };
   if (status) { leave(0u); return; }  // (the records in front of this kernel were not written: nothing below may run)
   if (d2_lost) {
-    if (tid == 0) { atomicAdd(&S->anomalies, 1u); arena[td.arena_off + td.lmf] = '\0'; }
+    if (tid == 0) { if (!lost_counted) atomicAdd(&S->anomalies, 1u); arena[td.arena_off + td.lmf] = '\0'; }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     leave(0u);
     return;
@@ -1530,12 +1682,12 @@ __global__ __launch_bounds__(64 * NW) void g2s_d3_trace(const D3Params P, const 
     // The host analyses this gap's closure (a k-mer at two depths) and traces it, while the other gaps' waves work:
     // its record, closure segments and the rand() values of its traceback go to pinned memory, then the item's
     // ready word (the host polls it; it knows from *side.count how many items to expect).
-    const uint32_t it = uni(W.host_slot[i]);
+    const uint32_t it = CHAIN ? h_it : uni(W.host_slot[i]);
     if (it != 0xFFFFFFFFu) {
-      const g2s::D3HostItem* hp = &W.hitems[it];
-      const uint64_t so = (uint64_t)uni((uint32_t)hp->seg_off) | ((uint64_t)uni((uint32_t)(hp->seg_off >> 32)) << 32);
-      const uint64_t ro = (uint64_t)uni((uint32_t)hp->rnd_off) | ((uint64_t)uni((uint32_t)(hp->rnd_off >> 32)) << 32);
-      const uint32_t ns = uni(hp->n_segs), want = uni(hp->draws);
+      const g2s::D3HostItem* hp = &W.hitems[CHAIN ? 0u : it];
+      const uint64_t so = CHAIN ? h_so : (uint64_t)uni((uint32_t)hp->seg_off) | ((uint64_t)uni((uint32_t)(hp->seg_off >> 32)) << 32);
+      const uint64_t ro = CHAIN ? h_ro : (uint64_t)uni((uint32_t)hp->rnd_off) | ((uint64_t)uni((uint32_t)(hp->rnd_off >> 32)) << 32);
+      const uint32_t ns = CHAIN ? h_ns : uni(hp->n_segs), want = CHAIN ? h_want : uni(hp->draws);
       const GapOut& g = outs[i];
       if ((uint32_t)tid < sizeof(GapOut) / 4u) ((uint32_t*)&side.outs[it])[tid] = ((const uint32_t*)&g)[tid];
       const uint4* src = (const uint4*)(sub + td.sub_at);
@@ -2118,9 +2270,13 @@ hipError_t launch_d3_sharded_trace(hipStream_t st, const D3Params& P, const D3Wo
   hipError_t e = hipFuncSetAttribute((const void*)g2s_d3_trace<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(g2s_d3_trace<1>, dim3(P.n), dim3(64), lds, st, P, W, const_cast<GapOut*>(outs), sub, lastch_up, lastch_dn, rnd_all + 31, rnd_capacity,
-                     (g2s_result*)results, arena, (uint32_t*)summary_host, side, (uint32_t*)nullptr);
+                     (g2s_result*)results, arena, (uint32_t*)summary_host, side, (uint32_t*)nullptr, 0u);
   return hipGetLastError();
 }
+
+// TEST HOOK (g2s_test_d3_chain_launches): lists of this process whose trace kernel walked the chain itself
+static std::atomic<uint64_t> chain_launches{0};
+uint64_t d3_chain_launches() { return chain_launches.load(std::memory_order_relaxed); }
 
 hipError_t launch_d3(hipStream_t st, const D3Params& P, const D3Work& W, const GapDev* gaps, const GapOut* outs,
                      const D3Gap* dgaps, const SubRec* sub, const char* lastch_up, const char* lastch_dn,
@@ -2147,7 +2303,28 @@ hipError_t launch_d3(hipStream_t st, const D3Params& P, const D3Work& W, const G
   if (!P.restart) { e = launch_tables(st, P, W, sub, rnd_all, rnd_capacity); if (e != hipSuccess) return e; }
   // (g2s_d2_* runs on a stream of its own beside the kernels above; the hand-off reads what it decided)
   if (ev_d2 && short_list && !P.restart) { e = hipStreamWaitEvent(st, ev_d2, 0); if (e != hipSuccess) return e; }
+  // A short list on one session whose draws no list in flight waits for: no g2s_d3_back — the trace kernel's workgroups walk
+  // the chain themselves (g2s_d3_trace<4, true>).  G2S_D3_BACK=1 keeps the launch (the tests compare the two routes, and so
+  // does an A/B measurement).  The tables' room in that kernel: its dynamic LDS, which holds nothing yet when the chain is
+  // walked — at least 9 KB, config 2's tables are 2 KB — and no more than D3_CHAIN_ROOM entries: every workgroup asks for
+  // the room's worth before it knows the tables' size.  (TEST HOOK G2S_TEST_CHAIN_ROOM: fewer, so that a small list's chain
+  // goes through device memory.)
+  const char* waves_s = GENV("G2S_TRACE_WAVES");  // (read per launch: the tests switch it within a process)
+  const int waves_env = waves_s ? atoi(waves_s) : 0;
+  const bool four = waves_env ? waves_env == 4 : P.n <= 768u;  // (2 000 gaps on four waves each: 1-2 % slower than on one)
+  const size_t lds = (size_t)P.seg_cap * (sizeof(SegRec) + 16) + (size_t)P.map_cap * 8 + 16;  // closure, base map, rand() values, the walk's segments
+  bool chain_in_trace = false;
+  uint32_t chain_room = 0;
+  static_assert(D3_CHAIN_GAPS <= 768u, "g2s_d3_trace<4, true> is the four-wave kernel");
+  if (!P.restart && four && P.n <= D3_CHAIN_GAPS && ev_chain == nullptr && P.group_size >= P.n && !P.base0 && !P.R0 && !P.d_in) {
+    const char* back_s = GENV("G2S_D3_BACK");
+    chain_in_trace = !(back_s && atoi(back_s) != 0);
+    const char* room_s = GENV("G2S_TEST_CHAIN_ROOM");
+    chain_room = (uint32_t)std::min<size_t>(lds / 2u, 0x7FFFFFFFu);
+    if (room_s) chain_room = std::min(chain_room, (uint32_t)std::max(atoi(room_s), 0));
+  }
   if (P.restart) (void)ev_chain;  // (no chain: the list's draws are nobody's to continue)
+  else if (chain_in_trace) (void)ev_chain;
   else if (short_list) {
     hipLaunchKernelGGL(g2s_d3_back, dim3(1), dim3(1024), 0, st, P, W, outs, sub, rnd_all, rnd_capacity, side);
     if (ev_chain) { e = hipEventRecord(ev_chain, st); if (e != hipSuccess) return e; }
@@ -2158,28 +2335,35 @@ hipError_t launch_d3(hipStream_t st, const D3Params& P, const D3Work& W, const G
     if (ev_d2) { e = hipStreamWaitEvent(st, ev_d2, 0); if (e != hipSuccess) return e; }
     hipLaunchKernelGGL(g2s_d3_handoff, dim3((P.n + 63u) / 64u), dim3(64), 0, st, P, W, outs, sub, rnd_all + 31, rnd_capacity, side);
   }
-  const size_t lds = (size_t)P.seg_cap * (sizeof(SegRec) + 16) + (size_t)P.map_cap * 8 + 16;  // closure, base map, rand() values, the walk's segments
   // (a short list: four waves per gap — the kernel is its slowest gap, and the chip has the wave slots)
-  const char* waves_s = GENV("G2S_TRACE_WAVES");  // (read per launch: the tests switch it within a process)
-  const int waves_env = waves_s ? atoi(waves_s) : 0;
-  const bool four = waves_env ? waves_env == 4 : P.n <= 768u;  // (2 000 gaps on four waves each: 1-2 % slower than on one)
-  e = hipFuncSetAttribute(four ? (const void*)g2s_d3_trace<4> : (const void*)g2s_d3_trace<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  e = hipFuncSetAttribute(chain_in_trace ? (const void*)g2s_d3_trace<4, true> : four ? (const void*)g2s_d3_trace<4> : (const void*)g2s_d3_trace<1>,
+                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) return e;
+  if (chain_in_trace) {
+    chain_launches.fetch_add(1, std::memory_order_relaxed);
+    if (ev_stop != nullptr)  // (a timed list: as below)
+      hipExtLaunchKernelGGL((g2s_d3_trace<4, true>), dim3(P.n), dim3(256), (uint32_t)lds, st, nullptr, ev_stop, 0u, P, W, const_cast<GapOut*>(outs), sub, lastch_up, lastch_dn,
+                            rnd_all + 31, rnd_capacity, (g2s_result*)results, arena, (uint32_t*)summary_host, side, clean_words, chain_room);
+    else
+      hipLaunchKernelGGL((g2s_d3_trace<4, true>), dim3(P.n), dim3(256), lds, st, P, W, const_cast<GapOut*>(outs), sub, lastch_up, lastch_dn, rnd_all + 31, rnd_capacity,
+                         (g2s_result*)results, arena, (uint32_t*)summary_host, side, clean_words, chain_room);
+    return hipGetLastError();
+  }
   if (ev_stop != nullptr) {  // (a timed list: the dispatch's own stop time — an event recorded behind the kernel is a packet of its own)
     if (four)
       hipExtLaunchKernelGGL(g2s_d3_trace<4>, dim3(P.n), dim3(256), (uint32_t)lds, st, nullptr, ev_stop, 0u, P, W, const_cast<GapOut*>(outs), sub, lastch_up, lastch_dn,
-                            rnd_all + 31, rnd_capacity, (g2s_result*)results, arena, (uint32_t*)summary_host, side, clean_words);
+                            rnd_all + 31, rnd_capacity, (g2s_result*)results, arena, (uint32_t*)summary_host, side, clean_words, 0u);
     else
       hipExtLaunchKernelGGL(g2s_d3_trace<1>, dim3(P.n), dim3(64), (uint32_t)lds, st, nullptr, ev_stop, 0u, P, W, const_cast<GapOut*>(outs), sub, lastch_up, lastch_dn,
-                            rnd_all + 31, rnd_capacity, (g2s_result*)results, arena, (uint32_t*)summary_host, side, clean_words);
+                            rnd_all + 31, rnd_capacity, (g2s_result*)results, arena, (uint32_t*)summary_host, side, clean_words, 0u);
     return hipGetLastError();
   }
   if (four)
     hipLaunchKernelGGL(g2s_d3_trace<4>, dim3(P.n), dim3(256), lds, st, P, W, const_cast<GapOut*>(outs), sub, lastch_up, lastch_dn, rnd_all + 31, rnd_capacity,
-                       (g2s_result*)results, arena, (uint32_t*)summary_host, side, clean_words);
+                       (g2s_result*)results, arena, (uint32_t*)summary_host, side, clean_words, 0u);
   else
     hipLaunchKernelGGL(g2s_d3_trace<1>, dim3(P.n), dim3(64), lds, st, P, W, const_cast<GapOut*>(outs), sub, lastch_up, lastch_dn, rnd_all + 31, rnd_capacity,
-                       (g2s_result*)results, arena, (uint32_t*)summary_host, side, clean_words);
+                       (g2s_result*)results, arena, (uint32_t*)summary_host, side, clean_words, 0u);
   return hipGetLastError();
 }
 

@@ -5386,6 +5386,9 @@ extern "C" int g2s_test_d3_tables(int device, const uint32_t* segs, uint32_t n_s
   return G2S_OK;
 }
 
+// TEST HOOK: lists of this process that took phase D3's short route (d3_device.h: d3_chain_launches)
+extern "C" uint64_t g2s_test_d3_chain_launches(void) { return d3_chain_launches(); }
+
 // TEST HOOK: the n values behind `skip` values that were drawn elsewhere — GlibcRandStream::skip, the jump by the
 // recurrence's polynomial g2s_share_end moves a rank's generator with — for comparison with g2s_test_rand_stream
 extern "C" int g2s_test_rand_skip(uint32_t seed, uint64_t skip, uint32_t n, int32_t* out) {

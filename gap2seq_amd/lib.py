@@ -218,6 +218,7 @@ _SIGS = {
     "g2s_test_d3_tables": (C.c_int, [C.c_int, C.POINTER(C.c_uint32), C.c_uint32, C.c_int32, C.c_int32, C.c_int32, C.c_uint32,
                                      C.POINTER(C.c_uint32), C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                      C.POINTER(C.c_uint16), C.POINTER(C.c_uint8), C.POINTER(C.c_uint32)]),
+    "g2s_test_d3_chain_launches": (C.c_uint64, []),
     "g2s_test_post_closure": (C.c_int, [_VP, C.POINTER(g2s_params), C.POINTER(g2s_gap), C.c_uint32,
                                         C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint64), C.c_int32, C.c_int32,
                                         C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_uint32, C.c_uint64,
@@ -1092,6 +1093,11 @@ def test_d3_tables(device, segs, n_len, len0, len1, start_seg, rnd, base, R, dmi
     _check(load_library().g2s_test_d3_tables(device, sa, len(segs), n_len, len0, len1, start_seg, ra, len(rnd), base, R, dmin,
                                              dspread, ent, bad, C.byref(anom)))
     return list(ent), list(bad), anom.value
+
+
+def test_d3_chain_launches():
+    """TEST HOOK binding: lists of this process that took phase D3's short route (the chain walked by the trace kernel)."""
+    return int(load_library().g2s_test_d3_chain_launches())
 
 
 def test_group_queue_slow(nworkers, n, group_size, slow_worker, slow_us):

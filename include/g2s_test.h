@@ -80,6 +80,11 @@ int g2s_test_d3_tables(int device, const uint32_t* segs, uint32_t n_segs, int32_
                        uint32_t start_seg, const uint32_t* rnd, uint64_t rnd_cap, uint32_t base, uint32_t R, uint32_t dmin,
                        uint32_t dspread, uint16_t* entries, uint8_t* bad, uint32_t* anomalies);
 
+/* TEST HOOK: how many lists of this process took phase D3's short route: no g2s_d3_back between the tables' kernel and
+ * the trace kernel, whose workgroups walk the offsets' chain themselves (lists of up to 768 gaps on one session, not a
+ * set list, not in flight; G2S_D3_BACK=1 keeps every list off it). */
+uint64_t g2s_test_d3_chain_launches(void);
+
 /* TEST HOOK: the host worker pool that runs the per-gap analysis and tracebacks: `rounds`
  * parallel-for rounds of `n` tasks on `threads` threads (task i adds i+1 to a per-round
  * sum); returns G2S_OK when every task of every round ran exactly once. */
