@@ -313,9 +313,7 @@ void BamFile::set_inflate_device(int device) {
   inflate_device_ = device < 0 ? -1 : device;
 }
 
-// the buffers of the device path, sized by the file's largest window
-BgzfDevice* BamFile::device_buffers() const {
-  if (dev_) return dev_.get();
+size_t BamFile::largest_window(size_t* staged, size_t* members, size_t* inflated) const {
   Stream s(*this);
   size_t max_in = 0, max_out = 0, max_members = 0;
   for (size_t b = 0; b < blk_off_.size();) {
@@ -328,6 +326,17 @@ BgzfDevice* BamFile::device_buffers() const {
     max_members = std::max(max_members, e - b);
     b = e;
   }
+  if (staged) *staged = max_in;
+  if (members) *members = max_members;
+  if (inflated) *inflated = max_out;
+  return max_out;
+}
+
+// the buffers of the device path, sized by the file's largest window
+BgzfDevice* BamFile::device_buffers() const {
+  if (dev_) return dev_.get();
+  size_t max_in = 0, max_out = 0, max_members = 0;
+  largest_window(&max_in, &max_members, &max_out);
   std::string why;
   dev_.reset(BgzfDevice::create(inflate_device_, max_in, max_out, max_members, kDeviceFront, &why));
   if (!dev_) {
@@ -430,6 +439,18 @@ bool BamFile::for_each(const std::function<bool(const BamRec&)>& fn, std::string
   }
 }
 
+uint64_t BamFile::inflated_bytes() const {
+  uint64_t total = 0;
+  for (const uint32_t isize : blk_isize_) total += isize;
+  return total;
+}
+
+uint64_t BamFile::inflate_device_bytes() const {
+  size_t max_in = 0, max_out = 0, max_members = 0;
+  largest_window(&max_in, &max_members, &max_out);
+  return BgzfDevice::device_bytes(max_in, max_out, max_members, kDeviceFront);
+}
+
 // Pass A without the walk: every window is inflated into its slot's device buffer and left there, and the row kernels
 // (bam_rows.hip) follow the inflate kernel on the same stream; the host stages window n + 1 while window n is on the
 // device, and looks at a window's member status two windows later, when its slot is needed again.
@@ -437,8 +458,9 @@ bool BamFile::for_each(const std::function<bool(const BamRec&)>& fn, std::string
 // for pass B (bam_text.hip).  A window's base is then no word boundary in general, so the row kernels are given the
 // word boundary in front of it and start that many bytes in; a record cut by a window's end is whole in memory, and in
 // place of the carry the chain's head moves by the distance between the two bases (BamRowsDevice::advance).
+// The streaming form (`sink`): the two slots as without `resident`, the rows compact and consumed window by window.
 BamRowsDevice* BamFile::rows_on_device(size_t walk_window, int* anomaly, std::string* why, bool resident, uint64_t resident_cap,
-                                       int* resident_refused) const {
+                                       int* resident_refused, const RowsSink* sink) const {
   const auto t0 = std::chrono::steady_clock::now();
   *anomaly = kRowsHip;
   if (inflate_device_ < 0 || dev_refused_) { *why = "the reader does not inflate on a device"; return nullptr; }
@@ -457,7 +479,8 @@ BamRowsDevice* BamFile::rows_on_device(size_t walk_window, int* anomaly, std::st
     b = e;
   }
   const uint64_t cap_rows = total / 36 + 1;
-  if (first_rec_ > first_bytes || max_out + dev->front() + 64 >= (size_t)INT32_MAX || cap_rows >= (uint64_t)UINT32_MAX - 1) {
+  if (sink) resident = false;
+  if (first_rec_ > first_bytes || max_out + dev->front() + 64 >= (size_t)INT32_MAX || (!sink && cap_rows >= (uint64_t)UINT32_MAX - 1)) {
     *anomaly = kRowsLimits;
     *why = "a header beyond the first window, or a file outside the row kernels' index widths";
     return nullptr;
@@ -467,7 +490,7 @@ BamRowsDevice* BamFile::rows_on_device(size_t walk_window, int* anomaly, std::st
   ask.cap = resident_cap;
   int refused = kResidentKept;
   std::unique_ptr<BamRowsDevice> R(BamRowsDevice::create(inflate_device_, dev->stream(), max_out, walk_window, dev->front(),
-                                                         cap_rows, (int32_t)ref_names_.size(), first_rec_, why, &ask, &refused));
+                                                         cap_rows, (int32_t)ref_names_.size(), first_rec_, why, &ask, &refused, sink));
   if (resident_refused) *resident_refused = refused;
   if (!R) return nullptr;
   uint8_t* const keep = R->stream_buffer();  // (null: today's two slots)

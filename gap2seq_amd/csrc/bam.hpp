@@ -17,10 +17,11 @@
 #include <string>
 #include <vector>
 
+#include "bam_rows.h"
+
 namespace g2s {
 
 class BgzfDevice;
-class BamRowsDevice;
 
 enum : uint32_t {
   BAM_PAIRED = 1, BAM_UNMAPPED = 4, BAM_MATE_UNMAPPED = 8, BAM_REVERSE = 16, BAM_READ1 = 64, BAM_READ2 = 128,
@@ -81,9 +82,20 @@ class BamFile {
   // offset in it (BamRowsDevice::stream_buffer, DeviceRows::rec_off), when it fits the cap (bam_rows.h: ResidentAsk;
   // resident_cap 0: half the free device memory alone); *resident_refused (bam_rows.h: ResidentRefused) says when it did
   // not, and the rows are then made the two-slot way.
+  // `sink` (the read route's streaming form, not with `resident`): the two-slot way with compact rows (bam_rows.h:
+  // CompactRows) handed to *sink behind every walk window's row kernels, before the window's slot is written again;
+  // no array of the result grows with the file, and a file may hold more than 2^32 records.
   BamRowsDevice* rows_on_device(size_t walk_window, int* anomaly, std::string* why, bool resident = false,
-                                uint64_t resident_cap = 0, int* resident_refused = nullptr) const;
+                                uint64_t resident_cap = 0, int* resident_refused = nullptr, const RowsSink* sink = nullptr) const;
   uint64_t rows_windows() const { return rows_windows_; }  // walk windows of the last rows_on_device
+  // the file's inflated bytes (the members' ISIZE fields summed) and the offset of the first record among them
+  uint64_t inflated_bytes() const;
+  uint64_t first_record() const { return first_rec_; }
+  // the inflated bytes of the largest window of whole members; *staged, *members, *inflated (any may be null): the
+  // largest staged deflate bytes, member count and inflated bytes of a window, each over all windows
+  size_t largest_window(size_t* staged = nullptr, size_t* members = nullptr, size_t* inflated = nullptr) const;
+  // the device memory the inflate's two slots take for this file's windows (nothing is allocated to say so)
+  uint64_t inflate_device_bytes() const;
   // test paths (g2s_test_bgzf_inflate): the host path with inflate_core.h in zlib's place; any BGZF file, no BAM header
   void set_inflate_core(bool on) { use_core_ = on; }
   bool open_bgzf(const void* bytes, size_t n, std::string* err);

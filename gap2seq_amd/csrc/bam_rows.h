@@ -4,6 +4,7 @@
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include <functional>
 #include <string>
 
 namespace g2s {
@@ -40,6 +41,23 @@ struct ResidentAsk {
 };
 enum ResidentRefused : int { kResidentKept = 0, kResidentOverCap = 1, kResidentNoMemory = 2 };
 
+// The compact rows of the read route's streaming form (bam_reads.h): of every whole record of one walk window its
+// offset relative to the window buffer's first byte (negative: a record carried in front of it) and its flag, in file
+// order, in a ring of one walk window's capacity that the next walk window overwrites.  All device memory; *n_rec and
+// *anomaly are the row kernels' control words, read on the device (after an anomaly the ring is stale).
+struct CompactRows {
+  const int32_t* off = nullptr;
+  const uint32_t* flag = nullptr;
+  const uint32_t* n_rec = nullptr;
+  const uint32_t* anomaly = nullptr;
+  uint32_t capacity = 0;  // entries of off / flag
+  void* stream = nullptr;  // the hipStream_t the row kernels run on
+};
+// what consumes a walk window's compact rows: called behind the row kernels of every walk window, it enqueues its own
+// kernels on the same stream, so that they have run before the window's slot is written again.  d_win: the window
+// buffer's first byte, with `front` readable bytes in front of it; the walk window ends `end` bytes behind it.
+using RowsSink = std::function<bool(const CompactRows& rows, const uint8_t* d_win, size_t front, size_t end, std::string* why)>;
+
 class BamRowsDevice {
  public:
   // Kernels on `stream` (a hipStream_t: the reader's own, behind its inflate kernel) for windows of at most max_window
@@ -48,9 +66,15 @@ class BamRowsDevice {
   // `ask` (may be null): one device allocation for the whole inflated stream and an offset per row beside the rows, taken
   // only when stream and rows fit within half the free device memory (and ask->cap).  When they do not, or the
   // allocation fails, the object is made without them and *resident_refused says which.
+  // `sink` (may be null; not together with `ask`): the compact form — no whole-file arrays are made, cap_rows does not
+  // apply, every walk window's rows go to the ring and then to *sink; rows() stays empty but for n.
   static BamRowsDevice* create(int device, void* stream, size_t max_window, size_t walk_window, size_t front,
                                uint64_t cap_rows, int32_t n_ref, uint64_t first_head, std::string* why,
-                               const ResidentAsk* ask = nullptr, int* resident_refused = nullptr);
+                               const ResidentAsk* ask = nullptr, int* resident_refused = nullptr,
+                               const RowsSink* sink = nullptr);
+  // the device bytes create() takes in the compact form for walk windows of `walk_window` bytes
+  static uint64_t compact_bytes(size_t walk_window);
+  static uint32_t ring_capacity_of(size_t walk_window);  // the ring's entries
   ~BamRowsDevice();
   BamRowsDevice(const BamRowsDevice&) = delete;
   BamRowsDevice& operator=(const BamRowsDevice&) = delete;
@@ -91,6 +115,8 @@ class BamRowsDevice {
   uint64_t windows_ = 0, candidates_ = 0;
   uint8_t* stream_buf_ = nullptr;
   uint64_t stream_bytes_ = 0;
+  RowsSink sink_;  // (compact form)
+  bool compact_ = false;
 };
 
 }  // namespace g2s

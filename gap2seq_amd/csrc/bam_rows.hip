@@ -19,6 +19,9 @@
 //   rows        k_rec        the chain rises in offset, so a record's index in the window is the exclusive scan of the
 //                            marks (count per workgroup, k_scan, ballot); one thread a record reads the fixed fields,
 //                            sums the CIGAR as BamRec::end_pos does and hashes both names (name_hash.h)
+// The read route's streaming form (bam_reads.h) asks for compact rows instead: k_rec_compact writes a record's offset
+// in the window buffer and its flag to a ring of the walk window's capacity, and the caller's sink consumes the ring
+// behind it on the same stream — no array grows with the file, and the row limit of 2^32 does not apply.
 // From window to window the chain's EXIT offset stays in the control block (State::head), and the bytes from there to the
 // window's end are copied in front of the next window's buffer (k_carry).  Whatever does not fit this scheme — a marked
 // candidate with a DEAD link, more candidates than the capacity, a carry longer than the room in front, a chain that
@@ -285,6 +288,15 @@ __device__ __forceinline__ void make_row(const uint8_t* __restrict__ rec, uint64
   }
 }
 
+// a whole record's index among its walk window's, from the scan of the workgroups' counts and the ballot of its wave
+// (wave_cnt: the workgroup's four wave counts, behind its barrier)
+__device__ __forceinline__ uint32_t rec_rank(const uint32_t* __restrict__ blk, const uint32_t* wave_cnt, uint64_t mask, uint32_t wave,
+                                             uint32_t lane) {
+  uint32_t rank = blk[blockIdx.x] + (uint32_t)__popcll(mask & (((uint64_t)1 << lane) - 1));
+  for (uint32_t w = 0; w < wave; w++) rank += wave_cnt[w];
+  return rank;
+}
+
 // WRITE false: blk[workgroup] = the marked candidates that are whole records; the chain's way out of the window, or
 // its dead end (State::dead, not the anomaly word itself: every wave of this launch has to pass the test at the
 // kernel's entry the same way, or a workgroup's waves would part in front of its barrier).  WRITE true: their rows.
@@ -312,10 +324,31 @@ __global__ void __launch_bounds__(kBlock) k_rec(const uint8_t* __restrict__ win,
     return;
   }
   if (!take) return;
-  uint32_t rank = blk[blockIdx.x] + (uint32_t)__popcll(mask & (((uint64_t)1 << lane) - 1));
-  for (uint32_t w = 0; w < wave; w++) rank += wave_cnt[w];
+  const uint32_t rank = rec_rank(blk, wave_cnt, mask, wave, lane);
   make_row(win + cand[i], st->row_base + rank, st, ref_id, pos, end, flag, h_own, h_mate, rec_off,
            (uint64_t)((int64_t)win_off + (int64_t)cand[i]));
+}
+
+// k_rec<true> for the compact form: of every whole record its offset in the window buffer and its flag, at its index in
+// this walk window, in the ring
+__global__ void __launch_bounds__(kBlock) k_rec_compact(const uint8_t* __restrict__ win, const State* __restrict__ st,
+                                                        const int32_t* __restrict__ cand, const uint8_t* __restrict__ mark,
+                                                        const uint8_t* __restrict__ emit, const uint32_t* __restrict__ blk,
+                                                        int32_t* __restrict__ ring_off, uint32_t* __restrict__ ring_flag,
+                                                        uint32_t ring_cap) {
+  __shared__ uint32_t wave_cnt[kWaves];
+  if (st->anomaly) return;
+  const uint32_t n = st->n_cand, tid = threadIdx.x, i = blockIdx.x * kBlock + tid, wave = tid / kWave, lane = tid % kWave;
+  const bool take = i < n && mark[i] && emit[i];
+  const uint64_t mask = __ballot(take);
+  if (lane == 0) wave_cnt[wave] = (uint32_t)__popcll(mask);
+  __syncthreads();
+  if (!take) return;
+  const uint32_t rank = rec_rank(blk, wave_cnt, mask, wave, lane);
+  if (rank < ring_cap) {
+    ring_off[rank] = cand[i];
+    ring_flag[rank] = g_ld32(win + cand[i] + 16) >> 16;
+  }
 }
 
 // the bytes from the chain's exit to the window's end, in front of the next window's buffer
@@ -359,14 +392,17 @@ namespace g2s {
 
 // the object's device allocations: freed by their destructors, the last declared first
 struct BamRowsDevice::Buffers {
-  DevMem stream_buf, rec_off, h_mate, h_own, flag, end, pos, ref_id, blk, emit, mark, j1, j0, link, cand, state;
+  DevMem stream_buf, rec_off, h_mate, h_own, flag, end, pos, ref_id, ring_flag, ring_off, blk, emit, mark, j1, j0, link, cand, state;
 };
 
 BamRowsDevice* BamRowsDevice::create(int device, void* stream, size_t max_window, size_t walk_window, size_t front,
                                      uint64_t cap_rows, int32_t n_ref, uint64_t first_head, std::string* why,
-                                     const ResidentAsk* ask, int* resident_refused) {
+                                     const ResidentAsk* ask, int* resident_refused, const RowsSink* sink) {
   const size_t walk = walk_window && walk_window < max_window ? walk_window : (max_window ? max_window : 1);
-  if (max_window + front + 64 >= (size_t)INT32_MAX || first_head > max_window || cap_rows >= (uint64_t)UINT32_MAX - 1) {
+  const bool compact = sink != nullptr;
+  if (compact) cap_rows = UINT64_MAX;  // (a walk window's rows are bounded by its candidates)
+  if (max_window + front + 64 >= (size_t)INT32_MAX || first_head > max_window || (!compact && cap_rows >= (uint64_t)UINT32_MAX - 1) ||
+      (compact && ask && ask->bytes)) {
     if (why) *why = "a file outside the row kernels' index widths";
     return nullptr;
   }
@@ -378,11 +414,13 @@ BamRowsDevice* BamRowsDevice::create(int device, void* stream, size_t max_window
   D->front_ = front;
   D->cap_rows_ = cap_rows;
   D->n_ref_ = n_ref;
+  D->compact_ = compact;
+  if (compact) D->sink_ = *sink;
   D->cap_cand_ = window_capacity(walk);
   D->max_tiles_ = (uint32_t)((walk + kTile - 1) / kTile);
   const size_t nblk = std::max<size_t>(D->max_tiles_, (D->cap_cand_ + kBlock - 1) / kBlock) + 1;
   auto make = [&]() -> bool {
-    const size_t rows = (size_t)cap_rows + 1, cc = D->cap_cand_;
+    const size_t rows = compact ? 0 : (size_t)cap_rows + 1, cc = D->cap_cand_;
     G2S_HIP_TRY(hipSetDevice(device));
     // one-pass mode: the whole inflated stream and the records' offsets, when they fit under the cap with the rows
     if (ask && ask->bytes) {
@@ -403,20 +441,33 @@ BamRowsDevice* BamRowsDevice::create(int device, void* stream, size_t max_window
         }
       }
     }
-    G2S_HIP_TRY(B.state.alloc(sizeof(State)));
-    G2S_HIP_TRY(B.cand.alloc(cc * 4));
-    G2S_HIP_TRY(B.link.alloc(cc * 4));
-    G2S_HIP_TRY(B.j0.alloc(cc * 4));
-    G2S_HIP_TRY(B.j1.alloc(cc * 4));
-    G2S_HIP_TRY(B.mark.alloc(cc));
-    G2S_HIP_TRY(B.emit.alloc(cc));
-    G2S_HIP_TRY(B.blk.alloc(nblk * 4));
-    G2S_HIP_TRY(B.ref_id.alloc(rows * 4));
-    G2S_HIP_TRY(B.pos.alloc(rows * 4));
-    G2S_HIP_TRY(B.end.alloc(rows * 8));
-    G2S_HIP_TRY(B.flag.alloc(rows * 4));
-    G2S_HIP_TRY(B.h_own.alloc(rows * 8));
-    G2S_HIP_TRY(B.h_mate.alloc(rows * 8));
+    uint64_t held = 0;  // what the allocations below ask for
+    auto take = [&held](DevMem& m, size_t bytes) {
+      held += bytes ? bytes : 16;
+      return m.alloc(bytes);
+    };
+    G2S_HIP_TRY(take(B.state, sizeof(State)));
+    G2S_HIP_TRY(take(B.cand, cc * 4));
+    G2S_HIP_TRY(take(B.link, cc * 4));
+    G2S_HIP_TRY(take(B.j0, cc * 4));
+    G2S_HIP_TRY(take(B.j1, cc * 4));
+    G2S_HIP_TRY(take(B.mark, cc));
+    G2S_HIP_TRY(take(B.emit, cc));
+    G2S_HIP_TRY(take(B.blk, nblk * 4));
+    if (compact) {
+      G2S_HIP_TRY(take(B.ring_off, cc * 4));
+      G2S_HIP_TRY(take(B.ring_flag, cc * 4));
+    }
+    G2S_HIP_TRY(take(B.ref_id, rows * 4));
+    G2S_HIP_TRY(take(B.pos, rows * 4));
+    G2S_HIP_TRY(take(B.end, rows * 8));
+    G2S_HIP_TRY(take(B.flag, rows * 4));
+    G2S_HIP_TRY(take(B.h_own, rows * 8));
+    G2S_HIP_TRY(take(B.h_mate, rows * 8));
+    if (compact && held != compact_bytes(walk)) {  // (what the streaming form counted against its limit)
+      if (why) *why = "the compact form's allocations are not what compact_bytes() says";
+      return false;
+    }
     DeviceRows& R = D->rows_;  // (the plain pointers the joins read)
     R.ref_id = B.ref_id.as<int32_t>(), R.pos = B.pos.as<int32_t>(), R.end = B.end.as<int64_t>(), R.flag = B.flag.as<uint32_t>();
     R.h_own = B.h_own.as<uint64_t>(), R.h_mate = B.h_mate.as<uint64_t>();
@@ -432,6 +483,15 @@ BamRowsDevice* BamRowsDevice::create(int device, void* stream, size_t max_window
     return nullptr;
   }
   return D;
+}
+
+uint32_t BamRowsDevice::ring_capacity_of(size_t walk_window) { return window_capacity(walk_window ? walk_window : 1); }
+
+uint64_t BamRowsDevice::compact_bytes(size_t walk_window) {
+  const uint64_t cc = window_capacity(walk_window ? walk_window : 1), tiles = (walk_window + kTile - 1) / kTile;
+  const uint64_t nblk = std::max<uint64_t>(tiles, (cc + kBlock - 1) / kBlock) + 1;
+  // (cand, link, j0, j1, the ring's two arrays; mark, emit; blk; the control block; the six empty row arrays)
+  return cc * (6 * 4 + 2) + nblk * 4 + sizeof(State) + 6 * 16;
 }
 
 BamRowsDevice::~BamRowsDevice() {
@@ -469,10 +529,21 @@ bool BamRowsDevice::window(const uint8_t* d_win, size_t start, size_t bytes, std
                        (const uint8_t*)mark, (const uint8_t*)emit, blk, rows_.ref_id, rows_.pos, rows_.end, rows_.flag, rows_.h_own,
                        rows_.h_mate, rows_.rec_off, win_off);
     hipLaunchKernelGGL((k_scan<1>), dim3(1), dim3(kScan), 0, s, blk, groups, st, cap, cap_rows_, cand);
-    hipLaunchKernelGGL((k_rec<true>), dim3(groups), dim3(kBlock), 0, s, d_win, st, (const int32_t*)cand, (const uint32_t*)link,
-                       (const uint8_t*)mark, (const uint8_t*)emit, blk, rows_.ref_id, rows_.pos, rows_.end, rows_.flag, rows_.h_own,
-                       rows_.h_mate, rows_.rec_off, win_off);
+    int32_t* ring_off = buf_->ring_off.as<int32_t>();
+    uint32_t* ring_flag = buf_->ring_flag.as<uint32_t>();
+    if (compact_)
+      hipLaunchKernelGGL(k_rec_compact, dim3(groups), dim3(kBlock), 0, s, d_win, (const State*)st, (const int32_t*)cand,
+                         (const uint8_t*)mark, (const uint8_t*)emit, (const uint32_t*)blk, ring_off, ring_flag, cap_cand_);
+    else
+      hipLaunchKernelGGL((k_rec<true>), dim3(groups), dim3(kBlock), 0, s, d_win, st, (const int32_t*)cand, (const uint32_t*)link,
+                         (const uint8_t*)mark, (const uint8_t*)emit, blk, rows_.ref_id, rows_.pos, rows_.end, rows_.flag, rows_.h_own,
+                         rows_.h_mate, rows_.rec_off, win_off);
     G2S_HIP_TRY(hipGetLastError());
+    if (compact_) {
+      CompactRows cr;
+      cr.off = ring_off, cr.flag = ring_flag, cr.n_rec = &st->n_rec, cr.anomaly = &st->anomaly, cr.capacity = cap_cand_, cr.stream = stream_;
+      if (!sink_(cr, d_win, front_, we, why)) return false;
+    }
     windows_++;
   }
   return true;

@@ -48,6 +48,11 @@ class BgzfDevice {
   bool launch(int slot, size_t n_members, size_t in_bytes, size_t out_bytes, std::string* why, bool down = true,
               uint8_t* d_dst = nullptr);
   bool wait(int slot, std::string* why);
+  // the device memory create() takes for the two slots: staged input, the window with its front, member list and
+  // status words (create() checks its allocations against this)
+  static uint64_t device_bytes(size_t max_in, size_t max_out, size_t max_members, size_t front, bool host_window = true) {
+    return 2 * ((uint64_t)max_in + 16 + (host_window ? front + max_out + 64 : 0) + (max_members + 1) * (sizeof(BgzfMember) + 4));
+  }
 
  private:
   BgzfDevice() {}

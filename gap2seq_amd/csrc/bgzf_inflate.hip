@@ -152,18 +152,27 @@ BgzfDevice* BgzfDevice::create(int device, size_t max_in, size_t max_out, size_t
     hipStream_t st;
     G2S_HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
     D->stream_ = st;
+    uint64_t held = 0;  // what the device allocations below ask for
+    auto take = [&held](void** p, size_t bytes) {
+      held += bytes;
+      return hipMalloc(p, bytes);
+    };
     for (Slot& s : D->s_) {
       G2S_HIP_TRY(hipHostMalloc((void**)&s.h_in, max_in + 16, hipHostMallocDefault));
       if (host_window) G2S_HIP_TRY(hipHostMalloc((void**)&s.h_out, front + max_out + 16, hipHostMallocDefault));
       G2S_HIP_TRY(hipHostMalloc((void**)&s.h_mem, (max_members + 1) * sizeof(BgzfMember), hipHostMallocDefault));
       G2S_HIP_TRY(hipHostMalloc((void**)&s.h_st, (max_members + 1) * 4, hipHostMallocDefault));
-      G2S_HIP_TRY(hipMalloc((void**)&s.d_in, max_in + 16));
-      if (host_window) G2S_HIP_TRY(hipMalloc((void**)&s.d_out, front + max_out + 64));  // (else: the caller's destination)
-      G2S_HIP_TRY(hipMalloc((void**)&s.d_mem, (max_members + 1) * sizeof(BgzfMember)));
-      G2S_HIP_TRY(hipMalloc((void**)&s.d_st, (max_members + 1) * 4));
+      G2S_HIP_TRY(take((void**)&s.d_in, max_in + 16));
+      if (host_window) G2S_HIP_TRY(take((void**)&s.d_out, front + max_out + 64));  // (else: the caller's destination)
+      G2S_HIP_TRY(take((void**)&s.d_mem, (max_members + 1) * sizeof(BgzfMember)));
+      G2S_HIP_TRY(take((void**)&s.d_st, (max_members + 1) * 4));
       hipEvent_t ev;
       G2S_HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
       s.done = ev;
+    }
+    if (held != device_bytes(max_in, max_out, max_members, front, host_window)) {
+      if (why) *why = "the slots' allocations are not what device_bytes() says";
+      return false;
     }
     return true;
   };

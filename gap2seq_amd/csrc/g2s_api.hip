@@ -302,6 +302,11 @@ uint64_t env_bytes(const char* name) {
   const char* s = getenv(name);
   return s && *s ? strtoull(s, nullptr, 10) : 0;
 }
+// G2S_BUILD_BAM_STREAM: 1 the BAM read route's streaming form always, 0 never, unset: when resident does not fit
+int env_bam_stream() {
+  const char* s = getenv("G2S_BUILD_BAM_STREAM");
+  return s && *s ? (strcmp(s, "0") != 0 ? 1 : 0) : -1;
+}
 bool env_on(const char* name) {
   const char* s = getenv(name);
   return s && *s && strcmp(s, "0") != 0;
@@ -336,7 +341,8 @@ extern "C" int g2s_graph_build_files(const char* reads_csv, int k, int solid, in
     std::string why;
     const ReadsLoadResult r = load_reads_device(inputs, getenv("G2S_DEVICE") ? atoi(getenv("G2S_DEVICE")) : 0,
                                                 (size_t)piece, env_bytes("G2S_BUILD_TEXT_FIRST_BYTES"),
-                                                env_on("G2S_HOST_INFLATE"), &text, &info, &why, env_bytes("G2S_BUILD_RESIDENT_CAP"));
+                                                env_on("G2S_HOST_INFLATE"), &text, &info, &why, env_bytes("G2S_BUILD_RESIDENT_CAP"),
+                                                env_bam_stream());
     if (r == kReadsIoError) return fail(G2S_ERR_IO, why);
     if (r != kReadsOk) { bam_reason = info.bam_reason; bam_anomaly = info.bam_anomaly; }
     if (r == kReadsOk && text.T == 0) {  // (no sequence at all: the empty graph, as the host loader builds it)
@@ -443,6 +449,18 @@ extern "C" int g2s_test_last_reads_bam(uint64_t* bam_files, uint64_t* kept, uint
   return G2S_OK;
 }
 // TEST HOOK (include/g2s_test.h)
+extern "C" int g2s_test_last_reads_bam_stream(uint64_t* streamed_files, uint64_t* windows, uint64_t* peak_device_bytes) {
+  ReadsLoadInfo info;
+  {
+    std::lock_guard<std::mutex> lk(g_reads_info_mu);
+    info = g_reads_info;
+  }
+  if (streamed_files) *streamed_files = info.bam_streamed;
+  if (windows) *windows = info.bam_stream_windows;
+  if (peak_device_bytes) *peak_device_bytes = info.bam_stream_peak;
+  return G2S_OK;
+}
+// TEST HOOK (include/g2s_test.h)
 extern "C" int g2s_test_reads_text(const void* bytes, size_t n, int device, size_t piece_bytes, uint8_t* out, size_t cap,
                                    size_t* out_n) {
   if ((!bytes && n) || (!out && cap) || !out_n || device < -2) return fail(G2S_ERR_ARG, "g2s_test_reads_text: bad argument");
@@ -488,9 +506,10 @@ extern "C" int g2s_test_reads_text(const void* bytes, size_t n, int device, size
   std::string why;
   const ReadsLoadResult r = load_reads_device(inputs, device, piece_bytes,
                                               env_bytes("G2S_BUILD_TEXT_FIRST_BYTES"), env_on("G2S_HOST_INFLATE"), &text, &info, &why,
-                                              env_bytes("G2S_BUILD_RESIDENT_CAP"));
+                                              env_bytes("G2S_BUILD_RESIDENT_CAP"), env_bam_stream());
   if (r == kReadsIoError) return fail(G2S_ERR_IO, why);
   if (r != kReadsOk) {
+    info.bam_streamed = info.bam_stream_windows = info.bam_stream_peak = 0;  // (nothing of a refused call counts)
     set_reads_info(info);  // (g2s_test_last_reads_bam: what a BAM file met)
     return fail(G2S_ERR_HIP, "g2s_test_reads_text: the device refused (" + why + ")");
   }

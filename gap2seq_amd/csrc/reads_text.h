@@ -19,10 +19,11 @@ enum ReadsInflate : int { kInflateNone = 0, kInflateZlib = 1, kInflateDevice = 2
 
 // who wrote the text of the BAM files among the read files (g2s_test_last_reads_bam), and when not the kernels, why
 enum BamReadsReason : int {
-  kBamReadsKernels = 0,   // k_bamreads_* (bam_reads.hip)
+  kBamReadsKernels = 0,   // k_bamreads_* or, streaming, k_bamstream_* (bam_reads.hip)
   kBamReadsNotAsked = 1,  // G2S_HOST_BUILD, G2S_HOST_READS=1, G2S_HOST_INFLATE=1, or no usable device
   kBamReadsAnomaly = 2,   // the row kernels gave the file back (bam_rows.h: RowsAnomaly says which)
-  kBamReadsOverCap = 3,   // stream, rows and text beyond half the free device memory, or G2S_BUILD_RESIDENT_CAP
+  kBamReadsOverCap = 3,   // beyond half the free device memory, or G2S_BUILD_RESIDENT_CAP: stream, rows and text, and the
+                          // streaming form's slots, rings and text as well (or its text outgrew what the limit left)
   kBamReadsHip = 4,       // an allocation or a HIP call failed
 };
 
@@ -34,6 +35,9 @@ struct ReadsLoadInfo {
   // the BAM files among them: their number, the records kept and skipped, whether the kernels wrote their text
   uint64_t bam_files = 0, bam_kept = 0, bam_skipped = 0;
   int bam_kernels = 0, bam_reason = kBamReadsNotAsked, bam_anomaly = 0;
+  // the streaming form (g2s_test_last_reads_bam_stream): the BAM files whose text it wrote, the walk windows they took,
+  // the largest footprint counted against the limit (slots, candidates, ring, scan scratch and the text's capacity)
+  uint64_t bam_streamed = 0, bam_stream_windows = 0, bam_stream_peak = 0;
 };
 
 // one input of the loader: a file by name, or bytes in memory (the test hook)
@@ -68,9 +72,12 @@ enum ReadsLoadResult : int {
 // far, the text buffer sized from its count; `piece` is then its window, resident_cap (G2S_BUILD_RESIDENT_CAP, 0: none)
 // lowers the bound of half the free device memory on its stream, rows and text.  With host_inflate its text is made by
 // the host walk and copied up.  On kReadsGaveUp info->bam_reason / bam_anomaly say what a BAM file met.
+// A BAM file that cannot be resident within the bound takes the streaming form (bam_reads.h) when everything that form
+// holds fits the same bound; bam_stream (G2S_BUILD_BAM_STREAM) 1: the streaming form always, 0: never, -1: by that rule.
+// out->capacity may then exceed device_text_bytes(T).
 ReadsLoadResult load_reads_device(const std::vector<ReadsInput>& inputs, int device, size_t piece, uint64_t first_cap,
                                   bool host_inflate, DeviceText* out, ReadsLoadInfo* info, std::string* err,
-                                  uint64_t resident_cap = 0);
+                                  uint64_t resident_cap = 0, int bam_stream = -1);
 void free_device_text(DeviceText* t);
 
 // the machine of fastx_machine.h walked line by line on the host over one file's bytes: the text is appended to *out

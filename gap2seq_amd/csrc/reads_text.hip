@@ -19,7 +19,8 @@
 // falls away and the file's end writes the last N.
 //
 // A BAM file of the list (told by fastx.hpp: is_bam) takes no piece: Loader::run_bam_file has bam_reads.hip make its text
-// behind what the list gave so far and moves the carry's text base past it.
+// behind what the list gave so far and moves the carry's text base past it — resident, or, for a file over the bound,
+// streaming into a text sized from the file's inflated bytes.
 #include <hip/hip_runtime.h>
 #include <fcntl.h>
 #include <sys/mman.h>
@@ -421,6 +422,7 @@ struct Loader {
   size_t bam_window = 0;       // a BAM file's window: the piece as asked for (0: the reader's own)
   uint64_t resident_cap = 0;   // G2S_BUILD_RESIDENT_CAP
   uint64_t mem_limit = 0;      // half the free device memory when the loader began, and the cap
+  int bam_stream = -1;         // G2S_BUILD_BAM_STREAM: 1 the streaming form always, 0 never, -1 when resident does not fit
   uint64_t bam_by_host = 0;    // BAM files whose text the host walk made (host_inflate)
   ReadsLoadInfo* info = nullptr;
   std::string* why = nullptr;  // (G2S_HIP_TRY)
@@ -559,14 +561,44 @@ struct Loader {
       BamReadsDevice B;
       int reason = kBamReadsHip, anomaly = 0;
       std::string w;
-      const BamReadsDevice::Result r = B.prepare(in, device, bam_window, resident_cap, &reason, &anomaly, &w);
-      if (r == BamReadsDevice::kIoError) { io_error = w; return kReadsIoError; }
-      if (r != BamReadsDevice::kOk) return gave_up(reason, anomaly, w);
-      bytes = B.text_bytes();
-      if (B.resident_bytes() + device_text_bytes(have + bytes) > mem_limit)
-        return gave_up(kBamReadsOverCap, 0, "a BAM file's stream, rows and text are over the cap");
-      if (!room(have, bytes)) return gave_up(kBamReadsHip, 0, why ? *why : std::string());
-      if (!B.write(d_text.as<uint8_t>(), have, cap, &w)) return gave_up(kBamReadsHip, 0, w);
+      bool stream = bam_stream == 1;
+      if (!stream) {
+        const BamReadsDevice::Result r = B.prepare(in, device, bam_window, resident_cap, &reason, &anomaly, &w);
+        if (r == BamReadsDevice::kIoError) { io_error = w; return kReadsIoError; }
+        if (r == BamReadsDevice::kOk) {
+          bytes = B.text_bytes();
+          if (B.resident_bytes() + device_text_bytes(have + bytes) > mem_limit) {
+            if (bam_stream == 0) return gave_up(kBamReadsOverCap, 0, "a BAM file's stream, rows and text are over the cap");
+            stream = true;
+          }
+        } else if (bam_stream != 0 && B.resident_did_not_fit()) {
+          stream = true;
+        } else {
+          return gave_up(reason, anomaly, w);
+        }
+      }
+      if (stream) {
+        // everything the streaming form holds counts against the limit: the fixed part and the text, whose capacity
+        // comes from the bound of two thirds of the stream behind the header, or from what the limit leaves
+        const BamReadsDevice::Result o = B.stream_open(in, device, bam_window, &w);
+        if (o == BamReadsDevice::kIoError) { io_error = w; return kReadsIoError; }
+        if (o != BamReadsDevice::kOk) return gave_up(kBamReadsHip, 0, w);
+        const uint64_t fixed = B.stream_fixed_bytes(), pad = device_text_bytes(0), tile = device_text_bytes(1) - pad;
+        const uint64_t left = mem_limit > fixed + pad ? (mem_limit - fixed - pad) / tile * tile : 0;  // text positions
+        if (left <= have) return gave_up(kBamReadsOverCap, 0, "a BAM file's windows and text are over the cap");
+        const uint64_t most = std::min<uint64_t>(2 * B.stream_payload() / 3, left - have);
+        if (!room(have, most)) return gave_up(kBamReadsHip, 0, why ? *why : std::string());
+        // (the bound is the text's, not the buffer's: its padding stays free, so the text's end needs no larger one)
+        const BamReadsDevice::Result r = B.stream_run(d_text.as<uint8_t>(), have, have + most, bam_window, &reason, &anomaly, &w);
+        if (r != BamReadsDevice::kOk) return gave_up(reason, anomaly, w);
+        bytes = B.text_bytes();
+        info->bam_streamed++;
+        info->bam_stream_windows += B.windows();
+        info->bam_stream_peak = std::max<uint64_t>(info->bam_stream_peak, fixed + cap);
+      } else {
+        if (!room(have, bytes)) return gave_up(kBamReadsHip, 0, why ? *why : std::string());
+        if (!B.write(d_text.as<uint8_t>(), have, cap, &w)) return gave_up(kBamReadsHip, 0, w);
+      }
       kept = B.kept();
       skipped = B.skipped();
       info->pieces += B.windows();
@@ -745,7 +777,7 @@ struct Loader {
 
 ReadsLoadResult load_reads_device(const std::vector<ReadsInput>& inputs, int device, size_t piece, uint64_t first_cap,
                                   bool host_inflate, DeviceText* out, ReadsLoadInfo* info, std::string* err,
-                                  uint64_t resident_cap) {
+                                  uint64_t resident_cap, int bam_stream) {
   *info = ReadsLoadInfo();
   if (!filter_device_usable(device)) { *err = "no usable gfx950 device " + std::to_string(device); return kReadsGaveUp; }
   // the text's bound: an uncompressed file gives no more text than it has bytes; compressed input has no bound
@@ -789,6 +821,7 @@ ReadsLoadResult load_reads_device(const std::vector<ReadsInput>& inputs, int dev
   L.host_inflate = host_inflate;
   L.bam_window = piece;
   L.resident_cap = resident_cap;
+  L.bam_stream = bam_stream;
   L.info = info;
   L.why = err;
   // (compressed reads: four times their bytes to begin with, and from there by doubling)

@@ -246,6 +246,7 @@ _SIGS = {
                                            C.POINTER(C.c_int), C.c_uint64, C.POINTER(C.c_uint64)]),
     "g2s_test_last_reads_bam": (C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
                                           C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "g2s_test_last_reads_bam_stream": (C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "g2s_test_bgzf_inflate": (C.c_int, [C.c_char_p, C.c_size_t, C.c_int, C.POINTER(C.c_uint8), C.c_size_t,
                                         C.POINTER(C.c_size_t), C.POINTER(C.c_int64)]),
     "g2s_test_last_filter_inflate": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
@@ -1244,6 +1245,15 @@ def last_reads_bam():
                                                   C.byref(reason), C.byref(anomaly)))
     return dict(files=f.value, kept=kept.value, skipped=skipped.value, kernels=kernels.value,
                 reason=BAM_READS_REASONS[reason.value], anomaly=anomaly.value)
+
+
+def last_reads_bam_stream():
+    """TEST HOOK binding (g2s_test_last_reads_bam_stream): dict(streamed_files, windows, peak_device_bytes) of the
+    streaming form of the BAM read route in the process's last Graph.from_files or reads_text: the BAM files whose text
+    it wrote, their walk windows, the largest device footprint counted against the bound; zeros when none was streamed"""
+    f, w, peak = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    _check(load_library().g2s_test_last_reads_bam_stream(C.byref(f), C.byref(w), C.byref(peak)))
+    return dict(streamed_files=f.value, windows=w.value, peak_device_bytes=peak.value)
 
 
 def bgzf_inflate(data, device=-1):

@@ -89,7 +89,12 @@ const char* g2s_last_error(void);
  *  reverse-complemented back to the read as sequenced; a record without
  *  bases is an empty sequence.  With a usable device the
  *  files' bytes are parsed there and never form sequences on the host
- *  (G2S_HOST_READS=1: the host loader).  G2S_ERR_IO with the file's name in
+ *  (G2S_HOST_READS=1: the host loader).  A BAM file is held on the device
+ *  whole — inflated stream, rows and text — while that fits half the free
+ *  device memory; a larger one goes through two windows of the inflate, its
+ *  text written window by window, and is bounded by its text alone: a
+ *  buffer of two thirds of its inflated size and a fixed amount beside it
+ *  (G2S_BUILD_BAM_STREAM=1|0: that form always, never).  G2S_ERR_IO with the file's name in
  *  g2s_last_error() for a file that cannot be read or whose gzip stream is
  *  truncated or corrupt, and for a BAM file with a member that does not
  *  inflate, a cut record or a header that does not parse.

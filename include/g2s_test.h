@@ -137,7 +137,9 @@ int g2s_test_last_solid_count(uint64_t* positions, uint32_t* passes, uint32_t* r
  * G2S_ERR_NO_DEVICE when it is no usable gfx950, G2S_ERR_HIP when anything on the device refuses; never the host in
  * their place.  The bytes of a BAM file give the BAM text (include/g2s.h): device == -1 and -2 by the reader's walk (there
  * is no line machine for BAM), device >= 0 by the kernels k_bamreads_* of csrc/bam_reads.hip, piece_bytes being the
- * window; with G2S_HOST_INFLATE=1 by the reader's walk, copied up.
+ * window — by k_bamstream_*, the streaming form, when the file is over G2S_BUILD_RESIDENT_CAP or
+ * G2S_BUILD_BAM_STREAM=1 asks for it (both are read here as g2s_graph_build_files reads them) —; with
+ * G2S_HOST_INFLATE=1 by the reader's walk, copied up.
  * G2S_ERR_IO with g2s_last_error()'s text for a truncated or corrupt gzip stream.  *out_n receives the
  * text's size; the first min(cap, size) bytes are written, so a caller whose capacity was too small calls again.
  * g2s_test_last_reads_load then speaks of this call. */
@@ -154,12 +156,23 @@ int g2s_test_last_reads_load(uint64_t* files, uint64_t* raw_bytes, uint64_t* pos
 
 /* TEST HOOK: the BAM files (csrc/bam_reads.h) among the read files of the process's last g2s_graph_build_files (or
  * g2s_test_reads_text).  bam_files; kept / skipped: their records that gave a sequence / that were secondary or
- * supplementary; by_kernels: 1 when k_bamreads_* wrote the text of every one of them; reason, when they did not:
+ * supplementary; by_kernels: 1 when k_bamreads_* or k_bamstream_* wrote the text of every one of them; reason, when they did not:
  * 0 the kernels wrote it, 1 not asked (G2S_HOST_BUILD, G2S_HOST_READS=1, G2S_HOST_INFLATE=1, no usable device, or the
  * host loader took over for another reason), 2 the row kernels gave a file back — *anomaly is then the RowsAnomaly of
- * csrc/bam_rows.h —, 3 stream, rows and text over half the free device memory or G2S_BUILD_RESIDENT_CAP, 4 an
- * allocation or a HIP call failed.  Any pointer may be NULL. */
+ * csrc/bam_rows.h —, 3 over half the free device memory or G2S_BUILD_RESIDENT_CAP: stream, rows and text, and the
+ * streaming form's windows and text too (or its text outgrew what the bound left), 4 an allocation or a HIP call
+ * failed.  Any pointer may be NULL. */
 int g2s_test_last_reads_bam(uint64_t* bam_files, uint64_t* kept, uint64_t* skipped, int* by_kernels, int* reason, int* anomaly);
+
+/* TEST HOOK: the streaming form of the BAM read route (csrc/bam_reads.h) in the process's last g2s_graph_build_files (or
+ * g2s_test_reads_text).  streamed_files: the BAM files whose text k_bamstream_* wrote window by window (a file that is
+ * resident, or that the host loader read, counts 0); windows: the walk windows those files took (they are among
+ * g2s_test_last_reads_load's pieces); peak_device_bytes: the largest footprint counted against the bound of half the
+ * free device memory and G2S_BUILD_RESIDENT_CAP for one of them — the inflate's two slots with their fronts, the
+ * candidate and ring arrays, the lengths with the scan's scratch, and the text buffer's capacity, each as the bytes
+ * asked of the allocator (its granularity is not counted, nor are the loader's own raw buffers for the FASTA/FASTQ files
+ * of the list — as for the resident route).  All 0 when no file was streamed.  Any pointer may be NULL. */
+int g2s_test_last_reads_bam_stream(uint64_t* streamed_files, uint64_t* windows, uint64_t* peak_device_bytes);
 
 /* TEST HOOK: the planner of the key-range passes (pass_plan.hpp) on a histogram of the caller's: nbins consecutive bins
  * of the key space, cut greedily and in order into passes of at most cap keys — a pass is closed in front of the first

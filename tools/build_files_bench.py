@@ -9,11 +9,13 @@ left.  The ways alternate, --reps builds each; the median and the spread of each
 --bam: the same reads as unaligned BAM records (a writer of this tool's own; --read-length L cuts bench.py's genome-long sequences into short reads of the same k-mers,
 in every form) through the device route
 (gap2seq_amd/csrc/bam_reads.hip) and through the host loader, beside --parent's library on the BGZF FASTQ file — what a
-BAM file had to be converted to before BAM was read.
+BAM file had to be converted to before BAM was read — and through the streaming form of the device route
+(G2S_BUILD_BAM_STREAM=1: "stream bam"); --parent-bam has --parent's library read the BAM file too, both of its ways.
 
   python tools/build_files_bench.py --config C4 --reps 5 --threads 16 [--parent PATH/TO/libg2s_hip.so]
   python tools/build_files_bench.py --config C4 --once fastq     # one device-loader build in this process (kernel trace)
-  python tools/build_files_bench.py --config C4 --bam --reps 5 [--parent PATH/TO/libg2s_hip.so]   (and --once bam)
+  python tools/build_files_bench.py --config C4 --bam --reps 5 [--parent PATH/TO/libg2s_hip.so [--parent-bam]]
+  python tools/build_files_bench.py --config C4 --bam --read-length 250 --once bam     (or --once stream)
 
 Needs a GPU."""
 import argparse
@@ -33,7 +35,7 @@ import zlib
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 SWITCHES = ("G2S_HOST_BUILD", "G2S_HOST_READS", "G2S_HOST_INFLATE", "G2S_BUILD_PASS_KEYS", "G2S_BUILD_PIECE_BYTES",
-            "G2S_BUILD_TEXT_FIRST_BYTES", "G2S_BUILD_RESIDENT_CAP")
+            "G2S_BUILD_TEXT_FIRST_BYTES", "G2S_BUILD_RESIDENT_CAP", "G2S_BUILD_BAM_STREAM")
 
 
 def bgzf(raw, out):
@@ -133,6 +135,10 @@ def child(library, path, k, threads):
         lib.g2s_test_last_reads_bam(C.byref(files), None, None, C.byref(kernels), C.byref(reason), C.byref(anomaly))
         if files.value:  # (a BAM file: whether the kernels wrote its text, and when not, why — include/g2s_test.h)
             out.update(bam_by_kernels=kernels.value, bam_reason=reason.value, bam_anomaly=anomaly.value)
+            lib.g2s_test_last_reads_bam_stream.argtypes = [C.POINTER(C.c_uint64)] * 3
+            streamed, windows, peak = C.c_uint64(), C.c_uint64(), C.c_uint64()
+            lib.g2s_test_last_reads_bam_stream(C.byref(streamed), C.byref(windows), C.byref(peak))
+            out.update(bam_streamed=streamed.value, bam_stream_windows=windows.value, bam_stream_peak=peak.value)
     except AttributeError:  # (the parent's library)
         pass
     lib.g2s_graph_free(h)
@@ -145,7 +151,8 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--parent", default="", help="the library of the commit before, for the uncompressed files")
-    ap.add_argument("--bam", action="store_true", help="the BAM form: device route, host loader, and --parent on BGZF FASTQ")
+    ap.add_argument("--bam", action="store_true", help="the BAM form: device route, streaming form, host loader, and --parent on BGZF FASTQ")
+    ap.add_argument("--parent-bam", action="store_true", help="with --bam and --parent: the parent's library on the BAM file, both ways")
     ap.add_argument("--read-length", type=int, default=0, help="cut the sequences into reads of this length that overlap by k - 1")
     ap.add_argument("--once", default="", help="one device-loader build of this form in this process, nothing else")
     ap.add_argument("--child", nargs=4, metavar=("LIBRARY", "PATH", "K", "THREADS"), help=argparse.SUPPRESS)
@@ -155,17 +162,22 @@ def main():
         return 0
     here = os.path.join(ROOT, "gap2seq_amd", "libg2s_hip.so")
     with tempfile.TemporaryDirectory() as d:
-        k, paths = write_files(args.config, d, args.bam or args.once == "bam", args.read_length)
+        k, paths = write_files(args.config, d, args.bam or args.once in ("bam", "stream"), args.read_length)
         sizes = {f: os.path.getsize(p) for f, p in paths.items()}
         if args.once:
             for name in SWITCHES:
                 os.environ.pop(name, None)
-            child(here, paths[args.once], k, args.threads)
+            if args.once == "stream":  # (the BAM file through the streaming form)
+                os.environ["G2S_BUILD_BAM_STREAM"] = "1"
+            child(here, paths["bam" if args.once == "stream" else args.once], k, args.threads)
             return 0
         ways = []  # (name, form, library, switches)
         if args.bam:
-            ways = [("device bam", "bam", here, {}), ("host-reads bam", "bam", here, {"G2S_HOST_READS": "1"})]
-            if args.parent:
+            ways = [("stream bam", "bam", here, {"G2S_BUILD_BAM_STREAM": "1"}), ("device bam", "bam", here, {}),
+                    ("host-reads bam", "bam", here, {"G2S_HOST_READS": "1"})]
+            if args.parent and args.parent_bam:
+                ways += [("parent device bam", "bam", args.parent, {}), ("parent host-reads bam", "bam", args.parent, {"G2S_HOST_READS": "1"})]
+            elif args.parent:
                 ways.append(("parent bgzf.fastq.gz", "bgzf.fastq.gz", args.parent, {}))
         for f in ([] if args.bam else paths):
             ways.append(("device " + f, f, here, {}))
@@ -193,7 +205,9 @@ def main():
         out["ways"][name] = dict(median_s=statistics.median(ts), min_s=ts[0], max_s=ts[-1], reps=len(ts), kmers=rs[0]["kmers"],
                                  rss_mb=statistics.median(r["rss_mb"] for r in rs), text_on_device=rs[0].get("text_on_device"),
                                  raw_bytes=rs[0].get("raw_bytes"), positions=rs[0].get("positions"),
-                                 bam_by_kernels=rs[0].get("bam_by_kernels"), bam_reason=rs[0].get("bam_reason"))
+                                 bam_by_kernels=rs[0].get("bam_by_kernels"), bam_reason=rs[0].get("bam_reason"),
+                                 bam_streamed=rs[0].get("bam_streamed"), bam_stream_windows=rs[0].get("bam_stream_windows"),
+                                 bam_stream_peak=rs[0].get("bam_stream_peak"))
     out["same_kmers"] = len({v["kmers"] for v in out["ways"].values()}) == 1
     print(json.dumps(out))
     return 0 if out["same_kmers"] else 1
