@@ -15,6 +15,7 @@
 #include <thread>
 
 #include "bam_rows.h"
+#include "bam_store.h"
 #include "bgzf_inflate.h"
 #include "inflate_core.h"
 
@@ -439,6 +440,48 @@ bool BamFile::for_each(const std::function<bool(const BamRec&)>& fn, std::string
   }
 }
 
+bool BamFile::store_sample(uint64_t sample, StorePlan* plan, std::string* err) const {
+  const uint64_t total = inflated_bytes(), P = total > first_rec_ ? total - first_rec_ : 0;
+  const uint64_t lim = first_rec_ + std::min<uint64_t>(sample ? sample : kStoreSampleBytes, P);
+  const uint64_t want = std::min<uint64_t>(total, lim + bam_store::kHead);  // (the head of a record that begins at the sample's last byte)
+  std::vector<uint8_t> buf;
+  z_stream zs;
+  memset(&zs, 0, sizeof zs);
+  if (inflateInit2(&zs, -15) != Z_OK) { *err = "zlib"; return false; }
+  for (size_t b = 0; b < blk_off_.size() && buf.size() < want; b++) {
+    const size_t at = buf.size();
+    buf.resize(at + blk_isize_[b]);
+    if (!Stream::inflate_block(&zs, *this, b, buf.data() + at)) {
+      inflateEnd(&zs);
+      *err = "corrupt BGZF block " + std::to_string(b);
+      return false;
+    }
+  }
+  inflateEnd(&zs);
+  uint64_t r = 0, c = 0, o = first_rec_;
+  while (o < lim && o + bam_store::kHead <= buf.size()) {
+    const uint8_t* rec = buf.data() + o;
+    const uint32_t bs = rd32(rec), l_name = rec[12];
+    const int32_t l_seq = (int32_t)rd32(rec + 20);
+    if (bs < 32 || bs > (1u << 30) || l_seq < 0 || l_name == 0) break;  // (the pass itself says what is wrong with it)
+    r++;
+    c += bam_store::stored_bytes(l_name, (uint64_t)l_seq);
+    o += 4 + (uint64_t)bs;
+  }
+  *plan = store_plan(P, r, std::min(o, total) - first_rec_, c);
+  return true;
+}
+
+bool BamFile::store_on_host(std::vector<uint8_t>* store, std::vector<uint64_t>* rec_off, std::string* err) const {
+  store->clear();
+  rec_off->clear();
+  return for_each([&](const BamRec& r) {
+    rec_off->push_back(store->size());
+    bam_store::append_record((const uint8_t*)r.name - bam_store::kHead, store);
+    return true;
+  }, err);
+}
+
 uint64_t BamFile::inflated_bytes() const {
   uint64_t total = 0;
   for (const uint32_t isize : blk_isize_) total += isize;
@@ -459,10 +502,13 @@ uint64_t BamFile::inflate_device_bytes() const {
 // word boundary in front of it and start that many bytes in; a record cut by a window's end is whole in memory, and in
 // place of the carry the chain's head moves by the distance between the two bases (BamRowsDevice::advance).
 // The streaming form (`sink`): the two slots as without `resident`, the rows compact and consumed window by window.
+// The store route (`store`): the two slots as without `resident`, whole-file rows of the planned count, and the store's
+// kernels behind the row kernels of every walk window (BamRowsDevice::window).
 BamRowsDevice* BamFile::rows_on_device(size_t walk_window, int* anomaly, std::string* why, bool resident, uint64_t resident_cap,
-                                       int* resident_refused, const RowsSink* sink) const {
+                                       int* resident_refused, const RowsSink* sink, const StoreAsk* store) const {
   const auto t0 = std::chrono::steady_clock::now();
   *anomaly = kRowsHip;
+  store_report_ = StoreReport();
   if (inflate_device_ < 0 || dev_refused_) { *why = "the reader does not inflate on a device"; return nullptr; }
   Stream s(*this);
   if (!(s.dev = device_buffers())) { *why = "no device buffers"; return nullptr; }
@@ -480,7 +526,9 @@ BamRowsDevice* BamFile::rows_on_device(size_t walk_window, int* anomaly, std::st
   }
   const uint64_t cap_rows = total / 36 + 1;
   if (sink) resident = false;
-  if (first_rec_ > first_bytes || max_out + dev->front() + 64 >= (size_t)INT32_MAX || (!sink && cap_rows >= (uint64_t)UINT32_MAX - 1)) {
+  const bool may_store = resident && store && store->mode != 0;  // (the row limit then applies to the planned rows)
+  const bool rows_fit = sink || cap_rows < (uint64_t)UINT32_MAX - 1;
+  if (first_rec_ > first_bytes || max_out + dev->front() + 64 >= (size_t)INT32_MAX || (!rows_fit && !may_store)) {
     *anomaly = kRowsLimits;
     *why = "a header beyond the first window, or a file outside the row kernels' index widths";
     return nullptr;
@@ -488,12 +536,29 @@ BamRowsDevice* BamFile::rows_on_device(size_t walk_window, int* anomaly, std::st
   ResidentAsk ask;
   ask.bytes = resident ? total : 0;
   ask.cap = resident_cap;
+  if (may_store) {
+    const StoreAsk sa = *store;
+    const uint64_t P = total - first_rec_;
+    ask.store = sa.mode;
+    ask.plan = [this, sa, P](StorePlan* p) {
+      if (sa.worst_case) {
+        *p = StorePlan();
+        p->rows_cap = P / 36 + 1, p->store_cap = P, p->need = 52 * (p->rows_cap + 1) + P;
+        return true;
+      }
+      std::string e;
+      return store_sample(sa.sample, p, &e);
+    };
+  }
   int refused = kResidentKept;
   std::unique_ptr<BamRowsDevice> R(BamRowsDevice::create(inflate_device_, dev->stream(), max_out, walk_window, dev->front(),
                                                          cap_rows, (int32_t)ref_names_.size(), first_rec_, why, &ask, &refused, sink));
   if (resident_refused) *resident_refused = refused;
-  if (!R) return nullptr;
-  uint8_t* const keep = R->stream_buffer();  // (null: today's two slots)
+  if (!R) {
+    if (!rows_fit) *anomaly = kRowsLimits;
+    return nullptr;
+  }
+  uint8_t* const keep = R->store_form() ? nullptr : R->stream_buffer();  // (null: the two slots)
   uint64_t off = 0;                          // inflated offset of the window at hand
   size_t used_beg[2] = {0, 0}, used_end[2] = {0, 0};
   // the members of the window that went through `slot` last: 0, or the anomaly
@@ -546,6 +611,7 @@ BamRowsDevice* BamFile::rows_on_device(size_t walk_window, int* anomaly, std::st
     ok = R->finish(last_bytes, &a, why) && a == kRowsOk;
     if (a != kRowsOk && why->empty()) *why = "the row kernels met anomaly " + std::to_string(a);
   }
+  if (R->store_form()) store_report_ = R->store_report();
   if (!ok) {  // (nothing of this pass is left in flight when the host walk takes the buffers over)
     (void)dev->wait(0, nullptr);
     (void)dev->wait(1, nullptr);

@@ -85,9 +85,27 @@ class BamFile {
   // `sink` (the read route's streaming form, not with `resident`): the two-slot way with compact rows (bam_rows.h:
   // CompactRows) handed to *sink behind every walk window's row kernels, before the window's slot is written again;
   // no array of the result grows with the file, and a file may hold more than 2^32 records.
+  // `store` (with `resident`; bam_store.h): the store route between the two — when the whole stream is refused as over the
+  // cap (mode -1), or in any case (mode 1), and the capacities planned from the file's sample fit the same cap, the
+  // windows go through the two slots and every record's head, name and packed bases are copied to one device allocation
+  // of the result behind the row kernels; stream_buffer() and rec_off are then the store's.  A planned capacity that
+  // proves too small ends the pass with the anomaly kRowsPlanRows or kRowsPlanStore.  store_report() says what happened.
+  struct StoreAsk {
+    int mode = -1;          // -1 when the whole stream is over the cap, 1 always, 0 never
+    uint64_t sample = 0;    // the sample's bytes behind the header; 0: kStoreSampleBytes
+    bool worst_case = false;  // tests: no sample, the capacities that cannot overflow (P / 36 + 1 rows, P bytes)
+  };
   BamRowsDevice* rows_on_device(size_t walk_window, int* anomaly, std::string* why, bool resident = false,
-                                uint64_t resident_cap = 0, int* resident_refused = nullptr, const RowsSink* sink = nullptr) const;
+                                uint64_t resident_cap = 0, int* resident_refused = nullptr, const RowsSink* sink = nullptr,
+                                const StoreAsk* store = nullptr) const;
   uint64_t rows_windows() const { return rows_windows_; }  // walk windows of the last rows_on_device
+  const StoreReport& store_report() const { return store_report_; }  // the store route in the last rows_on_device
+  // The plan of the store route's capacities (bam_store.h: store_plan) from the records that begin in the first `sample`
+  // inflated bytes behind the header (0: kStoreSampleBytes; the whole file when it is smaller), inflated here with zlib.
+  // False: *err (a member of the sample did not inflate).
+  bool store_sample(uint64_t sample, StorePlan* plan, std::string* err) const;
+  // the host model of the store (tests): every record compacted by bam_store::append_record, and where each begins
+  bool store_on_host(std::vector<uint8_t>* store, std::vector<uint64_t>* rec_off, std::string* err) const;
   // the file's inflated bytes (the members' ISIZE fields summed) and the offset of the first record among them
   uint64_t inflated_bytes() const;
   uint64_t first_record() const { return first_rec_; }
@@ -133,6 +151,7 @@ class BamFile {
   mutable bool dev_refused_ = false;
   mutable InflateStats stats_;
   mutable uint64_t rows_windows_ = 0;
+  mutable StoreReport store_report_;
 };
 
 }  // namespace g2s

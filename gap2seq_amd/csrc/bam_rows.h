@@ -6,6 +6,9 @@
 #include <cstdint>
 #include <functional>
 #include <string>
+#include <vector>
+
+#include "bam_store.h"
 
 namespace g2s {
 
@@ -20,6 +23,10 @@ enum RowsAnomaly : int {
   kRowsHash = 6,       // name_hash.h is not this build's std::hash<std::string>
   kRowsCorrupt = 7,    // a member did not inflate
   kRowsLimits = 8,     // a file outside the kernels' index widths, or a header that does not end in the first window
+  // the store route (bam_store.h) alone: a capacity planned from the file's sample was too small.  No fault of the
+  // file's: the caller runs pass A again the two-pass way (bam_text.h: kTextStoreOverflow)
+  kRowsPlanRows = 9,   // more records than the planned rows
+  kRowsPlanStore = 10, // more stored bytes than the planned store
 };
 
 // rows in device memory, in file order; the arrays belong to the BamRowsDevice that made them
@@ -28,7 +35,7 @@ struct DeviceRows {
   int64_t* end = nullptr;
   uint32_t* flag = nullptr;
   uint64_t *h_own = nullptr, *h_mate = nullptr;  // (the joins replace them by their bits, in place)
-  uint64_t* rec_off = nullptr;  // one-pass mode: every record's offset in the resident inflated stream (else null)
+  uint64_t* rec_off = nullptr;  // one-pass mode: every record's offset in the resident inflated stream, or in the store (else null)
   uint64_t n = 0;
   int64_t max_span = 1;
   int32_t read_length = 0;
@@ -38,6 +45,12 @@ struct DeviceRows {
 struct ResidentAsk {
   uint64_t bytes = 0;  // the inflated stream, whole; 0: nothing is kept
   uint64_t cap = 0;    // G2S_FILTER_RESIDENT_CAP; 0: half the free device memory alone
+  // The store route (bam_store.h), between "the whole stream is kept" and "nothing is kept".  store: -1 it is taken when
+  // the whole stream is refused as over the cap, 1 it is taken even when the whole stream would fit, 0 never.  plan: the
+  // two capacities, asked for only when the route is about to be taken (the caller inflates the file's sample for it);
+  // false: no plan, no store.  The plan's need must fit the same bound.
+  int store = 0;
+  std::function<bool(StorePlan*)> plan;
 };
 enum ResidentRefused : int { kResidentKept = 0, kResidentOverCap = 1, kResidentNoMemory = 2 };
 
@@ -66,6 +79,10 @@ class BamRowsDevice {
   // `ask` (may be null): one device allocation for the whole inflated stream and an offset per row beside the rows, taken
   // only when stream and rows fit within half the free device memory (and ask->cap).  When they do not, or the
   // allocation fails, the object is made without them and *resident_refused says which.
+  // The store route (ask->store, ask->plan): in place of the whole stream a BamStoreDevice of the planned capacity, rows of
+  // the planned count in place of cap_rows, and window() runs the store's kernels behind the row kernels of every walk
+  // window: k_rec<true> leaves a record's offset in its window in rec_off, and the store's copy kernel replaces it by the
+  // record's offset in the store.  The windows are then handed over the two-slot way (carry(), not advance()).
   // `sink` (may be null; not together with `ask`): the compact form — no whole-file arrays are made, cap_rows does not
   // apply, every walk window's rows go to the ring and then to *sink; rows() stays empty but for n.
   static BamRowsDevice* create(int device, void* stream, size_t max_window, size_t walk_window, size_t front,
@@ -86,9 +103,12 @@ class BamRowsDevice {
   // the same step between two windows of the resident stream, whose (word aligned) bases lie `step` bytes apart, the
   // first ending win_end bytes behind its base: nothing to copy, the head moves: enqueued
   bool advance(size_t win_end, size_t step, std::string* why);
-  // the resident stream (null without one-pass mode) and its size
+  // the resident stream (null without one-pass mode) and its size; in store form the store and, after finish(), its
+  // used bytes: a stream of well-formed records either way
   uint8_t* stream_buffer() const { return stream_buf_; }
   uint64_t stream_bytes() const { return stream_bytes_; }
+  bool store_form() const { return store_ != nullptr; }
+  const StoreReport& store_report() const { return report_; }  // (store form: the plan from create(), the rest from finish())
   int device() const { return device_; }
   void* stream() const { return stream_; }
   // the end of the stream behind a last window of last_bytes bytes: waits, and reads the counts down.  False: a HIP
@@ -97,6 +117,8 @@ class BamRowsDevice {
   // the first m rows copied to the host (tests)
   bool download(uint64_t m, int32_t* ref_id, int32_t* pos, int64_t* end, uint32_t* flag, uint64_t* h_own, uint64_t* h_mate,
                 std::string* why) const;
+  // store form, after finish(): the store's used bytes and every record's offset in it, copied to the host (tests)
+  bool download_store(std::vector<uint8_t>* store, std::vector<uint64_t>* rec_off, std::string* why) const;
   const DeviceRows& rows() const { return rows_; }
   uint64_t windows() const { return windows_; }
   uint64_t candidates() const { return candidates_; }
@@ -117,6 +139,8 @@ class BamRowsDevice {
   uint64_t stream_bytes_ = 0;
   RowsSink sink_;  // (compact form)
   bool compact_ = false;
+  BamStoreDevice* store_ = nullptr;  // (store form; owned)
+  StoreReport report_;
 };
 
 }  // namespace g2s

@@ -149,9 +149,10 @@ __global__ void __launch_bounds__(kBlock) k_flag(const uint8_t* __restrict__ win
 
 // One workgroup: blk[0 .. n) from counts to their exclusive scan.  WHICH 0 (candidates): the list's size against its
 // capacity, its slot 0.  WHICH 1 (records): where the window's rows go, and the head of the window that follows.
+// (rows_over: the anomaly of rows beyond cap_rows — the kernels' limits, or in store form a planned count)
 template <int WHICH>
 __global__ void __launch_bounds__(kScan) k_scan(uint32_t* __restrict__ blk, uint32_t n, State* __restrict__ st, uint32_t cap_cand,
-                                                uint64_t cap_rows, int32_t* __restrict__ cand) {
+                                                uint64_t cap_rows, int32_t* __restrict__ cand, uint32_t rows_over) {
   __shared__ uint32_t part[kScan];
   if (st->anomaly) return;
   const uint32_t tid = threadIdx.x, per = (n + kScan - 1) / kScan;
@@ -188,7 +189,7 @@ __global__ void __launch_bounds__(kScan) k_scan(uint32_t* __restrict__ blk, uint
     if (st->dead || st->exit == INT32_MIN) {
       st->anomaly = g2s::kRowsDeadLink;
     } else if (st->base + total > cap_rows) {
-      st->anomaly = g2s::kRowsLimits;
+      st->anomaly = rows_over;
     } else {
       st->row_base = st->base;
       st->n_rec = total;
@@ -401,7 +402,10 @@ BamRowsDevice* BamRowsDevice::create(int device, void* stream, size_t max_window
   const size_t walk = walk_window && walk_window < max_window ? walk_window : (max_window ? max_window : 1);
   const bool compact = sink != nullptr;
   if (compact) cap_rows = UINT64_MAX;  // (a walk window's rows are bounded by its candidates)
-  if (max_window + front + 64 >= (size_t)INT32_MAX || first_head > max_window || (!compact && cap_rows >= (uint64_t)UINT32_MAX - 1) ||
+  // (store form: the row limit applies to the planned rows, which replace cap_rows below)
+  const bool may_store = !compact && ask && ask->bytes && ask->store != 0 && ask->plan;
+  bool whole_rows = compact || cap_rows < (uint64_t)UINT32_MAX - 1;
+  if (max_window + front + 64 >= (size_t)INT32_MAX || first_head > max_window || (!whole_rows && !may_store) ||
       (compact && ask && ask->bytes)) {
     if (why) *why = "a file outside the row kernels' index widths";
     return nullptr;
@@ -420,14 +424,16 @@ BamRowsDevice* BamRowsDevice::create(int device, void* stream, size_t max_window
   D->max_tiles_ = (uint32_t)((walk + kTile - 1) / kTile);
   const size_t nblk = std::max<size_t>(D->max_tiles_, (D->cap_cand_ + kBlock - 1) / kBlock) + 1;
   auto make = [&]() -> bool {
-    const size_t rows = compact ? 0 : (size_t)cap_rows + 1, cc = D->cap_cand_;
+    size_t rows = compact ? 0 : (size_t)cap_rows + 1;
+    const size_t cc = D->cap_cand_;
     G2S_HIP_TRY(hipSetDevice(device));
     // one-pass mode: the whole inflated stream and the records' offsets, when they fit under the cap with the rows
     if (ask && ask->bytes) {
       size_t free_b = 0, total_b = 0;
       G2S_HIP_TRY(hipMemGetInfo(&free_b, &total_b));
       const uint64_t need = ask->bytes + 64 + rows * 52, cap = std::min<uint64_t>(free_b / 2, ask->cap ? ask->cap : UINT64_MAX);
-      if (need > cap) {
+      const bool forced = may_store && ask->store > 0;
+      if (forced || need > cap || !whole_rows) {  // (forced: the whole stream is not tried)
         *resident_refused = kResidentOverCap;
       } else {
         DevMem off, buf;  // (taken buf first; when either fails, freed buf first, before anything else is taken)
@@ -440,6 +446,35 @@ BamRowsDevice* BamRowsDevice::create(int device, void* stream, size_t max_window
           D->stream_bytes_ = ask->bytes;
         }
       }
+      // the store route: the whole stream is over the cap (or the caller insists), and the planned store and rows fit it
+      if (may_store && (forced || *resident_refused == kResidentOverCap)) {
+        StorePlan plan;
+        *resident_refused = kResidentOverCap;
+        if (ask->plan(&plan) && plan.rows_cap < (uint64_t)UINT32_MAX - 1 && plan.need <= cap) {
+          StoreReport& rep = D->report_;
+          rep.store_cap = plan.store_cap, rep.rows_cap = plan.rows_cap, rep.device_bytes = plan.need;
+          std::string w;
+          DevMem off;
+          D->store_ = BamStoreDevice::create(device, stream, plan.store_cap, plan.rows_cap, D->cap_cand_, &w);
+          if (!D->store_ || off.alloc(((size_t)plan.rows_cap + 1) * 8) != hipSuccess) {
+            (void)hipGetLastError();
+            delete D->store_;
+            D->store_ = nullptr;
+            *resident_refused = kResidentNoMemory;
+          } else {
+            D->cap_rows_ = cap_rows = plan.rows_cap;
+            rows = (size_t)cap_rows + 1;
+            whole_rows = true;
+            D->stream_buf_ = D->store_->buffer();
+            D->rows_.rec_off = (B.rec_off = std::move(off)).as<uint64_t>();
+            *resident_refused = kResidentKept;
+          }
+        }
+      }
+    }
+    if (!whole_rows) {
+      if (why) *why = "a file outside the row kernels' index widths";
+      return false;
     }
     uint64_t held = 0;  // what the allocations below ask for
     auto take = [&held](DevMem& m, size_t bytes) {
@@ -497,6 +532,7 @@ uint64_t BamRowsDevice::compact_bytes(size_t walk_window) {
 BamRowsDevice::~BamRowsDevice() {
   if (device_ >= 0) (void)hipSetDevice(device_);
   if (stream_) (void)hipStreamSynchronize((hipStream_t)stream_);
+  delete store_;
   delete buf_;  // (the allocations free themselves)
 }
 
@@ -507,6 +543,7 @@ bool BamRowsDevice::window(const uint8_t* d_win, size_t start, size_t bytes, std
   uint32_t *link = buf_->link.as<uint32_t>(), *blk = buf_->blk.as<uint32_t>();
   uint8_t *mark = buf_->mark.as<uint8_t>(), *emit = buf_->emit.as<uint8_t>();
   G2S_HIP_TRY(hipSetDevice(device_));
+  const uint32_t rows_over = store_ ? (uint32_t)kRowsPlanRows : (uint32_t)kRowsLimits;
   for (size_t ws = start; ws < bytes; ws += walk_) {
     const size_t we = std::min(ws + walk_, bytes);
     const uint32_t cap = window_capacity(we - ws);  // (at most cap_cand_)
@@ -515,7 +552,7 @@ bool BamRowsDevice::window(const uint8_t* d_win, size_t start, size_t bytes, std
     while (((uint32_t)1 << rounds) < cap) rounds++;
     hipLaunchKernelGGL((k_flag<false>), dim3(tiles), dim3(kBlock), 0, s, d_win, (const State*)st, (int32_t)ws, (int32_t)we, n_ref_,
                        cap, blk, cand);
-    hipLaunchKernelGGL((k_scan<0>), dim3(1), dim3(kScan), 0, s, blk, tiles, st, cap, cap_rows_, cand);
+    hipLaunchKernelGGL((k_scan<0>), dim3(1), dim3(kScan), 0, s, blk, tiles, st, cap, cap_rows_, cand, rows_over);
     hipLaunchKernelGGL((k_flag<true>), dim3(tiles), dim3(kBlock), 0, s, d_win, (const State*)st, (int32_t)ws, (int32_t)we, n_ref_,
                        cap, blk, cand);
     hipLaunchKernelGGL(k_links, dim3(groups), dim3(kBlock), 0, s, d_win, (const State*)st, (int32_t)we, n_ref_,
@@ -528,7 +565,7 @@ bool BamRowsDevice::window(const uint8_t* d_win, size_t start, size_t bytes, std
     hipLaunchKernelGGL((k_rec<false>), dim3(groups), dim3(kBlock), 0, s, d_win, st, (const int32_t*)cand, (const uint32_t*)link,
                        (const uint8_t*)mark, (const uint8_t*)emit, blk, rows_.ref_id, rows_.pos, rows_.end, rows_.flag, rows_.h_own,
                        rows_.h_mate, rows_.rec_off, win_off);
-    hipLaunchKernelGGL((k_scan<1>), dim3(1), dim3(kScan), 0, s, blk, groups, st, cap, cap_rows_, cand);
+    hipLaunchKernelGGL((k_scan<1>), dim3(1), dim3(kScan), 0, s, blk, groups, st, cap, cap_rows_, cand, rows_over);
     int32_t* ring_off = buf_->ring_off.as<int32_t>();
     uint32_t* ring_flag = buf_->ring_flag.as<uint32_t>();
     if (compact_)
@@ -539,6 +576,8 @@ bool BamRowsDevice::window(const uint8_t* d_win, size_t start, size_t bytes, std
                          (const uint8_t*)mark, (const uint8_t*)emit, blk, rows_.ref_id, rows_.pos, rows_.end, rows_.flag, rows_.h_own,
                          rows_.h_mate, rows_.rec_off, win_off);
     G2S_HIP_TRY(hipGetLastError());
+    // store form: rec_off holds the offsets in this window (win_off is 0), and the store's kernels replace them
+    if (store_ && !store_->window(d_win, front_, we, &st->n_rec, &st->row_base, &st->anomaly, rows_.rec_off, why)) return false;
     if (compact_) {
       CompactRows cr;
       cr.off = ring_off, cr.flag = ring_flag, cr.n_rec = &st->n_rec, cr.anomaly = &st->anomaly, cr.capacity = cap_cand_, cr.stream = stream_;
@@ -579,6 +618,15 @@ bool BamRowsDevice::finish(size_t last_bytes, int* anomaly, std::string* why) {
   rows_.max_span = (int64_t)h.max_span;
   rows_.read_length = h.read_length;
   candidates_ = h.candidates;
+  if (store_) {  // the store's position and words, once
+    bool over = false, bad = false;
+    if (!store_->finish(&report_.store_bytes, &report_.records, &over, &bad, why)) return false;
+    stream_bytes_ = report_.store_bytes;
+    if (h.anomaly == kRowsPlanRows) report_.overflow = 1;
+    else if (h.anomaly == kRowsOk && bad) *anomaly = kRowsDeadLink;  // (a record outside its window: the host walk decides)
+    else if (h.anomaly == kRowsOk && over) *anomaly = kRowsPlanStore, report_.overflow = 2;
+    report_.used = *anomaly == kRowsOk ? 1 : 0;
+  }
   return true;
 }
 
@@ -592,6 +640,15 @@ bool BamRowsDevice::download(uint64_t m, int32_t* ref_id, int32_t* pos, int64_t*
   G2S_HIP_TRY(hipMemcpy(flag, rows_.flag, m * 4, hipMemcpyDeviceToHost));
   G2S_HIP_TRY(hipMemcpy(h_own, rows_.h_own, m * 8, hipMemcpyDeviceToHost));
   G2S_HIP_TRY(hipMemcpy(h_mate, rows_.h_mate, m * 8, hipMemcpyDeviceToHost));
+  return true;
+}
+
+bool BamRowsDevice::download_store(std::vector<uint8_t>* store, std::vector<uint64_t>* rec_off, std::string* why) const {
+  store->assign((size_t)std::min<uint64_t>(stream_bytes_, store_ ? store_->capacity() : 0), 0);
+  rec_off->assign((size_t)std::min<uint64_t>(rows_.n, cap_rows_), 0);
+  G2S_HIP_TRY(hipSetDevice(device_));
+  if (!store->empty()) G2S_HIP_TRY(hipMemcpy(store->data(), stream_buf_, store->size(), hipMemcpyDeviceToHost));
+  if (!rec_off->empty()) G2S_HIP_TRY(hipMemcpy(rec_off->data(), rows_.rec_off, rec_off->size() * 8, hipMemcpyDeviceToHost));
   return true;
 }
 

@@ -1,6 +1,7 @@
 // gap2seq_amd/csrc/bam_text.h — pass B of the batched read filter on the device (bam_text.hip), for one-pass mode: the
 // bases, names and FASTA text of the records the joins selected, gathered and decoded from the inflated stream pass A
-// left in device memory (bam_rows.h: BamRowsDevice::stream_buffer, DeviceRows::rec_off).  No inflate, no host walk.
+// left in device memory (bam_rows.h: BamRowsDevice::stream_buffer, DeviceRows::rec_off) — or from the store of compacted
+// records it left there (bam_store.h), which reads the same.  No inflate, no host walk.
 // What it makes is what the host walk of pass B makes (readfilter_gaps.cpp: pass_b_host), array for array.
 #pragma once
 #include <cstddef>
@@ -25,6 +26,7 @@ enum TextReason : int {
   kTextNoDeviceRows = 2,  // pass A's rows were not made on the device: no device, a switch, a pass-A anomaly
   kTextOverCap = 3,     // stream and rows beyond half the free device memory, or G2S_FILTER_RESIDENT_CAP
   kTextFailed = 4,      // an allocation or a HIP call failed, in pass A's resident buffer or in pass B
+  kTextStoreOverflow = 5,  // the store route (bam_store.h): a capacity planned from the sample was too small; three passes
 };
 
 // A base as the filter prints it (readfilter_gaps.hpp: append_bases): the 4-bit codes 1, 2, 4, 8 are A, C, G, T, every

@@ -1,5 +1,5 @@
 // gap2seq_amd/csrc/hip_host.h — the host side's plumbing around HIP and rocPRIM, once, for the .hip files of the graph
-// build and the read filter (dbg_gpu, readfilter_gpu, bam_rows, bam_text, bgzf_inflate, seg_tables): an owned device
+// build and the read filter (dbg_gpu, readfilter_gpu, bam_rows, bam_store, bam_text, bgzf_inflate, seg_tables): an owned device
 // allocation, page-locked buffer and event, "run this HIP call or leave with its text", rocPRIM's two-call protocol, scan-and-total, "is there such a
 // device".  Host only; no kernel, no other project header.  (g2s_api.hip's DevBuf / PinBuf are grow-only session buffers,
 // another thing.)

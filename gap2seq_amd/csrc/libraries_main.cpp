@@ -15,7 +15,8 @@
 // -filter-device: the GPU the read filter's joins run on (default: -device), -1 = host threads.
 // -filter-one-pass: 1 asks the read filter to inflate every BAM once and keep it on the GPU between its passes
 // (g2s_filter_set_one_pass), 0 forbids it; not given, G2S_FILTER_ONE_PASS decides, and without that the mode is on
-// (kOnePassDefault: DESIGN 3.6b has the measurement behind it).  The output is the same bytes either way.
+// (kOnePassDefault: DESIGN 3.6b has the measurement behind it).  A BAM too large to stay there whole keeps every
+// record's head, name and bases instead (the store route, bam_store.h).  The output is the same bytes either way.
 // libs.txt: tab separated `bam mean std_dev threshold`, one library a line.  out.fa: per gap, in input order,
 // `comment\nfill\n` (the file GapMerger -gaps takes); stdout ends with `Filled X out of Y gaps`.
 #include <cmath>

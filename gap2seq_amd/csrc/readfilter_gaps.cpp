@@ -28,6 +28,13 @@
 // from there: the file is inflated once and the host walks nothing.  Whatever stands in the way — not asked for, no
 // device rows, over the cap, a failed allocation or HIP call — sends the call down the two-pass route from the point it
 // is at, with the resident buffer released first and nothing tried twice on the device; the outputs are the same bytes.
+// The store route (bam_store.h) sits between the two: when the whole stream is refused as over the cap and the store's
+// planned need fits it, the file goes through the inflate's two slots as in the two-pass route, and behind the row
+// kernels of every window the store's kernels copy each record's head, name and packed bases into one device allocation;
+// pass B's kernels read that as they read the resident stream.  The file is inflated once and nothing of the inflated
+// stream outlives its slot.  G2S_FILTER_STORE=1 takes the route even when the whole stream would fit, =0 never takes it.
+// A planned capacity that proves too small (kTextStoreOverflow) releases the store and the rows, runs pass A again the
+// two-pass way and pass B on the host: three passes, the same bytes.
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -234,6 +241,19 @@ struct LastText {
 };
 LastText g_last_text;
 
+// g2s_test_last_filter_store: the store route in pass A of the process's last batched call
+StoreReport g_last_store;
+// the store route's switches, read per call: G2S_FILTER_STORE (1 always, 0 never), G2S_FILTER_STORE_SAMPLE (bytes)
+BamFile::StoreAsk store_ask_from_env() {
+  BamFile::StoreAsk a;
+  const char* e = getenv("G2S_FILTER_STORE");
+  a.mode = e && strcmp(e, "1") == 0 ? 1 : e && strcmp(e, "0") == 0 ? 0 : -1;
+  const char* b = getenv("G2S_FILTER_STORE_SAMPLE");
+  const long long n = b ? atoll(b) : 0;
+  a.sample = n > 0 ? (uint64_t)n : 0;
+  return a;
+}
+
 // G2S_DEBUG=1: where a batched call's time outside its three laps goes — opening the file (the BGZF index and the header,
 // whose first window zlib inflates), releasing run_filter_gaps' buffers, releasing the reader (its page-locked and device
 // buffers).  Declared in front of the BamFile, so that it is destroyed behind it.
@@ -318,7 +338,7 @@ bool name_hash_usable() {
 // Pass A on the device.  Null: *anomaly says why (kRowsOk: nothing asked for it), the reader's statistics are as they
 // were, and the host walk runs.
 std::unique_ptr<BamRowsDevice> pass_a_device(const BamFile& bam, size_t walk_window, int* anomaly, bool resident = false,
-                                             int* resident_refused = nullptr) {
+                                             int* resident_refused = nullptr, const BamFile::StoreAsk* store = nullptr) {
   std::string why;
   *anomaly = kRowsOk;
   std::unique_ptr<BamRowsDevice> D;
@@ -328,7 +348,7 @@ std::unique_ptr<BamRowsDevice> pass_a_device(const BamFile& bam, size_t walk_win
   } else {
     const char* cap = getenv("G2S_FILTER_RESIDENT_CAP");
     D.reset(bam.rows_on_device(walk_window, anomaly, &why, resident, cap ? (uint64_t)strtoull(cap, nullptr, 10) : 0,
-                               resident_refused));
+                               resident_refused, nullptr, store));
   }
   if (!D && getenv("G2S_DEBUG"))
     fprintf(stderr, "[g2s] pass A: no device rows (anomaly %d: %s): the host walk\n", *anomaly, why.c_str());
@@ -416,26 +436,48 @@ int run_filter_gaps(BamFile& bam, const g2s_filter_opts* lib, const g2s_filter_g
   LastRows lr;
   // one-pass mode: asked for, and then whatever stands in its way is the reason it did not run
   LastText lt;
+  StoreReport ls;
+  bool store_overflow = false;
   const bool asked = one_pass_asked();
   lt.reason = asked ? kTextNoDeviceRows : kTextNotAsked;
   if (device_inflate && !env_is_1("G2S_HOST_ROWS") && (kDeviceRowsDefault || env_is_1("G2S_DEVICE_ROWS"))) {
     int refused = kResidentKept;
-    drows = pass_a_device(bam, 0, &lr.anomaly, asked, &refused);
+    const BamFile::StoreAsk sa = store_ask_from_env();
+    drows = pass_a_device(bam, 0, &lr.anomaly, asked, &refused, asked ? &sa : nullptr);
     lr.windows = bam.rows_windows();
+    if (asked) ls = bam.store_report();
     if (!drows) bam.reset_inflate_stats();
-    if (asked && refused != kResidentKept) lt.reason = refused == kResidentOverCap ? kTextOverCap : kTextFailed;
+    if (!drows && ls.overflow) {
+      // a planned capacity was too small: the store and the rows are gone, and pass A runs again the two-pass way
+      if (getenv("G2S_DEBUG"))
+        fprintf(stderr, "[g2s] store route given up: the planned %s overflowed (rows %llu, store %llu bytes): pass A again\n",
+                ls.overflow == 1 ? "rows" : "store", (unsigned long long)ls.rows_cap, (unsigned long long)ls.store_cap);
+      st.file_passes++;
+      store_overflow = true;
+      drows = pass_a_device(bam, 0, &lr.anomaly, false, nullptr);
+      lr.windows = bam.rows_windows();
+      if (!drows) bam.reset_inflate_stats();
+    }
+    if (store_overflow) lt.reason = kTextStoreOverflow;
+    else if (asked && refused != kResidentKept) lt.reason = refused == kResidentOverCap ? kTextOverCap : kTextFailed;
     else if (asked && drows && drows->stream_buffer()) lt.resident_bytes = drows->stream_bytes();
   }
   const bool resident = drows && drows->stream_buffer();
   if (asked && getenv("G2S_DEBUG")) {
-    static const char* const kWhy[] = {"", "", "pass A's rows were not made on the device", "over the cap", "an allocation failed"};
-    if (resident) fprintf(stderr, "[g2s] one-pass route: the inflated file stays on the device (%llu bytes)\n",
-                          (unsigned long long)lt.resident_bytes);
+    static const char* const kWhy[] = {"", "", "pass A's rows were not made on the device", "over the cap", "an allocation failed",
+                                       "a planned capacity of the store route overflowed"};
+    if (resident && ls.used)
+      fprintf(stderr, "[g2s] one-pass route: the records' heads, names and bases stay on the device (store %llu of %llu bytes, "
+                      "rows %llu of %llu, need %llu bytes)\n", (unsigned long long)ls.store_bytes, (unsigned long long)ls.store_cap,
+              (unsigned long long)ls.records, (unsigned long long)ls.rows_cap, (unsigned long long)ls.device_bytes);
+    else if (resident) fprintf(stderr, "[g2s] one-pass route: the inflated file stays on the device (%llu bytes)\n",
+                               (unsigned long long)lt.resident_bytes);
     else fprintf(stderr, "[g2s] two-pass route (%s)\n", kWhy[lt.reason]);
   }
   auto note_text = [&] {
     std::lock_guard<std::mutex> lk(g_last_mu);
     g_last_text = lt;
+    g_last_store = ls;
   };
   note_text();
   if (drows) {
@@ -517,6 +559,7 @@ int run_filter_gaps(BamFile& bam, const g2s_filter_opts* lib, const g2s_filter_g
       lt.bytes = pool ? T.pbases.size() + T.pnames.size() : T.text.size() + T.unmapped.size();
     } else {
       lt.reason = kTextFailed;
+      ls.used = 0;
       if (getenv("G2S_DEBUG")) fprintf(stderr, "[g2s] one-pass route given up in pass B (%s): the second pass on the host\n", why.c_str());
     }
     note_text();
@@ -760,10 +803,11 @@ int g2s_test_last_filter_text(int* one_pass, int* reason, uint64_t* reads, uint6
 
 int g2s_filter_set_one_pass(int mode) { return g2s::g_one_pass.exchange(mode < 0 ? -1 : mode > 0 ? 1 : 0); }
 
-// TEST HOOK (include/g2s_test.h): pass B alone
-int g2s_test_bam_text(const void* bytes, size_t n, int device, const uint32_t* rows, uint64_t n_rows, int want_names, int fasta,
-                      uint8_t* bases, uint64_t bases_cap, uint64_t* bases_n, uint8_t* names, uint64_t names_cap,
-                      uint64_t* names_n, uint64_t* base_off, uint64_t* name_off, uint64_t off_cap, uint64_t* n_reads) {
+// pass B alone (g2s_test_bam_text; `store`: g2s_test_bam_text_store, pass A in store form at the walk window `window`)
+static int bam_text_hook(bool store, size_t window, const void* bytes, size_t n, int device, const uint32_t* rows, uint64_t n_rows,
+                         int want_names, int fasta, uint8_t* bases, uint64_t bases_cap, uint64_t* bases_n, uint8_t* names,
+                         uint64_t names_cap, uint64_t* names_n, uint64_t* base_off, uint64_t* name_off, uint64_t off_cap,
+                         uint64_t* n_reads) {
   if (!bytes || (n_rows && !rows) || !bases_n || !names_n || !n_reads || (bases_cap && !bases) || (names_cap && !names) ||
       (off_cap && (!base_off || !name_off))) {
     g2s::set_filter_error("g2s_test_bam_text: bad argument");
@@ -784,8 +828,11 @@ int g2s_test_bam_text(const void* bytes, size_t n, int device, const uint32_t* r
   uint64_t total = 0;
   if (device >= 0) {
     int anomaly = 0, refused = 0;
-    D = g2s::pass_a_device(bam, 0, &anomaly, true, &refused);
-    if (!D || !D->stream_buffer()) {  // (never the host in the kernels' place)
+    g2s::BamFile::StoreAsk sa;  // (no switch is read: the store always, at the capacities that cannot overflow)
+    sa.mode = 1;
+    sa.worst_case = true;
+    D = g2s::pass_a_device(bam, store ? window : 0, &anomaly, true, &refused, store ? &sa : nullptr);
+    if (!D || !D->stream_buffer() || D->store_form() != store) {  // (never the host in the kernels' place)
       g2s::set_filter_error("g2s_test_bam_text: no resident stream (anomaly " + std::to_string(anomaly) + ", refused " +
                             std::to_string(refused) + ")");
       return G2S_ERR_HIP;
@@ -832,6 +879,98 @@ int g2s_test_bam_text(const void* bytes, size_t n, int device, const uint32_t* r
     name_off[i] = ask.names ? T.pnoff[i] : 0;
   }
   g2s::set_filter_error("");
+  return G2S_OK;
+}
+
+// TEST HOOKS (include/g2s_test.h)
+int g2s_test_bam_text(const void* bytes, size_t n, int device, const uint32_t* rows, uint64_t n_rows, int want_names, int fasta,
+                      uint8_t* bases, uint64_t bases_cap, uint64_t* bases_n, uint8_t* names, uint64_t names_cap,
+                      uint64_t* names_n, uint64_t* base_off, uint64_t* name_off, uint64_t off_cap, uint64_t* n_reads) {
+  return bam_text_hook(false, 0, bytes, n, device, rows, n_rows, want_names, fasta, bases, bases_cap, bases_n, names, names_cap,
+                       names_n, base_off, name_off, off_cap, n_reads);
+}
+int g2s_test_bam_text_store(const void* bytes, size_t n, int device, size_t window, const uint32_t* rows, uint64_t n_rows,
+                            int want_names, int fasta, uint8_t* bases, uint64_t bases_cap, uint64_t* bases_n, uint8_t* names,
+                            uint64_t names_cap, uint64_t* names_n, uint64_t* base_off, uint64_t* name_off, uint64_t off_cap,
+                            uint64_t* n_reads) {
+  return bam_text_hook(device >= 0, window, bytes, n, device, rows, n_rows, want_names, fasta, bases, bases_cap, bases_n, names,
+                       names_cap, names_n, base_off, name_off, off_cap, n_reads);
+}
+
+// TEST HOOK (include/g2s_test.h): the plan of the store route's capacities, on the host
+int g2s_test_filter_store_plan(const void* bytes, size_t n, uint64_t* sample_records, uint64_t* sample_bytes,
+                               uint64_t* sample_stored, uint64_t* rows_cap, uint64_t* store_cap, uint64_t* need) {
+  if (!bytes) { g2s::set_filter_error("g2s_test_filter_store_plan: bad argument"); return G2S_ERR_ARG; }
+  g2s::BamFile bam;
+  std::string err;
+  if (!bam.open_mem(bytes, n, &err)) { g2s::set_filter_error(err); return G2S_ERR_IO; }
+  g2s::StorePlan p;
+  if (!bam.store_sample(g2s::store_ask_from_env().sample, &p, &err)) { g2s::set_filter_error(err); return G2S_ERR_IO; }
+  if (sample_records) *sample_records = p.sample_records;
+  if (sample_bytes) *sample_bytes = p.sample_bytes;
+  if (sample_stored) *sample_stored = p.sample_stored;
+  if (rows_cap) *rows_cap = p.rows_cap;
+  if (store_cap) *store_cap = p.store_cap;
+  if (need) *need = p.need;
+  g2s::set_filter_error("");
+  return G2S_OK;
+}
+
+// TEST HOOK (include/g2s_test.h): the store alone
+int g2s_test_bam_store(const void* bytes, size_t n, int device, size_t window, uint8_t* store, uint64_t store_cap,
+                       uint64_t* store_n, uint64_t* rec_off, uint64_t off_cap, uint64_t* n_records) {
+  if (!bytes || !store_n || !n_records || (store_cap && !store) || (off_cap && !rec_off)) {
+    g2s::set_filter_error("g2s_test_bam_store: bad argument");
+    return G2S_ERR_ARG;
+  }
+  *store_n = *n_records = 0;
+  if (device >= 0 && !g2s::filter_device_usable(device)) {
+    g2s::set_filter_error("g2s_test_bam_store: no usable gfx950 device " + std::to_string(device));
+    return G2S_ERR_NO_DEVICE;
+  }
+  g2s::BamFile bam;
+  std::string err;
+  if (!bam.open_mem(bytes, n, &err)) { g2s::set_filter_error(err); return G2S_ERR_IO; }
+  bam.set_threads(1);
+  bam.set_inflate_device(device >= 0 ? device : -1);
+  std::vector<uint8_t> S;
+  std::vector<uint64_t> off;
+  if (device >= 0) {
+    int anomaly = 0, refused = 0;
+    g2s::BamFile::StoreAsk sa;  // (no switch is read: the store always, at the capacities that cannot overflow)
+    sa.mode = 1;
+    sa.worst_case = true;
+    std::unique_ptr<g2s::BamRowsDevice> D = g2s::pass_a_device(bam, window, &anomaly, true, &refused, &sa);
+    if (!D || !D->store_form()) {  // (never the host in the kernels' place)
+      g2s::set_filter_error("g2s_test_bam_store: no store (anomaly " + std::to_string(anomaly) + ", refused " +
+                            std::to_string(refused) + ")");
+      return G2S_ERR_HIP;
+    }
+    if (!D->download_store(&S, &off, &err)) { g2s::set_filter_error(err); return G2S_ERR_HIP; }
+  } else if (!bam.store_on_host(&S, &off, &err)) {
+    g2s::set_filter_error(err);
+    return G2S_ERR_IO;
+  }
+  *store_n = S.size();
+  *n_records = off.size();
+  if (store_cap && !S.empty()) memcpy(store, S.data(), (size_t)std::min<uint64_t>(store_cap, S.size()));
+  if (off_cap && !off.empty()) memcpy(rec_off, off.data(), 8 * (size_t)std::min<uint64_t>(off_cap, off.size()));
+  g2s::set_filter_error("");
+  return G2S_OK;
+}
+
+// TEST HOOK (include/g2s_test.h)
+int g2s_test_last_filter_store(int* used, uint64_t* records, uint64_t* store_bytes, uint64_t* store_cap, uint64_t* rows_cap,
+                               uint64_t* device_bytes, int* overflow) {
+  std::lock_guard<std::mutex> lk(g2s::g_last_mu);
+  const g2s::StoreReport& r = g2s::g_last_store;
+  if (used) *used = r.used;
+  if (records) *records = r.records;
+  if (store_bytes) *store_bytes = r.store_bytes;
+  if (store_cap) *store_cap = r.store_cap;
+  if (rows_cap) *rows_cap = r.rows_cap;
+  if (device_bytes) *device_bytes = r.device_bytes;
+  if (overflow) *overflow = r.overflow;
   return G2S_OK;
 }
 

@@ -267,6 +267,14 @@ _SIGS = {
                                     C.POINTER(C.c_uint8), C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint8), C.c_uint64,
                                     C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_uint64,
                                     C.POINTER(C.c_uint64)]),
+    "g2s_test_bam_text_store": (C.c_int, [C.c_char_p, C.c_size_t, C.c_int, C.c_size_t, C.POINTER(C.c_uint32), C.c_uint64, C.c_int,
+                                          C.c_int, C.POINTER(C.c_uint8), C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint8),
+                                          C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                          C.c_uint64, C.POINTER(C.c_uint64)]),
+    "g2s_test_filter_store_plan": (C.c_int, [C.c_char_p, C.c_size_t] + [C.POINTER(C.c_uint64)] * 6),
+    "g2s_test_bam_store": (C.c_int, [C.c_char_p, C.c_size_t, C.c_int, C.c_size_t, C.POINTER(C.c_uint8), C.c_uint64,
+                                     C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(C.c_uint64)]),
+    "g2s_test_last_filter_store": (C.c_int, [C.POINTER(C.c_int)] + [C.POINTER(C.c_uint64)] * 5 + [C.POINTER(C.c_int)]),
     "g2s_graph_validate": (C.c_int64, [C.c_void_p, C.c_char_p, C.c_size_t]),
     "g2s_test_post_gap": (C.c_int, [_VP, C.POINTER(g2s_params), C.POINTER(g2s_gap), C.c_int32,
                                     C.POINTER(C.c_uint32), C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.c_int32,
@@ -1334,7 +1342,8 @@ def filter_set_one_pass(mode):
     return load_library().g2s_filter_set_one_pass(int(mode))
 
 
-TEXT_REASONS = ("on the device", "not asked", "no device rows", "over the cap", "allocation or HIP failure")
+TEXT_REASONS = ("on the device", "not asked", "no device rows", "over the cap", "allocation or HIP failure",
+                "a planned capacity of the store route overflowed")
 
 
 def last_filter_text():
@@ -1345,11 +1354,12 @@ def last_filter_text():
     return dict(one_pass=o.value, reason=r.value, reads=n.value, bytes=b.value, resident_bytes=rb.value)
 
 
-def bam_text(data, rows, device=-1, names=True, fasta=False):
+def bam_text(data, rows, device=-1, names=True, fasta=False, store=False, window=0):
     """TEST HOOK binding (g2s_test_bam_text): pass B alone on a BAM file in memory for the records `rows` (indices in file
     order), by the host walk (device -1) or by the kernels on `device`.  Returns (code, dict(bases, base_off, names,
     name_off) or None, g2s_filter_last_error's text): the pool's arrays of the selected records in file order, or with
-    fasta=True their FASTA records in `bases`; nothing is raised, the code is the caller's to check."""
+    fasta=True their FASTA records in `bases`; nothing is raised, the code is the caller's to check.  store=True
+    (g2s_test_bam_text_store): pass A in store form, the row kernels `window` bytes at a time (0: the reader's window)."""
     lib = load_library()
     data = bytes(data)
     rows = list(rows)
@@ -1359,8 +1369,11 @@ def bam_text(data, rows, device=-1, names=True, fasta=False):
         B, N = (C.c_uint8 * bcap)(), (C.c_uint8 * ncap)()
         bo, no = (C.c_uint64 * ocap)(), (C.c_uint64 * ocap)()
         bn, nn, nr = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
-        rc = lib.g2s_test_bam_text(data, len(data), device, arr, len(rows), int(names), int(fasta), B, bcap, C.byref(bn), N, ncap,
-                                   C.byref(nn), bo, no, ocap, C.byref(nr))
+        tail = (arr, len(rows), int(names), int(fasta), B, bcap, C.byref(bn), N, ncap, C.byref(nn), bo, no, ocap, C.byref(nr))
+        if store:
+            rc = lib.g2s_test_bam_text_store(data, len(data), device, window, *tail)
+        else:
+            rc = lib.g2s_test_bam_text(data, len(data), device, *tail)
         if rc != G2S_OK or (bn.value <= bcap and nn.value <= ncap and nr.value + 1 <= ocap):
             break
         bcap, ncap, ocap = max(bcap, bn.value), max(ncap, nn.value), max(ocap, nr.value + 1)
@@ -1370,3 +1383,48 @@ def bam_text(data, rows, device=-1, names=True, fasta=False):
     m = nr.value + 1
     return rc, dict(bases=bytes(B[:bn.value]), base_off=list(bo[:m]), names=bytes(N[:nn.value]),
                     name_off=list(no[:m]) if names and not fasta else None), msg
+
+
+def filter_store_plan(data):
+    """TEST HOOK binding (g2s_test_filter_store_plan): the store route's plan for a BAM file in memory, on the host.
+    Returns (code, dict(sample_records, sample_bytes, sample_stored, rows_cap, store_cap, need) or None,
+    g2s_filter_last_error's text); G2S_FILTER_STORE_SAMPLE is read."""
+    lib = load_library()
+    data = bytes(data)
+    v = [C.c_uint64() for _ in range(6)]
+    rc = lib.g2s_test_filter_store_plan(data, len(data), *[C.byref(x) for x in v])
+    msg = (lib.g2s_filter_last_error() or b"").decode("utf-8", "replace")
+    if rc != G2S_OK:
+        return rc, None, msg
+    keys = ("sample_records", "sample_bytes", "sample_stored", "rows_cap", "store_cap", "need")
+    return rc, dict(zip(keys, (x.value for x in v))), msg
+
+
+def bam_store(data, device=-1, window=0):
+    """TEST HOOK binding (g2s_test_bam_store): the store of a BAM file in memory, by the host model (device -1) or by the
+    kernels on `device` behind the row kernels, `window` bytes at a time (0: the reader's window).  Returns (code,
+    (store bytes, [every record's offset]) or None, g2s_filter_last_error's text); nothing is raised."""
+    lib = load_library()
+    data = bytes(data)
+    scap, ocap = 1 << 16, 1 << 10
+    while True:
+        S, O = (C.c_uint8 * scap)(), (C.c_uint64 * ocap)()
+        sn, on = C.c_uint64(0), C.c_uint64(0)
+        rc = lib.g2s_test_bam_store(data, len(data), device, window, S, scap, C.byref(sn), O, ocap, C.byref(on))
+        if rc != G2S_OK or (sn.value <= scap and on.value <= ocap):
+            break
+        scap, ocap = max(scap, sn.value), max(ocap, on.value)
+    msg = (lib.g2s_filter_last_error() or b"").decode("utf-8", "replace")
+    if rc != G2S_OK:
+        return rc, None, msg
+    return rc, (bytes(S[:sn.value]), list(O[:on.value])), msg
+
+
+def last_filter_store():
+    """TEST HOOK binding (g2s_test_last_filter_store): dict(used, records, store_bytes, store_cap, rows_cap, device_bytes,
+    overflow) of the store route in the process's last batched filter call; overflow is 0 none, 1 the rows, 2 the store"""
+    u, o = C.c_int(), C.c_int()
+    v = [C.c_uint64() for _ in range(5)]
+    _check(load_library().g2s_test_last_filter_store(C.byref(u), *[C.byref(x) for x in v], C.byref(o)))
+    keys = ("records", "store_bytes", "store_cap", "rows_cap", "device_bytes")
+    return dict(zip(keys, (x.value for x in v)), used=u.value, overflow=o.value)

@@ -535,7 +535,8 @@ typedef struct g2s_filter_gap {
   int32_t breakpoint, gap_length, flank_length;   /* as in g2s_filter_opts; flank_length -1 = no flank reads */
 } g2s_filter_gap;
 typedef struct g2s_filter_stats {
-  uint32_t file_passes;              /* inflating passes over the BAM made by this call (2, or 1 in one-pass mode) */
+  uint32_t file_passes;              /* inflating passes over the BAM made by this call: 2, or 1 in one-pass mode, or 3
+                                      * when one-pass mode's store route planned a capacity too small and started over */
   uint32_t on_device;                /* 1 when the joins ran on the GPU */
   double ms_inflate, ms_join, ms_text;   /* laps: pass A; windows and joins; pass B and the per-gap texts */
 } g2s_filter_stats;
@@ -576,11 +577,18 @@ void g2s_read_pool_free(g2s_read_pool* p);
 
 /* One-pass mode of the four batched calls above (ABI 6, additive), process-wide and atomic: 1 asks for it in every
  * later call, 0 forbids it, -1 (the initial state) follows the environment (G2S_FILTER_ONE_PASS=1|0, read per call;
- * off when it is not set).  Returns the previous mode.  In one-pass mode pass A leaves the inflated file in device memory
- * and pass B is kernels that gather the selected reads from it: the file is inflated once.  It is taken only when the
- * joins, the inflate and pass A's rows all run on the device and the inflated file with its rows fits half the free
- * device memory (G2S_FILTER_RESIDENT_CAP=BYTES lowers that); otherwise the call takes the two-pass route.  Outputs,
- * messages and codes are the same bytes on either route; g2s_filter_stats::file_passes says which one ran. */
+ * off when it is not set).  Returns the previous mode.  One-pass mode is taken only when the joins, the inflate and
+ * pass A's rows all run on the device, and then a call takes the first of three routes that fits:
+ *   1. the whole stream resident: pass A leaves the inflated file in device memory and pass B is kernels that gather the
+ *      selected reads from it.  Taken when the inflated file with its rows (about 2.44 times its size) fits half the free
+ *      device memory (G2S_FILTER_RESIDENT_CAP=BYTES lowers that).  file_passes 1.
+ *   2. the store route: the file goes through the inflate's two window slots, and pass A keeps of every record only its
+ *      head, name and packed bases in one device allocation, which pass B's kernels read the same way.  Its capacities
+ *      are planned from the records in the file's first MiB with a margin of a quarter, and the plan must fit the same
+ *      bound.  file_passes 1 — or 3 when a planned capacity proves too small: the store is released, pass A runs again
+ *      the two-pass way and pass B on the host.  (G2S_FILTER_STORE=1 takes this route even when route 1 fits, =0 never.)
+ *   3. two passes: the file is inflated twice and the host walks it for pass B.  file_passes 2.
+ * Outputs, messages and codes are the same bytes on every route; g2s_filter_stats::file_passes says which one ran. */
 int g2s_filter_set_one_pass(int mode);
 
 /* ---------------------------------------------------------------------------

@@ -256,9 +256,12 @@ int g2s_test_last_filter_rows(int* on_device, uint64_t* windows, uint64_t* recor
  * ran on the device from the stream pass A kept there (one-pass mode, g2s_filter_set_one_pass); *reason why it did not
  * (csrc/bam_text.h: TextReason): 0 it did, 1 not asked for, 2 pass A's rows were not made on the device (no device, a
  * switch, an anomaly), 3 the inflated file and its rows are over the cap (half the free device memory,
- * G2S_FILTER_RESIDENT_CAP), 4 an allocation or a HIP call failed.  *reads / *bytes: the records pass B's kernels
- * produced and the bytes of their bases, names or text (0 when it did not run there); *resident_bytes: the inflated
- * stream pass A kept on the device (0: none).  Any pointer may be NULL. */
+ * G2S_FILTER_RESIDENT_CAP) and so is the store route's need (or G2S_FILTER_STORE=0), 4 an allocation or a HIP call
+ * failed, 5 a capacity the store route planned from the file's sample was too small: pass A ran again the two-pass way
+ * and pass B on the host (file_passes 3).  *reads / *bytes: the records pass B's kernels produced and the bytes of their
+ * bases, names or text (0 when it did not run there); *resident_bytes: the inflated stream pass A kept on the device,
+ * or on the store route the store's used bytes, which are fewer than the inflated file's (0: none).  Any pointer may be
+ * NULL. */
 int g2s_test_last_filter_text(int* one_pass, int* reason, uint64_t* reads, uint64_t* bytes, uint64_t* resident_bytes);
 
 /* TEST HOOK: pass B of the batched read filter alone, on a BAM file in memory, for the records whose indices (in file
@@ -275,6 +278,43 @@ int g2s_test_last_filter_text(int* one_pass, int* reason, uint64_t* reads, uint6
 int g2s_test_bam_text(const void* bytes, size_t n, int device, const uint32_t* rows, uint64_t n_rows, int want_names, int fasta,
                       uint8_t* bases, uint64_t bases_cap, uint64_t* bases_n, uint8_t* names, uint64_t names_cap,
                       uint64_t* names_n, uint64_t* base_off, uint64_t* name_off, uint64_t off_cap, uint64_t* n_reads);
+
+/* TEST HOOK: g2s_test_bam_text with pass A in store form on a device (csrc/bam_store.h): the file through the inflate's two
+ * slots, the row kernels `window` bytes at a time (0: a whole window of inflated members), the store's kernels behind
+ * them, and pass B's kernels on the store.  The capacities are the ones that cannot overflow; no switch is read.
+ * G2S_ERR_HIP when the store was not made; device == -1 is the host walk, as there. */
+int g2s_test_bam_text_store(const void* bytes, size_t n, int device, size_t window, const uint32_t* rows, uint64_t n_rows,
+                            int want_names, int fasta, uint8_t* bases, uint64_t bases_cap, uint64_t* bases_n, uint8_t* names,
+                            uint64_t names_cap, uint64_t* names_n, uint64_t* base_off, uint64_t* name_off, uint64_t off_cap,
+                            uint64_t* n_reads);
+
+/* TEST HOOK: the store route's plan (csrc/bam_store.h: store_plan) for a BAM file in memory; needs no device.  The sample
+ * is the records that begin in the first 1 MiB (G2S_FILTER_STORE_SAMPLE=BYTES) of the inflated stream behind the
+ * header, or in the whole file when it is smaller: *sample_records records over *sample_bytes bytes (the last one
+ * whole, so the bytes may reach beyond the sample's end) with *sample_stored stored bytes.  With P the inflated bytes
+ * behind the header, *rows_cap = min(P / 36 + 1, ceil(1.25 r / z P) + 64), *store_cap = min(P, ceil(1.25 c / z P) +
+ * 4096), *need = 52 (rows_cap + 1) + store_cap.  Any pointer may be NULL. */
+int g2s_test_filter_store_plan(const void* bytes, size_t n, uint64_t* sample_records, uint64_t* sample_bytes,
+                               uint64_t* sample_stored, uint64_t* rows_cap, uint64_t* store_cap, uint64_t* need);
+
+/* TEST HOOK: the store of a BAM file in memory (csrc/bam_store.h): of every record in file order the 36 head bytes with
+ * block_size rewritten to 32 + l_name + ceil(l_seq / 2) and n_cigar_op to 0, the l_name name bytes and the packed
+ * bases, back to back; rec_off[i] is where record i begins.  device == -1: the host model (bam_store::append_record
+ * under BamFile::for_each).  device >= 0: the kernels of csrc/bam_store.hip behind the device inflate and the row
+ * kernels, `window` bytes at a time — G2S_ERR_NO_DEVICE when it is no usable gfx950, G2S_ERR_HIP when anything on the
+ * device refuses; never the host in their place, and no switch is read.  *store_n / *n_records are the true sizes; the
+ * first min(store_cap, *store_n) bytes and min(off_cap, *n_records) offsets are written, so a caller whose capacity was
+ * too small calls again. */
+int g2s_test_bam_store(const void* bytes, size_t n, int device, size_t window, uint8_t* store, uint64_t store_cap,
+                       uint64_t* store_n, uint64_t* rec_off, uint64_t off_cap, uint64_t* n_records);
+
+/* TEST HOOK: the store route in pass A of the process's last g2s_filter_reads_gaps[_mem] / _pool[_mem] call.  *used: 1
+ * when pass B read the store; *records / *store_bytes: what the store held; *store_cap / *rows_cap: the planned
+ * capacities (0: no plan was made); *device_bytes: the plan's need, counted against the bound of half the free device
+ * memory and G2S_FILTER_RESIDENT_CAP; *overflow: 0 none, 1 the planned rows, 2 the planned store.  Any pointer may be
+ * NULL. */
+int g2s_test_last_filter_store(int* used, uint64_t* records, uint64_t* store_bytes, uint64_t* store_cap, uint64_t* rows_cap,
+                               uint64_t* device_bytes, int* overflow);
 
 #ifdef __cplusplus
 }

@@ -8,8 +8,12 @@
   device_host_inflate   (--host-inflate) the same with G2S_HOST_INFLATE=1: zlib on host threads, the joins on the GPU
   --one-pass            asks for one-pass mode in every batched call (g2s_filter_set_one_pass(1)): the device legs then
                         report file_passes 1, and every leg says whether pass B ran on the device (text_on_device)
+  --resident-cap BYTES  G2S_FILTER_RESIDENT_CAP for the legs: under the whole stream's need (the inflated file and 52 bytes
+                        for every 36 of them) one-pass mode takes the store route (store.used 1) when its need fits
+  --store 0|1           G2S_FILTER_STORE for the legs: 1 takes the store route even when the whole stream fits, 0 never
 
-Every run also carries the reader's own laps (g2s_test_last_filter_inflate): whether the file was inflated on the
+Every batched run carries the store route's hook (g2s_test_last_filter_store: used, records, store_bytes, store_cap,
+rows_cap, device_bytes, overflow) under "store".  Every run also carries the reader's own laps (g2s_test_last_filter_inflate): whether the file was inflated on the
 device and the time inside the reader's refills in pass A and pass B.
 
 Prints one JSON line.  The library is tests/bamwriter.simulate_library's, about --pairs read pairs on 10 scaffolds,
@@ -17,7 +21,7 @@ with --gaps gaps at random breakpoints; the same gaps for all three, on the coor
 records shuffled (where the host joins sort their index, which a sorted file spares them).
 
   python tools/readfilter_bench.py [--pairs 1000000] [--gaps 1000] [--loop-gaps 20] [--device 0] [--threads 0]
-                                   [--host-inflate] [--one-pass]
+                                   [--host-inflate] [--one-pass] [--resident-cap BYTES] [--store 0|1]
 """
 import argparse
 import json
@@ -44,7 +48,13 @@ def main():
     ap.add_argument("--seed", type=int, default=5)
     ap.add_argument("--host-inflate", action="store_true", help="add a leg with G2S_HOST_INFLATE=1")
     ap.add_argument("--one-pass", action="store_true", help="ask for one-pass mode (g2s_filter_set_one_pass(1))")
+    ap.add_argument("--resident-cap", type=int, default=None, help="G2S_FILTER_RESIDENT_CAP for the legs")
+    ap.add_argument("--store", choices=("0", "1"), default=None, help="G2S_FILTER_STORE for the legs")
     a = ap.parse_args()
+    if a.resident_cap is not None:
+        os.environ["G2S_FILTER_RESIDENT_CAP"] = str(a.resident_cap)
+    if a.store is not None:
+        os.environ["G2S_FILTER_STORE"] = a.store
     if a.one_pass:
         P.filter_set_one_pass(1)
     t0 = time.time()
@@ -93,7 +103,7 @@ def main():
         out[label] = dict(s=round(dt, 3), inflate_ms=round(st["ms_inflate"], 1), join_ms=round(st["ms_join"], 1),
                           text_ms=round(st["ms_text"], 1), on_device=st["on_device"], file_passes=st["file_passes"],
                           text_on_device=txt["one_pass"], text_reason=P.TEXT_REASONS[txt["reason"]],
-                          resident_mb=round(txt["resident_bytes"] / 1e6, 1),
+                          resident_mb=round(txt["resident_bytes"] / 1e6, 1), store=P.last_filter_store(),
                           extracted=sum(x[3] for x in got), inflate_on_device=inf["on_device"],
                           refill_a_ms=round(inf["ms_pass_a_inflate"], 1), refill_b_ms=round(inf["ms_pass_b_inflate"], 1))
     print(json.dumps(out))
