@@ -4,6 +4,8 @@
 // It accepts exactly the argv the reference wrapper builds
 // (/root/reference/src/Gap2Seq.py:178-188,230-241).  Everything below the option
 // parsing goes through the C ABI in include/g2s.h.
+#include <sys/stat.h>
+
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -31,6 +33,7 @@ int main(int argc, char** argv) {
   memset(&p, 0, sizeof p);
   p.d_err = 500; p.all_paths = 1;
   int randseed = 0, device = 0, streams = 2, stream_gaps = 8192;
+  int device_gzip = -1;  // -device-gzip 0|1; not given: G2S_DEVICE_GZIP, and without that the rule below
   bool streams_given = false;
   static int fasta_width = 0;  // (static: read by the output callback)
   std::string devices;  // "0,1,2": GPUs sharing the gap list (the graph is replicated)
@@ -65,13 +68,17 @@ int main(int argc, char** argv) {
     else if (a == "-streams") { streams = atoi(val()); streams_given = true; }
     else if (a == "-stream-gaps") stream_gaps = atoi(val());
     else if (a == "-fasta-width") fasta_width = atoi(val());
+    else if (a == "-device-gzip") { device_gzip = atoi(val()) != 0 ? 1 : 0; g2s_reads_set_device_gzip(device_gzip); }
     else if (a == "-help" || a == "-h") {
       std::cout << "Gap2Seq-core (MI355X) -reads a.fq[,b.fq] -filled out.fa (-scaffolds in.fa | -left S -right S -length N)\n"
                    "  [-k 31 (1..127)] [-solid 2] [-dist-error 500] [-fuz 10] [-max-mem 20] [-randseed 0]\n"
                    "  [-all-upper] [-best-only] [-unique] [-nb-cores N] [-device D | -devices D0,D1,...] [-streams 2]\n"
-                   "  [-stream-gaps 8192] [-fasta-width 0]\n"
+                   "  [-stream-gaps 8192] [-fasta-width 0] [-device-gzip 0|1]\n"
                    "  -reads: FASTA or FASTQ files (plain, gzip or BGZF) and BAM files, told by their bytes; a BAM file gives\n"
-                   "  every record that is neither secondary nor supplementary, as the read was sequenced\n";
+                   "  every record that is neither secondary nor supplementary, as the read was sequenced\n"
+                   "  -device-gzip 1: a plain gzip read file is inflated on the device from many places of its stream at once\n"
+                   "  (zlib reads it again when that route gives it back); 0 never; not given: G2S_DEVICE_GZIP=1|0, else for\n"
+                   "  gzip files of 90 MB and more\n";
       return EXIT_SUCCESS;
     }
     else {  // GATB's OptionsParser rejects what it does not know; main.cpp:29-31 prints the message
@@ -82,6 +89,29 @@ int main(int argc, char** argv) {
   if (reads.empty() || filled.empty()) {
     std::cout << "EXCEPTION: missing mandatory option (-reads, -filled)" << std::endl;  // main.cpp:29-31
     return EXIT_FAILURE;
+  }
+  // The chunked device inflate of plain gzip read files (g2s_reads_set_device_gzip) is asked for when a gzip file of the
+  // list has at least kDeviceGzipFrom bytes: measured from file to graph, it loses on a 9 MB .fq.gz (0.197 s
+  // against zlib's 0.161 s: one window, a wave a chunk) and wins on the next size measured, 90.8 MB (1.09 s against 1.47 s).
+  // A BGZF file is not meant (the library tells it by its first member and keeps the BGZF route either way).
+  constexpr long long kDeviceGzipFrom = 90000000;
+  if (device_gzip < 0 && !getenv("G2S_DEVICE_GZIP")) {
+    size_t pos = 0;
+    while (pos <= reads.size()) {
+      size_t e = reads.find(',', pos);
+      if (e == std::string::npos) e = reads.size();
+      // (stat before any open: a pipe among the read files is the library's to read, once)
+      struct stat st;
+      const std::string file = reads.substr(pos, e > pos ? e - pos : 0);
+      if (!file.empty() && stat(file.c_str(), &st) == 0 && S_ISREG(st.st_mode) && (long long)st.st_size >= kDeviceGzipFrom) {
+        if (FILE* f = fopen(file.c_str(), "rb")) {
+          unsigned char magic[2] = {0, 0};
+          if (fread(magic, 1, 2, f) == 2 && magic[0] == 0x1f && magic[1] == 0x8b) g2s_reads_set_device_gzip(1);
+          fclose(f);
+        }
+      }
+      pos = e + 1;
+    }
   }
   // -max-mem is divided by the number of threads (:302) — by an EXPLICIT -nb-cores here: with the option omitted
   // (GATB: all cores) the reference's per-gap budget depends on the host's CPU count, which says nothing about

@@ -342,7 +342,7 @@ extern "C" int g2s_graph_build_files(const char* reads_csv, int k, int solid, in
     const ReadsLoadResult r = load_reads_device(inputs, getenv("G2S_DEVICE") ? atoi(getenv("G2S_DEVICE")) : 0,
                                                 (size_t)piece, env_bytes("G2S_BUILD_TEXT_FIRST_BYTES"),
                                                 env_on("G2S_HOST_INFLATE"), &text, &info, &why, env_bytes("G2S_BUILD_RESIDENT_CAP"),
-                                                env_bam_stream());
+                                                env_bam_stream(), device_gzip_asked());
     if (r == kReadsIoError) return fail(G2S_ERR_IO, why);
     if (r != kReadsOk) { bam_reason = info.bam_reason; bam_anomaly = info.bam_anomaly; }
     if (r == kReadsOk && text.T == 0) {  // (no sequence at all: the empty graph, as the host loader builds it)
@@ -506,7 +506,7 @@ extern "C" int g2s_test_reads_text(const void* bytes, size_t n, int device, size
   std::string why;
   const ReadsLoadResult r = load_reads_device(inputs, device, piece_bytes,
                                               env_bytes("G2S_BUILD_TEXT_FIRST_BYTES"), env_on("G2S_HOST_INFLATE"), &text, &info, &why,
-                                              env_bytes("G2S_BUILD_RESIDENT_CAP"), env_bam_stream());
+                                              env_bytes("G2S_BUILD_RESIDENT_CAP"), env_bam_stream(), device_gzip_asked());
   if (r == kReadsIoError) return fail(G2S_ERR_IO, why);
   if (r != kReadsOk) {
     info.bam_streamed = info.bam_stream_windows = info.bam_stream_peak = 0;  // (nothing of a refused call counts)
@@ -519,6 +519,80 @@ extern "C" int g2s_test_reads_text(const void* bytes, size_t n, int device, size
   const hipError_t e = take ? hipMemcpy(out, text.d_text, take, hipMemcpyDeviceToHost) : hipSuccess;
   free_device_text(&text);
   if (e != hipSuccess) return fail(G2S_ERR_HIP, std::string("g2s_test_reads_text: ") + hipGetErrorString(e));
+  return G2S_OK;
+}
+
+extern "C" int g2s_reads_set_device_gzip(int mode) { return set_device_gzip(mode); }
+// TEST HOOK (include/g2s_test.h)
+extern "C" int g2s_test_last_reads_gzip(uint64_t* files, uint64_t* windows, uint64_t* chunks, uint64_t* starts_found,
+                                        uint64_t* absorbed, uint64_t* members, int* outcome, uint64_t* peak_device_bytes) {
+  ReadsLoadInfo info;
+  {
+    std::lock_guard<std::mutex> lk(g_reads_info_mu);
+    info = g_reads_info;
+  }
+  if (files) *files = info.gzip.files;
+  if (windows) *windows = info.gzip.windows;
+  if (chunks) *chunks = info.gzip.chunks;
+  if (starts_found) *starts_found = info.gzip.starts_found;
+  if (absorbed) *absorbed = info.gzip.absorbed;
+  if (members) *members = info.gzip.members;
+  if (outcome) *outcome = info.gzip.outcome;
+  if (peak_device_bytes) *peak_device_bytes = info.gzip.peak_device_bytes;
+  return G2S_OK;
+}
+// TEST HOOK (include/g2s_test.h)
+extern "C" int g2s_test_gzip_inflate(const void* bytes, size_t n, int device, uint32_t chunk_bytes, uint32_t window_chunks,
+                                     uint8_t* out, size_t cap, size_t* out_n, int* outcome) {
+  if (!bytes || !out_n || (!out && cap) || device < -2) return fail(G2S_ERR_ARG, "g2s_test_gzip_inflate: bad argument");
+  *out_n = 0;
+  if (outcome) *outcome = kGzDone;
+  const uint8_t* p = (const uint8_t*)bytes;
+  std::string all;
+  if (device == -1) {
+    std::string err;
+    if (!reads_text_of_bytes(p, n, "(memory)", &all, nullptr, &err)) return fail(G2S_ERR_IO, err);
+  } else {
+    GzipParams P = gzip_params_from_env();
+    if (chunk_bytes) P.chunk = std::max<uint32_t>(chunk_bytes, 1024);
+    // (0: the whole file in one window)
+    P.window_chunks = window_chunks ? std::max<uint32_t>(window_chunks, 2) : (uint32_t)std::min<uint64_t>(65535, std::max<uint64_t>(n / P.chunk + 1, 2));
+    std::unique_ptr<GzipBackend> B;
+    if (device >= 0) {
+      if (!filter_device_usable(device)) return fail(G2S_ERR_NO_DEVICE, "g2s_test_gzip_inflate: no usable gfx950 device " + std::to_string(device));
+      std::string why;
+      if (hipSetDevice(device) != hipSuccess) return fail(G2S_ERR_HIP, "g2s_test_gzip_inflate: the device cannot be used");
+      B = make_gzip_device_backend(device, nullptr, P, &why);
+      if (!B) return fail(G2S_ERR_HIP, "g2s_test_gzip_inflate: " + why);
+    } else {
+      B = make_gzip_host_backend(P);
+    }
+    GzipStats st;
+    std::string hip_why;
+    const int oc = gzip_route(
+        p, n, P, *B, &st, []() -> uint32_t { return 0; },
+        [&](const uint8_t* from, uint64_t m, bool) -> bool {
+          if (!m) return true;
+          const size_t at = all.size();
+          all.resize(at + m);
+          if (device < 0) {
+            memcpy(&all[at], from, m);
+            return true;
+          }
+          const hipError_t e = hipMemcpy(&all[at], from, m, hipMemcpyDeviceToHost);
+          if (e != hipSuccess) hip_why = hipGetErrorString(e);
+          return e == hipSuccess;
+        });
+    ReadsLoadInfo info;
+    info.gzip = st;
+    info.gzip.peak_device_bytes = B->device_bytes();
+    set_reads_info(info);
+    if (oc == kGzHip) return fail(G2S_ERR_HIP, "g2s_test_gzip_inflate: " + (hip_why.empty() ? B->why : hip_why));
+    if (outcome) *outcome = oc;
+    if (oc != kGzDone) return G2S_OK;  // (given back: no bytes)
+  }
+  *out_n = all.size();
+  if (!all.empty()) memcpy(out, all.data(), std::min(cap, all.size()));
   return G2S_OK;
 }
 

@@ -312,6 +312,18 @@ G2S_INF_FN uint32_t crc_x8n(uint32_t bytes) {
     if (bytes & 1u) p = crc_mul(t.v[k & 31u], p);
   return p;
 }
+// the same for a length of 64 bits (gzip_chunks.h: a gzip member may hold more than 4 GiB), the power squared as the
+// length's bits go by
+G2S_INF_FN uint32_t crc_x8n64(uint64_t bytes) {
+  constexpr CrcPowers t = crc_powers();
+  uint32_t p = 1u << 31, sq = t.v[3];  // x^0, x^8
+  for (; bytes; bytes >>= 1) {
+    if (bytes & 1u) p = crc_mul(sq, p);
+    sq = crc_mul(sq, sq);
+  }
+  return p;
+}
+G2S_INF_FN uint32_t crc_shift64(uint32_t crc, uint64_t bytes_behind) { return crc_mul(crc_x8n64(bytes_behind), crc); }
 // the running (not yet inverted) CRC over one more byte
 G2S_INF_FN uint32_t crc_byte(const uint32_t* table, uint32_t c, uint8_t v) { return table[(c ^ v) & 0xFFu] ^ (c >> 8); }
 // CRC(A || B) = crc_shift(CRC(A), |B|) ^ CRC(B), for finished CRCs; an empty piece has CRC 0

@@ -3,7 +3,9 @@
 // For the sequences s0 ... s(n-1) of a list of FASTA/FASTQ (and BAM: bam_reads.h) files the build's text is s0 N s1 N ... s(n-1) N.  The device
 // loader makes it in device memory from the files' raw bytes, a piece at a time, with the kernels k_fastx_* (the state
 // machine of fastx_machine.h); gzip input is inflated on the way: BGZF members on the device (bgzf_inflate.h), any
-// other gzip stream by zlib into the staging buffers.  The host loader (fastx.hpp) is the fallback and the authority.
+// other gzip stream by zlib into the staging buffers — or, when asked for, chunk by chunk on the device too
+// (gzip_inflate.h), zlib reading again what that route gives back.  The host loader (fastx.hpp) is the fallback and the
+// authority.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -11,11 +13,12 @@
 #include <vector>
 
 #include "fastx_machine.h"
+#include "gzip_inflate.h"
 
 namespace g2s {
 
 // how a file's bytes were inflated
-enum ReadsInflate : int { kInflateNone = 0, kInflateZlib = 1, kInflateDevice = 2, kInflateMixed = 3 };
+enum ReadsInflate : int { kInflateNone = 0, kInflateZlib = 1, kInflateDevice = 2, kInflateMixed = 3, kInflateDeviceGzip = 4 };
 
 // who wrote the text of the BAM files among the read files (g2s_test_last_reads_bam), and when not the kernels, why
 enum BamReadsReason : int {
@@ -38,6 +41,9 @@ struct ReadsLoadInfo {
   // the streaming form (g2s_test_last_reads_bam_stream): the BAM files whose text it wrote, the walk windows they took,
   // the largest footprint counted against the limit (slots, candidates, ring, scan scratch and the text's capacity)
   uint64_t bam_streamed = 0, bam_stream_windows = 0, bam_stream_peak = 0;
+  // the plain gzip files the chunked device inflate was tried on (gzip_inflate.h; g2s_test_last_reads_gzip): outcome is the
+  // last file's that was given back to zlib, kGzDone when none was
+  GzipStats gzip;
 };
 
 // one input of the loader: a file by name, or bytes in memory (the test hook)
@@ -75,9 +81,11 @@ enum ReadsLoadResult : int {
 // A BAM file that cannot be resident within the bound takes the streaming form (bam_reads.h) when everything that form
 // holds fits the same bound; bam_stream (G2S_BUILD_BAM_STREAM) 1: the streaming form always, 0: never, -1: by that rule.
 // out->capacity may then exceed device_text_bytes(T).
+// device_gzip: a gzip file that is no BGZF file is inflated chunk by chunk on the device (gzip_inflate.h) and read again by
+// zlib from its first byte when that route gives it back; not with host_inflate.
 ReadsLoadResult load_reads_device(const std::vector<ReadsInput>& inputs, int device, size_t piece, uint64_t first_cap,
                                   bool host_inflate, DeviceText* out, ReadsLoadInfo* info, std::string* err,
-                                  uint64_t resident_cap = 0, int bam_stream = -1);
+                                  uint64_t resident_cap = 0, int bam_stream = -1, bool device_gzip = false);
 void free_device_text(DeviceText* t);
 
 // the machine of fastx_machine.h walked line by line on the host over one file's bytes: the text is appended to *out

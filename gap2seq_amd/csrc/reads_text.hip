@@ -431,7 +431,8 @@ struct Loader {
   hipStream_t own = nullptr, cur = nullptr;
   // (one allocation each for the two raw buffers, for the carry and the tile arrays, and for the two staging buffers:
   // on a small file the calls that make and free them are what the loader costs)
-  DevMem d_raw_both, d_work, d_text;
+  DevMem d_raw_both, d_work, d_text, d_held;
+  bool device_gzip = false;    // gzip files that are no BGZF files take the chunked device inflate (gzip_inflate.h)
   PinMem h_both;
   struct Part {
     void* p = nullptr;
@@ -614,9 +615,8 @@ struct Loader {
     return kReadsOk;
   }
 
-  // the kernels of one piece: m bytes at d_raw[b], the halo behind them unless `last`
-  bool run_piece(int b, uint32_t m, bool last) {
-    const uint8_t* raw = d_raw[b].as<uint8_t>();
+  // the kernels of one piece: m bytes at raw (a 16-byte boundary), the halo behind them unless `last`
+  bool run_piece(const uint8_t* raw, uint32_t m, bool last) {
     FxCarry* carry = d_carry.as<FxCarry>();
     if (m) {
       const uint32_t avail = last ? m : m + 1, ntiles = (m + FX_TILE - 1) / FX_TILE;
@@ -660,6 +660,81 @@ struct Loader {
     return bg != nullptr;
   }
 
+  // A gzip file that is no BGZF file, inflated chunk by chunk on the device (gzip_inflate.h): every window's resolved
+  // bytes go through run_piece where they lie, in pieces of at most `piece` bytes, the byte a window holds back for the
+  // next one kept in d_held.  *done: the route completed the file.  Else the text position, the carry and the counts
+  // are back where the file began, and zlib reads it.  False only when the loader itself cannot go on (*why).
+  bool run_gzip_device(const OpenInput& f, bool* done) {
+    *done = false;
+    FxCarry c0;
+    if (!use_stream(own) || !read_carry(&c0)) return false;
+    const uint64_t bound0 = bound, pieces0 = info->pieces, raw0 = info->raw_bytes;
+    GzipParams P = gzip_params_from_env();
+    P.quarter_rule = true;
+    // the window's buffers count against the loader's bound beside the text; W from what it leaves
+    P.window_chunks = (uint32_t)std::min<uint64_t>(P.window_chunks, std::max<uint64_t>((f.n + P.chunk - 1) / P.chunk, 2));
+    const uint64_t room = mem_limit > cap ? mem_limit - cap : 0;
+    while (P.window_chunks > 2 && gzip_device_bytes(P) > room) P.window_chunks = std::max<uint32_t>(P.window_chunks / 2, 2);
+    info->gzip.files++;
+    auto give_back = [&](int outcome) {
+      info->gzip.outcome = outcome;
+      if (getenv("G2S_DEBUG")) fprintf(stderr, "[g2s]   %s: the device gzip route gave the file back (outcome %d)\n", f.name.c_str(), outcome);
+      // (what the route wrote behind the file's first text position is overwritten by what zlib gives)
+      G2S_HIP_TRY(hipStreamSynchronize(cur));
+      G2S_HIP_TRY(hipMemcpy(d_carry.p, &c0, sizeof c0, hipMemcpyHostToDevice));
+      bound = bound0;
+      info->pieces = pieces0;
+      info->raw_bytes = raw0;
+      have_front = false;
+      return true;
+    };
+    if (gzip_device_bytes(P) > room) return give_back(kGzMemory);
+    std::string w;
+    std::unique_ptr<GzipBackend> B = make_gzip_device_backend(device, cur, P, &w);
+    if (!B) return give_back(kGzHip);
+    info->gzip.peak_device_bytes = std::max<uint64_t>(info->gzip.peak_device_bytes, B->device_bytes());
+    if (!d_held.p) G2S_HIP_TRY(d_held.alloc(16));
+    const size_t step = std::max<size_t>(piece & ~(size_t)15, 16);
+    bool failed = false;
+    GzipStats st;
+    const int outcome = gzip_route(
+        f.mem, f.n, P, *B, &st, [&]() -> uint32_t { return have_front ? 1u : 0u; },
+        [&](const uint8_t* bytes, uint64_t n_new, bool last) -> bool {
+          const uint32_t front = have_front ? 1u : 0u;
+          uint8_t* raw = const_cast<uint8_t*>(bytes) - front;
+          const uint64_t total = front + n_new;
+          if (total == 0 && !last) return true;
+          if (front) G2S_HIP_TRY_AS(hipMemcpyAsync(raw, d_held.p, 1, hipMemcpyDeviceToDevice, cur), (hip_fail(why, what_, e_), failed = true, false));
+          const uint64_t M = last ? total : total - 1;  // (the last byte is held back: it is the next window's halo)
+          for (uint64_t o = 0; o < M || (last && o == 0); o += step) {
+            const uint32_t m = (uint32_t)std::min<uint64_t>(step, M - o);
+            if (!reserve(m) || !run_piece(raw + o, m, last && o + m == M)) { failed = true; return false; }
+            if (M == 0) break;
+          }
+          if (!last) G2S_HIP_TRY_AS(hipMemcpyAsync(d_held.p, raw + M, 1, hipMemcpyDeviceToDevice, cur), (hip_fail(why, what_, e_), failed = true, false));
+          info->raw_bytes += n_new;
+          have_front = !last;
+          return true;
+        });
+    info->gzip.windows += st.windows;
+    info->gzip.chunks += st.chunks;
+    info->gzip.starts_found += st.starts_found;
+    info->gzip.absorbed += st.absorbed;
+    if (failed) return false;  // (a HIP call of the loader's own failed: the host loader takes over)
+    if (outcome != kGzDone) {
+      if (outcome == kGzHip && why) *why = B->why;
+      return give_back(outcome);
+    }
+    info->gzip.members += st.members;
+    if (getenv("G2S_DEBUG"))
+      fprintf(stderr, "[g2s]   %s: inflated on the device, %llu members in %llu windows, %llu chunks with %llu starts found\n", f.name.c_str(),
+              (unsigned long long)st.members, (unsigned long long)st.windows, (unsigned long long)st.chunks, (unsigned long long)st.starts_found);
+    G2S_HIP_TRY(hipStreamSynchronize(cur));  // (the pieces read the backend's buffer, which goes with B)
+    have_front = false;
+    *done = true;
+    return true;
+  }
+
   // One file.  kReadsOk, kReadsGaveUp (*why) or kReadsIoError (io_error).
   ReadsLoadResult run_file(const ReadsInput& in, int* how) {
     OpenInput f;
@@ -671,9 +746,16 @@ struct Loader {
       mapped.mem_n = f.n;
       return run_bam_file(mapped, how);
     }
-    enum { PLAIN, ZLIB, BGZF } mode = !f.gz ? PLAIN : ZLIB;
+    enum { PLAIN, ZLIB, BGZF, DEVGZ } mode = !f.gz ? PLAIN : ZLIB;
     size_t bsize = 0, doff = 0;
     if (f.gz && !host_inflate && bgzf_member(f.mem, f.n, &bsize, &doff)) mode = BGZF;
+    else if (f.gz && !host_inflate && device_gzip) mode = DEVGZ;
+    if (mode == DEVGZ) {
+      bool done = false;
+      if (!run_gzip_device(f, &done)) return kReadsGaveUp;
+      if (done) { *how = kInflateDeviceGzip; return kReadsOk; }
+      mode = ZLIB;  // (given back: zlib reads the file from its first byte, and says what is wrong with it if anything is)
+    }
     std::unique_ptr<GzipReader> zr;
     if (mode == ZLIB) zr.reset(new GzipReader(f.mem, f.n));
     bool used_zlib = false, used_dev = false;
@@ -752,7 +834,7 @@ struct Loader {
       }
       const size_t availb = front + n_new;
       const uint32_t m = (uint32_t)(last ? availb : availb - 1);
-      if (!reserve(m) || !run_piece(b, m, last)) return kReadsGaveUp;
+      if (!reserve(m) || !run_piece(raw, m, last)) return kReadsGaveUp;
       G2S_HIP_TRY_AS(hipEventRecord(done[b].e, cur), (hip_fail(why, what_, e_), kReadsGaveUp));
       used[b] = true;
       info->raw_bytes += n_new;
@@ -777,7 +859,7 @@ struct Loader {
 
 ReadsLoadResult load_reads_device(const std::vector<ReadsInput>& inputs, int device, size_t piece, uint64_t first_cap,
                                   bool host_inflate, DeviceText* out, ReadsLoadInfo* info, std::string* err,
-                                  uint64_t resident_cap, int bam_stream) {
+                                  uint64_t resident_cap, int bam_stream, bool device_gzip) {
   *info = ReadsLoadInfo();
   if (!filter_device_usable(device)) { *err = "no usable gfx950 device " + std::to_string(device); return kReadsGaveUp; }
   // the text's bound: an uncompressed file gives no more text than it has bytes; compressed input has no bound
@@ -822,6 +904,7 @@ ReadsLoadResult load_reads_device(const std::vector<ReadsInput>& inputs, int dev
   L.bam_window = piece;
   L.resident_cap = resident_cap;
   L.bam_stream = bam_stream;
+  L.device_gzip = device_gzip;
   L.info = info;
   L.why = err;
   // (compressed reads: four times their bytes to begin with, and from there by doubling)

@@ -261,6 +261,12 @@ _SIGS = {
     "g2s_test_last_filter_rows": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
                                             C.POINTER(C.c_uint64), C.POINTER(C.c_int)]),
     "g2s_filter_set_one_pass": (C.c_int, [C.c_int]),
+    "g2s_reads_set_device_gzip": (C.c_int, [C.c_int]),
+    "g2s_test_gzip_inflate": (C.c_int, [C.c_char_p, C.c_size_t, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint8),
+                                        C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),
+    "g2s_test_last_reads_gzip": (C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                           C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                           C.POINTER(C.c_int), C.POINTER(C.c_uint64)]),
     "g2s_test_last_filter_text": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
                                             C.POINTER(C.c_uint64)]),
     "g2s_test_bam_text": (C.c_int, [C.c_char_p, C.c_size_t, C.c_int, C.POINTER(C.c_uint32), C.c_uint64, C.c_int, C.c_int,
@@ -1229,7 +1235,7 @@ def reads_text(data, device=-1, piece_bytes=0):
 def last_reads_load():
     """TEST HOOK binding (g2s_test_last_reads_load): dict(files, raw_bytes, positions, records, pieces, on_device,
     inflate, grows) of the process's last Graph.from_files or reads_text; inflate is a list with one of "none", "zlib",
-    "device", "mixed" a file"""
+    "device", "mixed", "device-gzip" a file (the last only when set_device_gzip or G2S_DEVICE_GZIP asked for it)"""
     f, rb, ps, rc, pc, gr = (C.c_uint64() for _ in range(6))
     on = C.c_int()
     _check(load_library().g2s_test_last_reads_load(C.byref(f), None, None, None, None, None, None, 0, None))
@@ -1237,7 +1243,7 @@ def last_reads_load():
     _check(load_library().g2s_test_last_reads_load(C.byref(f), C.byref(rb), C.byref(ps), C.byref(rc), C.byref(pc), C.byref(on),
                                                    how, f.value, C.byref(gr)))
     return dict(files=f.value, raw_bytes=rb.value, positions=ps.value, records=rc.value, pieces=pc.value,
-                on_device=on.value, inflate=[("none", "zlib", "device", "mixed")[x] for x in how[:f.value]], grows=gr.value)
+                on_device=on.value, inflate=[("none", "zlib", "device", "mixed", "device-gzip")[x] for x in how[:f.value]], grows=gr.value)
 
 
 BAM_READS_REASONS = ("kernels", "not asked", "rows anomaly", "over the cap", "hip")
@@ -1262,6 +1268,44 @@ def last_reads_bam_stream():
     f, w, peak = C.c_uint64(), C.c_uint64(), C.c_uint64()
     _check(load_library().g2s_test_last_reads_bam_stream(C.byref(f), C.byref(w), C.byref(peak)))
     return dict(streamed_files=f.value, windows=w.value, peak_device_bytes=peak.value)
+
+
+GZIP_OUTCOMES = ("done", "too few starts", "boundary mismatch", "slot full", "corrupt", "trailer", "memory", "hip", "header")
+
+
+def set_device_gzip(mode=1):
+    """g2s_reads_set_device_gzip: 1 asks for the chunked device inflate of plain gzip read files in every later
+    Graph.from_files of the process, 0 forbids it, -1 follows G2S_DEVICE_GZIP.  Returns the previous mode."""
+    return load_library().g2s_reads_set_device_gzip(int(mode))
+
+
+def gzip_inflate(data, device=-1, chunk_bytes=0, window_chunks=0):
+    """TEST HOOK binding (g2s_test_gzip_inflate): a whole gzip file inflated on `device` (>= 0: the kernels; -1: zlib;
+    -2: the kernels' algorithm compiled for the host) in chunks of chunk_bytes and windows of window_chunks chunks (0: the
+    whole file).  Returns (bytes, outcome): outcome one of GZIP_OUTCOMES, and anything but "done" comes with no bytes.
+    Raises G2SError (device -1: a damaged file, with zlib's message)."""
+    lib = load_library()
+    data = bytes(data)
+    cap = max(1 << 16, 8 * len(data))
+    while True:
+        out = (C.c_uint8 * cap)()
+        n, oc = C.c_size_t(0), C.c_int(0)
+        _check(lib.g2s_test_gzip_inflate(data, len(data), device, chunk_bytes, window_chunks, out, cap, C.byref(n), C.byref(oc)))
+        if n.value <= cap:
+            return bytes(out[:n.value]), GZIP_OUTCOMES[oc.value]
+        cap = n.value
+
+
+def last_reads_gzip():
+    """TEST HOOK binding (g2s_test_last_reads_gzip): dict(files, windows, chunks, starts_found, absorbed, members,
+    outcome (one of GZIP_OUTCOMES), peak_device_bytes) of the chunked device inflate in the process's last
+    Graph.from_files, reads_text or gzip_inflate"""
+    v = [C.c_uint64() for _ in range(7)]
+    oc = C.c_int()
+    _check(load_library().g2s_test_last_reads_gzip(C.byref(v[0]), C.byref(v[1]), C.byref(v[2]), C.byref(v[3]), C.byref(v[4]),
+                                                   C.byref(v[5]), C.byref(oc), C.byref(v[6])))
+    return dict(files=v[0].value, windows=v[1].value, chunks=v[2].value, starts_found=v[3].value, absorbed=v[4].value,
+                members=v[5].value, outcome=GZIP_OUTCOMES[oc.value], peak_device_bytes=v[6].value)
 
 
 def bgzf_inflate(data, device=-1):

@@ -591,6 +591,17 @@ void g2s_read_pool_free(g2s_read_pool* p);
  * Outputs, messages and codes are the same bytes on every route; g2s_filter_stats::file_passes says which one ran. */
 int g2s_filter_set_one_pass(int mode);
 
+/* The chunked device inflate of plain gzip read files (ABI 6, additive), process-wide and atomic: 1 asks for it in every
+ * later g2s_graph_build_files, 0 forbids it, -1 (the initial state) follows the environment (G2S_DEVICE_GZIP=1|0, read
+ * per call; off when it is not set).  Returns the previous mode.  With it a read file that is gzip but no BGZF file (a
+ * .fq.gz as gzip(1) writes it) is inflated on the device from many places of its deflate stream at once
+ * (csrc/gzip_inflate.h) instead of by one zlib stream on the host.  The route completes a file only when every chunk
+ * ended at the block start the next one began at and every member's CRC-32 and ISIZE matched; on anything else the file
+ * is read again from its first byte by zlib, so texts, counts, errors and messages are the same bytes either way.
+ * G2S_HOST_READS=1, G2S_HOST_INFLATE=1, G2S_HOST_BUILD, pipes and a missing device keep their routes.
+ * G2S_GZIP_CHUNK_BYTES, G2S_GZIP_WINDOW_CHUNKS and G2S_GZIP_SLOT_RATIO size it (README). */
+int g2s_reads_set_device_gzip(int mode);
+
 /* ---------------------------------------------------------------------------
  *  Page-locked host memory the GPUs can write: a `results` array or fill arena
  *  allocated here is written by the kernels directly (no staging copy) when a

@@ -149,7 +149,8 @@ int g2s_test_reads_text(const void* bytes, size_t n, int device, size_t piece_by
  * the files' bytes after inflation; positions: the text's (bases + 1 a record); records; pieces: the pieces the kernels
  * walked (0 on the host); on_device: the text was made by the kernels (0 also when the device loader or the device
  * count gave up and the host loader took over); inflate[i] for the first min(inflate_cap, files) files: 0 not compressed,
- * 1 zlib on the host, 2 BGZF members inflated on the device, 3 both (BGZF members first, then another gzip stream);
+ * 1 zlib on the host, 2 BGZF members inflated on the device, 3 both (BGZF members first, then another gzip stream),
+ * 4 a plain gzip stream inflated chunk by chunk on the device (only when asked for: g2s_reads_set_device_gzip);
  * grows: how often the text buffer was enlarged.  Any pointer may be NULL. */
 int g2s_test_last_reads_load(uint64_t* files, uint64_t* raw_bytes, uint64_t* positions, uint64_t* records, uint64_t* pieces,
                              int* on_device, int* inflate, uint64_t inflate_cap, uint64_t* grows);
@@ -315,6 +316,30 @@ int g2s_test_bam_store(const void* bytes, size_t n, int device, size_t window, u
  * NULL. */
 int g2s_test_last_filter_store(int* used, uint64_t* records, uint64_t* store_bytes, uint64_t* store_cap, uint64_t* rows_cap,
                                uint64_t* device_bytes, int* overflow);
+
+/* TEST HOOK: a whole gzip file (any members; no BGZF needed) inflated by one of three inflaters, in chunks of chunk_bytes
+ * compressed bytes (0: G2S_GZIP_CHUNK_BYTES or the default) and windows of window_chunks chunks (0: the whole file in
+ * one window).  device >= 0: the kernels of csrc/gzip_inflate.hip on that device — G2S_ERR_NO_DEVICE when it is no
+ * usable gfx950, G2S_ERR_HIP when it refuses; never the host in their place.  device == -1: zlib, the product's host
+ * path.  device == -2: csrc/gzip_chunks.h, the kernels' algorithm, compiled for the host, chunk by chunk.  For -2 and
+ * the kernels *outcome (may be NULL) receives why the route gave the file back (csrc/gzip_inflate.h: GzipOutcome) — 0 it
+ * did not, 1 too few starts (a window that does not reach the file's end found no second start; the loader's rule of a
+ * quarter of the chunks is not applied here), 2 boundary mismatch, 3 slot full, 4 corrupt, 5 a member's CRC-32, ISIZE or
+ * cut trailer, 6 memory, 8 a member header — and then *out_n is 0 and no byte is written: G2S_OK all the same.
+ * device == -1 gives G2S_ERR_IO with zlib's message for a damaged file.  *out_n receives the inflated size; the first
+ * min(cap, size) bytes are written, so a caller whose capacity was too small calls again.  g2s_test_last_reads_gzip
+ * tells the call's windows, chunks and starts afterwards. */
+int g2s_test_gzip_inflate(const void* bytes, size_t n, int device, uint32_t chunk_bytes, uint32_t window_chunks, uint8_t* out,
+                          size_t cap, size_t* out_n, int* outcome);
+
+/* TEST HOOK: the chunked device inflate (csrc/gzip_inflate.h) in the process's last g2s_graph_build_files,
+ * g2s_test_reads_text or g2s_test_gzip_inflate.  files: the gzip files the route was tried on; windows; chunks: the
+ * chunks those windows covered; starts_found: the block starts the finder gave; absorbed: the chunks decoded by the chunk
+ * in front of them; members: the gzip members of the files the route completed; outcome: the GzipOutcome of the last
+ * file given back to zlib (0: none was); peak_device_bytes: the largest window footprint asked of the allocator.  All 0
+ * when the mode was not asked for.  Any pointer may be NULL. */
+int g2s_test_last_reads_gzip(uint64_t* files, uint64_t* windows, uint64_t* chunks, uint64_t* starts_found, uint64_t* absorbed,
+                             uint64_t* members, int* outcome, uint64_t* peak_device_bytes);
 
 #ifdef __cplusplus
 }

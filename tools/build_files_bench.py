@@ -16,6 +16,12 @@ BAM file had to be converted to before BAM was read — and through the streamin
   python tools/build_files_bench.py --config C4 --once fastq     # one device-loader build in this process (kernel trace)
   python tools/build_files_bench.py --config C4 --bam --reps 5 [--parent PATH/TO/libg2s_hip.so [--parent-bam]]
   python tools/build_files_bench.py --config C4 --bam --read-length 250 --once bam     (or --once stream)
+  python tools/build_files_bench.py --config C4 --gzip --reps 3 --parent PATH/TO/libg2s_hip.so [--genome BP] [--read-length L] [--slot-ratio R]
+  python tools/build_files_bench.py --config C4 --gzip --once gzip [--chunk BYTES]    # the chunked device inflate, one build (kernel trace)
+
+--gzip: the gzip FASTQ file alone (--quality random: qualities drawn from eight values, as a sequencer's, in place of a
+constant line): the chunked device inflate of gap2seq_amd/csrc/gzip_inflate.hip asked for (G2S_DEVICE_GZIP=1) at chunks of 256 KiB
+and of 1 MiB, the same build with the mode off (zlib), and --parent's library.
 
 Needs a GPU."""
 import argparse
@@ -35,7 +41,8 @@ import zlib
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 SWITCHES = ("G2S_HOST_BUILD", "G2S_HOST_READS", "G2S_HOST_INFLATE", "G2S_BUILD_PASS_KEYS", "G2S_BUILD_PIECE_BYTES",
-            "G2S_BUILD_TEXT_FIRST_BYTES", "G2S_BUILD_RESIDENT_CAP", "G2S_BUILD_BAM_STREAM")
+            "G2S_BUILD_TEXT_FIRST_BYTES", "G2S_BUILD_RESIDENT_CAP", "G2S_BUILD_BAM_STREAM", "G2S_DEVICE_GZIP",
+            "G2S_GZIP_CHUNK_BYTES", "G2S_GZIP_WINDOW_CHUNKS", "G2S_GZIP_SLOT_RATIO")
 
 
 def bgzf(raw, out):
@@ -76,17 +83,29 @@ def cut_reads(lines, length, k):
     return out + [b""]
 
 
-def write_files(config, d, with_bam=False, read_length=0):
+def write_files(config, d, with_bam=False, read_length=0, genome=0, only_gzip=False, quality="constant"):
     import bench
     from gap2seq_amd import lib as P
     genome_bp, k = bench.CONFIGS[config][:2]
+    genome_bp = genome or genome_bp
     fa = P.G2S.synth_genome(genome_bp, 3, bench.GENOME_SEED).encode("ascii")
     lines = fa.split(b"\n")
     if read_length:  # (bench.py's read sets are a few sequences of the genome's length: short reads of the same k-mers)
         lines = cut_reads(lines, max(read_length, k), k)
         fa = b"\n".join(lines)
-    fq = b"".join(b"@" + lines[i][1:] + b"\n" + lines[i + 1] + b"\n+\n" + b"I" * len(lines[i + 1]) + b"\n"
+    if quality == "random":
+        import random
+        pool = bytes(random.Random(5).choices(b"FFFFF:,#", k=1 << 20))
+        qual = lambda i, n: pool[(i * 7919) % ((1 << 20) - n):][:n] if n < (1 << 19) else (pool * (n // len(pool) + 1))[:n]
+    else:
+        qual = lambda i, n: b"I" * n
+    fq = b"".join(b"@" + lines[i][1:] + b"\n" + lines[i + 1] + b"\n+\n" + qual(i, len(lines[i + 1])) + b"\n"
                   for i in range(0, len(lines) - 1, 2))
+    if only_gzip:
+        path = os.path.join(d, "reads.fastq.gz")
+        with gzip.GzipFile(path, "wb", compresslevel=6, mtime=0) as f:
+            f.write(fq)
+        return k, {"fastq.gz": path}
     paths = {f: os.path.join(d, "reads." + f) for f in ("fasta", "fastq", "fastq.gz", "bgzf.fastq.gz")}
     open(paths["fasta"], "wb").write(fa)
     open(paths["fastq"], "wb").write(fq)
@@ -139,6 +158,13 @@ def child(library, path, k, threads):
             streamed, windows, peak = C.c_uint64(), C.c_uint64(), C.c_uint64()
             lib.g2s_test_last_reads_bam_stream(C.byref(streamed), C.byref(windows), C.byref(peak))
             out.update(bam_streamed=streamed.value, bam_stream_windows=windows.value, bam_stream_peak=peak.value)
+        lib.g2s_test_last_reads_gzip.argtypes = [C.POINTER(C.c_uint64)] * 6 + [C.POINTER(C.c_int), C.POINTER(C.c_uint64)]
+        v = [C.c_uint64() for _ in range(7)]
+        oc = C.c_int()
+        lib.g2s_test_last_reads_gzip(*[C.byref(x) for x in v[:6]], C.byref(oc), C.byref(v[6]))
+        if v[0].value:  # (the chunked device inflate was tried: include/g2s_test.h)
+            out.update(gzip=dict(windows=v[1].value, chunks=v[2].value, starts_found=v[3].value, absorbed=v[4].value,
+                                 members=v[5].value, outcome=oc.value, peak_device_bytes=v[6].value))
     except AttributeError:  # (the parent's library)
         pass
     lib.g2s_graph_free(h)
@@ -154,6 +180,12 @@ def main():
     ap.add_argument("--bam", action="store_true", help="the BAM form: device route, streaming form, host loader, and --parent on BGZF FASTQ")
     ap.add_argument("--parent-bam", action="store_true", help="with --bam and --parent: the parent's library on the BAM file, both ways")
     ap.add_argument("--read-length", type=int, default=0, help="cut the sequences into reads of this length that overlap by k - 1")
+    ap.add_argument("--gzip", action="store_true", help="the gzip FASTQ file alone: the chunked device inflate, zlib, and --parent")
+    ap.add_argument("--genome", type=int, default=0, help="base pairs of the synthetic genome in place of the config's")
+    ap.add_argument("--quality", default="constant", choices=["constant", "random"])
+    ap.add_argument("--slot-ratio", type=int, default=0, help="G2S_GZIP_SLOT_RATIO of the device-gzip ways")
+    ap.add_argument("--more-ways", action="store_true", help="--gzip: chunks of 64 KiB in windows of 512 and of 256 KiB in windows of 256 too")
+    ap.add_argument("--chunk", type=int, default=0, help="--once gzip: G2S_GZIP_CHUNK_BYTES")
     ap.add_argument("--once", default="", help="one device-loader build of this form in this process, nothing else")
     ap.add_argument("--child", nargs=4, metavar=("LIBRARY", "PATH", "K", "THREADS"), help=argparse.SUPPRESS)
     args = ap.parse_args()
@@ -162,14 +194,21 @@ def main():
         return 0
     here = os.path.join(ROOT, "gap2seq_amd", "libg2s_hip.so")
     with tempfile.TemporaryDirectory() as d:
-        k, paths = write_files(args.config, d, args.bam or args.once in ("bam", "stream"), args.read_length)
+        k, paths = write_files(args.config, d, args.bam or args.once in ("bam", "stream"), args.read_length, args.genome,
+                               args.gzip, args.quality)
         sizes = {f: os.path.getsize(p) for f, p in paths.items()}
         if args.once:
             for name in SWITCHES:
                 os.environ.pop(name, None)
             if args.once == "stream":  # (the BAM file through the streaming form)
                 os.environ["G2S_BUILD_BAM_STREAM"] = "1"
-            child(here, paths["bam" if args.once == "stream" else args.once], k, args.threads)
+            if args.once == "gzip":
+                os.environ["G2S_DEVICE_GZIP"] = "1"
+                if args.chunk:
+                    os.environ["G2S_GZIP_CHUNK_BYTES"] = str(args.chunk)
+                if args.slot_ratio:
+                    os.environ["G2S_GZIP_SLOT_RATIO"] = str(args.slot_ratio)
+            child(here, paths[{"stream": "bam", "gzip": "fastq.gz"}.get(args.once, args.once)], k, args.threads)
             return 0
         ways = []  # (name, form, library, switches)
         if args.bam:
@@ -179,12 +218,22 @@ def main():
                 ways += [("parent device bam", "bam", args.parent, {}), ("parent host-reads bam", "bam", args.parent, {"G2S_HOST_READS": "1"})]
             elif args.parent:
                 ways.append(("parent bgzf.fastq.gz", "bgzf.fastq.gz", args.parent, {}))
-        for f in ([] if args.bam else paths):
+        if args.gzip:
+            ratio = {"G2S_GZIP_SLOT_RATIO": str(args.slot_ratio)} if args.slot_ratio else {}
+            ways = [("device-gzip 256K fastq.gz", "fastq.gz", here, dict(ratio, G2S_DEVICE_GZIP="1", G2S_GZIP_CHUNK_BYTES=str(256 << 10))),
+                    ("device-gzip 1M fastq.gz", "fastq.gz", here, dict(ratio, G2S_DEVICE_GZIP="1", G2S_GZIP_CHUNK_BYTES=str(1 << 20))),
+                    ("zlib fastq.gz", "fastq.gz", here, {})]
+            for chunk, window in ([(64 << 10, 512), (256 << 10, 256)] if args.more_ways else []):
+                ways.append(("device-gzip %dK x %d fastq.gz" % (chunk >> 10, window), "fastq.gz", here,
+                             dict(ratio, G2S_DEVICE_GZIP="1", G2S_GZIP_CHUNK_BYTES=str(chunk), G2S_GZIP_WINDOW_CHUNKS=str(window))))
+            if args.parent:
+                ways.append(("parent fastq.gz", "fastq.gz", args.parent, {}))
+        for f in ([] if args.bam or args.gzip else paths):
             ways.append(("device " + f, f, here, {}))
             ways.append(("host-reads " + f, f, here, {"G2S_HOST_READS": "1"}))
             if args.parent and not f.endswith(".gz"):
                 ways.append(("parent " + f, f, args.parent, {}))
-        if not args.bam:
+        if not args.bam and not args.gzip:
             ways.append(("device+zlib bgzf.fastq.gz", "bgzf.fastq.gz", here, {"G2S_HOST_INFLATE": "1"}))
         runs = {w[0]: [] for w in ways}
         for rep in range(args.reps):
@@ -207,7 +256,7 @@ def main():
                                  raw_bytes=rs[0].get("raw_bytes"), positions=rs[0].get("positions"),
                                  bam_by_kernels=rs[0].get("bam_by_kernels"), bam_reason=rs[0].get("bam_reason"),
                                  bam_streamed=rs[0].get("bam_streamed"), bam_stream_windows=rs[0].get("bam_stream_windows"),
-                                 bam_stream_peak=rs[0].get("bam_stream_peak"))
+                                 bam_stream_peak=rs[0].get("bam_stream_peak"), gzip=rs[0].get("gzip"))
     out["same_kmers"] = len({v["kmers"] for v in out["ways"].values()}) == 1
     print(json.dumps(out))
     return 0 if out["same_kmers"] else 1
