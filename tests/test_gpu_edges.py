@@ -6,14 +6,12 @@ the path count's saturation at MAX_PATHS = 2^30 - 2; beside them D = lmf + rmf +
 32768 (16-bit depths) and fuz 31 / 32 (32 seeds and targets).  tests/test_seg_model.py proves on the host that each
 gap is where the table says.  Every case asserts where the gap went, from the library's own records (G2S_SEG_DUMP,
 G2S_D2_LOG, g2s_timing), and that what it computed is the oracle's, field by field."""
-import json
 import os
-import subprocess
-import sys
 
 import pytest
 
 import cases
+from d2_witness import _d2_log
 from test_gpu_parity import _check_batch, _gaps
 
 pytestmark = pytest.mark.gpu
@@ -155,45 +153,7 @@ def test_count_ladders_best_only_and_skip_rule(product, oracle, edge_tier, skip,
         assert tm.resident_launches == 1 and tm.resident_fallbacks == 0
 
 
-_D2_CHILD = r"""
-import json, os, sys
-sys.path[:0] = [os.path.join(sys.argv[1]), os.path.join(sys.argv[1], "tests")]
-import cases
-from gap2seq_amd import lib as P
-P.load_library()
-names = json.loads(sys.argv[2])
-seqs, gaps, idx = cases.edge_ladder_list(names, pad=100)
-pg = P.Graph.from_seqs(seqs, 31, 1)
-sess = P.Session(pg, 0, d_err=10, randseed=5)
-res, tm = sess.fill_batch([P.Gap(g["left"], g["right"], g["gap_len"], g["lmf"], g["rmf"]) for g in gaps], True)
-sess.destroy()
-pg.free()
-print(json.dumps(dict(idx=idx, watchdog=tm.watchdog_gaps, resident=tm.resident_launches, fallbacks=tm.resident_fallbacks)))
-"""
-
 D2_LADDERS = ["seg191", "seg192", "seg193", "cl255", "cl256", "cl257", "indel20"]
-
-
-def _d2_log(tmp_path, names, **env):
-    """{planted gap name: [dict(kernel=0 small | 1 big, rc=0 taken | passed on)]} from G2S_D2_LOG (written when the
-    session ends; in a child process, as the switch that turns the log on is read once per process).  The list is
-    finished on the device with phase D2 there (G2S_DEVICE_D2=1); g2s_d2_small runs on one wave a closure, so that
-    the log's workgroup-size bit tells the two instantiations apart."""
-    log = tmp_path / ("d2_%s.log" % "_".join("%s%s" % kv for kv in sorted(env.items())))
-    env = dict(os.environ, G2S_DEVICE_D2="1", G2S_D2_PROF="1", G2S_D2_LOG=str(log), G2S_RESIDENT="1", G2S_D2_SMALL_WAVES="1",
-               **env)
-    out = subprocess.run([sys.executable, "-c", _D2_CHILD, ROOT, json.dumps(names)], env=env, capture_output=True,
-                         text=True, timeout=300)
-    assert out.returncode == 0, out.stderr[-3000:]
-    r = json.loads(out.stdout.strip().splitlines()[-1])
-    assert r["watchdog"] == 0 and r["resident"] == 1 and r["fallbacks"] == 0
-    rows = {}
-    for line in open(log):
-        w = line.split()
-        if len(w) == 16:
-            w = [int(x) for x in w]
-            rows.setdefault(w[0] & 0xFFFFFFFF, []).append(dict(kernel=w[15] & 1, rc=(w[2] >> 32) & 0xFFFF))
-    return {name: rows.get(i, []) for i, name in zip(r["idx"], names)}
 
 
 def test_d2_instantiation_by_closure_size(product, tmp_path):
