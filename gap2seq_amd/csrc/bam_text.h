@@ -44,6 +44,10 @@ struct BamTextAsk {
   bool pool = false;      // the pool's arrays (else the FASTA texts)
   bool names = false;     // pool: names too
   bool unmapped = false;  // the unmapped reads too
+  // pool form on the device: the bases stay there (BamText::d_text) in the pooled build's layout, every read followed
+  // by one 'N'; no bases and no names come down, pnoff does.  The host walk does not know it and makes what it always
+  // makes.
+  bool device_text = false;
 };
 
 // what pass B makes, on the host walk and on the device alike (the members stand in the order the two-pass route has
@@ -60,6 +64,12 @@ struct BamText {
   std::string pbases, pnames;
   std::vector<uint64_t> pboff{0}, pnoff{0};
   std::vector<uint32_t> pidx, punmapped;
+  // device_text: one device allocation of d_bytes bytes, the caller's to hipFree on `d_device` — the text, and at
+  // d_start the held reads' starts in it (pboff.size() entries; pboff[i] is d_start[i] - i); pbases and pnames empty
+  void* d_text = nullptr;
+  const uint64_t* d_start = nullptr;
+  uint64_t d_bytes = 0;
+  int d_device = -1;
 };
 
 // Pass B on the device of `rows`, whose resident stream and record offsets must be there; sel[r] != 0 for the rows of

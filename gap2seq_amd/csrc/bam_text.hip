@@ -11,6 +11,10 @@
 //                         the held ones, its index among the unmapped ones; entry n holds the totals, which size every
 //                         output before it is written (k_totals gathers them for one copy down).
 //   entries   k_entries   pool form: base_off / name_off per held record, the unmapped list, the index by row
+//                         (BamTextAsk::device_text: a held record's bases count one byte more, the 'N' k_decode writes
+//                         behind them, so that base_off is the read's start in the pooled build's text; that text and
+//                         the starts go into an allocation of their own, which the caller keeps, and nothing of
+//                         either output comes down but the offsets)
 //   decode    k_decode    a wave a row, the lanes over the row's output bytes, 64 consecutive bytes a step, so that a
 //                         wave's store is one run of bytes whatever the read's length.  A wave takes 64 rows at a time,
 //                         finds the ones with output by ballot and visits those alone.
@@ -28,6 +32,7 @@
 #include "bam.hpp"
 #include "bam_decode.h"
 #include "bam_text.h"
+#include "device_pool.h"
 #include "hip_host.h"
 
 namespace {
@@ -71,7 +76,7 @@ __global__ void __launch_bounds__(kBlock) k_lengths(const uint8_t* __restrict__ 
           if (pool) {
             h = 1;
             u = is_un ? 1u : 0u;
-            a = (uint64_t)l_seq;
+            a = (uint64_t)l_seq + (pool == 2 ? 1u : 0u);  // (2: the build's layout, an 'N' behind every read)
             b = names ? nl + 2u : 0u;
           } else {
             const uint64_t fasta = (uint64_t)nl + 5u + (uint64_t)l_seq;  // > name /1 \n bases \n
@@ -187,6 +192,7 @@ bool bam_text_device(const BamRowsDevice& rows, const uint8_t* sel, const BamTex
   if (!n) return true;
   hipStream_t s = (hipStream_t)rows.stream();
   G2S_HIP_TRY(hipSetDevice(rows.device()));
+  const bool device_text = ask.pool && ask.device_text;
   const size_t m = (size_t)n + 1;
   const unsigned groups = (unsigned)((m + kBlock - 1) / kBlock);
   Buf d_sel, d_len_a, d_len_b, d_held, d_un, d_off_a, d_off_b, d_idx, d_uidx, d_tot, d_tmp;
@@ -210,7 +216,7 @@ bool bam_text_device(const BamRowsDevice& rows, const uint8_t* sel, const BamTex
   G2S_HIP_TRY(hipMemcpyAsync(d_sel.p, sel, (size_t)n, hipMemcpyHostToDevice, s));
   G2S_HIP_TRY(hipMemsetAsync(d_tot.p, 0, sizeof(Totals), s));
   hipLaunchKernelGGL(k_lengths, dim3(groups), dim3(kBlock), 0, s, (const uint8_t*)rows.stream_buffer(), rows.stream_bytes(),
-                     (const uint64_t*)R.rec_off, n, d_sel.as<const uint8_t>(), (int)ask.pool, (int)ask.names, (int)ask.unmapped,
+                     (const uint64_t*)R.rec_off, n, d_sel.as<const uint8_t>(), ask.pool ? (device_text ? 2 : 1) : 0, (int)ask.names, (int)ask.unmapped,
                      d_len_a.as<uint64_t>(), d_len_b.as<uint64_t>(), d_held.as<uint32_t>(), d_un.as<uint32_t>(), d_tot.as<Totals>());
   G2S_HIP_TRY(hipGetLastError());
   // ---- the offsets
@@ -235,16 +241,17 @@ bool bam_text_device(const BamRowsDevice& rows, const uint8_t* sel, const BamTex
   }
   // ---- the outputs, sized by their counts
   Buf d_out_a, d_out_b, d_boff, d_noff, d_unl, d_pidx;
-  Arena outs;
-  outs.add(&d_out_a, (size_t)bytes_a);
-  outs.add(&d_out_b, (size_t)bytes_b);
+  Arena outs, keep;  // (keep: what a device_text caller takes over)
+  (device_text ? keep : outs).add(&d_out_a, (size_t)bytes_a);
+  outs.add(&d_out_b, device_text ? 0 : (size_t)bytes_b);
   if (ask.pool) {
-    outs.add(&d_boff, ((size_t)n_held + 1) * 8);
+    (device_text ? keep : outs).add(&d_boff, ((size_t)n_held + 1) * 8);
     outs.add(&d_noff, ((size_t)n_held + 1) * 8);
     outs.add(&d_unl, (size_t)n_un * 4);
     outs.add(&d_pidx, (size_t)n * 4);
   }
   G2S_HIP_TRY(outs.get());
+  if (device_text) G2S_HIP_TRY(keep.get());
   const unsigned waves_wanted = (unsigned)((n + kWave - 1) / kWave);
   const unsigned dgroups = std::max(1u, std::min((waves_wanted + kBlock / kWave - 1) / (kBlock / kWave), 256u * 16u));
   if (ask.pool) {
@@ -254,7 +261,7 @@ bool bam_text_device(const BamRowsDevice& rows, const uint8_t* sel, const BamTex
                        d_unl.as<uint32_t>(), d_pidx.as<uint32_t>());
     hipLaunchKernelGGL((k_decode<kBases, kName>), dim3(dgroups), dim3(kBlock), 0, s, (const uint8_t*)rows.stream_buffer(),
                        (const uint64_t*)R.rec_off, n, d_off_a.as<const uint64_t>(), d_off_b.as<const uint64_t>(),
-                       d_out_a.as<uint8_t>(), bytes_a, d_out_b.as<uint8_t>(), bytes_b);
+                       d_out_a.as<uint8_t>(), bytes_a, d_out_b.as<uint8_t>(), device_text ? 0 : bytes_b);  // (cap 0: no names)
   } else {
     hipLaunchKernelGGL((k_decode<kFasta, kFasta>), dim3(dgroups), dim3(kBlock), 0, s, (const uint8_t*)rows.stream_buffer(),
                        (const uint64_t*)R.rec_off, n, d_off_a.as<const uint64_t>(), d_off_b.as<const uint64_t>(),
@@ -263,20 +270,27 @@ bool bam_text_device(const BamRowsDevice& rows, const uint8_t* sel, const BamTex
   G2S_HIP_TRY(hipGetLastError());
   // ---- down, once
   if (ask.pool) {
-    out->pbases.resize((size_t)bytes_a);
+    if (!device_text) out->pbases.resize((size_t)bytes_a);
     out->pboff.assign((size_t)n_held + 1, 0);
     out->punmapped.assign((size_t)n_un, 0);
-    if (bytes_a) G2S_HIP_TRY(hipMemcpyAsync(&out->pbases[0], d_out_a.p, (size_t)bytes_a, hipMemcpyDeviceToHost, s));
+    if (bytes_a && !device_text) G2S_HIP_TRY(hipMemcpyAsync(&out->pbases[0], d_out_a.p, (size_t)bytes_a, hipMemcpyDeviceToHost, s));
     G2S_HIP_TRY(hipMemcpyAsync(out->pboff.data(), d_boff.p, ((size_t)n_held + 1) * 8, hipMemcpyDeviceToHost, s));
     if (n_un) G2S_HIP_TRY(hipMemcpyAsync(out->punmapped.data(), d_unl.p, (size_t)n_un * 4, hipMemcpyDeviceToHost, s));
     G2S_HIP_TRY(hipMemcpyAsync(out->pidx.data(), d_pidx.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
     if (ask.names) {
-      out->pnames.resize((size_t)bytes_b);
+      if (!device_text) out->pnames.resize((size_t)bytes_b);
       out->pnoff.assign((size_t)n_held + 1, 0);
-      if (bytes_b) G2S_HIP_TRY(hipMemcpyAsync(&out->pnames[0], d_out_b.p, (size_t)bytes_b, hipMemcpyDeviceToHost, s));
+      if (bytes_b && !device_text) G2S_HIP_TRY(hipMemcpyAsync(&out->pnames[0], d_out_b.p, (size_t)bytes_b, hipMemcpyDeviceToHost, s));
       G2S_HIP_TRY(hipMemcpyAsync(out->pnoff.data(), d_noff.p, ((size_t)n_held + 1) * 8, hipMemcpyDeviceToHost, s));
     }
-    G2S_HIP_TRY(hipStreamSynchronize(s));
+    G2S_HIP_TRY(hipStreamSynchronize(s));  // (a device_text caller reads the text from other streams from here on)
+    if (device_text) {
+      for (size_t i = 0; i <= (size_t)n_held; i++) out->pboff[i] -= i;  // (the starts without the separators in front)
+      out->d_start = d_boff.as<const uint64_t>();
+      out->d_bytes = keep.bytes;
+      out->d_device = rows.device();
+      out->d_text = keep.base.release();
+    }
   } else {
     std::vector<uint64_t> off(m);
     out->text.resize((size_t)bytes_a);
@@ -292,6 +306,19 @@ bool bam_text_device(const BamRowsDevice& rows, const uint8_t* sel, const BamTex
       }
     out->n_unmapped = (int64_t)n_un;
   }
+  return true;
+}
+
+void device_pool_release(int device, void* p) {
+  if (!p) return;
+  (void)hipSetDevice(device);
+  (void)hipFree(p);
+}
+
+bool device_pool_copy_down(int device, const void* d_text, uint64_t off, uint64_t n, void* dst, std::string* why) {
+  if (!n) return true;
+  G2S_HIP_TRY(hipSetDevice(device));
+  G2S_HIP_TRY(hipMemcpy(dst, (const uint8_t*)d_text + off, (size_t)n, hipMemcpyDeviceToHost));
   return true;
 }
 

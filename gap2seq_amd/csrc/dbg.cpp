@@ -653,6 +653,18 @@ static bool check_pool_sets(const PoolSets& ps, int k, std::string* err) {
   return true;
 }
 
+// the positions (bases + 1) of the pool's sequences some list names, once each: what the host build reads as host text
+static uint64_t pool_text_in_use(const PoolSets& ps) {
+  const std::vector<std::pair<const char*, uint64_t>>& seqs = *ps.seqs;
+  std::vector<uint8_t> seen(seqs.size(), 0);
+  uint64_t n = 0, flagged = 0;
+  auto use = [&](uint32_t j) { if (!seen[j]) { seen[j] = 1; n += seqs[j].second + 1; } };
+  for (uint64_t q = ps.set_begin[0]; q < ps.set_begin[ps.nsets]; q++) use(ps.set_seq[q]);
+  for (uint32_t s = 0; s < ps.nsets; s++) flagged += ps.flagged(s) ? 1 : 0;
+  for (uint64_t x = 0; flagged && x < ps.nshared; x++) use(ps.shared_seq[x]);
+  return n;
+}
+
 Graph* graph_build_pool(const PoolSets& ps, int k, int solid, int nthreads, std::string* err) {
   if (!check_pool_sets(ps, k, err)) return nullptr;
   const std::vector<std::pair<const char*, uint64_t>>& seqs = *ps.seqs;
@@ -666,7 +678,14 @@ Graph* graph_build_pool(const PoolSets& ps, int k, int solid, int nthreads, std:
   };
   if (ps.nsets == 1) {  // an ordinary graph, as graph_build_sets' callers get for one set
     std::vector<std::pair<const char*, uint64_t>> all;
-    return graph_build(*expand(0, &all), k, solid, nthreads, err);
+    if (ps.host_text && !ps.host_text(err)) return nullptr;  // (graph_build takes host pointers)
+    Graph* g1 = graph_build(*expand(0, &all), k, solid, nthreads, err);
+    if (g1) {
+      std::lock_guard<std::mutex> lk(g_pool_info_mu);  // (no pooled build ran: the text counters alone change)
+      g_pool_info.text_gathered = 0;
+      g_pool_info.text_packed = pool_text_in_use(ps);
+    }
+    return g1;
   }
   if (nthreads <= 0) nthreads = (int)std::max(1u, std::thread::hardware_concurrency());
   const auto t0 = std::chrono::steady_clock::now();
@@ -697,7 +716,9 @@ Graph* graph_build_pool(const PoolSets& ps, int k, int solid, int nthreads, std:
     if (getenv("G2S_DEBUG")) fprintf(stderr, "[g2s]   pooled set graph on the host (%s)\n", why.c_str());
     delete g;
   }
+  if (ps.host_text && !ps.host_text(err)) return nullptr;
   info = PoolBuildInfo();
+  info.text_packed = pool_text_in_use(ps);
   uint64_t flagged = 0;
   for (uint32_t s = 0; s < ps.nsets; s++) flagged += ps.flagged(s) ? 1 : 0;
   for (uint64_t q = ps.set_begin[0]; q < ps.set_begin[ps.nsets]; q++) info.own_positions += seqs[ps.set_seq[q]].second + 1;
@@ -932,7 +953,9 @@ Graph* graph_build_pool_reach(const PoolSets& ps_in, const PoolReach& reach_in, 
     }
   }
   if (!g) {
+    if (ps.host_text && !ps.host_text(err)) return nullptr;
     info = PoolBuildInfo();
+    info.text_packed = pool_text_in_use(ps);
     rinfo = PoolReachInfo();
     uint64_t whole = 0, bounded = 0;  // flagged sets without / with a record
     for (uint32_t s = 0; s < ps.nsets; s++)

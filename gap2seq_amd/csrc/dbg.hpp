@@ -11,6 +11,7 @@
 #include <mutex>
 #include <cstdint>
 #include <map>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -137,8 +138,22 @@ Graph* graph_build_sets(const std::vector<std::pair<const char*, uint64_t>>& seq
 // set_shared[s] is set.  A sequence may be in any number of sets, and more than once in one; every occurrence counts
 // towards solidity.  The graph is graph_build_sets' for the expanded list, up to the numbering of nodes inside a set.
 // On the device (dbg_gpu.hip) the shared list is encoded and sorted once, whatever the number of flagged sets.
+// A pool whose text lies in device memory (device_pool.h), for the sequences [first, first + n_reads) of PoolSets::seqs:
+// every read followed by one 'N', read r at text + start[r] (start: device memory, n_reads + 1 entries).
+struct PoolDeviceText {
+  int device = -1;
+  const uint8_t* text = nullptr;
+  const uint64_t* start = nullptr;
+  uint32_t first = 0;
+  uint64_t n_reads = 0;
+};
 struct PoolSets {
   const std::vector<std::pair<const char*, uint64_t>>* seqs = nullptr;
+  // g2s_graph_build_dpool_reach: a sequence whose pointer is null lies in one of these (sorted by `first`); the device
+  // build gathers it from there (dbg_gpu.hip: k_gather_reads).  host_text() gives every such sequence a host pointer —
+  // it is called once, in front of whatever reads the sequences on the host, and false fails the build with *err.
+  const std::vector<PoolDeviceText>* device_text = nullptr;
+  std::function<bool(std::string* err)> host_text;
   const uint64_t* set_begin = nullptr;   // [nsets + 1]
   const uint32_t* set_seq = nullptr;     // [set_begin[nsets]]
   const uint32_t* shared_seq = nullptr;  // [nshared]
@@ -151,9 +166,12 @@ Graph* graph_build_pool(const PoolSets& ps, int k, int solid, int nthreads, std:
 // What the process's last graph_build_pool of several sets did (g2s_test_last_pool_build): the positions (bases + 1 a
 // sequence) of the own lists and of the shared list, and the keys that went through a sort — on the device
 // own + shared whatever the number of flagged sets; the host build works on every flagged set's expanded list.
+// text_gathered / text_packed (g2s_test_last_dpool): the positions of the sequences in use, once each, whose text the
+// device build copied from a device-held pool / that went through host memory (the host build: all of them).
 struct PoolBuildInfo {
   uint64_t own_positions = 0, shared_positions = 0, keys_sorted = 0;
   int on_device = 0;
+  uint64_t text_gathered = 0, text_packed = 0;
 };
 PoolBuildInfo last_pool_build();
 // Reach records of a pooled build (g2s_graph_build_pool_reach): set s with radius[s] >= 0 keeps, of its full graph, only

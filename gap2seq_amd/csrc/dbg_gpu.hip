@@ -451,6 +451,49 @@ __global__ void k_inst_len(const uint32_t* __restrict__ inst_seq, const uint32_t
   const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
   if (j < ninst) len1[j] = seq_len1[inst_seq[j]];
 }
+// The text of the sequences in use that lie in a device-held pool (dbg.hpp: PoolDeviceText), copied device to device to
+// their places in the build's text, each with its separator.  A wave a read: reads are 50 to 250 bytes, so one step of
+// 64 lanes x 4 bytes covers most of them, and a wave's loads and stores are each one run of consecutive dwords.  Source
+// and destination are not mutually aligned: the destination is brought to a 4-byte boundary by bytes, every lane then
+// stores one aligned dword made of the two aligned source dwords around its place (both hold a byte of the read, and
+// the pool's text begins on a 256-byte boundary, so neither load leaves the pool's allocation); the tail of up to three
+// bytes and the 'N' go by bytes.  A read whose place would end beyond the text is skipped (the host checked; belt and
+// braces).
+struct GatherSource {
+  const uint8_t* text;
+  const uint64_t* start;
+};
+__global__ void __launch_bounds__(256) k_gather_reads(const GatherSource* __restrict__ src, const uint32_t* __restrict__ g_src,
+                                                      const uint32_t* __restrict__ g_read, const uint32_t* __restrict__ g_dst,
+                                                      const uint32_t* __restrict__ g_len1, uint32_t n,
+                                                      uint8_t* __restrict__ text, uint64_t P) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint64_t waves = (uint64_t)gridDim.x * 4;
+  for (uint64_t i = (uint64_t)blockIdx.x * 4 + threadIdx.x / 64; i < n; i += waves) {
+    const uint32_t len1 = g_len1[i];
+    const uint64_t d0 = g_dst[i];
+    if (len1 == 0 || d0 + len1 > P) continue;
+    const uint32_t len = len1 - 1;
+    const GatherSource S = src[g_src[i]];
+    const uint8_t* from = S.text + S.start[g_read[i]];
+    uint8_t* to = text + d0;  // (the text begins on a 256-byte boundary: d0 gives the alignment)
+    const uint32_t head = min(len, (uint32_t)((4u - (uint32_t)(d0 & 3u)) & 3u));
+    if (lane < head) to[lane] = from[lane];
+    const uint32_t words = (len - head) / 4;
+    const uint8_t* f = from + head;
+    const uint32_t sh = (uint32_t)((uintptr_t)f & 3u);
+    const uint32_t* fw = (const uint32_t*)(f - sh);
+    uint32_t* tw = (uint32_t*)(to + head);
+    for (uint32_t w = lane; w < words; w += 64) {
+      uint32_t v = fw[w];
+      if (sh) v = (v >> (8u * sh)) | (fw[w + 1] << (32u - 8u * sh));
+      tw[w] = v;
+    }
+    const uint32_t done = head + 4 * words;
+    if (lane < len - done) to[done + lane] = from[done + lane];
+    if (lane == 0) to[len] = 'N';
+  }
+}
 // one (key, set) pair per instance position: the instance by binary search in the instances' start table (the scan of
 // their lengths + 1), the key by gather from the pool position.  A window that crosses the sequence's end or holds an
 // N is the all-ones filler there already.  sid / inst_set == nullptr: keys only (the shared list).
@@ -1268,12 +1311,20 @@ static bool count_solid_pool_gpu_t(Graph& g, std::vector<KT>& out, std::vector<u
       S += seqs[ps.shared_seq[x]].second + 1;
     }
   const uint32_t nu = (uint32_t)used.size(), ninst = (uint32_t)ninst64, nsh = (uint32_t)sh_seq.size();
+  // the text: the sequences with a host pointer in order of first use, packed here and uploaded; behind them those
+  // that lie in a device-held pool (a null pointer: PoolSets::device_text), gathered where they are
   std::vector<uint32_t> seq_start(nu), seq_len1(nu);
-  for (uint32_t u = 0; u < nu && P < (1ull << 32); u++) {
-    const uint64_t len = std::min<uint64_t>(seqs[used[u]].second, 1ull << 32);  // (a longer one fails the guard below)
-    seq_start[u] = (uint32_t)P;
-    seq_len1[u] = (uint32_t)(len + 1);
-    P += len + 1;
+  auto in_pool = [&](uint32_t j) { return ps.device_text != nullptr && seqs[j].first == nullptr; };
+  uint64_t PH = 0;  // the positions of the host part
+  for (int part = 0; part < 2; part++) {
+    for (uint32_t u = 0; u < nu && P < (1ull << 32); u++) {
+      if (in_pool(used[u]) != (part == 1)) continue;
+      const uint64_t len = std::min<uint64_t>(seqs[used[u]].second, 1ull << 32);  // (a longer one fails the guard below)
+      seq_start[u] = (uint32_t)P;
+      seq_len1[u] = (uint32_t)(len + 1);
+      P += len + 1;
+    }
+    if (part == 0) PH = P;
   }
   // (instance positions + shared positions below 2^32, as the set build wants of its text; the pool in use is no larger)
   if (I + S == 0 || I + S >= (1ull << 32) || P >= (1ull << 32)) { if (why) *why = "text size"; return false; }
@@ -1285,10 +1336,39 @@ static bool count_solid_pool_gpu_t(Graph& g, std::vector<KT>& out, std::vector<u
     if (why) *why = "text too large for the device";
     return false;
   }
-  std::vector<uint8_t> text((size_t)P);
+  std::vector<uint8_t> text((size_t)PH);
+  // (what k_gather_reads is told of every read it copies, as four arrays of ng entries in one: pool, read in the pool,
+  // place in the text, length + 1)
+  std::vector<GatherSource> g_table;
+  size_t ng = 0;
+  for (uint32_t u = 0; u < nu; u++) ng += in_pool(used[u]) ? 1 : 0;
+  std::vector<uint32_t> g_rows(4 * ng);
+  size_t gi = 0;
+  if (P > PH)
+    for (const PoolDeviceText& d : *ps.device_text) g_table.push_back(GatherSource{d.text, d.start});
   for (uint32_t u = 0; u < nu; u++) {
-    memcpy(text.data() + seq_start[u], seqs[used[u]].first, (size_t)seqs[used[u]].second);
-    text[(size_t)seq_start[u] + seq_len1[u] - 1] = 'N';  // one separator after every sequence
+    const uint32_t j = used[u];
+    if (!in_pool(j)) {
+      memcpy(text.data() + seq_start[u], seqs[j].first, (size_t)seqs[j].second);
+      text[(size_t)seq_start[u] + seq_len1[u] - 1] = 'N';  // one separator after every sequence
+      continue;
+    }
+    // the pool that holds j: the last one that begins at or before it
+    const std::vector<PoolDeviceText>& dv = *ps.device_text;
+    size_t lo = 0, hi = dv.size();
+    while (hi - lo > 1) {
+      const size_t mid = (lo + hi) / 2;
+      if (dv[mid].first <= j) lo = mid; else hi = mid;
+    }
+    if (dv.empty() || j < dv[lo].first || (uint64_t)(j - dv[lo].first) >= dv[lo].n_reads || dv[lo].device != device) {
+      if (why) *why = "a sequence in no pool of this device";
+      return false;
+    }
+    g_rows[gi] = (uint32_t)lo;
+    g_rows[ng + gi] = j - dv[lo].first;
+    g_rows[2 * ng + gi] = seq_start[u];
+    g_rows[3 * ng + gi] = seq_len1[u];
+    gi++;
   }
   const dim3 blk(256);
   auto grid = [](uint64_t n) { return dim3((unsigned)((n + 255) / 256)); };
@@ -1299,7 +1379,21 @@ static bool count_solid_pool_gpu_t(Graph& g, std::vector<KT>& out, std::vector<u
     G2S_HIP_TRY(d_pkeys.alloc((size_t)P * sizeof(KT)));
     G2S_HIP_TRY(d_sstart.alloc((size_t)nu * 4));
     G2S_HIP_TRY(d_slen1.alloc((size_t)nu * 4));
-    G2S_HIP_TRY(hipMemcpy(d_text.p, text.data(), (size_t)P, hipMemcpyHostToDevice));
+    if (PH) G2S_HIP_TRY(hipMemcpy(d_text.p, text.data(), (size_t)PH, hipMemcpyHostToDevice));
+    if (ng) {
+      // (one allocation: the pools' table, then the four arrays — an allocation costs more than the kernel)
+      const size_t tab_bytes = (g_table.size() * sizeof(GatherSource) + 255) & ~(size_t)255;
+      DevMem d_g;
+      G2S_HIP_TRY(d_g.alloc(tab_bytes + 4 * ng * 4));
+      const uint32_t* rows = (const uint32_t*)(d_g.as<uint8_t>() + tab_bytes);
+      G2S_HIP_TRY(hipMemcpy(d_g.p, g_table.data(), g_table.size() * sizeof(GatherSource), hipMemcpyHostToDevice));
+      G2S_HIP_TRY(hipMemcpy(d_g.as<uint8_t>() + tab_bytes, g_rows.data(), 4 * ng * 4, hipMemcpyHostToDevice));
+      const unsigned ggroups = (unsigned)std::min<uint64_t>(((uint64_t)ng + 3) / 4, 256u * 16u);
+      hipLaunchKernelGGL(k_gather_reads, dim3(ggroups), blk, 0, 0, (const GatherSource*)d_g.p, rows, rows + ng, rows + 2 * ng,
+                         rows + 3 * ng, (uint32_t)ng, (uint8_t*)d_text.p, P);
+      G2S_HIP_TRY(hipGetLastError());
+      G2S_HIP_TRY(hipDeviceSynchronize());  // (the tables go with this scope)
+    }
     G2S_HIP_TRY(hipMemcpy(d_sstart.p, seq_start.data(), (size_t)nu * 4, hipMemcpyHostToDevice));
     G2S_HIP_TRY(hipMemcpy(d_slen1.p, seq_len1.data(), (size_t)nu * 4, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(k_extract<KT>, grid(P), blk, 0, 0, (const uint8_t*)d_text.p, P, k, (KT*)d_pkeys.p);
@@ -1331,6 +1425,8 @@ static bool count_solid_pool_gpu_t(Graph& g, std::vector<KT>& out, std::vector<u
   info->own_positions = I;
   info->shared_positions = S;
   info->keys_sorted = 0;
+  info->text_gathered = P - PH;
+  info->text_packed = PH;
   // ---- the own lists: (set, k-mer) sort, runs, the run table and every set's first run
   DevMem d_rkey, d_rset, d_rcnt, d_rlo;
   uint32_t nruns = 0;

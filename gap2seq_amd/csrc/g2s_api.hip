@@ -31,6 +31,7 @@
 #include "d2_device.h"
 #include "d3_device.h"
 #include "dbg.hpp"
+#include "device_pool.h"
 #include "fastx.hpp"
 #include "fill_device.h"
 #include "fill_launch.h"
@@ -164,17 +165,21 @@ extern "C" int g2s_graph_build_sets(const char* const* seqs, const uint64_t* len
   (*out)->g = g;
   return G2S_OK;
 }
+static int build_pool_reach_of(const PoolSets& ps, int k, int solid, int nthreads, const g2s_gap* reach_gap,
+                               const int32_t* reach_radius, g2s_graph** out);
 // the pooled builds' arguments, checked and as a PoolSets over `v`
 static int pool_sets_of(const char* name, const char* const* seqs, const uint64_t* lens, uint64_t nseqs, const uint64_t* set_begin,
                         const uint32_t* set_seq, const uint32_t* shared_seq, uint64_t nshared, const uint8_t* set_shared,
                         uint32_t nsets, g2s_graph** out, std::vector<std::pair<const char*, uint64_t>>* v, PoolSets* ps) {
-  if ((!seqs && nseqs) || !set_begin || !out || nsets == 0 || nseqs >= (1ull << 32) || (!shared_seq && nshared))
+  if ((!seqs && nseqs && v->size() != nseqs) || !set_begin || !out || nsets == 0 || nseqs >= (1ull << 32) || (!shared_seq && nshared))
     return fail(G2S_ERR_ARG, std::string(name) + ": bad argument");
   for (uint32_t s = 0; s < nsets; s++)
     if (set_begin[s + 1] < set_begin[s]) return fail(G2S_ERR_ARG, std::string(name) + ": set_begin decreases");
   if (!set_seq && set_begin[nsets] > set_begin[0]) return fail(G2S_ERR_ARG, std::string(name) + ": bad argument");
-  v->reserve((size_t)nseqs);
-  for (uint64_t i = 0; i < nseqs; i++) v->emplace_back(seqs[i], lens ? lens[i] : (uint64_t)strlen(seqs[i]));
+  if (seqs) {  // (nullptr with sequences: g2s_graph_build_dpool_reach, which has filled `v` from its pools)
+    v->reserve((size_t)nseqs);
+    for (uint64_t i = 0; i < nseqs; i++) v->emplace_back(seqs[i], lens ? lens[i] : (uint64_t)strlen(seqs[i]));
+  }
   ps->seqs = v;
   ps->set_begin = set_begin;
   ps->set_seq = set_seq;
@@ -208,6 +213,12 @@ extern "C" int g2s_graph_build_pool_reach(const char* const* seqs, const uint64_
   PoolSets ps;
   const int rc = pool_sets_of("g2s_graph_build_pool_reach", seqs, lens, nseqs, set_begin, set_seq, shared_seq, nshared, set_shared, nsets, out, &v, &ps);
   if (rc != G2S_OK) return rc;
+  return build_pool_reach_of(ps, k, solid, nthreads, reach_gap, reach_radius, out);
+}
+// the pooled build with reach records over a checked PoolSets: the host-pointer entry and the device-pool entry alike
+static int build_pool_reach_of(const PoolSets& ps, int k, int solid, int nthreads, const g2s_gap* reach_gap,
+                               const int32_t* reach_radius, g2s_graph** out) {
+  const uint32_t nsets = ps.nsets;
   if (k < 1 || k > kMaxK) return fail(G2S_ERR_ARG, "k must be in [1," + std::to_string(kMaxK) + "]");  // (the seeds below read k characters)
   // the seeds: the flank k-mers the fill looks up (g2s_batch_prepare), none for a gap it rejects
   PoolReach reach;
@@ -229,6 +240,81 @@ extern "C" int g2s_graph_build_pool_reach(const char* const* seqs, const uint64_
   if (!g) return fail(G2S_ERR_ARG, err);
   *out = new g2s_graph();
   (*out)->g = g;
+  return G2S_OK;
+}
+// The pooled build over pools the read filter left where it made them (device_pool.h).  A pool held on the build's device
+// hands its reads over as null pointers with a PoolDeviceText (dbg_gpu.hip gathers them device to device); every other
+// pool hands over host pointers — into its own text when host-held, into a copy that comes down here when it lies on
+// another device or the host builds.  The device build giving up later brings the rest down through PoolSets::host_text.
+extern "C" int g2s_graph_build_dpool_reach(const g2s_device_pool* const* pools, uint32_t npools, const uint64_t* set_begin,
+                                           const uint32_t* set_seq, const uint32_t* shared_seq, uint64_t nshared,
+                                           const uint8_t* set_shared, uint32_t nsets, int k, int solid, int nthreads,
+                                           const g2s_gap* reach_gap, const int32_t* reach_radius, g2s_graph** out) {
+  const char* const name = "g2s_graph_build_dpool_reach";
+  if ((reach_gap == nullptr) != (reach_radius == nullptr)) return fail(G2S_ERR_ARG, std::string(name) + ": reach_gap and reach_radius go together");
+  if (!pools || npools == 0) return fail(G2S_ERR_ARG, std::string(name) + ": bad argument");
+  uint64_t total = 0;
+  for (uint32_t p = 0; p < npools; p++) {
+    if (!pools[p]) return fail(G2S_ERR_ARG, std::string(name) + ": bad argument");
+    total += pools[p]->view.n_reads;
+  }
+  if (total >= (1ull << 32)) return fail(G2S_ERR_ARG, std::string(name) + ": bad argument");
+  const bool host_build = getenv("G2S_HOST_BUILD") != nullptr;
+  const int device = getenv("G2S_DEVICE") ? atoi(getenv("G2S_DEVICE")) : 0;
+  std::vector<std::pair<const char*, uint64_t>> v((size_t)total);
+  std::vector<PoolDeviceText> dtext;
+  std::vector<std::string> down(npools);  // the text of a device-held pool, once it has come down
+  std::vector<uint32_t> first(npools);
+  auto point_at = [&](uint32_t p, const char* text) {
+    const g2s_device_pool& D = *pools[p];
+    for (uint64_t r = 0; r < D.view.n_reads; r++) v[(size_t)(first[p] + r)].first = text + D.start(r);
+  };
+  auto copy_down = [&](uint32_t p, std::string* err) {
+    const g2s_device_pool& D = *pools[p];
+    down[p].resize((size_t)D.text_bytes());
+    if (!device_pool_copy_down(D.device, D.d_text, 0, D.text_bytes(), &down[p][0], err)) return false;
+    point_at(p, down[p].data());
+    return true;
+  };
+  uint64_t at = 0;
+  for (uint32_t p = 0; p < npools; p++) {
+    const g2s_device_pool& D = *pools[p];
+    first[p] = (uint32_t)at;
+    for (uint64_t r = 0; r < D.view.n_reads; r++) v[(size_t)(at + r)] = {nullptr, D.base_off[(size_t)r + 1] - D.base_off[(size_t)r]};
+    at += D.view.n_reads;
+    std::string err;
+    if (D.device < 0) point_at(p, D.host_text.data());
+    else if (!host_build && D.device == device) dtext.push_back(PoolDeviceText{D.device, (const uint8_t*)D.d_text, D.d_start, first[p], D.view.n_reads});
+    else if (!copy_down(p, &err)) return fail(G2S_ERR_HIP, std::string(name) + ": " + err);
+  }
+  PoolSets ps;
+  const int rc = pool_sets_of(name, nullptr, nullptr, total, set_begin, set_seq, shared_seq, nshared, set_shared, nsets, out, &v, &ps);
+  if (rc != G2S_OK) return rc;
+  if (!dtext.empty()) {
+    ps.device_text = &dtext;
+    ps.host_text = [&](std::string* err) {
+      for (uint32_t p = 0; p < npools; p++)
+        if (pools[p]->device >= 0 && down[p].empty() && pools[p]->text_bytes() && !copy_down(p, err)) return false;
+      return true;
+    };
+  }
+  if (reach_radius) return build_pool_reach_of(ps, k, solid, nthreads, reach_gap, reach_radius, out);
+  std::string err;
+  Graph* g = graph_build_pool(ps, k, solid, nthreads, &err);
+  if (!g) return fail(G2S_ERR_ARG, err);
+  *out = new g2s_graph();
+  (*out)->g = g;
+  return G2S_OK;
+}
+// TEST HOOK (include/g2s_test.h)
+extern "C" int g2s_test_last_dpool(int* held_on_device, uint64_t* bases_bytes_to_host, uint64_t* text_bytes_gathered_on_device,
+                                   uint64_t* text_bytes_packed_on_host) {
+  const LastDpoolFilter f = last_dpool_filter();
+  const PoolBuildInfo b = last_pool_build();
+  if (held_on_device) *held_on_device = f.held_on_device;
+  if (bases_bytes_to_host) *bases_bytes_to_host = f.bases_bytes_to_host;
+  if (text_bytes_gathered_on_device) *text_bytes_gathered_on_device = b.text_gathered;
+  if (text_bytes_packed_on_host) *text_bytes_packed_on_host = b.text_packed;
   return G2S_OK;
 }
 // TEST HOOK (include/g2s_test.h)

@@ -11,12 +11,18 @@
 //   Gap2Seq-libraries -libraries libs.txt -gaps gaps.fa -bed gaps.bed -filled out.fa
 //                     [-k 31] [-fuz 10] [-solid 2] [-dist-error 500] [-max-mem 20] [-randseed 0]
 //                     [-all-upper] [-unique] [-best-only] [-device D] [-filter-device D|-1] [-filter-one-pass 0|1]
+//                     [-device-pool 0|1]
 //
 // -filter-device: the GPU the read filter's joins run on (default: -device), -1 = host threads.
 // -filter-one-pass: 1 asks the read filter to inflate every BAM once and keep it on the GPU between its passes
 // (g2s_filter_set_one_pass), 0 forbids it; not given, G2S_FILTER_ONE_PASS decides, and without that the mode is on
 // (kOnePassDefault: DESIGN 3.6b has the measurement behind it).  A BAM too large to stay there whole keeps every
 // record's head, name and bases instead (the store route, bam_store.h).  The output is the same bytes either way.
+// -device-pool: 1 leaves every library's reads where the filter made them — in device memory when it ran one pass
+// (g2s_filter_reads_gaps_dpool) — and builds every chunk's set graph from there (g2s_graph_build_dpool_reach): the reads
+// never become host memory; 0 takes them through host memory (g2s_filter_reads_gaps_pool, g2s_graph_build_pool_reach).
+// Not given, G2S_DEVICE_POOL=1|0 decides, and without that the switch is on (kDevicePoolDefault: DESIGN 3.6b).  With -filter-device different from -device the pools lie on another device and the
+// build packs them on the host.  The output is the same bytes either way.
 // libs.txt: tab separated `bam mean std_dev threshold`, one library a line.  out.fa: per gap, in input order,
 // `comment\nfill\n` (the file GapMerger -gaps takes); stdout ends with `Filled X out of Y gaps`.
 #include <cmath>
@@ -37,6 +43,12 @@ namespace {
 // says otherwise.  By DESIGN 3.6b's table the whole filter call in one-pass mode beats the parent's on average by
 // more than the parent's own spread over six calls, with 8 and with 2 host threads.
 constexpr bool kOnePassDefault = true;
+
+// Whether the libraries' reads go from the filter to the set build as device-held pools when neither -device-pool nor
+// G2S_DEVICE_POOL says otherwise.  By DESIGN 3.6b's table the way from a BAM file to its uploaded set graph through a
+// device-held pool is 9 to 10 ms shorter on average than through host memory, on a 3 MB and on a 32 MB file, the two
+// variants' ranges over six alternating calls disjoint at both sizes.
+constexpr bool kDevicePoolDefault = true;
 
 struct Library {
   std::string bam;
@@ -92,7 +104,9 @@ std::vector<std::string> gap_records(const std::string& text) {
 // the reads of every gap from one library, and the library's unmapped reads, in one call (two passes over the BAM), as
 // a pool: every read held once however many gaps select it, every gap a list of indices.  A library whose BAM cannot
 // be read gives no reads (as the wrapper's ReadFilter run that fails, Gap2Seq.py:151-153).
-g2s_read_pool* filter_library(const Library& lib, const std::vector<GapRec>& gaps, int device) {
+// (dpool: the pool as a g2s_device_pool in *dout, and its view returned)
+const g2s_read_pool* filter_library(const Library& lib, const std::vector<GapRec>& gaps, int device, g2s_read_pool** hout,
+                                    g2s_device_pool** dout) {
   g2s_filter_opts o;
   memset(&o, 0, sizeof o);
   o.mean_insert = lib.mean;
@@ -104,19 +118,23 @@ g2s_read_pool* filter_library(const Library& lib, const std::vector<GapRec>& gap
     gv[i].gap_length = gaps[i].gap_length;
     gv[i].flank_length = gaps[i].flank_length;
   }
-  g2s_read_pool* pool = nullptr;
   int64_t total = 0;
-  // (with names: the chunk rule below counts the bytes of the FASTA text the reads would make)
-  int rc = g2s_filter_reads_gaps_pool(lib.bam.c_str(), &o, gv.data(), gv.size(), device, 1, 1, &pool, &total, nullptr);
+  // (with names: the chunk rule below counts the bytes of the FASTA text the reads would make; a device pool's view has
+  // the names' lengths always)
+  auto call = [&](int dev) {
+    return dout ? g2s_filter_reads_gaps_dpool(lib.bam.c_str(), &o, gv.data(), gv.size(), dev, 1, dout, &total, nullptr)
+                : g2s_filter_reads_gaps_pool(lib.bam.c_str(), &o, gv.data(), gv.size(), dev, 1, 1, hout, &total, nullptr);
+  };
+  int rc = call(device);
   if (rc != G2S_OK && rc != G2S_ERR_IO && device >= 0) {  // (the device could not take it: the same joins on the host)
     std::cerr << "Gap2Seq-libraries: " << lib.bam << ": " << g2s_filter_last_error() << "; filtering on the host" << std::endl;
-    rc = g2s_filter_reads_gaps_pool(lib.bam.c_str(), &o, gv.data(), gv.size(), -1, 1, 1, &pool, &total, nullptr);
+    rc = call(-1);
   }
   if (rc != G2S_OK) {
     std::cerr << "Gap2Seq-libraries: " << lib.bam << ": " << g2s_filter_last_error() << std::endl;
     return nullptr;
   }
-  return pool;
+  return dout ? g2s_device_pool_view(*dout) : *hout;
 }
 
 }  // namespace
@@ -125,7 +143,7 @@ int main(int argc, char** argv) {
   std::string libs_path, gaps_path, bed_path, filled_path;
   int k = 31, fuz = 10, solid = 2, derr = 500, device = 0, filter_device = 0;
   bool filter_device_set = false;
-  int filter_one_pass = -1;
+  int filter_one_pass = -1, device_pool = -1;
   double max_mem = 20;
   uint32_t randseed = 0;
   bool upper = false, unique = false, best = false;
@@ -145,6 +163,7 @@ int main(int argc, char** argv) {
     else if (a == "-device") device = atoi(val());
     else if (a == "-filter-device") { filter_device = atoi(val()); filter_device_set = true; }
     else if (a == "-filter-one-pass") filter_one_pass = atoi(val()) != 0 ? 1 : 0;
+    else if (a == "-device-pool") device_pool = atoi(val()) != 0 ? 1 : 0;
     else if (a == "-all-upper") upper = true;
     else if (a == "-unique") unique = true;
     else if (a == "-best-only") best = true;
@@ -152,6 +171,10 @@ int main(int argc, char** argv) {
   }
   if (filter_one_pass < 0 && kOnePassDefault && !getenv("G2S_FILTER_ONE_PASS")) filter_one_pass = 1;
   g2s_filter_set_one_pass(filter_one_pass);
+  if (device_pool < 0) {
+    const char* e = getenv("G2S_DEVICE_POOL");
+    device_pool = e ? (atoi(e) != 0 ? 1 : 0) : (kDevicePoolDefault ? 1 : 0);
+  }
   if (libs_path.empty() || gaps_path.empty() || bed_path.empty() || filled_path.empty()) {
     std::cerr << "Gap2Seq-libraries: -libraries, -gaps, -bed and -filled are required" << std::endl;
     return EXIT_FAILURE;
@@ -194,24 +217,40 @@ int main(int argc, char** argv) {
   // ---- every library's pool; the reads of all libraries as one array of (pointer, length), every gap's own list
   // (its reads of library 0, 1, ... in order) as indices into it, and the shared list: every library's unmapped reads
   // in library order.  What is held is the pools and the index lists: nothing grows with gaps x unmapped reads.
-  std::vector<g2s_read_pool*> pools;
-  std::vector<const char*> seq_ptr;
+  std::vector<const g2s_read_pool*> pools;  // (a library's arrays: its host pool, or the view of its device pool)
+  std::vector<g2s_read_pool*> host_pools;
+  std::vector<g2s_device_pool*> dev_pools;  // (-device-pool 1: the libraries that gave reads, in order)
+  std::vector<const char*> seq_ptr;         // (null for a read of a device pool)
   std::vector<uint64_t> seq_len, seq_fasta;  // (bytes of the read's FASTA record: '>' name '\n' bases '\n')
   std::vector<uint32_t> lib_first;
   double threshold = 0;
   for (const Library& L : libs) {  // (Gap2Seq.py:143-159; every library's unmapped reads, Gap2Seq.py:64-72, :437-439)
-    g2s_read_pool* P = filter_library(L, gaps, filter_device_set ? filter_device : device);
+    g2s_read_pool* hp = nullptr;
+    g2s_device_pool* dp = nullptr;
+    const g2s_read_pool* P = filter_library(L, gaps, filter_device_set ? filter_device : device, &hp, device_pool ? &dp : nullptr);
     pools.push_back(P);
+    if (hp) host_pools.push_back(hp);
+    if (dp) dev_pools.push_back(dp);
     lib_first.push_back((uint32_t)seq_ptr.size());
     if (P) {
       if (seq_ptr.size() + P->n_reads >= ((uint64_t)1 << 32)) { std::cerr << "Gap2Seq-libraries: 2^32 reads or more selected" << std::endl; return EXIT_FAILURE; }
       for (uint64_t r = 0; r < P->n_reads; r++) {
-        seq_ptr.push_back(P->bases + P->base_off[r]);
+        seq_ptr.push_back(P->bases ? P->bases + P->base_off[r] : nullptr);
         seq_len.push_back(P->base_off[r + 1] - P->base_off[r]);
         seq_fasta.push_back(seq_len.back() + (P->name_off[r + 1] - P->name_off[r]) + 3);
       }
     }
     threshold += L.threshold;
+  }
+  if (device_pool && getenv("G2S_DEBUG")) {
+    size_t held = 0;
+    uint64_t bytes = 0;
+    for (const g2s_device_pool* P : dev_pools) {
+      held += g2s_device_pool_device(P) >= 0 ? 1 : 0;
+      bytes += g2s_device_pool_bytes(P);
+    }
+    std::cerr << "[g2s] libraries: " << held << " of " << dev_pools.size() << " pools held on the device (" << bytes << " bytes)"
+              << std::endl;
   }
   std::vector<uint64_t> own_begin(ngaps + 1, 0);
   for (size_t i = 0; i < ngaps; i++) {
@@ -273,6 +312,7 @@ int main(int argc, char** argv) {
     std::vector<uint64_t> sl, set_begin(1, 0);
     std::vector<uint32_t> set_seq, chunk_shared;
     auto local = [&](uint32_t j) -> uint32_t {
+      if (device_pool) return j;  // (the build numbers the pools' reads as lib_first does: nothing to rebase)
       if (chunk_of[j] == UINT32_MAX) { chunk_of[j] = (uint32_t)sp.size(); sp.push_back(seq_ptr[j]); sl.push_back(seq_len[j]); touched.push_back(j); }
       return chunk_of[j];
     };
@@ -304,9 +344,21 @@ int main(int argc, char** argv) {
       reach_radius[i - lo] = std::max(0, g.gap_length + derr) + std::max(0, x.lmf) + std::max(0, x.rmf);
     }
     g2s_graph* graph = nullptr;
-    int rc = g2s_graph_build_pool_reach(sp.data(), sl.data(), sp.size(), set_begin.data(), set_seq.data(), chunk_shared.data(),
-                                        chunk_shared.size(), takes_unmapped.data() + lo, (uint32_t)(hi - lo), k, solid, 0,
-                                        use_reach ? reach_gap.data() : nullptr, use_reach ? reach_radius.data() : nullptr, &graph);
+    int rc;
+    if (device_pool && dev_pools.empty()) {  // (no library gave reads: the build over no sequences)
+      rc = g2s_graph_build_pool_reach(nullptr, nullptr, 0, set_begin.data(), set_seq.data(), chunk_shared.data(), chunk_shared.size(),
+                                      takes_unmapped.data() + lo, (uint32_t)(hi - lo), k, solid, 0,
+                                      use_reach ? reach_gap.data() : nullptr, use_reach ? reach_radius.data() : nullptr, &graph);
+    } else if (device_pool) {
+      rc = g2s_graph_build_dpool_reach(dev_pools.data(), (uint32_t)dev_pools.size(), set_begin.data(), set_seq.data(),
+                                       chunk_shared.data(), chunk_shared.size(), takes_unmapped.data() + lo, (uint32_t)(hi - lo), k,
+                                       solid, 0, use_reach ? reach_gap.data() : nullptr, use_reach ? reach_radius.data() : nullptr,
+                                       &graph);
+    } else {
+      rc = g2s_graph_build_pool_reach(sp.data(), sl.data(), sp.size(), set_begin.data(), set_seq.data(), chunk_shared.data(),
+                                      chunk_shared.size(), takes_unmapped.data() + lo, (uint32_t)(hi - lo), k, solid, 0,
+                                      use_reach ? reach_gap.data() : nullptr, use_reach ? reach_radius.data() : nullptr, &graph);
+    }
     for (uint32_t j : touched) chunk_of[j] = UINT32_MAX;
     touched.clear();
     g2s_session* s = nullptr;
@@ -369,7 +421,8 @@ int main(int argc, char** argv) {
   if (!f) { std::cerr << "Gap2Seq-libraries: cannot write " << filled_path << std::endl; return EXIT_FAILURE; }
   fwrite(out.data(), 1, out.size(), f);
   fclose(f);
-  for (g2s_read_pool* P : pools) g2s_read_pool_free(P);
+  for (g2s_read_pool* P : host_pools) g2s_read_pool_free(P);
+  for (g2s_device_pool* P : dev_pools) g2s_device_pool_free(P);
   std::cout << "Filled " << successful << " out of " << ngaps << " gaps" << std::endl;  // (Gap2Seq.py:513)
   return EXIT_SUCCESS;
 }

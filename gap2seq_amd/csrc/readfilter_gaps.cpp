@@ -35,6 +35,10 @@
 // stream outlives its slot.  G2S_FILTER_STORE=1 takes the route even when the whole stream would fit, =0 never takes it.
 // A planned capacity that proves too small (kTextStoreOverflow) releases the store and the rows, runs pass A again the
 // two-pass way and pass B on the host: three passes, the same bytes.
+// g2s_filter_reads_gaps_dpool (device_pool.h) is the pool form asking for one-pass mode by itself and keeping the text
+// pass B's kernels wrote — the pooled build's layout, every read followed by 'N' — in device memory for the build to
+// read there (g2s_graph_build_dpool_reach); only offsets and index lists come down.  Any other route gives the same
+// handle with its text in host memory.
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -44,6 +48,7 @@
 #include <functional>
 #include <memory>
 #include <mutex>
+#include <new>
 #include <string>
 #include <thread>
 #include <vector>
@@ -53,6 +58,7 @@
 #include "bam.hpp"
 #include "bam_rows.h"
 #include "bam_text.h"
+#include "device_pool.h"
 #include "name_hash.h"
 #include "readfilter_gaps.hpp"
 
@@ -233,6 +239,15 @@ bool one_pass_asked() {
   const int m = g_one_pass.load();
   return m < 0 ? env_is_1("G2S_FILTER_ONE_PASS") : m > 0;
 }
+// g2s_filter_reads_gaps_dpool asks by itself: a device-held pool is what the call is for.  Forbidding still forbids.
+bool one_pass_asked_dpool() {
+  const int m = g_one_pass.load();
+  const char* e = getenv("G2S_FILTER_ONE_PASS");
+  return m < 0 ? !(e && strcmp(e, "0") == 0) : m > 0;
+}
+
+// g2s_test_last_dpool: the process's last g2s_filter_reads_gaps_dpool[_mem]
+LastDpoolFilter g_last_dpool;
 
 // g2s_test_last_filter_text: what pass B of the process's last batched call did
 struct LastText {
@@ -391,9 +406,11 @@ bool pass_b_host(const BamFile& bam, uint64_t total, const std::vector<uint8_t>&
 }
 
 // what g2s_filter_reads_gaps_pool asks of run_filter_gaps in place of the per-gap texts
+// (dout: g2s_filter_reads_gaps_dpool — the pool as a g2s_device_pool, its bases left on the device when pass B ran there)
 struct PoolRequest {
   bool names, unmapped;
   g2s_read_pool** out;
+  g2s_device_pool** dout = nullptr;
 };
 
 int run_filter_gaps(BamFile& bam, const g2s_filter_opts* lib, const g2s_filter_gap* gaps, size_t n, int device,
@@ -438,7 +455,8 @@ int run_filter_gaps(BamFile& bam, const g2s_filter_opts* lib, const g2s_filter_g
   LastText lt;
   StoreReport ls;
   bool store_overflow = false;
-  const bool asked = one_pass_asked();
+  const bool dpool = pool && pool->dout;
+  const bool asked = dpool ? one_pass_asked_dpool() : one_pass_asked();
   lt.reason = asked ? kTextNoDeviceRows : kTextNotAsked;
   if (device_inflate && !env_is_1("G2S_HOST_ROWS") && (kDeviceRowsDefault || env_is_1("G2S_DEVICE_ROWS"))) {
     int refused = kResidentKept;
@@ -541,7 +559,13 @@ int run_filter_gaps(BamFile& bam, const g2s_filter_opts* lib, const g2s_filter_g
   ask.pool = pool != nullptr;
   ask.names = pool && pool->names;
   ask.unmapped = pool ? pool->unmapped : unmapped_out != nullptr;
+  ask.device_text = dpool;
   BamText T;
+  // (a text left on the device belongs to the handle made below; until then it goes with this scope)
+  struct TextGuard {
+    BamText& t;
+    ~TextGuard() { if (t.d_text) device_pool_release(t.d_device, t.d_text); }
+  } text_guard{T};
   bool text_done = false;
   if (resident) {  // (one-pass mode: from the stream pass A left on the device)
     std::string why;
@@ -591,7 +615,58 @@ int run_filter_gaps(BamFile& bam, const g2s_filter_opts* lib, const g2s_filter_g
       for (size_t q = at2[g]; q < at2[g + 1]; q++) gread[o++] = pidx[(uint32_t)J.list2[q]];
       gbeg[g + 1] = o;
     }
-    g2s_read_pool* P = (g2s_read_pool*)calloc(1, sizeof(g2s_read_pool));
+    if (dpool) {  // ... as a handle that owns the same arrays, and the text where pass B left it
+      g2s_device_pool* H = new (std::nothrow) g2s_device_pool();
+      if (!H) { set_filter_error("out of memory"); return G2S_ERR_NOMEM; }
+      LastDpoolFilter ld;
+      try {
+        H->base_off = pboff;
+        H->name_off = pnoff;
+        H->gap_begin.swap(gbeg);
+        H->gap_read.swap(gread);
+        H->unmapped_read = punmapped;
+        if (T.d_text) {
+          H->device = T.d_device;
+          H->d_text = T.d_text;
+          H->d_start = T.d_start;
+          H->device_bytes = T.d_bytes;
+          T.d_text = nullptr;
+          ld.held_on_device = 1;
+        } else {  // (host-held: the build's layout, so that both kinds read alike)
+          H->host_text.resize((size_t)H->text_bytes());
+          for (size_t r = 0; r + 1 < pboff.size(); r++) {
+            const size_t len = (size_t)(pboff[r + 1] - pboff[r]), at = (size_t)H->start(r);
+            if (len) memcpy(&H->host_text[at], pbases.data() + pboff[r], len);
+            H->host_text[at + len] = 'N';
+          }
+          ld.bases_bytes_to_host = pbases.size();
+        }
+        H->gap_read.reserve(1);  // (one element at least behind every pointer, as g2s_read_pool's arrays have)
+        H->unmapped_read.reserve(1);
+      } catch (const std::bad_alloc&) {
+        g2s_device_pool_free(H);
+        set_filter_error("out of memory");
+        return G2S_ERR_NOMEM;
+      }
+      H->view.n_reads = H->base_off.size() - 1;
+      H->view.base_off = H->base_off.data();
+      H->view.name_off = H->name_off.data();
+      H->view.gap_begin = H->gap_begin.data();
+      H->view.gap_read = H->gap_read.data();
+      H->view.n_unmapped = H->unmapped_read.size();
+      H->view.unmapped_read = H->unmapped_read.data();
+      *pool->dout = H;
+      {
+        std::lock_guard<std::mutex> lk(g_last_mu);
+        g_last_dpool = ld;
+      }
+      if (total_out) *total_out = (int64_t)total;
+      st.ms_text = ms_since(t0);
+      if (stats) *stats = st;
+      g_laps_end = std::chrono::steady_clock::now();
+      return G2S_OK;
+    }
+    g2s_read_pool* P =(g2s_read_pool*)calloc(1, sizeof(g2s_read_pool));
     if (P) {
       P->n_reads = pboff.size() - 1;
       P->bases = dup_array(pbases.data(), pbases.size());
@@ -671,6 +746,11 @@ bool gap_args_ok(const g2s_filter_opts* lib, const g2s_filter_gap* gaps, size_t 
 
 }  // namespace
 
+LastDpoolFilter last_dpool_filter() {
+  std::lock_guard<std::mutex> lk(g_last_mu);
+  return g_last_dpool;
+}
+
 }  // namespace g2s
 
 extern "C" {
@@ -726,6 +806,54 @@ int g2s_filter_reads_gaps_pool_mem(const void* bam_bytes, size_t nbytes, const g
   const g2s::PoolRequest req{want_names != 0, want_unmapped != 0, out};
   return laps.run_done(g2s::run_filter_gaps(bam, lib, gaps, n, device, nullptr, nullptr, nullptr, nullptr, total, nullptr, nullptr,
                                             stats, &req));
+}
+
+int g2s_filter_reads_gaps_dpool(const char* bam_path, const g2s_filter_opts* lib, const g2s_filter_gap* gaps, size_t n, int device,
+                                int want_unmapped, g2s_device_pool** out, int64_t* total, g2s_filter_stats* stats) {
+  if (!bam_path || !out || !g2s::gap_args_ok(lib, gaps, n)) return G2S_ERR_ARG;
+  g2s::OutsideLaps laps;
+  g2s::BamFile bam;
+  std::string err;
+  if (!bam.open_path(bam_path, &err)) { g2s::set_filter_error(err); return G2S_ERR_IO; }
+  laps.open_done();
+  const g2s::PoolRequest req{true, want_unmapped != 0, nullptr, out};
+  return laps.run_done(g2s::run_filter_gaps(bam, lib, gaps, n, device, nullptr, nullptr, nullptr, nullptr, total, nullptr, nullptr,
+                                            stats, &req));
+}
+
+int g2s_filter_reads_gaps_dpool_mem(const void* bam_bytes, size_t nbytes, const g2s_filter_opts* lib, const g2s_filter_gap* gaps,
+                                    size_t n, int device, int want_unmapped, g2s_device_pool** out, int64_t* total,
+                                    g2s_filter_stats* stats) {
+  if (!bam_bytes || !out || !g2s::gap_args_ok(lib, gaps, n)) return G2S_ERR_ARG;
+  g2s::OutsideLaps laps;
+  g2s::BamFile bam;
+  std::string err;
+  if (!bam.open_mem(bam_bytes, nbytes, &err)) { g2s::set_filter_error(err); return G2S_ERR_IO; }
+  laps.open_done();
+  const g2s::PoolRequest req{true, want_unmapped != 0, nullptr, out};
+  return laps.run_done(g2s::run_filter_gaps(bam, lib, gaps, n, device, nullptr, nullptr, nullptr, nullptr, total, nullptr, nullptr,
+                                            stats, &req));
+}
+
+const g2s_read_pool* g2s_device_pool_view(const g2s_device_pool* p) { return p ? &p->view : nullptr; }
+int g2s_device_pool_device(const g2s_device_pool* p) { return p ? p->device : -1; }
+uint64_t g2s_device_pool_bytes(const g2s_device_pool* p) { return p ? p->device_bytes : 0; }
+
+int g2s_device_pool_read(const g2s_device_pool* p, uint64_t r, char* out) {
+  if (!p || r >= p->view.n_reads) { g2s::set_filter_error("g2s_device_pool_read: bad argument"); return G2S_ERR_ARG; }
+  const uint64_t len = p->base_off[(size_t)r + 1] - p->base_off[(size_t)r];
+  if (!len) return G2S_OK;
+  if (!out) { g2s::set_filter_error("g2s_device_pool_read: bad argument"); return G2S_ERR_ARG; }
+  if (p->device < 0) { memcpy(out, p->host_text.data() + p->start(r), (size_t)len); return G2S_OK; }
+  std::string why;
+  if (!g2s::device_pool_copy_down(p->device, p->d_text, p->start(r), len, out, &why)) { g2s::set_filter_error(why); return G2S_ERR_HIP; }
+  return G2S_OK;
+}
+
+void g2s_device_pool_free(g2s_device_pool* p) {
+  if (!p) return;
+  if (p->d_text) g2s::device_pool_release(p->device, p->d_text);  // (sets the handle's device first)
+  delete p;
 }
 
 void g2s_read_pool_free(g2s_read_pool* p) {

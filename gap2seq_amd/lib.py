@@ -207,6 +207,22 @@ _SIGS = {
                                                  C.c_size_t, C.c_int, C.c_int, C.c_int, C.POINTER(C.POINTER(g2s_read_pool)),
                                                  C.POINTER(C.c_int64), C.POINTER(g2s_filter_stats)]),
     "g2s_read_pool_free": (None, [C.POINTER(g2s_read_pool)]),
+    "g2s_filter_reads_gaps_dpool": (C.c_int, [C.c_char_p, C.POINTER(g2s_filter_opts), C.POINTER(g2s_filter_gap), C.c_size_t,
+                                              C.c_int, C.c_int, C.POINTER(_VP), C.POINTER(C.c_int64),
+                                              C.POINTER(g2s_filter_stats)]),
+    "g2s_filter_reads_gaps_dpool_mem": (C.c_int, [C.c_char_p, C.c_size_t, C.POINTER(g2s_filter_opts), C.POINTER(g2s_filter_gap),
+                                                  C.c_size_t, C.c_int, C.c_int, C.POINTER(_VP), C.POINTER(C.c_int64),
+                                                  C.POINTER(g2s_filter_stats)]),
+    "g2s_device_pool_view": (C.POINTER(g2s_read_pool), [_VP]),
+    "g2s_device_pool_device": (C.c_int, [_VP]),
+    "g2s_device_pool_bytes": (C.c_uint64, [_VP]),
+    "g2s_device_pool_read": (C.c_int, [_VP, C.c_uint64, C.c_char_p]),
+    "g2s_device_pool_free": (None, [_VP]),
+    "g2s_graph_build_dpool_reach": (C.c_int, [C.POINTER(_VP), C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32),
+                                              C.POINTER(C.c_uint32), C.c_uint64, C.POINTER(C.c_uint8), C.c_uint32, C.c_int,
+                                              C.c_int, C.c_int, C.POINTER(g2s_gap), C.POINTER(C.c_int32), C.POINTER(_VP)]),
+    "g2s_test_last_dpool": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                      C.POINTER(C.c_uint64)]),
     "g2s_filter_last_error": (C.c_char_p, []),
     "g2s_device_count": (C.c_int, []),
     "g2s_synth_genome": (C.c_int, [C.c_uint64, C.c_uint32, C.c_uint64, C.POINTER(_VP)]),
@@ -529,6 +545,87 @@ def filter_reads_gaps_pool(bam, mean, std_dev, gaps, device=0, threads=0, names=
     return ReadPool(out, n, tot.value, stats)
 
 
+class DevicePool:
+    """g2s_device_pool: a ReadPool whose bases stay where the read filter made them — in device memory when one of the
+    one-pass routes ran (`device` >= 0), in host memory otherwise (`device` -1).  The view's arrays as numpy arrays:
+    base_off, name_off (the names themselves are never kept), gap_begin, gap_read, unmapped_read; n_reads; device_bytes;
+    read(r): read r's bases (a copy from the device a call: for tests); total, stats as filter_reads_gaps returns them."""
+
+    def __init__(self, handle, n_gaps, total, stats):
+        import numpy as np
+        self.h, self.n_gaps, self.total, self.stats = handle, n_gaps, total, stats
+        v = load_library().g2s_device_pool_view(handle).contents
+        self.n_reads = int(v.n_reads)
+
+        def arr(ptr, n, dtype):
+            return np.ctypeslib.as_array(ptr, shape=(n,)).astype(dtype, copy=True) if n else np.zeros(0, dtype)
+        self.base_off = arr(v.base_off, self.n_reads + 1, np.uint64)
+        self.name_off = arr(v.name_off, self.n_reads + 1, np.uint64)
+        self.gap_begin = arr(v.gap_begin, n_gaps + 1, np.uint64)
+        self.gap_read = arr(v.gap_read, int(self.gap_begin[n_gaps]), np.uint32)
+        self.unmapped_read = arr(v.unmapped_read, int(v.n_unmapped), np.uint32)
+        self.bases_is_null, self.names_is_null = not v.bases, not v.names
+
+    @property
+    def device(self):
+        return load_library().g2s_device_pool_device(self.h)
+
+    @property
+    def device_bytes(self):
+        return load_library().g2s_device_pool_bytes(self.h)
+
+    def read(self, r):
+        if not 0 <= r < self.n_reads:
+            raise IndexError(r)
+        n = int(self.base_off[r + 1] - self.base_off[r])
+        buf = C.create_string_buffer(max(1, n))
+        rc = load_library().g2s_device_pool_read(self.h, r, buf)
+        if rc != G2S_OK:
+            raise G2SError(rc, (load_library().g2s_filter_last_error() or b"").decode("utf-8", "replace"))
+        return buf.raw[:n]
+
+    def gap_reads(self, i):
+        if not 0 <= i < self.n_gaps:
+            raise IndexError(i)
+        return [int(x) for x in self.gap_read[int(self.gap_begin[i]):int(self.gap_begin[i + 1])]]
+
+    def free(self):
+        if self.h:
+            load_library().g2s_device_pool_free(self.h)
+            self.h = None
+
+
+def filter_reads_gaps_dpool(bam, mean, std_dev, gaps, device=0, threads=0, unmapped=True):
+    """g2s_filter_reads_gaps_dpool / _mem: filter_reads_gaps_pool(names=True) handing over a DevicePool.  The call asks
+    for one-pass mode by itself; filter_set_one_pass(0) forbids it and gives a host-held pool."""
+    lib = load_library()
+    arr = _filter_gap_array(gaps)
+    n = len(gaps)
+    o = g2s_filter_opts(mean, std_dev, 0, -1, -1, 0, threads, b"")
+    out = _VP()
+    tot = C.c_int64(0)
+    st = g2s_filter_stats()
+    tail = [C.byref(o), arr, n, device, int(bool(unmapped)), C.byref(out), C.byref(tot), C.byref(st)]
+    if isinstance(bam, (bytes, bytearray)):
+        rc = lib.g2s_filter_reads_gaps_dpool_mem(bytes(bam), len(bam), *tail)
+    else:
+        rc = lib.g2s_filter_reads_gaps_dpool(str(bam).encode(), *tail)
+    if rc != G2S_OK:
+        raise G2SError(rc, (lib.g2s_filter_last_error() or b"").decode("utf-8", "replace"))
+    stats = dict(file_passes=st.file_passes, on_device=st.on_device, ms_inflate=st.ms_inflate, ms_join=st.ms_join,
+                 ms_text=st.ms_text)
+    return DevicePool(out, n, tot.value, stats)
+
+
+def test_last_dpool():
+    """g2s_test_last_dpool: of the last filter_reads_gaps_dpool, whether its pool is device-held and the bytes of bases
+    that became host memory; of the last pooled build, the text positions gathered on the device / packed on the host."""
+    held, down, gathered, packed = C.c_int(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    _check(load_library().g2s_test_last_dpool(C.byref(held), C.byref(down), C.byref(gathered), C.byref(packed)))
+    return dict(held_on_device=held.value, bases_bytes_to_host=down.value, text_bytes_gathered_on_device=gathered.value,
+                text_bytes_packed_on_host=packed.value)
+
+
 class Graph:
     """g2s_graph: replaces gatb Graph::create / Graph::load (Gap2Seq.cpp:193-219)."""
 
@@ -601,6 +698,38 @@ class Graph:
             return cls(h)
         _check(lib.g2s_graph_build_pool(arr, lens, n, set_begin, set_seq, sh, len(shared), flags, len(set_lists), k, solid,
                                         nthreads, C.byref(h)))
+        return cls(h)
+
+    @classmethod
+    def from_dpools(cls, pools, set_lists, k, solid, shared=None, set_shared=None, reach=None, nthreads=0):
+        """g2s_graph_build_dpool_reach: from_pool over the reads of `pools` (DevicePool objects), read r of pools[p]
+        having the index sum(n_reads of pools[:p]) + r; the other arguments as from_pool's."""
+        lib = load_library()
+        hs = (_VP * max(1, len(pools)))(*[p.h for p in pools])
+        begin, flat = [0], []
+        for lst in set_lists:
+            flat.extend(lst)
+            begin.append(len(flat))
+        set_begin = (C.c_uint64 * len(begin))(*begin)
+        set_seq = (C.c_uint32 * max(1, len(flat)))(*flat)
+        shared = list(shared) if shared is not None else []
+        sh = (C.c_uint32 * len(shared))(*shared) if shared else None
+        flags = None
+        if set_shared is not None:
+            if len(set_shared) != len(set_lists):
+                raise ValueError("set_shared needs one entry a set")
+            flags = (C.c_uint8 * max(1, len(set_lists)))(*[1 if f else 0 for f in set_shared])
+        gaps = radius = keep = None
+        if reach is not None:
+            if len(reach) != len(set_lists):
+                raise ValueError("reach needs one entry a set")
+            blank = Gap("", "", 0, 0, 0)
+            gaps, keep = _gap_array([r[0] if r is not None else blank for r in reach])
+            radius = (C.c_int32 * max(1, len(reach)))(*[int(r[1]) if r is not None else -1 for r in reach])
+        h = _VP()
+        _check(lib.g2s_graph_build_dpool_reach(hs, len(pools), set_begin, set_seq, sh, len(shared), flags, len(set_lists), k,
+                                               solid, nthreads, gaps, radius, C.byref(h)))
+        del keep
         return cls(h)
 
     @property

@@ -591,6 +591,50 @@ void g2s_read_pool_free(g2s_read_pool* p);
  * Outputs, messages and codes are the same bytes on every route; g2s_filter_stats::file_passes says which one ran. */
 int g2s_filter_set_one_pass(int mode);
 
+/* ---------------------------------------------------------------------------
+ *  A DEVICE-HELD read pool (ABI 6, additive): g2s_filter_reads_gaps_pool with the reads' bases left where pass B made
+ *  them, and the pooled build reading them there, so that a set graph is built from BAM libraries without the reads
+ *  becoming host memory.  Joins, limits, codes, messages, *total and stats are g2s_filter_reads_gaps_pool's.
+ *    view     a g2s_read_pool the handle owns, with bases == NULL and names == NULL; n_reads, base_off, name_off
+ *             (always: callers want the lengths), gap_begin, gap_read, n_unmapped and unmapped_read equal what
+ *             g2s_filter_reads_gaps_pool(..., want_names = 1, ...) returns for the same call.
+ *    device   the device whose memory holds the bases, or -1 when they lie in host memory.
+ *    bytes    the device bytes the handle holds.
+ *    read     copies read r's base_off[r+1] - base_off[r] characters to `out` (for tests and debugging: one copy a call).
+ *  The call asks for one-pass mode by itself (g2s_filter_set_one_pass(0) and G2S_FILTER_ONE_PASS=0 still forbid it).
+ *  When one of the two one-pass routes ran, pass B's kernels have written the bases straight into the allocation the
+ *  handle keeps, in the pooled build's layout (every read followed by one 'N', the starts as 64-bit offsets): no bases
+ *  and no names are copied to the host, only offsets, lengths and index lists, and pass B's stream is synchronised before
+ *  the call returns.  On every other route (two passes, the host walk, device -1, no gfx950, G2S_HOST_FILTER,
+ *  G2S_HOST_ROWS, G2S_HOST_INFLATE, a store overflow, a failed allocation) the handle is host-held, with the same
+ *  contents; a caller never has to care which kind it got.  *out is written on G2S_OK only.
+ *  g2s_device_pool_free sets the handle's device before it frees.  A build keeps no pointer into a pool: pools may be
+ *  freed while graphs built from them live.
+ * ------------------------------------------------------------------------ */
+typedef struct g2s_device_pool g2s_device_pool;
+int g2s_filter_reads_gaps_dpool(const char* bam_path, const g2s_filter_opts* lib, const g2s_filter_gap* gaps, size_t n,
+                                int device, int want_unmapped, g2s_device_pool** out, int64_t* total, g2s_filter_stats* stats);
+int g2s_filter_reads_gaps_dpool_mem(const void* bam_bytes, size_t nbytes, const g2s_filter_opts* lib, const g2s_filter_gap* gaps,
+                                    size_t n, int device, int want_unmapped, g2s_device_pool** out, int64_t* total,
+                                    g2s_filter_stats* stats);
+const g2s_read_pool* g2s_device_pool_view(const g2s_device_pool* p);
+int g2s_device_pool_device(const g2s_device_pool* p);
+uint64_t g2s_device_pool_bytes(const g2s_device_pool* p);
+int g2s_device_pool_read(const g2s_device_pool* p, uint64_t r, char* out);
+void g2s_device_pool_free(g2s_device_pool* p);
+/* g2s_graph_build_pool_reach over such pools: read r of pools[p] has index first[p] + r, first[p] being the sum of n_reads
+ * over the earlier pools; every other argument, the argument errors (an index >= the pools' total, npools == 0, exactly
+ * one reach array NULL: G2S_ERR_ARG, *out not written) and the graph are g2s_graph_build_pool_reach's on the sequences
+ * the pools hold (both reach arrays NULL: g2s_graph_build_pool's).  The device build copies the reads in use that lie in
+ * a pool held on its device into its text device to device; reads of a host-held pool, or of a pool on another device,
+ * are packed on the host and uploaded, their share of the text only.  The host build (no device, G2S_HOST_BUILD=1, the
+ * device build giving up, and one set without reach records, which is an ordinary graph build) copies a device-held
+ * pool's text down once a call. */
+int g2s_graph_build_dpool_reach(const g2s_device_pool* const* pools, uint32_t npools, const uint64_t* set_begin,
+                                const uint32_t* set_seq, const uint32_t* shared_seq, uint64_t nshared,
+                                const uint8_t* set_shared, uint32_t nsets, int k, int solid, int nthreads,
+                                const struct g2s_gap* reach_gap, const int32_t* reach_radius, g2s_graph** out);
+
 /* The chunked device inflate of plain gzip read files (ABI 6, additive), process-wide and atomic: 1 asks for it in every
  * later g2s_graph_build_files, 0 forbids it, -1 (the initial state) follows the environment (G2S_DEVICE_GZIP=1|0, read
  * per call; off when it is not set).  Returns the previous mode.  With it a read file that is gzip but no BGZF file (a

@@ -120,6 +120,15 @@ int g2s_test_filter_join(int device, int32_t threads, uint64_t nr, const int32_t
  * pointer may be NULL. */
 int g2s_test_last_pool_build(uint64_t* own_positions, uint64_t* shared_positions, uint64_t* keys_sorted, int* on_device);
 
+/* TEST HOOK: the device-held read pools (g2s.h: g2s_device_pool).  Of the process's last g2s_filter_reads_gaps_dpool[_mem]:
+ * held_on_device, 1 when the handle it returned holds its bases in device memory, and bases_bytes_to_host, the bytes of
+ * bases that became host memory in that call (0 for a device-held handle).  Of the process's last pooled build
+ * (g2s_graph_build_pool[_reach], g2s_graph_build_dpool_reach): the positions (bases + 1) of the sequences in use, once
+ * each, that the device build copied from a device-held pool (text_bytes_gathered_on_device) and that went through host
+ * memory (text_bytes_packed_on_host; the host build: all of them).  Any pointer may be NULL. */
+int g2s_test_last_dpool(int* held_on_device, uint64_t* bases_bytes_to_host, uint64_t* text_bytes_gathered_on_device,
+                        uint64_t* text_bytes_packed_on_host);
+
 /* TEST HOOK: what the process's last single-graph build (g2s_graph_build_files / g2s_graph_build_seqs) did for its solid
  * k-mer set.  positions: bases + 1 of every sequence; passes: the key-range passes that ran on the device (0: the
  * one-sort device count, or the host count); refined_bins: the histogram bins that held more than a pass's keys and were
