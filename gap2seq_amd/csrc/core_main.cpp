@@ -34,6 +34,7 @@ int main(int argc, char** argv) {
   p.d_err = 500; p.all_paths = 1;
   int randseed = 0, device = 0, streams = 2, stream_gaps = 8192;
   int device_gzip = -1;  // -device-gzip 0|1; not given: G2S_DEVICE_GZIP, and without that the rule below
+  int reach_mode = G2S_REACH_AUTO;  // -reach auto|0|1: the graph bounded to what this run's gaps can reach
   bool streams_given = false;
   static int fasta_width = 0;  // (static: read by the output callback)
   std::string devices;  // "0,1,2": GPUs sharing the gap list (the graph is replicated)
@@ -69,11 +70,17 @@ int main(int argc, char** argv) {
     else if (a == "-stream-gaps") stream_gaps = atoi(val());
     else if (a == "-fasta-width") fasta_width = atoi(val());
     else if (a == "-device-gzip") { device_gzip = atoi(val()) != 0 ? 1 : 0; g2s_reads_set_device_gzip(device_gzip); }
+    else if (a == "-reach") {
+      const std::string v = val();
+      reach_mode = v == "auto" ? G2S_REACH_AUTO : atoi(v.c_str()) != 0 ? G2S_REACH_ALWAYS : G2S_REACH_NEVER;
+    }
     else if (a == "-help" || a == "-h") {
       std::cout << "Gap2Seq-core (MI355X) -reads a.fq[,b.fq] -filled out.fa (-scaffolds in.fa | -left S -right S -length N)\n"
                    "  [-k 31 (1..127)] [-solid 2] [-dist-error 500] [-fuz 10] [-max-mem 20] [-randseed 0]\n"
                    "  [-all-upper] [-best-only] [-unique] [-nb-cores N] [-device D | -devices D0,D1,...] [-streams 2]\n"
-                   "  [-stream-gaps 8192] [-fasta-width 0] [-device-gzip 0|1]\n"
+                   "  [-stream-gaps 8192] [-fasta-width 0] [-device-gzip 0|1] [-reach auto|0|1]\n"
+                   "  -reach 1: the graph holds only the k-mers this run's gaps can reach (the 2^30 k-mer cap then applies to\n"
+                   "  those, not to the read set); 0 never; auto (the default): only when the whole graph is over the cap\n"
                    "  -reads: FASTA or FASTQ files (plain, gzip or BGZF) and BAM files, told by their bytes; a BAM file gives\n"
                    "  every record that is neither secondary nor supplementary, as the read was sequenced\n"
                    "  -device-gzip 1: a plain gzip read file is inflated on the device from many places of its stream at once\n"
@@ -133,6 +140,58 @@ int main(int argc, char** argv) {
     if (!devices.empty()) build_dev = atoi(devices.c_str());
     setenv("G2S_DEVICE", std::to_string(build_dev).c_str(), 1);
   }
+  // the gaps come first: their reach records bound the graph (g2s_graph_build_files_reach) when -reach asks for it or,
+  // with auto, when the whole graph is over the cap
+  const bool single = saw_left && saw_right && saw_len;
+  std::string scaffolds_text;
+  bool scaffolds_read = false;
+  auto read_scaffolds = [&]() -> bool {
+    if (scaffolds_read) return true;
+    FILE* f = fopen(scaffolds.c_str(), "rb");
+    if (!f) { std::cout << "EXCEPTION: cannot open " << scaffolds << std::endl; return false; }
+    char buf[1 << 16];
+    size_t got;
+    while ((got = fread(buf, 1, sizeof buf, f)) > 0) scaffolds_text.append(buf, got);
+    fclose(f);
+    return scaffolds_read = true;
+  };
+  // (-reach 0 needs no records: the scaffolds are read behind the graph build, as ever)
+  if (!single && reach_mode != G2S_REACH_NEVER && !read_scaffolds()) return EXIT_FAILURE;
+  g2s_reach_records* records = nullptr;
+  g2s_gap one_gap;
+  int32_t one_radius = 0;
+  const g2s_gap* reach_gap = nullptr;
+  const int32_t* reach_radius = nullptr;
+  uint64_t nreach = 0;
+  if (reach_mode != G2S_REACH_NEVER && single) {
+    memset(&one_gap, 0, sizeof one_gap);
+    one_gap.left = left.c_str();
+    one_gap.right = right.c_str();
+    one_gap.left_len = (int32_t)left.size();
+    one_gap.right_len = (int32_t)right.size();
+    one_gap.gap_len = length;
+    one_gap.lmf = std::min((int)left.size() - o.k, o.max_fuz);   // (as g2s_execute_single takes them)
+    one_gap.rmf = std::min((int)right.size() - o.k, o.max_fuz);
+    one_gap.skip_if_prev_right_fuz_gt = -1;
+    one_radius = (int32_t)std::min<long long>(std::max(0ll, (long long)length + p.d_err) + std::max(0, one_gap.lmf) + std::max(0, one_gap.rmf),
+                                              2147483647ll);
+    reach_gap = &one_gap;
+    reach_radius = &one_radius;
+    nreach = 1;
+  } else if (reach_mode != G2S_REACH_NEVER) {
+    if (g2s_scaffolds_reach(scaffolds_text.c_str(), o.k, o.max_fuz, p.d_err, &records) != G2S_OK) {
+      std::cout << "EXCEPTION: -k and -fuz do not give reach records" << std::endl;
+      return EXIT_FAILURE;
+    }
+    reach_gap = g2s_reach_records_gaps(records);
+    reach_radius = g2s_reach_records_radii(records);
+    nreach = g2s_reach_records_count(records);
+    if (nreach == 0) { static const g2s_gap no_gap = {}; static const int32_t no_radius = 0; reach_gap = &no_gap; reach_radius = &no_radius; }
+  }
+  auto build = [&](g2s_graph** out) {
+    return reach_gap ? g2s_graph_build_files_reach(reads.c_str(), o.k, o.solid, 0, reach_gap, reach_radius, nreach, reach_mode, out)
+                     : g2s_graph_build_files(reads.c_str(), o.k, o.solid, 0, out);
+  };
   g2s_graph* g = nullptr;
   const std::string cache = reads + ".g2s";  // the reference reuses "<reads>.h5" (:171,195-197)
   int rc;
@@ -142,14 +201,19 @@ int main(int argc, char** argv) {
     if (rc == G2S_OK && (g2s_graph_k(g) != o.k || g2s_graph_solid(g) != o.solid)) {  // a cache of another -k or -solid is not this run's graph
       g2s_graph_free(g);
       g = nullptr;
-      rc = g2s_graph_build_files(reads.c_str(), o.k, o.solid, 0, &g);
+      rc = build(&g);
     }
   } else {
-    rc = g2s_graph_build_files(reads.c_str(), o.k, o.solid, 0, &g);
+    rc = build(&g);
     // like Graph::create leaving "<reads>.h5" behind for the next run (:195-197); opt-in here
     // because the file is as large as the graph (32 B per k-mer)
-    if (rc == G2S_OK && getenv("G2S_SAVE_GRAPH")) (void)g2s_graph_save(g, cache.c_str());
+    if (rc == G2S_OK && getenv("G2S_SAVE_GRAPH")) {
+      // (a bounded graph belongs to this gap list, not to the reads)
+      if (g2s_graph_bounded(g)) std::cerr << "[g2s] the graph is bounded to this run's gaps (-reach): not saved as " << cache << std::endl;
+      else (void)g2s_graph_save(g, cache.c_str());
+    }
   }
+  if (records) g2s_reach_records_free(records);
   if (rc != G2S_OK) {
     std::cout << "DBG building failed: " << g2s_last_error() << std::endl;  // :215-218
     return EXIT_FAILURE;
@@ -192,16 +256,11 @@ int main(int argc, char** argv) {
   if (!helpers.empty()) g2s_session_set_team(s, helpers.data(), (int)helpers.size(), per_gpu_shares ? G2S_GROUP_PER_SESSION : 0);
   if (per_gpu_shares) stream_gaps = (int)std::min<long long>((long long)std::max(0, stream_gaps) * (long long)devs.size(), 1 << 24);
   char *fasta = nullptr, *log = nullptr;
-  if (saw_left && saw_right && saw_len) {
+  if (single) {
     rc = g2s_execute_single(s, &o, reads.c_str(), filled.c_str(), left.c_str(), right.c_str(), length, &fasta, &log);
   } else {
-    FILE* f = fopen(scaffolds.c_str(), "rb");
-    if (!f) { std::cout << "EXCEPTION: cannot open " << scaffolds << std::endl; return EXIT_FAILURE; }
-    std::string text;
-    char buf[1 << 16];
-    size_t got;
-    while ((got = fread(buf, 1, sizeof buf, f)) > 0) text.append(buf, got);
-    fclose(f);
+    if (!read_scaffolds()) return EXIT_FAILURE;
+    const std::string& text = scaffolds_text;
     int32_t gaps = 0, nfilled = 0;
     // the log is printed and the records are written as the batches finish (-stream-gaps N per batch)
     // (written beside the target and renamed when the run is complete: a failed run leaves no partial -filled file)

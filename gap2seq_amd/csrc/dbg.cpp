@@ -417,18 +417,113 @@ SolidCountInfo last_solid_count() {
   return g_solid_info;
 }
 
-namespace {
-Graph* graph_build_from(const BuildInput& in, int k, int solid, int nthreads, std::string* err, bool* gave_up);
+uint64_t graph_max_kmers() {
+  const uint64_t cap = 1ull << 30;
+  const char* s = getenv("G2S_BUILD_MAX_KMERS");
+  const uint64_t v = s && *s ? strtoull(s, nullptr, 10) : 0;
+  return v && v < cap ? v : cap;
 }
+
+namespace {
+std::mutex g_graph_reach_mu;
+GraphReachInfo g_graph_reach_info;
+
+// The bounded set of a single graph on host threads (dbg.hpp: GraphReach; the device form is graph_reach.h): `keep`
+// holds the sorted solid k-mers and leaves with those of them within reach of a seed.  One search for all records: level
+// L's frontier is what level L - 1 claimed plus the seeds that enter at L = Rmax - their radius, one bit a solid k-mer
+// marks what is visited, and a k-mer is claimed at the earliest level that reaches it — the one that leaves it the most
+// budget — so that what is visited after level Rmax is the union of the records' balls.
+template <class KT>
+void reach_filter_host(std::vector<KT>& keep, const GraphReach& reach, int k, int nthreads, GraphReachInfo* info) {
+  const ReachSeeds<KT> rs = make_reach_seeds<KT>(reach, k);
+  const uint64_t n = keep.size();
+  std::vector<std::atomic<uint64_t>> vis((size_t)(n / 64 + 1));
+  for (auto& w : vis) w.store(0, std::memory_order_relaxed);
+  auto find = [&](const KT& x) -> int64_t {
+    auto it = std::lower_bound(keep.begin(), keep.end(), x);
+    return (it != keep.end() && *it == x) ? (int64_t)(it - keep.begin()) : -1;
+  };
+  auto claim = [&](uint64_t i) { return !(vis[(size_t)(i >> 6)].fetch_or(1ull << (i & 63), std::memory_order_relaxed) & (1ull << (i & 63))); };
+  const KT mask = KmerOps<KT>::mask(k);
+  std::vector<uint64_t> frontier, next;
+  std::vector<std::vector<uint64_t>> local((size_t)std::max(1, nthreads));
+  uint64_t in_full = 0;
+  uint32_t levels = 0;
+  size_t cursor = 0;
+  const auto t_search = std::chrono::steady_clock::now();
+  for (uint32_t level = 0; level <= rs.rmax; level++) {
+    uint64_t s0, s1;
+    rs.at(level, &cursor, &s0, &s1);
+    for (uint64_t s = s0; s < s1; s++) {
+      const int64_t i = find(rs.key[(size_t)s]);
+      if (i < 0) continue;
+      in_full++;
+      if (claim((uint64_t)i)) frontier.push_back((uint64_t)i);
+    }
+    if (frontier.empty()) {
+      if (cursor == rs.entry.size()) break;  // (nothing enters later either)
+      level = rs.entry[cursor] - 1;          // (on to the level at which seeds enter next)
+      continue;
+    }
+    levels = level;
+    if (level == rs.rmax) break;  // (the rim: claimed, not expanded)
+    for (auto& l : local) l.clear();
+    parallel_for(frontier.size(), nthreads, [&](uint64_t b, uint64_t e, int t) {
+      std::vector<uint64_t>& out = local[(size_t)t];
+      for (uint64_t f = b; f < e; f++) {
+        const KT c = keep[(size_t)frontier[(size_t)f]], rc = KmerOps<KT>::revcomp(c, k);
+        for (int strand = 0; strand < 2; strand++) {
+          const KT seq = strand == 0 ? c : rc, rseq = strand == 0 ? rc : c;
+          for (int nt = 0; nt < 4; nt++) {
+            const KT y = ((seq << 2) | (KT)nt) & mask;
+            const KT ry = (rseq >> 2) | ((KT)(nt ^ 2) << (2 * (k - 1)));
+            const int64_t i = find(y < ry ? y : ry);
+            if (i >= 0 && claim((uint64_t)i)) out.push_back((uint64_t)i);
+          }
+        }
+      }
+    });
+    next.clear();
+    for (auto& l : local) next.insert(next.end(), l.begin(), l.end());
+    frontier.swap(next);
+  }
+  info->ms_search = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_search).count();
+  std::vector<KT> kept;
+  for (uint64_t i = 0; i < n; i++)
+    if (vis[(size_t)(i >> 6)].load(std::memory_order_relaxed) >> (i & 63) & 1) kept.push_back(keep[(size_t)i]);
+  info->seeds_in_full = in_full;
+  info->full_kmers = n;
+  info->kept_kmers = kept.size();
+  info->levels = levels;
+  info->on_device = 0;
+  keep.swap(kept);
+}
+
+Graph* graph_build_from(const BuildInput& in, int k, int solid, int nthreads, std::string* err, bool* gave_up);
+}  // namespace
+
+GraphReachInfo last_graph_reach() {
+  std::lock_guard<std::mutex> lk(g_graph_reach_mu);
+  return g_graph_reach_info;
+}
+// dbg_gpu.hip: what the device form of the bounded build did
+void set_graph_reach_info(const GraphReachInfo& info) {
+  std::lock_guard<std::mutex> lk(g_graph_reach_mu);
+  g_graph_reach_info = info;
+}
+
 Graph* graph_build(const std::vector<std::pair<const char*, uint64_t>>& seqs, int k, int solid, int nthreads,
-                   std::string* err) {
+                   std::string* err, const GraphReach* reach) {
   BuildInput in;
   in.seqs = &seqs;
+  in.reach = reach;
   return graph_build_from(in, k, solid, nthreads, err, nullptr);
 }
-Graph* graph_build_text(DeviceText* text, int k, int solid, int nthreads, std::string* err, bool* gave_up) {
+Graph* graph_build_text(DeviceText* text, int k, int solid, int nthreads, std::string* err, bool* gave_up,
+                        const GraphReach* reach) {
   BuildInput in;
   in.text = text;
+  in.reach = reach;
   *gave_up = false;
   return graph_build_from(in, k, solid, nthreads, err, gave_up);
 }
@@ -441,6 +536,7 @@ Graph* graph_build_from(const BuildInput& in, int k, int solid, int nthreads, st
   g->k = k;
   g->solid = solid;
   g->kmer_bytes = kmer_width(k);
+  g->bounded = in.reach != nullptr;
   const auto t0 = std::chrono::steady_clock::now();
   // the solid k-mer set: sort on the GPU when there is one (dbg_gpu.hip), host threads otherwise
   bool set_on_gpu = false;
@@ -463,6 +559,19 @@ Graph* graph_build_from(const BuildInput& in, int k, int solid, int nthreads, st
     if (g->kmer_bytes == 8) count_solid<uint64_t>(*g, seqs, solid, nthreads);
     else if (g->kmer_bytes == 16) count_solid<u128>(*g, seqs, solid, nthreads);
     else count_solid<u256>(*g, seqs, solid, nthreads);
+    if (in.reach) {  // the same search as the device's, over the sorted vector
+      GraphReachInfo ri;
+      ri.records = in.reach->records;
+      ri.seeds = in.reach->seed.size();
+      if (g->kmer_bytes == 8) reach_filter_host<uint64_t>(g->kmers64, *in.reach, k, nthreads, &ri);
+      else if (g->kmer_bytes == 16) reach_filter_host<u128>(g->kmers128, *in.reach, k, nthreads, &ri);
+      else reach_filter_host<u256>(g->kmers256, *in.reach, k, nthreads, &ri);
+      g->n = ri.kept_kmers;
+      if (getenv("G2S_DEBUG"))
+        fprintf(stderr, "[g2s]   reach: %llu of %llu k-mers kept on the host, %u levels\n", (unsigned long long)ri.kept_kmers,
+                (unsigned long long)ri.full_kmers, ri.levels);
+      set_graph_reach_info(ri);
+    }
   }
   const auto t1 = std::chrono::steady_clock::now();
   if (!set_on_gpu) info.passes = info.refined_bins = 0, info.max_pass_keys = 0;
@@ -473,7 +582,7 @@ Graph* graph_build_from(const BuildInput& in, int k, int solid, int nthreads, st
     g_solid_info = info;
   }
   const std::string how = !set_on_gpu ? "host" : info.passes ? "GPU, " + std::to_string(info.passes) + " key-range passes" : "GPU sort";
-  if (g->n >= (1ull << 30)) { if (err) *err = "too many k-mers for 32-bit oriented node ids"; delete g; return nullptr; }
+  if (g->n >= graph_max_kmers()) { if (err) *err = kTooManyKmers; delete g; return nullptr; }
   if (g->kmer_bytes == 8) finish_graph<uint64_t>(*g, nthreads);
   else if (g->kmer_bytes == 16) finish_graph<u128>(*g, nthreads);
   else finish_graph<u256>(*g, nthreads);

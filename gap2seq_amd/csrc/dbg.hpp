@@ -8,6 +8,7 @@
 // sites are Gap2Seq.cpp:879,884,924,955,957,995,1000,1043,1084,1086,1114,1199,
 // 1203,1204,1263,1271,1452,1456,1476.  Membership is exact (no Bloom filter).
 #pragma once
+#include <algorithm>
 #include <mutex>
 #include <cstdint>
 #include <map>
@@ -40,6 +41,7 @@ struct Graph {
   int kmer_bytes = 8; // k-mer width: 8 (k <= 31), 16 (k <= 63) or 32 bytes (k <= 127); kmer_width(k)
   uint64_t n = 0;     // canonical solid k-mers
   uint64_t n_unitigs = 0;
+  bool bounded = false;  // built from reach records (GraphReach): the k-mers a gap list can reach, not the read set's
   // sorted canonical k-mers; exactly one of the three is used (the one of kmer_bytes)
   std::vector<uint64_t> kmers64;
   std::vector<u128> kmers128;
@@ -104,20 +106,74 @@ static const int kMaxK = 127;
 // bytes of the k-mer word for k in [1, kMaxK]
 static inline int kmer_width(int k) { return k <= 31 ? 8 : k <= 63 ? 16 : 32; }
 
-// seqs may contain any bytes; k-mers containing N/n are skipped (GATB model).
+struct GraphReach;
+// seqs may contain any bytes; k-mers containing N/n are skipped (GATB model).  reach: BuildInput::reach.
 Graph* graph_build(const std::vector<std::pair<const char*, uint64_t>>& seqs, int k, int solid, int nthreads,
-                   std::string* err);
+                   std::string* err, const GraphReach* reach = nullptr);
 // What the solid k-mer count reads: the caller's sequences, or a text that is already on a device (reads_text.h: every
 // sequence followed by one 'N').  The device count frees a text as soon as it has read it for the last time.
 struct DeviceText;
+// Reach records of a single graph (g2s_graph_build_seqs_reach / _files_reach): the graph keeps, of the solid k-mers,
+// those within radius[i] undirected steps of seed[i] for some i (k characters each, encoded as the fill's flank look-ups
+// encode them; a seed outside the solid set is ignored).  One entry a seed: a record's seeds all carry its radius.
+struct GraphReach {
+  std::vector<const char*> seed;
+  std::vector<int32_t> radius;  // [seed.size()], >= 0
+  uint64_t records = 0;
+};
 struct BuildInput {
   const std::vector<std::pair<const char*, uint64_t>>* seqs = nullptr;
   DeviceText* text = nullptr;
+  const GraphReach* reach = nullptr;  // the kept set instead of the full one (the cap applies to what is kept)
 };
+// The cap on a graph's k-mers (32-bit oriented node ids): 2^30, or G2S_BUILD_MAX_KMERS when that is lower (tests).
+uint64_t graph_max_kmers();
+static const char* const kTooManyKmers = "too many k-mers for 32-bit oriented node ids";
+// The seeds of a bounded build as canonical k-mers in the order they enter the search: seed i at level
+// Rmax - radius[i], so that a k-mer is claimed with the largest budget any record leaves it (graph_reach.h).
+template <class KT>
+struct ReachSeeds {
+  std::vector<KT> key;            // sorted by entry level
+  std::vector<uint32_t> entry;    // the distinct entry levels, ascending (sparse: a radius is bounded by int32 alone)
+  std::vector<uint64_t> begin;    // [entry.size() + 1]: the seeds of level entry[j] are key[begin[j] .. begin[j + 1])
+  uint32_t rmax = 0;
+  // the seeds that enter at `level`, *cursor being the first entry level not yet taken (levels are asked for in order)
+  void at(uint32_t level, size_t* cursor, uint64_t* s0, uint64_t* s1) const {
+    *s0 = *s1 = 0;
+    if (*cursor < entry.size() && entry[*cursor] == level) { *s0 = begin[*cursor]; *s1 = begin[*cursor + 1]; ++*cursor; }
+  }
+};
+template <class KT>
+static inline ReachSeeds<KT> make_reach_seeds(const GraphReach& reach, int k) {
+  ReachSeeds<KT> rs;
+  int32_t rmax = 0;
+  for (int32_t r : reach.radius) rmax = r > rmax ? r : rmax;
+  rs.rmax = (uint32_t)rmax;
+  std::vector<std::pair<uint32_t, size_t>> order(reach.seed.size());  // (entry level, seed)
+  for (size_t i = 0; i < reach.seed.size(); i++) order[i] = {(uint32_t)(rmax - reach.radius[i]), i};
+  std::sort(order.begin(), order.end());
+  rs.key.resize(order.size());
+  for (size_t j = 0; j < order.size(); j++) {
+    if (rs.entry.empty() || rs.entry.back() != order[j].first) { rs.entry.push_back(order[j].first); rs.begin.push_back(j); }
+    int strand;
+    encode_kmer<KT>(reach.seed[order[j].second], k, &rs.key[j], &strand);
+  }
+  rs.begin.push_back(order.size());
+  return rs;
+}
+// What the process's last bounded single-graph build did (g2s_test_last_graph_reach).
+struct GraphReachInfo {
+  uint64_t records = 0, seeds = 0, seeds_in_full = 0, full_kmers = 0, kept_kmers = 0;
+  uint32_t levels = 0, passes = 0, regrowths = 0;
+  int on_device = 0;
+  double ms_search = 0;  // the level loop alone (the last run of it, when the queue had to grow), wall time
+};
+GraphReachInfo last_graph_reach();
 // graph_build from a text on a device.  Only the device count can read it: when that gives up (G2S_HOST_BUILD, no room,
 // a HIP error) the result is nullptr with *gave_up set and the reason in *err, and the caller builds from the sequences.
 // The text is the caller's to free either way (free_device_text: what the count has freed already is not freed twice).
-Graph* graph_build_text(DeviceText* text, int k, int solid, int nthreads, std::string* err, bool* gave_up);
+Graph* graph_build_text(DeviceText* text, int k, int solid, int nthreads, std::string* err, bool* gave_up,
+                        const GraphReach* reach = nullptr);
 // What the process's last graph_build did for its solid k-mer set (g2s_test_last_solid_count): the text positions (bases
 // + 1 a sequence), the key-range passes that ran (dbg_gpu.hip's pass form; 0: the one-sort device count, or the host), the
 // histogram bins that had to be histogrammed again, the keys of the largest pass, the solid k-mers found, and whether the

@@ -817,6 +817,8 @@ __global__ void k_reach_copy_kept(const KT* __restrict__ sk, const uint32_t* __r
 
 }  // namespace
 
+#include "graph_reach.h"
+
 namespace g2s {
 
 // Everything of the graph build after the sorted solid k-mer set (and its prefix index):
@@ -1090,6 +1092,31 @@ static bool count_solid_gpu_t(Graph& g, std::vector<KT>& out, const BuildInput& 
     }
   }
   G2S_HIP_TRY(hipGetLastError());
+  // ---- with reach records: the kept part of the set takes the set's place (graph_reach.h)
+  if (in.reach) {
+    GraphReachInfo rinfo;
+    uint64_t nkept = 0;
+    DevMem d_kept;
+    // (the sort's buffers are read for the last time by k_compact: the search's index, bitmap and queue take their room)
+    G2S_HIP_TRY(hipDeviceSynchronize());
+    d_keys.free(); d_alt.free(); d_lo.free(); d_hi.free(); d_lo2.free(); d_hi2.free(); d_flag.free(); d_pos.free();
+    d_hidx.free(); d_keep.free(); d_kpos.free(); d_tmp.free(); d_tmp2.free();
+    if (n_solid && !reach_on_device<KT>((const KT*)d_out.p, (uint64_t)n_solid, k, *in.reach, d_kept, &nkept, why, &rinfo)) return false;
+    if (!n_solid) { rinfo.records = in.reach->records; rinfo.seeds = in.reach->seed.size(); rinfo.on_device = 1; }
+    set_graph_reach_info(rinfo);
+    if (getenv("G2S_DEBUG"))
+      fprintf(stderr, "[g2s]   reach: %llu of %llu k-mers kept on the GPU, %u levels, the queue grown %u times\n",
+              (unsigned long long)nkept, (unsigned long long)n_solid, rinfo.levels, rinfo.regrowths);
+    if (nkept >= graph_max_kmers()) {  // (graph_build refuses it: nothing comes down)
+      out.clear();
+      g.n = nkept;
+      g.bucket.clear();
+      return true;
+    }
+    d_out.free();
+    d_out = std::move(d_kept);
+    n_solid = (uint32_t)nkept;
+  }
   // ---- prefix index and the copies the host keeps (node look-ups, node strings)
   const int bits = std::min(2 * k, 22);
   const uint32_t nb = 1u << bits;

@@ -137,16 +137,92 @@ struct g2s_graph {
   Graph* g = nullptr;
 };
 
-extern "C" int g2s_graph_build_seqs(const char* const* seqs, const uint64_t* lens, int nseqs, int k, int solid,
-                                    int nthreads, g2s_graph** out) {
+static int build_seqs_of(const char* const* seqs, const uint64_t* lens, int nseqs, int k, int solid, int nthreads,
+                         const GraphReach* reach, g2s_graph** out) {
   if (!seqs || !out || nseqs < 0) return fail(G2S_ERR_ARG, "g2s_graph_build_seqs: bad argument");
   std::vector<std::pair<const char*, uint64_t>> v;
   for (int i = 0; i < nseqs; i++) v.emplace_back(seqs[i], lens ? lens[i] : (uint64_t)strlen(seqs[i]));
   std::string err;
-  Graph* g = graph_build(v, k, solid, nthreads, &err);
+  Graph* g = graph_build(v, k, solid, nthreads, &err, reach);
   if (!g) return fail(G2S_ERR_ARG, err);
   *out = new g2s_graph();
   (*out)->g = g;
+  return G2S_OK;
+}
+extern "C" int g2s_graph_build_seqs(const char* const* seqs, const uint64_t* lens, int nseqs, int k, int solid,
+                                    int nthreads, g2s_graph** out) {
+  return build_seqs_of(seqs, lens, nseqs, k, solid, nthreads, nullptr, out);
+}
+
+// ---- single graphs bounded by reach records (include/g2s.h: g2s_graph_build_seqs_reach) --------------------
+// the records' seeds, one entry a seed with its record's radius: the flank k-mers the fill looks up
+// (build_pool_reach_of below takes the same ones), none for a gap it rejects
+static int graph_reach_of(const char* name, int k, const g2s_gap* reach_gap, const int32_t* reach_radius, uint64_t nreach,
+                          GraphReach* reach) {
+  if (nreach && (!reach_gap || !reach_radius)) return fail(G2S_ERR_ARG, std::string(name) + ": reach_gap and reach_radius go together");
+  if (k < 1 || k > kMaxK) return fail(G2S_ERR_ARG, "k must be in [1," + std::to_string(kMaxK) + "]");  // (the seeds read k characters)
+  for (uint64_t r = 0; r < nreach; r++)
+    if (reach_radius[r] < 0) return fail(G2S_ERR_ARG, std::string(name) + ": negative radius in record " + std::to_string(r));
+  reach->records = nreach;
+  for (uint64_t r = 0; r < nreach; r++) {
+    const g2s_gap& in = reach_gap[r];
+    if (!in.left || !in.right || in.lmf < 0 || in.rmf < 0 || in.gap_len < 0 || in.left_len < k + in.lmf || in.right_len < k + in.rmf) continue;
+    for (int x = 0; x <= in.lmf; x++) reach->seed.push_back(in.left + x);
+    for (int x = 0; x <= in.rmf; x++) reach->seed.push_back(in.right + (in.right_len - k - x));
+    for (int x = 0; x <= in.rmf; x++) reach->seed.push_back(in.right + x);
+    reach->radius.resize(reach->seed.size(), reach_radius[r]);
+  }
+  return G2S_OK;
+}
+// G2S_REACH_AUTO resolved: G2S_BUILD_REACH=1|0 overrides it; -1 for a mode that is none of the three
+static int reach_mode_of(int mode) {
+  if (mode != G2S_REACH_AUTO && mode != G2S_REACH_ALWAYS && mode != G2S_REACH_NEVER) return -1;
+  const char* s = getenv("G2S_BUILD_REACH");
+  if (mode == G2S_REACH_AUTO && s && *s) return strcmp(s, "0") != 0 ? G2S_REACH_ALWAYS : G2S_REACH_NEVER;
+  return mode;
+}
+// plain(reach) is the build: with nullptr today's path.  AUTO runs that first and starts over on the cap error alone.
+template <class Build>
+static int build_with_reach(const char* name, int k, const g2s_gap* reach_gap, const int32_t* reach_radius, uint64_t nreach, int mode,
+                            g2s_graph** out, Build&& build) {
+  if (!out) return fail(G2S_ERR_ARG, std::string(name) + ": bad argument");
+  mode = reach_mode_of(mode);
+  if (mode < 0) return fail(G2S_ERR_ARG, std::string(name) + ": unknown mode");
+  if (!reach_gap && !reach_radius) return build(nullptr);  // (no records: the plain call)
+  GraphReach reach;
+  const int rc = graph_reach_of(name, k, reach_gap, reach_radius, nreach, &reach);
+  if (rc != G2S_OK) return rc;
+  if (mode == G2S_REACH_NEVER) return build(nullptr);
+  if (mode == G2S_REACH_AUTO) {
+    const int plain = build(nullptr);
+    if (plain == G2S_OK || tl_error != kTooManyKmers) return plain;
+    if (getenv("G2S_DEBUG")) fprintf(stderr, "[g2s] graph build: over the cap, starting over bounded by %llu reach records\n", (unsigned long long)nreach);
+  }
+  return build(&reach);
+}
+extern "C" int g2s_graph_build_seqs_reach(const char* const* seqs, const uint64_t* lens, int nseqs, int k, int solid, int nthreads,
+                                          const g2s_gap* reach_gap, const int32_t* reach_radius, uint64_t nreach, int mode,
+                                          g2s_graph** out) {
+  return build_with_reach("g2s_graph_build_seqs_reach", k, reach_gap, reach_radius, nreach, mode, out, [&](const GraphReach* reach) {
+    return build_seqs_of(seqs, lens, nseqs, k, solid, nthreads, reach, out);
+  });
+}
+extern "C" int g2s_graph_bounded(const g2s_graph* g) { return g && g->g->bounded ? 1 : 0; }
+// TEST HOOK (include/g2s_test.h)
+extern "C" int g2s_test_last_graph_reach(uint64_t* records, uint64_t* seeds, uint64_t* seeds_in_full, uint64_t* full_kmers,
+                                         uint64_t* kept_kmers, uint32_t* levels, uint32_t* passes, uint32_t* regrowths, int* on_device,
+                                         double* ms_search) {
+  const GraphReachInfo info = last_graph_reach();
+  if (ms_search) *ms_search = info.ms_search;
+  if (records) *records = info.records;
+  if (seeds) *seeds = info.seeds;
+  if (seeds_in_full) *seeds_in_full = info.seeds_in_full;
+  if (full_kmers) *full_kmers = info.full_kmers;
+  if (kept_kmers) *kept_kmers = info.kept_kmers;
+  if (levels) *levels = info.levels;
+  if (passes) *passes = info.passes;
+  if (regrowths) *regrowths = info.regrowths;
+  if (on_device) *on_device = info.on_device;
   return G2S_OK;
 }
 
@@ -411,7 +487,17 @@ std::vector<std::string> split_csv(const char* reads_csv) {  // comma separated 
 }
 }  // namespace
 
+static int build_files_of(const char* reads_csv, int k, int solid, int nthreads, const GraphReach* reach, g2s_graph** out);
 extern "C" int g2s_graph_build_files(const char* reads_csv, int k, int solid, int nthreads, g2s_graph** out) {
+  return build_files_of(reads_csv, k, solid, nthreads, nullptr, out);
+}
+extern "C" int g2s_graph_build_files_reach(const char* reads_csv, int k, int solid, int nthreads, const g2s_gap* reach_gap,
+                                           const int32_t* reach_radius, uint64_t nreach, int mode, g2s_graph** out) {
+  return build_with_reach("g2s_graph_build_files_reach", k, reach_gap, reach_radius, nreach, mode, out, [&](const GraphReach* reach) {
+    return build_files_of(reads_csv, k, solid, nthreads, reach, out);
+  });
+}
+static int build_files_of(const char* reads_csv, int k, int solid, int nthreads, const GraphReach* reach, g2s_graph** out) {
   if (!reads_csv || !out) return fail(G2S_ERR_ARG, "g2s_graph_build_files: bad argument");
   const std::vector<std::string> files = split_csv(reads_csv);
   const bool debug = getenv("G2S_DEBUG") != nullptr;
@@ -441,7 +527,7 @@ extern "C" int g2s_graph_build_files(const char* reads_csv, int k, int solid, in
                 (unsigned long long)info.records, (unsigned long long)info.pieces, ms_since(t0) / 1e3);
       bool gave_up = false;
       std::string err;
-      Graph* g = graph_build_text(&text, k, solid, nthreads, &err, &gave_up);
+      Graph* g = graph_build_text(&text, k, solid, nthreads, &err, &gave_up, reach);
       free_device_text(&text);
       if (g) {
         set_reads_info(info);
@@ -492,7 +578,7 @@ extern "C" int g2s_graph_build_files(const char* reads_csv, int k, int solid, in
   }
   info.records = recs.size();
   std::string err;
-  Graph* g = graph_build(v, k, solid, nthreads, &err);
+  Graph* g = graph_build(v, k, solid, nthreads, &err, reach);
   if (!g) return fail(G2S_ERR_ARG, err);
   set_reads_info(info);
   *out = new g2s_graph();

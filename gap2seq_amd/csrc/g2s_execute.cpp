@@ -242,6 +242,17 @@ extern "C" int g2s_execute_scaffolds_stream(g2s_session* s, const g2s_run_opts* 
       jobs[j].left = flanks[flank_idx[j].first].c_str();
       jobs[j].right = flanks[flank_idx[j].second].c_str();
     }
+    // G2S_JOBS_DUMP=FILE (tests): every job as the scanner hands it to the fill, a line
+    // "<record> <istart> <iend> <kmer_start> <lmf> <rmf> <gap> <left> <right>", appended batch by batch
+    if (const char* dump = getenv("G2S_JOBS_DUMP")) {
+      if (FILE* f = fopen(dump, "a")) {
+        for (const GapEvent& ev : events)
+          if (ev.job >= 0)
+            fprintf(f, "%zu %zu %zu %d %d %d %d %s %s\n", ev.rec, ev.istart, ev.iend, ev.kmer_start, ev.lmf, ev.rmf, ev.gap,
+                    jobs[(size_t)ev.job].left, jobs[(size_t)ev.job].right);
+        fclose(f);
+      }
+    }
 
     c->sr = sr; c->si = si; c->barrier = barrier; c->soft = soft;
     return c;
@@ -437,3 +448,63 @@ extern "C" int g2s_execute_single(g2s_session* s, const g2s_run_opts* o, const c
   if (log_out) *log_out = dup_text(os.str());
   return G2S_OK;
 }
+
+// ---- reach records of a scaffolds text (include/g2s.h: g2s_scaffolds_reach) -----------------------------------------
+// One record per N-run, from the runs alone: whatever state the scanner above is in when it meets the run (the previous
+// gap's right_fuz, a barrier, the skip rule), its left flank starts at or behind max(previous run's end, istart - k -
+// max_fuz) and ends at istart, and its right flank is the one taken here.
+struct g2s_reach_records {
+  std::vector<std::string> flanks;
+  std::vector<g2s_gap> gaps;
+  std::vector<int32_t> radii;
+};
+extern "C" int g2s_scaffolds_reach(const char* scaffolds_text, int k, int max_fuz, int d_err, g2s_reach_records** out) {
+  if (!scaffolds_text || !out || k < 1 || max_fuz < 0) return G2S_ERR_ARG;
+  std::vector<FastxRecord> recs;
+  parse_fastx(std::string(scaffolds_text), &recs);
+  std::unique_ptr<g2s_reach_records> h(new g2s_reach_records);
+  std::vector<std::pair<size_t, size_t>> idx;
+  for (const FastxRecord& rec : recs) {
+    const std::string& seq = rec.seq;
+    size_t si = 0, prev_end = 0;
+    while (si < seq.size()) {
+      if (!is_n(seq[si])) { si++; continue; }
+      const size_t istart = si;
+      int gap = 0;
+      while (si < seq.size() && is_n(seq[si])) { si++; gap++; }
+      const long long a = std::max<long long>({(long long)prev_end, (long long)istart - k - max_fuz, 0});
+      const int lmf = (int)((long long)istart - a) - k;  // negative: no left seed (the fill rejects such a gap)
+      int rmf = std::min((int)seq.size() - ((int)si + k), max_fuz);
+      bool ok = rmf >= 0 && si + (size_t)k + (size_t)rmf <= seq.size();
+      for (int j = 0; ok && j < k + rmf; j++)
+        if (is_n(seq[si + (size_t)j])) ok = false;
+      g2s_gap gj;
+      memset(&gj, 0, sizeof gj);
+      h->flanks.push_back(seq.substr((size_t)a, istart - (size_t)a));
+      h->flanks.push_back(ok ? seq.substr(si, (size_t)(k + rmf)) : std::string());
+      idx.emplace_back(h->flanks.size() - 2, h->flanks.size() - 1);
+      if (!ok) rmf = std::max(rmf, 0);
+      gj.left_len = (int32_t)(istart - (size_t)a);
+      gj.right_len = ok ? k + rmf : 0;  // (no usable right flank: shorter than k + rmf, so no seeds)
+      gj.gap_len = gap;
+      gj.lmf = lmf;
+      gj.rmf = rmf;
+      gj.skip_if_prev_right_fuz_gt = -1;
+      h->gaps.push_back(gj);
+      // (64-bit: -dist-error is the caller's; a radius beyond int32 is the largest one, which no graph of 2^30 k-mers outgrows)
+      const long long radius = std::max(0ll, (long long)gap + d_err) + std::max(0, lmf) + rmf;
+      h->radii.push_back((int32_t)std::min<long long>(radius, 2147483647ll));
+      prev_end = si;
+    }
+  }
+  for (size_t j = 0; j < h->gaps.size(); j++) {
+    h->gaps[j].left = h->flanks[idx[j].first].c_str();
+    h->gaps[j].right = h->flanks[idx[j].second].c_str();
+  }
+  *out = h.release();
+  return G2S_OK;
+}
+extern "C" uint64_t g2s_reach_records_count(const g2s_reach_records* r) { return r ? r->gaps.size() : 0; }
+extern "C" const g2s_gap* g2s_reach_records_gaps(const g2s_reach_records* r) { return r ? r->gaps.data() : nullptr; }
+extern "C" const int32_t* g2s_reach_records_radii(const g2s_reach_records* r) { return r ? r->radii.data() : nullptr; }
+extern "C" void g2s_reach_records_free(g2s_reach_records* r) { delete r; }

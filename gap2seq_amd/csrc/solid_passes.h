@@ -221,7 +221,29 @@ struct SolidPasses {
     key_words<KT>(last, rg.last);
     return rg;
   }
-  bool full() const { return out->size() >= ((size_t)1 << 30); }  // (graph_build refuses such a set: no need to finish it)
+  // With reach records the passes' solid keys stay on the device, one behind the other in d_table (graph_reach.h searches
+  // that table; it may hold any number of keys the device has room for).
+  bool keep_on_device = false;
+  DevMem d_table;
+  uint64_t table_n = 0, table_cap = 0;
+  // (graph_build refuses a host-bound set of 2^30 k-mers: no need to finish it; a device-held table is not the graph's set)
+  bool full() const { return !keep_on_device && out->size() >= ((size_t)1 << 30); }
+  bool append_on_device(const KT* d_keys, uint64_t n_new, uint64_t count) {
+    if (table_n + n_new > table_cap) {
+      // (room for the passes to come at this pass's share of solid keys; doubling behind that)
+      uint64_t want = std::max<uint64_t>(table_n + n_new, 2 * table_cap);
+      if (table_cap == 0 && count < valid_keys) want = std::max<uint64_t>(want, (uint64_t)(1.05 * (double)n_new / (double)count * (double)valid_keys) + 1024);
+      DevMem bigger;
+      G2S_HIP_TRY(bigger.alloc((size_t)want * sizeof(KT)));
+      if (table_n) G2S_HIP_TRY(hipMemcpy(bigger.p, d_table.p, (size_t)table_n * sizeof(KT), hipMemcpyDeviceToDevice));
+      d_table.free();
+      d_table = std::move(bigger);
+      table_cap = want;
+    }
+    G2S_HIP_TRY(hipMemcpy(d_table.as<KT>() + table_n, d_keys, (size_t)n_new * sizeof(KT), hipMemcpyDeviceToDevice));
+    table_n += n_new;
+    return true;
+  }
 
   // the keys below `prefix`'s bits that level `level` and the levels above it have fixed: histogram, plan, passes
   bool run_level(int level, const KT& prefix) {
@@ -316,7 +338,9 @@ struct SolidPasses {
       }
     }
     G2S_HIP_TRY(hipGetLastError());
-    if (n_solid) {
+    if (n_solid && keep_on_device) {
+      if (!append_on_device(d_out.as<KT>(), n_solid, count)) return false;
+    } else if (n_solid) {
       const size_t at = out->size();
       // (room for the passes to come at this pass's share of solid keys, so that the array is not copied as it grows)
       if (passes == 0 && count < valid_keys)
@@ -367,7 +391,9 @@ static bool count_solid_passes_gpu_t(Graph& g, std::vector<KT>& out, const Build
   }
   if (!forced) {
     G2S_HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-    cap = (uint64_t)(0.5 * (double)free_b / per_key);
+    // (with reach records the solid keys stay on the device: a quarter of the free memory is left to that table, whose
+    // growth holds the old and the new array at once)
+    cap = (uint64_t)((in.reach ? 0.25 : 0.5) * (double)free_b / per_key);
   }
   cap = std::min(cap, cap_max);
   std::vector<KT> kept;
@@ -379,10 +405,37 @@ static bool count_solid_passes_gpu_t(Graph& g, std::vector<KT>& out, const Build
   sp.solid = solid;
   sp.out = &kept;
   sp.why = why;
+  sp.keep_on_device = in.reach != nullptr;
   G2S_HIP_TRY(sp.d_hist.alloc((size_t)PB_MAX_BINS * 8));
   G2S_HIP_TRY(sp.d_cursor.alloc(8));
   if (!sp.run_level(0, KT((uint64_t)0))) return false;
   if (in.text) free_device_text(in.text);  // (the passes were its last readers; d_text goes at the function's end)
+  if (in.reach) {  // the kept part of the device-held table is the set (graph_reach.h)
+    d_text.free();
+    GraphReachInfo rinfo;
+    uint64_t nkept = 0;
+    DevMem d_kept;
+    if (sp.table_n && !reach_on_device<KT>(sp.d_table.template as<KT>(), sp.table_n, g.k, *in.reach, d_kept, &nkept, why, &rinfo)) return false;
+    if (!sp.table_n) { rinfo.records = in.reach->records; rinfo.seeds = in.reach->seed.size(); rinfo.on_device = 1; }
+    rinfo.passes = sp.passes;
+    set_graph_reach_info(rinfo);
+    if (getenv("G2S_DEBUG"))
+      fprintf(stderr, "[g2s]   reach: %llu of %llu k-mers kept on the GPU, %u levels, the queue grown %u times\n",
+              (unsigned long long)nkept, (unsigned long long)sp.table_n, rinfo.levels, rinfo.regrowths);
+    if (nkept < graph_max_kmers() && nkept) {
+      kept.resize((size_t)nkept);
+      G2S_HIP_TRY(hipMemcpy(kept.data(), d_kept.p, (size_t)nkept * sizeof(KT), hipMemcpyDeviceToHost));
+    }
+    out.swap(kept);
+    g.n = nkept;  // (at or over the cap: graph_build refuses it, nothing came down)
+    g.bucket.clear();
+    if (info) {
+      info->passes = sp.passes;
+      info->refined_bins = sp.refined;
+      info->max_pass_keys = sp.max_pass_keys;
+    }
+    return true;
+  }
   if (getenv("G2S_DEBUG"))
     fprintf(stderr, "[g2s]   k-mer set in %u key-range passes of at most %llu keys (largest %llu, %u bins refined, %llu of %llu positions valid)\n",
             sp.passes, (unsigned long long)cap, (unsigned long long)sp.max_pass_keys, sp.refined,

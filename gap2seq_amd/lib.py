@@ -129,6 +129,18 @@ _SIGS = {
                                              C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_uint64, C.POINTER(C.c_uint8),
                                              C.c_uint32, C.c_int, C.c_int, C.c_int, C.POINTER(g2s_gap), C.POINTER(C.c_int32),
                                              C.POINTER(_VP)]),
+    "g2s_graph_build_seqs_reach": (C.c_int, [C.POINTER(C.c_char_p), C.POINTER(C.c_uint64), C.c_int, C.c_int, C.c_int, C.c_int,
+                                             C.POINTER(g2s_gap), C.POINTER(C.c_int32), C.c_uint64, C.c_int, C.POINTER(_VP)]),
+    "g2s_graph_build_files_reach": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.POINTER(g2s_gap), C.POINTER(C.c_int32),
+                                              C.c_uint64, C.c_int, C.POINTER(_VP)]),
+    "g2s_scaffolds_reach": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.POINTER(_VP)]),
+    "g2s_reach_records_count": (C.c_uint64, [_VP]),
+    "g2s_reach_records_gaps": (C.POINTER(g2s_gap), [_VP]),
+    "g2s_reach_records_radii": (C.POINTER(C.c_int32), [_VP]),
+    "g2s_reach_records_free": (None, [_VP]),
+    "g2s_graph_bounded": (C.c_int, [_VP]),
+    "g2s_test_last_graph_reach": (C.c_int, [C.POINTER(C.c_uint64)] * 5 + [C.POINTER(C.c_uint32)] * 3 + [C.POINTER(C.c_int),
+                                                                                                                  C.POINTER(C.c_double)]),
     "g2s_test_last_pool_reach": (C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.POINTER(C.c_uint64),
                                            C.POINTER(C.c_uint32), C.POINTER(C.c_int)]),
     "g2s_test_last_pool_build": (C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
@@ -633,14 +645,28 @@ class Graph:
         self.h = handle
 
     @classmethod
-    def from_seqs(cls, seqs, k, solid, nthreads=0):
+    def from_seqs(cls, seqs, k, solid, nthreads=0, reach=None, reach_mode=None):
+        """g2s_graph_build_seqs; with `reach` = [(Gap, radius), ...] g2s_graph_build_seqs_reach: the graph of the solid
+        k-mers within `radius` steps of the flank k-mers the fill looks up for some record's Gap (reach_radius(gap, d_err)
+        loses nothing of that fill).  reach_mode: REACH_ALWAYS (the default with records), REACH_NEVER, REACH_AUTO."""
         lib = load_library()
         enc = [s.encode("ascii") if isinstance(s, str) else s for s in seqs]
         arr = (C.c_char_p * len(enc))(*enc)
         lens = (C.c_uint64 * len(enc))(*[len(e) for e in enc])
         h = _VP()
+        if reach is not None:
+            gaps, radius, keep = _reach_arrays(reach)
+            _check(lib.g2s_graph_build_seqs_reach(arr, lens, len(enc), k, solid, nthreads, gaps, radius, len(reach),
+                                                  REACH_ALWAYS if reach_mode is None else reach_mode, C.byref(h)))
+            del keep
+            return cls(h)
         _check(lib.g2s_graph_build_seqs(arr, lens, len(enc), k, solid, nthreads, C.byref(h)))
         return cls(h)
+
+    @property
+    def bounded(self):
+        """True for a graph that reach records bounded (it belongs to its gap list, not to its reads)."""
+        return bool(load_library().g2s_graph_bounded(self.h))
 
     @classmethod
     def from_sets(cls, sets, k, solid, nthreads=0):
@@ -746,11 +772,18 @@ class Graph:
         return load_library().g2s_graph_set_node(self.h, s, kmer.encode("ascii"))
 
     @classmethod
-    def from_files(cls, reads_csv, k, solid, nthreads=0):
+    def from_files(cls, reads_csv, k, solid, nthreads=0, reach=None, reach_mode=None):
         """The graph of a comma-separated list of read files: FASTA or FASTQ (plain, gzip or BGZF) and BAM, in any
         mixture, each told by its bytes, never by its name.  A BAM file gives every record that is neither secondary
-        nor supplementary, mapped or not, as the read was sequenced (include/g2s.h: g2s_graph_build_files)."""
+        nor supplementary, mapped or not, as the read was sequenced (include/g2s.h: g2s_graph_build_files).
+        reach, reach_mode: as from_seqs' (g2s_graph_build_files_reach)."""
         h = _VP()
+        if reach is not None:
+            gaps, radius, keep = _reach_arrays(reach)
+            _check(load_library().g2s_graph_build_files_reach(reads_csv.encode(), k, solid, nthreads, gaps, radius, len(reach),
+                                                              REACH_ALWAYS if reach_mode is None else reach_mode, C.byref(h)))
+            del keep
+            return cls(h)
         _check(load_library().g2s_graph_build_files(reads_csv.encode(), k, solid, nthreads, C.byref(h)))
         return cls(h)
 
@@ -822,6 +855,50 @@ class Gap:
 def make_params(d_err=500, skip_confident=False, all_paths=True, unique_paths=False, max_mem=20 << 30, randseed=1,
                 host_threads=0):
     return g2s_params(d_err, int(skip_confident), int(all_paths), int(unique_paths), max_mem, randseed, host_threads)
+
+
+REACH_NEVER, REACH_ALWAYS, REACH_AUTO = 0, 1, 2  # g2s_graph_build_seqs_reach's mode
+
+
+def _reach_arrays(reach):
+    """[(Gap, radius), ...] as the two arrays of the reach calls (+ what keeps their strings alive)"""
+    gaps, keep = _gap_array([r[0] for r in reach])
+    radius = (C.c_int32 * max(1, len(reach)))(*[int(r[1]) for r in reach])
+    return gaps, radius, keep
+
+
+def scaffolds_reach(text, k, fuz, d_err):
+    """g2s_scaffolds_reach: [(Gap, radius)], one record per N-run of every scaffold record of `text`, for
+    execute_scaffolds with max_fuz = fuz on a session with d_err — what Graph.from_seqs / from_files take as `reach`.
+    A record without usable flanks has a Gap the fill rejects (no seeds)."""
+    lib = load_library()
+    h = _VP()
+    _check(lib.g2s_scaffolds_reach(text.encode("ascii"), k, fuz, d_err, C.byref(h)))
+    try:
+        n = lib.g2s_reach_records_count(h)
+        gaps, radii = lib.g2s_reach_records_gaps(h), lib.g2s_reach_records_radii(h)
+        out = []
+        for i in range(n):
+            g = gaps[i]
+            left, right = (g.left or b"").decode("ascii"), (g.right or b"").decode("ascii")
+            out.append((Gap(left, right, g.gap_len, g.lmf, g.rmf), radii[i]))
+        return out
+    finally:
+        lib.g2s_reach_records_free(h)
+
+
+def test_last_graph_reach():
+    """g2s_test_last_graph_reach: dict(records, seeds, seeds_in_full, full_kmers, kept_kmers, levels, passes, regrowths,
+    on_device, ms_search) of the last bounded single-graph build"""
+    u = [C.c_uint64() for _ in range(5)]
+    w = [C.c_uint32() for _ in range(3)]
+    on, ms = C.c_int(), C.c_double()
+    _check(load_library().g2s_test_last_graph_reach(*[C.byref(x) for x in u + w], C.byref(on), C.byref(ms)))
+    names = ("records", "seeds", "seeds_in_full", "full_kmers", "kept_kmers", "levels", "passes", "regrowths")
+    out = {name: x.value for name, x in zip(names, u + w)}
+    out["on_device"] = on.value
+    out["ms_search"] = ms.value
+    return out
 
 
 def _gap_array(gaps):

@@ -76,7 +76,8 @@ const char* g2s_last_error(void);
  *  reads are kept there as text and the solid k-mers are counted in key-range
  *  passes.  The host counts them only when the text does not fit beside one
  *  pass or one k-mer alone occurs more often than a pass holds keys
- *  (G2S_DEBUG=1 says which).  The graph itself holds fewer than 2^30 k-mers.
+ *  (G2S_DEBUG=1 says which).  The graph itself holds fewer than 2^30 k-mers
+ *  (g2s_graph_build_seqs_reach / _files_reach below: a graph bounded to a gap list's reach, the cap on what is kept).
  *  g2s_graph_build_files: reads_csv is a comma-separated list of FASTA/FASTQ
  *  files; gzip-compressed ones (plain gzip or BGZF, recognised by their magic
  *  bytes, not their names) are read transparently.  BAM files may stand in
@@ -173,6 +174,57 @@ int g2s_graph_build_pool_reach(const char* const* seqs, const uint64_t* lens, ui
                                const struct g2s_gap* reach_gap,  /* [nsets], or NULL */
                                const int32_t* reach_radius,      /* [nsets], or NULL */
                                g2s_graph** out);
+/* ---------------------------------------------------------------------------
+ *  A SINGLE graph bounded to what a gap list can reach (ABI 6, additive): g2s_graph_build_seqs / _files plus reach
+ *  records, for read sets whose solid k-mers number 2^30 and more — the cap of 32-bit oriented node ids then applies to
+ *  what the gaps can touch, not to the read set.  reach_gap[r] with reach_radius[r] >= 0, r < nreach, is a record:
+ *    full set    the solid canonical k-mers the plain call would find;
+ *    seeds of r  the seeds g2s_graph_build_pool_reach defines for reach_gap[r] (none for a gap the fill rejects); a seed
+ *                outside the full set is ignored;
+ *    kept set    every k-mer of the full set at an undirected distance <= reach_radius[r] of a seed of SOME record r, the
+ *                distance counted over canonical k-mers with their eight neighbours, as for the pool form;
+ *    the graph   what the plain call gives for the kept set: the induced subgraph, one set, ordinary numbering; EMPTY
+ *                with nreach == 0 or no seed in the full set.
+ *  At the SOUND RADIUS (above) of every gap of a list the fills on the bounded graph equal those on the whole one.
+ *  mode: G2S_REACH_ALWAYS the bounded graph; G2S_REACH_NEVER the plain call; G2S_REACH_AUTO the plain call, bit for bit —
+ *  and only when that fails with "too many k-mers for 32-bit oriented node ids" the build starts over bounded, so only
+ *  inputs that fail today pay for it (G2S_BUILD_REACH=1|0 in the environment turns AUTO into ALWAYS | NEVER).
+ *  Both arrays NULL: the plain call whatever the mode.  The cap (2^30 k-mers; G2S_BUILD_MAX_KMERS=N lowers it, for
+ *  tests) applies to the KEPT set.  On the device the full set stays in device memory as one sorted table of any size
+ *  that fits beside the text and one pass — the one sort's result, or the key-range passes' results one behind the other —
+ *  and one level-synchronous search over the whole chip serves all records (csrc/graph_reach.h); an allocation that
+ *  fails or a HIP error hands the build to the host path (G2S_DEBUG=1 says why), where the bound is host memory and the
+ *  same search runs on `nthreads` threads.  Either way the same graph, node for node.
+ *  G2S_ERR_ARG: a negative radius, exactly one of the arrays NULL with nreach > 0, an unknown mode, and the plain call's;
+ *  *out is not written then. */
+#define G2S_REACH_NEVER 0
+#define G2S_REACH_ALWAYS 1
+#define G2S_REACH_AUTO 2
+int g2s_graph_build_seqs_reach(const char* const* seqs, const uint64_t* lens, int nseqs, int k, int solid, int nthreads,
+                               const struct g2s_gap* reach_gap, const int32_t* reach_radius, uint64_t nreach, int mode,
+                               g2s_graph** out);
+int g2s_graph_build_files_reach(const char* reads_csv, int k, int solid, int nthreads, const struct g2s_gap* reach_gap,
+                                const int32_t* reach_radius, uint64_t nreach, int mode, g2s_graph** out);
+/* The reach records of a scaffolds file for g2s_execute_scaffolds with max_fuz and g2s_params.d_err = d_err: one record
+ * per N-run [istart, iend) of every scaffold record, in input order.
+ *   left flank   seq[a, istart) with a = max(the previous run's end, istart - k - max_fuz, 0), lmf = its length - k (a
+ *                window shorter than k gives a record without seeds: the scanner cannot fill that gap either);
+ *   right flank  seq[iend, iend + k + rmf), rmf as the scanner takes it; where the scanner finds no usable right flank
+ *                the record has no seeds;
+ *   radius       max(0, gap + d_err) + lmf + rmf.
+ * Whatever the previous gap's right_fuz was, the left flank the scanner hands the fill lies inside that window and its
+ * left_max_fuz is at most lmf, so every record holds a superset of the fill's seeds at a radius at least the fill's own.
+ * The handle owns the flank strings; the arrays hold g2s_reach_records_count() entries and live until
+ * g2s_reach_records_free. */
+typedef struct g2s_reach_records g2s_reach_records;
+int g2s_scaffolds_reach(const char* scaffolds_text, int k, int max_fuz, int d_err, g2s_reach_records** out);
+uint64_t g2s_reach_records_count(const g2s_reach_records* r);
+const struct g2s_gap* g2s_reach_records_gaps(const g2s_reach_records* r);
+const int32_t* g2s_reach_records_radii(const g2s_reach_records* r);
+void g2s_reach_records_free(g2s_reach_records* r);
+/* 1 for a graph that reach records bounded (g2s_graph_build_seqs_reach / _files_reach on the bounded path): it belongs to
+ * its gap list, and a caller that caches graphs by their reads (Gap2Seq-core's "<reads>.g2s") must not cache it. */
+int g2s_graph_bounded(const g2s_graph* g);
 uint32_t g2s_graph_num_sets(const g2s_graph* g); /* 1 for every graph built the other ways */
 int g2s_graph_set_nodes(const g2s_graph* g, uint32_t set, uint64_t* first_kmer, uint64_t* n_kmers);
 uint32_t g2s_graph_set_node(const g2s_graph* g, uint32_t set, const char* kmer); /* G2S_INVALID_NODE if absent */

@@ -193,6 +193,16 @@ int g2s_test_last_reads_bam_stream(uint64_t* streamed_files, uint64_t* windows, 
 int g2s_test_plan_passes(const uint64_t* hist, uint32_t nbins, uint64_t cap, uint32_t* first_bin_of_pass,
                          uint32_t max_passes, uint32_t* npasses, uint32_t* first_oversized_bin);
 
+/* TEST HOOK: what the process's last bounded single-graph build (g2s_graph_build_seqs_reach / _files_reach taking the
+ * bounded path) did: the records, their seeds, the seeds that are solid k-mers (counted with their copies), the k-mers
+ * of the full and of the kept set, the key-range passes that made the device-held table (0: one sort, or the host), how
+ * often the search started over with a larger queue, whether it ran on the device, and the wall time of the level loop.
+ * levels differs by path: on the host the last level with a frontier; on the device the level at which the loop
+ * stopped — the largest radius, or, when the search died out earlier, the level of the control read that saw it, up to
+ * 7 behind the host's figure.  Compare it between the paths only where the search runs to the largest radius. */
+int g2s_test_last_graph_reach(uint64_t* records, uint64_t* seeds, uint64_t* seeds_in_full, uint64_t* full_kmers,
+                              uint64_t* kept_kmers, uint32_t* levels, uint32_t* passes, uint32_t* regrowths, int* on_device,
+                              double* ms_search);
 /* TEST HOOK: what the process's last g2s_graph_build_pool_reach with at least one reach record did.  reach_sets: the
  * sets with a record; full_kmers: the k-mers of those sets' full graphs, valid when *full_known != 0 (the host build
  * counts them when it was the first choice — no device, G2S_HOST_BUILD=1; the device build never forms the
