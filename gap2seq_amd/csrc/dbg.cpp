@@ -13,28 +13,23 @@
 
 namespace g2s {
 
+// numbers what the device's list ranking leaves unnumbered (circular unitigs): rank-space successors, the first free id
+using HostWalk = std::function<void(const std::vector<uint32_t>&, uint32_t)>;
 // dbg_gpu.hip
 bool count_solid_gpu(Graph& g, const BuildInput& in, int solid, int device, std::string* why, SolidCountInfo* info);
-bool graph_finish_gpu(Graph& g, int device, const std::function<void(const std::vector<uint32_t>&, uint32_t)>& host_walk,
-                      std::string* why);
+bool graph_finish_gpu(Graph& g, int device, const HostWalk& host_walk, std::string* why);
 bool graph_build_sets_gpu(Graph& g, const std::vector<std::pair<const char*, uint64_t>>& seqs, const std::vector<uint32_t>& seq_set,
-                          uint32_t nsets, int solid, int device,
-                          const std::function<void(const std::vector<uint32_t>&, uint32_t)>& host_walk, std::string* why);
-bool graph_build_pool_gpu(Graph& g, const PoolSets& ps, int solid, int device,
-                          const std::function<void(const std::vector<uint32_t>&, uint32_t)>& host_walk, PoolBuildInfo* info,
+                          uint32_t nsets, int solid, int device, const HostWalk& host_walk, std::string* why);
+bool graph_build_pool_gpu(Graph& g, const PoolSets& ps, int solid, int device, const HostWalk& host_walk, PoolBuildInfo* info,
                           std::string* why, const PoolReach* reach = nullptr, PoolReachInfo* rinfo = nullptr,
                           bool* device_usable = nullptr);
 
 namespace {
 
-template <class KT> std::vector<KT>& kmer_vec(Graph& g);
-template <> std::vector<uint64_t>& kmer_vec<uint64_t>(Graph& g) { return g.kmers64; }
-template <> std::vector<u128>& kmer_vec<u128>(Graph& g) { return g.kmers128; }
-template <> std::vector<u256>& kmer_vec<u256>(Graph& g) { return g.kmers256; }
-template <class KT> const std::vector<KT>& kmer_vec(const Graph& g);
-template <> const std::vector<uint64_t>& kmer_vec<uint64_t>(const Graph& g) { return g.kmers64; }
-template <> const std::vector<u128>& kmer_vec<u128>(const Graph& g) { return g.kmers128; }
-template <> const std::vector<u256>& kmer_vec<u256>(const Graph& g) { return g.kmers256; }
+LastInfo<SolidCountInfo> g_solid_info;
+LastInfo<GraphReachInfo> g_graph_reach_info;
+LastInfo<PoolBuildInfo> g_pool_info;
+LastInfo<PoolReachInfo> g_reach_info;
 
 template <class F>
 void parallel_for(uint64_t n, int nthreads, F f) {
@@ -281,6 +276,39 @@ void build_ustart(Graph& g) {
   for (uint64_t i = n; i < (uint64_t)g.ustart.size() * 64; i++) g.ustart[(size_t)(i >> 6)] |= 1ull << (i & 63);
 }
 
+// ---- the device-first route every builder takes: the device build (dbg_gpu.hip), the host build behind it ----------
+Graph* new_graph(int k, int solid) {
+  Graph* g = new Graph();
+  g->k = k;
+  g->solid = solid;
+  g->kmer_bytes = kmer_width(k);
+  return g;
+}
+
+// G2S_HOST_BUILD (set to anything): no builder tries the device.  Read on every call: it changes within a process.
+bool host_build_asked() { return getenv("G2S_HOST_BUILD") != nullptr; }
+
+// what the device builds hand the circular unitigs to: unitig_order resuming on g's own numbering
+HostWalk host_walk_of(Graph& g) {
+  return [&g](const std::vector<uint32_t>& succ_r, uint32_t first_id) {
+    unitig_order(succ_r, g.n, (g.k % 2) == 0, &g.rank2id, &g.flip, &g.n_unitigs, true, first_id);
+  };
+}
+
+// A set builder's device attempt: attempt(g, device, host_walk, &why) on a new graph.  The graph when that succeeds (the
+// success line is the caller's: it differs between builders); nullptr for the host build to follow — at once under
+// G2S_HOST_BUILD, else after the line "<what> on the host (<why>)".
+template <class Attempt>
+Graph* build_on_device(int k, int solid, const char* what, Attempt&& attempt) {
+  if (host_build_asked()) return nullptr;
+  Graph* g = new_graph(k, solid);
+  std::string why;
+  if (attempt(*g, build_device(), host_walk_of(*g), &why)) return g;
+  if (getenv("G2S_DEBUG")) fprintf(stderr, "[g2s]   %s on the host (%s)\n", what, why.c_str());
+  delete g;
+  return nullptr;
+}
+
 template <class KT>
 void finish_graph_host(Graph& g, int nthreads);
 
@@ -292,12 +320,9 @@ void finish_graph(Graph& g, int nthreads) {
   // along unitigs by list ranking, tables in id space and the unitig-start bitmap all on the device
   // (dbg_gpu.hip); the host only numbers circular unitigs.  Otherwise the host build below, which
   // is the authority on palindromic k-mers (even k) the device build is tested against.
-  if (!getenv("G2S_HOST_BUILD")) {
+  if (!host_build_asked()) {
     std::string why;
-    const int dev = getenv("G2S_DEVICE") ? atoi(getenv("G2S_DEVICE")) : 0;
-    const bool ok = graph_finish_gpu(g, dev, [&](const std::vector<uint32_t>& succ_r, uint32_t first_id) {
-      unitig_order(succ_r, g.n, (g.k % 2) == 0, &g.rank2id, &g.flip, &g.n_unitigs, true, first_id);
-    }, &why);
+    const bool ok = graph_finish_gpu(g, build_device(), host_walk_of(g), &why);
     if (getenv("G2S_DEBUG"))
       fprintf(stderr, "[g2s]   tables, unitig order, id space: %.3f s on the %s%s%s\n",
               std::chrono::duration<double>(std::chrono::steady_clock::now() - f0).count(), ok ? "GPU" : "host next (",
@@ -352,27 +377,24 @@ void finish_graph_host(Graph& g, int nthreads) {
   build_ustart(g);
 }
 
+// the oriented node of the k characters at s, or kInvalidNode: rank(c) is the sorted rank of their canonical k-mer, or -1
+template <class Rank>
+uint32_t node_at(const Graph& g, const char* s, Rank&& rank) {
+  int strand = 0;
+  const int64_t r = with_kmer_type(g.kmer_bytes, [&](auto t) -> int64_t {
+    typename decltype(t)::type c;
+    encode_kmer(s, g.k, &c, &strand);
+    return rank(c);
+  });
+  if (r < 0) return kInvalidNode;
+  return 2 * g.rank2id[(size_t)r] + ((uint32_t)strand ^ (uint32_t)g.flip[(size_t)r]);
+}
+
 }  // namespace
 
 uint32_t Graph::node_of(const char* s) const {
   if (n == 0 || num_sets() > 1) return kInvalidNode;
-  int strand = 0;
-  int64_t r;
-  if (kmer_bytes == 8) {
-    uint64_t c;
-    encode_kmer<uint64_t>(s, k, &c, &strand);
-    r = rank_of<uint64_t>(*this, c);
-  } else if (kmer_bytes == 16) {
-    u128 c;
-    encode_kmer<u128>(s, k, &c, &strand);
-    r = rank_of<u128>(*this, c);
-  } else {
-    u256 c;
-    encode_kmer<u256>(s, k, &c, &strand);
-    r = rank_of<u256>(*this, c);
-  }
-  if (r < 0) return kInvalidNode;
-  return 2 * rank2id[(size_t)r] + ((uint32_t)strand ^ (uint32_t)flip[(size_t)r]);
+  return node_at(*this, s, [&](auto c) { return rank_of(*this, c); });
 }
 
 uint32_t Graph::node_of_in(uint32_t set, const char* s) const {
@@ -380,42 +402,19 @@ uint32_t Graph::node_of_in(uint32_t set, const char* s) const {
   if (set_lo.empty()) return node_of(s);
   const uint64_t lo = set_lo[set], hi = set_lo[(size_t)set + 1];
   if (lo == hi) return kInvalidNode;
-  int strand = 0;
-  int64_t r;
-  if (kmer_bytes == 8) {
-    uint64_t c;
-    encode_kmer<uint64_t>(s, k, &c, &strand);
-    r = rank_in<uint64_t>(*this, lo, hi, c);
-  } else if (kmer_bytes == 16) {
-    u128 c;
-    encode_kmer<u128>(s, k, &c, &strand);
-    r = rank_in<u128>(*this, lo, hi, c);
-  } else {
-    u256 c;
-    encode_kmer<u256>(s, k, &c, &strand);
-    r = rank_in<u256>(*this, lo, hi, c);
-  }
-  if (r < 0) return kInvalidNode;
-  return 2 * rank2id[(size_t)r] + ((uint32_t)strand ^ (uint32_t)flip[(size_t)r]);
+  return node_at(*this, s, [&](auto c) { return rank_in(*this, lo, hi, c); });
 }
 
 std::string Graph::node_string(uint32_t v) const {
   const uint32_t r = id2rank[v >> 1];
   const int strand = (int)((v & 1u) ^ (uint32_t)flip[r]);
-  if (kmer_bytes == 8) return decode_kmer<uint64_t>(kmers64[r], strand, k);
-  if (kmer_bytes == 16) return decode_kmer<u128>(kmers128[r], strand, k);
-  return decode_kmer<u256>(kmers256[r], strand, k);
+  return with_kmer_type(kmer_bytes, [&](auto t) {
+    using KT = typename decltype(t)::type;
+    return decode_kmer<KT>(kmer_vec<KT>(*this)[r], strand, k);
+  });
 }
 
-namespace {
-std::mutex g_solid_info_mu;
-SolidCountInfo g_solid_info;
-}  // namespace
-
-SolidCountInfo last_solid_count() {
-  std::lock_guard<std::mutex> lk(g_solid_info_mu);
-  return g_solid_info;
-}
+SolidCountInfo last_solid_count() { return g_solid_info.get(); }
 
 uint64_t graph_max_kmers() {
   const uint64_t cap = 1ull << 30;
@@ -425,8 +424,6 @@ uint64_t graph_max_kmers() {
 }
 
 namespace {
-std::mutex g_graph_reach_mu;
-GraphReachInfo g_graph_reach_info;
 
 // The bounded set of a single graph on host threads (dbg.hpp: GraphReach; the device form is graph_reach.h): `keep`
 // holds the sorted solid k-mers and leaves with those of them within reach of a seed.  One search for all records: level
@@ -502,15 +499,9 @@ void reach_filter_host(std::vector<KT>& keep, const GraphReach& reach, int k, in
 Graph* graph_build_from(const BuildInput& in, int k, int solid, int nthreads, std::string* err, bool* gave_up);
 }  // namespace
 
-GraphReachInfo last_graph_reach() {
-  std::lock_guard<std::mutex> lk(g_graph_reach_mu);
-  return g_graph_reach_info;
-}
+GraphReachInfo last_graph_reach() { return g_graph_reach_info.get(); }
 // dbg_gpu.hip: what the device form of the bounded build did
-void set_graph_reach_info(const GraphReachInfo& info) {
-  std::lock_guard<std::mutex> lk(g_graph_reach_mu);
-  g_graph_reach_info = info;
-}
+void set_graph_reach_info(const GraphReachInfo& info) { g_graph_reach_info.set(info); }
 
 Graph* graph_build(const std::vector<std::pair<const char*, uint64_t>>& seqs, int k, int solid, int nthreads,
                    std::string* err, const GraphReach* reach) {
@@ -532,10 +523,7 @@ namespace {
 Graph* graph_build_from(const BuildInput& in, int k, int solid, int nthreads, std::string* err, bool* gave_up) {
   if (k < 1 || k > kMaxK) { if (err) *err = "k must be in [1," + std::to_string(kMaxK) + "]"; return nullptr; }
   if (nthreads <= 0) nthreads = (int)std::max(1u, std::thread::hardware_concurrency());
-  Graph* g = new Graph();
-  g->k = k;
-  g->solid = solid;
-  g->kmer_bytes = kmer_width(k);
+  Graph* g = new_graph(k, solid);
   g->bounded = in.reach != nullptr;
   const auto t0 = std::chrono::steady_clock::now();
   // the solid k-mer set: sort on the GPU when there is one (dbg_gpu.hip), host threads otherwise
@@ -544,8 +532,8 @@ Graph* graph_build_from(const BuildInput& in, int k, int solid, int nthreads, st
   if (in.text) info.positions = in.text->T;
   else for (auto& sq : *in.seqs) info.positions += sq.second + 1;
   std::string why = "G2S_HOST_BUILD";
-  if (!getenv("G2S_HOST_BUILD")) {
-    set_on_gpu = count_solid_gpu(*g, in, solid, getenv("G2S_DEVICE") ? atoi(getenv("G2S_DEVICE")) : 0, &why, &info);
+  if (!host_build_asked()) {
+    set_on_gpu = count_solid_gpu(*g, in, solid, build_device(), &why, &info);
     if (!set_on_gpu && getenv("G2S_DEBUG")) fprintf(stderr, "[g2s]   k-mer set on the host (%s)\n", why.c_str());
   }
   if (!set_on_gpu && in.text) {  // (the host count reads sequences: the caller loads them on the host and comes back)
@@ -554,38 +542,29 @@ Graph* graph_build_from(const BuildInput& in, int k, int solid, int nthreads, st
     delete g;
     return nullptr;
   }
-  if (!set_on_gpu) {
-    const auto& seqs = *in.seqs;
-    if (g->kmer_bytes == 8) count_solid<uint64_t>(*g, seqs, solid, nthreads);
-    else if (g->kmer_bytes == 16) count_solid<u128>(*g, seqs, solid, nthreads);
-    else count_solid<u256>(*g, seqs, solid, nthreads);
+  if (!set_on_gpu) with_kmer_type(g->kmer_bytes, [&](auto t) {
+    using KT = typename decltype(t)::type;
+    count_solid<KT>(*g, *in.seqs, solid, nthreads);
     if (in.reach) {  // the same search as the device's, over the sorted vector
       GraphReachInfo ri;
       ri.records = in.reach->records;
       ri.seeds = in.reach->seed.size();
-      if (g->kmer_bytes == 8) reach_filter_host<uint64_t>(g->kmers64, *in.reach, k, nthreads, &ri);
-      else if (g->kmer_bytes == 16) reach_filter_host<u128>(g->kmers128, *in.reach, k, nthreads, &ri);
-      else reach_filter_host<u256>(g->kmers256, *in.reach, k, nthreads, &ri);
+      reach_filter_host<KT>(kmer_vec<KT>(*g), *in.reach, k, nthreads, &ri);
       g->n = ri.kept_kmers;
       if (getenv("G2S_DEBUG"))
         fprintf(stderr, "[g2s]   reach: %llu of %llu k-mers kept on the host, %u levels\n", (unsigned long long)ri.kept_kmers,
                 (unsigned long long)ri.full_kmers, ri.levels);
       set_graph_reach_info(ri);
     }
-  }
+  });
   const auto t1 = std::chrono::steady_clock::now();
   if (!set_on_gpu) info.passes = info.refined_bins = 0, info.max_pass_keys = 0;
   info.on_device = set_on_gpu ? 1 : 0;
   info.solid = g->n;
-  {
-    std::lock_guard<std::mutex> lk(g_solid_info_mu);
-    g_solid_info = info;
-  }
+  g_solid_info.set(info);
   const std::string how = !set_on_gpu ? "host" : info.passes ? "GPU, " + std::to_string(info.passes) + " key-range passes" : "GPU sort";
   if (g->n >= graph_max_kmers()) { if (err) *err = kTooManyKmers; delete g; return nullptr; }
-  if (g->kmer_bytes == 8) finish_graph<uint64_t>(*g, nthreads);
-  else if (g->kmer_bytes == 16) finish_graph<u128>(*g, nthreads);
-  else finish_graph<u256>(*g, nthreads);
+  with_kmer_type(g->kmer_bytes, [&](auto t) { finish_graph<typename decltype(t)::type>(*g, nthreads); });
   if (getenv("G2S_DEBUG"))
     fprintf(stderr, "[g2s] graph build: %llu k-mers; solid k-mer set %.3f s (%s), tables + unitig order %.3f s (%d threads)\n",
             (unsigned long long)g->n, std::chrono::duration<double>(t1 - t0).count(), how.c_str(),
@@ -599,10 +578,7 @@ namespace {
 // One set's graph on one host thread (a small prefix index: sets are small), appended to the union at ranks and node
 // indices [off, off + n_s).
 template <class KT>
-void build_set_part(const std::vector<std::pair<const char*, uint64_t>>& seqs, int k, int solid, Graph* part) {
-  part->k = k;
-  part->solid = solid;
-  part->kmer_bytes = kmer_width(k);
+void build_set_part(const std::vector<std::pair<const char*, uint64_t>>& seqs, int solid, Graph* part) {
   count_solid<KT>(*part, seqs, solid, 1);
   int bits = 1;
   while (bits < 22 && (1ull << bits) < part->n) bits++;
@@ -644,24 +620,13 @@ Graph* graph_build_sets(const std::vector<std::pair<const char*, uint64_t>>& seq
   const auto t0 = std::chrono::steady_clock::now();
   // on the GPU when there is one (dbg_gpu.hip: keyed k-mer sort, successors searched inside their set); no device,
   // G2S_HOST_BUILD=1, an empty union: the host build below, set by set
-  if (!getenv("G2S_HOST_BUILD")) {
-    Graph* g = new Graph();
-    g->k = k;
-    g->solid = solid;
-    g->kmer_bytes = kmer_width(k);
-    std::string why;
-    const bool ok = graph_build_sets_gpu(*g, seqs, seq_set, nsets, solid, getenv("G2S_DEVICE") ? atoi(getenv("G2S_DEVICE")) : 0,
-                                         [&](const std::vector<uint32_t>& succ_r, uint32_t first_id) {
-                                           unitig_order(succ_r, g->n, (g->k % 2) == 0, &g->rank2id, &g->flip, &g->n_unitigs, true, first_id);
-                                         }, &why);
-    if (ok) {
-      if (getenv("G2S_DEBUG"))
-        fprintf(stderr, "[g2s] set graph build: %u sets, %llu k-mers, %.3f s on the GPU\n", nsets, (unsigned long long)g->n,
-                std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
-      return g;
-    }
-    if (getenv("G2S_DEBUG")) fprintf(stderr, "[g2s]   set graph on the host (%s)\n", why.c_str());
-    delete g;
+  if (Graph* g = build_on_device(k, solid, "set graph", [&](Graph& dg, int device, const HostWalk& walk, std::string* why) {
+        return graph_build_sets_gpu(dg, seqs, seq_set, nsets, solid, device, walk, why);
+      })) {
+    if (getenv("G2S_DEBUG"))
+      fprintf(stderr, "[g2s] set graph build: %u sets, %llu k-mers, %.3f s on the GPU\n", nsets, (unsigned long long)g->n,
+              std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+    return g;
   }
   std::vector<std::vector<std::pair<const char*, uint64_t>>> by_set(nsets);
   for (size_t j = 0; j < seqs.size(); j++) by_set[seq_set[j]].push_back(seqs[j]);
@@ -684,12 +649,10 @@ Graph* build_sets_host(const SetSeqsFn& set_seqs, uint32_t nsets, int k, int sol
       while (true) {
         const uint32_t s = next.fetch_add(1);
         if (s >= nsets) break;
-        Graph* p = new Graph();
+        Graph* p = new_graph(k, solid);
         const std::vector<std::pair<const char*, uint64_t>>& mine = *set_seqs(s, &tmp);
-        if (own_part && (*own_part)(s, mine, p)) {}
-        else if (kb == 8) build_set_part<uint64_t>(mine, k, solid, p);
-        else if (kb == 16) build_set_part<u128>(mine, k, solid, p);
-        else build_set_part<u256>(mine, k, solid, p);
+        if (!(own_part && (*own_part)(s, mine, p)))
+          with_kmer_type(kb, [&](auto t) { build_set_part<typename decltype(t)::type>(mine, solid, p); });
         parts[s] = p;
       }
     };
@@ -698,25 +661,20 @@ Graph* build_sets_host(const SetSeqsFn& set_seqs, uint32_t nsets, int k, int sol
     work();
     for (auto& x : th) x.join();
   }
-  Graph* g = new Graph();
-  g->k = k;
-  g->solid = solid;
-  g->kmer_bytes = kb;
+  Graph* g = new_graph(k, solid);
   g->set_lo.assign((size_t)nsets + 1, 0);
   for (uint32_t s = 0; s < nsets; s++) {
     g->set_lo[(size_t)s + 1] = g->set_lo[s] + parts[s]->n;
     g->n_unitigs += parts[s]->n_unitigs;
   }
   g->n = g->set_lo[nsets];
-  if (g->n >= (1ull << 30)) {
-    if (err) *err = "too many k-mers for 32-bit oriented node ids";
+  if (g->n >= (1ull << 30)) {  // (not graph_max_kmers(): G2S_BUILD_MAX_KMERS bounds single graphs, not set graphs)
+    if (err) *err = kTooManyKmers;
     for (Graph* p : parts) delete p;
     delete g;
     return nullptr;
   }
-  if (kb == 8) g->kmers64.resize((size_t)g->n);
-  else if (kb == 16) g->kmers128.resize((size_t)g->n);
-  else g->kmers256.resize((size_t)g->n);
+  with_kmer_type(kb, [&](auto t) { kmer_vec<typename decltype(t)::type>(*g).resize((size_t)g->n); });
   g->rank2id.assign((size_t)g->n, 0);
   g->id2rank.assign((size_t)g->n, 0);
   g->flip.assign((size_t)g->n, 0);
@@ -725,9 +683,7 @@ Graph* build_sets_host(const SetSeqsFn& set_seqs, uint32_t nsets, int k, int sol
   g->lastnt.assign((size_t)g->n * 2, 0);
   parallel_for(nsets, std::min(nthreads, 16), [&](uint64_t b, uint64_t e, int) {
     for (uint64_t s = b; s < e; s++) {
-      if (kb == 8) append_set_part<uint64_t>(*g, *parts[s], g->set_lo[s]);
-      else if (kb == 16) append_set_part<u128>(*g, *parts[s], g->set_lo[s]);
-      else append_set_part<u256>(*g, *parts[s], g->set_lo[s]);
+      with_kmer_type(kb, [&](auto t) { append_set_part<typename decltype(t)::type>(*g, *parts[s], g->set_lo[s]); });
       delete parts[s];
       parts[s] = nullptr;
     }
@@ -739,15 +695,9 @@ Graph* build_sets_host(const SetSeqsFn& set_seqs, uint32_t nsets, int k, int sol
   return g;
 }
 
-std::mutex g_pool_info_mu;
-PoolBuildInfo g_pool_info;
-
 }  // namespace
 
-PoolBuildInfo last_pool_build() {
-  std::lock_guard<std::mutex> lk(g_pool_info_mu);
-  return g_pool_info;
-}
+PoolBuildInfo last_pool_build() { return g_pool_info.get(); }
 
 static bool check_pool_sets(const PoolSets& ps, int k, std::string* err) {
   if (k < 1 || k > kMaxK) { if (err) *err = "k must be in [1," + std::to_string(kMaxK) + "]"; return false; }
@@ -774,26 +724,41 @@ static uint64_t pool_text_in_use(const PoolSets& ps) {
   return n;
 }
 
+// set s's list into *out, its own sequences and behind them the shared list's when `with_shared`: pointers only, no text moves
+static std::vector<std::pair<const char*, uint64_t>>* expand_set(const PoolSets& ps, uint32_t s, bool with_shared,
+                                                                 std::vector<std::pair<const char*, uint64_t>>* out) {
+  const std::vector<std::pair<const char*, uint64_t>>& seqs = *ps.seqs;
+  out->clear();
+  for (uint64_t q = ps.set_begin[s]; q < ps.set_begin[s + 1]; q++) out->push_back(seqs[ps.set_seq[q]]);
+  if (with_shared)
+    for (uint64_t x = 0; x < ps.nshared; x++) out->push_back(seqs[ps.shared_seq[x]]);
+  return out;
+}
+
+// What the host route of a pooled build does, of its flagged sets `whole` built from their expanded lists and `bounded`
+// from reach records: those read the shared list through one table, sorted once for all of them.
+static PoolBuildInfo pool_info_host(const PoolSets& ps, uint64_t whole, uint64_t bounded) {
+  const std::vector<std::pair<const char*, uint64_t>>& seqs = *ps.seqs;
+  PoolBuildInfo info;
+  info.text_packed = pool_text_in_use(ps);
+  for (uint64_t q = ps.set_begin[0]; q < ps.set_begin[ps.nsets]; q++) info.own_positions += seqs[ps.set_seq[q]].second + 1;
+  if (whole + bounded)
+    for (uint64_t x = 0; x < ps.nshared; x++) info.shared_positions += seqs[ps.shared_seq[x]].second + 1;
+  info.keys_sorted = info.own_positions + (whole + (bounded ? 1 : 0)) * info.shared_positions;
+  return info;
+}
+
 Graph* graph_build_pool(const PoolSets& ps, int k, int solid, int nthreads, std::string* err) {
   if (!check_pool_sets(ps, k, err)) return nullptr;
-  const std::vector<std::pair<const char*, uint64_t>>& seqs = *ps.seqs;
-  // a set's expanded list: pointers only, no text moves
-  auto expand = [&](uint32_t s, std::vector<std::pair<const char*, uint64_t>>* out) {
-    out->clear();
-    for (uint64_t q = ps.set_begin[s]; q < ps.set_begin[s + 1]; q++) out->push_back(seqs[ps.set_seq[q]]);
-    if (ps.flagged(s))
-      for (uint64_t x = 0; x < ps.nshared; x++) out->push_back(seqs[ps.shared_seq[x]]);
-    return out;
-  };
   if (ps.nsets == 1) {  // an ordinary graph, as graph_build_sets' callers get for one set
     std::vector<std::pair<const char*, uint64_t>> all;
     if (ps.host_text && !ps.host_text(err)) return nullptr;  // (graph_build takes host pointers)
-    Graph* g1 = graph_build(*expand(0, &all), k, solid, nthreads, err);
-    if (g1) {
-      std::lock_guard<std::mutex> lk(g_pool_info_mu);  // (no pooled build ran: the text counters alone change)
-      g_pool_info.text_gathered = 0;
-      g_pool_info.text_packed = pool_text_in_use(ps);
-    }
+    Graph* g1 = graph_build(*expand_set(ps, 0, ps.flagged(0), &all), k, solid, nthreads, err);
+    if (g1)  // (no pooled build ran: the text counters alone change)
+      g_pool_info.update([&](PoolBuildInfo& last) {
+        last.text_gathered = 0;
+        last.text_packed = pool_text_in_use(ps);
+      });
     return g1;
   }
   if (nthreads <= 0) nthreads = (int)std::max(1u, std::thread::hardware_concurrency());
@@ -802,52 +767,29 @@ Graph* graph_build_pool(const PoolSets& ps, int k, int solid, int nthreads, std:
   // on the GPU when there is one (dbg_gpu.hip: the pool's k-mers extracted once, the own lists' (set, k-mer) pairs and
   // the shared list's k-mers gathered from them, the shared list sorted once and merged into every flagged set); no
   // device, G2S_HOST_BUILD=1, an empty union: the host build, set by set over each set's pointers
-  if (!getenv("G2S_HOST_BUILD")) {
-    Graph* g = new Graph();
-    g->k = k;
-    g->solid = solid;
-    g->kmer_bytes = kmer_width(k);
-    std::string why;
-    const bool ok = graph_build_pool_gpu(*g, ps, solid, getenv("G2S_DEVICE") ? atoi(getenv("G2S_DEVICE")) : 0,
-                                         [&](const std::vector<uint32_t>& succ_r, uint32_t first_id) {
-                                           unitig_order(succ_r, g->n, (g->k % 2) == 0, &g->rank2id, &g->flip, &g->n_unitigs, true, first_id);
-                                         }, &info, &why);
-    if (ok) {
-      if (getenv("G2S_DEBUG"))
-        fprintf(stderr, "[g2s] pooled set graph build: %u sets, %llu k-mers, %llu own + %llu shared positions, %llu keys sorted, %.3f s on the GPU\n",
-                ps.nsets, (unsigned long long)g->n, (unsigned long long)info.own_positions, (unsigned long long)info.shared_positions,
-                (unsigned long long)info.keys_sorted, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
-      info.on_device = 1;
-      std::lock_guard<std::mutex> lk(g_pool_info_mu);
-      g_pool_info = info;
-      return g;
-    }
-    if (getenv("G2S_DEBUG")) fprintf(stderr, "[g2s]   pooled set graph on the host (%s)\n", why.c_str());
-    delete g;
+  if (Graph* g = build_on_device(k, solid, "pooled set graph", [&](Graph& dg, int device, const HostWalk& walk, std::string* why) {
+        return graph_build_pool_gpu(dg, ps, solid, device, walk, &info, why);
+      })) {
+    if (getenv("G2S_DEBUG"))
+      fprintf(stderr, "[g2s] pooled set graph build: %u sets, %llu k-mers, %llu own + %llu shared positions, %llu keys sorted, %.3f s on the GPU\n",
+              ps.nsets, (unsigned long long)g->n, (unsigned long long)info.own_positions, (unsigned long long)info.shared_positions,
+              (unsigned long long)info.keys_sorted, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+    info.on_device = 1;
+    g_pool_info.set(info);
+    return g;
   }
   if (ps.host_text && !ps.host_text(err)) return nullptr;
-  info = PoolBuildInfo();
-  info.text_packed = pool_text_in_use(ps);
   uint64_t flagged = 0;
   for (uint32_t s = 0; s < ps.nsets; s++) flagged += ps.flagged(s) ? 1 : 0;
-  for (uint64_t q = ps.set_begin[0]; q < ps.set_begin[ps.nsets]; q++) info.own_positions += seqs[ps.set_seq[q]].second + 1;
-  if (flagged)
-    for (uint64_t x = 0; x < ps.nshared; x++) info.shared_positions += seqs[ps.shared_seq[x]].second + 1;
-  info.keys_sorted = info.own_positions + flagged * info.shared_positions;
-  Graph* g = build_sets_host([&](uint32_t s, std::vector<std::pair<const char*, uint64_t>>* tmp) { return expand(s, tmp); }, ps.nsets, k,
-                             solid, nthreads, t0, err);
-  if (g) {
-    std::lock_guard<std::mutex> lk(g_pool_info_mu);
-    g_pool_info = info;
-  }
+  info = pool_info_host(ps, flagged, 0);
+  Graph* g = build_sets_host([&](uint32_t s, std::vector<std::pair<const char*, uint64_t>>* tmp) { return expand_set(ps, s, ps.flagged(s), tmp); },
+                             ps.nsets, k, solid, nthreads, t0, err);
+  if (g) g_pool_info.set(info);
   return g;
 }
 
 // ---- pooled set graphs bounded by reach records (dbg.hpp: PoolReach) ---------------------------------
 namespace {
-
-std::mutex g_reach_info_mu;
-PoolReachInfo g_reach_info;
 
 template <class KT>
 struct KmerHasher {
@@ -888,9 +830,6 @@ template <class KT>
 void build_reach_part(const std::vector<std::pair<const char*, uint64_t>>& own_seqs, const CountTable<KT>* shared,
                       const char* const* seeds, uint64_t nseeds, int32_t radius, int k, int solid, Graph* part, uint64_t* full,
                       uint32_t* levels) {
-  part->k = k;
-  part->solid = solid;
-  part->kmer_bytes = kmer_width(k);
   const uint64_t so = (uint64_t)std::max(1, solid);
   CountTable<KT> own;
   own.build(own_seqs, k);
@@ -961,23 +900,16 @@ Graph* build_pool_reach_host(const PoolSets& ps, const PoolReach& reach, int k, 
   const SetPartFn own_part = [&](uint32_t s, const std::vector<std::pair<const char*, uint64_t>>&, Graph* part) -> bool {
     if (!reach.has(s)) return false;
     std::vector<std::pair<const char*, uint64_t>> own;
-    for (uint64_t q = ps.set_begin[s]; q < ps.set_begin[s + 1]; q++) own.push_back(seqs[ps.set_seq[q]]);
-    build_reach_part<KT>(own, ps.flagged(s) ? &shared : nullptr, reach.seed.data() + reach.seed_begin[s],
+    build_reach_part<KT>(*expand_set(ps, s, false, &own), ps.flagged(s) ? &shared : nullptr, reach.seed.data() + reach.seed_begin[s],
                          reach.seed_begin[s + 1] - reach.seed_begin[s], reach.radius[s], k, solid, part,
                          count_full ? &full[s] : nullptr, &levels[s]);
     kept[s] = part->n;
     return true;
   };
-  auto expand = [&](uint32_t s, std::vector<std::pair<const char*, uint64_t>>* out) {
-    out->clear();
-    if (reach.has(s)) return out;  // (own_part reads the lists itself)
-    for (uint64_t q = ps.set_begin[s]; q < ps.set_begin[s + 1]; q++) out->push_back(seqs[ps.set_seq[q]]);
-    if (ps.flagged(s))
-      for (uint64_t x = 0; x < ps.nshared; x++) out->push_back(seqs[ps.shared_seq[x]]);
-    return out;
-  };
-  Graph* g = build_sets_host([&](uint32_t s, std::vector<std::pair<const char*, uint64_t>>* tmp) { return expand(s, tmp); }, ps.nsets, k,
-                             solid, nthreads, t0, err, &own_part);
+  Graph* g = build_sets_host([&](uint32_t s, std::vector<std::pair<const char*, uint64_t>>* tmp) {
+    if (reach.has(s)) { tmp->clear(); return tmp; }  // (own_part reads the lists itself)
+    return expand_set(ps, s, ps.flagged(s), tmp);
+  }, ps.nsets, k, solid, nthreads, t0, err, &own_part);
   for (uint32_t s = 0; s < ps.nsets; s++) {
     if (!reach.has(s)) continue;
     rinfo->reach_sets++;
@@ -999,10 +931,7 @@ void collapse_to_one_set(Graph& g) {
 
 }  // namespace
 
-PoolReachInfo last_pool_reach() {
-  std::lock_guard<std::mutex> lk(g_reach_info_mu);
-  return g_reach_info;
-}
+PoolReachInfo last_pool_reach() { return g_reach_info.get(); }
 
 Graph* graph_build_pool_reach(const PoolSets& ps_in, const PoolReach& reach_in, int k, int solid, int nthreads, std::string* err) {
   if (!reach_in.any()) return graph_build_pool(ps_in, k, solid, nthreads, err);
@@ -1030,65 +959,36 @@ Graph* graph_build_pool_reach(const PoolSets& ps_in, const PoolReach& reach_in, 
   const PoolReach& reach = one ? reach1 : reach_in;
   if (nthreads <= 0) nthreads = (int)std::max(1u, std::thread::hardware_concurrency());
   const auto t0 = std::chrono::steady_clock::now();
-  const std::vector<std::pair<const char*, uint64_t>>& seqs = *ps.seqs;
   const int kb = kmer_width(k);
   PoolBuildInfo info;
   PoolReachInfo rinfo;
-  Graph* g = nullptr;
-  bool device_gave_up = false;
-  if (!getenv("G2S_HOST_BUILD")) {
-    g = new Graph();
-    g->k = k;
-    g->solid = solid;
-    g->kmer_bytes = kb;
-    std::string why;
-    const bool ok = graph_build_pool_gpu(*g, ps, solid, getenv("G2S_DEVICE") ? atoi(getenv("G2S_DEVICE")) : 0,
-                                         [&](const std::vector<uint32_t>& succ_r, uint32_t first_id) {
-                                           unitig_order(succ_r, g->n, (g->k % 2) == 0, &g->rank2id, &g->flip, &g->n_unitigs, true, first_id);
-                                         }, &info, &why, &reach, &rinfo, &device_gave_up);
-    if (ok) {
-      if (getenv("G2S_DEBUG"))
-        fprintf(stderr, "[g2s] pooled set graph build: %u sets, %llu k-mers, %llu own + %llu shared positions, %llu keys sorted, %.3f s on the GPU; "
-                        "reach: %llu sets, %llu k-mers kept, %u levels\n",
-                ps_in.nsets, (unsigned long long)g->n, (unsigned long long)info.own_positions, (unsigned long long)info.shared_positions,
-                (unsigned long long)info.keys_sorted, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(),
-                (unsigned long long)rinfo.reach_sets, (unsigned long long)rinfo.kept_kmers, rinfo.levels);
-      info.on_device = 1;
-    } else {
-      if (getenv("G2S_DEBUG")) fprintf(stderr, "[g2s]   pooled set graph on the host (%s)\n", why.c_str());
-      // (device_gave_up: the build got as far as selecting the device — not a machine without one)
-      delete g;
-      g = nullptr;
-    }
-  }
-  if (!g) {
+  bool device_gave_up = false;  // (the device build got as far as selecting the device — not a machine without one)
+  Graph* g = build_on_device(k, solid, "pooled set graph", [&](Graph& dg, int device, const HostWalk& walk, std::string* why) {
+    return graph_build_pool_gpu(dg, ps, solid, device, walk, &info, why, &reach, &rinfo, &device_gave_up);
+  });
+  if (g) {
+    if (getenv("G2S_DEBUG"))
+      fprintf(stderr, "[g2s] pooled set graph build: %u sets, %llu k-mers, %llu own + %llu shared positions, %llu keys sorted, %.3f s on the GPU; "
+                      "reach: %llu sets, %llu k-mers kept, %u levels\n",
+              ps_in.nsets, (unsigned long long)g->n, (unsigned long long)info.own_positions, (unsigned long long)info.shared_positions,
+              (unsigned long long)info.keys_sorted, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(),
+              (unsigned long long)rinfo.reach_sets, (unsigned long long)rinfo.kept_kmers, rinfo.levels);
+    info.on_device = 1;
+  } else {
     if (ps.host_text && !ps.host_text(err)) return nullptr;
-    info = PoolBuildInfo();
-    info.text_packed = pool_text_in_use(ps);
-    rinfo = PoolReachInfo();
     uint64_t whole = 0, bounded = 0;  // flagged sets without / with a record
     for (uint32_t s = 0; s < ps.nsets; s++)
       if (ps.flagged(s)) (reach.has(s) ? bounded : whole)++;
-    for (uint64_t q = ps.set_begin[0]; q < ps.set_begin[ps.nsets]; q++) info.own_positions += seqs[ps.set_seq[q]].second + 1;
-    if (whole + bounded)
-      for (uint64_t x = 0; x < ps.nshared; x++) info.shared_positions += seqs[ps.shared_seq[x]].second + 1;
-    info.keys_sorted = info.own_positions + (whole + (bounded ? 1 : 0)) * info.shared_positions;  // (the shared table: once)
-    if (kb == 8) g = build_pool_reach_host<uint64_t>(ps, reach, k, solid, nthreads, !device_gave_up, t0, &rinfo, err);
-    else if (kb == 16) g = build_pool_reach_host<u128>(ps, reach, k, solid, nthreads, !device_gave_up, t0, &rinfo, err);
-    else g = build_pool_reach_host<u256>(ps, reach, k, solid, nthreads, !device_gave_up, t0, &rinfo, err);
+    info = pool_info_host(ps, whole, bounded);
+    rinfo = PoolReachInfo();
+    g = with_kmer_type(kb, [&](auto t) {
+      return build_pool_reach_host<typename decltype(t)::type>(ps, reach, k, solid, nthreads, !device_gave_up, t0, &rinfo, err);
+    });
     if (!g) return nullptr;
   }
-  if (one) {
-    if (kb == 8) collapse_to_one_set<uint64_t>(*g);
-    else if (kb == 16) collapse_to_one_set<u128>(*g);
-    else collapse_to_one_set<u256>(*g);
-  }
-  {
-    std::lock_guard<std::mutex> lk(g_pool_info_mu);
-    g_pool_info = info;
-  }
-  std::lock_guard<std::mutex> lk(g_reach_info_mu);
-  g_reach_info = rinfo;
+  if (one) with_kmer_type(kb, [&](auto t) { collapse_to_one_set<typename decltype(t)::type>(*g); });
+  g_pool_info.set(info);
+  g_reach_info.set(rinfo);
   return g;
 }
 
@@ -1103,9 +1003,10 @@ bool graph_save(const Graph& g, const std::string& path, std::string* err) {
   bool ok = fwrite(kMagic, 1, 8, f) == 8 && fwrite(hdr, 8, 4, f) == 4;
   auto put = [&](const void* p, size_t bytes) { if (ok && bytes) ok = fwrite(p, 1, bytes, f) == bytes; };
   // (the width follows from k: 8-, 16- or 32-byte k-mers, little-endian words, least significant first)
-  if (g.kmer_bytes == 8) put(g.kmers64.data(), g.kmers64.size() * 8);
-  else if (g.kmer_bytes == 16) put(g.kmers128.data(), g.kmers128.size() * 16);
-  else put(g.kmers256.data(), g.kmers256.size() * 32);
+  with_kmer_type(g.kmer_bytes, [&](auto t) {
+    using KT = typename decltype(t)::type;
+    put(kmer_vec<KT>(g).data(), kmer_vec<KT>(g).size() * sizeof(KT));
+  });
   put(g.rank2id.data(), g.rank2id.size() * 4);
   put(g.flip.data(), g.flip.size());
   put(g.succ.data(), g.succ.size() * 4);
@@ -1154,9 +1055,11 @@ Graph* graph_load(const std::string& path, std::string* err) {
   g->kmer_bytes = kmer_width(g->k);
   bool ok = true;
   auto get = [&](void* p, size_t bytes) { if (ok && bytes) ok = fread(p, 1, bytes, f) == bytes; };
-  if (g->kmer_bytes == 8) { g->kmers64.resize((size_t)g->n); get(g->kmers64.data(), (size_t)g->n * 8); }
-  else if (g->kmer_bytes == 16) { g->kmers128.resize((size_t)g->n); get(g->kmers128.data(), (size_t)g->n * 16); }
-  else { g->kmers256.resize((size_t)g->n); get(g->kmers256.data(), (size_t)g->n * 32); }
+  with_kmer_type(g->kmer_bytes, [&](auto t) {
+    using KT = typename decltype(t)::type;
+    kmer_vec<KT>(*g).resize((size_t)g->n);
+    get(kmer_vec<KT>(*g).data(), (size_t)g->n * sizeof(KT));
+  });
   g->rank2id.resize((size_t)g->n); get(g->rank2id.data(), (size_t)g->n * 4);
   g->flip.resize((size_t)g->n); get(g->flip.data(), (size_t)g->n);
   g->succ.resize((size_t)g->n * 8); get(g->succ.data(), (size_t)g->n * 32);
@@ -1170,12 +1073,13 @@ Graph* graph_load(const std::string& path, std::string* err) {
     return nullptr;
   };
   // sorted k-mer set, rank2id a permutation, neighbour ids in range, codes 0..3
-  for (uint64_t r = 1; r < g->n; r++) {
-    const bool ascending = g->kmer_bytes == 8    ? g->kmers64[(size_t)r - 1] < g->kmers64[(size_t)r]
-                           : g->kmer_bytes == 16 ? g->kmers128[(size_t)r - 1] < g->kmers128[(size_t)r]
-                                                 : g->kmers256[(size_t)r - 1] < g->kmers256[(size_t)r];
-    if (!ascending) return corrupt("k-mers not strictly ascending");
-  }
+  const bool ascending = with_kmer_type(g->kmer_bytes, [&](auto t) {
+    const auto& v = kmer_vec<typename decltype(t)::type>(*g);
+    for (size_t r = 1; r < v.size(); r++)
+      if (!(v[r - 1] < v[r])) return false;
+    return true;
+  });
+  if (!ascending) return corrupt("k-mers not strictly ascending");
   g->id2rank.assign((size_t)g->n, kInvalidNode);
   for (uint64_t r = 0; r < g->n; r++) {
     const uint32_t id = g->rank2id[(size_t)r];
@@ -1186,9 +1090,7 @@ Graph* graph_load(const std::string& path, std::string* err) {
   for (uint32_t w : g->pred) if (w != kInvalidNode && w >= 2 * g->n) return corrupt("predecessor out of range");
   for (uint8_t c : g->lastnt) if (c > 3) return corrupt("base code out of range");
   for (uint8_t c : g->flip) if (c > 1) return corrupt("strand flag out of range");
-  if (g->kmer_bytes == 8) build_bucket_index<uint64_t>(*g);
-  else if (g->kmer_bytes == 16) build_bucket_index<u128>(*g);
-  else build_bucket_index<u256>(*g);
+  with_kmer_type(g->kmer_bytes, [&](auto t) { build_bucket_index<typename decltype(t)::type>(*g); });
   build_ustart(*g);
   return g;
 }

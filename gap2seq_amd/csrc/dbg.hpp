@@ -11,6 +11,7 @@
 #include <algorithm>
 #include <mutex>
 #include <cstdint>
+#include <cstdlib>
 #include <map>
 #include <functional>
 #include <string>
@@ -105,6 +106,51 @@ struct Graph {
 static const int kMaxK = 127;
 // bytes of the k-mer word for k in [1, kMaxK]
 static inline int kmer_width(int k) { return k <= 31 ? 8 : k <= 63 ? 16 : 32; }
+// The one dispatch on a k-mer width: f is called with a tag of the width's word and its result handed back, as in
+//   with_kmer_type(g.kmer_bytes, [&](auto t) { using KT = typename decltype(t)::type; ... });
+// A further width is added here, in kmer_vec below and in kmer_width alone.
+template <class KT>
+struct KmerTag { using type = KT; };
+template <class F>
+static inline auto with_kmer_type(int kmer_bytes, F&& f) {
+  if (kmer_bytes == 8) return f(KmerTag<uint64_t>());
+  if (kmer_bytes == 16) return f(KmerTag<u128>());
+  return f(KmerTag<u256>());
+}
+// the graph's sorted k-mers as the vector of their width
+template <class KT> std::vector<KT>& kmer_vec(Graph& g);
+template <> inline std::vector<uint64_t>& kmer_vec<uint64_t>(Graph& g) { return g.kmers64; }
+template <> inline std::vector<u128>& kmer_vec<u128>(Graph& g) { return g.kmers128; }
+template <> inline std::vector<u256>& kmer_vec<u256>(Graph& g) { return g.kmers256; }
+template <class KT> const std::vector<KT>& kmer_vec(const Graph& g);
+template <> inline const std::vector<uint64_t>& kmer_vec<uint64_t>(const Graph& g) { return g.kmers64; }
+template <> inline const std::vector<u128>& kmer_vec<u128>(const Graph& g) { return g.kmers128; }
+template <> inline const std::vector<u256>& kmer_vec<u256>(const Graph& g) { return g.kmers256; }
+
+// The device the graph builds and the reads loader run on: G2S_DEVICE, read on every call (it changes within a process).
+static inline int build_device() {
+  const char* s = getenv("G2S_DEVICE");
+  return s ? atoi(s) : 0;
+}
+// What the process's last call of one kind did, for the test hooks to read: a value behind a mutex.
+template <class T>
+class LastInfo {
+ public:
+  T get() {
+    std::lock_guard<std::mutex> lk(mu_);
+    return v_;
+  }
+  void set(const T& v) { update([&](T& cur) { cur = v; }); }
+  template <class F>
+  void update(F&& f) {  // (some fields alone, under the lock)
+    std::lock_guard<std::mutex> lk(mu_);
+    f(v_);
+  }
+
+ private:
+  std::mutex mu_;
+  T v_;
+};
 
 struct GraphReach;
 // seqs may contain any bytes; k-mers containing N/n are skipped (GATB model).  reach: BuildInput::reach.

@@ -828,9 +828,9 @@ namespace g2s {
 // unnumbered (circular unitigs).  Returns false (with a reason) when the device cannot be
 // used; nothing of g is touched then and the caller runs the host build.
 template <class KT, bool EVEN>
-static bool finish_gpu_e(Graph& g, const std::vector<KT>& kmers, int device,
-                         const std::function<void(const std::vector<uint32_t>&, uint32_t)>& host_walk, std::string* why,
-                         const std::vector<uint32_t>* rank_set) {
+static bool finish_gpu_e(Graph& g, int device, const std::function<void(const std::vector<uint32_t>&, uint32_t)>& host_walk,
+                         std::string* why, const std::vector<uint32_t>* rank_set) {
+  const std::vector<KT>& kmers = kmer_vec<KT>(g);
   if (!device_exists(device)) { if (why) *why = "no device"; return false; }
   const uint64_t n = g.n;
   if (n == 0 || 2 * n >= (1ull << 31)) { if (why) *why = "size"; return false; }
@@ -971,11 +971,10 @@ static bool finish_gpu_e(Graph& g, const std::vector<KT>& kmers, int device,
 }
 
 template <class KT>
-static bool finish_gpu_t(Graph& g, const std::vector<KT>& kmers, int device,
-                         const std::function<void(const std::vector<uint32_t>&, uint32_t)>& host_walk, std::string* why,
-                         const std::vector<uint32_t>* rank_set = nullptr) {
-  return (g.k % 2) == 0 ? finish_gpu_e<KT, true>(g, kmers, device, host_walk, why, rank_set)
-                        : finish_gpu_e<KT, false>(g, kmers, device, host_walk, why, rank_set);
+static bool finish_gpu_t(Graph& g, int device, const std::function<void(const std::vector<uint32_t>&, uint32_t)>& host_walk,
+                         std::string* why, const std::vector<uint32_t>* rank_set = nullptr) {
+  return (g.k % 2) == 0 ? finish_gpu_e<KT, true>(g, device, host_walk, why, rank_set)
+                        : finish_gpu_e<KT, false>(g, device, host_walk, why, rank_set);
 }
 
 // solid_passes.h
@@ -991,8 +990,8 @@ static bool solid_passes_forced();
 // sort's bytes a position) goes through the key-range passes of solid_passes.h, as does every text under
 // G2S_BUILD_PASS_KEYS.  Returns false (g untouched) when the device cannot be used or not even the passes fit.
 template <class KT>
-static bool count_solid_gpu_t(Graph& g, std::vector<KT>& out, const BuildInput& in, int solid, int device, std::string* why,
-                              SolidCountInfo* info) {
+static bool count_solid_gpu_t(Graph& g, const BuildInput& in, int solid, int device, std::string* why, SolidCountInfo* info) {
+  std::vector<KT>& out = kmer_vec<KT>(g);
   if (in.text) device = in.text->device;  // (where the text is)
   if (!device_exists(device)) { if (why) *why = "no device"; return false; }
   G2S_HIP_TRY(hipSetDevice(device));
@@ -1203,9 +1202,9 @@ static bool runs_keyed_gpu(const KT* sk, const uint32_t* ss, uint64_t T, DevMem&
 // run, compaction, every set's first rank.  out / rank_set / g.set_lo set-major; false (g untouched) when the device
 // cannot be used.
 template <class KT>
-static bool count_solid_sets_gpu_t(Graph& g, std::vector<KT>& out, std::vector<uint32_t>* rank_set,
-                                   const std::vector<std::pair<const char*, uint64_t>>& seqs, const std::vector<uint32_t>& seq_set,
-                                   uint32_t nsets, int solid, int device, std::string* why) {
+static bool count_solid_sets_gpu_t(Graph& g, std::vector<uint32_t>* rank_set, const std::vector<std::pair<const char*, uint64_t>>& seqs,
+                                   const std::vector<uint32_t>& seq_set, uint32_t nsets, int solid, int device, std::string* why) {
+  std::vector<KT>& out = kmer_vec<KT>(g);
   if (!device_exists(device)) { if (why) *why = "no device"; return false; }
   G2S_HIP_TRY(hipSetDevice(device));
   const int k = g.k;
@@ -1286,16 +1285,12 @@ static bool count_solid_sets_gpu_t(Graph& g, std::vector<KT>& out, std::vector<u
 bool graph_build_sets_gpu(Graph& g, const std::vector<std::pair<const char*, uint64_t>>& seqs, const std::vector<uint32_t>& seq_set,
                           uint32_t nsets, int solid, int device,
                           const std::function<void(const std::vector<uint32_t>&, uint32_t)>& host_walk, std::string* why) {
-  std::vector<uint32_t> rank_set;
-  bool ok;
-  if (g.kmer_bytes == 32) ok = count_solid_sets_gpu_t<u256>(g, g.kmers256, &rank_set, seqs, seq_set, nsets, solid, device, why);
-  else if (g.kmer_bytes == 16) ok = count_solid_sets_gpu_t<u128>(g, g.kmers128, &rank_set, seqs, seq_set, nsets, solid, device, why);
-  else ok = count_solid_sets_gpu_t<uint64_t>(g, g.kmers64, &rank_set, seqs, seq_set, nsets, solid, device, why);
-  if (!ok) return false;
-  if (g.kmer_bytes == 32) ok = finish_gpu_t<u256>(g, g.kmers256, device, host_walk, why, &rank_set);
-  else if (g.kmer_bytes == 16) ok = finish_gpu_t<u128>(g, g.kmers128, device, host_walk, why, &rank_set);
-  else ok = finish_gpu_t<uint64_t>(g, g.kmers64, device, host_walk, why, &rank_set);
-  return ok;
+  return with_kmer_type(g.kmer_bytes, [&](auto t) {
+    using KT = typename decltype(t)::type;
+    std::vector<uint32_t> rank_set;
+    return count_solid_sets_gpu_t<KT>(g, &rank_set, seqs, seq_set, nsets, solid, device, why) &&
+           finish_gpu_t<KT>(g, device, host_walk, why, &rank_set);
+  });
 }
 
 // The solid k-mer sets of a pooled set graph (dbg.hpp: PoolSets).  The expanded lists are never formed: the text of the
@@ -1304,9 +1299,10 @@ bool graph_build_sets_gpu(Graph& g, const std::vector<std::pair<const char*, uin
 // count_solid_sets_gpu_t; the shared keys are sorted ONCE and run-length counted, however many sets hold them; the two
 // tables are merged per set into the (set, k-mer) order the rest of the build wants.  info: positions and keys sorted.
 template <class KT>
-static bool count_solid_pool_gpu_t(Graph& g, std::vector<KT>& out, std::vector<uint32_t>* rank_set, const PoolSets& ps, int solid,
-                                   int device, PoolBuildInfo* info, std::string* why, const PoolReach* reach, PoolReachInfo* rinfo,
+static bool count_solid_pool_gpu_t(Graph& g, std::vector<uint32_t>* rank_set, const PoolSets& ps, int solid, int device,
+                                   PoolBuildInfo* info, std::string* why, const PoolReach* reach, PoolReachInfo* rinfo,
                                    bool* device_usable) {
+  std::vector<KT>& out = kmer_vec<KT>(g);
   if (!device_exists(device)) { if (why) *why = "no device"; return false; }
   G2S_HIP_TRY(hipSetDevice(device));
   if (device_usable) *device_usable = true;  // (a failure from here on is the device build giving up, not its absence)
@@ -1723,16 +1719,12 @@ bool graph_build_pool_gpu(Graph& g, const PoolSets& ps, int solid, int device,
                           const std::function<void(const std::vector<uint32_t>&, uint32_t)>& host_walk, PoolBuildInfo* info,
                           std::string* why, const PoolReach* reach, PoolReachInfo* rinfo, bool* device_usable) {
   if (device_usable) *device_usable = false;
-  std::vector<uint32_t> rank_set;
-  bool ok;
-  if (g.kmer_bytes == 32) ok = count_solid_pool_gpu_t<u256>(g, g.kmers256, &rank_set, ps, solid, device, info, why, reach, rinfo, device_usable);
-  else if (g.kmer_bytes == 16) ok = count_solid_pool_gpu_t<u128>(g, g.kmers128, &rank_set, ps, solid, device, info, why, reach, rinfo, device_usable);
-  else ok = count_solid_pool_gpu_t<uint64_t>(g, g.kmers64, &rank_set, ps, solid, device, info, why, reach, rinfo, device_usable);
-  if (!ok) return false;
-  if (g.kmer_bytes == 32) ok = finish_gpu_t<u256>(g, g.kmers256, device, host_walk, why, &rank_set);
-  else if (g.kmer_bytes == 16) ok = finish_gpu_t<u128>(g, g.kmers128, device, host_walk, why, &rank_set);
-  else ok = finish_gpu_t<uint64_t>(g, g.kmers64, device, host_walk, why, &rank_set);
-  return ok;
+  return with_kmer_type(g.kmer_bytes, [&](auto t) {
+    using KT = typename decltype(t)::type;
+    std::vector<uint32_t> rank_set;
+    return count_solid_pool_gpu_t<KT>(g, &rank_set, ps, solid, device, info, why, reach, rinfo, device_usable) &&
+           finish_gpu_t<KT>(g, device, host_walk, why, &rank_set);
+  });
 }
 
 }  // namespace g2s
@@ -1742,16 +1734,16 @@ bool graph_build_pool_gpu(Graph& g, const PoolSets& ps, int solid, int device,
 namespace g2s {
 
 bool count_solid_gpu(Graph& g, const BuildInput& in, int solid, int device, std::string* why, SolidCountInfo* info) {
-  if (g.kmer_bytes == 32) return count_solid_gpu_t<u256>(g, g.kmers256, in, solid, device, why, info);
-  return g.kmer_bytes == 16 ? count_solid_gpu_t<u128>(g, g.kmers128, in, solid, device, why, info)
-                            : count_solid_gpu_t<uint64_t>(g, g.kmers64, in, solid, device, why, info);
+  return with_kmer_type(g.kmer_bytes, [&](auto t) {
+    return count_solid_gpu_t<typename decltype(t)::type>(g, in, solid, device, why, info);
+  });
 }
 
 bool graph_finish_gpu(Graph& g, int device, const std::function<void(const std::vector<uint32_t>&, uint32_t)>& host_walk,
                       std::string* why) {
-  if (g.kmer_bytes == 32) return finish_gpu_t<u256>(g, g.kmers256, device, host_walk, why);
-  return g.kmer_bytes == 16 ? finish_gpu_t<u128>(g, g.kmers128, device, host_walk, why)
-                            : finish_gpu_t<uint64_t>(g, g.kmers64, device, host_walk, why);
+  return with_kmer_type(g.kmer_bytes, [&](auto t) {
+    return finish_gpu_t<typename decltype(t)::type>(g, device, host_walk, why);
+  });
 }
 
 }  // namespace g2s

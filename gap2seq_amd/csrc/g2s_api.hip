@@ -136,18 +136,26 @@ extern "C" int g2s_device_count(void) {
 struct g2s_graph {
   Graph* g = nullptr;
 };
-
-static int build_seqs_of(const char* const* seqs, const uint64_t* lens, int nseqs, int k, int solid, int nthreads,
-                         const GraphReach* reach, g2s_graph** out) {
-  if (!seqs || !out || nseqs < 0) return fail(G2S_ERR_ARG, "g2s_graph_build_seqs: bad argument");
-  std::vector<std::pair<const char*, uint64_t>> v;
-  for (int i = 0; i < nseqs; i++) v.emplace_back(seqs[i], lens ? lens[i] : (uint64_t)strlen(seqs[i]));
-  std::string err;
-  Graph* g = graph_build(v, k, solid, nthreads, &err, reach);
+// what a builder of dbg.hpp made, handed back as a handle: null is the builder's refusal, with its reason in err
+static int wrap_graph(Graph* g, const std::string& err, g2s_graph** out) {
   if (!g) return fail(G2S_ERR_ARG, err);
   *out = new g2s_graph();
   (*out)->g = g;
   return G2S_OK;
+}
+// the callers' sequences as (pointer, length) pairs; lens == nullptr: C strings
+static std::vector<std::pair<const char*, uint64_t>> seq_pairs(const char* const* seqs, const uint64_t* lens, uint64_t n) {
+  std::vector<std::pair<const char*, uint64_t>> v;
+  v.reserve((size_t)n);
+  for (uint64_t i = 0; i < n; i++) v.emplace_back(seqs[i], lens ? lens[i] : (uint64_t)strlen(seqs[i]));
+  return v;
+}
+
+static int build_seqs_of(const char* const* seqs, const uint64_t* lens, int nseqs, int k, int solid, int nthreads,
+                         const GraphReach* reach, g2s_graph** out) {
+  if (!seqs || !out || nseqs < 0) return fail(G2S_ERR_ARG, "g2s_graph_build_seqs: bad argument");
+  std::string err;
+  return wrap_graph(graph_build(seq_pairs(seqs, lens, (uint64_t)nseqs), k, solid, nthreads, &err, reach), err, out);
 }
 extern "C" int g2s_graph_build_seqs(const char* const* seqs, const uint64_t* lens, int nseqs, int k, int solid,
                                     int nthreads, g2s_graph** out) {
@@ -155,8 +163,16 @@ extern "C" int g2s_graph_build_seqs(const char* const* seqs, const uint64_t* len
 }
 
 // ---- single graphs bounded by reach records (include/g2s.h: g2s_graph_build_seqs_reach) --------------------
-// the records' seeds, one entry a seed with its record's radius: the flank k-mers the fill looks up
-// (build_pool_reach_of below takes the same ones), none for a gap it rejects
+// A reach record's seeds: the flank k-mers the fill looks up (g2s_batch_prepare: the rule must match it), appended to
+// *out.  False, and nothing appended, for a gap the fill rejects.
+static bool flank_seeds(const g2s_gap& in, int k, std::vector<const char*>* out) {
+  if (!in.left || !in.right || in.lmf < 0 || in.rmf < 0 || in.gap_len < 0 || in.left_len < k + in.lmf || in.right_len < k + in.rmf) return false;
+  for (int x = 0; x <= in.lmf; x++) out->push_back(in.left + x);
+  for (int x = 0; x <= in.rmf; x++) out->push_back(in.right + (in.right_len - k - x));
+  for (int x = 0; x <= in.rmf; x++) out->push_back(in.right + x);
+  return true;
+}
+// the records' seeds, one entry a seed with its record's radius
 static int graph_reach_of(const char* name, int k, const g2s_gap* reach_gap, const int32_t* reach_radius, uint64_t nreach,
                           GraphReach* reach) {
   if (nreach && (!reach_gap || !reach_radius)) return fail(G2S_ERR_ARG, std::string(name) + ": reach_gap and reach_radius go together");
@@ -164,14 +180,8 @@ static int graph_reach_of(const char* name, int k, const g2s_gap* reach_gap, con
   for (uint64_t r = 0; r < nreach; r++)
     if (reach_radius[r] < 0) return fail(G2S_ERR_ARG, std::string(name) + ": negative radius in record " + std::to_string(r));
   reach->records = nreach;
-  for (uint64_t r = 0; r < nreach; r++) {
-    const g2s_gap& in = reach_gap[r];
-    if (!in.left || !in.right || in.lmf < 0 || in.rmf < 0 || in.gap_len < 0 || in.left_len < k + in.lmf || in.right_len < k + in.rmf) continue;
-    for (int x = 0; x <= in.lmf; x++) reach->seed.push_back(in.left + x);
-    for (int x = 0; x <= in.rmf; x++) reach->seed.push_back(in.right + (in.right_len - k - x));
-    for (int x = 0; x <= in.rmf; x++) reach->seed.push_back(in.right + x);
-    reach->radius.resize(reach->seed.size(), reach_radius[r]);
-  }
+  for (uint64_t r = 0; r < nreach; r++)
+    if (flank_seeds(reach_gap[r], k, &reach->seed)) reach->radius.resize(reach->seed.size(), reach_radius[r]);
   return G2S_OK;
 }
 // G2S_REACH_AUTO resolved: G2S_BUILD_REACH=1|0 overrides it; -1 for a mode that is none of the three
@@ -232,14 +242,10 @@ extern "C" int g2s_graph_build_sets(const char* const* seqs, const uint64_t* len
   for (int i = 0; i < nseqs; i++)
     if (seq_set[i] >= nsets) return fail(G2S_ERR_ARG, "g2s_graph_build_sets: set id out of range");
   if (nsets == 1) return g2s_graph_build_seqs(seqs, lens, nseqs, k, solid, nthreads, out);  // an ordinary graph
-  std::vector<std::pair<const char*, uint64_t>> v;
-  for (int i = 0; i < nseqs; i++) v.emplace_back(seqs[i], lens ? lens[i] : (uint64_t)strlen(seqs[i]));
   std::string err;
-  Graph* g = graph_build_sets(v, std::vector<uint32_t>(seq_set, seq_set + nseqs), nsets, k, solid, nthreads, &err);
-  if (!g) return fail(G2S_ERR_ARG, err);
-  *out = new g2s_graph();
-  (*out)->g = g;
-  return G2S_OK;
+  Graph* g = graph_build_sets(seq_pairs(seqs, lens, (uint64_t)nseqs), std::vector<uint32_t>(seq_set, seq_set + nseqs), nsets, k, solid,
+                              nthreads, &err);
+  return wrap_graph(g, err, out);
 }
 static int build_pool_reach_of(const PoolSets& ps, int k, int solid, int nthreads, const g2s_gap* reach_gap,
                                const int32_t* reach_radius, g2s_graph** out);
@@ -252,10 +258,8 @@ static int pool_sets_of(const char* name, const char* const* seqs, const uint64_
   for (uint32_t s = 0; s < nsets; s++)
     if (set_begin[s + 1] < set_begin[s]) return fail(G2S_ERR_ARG, std::string(name) + ": set_begin decreases");
   if (!set_seq && set_begin[nsets] > set_begin[0]) return fail(G2S_ERR_ARG, std::string(name) + ": bad argument");
-  if (seqs) {  // (nullptr with sequences: g2s_graph_build_dpool_reach, which has filled `v` from its pools)
-    v->reserve((size_t)nseqs);
-    for (uint64_t i = 0; i < nseqs; i++) v->emplace_back(seqs[i], lens ? lens[i] : (uint64_t)strlen(seqs[i]));
-  }
+  // (nullptr with sequences: g2s_graph_build_dpool_reach, which has filled `v` from its pools)
+  if (seqs) *v = seq_pairs(seqs, lens, nseqs);
   ps->seqs = v;
   ps->set_begin = set_begin;
   ps->set_seq = set_seq;
@@ -273,11 +277,7 @@ extern "C" int g2s_graph_build_pool(const char* const* seqs, const uint64_t* len
   const int rc = pool_sets_of("g2s_graph_build_pool", seqs, lens, nseqs, set_begin, set_seq, shared_seq, nshared, set_shared, nsets, out, &v, &ps);
   if (rc != G2S_OK) return rc;
   std::string err;
-  Graph* g = graph_build_pool(ps, k, solid, nthreads, &err);
-  if (!g) return fail(G2S_ERR_ARG, err);
-  *out = new g2s_graph();
-  (*out)->g = g;
-  return G2S_OK;
+  return wrap_graph(graph_build_pool(ps, k, solid, nthreads, &err), err, out);
 }
 extern "C" int g2s_graph_build_pool_reach(const char* const* seqs, const uint64_t* lens, uint64_t nseqs, const uint64_t* set_begin,
                                           const uint32_t* set_seq, const uint32_t* shared_seq, uint64_t nshared,
@@ -296,27 +296,15 @@ static int build_pool_reach_of(const PoolSets& ps, int k, int solid, int nthread
                                const int32_t* reach_radius, g2s_graph** out) {
   const uint32_t nsets = ps.nsets;
   if (k < 1 || k > kMaxK) return fail(G2S_ERR_ARG, "k must be in [1," + std::to_string(kMaxK) + "]");  // (the seeds below read k characters)
-  // the seeds: the flank k-mers the fill looks up (g2s_batch_prepare), none for a gap it rejects
   PoolReach reach;
   reach.radius.assign(reach_radius, reach_radius + nsets);
   reach.seed_begin.assign(1, 0);
   for (uint32_t s = 0; s < nsets; s++) {
-    const g2s_gap& in = reach_gap[s];
-    const bool bad = reach_radius[s] < 0 || !in.left || !in.right || in.lmf < 0 || in.rmf < 0 || in.gap_len < 0 ||
-                     in.left_len < k + in.lmf || in.right_len < k + in.rmf;
-    if (!bad) {
-      for (int x = 0; x <= in.lmf; x++) reach.seed.push_back(in.left + x);
-      for (int x = 0; x <= in.rmf; x++) reach.seed.push_back(in.right + (in.right_len - k - x));
-      for (int x = 0; x <= in.rmf; x++) reach.seed.push_back(in.right + x);
-    }
+    if (reach_radius[s] >= 0) flank_seeds(reach_gap[s], k, &reach.seed);  // (none for the whole set, or a gap the fill rejects)
     reach.seed_begin.push_back(reach.seed.size());
   }
   std::string err;
-  Graph* g = graph_build_pool_reach(ps, reach, k, solid, nthreads, &err);
-  if (!g) return fail(G2S_ERR_ARG, err);
-  *out = new g2s_graph();
-  (*out)->g = g;
-  return G2S_OK;
+  return wrap_graph(graph_build_pool_reach(ps, reach, k, solid, nthreads, &err), err, out);
 }
 // The pooled build over pools the read filter left where it made them (device_pool.h).  A pool held on the build's device
 // hands its reads over as null pointers with a PoolDeviceText (dbg_gpu.hip gathers them device to device); every other
@@ -336,7 +324,7 @@ extern "C" int g2s_graph_build_dpool_reach(const g2s_device_pool* const* pools, 
   }
   if (total >= (1ull << 32)) return fail(G2S_ERR_ARG, std::string(name) + ": bad argument");
   const bool host_build = getenv("G2S_HOST_BUILD") != nullptr;
-  const int device = getenv("G2S_DEVICE") ? atoi(getenv("G2S_DEVICE")) : 0;
+  const int device = build_device();
   std::vector<std::pair<const char*, uint64_t>> v((size_t)total);
   std::vector<PoolDeviceText> dtext;
   std::vector<std::string> down(npools);  // the text of a device-held pool, once it has come down
@@ -376,11 +364,7 @@ extern "C" int g2s_graph_build_dpool_reach(const g2s_device_pool* const* pools, 
   }
   if (reach_radius) return build_pool_reach_of(ps, k, solid, nthreads, reach_gap, reach_radius, out);
   std::string err;
-  Graph* g = graph_build_pool(ps, k, solid, nthreads, &err);
-  if (!g) return fail(G2S_ERR_ARG, err);
-  *out = new g2s_graph();
-  (*out)->g = g;
-  return G2S_OK;
+  return wrap_graph(graph_build_pool(ps, k, solid, nthreads, &err), err, out);
 }
 // TEST HOOK (include/g2s_test.h)
 extern "C" int g2s_test_last_dpool(int* held_on_device, uint64_t* bases_bytes_to_host, uint64_t* text_bytes_gathered_on_device,
@@ -454,12 +438,8 @@ extern "C" uint32_t g2s_graph_set_node(const g2s_graph* g, uint32_t set, const c
 // bytes and hands it to the device count; the host loader (zlib, parse_fastx, graph_build) is the fallback for everything
 // but a file that cannot be read, and what G2S_HOST_BUILD=1, G2S_HOST_READS=1 or a machine without a device get.
 namespace {
-std::mutex g_reads_info_mu;
-ReadsLoadInfo g_reads_info;
-void set_reads_info(const ReadsLoadInfo& info) {
-  std::lock_guard<std::mutex> lk(g_reads_info_mu);
-  g_reads_info = info;
-}
+LastInfo<ReadsLoadInfo> g_reads_info;
+void set_reads_info(const ReadsLoadInfo& info) { g_reads_info.set(info); }
 uint64_t env_bytes(const char* name) {
   const char* s = getenv(name);
   return s && *s ? strtoull(s, nullptr, 10) : 0;
@@ -511,8 +491,7 @@ static int build_files_of(const char* reads_csv, int k, int solid, int nthreads,
     DeviceText text;
     ReadsLoadInfo info;
     std::string why;
-    const ReadsLoadResult r = load_reads_device(inputs, getenv("G2S_DEVICE") ? atoi(getenv("G2S_DEVICE")) : 0,
-                                                (size_t)piece, env_bytes("G2S_BUILD_TEXT_FIRST_BYTES"),
+    const ReadsLoadResult r = load_reads_device(inputs, build_device(), (size_t)piece, env_bytes("G2S_BUILD_TEXT_FIRST_BYTES"),
                                                 env_on("G2S_HOST_INFLATE"), &text, &info, &why, env_bytes("G2S_BUILD_RESIDENT_CAP"),
                                                 env_bam_stream(), device_gzip_asked());
     if (r == kReadsIoError) return fail(G2S_ERR_IO, why);
@@ -529,13 +508,8 @@ static int build_files_of(const char* reads_csv, int k, int solid, int nthreads,
       std::string err;
       Graph* g = graph_build_text(&text, k, solid, nthreads, &err, &gave_up, reach);
       free_device_text(&text);
-      if (g) {
-        set_reads_info(info);
-        *out = new g2s_graph();
-        (*out)->g = g;
-        return G2S_OK;
-      }
-      if (!gave_up) return fail(G2S_ERR_ARG, err);
+      if (g) set_reads_info(info);
+      if (g || !gave_up) return wrap_graph(g, err, out);
       why = "the device count gave up: " + err;
     }
     if (debug) fprintf(stderr, "[g2s] reads: the host loader takes over (%s)\n", why.c_str());
@@ -579,20 +553,13 @@ static int build_files_of(const char* reads_csv, int k, int solid, int nthreads,
   info.records = recs.size();
   std::string err;
   Graph* g = graph_build(v, k, solid, nthreads, &err, reach);
-  if (!g) return fail(G2S_ERR_ARG, err);
-  set_reads_info(info);
-  *out = new g2s_graph();
-  (*out)->g = g;
-  return G2S_OK;
+  if (g) set_reads_info(info);
+  return wrap_graph(g, err, out);
 }
 // TEST HOOK (include/g2s_test.h)
 extern "C" int g2s_test_last_reads_load(uint64_t* files, uint64_t* raw_bytes, uint64_t* positions, uint64_t* records,
                                         uint64_t* pieces, int* on_device, int* inflate, uint64_t inflate_cap, uint64_t* grows) {
-  ReadsLoadInfo info;
-  {
-    std::lock_guard<std::mutex> lk(g_reads_info_mu);
-    info = g_reads_info;
-  }
+  const ReadsLoadInfo info = g_reads_info.get();
   if (files) *files = info.files;
   if (raw_bytes) *raw_bytes = info.raw_bytes;
   if (positions) *positions = info.positions;
@@ -607,11 +574,7 @@ extern "C" int g2s_test_last_reads_load(uint64_t* files, uint64_t* raw_bytes, ui
 // TEST HOOK (include/g2s_test.h)
 extern "C" int g2s_test_last_reads_bam(uint64_t* bam_files, uint64_t* kept, uint64_t* skipped, int* by_kernels, int* reason,
                                        int* anomaly) {
-  ReadsLoadInfo info;
-  {
-    std::lock_guard<std::mutex> lk(g_reads_info_mu);
-    info = g_reads_info;
-  }
+  const ReadsLoadInfo info = g_reads_info.get();
   if (bam_files) *bam_files = info.bam_files;
   if (kept) *kept = info.bam_kept;
   if (skipped) *skipped = info.bam_skipped;
@@ -622,11 +585,7 @@ extern "C" int g2s_test_last_reads_bam(uint64_t* bam_files, uint64_t* kept, uint
 }
 // TEST HOOK (include/g2s_test.h)
 extern "C" int g2s_test_last_reads_bam_stream(uint64_t* streamed_files, uint64_t* windows, uint64_t* peak_device_bytes) {
-  ReadsLoadInfo info;
-  {
-    std::lock_guard<std::mutex> lk(g_reads_info_mu);
-    info = g_reads_info;
-  }
+  const ReadsLoadInfo info = g_reads_info.get();
   if (streamed_files) *streamed_files = info.bam_streamed;
   if (windows) *windows = info.bam_stream_windows;
   if (peak_device_bytes) *peak_device_bytes = info.bam_stream_peak;
@@ -698,11 +657,7 @@ extern "C" int g2s_reads_set_device_gzip(int mode) { return set_device_gzip(mode
 // TEST HOOK (include/g2s_test.h)
 extern "C" int g2s_test_last_reads_gzip(uint64_t* files, uint64_t* windows, uint64_t* chunks, uint64_t* starts_found,
                                         uint64_t* absorbed, uint64_t* members, int* outcome, uint64_t* peak_device_bytes) {
-  ReadsLoadInfo info;
-  {
-    std::lock_guard<std::mutex> lk(g_reads_info_mu);
-    info = g_reads_info;
-  }
+  const ReadsLoadInfo info = g_reads_info.get();
   if (files) *files = info.gzip.files;
   if (windows) *windows = info.gzip.windows;
   if (chunks) *chunks = info.gzip.chunks;
