@@ -1172,6 +1172,8 @@ struct g2s_session {
   const void* flank_owner = nullptr;  // batch whose flank nodes d_flank holds
   const void* desc_owner = nullptr;   // batch whose resident-mode descriptors h_gaps / h_d3 hold
   std::vector<g2s_session*> helpers;  // g2s_session_set_team
+  g2s_session* team_lead = nullptr;   // (a helper) the session whose team it was put in last
+  bool team_sharded_tried = false;    // (g2s_fill_end) the list being run again left the sharded form: the other forms take it
   size_t team_group = 0;
   PinBuf h_gaps;                 // staging for the GapDev upload
   std::vector<PinBuf*> pin_free; // pinned buffers of finished batches (flank text in, node ids out), reused
@@ -1221,7 +1223,8 @@ struct g2s_session {
   hipEvent_t ev_segw = nullptr;  // behind the large variant's launch (timed launches)
   // g2s_fill_begin / g2s_fill_end: up to G2S_MAX_IN_FLIGHT lists in flight, each on this session or a twin of it on the
   // same device (own streams and buffers; created on first use).  The rand() stream is this session's: a list that
-  // ends on a twin borrows it.
+  // ends on a twin borrows it.  (A helper of a team has twins too: a team's list in flight takes the members
+  // themselves or twin c - 1 of every member — three lists, three sets of streams and buffers per GPU.)
   g2s_session* twins[G2S_MAX_IN_FLIGHT - 1] = {};
   // (lists in flight) the generator's state behind the last draw of the list whose phase D3 ran here last, in device
   // memory (D3Work.link), and the event behind the kernel that writes it: the next list's stream starts from it
@@ -1232,7 +1235,10 @@ struct g2s_session {
   struct InFlight { g2s_batch* b = nullptr; g2s_session* on = nullptr; g2s_result* results = nullptr; char* arena = nullptr; size_t cap = 0;
                     const g2s_gap* gaps = nullptr; size_t n = 0; double ms_prepare = 0;
                     bool d3_queued = false;
-                    bool chained = false; };  // its rand() stream continues the older list's on the device
+                    bool chained = false;  // its rand() stream continues the older list's on the device
+                    // a team's list whose first step is queued on every share's device (TeamFlight, with the team's code
+                    // below); `on` is then the lead's session of the set the list runs on
+                    struct TeamFlight* team = nullptr; };
   InFlight inflight[G2S_MAX_IN_FLIGHT];
   int n_inflight = 0;
   // g2s_fill_begin / g2s_fill_end calling the other entry points for a list of their own: those refuse callers
@@ -1256,7 +1262,13 @@ static void d3_pending_drop(g2s_session* s);  // (D3Pending is defined with phas
 namespace {
 // Between g2s_fill_begin and the matching g2s_fill_end the session's pinned and device buffers belong to the lists in
 // flight: every other entry point that would queue work on the session, or move its rand() stream, refuses.
-inline bool lists_in_flight(const g2s_session* s) { return s && s->n_inflight > 0 && s->internal_calls == 0; }
+// A helper's buffers belong to its lead's lists in the same way (a team's list in flight has a share on every member).
+inline bool lists_in_flight(const g2s_session* s) {
+  if (!s || s->internal_calls != 0) return false;
+  if (s->n_inflight > 0) return true;
+  const g2s_session* lead = s->team_lead;
+  return lead && lead->n_inflight > 0 && lead->internal_calls == 0;
+}
 struct InternalCall {
   g2s_session* s;
   explicit InternalCall(g2s_session* s_) : s(s_) { s->internal_calls++; }
@@ -1400,6 +1412,26 @@ extern "C" int g2s_session_create(g2s_graph* g, int device, const g2s_params* p,
   return G2S_OK;
 }
 
+static void team_flight_drop(TeamFlight* f);  // (with the team's code below)
+// Lists begun and never ended: their kernels first — on all three streams of every session that carries one (the
+// rand() stream and the descriptors run on the second, the large variant's early launch on the third; a team's list:
+// on every share's device) — and what was queued for their phase D3 (it points into the batches freed here).
+static void inflight_drop_all(g2s_session* s) {
+  if (s->n_inflight < 1) return;
+  for (int q = 0; q < s->n_inflight; q++) {
+    g2s_session::InFlight& f = s->inflight[q];
+    if (f.team) { team_flight_drop(f.team); f.team = nullptr; continue; }
+    if (g2s_session* on = f.b ? f.on : nullptr) {
+      (void)hipSetDevice(on->device);
+      for (hipStream_t st : {on->stream, on->stream2, on->stream3}) if (st) (void)hipStreamSynchronize(st);
+    }
+  }
+  d3_pending_drop(s);
+  for (g2s_session* t : s->twins) if (t) d3_pending_drop(t);
+  for (int q = 0; q < s->n_inflight; q++) { g2s_batch_free(s->inflight[q].b); s->inflight[q] = g2s_session::InFlight(); }
+  s->n_inflight = 0;
+}
+
 extern "C" void g2s_session_destroy(g2s_session* s) {
   if (!s) return;
   if (s->d2_prof_on && s->d_counter.p) {  // (G2S_D2_PROF: what g2s_d2_* spent where, over the session's lists)
@@ -1433,18 +1465,16 @@ extern "C" void g2s_session_destroy(g2s_session* s) {
           }
       }
   }
-  // lists begun and never ended: their kernels first — on all three streams of every session that carries one (the
-  // rand() stream and the descriptors run on the second, the large variant's early launch on the third) — and what
-  // was queued for their phase D3 (it points into the batches freed below)
-  for (int q = 0; q < s->n_inflight; q++)
-    if (g2s_session* on = s->inflight[q].on) {
-      (void)hipSetDevice(on->device);
-      for (hipStream_t st : {on->stream, on->stream2, on->stream3}) if (st) (void)hipStreamSynchronize(st);
-    }
-  d3_pending_drop(s);
-  for (g2s_session* t : s->twins) if (t) d3_pending_drop(t);
-  for (int q = 0; q < s->n_inflight; q++) g2s_batch_free(s->inflight[q].b);
-  s->n_inflight = 0;
+  // (a helper whose lead still has lists in flight — a caller's error, and this call cannot say so: the lead's lists
+  // have shares on this session or its twins; their kernels are waited for and the lists dropped.  The lead's team
+  // loses the session either way.)
+  if (g2s_session* lead = s->team_lead) {
+    inflight_drop_all(lead);
+    lead->helpers.erase(std::remove(lead->helpers.begin(), lead->helpers.end(), s), lead->helpers.end());
+    s->team_lead = nullptr;
+  }
+  inflight_drop_all(s);
+  for (g2s_session* h : s->helpers) if (h->team_lead == s) h->team_lead = nullptr;
   for (g2s_session*& t : s->twins) if (t) { g2s_session_destroy(t); t = nullptr; }
   (void)hipSetDevice(s->device);
   for (hipStream_t st : {s->stream, s->stream2, s->stream3}) if (st) (void)hipStreamSynchronize(st);
@@ -4228,21 +4258,30 @@ enum { SHARD_NOT_RESIDENT = 1,   // the batch is not one for resident mode (resi
 };
 // step 1: fill kernel, classes, the batch's totals (fewest draws, spread).  The batch is prepared (prepare_group);
 // results: of its first gap; arena: the whole list's, arena_total bytes; what: the text of a failing wait.
-static int shard_fill(g2s_batch* b, g2s_result* results, char* arena, size_t arena_total, ResidentLaunch* rl, uint64_t totals[2],
-                      const char* what) {
+// (in two parts, for a team's lists in flight — g2s_fill_begin / g2s_fill_end: the first queues the kernels and waits
+// for nothing, the second waits for the stream and reads the totals)
+static int shard_fill_queue(g2s_batch* b, g2s_result* results, char* arena, size_t arena_total, ResidentLaunch* rl) {
   g2s_session* s = b->s;
   int rc = resident_launch_fill(b, rl);
   if (rc != G2S_OK) return rc == 1 ? (int)SHARD_NOT_RESIDENT : rc;
   const ResidentList L = resident_list_of(b, b->arena_base, arena_total);
   if (b->arena_base) shift_arena_offsets(s, L.n, b->arena_base);
   rc = resident_d3_launch(s, L, rl->timed, false, results, arena, true, true);
-  if (rc == 1) return SHARD_NOT_D3;
-  if (rc == G2S_OK && hipStreamSynchronize(s->stream) != hipSuccess) rc = fail(G2S_ERR_HIP, what);
-  if (rc != G2S_OK) return rc;
+  return rc == 1 ? (int)SHARD_NOT_D3 : rc;
+}
+static int shard_fill_wait(g2s_batch* b, uint64_t totals[2], const char* what) {
+  g2s_session* s = b->s;
+  if (hipSetDevice(s->device) != hipSuccess) return fail(G2S_ERR_NO_DEVICE, "cannot select device");
+  if (hipStreamSynchronize(s->stream) != hipSuccess) return fail(G2S_ERR_HIP, what);
   const D3Summary* hs = ((D3Pending*)s->d3_pending)->hsum;
   if (hs->status != 0) return SHARD_BEYOND_DEVICE;
   totals[0] = hs->draws_min; totals[1] = hs->draws_spread;
   return G2S_OK;
+}
+static int shard_fill(g2s_batch* b, g2s_result* results, char* arena, size_t arena_total, ResidentLaunch* rl, uint64_t totals[2],
+                      const char* what) {
+  const int rc = shard_fill_queue(b, results, arena, arena_total, rl);
+  return rc != G2S_OK ? rc : shard_fill_wait(b, totals, what);
 }
 // step 2: the stream as far as the batch reaches, the tables, the group function (pinned memory of the session)
 static int shard_tables(g2s_session* s, uint32_t base0, uint32_t R0, const uint32_t* win, const uint32_t** group_fn, const char* what) {
@@ -4510,22 +4549,95 @@ static int team_last_error(const std::vector<int>& rcs, const std::vector<std::s
   for (size_t t = 0; t < rcs.size(); t++) if (rcs[t] != G2S_OK) { rc = rcs[t]; tl_error = errs[t]; }
   return rc;
 }
-static int team_resident_sharded(g2s_session* const* sessions, int nsessions, const g2s_gap* gaps, size_t n, size_t group_size,
-                                 g2s_result* results, char* arena, g2s_timing* timing_out) {
-  g2s_session* lead = sessions[0];
+// The list between its two halves.  The first (team_sharded_queue) prepares every share and queues its step 1 on the
+// share's session, waiting for nothing on the devices; the second (team_sharded_finish) waits for the totals and runs
+// steps 2 and 3.  g2s_team_fill calls them back to back; g2s_fill_begin / g2s_fill_end keep the list in this form while
+// it is in flight — step 1 reads nothing of the rand() stream, so it holds whatever the lists in front of it do.
+struct TeamFlight {
+  std::vector<g2s_session*> on;   // the session of every share: the team's members, or one twin of each
+  const g2s_gap* gaps = nullptr;
+  size_t n = 0, group_size = 0;
+  g2s_result* results = nullptr;
+  char* arena = nullptr;
+  std::vector<size_t> group_arena;
+  std::vector<g2s_batch*> subs;
+  std::vector<ResidentLaunch> rls;
+  std::vector<int> step1;          // per share: G2S_OK (queued), why not (SHARD_*), or an error
+  std::vector<std::string> errs;
+  std::unique_ptr<InTeam> in_team;  // (the sessions know they carry a share, from the queueing to the end)
+  bool through_begin = false, others_in_flight = false;  // (g2s_fill_begin's: what resident_launch_fill reads of them)
+  std::chrono::steady_clock::time_point t_begin;          // what the list's wall times count from
+};
+// is the list one for this form?  (the checks that launch nothing)
+static bool team_sharded_takes(g2s_session* const* sessions, int nsessions, const g2s_gap* gaps, size_t n, size_t group_size,
+                               g2s_result* results, char* arena) {
+  if (group_size == 0 || n == 0) return false;
   const size_t ngroups = (n + group_size - 1) / group_size;
-  if (nsessions < 2 || ngroups != (size_t)nsessions || nsessions > 16) return 1;
-  for (int t = 0; t < nsessions; t++) if (!resident_applicable(sessions[t], n) || sessions[t]->d3_pending) return 1;
-  for (size_t q = 1; q < ngroups; q++) if (gaps[q * group_size].skip_if_prev_right_fuz_gt >= 0) return 1;  // a record cut by a group boundary
-  {  // the kernels write the caller's buffers from every device: page-locked through the ABI (g2s_host_alloc), or not this form
-    void* d = nullptr;
-    if (!device_pointer_of(results, &d) || !device_pointer_of(arena, &d)) return 1;
+  if (nsessions < 2 || ngroups != (size_t)nsessions || nsessions > 16) return false;
+  for (int t = 0; t < nsessions; t++) if (!resident_applicable(sessions[t], n) || sessions[t]->d3_pending) return false;
+  for (size_t q = 1; q < ngroups; q++) if (gaps[q * group_size].skip_if_prev_right_fuz_gt >= 0) return false;  // a record cut by a group boundary
+  // the kernels write the caller's buffers from every device: page-locked through the ABI (g2s_host_alloc), or not this form
+  void* d = nullptr;
+  return device_pointer_of(results, &d) && device_pointer_of(arena, &d);
+}
+// ---- step 1 of every share, queued: fill kernel, classes, totals.  (SHARD_NOT_D3 is not a reason to give the list up
+// here, unlike in g2s_share_begin: the share's session sits the steps out — resident_launch_fill in front of it has the
+// same bounds.)  Returns true when every share's kernels are on its stream.
+static bool team_sharded_queue(g2s_session* lead, TeamFlight& F) {
+  const int nsessions = (int)F.on.size();
+  const size_t ngroups = (size_t)nsessions;
+  F.in_team.reset(new InTeam(F.on.data(), nsessions, true));
+  F.group_arena = group_arena_offsets(lead, F.gaps, F.n, F.group_size);
+  F.subs.assign(ngroups, nullptr);
+  F.rls.assign(ngroups, ResidentLaunch());
+  F.step1.assign(ngroups, G2S_OK);
+  F.errs.assign(ngroups, std::string());
+  auto worker = [&](int t) {
+    g2s_session* s = F.on[(size_t)t];
+    const size_t off = (size_t)t * F.group_size, cnt = std::min(F.group_size, F.n - off);
+    int rc = prepare_group(s, F.gaps + off, cnt, F.arena, F.group_arena[(size_t)t], &F.subs[(size_t)t]);
+    if (rc == G2S_OK) {
+      F.subs[(size_t)t]->through_begin = F.through_begin;
+      F.subs[(size_t)t]->others_in_flight = F.others_in_flight;
+      rc = shard_fill_queue(F.subs[(size_t)t], F.results + off, F.arena, F.group_arena[ngroups], &F.rls[(size_t)t]);
+      if (rc >= 0 && rc != SHARD_NOT_RESIDENT) s->desc_owner = nullptr;  // (its D3Gap offsets are the arena's now)
+    }
+    F.step1[(size_t)t] = rc;
+    if (rc < 0) F.errs[(size_t)t] = tl_error;
+  };
+  team_run(lead, nsessions, worker);
+  for (int rc : F.step1) if (rc != G2S_OK) return false;
+  return true;
+}
+// What the list's kernels wrote is dropped, on every session it ran on (the list goes another way, or nowhere).
+static void team_sharded_abandon(TeamFlight& F) {
+  for (size_t t = 0; t < F.on.size(); t++) {
+    g2s_session* s = F.on[t];
+    const size_t cnt = t < F.subs.size() && F.subs[t] ? F.subs[t]->jobs.size() : 0;
+    if (s->d3_pending) resident_abandon(s, cnt);
+    else if (cnt) {  // (a fill launch, if it got that far, and nothing behind it)
+      (void)hipSetDevice(s->device);
+      for (hipStream_t st : {s->stream, s->stream2, s->stream3}) if (st) (void)hipStreamSynchronize(st);
+    }
   }
-  InTeam in_team(sessions, nsessions, true);
-  const auto t_begin = std::chrono::steady_clock::now();
-  const std::vector<size_t> group_arena = group_arena_offsets(lead, gaps, n, group_size);
-  std::vector<g2s_batch*> subs(ngroups, nullptr);
-  std::vector<ResidentLaunch> rls(ngroups);
+  for (g2s_batch*& b : F.subs) if (b) { g2s_batch_free(b); b = nullptr; }
+  F.in_team.reset();
+}
+static void team_flight_drop(TeamFlight* f) {
+  if (!f) return;
+  team_sharded_abandon(*f);
+  delete f;
+}
+// ---- the wait for step 1, the shares' places in the stream, steps 2 and 3, the sessions' threads meeting twice.
+// lead: the session whose rand() stream the list draws from (F.on may be twins of the team).  Leaves every session
+// without anything queued, the shares' batches freed.
+static int team_sharded_finish(g2s_session* lead, TeamFlight& F, g2s_timing* timing_out) {
+  g2s_session* const* sessions = F.on.data();
+  const int nsessions = (int)F.on.size();
+  const size_t ngroups = (size_t)nsessions, n = F.n, group_size = F.group_size;
+  const auto t_begin = F.t_begin;
+  std::vector<g2s_batch*>& subs = F.subs;
+  std::vector<ResidentLaunch>& rls = F.rls;
   std::vector<int> rcs((size_t)nsessions, G2S_OK);
   std::vector<std::string> errs((size_t)nsessions);
   std::vector<uint64_t> tot_min(ngroups, 0), tot_spread(ngroups, 0);
@@ -4541,19 +4653,18 @@ static int team_resident_sharded(g2s_session* const* sessions, int nsessions, co
     g2s_session* s = sessions[t];
     const size_t off = (size_t)t * group_size, cnt = std::min(group_size, n - off);
     auto failed = [&](int rc) { rcs[(size_t)t] = rc; errs[(size_t)t] = tl_error; give_up.store(2); };
-    // ---- step 1: fill kernel, classes, totals
+    // ---- step 1's totals
     bool mine_ok = false;
     {
-      int rc = prepare_group(s, gaps + off, cnt, arena, group_arena[(size_t)t], &subs[(size_t)t]);
+      int rc = F.step1[(size_t)t];
+      if (rc < 0) tl_error = F.errs[(size_t)t];
       if (rc == G2S_OK) {
         uint64_t tot[2] = {0, 0};
-        rc = shard_fill(subs[(size_t)t], results + off, arena, group_arena[ngroups], &rls[(size_t)t], tot, "sharded list, step 1");
-        if (rc >= 0 && rc != SHARD_NOT_RESIDENT) s->desc_owner = nullptr;  // (its D3Gap offsets are the arena's now)
+        rc = shard_fill_wait(subs[(size_t)t], tot, "sharded list, step 1");
         if (rc == G2S_OK) { tot_min[(size_t)t] = tot[0]; tot_spread[(size_t)t] = tot[1]; mine_ok = true; }
-        // (beyond the device: the host path's business.  SHARD_NOT_D3 is not reported here, unlike in g2s_share_begin:
-        // the group's session sits the steps out — resident_launch_fill in front of it has the same bounds)
-        else if (rc == SHARD_NOT_RESIDENT || rc == SHARD_BEYOND_DEVICE) give_up.store(1);
       }
+      // (beyond the device: the host path's business)
+      if (rc == SHARD_NOT_RESIDENT || rc == SHARD_BEYOND_DEVICE) give_up.store(1);
       if (rc < 0) failed(rc);
     }
     bar.wait();
@@ -4618,7 +4729,8 @@ static int team_resident_sharded(g2s_session* const* sessions, int nsessions, co
     total.team_d3_sharded = 1;
     total.resident_launches = 1;  // (one list, finished on the devices)
   }
-  for (g2s_batch* b : subs) if (b) g2s_batch_free(b);
+  for (g2s_batch*& b : subs) if (b) { g2s_batch_free(b); b = nullptr; }
+  F.in_team.reset();
   if (rc != G2S_OK) return rc;
   if (fell_back) return 1;
   total.ms_total = ms_since(t_begin);
@@ -4626,10 +4738,20 @@ static int team_resident_sharded(g2s_session* const* sessions, int nsessions, co
   lead->last_timing = total;
   return G2S_OK;
 }
+static int team_resident_sharded(g2s_session* const* sessions, int nsessions, const g2s_gap* gaps, size_t n, size_t group_size,
+                                 g2s_result* results, char* arena, g2s_timing* timing_out) {
+  if (!team_sharded_takes(sessions, nsessions, gaps, n, group_size, results, arena)) return 1;
+  TeamFlight F;
+  F.on.assign(sessions, sessions + nsessions);
+  F.gaps = gaps; F.n = n; F.group_size = group_size; F.results = results; F.arena = arena;
+  F.t_begin = std::chrono::steady_clock::now();
+  (void)team_sharded_queue(sessions[0], F);  // (a share that is not for this form: the second half sees it and gives the list up)
+  return team_sharded_finish(sessions[0], F, timing_out);
+}
 
 static int team_resident(g2s_session* const* sessions, int nsessions, const g2s_gap* gaps, size_t n, size_t group_size,
                          g2s_result* results, char* arena, g2s_timing* timing_out) {
-  {  // one group per session: the groups stay where they were filled (phase D3 sharded)
+  if (!sessions[0]->team_sharded_tried) {  // one group per session: the groups stay where they were filled (phase D3 sharded)
     const int rs = team_resident_sharded(sessions, nsessions, gaps, n, group_size, results, arena, timing_out);
     if (rs != 1) return rs;
   }
@@ -5016,12 +5138,71 @@ int inflight_settle(g2s_session* s) {
   }
   return G2S_OK;
 }
+// Set c of the sessions lists in flight take turns on: 0 is the session itself (and, for a team's list, its helpers),
+// c > 0 the twin c - 1 of it (and of every helper).  A list on one session holds the lead's session of a set, a team's
+// list the whole set; a list that g2s_fill_end will hand to g2s_fill_batch (no kernels queued) runs on set 0 when its
+// turn comes, so nothing begun behind it goes there.
+bool inflight_set_busy(const g2s_session* s, int c) {
+  const g2s_session* cand = c == 0 ? s : s->twins[c - 1];
+  for (int i = 0; i < s->n_inflight; i++) {
+    const g2s_session::InFlight& f = s->inflight[i];
+    if ((f.b || f.team) ? (cand != nullptr && f.on == cand) : c == 0) return true;
+  }
+  return false;
+}
+// G2S_TEAM_IN_FLIGHT=0 (measurements, tests; read per call): a team's lists wait for g2s_fill_end with all their steps
+bool team_in_flight_enabled() {
+  const char* env = GENV("G2S_TEAM_IN_FLIGHT");
+  return !env || atoi(env) != 0;
+}
 }  // namespace
+
+// A team's list at g2s_fill_begin: step 1 of every share — preparation, look-ups, fill kernel, classes and totals —
+// queued on a free set of the members' sessions when the list is one the sharded form takes.  Returns G2S_OK with
+// *out set (queued) or null (the list waits for g2s_fill_end as it is), or an error.
+static int team_begin(g2s_session* s, const g2s_gap* gaps, size_t n, size_t group, g2s_result* results, char* arena, size_t arena_cap,
+                      TeamFlight** out) {
+  *out = nullptr;
+  // (a list g2s_team_fill would cut into slices is not one list to the sharded form: 20 480 gaps is phase D3's bound)
+  if (!team_in_flight_enabled() || s->team_group != G2S_GROUP_PER_SESSION || n > 20480) return G2S_OK;
+  if (arena_cap < g2s_team_arena_bytes(s, gaps, n)) return G2S_OK;  // (g2s_fill_end says so, as it does now)
+  std::vector<g2s_session*> members{s};
+  members.insert(members.end(), s->helpers.begin(), s->helpers.end());
+  const int ns = (int)members.size();
+  int c = 0;
+  while (c < G2S_MAX_IN_FLIGHT && inflight_set_busy(s, c)) c++;
+  if (c == G2S_MAX_IN_FLIGHT) return G2S_OK;
+  std::unique_ptr<TeamFlight> F(new TeamFlight);
+  for (g2s_session* m : members) {
+    if (c > 0 && !m->twins[c - 1]) {
+      const int rc = g2s_session_create(m->graph, m->device, &m->params, &m->twins[c - 1]);
+      if (rc != G2S_OK) return rc;
+    }
+    F->on.push_back(c == 0 ? m : m->twins[c - 1]);
+  }
+  if (!team_sharded_takes(F->on.data(), ns, gaps, n, group, results, arena)) return G2S_OK;
+  F->gaps = gaps; F->n = n; F->group_size = group; F->results = results; F->arena = arena;
+  F->through_begin = true;
+  F->others_in_flight = s->n_inflight > 0;
+  F->t_begin = std::chrono::steady_clock::now();
+  if (!team_sharded_queue(s, *F)) {  // (a share that is not for the form: what was queued is dropped, the list waits as it is)
+    int err = G2S_OK;
+    std::string text;
+    for (size_t t = 0; t < F->step1.size(); t++) if (F->step1[t] < 0) { err = F->step1[t]; text = F->errs[t]; }
+    team_sharded_abandon(*F);
+    if (err != G2S_OK) tl_error = text;
+    return err;
+  }
+  *out = F.release();
+  return G2S_OK;
+}
 
 extern "C" int g2s_fill_begin(g2s_session* s, const g2s_gap* gaps, size_t n, g2s_result* results, char* fill_arena, size_t arena_cap) {
   g2s_env_sync();
   if (!s || (!gaps && n) || (!results && n)) return fail(G2S_ERR_ARG, "g2s_fill_begin: bad argument");
   if (s->n_inflight >= G2S_MAX_IN_FLIGHT) return fail(G2S_ERR_ARG, "g2s_fill_begin: G2S_MAX_IN_FLIGHT lists are in flight already (g2s_fill_end first)");
+  if (s->team_lead && s->team_lead->n_inflight > 0)  // (a helper: its buffers carry shares of its lead's lists)
+    return fail(G2S_ERR_STATE, "g2s_fill_begin: lists are in flight on this session's lead (g2s_fill_end them first)");
   InternalCall own(s);
   g2s_session::InFlight f;
   f.results = results; f.arena = fill_arena; f.cap = arena_cap; f.gaps = gaps; f.n = n;
@@ -5031,9 +5212,7 @@ extern "C" int g2s_fill_begin(g2s_session* s, const g2s_gap* gaps, size_t n, g2s
     g2s_session* on = nullptr;
     for (int c = 0; c < G2S_MAX_IN_FLIGHT && !on; c++) {
       g2s_session* cand = c == 0 ? s : s->twins[c - 1];
-      bool busy = false;
-      for (int i = 0; i < s->n_inflight; i++) busy = busy || (s->inflight[i].b ? s->inflight[i].on == cand && cand != nullptr : c == 0);
-      if (busy) continue;
+      if (inflight_set_busy(s, c)) continue;
       if (!cand) {
         const int rc = g2s_session_create(s->graph, s->device, &s->params, &s->twins[c - 1]);
         if (rc != G2S_OK) return rc;
@@ -5056,12 +5235,20 @@ extern "C" int g2s_fill_begin(g2s_session* s, const g2s_gap* gaps, size_t n, g2s
     rc = resident_launch_fill(f.b, &rl, results, fill_arena);  // (1: not a list for resident mode — g2s_fill_end runs it on the host path)
     if (rc < 0) { g2s_batch_free(f.b); return rc; }
     if (rc == G2S_OK) { f.b->pre_launched = true; f.b->pre = rl; }
-  }  // (a list for the team pipeline, or an empty one: g2s_fill_end calls g2s_fill_batch)
+  } else if (n > group && !s->helpers.empty()) {
+    // a list for the team: one share per session, step 1 queued on every share's device now (the steps that place the
+    // shares in the rand() stream follow in g2s_fill_end, when every list in front has drawn)
+    const auto t0 = std::chrono::steady_clock::now();
+    const int rc = team_begin(s, gaps, n, group, results, fill_arena, arena_cap, &f.team);
+    if (rc != G2S_OK) return rc;
+    if (f.team) { f.on = f.team->on[0]; f.ms_prepare = ms_since(t0); }
+  }  // (otherwise — a list for the group pipeline, one the sharded form does not take, an empty one: g2s_fill_end calls g2s_fill_batch)
   s->inflight[s->n_inflight++] = f;
   s->begun++;
   const int rs = inflight_settle(s);  // (phase D3 behind the fill kernel at once, where that can be)
   if (rs < 0) {  // (the list is not in flight then)
     s->n_inflight--;
+    team_flight_drop(f.team);
     if (f.b) { if (f.on->d3_pending && f.b->d3_queued) ((D3Pending*)f.on->d3_pending)->discard = true; g2s_batch_free(f.b); }
     s->inflight[s->n_inflight] = g2s_session::InFlight();
     return rs;
@@ -5078,7 +5265,31 @@ extern "C" int g2s_fill_end(g2s_session* s) {
   s->n_inflight--;
   int rc;
   bool on_device = false;
-  if (!f.b) rc = g2s_fill_batch(s, f.gaps, f.n, f.results, f.arena, f.cap);
+  if (f.team) {
+    // a team's list whose step 1 is queued: the wait for its totals, then steps 2 and 3 on the sessions it ran on —
+    // the generator's window is taken now, every list in front having drawn
+    std::unique_ptr<TeamFlight> F(f.team);
+    F->t_begin = std::chrono::steady_clock::now();
+    rc = team_sharded_finish(s, *F, nullptr);
+    if (rc == G2S_OK) s->last_timing.ms_prepare = f.ms_prepare;  // (the time spent inside g2s_fill_begin)
+    if (rc == 1) {
+      // Not a list for the form after all (a gap beyond the device, tables beyond the budget, a share that fell back):
+      // what its kernels wrote has been dropped, and the list runs as g2s_fill_batch would run it behind the sharded
+      // form — gathered on the lead, or on the host path — on the sessions it was queued on (the team's own may carry
+      // a younger list by now), from the lead's generator.  The lists behind it keep their step 1.
+      g2s_session* on = F->on[0];
+      g2s_timing tm;
+      memset(&tm, 0, sizeof tm);
+      if (on != s) on->rcache.swap(s->rcache);
+      on->team_sharded_tried = true;
+      rc = g2s_team_fill(F->on.data(), (int)F->on.size(), f.gaps, f.n, F->group_size, f.results, f.arena, f.cap, &tm);
+      on->team_sharded_tried = false;
+      if (on != s) on->rcache.swap(s->rcache);
+      tm.resident_fallbacks++;
+      tm.ms_prepare += f.ms_prepare;
+      s->last_timing = tm;
+    }
+  } else if (!f.b) rc = g2s_fill_batch(s, f.gaps, f.n, f.results, f.arena, f.cap);
   else {
     g2s_session* on = f.on;
     if (on != s) on->rcache.swap(s->rcache);  // the one rand() stream (:178), wherever the list ends
@@ -5103,6 +5314,14 @@ extern "C" int g2s_fill_end(g2s_session* s) {
   return rc;
 }
 extern "C" int g2s_fill_in_flight(const g2s_session* s) { return s ? s->n_inflight : 0; }
+extern "C" int g2s_fill_in_flight_launched(const g2s_session* s) {
+  int launched = 0;
+  for (int i = 0; s && i < s->n_inflight; i++) {
+    const g2s_session::InFlight& f = s->inflight[i];
+    if (f.team || (f.b && (f.b->pre_launched || f.b->d3_queued))) launched++;
+  }
+  return launched;
+}
 
 // ---- one list over several processes, a GPU and a share each (include/g2s.h): the three steps of a sharded list
 // (shard_fill, shard_tables, shard_trace: the ones team_resident_sharded's threads take) with the exchanges between
@@ -5198,6 +5417,18 @@ extern "C" int g2s_session_set_team(g2s_session* lead, g2s_session* const* helpe
     if (!helpers[i] || helpers[i] == lead || helpers[i]->graph != lead->graph)
       return fail(G2S_ERR_ARG, "g2s_session_set_team: helpers must be other sessions on the same graph");
   REFUSE_IN_FLIGHT(lead, "g2s_session_set_team");
+  // (a helper knows its lead: while the lead has lists in flight the helper refuses what the lead refuses, and a
+  // session that goes tells the team it was in)
+  for (g2s_session* h : lead->helpers) if (h->team_lead == lead) h->team_lead = nullptr;
+  for (int i = 0; i < nhelpers; i++) {
+    g2s_session* h = helpers[i];
+    if (h->team_lead && h->team_lead != lead) {
+      REFUSE_IN_FLIGHT(h, "g2s_session_set_team");  // (its present lead's lists have shares on it)
+      std::vector<g2s_session*>& was = h->team_lead->helpers;
+      was.erase(std::remove(was.begin(), was.end(), h), was.end());
+    }
+  }
+  for (int i = 0; i < nhelpers; i++) helpers[i]->team_lead = lead;
   lead->helpers.assign(helpers, helpers + nhelpers);
   lead->team_group = group_size;
   return G2S_OK;

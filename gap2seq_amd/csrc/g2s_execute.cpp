@@ -264,7 +264,8 @@ extern "C" int g2s_execute_scaffolds_stream(g2s_session* s, const g2s_run_opts* 
     c->arena_bytes = c->jobs.empty() ? 0 : g2s_team_arena_bytes(s, c->jobs.data(), c->jobs.size());
     c->arena = (char*)arena_buf[q].get(std::max<size_t>(1, c->arena_bytes));
     if (c->jobs.empty()) return G2S_OK;
-    // (long lists go through the session's team in g2s_fill_end: g2s_session_set_team)
+    // (long lists go through the session's team — g2s_session_set_team: every share's fill kernel queued here, the
+    // steps that place the shares in the rand() stream in g2s_fill_end)
     const int rc = g2s_fill_begin(s, c->jobs.data(), c->jobs.size(), c->results, c->arena, c->arena_bytes);
     c->begun = rc == G2S_OK;
     return rc;

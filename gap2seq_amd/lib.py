@@ -110,6 +110,7 @@ _SIGS = {
     "g2s_fill_begin": (C.c_int, [_VP, C.POINTER(g2s_gap), C.c_size_t, C.POINTER(g2s_result), C.c_void_p, C.c_size_t]),
     "g2s_fill_end": (C.c_int, [_VP]),
     "g2s_fill_in_flight": (C.c_int, [_VP]),
+    "g2s_fill_in_flight_launched": (C.c_int, [_VP]),
     "g2s_share_begin": (C.c_int, [_VP, C.POINTER(g2s_gap), C.c_size_t, C.POINTER(g2s_result), C.c_void_p, C.c_size_t,
                                   C.POINTER(C.c_uint64)]),
     "g2s_share_tables": (C.c_int, [_VP, C.c_uint64, C.c_uint64, C.POINTER(C.POINTER(C.c_uint32))]),
@@ -1038,6 +1039,15 @@ class Session:
                     c["rbuf"].free()
                     c["arena"].free()
         return out, t
+
+    def in_flight(self):
+        """g2s_fill_in_flight: lists begun and not ended."""
+        return load_library().g2s_fill_in_flight(self.h)
+
+    def in_flight_launched(self):
+        """g2s_fill_in_flight_launched: how many of the lists in flight have their fill kernels queued on the device(s)
+        (a team's list: on every share's device)."""
+        return load_library().g2s_fill_in_flight_launched(self.h)
 
     def fill_batch_onecall(self, gaps, pinned=False, want_timing=False):
         """g2s_fill_batch (prepare + run + free in one ABI call; lists longer than the group size

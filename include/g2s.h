@@ -326,11 +326,26 @@ typedef struct g2s_result {
  * While lists are in flight the session's buffers and its rand() stream belong to them: g2s_fill_batch,
  * g2s_batch_prepare, g2s_batch_run, g2s_team_fill (with this session in the team), g2s_session_set_team,
  * g2s_session_srand and g2s_session_skip_draws return G2S_ERR_STATE and do nothing until every list has been ended
- * (ABI 5; g2s_session_destroy may be called at any time: it waits for the lists' kernels and drops them). */
+ * (ABI 5; g2s_session_destroy may be called at any time: it waits for the lists' kernels and drops them).
+ *
+ * A session with a team (g2s_session_set_team, G2S_GROUP_PER_SESSION): a list long enough for one share per session,
+ * in g2s_host_alloc buffers, no record cut by a share boundary, has the first step of every share — preparation,
+ * look-ups, fill kernel, classes and totals — queued on that share's device by g2s_fill_begin(), on the member's
+ * session or on a twin of it on the same device (three lists in flight: three sets of streams and buffers per GPU).
+ * That step reads nothing of the rand() stream.  g2s_fill_end() waits for the shares' totals, places the shares in the
+ * stream from where the lead's generator then stands, and runs the tables and the tracebacks on the same sessions:
+ * they overlap the first step of the lists begun behind.  A list that then turns out not to be one for the devices is
+ * run by g2s_fill_end() as g2s_fill_batch() would run it; the lists behind it keep what they queued.  Any other list of
+ * a team (pageable buffers, a record across a share boundary, G2S_TEAM_IN_FLIGHT=0) waits for g2s_fill_end() with all
+ * of its work, on the team's own sessions, which nothing begun behind it uses.  While the lead has lists in flight its
+ * helpers refuse what the lead refuses (their buffers carry shares); the lead is to be destroyed before its helpers, or
+ * its lists ended first — a helper destroyed under its lead's lists waits for their kernels and drops them all.
+ * g2s_fill_in_flight_launched(): how many of the lists in flight have their fill kernels queued on the device(s). */
 #define G2S_MAX_IN_FLIGHT 3
 int g2s_fill_begin(g2s_session* s, const g2s_gap* gaps, size_t n, g2s_result* results, char* fill_arena, size_t arena_cap);
 int g2s_fill_end(g2s_session* s);
 int g2s_fill_in_flight(const g2s_session* s);
+int g2s_fill_in_flight_launched(const g2s_session* s);
 
 /* The reference's line for a gap flagged G2S_GAP_BACKTRACE_FAIL (Gap2Seq.cpp:1494): "Unable to backtrace! <currentD2>
  * <currentD> <toString(reachedTarget)>", without the newline; the k-mer is right[right_fuz .. right_fuz + k) in upper
