@@ -3,7 +3,7 @@
 // read followed by one 'N') and, behind it, the reads' starts in it as 64-bit offsets (n_reads + 1 entries: read r lies
 // at start[r] = base_off[r] + r, base_off[r + 1] - base_off[r] characters long).  Host-held: the same text in host
 // memory.  The view's arrays are the handle's either way; its bases and names are NULL (names are never kept: the
-// callers want their lengths alone).  Made by readfilter_gaps.cpp, read by g2s_api.hip (g2s_graph_build_dpool_reach).
+// callers want their lengths alone).  Made by readfilter_gaps.cpp, read by api_graph.hip (g2s_graph_build_dpool_reach).
 #pragma once
 #include <cstdint>
 #include <string>

@@ -27,55 +27,27 @@
 
 #include "../../include/g2s.h"
 #include "../../include/g2s_test.h"
+#include "api_internal.h"
 #include "envcache.hpp"
 #include "d2_device.h"
 #include "d3_device.h"
 #include "dbg.hpp"
-#include "device_pool.h"
-#include "fastx.hpp"
 #include "fill_device.h"
 #include "fill_launch.h"
 #include "fill_seg.h"
 #include "flank_lookup.h"
 #include "glibc_rand.hpp"
-#include "pass_plan.hpp"
 #include "post.hpp"
-#include "bam_reads.h"
-#include "reads_text.h"
-#include "readfilter_gaps.hpp"
 #include "seg_tables.h"
 
 using namespace g2s;
+using namespace g2s::api;
 
 // ---------------------------------------------------------------------------
 // errors
 // ---------------------------------------------------------------------------
 static thread_local std::string tl_error;
-static int fail(int code, const std::string& msg) { tl_error = msg; return code; }
-#define HIP_TRY(expr)                                                                         \
-  do {                                                                                        \
-    hipError_t e_ = (expr);                                                                   \
-    if (e_ != hipSuccess)                                                                     \
-      return fail(G2S_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));            \
-  } while (0)
-// (resident mode: kernels of the list may be in flight on the session's streams and write the caller's pinned buffers
-// — an error return waits for them first)
-#define HIP_TRY_S(expr)                                                                       \
-  do {                                                                                        \
-    hipError_t e_ = (expr);                                                                   \
-    if (e_ != hipSuccess) {                                                                   \
-      (void)hipStreamSynchronize(s->stream);                                                  \
-      (void)hipStreamSynchronize(s->stream2);                                                 \
-      if (s->stream3) (void)hipStreamSynchronize(s->stream3);                                 \
-      return fail(G2S_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));            \
-    }                                                                                         \
-  } while (0)
-
-// wall time in milliseconds: between two time points, and from one until now
-using TimePoint = std::chrono::steady_clock::time_point;
-static inline double ms_between(TimePoint a, TimePoint b) { return std::chrono::duration<double, std::milli>(b - a).count(); }
-static inline double ms_since(TimePoint t0) { return ms_between(t0, std::chrono::steady_clock::now()); }
-
+int api::fail(int code, const std::string& msg) { tl_error = msg; return code; }
 // The sum of two g2s_timing: every figure that counts gaps, launches, lists, bytes or the milliseconds of kernels and
 // host phases.  Not ms_total (a wall time: the caller measures its own), team_sessions and team_d3_sharded (what a
 // call was, not how much), the per-session team_ms_* (a team's own: the slices of g2s_team_fill add them), host_us
@@ -128,703 +100,6 @@ extern "C" int g2s_device_count(void) {
     if (hipGetDeviceProperties(&prop, d) == hipSuccess && strncmp(prop.gcnArchName, "gfx950", 6) == 0) ok++;
   }
   return ok;
-}
-
-// ---------------------------------------------------------------------------
-// graph
-// ---------------------------------------------------------------------------
-struct g2s_graph {
-  Graph* g = nullptr;
-};
-// what a builder of dbg.hpp made, handed back as a handle: null is the builder's refusal, with its reason in err
-static int wrap_graph(Graph* g, const std::string& err, g2s_graph** out) {
-  if (!g) return fail(G2S_ERR_ARG, err);
-  *out = new g2s_graph();
-  (*out)->g = g;
-  return G2S_OK;
-}
-// the callers' sequences as (pointer, length) pairs; lens == nullptr: C strings
-static std::vector<std::pair<const char*, uint64_t>> seq_pairs(const char* const* seqs, const uint64_t* lens, uint64_t n) {
-  std::vector<std::pair<const char*, uint64_t>> v;
-  v.reserve((size_t)n);
-  for (uint64_t i = 0; i < n; i++) v.emplace_back(seqs[i], lens ? lens[i] : (uint64_t)strlen(seqs[i]));
-  return v;
-}
-
-static int build_seqs_of(const char* const* seqs, const uint64_t* lens, int nseqs, int k, int solid, int nthreads,
-                         const GraphReach* reach, g2s_graph** out) {
-  if (!seqs || !out || nseqs < 0) return fail(G2S_ERR_ARG, "g2s_graph_build_seqs: bad argument");
-  std::string err;
-  return wrap_graph(graph_build(seq_pairs(seqs, lens, (uint64_t)nseqs), k, solid, nthreads, &err, reach), err, out);
-}
-extern "C" int g2s_graph_build_seqs(const char* const* seqs, const uint64_t* lens, int nseqs, int k, int solid,
-                                    int nthreads, g2s_graph** out) {
-  return build_seqs_of(seqs, lens, nseqs, k, solid, nthreads, nullptr, out);
-}
-
-// ---- single graphs bounded by reach records (include/g2s.h: g2s_graph_build_seqs_reach) --------------------
-// A reach record's seeds: the flank k-mers the fill looks up (g2s_batch_prepare: the rule must match it), appended to
-// *out.  False, and nothing appended, for a gap the fill rejects.
-static bool flank_seeds(const g2s_gap& in, int k, std::vector<const char*>* out) {
-  if (!in.left || !in.right || in.lmf < 0 || in.rmf < 0 || in.gap_len < 0 || in.left_len < k + in.lmf || in.right_len < k + in.rmf) return false;
-  for (int x = 0; x <= in.lmf; x++) out->push_back(in.left + x);
-  for (int x = 0; x <= in.rmf; x++) out->push_back(in.right + (in.right_len - k - x));
-  for (int x = 0; x <= in.rmf; x++) out->push_back(in.right + x);
-  return true;
-}
-// the records' seeds, one entry a seed with its record's radius
-static int graph_reach_of(const char* name, int k, const g2s_gap* reach_gap, const int32_t* reach_radius, uint64_t nreach,
-                          GraphReach* reach) {
-  if (nreach && (!reach_gap || !reach_radius)) return fail(G2S_ERR_ARG, std::string(name) + ": reach_gap and reach_radius go together");
-  if (k < 1 || k > kMaxK) return fail(G2S_ERR_ARG, "k must be in [1," + std::to_string(kMaxK) + "]");  // (the seeds read k characters)
-  for (uint64_t r = 0; r < nreach; r++)
-    if (reach_radius[r] < 0) return fail(G2S_ERR_ARG, std::string(name) + ": negative radius in record " + std::to_string(r));
-  reach->records = nreach;
-  for (uint64_t r = 0; r < nreach; r++)
-    if (flank_seeds(reach_gap[r], k, &reach->seed)) reach->radius.resize(reach->seed.size(), reach_radius[r]);
-  return G2S_OK;
-}
-// G2S_REACH_AUTO resolved: G2S_BUILD_REACH=1|0 overrides it; -1 for a mode that is none of the three
-static int reach_mode_of(int mode) {
-  if (mode != G2S_REACH_AUTO && mode != G2S_REACH_ALWAYS && mode != G2S_REACH_NEVER) return -1;
-  const char* s = getenv("G2S_BUILD_REACH");
-  if (mode == G2S_REACH_AUTO && s && *s) return strcmp(s, "0") != 0 ? G2S_REACH_ALWAYS : G2S_REACH_NEVER;
-  return mode;
-}
-// plain(reach) is the build: with nullptr today's path.  AUTO runs that first and starts over on the cap error alone.
-template <class Build>
-static int build_with_reach(const char* name, int k, const g2s_gap* reach_gap, const int32_t* reach_radius, uint64_t nreach, int mode,
-                            g2s_graph** out, Build&& build) {
-  if (!out) return fail(G2S_ERR_ARG, std::string(name) + ": bad argument");
-  mode = reach_mode_of(mode);
-  if (mode < 0) return fail(G2S_ERR_ARG, std::string(name) + ": unknown mode");
-  if (!reach_gap && !reach_radius) return build(nullptr);  // (no records: the plain call)
-  GraphReach reach;
-  const int rc = graph_reach_of(name, k, reach_gap, reach_radius, nreach, &reach);
-  if (rc != G2S_OK) return rc;
-  if (mode == G2S_REACH_NEVER) return build(nullptr);
-  if (mode == G2S_REACH_AUTO) {
-    const int plain = build(nullptr);
-    if (plain == G2S_OK || tl_error != kTooManyKmers) return plain;
-    if (getenv("G2S_DEBUG")) fprintf(stderr, "[g2s] graph build: over the cap, starting over bounded by %llu reach records\n", (unsigned long long)nreach);
-  }
-  return build(&reach);
-}
-extern "C" int g2s_graph_build_seqs_reach(const char* const* seqs, const uint64_t* lens, int nseqs, int k, int solid, int nthreads,
-                                          const g2s_gap* reach_gap, const int32_t* reach_radius, uint64_t nreach, int mode,
-                                          g2s_graph** out) {
-  return build_with_reach("g2s_graph_build_seqs_reach", k, reach_gap, reach_radius, nreach, mode, out, [&](const GraphReach* reach) {
-    return build_seqs_of(seqs, lens, nseqs, k, solid, nthreads, reach, out);
-  });
-}
-extern "C" int g2s_graph_bounded(const g2s_graph* g) { return g && g->g->bounded ? 1 : 0; }
-// TEST HOOK (include/g2s_test.h)
-extern "C" int g2s_test_last_graph_reach(uint64_t* records, uint64_t* seeds, uint64_t* seeds_in_full, uint64_t* full_kmers,
-                                         uint64_t* kept_kmers, uint32_t* levels, uint32_t* passes, uint32_t* regrowths, int* on_device,
-                                         double* ms_search) {
-  const GraphReachInfo info = last_graph_reach();
-  if (ms_search) *ms_search = info.ms_search;
-  if (records) *records = info.records;
-  if (seeds) *seeds = info.seeds;
-  if (seeds_in_full) *seeds_in_full = info.seeds_in_full;
-  if (full_kmers) *full_kmers = info.full_kmers;
-  if (kept_kmers) *kept_kmers = info.kept_kmers;
-  if (levels) *levels = info.levels;
-  if (passes) *passes = info.passes;
-  if (regrowths) *regrowths = info.regrowths;
-  if (on_device) *on_device = info.on_device;
-  return G2S_OK;
-}
-
-extern "C" int g2s_graph_build_sets(const char* const* seqs, const uint64_t* lens, const uint32_t* seq_set, int nseqs,
-                                    uint32_t nsets, int k, int solid, int nthreads, g2s_graph** out) {
-  if ((!seqs && nseqs) || (!seq_set && nseqs) || !out || nseqs < 0 || nsets == 0) return fail(G2S_ERR_ARG, "g2s_graph_build_sets: bad argument");
-  for (int i = 0; i < nseqs; i++)
-    if (seq_set[i] >= nsets) return fail(G2S_ERR_ARG, "g2s_graph_build_sets: set id out of range");
-  if (nsets == 1) return g2s_graph_build_seqs(seqs, lens, nseqs, k, solid, nthreads, out);  // an ordinary graph
-  std::string err;
-  Graph* g = graph_build_sets(seq_pairs(seqs, lens, (uint64_t)nseqs), std::vector<uint32_t>(seq_set, seq_set + nseqs), nsets, k, solid,
-                              nthreads, &err);
-  return wrap_graph(g, err, out);
-}
-static int build_pool_reach_of(const PoolSets& ps, int k, int solid, int nthreads, const g2s_gap* reach_gap,
-                               const int32_t* reach_radius, g2s_graph** out);
-// the pooled builds' arguments, checked and as a PoolSets over `v`
-static int pool_sets_of(const char* name, const char* const* seqs, const uint64_t* lens, uint64_t nseqs, const uint64_t* set_begin,
-                        const uint32_t* set_seq, const uint32_t* shared_seq, uint64_t nshared, const uint8_t* set_shared,
-                        uint32_t nsets, g2s_graph** out, std::vector<std::pair<const char*, uint64_t>>* v, PoolSets* ps) {
-  if ((!seqs && nseqs && v->size() != nseqs) || !set_begin || !out || nsets == 0 || nseqs >= (1ull << 32) || (!shared_seq && nshared))
-    return fail(G2S_ERR_ARG, std::string(name) + ": bad argument");
-  for (uint32_t s = 0; s < nsets; s++)
-    if (set_begin[s + 1] < set_begin[s]) return fail(G2S_ERR_ARG, std::string(name) + ": set_begin decreases");
-  if (!set_seq && set_begin[nsets] > set_begin[0]) return fail(G2S_ERR_ARG, std::string(name) + ": bad argument");
-  // (nullptr with sequences: g2s_graph_build_dpool_reach, which has filled `v` from its pools)
-  if (seqs) *v = seq_pairs(seqs, lens, nseqs);
-  ps->seqs = v;
-  ps->set_begin = set_begin;
-  ps->set_seq = set_seq;
-  ps->shared_seq = shared_seq;
-  ps->nshared = nshared;
-  ps->set_shared = set_shared;
-  ps->nsets = nsets;
-  return G2S_OK;
-}
-extern "C" int g2s_graph_build_pool(const char* const* seqs, const uint64_t* lens, uint64_t nseqs, const uint64_t* set_begin,
-                                    const uint32_t* set_seq, const uint32_t* shared_seq, uint64_t nshared, const uint8_t* set_shared,
-                                    uint32_t nsets, int k, int solid, int nthreads, g2s_graph** out) {
-  std::vector<std::pair<const char*, uint64_t>> v;
-  PoolSets ps;
-  const int rc = pool_sets_of("g2s_graph_build_pool", seqs, lens, nseqs, set_begin, set_seq, shared_seq, nshared, set_shared, nsets, out, &v, &ps);
-  if (rc != G2S_OK) return rc;
-  std::string err;
-  return wrap_graph(graph_build_pool(ps, k, solid, nthreads, &err), err, out);
-}
-extern "C" int g2s_graph_build_pool_reach(const char* const* seqs, const uint64_t* lens, uint64_t nseqs, const uint64_t* set_begin,
-                                          const uint32_t* set_seq, const uint32_t* shared_seq, uint64_t nshared,
-                                          const uint8_t* set_shared, uint32_t nsets, int k, int solid, int nthreads,
-                                          const g2s_gap* reach_gap, const int32_t* reach_radius, g2s_graph** out) {
-  if ((reach_gap == nullptr) != (reach_radius == nullptr)) return fail(G2S_ERR_ARG, "g2s_graph_build_pool_reach: reach_gap and reach_radius go together");
-  if (!reach_radius) return g2s_graph_build_pool(seqs, lens, nseqs, set_begin, set_seq, shared_seq, nshared, set_shared, nsets, k, solid, nthreads, out);
-  std::vector<std::pair<const char*, uint64_t>> v;
-  PoolSets ps;
-  const int rc = pool_sets_of("g2s_graph_build_pool_reach", seqs, lens, nseqs, set_begin, set_seq, shared_seq, nshared, set_shared, nsets, out, &v, &ps);
-  if (rc != G2S_OK) return rc;
-  return build_pool_reach_of(ps, k, solid, nthreads, reach_gap, reach_radius, out);
-}
-// the pooled build with reach records over a checked PoolSets: the host-pointer entry and the device-pool entry alike
-static int build_pool_reach_of(const PoolSets& ps, int k, int solid, int nthreads, const g2s_gap* reach_gap,
-                               const int32_t* reach_radius, g2s_graph** out) {
-  const uint32_t nsets = ps.nsets;
-  if (k < 1 || k > kMaxK) return fail(G2S_ERR_ARG, "k must be in [1," + std::to_string(kMaxK) + "]");  // (the seeds below read k characters)
-  PoolReach reach;
-  reach.radius.assign(reach_radius, reach_radius + nsets);
-  reach.seed_begin.assign(1, 0);
-  for (uint32_t s = 0; s < nsets; s++) {
-    if (reach_radius[s] >= 0) flank_seeds(reach_gap[s], k, &reach.seed);  // (none for the whole set, or a gap the fill rejects)
-    reach.seed_begin.push_back(reach.seed.size());
-  }
-  std::string err;
-  return wrap_graph(graph_build_pool_reach(ps, reach, k, solid, nthreads, &err), err, out);
-}
-// The pooled build over pools the read filter left where it made them (device_pool.h).  A pool held on the build's device
-// hands its reads over as null pointers with a PoolDeviceText (dbg_gpu.hip gathers them device to device); every other
-// pool hands over host pointers — into its own text when host-held, into a copy that comes down here when it lies on
-// another device or the host builds.  The device build giving up later brings the rest down through PoolSets::host_text.
-extern "C" int g2s_graph_build_dpool_reach(const g2s_device_pool* const* pools, uint32_t npools, const uint64_t* set_begin,
-                                           const uint32_t* set_seq, const uint32_t* shared_seq, uint64_t nshared,
-                                           const uint8_t* set_shared, uint32_t nsets, int k, int solid, int nthreads,
-                                           const g2s_gap* reach_gap, const int32_t* reach_radius, g2s_graph** out) {
-  const char* const name = "g2s_graph_build_dpool_reach";
-  if ((reach_gap == nullptr) != (reach_radius == nullptr)) return fail(G2S_ERR_ARG, std::string(name) + ": reach_gap and reach_radius go together");
-  if (!pools || npools == 0) return fail(G2S_ERR_ARG, std::string(name) + ": bad argument");
-  uint64_t total = 0;
-  for (uint32_t p = 0; p < npools; p++) {
-    if (!pools[p]) return fail(G2S_ERR_ARG, std::string(name) + ": bad argument");
-    total += pools[p]->view.n_reads;
-  }
-  if (total >= (1ull << 32)) return fail(G2S_ERR_ARG, std::string(name) + ": bad argument");
-  const bool host_build = getenv("G2S_HOST_BUILD") != nullptr;
-  const int device = build_device();
-  std::vector<std::pair<const char*, uint64_t>> v((size_t)total);
-  std::vector<PoolDeviceText> dtext;
-  std::vector<std::string> down(npools);  // the text of a device-held pool, once it has come down
-  std::vector<uint32_t> first(npools);
-  auto point_at = [&](uint32_t p, const char* text) {
-    const g2s_device_pool& D = *pools[p];
-    for (uint64_t r = 0; r < D.view.n_reads; r++) v[(size_t)(first[p] + r)].first = text + D.start(r);
-  };
-  auto copy_down = [&](uint32_t p, std::string* err) {
-    const g2s_device_pool& D = *pools[p];
-    down[p].resize((size_t)D.text_bytes());
-    if (!device_pool_copy_down(D.device, D.d_text, 0, D.text_bytes(), &down[p][0], err)) return false;
-    point_at(p, down[p].data());
-    return true;
-  };
-  uint64_t at = 0;
-  for (uint32_t p = 0; p < npools; p++) {
-    const g2s_device_pool& D = *pools[p];
-    first[p] = (uint32_t)at;
-    for (uint64_t r = 0; r < D.view.n_reads; r++) v[(size_t)(at + r)] = {nullptr, D.base_off[(size_t)r + 1] - D.base_off[(size_t)r]};
-    at += D.view.n_reads;
-    std::string err;
-    if (D.device < 0) point_at(p, D.host_text.data());
-    else if (!host_build && D.device == device) dtext.push_back(PoolDeviceText{D.device, (const uint8_t*)D.d_text, D.d_start, first[p], D.view.n_reads});
-    else if (!copy_down(p, &err)) return fail(G2S_ERR_HIP, std::string(name) + ": " + err);
-  }
-  PoolSets ps;
-  const int rc = pool_sets_of(name, nullptr, nullptr, total, set_begin, set_seq, shared_seq, nshared, set_shared, nsets, out, &v, &ps);
-  if (rc != G2S_OK) return rc;
-  if (!dtext.empty()) {
-    ps.device_text = &dtext;
-    ps.host_text = [&](std::string* err) {
-      for (uint32_t p = 0; p < npools; p++)
-        if (pools[p]->device >= 0 && down[p].empty() && pools[p]->text_bytes() && !copy_down(p, err)) return false;
-      return true;
-    };
-  }
-  if (reach_radius) return build_pool_reach_of(ps, k, solid, nthreads, reach_gap, reach_radius, out);
-  std::string err;
-  return wrap_graph(graph_build_pool(ps, k, solid, nthreads, &err), err, out);
-}
-// TEST HOOK (include/g2s_test.h)
-extern "C" int g2s_test_last_dpool(int* held_on_device, uint64_t* bases_bytes_to_host, uint64_t* text_bytes_gathered_on_device,
-                                   uint64_t* text_bytes_packed_on_host) {
-  const LastDpoolFilter f = last_dpool_filter();
-  const PoolBuildInfo b = last_pool_build();
-  if (held_on_device) *held_on_device = f.held_on_device;
-  if (bases_bytes_to_host) *bases_bytes_to_host = f.bases_bytes_to_host;
-  if (text_bytes_gathered_on_device) *text_bytes_gathered_on_device = b.text_gathered;
-  if (text_bytes_packed_on_host) *text_bytes_packed_on_host = b.text_packed;
-  return G2S_OK;
-}
-// TEST HOOK (include/g2s_test.h)
-extern "C" int g2s_test_last_pool_reach(uint64_t* reach_sets, uint64_t* full_kmers, int* full_known, uint64_t* kept_kmers,
-                                        uint32_t* levels, int* on_device) {
-  const PoolReachInfo info = last_pool_reach();
-  if (reach_sets) *reach_sets = info.reach_sets;
-  if (full_kmers) *full_kmers = info.full_kmers;
-  if (full_known) *full_known = info.full_known;
-  if (kept_kmers) *kept_kmers = info.kept_kmers;
-  if (levels) *levels = info.levels;
-  if (on_device) *on_device = info.on_device;
-  return G2S_OK;
-}
-// TEST HOOK (include/g2s_test.h)
-extern "C" int g2s_test_last_pool_build(uint64_t* own_positions, uint64_t* shared_positions, uint64_t* keys_sorted, int* on_device) {
-  const PoolBuildInfo info = last_pool_build();
-  if (own_positions) *own_positions = info.own_positions;
-  if (shared_positions) *shared_positions = info.shared_positions;
-  if (keys_sorted) *keys_sorted = info.keys_sorted;
-  if (on_device) *on_device = info.on_device;
-  return G2S_OK;
-}
-// TEST HOOK (include/g2s_test.h)
-extern "C" int g2s_test_last_solid_count(uint64_t* positions, uint32_t* passes, uint32_t* refined_bins, uint64_t* max_pass_keys,
-                                         uint64_t* solid, int* on_device) {
-  const SolidCountInfo info = last_solid_count();
-  if (positions) *positions = info.positions;
-  if (passes) *passes = info.passes;
-  if (refined_bins) *refined_bins = info.refined_bins;
-  if (max_pass_keys) *max_pass_keys = info.max_pass_keys;
-  if (solid) *solid = info.solid;
-  if (on_device) *on_device = info.on_device;
-  return G2S_OK;
-}
-// TEST HOOK (include/g2s_test.h)
-extern "C" int g2s_test_plan_passes(const uint64_t* hist, uint32_t nbins, uint64_t cap, uint32_t* first_bin_of_pass,
-                                    uint32_t max_passes, uint32_t* npasses, uint32_t* first_oversized_bin) {
-  if ((!hist && nbins) || (!first_bin_of_pass && max_passes) || !npasses)
-    return fail(G2S_ERR_ARG, "g2s_test_plan_passes: bad argument");
-  std::vector<uint32_t> first_bin;
-  *npasses = plan_passes(hist, nbins, cap, &first_bin, first_oversized_bin);
-  for (uint32_t p = 0; p < std::min(*npasses, max_passes); p++) first_bin_of_pass[p] = first_bin[p];
-  return G2S_OK;
-}
-extern "C" uint32_t g2s_graph_num_sets(const g2s_graph* g) { return g ? g->g->num_sets() : 0; }
-extern "C" int g2s_graph_set_nodes(const g2s_graph* g, uint32_t set, uint64_t* first_kmer, uint64_t* n_kmers) {
-  if (!g || set >= g->g->num_sets()) return fail(G2S_ERR_ARG, "g2s_graph_set_nodes: bad set");
-  const uint64_t lo = g->g->set_lo.empty() ? 0 : g->g->set_lo[set];
-  const uint64_t hi = g->g->set_lo.empty() ? g->g->n : g->g->set_lo[(size_t)set + 1];
-  if (first_kmer) *first_kmer = lo;
-  if (n_kmers) *n_kmers = hi - lo;
-  return G2S_OK;
-}
-extern "C" uint32_t g2s_graph_set_node(const g2s_graph* g, uint32_t set, const char* kmer) {
-  if (!g || !kmer || (int)strnlen(kmer, (size_t)g->g->k) < g->g->k) return G2S_INVALID_NODE;
-  return g->g->node_of_in(set, kmer);
-}
-
-// ---- graphs from read files.  The device loader (reads_text.h) makes the build's text on the device from the files' raw
-// bytes and hands it to the device count; the host loader (zlib, parse_fastx, graph_build) is the fallback for everything
-// but a file that cannot be read, and what G2S_HOST_BUILD=1, G2S_HOST_READS=1 or a machine without a device get.
-namespace {
-LastInfo<ReadsLoadInfo> g_reads_info;
-void set_reads_info(const ReadsLoadInfo& info) { g_reads_info.set(info); }
-uint64_t env_bytes(const char* name) {
-  const char* s = getenv(name);
-  return s && *s ? strtoull(s, nullptr, 10) : 0;
-}
-// G2S_BUILD_BAM_STREAM: 1 the BAM read route's streaming form always, 0 never, unset: when resident does not fit
-int env_bam_stream() {
-  const char* s = getenv("G2S_BUILD_BAM_STREAM");
-  return s && *s ? (strcmp(s, "0") != 0 ? 1 : 0) : -1;
-}
-bool env_on(const char* name) {
-  const char* s = getenv(name);
-  return s && *s && strcmp(s, "0") != 0;
-}
-std::vector<std::string> split_csv(const char* reads_csv) {  // comma separated list (Gap2Seq.cpp:199-210)
-  std::vector<std::string> files;
-  std::string csv(reads_csv);
-  size_t pos = 0;
-  while (pos <= csv.size()) {
-    size_t e = csv.find(',', pos);
-    if (e == std::string::npos) e = csv.size();
-    if (e > pos) files.push_back(csv.substr(pos, e - pos));
-    pos = e + 1;
-  }
-  return files;
-}
-}  // namespace
-
-static int build_files_of(const char* reads_csv, int k, int solid, int nthreads, const GraphReach* reach, g2s_graph** out);
-extern "C" int g2s_graph_build_files(const char* reads_csv, int k, int solid, int nthreads, g2s_graph** out) {
-  return build_files_of(reads_csv, k, solid, nthreads, nullptr, out);
-}
-extern "C" int g2s_graph_build_files_reach(const char* reads_csv, int k, int solid, int nthreads, const g2s_gap* reach_gap,
-                                           const int32_t* reach_radius, uint64_t nreach, int mode, g2s_graph** out) {
-  return build_with_reach("g2s_graph_build_files_reach", k, reach_gap, reach_radius, nreach, mode, out, [&](const GraphReach* reach) {
-    return build_files_of(reads_csv, k, solid, nthreads, reach, out);
-  });
-}
-static int build_files_of(const char* reads_csv, int k, int solid, int nthreads, const GraphReach* reach, g2s_graph** out) {
-  if (!reads_csv || !out) return fail(G2S_ERR_ARG, "g2s_graph_build_files: bad argument");
-  const std::vector<std::string> files = split_csv(reads_csv);
-  const bool debug = getenv("G2S_DEBUG") != nullptr;
-  int bam_reason = kBamReadsNotAsked, bam_anomaly = 0;  // what the device loader met in a BAM file, when it gave up
-  // (G2S_HOST_BUILD: set to anything, as graph_build reads it)
-  if (!getenv("G2S_HOST_BUILD") && !env_on("G2S_HOST_READS")) {
-    const auto t0 = std::chrono::steady_clock::now();
-    std::vector<ReadsInput> inputs(files.size());
-    for (size_t i = 0; i < files.size(); i++) inputs[i].path = files[i];
-    const uint64_t piece = env_bytes("G2S_BUILD_PIECE_BYTES");
-    DeviceText text;
-    ReadsLoadInfo info;
-    std::string why;
-    const ReadsLoadResult r = load_reads_device(inputs, build_device(), (size_t)piece, env_bytes("G2S_BUILD_TEXT_FIRST_BYTES"),
-                                                env_on("G2S_HOST_INFLATE"), &text, &info, &why, env_bytes("G2S_BUILD_RESIDENT_CAP"),
-                                                env_bam_stream(), device_gzip_asked());
-    if (r == kReadsIoError) return fail(G2S_ERR_IO, why);
-    if (r != kReadsOk) { bam_reason = info.bam_reason; bam_anomaly = info.bam_anomaly; }
-    if (r == kReadsOk && text.T == 0) {  // (no sequence at all: the empty graph, as the host loader builds it)
-      free_device_text(&text);
-      why = "no text";
-    } else if (r == kReadsOk) {
-      if (debug)
-        fprintf(stderr, "[g2s] reads: %llu files, %llu raw bytes, %llu text positions, %llu records in %llu pieces on the device, %.3f s\n",
-                (unsigned long long)info.files, (unsigned long long)info.raw_bytes, (unsigned long long)info.positions,
-                (unsigned long long)info.records, (unsigned long long)info.pieces, ms_since(t0) / 1e3);
-      bool gave_up = false;
-      std::string err;
-      Graph* g = graph_build_text(&text, k, solid, nthreads, &err, &gave_up, reach);
-      free_device_text(&text);
-      if (g) set_reads_info(info);
-      if (g || !gave_up) return wrap_graph(g, err, out);
-      why = "the device count gave up: " + err;
-    }
-    if (debug) fprintf(stderr, "[g2s] reads: the host loader takes over (%s)\n", why.c_str());
-  }
-  ReadsLoadInfo info;
-  info.bam_reason = bam_reason;
-  info.bam_anomaly = bam_anomaly;
-  std::vector<FastxRecord> recs;
-  for (const std::string& file : files) {
-    std::string raw, text, err;
-    if (!read_text_file(file, &raw)) return fail(G2S_ERR_IO, "cannot read " + file);
-    const uint8_t* bytes = (const uint8_t*)raw.data();
-    const bool gz = is_gzip(bytes, raw.size());
-    info.files++;
-    info.inflate.push_back(gz ? kInflateZlib : kInflateNone);
-    if (gz && is_bam(bytes, raw.size())) {  // (bam_reads.h: the kept records' sequences, by the reader's walk)
-      ReadsInput in;
-      in.path = file;
-      in.mem = bytes;
-      in.mem_n = raw.size();
-      std::vector<std::string> seqs;
-      if (!bam_reads_host(in, &seqs, &info.bam_skipped, &info.raw_bytes, &err)) return fail(G2S_ERR_IO, err);
-      info.bam_files++;
-      info.bam_kept += seqs.size();
-      for (std::string& q : seqs) {
-        recs.emplace_back();
-        recs.back().seq.swap(q);
-      }
-      continue;
-    }
-    if (!gz) text.swap(raw);
-    else if (!reads_text_of_bytes(bytes, raw.size(), file, &text, nullptr, &err)) return fail(G2S_ERR_IO, err);
-    info.raw_bytes += text.size();
-    parse_fastx(text, &recs);
-  }
-  std::vector<std::pair<const char*, uint64_t>> v;
-  for (auto& r : recs) {
-    v.emplace_back(r.seq.data(), (uint64_t)r.seq.size());
-    info.positions += r.seq.size() + 1;
-  }
-  info.records = recs.size();
-  std::string err;
-  Graph* g = graph_build(v, k, solid, nthreads, &err, reach);
-  if (g) set_reads_info(info);
-  return wrap_graph(g, err, out);
-}
-// TEST HOOK (include/g2s_test.h)
-extern "C" int g2s_test_last_reads_load(uint64_t* files, uint64_t* raw_bytes, uint64_t* positions, uint64_t* records,
-                                        uint64_t* pieces, int* on_device, int* inflate, uint64_t inflate_cap, uint64_t* grows) {
-  const ReadsLoadInfo info = g_reads_info.get();
-  if (files) *files = info.files;
-  if (raw_bytes) *raw_bytes = info.raw_bytes;
-  if (positions) *positions = info.positions;
-  if (records) *records = info.records;
-  if (pieces) *pieces = info.pieces;
-  if (on_device) *on_device = info.on_device;
-  if (grows) *grows = info.grows;
-  if (inflate)
-    for (uint64_t i = 0; i < std::min<uint64_t>(inflate_cap, info.inflate.size()); i++) inflate[i] = info.inflate[i];
-  return G2S_OK;
-}
-// TEST HOOK (include/g2s_test.h)
-extern "C" int g2s_test_last_reads_bam(uint64_t* bam_files, uint64_t* kept, uint64_t* skipped, int* by_kernels, int* reason,
-                                       int* anomaly) {
-  const ReadsLoadInfo info = g_reads_info.get();
-  if (bam_files) *bam_files = info.bam_files;
-  if (kept) *kept = info.bam_kept;
-  if (skipped) *skipped = info.bam_skipped;
-  if (by_kernels) *by_kernels = info.bam_kernels;
-  if (reason) *reason = info.bam_reason;
-  if (anomaly) *anomaly = info.bam_anomaly;
-  return G2S_OK;
-}
-// TEST HOOK (include/g2s_test.h)
-extern "C" int g2s_test_last_reads_bam_stream(uint64_t* streamed_files, uint64_t* windows, uint64_t* peak_device_bytes) {
-  const ReadsLoadInfo info = g_reads_info.get();
-  if (streamed_files) *streamed_files = info.bam_streamed;
-  if (windows) *windows = info.bam_stream_windows;
-  if (peak_device_bytes) *peak_device_bytes = info.bam_stream_peak;
-  return G2S_OK;
-}
-// TEST HOOK (include/g2s_test.h)
-extern "C" int g2s_test_reads_text(const void* bytes, size_t n, int device, size_t piece_bytes, uint8_t* out, size_t cap,
-                                   size_t* out_n) {
-  if ((!bytes && n) || (!out && cap) || !out_n || device < -2) return fail(G2S_ERR_ARG, "g2s_test_reads_text: bad argument");
-  const uint8_t* p = (const uint8_t*)bytes;
-  if (device < 0) {
-    std::string raw, err, text;
-    ReadsLoadInfo info;
-    info.files = 1;
-    if (is_bam(p, n)) {  // (either host form: there is no line machine for BAM)
-      ReadsInput in;
-      in.mem = p;
-      in.mem_n = n;
-      std::vector<std::string> seqs;
-      if (!bam_reads_host(in, &seqs, &info.bam_skipped, &info.raw_bytes, &err)) return fail(G2S_ERR_IO, err);
-      for (const std::string& q : seqs) { text += q; text.push_back('N'); }
-      info.records = info.bam_kept = seqs.size();
-      info.bam_files = 1;
-      info.inflate.push_back(kInflateZlib);
-    } else {
-      if (!reads_text_of_bytes(p, n, "(memory)", &raw, nullptr, &err)) return fail(G2S_ERR_IO, err);
-      info.raw_bytes = raw.size();
-      if (device == -1) {
-        std::vector<FastxRecord> recs;
-        parse_fastx(raw, &recs);
-        for (auto& r : recs) { text += r.seq; text.push_back('N'); }
-        info.records = recs.size();
-      } else {
-        machine_text_host((const uint8_t*)raw.data(), raw.size(), &text, &info.records);
-      }
-    }
-    info.positions = text.size();
-    set_reads_info(info);
-    *out_n = text.size();
-    if (!text.empty()) memcpy(out, text.data(), std::min(cap, text.size()));
-    return G2S_OK;
-  }
-  if (!filter_device_usable(device)) return fail(G2S_ERR_NO_DEVICE, "g2s_test_reads_text: no usable gfx950 device " + std::to_string(device));
-  std::vector<ReadsInput> inputs(1);
-  inputs[0].mem = p;
-  inputs[0].mem_n = n;
-  DeviceText text;
-  ReadsLoadInfo info;
-  std::string why;
-  const ReadsLoadResult r = load_reads_device(inputs, device, piece_bytes,
-                                              env_bytes("G2S_BUILD_TEXT_FIRST_BYTES"), env_on("G2S_HOST_INFLATE"), &text, &info, &why,
-                                              env_bytes("G2S_BUILD_RESIDENT_CAP"), env_bam_stream(), device_gzip_asked());
-  if (r == kReadsIoError) return fail(G2S_ERR_IO, why);
-  if (r != kReadsOk) {
-    info.bam_streamed = info.bam_stream_windows = info.bam_stream_peak = 0;  // (nothing of a refused call counts)
-    set_reads_info(info);  // (g2s_test_last_reads_bam: what a BAM file met)
-    return fail(G2S_ERR_HIP, "g2s_test_reads_text: the device refused (" + why + ")");
-  }
-  set_reads_info(info);
-  *out_n = (size_t)text.T;
-  const size_t take = std::min<size_t>(cap, (size_t)text.T);
-  const hipError_t e = take ? hipMemcpy(out, text.d_text, take, hipMemcpyDeviceToHost) : hipSuccess;
-  free_device_text(&text);
-  if (e != hipSuccess) return fail(G2S_ERR_HIP, std::string("g2s_test_reads_text: ") + hipGetErrorString(e));
-  return G2S_OK;
-}
-
-extern "C" int g2s_reads_set_device_gzip(int mode) { return set_device_gzip(mode); }
-// TEST HOOK (include/g2s_test.h)
-extern "C" int g2s_test_last_reads_gzip(uint64_t* files, uint64_t* windows, uint64_t* chunks, uint64_t* starts_found,
-                                        uint64_t* absorbed, uint64_t* members, int* outcome, uint64_t* peak_device_bytes) {
-  const ReadsLoadInfo info = g_reads_info.get();
-  if (files) *files = info.gzip.files;
-  if (windows) *windows = info.gzip.windows;
-  if (chunks) *chunks = info.gzip.chunks;
-  if (starts_found) *starts_found = info.gzip.starts_found;
-  if (absorbed) *absorbed = info.gzip.absorbed;
-  if (members) *members = info.gzip.members;
-  if (outcome) *outcome = info.gzip.outcome;
-  if (peak_device_bytes) *peak_device_bytes = info.gzip.peak_device_bytes;
-  return G2S_OK;
-}
-// TEST HOOK (include/g2s_test.h)
-extern "C" int g2s_test_gzip_inflate(const void* bytes, size_t n, int device, uint32_t chunk_bytes, uint32_t window_chunks,
-                                     uint8_t* out, size_t cap, size_t* out_n, int* outcome) {
-  if (!bytes || !out_n || (!out && cap) || device < -2) return fail(G2S_ERR_ARG, "g2s_test_gzip_inflate: bad argument");
-  *out_n = 0;
-  if (outcome) *outcome = kGzDone;
-  const uint8_t* p = (const uint8_t*)bytes;
-  std::string all;
-  if (device == -1) {
-    std::string err;
-    if (!reads_text_of_bytes(p, n, "(memory)", &all, nullptr, &err)) return fail(G2S_ERR_IO, err);
-  } else {
-    GzipParams P = gzip_params_from_env();
-    if (chunk_bytes) P.chunk = std::max<uint32_t>(chunk_bytes, 1024);
-    // (0: the whole file in one window)
-    P.window_chunks = window_chunks ? std::max<uint32_t>(window_chunks, 2) : (uint32_t)std::min<uint64_t>(65535, std::max<uint64_t>(n / P.chunk + 1, 2));
-    std::unique_ptr<GzipBackend> B;
-    if (device >= 0) {
-      if (!filter_device_usable(device)) return fail(G2S_ERR_NO_DEVICE, "g2s_test_gzip_inflate: no usable gfx950 device " + std::to_string(device));
-      std::string why;
-      if (hipSetDevice(device) != hipSuccess) return fail(G2S_ERR_HIP, "g2s_test_gzip_inflate: the device cannot be used");
-      B = make_gzip_device_backend(device, nullptr, P, &why);
-      if (!B) return fail(G2S_ERR_HIP, "g2s_test_gzip_inflate: " + why);
-    } else {
-      B = make_gzip_host_backend(P);
-    }
-    GzipStats st;
-    std::string hip_why;
-    const int oc = gzip_route(
-        p, n, P, *B, &st, []() -> uint32_t { return 0; },
-        [&](const uint8_t* from, uint64_t m, bool) -> bool {
-          if (!m) return true;
-          const size_t at = all.size();
-          all.resize(at + m);
-          if (device < 0) {
-            memcpy(&all[at], from, m);
-            return true;
-          }
-          const hipError_t e = hipMemcpy(&all[at], from, m, hipMemcpyDeviceToHost);
-          if (e != hipSuccess) hip_why = hipGetErrorString(e);
-          return e == hipSuccess;
-        });
-    ReadsLoadInfo info;
-    info.gzip = st;
-    info.gzip.peak_device_bytes = B->device_bytes();
-    set_reads_info(info);
-    if (oc == kGzHip) return fail(G2S_ERR_HIP, "g2s_test_gzip_inflate: " + (hip_why.empty() ? B->why : hip_why));
-    if (outcome) *outcome = oc;
-    if (oc != kGzDone) return G2S_OK;  // (given back: no bytes)
-  }
-  *out_n = all.size();
-  if (!all.empty()) memcpy(out, all.data(), std::min(cap, all.size()));
-  return G2S_OK;
-}
-
-extern "C" int g2s_graph_save(const g2s_graph* g, const char* path) {
-  std::string err;
-  if (!g || !path) return fail(G2S_ERR_ARG, "g2s_graph_save: bad argument");
-  if (g->g->num_sets() > 1) return fail(G2S_ERR_ARG, "g2s_graph_save: graphs of several read sets are not saved");
-  return graph_save(*g->g, path, &err) ? G2S_OK : fail(G2S_ERR_IO, err);
-}
-extern "C" int g2s_graph_load(const char* path, g2s_graph** out) {
-  std::string err;
-  if (!path || !out) return fail(G2S_ERR_ARG, "g2s_graph_load: bad argument");
-  Graph* g = graph_load(path, &err);
-  if (!g) return fail(G2S_ERR_IO, err);
-  *out = new g2s_graph();
-  (*out)->g = g;
-  return G2S_OK;
-}
-extern "C" void g2s_graph_free(g2s_graph* g) {
-  if (!g) return;
-  if (g->g) {
-    for (auto& kv : g->g->dev) {
-      if (hipSetDevice(kv.first) == hipSuccess) {
-        if (kv.second.succ) (void)hipFree(kv.second.succ);
-        if (kv.second.pred) (void)hipFree(kv.second.pred);
-        if (kv.second.ustart) (void)hipFree(kv.second.ustart - kUstartPad);
-        if (kv.second.rem) (void)hipFree(kv.second.rem);
-        if (kv.second.urec) (void)hipFree(kv.second.urec);
-        if (kv.second.brec) (void)hipFree(kv.second.brec);
-      }
-    }
-    delete g->g;
-  }
-  delete g;
-}
-extern "C" int g2s_graph_k(const g2s_graph* g) { return g ? g->g->k : 0; }
-extern "C" int g2s_graph_solid(const g2s_graph* g) { return g ? g->g->solid : 0; }
-extern "C" uint64_t g2s_graph_num_kmers(const g2s_graph* g) { return g ? g->g->n : 0; }
-extern "C" uint64_t g2s_graph_num_unitigs(const g2s_graph* g) { return g ? g->g->n_unitigs : 0; }
-extern "C" uint32_t g2s_graph_node(const g2s_graph* g, const char* kmer) {
-  if (!g || !kmer || (int)strnlen(kmer, (size_t)g->g->k) < g->g->k) return G2S_INVALID_NODE;
-  return g->g->node_of(kmer);
-}
-extern "C" int g2s_graph_successors(const g2s_graph* g, uint32_t node, uint32_t out[4]) {
-  if (!g || (uint64_t)node >= 2 * g->g->n) return 0;
-  int c = 0;
-  for (int nt = 0; nt < 4; nt++) {
-    uint32_t w = g->g->succ_of(node, nt);
-    if (w != kInvalidNode) out[c++] = w;
-  }
-  return c;
-}
-extern "C" int g2s_graph_predecessors(const g2s_graph* g, uint32_t node, uint32_t out[4]) {
-  if (!g || (uint64_t)node >= 2 * g->g->n) return 0;
-  int c = 0;
-  for (int nt = 0; nt < 4; nt++) {
-    uint32_t w = g->g->pred_of(node, nt);
-    if (w != kInvalidNode) out[c++] = w;
-  }
-  return c;
-}
-extern "C" int g2s_graph_node_string(const g2s_graph* g, uint32_t node, char* out) {
-  if (!g || !out || (uint64_t)node >= 2 * g->g->n) return fail(G2S_ERR_ARG, "g2s_graph_node_string: bad node");
-  std::string s = g->g->node_string(node);
-  memcpy(out, s.c_str(), s.size() + 1);
-  return G2S_OK;
-}
-
-extern "C" int g2s_graph_upload(g2s_graph* gh, int device) {
-  g2s_env_sync();
-  if (!gh) return fail(G2S_ERR_ARG, "g2s_graph_upload: null graph");
-  Graph& g = *gh->g;
-  if (g.dev.count(device)) return G2S_OK;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
-    return fail(G2S_ERR_NO_DEVICE, "no HIP device " + std::to_string(device) + " (this library has no CPU fallback)");
-  HIP_TRY(hipSetDevice(device));
-  DeviceGraph dg;
-  const size_t bytes = g.succ.size() * sizeof(uint32_t);
-  // 1 KB of INVALID entries behind the table: a read a little past its last row finds no successor
-  HIP_TRY(hipMalloc((void**)&dg.succ, bytes + 1024));
-  HIP_TRY(hipMemset(dg.succ, 0xFF, bytes + 1024));
-  HIP_TRY(hipMemcpy(dg.succ, g.succ.data(), bytes, hipMemcpyHostToDevice));
-  dg.bytes = bytes;
-  if (!g.pred.empty()) {
-    HIP_TRY(hipMalloc((void**)&dg.pred, bytes));
-    HIP_TRY(hipMemcpy(dg.pred, g.pred.data(), bytes, hipMemcpyHostToDevice));
-    dg.bytes += bytes;
-  }
-  {  // unitig-start bitmap between two pads of all-ones words (scans past either end stop there)
-    const size_t words = g.ustart.size();
-    uint64_t* base = nullptr;
-    HIP_TRY(hipMalloc((void**)&base, (words + 2 * kUstartPad) * 8));
-    HIP_TRY(hipMemset(base, 0xFF, (words + 2 * kUstartPad) * 8));
-    HIP_TRY(hipMemcpy(base + kUstartPad, g.ustart.data(), words * 8, hipMemcpyHostToDevice));
-    dg.ustart = base + kUstartPad;
-    dg.bytes += (words + 2 * kUstartPad) * 8;
-  }
-  g.dev[device] = dg;
-  return G2S_OK;
-}
-extern "C" uint64_t g2s_graph_device_bytes(const g2s_graph* g, int device) {
-  if (!g) return 0;
-  auto it = g->g->dev.find(device);
-  return it == g->g->dev.end() ? 0 : it->second.bytes;
 }
 
 // ---------------------------------------------------------------------------
@@ -1280,7 +555,7 @@ struct InternalCall {
 
 // the segment tier's tables of an uploaded graph, derived on the device from the bitmap that is already there (the
 // device is current)
-static int ensure_seg_tables(g2s_graph* g, int device) {
+int api::ensure_seg_tables(g2s_graph* g, int device) {
   DeviceGraph& dg = g->g->dev.at(device);
   if (dg.rem || g->g->n == 0) return G2S_OK;
   // all of them or none: dg.rem is what the gates and this function's early return read, so it is set last, and a table
@@ -1311,19 +586,6 @@ static g2s::SegGraph seg_graph(const DeviceGraph& dg) {
   t.pflip = dg.pred ? 0u : 1u;
   return t;
 }
-// TEST HOOK (include/g2s_test.h)
-extern "C" int g2s_test_seg_back_record(g2s_graph* g, int device, uint32_t node, uint32_t out[5]) {
-  g2s_env_sync();
-  if (!g || !out || (uint64_t)node >= 2 * g->g->n) return fail(G2S_ERR_ARG, "g2s_test_seg_back_record: bad argument");
-  int rc = g2s_graph_upload(g, device);
-  if (rc != G2S_OK) return rc;
-  HIP_TRY(hipSetDevice(device));
-  rc = ensure_seg_tables(g, device);
-  if (rc != G2S_OK) return rc;
-  HIP_TRY(hipMemcpy(out, g->g->dev.at(device).back_table() + (size_t)(node ^ 1u) * 8, 5 * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  return G2S_OK;
-}
-
 extern "C" int g2s_session_create(g2s_graph* g, int device, const g2s_params* p, g2s_session** out) {
   g2s_env_sync();
   if (!g || !p || !out) return fail(G2S_ERR_ARG, "g2s_session_create: bad argument");
@@ -5442,307 +4704,6 @@ extern "C" int g2s_session_get_params(const g2s_session* s, g2s_params* out) {
   return G2S_OK;
 }
 
-// TEST HOOK, see include/g2s_test.h: host half of phase D on a caller-supplied DP table.
-// The closure the g2s_extract kernel would compute is derived on the host (host_closure).
-extern "C" int g2s_test_post_gap(const g2s_graph* gh, const g2s_params* p, const g2s_gap* gap, int32_t n_states,
-                                 const uint32_t* nodes, const int32_t* depths, const uint32_t* counts,
-                                 int32_t c_count, int32_t n_lengths, const int32_t* lengths, int32_t reached_j,
-                                 int32_t final_d, uint32_t seed, uint32_t skip, g2s_result* res, char* buf) {
-  if (!gh || !p || !gap || !res || !buf || n_states < 0) return fail(G2S_ERR_ARG, "g2s_test_post_gap: bad argument");
-  const Graph& g = *gh->g;
-  const int k = g.k;
-  GapJob j;
-  j.g = gap->gap_len; j.lmf = gap->lmf; j.rmf = gap->rmf;
-  if (gap->left_len < k + j.lmf || gap->right_len < k + j.rmf) return fail(G2S_ERR_ARG, "flank too short");
-  std::vector<uint32_t> flank_store;
-  j.resolve_on_host(g, gap->left, (size_t)gap->left_len, gap->right, (size_t)gap->right_len, &flank_store);
-  HostTable t;
-  t.D = j.lmf + j.rmf + j.g + p->d_err;
-  t.lvl.assign((size_t)t.D + 2, 0);
-  for (int i = 0; i < n_states; i++) if (depths[i] >= 0 && depths[i] <= t.D) t.lvl[(size_t)depths[i] + 1]++;
-  for (int d = 0; d <= t.D; d++) t.lvl[(size_t)d + 1] += t.lvl[(size_t)d];
-  t.states.assign((size_t)n_states + 1, 0);
-  {
-    std::vector<uint32_t> pos(t.lvl.begin(), t.lvl.end() - 1);
-    for (int i = 0; i < n_states; i++)
-      if (depths[i] >= 0 && depths[i] <= t.D)
-        t.states[pos[(size_t)depths[i]]++] = ((uint64_t)nodes[i] << 32) | std::min<uint32_t>(counts[i], G2S_MAX_PATHS);
-    for (int d = 0; d <= t.D; d++) std::sort(t.states.begin() + t.lvl[(size_t)d], t.states.begin() + t.lvl[(size_t)d + 1]);
-  }
-  GapOut go;
-  memset(&go, 0, sizeof go);
-  go.c_count = c_count; go.n_len = n_lengths; go.reached_j = reached_j; go.final_d = final_d;
-  for (int i = 0; i < n_lengths && i < 2; i++) go.len[i] = lengths[i];
-  FillParams fp;
-  fp.k = k; fp.d_err = p->d_err; fp.skip_confident = p->skip_confident != 0; fp.all_paths = p->all_paths != 0;
-  fp.unique_paths = p->unique_paths != 0;
-  std::vector<SubState> closure;
-  uint32_t q7 = 0;
-  host_closure(g, fp, j, t, go, &closure, &q7);
-  std::vector<SubRec> recs;
-  std::vector<uint64_t> xps;
-  sub_convert(closure.data(), (uint32_t)closure.size(), &recs, &xps);
-  SubView v;
-  v.out = &go; v.st = recs.data(); v.n = (uint32_t)recs.size(); v.xp = xps.data(); v.n_xp = (uint32_t)xps.size();
-  SubPrep prep;
-  sub_analyze(fp, j, v, &prep);
-  memset(res, 0, sizeof *res);
-  memset(buf, 0, j.buf_bytes(k, fp.d_err));
-  res->phaseC_count = c_count;
-  res->count = prep.count;
-  res->flags |= prep.flags | q7;
-  res->fill_off = (uint64_t)j.lmf;
-  if (prep.phase_d) {
-    GlibcRand rng;
-    rng.seed(seed);
-    for (uint32_t i = 0; i < skip; i++) rng.next();
-    std::vector<uint32_t> rands((size_t)t.D + 4);
-    for (auto& x : rands) x = (uint32_t)rng.next() << 1;  // raw words: value = word >> 1
-    const int pick = (int)((rands[0] >> 1) % (uint32_t)go.n_len);
-    const int fixed = sub_fixed_draws(v, prep, pick);
-    sub_traceback(g, fp, j, v, prep, rands.data(), buf, res);
-    if (fixed >= 0 && fixed != res->draws) return fail(G2S_ERR_STATE, "stop-depth analysis disagrees with the traceback");
-    // the two shortcuts of the batch path, checked here on the CPU: the draw-count walk, and
-    // the fill written without rand() values when no state has a second parent
-    if (sub_count_draws(g, v, prep, rands.data()) != res->draws)
-      return fail(G2S_ERR_STATE, "draw-count walk disagrees with the traceback");
-    if (go.n_len == 1 && v.n_xp == 0 && fixed >= 0) {
-      std::vector<char> buf2(j.buf_bytes(k, fp.d_err), 0);
-      g2s_result r2;
-      memset(&r2, 0, sizeof r2);
-      sub_traceback(g, fp, j, v, prep, nullptr, buf2.data(), &r2);
-      if (r2.draws != res->draws || r2.left_fuz != res->left_fuz || memcmp(buf2.data(), buf, buf2.size()) != 0)
-        return fail(G2S_ERR_STATE, "rand()-free traceback disagrees with the traceback");
-    }
-    res->vertices = prep.sub[0]; res->edges = prep.sub[1]; res->nontrivial_components = prep.sub[2];
-    res->size_nontrivial_components = prep.sub[3]; res->vertices_final = prep.sub[4]; res->edges_final = prep.sub[5];
-    res->fill_off = (uint64_t)(j.lmf - res->left_fuz);
-    res->fill_len = (int32_t)strlen(buf + res->fill_off);
-  }
-  return G2S_OK;
-}
-
-extern "C" int g2s_test_post_closure(const g2s_graph* gh, const g2s_params* p, const g2s_gap* gap, uint32_t n_records,
-                                     const uint32_t* records, uint32_t n_xp, const uint64_t* xp, int32_t c_count,
-                                     int32_t n_lengths, const int32_t* lengths, int32_t reached_j, int32_t final_d,
-                                     uint32_t seed, uint64_t skip, g2s_result* res, char* buf) {
-  if (!gh || !p || !gap || !res || !buf || (n_records && !records) || (n_xp && !xp))
-    return fail(G2S_ERR_ARG, "g2s_test_post_closure: bad argument");
-  const Graph& g = *gh->g;
-  const int k = g.k;
-  GapJob j;
-  j.g = gap->gap_len; j.lmf = gap->lmf; j.rmf = gap->rmf;
-  if (gap->left_len < k + j.lmf || gap->right_len < k + j.rmf) return fail(G2S_ERR_ARG, "flank too short");
-  std::vector<uint32_t> flank_store;
-  j.resolve_on_host(g, gap->left, (size_t)gap->left_len, gap->right, (size_t)gap->right_len, &flank_store);
-  GapOut go;
-  memset(&go, 0, sizeof go);
-  go.c_count = c_count; go.n_len = n_lengths; go.reached_j = reached_j; go.final_d = final_d;
-  for (int i = 0; i < n_lengths && i < 2; i++) go.len[i] = lengths[i];
-  FillParams fp;
-  fp.k = k; fp.d_err = p->d_err; fp.skip_confident = p->skip_confident != 0; fp.all_paths = p->all_paths != 0;
-  fp.unique_paths = p->unique_paths != 0;
-  std::vector<SubRec> recs(n_records);
-  if (n_records) memcpy(recs.data(), records, (size_t)n_records * sizeof(SubRec));
-  std::vector<uint64_t> xps(xp, xp + n_xp);
-  std::sort(xps.begin(), xps.end());
-  SubView v;
-  v.out = &go; v.st = recs.data(); v.n = n_records; v.xp = xps.data(); v.n_xp = n_xp;
-  SubPrep prep;
-  sub_analyze(fp, j, v, &prep);
-  memset(res, 0, sizeof *res);
-  memset(buf, 0, j.buf_bytes(k, fp.d_err));
-  res->phaseC_count = c_count;
-  res->n_lengths = n_lengths;
-  for (int i = 0; i < n_lengths && i < 2; i++) res->lengths[i] = lengths[i];
-  res->count = prep.count;
-  res->flags |= prep.flags;
-  res->fill_off = (uint64_t)j.lmf;
-  if (prep.phase_d) {
-    GlibcRand rng;
-    rng.seed(seed);
-    for (uint64_t i = 0; i < skip; i++) rng.next();
-    const int D = j.lmf + j.rmf + j.g + p->d_err;
-    std::vector<uint32_t> rands((size_t)D + 4);
-    for (auto& x : rands) x = (uint32_t)rng.next() << 1;  // raw words: value = word >> 1
-    sub_traceback(g, fp, j, v, prep, rands.data(), buf, res);
-    res->vertices = prep.sub[0]; res->edges = prep.sub[1]; res->nontrivial_components = prep.sub[2];
-    res->size_nontrivial_components = prep.sub[3]; res->vertices_final = prep.sub[4]; res->edges_final = prep.sub[5];
-    res->fill_off = (uint64_t)(j.lmf - res->left_fuz);
-    res->fill_len = (int32_t)strlen(buf + res->fill_off);
-  }
-  return G2S_OK;
-}
-
-extern "C" int g2s_test_post_segments(const g2s_graph* gh, const g2s_params* p, const g2s_gap* gap, uint32_t n_segs,
-                                      const uint32_t* segs, int32_t c_count, int32_t n_lengths, const int32_t* lengths,
-                                      int32_t reached_j, int32_t final_d, uint32_t seed, uint64_t skip, g2s_result* res,
-                                      char* buf, int32_t* on_segments) {
-  if (!gh || !p || !gap || !res || !buf || (n_segs && !segs)) return fail(G2S_ERR_ARG, "g2s_test_post_segments: bad argument");
-  const Graph& g = *gh->g;
-  const int k = g.k;
-  GapJob j;
-  j.g = gap->gap_len; j.lmf = gap->lmf; j.rmf = gap->rmf;
-  if (gap->left_len < k + j.lmf || gap->right_len < k + j.rmf) return fail(G2S_ERR_ARG, "flank too short");
-  std::vector<uint32_t> flank_store;
-  j.resolve_on_host(g, gap->left, (size_t)gap->left_len, gap->right, (size_t)gap->right_len, &flank_store);
-  GapOut go;
-  memset(&go, 0, sizeof go);
-  go.c_count = c_count; go.n_len = n_lengths; go.reached_j = reached_j; go.final_d = final_d;
-  for (int i = 0; i < n_lengths && i < 2; i++) go.len[i] = lengths[i];
-  FillParams fp;
-  fp.k = k; fp.d_err = p->d_err; fp.skip_confident = p->skip_confident != 0; fp.all_paths = p->all_paths != 0;
-  fp.unique_paths = p->unique_paths != 0;
-  SubView v;
-  v.out = &go; v.segs = (const SegRec*)segs; v.n_segs = n_segs;
-  SubPrep prep;
-  const auto t_an0 = std::chrono::steady_clock::now();
-  const bool ok = seg_analyze(fp, j, v, &prep);
-  if (on_segments) *on_segments = ok ? 1 : 0;
-  if (n_segs >= 2000 && prep.run_mode && GENV("G2S_POST_LAPS")) {  // (tools/host_items_replay.py)
-    const double* l = g2s_post_laps;
-    const double t1 = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count();
-    fprintf(stderr, "[g2s] %u segments, run analysis laps (us): front %.0f | collect %.0f merge+sort %.0f runs %.0f edges %.0f csr %.0f tarjan %.0f rest %.0f | all %.0f\n", n_segs,
-            l[0] - std::chrono::duration<double, std::micro>(t_an0.time_since_epoch()).count(), l[1] - l[0], l[2] - l[1], l[3] - l[2], l[4] - l[3], l[5] - l[4], l[6] - l[5], l[7] - l[6],
-            t1 - std::chrono::duration<double, std::micro>(t_an0.time_since_epoch()).count());
-  }
-  memset(res, 0, sizeof *res);
-  memset(buf, 0, j.buf_bytes(k, fp.d_err));
-  if (!ok) return G2S_OK;  // a k-mer at two depths: the caller takes g2s_test_seg_expand + g2s_test_post_closure
-  res->phaseC_count = c_count;
-  res->n_lengths = n_lengths;
-  for (int i = 0; i < n_lengths && i < 2; i++) res->lengths[i] = lengths[i];
-  res->count = prep.count;
-  res->flags |= prep.flags;
-  res->fill_off = (uint64_t)j.lmf;
-  if (prep.phase_d) {
-    GlibcRand rng;
-    rng.seed(seed);
-    for (uint64_t i = 0; i < skip; i++) rng.next();
-    const int D = j.lmf + j.rmf + j.g + p->d_err;
-    std::vector<uint32_t> rands((size_t)D + 4);
-    for (auto& x : rands) x = (uint32_t)rng.next() << 1;
-    const int pick = (int)((rands[0] >> 1) % (uint32_t)go.n_len);
-    const int fixed = sub_fixed_draws(v, prep, pick);
-    seg_traceback(g, fp, j, v, prep, rands.data(), buf, res);
-    if (fixed >= 0 && fixed != res->draws) return fail(G2S_ERR_STATE, "stop-depth analysis disagrees with the traceback (segments)");
-    if (seg_count_draws(g, v, prep, rands.data()) != res->draws)
-      return fail(G2S_ERR_STATE, "draw-count walk disagrees with the traceback (segments)");
-    if (go.n_len == 1 && !prep.has_choice && fixed >= 0) {
-      std::vector<char> buf2(j.buf_bytes(k, fp.d_err), 0);
-      g2s_result r2;
-      memset(&r2, 0, sizeof r2);
-      seg_traceback(g, fp, j, v, prep, nullptr, buf2.data(), &r2);
-      if (r2.draws != res->draws || r2.left_fuz != res->left_fuz || memcmp(buf2.data(), buf, buf2.size()) != 0)
-        return fail(G2S_ERR_STATE, "rand()-free traceback disagrees with the traceback (segments)");
-    }
-    res->vertices = prep.sub[0]; res->edges = prep.sub[1]; res->nontrivial_components = prep.sub[2];
-    res->size_nontrivial_components = prep.sub[3]; res->vertices_final = prep.sub[4]; res->edges_final = prep.sub[5];
-    res->fill_off = (uint64_t)(j.lmf - res->left_fuz);
-    res->fill_len = (int32_t)strlen(buf + res->fill_off);
-  }
-  return G2S_OK;
-}
-
-extern "C" int g2s_test_seg_expand(const g2s_graph* gh, const g2s_params* p, const g2s_gap* gap, uint32_t n_segs,
-                                   const uint32_t* segs, int32_t n_lengths, const int32_t* lengths, int32_t reached_j,
-                                   uint32_t n_records, uint32_t* records, uint32_t n_xp, uint64_t* xp) {
-  if (!gh || !p || !gap || (n_segs && !segs) || (n_records && !records) || (n_xp && !xp))
-    return fail(G2S_ERR_ARG, "g2s_test_seg_expand: bad argument");
-  const Graph& g = *gh->g;
-  const int k = g.k;
-  GapJob j;
-  j.g = gap->gap_len; j.lmf = gap->lmf; j.rmf = gap->rmf;
-  if (gap->left_len < k + j.lmf || gap->right_len < k + j.rmf) return fail(G2S_ERR_ARG, "flank too short");
-  std::vector<uint32_t> flank_store;
-  j.resolve_on_host(g, gap->left, (size_t)gap->left_len, gap->right, (size_t)gap->right_len, &flank_store);
-  GapOut go;
-  memset(&go, 0, sizeof go);
-  go.n_len = n_lengths; go.reached_j = reached_j;
-  for (int i = 0; i < n_lengths && i < 2; i++) go.len[i] = lengths[i];
-  FillParams fp;
-  fp.k = k; fp.d_err = p->d_err; fp.skip_confident = p->skip_confident != 0; fp.all_paths = p->all_paths != 0;
-  fp.unique_paths = p->unique_paths != 0;
-  const SegRec* sr = (const SegRec*)segs;
-  size_t total = 0, nx = 0;
-  for (uint32_t i = 0; i < n_segs; i++) {
-    total += sr[i].depth_len >> 16;
-    if (!(sr[i].flags & G2S_SUB_SOURCE)) {
-      int np = ((sr[i].par01 & 0xFFFFu) != 0xFFFFu) + ((sr[i].par01 >> 16) != 0xFFFFu) + ((sr[i].par23 & 0xFFFFu) != 0xFFFFu) +
-               ((sr[i].par23 >> 16) != 0xFFFFu);
-      if (np > 1) nx += (size_t)np - 1;
-    }
-  }
-  if (total != n_records || nx != n_xp) return fail(G2S_ERR_ARG, "g2s_test_seg_expand: output sizes do not match the segments");
-  seg_expand(fp, j, go, sr, n_segs, (SubRec*)records, xp);
-  return G2S_OK;
-}
-
-extern "C" int g2s_test_graph_tables(const g2s_graph* gh, uint32_t* succ_out, uint64_t* ustart_out) {
-  if (!gh || !gh->g) return fail(G2S_ERR_ARG, "g2s_test_graph_tables: bad argument");
-  const Graph& g = *gh->g;
-  if (succ_out) memcpy(succ_out, g.succ.data(), (size_t)g.n * 8 * sizeof(uint32_t));
-  if (ustart_out) memcpy(ustart_out, g.ustart.data(), (size_t)((g.n + 63) / 64) * 8);
-  return G2S_OK;
-}
-
-extern "C" int64_t g2s_graph_validate(const g2s_graph* gr, char* msg, size_t msg_cap) {
-  if (!gr || !gr->g) return -1;
-  const Graph& g = *gr->g;
-  std::string text;
-  int64_t bad = 0;
-  auto note = [&](const char* what, uint64_t i) {
-    if (bad++ < 8) text += std::string(what) + " at k-mer " + std::to_string(i) + "; ";
-  };
-  auto only = [&](uint32_t v, uint32_t want) {  // the single valid successor of v is `want`
-    int cnt = 0;
-    bool hit = false;
-    for (int nt = 0; nt < 4; nt++) {
-      const uint32_t w = g.succ_of(v, nt);
-      if (w == kInvalidNode) continue;
-      cnt++;
-      hit = hit || w == want;
-    }
-    return cnt == 1 && hit;
-  };
-  uint64_t starts = 0;
-  for (uint64_t i = 0; i < g.n; i++) {
-    const bool start = (g.ustart[i >> 6] >> (i & 63)) & 1;
-    starts += start;
-    if (i == 0) { if (!start) note("first k-mer is not a unitig start", i); continue; }
-    if (start) continue;
-    const uint32_t a = (uint32_t)(2 * (i - 1)), b = (uint32_t)(2 * i);
-    if (!only(a, b)) note("internal edge is not the only successor (even orientation)", i);
-    if (!only(b ^ 1u, a ^ 1u)) note("internal edge is not the only successor (odd orientation)", i);
-  }
-  if (starts != g.n_unitigs) note("bitmap population differs from the unitig count", starts);
-  if (!g.set_lo.empty()) {  // set graphs: the sets' ranges tile the nodes, no edge leaves its set
-    if (g.set_lo.front() != 0 || g.set_lo.back() != g.n) note("set ranges do not cover the k-mers", g.n);
-    for (size_t s = 0; s + 1 < g.set_lo.size(); s++) {
-      if (g.set_lo[s] > g.set_lo[s + 1]) { note("set ranges not ascending", g.set_lo[s]); continue; }
-      for (uint64_t i = g.set_lo[s]; i < g.set_lo[s + 1]; i++)
-        for (uint32_t v = (uint32_t)(2 * i); v <= (uint32_t)(2 * i + 1); v++)
-          for (int nt = 0; nt < 4; nt++) {
-            const uint32_t w = g.succ_of(v, nt);
-            if (w != kInvalidNode && ((w >> 1) < g.set_lo[s] || (w >> 1) >= g.set_lo[s + 1])) note("successor outside its set", i);
-          }
-    }
-  }
-  for (uint64_t v = 0; v < 2 * g.n; v++)
-    for (int nt = 0; nt < 4; nt++) {
-      const uint32_t w = g.succ_of((uint32_t)v, nt);
-      if (w == kInvalidNode) continue;
-      if (w >= 2 * g.n) { note("successor out of range", v >> 1); continue; }
-      if (g.lastnt[w] != nt) note("last base of a successor differs from its slot", v >> 1);
-    }
-  if (msg && msg_cap) {
-    const size_t c = std::min(text.size(), msg_cap - 1);
-    memcpy(msg, text.data(), c);
-    msg[c] = 0;
-  }
-  return bad;
-}
-
 extern "C" int g2s_test_worker_pool(int32_t threads, int32_t rounds, int32_t n) {
   if (threads < 1 || rounds < 0 || n < 0) return fail(G2S_ERR_ARG, "g2s_test_worker_pool: bad argument");
   WorkerPool pool(threads - 1);
@@ -5785,81 +4746,3 @@ extern "C" int g2s_test_group_queue_slow(int32_t nworkers, uint64_t n, uint64_t 
   return G2S_OK;
 }
 
-extern "C" int g2s_test_device_rand(int device, uint32_t seed, uint64_t skip, uint32_t n, int32_t* out) {
-  if (!out) return fail(G2S_ERR_ARG, "g2s_test_device_rand: bad argument");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return fail(G2S_ERR_NO_DEVICE, "no such device");
-  HIP_TRY(hipSetDevice(device));
-  GlibcRandStream st;
-  st.seed(seed);
-  for (uint64_t left = skip; left;) {  // the host's generator up to the position, as a session would have consumed it
-    const size_t c = (size_t)std::min<uint64_t>(left, 1u << 20);
-    st.ensure(c);
-    st.consume(c);
-    left -= c;
-  }
-  std::vector<uint32_t> tables((128 + 256 + 64) * 31);
-  rand_tables_host(tables.data(), tables.data() + 128 * 31, tables.data() + (128 + 256) * 31);
-  const uint64_t cap = ((uint64_t)n + 2 * G2S_RAND_BLOCK) & ~(uint64_t)(G2S_RAND_BLOCK - 1);
-  uint32_t *d_tab = nullptr, *d_rnd = nullptr;
-  D3Summary* d_sum = nullptr;
-  HIP_TRY(hipMalloc((void**)&d_tab, tables.size() * 4));
-  HIP_TRY(hipMalloc((void**)&d_rnd, (31 + cap + 64) * 4));
-  HIP_TRY(hipMalloc((void**)&d_sum, sizeof(D3Summary)));
-  D3Summary sum;
-  memset(&sum, 0, sizeof sum);
-  sum.draws_min = n;
-  HIP_TRY(hipMemcpy(d_tab, tables.data(), tables.size() * 4, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_sum, &sum, sizeof sum, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_rnd, st.window(G2S_RAND_WINDOW), G2S_RAND_WINDOW * 4, hipMemcpyHostToDevice));
-  RandTables rt;
-  rt.hi = d_tab; rt.mid = d_tab + 128 * 31; rt.lane = d_tab + (128 + 256) * 31;
-  HIP_TRY(launch_rand_fill(nullptr, d_rnd, rt, d_sum, cap));
-  HIP_TRY(hipDeviceSynchronize());
-  std::vector<uint32_t> h(n);
-  HIP_TRY(hipMemcpy(h.data(), d_rnd + 31, (size_t)n * 4, hipMemcpyDeviceToHost));
-  for (uint32_t i = 0; i < n; i++) out[i] = (int32_t)(h[i] >> 1);
-  (void)hipFree(d_tab); (void)hipFree(d_rnd); (void)hipFree(d_sum);
-  return G2S_OK;
-}
-
-// TEST HOOK: g2s_d3_tables_waves for one gap of the caller's design (d3_device.h: test_d3_tables)
-extern "C" int g2s_test_d3_tables(int device, const uint32_t* segs, uint32_t n_segs, int32_t n_len, int32_t len0, int32_t len1,
-                                  uint32_t start_seg, const uint32_t* rnd, uint64_t rnd_cap, uint32_t base, uint32_t R, uint32_t dmin,
-                                  uint32_t dspread, uint16_t* entries, uint8_t* bad, uint32_t* anomalies) {
-  if ((!segs && n_segs) || (!rnd && rnd_cap) || !entries || !bad || !anomalies || n_segs > 0xFFFFu || n_len < 1 || n_len > 2 ||
-      (uint64_t)R + 1u > (uint64_t)G2S_D3_TABLE_BUDGET)
-    return fail(G2S_ERR_ARG, "g2s_test_d3_tables: bad argument");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return fail(G2S_ERR_NO_DEVICE, "no such device");
-  HIP_TRY(hipSetDevice(device));
-  HIP_TRY(test_d3_tables(segs, n_segs, n_len, len0, len1, start_seg, rnd, rnd_cap, base, R, dmin, dspread, entries, bad, anomalies));
-  return G2S_OK;
-}
-
-// TEST HOOK: lists of this process that took phase D3's short route (d3_device.h: d3_chain_launches)
-extern "C" uint64_t g2s_test_d3_chain_launches(void) { return d3_chain_launches(); }
-
-// TEST HOOK: the n values behind `skip` values that were drawn elsewhere — GlibcRandStream::skip, the jump by the
-// recurrence's polynomial g2s_share_end moves a rank's generator with — for comparison with g2s_test_rand_stream
-extern "C" int g2s_test_rand_skip(uint32_t seed, uint64_t skip, uint32_t n, int32_t* out) {
-  if (!out) return fail(G2S_ERR_ARG, "g2s_test_rand_skip: bad argument");
-  GlibcRandStream st;
-  st.seed(seed);
-  st.skip(skip);
-  st.ensure(n);
-  for (uint32_t i = 0; i < n; i++) out[i] = st.value(i);
-  return G2S_OK;
-}
-extern "C" int g2s_test_rand_stream(uint32_t seed, uint32_t skip, uint32_t n, int32_t* out) {
-  if (!out) return fail(G2S_ERR_ARG, "g2s_test_rand_stream: bad argument");
-  GlibcRandStream st;
-  st.seed(seed);
-  // consume in two pieces so that the compaction path is exercised too
-  st.ensure(skip / 2 + 1);
-  st.consume(skip / 2);
-  st.ensure(skip - skip / 2 + n);
-  st.consume(skip - skip / 2);
-  for (uint32_t i = 0; i < n; i++) out[i] = st.value(i);
-  return G2S_OK;
-}

@@ -33,6 +33,26 @@ def test_abi_exports_every_declared_symbol(product):
     assert so.g2s_abi_version() == 6
 
 
+def test_last_error_is_one_text_for_every_unit_of_the_abi(product):
+    """The ABI is implemented by several units of gap2seq_amd/csrc; the calling thread's error text exists once, so a
+    failure raised in any of them (the unit is named in front of its call) is what g2s_last_error() returns.  The
+    entry points of teams and of lists in flight are listed by name: they keep their line when they get units."""
+    lib = product.load_library()
+    failing = [
+        ("g2s_api.hip", "g2s_batch_prepare", lambda: lib.g2s_batch_prepare(None, None, 0, None)),
+        ("g2s_api.hip", "g2s_batch_run", lambda: lib.g2s_batch_run(None, None, None, 0)),
+        ("api_graph.hip", "g2s_graph_build_seqs", lambda: lib.g2s_graph_build_seqs(None, None, 0, 11, 1, 0, None)),
+        ("api_graph.hip", "g2s_test_plan_passes", lambda: lib.g2s_test_plan_passes(None, 0, 1, None, 0, None, None)),
+        ("g2s_api.hip", "g2s_team_fill", lambda: lib.g2s_team_fill(None, 0, None, 0, 0, None, None, 0, None)),
+        ("g2s_api.hip", "g2s_fill_begin", lambda: lib.g2s_fill_begin(None, None, 0, None, None, 0)),
+        ("g2s_api.hip", "g2s_test_worker_pool", lambda: lib.g2s_test_worker_pool(0, 0, 0)),
+        ("api_test_hooks.hip", "g2s_test_rand_stream", lambda: lib.g2s_test_rand_stream(1, 0, 1, None)),
+    ]
+    for unit, name, call in failing:
+        assert call() == -1, (unit, name)  # G2S_ERR_ARG
+        assert lib.g2s_last_error().decode() == name + ": bad argument", (unit, name)
+
+
 def test_product_never_touches_the_oracle():
     pkg = os.path.join(ROOT, "gap2seq_amd")
     for d, _, files in os.walk(pkg):
