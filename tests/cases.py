@@ -115,7 +115,7 @@ def clean_haplotypes(seqs, k):
     return True
 
 
-def bubble_ladder(seed, k, m, spacing, indel=False, lead=0, tail=0, out_tips=(), in_tips=(), fuz=3):
+def bubble_ladder(seed, k, m, spacing, indel=False, lead=0, tail=0, out_tips=(), in_tips=(), fuz=3, indel_every=3):
     """A chain of m bubbles between two flanks, with tips added on demand.  Returns dict(seqs, gap, bubbles, paths):
     seqs[0] is the random backbone, seqs[1] a second haplotype with m substitutions `spacing` (>= k + 1) bases apart,
     the first `lead` bases after the left flank's last k-mer and the last `tail` bases in front of the right flank's
@@ -126,7 +126,10 @@ def bubble_ladder(seed, k, m, spacing, indel=False, lead=0, tail=0, out_tips=(),
     one per shared stretch: about 3 segments per bubble, 2^m paths of one length (the count saturates at MAX_PATHS
     from m = 30 on).  With indel=True every third bubble is a deletion on haplotype 2 instead (arms of k and k - 1
     k-mers): later unitigs are entered at two depths, the paths have several lengths, and the closure has k-mers at
-    several depths (the fill kernels leave it to phase D2 on the device or to the host).
+    several depths (the fill kernels leave it to phase D2 on the device or to the host).  indel_every = n makes every
+    n-th bubble the deletion instead: behind d deletions a unitig is entered at d + 1 depths, so the logged segments
+    grow with the square of their number (a substitution ladder logs 3 a bubble and would need D > 32767 to fill the
+    large variant's log at k = 31).
 
     out_tips: backbone offsets (from the left flank's last k-mer) at which a dead end of k + 2 bases branches off
     (a third read that leaves the backbone): in the left half of the gap each cuts one unitig in two and adds the
@@ -144,7 +147,7 @@ def bubble_ladder(seed, k, m, spacing, indel=False, lead=0, tail=0, out_tips=(),
         bubbles = []
         for b in range(m):
             p = fl + lead + b * spacing
-            if indel and b % 3 == 2:
+            if indel and b % indel_every == indel_every - 1:
                 h[p] = ""
             else:
                 h[p] = "ACGT"[("ACGT".index(h[p]) + 1 + rng.randint(0, 2)) % 4]
@@ -216,6 +219,188 @@ def edge_ladder_list(names, pad=0):
     seqs, gaps, idx = [], [], []
     for name in names:
         lad, _ = edge_ladder(name)
+        seqs += lad["seqs"]
+        gaps.append(lad["gap"])
+    if pad:
+        genome = random_dna(SplitMix(909), 30000)
+        seqs.append(genome)
+        planted, gaps = gaps, cut_gaps(31, genome, 31, fuz=3, ngaps=pad, min_len=20, max_len=300, d_err=10, vary_fuz=False)
+        for j, g in enumerate(planted):
+            idx.append(min(len(gaps), 3 + 4 * j))
+            gaps.insert(idx[-1], g)
+    else:
+        idx = list(range(len(gaps)))
+    return seqs, gaps, idx
+
+
+def fan_paths(widths):
+    """The leaves of a tree of free bases with widths[j] nodes at level j + 1, as strings over ACGT: child c of a level
+    hangs from node c mod (nodes above) and takes the base c div (nodes above), so every node has two to four children
+    (a node with one child would be no branch: the unitig would go on) and widths sets each level to the unit."""
+    level = [""]
+    for w in widths:
+        assert 2 * len(level) <= w <= 4 * len(level), widths
+        level = [level[c % len(level)] + "ACGT"[c // len(level)] for c in range(w)]
+    return level
+
+
+def _numbered_along(read, k, n):
+    """Does the k-mer index grow along `read` over its first n k-mers, taken as one unitig?  The graph numbers a unitig
+    in the direction in which its smallest canonical k-mer (bases ordered A, C, T, G) reads canonically (dbg.cpp,
+    unitig_order)."""
+    order = str.maketrans("ACGT", "0132")
+    comp = str.maketrans("ACGT", "TGCA")
+    best = None
+    for i in range(n):
+        x = read[i:i + k]
+        f, r = x.translate(order), x.translate(comp)[::-1].translate(order)
+        c = (min(f, r), f <= r)
+        if best is None or c < best:
+            best = c
+    return best[1]
+
+
+def fan_trees(seed, k, out=(), inn=(), link=1, lead=20, mid=40, tail=20, leaf_out=8, leaf_in=100, merge=False, fuz=3,
+              aligned=False):
+    """One gap whose left flank opens into a fan-out tree and whose right flank is reached through a fan-in tree.
+    Returns dict(seqs, gap) as bubble_ladder does; seqs[0] is the backbone, the one read from flank to flank.
+
+    out: the fan-out trees, a list of (spacer, widths).  Behind the left flank and `lead` shared bases the reads differ
+    in consecutive free bases (fan_paths(widths)): the k-mers that end on the j-th free base are the widths[j - 1]
+    events of one round of phase B, each a unitig of one k-mer, so widths[-1] events are pending behind the last
+    level.  With several trees the root has one child per tree (one more free base), and tree t begins behind `spacer`
+    bases of its own: a longer spacer puts the subtree deeper, where its events wait while the others run.  A leaf
+    ends after leaf_out more bases (a dead end) unless it is linked.  merge: two more reads leave node 0 of the last
+    level but two one level early, differ in that one base and share what follows: two arms of k k-mers, final in
+    the same round as the last level's parents, whose one child is proposed twice in that round (a merge).
+    inn: the widths of the fan-in tree, the mirror image in front of the right flank and `tail` shared bases: a leaf
+    is a read of leaf_in bases that joins through its free bases.  Phase A enters every leaf; where leaf_in is longer
+    than what right_half still reaches it stops inside, so that the right set's intervals keep holes between them.
+    aligned: every leaf of `inn` is drawn again until its unitig is numbered along the read.  Phase A covers the end
+    of a leaf; of two leaves numbered one after the other in opposite directions the covered ends can touch and their
+    intervals merge (a quarter of all pairs): with every leaf numbered the same way M stays near the number of leaves,
+    which M = 4097 needs to fit below G2S_SEGX_EA entries (an entry per leaf and one per node of the tree).
+    link: leaves 0 .. link - 1 of out[0] run on, through `mid` bases of their own, into the same leaves of `inn` (the
+    backbone is leaf 0; without a tree on a side the backbone simply has no free bases there)."""
+    rng = SplitMix(seed * 6151 + 211)
+    fl = k + fuz
+    opaths = [(t, p) for t, (_, widths) in enumerate(out) for p in fan_paths(widths)] or [(0, "")]
+    ipaths = fan_paths(inn) if inn else [""]
+    n0 = len(fan_paths(out[0][1])) if out else 1
+    assert 1 <= link <= min(n0, len(ipaths))
+    for _ in range(1000):
+        pre, post = random_dna(rng, fl + lead), random_dna(rng, tail + fl)
+        stems = [("ACGT"[t] if len(out) > 1 else "") + random_dna(rng, sp) for t, (sp, _) in enumerate(out)] or [""]
+        seqs = []
+        for i, (t, p) in enumerate(opaths):
+            head = (pre if i == 0 else pre[1 - k:]) + stems[t] + p
+            if i < link:
+                seqs.append(head + random_dna(rng, mid) + ipaths[i][::-1] + (post if i == 0 else post[:k - 1]))
+            else:
+                seqs.append(head + random_dna(rng, leaf_out))
+        for p in ipaths[link:]:
+            while True:
+                seqs.append(random_dna(rng, leaf_in) + p[::-1] + post[:k - 1])
+                if not aligned or _numbered_along(seqs[-1], k, leaf_in):
+                    break
+                seqs.pop()
+        if merge:
+            widths = out[0][1]
+            assert len(out) == 1 and len(widths) >= 3 and widths[-2] <= 2 * widths[-3]
+            arm = random_dna(rng, k + leaf_out)
+            stem = pre[1 - k:] + stems[0] + fan_paths(widths[:-2])[0]
+            seqs += [stem + "G" + arm, stem + "T" + arm]
+        if clean_haplotypes(seqs, k):
+            break
+    else:
+        raise RuntimeError("fan_trees: no clean seed")
+    g = seqs[0]
+    true_len = len(g) - 2 * fl
+    gap = dict(left=g[:fl], right=g[len(g) - fl:], gap_len=true_len + k, lmf=fuz, rmf=fuz, true_len=true_len)
+    return dict(seqs=seqs, gap=gap)
+
+
+# Planted gaps at the limits behind EDGE_LADDERS that bubble ladders do not reach (k = 31, d_err 10), a graph of its own
+# each.  Each entry: the generator ("fan": fan_trees, "ladder": bubble_ladder), its arguments and what the gap gives by
+# the model (tests/seg_model.py): `nseg`, `nA`, `ncl`, `count` as in EDGE_LADDERS; `ev`: the most events pending behind
+# a round (g2s_fill_seg / g2s_fill_seg2 hold 64: WHY_FRONTIER from 65 on); `ring`: the most, over the rounds, of events
+# pending at the round's start plus children proposed in it (g2s_fill_segw's ring hands out G2S_SEGX_PE = 1024 slots a
+# round: WHY_FRONTIER from 1025 on); `gen`: the rounds of phase B (the dump's roundsB); where given, `merges`: children
+# of the fullest round that met their event pending, `sweeps`: rebuilds of the large variant's event table with events
+# live, `M`: merged intervals of the right set.  tests/test_seg_model.py proves every value and the model's equality
+# with the oracle; tests/test_gpu_segw_edges.py checks that the kernels count and route the same.
+_F = dict(k=31, lead=20, tail=200)
+FRONTIER_EDGES = {
+    # the regular tier's 64 lanes: 63 / 64 / 65 events behind the round of the tree's last level
+    "ev63": ("fan", dict(_F, seed=301, out=[(0, (4, 16, 63))]), dict(nseg=85, nA=4, ncl=4, count=1, ev=63, ring=79, gen=5)),
+    "ev64": ("fan", dict(_F, seed=302, out=[(0, (4, 16, 64))]), dict(nseg=86, nA=4, ncl=4, count=1, ev=64, ring=80, gen=5)),
+    "ev65": ("fan", dict(_F, seed=303, out=[(0, (4, 8, 17, 65))]),
+             dict(nseg=96, nA=4, ncl=5, count=1, ev=65, ring=82, gen=6)),
+    # 63 new events and the arms' child, proposed twice: 64 pending and a 65th child that merges
+    "ev64merge": ("fan", dict(_F, seed=304, out=[(0, (4, 8, 16, 63))], merge=True),
+                  dict(nseg=96, nA=4, ncl=5, count=1, ev=64, ring=83, gen=7, merges=1)),
+    # 64 leaves that all reach the right flank, the last level's children at depth prune_from exactly: the round
+    # that fills the lanes is the first to need the right set (two waves: the round that starts again)
+    "ev64straddle": ("fan", dict(k=31, seed=305, out=[(0, (4, 16, 64))], inn=(4, 16, 64), link=64, mid=40, tail=10, lead=91),
+                     dict(nseg=107, nA=109, ncl=106, count=64, ev=64, ring=128, gen=8, straddle=True)),
+    # the large variant's ring: 256 events pending and 768 / 769 children; once with a subtree of 855 events run
+    # and dead before (one sweep of the event table, four events live)
+    "ring1024": ("fan", dict(_F, seed=306, out=[(0, (4, 16, 64, 256, 768))]),
+                 dict(nseg=1110, nA=4, ncl=6, count=1, ev=768, ring=1024, gen=7, sweeps=0)),
+    "ring1025": ("fan", dict(_F, seed=307, out=[(0, (4, 16, 64, 256, 769))]),
+                 dict(nseg=1111, nA=4, ncl=6, count=1, ev=769, ring=1025, gen=7)),
+    "ring1024sweep": ("fan", dict(_F, seed=308, out=[(30, (4, 16, 64, 256, 768)), (0, (4, 16, 64, 256, 512))]),
+                      dict(nseg=1964, nA=4, ncl=7, count=1, ev=768, ring=1024, gen=13, sweeps=1)),
+}
+_LOG = dict(k=31, spacing=32, seed=611, indel=True, indel_every=2, lead=200, m=146)
+_RS = dict(k=31, lead=20, tail=10, mid=20, leaf_in=50, seed=621)
+_IV = dict(k=31, lead=70, tail=10, mid=10, leaf_in=80, leaf_out=30, out=[(0, (4, 16, 64))], aligned=True)
+SEGW_EDGES = {
+    # G2S_SEGX_CAP = 16384 logged segments: 146 bubbles, every second a deletion, D = 4888; 31 sweeps of the event table
+    "log16383": ("ladder", dict(_LOG, out_tips=(2424, 1176)),
+                 dict(nseg=16383, nA=238, ncl=5204, ev=81, ring=107, gen=3245, sweeps=31)),
+    "log16384": ("ladder", dict(_LOG, out_tips=(2424, 1176), in_tips=(120,)),
+                 dict(nseg=16384, nA=238, ncl=5205, ev=81, ring=107, gen=3246, sweeps=31)),
+    "log16385": ("ladder", dict(_LOG, out_tips=(2424, 1176, 90)),
+                 dict(nseg=16385, nA=238, ncl=5205, ev=81, ring=107, gen=3246, sweeps=31)),
+    # G2S_SEGX_EA = 6144 right-set entries: a fan-in tree of 4603 / 4604 leaves (and one more node inside)
+    "rs6143": ("fan", dict(_RS, inn=(2, 5, 18, 72, 288, 1151, 4603)), dict(nseg=9, nA=6143, ncl=8, count=1, ev=1, ring=2, gen=9)),
+    "rs6144": ("fan", dict(_RS, inn=(2, 5, 18, 72, 288, 1151, 4604)), dict(nseg=9, nA=6144, ncl=8, count=1, ev=1, ring=2, gen=9)),
+    "rs6145": ("fan", dict(_RS, inn=(2, 5, 18, 72, 288, 1152, 4604)), dict(nseg=9, nA=6145, ncl=8, count=1, ev=1, ring=2, gen=9)),
+    # the levels of the right set's search (iv_rank reads one more when M passes 8, 64, 512, 4096): M depends on the
+    # numbering of the unitigs, so these graphs are built on the host (G2S_HOST_BUILD=1), one graph a gap
+    "iv8": ("fan", dict(_IV, seed=403, inn=(4,), link=2), dict(nseg=9, nA=13, ncl=8, count=2, ev=2, ring=4, gen=6, M=8)),
+    "iv9": ("fan", dict(_IV, seed=421, inn=(4,), link=2), dict(nseg=9, nA=13, ncl=8, count=2, ev=2, ring=4, gen=6, M=9)),
+    "iv64": ("fan", dict(_IV, seed=441, inn=(2, 5, 19, 73), link=16),
+             dict(nseg=62, nA=124, ncl=61, count=16, ev=16, ring=32, gen=9, M=64)),
+    "iv65": ("fan", dict(_IV, seed=461, inn=(2, 5, 20, 77), link=16),
+             dict(nseg=62, nA=129, ncl=61, count=16, ev=16, ring=32, gen=9, M=65)),
+    "iv512": ("fan", dict(_IV, seed=481, inn=(3, 9, 34, 134, 536), link=32),
+              dict(nseg=131, nA=741, ncl=130, count=32, ev=32, ring=64, gen=10, M=512)),
+    "iv513": ("fan", dict(_IV, seed=501, inn=(3, 9, 34, 134, 534), link=32),
+              dict(nseg=131, nA=739, ncl=130, count=32, ev=32, ring=64, gen=10, M=513)),
+    "iv4096": ("fan", dict(_IV, seed=560, inn=(2, 5, 17, 65, 258, 1031, 4123), link=32),
+               dict(nseg=175, nA=5526, ncl=174, count=32, ev=32, ring=64, gen=12, M=4096)),
+    "iv4097": ("fan", dict(_IV, seed=580, inn=(2, 5, 17, 65, 258, 1032, 4128), link=32),
+               dict(nseg=175, nA=5532, ncl=174, count=32, ev=32, ring=64, gen=12, M=4097)),
+}
+LIMIT_EDGES = dict(FRONTIER_EDGES, **SEGW_EDGES)
+_limit_cache = {}
+
+
+def limit_edge(name):
+    """(dict(seqs, gap), want) of one row of FRONTIER_EDGES / SEGW_EDGES; built once a process."""
+    if name not in _limit_cache:
+        how, kw, _ = LIMIT_EDGES[name]
+        _limit_cache[name] = bubble_ladder(**kw) if how == "ladder" else fan_trees(**kw)
+    return _limit_cache[name], LIMIT_EDGES[name][2]
+
+
+def limit_edge_list(names, pad=0):
+    """edge_ladder_list for rows of FRONTIER_EDGES / SEGW_EDGES: (haplotypes, gaps, index of each planted gap)."""
+    seqs, gaps, idx = [], [], []
+    for name in names:
+        lad, _ = limit_edge(name)
         seqs += lad["seqs"]
         gaps.append(lad["gap"])
     if pad:

@@ -30,6 +30,8 @@ What it models (phases of /root/reference/src/Gap2Seq.cpp:858-1312, SURVEY.md Ap
             closure is expanded into the 16-byte per-state records the host part of phase D
             takes, children before parents.
 """
+import bisect
+
 import numpy as np
 
 INVALID = 0xFFFFFFFF
@@ -129,7 +131,8 @@ def fill_model(tb, gap, rs=None, stats=None):
     by_kmer = {}  # (k-mer, depth) -> node of the first event there
 
     def add_event(node, depth, count, parent, fixed=False):
-        nonlocal q7
+        nonlocal q7, proposals
+        proposals += 1
         key = (node, depth)
         ev = events.get(key)
         if ev is None:
@@ -146,6 +149,7 @@ def fill_model(tb, gap, rs=None, stats=None):
 
     segs = []     # [v0, d0, count, length, parents, generation]
     gen = 0
+    proposals = 0  # calls of add_event in the running round, merges included
     s0 = gap.lseeds[0]
     chain = (lmf >= 1 and s0 != INVALID and all(gap.lseeds[d] == seg_node(s0, d) for d in range(lmf + 1))
              and int(tb.rem[s0]) >= lmf
@@ -163,8 +167,41 @@ def fill_model(tb, gap, rs=None, stats=None):
                 add_event(gap.lseeds[d], d, 0, None, fixed=True)
     rounds = 0
     max_pending = max_batch = 0
+    run_lo, run_hi = [], []  # the right set as maximal runs of consecutive k-mer indices
+    for x in sorted(rs):
+        if run_hi and x == run_hi[-1] + 1:
+            run_hi[-1] = x
+        else:
+            run_lo.append(x)
+            run_hi.append(x)
+    # The kernels' own limits on pending events, restated (see Result's fields below).
+    # g2s_fill_seg / g2s_fill_seg2 (fill_seg.hip, add_event): an event is a lane of 64.  A round clears the lanes of
+    # its batch (`ev &= ~sel`) before any child arrives, a child that meets its (node, depth) pending merges without
+    # a lane, any other takes the lowest free one: the round overflows iff (pending - batch) + distinct new events
+    # > 64, whatever the order of the children, i.e. iff more than 64 events are pending behind some round.  That is
+    # max_pending (the seeds are at most lmf + 1 <= 32 lanes).
+    # g2s_fill_segw (fill_segw.hip, ev_insert): an event is one of PE = 1024 slots handed out by a ring.  Every child
+    # that passes the pruning rule pops a slot BEFORE the table tells whether it merges, and pops take only what lay
+    # in the ring when the round began (tail_snap): the slots of the round's own batch and of its merged children
+    # are pushed behind that mark.  The ring holds PE - pending slots then, so the round overflows iff
+    # pending at its start + proposals of the round (new and merging alike) > PE.  The seeds pop from a full ring.
+    # Dead entries: a batch's entries stay in the event table; at the head of a round, with SH_NDEAD > HS / 8 = 512,
+    # the table is built again from the live slots.
+    ring_peak = 0          # max over rounds of pending at the start + proposals
+    ring_round = reg_round = rs_round = -1
+    reg_first = None       # which of its two phase-B limits the regular tier meets first: "log", "frontier" or None
+    merges_at_peak = 0
+    ndead, sweeps, sweep_live = 0, 0, 0
+    queries = []           # (k-mer index, inside) of every search phase B makes in the large variant
     while pending:
+        if len(pending) > max_pending:
+            reg_round = rounds - 1  # the round behind which most events were pending
         max_pending = max(max_pending, len(pending))
+        if ndead > 512:
+            sweeps += 1
+            sweep_live = max(sweep_live, len(pending))
+            ndead = 0
+        n_start, proposals = len(pending), 0
         def steps(key):
             node, depth = key
             return 1 if depth < lmf else int(tb.rem[node]) + 1  # states up to the end of the unitig
@@ -173,44 +210,69 @@ def fill_model(tb, gap, rs=None, stats=None):
         assert batch
         rounds += 1
         max_batch = max(max_batch, len(batch))
+        ndead += len(batch)
+        if reg_first is None and len(segs) + len(batch) > 512:
+            reg_first = "log"       # (fill_seg.hip: nseg + nsel > G2S_SEG_CAP, looked at before the round's children)
+        if rs_round < 0 and any(d + min(steps((n, d)), D - d + 1) >= gap.prune_from for n, d in batch):
+            rs_round = rounds - 1  # (two waves) the first round that needs the right set: it starts again
         for key in batch:
             pending.discard(key)
+        n_keys = len(events)
+        for key in batch:
             node, depth = key
             cnt, fixed, parents = events[key]
             if fixed:
                 cnt, parents = 1, [p for p in parents]
             lcap = min(steps(key), D - depth + 1)
-            length = 1
-            while length < lcap:  # interior states are entered under the pruning rule (:1050)
-                dd = depth + length
-                if dd >= gap.prune_from and (seg_node(node, length) >> 1) not in rs:
-                    break
-                length += 1
+            if lcap > 1 and depth + lcap - 1 >= gap.prune_from and (fixed or depth < gap.prune_from):
+                # (large variant) an event from above the rule's depth looks up its first state under the rule
+                t1 = max(1, gap.prune_from - depth)
+                q0 = seg_node(node, t1) >> 1
+                queries.append((q0, q0 in rs))
+            # interior states are entered under the pruning rule (:1050): the run ends in front of the first state at
+            # or below prune_from whose k-mer is not in the right set.  (Looked up in the set's maximal runs of
+            # consecutive indices, not state by state: a 16 384-segment gap has millions of states.)
+            length = lcap
+            t1 = max(1, gap.prune_from - depth)
+            if t1 < lcap:
+                x = seg_node(node, t1) >> 1
+                r = bisect.bisect_right(run_lo, x) - 1
+                if r < 0 or x > run_hi[r]:
+                    length = t1
+                elif node & 1:
+                    length = min(lcap, (node >> 1) - run_lo[r] + 1)
+                else:
+                    length = min(lcap, run_hi[r] - (node >> 1) + 1)
             sid = len(segs)
             segs.append([node, depth, cnt, length, parents, gen])
             x_depth = depth + length - 1
             if length == lcap and x_depth < D:  # the walk reached the end of its stretch: leave through the table
                 for w in tb.successors(seg_node(node, length - 1)):
+                    if x_depth + 1 >= gap.prune_from:
+                        queries.append((w >> 1, (w >> 1) in rs))
                     if x_depth + 1 < gap.prune_from or (w >> 1) in rs:
                         add_event(w, x_depth + 1, cnt, sid)
+        if n_start + proposals > ring_peak:
+            ring_peak, ring_round = n_start + proposals, rounds - 1
+        if len(pending) > max_pending:
+            merges_at_peak = proposals - (len(events) - n_keys)
+        if reg_first is None and len(pending) > 64:
+            reg_first = "frontier"
         gen += 1
     n_gen = gen
     # ---- Q7 among segments: an upward and a downward segment of one unitig meeting on a k-mer ----
     ups = [s for s in segs if (s[0] & 1) == 0 and s[3] > 0]
     downs = [s for s in segs if (s[0] & 1) == 1 and s[3] > 0]
-    if not q7 and ups and downs:
+    if not q7 and ups and downs:  # (every pair, a row of numpy at a time: the pairs of a full log are 10^8)
+        ib = np.array([b[0] >> 1 for b in downs], dtype=np.int64)
+        db = np.array([b[1] for b in downs], dtype=np.int64)
+        lb = np.array([b[3] for b in downs], dtype=np.int64)
         for a in ups:
             ia, da, la = a[0] >> 1, a[1], a[3]
-            for b in downs:
-                ib, db, lb = b[0] >> 1, b[1], b[3]
-                s_, dl = ib - ia, db - da
-                if (s_ + dl) & 1:
-                    continue
-                t1, t2 = (s_ + dl) // 2, (s_ - dl) // 2
-                if 0 <= t1 < la and 0 <= t2 < lb:
-                    q7 = True
-                    break
-            if q7:
+            s_, dl = ib - ia, db - da
+            t1, t2 = (s_ + dl) >> 1, (s_ - dl) >> 1
+            if np.any((((s_ + dl) & 1) == 0) & (t1 >= 0) & (t1 < la) & (t2 >= 0) & (t2 < lb)):
+                q7 = True
                 break
     # ---- phase C in closed form -----------------------------------------------------------------
     best = None  # (found level, j) -> [c1, c2]
@@ -234,6 +296,12 @@ def fill_model(tb, gap, rs=None, stats=None):
     res.q7 = q7
     res.rounds, res.n_seg, res.n_gen = rounds, len(segs), n_gen
     res.max_pending, res.max_batch = max_pending, max_batch
+    # peak events by each kernel's rule (overflow: max_pending > 64; ring_peak > 1024), the rounds they fall in
+    # (0-based), the first round that needs the right set, merges in the round that left max_pending, the sweeps of
+    # the large variant's event table and the most events live at one, its searches of the right set
+    res.ring_peak, res.ring_round, res.reg_round, res.rs_round = ring_peak, ring_round, reg_round, rs_round
+    res.merges_at_peak, res.sweeps, res.sweep_live, res.queries = merges_at_peak, sweeps, sweep_live, queries
+    res.reg_first = reg_first
     found = best is not None
     res.c_count = min(MAX_PATHS, c12[0] + c12[1]) if found else 0
     res.reached_j = best[1] if found else 0
@@ -384,6 +452,49 @@ def right_entries(tb, gap):
                         nxt.append(p)
         queue = list(dict.fromkeys(nxt))
     return label
+
+
+def merged_intervals(tb, gap, label):
+    """The right set as the kernels keep it: the entries' k-mer index intervals, sorted, overlapping AND adjacent
+    ones merged (seg_device.h, lds_merge_intervals: a hole lies between any two).  [(first, last)], M = its length."""
+    ivs = []
+    for v, d in label.items():
+        steps = min(int(tb.rem[v ^ 1]), gap.right_half - d)
+        a, b = (v ^ 1) >> 1, seg_node(v ^ 1, steps) >> 1
+        ivs.append((min(a, b), max(a, b)))
+    out = []
+    for lo, hi in sorted(ivs):
+        if out and lo <= out[-1][1] + 1:
+            out[-1][1] = max(out[-1][1], hi)
+        else:
+            out.append([lo, hi])
+    return [tuple(x) for x in out]
+
+
+def rank_blocks(firsts, q):
+    """g2s_fill_segw's search (fill_segw.hip, iv_rank) for k-mer index q over the M sorted firsts: the number of
+    intervals that begin at or before q, found by counting, level by level, the samples at or below q in ONE block of
+    eight: level 0 is the firsts themselves (padded), level j + 1 every eighth of level j taken at positions 8 i + 7;
+    the search starts at the first level that fits one block (levels in use: 1 for M <= 8, 2 for M <= 64, 3 for
+    M <= 512, 4 for M <= 4096, 5 above) in block 0 and goes down into block `rank so far`.  Returns (rank, [block read
+    at each level, top first], samples of the top block at or below q).  The rank equals the plain count: asserted
+    here, so that the levels' arithmetic is checked against it."""
+    pad = 0x7FFFFFFF
+    m = len(firsts)
+    levels = [list(firsts)]
+    for size in (784, 112, 32, 16):
+        below = levels[-1]
+        levels.append([below[8 * i + 7] if 8 * i + 7 < len(below) else pad for i in range(size)])
+    use = 1 + sum(m > cap for cap in (8, 64, 512, 4096))
+    blk, blocks, top = 0, [], None
+    for lv in range(use - 1, -1, -1):
+        blocks.append(blk)
+        arr = levels[lv]
+        blk = 8 * blk + sum(1 for x in arr[8 * blk:8 * blk + 8] if x <= q)
+        if top is None:
+            top = blk
+    assert blk == bisect.bisect_right(firsts, q)
+    return blk, blocks, top
 
 
 def entries_to_set(tb, gap, label):

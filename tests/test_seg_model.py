@@ -218,3 +218,104 @@ def test_edge_ladders_share_one_graph():
     seqs, gaps, idx = cases.edge_ladder_list(sorted(cases.EDGE_LADDERS), pad=300)
     assert cases.clean_haplotypes(seqs, 31) and len(gaps) == 300 + len(cases.EDGE_LADDERS)
     assert [gaps[i] for i in idx] == cases.edge_ladder_list(sorted(cases.EDGE_LADDERS))[1]
+
+
+def _limit_facts(product, oracle, name, monkeypatch):
+    """Model, right-set entries, merged intervals and oracle result of one row of cases.LIMIT_EDGES."""
+    lad, want = cases.limit_edge(name)
+    if "M" in want:  # M depends on how the unitigs are numbered: the host build's numbering, on every machine
+        monkeypatch.setenv("G2S_HOST_BUILD", "1")
+    g = lad["gap"]
+    pg = product.Graph.from_seqs(lad["seqs"], 31, 1)
+    og = oracle.OracleGraph(lad["seqs"], 31, 1)
+    try:
+        tb = M.Tables(product, pg)
+        mg = _model_gap(pg, 31, g, 10)
+        label = M.right_entries(tb, mg)
+        rs = M.entries_to_set(tb, mg, label)
+        if len(label) < 1000:
+            assert rs == M.right_set(tb, mg)
+        ivs = M.merged_intervals(tb, mg, label)
+        assert {x for lo, hi in ivs for x in range(lo, hi + 1)} == rs
+        assert all(b[0] > a[1] + 1 for a, b in zip(ivs, ivs[1:]))  # a hole between any two
+        m = M.fill_model(tb, mg, rs)
+        rng = oracle.OracleRng(5)
+        o = oracle.fill_gap(og, rng, g["left"], g["right"], g["gap_len"], 10, g["lmf"], g["rmf"], False, True)
+        rng.free()
+    finally:
+        pg.free()
+        og.free()
+    return m, label, ivs, o, want
+
+
+@pytest.mark.parametrize("name", sorted(cases.LIMIT_EDGES))
+def test_limit_edges_sit_where_the_gpu_tests_say(product, oracle, monkeypatch, name):
+    """Every planted gap of cases.FRONTIER_EDGES and cases.SEGW_EDGES (tests/test_gpu_segw_edges.py) at its limit:
+    logged segments, right-set entries, closure segments, count, the peak of pending events by each kernel's own
+    rule, rounds, and where the table names them merges, sweeps and M are the model's; the model's count and lengths
+    are the oracle's and neither sees Q7."""
+    m, label, ivs, o, want = _limit_facts(product, oracle, name, monkeypatch)
+    assert not m.q7 and not o.info.q7
+    got = dict(nseg=m.n_seg, nA=len(label), ncl=len(m.compact), count=m.c_count, ev=m.max_pending, ring=m.ring_peak,
+               gen=m.n_gen, merges=m.merges_at_peak, sweeps=m.sweeps, M=len(ivs), straddle=m.rs_round == m.reg_round)
+    want = dict(want)
+    want.setdefault("count", cases.MAX_PATHS)
+    assert {key: got[key] for key in want} == want
+    assert m.c_count == o.info.phaseC_count and m.lengths == o.lengths and o.count > 0
+    # the regular tier's first limit in phase B, as tests/test_gpu_segw_edges.py expects it from these numbers
+    assert m.reg_first == ("log" if want["nseg"] > 16000 else "frontier" if want["ev"] > 64 else None)
+    if want.get("sweeps"):
+        assert m.sweep_live >= 1  # the table was rebuilt with events pending in it
+    if "M" in want:
+        # a case tests a level only if its searches reach the ends of the top block: with c = the samples of the top
+        # block at or below the key, c = 0 (the first block below), c = the block's last real sample (8 at M = 8^j,
+        # 1 at M = 8^j + 1: the last block) and, where there is one, a c in between; answers inside and outside
+        firsts = [lo for lo, hi in ivs]
+        tops, answers = set(), set()
+        for q, inside in m.queries:
+            rank, blocks, top = M.rank_blocks(firsts, q)
+            assert inside == (rank > 0 and q <= ivs[rank - 1][1])
+            assert len(blocks) == 1 + sum(want["M"] > cap for cap in (8, 64, 512, 4096))
+            tops.add(top)
+            answers.add(inside)
+        last = 8 if want["M"] in (8, 64, 512, 4096) else 1
+        assert {0, last} <= tops and max(tops) == last and (last == 1 or tops - {0, last}), sorted(tops)
+        assert answers == {True, False}
+
+
+def test_limit_edges_step_by_one_across_each_limit():
+    """The tables hold limit - 1, limit and limit + 1 for the lanes of the regular tier and for every capacity of
+    the large variant that a Q7-free gap can reach (DESIGN section 6 for the two that none can), and the eight values
+    of M around the four level boundaries of the search."""
+    col = lambda table, key: {w[key] for _, _, w in table.values() if key in w}
+    assert {63, 64, 65} <= col(cases.FRONTIER_EDGES, "ev")
+    assert {1024, 1025} <= col(cases.FRONTIER_EDGES, "ring") and max(col(cases.LIMIT_EDGES, "ring")) == 1025
+    assert {16383, 16384, 16385} <= col(cases.SEGW_EDGES, "nseg")
+    assert {6143, 6144, 6145} <= col(cases.SEGW_EDGES, "nA")
+    assert col(cases.SEGW_EDGES, "M") == {8, 9, 64, 65, 512, 513, 4096, 4097}
+    rows = cases.FRONTIER_EDGES
+    assert rows["ev64merge"][2]["merges"] >= 1 and rows["ev64straddle"][2]["straddle"]
+    assert any(w.get("sweeps", 0) >= 1 and w["ring"] == 1024 for _, _, w in rows.values())
+    # every over-by-one row is over ONE limit of its kernel, so that its reason bit is that limit's
+    for name, (_, _, w) in cases.LIMIT_EDGES.items():
+        over = [w["nA"] > 6144, w["nseg"] > 16384, w["ring"] > 1024]
+        assert sum(over) <= 1, name
+
+
+@pytest.mark.parametrize("name", ["ev64merge", "ev64straddle", "ev65", "iv9", "iv65"])
+def test_limit_edges_in_every_mode(product, oracle, monkeypatch, name):
+    """Small rows with -best-only and with the skip rule, the host half of phase D included: the model equals the
+    oracle in every field (DP table, counters, fill, fuz, draws, subgraph statistics)."""
+    lad, want = cases.limit_edge(name)
+    for skip, allp in ((False, True), (False, False), (True, True)):
+        c, q = check_config(product, oracle, lad["seqs"], 31, [lad["gap"]], 10, allp, skip)
+        assert (c, q) == (1, 0)
+
+
+def test_limit_edges_share_one_graph():
+    """tests/test_gpu_segw_edges.py runs the frontier rows as one list on one graph among ordinary gaps, and puts
+    them with the search-level rows into a long resident list: no row's k-mer is another's or the plain genome's."""
+    names = sorted(cases.FRONTIER_EDGES) + sorted(n for n in cases.SEGW_EDGES if n.startswith("iv"))
+    seqs, gaps, idx = cases.limit_edge_list(names, pad=300)
+    assert cases.clean_haplotypes(seqs, 31) and len(gaps) == 300 + len(names)
+    assert [gaps[i] for i in idx] == cases.limit_edge_list(names)[1]
