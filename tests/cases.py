@@ -115,7 +115,8 @@ def clean_haplotypes(seqs, k):
     return True
 
 
-def bubble_ladder(seed, k, m, spacing, indel=False, lead=0, tail=0, out_tips=(), in_tips=(), fuz=3, indel_every=3):
+def bubble_ladder(seed, k, m, spacing, indel=False, lead=0, tail=0, out_tips=(), in_tips=(), fuz=3, indel_every=3,
+                  run=0, run_step=None, del_len=1):
     """A chain of m bubbles between two flanks, with tips added on demand.  Returns dict(seqs, gap, bubbles, paths):
     seqs[0] is the random backbone, seqs[1] a second haplotype with m substitutions `spacing` (>= k + 1) bases apart,
     the first `lead` bases after the left flank's last k-mer and the last `tail` bases in front of the right flank's
@@ -136,11 +137,21 @@ def bubble_ladder(seed, k, m, spacing, indel=False, lead=0, tail=0, out_tips=(),
     tip's own segment: +2 logged segments, no right-set entry.  in_tips: offsets at which a source of k + 2 bases
     joins the backbone (a read that ends on it): the backbone's unitig is cut (+1 logged segment) and the tip is
     one more predecessor for phase A to enter (+1 right-set entry when it lies in the right half).  Seeds whose
-    haplotypes repeat a k-mer anywhere (either strand) are rejected and the next seed of the stream is tried."""
-    assert spacing >= k + 1
+    haplotypes repeat a k-mer anywhere (either strand) are rejected and the next seed of the stream is tried.
+
+    run = J (tests/trace_cases.py): every substitution becomes a row of them, run_step (<= k - 1, default k - 1) bases
+    apart over J bases: the arms do not meet between two of them, so the bubble's arms are J' + k k-mers long (J' the
+    distance from the first to the last substitution) — a run of unsafe states longer than a wave.  del_len = n: a
+    deletion takes n bases (arms of k and k - n k-mers: paths whose lengths differ by n; two lengths are both phase
+    C's only when they differ by an even number, :1125-1126).  lead may be negative (down to 1 - fuz): the first
+    bubble then opens inside the left seeds.  With the defaults the output is what it was without these arguments."""
+    assert spacing >= k + 1 + run and del_len >= 1
     rng = SplitMix(seed * 6151 + 101)
     fl = k + fuz
     n = fl + lead + (m - 1) * spacing + 1 + tail + fl if m else fl + lead + tail + fl
+    n += (run + del_len - 1) if m else 0
+    step = run_step or k - 1
+    assert 1 <= step <= k - 1
     for _ in range(1000):
         g = random_dna(rng, n)
         h = list(g)
@@ -148,9 +159,11 @@ def bubble_ladder(seed, k, m, spacing, indel=False, lead=0, tail=0, out_tips=(),
         for b in range(m):
             p = fl + lead + b * spacing
             if indel and b % indel_every == indel_every - 1:
-                h[p] = ""
+                for q in range(del_len):
+                    h[p + q] = ""
             else:
-                h[p] = "ACGT"[("ACGT".index(h[p]) + 1 + rng.randint(0, 2)) % 4]
+                for q in range(0, run + 1, step):
+                    h[p + q] = "ACGT"[("ACGT".index(h[p + q]) + 1 + rng.randint(0, 2)) % 4]
             bubbles.append(p)
         seqs = [g, "".join(h)] if m else [g]
         for t in out_tips:  # the backbone up to offset t, then a fresh k + 2 bases: a dead end behind fl + t

@@ -21,6 +21,11 @@ if "designs" in what:
     import d2_cases
     seqs, gaps, idx, _ = d2_cases.design_list(what["designs"], pad=100)
     d_err = what["designs"]
+elif "trace" in what:  # (tests/trace_cases.py: the first copy of every planted gap of one list)
+    import trace_cases
+    seqs, gaps, idx = trace_cases.trace_list(what["trace"])
+    idx = [v[0] for v in idx.values()]
+    d_err = what["d_err"]
 else:
     seqs, gaps, idx = cases.edge_ladder_list(what["ladders"], pad=100)
     d_err = 10
